@@ -4,6 +4,10 @@
 Contract (driver): python bench.py --gpus N --steps K --warmup W ; for N > 1 it is launched by
 torch.distributed.run with one rank per GPU.  A step = one frame pair for each of the --seqs
 sequences resident on a GPU (inputs already in HBM).  Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the line.  --full adds the extra
+legs after the timed region (CPU-oracle baseline, OpenCV probe, float-sums mode, ATE long run).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -87,6 +91,23 @@ def opencv_probe(seq, cal, over, ping_pong, frames):
         return "present but tools/opencv_baseline.cpp did not build or run: %r (probed: %s)" % (e, ", ".join(probed))
 
 
+def render_sequence(kw):
+    """One pool sequence (runs in a spawned worker process: numpy only, never the GPU)."""
+    from stereo_visual_odometry_amd import synthetic as syn
+    return syn.StereoSequence(**kw)
+
+
+def render_pool(kws, workers):
+    """The pool's sequences rendered in parallel by fresh (spawned) processes: each is seeded on its own, so the frames are
+    the same bytes as a serial render."""
+    if workers <= 1 or len(kws) <= 1:
+        return [render_sequence(kw) for kw in kws]
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(max_workers=min(workers, len(kws)), mp_context=multiprocessing.get_context("spawn")) as ex:
+        return list(ex.map(render_sequence, kws))
+
+
 def level_sizes(W, H, win, max_level):
     out = []
     w, h = W, H
@@ -122,14 +143,18 @@ def main():
     ap.add_argument("--movers", type=float, default=None, help="fraction of the pixels covered by an independently moving foreground layer "
                     "(RANSAC-PnP outliers; 0 = static scene, the best case for PnP).  Default: 0.3 for cfg2 (the metric's workload), 0 for the others")
     ap.add_argument("--frames", type=int, default=10, help="frames rendered per pool sequence (ping-pong replay)")
-    ap.add_argument("--cpu-frames", type=int, default=120, help="frames of the CPU-oracle baseline sample (0 = skip)")
-    ap.add_argument("--ate-frames", type=int, default=40, help="frame transitions of the ATE leg: one freshly rendered sequence (not a ping-pong "
+    ap.add_argument("--full", action="store_true", help="also run the extra legs after the timed region: the CPU-oracle baseline (--cpu-frames), "
+                    "the float-sums leg (--float-sums-steps) and the ATE long run (--ate-frames).  Off by default: a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned to its "
+                    "caller (rank 0's sequences) as DIR/<name>.npy: pose (seqs, 4, 4) f64, pose_ok (seqs,) f32, frame_stats (seqs, 14) f64")
+    ap.add_argument("--cpu-frames", type=int, default=120, help="with --full: frames of the CPU-oracle baseline sample (0 = skip)")
+    ap.add_argument("--ate-frames", type=int, default=40, help="with --full: frame transitions of the ATE leg: one freshly rendered sequence (not a ping-pong "
                     "replay) through a one-sequence context and through the CPU oracle, outside the timed region (0 = only the timed steps of slot 0)")
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg3", "cfg5"],
                     help="BASELINE.json configs[1] (the metric's configuration, default) / configs[2] / configs[4]; the others are extra measurements")
     ap.add_argument("--float-sums", type=int, default=0, help="1 = svo_config.lk_float_sums (LK sums in float in OpenCV's SIMD128 lane order: the mode that "
                     "reproduces the reference's recording digit for digit; several times slower in LK).  An extra measurement, not the bench line")
-    ap.add_argument("--float-sums-steps", type=int, default=10, help="steps of the extra leg that re-times the SAME workload with lk_float_sums = 1 (the mode whose "
+    ap.add_argument("--float-sums-steps", type=int, default=10, help="with --full: steps of the extra leg that re-times the SAME workload with lk_float_sums = 1 (the mode whose "
                     "output is the reference's own rounding) on rank 0 after the timed region -> float_sums_mode in the line; skipped when 0, when the line itself "
                     "is a float-sums run, and when --cpu-frames is 0 (the profiling runs: their counter passes must only see the default kernels)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse on one GPU)")
@@ -202,8 +227,8 @@ def main():
         over["lk_float_sums"] = 1
     B, F = args.seqs, args.frames
     seed0 = scene.pop("seed")
-    pool = [syn.StereoSequence(cal=cal, n_frames=F, seed=seed0 + 97 * rank + g, movers=args.movers, **scene)
-            for g in range(args.pool)]
+    pool = render_pool([dict(cal=cal, n_frames=F, seed=seed0 + 97 * rank + g, movers=args.movers, **scene) for g in range(args.pool)],
+                       max(1, host_cores() // world))
     left = torch.stack([torch.from_numpy(np.stack(s.left)) for s in pool]).to(dev)      # (G, F, H, W) u8, resident in HBM
     right = torch.stack([torch.from_numpy(np.stack(s.right)) for s in pool]).to(dev)
     frame_bytes = W * H
@@ -276,6 +301,7 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     run(args.warmup + 1, args.steps, True)
+    last_stats = [[list(st.as_dict().values()) for st in vo.stats] for vo in vos]     # the last timed step's counters, per context
     if grouped:                                              # the path's only exchange: pose streams -> rank 0 (RCCL over xGMI)
         gathered = sharding.gather_pose_streams(torch.from_numpy(poses).to(comm_dev), dst=0)
     torch.cuda.synchronize()
@@ -308,6 +334,12 @@ def main():
             assert np.array_equal(gathered[0].cpu().numpy(), poses)
         dist.barrier()
         dist.destroy_process_group()                          # everything below is rank 0's own work (CPU baseline, ATE): no rank waits for it
+
+    if rank == 0 and args.dump_outputs:                       # what the caller of the timed path received in its last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pose.npy"), poses[:, -1, :16].reshape(B, 4, 4).astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "pose_ok.npy"), poses[:, -1, 16].astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "frame_stats.npy"), np.array(sum(last_stats, []), dtype=np.float64).reshape(B, -1))
 
     if rank == 0:
         N = float(np.mean(n_lk))
@@ -350,7 +382,7 @@ def main():
                      "peak_TFLOPs": 157.3, "frac_at_job_rate": lk_flops * value / world / 157.3e12,
                      "frac_in_kernel": lk_flops * Bc / (lk_avg_ms * 1e-3) / 157.3e12}
         cpu = None
-        if args.cpu_frames > 0:                               # rank 0, any N: the timed region and the last barrier are behind us
+        if args.full and args.cpu_frames > 0:                 # rank 0, any N: the timed region and the last barrier are behind us
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             # the CPU number is taken with -O3 -march=native, so that build is made HERE, on the machine that
             # times it (never shipped: a -march=native object from another host may not even run); same IEEE-strict flags
@@ -389,7 +421,7 @@ def main():
         # sums in float in OpenCV's SIMD128 lane order) — an extra figure next to `value`, never `value`: rank 0,
         # its own GPU, fresh contexts, same sequences / contexts / frames in flight, after everything timed above
         fs_leg = None
-        if args.float_sums_steps > 0 and args.cpu_frames > 0 and not args.float_sums:
+        if args.full and args.float_sums_steps > 0 and args.cpu_frames > 0 and not args.float_sums:
             for v in vos:
                 v.close()
             fvos = []
@@ -439,7 +471,7 @@ def main():
             if common:
                 ate["vs_cpu_oracle_m"] = syn.ate_rmse(syn.integrate([est[c] for c in common]), syn.integrate([cpu_T[first + c] for c in common]))
                 ate["oracle_frames"] = len(common)
-        if args.ate_frames > 0:
+        if args.full and args.ate_frames > 0:
             # the metric's "ATE vs ref" on a real path: one freshly rendered sequence of ate_frames + 1 frames (forward motion, no
             # ping-pong), through a one-sequence HIP context and, frame for frame, through the CPU oracle
             sq = syn.StereoSequence(cal=cal, n_frames=args.ate_frames + 1, seed=seed0 + 7919, movers=args.movers, **scene)
@@ -475,7 +507,7 @@ def main():
                        "mean_tracks_after_bounds": float(np.mean(n_bounds)), "mean_inliers": float(np.mean(n_inl)),
                        "mean_ransac_iters": float(np.mean(n_iters)),
                        "mean_features_dead_after_lk_pass_0_1_2": [float(v) for v in dead],
-                       "ate_frames": {"timed_steps_of_slot_0": args.steps, "long_run": args.ate_frames},
+                       "ate_frames": {"timed_steps_of_slot_0": args.steps, "long_run": args.ate_frames if args.full else 0},
                        "distinct_streams": min(B, args.pool * max(1, (2 * F - 2) // 3)),
                        "distinct_rendered_sequences": args.pool, "frames_per_sequence": F,
                        "pose_ok_fraction": n_ok_all / float(world * B * args.steps)},

@@ -80,7 +80,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu_gloo():
     device.  Sharded sequences, barrier, max-over-ranks timing, the pose-stream gather to rank 0 and the reductions all run; the
     line says n_gpus 2 and counts both ranks' sequences."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "3",
-                        "--warmup", "1", "--seqs", "8", "--contexts", "1", "--pool", "2", "--cpu-frames", "6", "--ate-frames", "3"],
+                        "--warmup", "1", "--seqs", "8", "--contexts", "1", "--pool", "2", "--full", "--cpu-frames", "6", "--ate-frames", "3"],
                        env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

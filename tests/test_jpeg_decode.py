@@ -2,7 +2,7 @@
 main.cpp reads with cv::imread.  tools/jpeg_decode.hpp is the CLI's own baseline decoder, written to reproduce libjpeg(-turbo)'s
 default output — the decoder behind cv::imread and behind PIL — byte for byte (slow-integer IDCT, fancy chroma upsampling, JFIF
 colour tables).  Checked against PIL on every sampling layout, odd sizes, optimised tables, restart markers and gray files, and
-(build container only) on the reference's own JPEG frames."""
+on four of the reference's own JPEG frames (tests/golden/jpeg/)."""
 import os
 import subprocess
 
@@ -76,10 +76,11 @@ def test_progressive_files_are_rejected(tmp_path):
     assert r.returncode != 0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/slam_feats"), reason="needs the reference's JPEG sets (build container only)")
 def test_reference_jpeg_frames_decode_exactly(tmp_path):
-    for p in ("/root/reference/slam_feats/left/frame0000.jpg", "/root/reference/slam_feats/right/frame0200.jpg",
-              "/root/reference/rand_feats/left/frame0003.jpg", "/root/reference/rand_feats/right/frame0100.jpg"):
+    gold = os.path.join(ROOT, "tests", "golden", "jpeg")          # four frames of the reference's slam_feats/ and rand_feats/ sets
+    for name in ("slam_feats_left_frame0000.jpg", "slam_feats_right_frame0200.jpg",
+                 "rand_feats_left_frame0003.jpg", "rand_feats_right_frame0100.jpg"):
+        p = os.path.join(gold, name)
         assert np.array_equal(decode(p, str(tmp_path)), np.asarray(PIL_Image.open(p).convert("RGB"))), p
 
 

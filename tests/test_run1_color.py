@@ -5,26 +5,21 @@ B-1: cv::FAST walks the first W bytes of each interleaved row, pyramids and LK a
 <= 1e-6 m).  Fed the same BGR frames, the oracle reproduces the recorded positions to <= 1e-6 m absolute (3-4 significant digits
 of millimetre-sized values; the file prints 6) for the first 13 frames and to centimetres over all 128 — the only end-to-end evidence about OpenCV's arithmetic
 available without OpenCV, and it covers FAST, bucketing, pyramids, LK, triangulation, RANSAC-PnP and the LM refine at once."""
-import lzma
 import os
 
 import numpy as np
 import pytest
 
+import golden_run1
 import oracle_lib as orc
 from stereo_visual_odometry_amd import synthetic as syn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF_RUN1 = "/root/reference/run1"
 
 
-def fixture_frames():
-    out = []
-    for cam in ("left", "right"):
-        with lzma.open(os.path.join(GOLD, "run1_bgr_%s_0_47.npy.xz" % cam), "rb") as f:
-            out.append(np.load(f, allow_pickle=False))
-    return out
+def fixture_frames(n=48):
+    return golden_run1.bgr_frames(n)
 
 
 def recorded():
@@ -65,7 +60,7 @@ def check_against_recording(track, ref):
     if n > 16:
         assert inc[16:min(n, 22)].max() < 2e-6, inc[16:22]               # the frames between the flips agree as well as the first 13
     if n > 23:
-        m = min(n, 48)                                                 # the committed fixture ends at frame 47; the 128-frame run has its own bounds
+        m = min(n, 48)                                                 # the 48-frame checks end at frame 47; the 128-frame run has its own bounds
         assert err[23:m].max() < 1.2e-2, err[23:m]
         assert inc[28:m].max() < 2e-4 if m > 28 else True
         assert inc[23:min(m, 28)].max() < 8e-3
@@ -91,14 +86,10 @@ def test_gray_input_does_not_reproduce_it():
     assert all(flags[1:]) and err[1:14].min() > 3e-4 and err.max() < 0.05      # 0.5 .. 25 mm off: 3-5 orders of magnitude worse
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_RUN1), reason="needs the reference's run1/ images (build container only)")
 def test_oracle_tracks_the_whole_recording():
-    """All 128 recorded frames (read straight from the reference's data set, which exists in the build container only)."""
-    from PIL import Image
-    bgr = lambda p: np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[..., ::-1])
+    """All 128 recorded frames (the whole of the reference's run1/ set, committed under tests/golden/)."""
     n = 128
-    left = [bgr("%s/left/frame%06d.png" % (REF_RUN1, i)) for i in range(n)]
-    right = [bgr("%s/right/frame%06d.png" % (REF_RUN1, i)) for i in range(n)]
+    left, right = fixture_frames(n)
     orc.set_threads(4)
     try:
         track, flags = positions(new_oracle(), left, right)

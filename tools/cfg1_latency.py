@@ -1,10 +1,10 @@
 """cfg1 (the reference's own run1 set: 512x288 BGR, LK 10x10, 3 levels, K=100) through VisualOdometry.stereo_callback, colour and gray:\nms per frame pair and per-stage HIP-event times, on the committed 48-frame fixture.  usage: python tools/cfg1_latency.py"""
-import sys, time, lzma, io, numpy as np
+import sys, time, numpy as np
 import os; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); os.chdir(ROOT)
 from stereo_visual_odometry_amd import api
-def load(p):
-    return np.load(io.BytesIO(lzma.open(p).read()))
-L = load('tests/golden/run1_bgr_left_0_47.npy.xz'); R = load('tests/golden/run1_bgr_right_0_47.npy.xz')
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import golden_run1
+L, R = golden_run1.bgr_frames(48)
 print(L.shape, L.dtype)
 P = np.array([[320., 0, 256, 0], [0, 320, 144, 0], [0, 0, 1, 0]], np.float32); Pr = P.copy(); Pr[0, 3] = -32.0
 for mode in ('bgr', 'gray', 'bgr, float sums (the reference\'s own LK rounding)'):

@@ -42,8 +42,8 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCL
 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_SMEM --output-format csv -d $O/sq2 -o sq2 -- $B > $O/sq2.log 2>&1
 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/gui -o gui -- $B > $O/gui.log 2>&1
 echo sq counters done
-python3 bench.py > $O/bench.json 2> $O/bench.err
-python3 bench.py --movers 0 --cpu-frames 0 > $O/bench_static.json 2> $O/bench_static.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --movers 0 --cpu-frames 0 > $O/bench_static.json 2> $O/bench_static.err
 python3 tools/measure_pcie.py > $O/latency.txt 2>&1
 python3 tools/stage_latency.py >> $O/latency.txt 2>&1
 python3 tools/latency_cpp.py 21 300 > $O/latency_cpp.txt 2>/dev/null

@@ -8,11 +8,10 @@ the per-frame counters that show whether a track or an inlier decision differs f
 
     python tools/deviation_ablation.py [--frames 128] [--out tests/golden/deviation_ablation.txt]
 
-Reads /root/reference/run1 when it exists (build container: all 128 frames), else the committed 48-frame fixture.
+Reads the committed fixture of all 128 run1 frames (tests/golden/run1_bgr_*.npy.xz).
 TEST INFRASTRUCTURE: uses oracle/ only; nothing here touches the product library.
 """
 import argparse
-import lzma
 import os
 import sys
 
@@ -21,11 +20,11 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import golden_run1                                                          # noqa: E402
 import oracle_lib as orc                                                    # noqa: E402
 from stereo_visual_odometry_amd import synthetic as syn                     # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF_RUN1 = "/root/reference/run1"
 
 D1, D2, D3R, D4, D5, HYPOT = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20          # D3R: the FORMER deviation D3 (right singular vectors) back in force
 D1_FMA, D1_W4, D1_SCALAR = 0x100, 0x200, 0x400
@@ -55,18 +54,9 @@ SETTINGS = [
 
 
 def load_frames(n):
-    if os.path.isdir(REF_RUN1):
-        from PIL import Image
-        bgr = lambda p: np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[..., ::-1])
-        n = min(n, 128)
-        return ([bgr("%s/left/frame%06d.png" % (REF_RUN1, i)) for i in range(n)],
-                [bgr("%s/right/frame%06d.png" % (REF_RUN1, i)) for i in range(n)], "reference run1/ (%d frames)" % n)
-    out = []
-    for cam in ("left", "right"):
-        with lzma.open(os.path.join(GOLD, "run1_bgr_%s_0_47.npy.xz" % cam), "rb") as f:
-            out.append(np.load(f, allow_pickle=False))
-    n = min(n, len(out[0]))
-    return list(out[0][:n]), list(out[1][:n]), "committed fixture (%d frames)" % n
+    n = min(n, golden_run1.N_FRAMES)
+    left, right = golden_run1.bgr_frames(n)
+    return list(left), list(right), "reference run1/ (%d frames, committed fixture)" % n
 
 
 def replay(mode, left, right):
