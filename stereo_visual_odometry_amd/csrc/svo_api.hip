@@ -355,7 +355,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         if (g.armed) HIPCHK(hipStreamWaitEvent(s, g.ev, 0));
     }
     if (with_events) HIPCHK(hipEventRecord(c->ev_lk0[slot], s));
-    if (!launch_lk_chain(d, gn, s, 1)) { g_err = "no LK kernel is built for this window / lanes-per-feature / channel count"; return SVO_ERR_STATE; }
+    if (!launch_lk_chain(d, gn, s, 1)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
     if (with_events) HIPCHK(hipEventRecord(c->ev_lk1[slot], s));
     if (gated) {
         LkGate& g = g_lk_gate[c->device];
@@ -576,7 +576,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     if ((rc = stage_host_images(c, l, r, stride, lp, rp)) != SVO_OK) return rc;
     const uint8_t** hp = c->h_ptrs; hp[0] = lp[0]; hp[1] = rp[0];
     launch_ingest_pyramid(c->d, c->d.img_ptrs, c->d.geom.W * c->d.CN, c->stream, false);          // vo.cpp:200-201
-    if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / lanes-per-feature / channel count"; return SVO_ERR_STATE; }   // vo.cpp:203-230 (the caller gets every pass's raw points)
+    if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // vo.cpp:203-230 (the caller gets every pass's raw points)
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(pl1, c->d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(pr1, c->d.pr1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
@@ -964,7 +964,7 @@ extern "C" int svo_circular_match(int device, const svo_config* cfg_in, const ui
     hs.frame_id = 1; hs.active = 1; hs.slot_img_t0 = 0; hs.slot_pyr_t0 = 0; hs.n_feat = n; hs.feat_buf = 0;
     if ((rc = build_pyramid_in_slot(c, hs, 1)) != SVO_OK) return rc;             // leaves slot_t1 = 1
     HIPCHK(hipMemcpyAsync(c->d.feat_xy[0], pl0, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-    if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / lanes-per-feature / channel count"; return SVO_ERR_STATE; }
+    if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(pl1, c->d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(pr1, c->d.pr1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));

@@ -17,7 +17,8 @@
 //   * the search-image window (2 rows x (PPL+1) bytes per lane) is also held in VGPRs and only
 //     re-loaded when the INTEGER window position changes — in the sub-pixel phase of the Newton
 //     iteration (most steps) the loop touches no memory at all;
-//   * windows that cross the image border take a per-byte REFLECT_101 path (rare);
+//   * every pyramid level is stored with its REFLECT_101 border (Geometry::pad, k_pad_pyramid), so a window that crosses
+//     the image border is loaded like any other;
 //   * the 2x2 normal matrix and the mismatch vector are per-lane int32 partials, split into 16-bit
 //     halves and reduced with DPP row operations + v_readlane into SGPRs — exact integers, so the
 //     result is order-independent and bit-identical to the sequential CPU loop, and the float tail
@@ -25,12 +26,9 @@
 #include "svo_internal.hpp"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #define LK_WBITS 14
-// Newton-loop form per lanes-per-feature: 0 = epochs, 1 = flat
-#ifndef LK_LOOP_FORM
-#define LK_LOOP_FORM(G) ((G) >= 32 ? 0 : 1)
-#endif
 #define DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 
 __device__ __forceinline__ int reflect101(int i, int n) {
@@ -39,9 +37,9 @@ __device__ __forceinline__ int reflect101(int i, int n) {
     return i < 0 ? 0 : (i >= n ? n - 1 : i);
 }
 
-// G lanes cooperate on one feature (G = 16: one DPP row per feature, 4 features per wave; G = 64: the whole wave).
-// The window is cut into NSEG = W * LPR row segments of PPL pixels; each lane owns SPL consecutive segments.
-template <int W, int G> struct LkLayout {
+// The 64 lanes of a wave cooperate on one feature.  The window is cut into NSEG = W * LPR <= 64 row segments of PPL pixels;
+// lane l owns segment l (lanes from NSEG on are idle).
+template <int W> struct LkLayout {
     static constexpr int ppl() {                 // pixels per segment: smallest p with W * ceil(W/p) <= 64
         for (int p = 1; p <= W; p++) if (W * ((W + p - 1) / p) <= 64) return p;
         return W;
@@ -50,14 +48,13 @@ template <int W, int G> struct LkLayout {
     static constexpr int LPR = (W + PPL - 1) / PPL;   // segments per window row
     static constexpr int EXT = LPR * PPL;             // columns covered by the segments of a row (>= W)
     static constexpr int NSEG = W * LPR;
-    static constexpr int SPL = (NSEG + G - 1) / G;    // segments per lane
     static constexpr int NS = PPL + 3;                // template source bytes per segment per row
     static constexpr int NB = PPL + 1;                // search-window bytes per segment per row
 };
 
 // Border width the kernel's reads need around every pyramid level at window `win` (Geometry::pad): the template reads rows and
 // columns origin - 1 .. origin + EXT + 1 (+ up to 3 bytes of the last dword) with origin in [-win, size), the search window
-// origin .. origin + EXT.  Same PPL / EXT recipe as LkLayout (which does not depend on the lanes per feature).
+// origin .. origin + EXT.  Same PPL / EXT recipe as LkLayout.
 int lk_pad_for(int win) {
     if (win < 1) win = 1;
     int ppl = win;
@@ -74,19 +71,11 @@ __device__ __forceinline__ int dpp_row_step(int v) {
     if (S == 2) return v + __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);   // row_half_mirror
     return v + __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);               // row_mirror: every lane holds its row's sum
 }
-// rows -> group: every lane of the group ends up with the group total
-template <int G>
+// rows -> wave: the wave total, as a scalar
 __device__ __forceinline__ int dpp_cross_rows(int v) {
-    if (G == 64) {
-        v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-        v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-        v = __builtin_amdgcn_readlane(v, 63);
-    }
-    if (G == 32) {
-        const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        v = r[0] + r[1];
-    }
-    return v;
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
+    return __builtin_amdgcn_readlane(v, 63);
 }
 // Largest per-lane |partial| of PIX window pixels: |diff| <= 255 * 32, |Ix|, |Iy| <= 4080 (Scharr of u8).  PRE = number of
 // doubling steps such a partial survives in int32; the split into 16-bit halves can wait that long.
@@ -96,71 +85,31 @@ constexpr int lk_presplit_steps(int pix) {
     while (k < 4 && m * 2 <= 2147483647LL) { m *= 2; k++; }
     return k;
 }
-// N independent exact sums at once ("wide" form, any input): the partials are split into 16-bit halves (each half-sum fits
-// 23 bits) after the first PRE steps; the DPP steps of the values are issued round-robin so every DPP instruction has
-// independent work between it and its predecessor (DPP needs 2 wait states after a VALU write of its source).
-template <int G, int N, int PRE>
-__device__ __forceinline__ void group_sums_to_float(const int (&partial)[N], float (&out)[N]) {
-    int u[N], v[2 * N];
-#pragma unroll
-    for (int i = 0; i < N; i++) u[i] = partial[i];
-    if (PRE > 0) {
-#pragma unroll
-        for (int i = 0; i < N; i++) u[i] = dpp_row_step<0>(u[i]);
-    }
-    if (PRE > 1) {
-#pragma unroll
-        for (int i = 0; i < N; i++) u[i] = dpp_row_step<1>(u[i]);
-    }
-    if (PRE > 2) {
-#pragma unroll
-        for (int i = 0; i < N; i++) u[i] = dpp_row_step<2>(u[i]);
-    }
-    if (PRE > 3) {
-#pragma unroll
-        for (int i = 0; i < N; i++) u[i] = dpp_row_step<3>(u[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) { v[2 * i] = u[i] & 0xFFFF; v[2 * i + 1] = u[i] >> 16; }
-    if (PRE < 1) {
-#pragma unroll
-        for (int i = 0; i < 2 * N; i++) v[i] = dpp_row_step<0>(v[i]);
-    }
-    if (PRE < 2) {
-#pragma unroll
-        for (int i = 0; i < 2 * N; i++) v[i] = dpp_row_step<1>(v[i]);
-    }
-    if (PRE < 3) {
-#pragma unroll
-        for (int i = 0; i < 2 * N; i++) v[i] = dpp_row_step<2>(v[i]);
-    }
-    if (PRE < 4) {
-#pragma unroll
-        for (int i = 0; i < 2 * N; i++) v[i] = dpp_row_step<3>(v[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < 2 * N; i++) v[i] = dpp_cross_rows<G>(v[i]);
-#pragma unroll
-    for (int i = 0; i < N; i++) out[i] = (float)v[2 * i + 1] * 65536.f + (float)v[2 * i];
+// One exact wave sum, "wide" form (any input): the partial is split into 16-bit halves (each half-sum fits 23 bits) after the
+// first PRE steps; the DPP steps of the two halves alternate so every DPP instruction has independent work between it and its
+// predecessor (DPP needs 2 wait states after a VALU write of its source).
+template <int PRE>
+__device__ __forceinline__ float wave_sum_wide(int u) {
+    static_assert(PRE >= 1, "every built window survives one doubling in int32");
+    u = dpp_row_step<0>(u);
+    if (PRE > 1) u = dpp_row_step<1>(u);
+    if (PRE > 2) u = dpp_row_step<2>(u);
+    if (PRE > 3) u = dpp_row_step<3>(u);
+    int lo = u & 0xFFFF, hi = u >> 16;
+    if (PRE < 2) { lo = dpp_row_step<1>(lo); hi = dpp_row_step<1>(hi); }
+    if (PRE < 3) { lo = dpp_row_step<2>(lo); hi = dpp_row_step<2>(hi); }
+    if (PRE < 4) { lo = dpp_row_step<3>(lo); hi = dpp_row_step<3>(hi); }
+    lo = dpp_cross_rows(lo); hi = dpp_cross_rows(hi);
+    return (float)hi * 65536.f + (float)lo;
 }
 // "narrow" form: the caller guarantees that the sum of |terms| stays below 2^31, so every intermediate fits int32 and
 // v_cvt_f32_i32 rounds the exact total once (nearest-even) — the same float as the wide form.
-template <int G, int N>
-__device__ __forceinline__ void group_sums_to_float_narrow(const int (&partial)[N], float (&out)[N]) {
-    int u[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) u[i] = dpp_row_step<0>(partial[i]);
-#pragma unroll
-    for (int i = 0; i < N; i++) u[i] = dpp_row_step<1>(u[i]);
-#pragma unroll
-    for (int i = 0; i < N; i++) u[i] = dpp_row_step<2>(u[i]);
-#pragma unroll
-    for (int i = 0; i < N; i++) u[i] = dpp_row_step<3>(u[i]);
-#pragma unroll
-    for (int i = 0; i < N; i++) out[i] = (float)dpp_cross_rows<G>(u[i]);
+__device__ __forceinline__ float wave_sum_narrow(int u) {
+    u = dpp_row_step<0>(u); u = dpp_row_step<1>(u); u = dpp_row_step<2>(u); u = dpp_row_step<3>(u);
+    return (float)dpp_cross_rows(u);
 }
 
-// ---- wave-wide (G == 64) sums of TWO values at once.  v_permlane32_swap exchanges the upper 32 lanes of one register with
+// ---- wave sums of TWO values at once.  v_permlane32_swap exchanges the upper 32 lanes of one register with
 // the lower 32 of another: after it, (r0 + r1) holds a's 32 pairwise partials in lanes 0..31 and b's in lanes 32..63, so every
 // following DPP step reduces both values in one instruction (rows 0-1 belong to a, rows 2-3 to b; row_bcast:15 joins each
 // pair of rows).  7 VALU instructions + 2 v_readlane instead of 12 + 2.
@@ -232,17 +181,13 @@ __device__ __forceinline__ void lk_weights(float a, float b, unsigned& w0, unsig
 
 // eps_hi / eps_lo bracket eps2 for the f32 screening of the convergence test (see newton_step)
 struct LkCrit { int max_count; double eps2; float mineig_cut; float eps_hi, eps_lo; };
-// With G == 64 every per-feature quantity is identical in all lanes of the wave, so every branch on one is wave-uniform.
-// The compiler cannot prove that (the values live in VGPRs) and would guard each branch with exec-mask bookkeeping and keep
-// loop counters in VGPRs; a ballot of the condition IS uniform by construction and costs nothing extra (v_cmp writes an
-// SGPR pair either way): branches become s_cbranch, counters become SALU.  Groups smaller than a wave keep plain SIMT.
-template <int G> __device__ __forceinline__ bool uni(bool c) {
-    if constexpr (G == 64) return __builtin_amdgcn_ballot_w64(c) != 0ull; else return c;
-}
-template <int G> __device__ __forceinline__ int uni_i(int v) {
-    if constexpr (G == 64) return __builtin_amdgcn_readfirstlane(v); else return v;
-}
-template <int SPL> struct LkSegs { int row[SPL]; int xs[SPL]; bool on[SPL]; };   // the window segments a lane owns
+// Every per-feature quantity is identical in all lanes of the wave, so every branch on one is wave-uniform.  The compiler
+// cannot prove that (the values live in VGPRs) and would guard each branch with exec-mask bookkeeping and keep loop counters
+// in VGPRs; a ballot of the condition IS uniform by construction and costs nothing extra (v_cmp writes an SGPR pair either
+// way): branches become s_cbranch, counters become SALU.
+__device__ __forceinline__ bool uni(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0ull; }
+__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+struct LkSeg { int row, xs; bool on; };   // the window segment a lane owns
 
 typedef short short2v __attribute__((ext_vector_type(2)));
 typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
@@ -416,23 +361,19 @@ __device__ __forceinline__ void fs_sum_b(int* __restrict__ lds, float& b1, float
 }
 
 // One cv::calcOpticalFlowPyrLK track of a single point across all pyramid levels (LKTrackerInvoker semantics,
-// SURVEY.md Appendix A.3).  (px,py) -> (outx,outy), status.  Written as plain SIMT code: every "per feature" quantity
-// lives in a VGPR and is identical across the G lanes of the feature's group; control flow diverges between groups and
-// is handled by the exec mask.  segrow / segxs / segon describe the SPL window segments this lane owns.
+// SURVEY.md Appendix A.3).  (px,py) -> (outx,outy), status.  Every "per feature" quantity lives in a VGPR and is identical
+// in all lanes of the wave (uni() above makes the branches on it scalar).  sg is the window segment this lane owns.
 // CN = image channels: the window sums of LKTrackerInvoker run over every channel of every pixel (x < winSize.width*cn).
-// Each colour plane is its own single-channel pyramid (plane k at pyr + k * pstride); the (plane, segment) pairs a lane owns
-// are flattened into one index kk = plane * SPL + segment, so CN = 3 simply triples the per-lane pixel arrays.
-// FS = float-sums mode (above): fs_lds is the block's LkFs<W, CN>::LDS_INTS ints of LDS (unused otherwise).
-template <int W, int G, int CN, bool FS = false>
+// Each colour plane kk is its own single-channel pyramid (at pyr + kk * pstride), so CN = 3 simply triples the per-lane
+// pixel arrays.  FS = float-sums mode (above): fs_lds is the block's LkFs<W, CN>::LDS_INTS ints of LDS (unused otherwise).
+template <int W, int CN, bool FS = false>
 __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, const uint8_t* __restrict__ pyrB, size_t pstride,
                         float px, float py, float& outx, float& outy, int& status, const LkCrit& crit,
-                        const LkSegs<LkLayout<W, G>::SPL>& sg, int& n_visits, int& n_steps, int* fs_lds = nullptr) {
-    static_assert(!FS || G == 64, "the float-sums mode runs one feature per wave");
+                        const LkSeg& sg, int& n_visits, int& n_steps, int* fs_lds = nullptr) {
     constexpr int FE = W * CN;                                          // interleaved elements per window row (float-sums mode)
-    using LL = LkLayout<W, G>;
-    constexpr int PPL = LL::PPL, EXT = LL::EXT, NS = LL::NS, NB = LL::NB, SPL = LL::SPL;
-    constexpr int KS = SPL * CN;                                        // (plane, segment) pairs per lane
-    constexpr int PRE = lk_presplit_steps(PPL * KS);
+    using LL = LkLayout<W>;
+    constexpr int PPL = LL::PPL, EXT = LL::EXT, NS = LL::NS, NB = LL::NB;
+    constexpr int PRE = lk_presplit_steps(PPL * CN);
     constexpr float NARROW_LIMIT = (float)(0.95 * 4611686018427387904.0 / (8160.0 * 8160.0 * W * W * CN));
     const float half = (W - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (float)(1 << 20);
@@ -451,7 +392,7 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         ppx -= half; ppy -= half;
         const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
         // -W <= ip < size  <=>  (unsigned)(ip + W) < (unsigned)(size + W): one compare per axis
-        if (uni<G>(ipx < -W || ipx >= L.w || ipy < -W || ipy >= L.h)) {
+        if (uni(ipx < -W || ipx >= L.w || ipy < -W || ipy >= L.h)) {
             if (level == 0) status = 0;
             continue;
         }
@@ -468,23 +409,22 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         // shift unit, so folding it in is exact); and the derivatives as packed signed 16-bit pairs of adjacent pixels, the
         // operand layout of v_dot2_i32_i16: one instruction multiplies two mismatches with two derivatives and accumulates.
         constexpr int NPR = (PPL + 1) / 2;
-        int Kr[KS][PPL];
-        unsigned Ixp[KS][NPR], Iyp[KS][NPR];
+        int Kr[CN][PPL];
+        unsigned Ixp[CN][NPR], Iyp[CN][NPR];
         int pA11 = 0, pA12 = 0, pA22 = 0;
         // 1 <= ipx && ipx + EXT + 1 < w  <=>  (unsigned)(ipx - 1) < (unsigned)(w - EXT - 2)   (a non-positive bound never holds: the image is larger than the window)
-        const bool interior = uni<G>(ipx >= 1 && ipx + EXT + 1 < L.w && ipy >= 1 && ipy + W + 1 < L.h);
-        // interior windows: one (wave-uniform for G == 64) base address per level visit, 32-bit lane offsets
-        const uint8_t* __restrict__ Abase = A + (ptrdiff_t)(uni_i<G>(ipy) - 1) * L.stride + (uni_i<G>(ipx) - 1);
+        const bool interior = uni(ipx >= 1 && ipx + EXT + 1 < L.w && ipy >= 1 && ipy + W + 1 < L.h);
+        // interior windows: one wave-uniform base address per level visit, 32-bit lane offsets
+        const uint8_t* __restrict__ Abase = A + (ptrdiff_t)(uni_i(ipy) - 1) * L.stride + (uni_i(ipx) - 1);
 #pragma unroll
-        for (int kk = 0; kk < KS; kk++) {
-            const int k = kk % SPL;
-            const int row = sg.row[k], xs = sg.xs[k];
+        for (int kk = 0; kk < CN; kk++) {
+            const int row = sg.row, xs = sg.xs;
             unsigned Ip[2][PPL], DXp[2][PPL], DYp[2][PPL];             // [row 0/1 of the bilinear][pixel]: packed pairs
             // source pairs of the four rows: unaligned dword loads.  A window over the image border reads the level's REFLECT_101
             // border, which is stored with it (Geometry::pad, k_pad_pyramid) — the same bytes the per-byte path used to gather
             unsigned Q[4][NS - 1];
             {
-                const uint8_t* p = Abase + (size_t)(kk / SPL) * pstride + (unsigned)(row * L.stride + xs);
+                const uint8_t* p = Abase + (size_t)kk * pstride + (unsigned)(row * L.stride + xs);
 #pragma unroll
                 for (int r = 0; r < 4; r++) load_pairs<NS>(p + (unsigned)(r * L.stride), Q[r]);
             }
@@ -535,7 +475,7 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
             }
             // patch samples (kept in registers for the Newton loop) + covariance partials.  Segments / pixels outside
             // the window get zero derivative weights: their Ix = Iy = 0, so they contribute exact zeros everywhere.
-            const unsigned wd0 = sg.on[k] ? w0 : 0u, wd1 = sg.on[k] ? w1 : 0u;
+            const unsigned wd0 = sg.on ? w0 : 0u, wd1 = sg.on ? w1 : 0u;
             int ixv[PPL], iyv[PPL];
 #pragma unroll
             for (int j = 0; j < PPL; j++) {
@@ -548,7 +488,7 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
                 const int iyacc = dot2(DYp[1][j], wd1, dot2_keep(DYp[0][j], wd0, 1 << (LK_WBITS + 1)));
                 ixv[j] = on ? ixacc : 0; iyv[j] = on ? iyacc : 0;
                 if constexpr (FS) {
-                    if (sg.on[k] && on) fs_lds[row * FE + (xs + j) * CN + kk / SPL] = (int)pack_hi16(ixacc, iyacc);
+                    if (sg.on && on) fs_lds[row * FE + (xs + j) * CN + kk] = (int)pack_hi16(ixacc, iyacc);
                 }
             }
 #pragma unroll
@@ -565,21 +505,12 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
             fs_sum_A<W, CN>(fs_lds, As);
             __syncthreads();
         } else {
-            const int pa[3] = {pA11, pA12, pA22};
             // pA11, pA22 >= 0 and |pA12| <= (pA11 + pA22) / 2 per lane (|ab| <= (a^2 + b^2) / 2 term by term), so one unsigned
-            // compare bounds all three partials: below 2^25 per lane the group sums stay inside int32 -> narrow reduction
+            // compare bounds all three partials: below 2^25 per lane the wave sums stay inside int32 -> narrow reduction
             const bool big = ((unsigned)pA11 | (unsigned)pA22) >= (1u << 25);
-            const unsigned long long bigs = __builtin_amdgcn_ballot_w64(big);
-            const bool nar = G == 64 ? bigs == 0ull : ((bigs >> ((threadIdx.x / G) * G)) & ((G == 64 ? 0ull : (1ull << (G & 63))) - 1ull)) == 0ull;
-            if constexpr (G == 64 && PRE >= 1) {
-                const int p1[1] = {pA12}; float a1[1];
-                if (nar) { wave_sums2_narrow(pA11, pA22, As[0], As[2]); group_sums_to_float_narrow<G, 1>(p1, a1); }
-                else { wave_sums2_wide<PRE>(pA11, pA22, As[0], As[2]); group_sums_to_float<G, 1, PRE>(p1, a1); }
-                As[1] = a1[0];
-            } else {
-                if (nar) group_sums_to_float_narrow<G, 3>(pa, As);
-                else group_sums_to_float<G, 3, PRE>(pa, As);
-            }
+            const bool nar = __builtin_amdgcn_ballot_w64(big) == 0ull;
+            if (nar) { wave_sums2_narrow(pA11, pA22, As[0], As[2]); As[1] = wave_sum_narrow(pA12); }
+            else { wave_sums2_wide<PRE>(pA11, pA22, As[0], As[2]); As[1] = wave_sum_wide<PRE>(pA12); }
         }
         // |sum diff*Ix| <= 8160 * sqrt(CN W^2 * sum Ix^2) (Cauchy-Schwarz): below 2^31 when sum Ix^2 < 2^62 / (8160^2 CN W^2); 5 % margin
         // covers the float rounding of As.  Then the mismatch sums never leave int32 and take the narrow reduction.
@@ -591,7 +522,7 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         // host found by bisection over the floats (lk_mineig_cut): division by a positive constant is monotone, so
         // "(double)fl(num / den) < threshold"  <=>  "num < cut" exactly.
         const float eig_num = A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12);
-        if (uni<G>(eig_num < crit.mineig_cut || Dt < 1.1920928955078125e-07f)) {
+        if (uni(eig_num < crit.mineig_cut || Dt < 1.1920928955078125e-07f)) {
             if (level == 0) status = 0;
             continue;
         }
@@ -604,17 +535,16 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         // re-loaded only when the INTEGER window origin floor(n) changes; most iterations move the window by a fraction of
         // a pixel and touch no memory.
         int j = 0;
-        const int max_count = uni_i<G>(crit.max_count);
+        const int max_count = uni_i(crit.max_count);
         float pdx = 0.f, pdy = 0.f, ldx = 0.f, ldy = 0.f;
         bool moved = false, osc = false, conv = false;
-        unsigned P0[KS][PPL], P1[KS][PPL];
+        unsigned P0[CN][PPL], P1[CN][PPL];
         auto load_window = [&](int inx, int iny) __attribute__((always_inline)) {
             // any origin in reach ([-W, size) per axis) lies inside the stored border
-            const uint8_t* base = Bm + (ptrdiff_t)uni_i<G>(iny) * L.stride + uni_i<G>(inx);
+            const uint8_t* base = Bm + (ptrdiff_t)uni_i(iny) * L.stride + uni_i(inx);
 #pragma unroll
-            for (int kk = 0; kk < KS; kk++) {
-                const int k = kk % SPL;
-                const uint8_t* p = base + (size_t)(kk / SPL) * pstride + (unsigned)(sg.row[k] * L.stride + sg.xs[k]);
+            for (int kk = 0; kk < CN; kk++) {
+                const uint8_t* p = base + (size_t)kk * pstride + (unsigned)(sg.row * L.stride + sg.xs);
                 load_pairs<NB>(p, P0[kk]);
                 load_pairs<NB>(p + L.stride, P1[kk]);
             }
@@ -623,10 +553,9 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         // returns true when the track is finished at this level
         auto newton_step = [&](float fa, float fb) __attribute__((always_inline)) -> bool {
             lk_weights(fa, fb, w0, w1);
-            if constexpr (G != 64) n_steps++;                               // one feature per wave: counted from j after the loop (scalar)
             int pb1 = 0, pb2 = 0;
 #pragma unroll
-            for (int kk = 0; kk < KS; kk++) {
+            for (int kk = 0; kk < CN; kk++) {
                 int dv[PPL];
                 // J - I, |.| <= 8160; three sweeps so that dependent dot instructions are PPL instructions apart
 #pragma unroll
@@ -641,14 +570,13 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
                     const unsigned dp = (2 * q + 1 < PPL) ? pack_lo16(dv[2 * q], dv[2 * q + 1]) : (unsigned)dv[2 * q];
                     if constexpr (FS) {
                         // per-element products diff * Ix, diff * Iy (exact int32) to LDS; the chain lanes sum them in OpenCV's order
-                        const int k = kk % SPL;
-                        const int xs = sg.xs[k];
-                        int* dst = fs_lds + sg.row[k] * FE + (xs + 2 * q) * CN + kk / SPL;
+                        const int xs = sg.xs;
+                        int* dst = fs_lds + sg.row * FE + (xs + 2 * q) * CN + kk;
                         const unsigned dlo = dp & 0xFFFFu, dhi = dp & 0xFFFF0000u;
-                        if (sg.on[k] && ((EXT == W) || (xs + 2 * q < W))) {
+                        if (sg.on && ((EXT == W) || (xs + 2 * q < W))) {
                             dst[0] = dot2_keep(dlo, Ixp[kk][q], 0); dst[W * FE] = dot2_keep(dlo, Iyp[kk][q], 0);
                         }
-                        if (2 * q + 1 < PPL && sg.on[k] && ((EXT == W) || (xs + 2 * q + 1 < W))) {
+                        if (2 * q + 1 < PPL && sg.on && ((EXT == W) || (xs + 2 * q + 1 < W))) {
                             dst[CN] = dot2_keep(dhi, Ixp[kk][q], 0); dst[W * FE + CN] = dot2_keep(dhi, Iyp[kk][q], 0);
                         }
                     } else {
@@ -663,22 +591,15 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
                 fs_sum_b<W, CN>(fs_lds, bs[0], bs[1]);
                 __syncthreads();
             } else {
-                const int pb[2] = {pb1, pb2};
                 // narrow (int32 end to end) when the level's Cauchy-Schwarz bound allows it, or when this iteration's own
-                // partials are small: every lane |partial| < 2^25  =>  any sum over the <= 64 lanes of a group stays below 2^31
+                // partials are small: every lane |partial| < 2^25  =>  any sum over the 64 lanes stays below 2^31
                 bool nar = narrow;
                 if (!nar) {
                     const bool big = ((unsigned)(pb1 + (1 << 25)) | (unsigned)(pb2 + (1 << 25))) >= (1u << 26);
-                    const unsigned long long bigs = __builtin_amdgcn_ballot_w64(big);
-                    nar = G == 64 ? bigs == 0ull : ((bigs >> ((threadIdx.x / G) * G)) & ((G == 64 ? 0ull : (1ull << (G & 63))) - 1ull)) == 0ull;
+                    nar = __builtin_amdgcn_ballot_w64(big) == 0ull;
                 }
-                if constexpr (G == 64 && PRE >= 1) {
-                    if (nar) wave_sums2_narrow(pb1, pb2, bs[0], bs[1]);
-                    else wave_sums2_wide<PRE>(pb1, pb2, bs[0], bs[1]);
-                } else {
-                    if (nar) group_sums_to_float_narrow<G, 2>(pb, bs);
-                    else group_sums_to_float<G, 2, PRE>(pb, bs);
-                }
+                if (nar) wave_sums2_narrow(pb1, pb2, bs[0], bs[1]);
+                else wave_sums2_wide<PRE>(pb1, pb2, bs[0], bs[1]);
             }
             const float dx = (A12 * bs[1] - A22 * bs[0]) * Dts, dy = (A12 * bs[0] - A11 * bs[1]) * Dts;
             nx += dx; ny += dy;
@@ -686,63 +607,42 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
             // termination on |delta|^2 <= eps^2, an f64 comparison in lkpyramid.cpp.  The f32 sum of squares is within 2e-7
             // (relative) of the exact one, so away from the threshold it decides; the f64 form only runs in the gap.
             const float s32 = dx * dx + dy * dy;
-            if (!uni<G>(s32 > crit.eps_hi)) {
-                if (uni<G>(s32 < crit.eps_lo)) { conv = true; return true; }
-                if (uni<G>((double)dx * (double)dx + (double)dy * (double)dy <= crit.eps2)) { conv = true; return true; }
+            if (!uni(s32 > crit.eps_hi)) {
+                if (uni(s32 < crit.eps_lo)) { conv = true; return true; }
+                if (uni((double)dx * (double)dx + (double)dy * (double)dy <= crit.eps2)) { conv = true; return true; }
             }
             // "(double)|v| < 0.01" for a float v is exactly "|v| < nextafterf((float)0.01)": 0.01 lies between the floats
             // 0x3C23D70A and 0x3C23D70B, so v < 0.01 (as doubles) <=> v <= 0x3C23D70A <=> v < 0x3C23D70B
-            if (j > 0 && uni<G>(fabsf(dx + pdx) < 0.010000000707805157f) && uni<G>(fabsf(dy + pdy) < 0.010000000707805157f)) {
+            if (j > 0 && uni(fabsf(dx + pdx) < 0.010000000707805157f) && uni(fabsf(dy + pdy) < 0.010000000707805157f)) {
                 osc = true;                                                  // nextPts -= delta * 0.5 (applied after the loop)
                 return true;
             }
             pdx = dx; pdy = dy;
             return ++j >= max_count;
         };
-        if (LK_LOOP_FORM(G) == 0) {
-            // one or two features per wave: epochs of constant integer origin, the inner loop is pure register arithmetic
-            // (measured on MI355X, LK chain ms for 32 sequences, epoch / flat: W=21 G=64 2.12 / 2.42, W=15 G=32 1.48 / 1.55)
-            bool stop = max_count <= 0;
-            while (!stop) {
-                const float fx0 = floorf(nx), fy0 = floorf(ny);             // (float)(int)floorf(n) == floorf(n) wherever the origin is in reach
-                const int inx = (int)fx0, iny = (int)fy0;
-                // -W <= in < size  <=>  (unsigned)(in + W) < (unsigned)(size + W): one compare per axis
-                if (uni<G>((unsigned)(inx + W) >= (unsigned)(L.w + W) || (unsigned)(iny + W) >= (unsigned)(L.h + W))) {
-                    if (level == 0) status = 0;
-                    break;
-                }
-                load_window(inx, iny);
-                float fa = nx - fx0, fb = ny - fy0;
-                for (;;) {
-                    if (newton_step(fa, fb)) { stop = true; break; }
-                    // same epoch <=> floor(n) == origin <=> 0 <= n - origin < 1.  The difference is exact there (|n| < 2^23, so it is
-                    // a multiple of ulp(n) below 1: at most 24 bits) and rounding is monotone elsewhere; a float in [0, 1) is exactly
-                    // a bit pattern below 0x3F800000 (negatives have the sign bit set)
-                    fa = nx - fx0; fb = ny - fy0;
-                    if (uni<G>(__float_as_uint(fa) >= 0x3F800000u || __float_as_uint(fb) >= 0x3F800000u)) break;
-                }
+        // epochs of constant integer origin: the inner loop is pure register arithmetic (measured on MI355X, LK chain ms for 32
+        // sequences at W = 21, against one flat loop that re-checks the origin every step: 2.12 / 2.42)
+        bool stop = max_count <= 0;
+        while (!stop) {
+            const float fx0 = floorf(nx), fy0 = floorf(ny);             // (float)(int)floorf(n) == floorf(n) wherever the origin is in reach
+            const int inx = (int)fx0, iny = (int)fy0;
+            // -W <= in < size  <=>  (unsigned)(in + W) < (unsigned)(size + W): one compare per axis
+            if (uni((unsigned)(inx + W) >= (unsigned)(L.w + W) || (unsigned)(iny + W) >= (unsigned)(L.h + W))) {
+                if (level == 0) status = 0;
+                break;
             }
-        } else {
-            // four features per wave: one flat loop, the groups reload independently under the exec mask while the
-            // arithmetic of the iteration stays converged (W=10 G=16: 1.05 flat / 1.10 epoch, W=7: 0.77 / 0.83).  A third form,
-            // wave-wide epochs left by a ballot as soon as any group's origin moves, cost registers (W=21 G=64: 131 vs 112
-            // VGPRs, 4 -> 3 waves per SIMD) and was slower everywhere (W=21 G=32: 2.29 ms vs 2.03 for the epoch form).
-            bool run = crit.max_count > 0;
-            int inx = -0x40000000, iny = -0x40000000;
-            while (run) {
-                const int cx = (int)floorf(nx), cy = (int)floorf(ny);
-                if (cx != inx || cy != iny) {
-                    inx = cx; iny = cy;
-                    if (inx < -W || inx >= L.w || iny < -W || iny >= L.h) {
-                        if (level == 0) status = 0;
-                        break;
-                    }
-                    load_window(inx, iny);
-                }
-                if (newton_step(nx - (float)inx, ny - (float)iny)) break;
+            load_window(inx, iny);
+            float fa = nx - fx0, fb = ny - fy0;
+            for (;;) {
+                if (newton_step(fa, fb)) { stop = true; break; }
+                // same epoch <=> floor(n) == origin <=> 0 <= n - origin < 1.  The difference is exact there (|n| < 2^23, so it is
+                // a multiple of ulp(n) below 1: at most 24 bits) and rounding is monotone elsewhere; a float in [0, 1) is exactly
+                // a bit pattern below 0x3F800000 (negatives have the sign bit set)
+                fa = nx - fx0; fb = ny - fy0;
+                if (uni(__float_as_uint(fa) >= 0x3F800000u || __float_as_uint(fb) >= 0x3F800000u)) break;
             }
         }
-        if constexpr (G == 64) n_steps += j + ((conv || osc) ? 1 : 0);       // a step that ends the track returns before ++j
+        n_steps += j + ((conv || osc) ? 1 : 0);                              // a step that ends the track returns before ++j
         if (moved) {                                                         // nextPts[i] = nextPt + halfWin (every iteration in lkpyramid.cpp)
             outx = nx + half; outy = ny + half;
             if (osc) { outx -= ldx * 0.5f; outy -= ldy * 0.5f; }
@@ -755,19 +655,21 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
     }
 }
 
-// per-lane description of the window segments it owns
-template <int W, int G>
-__device__ __forceinline__ void lk_segments(LkSegs<LkLayout<W, G>::SPL>& sg) {
-    using LL = LkLayout<W, G>;
-    const int li = threadIdx.x % G;
-#pragma unroll
-    for (int k = 0; k < LL::SPL; k++) {
-        const int sidx = li * LL::SPL + k;
-        sg.on[k] = sidx < LL::NSEG;
-        const int sc = sg.on[k] ? sidx : 0;          // idle slots shadow segment 0 so their loads stay in bounds
-        sg.row[k] = sc / LL::LPR;
-        sg.xs[k] = (sc % LL::LPR) * LL::PPL;
-    }
+// The window segment this lane owns.  Lanes are written threadIdx.x % 64 (here, lk_chain_feature's writer, k_lk_single) and the
+// feature index adds threadIdx.x / 64 (k_lk_chain, k_lk_single) although a block is one wave: the compiler does not fold them,
+// so the feature index stays per lane, and the register allocation of every LK kernel was tuned that way.  Folding them away
+// makes it scalar and moves every kernel's register count (about 6 VGPRs fewer; occupancy up at some windows, down at others)
+// and with it lk_registers_left: a change to measure on its own.
+template <int W>
+__device__ __forceinline__ LkSeg lk_segment() {
+    using LL = LkLayout<W>;
+    const int li = threadIdx.x % 64;
+    LkSeg sg;
+    sg.on = li < LL::NSEG;
+    const int sc = sg.on ? li : 0;               // idle lanes shadow segment 0 so their loads stay in bounds
+    sg.row = sc / LL::LPR;
+    sg.xs = (sc % LL::LPR) * LL::PPL;
+    return sg;
 }
 
 __device__ __forceinline__ LkCrit make_crit(const svo_config& c, float mineig_cut) {
@@ -783,31 +685,26 @@ __device__ __forceinline__ LkCrit make_crit(const svo_config& c, float mineig_cu
 }
 
 // ---- fused circular matching: L0 -> L1 -> R1 -> R0 -> L0 + masks (vo.cpp:203-230, 341-359) ----
-// Block -> (sequence, feature group) mapping.  Workgroups are dealt round-robin over the 8 XCDs (block b lands on XCD
-// b % 8, MI355X_MICROARCH.md; used for speed only, never for correctness) and every XCD has a private 4 MiB L2; one
-// sequence's four pyramids are 2.5 MB and 2-3 sequences are in flight at any time.  Three forms (launch argument `mode`):
-//  * LK_MAP_STRIPE (default): sequence-major, `slots` blocks per sequence; XCD x takes runs of `chunk` consecutive
-//    feature groups, cyclically (run q of XCD x = groups (8q + x) * chunk ...).  Features are in bucket raster order, so
-//    a run is a short horizontal strip of the image whose windows share cache lines, and every XCD touches a fraction of
-//    each pyramid instead of all of it.  The runs must stay short: work per feature is spatially correlated and the
-//    dispatcher is in-order, so long runs unbalance the XCDs.
-//  * LK_MAP_INTERLEAVED (= chunk 1): every XCD sees every 8th feature, i.e. the whole image.
-//  * LK_MAP_AFFINE (SVO_LK_XCD=1): XCD x is given the sequences x, x+8, ... and walks through them one at a time.
+// Block -> (sequence, feature) mapping.  Workgroups are dealt round-robin over the 8 XCDs (block b lands on XCD b % 8,
+// MI355X_MICROARCH.md; used for speed only, never for correctness) and every XCD has a private 4 MiB L2; one sequence's four
+// pyramids are 2.5 MB and 2-3 sequences are in flight at any time.  Sequence-major, `slots` blocks per sequence; XCD x takes
+// runs of `chunk` (SVO_LK_CHUNK) consecutive features, cyclically (run q of XCD x = features (8q + x) * chunk ...).  Features
+// are in bucket raster order, so a run is a short horizontal strip of the image whose windows share cache lines, and every
+// XCD touches a fraction of each pyramid instead of all of it.  The runs must stay short: work per feature is spatially
+// correlated and the dispatcher is in-order, so long runs unbalance the XCDs.  SVO_LK_CHUNK=1 is the interleaved form (every
+// XCD sees every 8th feature, i.e. the whole image).
 // Measured on MI355X, 32 sequences per launch (rocprofv3 FETCH_SIZE per launch / HIP-event time):
 //   chunk 1: 340 MB / 1.90 ms    4: 214 / 1.91    16: 174 / 1.94    64: 118 / 2.18    whole eighths: 61 / 2.79
-//   affine: 39 MB / 2.02 ms.  The kernel is VALU-bound and the fetches are served by the Infinity Cache, so the default
-//   takes a traffic reduction that is free; the others stay selectable.  Round 1 chose 8; re-measured at the end of round 2 at
-//   the default bench configuration (two contexts of 128 sequences, A/B in one call): 4 is 0.5-0.7 % faster than 8 on both the
-//   mover and the static scene (1, 2 and 4 tie), 16 is 1.8 % slower: default 4.
-#define LK_MAP_STRIPE 0
-#define LK_MAP_AFFINE 1
-#define LK_MAP_INTERLEAVED 2
-// The four passes of ONE feature (or FPW features side by side) and its masks: one inlined copy inside k_lk_chain (experiments/lk_queue_fed_persistent.patch fed the same function from a work queue).
+//   The kernel is VALU-bound and the fetches are served by the Infinity Cache, so the default takes a traffic reduction that
+//   is free.  Round 1 chose 8; re-measured at the end of round 2 at the default bench configuration (two contexts of 128
+//   sequences, A/B in one call): 4 is 0.5-0.7 % faster than 8 on both the mover and the static scene (1, 2 and 4 tie), 16 is
+//   1.8 % slower: default 4.  (An XCD-affine form, XCD x walking the sequences x, x + 8, ... one at a time, fetched least,
+//   39 MB, but took 2.02 ms; it was removed.)
+// The four passes of ONE feature and its masks: one inlined copy inside k_lk_chain (profiles/experiments/lk_queue_fed_persistent.patch fed the same function from a work queue).
 struct LkSeqCtx { const uint8_t *L0, *R0, *L1, *R1; int seq, buf; };
-template <int W, int G, int CN, bool FS>
+template <int W, int CN, bool FS>
 __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSeqCtx& q, int idx, const LkCrit& crit, float thr, float Wf, float Hf,
-                                                 const LkSegs<LkLayout<W, G>::SPL>& sg, int early_out, int* fs_lds) {
-    constexpr int FPW = 64 / G;
+                                                 const LkSeg& sg, int early_out, int* fs_lds) {
     const int seq = q.seq;
     const uint8_t *L0 = q.L0, *R0 = q.R0, *L1 = q.L1, *R1 = q.R1;
     const size_t o = (size_t)seq * d.CAP + idx;
@@ -815,7 +712,7 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
     // the four passes share ONE inlined copy of lk_pass (a loop, not four copies): 4x less code in the instruction cache.
     // Every pass's point is written out and folded into the masks as soon as it exists, so only the running point,
     // the start point and two flags stay live across the passes (fewer registers held through lk_pass).
-    const bool writer = threadIdx.x % G == 0;
+    const bool writer = threadIdx.x % 64 == 0;
     // per-feature state across the passes, packed so that it holds ONE register through lk_pass (the kernel sits at the edge
     // of its register budget: 104 VGPRs leave room for the other context's f64 kernels, svo_api.hip LkGate): bit 0 = every
     // status so far is 1, bit 1 = every point so far lies inside the image, bits 2-3 = 1 + the first pass (0..2) that
@@ -830,7 +727,7 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
         const uint8_t* Bq = pass == 0 ? L1 : pass == 1 ? R1 : pass == 2 ? R0 : L0;
         float2* out = pass == 0 ? d.pl1 : pass == 1 ? d.pr1 : pass == 2 ? d.pr0 : d.plc;
         float2 q; int st;
-        lk_pass<W, G, CN, FS>(d.geom, A, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds);
+        lk_pass<W, CN, FS>(d.geom, A, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds);
         if (pass < 3 && ((q.x < 0) || (q.y < 0) || (q.y >= Hf) || (q.x >= Wf))) flags &= ~2;     // pl1, pr1, pr0 (not the returned point)
         if (writer) out[o] = q;
         cur = q;
@@ -840,7 +737,7 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
         if (st == 0) {
             if ((flags & 1) && pass < 3) flags |= (pass + 1) << 2;
             flags &= ~1;
-            if (early_out && pass < 3) { if constexpr (G == 64) { if (uni<G>(true)) break; } else if (FPW == 1) break; }
+            if (early_out && pass < 3) { if (uni(true)) break; }               // uni: a scalar branch out of the pass loop
         }
     }
     if (writer) {
@@ -871,25 +768,16 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
 #ifndef FS_WAVES21
 #define FS_WAVES21 5
 #endif
-template <int W, int G, int CN, bool FS> constexpr int lk_min_waves() { return (W == 21 && G == 64 && CN == 1) ? (FS ? FS_WAVES21 : 6) : 1; }
+template <int W, int CN, bool FS> constexpr int lk_min_waves() { return (W == 21 && CN == 1) ? (FS ? FS_WAVES21 : 6) : 1; }
 #ifdef LK_EXP_MINWAVES                      // experiments: -DLK_EXP_MINWAVES=<n> overrides the table
-#define LK_MIN_WAVES(W, G, CN, FS) LK_EXP_MINWAVES
+#define LK_MIN_WAVES(W, CN, FS) LK_EXP_MINWAVES
 #else
-#define LK_MIN_WAVES(W, G, CN, FS) (lk_min_waves<W, G, CN, FS>())
+#define LK_MIN_WAVES(W, CN, FS) (lk_min_waves<W, CN, FS>())
 #endif
-template <int W, int G, int CN, bool FS = false>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(LK_MIN_WAVES(W, G, CN, FS)))) void k_lk_chain(DevBuffers d, int slots, int mode, int chunk, int early_out) {
-    constexpr int FPW = 64 / G;                                       // features per wave (= per block)
+template <int W, int CN, bool FS>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(LK_MIN_WAVES(W, CN, FS)))) void k_lk_chain(DevBuffers d, int slots, int chunk, int early_out) {
     __shared__ __attribute__((aligned(16))) int fs_lds[FS ? LkFs<W, CN>::LDS_INTS : 1];            // float-sums mode only (the default build uses no LDS)
-    int seq, fb;
-    if (mode == LK_MAP_AFFINE) {
-        const int xcd = blockIdx.x & 7, t = blockIdx.x >> 3;
-        const int jr = t / slots;                                     // round of sequences on this XCD
-        fb = t - jr * slots;                                          // feature block
-        seq = jr * 8 + xcd;
-    } else {
-        seq = blockIdx.x / slots; fb = blockIdx.x - seq * slots;
-    }
+    const int seq = blockIdx.x / slots, fb = blockIdx.x - seq * slots;
     if (seq >= d.B) return;
     SeqState& s = d.st[seq];
     if (!s.active) return;
@@ -904,79 +792,38 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_e
     const LkCrit crit = make_crit(d.cfg, d.lk_mineig_cut);
     const float thr = (float)d.cfg.circular_matching_success_threshold;                // findClosePoints takes a float32 (vo.h:432)
     const float Wf = (float)d.geom.W, Hf = (float)d.geom.H;
-    LkSegs<LkLayout<W, G>::SPL> sg;
-    lk_segments<W, G>(sg);
-    const int slot = threadIdx.x / G;
-    const int ngroups = (n + FPW - 1) / FPW;                          // feature groups (one block's worth) in this sequence
-    for (int gbase = 0; gbase < ngroups; gbase += slots) {
-        int grp;
-        if (mode == LK_MAP_STRIPE) {
-            const int ng = min(slots, ngroups - gbase);              // groups handled in this round by the sequence's blocks
-            const int x = fb & 7, r = fb >> 3;                       // slots % 8 == 0, so fb & 7 == blockIdx.x & 7 == the XCD
-            const int q = r / chunk;                                 // the r-th block of XCD x works in that XCD's q-th run
-            grp = (q * 8 + x) * chunk + (r - q * chunk);
-            if (grp >= ng) break;
-            grp += gbase;
-        } else {
-            grp = gbase + fb;
-            if (grp >= ngroups) break;
-        }
-        const int idx = grp * FPW + slot;
-        if (idx >= n) continue;                                       // whole group idle (group-uniform)
-        lk_chain_feature<W, G, CN, FS>(d, sc, idx, crit, thr, Wf, Hf, sg, early_out, fs_lds);
+    const LkSeg sg = lk_segment<W>();
+    // this block's feature in every round of `slots`: the r-th block of XCD x works in that XCD's q-th run.  slots is a multiple
+    // of 8 * chunk, so fb & 7 == blockIdx.x & 7 is the XCD and f runs over 0 .. slots - 1 once as fb does
+    const int x = fb & 7, r = fb >> 3;
+    const int q = r / chunk;
+    const int f = (q * 8 + x) * chunk + (r - q * chunk);
+    for (int base = f; base < n; base += slots) {
+        const int idx = base + threadIdx.x / 64;                      // / 64: see lk_segment
+        if (idx >= n) continue;
+        lk_chain_feature<W, CN, FS>(d, sc, idx, crit, thr, Wf, Hf, sg, early_out, fs_lds);
     }
 }
 
 // ---- single pass, for the cv::calcOpticalFlowPyrLK-shaped stage API ----
-template <int W, int G>
+template <int W>
 __global__ __launch_bounds__(64) void k_lk_single(DevBuffers d, int slotA, int camA, int slotB, int camB, int n,
                                                   const float2* prev, float2* next, uint8_t* status) {
-    constexpr int FPW = 64 / G;
     const uint8_t* A = d.pyr + pyr_index(d, 0, slotA, camA);
     const uint8_t* Bp = d.pyr + pyr_index(d, 0, slotB, camB);
     const LkCrit crit = make_crit(d.cfg, d.lk_mineig_cut);
-    LkSegs<LkLayout<W, G>::SPL> sg;
-    lk_segments<W, G>(sg);
-    const int slot = threadIdx.x / G;
-    for (int base = blockIdx.x * FPW; base < n; base += gridDim.x * FPW) {
-        const int idx = base + slot;
+    const LkSeg sg = lk_segment<W>();
+    for (int base = blockIdx.x; base < n; base += gridDim.x) {
+        const int idx = base + threadIdx.x / 64;                      // / 64: see lk_segment
         if (idx >= n) continue;
         float2 p = prev[idx], q; int st, nv = 0, ns = 0;
-        lk_pass<W, G, 1>(d.geom, A, Bp, 0, p.x, p.y, q.x, q.y, st, crit, sg, nv, ns);
-        if (threadIdx.x % G == 0) { next[idx] = q; status[idx] = (uint8_t)st; }
+        lk_pass<W, 1>(d.geom, A, Bp, 0, p.x, p.y, q.x, q.y, st, crit, sg, nv, ns);
+        if (threadIdx.x % 64 == 0) { next[idx] = q; status[idx] = (uint8_t)st; }
     }
 }
 
 #define LK_MAX_GRID 16384
 static int lk_chunk() { static int v = -1; if (v < 0) { const char* e = getenv("SVO_LK_CHUNK"); v = e ? atoi(e) : 4; if (v < 1) v = 1; if (v > 2048) v = 2048; } return v; }
-static int lk_xcd_mapping() { static int v = -1; if (v < 0) { const char* e = getenv("SVO_LK_XCD"); v = e ? atoi(e) : 0; } return v; }
-// (window, lanes per feature) instantiations; the FIRST entry of a window is its default, the others are selectable with
-// SVO_LK_G=<lanes> for measurement.
-// winSize is a mutable member in the reference (vo.h:251), so every square window from 5 to 31 is built: the tuned entries
-// first (lanes per feature chosen by measurement), then the generic one-wave-per-feature form for all other sizes — the same
-// code (LkLayout derives the segment shape from W), just not tuned.
-#ifdef SVO_LK_DEV_W21   // developer build (-DSVO_LK_DEV_W21): only the w = 21 grey default-mode kernel, compiles in seconds; never shipped
-#define LK_FOR_EACH_WINDOW(X) X(21, 64)
-#define LK_FOR_EACH_WINDOW_CN3(X)
-#define LK_FOR_EACH_WINDOW_FS(X)
-#define LK_FOR_EACH_WINDOW_FS_CN3(X)
-#else
-#define LK_FOR_EACH_WINDOW_TUNED(X) X(7, 16) X(7, 64) X(10, 16) X(10, 64) X(15, 32) X(15, 64) X(21, 64) X(21, 32) X(31, 64)
-#define LK_FOR_EACH_WINDOW_GENERIC(X) X(5, 64) X(6, 64) X(8, 64) X(9, 64) X(11, 64) X(12, 64) X(13, 64) X(14, 64) X(16, 64) X(17, 64) X(18, 64) \
-    X(19, 64) X(20, 64) X(22, 64) X(23, 64) X(24, 64) X(25, 64) X(26, 64) X(27, 64) X(28, 64) X(29, 64) X(30, 64)
-#define LK_FOR_EACH_WINDOW(X) LK_FOR_EACH_WINDOW_TUNED(X) LK_FOR_EACH_WINDOW_GENERIC(X)
-
-// 3-channel (BGR) instantiations: one per window up to 21, at the window's default lanes-per-feature (beyond that a lane would
-// hold three planes of >= 11 pixels of template and search window: more registers than a wave has)
-#define LK_FOR_EACH_WINDOW_CN3(X) X(7, 16) X(7, 64) X(10, 16) X(10, 64) X(15, 32) X(15, 64) X(21, 64) X(5, 64) X(6, 64) X(8, 64) X(9, 64) X(11, 64) X(12, 64) X(13, 64) \
-    X(14, 64) X(16, 64) X(17, 64) X(18, 64) X(19, 64) X(20, 64)
-
-// float-sums builds (svo_config.lk_float_sums): one feature per wave at every window
-#define LK_FOR_EACH_WINDOW_FS(X) X(5, 64) X(6, 64) X(7, 64) X(8, 64) X(9, 64) X(10, 64) X(11, 64) X(12, 64) X(13, 64) X(14, 64) X(15, 64) X(16, 64) X(17, 64) \
-    X(18, 64) X(19, 64) X(20, 64) X(21, 64) X(22, 64) X(23, 64) X(24, 64) X(25, 64) X(26, 64) X(27, 64) X(28, 64) X(29, 64) X(30, 64) X(31, 64)
-#define LK_FOR_EACH_WINDOW_FS_CN3(X) X(5, 64) X(6, 64) X(7, 64) X(8, 64) X(9, 64) X(10, 64) X(11, 64) X(12, 64) X(13, 64) X(14, 64) X(15, 64) X(16, 64) X(17, 64) \
-    X(18, 64) X(19, 64) X(20, 64) X(21, 64)
-#endif
 
 // Smallest float x with (double)(float)(x / (2 w^2)) >= threshold — found by bisection over the floats in their numeric order
 // (IEEE f32 division on the host, the same operation the kernel would do).  +inf if no finite float qualifies.
@@ -991,55 +838,41 @@ float lk_mineig_cut(int win, double threshold) {
     return key_to_float(hi);
 }
 
-bool lk_window_supported(int win) {
-#define CHK(Wn, Gn) if (win == Wn) return true;
-    LK_FOR_EACH_WINDOW(CHK)
-#undef CHK
-    return false;
+// The built kernels.  winSize is a mutable member in the reference (vo.h:251), so every square window from 5 to 31 is built for
+// grey input and 5 to 21 for BGR (beyond that a lane would hold three planes of >= 11 pixels of template and search window:
+// more registers than a wave has), each in both summation modes.  LkLayout derives the segment shape from W.
+// Developer build (-DSVO_LK_DEV_W21): only the w = 21 grey default-mode kernel, compiles in seconds; never shipped.
+constexpr bool lk_built(int win, int cn, bool fs) {
+#ifdef SVO_LK_DEV_W21
+    return win == 21 && cn == 1 && !fs;
+#else
+    return win >= 5 && win <= (cn == 1 ? 31 : cn == 3 ? 21 : 0);
+#endif
 }
-bool lk_window_supported_cn(int win, int cn) {
-    if (cn == 1) return lk_window_supported(win);
-#define CHK(Wn, Gn) if (win == Wn) return true;
-    if (cn == 3) { LK_FOR_EACH_WINDOW_CN3(CHK) }
-#undef CHK
-    return false;
+// Calls f(W, CN, FS), the three as std::integral_constant, for the built kernel that matches (win, cn, fs); false if none does.
+template <int W = 5, int CN = 1, bool FS = false, class F>
+static bool lk_dispatch(int win, int cn, bool fs, F&& f) {
+    if constexpr (lk_built(W, CN, FS)) {
+        if (win == W && cn == CN && fs == FS) {
+            f(std::integral_constant<int, W>(), std::integral_constant<int, CN>(), std::bool_constant<FS>());
+            return true;
+        }
+    }
+    if constexpr (!FS) return lk_dispatch<W, CN, true>(win, cn, fs, f);
+    else if constexpr (CN == 1) return lk_dispatch<W, 3, false>(win, cn, fs, f);
+    else if constexpr (W < 31) return lk_dispatch<W + 1, 1, false>(win, cn, fs, f);
+    else return false;
 }
-// One feature per wave (64 lanes) is the default for EVERY window.  Round 1 chose four features per wave for w = 7 and 10 and two
-// for w = 15 by measurement; after round 2's work on the kernel (wave-uniform control flow, scalar base addresses, two-value
-// reductions — all of which need the whole wave on one feature) the 64-lane build wins at every batch size, re-measured on
-// KITTI-sized frames with ~2 000 features (LK time per frame, 64 lanes vs grouped): w = 10: 111 vs 239 us at 1 sequence, 285 vs
-// 411 at 8, 1 809 vs 1 954 at 64; w = 15: 135 vs 213, 363 vs 458, 2 375 vs 2 676.  A grouped wave runs until its slowest feature
-// is done and cannot branch per feature.  The grouped builds stay selectable (SVO_LK_G=16 / 32) for measurement.
-// cn selects the list the answer must come from: a lanes-per-feature value asked for with SVO_LK_G is honoured only if that
-// (window, lanes) pair is built for this channel count, else the window's default applies (a 3-channel context with
-// SVO_LK_G=32 at w = 21 used to match no instantiation and launch nothing).
-static int lk_group_for(int win, int cn = 1) {
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("SVO_LK_G"); env = e ? atoi(e) : 0; }
-    int def = 0; bool have_env = false, have64 = false;
-#define CHK(Wn, Gn) if (win == Wn) { if (!def) def = Gn; if (env == Gn) have_env = true; if (Gn == 64) have64 = true; }
-    if (cn == 3) { LK_FOR_EACH_WINDOW_CN3(CHK) } else { LK_FOR_EACH_WINDOW(CHK) }
-#undef CHK
-    return have_env ? env : have64 ? 64 : def;
-}
+
+bool lk_window_supported(int win) { return lk_built(win, 1, false); }
+bool lk_window_supported_cn(int win, int cn) { return lk_built(win, cn, false); }
 
 // VGPRs a SIMD has left beside a full complement of this context's LK waves (512 per SIMD lane, allocated in eights, at most 8
 // waves): the 96-register builds of the f64 kernels (svo_kernels_pnp.hip) can run under another context's LK grid only if this
 // is >= 96 — true at w = 21 (100 registers: four waves, 96 left) and 31, not at w = 10 (74: six waves, 32 left).  -1 if unknown.
 int lk_registers_left(const DevBuffers& d) {
-    const bool fs = d.cfg.lk_float_sums != 0;
-    const int G = fs ? 64 : lk_group_for(d.cfg.win_w, d.CN);
     const void* fn = nullptr;
-#define PICK(Wn, Gn) if (!fn && !fs && d.cfg.win_w == Wn && G == Gn) fn = (const void*)k_lk_chain<Wn, Gn, CNn>;
-#define PICKFS(Wn, Gn) if (!fn && fs && d.cfg.win_w == Wn) fn = (const void*)k_lk_chain<Wn, 64, CNn, true>;
-#define CNn 1
-    if (d.CN == 1) { LK_FOR_EACH_WINDOW(PICK) LK_FOR_EACH_WINDOW_FS(PICKFS) }
-#undef CNn
-#define CNn 3
-    if (d.CN == 3) { LK_FOR_EACH_WINDOW_CN3(PICK) LK_FOR_EACH_WINDOW_FS_CN3(PICKFS) }
-#undef CNn
-#undef PICK
-#undef PICKFS
+    lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) { fn = (const void*)k_lk_chain<w, cn, fs>; });
     hipFuncAttributes at;
     if (!fn || hipFuncGetAttributes(&at, fn) != hipSuccess || at.numRegs <= 0) return -1;
     const int alloc = (at.numRegs + 7) / 8 * 8;
@@ -1050,56 +883,21 @@ int lk_registers_left(const DevBuffers& d) {
 bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t st, int early_out) {
     if (grid_n < 1) grid_n = 1;
     if (grid_n > d.CAP) grid_n = d.CAP;
-    const bool fs = d.cfg.lk_float_sums != 0;
-    const int G = fs ? 64 : lk_group_for(d.cfg.win_w, d.CN);
-    const int mode = lk_xcd_mapping();
-    if (fs) {
-#define LAUNCHFS(Wn, Gn) if (d.cfg.win_w == Wn) { int gx = grid_n; if (gx > LK_MAX_GRID) gx = LK_MAX_GRID; \
-        const int chunk = lk_chunk(); \
-        gx = (gx + 8 * chunk - 1) / (8 * chunk) * (8 * chunk); \
-        const int rounds = (d.B + 7) / 8; \
-        const unsigned blocks = mode == LK_MAP_AFFINE ? (unsigned)gx * 8u * (unsigned)rounds : (unsigned)gx * (unsigned)d.B; \
-        hipLaunchKernelGGL((k_lk_chain<Wn, 64, CNn, true>), dim3(blocks), dim3(64), 0, st, d, gx, mode, chunk, early_out); \
-        return true; }
-#define CNn 1
-        if (d.CN == 1) { LK_FOR_EACH_WINDOW_FS(LAUNCHFS) }
-#undef CNn
-#define CNn 3
-        if (d.CN == 3) { LK_FOR_EACH_WINDOW_FS_CN3(LAUNCHFS) }
-#undef CNn
-#undef LAUNCHFS
-        return false;
-    }
-#define LAUNCH(Wn, Gn) if (d.cfg.win_w == Wn && G == Gn) { int gx = (grid_n + (64 / Gn) - 1) / (64 / Gn); if (gx > LK_MAX_GRID) gx = LK_MAX_GRID; \
-        const int chunk = lk_chunk(); \
-        gx = (gx + 8 * chunk - 1) / (8 * chunk) * (8 * chunk);   /* blocks per sequence: whole runs on every XCD */ \
-        const int rounds = (d.B + 7) / 8; \
-        const unsigned blocks = mode == LK_MAP_AFFINE ? (unsigned)gx * 8u * (unsigned)rounds : (unsigned)gx * (unsigned)d.B; \
-        hipLaunchKernelGGL((k_lk_chain<Wn, Gn, CNn>), dim3(blocks), dim3(64), 0, st, d, gx, mode, chunk, early_out); \
-        return true; }
-#define CNn 1
-    if (d.CN == 1) { LK_FOR_EACH_WINDOW(LAUNCH) }
-#undef CNn
-#undef LAUNCH
-    // 3-channel contexts
-#define LAUNCH3(Wn, Gn) if (d.cfg.win_w == Wn && G == Gn) { int gx = (grid_n + (64 / Gn) - 1) / (64 / Gn); if (gx > LK_MAX_GRID) gx = LK_MAX_GRID; \
-        const int chunk = lk_chunk(); \
-        gx = (gx + 8 * chunk - 1) / (8 * chunk) * (8 * chunk); \
-        const int rounds = (d.B + 7) / 8; \
-        const unsigned blocks = mode == LK_MAP_AFFINE ? (unsigned)gx * 8u * (unsigned)rounds : (unsigned)gx * (unsigned)d.B; \
-        hipLaunchKernelGGL((k_lk_chain<Wn, Gn, 3>), dim3(blocks), dim3(64), 0, st, d, gx, mode, chunk, early_out); \
-        return true; }
-    if (d.CN == 3) { LK_FOR_EACH_WINDOW_CN3(LAUNCH3) }
-#undef LAUNCH3
-    return false;                                                     // no (window, lanes, channels) instantiation: the caller reports it
+    const int chunk = lk_chunk();
+    int gx = grid_n > LK_MAX_GRID ? LK_MAX_GRID : grid_n;
+    gx = (gx + 8 * chunk - 1) / (8 * chunk) * (8 * chunk);           // blocks per sequence: whole runs on every XCD
+    const unsigned blocks = (unsigned)gx * (unsigned)d.B;
+    // false: no kernel is built for this window / channel count / summation mode; the caller reports it
+    return lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) {
+        hipLaunchKernelGGL((k_lk_chain<w, cn, fs>), dim3(blocks), dim3(64), 0, st, d, gx, chunk, early_out);
+    });
 }
 
 void launch_lk_single(const DevBuffers& d, int slotA, int camA, int slotB, int camB, int n, const float2* prev, float2* next,
                       uint8_t* status, hipStream_t st) {
     if (n <= 0) return;
-    const int G = lk_group_for(d.cfg.win_w);
-#define LAUNCH(Wn, Gn) if (d.cfg.win_w == Wn && G == Gn) { int gx = (n + (64 / Gn) - 1) / (64 / Gn); if (gx > LK_MAX_GRID) gx = LK_MAX_GRID; \
-        hipLaunchKernelGGL((k_lk_single<Wn, Gn>), dim3(gx), dim3(64), 0, st, d, slotA, camA, slotB, camB, n, prev, next, status); return; }
-    LK_FOR_EACH_WINDOW(LAUNCH)
-#undef LAUNCH
+    const int gx = n > LK_MAX_GRID ? LK_MAX_GRID : n;
+    lk_dispatch(d.cfg.win_w, 1, false, [&](auto w, auto, auto) {
+        hipLaunchKernelGGL((k_lk_single<w>), dim3(gx), dim3(64), 0, st, d, slotA, camA, slotB, camB, n, prev, next, status);
+    });
 }

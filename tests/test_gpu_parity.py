@@ -824,9 +824,7 @@ def test_two_many_sequence_contexts_sharing_the_device(api):
 
 @pytest.mark.parametrize("win", [7, 10, 15])
 def test_many_sequence_context_small_windows(api, win):
-    """A many-sequence context (9 sequences) at the small windows against the oracle.  (These windows also have grouped LK
-    builds — four / four / two features per wave, selectable with SVO_LK_G=16 / 32 for measurement; run this file once with that
-    variable set to put them through the same checks.)"""
+    """A many-sequence context (9 sequences) at the small windows against the oracle."""
     from stereo_visual_odometry_amd import synthetic as syn
     cal = dict(syn.KITTI00, width=400, height=176, cx=200.0, cy=88.0)
     over = dict(win_w=win, win_h=win, max_level=2, max_translation_norm=2.0)
