@@ -76,7 +76,9 @@ typedef struct {
     int n_after_bounds;     /* vo.cpp:365 */
     int n_inliers;          /* vo.cpp:103 */
     int ransac_iters;       /* iterations the adaptive RANSAC loop would have run */
-    int fail_reason;        /* 0 ok, 1 first frame, 2 too few tracks (vo.cpp:82), 3 RANSAC fail / few inliers (:106), 4 motion gate (:129) */
+    int fail_reason;        /* 0 ok, 1 first frame, 2 too few tracks (vo.cpp:82), 3 RANSAC fail / few inliers (:106), 4 motion gate (:129),
+                             * 5 idle: the sequence did not take this frame (svo_process_batch_masked / svo_submit_batch_masked; every
+                             * other field is 0, T is its last good transform, ok is 0) */
     int n_features_out;     /* size of currentVOFeatures on return */
     int lk_level_visits;    /* (feature, pass, level) visits of the LK passes that reached the Newton loop.  A feature runs its passes
                              * up to and including the first one that returns status 0: vo.cpp:227-238 deletes it whatever the later
@@ -149,6 +151,23 @@ int svo_get_lk_registers_left(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
 int svo_collect(svo_context* ctx, double* T_out, int* ok_out, svo_frame_stats* stats);
+
+/* Ragged / continuous batching (the reference has no counterpart: it is one object per stream).  active: host array of n_seq
+ * bytes, nonzero = the sequence takes this frame; NULL = all active (then identical to the unmasked call).  The image pointers of
+ * idle sequences are not read and may be NULL (the arrays too, when no sequence is active); an active sequence with a NULL
+ * pointer is SVO_ERR_ARG.  An idle sequence's state is not touched — its active frames give the same results whether idle frames
+ * are interleaved or not — and its result row is its last good T, ok 0, all stats 0 but fail_reason 5; frame_id does not advance.
+ * An all-idle frame is legal, takes a results-ring slot like any other and launches only the result write.  The kernels' grids
+ * cover the active sequences only. */
+int svo_process_batch_masked(svo_context* ctx, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                             int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats);
+int svo_submit_batch_masked(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
+                            const uint8_t* active);
+/* Return one sequence (seq = -1: all) to the state of a freshly created context, so its next active frame is a first frame
+ * (fail_reason 1).  Pl / Pr: new projection matrices for it (K = Pl[:, :3], as svo_set_projection), or both NULL to keep them;
+ * exactly one NULL is SVO_ERR_ARG.  Stream-ordered: takes effect after every frame already submitted and before every frame
+ * submitted later.  Does not synchronise, and is legal with frames in flight. */
+int svo_reset_sequence(svo_context* ctx, int seq, const float Pl[12], const float Pr[12]);
 
 /* Introspection (parity tests): currentVOFeatures (vo.h:245) of one sequence, and the last frame's
  * compacted tracks.  Arrays may be NULL.  Returns the count or a negative status.  inlier[] is the is_ok vector of vo.cpp:115-119:

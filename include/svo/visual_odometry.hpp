@@ -244,6 +244,12 @@ class VisualOdometry {                                               // include/
         deletePointsWithFailureStatus(pointsRightT0, inside); deletePointsWithFailureStatus(pointsRightT1, inside);
     }
 
+    // Start over as a freshly constructed object with the same projection matrices: the next stereo_callback is a first frame
+    // (svo_reset_sequence).  The reference has no counterpart; there a tracker that is lost is replaced by a new VisualOdometry.
+    void reset() {
+        if (ctx_) svo_throw(svo_reset_sequence(ctx_, 0, nullptr, nullptr));
+    }
+
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
 

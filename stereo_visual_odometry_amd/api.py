@@ -277,32 +277,67 @@ class BatchVisualOdometry:
         Pr = np.ascontiguousarray(rightCameraProjection, np.float32).reshape(12)
         check(lib.svo_set_projection(self._h, seq, ptr(Pl), ptr(Pr)))
 
-    def stereo_callback_batch(self, lefts, rights):
-        """lists of n_seq host images -> (ok (n_seq,) bool, T (n_seq,4,4) f64)."""
-        L = [u8frame(i) for i in lefts]; R = [u8frame(i) for i in rights]
+    def _active(self, active):
+        """None, or n_seq truthy flags -> a uint8 array for the masked entry points."""
+        if active is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
+        if a.shape != (self.n_seq,):
+            raise ValueError("active must hold n_seq = %d flags" % self.n_seq)
+        return a
+
+    def stereo_callback_batch(self, lefts, rights, active=None):
+        """lists of n_seq host images -> (ok (n_seq,) bool, T (n_seq,4,4) f64).
+        active: None (every sequence takes the frame) or n_seq flags; an idle sequence's images may be None, its state is left
+        alone and its row is its last good T with ok False and stats.fail_reason 5 (svo_process_batch_masked)."""
+        act = self._active(active)
+        on = [True] * self.n_seq if act is None else [bool(x) for x in act]
+        L = [u8frame(i) if o else None for i, o in zip(lefts, on)]; R = [u8frame(i) if o else None for i, o in zip(rights, on)]
         assert len(L) == self.n_seq and len(R) == self.n_seq
         cn = max(1, self.cfg.channels)
-        assert all(i.shape == (self.height, self.width) + ((3,) if cn == 3 else ()) for i in L + R), "image shape / channels"
-        lp = (C.c_void_p * self.n_seq)(*[i.ctypes.data for i in L])
-        rp = (C.c_void_p * self.n_seq)(*[i.ctypes.data for i in R])
+        assert all(i.shape == (self.height, self.width) + ((3,) if cn == 3 else ()) for i in L + R if i is not None), "image shape / channels"
+        lp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in L])
+        rp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in R])
         T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
         st = (SvoFrameStats * self.n_seq)()
-        check(lib.svo_process_batch(self._h, lp, rp, self.width * cn, 0, ptr(T), ptr(ok), st))
+        if act is None:
+            check(lib.svo_process_batch(self._h, lp, rp, self.width * cn, 0, ptr(T), ptr(ok), st))
+        else:
+            check(lib.svo_process_batch_masked(self._h, lp, rp, self.width * cn, 0, ptr(act), ptr(T), ptr(ok), st))
         self.stats = list(st)
         return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
 
-    def process_device(self, left_ptrs, right_ptrs, stride):
-        """device pointers (ints) -> same outputs; inputs stay resident in HBM."""
+    def process_device(self, left_ptrs, right_ptrs, stride, active=None):
+        """device pointers (ints; None for idle sequences) -> same outputs; inputs stay resident in HBM."""
+        act = self._active(active)
         lp = (C.c_void_p * self.n_seq)(*left_ptrs); rp = (C.c_void_p * self.n_seq)(*right_ptrs)
         T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
         st = (SvoFrameStats * self.n_seq)()
-        check(lib.svo_process_batch(self._h, lp, rp, stride, 1, ptr(T), ptr(ok), st))
+        if act is None:
+            check(lib.svo_process_batch(self._h, lp, rp, stride, 1, ptr(T), ptr(ok), st))
+        else:
+            check(lib.svo_process_batch_masked(self._h, lp, rp, stride, 1, ptr(act), ptr(T), ptr(ok), st))
         self.stats = list(st)
         return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
 
-    def submit_device(self, left_ptrs, right_ptrs, stride):
+    def submit_device(self, left_ptrs, right_ptrs, stride, active=None):
+        act = self._active(active)
         lp = (C.c_void_p * self.n_seq)(*left_ptrs); rp = (C.c_void_p * self.n_seq)(*right_ptrs)
-        check(lib.svo_submit_batch(self._h, lp, rp, stride))
+        if act is None:
+            check(lib.svo_submit_batch(self._h, lp, rp, stride))
+        else:
+            check(lib.svo_submit_batch_masked(self._h, lp, rp, stride, ptr(act)))
+
+    def reset_sequence(self, seq=-1, Pl=None, Pr=None):
+        """Return sequence `seq` (-1: all) to a fresh context's state, optionally with new projection matrices (both or
+        neither); its next active frame is a first frame.  Stream-ordered with submit_device, no synchronisation
+        (svo_reset_sequence)."""
+        if (Pl is None) != (Pr is None):
+            raise ValueError("give both Pl and Pr, or neither")
+        pl = pr = None
+        if Pl is not None:
+            pl = np.ascontiguousarray(Pl, np.float32).reshape(12); pr = np.ascontiguousarray(Pr, np.float32).reshape(12)
+        check(lib.svo_reset_sequence(self._h, seq, ptr(pl), ptr(pr)))
 
     def collect(self):
         T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
@@ -388,6 +423,12 @@ class VisualOdometry(BatchVisualOdometry):
         rc = check(lib.svo_process(self._h, ptr(L), ptr(R), L.strides[0], ptr(T), C.byref(st)))
         self.stats = st
         return bool(rc), T.reshape(4, 4)
+
+    def reset(self):
+        """Start over as a freshly constructed object with the same projection matrices: the next stereo_callback is a first
+        frame.  The reference has no counterpart (it constructs a new VisualOdometry); this wraps svo_reset_sequence."""
+        if self._created:
+            self.reset_sequence(0)
 
     def _check_frame(self, img, which):
         """cv::Mat carries size and type and OpenCV asserts on a mismatch; a raw pointer does not: check before the C call."""

@@ -79,6 +79,8 @@ struct svo_context {
     // host side of the results ring
     FrameResult* h_results = nullptr;            // pinned [SVO_RING][B]
     const uint8_t** h_ptrs = nullptr;            // pinned [SVO_RING][2][B]
+    int* h_act = nullptr;                        // pinned [SVO_RING][2 B]: a ragged frame's active list and flags (DevBuffers::act) ...
+    int* d_act = nullptr;                        // ... and their device copy, one hipMemcpyAsync per ragged frame (kernels never read host memory for it)
     hipEvent_t ev_done[SVO_RING] = {}, ev_f0[SVO_RING] = {}, ev_lk0[SVO_RING] = {}, ev_lk1[SVO_RING] = {};
     hipEvent_t ev_pyr[SVO_RING] = {}, ev_tri[SVO_RING] = {};   // stage boundaries: pyramids built / world points triangulated
     // many-sequence contexts build the NEXT frame's pyramids on a second stream while the current frame is in its LK kernel (issue_frame)
@@ -176,6 +178,7 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     ALLOC(d.tl0, B * CAP); ALLOC(d.tr0, B * CAP); ALLOC(d.tl1, B * CAP); ALLOC(d.tr1, B * CAP);
     ALLOC(d.world, B * CAP * 3); ALLOC(d.inlier, B * CAP); ALLOC(d.inl_idx, B * CAP);
     ALLOC(d.subsets, B * (size_t)d.K * 5); ALLOC(d.hyp, B * (size_t)d.K * 12); ALLOC(d.hyp_good, B * (size_t)d.K);
+    ALLOC(c->d_act, (size_t)SVO_RING * 2 * B);
     {
         double* lam = nullptr;
         ALLOC(lam, 33);
@@ -194,6 +197,7 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     { void* dv = nullptr; HIPCHK(hipHostGetDevicePointer(&dv, c->h_results, 0)); d.results = (FrameResult*)dv; }
     HIPCHK(hipHostMalloc((void**)&c->h_ptrs, sizeof(uint8_t*) * SVO_RING * 2 * B, hipHostMallocMapped));
     HIPCHK(hipHostGetDevicePointer((void**)&d.img_ptrs, (void*)c->h_ptrs, 0));   // read in place by k_ingest: no per-frame upload
+    HIPCHK(hipHostMalloc((void**)&c->h_act, sizeof(int) * SVO_RING * 2 * B));
     for (int i = 0; i < SVO_RING; i++) {
         HIPCHK(hipEventCreate(&c->ev_done[i])); HIPCHK(hipEventCreate(&c->ev_f0[i]));
         HIPCHK(hipEventCreate(&c->ev_lk0[i])); HIPCHK(hipEventCreate(&c->ev_lk1[i]));
@@ -265,6 +269,7 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->h_upload) (void)hipHostFree(c->h_upload);
     if (c->h_results) (void)hipHostFree(c->h_results);
     if (c->h_ptrs) (void)hipHostFree((void*)c->h_ptrs);
+    if (c->h_act) (void)hipHostFree(c->h_act);
     for (int i = 0; i < SVO_RING; i++) {
         if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
         if (c->ev_f0[i]) (void)hipEventDestroy(c->ev_f0[i]);
@@ -308,21 +313,37 @@ extern "C" int svo_set_projection(svo_context* c, int seq, const float Pl[12], c
 }
 
 static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp);
+                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active = nullptr);
 
 // The launch list of one frame (vo.cpp:41-137 as kernels), between the pointer-table upload and the result download.
 // with_events: record the stage-boundary events (not inside a graph capture).
-static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, int shares = -1) {
+// n_act >= 0: a ragged frame — only the n_act sequences listed in the slot's row of h_act take it (its grids cover those alone,
+// through DevBuffers::act); the row is copied to the device on the stream of the frame's first kernel.
+static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, int shares = -1, int n_act = -1) {
     DevBuffers& d = c->d;
     const int B = d.B;
     hipStream_t s = c->stream;
+    struct ActReset { DevBuffers& d; ~ActReset() { d.act = nullptr; d.n_act = 0; } } act_reset{d};   // other launches see an unmasked context
+    const size_t act_bytes = sizeof(int) * 2 * (size_t)B;
+    const int* h_act = c->h_act + (size_t)slot * 2 * B;
+    if (n_act >= 0) { d.act = c->d_act + (size_t)slot * 2 * B; d.n_act = n_act; }
+    if (d.act && n_act == 0) {                                         // all idle: the result rows are the whole frame
+        HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, s));
+        if (with_events) { HIPCHK(hipEventRecord(c->ev_pyr[slot], s)); HIPCHK(hipEventRecord(c->ev_lk0[slot], s)); HIPCHK(hipEventRecord(c->ev_lk1[slot], s)); HIPCHK(hipEventRecord(c->ev_tri[slot], s)); }
+        launch_frame_end(d, slot, s);
+        c->begin_recorded = false;
+        return SVO_OK;
+    }
     static const bool force_lean = getenv("SVO_FORCE_LEAN") && atoi(getenv("SVO_FORCE_LEAN")) != 0;      // test knob: every context takes them
     const bool shares_device = shares < 0 ? lk_gated(c) : shares != 0;   // read once per frame: both uses below see the same answer
     d.co_resident = (shares_device || force_lean) ? 1 : 0;             // picks the 96-register builds of the f64 kernels (svo_kernels_pnp.hip)
     const uint8_t** dp = d.img_ptrs + (size_t)slot * 2 * B;         // the slot's pointer table: pinned host memory the kernel reads in place
-    if (launch_front_fused(d, dp, stride, s)) {                        // lone stream: ingest + pyramid beside detection, two launches
+    const bool ahead = !c->capturing && ingest_ahead_applies(d);
+    if (d.act && !ahead) HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, s));
+    if (!ahead && launch_front_fused(d, dp, stride, s)) {              // lone stream: ingest + pyramid beside detection, two launches
         if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));   // stage timers: ms[0] = the fused front, ms[1] ~ 0
-    } else if (!c->capturing && ingest_ahead_applies(d)) {
+        c->begin_recorded = false;
+    } else if (ahead) {
         // Many sequences: this frame's pyramids are built on the IMAGE stream, which only waits for the previous frame's reset — so,
         // with frames in flight, they are built while the previous frame sits in its LK kernel.  That kernel fills six of a SIMD's
         // eight wave slots and 480 of its 512 registers (svo_kernels_lk.hip): the ingest, pyramid and border kernels (11-17
@@ -333,7 +354,14 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
             for (int i = 0; i < SVO_RING; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_img[i], hipEventDisableTiming));
         }
         if (c->begin_recorded) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));   // the fields k_pick_next reads are those of the frame in flight
+        else if (c->inflight > 0) {
+            // the frame in flight did not come this way (a replayed graph, an all-idle frame): ev_begin does not mark its reset, so
+            // k_pick_next could read its slot fields before its reset and pick the slot that frame is building — wait for all of it
+            HIPCHK(hipEventRecord(c->ev_begin, s));
+            HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));
+        }
         if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_f0[slot], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
+        if (d.act) HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, c->img_stream));
         launch_ingest_pyramid_ahead(d, dp, stride, c->img_stream);
         HIPCHK(hipEventRecord(c->ev_img[slot], c->img_stream));
         HIPCHK(hipStreamWaitEvent(s, c->ev_img[slot], 0));
@@ -344,6 +372,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         launch_detect(d, 1, -1, s);
     } else {
         launch_ingest_pyramid(d, dp, stride, s, true);                // + the per-frame reset
+        c->begin_recorded = false;
         if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));
         launch_detect(d, 0, -1, s);
         launch_detect(d, 1, -1, s);
@@ -373,13 +402,39 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     return SVO_OK;
 }
 
-// Enqueue one frame for all sequences.  ptrs: host array [2][B] of DEVICE image pointers.
-static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride) {
+// Ragged-frame arguments: every active sequence needs both image pointers (an idle one's are never read, and the arrays themselves
+// may be NULL when no sequence is active).  *n_act = number of active sequences.
+static int check_active(const svo_context* c, const uint8_t* const* left, const uint8_t* const* right, const uint8_t* active, int* n_act) {
+    const int B = c->d.B;
+    int n = 0;
+    for (int i = 0; i < B; i++) {
+        if (active && !active[i]) continue;
+        if (!left || !right || !left[i] || !right[i]) return fail_arg("null image pointer for an active sequence");
+        n++;
+    }
+    *n_act = n;
+    return SVO_OK;
+}
+
+// Enqueue one frame.  ptrs: host arrays of B DEVICE image pointers.  active: NULL (every sequence takes the frame) or B flags,
+// checked by check_active; a mask with every flag set is the unmasked frame.
+static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
+                         const uint8_t* active = nullptr) {
     if (c->inflight >= SVO_RING) { g_err = "too many frames in flight (collect first)"; return SVO_ERR_STATE; }
     DevBuffers& d = c->d;
     const int slot = c->head, B = d.B;
     const uint8_t** hp = c->h_ptrs + (size_t)slot * 2 * B;
-    for (int i = 0; i < B; i++) { hp[i] = left_dev[i]; hp[B + i] = right_dev[i]; }
+    int n_act = -1;                                                  // -1: unmasked
+    if (active) {
+        int* ha = c->h_act + (size_t)slot * 2 * B;                   // free: the slot's previous frame has been collected
+        int n = 0;
+        for (int i = 0; i < B; i++) { ha[B + i] = active[i] ? 1 : 0; if (active[i]) ha[n++] = i; }
+        if (n < B) n_act = n;
+    }
+    for (int i = 0; i < B; i++) {
+        const bool on = !active || active[i];
+        hp[i] = on ? left_dev[i] : nullptr; hp[B + i] = on ? right_dev[i] : nullptr;
+    }
     hipStream_t s = c->stream;
     // LK grid sized from the last feature counts the host has seen (+30 %); the kernel strides, so an underestimate is only slower
     int gn = c->lk_grid;
@@ -390,7 +445,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     }
     HIPCHK(hipEventRecord(c->ev_f0[slot], s));
     bool replayed = false;
-    if (c->use_graph) {
+    if (c->use_graph && n_act < 0) {                                 // a ragged frame runs from the launch list
         // the captured launch list bakes in which builds of the f64 kernels run: a context captured while it had the device to
         // itself must be re-captured once another many-sequence context exists (and back), or it would keep the full-register
         // builds that cannot start beside the other's LK grid
@@ -414,9 +469,9 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
                 c->gexec[slot] = nullptr; c->use_graph = false;
             } else { c->g_stride[slot] = stride; c->g_gn[slot] = gn; c->g_co[slot] = co_now; }
         }
-        if (c->use_graph) { HIPCHK(hipGraphLaunch(c->gexec[slot], s)); replayed = true; }
+        if (c->use_graph) { HIPCHK(hipGraphLaunch(c->gexec[slot], s)); replayed = true; c->begin_recorded = false; }
     }
-    if (!replayed) { const int rc = issue_frame(c, slot, stride, gn, c->stage_timing); if (rc != SVO_OK) return rc; }
+    if (!replayed) { const int rc = issue_frame(c, slot, stride, gn, c->stage_timing, -1, n_act); if (rc != SVO_OK) return rc; }
     c->staged_slot[slot] = !replayed && c->stage_timing;
     c->staged_inputs = false;
     HIPCHK(hipEventRecord(c->ev_done[slot], s));
@@ -453,15 +508,39 @@ extern "C" int svo_submit_batch(svo_context* c, const uint8_t* const* left_dev, 
     return enqueue_frame(c, left_dev, right_dev, stride);
 }
 
+extern "C" int svo_submit_batch_masked(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
+                                       const uint8_t* active) {
+    if (!c) return fail_arg("null context");
+    if (!active) return svo_submit_batch(c, left_dev, right_dev, stride);
+    if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
+    if (stride < c->d.geom.W * c->d.CN) return fail_arg("stride < width * channels");
+    int n_act = 0, rc;
+    if ((rc = check_active(c, left_dev, right_dev, active, &n_act)) != SVO_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    return enqueue_frame(c, left_dev, right_dev, stride, active);
+}
+
+extern "C" int svo_reset_sequence(svo_context* c, int seq, const float Pl[12], const float Pr[12]) {
+    if (!c) return fail_arg("null context");
+    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if ((Pl == nullptr) != (Pr == nullptr)) return fail_arg("Pl and Pr must both be given or both be NULL");
+    HIPCHK(hipSetDevice(c->device));
+    SeqProjection p = {};
+    if (Pl) { memcpy(p.Pl, Pl, sizeof(p.Pl)); memcpy(p.Pr, Pr, sizeof(p.Pr)); p.set = 1; }
+    launch_reset_seq(c->d, seq, p, c->stream);                       // behind every frame submitted so far, before every later one
+    HIPCHK(hipGetLastError());
+    if (Pl && seq < 0) c->projection_set = true;
+    return SVO_OK;
+}
+
 extern "C" int svo_collect(svo_context* c, double* T_out, int* ok_out, svo_frame_stats* stats) {
     if (!c) return fail_arg("null context");
     HIPCHK(hipSetDevice(c->device));
     return collect_frame(c, T_out, ok_out, stats);
 }
 
-extern "C" int svo_process_batch(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                                 int images_on_device, double* T_out, int* ok_out, svo_frame_stats* stats) {
-    if (!c || !left || !right) return fail_arg("null argument");
+static int process_batch(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                         int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats) {
     if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
     if (stride < c->d.geom.W * c->d.CN) return fail_arg("stride < width * channels");
     if (c->inflight != 0) { g_err = "svo_process_batch with frames in flight"; return SVO_ERR_STATE; }
@@ -469,16 +548,31 @@ extern "C" int svo_process_batch(svo_context* c, const uint8_t* const* left, con
     const int W = c->d.geom.W;
     int rc;
     if (images_on_device) {
-        rc = enqueue_frame(c, left, right, stride);
+        rc = enqueue_frame(c, left, right, stride, active);
     } else {
         // the caller's buffers are only borrowed for the duration of the call: copy to the device first (SURVEY.md §8b "Ownership")
         const size_t rowb = (size_t)W * c->d.CN;
         std::vector<const uint8_t*> lp, rp;
-        if ((rc = stage_host_images(c, left, right, stride, lp, rp)) != SVO_OK) return rc;
-        rc = enqueue_frame(c, lp.data(), rp.data(), (int)rowb);
+        if ((rc = stage_host_images(c, left, right, stride, lp, rp, active)) != SVO_OK) return rc;
+        rc = enqueue_frame(c, lp.data(), rp.data(), (int)rowb, active);
     }
     if (rc != SVO_OK) return rc;
     return collect_frame(c, T_out, ok_out, stats);
+}
+
+extern "C" int svo_process_batch(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                                 int images_on_device, double* T_out, int* ok_out, svo_frame_stats* stats) {
+    if (!c || !left || !right) return fail_arg("null argument");
+    return process_batch(c, left, right, stride, images_on_device, nullptr, T_out, ok_out, stats);
+}
+
+extern "C" int svo_process_batch_masked(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                                        int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats) {
+    if (!c) return fail_arg("null context");
+    if (!active) return svo_process_batch(c, left, right, stride, images_on_device, T_out, ok_out, stats);
+    int n_act = 0, rc;
+    if ((rc = check_active(c, left, right, active, &n_act)) != SVO_OK) return rc;
+    return process_batch(c, left, right, stride, images_on_device, active, T_out, ok_out, stats);
 }
 
 extern "C" int svo_process(svo_context* c, const uint8_t* left, const uint8_t* right, int stride, double T_out[16], svo_frame_stats* stats) {
@@ -507,8 +601,9 @@ extern "C" void svo_free_pinned(void* p) { if (p) (void)hipHostFree(p); }
 // Host images -> pinned staging -> device staging (one contiguous H2D copy); fills lp / rp with the device addresses.
 // Images that already live in page-locked memory with packed rows skip the staging copy: the DMA reads them in place (the call
 // is synchronous, the caller's buffer outlives it) — 40 us of host memcpy less per KITTI-sized pair on the single-stream path.
+// active (ragged frame): idle sequences' images are not read (their pointers may be NULL; their staging areas keep old bytes).
 static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp) {
+                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active) {
     const int B = c->d.B, W = c->d.geom.W, H = c->d.geom.H;
     const size_t rowb = (size_t)W * c->d.CN, img = rowb * H;
     if (!c->staging) HIPCHK(hipMalloc((void**)&c->staging, img * 2 * B));
@@ -521,10 +616,15 @@ static int stage_host_images(svo_context* c, const uint8_t* const* left, const u
     for (int cam = 0; cam < 2; cam++) {
         const uint8_t* const* src = cam ? right : left;
         bool all_direct = (size_t)stride == rowb;
-        for (int i = 0; i < B && all_direct; i++) { if (!src[i]) return fail_arg("null image pointer"); all_direct = host_pointer_is_pinned(src[i]); }
-        for (int i = 0; i < B; i++) {
+        for (int i = 0; i < B && all_direct; i++) {
+            if (active && !active[i]) continue;
             if (!src[i]) return fail_arg("null image pointer");
+            all_direct = host_pointer_is_pinned(src[i]);
+        }
+        for (int i = 0; i < B; i++) {
             (cam ? rp : lp)[i] = c->staging + img * (cam * B + i);
+            if (active && !active[i]) continue;
+            if (!src[i]) return fail_arg("null image pointer");
             if (all_direct) {
                 HIPCHK(hipMemcpyAsync(c->staging + img * (cam * B + i), src[i], img, hipMemcpyHostToDevice, c->stream));
                 continue;

@@ -91,7 +91,16 @@ struct DevBuffers {
     const double* lm_lambda;                   // [33] 10^k, k = -16..16 (the damping factors CvLevMarq can reach), computed on the host
     FrameResult* results;                      // [SVO_RING][B]
     const uint8_t** img_ptrs;                  // [SVO_RING][2][B] source image pointers: pinned host memory, read in place
+    // Ragged frames (svo_*_batch_masked): act[0 .. n_act) lists the sequences that take the frame, act[B + seq] is the flag of every
+    // sequence (k_frame_end writes the idle rows from it) — the frame's row of a device [SVO_RING][2 B] buffer.  nullptr: every
+    // sequence takes it, and the grids are those of the unmasked calls.
+    const int* act; int n_act;
 };
+
+// The sequence of the b-th sequence slot of a launch (a block coordinate or a thread index): every per-sequence kernel maps its
+// sequence through this, and every grid's sequence dimension is launch_seqs() long.
+__device__ __forceinline__ int seq_of(const DevBuffers& d, int b) { return d.act ? d.act[b] : b; }
+__host__ __device__ inline int launch_seqs(const DevBuffers& d) { return d.act ? d.n_act : d.B; }
 
 // plane 0 of the pyramid of (sequence, slot, camera); plane k follows at + k * geom.pyr_bytes
 __host__ __device__ inline size_t pyr_index(const DevBuffers& d, int seq, int slot, int cam) {
@@ -121,6 +130,9 @@ void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right
 bool ingest_ahead_applies(const DevBuffers& d);
 void launch_ingest_pyramid_ahead(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride_bytes, hipStream_t s);
 void launch_frame_begin(const DevBuffers& d, hipStream_t s);
+// svo_reset_sequence (seq = -1: all): the constructor's fields, and the projection when `set`; stream-ordered, no host sync
+struct SeqProjection { float Pl[12], Pr[12]; int set; };
+void launch_reset_seq(const DevBuffers& d, int seq, const SeqProjection& p, hipStream_t s);
 void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s);   // pass 0: FAST_THRESHOLD, pass 1: /4 if needed; th_override >= 0 replaces it
 // grid_n = max features that can enter LK; early_out: a feature stops at its first pass with status 0 (frame pipeline) or runs all four (member call)
 bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out);   // false: no kernel built for this (window, channels, summation mode) — nothing ran

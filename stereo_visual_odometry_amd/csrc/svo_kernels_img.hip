@@ -42,10 +42,20 @@ __device__ __forceinline__ void frame_begin(SeqState& s, int t1 = -1) {
     s.stats = z;
 }
 
+// One thread per sequence of the context, idle ones included: an idle sequence (ragged frame, d.act[B + seq] == 0) gets the row
+// of a frame it did not take — its last good transform, ok 0, zero counters, fail_reason 5 — and nothing of its state is written.
 __global__ void k_frame_end(DevBuffers d, int ring_slot) {
     int seq = blockIdx.x * blockDim.x + threadIdx.x;
     if (seq >= d.B) return;
     SeqState& s = d.st[seq];
+    if (d.act && !d.act[d.B + seq]) {
+        FrameResult& r = d.results[(size_t)ring_slot * d.B + seq];
+        for (int i = 0; i < 16; i++) r.T[i] = s.last_T[i];
+        r.ok = 0;
+        svo_frame_stats z = {0, 0, 0, 0, 0, 0, 0, 5, 0, 0, 0};
+        r.stats = z;
+        return;
+    }
     s.slot_img_t0 = s.slot_t1;                                   // vo.cpp:48-49 / 74-75
     if (!s.active || s.n_lk > 0) s.slot_pyr_t0 = s.slot_t1;      // vo.cpp:50-53 / 231-232 (skipped on the early return :179-181)
     s.frame_id++;
@@ -71,7 +81,7 @@ void launch_frame_end(const DevBuffers& d, int ring_slot, hipStream_t st) {
 // vo.cpp:74-75 / the level-0 copy of cv::buildOpticalFlowPyramid).  One thread = 4 pixels of a row.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ingest(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
-    const int seq = blockIdx.z, cam = blockIdx.y;
+    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
     const int W = d.geom.W, H = d.geom.H;
     const int quads_per_row = (W + 3) >> 2;
     const int total = quads_per_row * H;
@@ -92,7 +102,7 @@ __global__ __launch_bounds__(256) void k_ingest(DevBuffers d, const uint8_t* con
 // Colour form: interleaved BGR rows -> three planes (level 0 of the three per-plane pyramids) and, for the left camera, the
 // W x H byte image made of the first W bytes of every row, which is what cv::FAST scans in a 3-channel Mat.
 __global__ __launch_bounds__(256) void k_ingest_bgr(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
-    const int seq = blockIdx.z, cam = blockIdx.y;
+    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
     const int W = d.geom.W, H = d.geom.H;
     const int total = W * H;
     const uint8_t* src = srcs[cam * d.B + seq];
@@ -115,12 +125,12 @@ __global__ __launch_bounds__(256) void k_ingest_bgr(DevBuffers d, const uint8_t*
 void launch_ingest(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st, bool begin_frame) {
     if (d.CN == 3) {
         int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
-        hipLaunchKernelGGL(k_ingest_bgr, dim3(gx, 2, d.B), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
+        hipLaunchKernelGGL(k_ingest_bgr, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
         return;
     }
     int total = ((d.geom.W + 3) >> 2) * d.geom.H;
     int gx = (total + 255) / 256; if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(k_ingest, dim3(gx, 2, d.B), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
+    hipLaunchKernelGGL(k_ingest, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -132,7 +142,7 @@ void launch_ingest(const DevBuffers& d, const uint8_t* const* left_right_dev_ptr
 #define PD_TH 8
 __global__ __launch_bounds__(256) void k_pyrdown(DevBuffers d, int level, int ahead) {
     const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;          // every colour plane is its own pyramid
-    const int seq = sc / 2, cam = sc & 1;
+    const int seq = seq_of(d, sc / 2), cam = sc & 1;
     const LevelInfo ls = d.geom.lv[level - 1], ld = d.geom.lv[level];
     uint8_t* base = d.pyr + pyr_index(d, seq, ahead ? d.st[seq].slot_next : d.st[seq].slot_t1, cam) + (size_t)plane * d.geom.pyr_bytes;
     const uint8_t* src = base + ls.off;
@@ -184,7 +194,7 @@ __global__ __launch_bounds__(256) void k_pyrdown(DevBuffers d, int level, int ah
 // 0.68 ms per 512 sequences = 1.6 TB/s), not by LDS or HBM; four times the work per block and half the halo.
 template <int TW, int TH>
 static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, const uint8_t* const* srcs, int stride, int begin_frame, int bx, int by, int bz) {
-    const int seq = bz >> 1, cam = bz & 1;
+    const int seq = seq_of(d, bz >> 1), cam = bz & 1;
     const LevelInfo ls = d.geom.lv[0], ld = d.geom.lv[1];
     const uint8_t* src = srcs[cam * d.B + seq];
     // begin_frame: 0 = into the T1 slot as it stands (stage entry points), 1 = the frame pipeline's own ingest (free slot + the per-frame
@@ -261,10 +271,10 @@ __global__ __launch_bounds__(256) void k_ingest_pyr1(DevBuffers d, const uint8_t
 }
 static void launch_ingest_pyr1(const DevBuffers& d, const uint8_t* const* ptrs, int stride, int begin_frame, hipStream_t st) {
     if (d.B > SVO_LONE_MAX_SEQ) {
-        dim3 g((d.geom.lv[1].w + IG_TW - 1) / IG_TW, (d.geom.lv[1].h + IG_TH - 1) / IG_TH, d.B * 2);
+        dim3 g((d.geom.lv[1].w + IG_TW - 1) / IG_TW, (d.geom.lv[1].h + IG_TH - 1) / IG_TH, launch_seqs(d) * 2);
         hipLaunchKernelGGL((k_ingest_pyr1<IG_TW, IG_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
     } else {
-        dim3 g((d.geom.lv[1].w + PD_TW - 1) / PD_TW, (d.geom.lv[1].h + PD_TH - 1) / PD_TH, d.B * 2);
+        dim3 g((d.geom.lv[1].w + PD_TW - 1) / PD_TW, (d.geom.lv[1].h + PD_TH - 1) / PD_TH, launch_seqs(d) * 2);
         hipLaunchKernelGGL((k_ingest_pyr1<PD_TW, PD_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
     }
 }
@@ -277,7 +287,7 @@ static void launch_ingest_pyr1(const DevBuffers& d, const uint8_t* const* ptrs, 
 #define P2_TH 8
 static __device__ __forceinline__ void pyrdown2_body(const DevBuffers& d, int level, int bx, int by, int bz, int ahead = 0) {
     const int plane = bz % d.CN, sc = bz / d.CN;
-    const int seq = sc / 2, cam = sc & 1;
+    const int seq = seq_of(d, sc / 2), cam = sc & 1;
     const LevelInfo ls = d.geom.lv[level], lm = d.geom.lv[level + 1], ld = d.geom.lv[level + 2];
     uint8_t* base = d.pyr + pyr_index(d, seq, ahead ? d.st[seq].slot_next : d.st[seq].slot_t1, cam) + (size_t)plane * d.geom.pyr_bytes;
     const uint8_t* src = base + ls.off;
@@ -360,7 +370,7 @@ __global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, int a
 // launches, so their time is whole-job time.)
 __global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, int ahead) {
     const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;
-    const int seq = sc / 2, cam = sc & 1, level = blockIdx.y;
+    const int seq = seq_of(d, sc / 2), cam = sc & 1, level = blockIdx.y;
     const LevelInfo L = d.geom.lv[level];
     const int P = d.geom.pad, w = L.w, h = L.h;
     uint8_t* img = d.pyr + pyr_index(d, seq, ahead ? d.st[seq].slot_next : d.st[seq].slot_t1, cam) + (size_t)plane * d.geom.pyr_bytes + L.off;
@@ -385,7 +395,7 @@ static void launch_pad_pyramid_into(const DevBuffers& d, hipStream_t st, int ahe
     const LevelInfo& L0 = d.geom.lv[0];
     const int P = d.geom.pad, ring0 = 2 * P * (L0.w + 2 * P) + 2 * P * L0.h;
     int gx = (ring0 + 4 * 256 - 1) / (4 * 256); if (gx < 1) gx = 1; if (gx > 64) gx = 64;      // ~one border dword per thread at level 0 (the smaller levels stride less)
-    hipLaunchKernelGGL(k_pad_pyramid, dim3(gx, d.geom.nlevels, d.B * 2 * d.CN), dim3(256), 0, st, d, ahead);
+    hipLaunchKernelGGL(k_pad_pyramid, dim3(gx, d.geom.nlevels, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, ahead);
 }
 void launch_pad_pyramid(const DevBuffers& d, hipStream_t st) { launch_pad_pyramid_into(d, st, 0); }
 
@@ -394,11 +404,11 @@ static void launch_pyramid_from(const DevBuffers& d, int first, hipStream_t st, 
     int l = first;
     while (l < d.geom.nlevels) {
         if (l + 1 < d.geom.nlevels) {
-            dim3 g((d.geom.lv[l + 1].w + P2_TW - 1) / P2_TW, (d.geom.lv[l + 1].h + P2_TH - 1) / P2_TH, d.B * 2 * d.CN);
+            dim3 g((d.geom.lv[l + 1].w + P2_TW - 1) / P2_TW, (d.geom.lv[l + 1].h + P2_TH - 1) / P2_TH, launch_seqs(d) * 2 * d.CN);
             hipLaunchKernelGGL(k_pyrdown2, g, dim3(256), 0, st, d, l - 1, ahead);
             l += 2;
         } else {
-            dim3 g((d.geom.lv[l].w + PD_TW - 1) / PD_TW, (d.geom.lv[l].h + PD_TH - 1) / PD_TH, d.B * 2 * d.CN);
+            dim3 g((d.geom.lv[l].w + PD_TW - 1) / PD_TW, (d.geom.lv[l].h + PD_TH - 1) / PD_TH, launch_seqs(d) * 2 * d.CN);
             hipLaunchKernelGGL(k_pyrdown, g, dim3(256), 0, st, d, l, ahead);
             l += 1;
         }
@@ -421,25 +431,50 @@ void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right
 // k_pick_next: one thread per sequence names the slot (a single decision per sequence: the blocks of the ingest that follows must
 // all write the same one, whatever k_frame_end of the frame in flight does to the fields meanwhile).
 __global__ void k_pick_next(DevBuffers d) {
-    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seq < d.B) d.st[seq].slot_next = next_slot(d.st[seq]);
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
+    d.st[seq].slot_next = next_slot(d.st[seq]);
 }
 __global__ void k_frame_begin(DevBuffers d) {
-    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seq < d.B) frame_begin(d.st[seq], d.st[seq].slot_next);
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
+    frame_begin(d.st[seq], d.st[seq].slot_next);
 }
 bool ingest_ahead_applies(const DevBuffers& d) {
     static const bool off = getenv("SVO_INGEST_AHEAD") && atoi(getenv("SVO_INGEST_AHEAD")) == 0;
     return !off && d.B > SVO_LONE_MAX_SEQ && d.CN == 1 && d.geom.nlevels >= 2;
 }
 void launch_ingest_pyramid_ahead(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st) {
-    hipLaunchKernelGGL(k_pick_next, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_pick_next, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
     launch_ingest_pyr1(d, left_right_dev_ptrs, stride, 2, st);
     launch_pyramid_from(d, 2, st, 1);
     launch_pad_pyramid_into(d, st, 1);
 }
 void launch_frame_begin(const DevBuffers& d, hipStream_t st) {
-    hipLaunchKernelGGL(k_frame_begin, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_frame_begin, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
+}
+
+// svo_reset_sequence: the fields the constructor sets (vo.h:266-268, svo_api.hip ctx_create) and nothing else — frame_id = 0 makes
+// the next frame a first frame, whose reset picks its T1 slot afresh.  The slot fields stay as they are: the image stream's
+// k_pick_next of a frame in flight may read them while this runs.  The matrices come by value (no staging, no host sync).
+__global__ void k_reset_seq(DevBuffers d, int seq0, int n, SeqProjection p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    SeqState& s = d.st[seq0 + i];
+    s.frame_id = 0; s.n_feat = 0;
+    for (int k = 0; k < 9; k++) s.R[k] = (k % 4 == 0);
+    for (int k = 0; k < 3; k++) s.t[k] = 0.;
+    for (int k = 0; k < 16; k++) s.last_T[k] = (k % 5 == 0);
+    if (p.set) {
+        for (int k = 0; k < 12; k++) { s.Pl[k] = p.Pl[k]; s.Pr[k] = p.Pr[k]; }
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) s.K[3 * r + c] = p.Pl[4 * r + c];   // K = Pl[:, :3] (vo.cpp:16-25)
+    }
+}
+void launch_reset_seq(const DevBuffers& d, int seq, const SeqProjection& p, hipStream_t st) {
+    const int s0 = seq < 0 ? 0 : seq, n = seq < 0 ? d.B : 1;
+    hipLaunchKernelGGL(k_reset_seq, dim3((n + 63) / 64), dim3(64), 0, st, d, s0, n, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -538,7 +573,7 @@ static __device__ __forceinline__ void fast_body(const uint8_t* img_single, int 
     __shared__ uint8_t sc[FT_SH][FT_SW + 2];
     __shared__ unsigned short cand[FT_SH * FT_SW];               // screened pixels of the tile (order is irrelevant)
     __shared__ int ncand;
-    const int seq = bz;
+    const int seq = MODE == 1 ? 0 : seq_of(d, bz);
     int W, H, istride; const uint8_t* img;                       // istride: row pitch of img (a pyramid level 0 carries its border)
     if (MODE != 1) {
         const SeqState& s = d.st[seq];
@@ -634,7 +669,7 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* img_single, int w_s
 // critical chain just to look at do_second and leave; here a sequence gets FAST_STRIDED_BLOCKS blocks that walk its tiles.
 #define FAST_STRIDED_BLOCKS 32
 __global__ __launch_bounds__(256) void k_fast_strided(DevBuffers d, int pass, int threshold, int fx, int fy) {
-    const SeqState& s = d.st[blockIdx.z];
+    const SeqState& s = d.st[seq_of(d, blockIdx.z)];
     if (pass == 0 ? !(s.frame_id > 0) : !s.do_second) return;
     for (int t = blockIdx.x; t < fx * fy; t += gridDim.x) {
         fast_body<0>(nullptr, 0, 0, nullptr, d, pass, threshold, t % fx, t / fx, blockIdx.z, fx, fy);
@@ -697,7 +732,8 @@ void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* 
 // pass kept too few features (vo.cpp:327) that last block also offers the new set to the grid for the second pass.
 #define EMIT_THREADS 256
 #define EMIT_WAVES (EMIT_THREADS / 64)
-static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int pass, int row, int seq, int n_rows) {
+static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int pass, int row, int b, int n_rows) {
+    const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (pass == 0 ? !s.active : !s.do_second) return;
     __shared__ int sh_before[EMIT_WAVES], sh_all[EMIT_WAVES], sh_cnt[EMIT_WAVES], sh_last;
@@ -773,7 +809,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit(DevBuffers d, int 
 // k_fast_strided): the ticket still counts ROWS, so the block that finishes the last row publishes
 #define EMIT_STRIDED_BLOCKS 8
 __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_strided(DevBuffers d, int pass, int n_rows) {
-    const SeqState& s = d.st[blockIdx.y];
+    const SeqState& s = d.st[seq_of(d, blockIdx.y)];
     if (pass == 0 ? !s.active : !s.do_second) return;
     for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
         bucket_emit_body(d, pass, row, blockIdx.y, n_rows);
@@ -805,12 +841,13 @@ __global__ __launch_bounds__(256) void k_front_b(DevBuffers d, int px, int py, i
 bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st) {
     static const bool off = getenv("SVO_FRONT_FUSED") && atoi(getenv("SVO_FRONT_FUSED")) == 0;
     if (off || d.B > SVO_LONE_MAX_SEQ || d.CN != 1 || d.geom.nlevels < 4 || d.cfg.features_per_bucket != 1) return false;
-    const int ax = (d.geom.lv[1].w + PD_TW - 1) / PD_TW, ay = (d.geom.lv[1].h + PD_TH - 1) / PD_TH, n_a = ax * ay * d.B * 2;
-    const int fx = (d.geom.W + FT_W - 1) / FT_W, fy = (d.geom.H + FT_H - 1) / FT_H, n_f = fx * fy * d.B;
+    const int ns = launch_seqs(d);
+    const int ax = (d.geom.lv[1].w + PD_TW - 1) / PD_TW, ay = (d.geom.lv[1].h + PD_TH - 1) / PD_TH, n_a = ax * ay * ns * 2;
+    const int fx = (d.geom.W + FT_W - 1) / FT_W, fy = (d.geom.H + FT_H - 1) / FT_H, n_f = fx * fy * ns;
     hipLaunchKernelGGL(k_front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
-    const int px = (d.geom.lv[3].w + P2_TW - 1) / P2_TW, py = (d.geom.lv[3].h + P2_TH - 1) / P2_TH, n_p = px * py * d.B * 2;
+    const int px = (d.geom.lv[3].w + P2_TW - 1) / P2_TW, py = (d.geom.lv[3].h + P2_TH - 1) / P2_TH, n_p = px * py * ns * 2;
     const int n_rows = d.cfg.buckets_along_height;
-    hipLaunchKernelGGL(k_front_b, dim3(n_p + n_rows * d.B), dim3(256), 0, st, d, px, py, n_p, n_rows);
+    hipLaunchKernelGGL(k_front_b, dim3(n_p + n_rows * ns), dim3(256), 0, st, d, px, py, n_p, n_rows);
     launch_pyramid_from(d, 4, st);                                    // a fifth level and beyond (cfg3)
     launch_pad_pyramid(d, st);
     launch_detect(d, 1, -1, st);                                      // the second pass exits at once unless needed (vo.cpp:327-332)
@@ -827,7 +864,7 @@ bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_de
 static __device__ __forceinline__ bool pass_runs(const SeqState& s, int pass) { return pass == 0 ? s.active : s.do_second; }
 
 __global__ void k_gen_row_count(DevBuffers d, int pass) {
-    const int seq = blockIdx.y, y = blockIdx.x, W = d.geom.W, H = d.geom.H;
+    const int seq = seq_of(d, blockIdx.y), y = blockIdx.x, W = d.geom.W, H = d.geom.H;
     if (!pass_runs(d.st[seq], pass)) return;
     const uint8_t* score = d.score + (size_t)seq * W * H;
     int cnt = 0;
@@ -836,8 +873,9 @@ __global__ void k_gen_row_count(DevBuffers d, int pass) {
     if (threadIdx.x == 0) d.kp_rows[(size_t)seq * H + y] = cnt;
 }
 __global__ void k_gen_scan_rows(DevBuffers d, int pass) {          // one lane per sequence; H is a few hundred
-    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seq >= d.B) return;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (!pass_runs(s, pass)) return;
     int* rows = d.kp_rows + (size_t)seq * d.geom.H;
@@ -847,7 +885,7 @@ __global__ void k_gen_scan_rows(DevBuffers d, int pass) {          // one lane p
     s.n_old = s.n_feat;
 }
 __global__ void k_gen_emit_candidates(DevBuffers d, int pass) {
-    const int seq = blockIdx.y, W = d.geom.W, H = d.geom.H;
+    const int seq = seq_of(d, blockIdx.y), W = d.geom.W, H = d.geom.H;
     const SeqState& s = d.st[seq];
     if (!pass_runs(s, pass)) return;
     const size_t co = (size_t)seq * d.KPCAP, fo = (size_t)seq * d.CAP;
@@ -873,7 +911,7 @@ __global__ void k_gen_emit_candidates(DevBuffers d, int pass) {
     }
 }
 __global__ void k_gen_bucket_walk(DevBuffers d, int pass) {
-    const int seq = blockIdx.y, b = blockIdx.x * blockDim.x + threadIdx.x;
+    const int seq = seq_of(d, blockIdx.y), b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= d.NB || !pass_runs(d.st[seq], pass)) return;
     const int baw = d.cfg.buckets_along_width, bah = d.cfg.buckets_along_height, per = d.cfg.features_per_bucket;
     const int cap = (b / baw) >= d.cfg.bucket_start_row ? per : 0;                     // feature_set.cpp:113-116
@@ -900,7 +938,7 @@ __global__ void k_gen_bucket_walk(DevBuffers d, int pass) {
 #define GEN_EMIT_THREADS 1024
 #define GEN_EMIT_WAVES (GEN_EMIT_THREADS / 64)
 __global__ __launch_bounds__(GEN_EMIT_THREADS) void k_gen_bucket_emit(DevBuffers d, int pass) {
-    const int seq = blockIdx.x;
+    const int seq = seq_of(d, blockIdx.x);
     SeqState& s = d.st[seq];
     if (!pass_runs(s, pass)) return;
     __shared__ int wave_tot[GEN_EMIT_WAVES];
@@ -935,14 +973,14 @@ __global__ __launch_bounds__(GEN_EMIT_THREADS) void k_gen_bucket_emit(DevBuffers
     }
 }
 static void launch_detect_general(const DevBuffers& d, int pass, int th, hipStream_t st) {
-    const int W = d.geom.W, H = d.geom.H;
-    dim3 g((W + FT_W - 1) / FT_W, (H + FT_H - 1) / FT_H, d.B);
+    const int W = d.geom.W, H = d.geom.H, ns = launch_seqs(d);
+    dim3 g((W + FT_W - 1) / FT_W, (H + FT_H - 1) / FT_H, ns);
     hipLaunchKernelGGL(k_fast<2>, g, dim3(256), 0, st, (const uint8_t*)nullptr, 0, 0, (uint8_t*)nullptr, d, pass, th);
-    hipLaunchKernelGGL(k_gen_row_count, dim3(H, d.B), dim3(64), 0, st, d, pass);
-    hipLaunchKernelGGL(k_gen_scan_rows, dim3((d.B + 63) / 64), dim3(64), 0, st, d, pass);
-    hipLaunchKernelGGL(k_gen_emit_candidates, dim3(H + 1, d.B), dim3(64), 0, st, d, pass);
-    hipLaunchKernelGGL(k_gen_bucket_walk, dim3((d.NB + 255) / 256, d.B), dim3(256), 0, st, d, pass);
-    hipLaunchKernelGGL(k_gen_bucket_emit, dim3(d.B), dim3(GEN_EMIT_THREADS), 0, st, d, pass);
+    hipLaunchKernelGGL(k_gen_row_count, dim3(H, ns), dim3(64), 0, st, d, pass);
+    hipLaunchKernelGGL(k_gen_scan_rows, dim3((ns + 63) / 64), dim3(64), 0, st, d, pass);
+    hipLaunchKernelGGL(k_gen_emit_candidates, dim3(H + 1, ns), dim3(64), 0, st, d, pass);
+    hipLaunchKernelGGL(k_gen_bucket_walk, dim3((d.NB + 255) / 256, ns), dim3(256), 0, st, d, pass);
+    hipLaunchKernelGGL(k_gen_bucket_emit, dim3(ns), dim3(GEN_EMIT_THREADS), 0, st, d, pass);
 }
 
 void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t st) {
@@ -950,15 +988,16 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
     if (th_override >= 0) th = th_override;
     if (d.cfg.features_per_bucket > 1) { launch_detect_general(d, pass, th, st); return; }
     // pass 0: k_fast offers the existing tracks itself; pass 1 finds them offered (and n_old set) by the last block of pass 0's emit
-    dim3 g((d.geom.W + FT_W - 1) / FT_W, (d.geom.H + FT_H - 1) / FT_H, d.B);
+    const int ns = launch_seqs(d);
+    dim3 g((d.geom.W + FT_W - 1) / FT_W, (d.geom.H + FT_H - 1) / FT_H, ns);
     static const bool strided_off = getenv("SVO_SECOND_PASS_STRIDED") && atoi(getenv("SVO_SECOND_PASS_STRIDED")) == 0;
     if (pass == 1 && d.B > SVO_LONE_MAX_SEQ && !strided_off) {
-        hipLaunchKernelGGL(k_fast_strided, dim3(FAST_STRIDED_BLOCKS, 1, d.B), dim3(256), 0, st, d, pass, th, (int)g.x, (int)g.y);
-        hipLaunchKernelGGL(k_bucket_emit_strided, dim3(EMIT_STRIDED_BLOCKS, d.B), dim3(EMIT_THREADS), 0, st, d, pass, d.cfg.buckets_along_height);
+        hipLaunchKernelGGL(k_fast_strided, dim3(FAST_STRIDED_BLOCKS, 1, ns), dim3(256), 0, st, d, pass, th, (int)g.x, (int)g.y);
+        hipLaunchKernelGGL(k_bucket_emit_strided, dim3(EMIT_STRIDED_BLOCKS, ns), dim3(EMIT_THREADS), 0, st, d, pass, d.cfg.buckets_along_height);
         return;
     }
     hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, (const uint8_t*)nullptr, 0, 0, (uint8_t*)nullptr, d, pass, th);
-    hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, d.B), dim3(EMIT_THREADS), 0, st, d, pass);
+    hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, ns), dim3(EMIT_THREADS), 0, st, d, pass);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1024,7 +1063,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_compact(DevBuffers d) {
     // survivor its rank inside the wave, LDS the survivors of the lower waves, a running total those of the earlier rounds — the
     // output keeps the input order (order is semantics: RANSAC samples rows).  (Round 1: 256 threads x a serial chunk of 8
     // tracks each, two passes of dependent loads: 19 us at one sequence.)
-    const int seq = blockIdx.x;
+    const int seq = seq_of(d, blockIdx.x);
     SeqState& s = d.st[seq];
     if (!s.active) return;
     __shared__ int sh_cnt[SCAN_WAVES], sh_c[SCAN_WAVES];
@@ -1091,7 +1130,7 @@ void launch_compact(const DevBuffers& d, hipStream_t st) {
     // tail of an LK grid, the image stream's kernels of a many-sequence context — that moment comes late: traces show this kernel
     // waiting 0.8-1.6 ms for 20 us of work.  Many-sequence contexts launch it with 256 threads (four times the rounds, no waiting).
     const int threads = d.B > SVO_LONE_MAX_SEQ ? 256 : SCAN_THREADS;
-    hipLaunchKernelGGL(k_compact, dim3(d.B), dim3(threads), 0, st, d);
+    hipLaunchKernelGGL(k_compact, dim3(launch_seqs(d)), dim3(threads), 0, st, d);
 }
 
 // findClosePoints (vo.cpp:265-280) as a stand-alone stage

@@ -777,8 +777,9 @@ template <int W, int CN, bool FS> constexpr int lk_min_waves() { return (W == 21
 template <int W, int CN, bool FS>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(LK_MIN_WAVES(W, CN, FS)))) void k_lk_chain(DevBuffers d, int slots, int chunk, int early_out) {
     __shared__ __attribute__((aligned(16))) int fs_lds[FS ? LkFs<W, CN>::LDS_INTS : 1];            // float-sums mode only (the default build uses no LDS)
-    const int seq = blockIdx.x / slots, fb = blockIdx.x - seq * slots;
-    if (seq >= d.B) return;
+    const int b = blockIdx.x / slots, fb = blockIdx.x - b * slots;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (!s.active) return;
     int n = s.n_feat;
@@ -886,7 +887,7 @@ bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t st, int early_
     const int chunk = lk_chunk();
     int gx = grid_n > LK_MAX_GRID ? LK_MAX_GRID : grid_n;
     gx = (gx + 8 * chunk - 1) / (8 * chunk) * (8 * chunk);           // blocks per sequence: whole runs on every XCD
-    const unsigned blocks = (unsigned)gx * (unsigned)d.B;
+    const unsigned blocks = (unsigned)gx * (unsigned)launch_seqs(d);
     // false: no kernel is built for this window / channel count / summation mode; the caller reports it
     return lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) {
         hipLaunchKernelGGL((k_lk_chain<w, cn, fs>), dim3(blocks), dim3(64), 0, st, d, gx, chunk, early_out);

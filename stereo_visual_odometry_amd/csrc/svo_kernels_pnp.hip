@@ -121,7 +121,8 @@ static __device__ __forceinline__ void triangulate_point(const SeqState& s, floa
 }
 // spare: the last block (bx == nblocks - 1) draws the RANSAC subsets instead of triangulating (many-sequence contexts; a
 // lone stream's k_compact has drawn them already, and its triangulation shares a launch with the first EPnP chunk, k_tri_epnp)
-static __device__ __forceinline__ void triangulate_body(const DevBuffers& d, int lanes, int bx, int seq, int nblocks, bool spare) {
+static __device__ __forceinline__ void triangulate_body(const DevBuffers& d, int lanes, int bx, int by, int nblocks, bool spare) {
+    const int seq = seq_of(d, by);
     SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
     if (spare && bx == nblocks - 1) {
@@ -147,21 +148,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_tri
 void launch_triangulate(const DevBuffers& d, hipStream_t st) {
     const bool lean = d.co_resident;
     const int lanes = d.B > SVO_LONE_MAX_SEQ ? 64 : 16;
-    if (lean) hipLaunchKernelGGL(k_triangulate_lean, dim3((d.CAP + lanes - 1) / lanes + 1, d.B), dim3(64), 0, st, d, lanes);
-    else hipLaunchKernelGGL(k_triangulate, dim3((d.CAP + lanes - 1) / lanes + 1, d.B), dim3(64), 0, st, d, lanes);
+    if (lean) hipLaunchKernelGGL(k_triangulate_lean, dim3((d.CAP + lanes - 1) / lanes + 1, launch_seqs(d)), dim3(64), 0, st, d, lanes);
+    else hipLaunchKernelGGL(k_triangulate, dim3((d.CAP + lanes - 1) / lanes + 1, launch_seqs(d)), dim3(64), 0, st, d, lanes);
 }
 
 // (pnp_draw_subsets — cv::RNG + getSubset — lives in svo_internal.hpp: k_compact draws the first chunk for lone-stream contexts)
 // stand-alone launch for callers that enter at launch_pnp without a triangulation before it (svo_camera_to_world)
 __global__ void k_pnp_subsets(DevBuffers d) {
-    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seq >= d.B) return;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
     pnp_draw_subsets(d, s, seq, pnp_first_chunk(d));
 }
 void launch_pnp_subsets(const DevBuffers& d, hipStream_t st) {
-    hipLaunchKernelGGL(k_pnp_subsets, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_pnp_subsets, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
 }
 
 // ------------------------------------------------------------------------------------------------ EPnP on 5 points
@@ -612,8 +614,9 @@ static __device__ __attribute__((always_inline)) void epnp_branch(double* ar, in
 // OWN_TRI: the hypothesis triangulates its five points itself (lanes 0..4, the same triangulate_point, hence the same floats)
 // instead of reading d.world — so that the first chunk can share a launch with the triangulation of all tracks (k_tri_epnp).
 template <int G, bool OWN_TRI = false>    // lanes per hypothesis: 8 (six rotate a pair each) or 16 (twelve: two lanes per pair)
-static __device__ __forceinline__ void pnp_epnp_body(const DevBuffers& d, int h0, int h1, double* arena, int bx, int seq) {
+static __device__ __forceinline__ void pnp_epnp_body(const DevBuffers& d, int h0, int h1, double* arena, int bx, int by) {
     constexpr int HPB = 64 / G;
+    const int seq = seq_of(d, by);
     const SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
     int hend = h0 > 0 ? (s.pnp_need < h1 ? s.pnp_need : h1) : h1;
@@ -740,7 +743,7 @@ static __device__ __forceinline__ bool point_is_inlier(const double* Rt, double 
 }
 
 __global__ __launch_bounds__(256) void k_pnp_score(DevBuffers d, int h0, int h1) {
-    const int seq = blockIdx.y, h = h0 + blockIdx.x;
+    const int seq = seq_of(d, blockIdx.y), h = h0 + blockIdx.x;
     const SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
     if (h >= (h0 > 0 ? (s.pnp_need < h1 ? s.pnp_need : h1) : h1)) return;
@@ -818,8 +821,9 @@ static __device__ void chol_solve6(const double* A, const double* b, double* x) 
 // After the first chunk: run the accept / shrink rule over its counts and publish how many iterations the serial loop
 // could still reach (RANSACPointSetRegistrator::run: niters only decreases).
 __global__ void k_pnp_decide(DevBuffers d, int c0) {
-    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seq >= d.B) return;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
     const int K = d.K, n = s.n_tracks;
@@ -993,7 +997,7 @@ __device__ __forceinline__ void inverse_transform(const double* R, const double*
 
 template <int THREADS>
 static __device__ __forceinline__ void pnp_final_body(const DevBuffers& d) {
-    const int seq = blockIdx.x;
+    const int seq = seq_of(d, blockIdx.x);
     SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
     __shared__ LmShared sh;
@@ -1317,8 +1321,9 @@ static __device__ void p3p_align(const double (*M_end)[3], const double (*Xw)[3]
 
 // one thread per sequence; expects s.n_tracks == 4
 __global__ void k_pnp_p3p(DevBuffers d) {
-    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
-    if (seq >= d.B) return;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (!seq_live(s) || s.n_tracks != 4) return;
     const size_t o = (size_t)seq * d.CAP;
@@ -1369,7 +1374,7 @@ __global__ void k_pnp_p3p(DevBuffers d) {
     for (int i = 0; i < 4; i++) { d.inlier[o + i] = 1; d.inl_idx[o + i] = i; }
 }
 void launch_pnp_p3p(const DevBuffers& d, hipStream_t st) {
-    hipLaunchKernelGGL(k_pnp_p3p, dim3((d.B + 63) / 64), dim3(64), 0, st, d);
+    hipLaunchKernelGGL(k_pnp_p3p, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
 }
 
 // ---- getInverseTransform (vo.cpp:246-258) as its own one-thread launch, for the stage API ----
@@ -1386,7 +1391,7 @@ bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t st) {
     if (off || d.B > SVO_LONE_MAX_SEQ || d.co_resident) return false;
     const int lanes = 16, c0 = pnp_first_chunk(d), hpb = 64 / EP_G_LONE;
     const int n_e = (c0 + hpb - 1) / hpb, n_t = (d.CAP + lanes - 1) / lanes;
-    hipLaunchKernelGGL(k_tri_epnp, dim3(n_e + n_t, d.B), dim3(64), 0, st, d, lanes, n_e, c0);
+    hipLaunchKernelGGL(k_tri_epnp, dim3(n_e + n_t, launch_seqs(d)), dim3(64), 0, st, d, lanes, n_e, c0);
     return true;
 }
 
@@ -1402,17 +1407,17 @@ void launch_pnp(const DevBuffers& d, hipStream_t st, bool first_chunk_solved) {
             asked[dev] = true;
         }
     }
-    const int hpb = 64 / (lean ? EP_G : EP_G_LONE);
+    const int hpb = 64 / (lean ? EP_G : EP_G_LONE), ns = launch_seqs(d);
     if (first_chunk_solved) { /* k_tri_epnp did it */ }
-    else if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((c0 + hpb - 1) / hpb, d.B), dim3(64), EP_LEAN_LDS, st, d, 0, c0);
-    else hipLaunchKernelGGL(k_pnp_epnp, dim3((c0 + hpb - 1) / hpb, d.B), dim3(64), 0, st, d, 0, c0);
-    hipLaunchKernelGGL(k_pnp_score, dim3(c0, d.B), dim3(256), 0, st, d, 0, c0);
+    else if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((c0 + hpb - 1) / hpb, ns), dim3(64), EP_LEAN_LDS, st, d, 0, c0);
+    else hipLaunchKernelGGL(k_pnp_epnp, dim3((c0 + hpb - 1) / hpb, ns), dim3(64), 0, st, d, 0, c0);
+    hipLaunchKernelGGL(k_pnp_score, dim3(c0, ns), dim3(256), 0, st, d, 0, c0);
     if (d.K > c0) {
-        hipLaunchKernelGGL(k_pnp_decide, dim3((d.B + 63) / 64), dim3(64), 0, st, d, c0);
-        if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((d.K - c0 + hpb - 1) / hpb, d.B), dim3(64), EP_LEAN_LDS, st, d, c0, d.K);
-        else hipLaunchKernelGGL(k_pnp_epnp, dim3((d.K - c0 + hpb - 1) / hpb, d.B), dim3(64), 0, st, d, c0, d.K);
-        hipLaunchKernelGGL(k_pnp_score, dim3(d.K - c0, d.B), dim3(256), 0, st, d, c0, d.K);
+        hipLaunchKernelGGL(k_pnp_decide, dim3((ns + 63) / 64), dim3(64), 0, st, d, c0);
+        if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((d.K - c0 + hpb - 1) / hpb, ns), dim3(64), EP_LEAN_LDS, st, d, c0, d.K);
+        else hipLaunchKernelGGL(k_pnp_epnp, dim3((d.K - c0 + hpb - 1) / hpb, ns), dim3(64), 0, st, d, c0, d.K);
+        hipLaunchKernelGGL(k_pnp_score, dim3(d.K - c0, ns), dim3(256), 0, st, d, c0, d.K);
     }
-    if (lean) hipLaunchKernelGGL(k_pnp_final_lean, dim3(d.B), dim3(PF_THREADS_LEAN), 0, st, d);
-    else hipLaunchKernelGGL(k_pnp_final, dim3(d.B), dim3(PF_THREADS), 0, st, d);
+    if (lean) hipLaunchKernelGGL(k_pnp_final_lean, dim3(ns), dim3(PF_THREADS_LEAN), 0, st, d);
+    else hipLaunchKernelGGL(k_pnp_final, dim3(ns), dim3(PF_THREADS), 0, st, d);
 }

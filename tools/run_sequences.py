@@ -6,8 +6,8 @@ its own files when --no-gather is given).
   python tools/run_sequences.py --lengths 40,12,45,9 --out /tmp/poses            # 1 GPU, 4 batched sequences
   python -m torch.distributed.run --nproc-per-node 8 tools/run_sequences.py --lengths 4541,1101,4661,801,271,2761,1101,1101
 
-Sequences are synthetic KITTI-00-shaped renders (seed 0x5EED0040 + id); a sequence that has ended is fed its last
-frame again (its outputs are discarded) so the batch keeps advancing in lock-step."""
+Sequences are synthetic KITTI-00-shaped renders (seed 0x5EED0040 + id); a sequence that has ended sits out the remaining
+frames of the batch (svo_process_batch_masked: idle sequences launch no work), so only useful frame pairs are processed."""
 import argparse
 import os
 import sys
@@ -50,9 +50,10 @@ def main():
         vo = api.BatchVisualOdometry(args.width, args.height, len(mine), api.default_config(win_w=21, win_h=21, max_translation_norm=2.0), device=local_rank)
         vo.initalize_projection_matricies(Pl, Pr)
         for k in range(max(lengths[s] for s in mine)):
-            L = [q.left[min(k, q.n_frames - 1)] for q in seqs]
-            R = [q.right[min(k, q.n_frames - 1)] for q in seqs]
-            ok, T = vo.stereo_callback_batch(L, R)
+            active = [k < q.n_frames for q in seqs]
+            L = [q.left[k] if a else None for q, a in zip(seqs, active)]
+            R = [q.right[k] if a else None for q, a in zip(seqs, active)]
+            ok, T = vo.stereo_callback_batch(L, R, active=active)
             for i, s in enumerate(mine):
                 if k < lengths[s]:
                     streams[i][k, :16] = T[i].reshape(16); streams[i][k, 16] = ok[i]
