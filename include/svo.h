@@ -169,6 +169,56 @@ int svo_submit_batch_masked(svo_context* ctx, const uint8_t* const* left_dev, co
  * submitted later.  Does not synchronise, and is legal with frames in flight. */
 int svo_reset_sequence(svo_context* ctx, int seq, const float Pl[12], const float Pr[12]);
 
+/* ------------------------------------------------------------------------------------------------
+ * Rectification of raw frames — replaces what feeds the reference's left/image_rect and right/image_rect topics
+ * (src/stereo_vo.cpp:53-54): image_geometry::PinholeCameraModel::rectifyImage in stereo_image_proc, i.e.
+ * cv::initUndistortRectifyMap once per calibration + cv::remap per frame.  A rectifying context takes RAW frames (raw_w x raw_h
+ * pixels, rows `stride` bytes, channels as configured) in every frame entry point (svo_process, svo_process_batch[_masked],
+ * svo_submit_batch[_masked], svo_circular_matching); level 0 of every pyramid and the FAST image are the rectified frame
+ * (width x height of svo_create), so everything downstream sees exactly the bytes it would have seen had the caller passed
+ * the rectified images.  Without maps a context is plain and launches exactly what it always did.
+ *
+ * Map (per camera): for every rectified pixel (u, v), a source position in the raw image in fixed point with 5 fractional
+ * bits, ix = round_half_even(src_x * 32) (likewise iy) — OpenCV's CV_16SC2 + CV_16UC1 pair:
+ *   map1[v][u] = (ix >> 5, iy >> 5) as int16 x 2,   map2[v][u] = (iy & 31) * 32 + (ix & 31) as uint16 (masked to 10 bits).
+ * Interpolation (bilinear, 8-bit, per channel), x0 = ix >> 5, fx = ix & 31 (likewise y):
+ *   out = ((32-fx)(32-fy) p(x0,y0) + fx(32-fy) p(x0+1,y0) + (32-fx)fy p(x0,y0+1) + fx fy p(x0+1,y0+1) + 512) >> 10,
+ * a tap outside the raw image reads 0 (BORDER_CONSTANT, value 0).  This is cv::remap's INTER_LINEAR with INTER_BITS = 5 and
+ * 15-bit weights: each weight * 32768 is an exact multiple of 32, so the forms agree and no weight correction ever applies.
+ * PARITY UNPINNED: equality with cv::remap is believed, not measured (no OpenCV on the machines this was built on); the tests
+ * pin the kernels to a numpy restatement of the formula above, bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* A ROS sensor_msgs/CameraInfo, as far as rectification needs it.  D: plumb_bob (n_d = 5: k1 k2 p1 p2 k3) or
+ * rational_polynomial (n_d = 8: k1 k2 p1 p2 k3 k4 k5 k6); n_d = 0 or 4 are accepted too.  R, P row-major.  width x height is
+ * the RAW image size.  Thin-prism / tilt coefficients and the fisheye model are not covered: pass your own maps for those. */
+typedef struct {
+    double K[9];
+    double D[8];
+    int n_d;
+    double R[9];
+    double P[12];
+    int width, height;
+} svo_camera_info;
+
+/* Install maps for one sequence, or (seq = -1) the shared maps used by every sequence without maps of its own — stored once,
+ * not per sequence.  map1_*: width*height*2 int16, map2_*: width*height uint16 (the context's rectified size).  raw_w / raw_h are
+ * fixed per context: the first call sets them, later calls must match (SVO_ERR_ARG).  Stream-ordered like svo_reset_sequence:
+ * legal with frames in flight, takes effect from the next frame submitted — every frame carries its own map pointers, a
+ * replaced map is freed once no frame in flight names it.  The slot handover of a continuous pool is svo_reset_sequence(seq,
+ * Pl, Pr) + svo_set_rectification(seq, ...) before the next submit.  A frame in which an active sequence has no map (neither
+ * its own nor shared) fails with SVO_ERR_STATE.  Host images given to svo_process / svo_process_batch are read in place by the
+ * DMA engines when pinned with stride == raw_w * channels. */
+int svo_set_rectification_maps(svo_context* ctx, int seq, int raw_w, int raw_h, const int16_t* map1_l, const uint16_t* map2_l,
+                               const int16_t* map1_r, const uint16_t* map2_r);
+/* Convenience: builds both maps with svo_init_rectify_map (raw size = left->width x left->height; both must agree) and installs
+ * them as svo_set_rectification_maps does.  It does NOT call svo_set_projection: pass left->P / right->P there (as float).  ROS's
+ * P_right[0][3] = -fx * baseline is exactly the reference's negative bf term (stereo_vo.cpp:47). */
+int svo_set_rectification(svo_context* ctx, int seq, const svo_camera_info* left, const svo_camera_info* right);
+/* Back to a plain context (frames at the rectified size, no remap) from the next frame submitted; results are then bit-identical
+ * to a context that never had maps.  The raw size may be set afresh afterwards. */
+int svo_clear_rectification(svo_context* ctx);
+
 /* Introspection (parity tests): currentVOFeatures (vo.h:245) of one sequence, and the last frame's
  * compacted tracks.  Arrays may be NULL.  Returns the count or a negative status.  inlier[] is the is_ok vector of vo.cpp:115-119:
  * all zero when the frame failed before it was built (RANSAC failure or fewer inliers than features_threshold, vo.cpp:106-113). */
@@ -261,6 +311,22 @@ int svo_triangulate(int device, const float Pl[12], const float Pr[12], int n, c
 int svo_camera_to_world(int device, const float K[9], int n, const float* cam_pts, const float* world_pts,
                         double R[9], double t[3], int* inliers, int* n_inliers, int* success,
                         int ransac_iterations, float reproj_error, float confidence, int* iters_run);
+
+/* replaces: cv::initUndistortRectifyMap(K, D, R, P[:, :3], (w, h), CV_16SC2, map1, map2) (the map half of
+ * image_geometry::PinholeCameraModel::rectifyImage).  Host only, f64, no device needed.  The scalar loop restated exactly
+ * (no FMA contraction): iR = (P33 R)^-1 by the 3x3 adjugate / determinant; per row i: _x = i ir[1] + ir[2], _y = i ir[4] + ir[5],
+ * _w = i ir[7] + ir[8], stepped by += ir[0], ir[3], ir[6] per column; w = 1/_w, x = _x w, y = _y w; r2 = x^2 + y^2;
+ * kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2); xd = x kr + p1 2xy + p2 (r2 + 2x^2),
+ * yd = y kr + p1 (r2 + 2y^2) + p2 2xy; u = fx xd + cx, v = fy yd + cy; ix = round_half_even(32 u) (likewise iy; outside the
+ * int32 range: INT_MIN, as cvRound).  R NULL = identity, P NULL = K.  map1: w*h*2 int16, map2: w*h uint16. */
+int svo_init_rectify_map(const double K[9], const double* D, int n_d, const double R[9], const double P[12], int w, int h,
+                         int16_t* map1, uint16_t* map2);
+
+/* replaces: cv::remap(raw, out, map1, map2, INTER_LINEAR, BORDER_CONSTANT, 0) (the per-frame half of rectifyImage): the remap
+ * of the rectification section alone, on the kernel's device function.  out: w*h*channels bytes, packed; raw rows raw_stride
+ * bytes apart; channels 1 or 3 (interleaved). */
+int svo_rectify_image(int device, const int16_t* map1, const uint16_t* map2, int w, int h, const uint8_t* raw, int raw_w, int raw_h,
+                      int raw_stride, int channels, uint8_t* out);
 
 /* replaces: getInverseTransform(rotation, translation)  (vo.h:469-470, vo.cpp:246-258): [R t; 0 1]^-1, 4x4 row-major.
  * Runs the device function the frame pipeline ends with (one tiny launch). */

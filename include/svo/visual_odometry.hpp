@@ -188,6 +188,7 @@ class VisualOdometry {                                               // include/
             // initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
             if (!have_p_) { leftCameraProjection_.fill(0.f); rightCameraProjection_.fill(0.f); }
             svo_throw(svo_set_projection(ctx_, -1, leftCameraProjection_.data(), rightCameraProjection_.data()));
+            if (rect_) apply_rectification();
         }
         check_frame(image_left, "left"); check_frame(image_right, "right");
         Mat44 T;
@@ -236,7 +237,7 @@ class VisualOdometry {                                               // include/
         for (size_t i = 0; i < inside.size(); i++) {
             const Point2f* q[4] = {&pointsLeftT0[i], &pointsLeftT1[i], &pointsRightT0[i], &pointsRightT1[i]};
             bool in = true;
-            for (const Point2f* p : q) if (p->x < 0 || p->y < 0 || p->y >= imageLeftT1.rows || p->x >= imageLeftT1.cols) in = false;
+            for (const Point2f* p : q) if (p->x < 0 || p->y < 0 || p->y >= height_ || p->x >= width_) in = false;   // the (rectified) image size
             inside[i] = in;
         }
         deleteFeaturesWithFailureStatus(currentVOFeatures, inside);                                 // :360-364
@@ -250,6 +251,20 @@ class VisualOdometry {                                               // include/
         if (ctx_) svo_throw(svo_reset_sequence(ctx_, 0, nullptr, nullptr));
     }
 
+    // Rectify raw frames on the GPU (svo_set_rectification; replaces image_geometry::PinholeCameraModel::rectifyImage, i.e.
+    // cv::initUndistortRectifyMap + cv::remap, what stereo_image_proc runs to publish image_rect).  From then on stereo_callback /
+    // circularMatching take RAW frames of left.width x left.height; the rectified size is the object's (learnt from the first
+    // frame when the call comes before it: then the raw size, as image_rect has).  Projection matrices are not touched: pass
+    // left.P / right.P to initalize_projection_matricies.  Takes effect from the next frame.
+    void set_rectification(const svo_camera_info& left, const svo_camera_info& right) {
+        rect_l_ = left; rect_r_ = right; rect_ = true;
+        if (ctx_) apply_rectification();
+    }
+    void clear_rectification() {                                     // back to rectified input (svo_clear_rectification)
+        rect_ = false; raw_w_ = raw_h_ = 0;
+        if (ctx_) svo_throw(svo_clear_rectification(ctx_));
+    }
+
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
 
@@ -261,13 +276,21 @@ class VisualOdometry {                                               // include/
     // frame against the context (a shorter or narrower buffer would be read past its end)
     void check_frame(const Image& im, const char* which) const {
         if (im.empty()) throw std::runtime_error(std::string(which) + " image is empty");
-        if (im.cols != width_ || im.rows != height_ || im.channels != cfg_.channels || im.step < im.cols * im.channels)
-            throw std::runtime_error(std::string(which) + " image does not match the size / channels of the first frame");
+        const int w = raw_w_ ? raw_w_ : width_, h = raw_w_ ? raw_h_ : height_;     // rectifying: frames are raw
+        if (im.cols != w || im.rows != h || im.channels != cfg_.channels || im.step < im.cols * im.channels)
+            throw std::runtime_error(std::string(which) + " image does not match the size / channels the object takes (the raw size when rectifying)");
+    }
+    void apply_rectification() {
+        svo_throw(svo_set_rectification(ctx_, -1, &rect_l_, &rect_r_));
+        raw_w_ = rect_l_.width; raw_h_ = rect_l_.height;
     }
     svo_config cfg_;
     svo_context* ctx_ = nullptr;
     bool have_p_ = false;
     int width_ = 0, height_ = 0;                                      // learnt from the first frame
+    bool rect_ = false;                                               // set_rectification was called (applied once the context exists)
+    svo_camera_info rect_l_{}, rect_r_{};
+    int raw_w_ = 0, raw_h_ = 0;                                       // raw frame size while rectifying, else 0
 };
 
 }   // namespace visual_odometry

@@ -60,6 +60,12 @@ class SvoFrameStats(C.Structure):
         return {f[0]: getattr(self, f[0]) for f in self._fields_}
 
 
+class SvoCameraInfo(C.Structure):
+    """svo_camera_info: what rectification needs of a ROS sensor_msgs/CameraInfo (raw width x height)."""
+    _fields_ = [("K", C.c_double * 9), ("D", C.c_double * 8), ("n_d", C.c_int), ("R", C.c_double * 9), ("P", C.c_double * 12),
+                ("width", C.c_int), ("height", C.c_int)]
+
+
 lib.svo_last_error.restype = C.c_char_p
 lib.svo_alloc_pinned.restype = C.c_void_p
 lib.svo_alloc_pinned.argtypes = [C.c_size_t]
@@ -76,6 +82,17 @@ lib.svo_submit_batch_masked.restype = C.c_int
 lib.svo_submit_batch_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
 lib.svo_reset_sequence.restype = C.c_int
 lib.svo_reset_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+# rectification (svo.h): maps are int16 (h, w, 2) + uint16 (h, w) host arrays
+lib.svo_init_rectify_map.restype = C.c_int
+lib.svo_init_rectify_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+lib.svo_set_rectification_maps.restype = C.c_int
+lib.svo_set_rectification_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_set_rectification.restype = C.c_int
+lib.svo_set_rectification.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+lib.svo_clear_rectification.restype = C.c_int
+lib.svo_clear_rectification.argtypes = [C.c_void_p]
+lib.svo_rectify_image.restype = C.c_int
+lib.svo_rectify_image.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
 
 # every symbol include/svo.h declares (tests/test_abi.py checks the list against the header)
 EXPORTS = [
@@ -84,6 +101,7 @@ EXPORTS = [
     "svo_get_lk_registers_left", "svo_get_last_timing", "svo_set_stage_timing", "svo_get_stage_timing", "svo_get_stream", "svo_fast_detect", "svo_fast_score_map", "svo_bucket_filter",
     "svo_append_features_from_image", "svo_build_pyramid", "svo_lk_track", "svo_circular_match",
     "svo_find_close_points", "svo_stage_cache_clear", "svo_stage_cache_clear_all", "svo_triangulate", "svo_camera_to_world", "svo_inverse_transform",
+    "svo_set_rectification_maps", "svo_set_rectification", "svo_clear_rectification", "svo_init_rectify_map", "svo_rectify_image",
 ]
 
 

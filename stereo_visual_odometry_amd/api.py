@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SvoConfig, SvoFrameStats, check, default_config, lib, ptr, u8frame, u8img
+from ._lib import SvoCameraInfo, SvoConfig, SvoFrameStats, check, default_config, lib, ptr, u8frame, u8img
 
 # the reference's constants (include/vo.h:53-127) for callers that used them by name
 BUCKET_START_ROW, BUCKETS_ALONG_HEIGHT, BUCKETS_ALONG_WIDTH, FEATURES_PER_BUCKET = 4, 92, 160, 1
@@ -157,6 +157,55 @@ def circularMatching(cfg, l0, r0, l1, r1, points_left_t0, device=0):
     return outs[0], outs[1], outs[2], outs[3], ok
 
 
+# ---------------------------------------------------------------------------- rectification (svo.h)
+def camera_info(info):
+    """A ROS camera_info as svo_camera_info: a dict or any object with K (3x3), D (5 plumb_bob or 8 rational_polynomial
+    coefficients, or empty), R (3x3), P (3x4), width, height (the raw image size)."""
+    get = (lambda k: info[k]) if isinstance(info, dict) else (lambda k: getattr(info, k))
+    ci = SvoCameraInfo()
+    D = np.asarray(get("D"), np.float64).reshape(-1)
+    if len(D) not in (0, 4, 5, 8):
+        raise ValueError("D must hold 0, 4, 5 (plumb_bob) or 8 (rational_polynomial) coefficients")
+    ci.K[:] = [float(v) for v in np.asarray(get("K"), np.float64).reshape(9)]
+    ci.D[:len(D)] = [float(v) for v in D]
+    ci.n_d = len(D)
+    ci.R[:] = [float(v) for v in np.asarray(get("R"), np.float64).reshape(9)]
+    ci.P[:] = [float(v) for v in np.asarray(get("P"), np.float64).reshape(12)]
+    ci.width, ci.height = int(get("width")), int(get("height"))
+    return ci
+
+
+def init_rectify_map(K, D, R, P, width, height):
+    """cv::initUndistortRectifyMap(K, D, R, P[:, :3], (width, height), CV_16SC2) on the host (svo_init_rectify_map) ->
+    (map1 (height, width, 2) int16, map2 (height, width) uint16).  R / P may be None (identity / K)."""
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    D = np.ascontiguousarray(D if D is not None else [], np.float64).reshape(-1)
+    R = None if R is None else np.ascontiguousarray(R, np.float64).reshape(9)
+    P = None if P is None else np.ascontiguousarray(P, np.float64).reshape(12)
+    m1 = np.zeros((height, width, 2), np.int16); m2 = np.zeros((height, width), np.uint16)
+    check(lib.svo_init_rectify_map(ptr(K), ptr(D) if len(D) else None, len(D), ptr(R), ptr(P), int(width), int(height), ptr(m1), ptr(m2)))
+    return m1, m2
+
+
+def _maps(map1, map2):
+    m1 = np.ascontiguousarray(map1, np.int16); m2 = np.ascontiguousarray(map2, np.uint16)
+    if m1.ndim != 3 or m1.shape[2] != 2 or m2.shape != m1.shape[:2]:
+        raise ValueError("map1 must be (h, w, 2) int16 and map2 (h, w) uint16")
+    return m1, m2
+
+
+def rectifyImage(raw, map1, map2, device=0):
+    """cv::remap(raw, map1, map2, INTER_LINEAR, BORDER_CONSTANT, 0) on the GPU (svo_rectify_image): the per-frame half of
+    image_geometry::PinholeCameraModel::rectifyImage.  raw: (h, w) or (h, w, 3) uint8 -> the map's size, same channels."""
+    img = u8frame(raw)
+    m1, m2 = _maps(map1, map2)
+    h, w = m2.shape
+    cn = 3 if img.ndim == 3 else 1
+    out = np.zeros((h, w, 3) if cn == 3 else (h, w), np.uint8)
+    check(lib.svo_rectify_image(device, ptr(m1), ptr(m2), w, h, ptr(img), img.shape[1], img.shape[0], img.strides[0], cn, ptr(out)))
+    return out
+
+
 # ---------------------------------------------------------------------------- FeatureSet / Bucket
 class FeatureSet:
     """vo.h:132-188 — parallel arrays points / ages / strengths."""
@@ -260,6 +309,36 @@ class BatchVisualOdometry:
         self._h = C.c_void_p()
         check(lib.svo_create(C.byref(self.cfg), device, n_seq, width, height, C.byref(self._h)))
         self.stats = None
+        self.raw_size = None                          # (raw_w, raw_h) while the context rectifies: frames are then raw
+
+    def _in_shape(self):
+        """(height, width) of the frames the caller passes: the raw size when rectifying."""
+        return (self.raw_size[1], self.raw_size[0]) if self.raw_size else (self.height, self.width)
+
+    def set_rectification(self, left_info, right_info, seq=-1):
+        """Rectify raw frames with these calibrations (svo_set_rectification): `seq` (-1: the shared maps of every sequence
+        without its own).  Frames passed from now on are raw (left_info's width x height).  The projection matrices are NOT
+        set here: pass left_info["P"] / right_info["P"] to initalize_projection_matricies."""
+        li, ri = camera_info(left_info), camera_info(right_info)
+        check(lib.svo_set_rectification(self._h, seq, C.byref(li), C.byref(ri)))
+        self.raw_size = (li.width, li.height)
+
+    def set_rectification_maps(self, map1_l, map2_l, map1_r, map2_r, seq=-1, raw_size=None):
+        """Install precomputed maps (svo_set_rectification_maps): map1 (height, width, 2) int16 and map2 (height, width) uint16
+        at the context's size.  raw_size = (raw_w, raw_h); may be omitted once the context rectifies."""
+        raw_size = raw_size or self.raw_size
+        if raw_size is None:
+            raise ValueError("raw_size = (raw_w, raw_h) is required for the first maps")
+        a, b = _maps(map1_l, map2_l); c, d = _maps(map1_r, map2_r)
+        if a.shape[:2] != (self.height, self.width) or c.shape[:2] != (self.height, self.width):
+            raise ValueError("maps must be (%d, %d)" % (self.height, self.width))
+        check(lib.svo_set_rectification_maps(self._h, seq, int(raw_size[0]), int(raw_size[1]), ptr(a), ptr(b), ptr(c), ptr(d)))
+        self.raw_size = (int(raw_size[0]), int(raw_size[1]))
+
+    def clear_rectification(self):
+        """Back to a plain context (svo_clear_rectification): frames at the context's size again."""
+        check(lib.svo_clear_rectification(self._h))
+        self.raw_size = None
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -295,15 +374,15 @@ class BatchVisualOdometry:
         L = [u8frame(i) if o else None for i, o in zip(lefts, on)]; R = [u8frame(i) if o else None for i, o in zip(rights, on)]
         assert len(L) == self.n_seq and len(R) == self.n_seq
         cn = max(1, self.cfg.channels)
-        assert all(i.shape == (self.height, self.width) + ((3,) if cn == 3 else ()) for i in L + R if i is not None), "image shape / channels"
+        assert all(i.shape == self._in_shape() + ((3,) if cn == 3 else ()) for i in L + R if i is not None), "image shape / channels"
         lp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in L])
         rp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in R])
         T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
         st = (SvoFrameStats * self.n_seq)()
         if act is None:
-            check(lib.svo_process_batch(self._h, lp, rp, self.width * cn, 0, ptr(T), ptr(ok), st))
+            check(lib.svo_process_batch(self._h, lp, rp, self._in_shape()[1] * cn, 0, ptr(T), ptr(ok), st))
         else:
-            check(lib.svo_process_batch_masked(self._h, lp, rp, self.width * cn, 0, ptr(act), ptr(T), ptr(ok), st))
+            check(lib.svo_process_batch_masked(self._h, lp, rp, self._in_shape()[1] * cn, 0, ptr(act), ptr(T), ptr(ok), st))
         self.stats = list(st)
         return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
 
@@ -393,6 +472,8 @@ class VisualOdometry(BatchVisualOdometry):
             self._created = True
         self._P = None
         self._timing = None
+        self._rect = None                             # rectification asked for before the context exists: applied at creation
+        self.raw_size = None
 
     def set_stage_timing(self, on=True):
         self._timing = bool(on)
@@ -404,14 +485,39 @@ class VisualOdometry(BatchVisualOdometry):
         if self._created:
             super().initalize_projection_matricies(leftCameraProjection, rightCameraProjection)
 
+    def set_rectification(self, left_info, right_info, seq=-1):
+        if self._created:
+            return super().set_rectification(left_info, right_info, seq)
+        self._rect = ("info", left_info, right_info)  # the rectified size is then the raw size (as ROS's image_rect)
+
+    def set_rectification_maps(self, map1_l, map2_l, map1_r, map2_r, seq=-1, raw_size=None):
+        if self._created:
+            return super().set_rectification_maps(map1_l, map2_l, map1_r, map2_r, seq, raw_size)
+        if raw_size is None:
+            raise ValueError("raw_size = (raw_w, raw_h) is required for the first maps")
+        self._rect = ("maps", (map1_l, map2_l, map1_r, map2_r), raw_size)
+
+    def clear_rectification(self):
+        self._rect = None
+        if self._created:
+            super().clear_rectification()
+
     def stereo_callback(self, image_left, image_right):
         L, R = u8frame(image_left), u8frame(image_right)
         if not self._created:                         # the reference learns the image size (and type) from the first frame
             cfg, device = self._args
             cfg = _lib.copy_config(cfg) if cfg is not None else default_config()       # never write into the caller's struct
             cfg.channels = 3 if L.ndim == 3 else 1    # colour Mats, as the reference CLI feeds them (main.cpp:38-46)
-            super().__init__(L.shape[1], L.shape[0], 1, cfg, device)
+            w, h = L.shape[1], L.shape[0]
+            if self._rect is not None and self._rect[0] == "maps":
+                h, w = np.asarray(self._rect[1][1]).shape
+            super().__init__(w, h, 1, cfg, device)
             self._created = True
+            if self._rect is not None:
+                if self._rect[0] == "info":
+                    super().set_rectification(self._rect[1], self._rect[2])
+                else:
+                    super().set_rectification_maps(*self._rect[1], raw_size=self._rect[2])
             # like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
             # initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
             super().initalize_projection_matricies(*(self._P if self._P is not None else (np.zeros(12, np.float32), np.zeros(12, np.float32))))
@@ -432,7 +538,7 @@ class VisualOdometry(BatchVisualOdometry):
 
     def _check_frame(self, img, which):
         """cv::Mat carries size and type and OpenCV asserts on a mismatch; a raw pointer does not: check before the C call."""
-        want = (self.height, self.width) + ((3,) if self.cfg.channels == 3 else ())
+        want = self._in_shape() + ((3,) if self.cfg.channels == 3 else ())
         if img.shape != want:
             raise ValueError("%s image has shape %s, the context was created for %s" % (which, img.shape, want))
 

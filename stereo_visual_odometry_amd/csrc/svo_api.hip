@@ -107,6 +107,19 @@ struct svo_context {
     hipGraphExec_t gexec[SVO_RING] = {};
     int g_stride[SVO_RING] = {}, g_gn[SVO_RING] = {}, g_co[SVO_RING] = {};   // what the slot's graph was captured with (stride, LK grid, co-resident builds)
     bool staged_slot[SVO_RING] = {};             // the slot's stage events were recorded (launch-list mode only)
+    // rectification (svo_set_rectification_maps): raw_w > 0 makes the context take RAW frames.  A map is one device buffer
+    // ([W*H] short2 + [W*H] u16) per camera; shared[cam] serves every sequence whose own[seq][cam] is null.  Each frame names its
+    // maps in the slot's row of the pinned table h_maps (read in place by the ingest kernels, beside h_ptrs), so a map replaced
+    // with frames in flight is only retired: freed once every frame enqueued before its replacement has been collected.
+    int raw_w = 0, raw_h = 0;
+    uint8_t* shared_map[2] = {};
+    std::vector<uint8_t*> own_map;               // [B][2]
+    const uint8_t** h_maps = nullptr;            // pinned [SVO_RING][2][B]
+    const uint8_t* const* d_maps = nullptr;      // its device address
+    struct Retired { uint8_t* p; long long after; };
+    std::vector<Retired> retired;                // freed when n_collected >= after
+    long long n_enqueued = 0, n_collected = 0;
+    size_t staging_bytes = 0;                    // size of `staging` / `h_staging` (host-image calls of a rectifying context stage raw frames)
 };
 
 template <typename T>
@@ -198,6 +211,10 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     HIPCHK(hipHostMalloc((void**)&c->h_ptrs, sizeof(uint8_t*) * SVO_RING * 2 * B, hipHostMallocMapped));
     HIPCHK(hipHostGetDevicePointer((void**)&d.img_ptrs, (void*)c->h_ptrs, 0));   // read in place by k_ingest: no per-frame upload
     HIPCHK(hipHostMalloc((void**)&c->h_act, sizeof(int) * SVO_RING * 2 * B));
+    HIPCHK(hipHostMalloc((void**)&c->h_maps, sizeof(uint8_t*) * SVO_RING * 2 * B, hipHostMallocMapped));
+    memset((void*)c->h_maps, 0, sizeof(uint8_t*) * SVO_RING * 2 * B);
+    HIPCHK(hipHostGetDevicePointer((void**)&c->d_maps, (void*)c->h_maps, 0));
+    c->own_map.assign(2 * B, nullptr);
     for (int i = 0; i < SVO_RING; i++) {
         HIPCHK(hipEventCreate(&c->ev_done[i])); HIPCHK(hipEventCreate(&c->ev_f0[i]));
         HIPCHK(hipEventCreate(&c->ev_lk0[i])); HIPCHK(hipEventCreate(&c->ev_lk1[i]));
@@ -270,6 +287,10 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->h_results) (void)hipHostFree(c->h_results);
     if (c->h_ptrs) (void)hipHostFree((void*)c->h_ptrs);
     if (c->h_act) (void)hipHostFree(c->h_act);
+    if (c->h_maps) (void)hipHostFree((void*)c->h_maps);
+    for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
+    for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
+    for (const auto& r : c->retired) (void)hipFree(r.p);
     for (int i = 0; i < SVO_RING; i++) {
         if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
         if (c->ev_f0[i]) (void)hipEventDestroy(c->ev_f0[i]);
@@ -314,6 +335,9 @@ extern "C" int svo_set_projection(svo_context* c, int seq, const float Pl[12], c
 
 static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
                              std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active = nullptr);
+// the size of the frames the caller passes: the raw size when the context rectifies, else the context's own
+static int in_width(const svo_context* c) { return c->raw_w > 0 ? c->raw_w : c->d.geom.W; }
+static int in_height(const svo_context* c) { return c->raw_w > 0 ? c->raw_h : c->d.geom.H; }
 
 // The launch list of one frame (vo.cpp:41-137 as kernels), between the pointer-table upload and the result download.
 // with_events: record the stage-boundary events (not inside a graph capture).
@@ -323,7 +347,8 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     DevBuffers& d = c->d;
     const int B = d.B;
     hipStream_t s = c->stream;
-    struct ActReset { DevBuffers& d; ~ActReset() { d.act = nullptr; d.n_act = 0; } } act_reset{d};   // other launches see an unmasked context
+    struct ActReset { DevBuffers& d; ~ActReset() { d.act = nullptr; d.n_act = 0; d.rmap = nullptr; } } act_reset{d};   // other launches see an unmasked, plain context
+    if (c->raw_w > 0) d.rmap = c->d_maps + (size_t)slot * 2 * B;     // the frame's own maps (enqueue_frame filled the row)
     const size_t act_bytes = sizeof(int) * 2 * (size_t)B;
     const int* h_act = c->h_act + (size_t)slot * 2 * B;
     if (n_act >= 0) { d.act = c->d_act + (size_t)slot * 2 * B; d.n_act = n_act; }
@@ -431,6 +456,17 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
         for (int i = 0; i < B; i++) { ha[B + i] = active[i] ? 1 : 0; if (active[i]) ha[n++] = i; }
         if (n < B) n_act = n;
     }
+    if (c->raw_w > 0) {                                              // the frame's maps, in the slot's row beside its image pointers
+        const uint8_t** hm = c->h_maps + (size_t)slot * 2 * B;
+        for (int i = 0; i < B; i++) {
+            const bool on = !active || active[i];
+            for (int cam = 0; cam < 2; cam++) {
+                const uint8_t* m = c->own_map[2 * i + cam] ? c->own_map[2 * i + cam] : c->shared_map[cam];
+                if (on && !m) { g_err = "rectifying context: a sequence has no rectification map (svo_set_rectification_maps)"; return SVO_ERR_STATE; }
+                hm[cam * B + i] = on ? m : nullptr;
+            }
+        }
+    }
     for (int i = 0; i < B; i++) {
         const bool on = !active || active[i];
         hp[i] = on ? left_dev[i] : nullptr; hp[B + i] = on ? right_dev[i] : nullptr;
@@ -445,7 +481,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     }
     HIPCHK(hipEventRecord(c->ev_f0[slot], s));
     bool replayed = false;
-    if (c->use_graph && n_act < 0) {                                 // a ragged frame runs from the launch list
+    if (c->use_graph && n_act < 0 && c->raw_w == 0) {                // a ragged or rectifying frame runs from the launch list
         // the captured launch list bakes in which builds of the f64 kernels run: a context captured while it had the device to
         // itself must be re-captured once another many-sequence context exists (and back), or it would keep the full-register
         // builds that cannot start beside the other's LK grid
@@ -476,7 +512,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     c->staged_inputs = false;
     HIPCHK(hipEventRecord(c->ev_done[slot], s));
     HIPCHK(hipGetLastError());
-    c->head = (c->head + 1) % SVO_RING; c->inflight++;
+    c->head = (c->head + 1) % SVO_RING; c->inflight++; c->n_enqueued++;
     return SVO_OK;
 }
 
@@ -496,14 +532,19 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
         if (mx > 0) c->lk_hint = mx;
     }
     c->last_slot = slot;
-    c->tail = (c->tail + 1) % SVO_RING; c->inflight--;
+    c->tail = (c->tail + 1) % SVO_RING; c->inflight--; c->n_collected++;
+    if (!c->retired.empty()) {                                       // maps no frame in flight can name any more
+        size_t k = 0;
+        for (const auto& r : c->retired) { if (r.after <= c->n_collected) (void)hipFree(r.p); else c->retired[k++] = r; }
+        c->retired.resize(k);
+    }
     return SVO_OK;
 }
 
 extern "C" int svo_submit_batch(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride) {
     if (!c || !left_dev || !right_dev) return fail_arg("null argument");
     if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
-    if (stride < c->d.geom.W * c->d.CN) return fail_arg("stride < width * channels");
+    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
     HIPCHK(hipSetDevice(c->device));
     return enqueue_frame(c, left_dev, right_dev, stride);
 }
@@ -513,7 +554,7 @@ extern "C" int svo_submit_batch_masked(svo_context* c, const uint8_t* const* lef
     if (!c) return fail_arg("null context");
     if (!active) return svo_submit_batch(c, left_dev, right_dev, stride);
     if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
-    if (stride < c->d.geom.W * c->d.CN) return fail_arg("stride < width * channels");
+    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
     int n_act = 0, rc;
     if ((rc = check_active(c, left_dev, right_dev, active, &n_act)) != SVO_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
@@ -542,10 +583,10 @@ extern "C" int svo_collect(svo_context* c, double* T_out, int* ok_out, svo_frame
 static int process_batch(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
                          int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats) {
     if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
-    if (stride < c->d.geom.W * c->d.CN) return fail_arg("stride < width * channels");
+    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
     if (c->inflight != 0) { g_err = "svo_process_batch with frames in flight"; return SVO_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    const int W = c->d.geom.W;
+    const int W = in_width(c);
     int rc;
     if (images_on_device) {
         rc = enqueue_frame(c, left, right, stride, active);
@@ -604,10 +645,16 @@ extern "C" void svo_free_pinned(void* p) { if (p) (void)hipHostFree(p); }
 // active (ragged frame): idle sequences' images are not read (their pointers may be NULL; their staging areas keep old bytes).
 static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
                              std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active) {
-    const int B = c->d.B, W = c->d.geom.W, H = c->d.geom.H;
+    const int B = c->d.B, W = in_width(c), H = in_height(c);
     const size_t rowb = (size_t)W * c->d.CN, img = rowb * H;
-    if (!c->staging) HIPCHK(hipMalloc((void**)&c->staging, img * 2 * B));
-    if (!c->h_staging) HIPCHK(hipHostMalloc((void**)&c->h_staging, img * 2 * B));
+    if (c->staging_bytes < img * 2 * B) {                             // no frame in flight reads the staging buffers (synchronous calls only)
+        if (c->staging) { (void)hipFree(c->staging); c->staging = nullptr; }
+        if (c->h_staging) { (void)hipHostFree(c->h_staging); c->h_staging = nullptr; }
+        c->staging_bytes = 0;
+        HIPCHK(hipMalloc((void**)&c->staging, img * 2 * B));
+        HIPCHK(hipHostMalloc((void**)&c->h_staging, img * 2 * B));
+        c->staging_bytes = img * 2 * B;
+    }
     // rows are packed into pinned memory on the CPU (handles any stride), then contiguous async H2D copies (a 2-D copy from
     // pageable memory degenerates into per-row transfers: 3.5 ms per 1241x376 image).  All left images first, so that their
     // DMA runs while the CPU packs the right ones.
@@ -651,7 +698,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     if (!c || !left_t1 || !right_t1 || n < 0) return fail_arg("bad arguments");
     if (n > 0 && (!pl0 || !pl1 || !pr1 || !pr0 || !pl0_circle || !ok)) return fail_arg("null arrays");
     if (c->d.B != 1) return fail_arg("svo_circular_matching needs a context created with n_seq == 1");
-    if (stride < c->d.geom.W * c->d.CN) return fail_arg("stride < width * channels");
+    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
     if (c->inflight != 0) { g_err = "svo_circular_matching with frames in flight"; return SVO_ERR_STATE; }
     if (n == 0) return SVO_OK;                                                    // vo.cpp:179-181
     if (n > c->d.CAP) { g_err = "more points than the context's feature capacity"; return SVO_ERR_CAPACITY; }
@@ -675,7 +722,13 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     const uint8_t* l[1] = {left_t1}; const uint8_t* r[1] = {right_t1};
     if ((rc = stage_host_images(c, l, r, stride, lp, rp)) != SVO_OK) return rc;
     const uint8_t** hp = c->h_ptrs; hp[0] = lp[0]; hp[1] = rp[0];
-    launch_ingest_pyramid(c->d, c->d.img_ptrs, c->d.geom.W * c->d.CN, c->stream, false);          // vo.cpp:200-201
+    if (c->raw_w > 0) {                                                           // no frame in flight: ring slot 0's map row is free
+        for (int cam = 0; cam < 2; cam++) c->h_maps[cam] = c->own_map[cam] ? c->own_map[cam] : c->shared_map[cam];
+        if (!c->h_maps[0] || !c->h_maps[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
+        c->d.rmap = c->d_maps;
+    }
+    launch_ingest_pyramid(c->d, c->d.img_ptrs, in_width(c) * c->d.CN, c->stream, false);          // vo.cpp:200-201
+    c->d.rmap = nullptr;
     if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // vo.cpp:203-230 (the caller gets every pass's raw points)
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(pl1, c->d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
@@ -1149,5 +1202,145 @@ extern "C" int svo_inverse_transform(int device, const double R[9], const double
     launch_inverse_transform(buf, buf + 9, buf + 12, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(T, buf + 12, sizeof(double) * 16, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+
+// ================================================================================================
+// Rectification (svo.h): map generation (host, f64), map installation, and the remap stage entry point
+// ================================================================================================
+// cv::initUndistortRectifyMap(K, D, R, P[:, :3], (w, h), CV_16SC2, map1, map2) restated as its scalar loop (plumb_bob and
+// rational_polynomial; no thin-prism / tilt terms, whose identity forms it reduces to exactly).  The order of every f64 operation
+// is OpenCV's: iR = (P33 R)^-1 by the explicit adjugate / determinant (Matx's fast 3x3 inverse), the row start, then the
+// column walk by repeated addition.  No FMA contraction anywhere in it (the pragma and the Makefile's -ffp-contract=off), so
+// it equals a numpy restatement (tests/rectify_ref.py) bit for bit.
+static int rect_round(double v) {                  // cvRound: round half to even; out of range (or NaN) gives INT_MIN, as cvtsd2si does
+    const double r = nearbyint(v);
+    return (r >= -2147483648.0 && r <= 2147483647.0) ? (int)r : (-2147483647 - 1);
+}
+extern "C" int svo_init_rectify_map(const double K[9], const double* D, int n_d, const double R[9], const double P[12], int w, int h,
+                                    int16_t* map1, uint16_t* map2) {
+#pragma clang fp contract(off)
+    if (!K || !map1 || !map2 || w < 1 || h < 1) return fail_arg("svo_init_rectify_map: null argument or empty size");
+    if (!(n_d == 0 || n_d == 4 || n_d == 5 || n_d == 8) || (n_d > 0 && !D)) return fail_arg("svo_init_rectify_map: n_d must be 0, 4, 5 (plumb_bob) or 8 (rational_polynomial)");
+    double k[8] = {0, 0, 0, 0, 0, 0, 0, 0};        // k1 k2 p1 p2 k3 k4 k5 k6
+    for (int i = 0; i < n_d; i++) k[i] = D[i];
+    const double Rd[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const double* Rm = R ? R : Rd;
+    double A[9];                                   // P[:, :3] (K when P is NULL) times R, Matx order: ((a0 b0 + a1 b1) + a2 b2)
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const double a0 = P ? P[4 * i] : K[3 * i], a1 = P ? P[4 * i + 1] : K[3 * i + 1], a2 = P ? P[4 * i + 2] : K[3 * i + 2];
+            A[3 * i + j] = a0 * Rm[j] + a1 * Rm[3 + j] + a2 * Rm[6 + j];
+        }
+#define a(r, c) A[3 * (r) + (c)]
+    double det = a(0, 0) * (a(1, 1) * a(2, 2) - a(2, 1) * a(1, 2)) - a(0, 1) * (a(1, 0) * a(2, 2) - a(2, 0) * a(1, 2)) +
+                 a(0, 2) * (a(1, 0) * a(2, 1) - a(2, 0) * a(1, 1));
+    if (det == 0.) return fail_arg("svo_init_rectify_map: P[:, :3] * R is singular");
+    det = 1. / det;
+    const double ir[9] = {
+        (a(1, 1) * a(2, 2) - a(1, 2) * a(2, 1)) * det, (a(0, 2) * a(2, 1) - a(0, 1) * a(2, 2)) * det, (a(0, 1) * a(1, 2) - a(0, 2) * a(1, 1)) * det,
+        (a(1, 2) * a(2, 0) - a(1, 0) * a(2, 2)) * det, (a(0, 0) * a(2, 2) - a(0, 2) * a(2, 0)) * det, (a(0, 2) * a(1, 0) - a(0, 0) * a(1, 2)) * det,
+        (a(1, 0) * a(2, 1) - a(1, 1) * a(2, 0)) * det, (a(0, 1) * a(2, 0) - a(0, 0) * a(2, 1)) * det, (a(0, 0) * a(1, 1) - a(0, 1) * a(1, 0)) * det};
+#undef a
+    const double fx = K[0], fy = K[4], u0 = K[2], v0 = K[5];
+    const double k1 = k[0], k2 = k[1], p1 = k[2], p2 = k[3], k3 = k[4], k4 = k[5], k5 = k[6], k6 = k[7];
+    for (int i = 0; i < h; i++) {
+        double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+        int16_t* m1 = map1 + (size_t)i * w * 2;
+        uint16_t* m2 = map2 + (size_t)i * w;
+        for (int j = 0; j < w; j++, _x += ir[0], _y += ir[3], _w += ir[6]) {
+            const double ww = 1. / _w, x = _x * ww, y = _y * ww;
+            const double x2 = x * x, y2 = y * y;
+            const double r2 = x2 + y2, _2xy = 2 * x * y;
+            const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+            const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2);
+            const double yd = y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy;
+            const double u = fx * xd + u0, v = fy * yd + v0;
+            const int iu = rect_round(u * 32), iv = rect_round(v * 32);
+            m1[2 * j] = (int16_t)(iu >> 5);
+            m1[2 * j + 1] = (int16_t)(iv >> 5);
+            m2[j] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+        }
+    }
+    return SVO_OK;
+}
+
+static void retire_map(svo_context* c, uint8_t* p) {
+    if (!p) return;
+    if (c->inflight == 0) (void)hipFree(p);                                       // every frame that could name it has been collected
+    else c->retired.push_back({p, c->n_enqueued});
+}
+static int upload_map(svo_context* c, const int16_t* m1, const uint16_t* m2, uint8_t** out) {
+    const size_t n = (size_t)c->d.geom.W * c->d.geom.H;
+    uint8_t* p = nullptr;
+    HIPCHK(hipMalloc((void**)&p, n * 6));
+    if (hipMemcpy(p, m1, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(p + n * 4, m2, n * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        g_err = "svo_set_rectification_maps: map upload failed";
+        (void)hipFree(p);
+        return SVO_ERR_HIP;
+    }
+    *out = p;
+    return SVO_OK;
+}
+
+extern "C" int svo_set_rectification_maps(svo_context* c, int seq, int raw_w, int raw_h, const int16_t* map1_l, const uint16_t* map2_l,
+                                          const int16_t* map1_r, const uint16_t* map2_r) {
+    if (!c) return fail_arg("null context");
+    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if (!map1_l || !map2_l || !map1_r || !map2_r) return fail_arg("null map");
+    if (raw_w < 1 || raw_h < 1 || raw_w > 32767 || raw_h > 32767) return fail_arg("raw size must be 1 .. 32767");
+    if (c->raw_w > 0 && (raw_w != c->raw_w || raw_h != c->raw_h)) return fail_arg("raw size differs from the one this context rectifies (svo_clear_rectification first)");
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* m[2] = {nullptr, nullptr};
+    int rc = upload_map(c, map1_l, map2_l, &m[0]);
+    if (rc == SVO_OK) rc = upload_map(c, map1_r, map2_r, &m[1]);
+    if (rc != SVO_OK) { if (m[0]) (void)hipFree(m[0]); return rc; }
+    for (int cam = 0; cam < 2; cam++) {
+        uint8_t*& slot = seq < 0 ? c->shared_map[cam] : c->own_map[2 * seq + cam];
+        retire_map(c, slot);
+        slot = m[cam];
+    }
+    c->raw_w = c->d.raw_w = raw_w; c->raw_h = c->d.raw_h = raw_h;
+    return SVO_OK;
+}
+
+extern "C" int svo_set_rectification(svo_context* c, int seq, const svo_camera_info* left, const svo_camera_info* right) {
+    if (!c || !left || !right) return fail_arg("null argument");
+    if (left->width != right->width || left->height != right->height) return fail_arg("left and right camera_info differ in raw size");
+    const size_t n = (size_t)c->d.geom.W * c->d.geom.H;
+    std::vector<int16_t> m1[2]; std::vector<uint16_t> m2[2];
+    for (int cam = 0; cam < 2; cam++) {
+        const svo_camera_info* ci = cam ? right : left;
+        m1[cam].resize(2 * n); m2[cam].resize(n);
+        const int rc = svo_init_rectify_map(ci->K, ci->D, ci->n_d, ci->R, ci->P, c->d.geom.W, c->d.geom.H, m1[cam].data(), m2[cam].data());
+        if (rc != SVO_OK) return rc;
+    }
+    return svo_set_rectification_maps(c, seq, left->width, left->height, m1[0].data(), m2[0].data(), m1[1].data(), m2[1].data());
+}
+
+extern "C" int svo_clear_rectification(svo_context* c) {
+    if (!c) return fail_arg("null context");
+    HIPCHK(hipSetDevice(c->device));
+    for (int cam = 0; cam < 2; cam++) { retire_map(c, c->shared_map[cam]); c->shared_map[cam] = nullptr; }
+    for (uint8_t*& p : c->own_map) { retire_map(c, p); p = nullptr; }
+    c->raw_w = c->raw_h = c->d.raw_w = c->d.raw_h = 0;
+    return SVO_OK;
+}
+
+extern "C" int svo_rectify_image(int device, const int16_t* map1, const uint16_t* map2, int w, int h, const uint8_t* raw, int raw_w, int raw_h,
+                                 int raw_stride, int channels, uint8_t* out) {
+    if (!map1 || !map2 || !raw || !out || w < 1 || h < 1 || raw_w < 1 || raw_h < 1) return fail_arg("bad arguments");
+    if (channels != 1 && channels != 3) return fail_arg("channels must be 1 or 3");
+    if (raw_stride < raw_w * channels) return fail_arg("raw_stride < raw_w * channels");
+    int rc = use_device(device); if (rc != SVO_OK) return rc;
+    const size_t n = (size_t)w * h, rowb = (size_t)raw_w * channels;
+    DevTmp t; short2* dm1; uint16_t* dm2; uint8_t *draw, *dout;
+    HIPCHK(t.get(&dm1, n)); HIPCHK(t.get(&dm2, n)); HIPCHK(t.get(&draw, rowb * raw_h)); HIPCHK(t.get(&dout, n * channels));
+    HIPCHK(hipMemcpy(dm1, map1, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dm2, map2, n * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy2D(draw, rowb, raw, (size_t)raw_stride, rowb, (size_t)raw_h, hipMemcpyHostToDevice));
+    launch_rectify_image(dm1, dm2, w, h, draw, raw_w, raw_h, (int)rowb, channels, dout, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dout, n * channels, hipMemcpyDeviceToHost));
     return SVO_OK;
 }

@@ -95,6 +95,11 @@ struct DevBuffers {
     // sequence (k_frame_end writes the idle rows from it) — the frame's row of a device [SVO_RING][2 B] buffer.  nullptr: every
     // sequence takes it, and the grids are those of the unmasked calls.
     const int* act; int n_act;
+    // Rectifying contexts (svo_set_rectification_maps): frames are RAW images of raw_w x raw_h pixels; level 0 and the FAST image
+    // are their remap through each frame's own maps.  rmap = the frame's row of a pinned [SVO_RING][2][B] table of map pointers
+    // (a map = [W*H] short2 integer positions, then [W*H] u16 fractions: OpenCV's CV_16SC2 + CV_16UC1 pair), set for the launches
+    // of one frame only, like act.  nullptr: the caller's images are level 0 as they stand, and the plain kernels run.
+    const uint8_t* const* rmap; int raw_w, raw_h;
 };
 
 // The sequence of the b-th sequence slot of a launch (a block coordinate or a thread index): every per-sequence kernel maps its
@@ -147,6 +152,9 @@ void launch_inverse_transform(const double* R, const double* t, double* T, hipSt
 // detection pass; false = not applicable to this context, nothing was launched
 bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t s);
 void launch_frame_end(const DevBuffers& d, int ring_slot, hipStream_t s);
+// svo_rectify_image: out (w x h x cn, packed) = the remap of raw through (map1, map2); all device pointers
+void launch_rectify_image(const short2* map1, const uint16_t* map2, int w, int h, const uint8_t* raw, int raw_w, int raw_h, int raw_stride,
+                          int cn, uint8_t* out, hipStream_t s);
 
 // stage helpers
 void launch_fast_score_map(const uint8_t* img_dev, int w, int h, int threshold, uint8_t* score_dev, hipStream_t s);

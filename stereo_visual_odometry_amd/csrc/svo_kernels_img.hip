@@ -12,6 +12,55 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Rectification (svo.h, svo_set_rectification_maps): cv::remap(raw, out, map1, map2, INTER_LINEAR, BORDER_CONSTANT, 0) with a
+// CV_16SC2 + CV_16UC1 map, the step image_geometry::PinholeCameraModel::rectifyImage runs to make image_rect.  One output byte
+// of channel c: integer position (x0, y0) = map1, fractions fx = map2 & 31, fy = (map2 >> 5) & 31 (OpenCV masks map2 to
+// INTER_TAB_SIZE2 - 1 as well); the four 15-bit OpenCV weights are 32 x the integer products below, so
+//   out = ((32-fx)(32-fy) p00 + fx(32-fy) p01 + (32-fx) fy p10 + fx fy p11 + 512) >> 10,
+// a tap outside the raw image reads 0.  Every tap is bounds-checked before it is loaded: any map is safe.
+// ------------------------------------------------------------------------------------------------
+template <int CN>
+__device__ __forceinline__ void remap_px(const uint8_t* __restrict__ raw, int stride, int rw, int rh, short2 p, unsigned f, uint8_t* out) {
+    const int x0 = p.x, y0 = p.y, fx = f & 31, fy = (f >> 5) & 31;
+    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+    const bool x0in = (unsigned)x0 < (unsigned)rw, x1in = (unsigned)(x0 + 1) < (unsigned)rw;
+    const bool y0in = (unsigned)y0 < (unsigned)rh, y1in = (unsigned)(y0 + 1) < (unsigned)rh;
+    const ptrdiff_t o00 = (ptrdiff_t)y0 * stride + (ptrdiff_t)x0 * CN;
+#pragma unroll
+    for (int c = 0; c < CN; c++) {
+        const int p00 = (y0in && x0in) ? raw[o00 + c] : 0, p01 = (y0in && x1in) ? raw[o00 + CN + c] : 0;
+        const int p10 = (y1in && x0in) ? raw[o00 + stride + c] : 0, p11 = (y1in && x1in) ? raw[o00 + stride + CN + c] : 0;
+        out[c] = (uint8_t)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
+    }
+}
+// the maps of (camera, sequence) of the frame being ingested: [W*H] short2, then [W*H] u16
+__device__ __forceinline__ const short2* rect_map1(const DevBuffers& d, int cam, int seq) {
+    return reinterpret_cast<const short2*>(d.rmap[cam * d.B + seq]);
+}
+__device__ __forceinline__ const uint16_t* rect_map2(const DevBuffers& d, int cam, int seq) {
+    return reinterpret_cast<const uint16_t*>(d.rmap[cam * d.B + seq] + (size_t)4 * d.geom.W * d.geom.H);
+}
+
+// svo_rectify_image: one thread per output pixel (all channels), packed output rows
+template <int CN>
+__global__ __launch_bounds__(256) void k_rectify_image(const short2* __restrict__ m1, const uint16_t* __restrict__ m2, int w, int h,
+                                                       const uint8_t* __restrict__ raw, int rw, int rh, int stride, uint8_t* __restrict__ out) {
+    const int total = w * h;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        uint8_t px[CN];
+        remap_px<CN>(raw, stride, rw, rh, m1[i], m2[i], px);
+#pragma unroll
+        for (int c = 0; c < CN; c++) out[(size_t)i * CN + c] = px[c];
+    }
+}
+void launch_rectify_image(const short2* map1, const uint16_t* map2, int w, int h, const uint8_t* raw, int raw_w, int raw_h, int raw_stride,
+                          int cn, uint8_t* out, hipStream_t st) {
+    int gx = (w * h + 255) / 256; if (gx > 4096) gx = 4096;
+    if (cn == 3) hipLaunchKernelGGL(k_rectify_image<3>, dim3(gx), dim3(256), 0, st, map1, map2, w, h, raw, raw_w, raw_h, raw_stride, out);
+    else hipLaunchKernelGGL(k_rectify_image<1>, dim3(gx), dim3(256), 0, st, map1, map2, w, h, raw, raw_w, raw_h, raw_stride, out);
+}
+
+// ------------------------------------------------------------------------------------------------
 // frame begin / end: the slot bookkeeping of stereo_callback (vo.cpp:47-56, 74-75) and of the
 // pyramid cache in circularMatching (vo.cpp:179-181 vs 231-232: the cache is NOT refreshed when
 // there were no points to match — the "stale pyramid" quirk).
@@ -121,8 +170,45 @@ __global__ __launch_bounds__(256) void k_ingest_bgr(DevBuffers d, const uint8_t*
     }
 }
 
+// Rectifying form of k_ingest (CN = 1) and k_ingest_bgr (CN = 3): level-0 pixel (x, y) of every plane is the remap of the raw
+// frame at the map's position.  The FAST image of a colour context is the first W bytes of every RECTIFIED interleaved row (the
+// reference quirk of svo.h, channels): bytes 3x .. 3x + 2 of that row are pixel x's three channels, so the threads of pixels
+// x < W / 3 write them — no remap is done twice.
+template <int CN>
+__global__ __launch_bounds__(256) void k_ingest_rect(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
+    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
+    const int W = d.geom.W, H = d.geom.H;
+    const int total = W * H;
+    const uint8_t* src = srcs[cam * d.B + seq];
+    const short2* m1 = rect_map1(d, cam, seq); const uint16_t* m2 = rect_map2(d, cam, seq);
+    const int slot = begin_frame ? free_slot(d.st[seq]) : d.st[seq].slot_t1;
+    if (begin_frame && blockIdx.x == 0 && cam == 0 && threadIdx.x == 0) frame_begin(d.st[seq]);
+    uint8_t* p0 = d.pyr + pyr_index(d, seq, slot, cam) + d.geom.lv[0].off;
+    const int dstride = d.geom.lv[0].stride;
+    uint8_t* fi = CN == 3 ? d.fastimg + fastimg_index(d, seq, slot) : nullptr;
+    const size_t pb = (size_t)d.geom.pyr_bytes;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int y = i / W, x = i - y * W;
+        uint8_t px[CN];
+        remap_px<CN>(src, stride, d.raw_w, d.raw_h, m1[i], m2[i], px);
+        const size_t o = (size_t)y * dstride + x;
+#pragma unroll
+        for (int c = 0; c < CN; c++) p0[c * pb + o] = px[c];
+        if (CN == 3 && cam == 0) {
+#pragma unroll
+            for (int c = 0; c < CN; c++) if (3 * x + c < W) fi[(size_t)y * W + 3 * x + c] = px[c];
+        }
+    }
+}
+
 // begin_frame: the kernel also performs the per-frame reset of stereo_callback (frame pipeline); the stage entry points pass false
 void launch_ingest(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st, bool begin_frame) {
+    if (d.rmap) {
+        int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
+        if (d.CN == 3) hipLaunchKernelGGL(k_ingest_rect<3>, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
+        else hipLaunchKernelGGL(k_ingest_rect<1>, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
+        return;
+    }
     if (d.CN == 3) {
         int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
         hipLaunchKernelGGL(k_ingest_bgr, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
@@ -192,7 +278,10 @@ __global__ __launch_bounds__(256) void k_pyrdown(DevBuffers d, int level, int ah
 // TW x TH = the block's tile of level 1 (2 TW x 2 TH pixels of level 0).  Lone streams: 32 x 8 (many blocks for one image).  Many-sequence
 // contexts: 64 x 16 — at a thousand images per launch the kernel was bound by block turnover (962 000 blocks of 1 KB of output each:
 // 0.68 ms per 512 sequences = 1.6 TB/s), not by LDS or HBM; four times the work per block and half the halo.
-template <int TW, int TH>
+// RECT (rectifying contexts, d.rmap set): the source tile is filled by remapping the raw frame — tile byte (tx, ty) = the rectified
+// pixel at (reflect101(sx0 + tx), reflect101(sy0 + ty)), the byte the plain form reads from a rectified caller image — and the
+// level-0 store and both pyrDown passes run unchanged on it.  The rectified level 0 never makes a round trip through memory.
+template <int TW, int TH, bool RECT = false>
 static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, const uint8_t* const* srcs, int stride, int begin_frame, int bx, int by, int bz) {
     const int seq = seq_of(d, bz >> 1), cam = bz & 1;
     const LevelInfo ls = d.geom.lv[0], ld = d.geom.lv[1];
@@ -210,7 +299,29 @@ static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, con
     const int ox = bx * TW, oy = by * TH;
     const int sx0 = 2 * ox - 2, sy0 = 2 * oy - 2;
     struct __attribute__((packed, aligned(1))) UD { unsigned v; };
-    if (sx0 >= 0 && sy0 >= 0 && sx0 + SW + 1 <= ls.w && sy0 + SH <= ls.h) {
+    if constexpr (RECT) {
+        const short2* m1 = rect_map1(d, cam, seq); const uint16_t* m2 = rect_map2(d, cam, seq);
+        for (int i = threadIdx.x; i < SW * SH; i += 256) {
+            const int ty = i / SW, tx = i - ty * SW;
+            const int m = reflect101(sy0 + ty, ls.h) * ls.w + reflect101(sx0 + tx, ls.w);
+            remap_px<1>(src, stride, d.raw_w, d.raw_h, m1[m], m2[m], &tile[ty][tx]);
+        }
+        __syncthreads();
+        if (2 * ox + 2 * TW <= ls.w && 2 * oy + 2 * TH <= ls.h) {       // the owned level-0 block lies inside: dword stores as below
+            for (int i = threadIdx.x; i < (TW / 2) * (2 * TH); i += 256) {
+                const int ty = i / (TW / 2), c = i - ty * (TW / 2);
+                const unsigned lo = *reinterpret_cast<const unsigned*>(&tile[ty + 2][4 * c]), hi = *reinterpret_cast<const unsigned*>(&tile[ty + 2][4 * c + 4]);
+                UD u; u.v = __builtin_amdgcn_alignbyte(hi, lo, 2);
+                *reinterpret_cast<UD*>(l0 + (size_t)(2 * oy + ty) * ls.stride + 2 * ox + 4 * c) = u;
+            }
+        } else {
+            for (int i = threadIdx.x; i < 2 * TW * 2 * TH; i += 256) {
+                const int ty = i / (2 * TW), tx = i - ty * (2 * TW);
+                const int gx = 2 * ox + tx, gy = 2 * oy + ty;
+                if (gx < ls.w && gy < ls.h) l0[(size_t)gy * ls.stride + gx] = tile[ty + 2][tx + 2];
+            }
+        }
+    } else if (sx0 >= 0 && sy0 >= 0 && sx0 + SW + 1 <= ls.w && sy0 + SH <= ls.h) {
         constexpr int DPR = (SW + 1) / 4;
         for (int i = threadIdx.x; i < DPR * SH; i += 256) {
             int ty = i / DPR, c = i - ty * DPR;
@@ -269,7 +380,21 @@ template <int TW, int TH>
 __global__ __launch_bounds__(256) void k_ingest_pyr1(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
     ingest_pyr1_body<TW, TH>(d, srcs, stride, begin_frame, blockIdx.x, blockIdx.y, blockIdx.z);
 }
+template <int TW, int TH>
+__global__ __launch_bounds__(256) void k_ingest_pyr1_rect(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
+    ingest_pyr1_body<TW, TH, true>(d, srcs, stride, begin_frame, blockIdx.x, blockIdx.y, blockIdx.z);
+}
 static void launch_ingest_pyr1(const DevBuffers& d, const uint8_t* const* ptrs, int stride, int begin_frame, hipStream_t st) {
+    if (d.rmap) {
+        if (d.B > SVO_LONE_MAX_SEQ) {
+            dim3 g((d.geom.lv[1].w + IG_TW - 1) / IG_TW, (d.geom.lv[1].h + IG_TH - 1) / IG_TH, launch_seqs(d) * 2);
+            hipLaunchKernelGGL((k_ingest_pyr1_rect<IG_TW, IG_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
+        } else {
+            dim3 g((d.geom.lv[1].w + PD_TW - 1) / PD_TW, (d.geom.lv[1].h + PD_TH - 1) / PD_TH, launch_seqs(d) * 2);
+            hipLaunchKernelGGL((k_ingest_pyr1_rect<PD_TW, PD_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
+        }
+        return;
+    }
     if (d.B > SVO_LONE_MAX_SEQ) {
         dim3 g((d.geom.lv[1].w + IG_TW - 1) / IG_TW, (d.geom.lv[1].h + IG_TH - 1) / IG_TH, launch_seqs(d) * 2);
         hipLaunchKernelGGL((k_ingest_pyr1<IG_TW, IG_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
@@ -830,6 +955,12 @@ __global__ __launch_bounds__(256) void k_front_a(DevBuffers d, const uint8_t* co
     const int j = i - n_a;
     fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
 }
+__global__ __launch_bounds__(256) void k_front_a_rect(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
+    const int i = blockIdx.x;
+    if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH, true>(d, srcs, stride, 1, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
+    const int j = i - n_a;
+    fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
+}
 __global__ __launch_bounds__(256) void k_front_b(DevBuffers d, int px, int py, int n_p, int n_rows) {
     const int i = blockIdx.x;
     if (i < n_p) { pyrdown2_body(d, 1, i % px, (i / px) % py, i / (px * py)); return; }
@@ -844,7 +975,8 @@ bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_de
     const int ns = launch_seqs(d);
     const int ax = (d.geom.lv[1].w + PD_TW - 1) / PD_TW, ay = (d.geom.lv[1].h + PD_TH - 1) / PD_TH, n_a = ax * ay * ns * 2;
     const int fx = (d.geom.W + FT_W - 1) / FT_W, fy = (d.geom.H + FT_H - 1) / FT_H, n_f = fx * fy * ns;
-    hipLaunchKernelGGL(k_front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
+    if (d.rmap) hipLaunchKernelGGL(k_front_a_rect, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
+    else hipLaunchKernelGGL(k_front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
     const int px = (d.geom.lv[3].w + P2_TW - 1) / P2_TW, py = (d.geom.lv[3].h + P2_TH - 1) / P2_TH, n_p = px * py * ns * 2;
     const int n_rows = d.cfg.buckets_along_height;
     hipLaunchKernelGGL(k_front_b, dim3(n_p + n_rows * ns), dim3(256), 0, st, d, px, py, n_p, n_rows);

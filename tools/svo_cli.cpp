@@ -2,7 +2,7 @@
 // 315-407) on top of the C++ facade / C-ABI.  SURVEY.md §8 f-1.
 //
 //   svo_cli <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1]
-//                               [--float-sums 1] [--ref-format 1]
+//                               [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml]
 //
 // Reads folder/left/frameNNNNNN.{pgm,png,jpg} (6 digits, as `run1`) or frameNNNN.{jpg,png,pgm} (4 digits, as the reference's
 // other two bundled sets slam_feats/ and rand_feats/, which its current CLI cannot open; tools/jpeg_decode.hpp) and
@@ -21,6 +21,10 @@
 //   * the run stops cleanly at the first missing image pair (the reference throws on run1's frame 128, B-12);
 //   * calibration may come from a YAML file with either key style (stereo_vo.cpp:40-44 `fx:` or kitti00.yaml `Camera.fx:`);
 //     without --calib the hard-coded run1 projection of main.cpp:357-364 is used.
+// `--rectify left.yaml right.yaml` takes RAW frames and their ROS camera_info files (camera_calibration_parsers YAML,
+// tools/camera_info_yaml.hpp): the frames are rectified on the GPU (svo_set_rectification, what stereo_image_proc does on
+// the CPU to publish image_rect) and the projection matrices are the files' P (P_right[0][3] = -fx * baseline is the
+// reference's bf); it overrides --calib.
 #include <zlib.h>
 #include <cmath>
 #include <cstdio>
@@ -33,6 +37,7 @@
 #include <vector>
 #include "svo/visual_odometry.hpp"
 #include "jpeg_decode.hpp"
+#include "camera_info_yaml.hpp"
 using namespace visual_odometry;
 
 struct Gray { int w = 0, h = 0; std::vector<uint8_t> px, bgr; bool ok() const { return w > 0; } };   // px: gray, bgr: interleaved B,G,R
@@ -161,13 +166,16 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
-    std::string calib, out = folder + "/result.csv";
+    std::string calib, out = folder + "/result.csv", rect_l, rect_r;
     bool gray = false, identity_start = false, float_sums = false, ref_format = false;
     for (int i = 3; i + 1 < argc; i += 2) {
-        if (!strcmp(argv[i], "--gray")) gray = std::atoi(argv[i + 1]) != 0;
+        if (!strcmp(argv[i], "--rectify")) {
+            if (i + 2 >= argc) { std::fprintf(stderr, "--rectify needs two camera_info files\n"); return 2; }
+            rect_l = argv[i + 1]; rect_r = argv[i + 2]; i++;
+        } else if (!strcmp(argv[i], "--gray")) gray = std::atoi(argv[i + 1]) != 0;
         else if (!strcmp(argv[i], "--identity-start")) identity_start = std::atoi(argv[i + 1]) != 0;
         else if (!strcmp(argv[i], "--float-sums")) float_sums = std::atoi(argv[i + 1]) != 0;
         else if (!strcmp(argv[i], "--ref-format")) ref_format = std::atoi(argv[i + 1]) != 0;
@@ -178,6 +186,12 @@ int main(int argc, char** argv) {
     Mat34f Pl = {322.11376f, 0, 327.47336f, 0, 0, 322.11376f, 176.33722f, 0, 0, 0, 1, 0};               // main.cpp:357-362
     Mat34f Pr = Pl; Pr[3] = -22.5428f;
     if (!calib.empty() && !read_calibration(calib, Pl, Pr)) { std::fprintf(stderr, "cannot read calibration %s\n", calib.c_str()); return 2; }
+    svo_camera_info ci_l{}, ci_r{};
+    if (!rect_l.empty()) {
+        std::string err;
+        if (!camera_info_yaml::load(rect_l, ci_l, err) || !camera_info_yaml::load(rect_r, ci_r, err)) { std::fprintf(stderr, "--rectify: %s\n", err.c_str()); return 2; }
+        for (int k = 0; k < 12; k++) { Pl[k] = (float)ci_l.P[k]; Pr[k] = (float)ci_r.P[k]; }
+    }
     // ground truth: skip the header line, then drop the first column of every row (main.cpp:336-344, 385-392)
     std::ifstream gt(folder + "/gt.csv");
     const bool has_gt = (bool)gt;
@@ -191,6 +205,7 @@ int main(int argc, char** argv) {
         cfg.lk_float_sums = float_sums ? 1 : 0;
         VisualOdometry vo(cfg);
         vo.initalize_projection_matricies(Pl, Pr);
+        if (!rect_l.empty()) vo.set_rectification(ci_l, ci_r);
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
         if (identity_start) { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(pose, I, sizeof(I)); }
