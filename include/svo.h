@@ -142,12 +142,27 @@ int svo_circular_matching(svo_context* ctx, const uint8_t* left_t1, const uint8_
 /* Diagnostics: VGPRs one SIMD has left beside a full complement of this context's LK waves (-1 unknown).  Several many-sequence
  * contexts on one device overlap their f64 kernels with each other's LK kernel only when this is >= 96.  At the metric's window
  * (w = 21, single channel) it is 32 since round 3 — six waves of 80 registers: the faster LK build wins over the overlap, DESIGN.md
- * section 2 — so such contexts simply take turns; builds that leave >= 96 (w = 31, 3-channel contexts) keep the overlap scheme.  A
- * test pins the figure, so that a change to the LK kernel that alters the regime fails loudly.
+ * section 2 — so such contexts simply take turns.  Builds that leave >= 96 keep the overlap scheme; by the compiler's register
+ * counts (profiles/r04_lk_vgprs.md) those are w = 22 single channel, and with lk_float_sums = 1 w = 17, 19, 23, 28-31 single
+ * channel and w = 10, 12 three-channel.  A test pins the w = 21 figure, so that a change to the LK kernel that alters the
+ * regime fails loudly; another probes which builds reach the overlap scheme and runs them against the oracle.
  * NOTE on locality: creating or destroying ANOTHER context with more than 8 sequences on the same device changes which builds of
  * the PnP / triangulation kernels this context launches from its next frame on (full-register alone; 96-register when the
- * device is shared and the figure above is >= 96) and chains its LK launches behind the other's.  Results are identical either way. */
+ * device is shared and the figure above is >= 96) and chains its LK launches behind the other's.  Results are bit-identical
+ * either way: the 96-register refine sums its terms in the order of the full build.  svo_get_last_frame_path tells which
+ * builds a frame took. */
 int svo_get_lk_registers_left(svo_context* ctx);
+
+/* Diagnostics: the decisions the library made for the most recently ISSUED frame of ctx (svo_process*, svo_submit*), as a
+ * bitmask of SVO_PATH_*; 0 before the first frame and for a frame on which every sequence was idle.  ctx == NULL: those of this
+ * thread's last stage call that runs the f64 kernels (svo_triangulate, svo_camera_to_world).  Host-side bookkeeping only. */
+#define SVO_PATH_LEAN            1   /* the 96-register builds of triangulation / EPnP / refine (shared device, or SVO_FORCE_LEAN=1) */
+#define SVO_PATH_LK_CHAINED      2   /* the LK launch waited for / armed the device's chaining event (several many-sequence contexts) */
+#define SVO_PATH_INGEST_AHEAD    4   /* the pyramids were built ahead on the context's image stream (many sequences) */
+#define SVO_PATH_FRONT_FUSED     8   /* the fused lone-stream front (ingest + pyramid beside detection) */
+#define SVO_PATH_TRI_EPNP_FUSED 16   /* triangulation and the first EPnP chunk in one launch (lone stream) */
+#define SVO_PATH_GRAPH          32   /* the frame replayed a captured hipGraph (SVO_GRAPH=1); the other bits are the capture's */
+int svo_get_last_frame_path(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
 int svo_collect(svo_context* ctx, double* T_out, int* ok_out, svo_frame_stats* stats);

@@ -75,6 +75,12 @@ lib.svo_get_stream.restype = C.c_void_p
 lib.svo_stage_cache_clear.restype = None
 lib.svo_stage_cache_clear.argtypes = []
 lib.svo_get_stream.argtypes = [C.c_void_p]
+lib.svo_get_lk_registers_left.restype = C.c_int
+lib.svo_get_lk_registers_left.argtypes = [C.c_void_p]
+lib.svo_get_last_frame_path.restype = C.c_int
+lib.svo_get_last_frame_path.argtypes = [C.c_void_p]
+# svo_get_last_frame_path bits (svo.h SVO_PATH_*)
+PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
 # ragged / continuous batching (svo.h): active is a host array of n_seq bytes or NULL; Pl / Pr 12 floats each or both NULL
 lib.svo_process_batch_masked.restype = C.c_int
 lib.svo_process_batch_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -98,7 +104,7 @@ lib.svo_rectify_image.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_
 EXPORTS = [
     "svo_last_error", "svo_device_count", "svo_config_default", "svo_create", "svo_destroy", "svo_set_projection",
     "svo_process_batch", "svo_process_batch_masked", "svo_submit_batch_masked", "svo_reset_sequence", "svo_process", "svo_alloc_pinned", "svo_free_pinned", "svo_circular_matching", "svo_submit_batch", "svo_collect", "svo_get_features", "svo_get_last_tracks",
-    "svo_get_lk_registers_left", "svo_get_last_timing", "svo_set_stage_timing", "svo_get_stage_timing", "svo_get_stream", "svo_fast_detect", "svo_fast_score_map", "svo_bucket_filter",
+    "svo_get_lk_registers_left", "svo_get_last_frame_path", "svo_get_last_timing", "svo_set_stage_timing", "svo_get_stage_timing", "svo_get_stream", "svo_fast_detect", "svo_fast_score_map", "svo_bucket_filter",
     "svo_append_features_from_image", "svo_build_pyramid", "svo_lk_track", "svo_circular_match",
     "svo_find_close_points", "svo_stage_cache_clear", "svo_stage_cache_clear_all", "svo_triangulate", "svo_camera_to_world", "svo_inverse_transform",
     "svo_set_rectification_maps", "svo_set_rectification", "svo_clear_rectification", "svo_init_rectify_map", "svo_rectify_image",

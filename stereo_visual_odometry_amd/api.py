@@ -95,6 +95,11 @@ def cameraToWorld(cameraProjection, cameraPoints, worldPoints, rotation, transla
     return (inl[:nin.value].copy(), bool(ok.value)), R.reshape(3, 3), t.reshape(3, 1), iters.value
 
 
+def last_stage_path():
+    """svo_get_last_frame_path(NULL): the SVO_PATH_* bits of this thread's last triangulatePoints / cameraToWorld call."""
+    return lib.svo_get_last_frame_path(None)
+
+
 def getInverseTransform(rotation, translation, device=0):
     """vo.h:469-470"""
     R = np.ascontiguousarray(rotation, np.float64).reshape(9)
@@ -445,6 +450,18 @@ class BatchVisualOdometry:
 
     def stream(self):
         return lib.svo_get_stream(self._h)
+
+    def last_frame_path(self):
+        """svo_get_last_frame_path: the SVO_PATH_* bits (_lib.PATH_*) of the most recently issued frame — which builds and
+        launch shapes it took; 0 before the first frame."""
+        h = getattr(self, "_h", None)                 # a VisualOdometry exists from its first frame on
+        return lib.svo_get_last_frame_path(h) if h is not None and h.value else 0
+
+    def lk_registers_left(self):
+        """svo_get_lk_registers_left: VGPRs a SIMD keeps beside this context's LK waves (>= 96: a shared device runs the
+        96-register f64 builds)."""
+        h = getattr(self, "_h", None)
+        return lib.svo_get_lk_registers_left(h) if h is not None and h.value else -1
 
     def features(self, seq=0):
         cap = 1 << 15

@@ -16,6 +16,13 @@
 
 static thread_local std::string g_err;
 extern "C" const char* svo_last_error(void) { return g_err.c_str(); }
+static thread_local int g_stage_path = 0;                            // svo_get_last_frame_path(NULL): this thread's last stage call
+
+// SVO_FORCE_LEAN=1 (test knob): every context, stage contexts included, takes the 96-register builds of the f64 kernels
+static bool force_lean() {
+    static const bool on = getenv("SVO_FORCE_LEAN") && atoi(getenv("SVO_FORCE_LEAN")) != 0;
+    return on;
+}
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -106,6 +113,8 @@ struct svo_context {
     bool stage_timing = false;                   // record the four stage-boundary events of a frame (svo_set_stage_timing; SVO_STAGE_TIMING=1)
     hipGraphExec_t gexec[SVO_RING] = {};
     int g_stride[SVO_RING] = {}, g_gn[SVO_RING] = {}, g_co[SVO_RING] = {};   // what the slot's graph was captured with (stride, LK grid, co-resident builds)
+    int g_path[SVO_RING] = {};                   // ... and the SVO_PATH_* bits of that capture
+    int last_path = 0;                           // SVO_PATH_* of the most recently issued frame (svo_get_last_frame_path)
     bool staged_slot[SVO_RING] = {};             // the slot's stage events were recorded (launch-list mode only)
     // rectification (svo_set_rectification_maps): raw_w > 0 makes the context take RAW frames.  A map is one device buffer
     // ([W*H] short2 + [W*H] u16) per camera; shared[cam] serves every sequence whose own[seq][cam] is null.  Each frame names its
@@ -257,7 +266,8 @@ extern "C" int svo_create(const svo_config* cfg, int device, int n_seq, int widt
 // Several many-sequence contexts on one device.  Two decisions, both read ONCE per frame (issue_frame); `contexts` is an atomic:
 // contexts are created and destroyed on other threads while this one enqueues frames.
 //  * lk_gated: the f64 kernels run as 96-register builds under the OTHER context's LK grid — only if those builds fit beside it
-//    (lk_registers_left >= 96: w = 31 and the 3-channel builds; not w = 21 since round 3, nor w = 10 / 15).
+//    (lk_registers_left >= 96: w = 22 grey, w = 17 / 23 / 31 grey and w = 10 / 12 BGR with float sums; not w = 21 since round 3,
+//    nor w = 10 / 15 grey, nor w = 31 in the default mode).
 //  * lk_chained: the contexts' LK launches wait for each other (one event per device).  Always, when the device is shared: two
 //    LK grids resident together only share the CUs — measured the same whole-job rate either way at w = 21 (18 370 vs 18 390
 //    frame-pairs/s) — and unchained each launch's duration contains a part of the other's (12.7 ms per launch chained, 13.3-16.4
@@ -311,6 +321,8 @@ extern "C" void* svo_get_stream(svo_context* c) { return c ? (void*)c->stream : 
 
 extern "C" int svo_get_lk_registers_left(svo_context* c) { return c ? c->lk_room : -1; }
 
+extern "C" int svo_get_last_frame_path(svo_context* c) { return c ? c->last_path : g_stage_path; }
+
 extern "C" int svo_set_projection(svo_context* c, int seq, const float Pl[12], const float Pr[12]) {
     if (!c || !Pl || !Pr) return fail_arg("null argument");
     if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
@@ -357,15 +369,18 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         if (with_events) { HIPCHK(hipEventRecord(c->ev_pyr[slot], s)); HIPCHK(hipEventRecord(c->ev_lk0[slot], s)); HIPCHK(hipEventRecord(c->ev_lk1[slot], s)); HIPCHK(hipEventRecord(c->ev_tri[slot], s)); }
         launch_frame_end(d, slot, s);
         c->begin_recorded = false;
+        c->last_path = 0;
         return SVO_OK;
     }
-    static const bool force_lean = getenv("SVO_FORCE_LEAN") && atoi(getenv("SVO_FORCE_LEAN")) != 0;      // test knob: every context takes them
     const bool shares_device = shares < 0 ? lk_gated(c) : shares != 0;   // read once per frame: both uses below see the same answer
-    d.co_resident = (shares_device || force_lean) ? 1 : 0;             // picks the 96-register builds of the f64 kernels (svo_kernels_pnp.hip)
+    d.co_resident = (shares_device || force_lean()) ? 1 : 0;           // picks the 96-register builds of the f64 kernels (svo_kernels_pnp.hip)
+    if (d.co_resident) HIPCHK(prepare_pnp_lean());
+    int path = d.co_resident ? SVO_PATH_LEAN : 0;
     const uint8_t** dp = d.img_ptrs + (size_t)slot * 2 * B;         // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(d);
     if (d.act && !ahead) HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, s));
     if (!ahead && launch_front_fused(d, dp, stride, s)) {              // lone stream: ingest + pyramid beside detection, two launches
+        path |= SVO_PATH_FRONT_FUSED;
         if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));   // stage timers: ms[0] = the fused front, ms[1] ~ 0
         c->begin_recorded = false;
     } else if (ahead) {
@@ -388,6 +403,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_f0[slot], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
         if (d.act) HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, c->img_stream));
         launch_ingest_pyramid_ahead(d, dp, stride, c->img_stream);
+        path |= SVO_PATH_INGEST_AHEAD;
         HIPCHK(hipEventRecord(c->ev_img[slot], c->img_stream));
         HIPCHK(hipStreamWaitEvent(s, c->ev_img[slot], 0));
         launch_frame_begin(d, s);
@@ -407,6 +423,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         LkGate& g = g_lk_gate[c->device];
         std::lock_guard<std::mutex> lock(g.mu);
         if (g.armed) HIPCHK(hipStreamWaitEvent(s, g.ev, 0));
+        path |= SVO_PATH_LK_CHAINED;
     }
     if (with_events) HIPCHK(hipEventRecord(c->ev_lk0[slot], s));
     if (!launch_lk_chain(d, gn, s, 1)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
@@ -421,9 +438,11 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     launch_compact(d, s);
     const bool tri_epnp = launch_triangulate_epnp_fused(d, s);          // lone stream: the first EPnP chunk runs beside the triangulation
     if (!tri_epnp) launch_triangulate(d, s);
+    if (tri_epnp) path |= SVO_PATH_TRI_EPNP_FUSED;
     if (with_events) HIPCHK(hipEventRecord(c->ev_tri[slot], s));       // (fused: the stage timers count that chunk with the triangulation)
     launch_pnp(d, s, tri_epnp);
     launch_frame_end(d, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
+    c->last_path = path;
     return SVO_OK;
 }
 
@@ -485,9 +504,9 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
         // the captured launch list bakes in which builds of the f64 kernels run: a context captured while it had the device to
         // itself must be re-captured once another many-sequence context exists (and back), or it would keep the full-register
         // builds that cannot start beside the other's LK grid
-        static const bool force_lean_g = getenv("SVO_FORCE_LEAN") && atoi(getenv("SVO_FORCE_LEAN")) != 0;
         const int shares_now = lk_gated(c) ? 1 : 0;
-        const int co_now = (shares_now || force_lean_g) ? 1 : 0;
+        const int co_now = (shares_now || force_lean()) ? 1 : 0;
+        if (co_now) HIPCHK(prepare_pnp_lean());                     // before the capture: issue_frame then finds it done
         if (!c->gexec[slot] || c->g_stride[slot] != stride || c->g_gn[slot] != gn || c->g_co[slot] != co_now) {
             if (c->gexec[slot]) { (void)hipGraphExecDestroy(c->gexec[slot]); c->gexec[slot] = nullptr; }
             hipGraph_t g = nullptr;
@@ -503,9 +522,12 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
             if (!ok) {                                                // capture is an optimisation: without it the same launches are issued directly
                 (void)hipGetLastError();
                 c->gexec[slot] = nullptr; c->use_graph = false;
-            } else { c->g_stride[slot] = stride; c->g_gn[slot] = gn; c->g_co[slot] = co_now; }
+            } else { c->g_stride[slot] = stride; c->g_gn[slot] = gn; c->g_co[slot] = co_now; c->g_path[slot] = c->last_path; }
         }
-        if (c->use_graph) { HIPCHK(hipGraphLaunch(c->gexec[slot], s)); replayed = true; c->begin_recorded = false; }
+        if (c->use_graph) {
+            HIPCHK(hipGraphLaunch(c->gexec[slot], s)); replayed = true; c->begin_recorded = false;
+            c->last_path = c->g_path[slot] | SVO_PATH_GRAPH;
+        }
     }
     if (!replayed) { const int rc = issue_frame(c, slot, stride, gn, c->stage_timing, -1, n_act); if (rc != SVO_OK) return rc; }
     c->staged_slot[slot] = !replayed && c->stage_timing;
@@ -901,11 +923,15 @@ static int stage_ctx(const svo_config& cfg_in, int device, int w, int h, int cap
     svo_config cfg = cfg_in;
     if (cfg.channels == 0) cfg.channels = 1;
     StageCache& sc = stage_cache_of_this_thread(cfg, device, w, h, cap);
+    // a stage context never shares the device with another's LK: it takes the 96-register builds only under the test knob
+    const int lean = force_lean() ? 1 : 0;
     if (sc.c && sc.device == device && sc.w == w && sc.h == h && sc.c->d.CAP >= cap) {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(sc.c->stream));
         if (cfg_equal(sc.cfg, cfg) || stage_reconfigure(sc.c, cfg)) {
             sc.cfg = cfg;
+            sc.c->d.co_resident = lean;
+            if (lean) HIPCHK(prepare_pnp_lean());
             *out = sc.c;
             return SVO_OK;
         }
@@ -914,6 +940,8 @@ static int stage_ctx(const svo_config& cfg_in, int device, int w, int h, int cap
     int rc = ctx_create(&cfg, device, 1, w, h, cap, &sc.c);
     if (rc != SVO_OK) { sc.c = nullptr; return rc; }
     sc.cfg = cfg; sc.device = device; sc.w = w; sc.h = h;
+    sc.c->d.co_resident = lean;
+    if (lean) HIPCHK(prepare_pnp_lean());
     *out = sc.c;
     return SVO_OK;
 }
@@ -1156,6 +1184,7 @@ extern "C" int svo_triangulate(int device, const float Pl[12], const float Pr[12
     if ((rc = set_state(c, hs)) != SVO_OK) return rc;
     launch_triangulate(c->d, c->stream);
     HIPCHK(hipGetLastError());
+    g_stage_path = c->d.co_resident ? SVO_PATH_LEAN : 0;
     HIPCHK(hipMemcpyAsync(xyz, c->d.world, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return SVO_OK;
@@ -1182,6 +1211,7 @@ extern "C" int svo_camera_to_world(int device, const float K[9], int n, const fl
     if (n == 4) launch_pnp_p3p(c->d, c->stream);                                 // solvepnp.cpp: npoints == 4 -> one direct P3P
     else { launch_pnp_subsets(c->d, c->stream); launch_pnp(c->d, c->stream); }   // n == 5: one direct EPnP (handled on the device)
     HIPCHK(hipGetLastError());
+    g_stage_path = n > 4 && c->d.co_resident ? SVO_PATH_LEAN : 0;               // (P3P has one build)
     if ((rc = read_state(c, 0, &hs)) != SVO_OK) return rc;
     if (iters_run) *iters_run = hs.pnp_iters;
     if (hs.pnp_best < 0) return SVO_OK;                                          // success = false: R, t untouched (vo.cpp:307-311)

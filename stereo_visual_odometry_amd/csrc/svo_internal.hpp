@@ -143,7 +143,8 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
 bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out);   // false: no kernel built for this (window, channels, summation mode) — nothing ran
 void launch_compact(const DevBuffers& d, hipStream_t s);
 void launch_triangulate(const DevBuffers& d, hipStream_t s);
-void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = false);   // expects the subsets drawn (launch_triangulate / k_compact do it)
+void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = false);
+hipError_t prepare_pnp_lean();   // before the first launch_pnp with co_resident on the current device (the lean EPnP's dynamic LDS)   // expects the subsets drawn (launch_triangulate / k_compact do it)
 bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t s);   // lone stream: triangulation || first EPnP chunk in one launch; false = not applicable
 void launch_pnp_subsets(const DevBuffers& d, hipStream_t s);
 void launch_pnp_p3p(const DevBuffers& d, hipStream_t s);                // exactly four points: one P3P, no RANSAC (stage API only)

@@ -870,7 +870,8 @@ bool lk_window_supported_cn(int win, int cn) { return lk_built(win, cn, false); 
 
 // VGPRs a SIMD has left beside a full complement of this context's LK waves (512 per SIMD lane, allocated in eights, at most 8
 // waves): the 96-register builds of the f64 kernels (svo_kernels_pnp.hip) can run under another context's LK grid only if this
-// is >= 96 — true at w = 21 (100 registers: four waves, 96 left) and 31, not at w = 10 (74: six waves, 32 left).  -1 if unknown.
+// is >= 96 — true at w = 22 grey, and in float-sums mode at w = 17, 23, 31 grey and w = 10, 12 BGR; not at w = 21 (80: six waves,
+// 32 left) nor at w = 31 in the default mode (128: four waves, 0 left).  -1 if unknown.
 int lk_registers_left(const DevBuffers& d) {
     const void* fn = nullptr;
     lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) { fn = (const void*)k_lk_chain<w, cn, fs>; });

@@ -15,6 +15,7 @@
 // the inlier mask is bit-reproducible; the final Levenberg–Marquardt refine runs in one workgroup.
 #include "svo_internal.hpp"
 #include "svo_linalg.hpp"
+#include <atomic>
 
 static __device__ __forceinline__ bool seq_live(const SeqState& s) { return s.active && s.fail_reason == 0; }
 static __device__ int ransac_update_num_iters(double log_num, double ep, int max_iters);
@@ -911,7 +912,17 @@ static __device__ __forceinline__ int lm_red_slot(int lane) {
 }
 
 // The points a thread evaluates stay the same through the whole refine: the first LM_CACHED of them live in registers.
+// Both builds sum over the partition of the full one: PF_THREADS virtual threads, virtual thread v taking points v, v + PF_THREADS,
+// ... in that order, then the wave sums of PF_WAVES virtual waves added in wave order.  A block of THREADS < PF_THREADS runs
+// PF_THREADS / THREADS virtual threads per thread one after the other, so the lean refine gives the full one's bits.
 #define LM_CACHED 4
+template <int THREADS> struct LmPart {
+    static constexpr int V = PF_THREADS / THREADS;                 // virtual threads per thread
+    static constexpr int CPV = LM_CACHED / V;                      // cached points per virtual thread
+    static_assert(V * THREADS == PF_THREADS && CPV * V == LM_CACHED && THREADS % 64 == 0, "refine partition");
+    // the point that entry k of a thread's point cache holds
+    static __device__ __forceinline__ int cached_point(int k) { return threadIdx.x + (k / CPV) * THREADS + (k % CPV) * PF_THREADS; }
+};
 struct LmPoints { float X[LM_CACHED], Y[LM_CACHED], Z[LM_CACHED], u[LM_CACHED], v[LM_CACHED]; bool in[LM_CACHED]; };
 
 static __device__ __forceinline__ void lm_point(double X, double Y, double Z, double cu, double cv, const double* R, const double* dRdr,
@@ -953,23 +964,32 @@ static __device__ __forceinline__ void lm_eval(const DevBuffers& d, const SeqSta
     for (int k = 0; k < 28; k++) acc[k] = 0;
     const double* R = sh.R; const double* dRdr = sh.dRdr;
     const double t0 = sh.param[3], t1 = sh.param[4], t2 = sh.param[5];
-#pragma unroll
-    for (int k = 0; k < LM_CACHED; k++)
-        if (pts.in[k]) lm_point(pts.X[k], pts.Y[k], pts.Z[k], pts.u[k], pts.v[k], R, dRdr, t0, t1, t2, fx, fy, cx, cy, acc);
-    for (int i = threadIdx.x + LM_CACHED * THREADS; i < n; i += THREADS) {              // more tracks than the registers hold
-        if (!d.inlier[o + i]) continue;
-        const float2 c = d.tl1[o + i];
-        lm_point(d.world[3 * (o + i)], d.world[3 * (o + i) + 1], d.world[3 * (o + i) + 2], c.x, c.y, R, dRdr, t0, t1, t2, fx, fy, cx, cy, acc);
-    }
+    using P = LmPart<THREADS>;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const double tot = lm_wave_sums28(acc, lane);
     const int slot = lm_red_slot(lane);
-    if (slot >= 0) sh.red[wv][slot] = tot;
+#pragma unroll
+    for (int v = 0; v < P::V; v++) {                                   // virtual thread vt of the PF_THREADS partition
+        const int vt = threadIdx.x + v * THREADS;
+        if (v > 0) {
+#pragma unroll
+            for (int k = 0; k < 28; k++) acc[k] = 0;
+        }
+#pragma unroll
+        for (int k = v * P::CPV; k < (v + 1) * P::CPV; k++)
+            if (pts.in[k]) lm_point(pts.X[k], pts.Y[k], pts.Z[k], pts.u[k], pts.v[k], R, dRdr, t0, t1, t2, fx, fy, cx, cy, acc);
+        for (int i = vt + P::CPV * PF_THREADS; i < n; i += PF_THREADS) {     // more tracks than the registers hold
+            if (!d.inlier[o + i]) continue;
+            const float2 c = d.tl1[o + i];
+            lm_point(d.world[3 * (o + i)], d.world[3 * (o + i) + 1], d.world[3 * (o + i) + 2], c.x, c.y, R, dRdr, t0, t1, t2, fx, fy, cx, cy, acc);
+        }
+        const double tot = lm_wave_sums28(acc, lane);
+        if (slot >= 0) sh.red[vt >> 6][slot] = tot;
+    }
     __syncthreads();
     if (threadIdx.x < 28) {                                            // wave 0 alone goes on: its thread 0 runs the state machine
         double t = sh.red[0][threadIdx.x];
 #pragma unroll
-        for (int w = 1; w < THREADS / 64; w++) t += sh.red[w][threadIdx.x];
+        for (int w = 1; w < PF_WAVES; w++) t += sh.red[w][threadIdx.x];
         sh.red[0][threadIdx.x] = t;
     }
     if (wv == 0) { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
@@ -1039,7 +1059,7 @@ static __device__ __forceinline__ void pnp_final_body(const DevBuffers& d) {
     LmPoints pts;
 #pragma unroll
     for (int k = 0; k < LM_CACHED; k++) {
-        const int i = threadIdx.x + k * THREADS;
+        const int i = LmPart<THREADS>::cached_point(k);
         pts.in[k] = i < n && d.inlier[o + i];
         const int ii = i < n ? i : 0;
         const float2 c = d.tl1[o + ii];
@@ -1395,18 +1415,23 @@ bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t st) {
     return true;
 }
 
+// k_pnp_epnp_lean's dynamic LDS arena is more than the 64 KB a kernel gets without asking: ask once per device, and report a
+// refusal (the launches would fail) instead of dropping it
+hipError_t prepare_pnp_lean() {
+    static std::atomic<bool> asked[SVO_MAX_DEVICES];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= SVO_MAX_DEVICES || asked[dev].load()) return hipSuccess;
+    e = hipFuncSetAttribute((const void*)k_pnp_epnp_lean, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EP_LEAN_LDS);
+    if (e == hipSuccess) asked[dev].store(true);
+    return e;
+}
+
 void launch_pnp(const DevBuffers& d, hipStream_t st, bool first_chunk_solved) {
     // the subsets were drawn by the last block of k_triangulate (stage entry points go through launch_triangulate too)
     const int c0 = pnp_first_chunk(d);
-    const bool lean = d.co_resident;                                 // see k_triangulate_lean
-    if (lean) {                                                      // more than the 64 KB a kernel gets without asking; per device
-        static bool asked[SVO_MAX_DEVICES];
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < SVO_MAX_DEVICES && !asked[dev]) {
-            (void)hipFuncSetAttribute((const void*)k_pnp_epnp_lean, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EP_LEAN_LDS);
-            asked[dev] = true;
-        }
-    }
+    const bool lean = d.co_resident;                                 // see k_triangulate_lean (the host called prepare_pnp_lean)
     const int hpb = 64 / (lean ? EP_G : EP_G_LONE), ns = launch_seqs(d);
     if (first_chunk_solved) { /* k_tri_epnp did it */ }
     else if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((c0 + hpb - 1) / hpb, ns), dim3(64), EP_LEAN_LDS, st, d, 0, c0);

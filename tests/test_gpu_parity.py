@@ -774,8 +774,9 @@ def test_batch_equals_single(api):
 
 
 def test_two_many_sequence_contexts_sharing_the_device(api):
-    """Contexts of more than 8 sequences that share a GPU launch the 96-register (`_lean`) builds of triangulate / EPnP / refine
-    and chain their LK launches through an event — the configuration bench.py runs.  Two contexts of 10 sequences,
+    """Contexts of more than 8 sequences that share a GPU chain their LK launches through an event — the
+    configuration bench.py runs.  At w = 21 the LK build leaves 32 registers free, so they keep the FULL builds of triangulate /
+    EPnP / refine: the 96-register builds are covered by test_gpu_shared_device_builds.py.  Two contexts of 10 sequences,
     frames submitted interleaved so that their kernels really overlap, an outlier layer so that RANSAC iterates: every
     sequence of both must give the oracle's flags, counters and feature sets, and its pose to the usual tolerance."""
     from stereo_visual_odometry_amd import synthetic as syn
@@ -805,6 +806,8 @@ def test_two_many_sequence_contexts_sharing_the_device(api):
         outs = []
         for c, vo in enumerate(ctx):                                # both contexts in flight before either is collected
             vo.submit_device([dev[pick(c, i)][k][0].data_ptr() for i in range(B)], [dev[pick(c, i)][k][1].data_ptr() for i in range(B)], 480)
+            path = vo.last_frame_path()
+            assert path & api._lib.PATH_LK_CHAINED and not path & api._lib.PATH_LEAN, (k, c, path)   # chained LK, full builds
         for c, vo in enumerate(ctx):
             outs.append(vo.collect())
         for c, vo in enumerate(ctx):
