@@ -240,6 +240,18 @@ int svo_clear_rectification(svo_context* ctx);
 int svo_get_features(svo_context* ctx, int seq, int cap, float* xy, int* ages, int* strengths);
 int svo_get_last_tracks(svo_context* ctx, int seq, int cap, float* pl0, float* pr0, float* pl1, float* pr1,
                         float* world, uint8_t* inlier);
+/* Diagnostics (pyramid tests): one level of one stored pyramid of sequence seq, WITH its stored border — every level keeps a
+ * REFLECT_101 border of `pad` pixels on each side (the LK kernel reads it directly), as cv::buildOpticalFlowPyramid keeps its
+ * winSize border.  out gets (h + 2 pad) rows of (w + 2 pad) bytes, packed, from pixel (-pad, -pad); cap is its size in bytes.
+ * which: SVO_PYR_T1 or SVO_PYR_LAST_LEFT; cam: 0 left, 1 right; plane: 0 .. channels-1 (a BGR context keeps one pyramid per
+ * colour plane); level: 0 .. n_levels-1.  w, h, pad, n_levels may be NULL; they are filled before anything else is checked, and
+ * out == NULL returns SVO_OK after filling them (sizes only, no device access).  SVO_ERR_STATE while frames are in flight, for a
+ * sequence without a frame since its creation or its last reset (the pyramids of a reset sequence are not its own any more), and
+ * for SVO_PYR_LAST_LEFT while no frame has cached that pair.  Bad indices: SVO_ERR_ARG.  Synchronises the context's stream. */
+#define SVO_PYR_T1        0   /* the pyramids of the sequence's last frame (= imageLeftT0_ / imageRightT0_ of the next) */
+#define SVO_PYR_LAST_LEFT 1   /* lastLeftPyramid's slot (vo.cpp:50-53, 179-181, 231-232): may be older than T1 */
+int svo_get_pyramid(svo_context* ctx, int seq, int which, int cam, int plane, int level,
+                    uint8_t* out, int64_t cap, int* w, int* h, int* pad, int* n_levels);
 /* Timing: HIP-event milliseconds of the dominant kernel (the fused LK chain) in the last processed frame, and of the whole frame.
  * With SVO_GRAPH=1 in the environment a context replays each frame as a captured hipGraph (one per results-ring slot; off by
  * default: measured slightly slower than the launch list on MI355X): stage events are then not recorded and lk_ms /

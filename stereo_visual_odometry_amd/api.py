@@ -477,6 +477,25 @@ class BatchVisualOdometry:
         return dict(pl0=a[0][:n].copy(), pr0=a[1][:n].copy(), pl1=a[2][:n].copy(), pr1=a[3][:n].copy(),
                     world=world[:n].copy(), inlier=inl[:n].copy())
 
+    PYRAMIDS = {"t1": _lib.PYR_T1, "last_left": _lib.PYR_LAST_LEFT}
+
+    def pyramid(self, seq, which="t1", cam=0, level=0, plane=0):
+        """One stored pyramid level of sequence `seq` WITH its REFLECT_101 border (svo_get_pyramid) -> (array, pad): a uint8
+        (h + 2 pad, w + 2 pad) array whose [pad:-pad, pad:-pad] is the level.  which: "t1" (the last frame's pyramids) or
+        "last_left" (lastLeftPyramid's pair; cam 1 = lastRightPyramid); plane: colour plane of a BGR context."""
+        wh = self.PYRAMIDS[which]
+        w, h, pad, nl = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(lib.svo_get_pyramid(self._h, seq, wh, cam, plane, level, None, 0, C.byref(w), C.byref(h), C.byref(pad), C.byref(nl)))
+        out = np.zeros((h.value + 2 * pad.value, w.value + 2 * pad.value), np.uint8)
+        check(lib.svo_get_pyramid(self._h, seq, wh, cam, plane, level, ptr(out), out.size, None, None, None, None))
+        return out, pad.value
+
+    def pyramid_levels(self):
+        """Number of levels the context builds (the buildOpticalFlowPyramid stop rule at its window and max_level)."""
+        nl = C.c_int()
+        check(lib.svo_get_pyramid(self._h, 0, _lib.PYR_T1, 0, 0, 0, None, 0, None, None, None, C.byref(nl)))
+        return nl.value
+
 
 class VisualOdometry(BatchVisualOdometry):
     """vo.h:231-380 — one stereo stream.  stereo_callback(left, right) -> (success, 4x4 float64)."""
@@ -546,6 +565,11 @@ class VisualOdometry(BatchVisualOdometry):
         rc = check(lib.svo_process(self._h, ptr(L), ptr(R), L.strides[0], ptr(T), C.byref(st)))
         self.stats = st
         return bool(rc), T.reshape(4, 4)
+
+    def pyramid(self, seq=0, which="t1", cam=0, level=0, plane=0):
+        if not self._created:
+            raise RuntimeError("pyramid: no frame yet (call stereo_callback first)")
+        return super().pyramid(seq, which, cam, level, plane)
 
     def reset(self):
         """Start over as a freshly constructed object with the same projection matrices: the next stereo_callback is a first

@@ -831,6 +831,31 @@ extern "C" int svo_get_last_tracks(svo_context* c, int seq, int cap, float* pl0,
     return hs.n_tracks;
 }
 
+extern "C" int svo_get_pyramid(svo_context* c, int seq, int which, int cam, int plane, int level,
+                               uint8_t* out, int64_t cap, int* w, int* h, int* pad, int* n_levels) {
+    if (!c || seq < 0 || seq >= c->d.B) return fail_arg("bad context / seq");
+    if (which != SVO_PYR_T1 && which != SVO_PYR_LAST_LEFT) return fail_arg("which must be SVO_PYR_T1 or SVO_PYR_LAST_LEFT");
+    if (cam < 0 || cam > 1 || plane < 0 || plane >= c->d.CN) return fail_arg("bad camera / plane");
+    const Geometry& g = c->d.geom;
+    if (level < 0 || level >= g.nlevels) return fail_arg("level out of range");
+    const LevelInfo& L = g.lv[level];
+    if (w) *w = L.w;
+    if (h) *h = L.h;
+    if (pad) *pad = g.pad;
+    if (n_levels) *n_levels = g.nlevels;
+    if (!out) return SVO_OK;
+    const size_t pw = (size_t)L.w + 2 * g.pad, ph = (size_t)L.h + 2 * g.pad;
+    if (cap < (int64_t)(pw * ph)) return fail_arg("out too small: (h + 2 pad) * (w + 2 pad) bytes needed");
+    if (c->inflight > 0) { g_err = "svo_get_pyramid with frames in flight (collect first)"; return SVO_ERR_STATE; }
+    SeqState hs; int rc = read_state(c, seq, &hs); if (rc != SVO_OK) return rc;
+    if (hs.frame_id == 0) { g_err = "the sequence has no frame since its creation or its last reset"; return SVO_ERR_STATE; }
+    const int slot = which == SVO_PYR_T1 ? hs.slot_t1 : hs.slot_pyr_t0;
+    if (slot < 0 || slot >= SVO_PYR_SLOTS) { g_err = "no cached lastLeftPyramid yet"; return SVO_ERR_STATE; }
+    const uint8_t* src = c->d.pyr + pyr_index(c->d, seq, slot, cam) + (size_t)plane * g.pyr_bytes + L.off - (size_t)g.pad * L.stride - g.pad;
+    HIPCHK(hipMemcpy2D(out, pw, src, (size_t)L.stride, pw, ph, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+
 // ================================================================================================
 // Stage-level entry points
 // ================================================================================================

@@ -5,10 +5,14 @@
 // functions they call is restated independently, not translated.
 #include "svo_internal.hpp"
 
+// cv::borderInterpolate(i, n, BORDER_REFLECT_101) for any i: reflect about the first and the last pixel until i lies inside (the
+// rule repeats with period 2n - 2).  A level narrower or shorter than the border pad needs more than one fold: the LK border of
+// k_pad_pyramid reaches up to pad pixels out.  Every other caller stays within one fold of its level for every byte it keeps (the
+// pyrDown taps reach 2 pixels out); the tile positions beyond a level's edge get some in-range pixel too, and are never stored.
 __device__ __forceinline__ int reflect101(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
+    if (n <= 1) return 0;
+    while ((unsigned)i >= (unsigned)n) i = i < 0 ? -i : 2 * n - 2 - i;
+    return i;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -484,11 +488,11 @@ static __device__ __forceinline__ void pyrdown2_body(const DevBuffers& d, int le
 __global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, int ahead) { pyrdown2_body(d, level, blockIdx.x, blockIdx.y, blockIdx.z, ahead); }
 
 // k_pad_pyramid: the REFLECT_101 border of every level of the T1 slot — what cv::buildOpticalFlowPyramid's copyMakeBorder leaves
-// around each level (pyrBorder = BORDER_REFLECT_101).  Pixel (x, y) outside the level takes level(reflect101(y), reflect101(x)) — the
-// same index function the LK kernel's per-byte border path used before the border was materialised, so the values it sees are the
-// same bytes.  One thread per border DWORD (row starts, the pad and pixel (0, 0) are 4-byte aligned): the ring of a level is cut
-// into its top and bottom bands (pad rows of the padded width) and, per image row, the left band and the right band — the latter
-// from the aligned x at or below the level's width, so up to three pixels of the level itself are rewritten with their own values.
+// around each level (pyrBorder = BORDER_REFLECT_101).  Pixel (x, y) outside the level takes level(reflect101(y), reflect101(x)), the
+// iterated borderInterpolate rule over the whole pad, also where the pad is wider than the level.  One thread per border DWORD (row
+// starts, the pad and pixel (0, 0) are 4-byte aligned): the ring of a level is cut into its top and bottom bands (pad rows of the
+// padded width) and, per image row, the left band and the right band — the latter from the aligned x at or below the level's width,
+// so up to three pixels of the level itself are rewritten with their own values.
 // The four source bytes of a dword are consecutive ascending (one unaligned dword load) or descending (load + byte swap) except
 // where a dword straddles a fold of a level narrower than the pad: those go byte by byte.  (First version: one thread, one byte
 // load and one byte store per border pixel — 0.39 ms per 512 sequences; the image stream's kernels run in the gap between two LK

@@ -31,12 +31,6 @@
 #define LK_WBITS 14
 #define DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
 
-__device__ __forceinline__ int reflect101(int i, int n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
-
 // The 64 lanes of a wave cooperate on one feature.  The window is cut into NSEG = W * LPR <= 64 row segments of PPL pixels;
 // lane l owns segment l (lanes from NSEG on are idle).
 template <int W> struct LkLayout {
