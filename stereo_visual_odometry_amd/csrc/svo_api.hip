@@ -174,7 +174,7 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     if (cap_override > d.CAP) d.CAP = cap_override;
     c->lk_grid = (cfg.max_features > 0 && cfg.max_features < d.CAP) ? cfg.max_features : d.CAP;
     make_geometry(d.geom, width, height, cfg.win_w, cfg.max_level, lk_pad_for(cfg.win_w));
-    d.lk_mineig_cut = lk_mineig_cut(cfg.win_w, cfg.optical_flow_min_eig_threshold);
+    d.lk_crit = lk_make_crit(cfg, d.geom);
     {
         double pc = (double)cfg.ransac_confidence; pc = pc > 0. ? pc : 0.; pc = pc < 1. ? pc : 1.;
         d.ransac_log_num = log(1. - pc > 2.2250738585072014e-308 ? 1. - pc : 2.2250738585072014e-308);
@@ -910,7 +910,7 @@ static bool stage_reconfigure(svo_context* c, const svo_config& cfg) {
     DevBuffers& d = c->d;
     d.cfg = cfg; d.K = cfg.ransac_iterations;
     c->lk_grid = (cfg.max_features > 0 && cfg.max_features < d.CAP) ? cfg.max_features : d.CAP;
-    d.lk_mineig_cut = lk_mineig_cut(cfg.win_w, cfg.optical_flow_min_eig_threshold);
+    d.lk_crit = lk_make_crit(cfg, d.geom);
     double pc = (double)cfg.ransac_confidence; pc = pc > 0. ? pc : 0.; pc = pc < 1. ? pc : 1.;
     d.ransac_log_num = log(1. - pc > 2.2250738585072014e-308 ? 1. - pc : 2.2250738585072014e-308);
     c->lk_room = lk_registers_left(d);

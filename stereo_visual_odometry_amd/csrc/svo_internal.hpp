@@ -24,6 +24,11 @@ struct Geometry {
     int pyr_bytes;                            // bytes of one pyramid (all levels with their borders; strides are multiples of 16)
 };
 
+// What the LK kernels need of a configuration, derived once on the host (lk_make_crit): the normalised termination criteria, the
+// minimum-eigenvalue cut-off (lk_mineig_cut), eps_hi / eps_lo bracketing eps2 for the f32 screening of the convergence test, the
+// circular-matching threshold and the image limits as floats.
+struct LkCrit { int max_count; double eps2; float mineig_cut; float eps_hi, eps_lo; float thr, Wf, Hf; };
+
 // Device-resident state of one sequence = the members of the reference's VisualOdometry (include/vo.h:233-269).
 struct SeqState {
     int frame_id;                             // vo.h:234
@@ -59,7 +64,7 @@ struct DevBuffers {
     Geometry geom;
     svo_config cfg;
     int bucket_h, bucket_w;
-    float lk_mineig_cut;                       // LK: numerators below this fail the minimum-eigenvalue test (see lk_mineig_cut())
+    LkCrit lk_crit;                            // LK: lk_make_crit(cfg, geom), recomputed whenever cfg changes
     SeqState* st;                              // [B]
     uint8_t* pyr;                              // [B][SVO_PYR_SLOTS][2 cams][CN planes][pyr_bytes]
     uint8_t* fastimg;                          // CN == 3 only: [B][3 slots][W*H] the first W bytes of every interleaved left row —
@@ -171,6 +176,7 @@ bool lk_window_supported(int win);
 int lk_registers_left(const DevBuffers& d);   // VGPRs per SIMD lane beside a full set of this context's LK waves (-1: unknown)
 bool lk_window_supported_cn(int win, int cn);
 float lk_mineig_cut(int win, double min_eig_threshold);
+LkCrit lk_make_crit(const svo_config& cfg, const Geometry& g);
 
 // ------------------------------------------------------------------------------------------------ subsets (cv::RNG, getSubset)
 // All K 5-subsets of one sequence, drawn with cv::RNG's multiply-with-carry recurrence from the seed (uint64)-1; the number

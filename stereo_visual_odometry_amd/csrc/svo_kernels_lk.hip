@@ -168,13 +168,13 @@ __device__ __forceinline__ void lk_weights(float a, float b, unsigned& w0, unsig
     const float2v mc = __builtin_elementwise_fma(cross, (float2v){SC, SC}, (float2v){MAGIC, MAGIC});   // iw01, iw10 as magic floats
     const float m0 = __builtin_fmaf(p00, SC, MAGIC);                                                   // iw00
     const unsigned m00 = __float_as_uint(m0), m01 = __float_as_uint(mc.x), m10 = __float_as_uint(mc.y);
-    const unsigned iw11 = ((1u << LK_WBITS) + 3u * 0x4B400000u) - (m00 + m01 + m10);
+    unsigned m3;                                                      // m00 + m01 + m10 in one instruction (the compiler emits two adds)
+    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(m3) : "v"(m00), "v"(m01), "v"(m10));
+    const unsigned iw11 = ((1u << LK_WBITS) + 3u * 0x4B400000u) - m3;
     w0 = pack_lo16((int)m00, (int)m01);
     w1 = pack_lo16((int)m10, (int)iw11);
 }
 
-// eps_hi / eps_lo bracket eps2 for the f32 screening of the convergence test (see newton_step)
-struct LkCrit { int max_count; double eps2; float mineig_cut; float eps_hi, eps_lo; };
 // Every per-feature quantity is identical in all lanes of the wave, so every branch on one is wave-uniform.  The compiler
 // cannot prove that (the values live in VGPRs) and would guard each branch with exec-mask bookkeeping and keep loop counters
 // in VGPRs; a ballot of the condition IS uniform by construction and costs nothing extra (v_cmp writes an SGPR pair either
@@ -196,6 +196,17 @@ __device__ __forceinline__ int dot2_keep(unsigned a, unsigned b, int acc) {
     return __builtin_amdgcn_sdot2(__builtin_bit_cast(short2v, a), __builtin_bit_cast(short2v, b), acc, true);
 }
 __device__ __forceinline__ unsigned pack16(int lo, int hi) { return ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16); }
+
+// (a >> S, b >> S) as one packed pair of their low halves, in two instructions: the second shift writes its low half straight into
+// the upper half of the first one's result (SDWA, dst_sel:WORD_1 with the rest preserved) instead of a third instruction packing
+// them.  gfx940 and later need one wait state between a VALU instruction that writes part of a register and a VALU read of that
+// register; the compiler does not see into the asm, so the s_nop is spelled out.
+template <int S>
+__device__ __forceinline__ unsigned shr_pack16(int a, int b) {
+    int r = a >> S;
+    asm("v_ashrrev_i32_sdwa %0, %1, %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\ts_nop 0" : "+v"(r) : "n"(S), "v"(b));
+    return (unsigned)r;
+}
 
 // N bytes at p (any alignment) -> N-1 packed pairs: pair[x] = byte[x] | byte[x+1] << 16 (one v_perm_b32 each)
 template <int N>
@@ -551,17 +562,15 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
 #pragma unroll
             for (int kk = 0; kk < CN; kk++) {
                 int dv[PPL];
-                // J - I, |.| <= 8160; three sweeps so that dependent dot instructions are PPL instructions apart
+                // J - I, |.| <= 8160; two sweeps so that dependent dot instructions are PPL instructions apart, descaled as they are packed
 #pragma unroll
                 for (int jj = 0; jj < PPL; jj++) dv[jj] = dot2_keep(P0[kk][jj], w0, Kr[kk][jj]);
 #pragma unroll
                 for (int jj = 0; jj < PPL; jj++) dv[jj] = dot2(P1[kk][jj], w1, dv[jj]);
 #pragma unroll
-                for (int jj = 0; jj < PPL; jj++) dv[jj] >>= (LK_WBITS - 5);
-#pragma unroll
                 for (int q = 0; q < NPR; q++) {
                     // masked pixels (and the unpaired upper half) have Ix = Iy = 0: whatever mismatch they see contributes an exact zero
-                    const unsigned dp = (2 * q + 1 < PPL) ? pack_lo16(dv[2 * q], dv[2 * q + 1]) : (unsigned)dv[2 * q];
+                    const unsigned dp = (2 * q + 1 < PPL) ? shr_pack16<LK_WBITS - 5>(dv[2 * q], dv[2 * q + 1]) : (unsigned)(dv[2 * q] >> (LK_WBITS - 5));
                     if constexpr (FS) {
                         // per-element products diff * Ix, diff * Iy (exact int32) to LDS; the chain lanes sum them in OpenCV's order
                         const int xs = sg.xs;
@@ -649,15 +658,11 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
     }
 }
 
-// The window segment this lane owns.  Lanes are written threadIdx.x % 64 (here, lk_chain_feature's writer, k_lk_single) and the
-// feature index adds threadIdx.x / 64 (k_lk_chain, k_lk_single) although a block is one wave: the compiler does not fold them,
-// so the feature index stays per lane, and the register allocation of every LK kernel was tuned that way.  Folding them away
-// makes it scalar and moves every kernel's register count (about 6 VGPRs fewer; occupancy up at some windows, down at others)
-// and with it lk_registers_left: a change to measure on its own.
+// The window segment this lane owns (a block is one wave: threadIdx.x is the lane).
 template <int W>
 __device__ __forceinline__ LkSeg lk_segment() {
     using LL = LkLayout<W>;
-    const int li = threadIdx.x % 64;
+    const int li = threadIdx.x;
     LkSeg sg;
     sg.on = li < LL::NSEG;
     const int sc = sg.on ? li : 0;               // idle lanes shadow segment 0 so their loads stay in bounds
@@ -666,15 +671,19 @@ __device__ __forceinline__ LkSeg lk_segment() {
     return sg;
 }
 
-__device__ __forceinline__ LkCrit make_crit(const svo_config& c, float mineig_cut) {
+// The termination criteria and the image limits of a configuration, as the kernels use them: computed once per configuration on the
+// host (svo_api.hip, beside lk_mineig_cut) and passed by value inside DevBuffers, so no wave repeats the f64 arithmetic at entry.
+LkCrit lk_make_crit(const svo_config& c, const Geometry& g) {
     LkCrit k;
     int mc = c.lk_max_count; mc = mc < 0 ? 0 : (mc > 100 ? 100 : mc);       // TermCriteria normalisation (lkpyramid.cpp)
     double e = c.lk_epsilon; e = e < 0. ? 0. : (e > 10. ? 10. : e);
-    k.max_count = mc; k.eps2 = e * e; k.mineig_cut = mineig_cut;
+    k.max_count = mc; k.eps2 = e * e; k.mineig_cut = lk_mineig_cut(c.win_w, c.optical_flow_min_eig_threshold);
     // f32 screen of "dx^2 + dy^2 <= eps2" (the f32 sum is within 2e-7 relative of the exact one): above eps_hi certainly not
     // converged, below eps_lo certainly converged, in between (practically never) the exact f64 comparison decides
     if (k.eps2 > 1e-30) { k.eps_hi = (float)(k.eps2 * 1.00001); k.eps_lo = (float)(k.eps2 * 0.99999); }
     else { k.eps_hi = __builtin_inff(); k.eps_lo = -1.f; }                        // tiny epsilon: always the exact path
+    k.thr = (float)c.circular_matching_success_threshold;                    // findClosePoints takes a float32 (vo.h:432)
+    k.Wf = (float)g.W; k.Hf = (float)g.H;
     return k;
 }
 
@@ -697,8 +706,9 @@ __device__ __forceinline__ LkCrit make_crit(const svo_config& c, float mineig_cu
 // The four passes of ONE feature and its masks: one inlined copy inside k_lk_chain (profiles/experiments/lk_queue_fed_persistent.patch fed the same function from a work queue).
 struct LkSeqCtx { const uint8_t *L0, *R0, *L1, *R1; int seq, buf; };
 template <int W, int CN, bool FS>
-__device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSeqCtx& q, int idx, const LkCrit& crit, float thr, float Wf, float Hf,
-                                                 const LkSeg& sg, int early_out, int* fs_lds) {
+__device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSeqCtx& q, int idx, const LkSeg& sg, int early_out, int* fs_lds) {
+    const LkCrit& crit = d.lk_crit;
+    const float thr = crit.thr, Wf = crit.Wf, Hf = crit.Hf;
     const int seq = q.seq;
     const uint8_t *L0 = q.L0, *R0 = q.R0, *L1 = q.L1, *R1 = q.R1;
     const size_t o = (size_t)seq * d.CAP + idx;
@@ -706,7 +716,7 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
     // the four passes share ONE inlined copy of lk_pass (a loop, not four copies): 4x less code in the instruction cache.
     // Every pass's point is written out and folded into the masks as soon as it exists, so only the running point,
     // the start point and two flags stay live across the passes (fewer registers held through lk_pass).
-    const bool writer = threadIdx.x % 64 == 0;
+    const bool writer = threadIdx.x == 0;
     // per-feature state across the passes, packed so that it holds ONE register through lk_pass (the kernel sits at the edge
     // of its register budget: 104 VGPRs leave room for the other context's f64 kernels, svo_api.hip LkGate): bit 0 = every
     // status so far is 1, bit 1 = every point so far lies inside the image, bits 2-3 = 1 + the first pass (0..2) that
@@ -753,8 +763,9 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
 //   5 waves (81 registers, the compiler's own choice)   1.76 ms / 17 240 frame-pairs/s / 302 MB
 //   6 waves (80 registers, no scratch)                  1.72 ms / 17 650            / 341 MB
 //   7 waves (72 registers, 10 dwords of scratch)        1.72 ms / 17 820            / 842 MB
-// Six: the seventh wave's 1 % is paid with 0.5 GB of scratch traffic per launch (every single-feature wave spills at entry).  Other
-// windows keep the compiler's choice (not measured).  Beside 6 x 80 registers none of the other context's f64 kernels fits, so the
+// Six: the seventh wave's 1 % is paid with 0.5 GB of scratch traffic per launch (every single-feature wave spills at entry).  (Since
+// the feature index is scalar the build needs 68 registers and a seventh wave fits without scratch: re-measured, no faster — see
+// lk_max_waves.)  Other windows keep the compiler's choice (not measured).  Beside 6 x 80 registers none of the other context's f64 kernels fits, so the
 // LkGate chaining (svo_api.hip) switches itself off and the two contexts' LK launches follow each other, each filling the other's tail.
 // Float-sums build at W = 21: FIVE waves per SIMD — its LDS (7.1 KB per one-wave block) allows it and the register cap (96) costs
 // 8 dwords of scratch; measured against four waves without scratch: LK 4.13 vs 4.22 ms per 32-sequence launch, 8 190 vs 7 910
@@ -763,13 +774,25 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
 #define FS_WAVES21 5
 #endif
 template <int W, int CN, bool FS> constexpr int lk_min_waves() { return (W == 21 && CN == 1) ? (FS ? FS_WAVES21 : 6) : 1; }
+// Upper bound (0 = none).  The scalar feature index freed about 13 registers in every build.  The default build needs 68, which would
+// let a seventh wave in (7 x 72 = 504; measured: no faster, the launch is bound by instruction issue): its budget stays six
+// waves' 80, the figure svo_get_lk_registers_left and the LkGate reasoning (svo_api.hip) are pinned to.  The builds that left >= 96
+// registers per SIMD lane before (the shared-device regime, lk_registers_left below) keep their wave count for the same reason: one
+// more LK wave would take the room the other context's 96-register kernels run in.
+template <int W, int CN, bool FS> constexpr int lk_max_waves() {
+    if (!FS) return CN != 1 ? 0 : W == 21 ? 6 : W == 22 ? 4 : 0;
+    if (CN == 3) return W == 10 ? 4 : W == 12 ? 3 : 0;
+    return (W == 17 || W == 19) ? 4 : W == 23 ? 3 : (W >= 28 && W <= 31) ? 2 : 0;
+}
 #ifdef LK_EXP_MINWAVES                      // experiments: -DLK_EXP_MINWAVES=<n> overrides the table
 #define LK_MIN_WAVES(W, CN, FS) LK_EXP_MINWAVES
+#define LK_MAX_WAVES(W, CN, FS) 0
 #else
 #define LK_MIN_WAVES(W, CN, FS) (lk_min_waves<W, CN, FS>())
+#define LK_MAX_WAVES(W, CN, FS) (lk_max_waves<W, CN, FS>())
 #endif
 template <int W, int CN, bool FS>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(LK_MIN_WAVES(W, CN, FS)))) void k_lk_chain(DevBuffers d, int slots, int chunk, int early_out) {
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(LK_MIN_WAVES(W, CN, FS), LK_MAX_WAVES(W, CN, FS)))) void k_lk_chain(DevBuffers d, int slots, int chunk, int early_out) {
     __shared__ __attribute__((aligned(16))) int fs_lds[FS ? LkFs<W, CN>::LDS_INTS : 1];            // float-sums mode only (the default build uses no LDS)
     const int b = blockIdx.x / slots, fb = blockIdx.x - b * slots;
     if (b >= launch_seqs(d)) return;
@@ -784,20 +807,13 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_e
     const uint8_t* L1 = d.pyr + pyr_index(d, seq, s.slot_t1, 0);
     const uint8_t* R1 = d.pyr + pyr_index(d, seq, s.slot_t1, 1);
     const LkSeqCtx sc = {L0, R0, L1, R1, seq, s.feat_buf};
-    const LkCrit crit = make_crit(d.cfg, d.lk_mineig_cut);
-    const float thr = (float)d.cfg.circular_matching_success_threshold;                // findClosePoints takes a float32 (vo.h:432)
-    const float Wf = (float)d.geom.W, Hf = (float)d.geom.H;
     const LkSeg sg = lk_segment<W>();
     // this block's feature in every round of `slots`: the r-th block of XCD x works in that XCD's q-th run.  slots is a multiple
     // of 8 * chunk, so fb & 7 == blockIdx.x & 7 is the XCD and f runs over 0 .. slots - 1 once as fb does
     const int x = fb & 7, r = fb >> 3;
     const int q = r / chunk;
     const int f = (q * 8 + x) * chunk + (r - q * chunk);
-    for (int base = f; base < n; base += slots) {
-        const int idx = base + threadIdx.x / 64;                      // / 64: see lk_segment
-        if (idx >= n) continue;
-        lk_chain_feature<W, CN, FS>(d, sc, idx, crit, thr, Wf, Hf, sg, early_out, fs_lds);
-    }
+    for (int idx = f; idx < n; idx += slots) lk_chain_feature<W, CN, FS>(d, sc, idx, sg, early_out, fs_lds);
 }
 
 // ---- single pass, for the cv::calcOpticalFlowPyrLK-shaped stage API ----
@@ -806,14 +822,11 @@ __global__ __launch_bounds__(64) void k_lk_single(DevBuffers d, int slotA, int c
                                                   const float2* prev, float2* next, uint8_t* status) {
     const uint8_t* A = d.pyr + pyr_index(d, 0, slotA, camA);
     const uint8_t* Bp = d.pyr + pyr_index(d, 0, slotB, camB);
-    const LkCrit crit = make_crit(d.cfg, d.lk_mineig_cut);
     const LkSeg sg = lk_segment<W>();
-    for (int base = blockIdx.x; base < n; base += gridDim.x) {
-        const int idx = base + threadIdx.x / 64;                      // / 64: see lk_segment
-        if (idx >= n) continue;
+    for (int idx = blockIdx.x; idx < n; idx += gridDim.x) {
         float2 p = prev[idx], q; int st, nv = 0, ns = 0;
-        lk_pass<W, 1>(d.geom, A, Bp, 0, p.x, p.y, q.x, q.y, st, crit, sg, nv, ns);
-        if (threadIdx.x % 64 == 0) { next[idx] = q; status[idx] = (uint8_t)st; }
+        lk_pass<W, 1>(d.geom, A, Bp, 0, p.x, p.y, q.x, q.y, st, d.lk_crit, sg, nv, ns);
+        if (threadIdx.x == 0) { next[idx] = q; status[idx] = (uint8_t)st; }
     }
 }
 
@@ -864,14 +877,18 @@ bool lk_window_supported_cn(int win, int cn) { return lk_built(win, cn, false); 
 
 // VGPRs a SIMD has left beside a full complement of this context's LK waves (512 per SIMD lane, allocated in eights, at most 8
 // waves): the 96-register builds of the f64 kernels (svo_kernels_pnp.hip) can run under another context's LK grid only if this
-// is >= 96 — true at w = 22 grey, and in float-sums mode at w = 17, 23, 31 grey and w = 10, 12 BGR; not at w = 21 (80: six waves,
-// 32 left) nor at w = 31 in the default mode (128: four waves, 0 left).  -1 if unknown.
+// is >= 96 — true at w = 22 grey, and in float-sums mode at w = 17, 19, 23, 28 .. 31 grey and w = 10, 12 BGR (lk_max_waves keeps
+// them there), and at the small windows whose eight waves are small (w <= 10 grey); not at w = 21 (six waves of 80: 32 left).
+// profiles/r05_lk_vgprs.md has every build.  -1 if unknown.
 int lk_registers_left(const DevBuffers& d) {
     const void* fn = nullptr;
-    lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) { fn = (const void*)k_lk_chain<w, cn, fs>; });
+    int cap = 0;
+    lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) { fn = (const void*)k_lk_chain<w, cn, fs>; cap = LK_MAX_WAVES(w, cn, fs); });
     hipFuncAttributes at;
     if (!fn || hipFuncGetAttributes(&at, fn) != hipSuccess || at.numRegs <= 0) return -1;
-    const int alloc = (at.numRegs + 7) / 8 * 8;
+    int alloc = (at.numRegs + 7) / 8 * 8;
+    // a kernel capped at `cap` waves is allocated at least the smallest block that keeps wave cap + 1 out, whatever it uses
+    if (cap > 0) { const int floor = 512 / (cap + 1) / 8 * 8 + 8; if (alloc < floor) alloc = floor; }
     int waves = 512 / alloc; if (waves > 8) waves = 8;
     return 512 - waves * alloc;
 }
