@@ -361,11 +361,13 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     hipStream_t s = c->stream;
     struct ActReset { DevBuffers& d; ~ActReset() { d.act = nullptr; d.n_act = 0; d.rmap = nullptr; } } act_reset{d};   // other launches see an unmasked, plain context
     if (c->raw_w > 0) d.rmap = c->d_maps + (size_t)slot * 2 * B;     // the frame's own maps (enqueue_frame filled the row)
-    const size_t act_bytes = sizeof(int) * 2 * (size_t)B;
-    const int* h_act = c->h_act + (size_t)slot * 2 * B;
+    // the slot's row of h_act to the device, on the stream of the frame's first kernel
+    const auto upload_act = [&](hipStream_t st) {
+        return hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, c->h_act + (size_t)slot * 2 * B, sizeof(int) * 2 * (size_t)B, hipMemcpyHostToDevice, st);
+    };
     if (n_act >= 0) { d.act = c->d_act + (size_t)slot * 2 * B; d.n_act = n_act; }
     if (d.act && n_act == 0) {                                         // all idle: the result rows are the whole frame
-        HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(upload_act(s));
         if (with_events) { HIPCHK(hipEventRecord(c->ev_pyr[slot], s)); HIPCHK(hipEventRecord(c->ev_lk0[slot], s)); HIPCHK(hipEventRecord(c->ev_lk1[slot], s)); HIPCHK(hipEventRecord(c->ev_tri[slot], s)); }
         launch_frame_end(d, slot, s);
         c->begin_recorded = false;
@@ -378,7 +380,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     int path = d.co_resident ? SVO_PATH_LEAN : 0;
     const uint8_t** dp = d.img_ptrs + (size_t)slot * 2 * B;         // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(d);
-    if (d.act && !ahead) HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, s));
+    if (d.act && !ahead) HIPCHK(upload_act(s));
     if (!ahead && launch_front_fused(d, dp, stride, s)) {              // lone stream: ingest + pyramid beside detection, two launches
         path |= SVO_PATH_FRONT_FUSED;
         if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));   // stage timers: ms[0] = the fused front, ms[1] ~ 0
@@ -401,8 +403,8 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
             HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));
         }
         if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_f0[slot], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
-        if (d.act) HIPCHK(hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, h_act, act_bytes, hipMemcpyHostToDevice, c->img_stream));
-        launch_ingest_pyramid_ahead(d, dp, stride, c->img_stream);
+        if (d.act) HIPCHK(upload_act(c->img_stream));
+        launch_ingest_pyramid(d, dp, stride, c->img_stream, PYR_NEXT);
         path |= SVO_PATH_INGEST_AHEAD;
         HIPCHK(hipEventRecord(c->ev_img[slot], c->img_stream));
         HIPCHK(hipStreamWaitEvent(s, c->ev_img[slot], 0));
@@ -412,7 +414,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         launch_detect(d, 0, -1, s);
         launch_detect(d, 1, -1, s);
     } else {
-        launch_ingest_pyramid(d, dp, stride, s, true);                // + the per-frame reset
+        launch_ingest_pyramid(d, dp, stride, s, PYR_BEGIN);           // + the per-frame reset
         c->begin_recorded = false;
         if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));
         launch_detect(d, 0, -1, s);
@@ -734,8 +736,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
         svo_context* c; const SeqState* st; bool armed = true;
         ~Restore() { if (armed) { (void)hipMemcpyAsync(c->d.st, st, sizeof(SeqState), hipMemcpyHostToDevice, c->stream); (void)hipStreamSynchronize(c->stream); } }
     } restore{c, &keep};
-    int t1 = 0;
-    for (int k = 0; k < 3; k++) if (k != hs.slot_img_t0 && k != hs.slot_pyr_t0) { t1 = k; break; }
+    const int t1 = free_slot(hs);
     // the points go into the idle half of the feature double-buffer (scratch between frames); the state is put back below
     hs.slot_t1 = t1; hs.active = 1; hs.feat_buf = keep.feat_buf ^ 1; hs.n_feat = n;
     HIPCHK(hipMemcpyAsync(c->d.feat_xy[hs.feat_buf], pl0, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
@@ -749,7 +750,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
         if (!c->h_maps[0] || !c->h_maps[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
         c->d.rmap = c->d_maps;
     }
-    launch_ingest_pyramid(c->d, c->d.img_ptrs, in_width(c) * c->d.CN, c->stream, false);          // vo.cpp:200-201
+    launch_ingest_pyramid(c->d, c->d.img_ptrs, in_width(c) * c->d.CN, c->stream, PYR_T1);          // vo.cpp:200-201
     c->d.rmap = nullptr;
     if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // vo.cpp:203-230 (the caller gets every pass's raw points)
     HIPCHK(hipGetLastError());

@@ -127,18 +127,38 @@ __host__ __device__ inline size_t fastimg_index(const DevBuffers& d, int seq, in
 #define SVO_MAX_DEVICES 64
 __host__ __device__ inline int pnp_first_chunk(const DevBuffers& d) { const int c = d.B <= SVO_LONE_MAX_SEQ ? 32 : 16; return d.K < c ? d.K : c; }
 
+// ---- the pyramid slot rule: which of a sequence's SVO_PYR_SLOTS slots a set of pyramids is built in ----
+//   PYR_T1     the T1 slot as it stands (stage entry points; every kernel that follows a frame's reset)
+//   PYR_BEGIN  the frame pipeline's own ingest: the free slot, and the ingest also runs the per-frame reset, which names it T1
+//   PYR_NEXT   ahead of the frame (image stream): SeqState::slot_next, which k_pick_next chose; nothing of the state is written
+enum PyrTarget { PYR_T1, PYR_BEGIN, PYR_NEXT };
+// the slot neither cached member refers to: a function of two fields the per-frame reset does not write, so every block of the
+// ingest that runs the reset derives it for itself
+__host__ __device__ inline int free_slot(const SeqState& s) {
+    int t1 = 0;
+    for (int c = 0; c < 3; c++) if (c != s.slot_img_t0 && c != s.slot_pyr_t0) { t1 = c; break; }
+    return t1;
+}
+// the slot no field refers to while a frame is in flight: where the NEXT frame's pyramids can be built ahead of time.  Read at any
+// moment of the current frame (even while k_frame_end rewrites the fields: the set in use only shrinks there) it is free.
+__host__ __device__ inline int next_slot(const SeqState& s) {
+    const int a = s.slot_img_t0, b = s.slot_pyr_t0, t = s.slot_t1;
+    for (int c = 0; c < SVO_PYR_SLOTS; c++) if (c != a && c != b && c != t) return c;
+    return 0;
+}
+__host__ __device__ inline int pyr_slot(const SeqState& s, PyrTarget target) {
+    return target == PYR_NEXT ? s.slot_next : target == PYR_BEGIN ? free_slot(s) : s.slot_t1;
+}
+
 // ---- launchers (each enqueues on `s`; none synchronises) ----
-void launch_ingest(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs /* [2][B] device-readable array */, int stride_bytes, hipStream_t s,
-                   bool begin_frame /* also run the per-frame reset of stereo_callback */);
 void launch_pyramid(const DevBuffers& d, hipStream_t s);                 // levels 1.. of the T1 slot from its level 0, then the borders of all levels
-void launch_pad_pyramid(const DevBuffers& d, hipStream_t s);             // REFLECT_101 borders of every level of the T1 slot (both cameras, every plane)
 int lk_pad_for(int win);                                                 // border width the LK kernel's reads need at this window (svo_kernels_lk.hip)
-void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride_bytes, hipStream_t s, bool begin_frame);   // both, fewer launches
-// The same for the NEXT frame, on another stream, while the current frame is still being processed: the pyramids go into the slot no
-// field of the sequence state refers to (SeqState::slot_next) and nothing else of the state is touched; launch_frame_begin (on the
-// frame's own stream, after that work) then performs the per-frame reset with that slot as T1.  Single-channel contexts with >= 2 levels.
+// Ingest + every pyramid level + the borders, into the target's slot.  PYR_NEXT is the NEXT frame's, on another stream, while the
+// current frame is still being processed (single-channel contexts with >= 2 levels: ingest_ahead_applies): k_pick_next names the
+// slot first, and launch_frame_begin (on the frame's own stream, after that work) then performs the per-frame reset with it as T1.
+void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs /* [2][B] device-readable array */, int stride_bytes, hipStream_t s,
+                           PyrTarget target);
 bool ingest_ahead_applies(const DevBuffers& d);
-void launch_ingest_pyramid_ahead(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride_bytes, hipStream_t s);
 void launch_frame_begin(const DevBuffers& d, hipStream_t s);
 // svo_reset_sequence (seq = -1: all): the constructor's fields, and the projection when `set`; stream-ordered, no host sync
 struct SeqProjection { float Pl[12], Pr[12]; int set; };

@@ -69,30 +69,24 @@ void launch_rectify_image(const short2* map1, const uint16_t* map2, int w, int h
 // pyramid cache in circularMatching (vo.cpp:179-181 vs 231-232: the cache is NOT refreshed when
 // there were no points to match — the "stale pyramid" quirk).
 // ------------------------------------------------------------------------------------------------
-// The per-frame reset, run by one thread per sequence inside the ingest kernel (begin_frame).  The T1 slot is a function of two
-// fields the reset does not write, so every ingest block derives it for itself.  (The bucket keys need no clearing: every
-// detection pass leaves them zero, see k_bucket_emit.)
-__device__ __forceinline__ int free_slot(const SeqState& s) {
-    int t1 = 0;
-    for (int c = 0; c < 3; c++) if (c != s.slot_img_t0 && c != s.slot_pyr_t0) { t1 = c; break; }
-    return t1;
-}
-// the slot no field refers to while a frame is in flight: where the NEXT frame's pyramids can be built ahead of time.  Read at any
-// moment of the current frame (even while k_frame_end rewrites the fields: the set in use only shrinks there) it is free.
-__device__ __forceinline__ int next_slot(const SeqState& s) {
-    const int a = s.slot_img_t0, b = s.slot_pyr_t0, t = s.slot_t1;
-    for (int c = 0; c < SVO_PYR_SLOTS; c++) if (c != a && c != b && c != t) return c;
-    return 0;
-}
-__device__ __forceinline__ void frame_begin(SeqState& s, int t1 = -1) {
+// The per-frame reset with t1 as the frame's T1 slot: run once per sequence, by a thread of the ingest kernel (PYR_BEGIN) or by
+// k_frame_begin.  (The bucket keys need no clearing: every detection pass leaves them zero, see k_bucket_emit.)
+__device__ __forceinline__ void frame_begin(SeqState& s, int t1) {
     s.n_old = s.n_feat;
     s.active = s.frame_id > 0;
-    s.slot_t1 = t1 >= 0 ? t1 : free_slot(s);
+    s.slot_t1 = t1;
     s.do_second = 0; s.n_lk = 0; s.n_tracks = 0; s.n_circ = 0; s.n_inliers = 0; s.ok = 0;
     s.pnp_best = -1; s.pnp_iters = 0; s.pnp_good = 0; s.pnp_drawn = 0;
     s.fail_reason = s.active ? 0 : 1;
     svo_frame_stats z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     s.stats = z;
+}
+// The slot an ingest block writes.  PYR_BEGIN: the thread for which `first` holds (one per sequence: camera 0, block (0, 0),
+// thread 0) also runs the reset; the other blocks need not wait for it, pyr_slot() reads no field the reset writes.
+__device__ __forceinline__ int ingest_slot(const DevBuffers& d, int seq, PyrTarget target, bool first) {
+    const int slot = pyr_slot(d.st[seq], target);
+    if (target == PYR_BEGIN && first) frame_begin(d.st[seq], slot);
+    return slot;
 }
 
 // One thread per sequence of the context, idle ones included: an idle sequence (ragged frame, d.act[B + seq] == 0) gets the row
@@ -130,63 +124,21 @@ void launch_frame_end(const DevBuffers& d, int ring_slot, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// ingest: copy the caller's two images into level 0 of the T1 pyramid slot (the deep copies of
-// vo.cpp:74-75 / the level-0 copy of cv::buildOpticalFlowPyramid).  One thread = 4 pixels of a row.
+// ingest: the caller's two images into level 0 of the target's pyramid slot (the deep copies of vo.cpp:74-75 / the level-0 copy of
+// cv::buildOpticalFlowPyramid), one thread per pixel.  CN = 3: interleaved BGR rows -> three planes (level 0 of the three
+// per-plane pyramids).  RECT (rectifying contexts, d.rmap set): a pixel is the remap of the raw frame at the map's position
+// instead of the caller's bytes.  Colour contexts also keep, for the left camera, the W x H byte image made of the first W bytes
+// of every interleaved row — of every RECTIFIED interleaved row when rectifying — which is what cv::FAST scans in a 3-channel Mat
+// (the reference quirk of svo.h, channels): bytes 3x .. 3x + 2 of that row are pixel x's three channels, so the threads of
+// pixels x < W / 3 write them.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ingest(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
-    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
-    const int W = d.geom.W, H = d.geom.H;
-    const int quads_per_row = (W + 3) >> 2;
-    const int total = quads_per_row * H;
-    const uint8_t* src = srcs[cam * d.B + seq];
-    const int slot = begin_frame ? free_slot(d.st[seq]) : d.st[seq].slot_t1;
-    if (begin_frame && blockIdx.x == 0 && cam == 0 && threadIdx.x == 0) frame_begin(d.st[seq]);
-    uint8_t* dst = d.pyr + pyr_index(d, seq, slot, cam) + d.geom.lv[0].off;
-    const int dstride = d.geom.lv[0].stride;
-    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < total; q += gridDim.x * blockDim.x) {
-        int y = q / quads_per_row, x = (q - y * quads_per_row) << 2;
-        const uint8_t* sp = src + (size_t)y * stride + x;
-        uint8_t* dp = dst + (size_t)y * dstride + x;
-        int n = W - x < 4 ? W - x : 4;
-        for (int k = 0; k < n; k++) dp[k] = sp[k];
-    }
-}
-
-// Colour form: interleaved BGR rows -> three planes (level 0 of the three per-plane pyramids) and, for the left camera, the
-// W x H byte image made of the first W bytes of every row, which is what cv::FAST scans in a 3-channel Mat.
-__global__ __launch_bounds__(256) void k_ingest_bgr(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
+template <int CN, bool RECT>
+__global__ __launch_bounds__(256) void k_ingest(DevBuffers d, const uint8_t* const* srcs, int stride, PyrTarget target) {
     const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
     const int W = d.geom.W, H = d.geom.H;
     const int total = W * H;
     const uint8_t* src = srcs[cam * d.B + seq];
-    const int slot = begin_frame ? free_slot(d.st[seq]) : d.st[seq].slot_t1;
-    if (begin_frame && blockIdx.x == 0 && cam == 0 && threadIdx.x == 0) frame_begin(d.st[seq]);
-    uint8_t* p0 = d.pyr + pyr_index(d, seq, slot, cam) + d.geom.lv[0].off;
-    const int dstride = d.geom.lv[0].stride;
-    uint8_t* fi = d.fastimg + fastimg_index(d, seq, slot);
-    const size_t pb = (size_t)d.geom.pyr_bytes;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int y = i / W, x = i - y * W;
-        const uint8_t* sp = src + (size_t)y * stride;
-        const size_t o = (size_t)y * dstride + x;
-        p0[o] = sp[3 * x]; p0[pb + o] = sp[3 * x + 1]; p0[2 * pb + o] = sp[3 * x + 2];
-        if (cam == 0) fi[i] = sp[x];
-    }
-}
-
-// Rectifying form of k_ingest (CN = 1) and k_ingest_bgr (CN = 3): level-0 pixel (x, y) of every plane is the remap of the raw
-// frame at the map's position.  The FAST image of a colour context is the first W bytes of every RECTIFIED interleaved row (the
-// reference quirk of svo.h, channels): bytes 3x .. 3x + 2 of that row are pixel x's three channels, so the threads of pixels
-// x < W / 3 write them — no remap is done twice.
-template <int CN>
-__global__ __launch_bounds__(256) void k_ingest_rect(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
-    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
-    const int W = d.geom.W, H = d.geom.H;
-    const int total = W * H;
-    const uint8_t* src = srcs[cam * d.B + seq];
-    const short2* m1 = rect_map1(d, cam, seq); const uint16_t* m2 = rect_map2(d, cam, seq);
-    const int slot = begin_frame ? free_slot(d.st[seq]) : d.st[seq].slot_t1;
-    if (begin_frame && blockIdx.x == 0 && cam == 0 && threadIdx.x == 0) frame_begin(d.st[seq]);
+    const int slot = ingest_slot(d, seq, target, blockIdx.x == 0 && cam == 0 && threadIdx.x == 0);
     uint8_t* p0 = d.pyr + pyr_index(d, seq, slot, cam) + d.geom.lv[0].off;
     const int dstride = d.geom.lv[0].stride;
     uint8_t* fi = CN == 3 ? d.fastimg + fastimg_index(d, seq, slot) : nullptr;
@@ -194,7 +146,11 @@ __global__ __launch_bounds__(256) void k_ingest_rect(DevBuffers d, const uint8_t
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int y = i / W, x = i - y * W;
         uint8_t px[CN];
-        remap_px<CN>(src, stride, d.raw_w, d.raw_h, m1[i], m2[i], px);
+        if constexpr (RECT) remap_px<CN>(src, stride, d.raw_w, d.raw_h, rect_map1(d, cam, seq)[i], rect_map2(d, cam, seq)[i], px);
+        else {
+#pragma unroll
+            for (int c = 0; c < CN; c++) px[c] = src[(size_t)y * stride + CN * x + c];
+        }
         const size_t o = (size_t)y * dstride + x;
 #pragma unroll
         for (int c = 0; c < CN; c++) p0[c * pb + o] = px[c];
@@ -204,105 +160,120 @@ __global__ __launch_bounds__(256) void k_ingest_rect(DevBuffers d, const uint8_t
         }
     }
 }
-
-// begin_frame: the kernel also performs the per-frame reset of stereo_callback (frame pipeline); the stage entry points pass false
-void launch_ingest(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st, bool begin_frame) {
-    if (d.rmap) {
-        int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
-        if (d.CN == 3) hipLaunchKernelGGL(k_ingest_rect<3>, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
-        else hipLaunchKernelGGL(k_ingest_rect<1>, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
-        return;
-    }
-    if (d.CN == 3) {
-        int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
-        hipLaunchKernelGGL(k_ingest_bgr, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
-        return;
-    }
-    int total = ((d.geom.W + 3) >> 2) * d.geom.H;
-    int gx = (total + 255) / 256; if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(k_ingest, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, left_right_dev_ptrs, stride, (int)begin_frame);
+template <int CN, bool RECT>
+static void launch_ingest_as(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
+    hipLaunchKernelGGL((k_ingest<CN, RECT>), dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, ptrs, stride, target);
+}
+static void launch_ingest(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    if (d.CN == 3) { if (d.rmap) launch_ingest_as<3, true>(d, ptrs, stride, target, st); else launch_ingest_as<3, false>(d, ptrs, stride, target, st); }
+    else { if (d.rmap) launch_ingest_as<1, true>(d, ptrs, stride, target, st); else launch_ingest_as<1, false>(d, ptrs, stride, target, st); }
 }
 
 // ------------------------------------------------------------------------------------------------
 // pyrDown (the level loop of cv::buildOpticalFlowPyramid, vo.cpp:50,52,200,201):
 // dst(x,y) = (sum_{i,j} k_i k_j src(2x+i-2, 2y+j-2) + 128) >> 8, k = [1 4 6 4 1], REFLECT_101.
-// 32x8 output tile per 256-thread block, source tile staged in LDS, separable in two LDS passes.
+// A 256-thread block owns a TW x TH output tile: the (2 TW + 3) x (2 TH + 3) source tile staged in LDS, separable in two LDS
+// passes.  The pieces below are shared by every pyrDown kernel; the LDS arrays are declared by the kernel bodies (k_front_a and
+// k_front_b run one of them beside a detection body in one launch) and passed in.
 // ------------------------------------------------------------------------------------------------
-#define PD_TW 32
-#define PD_TH 8
-__global__ __launch_bounds__(256) void k_pyrdown(DevBuffers d, int level, int ahead) {
-    const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;          // every colour plane is its own pyramid
-    const int seq = seq_of(d, sc / 2), cam = sc & 1;
-    const LevelInfo ls = d.geom.lv[level - 1], ld = d.geom.lv[level];
-    uint8_t* base = d.pyr + pyr_index(d, seq, ahead ? d.st[seq].slot_next : d.st[seq].slot_t1, cam) + (size_t)plane * d.geom.pyr_bytes;
-    const uint8_t* src = base + ls.off;
-    uint8_t* dst = base + ld.off;
-    constexpr int SW = 2 * PD_TW + 3, SH = 2 * PD_TH + 3;        // 67 x 19 source tile
-    __shared__ __attribute__((aligned(4))) uint8_t tile[SH][SW + 1];
-    __shared__ unsigned short hrow[SH][PD_TW];                   // horizontal pass result (<= 16*255)
-    const int ox = blockIdx.x * PD_TW, oy = blockIdx.y * PD_TH;
-    const int sx0 = 2 * ox - 2, sy0 = 2 * oy - 2;
-    if (sx0 >= 0 && sy0 >= 0 && sx0 + SW + 1 <= ls.w && sy0 + SH <= ls.h) {
-        // interior tile (almost all of them): 17 unaligned dword loads per source row, no border arithmetic
-        static_assert((SW + 1) % 4 == 0, "tile rows are whole dwords");
-        struct __attribute__((packed, aligned(1))) UD { unsigned v; };
-        constexpr int DPR = (SW + 1) / 4;
+struct __attribute__((packed, aligned(1))) UD { unsigned v; };          // a dword at any byte address
+__device__ __forceinline__ unsigned tap5(unsigned a, unsigned b, unsigned c, unsigned d, unsigned e) { return c * 6 + (b + d) * 4 + a + e; }
+__device__ __forceinline__ unsigned pd_round(unsigned v) { return (v + 128) >> 8; }   // v = a sum of 25 products: <= 256 * 255
+
+// The SW x SH source tile whose first pixel is (sx0, sy0) of a w x h level.  A tile whose padded rows (TS bytes: whole dwords) lie
+// inside the level — almost all of them — is TS / 4 unaligned dword loads per row, no border arithmetic; any other one takes
+// reflected bytes, and its columns SW .. TS - 1 stay unwritten (read by the paired pass below, never used).
+template <int SW, int SH, int TS>
+__device__ __forceinline__ void pd_fill_tile(uint8_t (&tile)[SH][TS], const uint8_t* src, int stride, int w, int h, int sx0, int sy0) {
+    static_assert(TS % 4 == 0 && TS > SW, "tile rows are whole dwords");
+    if (sx0 >= 0 && sy0 >= 0 && sx0 + TS <= w && sy0 + SH <= h) {
+        constexpr int DPR = TS / 4;
         for (int i = threadIdx.x; i < DPR * SH; i += 256) {
-            int ty = i / DPR, c = i - ty * DPR;
-            const unsigned v = reinterpret_cast<const UD*>(src + (size_t)(sy0 + ty) * ls.stride + sx0 + 4 * c)->v;
-            *reinterpret_cast<unsigned*>(&tile[ty][4 * c]) = v;
+            const int ty = i / DPR, c = i - ty * DPR;
+            *reinterpret_cast<unsigned*>(&tile[ty][4 * c]) = reinterpret_cast<const UD*>(src + (size_t)(sy0 + ty) * stride + sx0 + 4 * c)->v;
         }
     } else {
         for (int i = threadIdx.x; i < SW * SH; i += 256) {
-            int ty = i / SW, tx = i - ty * SW;
-            tile[ty][tx] = src[(size_t)reflect101(sy0 + ty, ls.h) * ls.stride + reflect101(sx0 + tx, ls.w)];
+            const int ty = i / SW, tx = i - ty * SW;
+            tile[ty][tx] = src[(size_t)reflect101(sy0 + ty, h) * stride + reflect101(sx0 + tx, w)];
         }
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < SH * PD_TW; i += 256) {
-        int ty = i / PD_TW, x = i - ty * PD_TW;
-        const uint8_t* r = &tile[ty][2 * x];
-        hrow[ty][x] = (unsigned short)(r[2] * 6 + (r[1] + r[3]) * 4 + r[0] + r[4]);
+}
+// horizontal 1-4-6-4-1 pass, TWO outputs per thread (even TW): outputs 2j and 2j + 1 of a row read tile bytes 4j .. 4j + 6 = two
+// aligned LDS dwords, and leave as one dword of hrow (a sum is <= 16 * 255)
+template <int TW, int SH, int TS>
+__device__ __forceinline__ void pd_hpass2(const uint8_t (&tile)[SH][TS], unsigned short (&hrow)[SH][TW]) {
+    static_assert(TW % 2 == 0 && TS >= 2 * TW + 4, "rows of whole dwords");
+    for (int i = threadIdx.x; i < SH * (TW / 2); i += 256) {
+        const int ty = i / (TW / 2), j = i - ty * (TW / 2);
+        const unsigned a = *reinterpret_cast<const unsigned*>(&tile[ty][4 * j]), b = *reinterpret_cast<const unsigned*>(&tile[ty][4 * j + 4]);
+        const unsigned r0 = a & 255u, r1 = (a >> 8) & 255u, r2 = (a >> 16) & 255u, r3 = a >> 24, r4 = b & 255u, r5 = (b >> 8) & 255u, r6 = (b >> 16) & 255u;
+        *reinterpret_cast<unsigned*>(&hrow[ty][2 * j]) = tap5(r0, r1, r2, r3, r4) | (tap5(r2, r3, r4, r5, r6) << 16);
     }
-    __syncthreads();
-    {
-        int y = threadIdx.x / PD_TW, x = threadIdx.x - y * PD_TW;
-        int gx = ox + x, gy = oy + y;
+}
+// vertical pass and rounding store of the TW x (SH - 3) / 2 outputs at (ox, oy) of level ld, two per thread: five LDS dwords, one
+// 2-byte store
+template <int TW, int SH>
+__device__ __forceinline__ void pd_vpass2(const unsigned short (&hrow)[SH][TW], uint8_t* dst, const LevelInfo& ld, int ox, int oy) {
+    constexpr int TH = (SH - 3) / 2;
+    for (int i = threadIdx.x; i < TH * (TW / 2); i += 256) {
+        const int y = i / (TW / 2), x = 2 * (i - y * (TW / 2));
+        const int gx = ox + x, gy = oy + y;
         if (gx < ld.w && gy < ld.h) {
-            int v = hrow[2 * y + 2][x] * 6 + (hrow[2 * y + 1][x] + hrow[2 * y + 3][x]) * 4 + hrow[2 * y][x] + hrow[2 * y + 4][x];
-            dst[(size_t)gy * ld.stride + gx] = (uint8_t)((v + 128) >> 8);
+            unsigned q[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) q[k] = *reinterpret_cast<const unsigned*>(&hrow[2 * y + k][x]);
+            const unsigned b0 = pd_round(tap5(q[0] & 0xFFFFu, q[1] & 0xFFFFu, q[2] & 0xFFFFu, q[3] & 0xFFFFu, q[4] & 0xFFFFu));
+            const unsigned b1 = pd_round(tap5(q[0] >> 16, q[1] >> 16, q[2] >> 16, q[3] >> 16, q[4] >> 16));
+            uint8_t* o = dst + (size_t)gy * ld.stride + gx;
+            if (gx + 1 < ld.w) *reinterpret_cast<unsigned short*>(o) = (unsigned short)(b0 | (b1 << 8));   // gx is even, rows are 16-byte aligned
+            else o[0] = (uint8_t)b0;
         }
     }
 }
 
+// k_pyrdown: one level from the one below it, 32 x 8 outputs per block (an odd last level, colour contexts, the stage calls)
+#define PD_TW 32
+#define PD_TH 8
+__global__ __launch_bounds__(256) void k_pyrdown(DevBuffers d, int level, PyrTarget target) {
+    const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;          // every colour plane is its own pyramid
+    const int seq = seq_of(d, sc / 2), cam = sc & 1;
+    const LevelInfo ls = d.geom.lv[level - 1], ld = d.geom.lv[level];
+    uint8_t* base = d.pyr + pyr_index(d, seq, pyr_slot(d.st[seq], target), cam) + (size_t)plane * d.geom.pyr_bytes;
+    constexpr int SW = 2 * PD_TW + 3, SH = 2 * PD_TH + 3;        // 67 x 19 source tile
+    __shared__ __attribute__((aligned(4))) uint8_t tile[SH][SW + 1];
+    __shared__ __attribute__((aligned(4))) unsigned short hrow[SH][PD_TW];
+    const int ox = blockIdx.x * PD_TW, oy = blockIdx.y * PD_TH;
+    pd_fill_tile<SW>(tile, base + ls.off, ls.stride, ls.w, ls.h, 2 * ox - 2, 2 * oy - 2);
+    __syncthreads();
+    pd_hpass2<PD_TW>(tile, hrow);
+    __syncthreads();
+    pd_vpass2<PD_TW>(hrow, base + ld.off, ld, ox, oy);
+}
+
 // ---- fewer launches for the front of a frame (a lone stream is launch-bound there: a 5 us kernel every 4.5 us of host time) ----
-// k_ingest_pyr1: ingest and the first pyrDown in one launch (single-channel contexts).  A block stages the 67 x 19 source tile (at 32 x 8) of
-// its 32 x 8 level-1 outputs straight from the caller's image, writes the 64 x 16 level-0 pixels it owns and the level-1 tile.
+// k_ingest_pyr1: ingest and the first pyrDown in one launch (single-channel contexts) = k_pyrdown's steps with the caller's image
+// as the source and one more: the block also writes the 2 TW x 2 TH level-0 pixels it owns, from the tile.
 // (bodies take their block coordinates as arguments so that k_front_a / k_front_b below can run two of them in one launch)
-// TW x TH = the block's tile of level 1 (2 TW x 2 TH pixels of level 0).  Lone streams: 32 x 8 (many blocks for one image).  Many-sequence
-// contexts: 64 x 16 — at a thousand images per launch the kernel was bound by block turnover (962 000 blocks of 1 KB of output each:
-// 0.68 ms per 512 sequences = 1.6 TB/s), not by LDS or HBM; four times the work per block and half the halo.
+// TW x TH = the block's tile of level 1.  Lone streams: 32 x 8 (many blocks for one image).  Many-sequence contexts: 64 x 16 — at
+// a thousand images per launch the kernel was bound by block turnover (962 000 blocks of 1 KB of output each: 0.68 ms per 512
+// sequences = 1.6 TB/s), not by LDS or HBM; four times the work per block and half the halo.
 // RECT (rectifying contexts, d.rmap set): the source tile is filled by remapping the raw frame — tile byte (tx, ty) = the rectified
 // pixel at (reflect101(sx0 + tx), reflect101(sy0 + ty)), the byte the plain form reads from a rectified caller image — and the
 // level-0 store and both pyrDown passes run unchanged on it.  The rectified level 0 never makes a round trip through memory.
-template <int TW, int TH, bool RECT = false>
-static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, const uint8_t* const* srcs, int stride, int begin_frame, int bx, int by, int bz) {
+template <int TW, int TH, bool RECT>
+static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, const uint8_t* const* srcs, int stride, PyrTarget target, int bx, int by, int bz) {
     const int seq = seq_of(d, bz >> 1), cam = bz & 1;
     const LevelInfo ls = d.geom.lv[0], ld = d.geom.lv[1];
     const uint8_t* src = srcs[cam * d.B + seq];
-    // begin_frame: 0 = into the T1 slot as it stands (stage entry points), 1 = the frame pipeline's own ingest (free slot + the per-frame
-    // reset), 2 = ahead of the frame (image stream): into SeqState::slot_next, which k_pick_next chose; nothing of the state is written
-    const int slot = begin_frame == 2 ? d.st[seq].slot_next : begin_frame ? free_slot(d.st[seq]) : d.st[seq].slot_t1;
-    if (begin_frame == 1 && bx == 0 && by == 0 && cam == 0 && threadIdx.x == 0) frame_begin(d.st[seq]);
-    uint8_t* base = d.pyr + pyr_index(d, seq, slot, cam);
-    uint8_t* l0 = base + ls.off; uint8_t* dst = base + ld.off;
+    uint8_t* base = d.pyr + pyr_index(d, seq, ingest_slot(d, seq, target, bx == 0 && by == 0 && cam == 0 && threadIdx.x == 0), cam);
+    uint8_t* l0 = base + ls.off;
     constexpr int SW = 2 * TW + 3, SH = 2 * TH + 3;              // 67 x 19 source tile at 32 x 8
-    static_assert((SW + 1) % 4 == 0 && TW % 2 == 0, "rows of whole dwords");
     __shared__ __attribute__((aligned(4))) uint8_t tile[SH][SW + 1];
     __shared__ __attribute__((aligned(4))) unsigned short hrow[SH][TW];
     const int ox = bx * TW, oy = by * TH;
     const int sx0 = 2 * ox - 2, sy0 = 2 * oy - 2;
-    struct __attribute__((packed, aligned(1))) UD { unsigned v; };
     if constexpr (RECT) {
         const short2* m1 = rect_map1(d, cam, seq); const uint16_t* m2 = rect_map2(d, cam, seq);
         for (int i = threadIdx.x; i < SW * SH; i += 256) {
@@ -310,30 +281,10 @@ static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, con
             const int m = reflect101(sy0 + ty, ls.h) * ls.w + reflect101(sx0 + tx, ls.w);
             remap_px<1>(src, stride, d.raw_w, d.raw_h, m1[m], m2[m], &tile[ty][tx]);
         }
-        __syncthreads();
-        if (2 * ox + 2 * TW <= ls.w && 2 * oy + 2 * TH <= ls.h) {       // the owned level-0 block lies inside: dword stores as below
-            for (int i = threadIdx.x; i < (TW / 2) * (2 * TH); i += 256) {
-                const int ty = i / (TW / 2), c = i - ty * (TW / 2);
-                const unsigned lo = *reinterpret_cast<const unsigned*>(&tile[ty + 2][4 * c]), hi = *reinterpret_cast<const unsigned*>(&tile[ty + 2][4 * c + 4]);
-                UD u; u.v = __builtin_amdgcn_alignbyte(hi, lo, 2);
-                *reinterpret_cast<UD*>(l0 + (size_t)(2 * oy + ty) * ls.stride + 2 * ox + 4 * c) = u;
-            }
-        } else {
-            for (int i = threadIdx.x; i < 2 * TW * 2 * TH; i += 256) {
-                const int ty = i / (2 * TW), tx = i - ty * (2 * TW);
-                const int gx = 2 * ox + tx, gy = 2 * oy + ty;
-                if (gx < ls.w && gy < ls.h) l0[(size_t)gy * ls.stride + gx] = tile[ty + 2][tx + 2];
-            }
-        }
-    } else if (sx0 >= 0 && sy0 >= 0 && sx0 + SW + 1 <= ls.w && sy0 + SH <= ls.h) {
-        constexpr int DPR = (SW + 1) / 4;
-        for (int i = threadIdx.x; i < DPR * SH; i += 256) {
-            int ty = i / DPR, c = i - ty * DPR;
-            const unsigned v = reinterpret_cast<const UD*>(src + (size_t)(sy0 + ty) * stride + sx0 + 4 * c)->v;
-            *reinterpret_cast<unsigned*>(&tile[ty][4 * c]) = v;
-        }
-        __syncthreads();
-        // the block's own 2 TW x 2 TH level-0 pixels, a dword at a time (tile bytes 4c + 2 .. 4c + 5: two aligned LDS dwords, shifted)
+    } else pd_fill_tile<SW>(tile, src, stride, ls.w, ls.h, sx0, sy0);
+    __syncthreads();
+    // the block's own 2 TW x 2 TH level-0 pixels: in range, so the tile holds the pixels themselves
+    if (2 * ox + 2 * TW <= ls.w && 2 * oy + 2 * TH <= ls.h) {     // all inside the level: a dword at a time (tile bytes 4c + 2 .. 4c + 5: two aligned LDS dwords, shifted)
         for (int i = threadIdx.x; i < (TW / 2) * (2 * TH); i += 256) {
             const int ty = i / (TW / 2), c = i - ty * (TW / 2);
             const unsigned lo = *reinterpret_cast<const unsigned*>(&tile[ty + 2][4 * c]), hi = *reinterpret_cast<const unsigned*>(&tile[ty + 2][4 * c + 4]);
@@ -341,85 +292,43 @@ static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, con
             *reinterpret_cast<UD*>(l0 + (size_t)(2 * oy + ty) * ls.stride + 2 * ox + 4 * c) = u;
         }
     } else {
-        for (int i = threadIdx.x; i < SW * SH; i += 256) {
-            int ty = i / SW, tx = i - ty * SW;
-            tile[ty][tx] = src[(size_t)reflect101(sy0 + ty, ls.h) * stride + reflect101(sx0 + tx, ls.w)];
-        }
-        __syncthreads();
         for (int i = threadIdx.x; i < 2 * TW * 2 * TH; i += 256) {
             const int ty = i / (2 * TW), tx = i - ty * (2 * TW);
             const int gx = 2 * ox + tx, gy = 2 * oy + ty;
-            if (gx < ls.w && gy < ls.h) l0[(size_t)gy * ls.stride + gx] = tile[ty + 2][tx + 2];   // in range: the tile holds the pixel itself
+            if (gx < ls.w && gy < ls.h) l0[(size_t)gy * ls.stride + gx] = tile[ty + 2][tx + 2];
         }
     }
-    // horizontal 1-4-6-4-1 pass, TWO outputs per thread: outputs 2j and 2j + 1 of a row read tile bytes 4j .. 4j + 6 = two aligned
-    // LDS dwords (ten byte reads before), and leave as one dword of hrow
-    for (int i = threadIdx.x; i < SH * (TW / 2); i += 256) {
-        const int ty = i / (TW / 2), j = i - ty * (TW / 2);
-        const unsigned a = *reinterpret_cast<const unsigned*>(&tile[ty][4 * j]), b = *reinterpret_cast<const unsigned*>(&tile[ty][4 * j + 4]);
-        const unsigned r0 = a & 255u, r1 = (a >> 8) & 255u, r2 = (a >> 16) & 255u, r3 = a >> 24, r4 = b & 255u, r5 = (b >> 8) & 255u, r6 = (b >> 16) & 255u;
-        const unsigned h0 = r2 * 6 + (r1 + r3) * 4 + r0 + r4, h1 = r4 * 6 + (r3 + r5) * 4 + r2 + r6;
-        *reinterpret_cast<unsigned*>(&hrow[ty][2 * j]) = h0 | (h1 << 16);
-    }
+    pd_hpass2<TW>(tile, hrow);
     __syncthreads();
-    for (int i = threadIdx.x; i < TH * (TW / 2); i += 256) {   // vertical pass, two outputs per thread: five LDS dwords, one 2-byte store
-        const int y = i / (TW / 2), x = 2 * (i - y * (TW / 2));
-        const int gx = ox + x, gy = oy + y;
-        if (gx < ld.w && gy < ld.h) {
-            unsigned q[5];
-#pragma unroll
-            for (int k = 0; k < 5; k++) q[k] = *reinterpret_cast<const unsigned*>(&hrow[2 * y + k][x]);
-            const unsigned v0 = (q[2] & 0xFFFFu) * 6 + ((q[1] & 0xFFFFu) + (q[3] & 0xFFFFu)) * 4 + (q[0] & 0xFFFFu) + (q[4] & 0xFFFFu);
-            const unsigned v1 = (q[2] >> 16) * 6 + ((q[1] >> 16) + (q[3] >> 16)) * 4 + (q[0] >> 16) + (q[4] >> 16);
-            uint8_t* o = dst + (size_t)gy * ld.stride + gx;
-            const unsigned b0 = (v0 + 128) >> 8, b1 = (v1 + 128) >> 8;
-            if (gx + 1 < ld.w) *reinterpret_cast<unsigned short*>(o) = (unsigned short)(b0 | (b1 << 8));   // gx is even, rows are 16-byte aligned
-            else o[0] = (uint8_t)b0;
-        }
-    }
+    pd_vpass2<TW>(hrow, base + ld.off, ld, ox, oy);
 }
 #define IG_TW 64
 #define IG_TH 16
-template <int TW, int TH>
-__global__ __launch_bounds__(256) void k_ingest_pyr1(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
-    ingest_pyr1_body<TW, TH>(d, srcs, stride, begin_frame, blockIdx.x, blockIdx.y, blockIdx.z);
+template <int TW, int TH, bool RECT>
+__global__ __launch_bounds__(256) void k_ingest_pyr1(DevBuffers d, const uint8_t* const* srcs, int stride, PyrTarget target) {
+    ingest_pyr1_body<TW, TH, RECT>(d, srcs, stride, target, blockIdx.x, blockIdx.y, blockIdx.z);
 }
-template <int TW, int TH>
-__global__ __launch_bounds__(256) void k_ingest_pyr1_rect(DevBuffers d, const uint8_t* const* srcs, int stride, int begin_frame) {
-    ingest_pyr1_body<TW, TH, true>(d, srcs, stride, begin_frame, blockIdx.x, blockIdx.y, blockIdx.z);
+template <int TW, int TH, bool RECT>
+static void launch_ingest_pyr1_as(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    dim3 g((d.geom.lv[1].w + TW - 1) / TW, (d.geom.lv[1].h + TH - 1) / TH, launch_seqs(d) * 2);
+    hipLaunchKernelGGL((k_ingest_pyr1<TW, TH, RECT>), g, dim3(256), 0, st, d, ptrs, stride, target);
 }
-static void launch_ingest_pyr1(const DevBuffers& d, const uint8_t* const* ptrs, int stride, int begin_frame, hipStream_t st) {
-    if (d.rmap) {
-        if (d.B > SVO_LONE_MAX_SEQ) {
-            dim3 g((d.geom.lv[1].w + IG_TW - 1) / IG_TW, (d.geom.lv[1].h + IG_TH - 1) / IG_TH, launch_seqs(d) * 2);
-            hipLaunchKernelGGL((k_ingest_pyr1_rect<IG_TW, IG_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
-        } else {
-            dim3 g((d.geom.lv[1].w + PD_TW - 1) / PD_TW, (d.geom.lv[1].h + PD_TH - 1) / PD_TH, launch_seqs(d) * 2);
-            hipLaunchKernelGGL((k_ingest_pyr1_rect<PD_TW, PD_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
-        }
-        return;
-    }
-    if (d.B > SVO_LONE_MAX_SEQ) {
-        dim3 g((d.geom.lv[1].w + IG_TW - 1) / IG_TW, (d.geom.lv[1].h + IG_TH - 1) / IG_TH, launch_seqs(d) * 2);
-        hipLaunchKernelGGL((k_ingest_pyr1<IG_TW, IG_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
-    } else {
-        dim3 g((d.geom.lv[1].w + PD_TW - 1) / PD_TW, (d.geom.lv[1].h + PD_TH - 1) / PD_TH, launch_seqs(d) * 2);
-        hipLaunchKernelGGL((k_ingest_pyr1<PD_TW, PD_TH>), g, dim3(256), 0, st, d, ptrs, stride, begin_frame);
-    }
+static void launch_ingest_pyr1(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    if (d.B > SVO_LONE_MAX_SEQ) { if (d.rmap) launch_ingest_pyr1_as<IG_TW, IG_TH, true>(d, ptrs, stride, target, st); else launch_ingest_pyr1_as<IG_TW, IG_TH, false>(d, ptrs, stride, target, st); }
+    else { if (d.rmap) launch_ingest_pyr1_as<PD_TW, PD_TH, true>(d, ptrs, stride, target, st); else launch_ingest_pyr1_as<PD_TW, PD_TH, false>(d, ptrs, stride, target, st); }
 }
 
 // k_pyrdown2: levels l+1 AND l+2 from level l in one launch.  A block owns a 16 x 8 tile of level l+2, i.e. 32 x 16 of level l+1;
 // it computes the 35 x 19 level-(l+1) pixels its own tile needs (the 3-pixel rim is recomputed by the neighbours: +30 % work on
 // levels that are 1/16 and 1/64 of the image) from a 73 x 41 source tile.  Rim positions outside level l+1 are never read:
-// REFLECT_101 folds them onto positions inside the tile.
+// REFLECT_101 folds them onto positions inside the tile.  (The middle tile is 35 wide — odd — so the passes go an output at a time.)
 #define P2_TW 16
 #define P2_TH 8
-static __device__ __forceinline__ void pyrdown2_body(const DevBuffers& d, int level, int bx, int by, int bz, int ahead = 0) {
+static __device__ __forceinline__ void pyrdown2_body(const DevBuffers& d, int level, PyrTarget target, int bx, int by, int bz) {
     const int plane = bz % d.CN, sc = bz / d.CN;
     const int seq = seq_of(d, sc / 2), cam = sc & 1;
     const LevelInfo ls = d.geom.lv[level], lm = d.geom.lv[level + 1], ld = d.geom.lv[level + 2];
-    uint8_t* base = d.pyr + pyr_index(d, seq, ahead ? d.st[seq].slot_next : d.st[seq].slot_t1, cam) + (size_t)plane * d.geom.pyr_bytes;
-    const uint8_t* src = base + ls.off;
+    uint8_t* base = d.pyr + pyr_index(d, seq, pyr_slot(d.st[seq], target), cam) + (size_t)plane * d.geom.pyr_bytes;
     uint8_t* mid = base + lm.off; uint8_t* dst = base + ld.off;
     constexpr int MW = 2 * P2_TW + 3, MH = 2 * P2_TH + 3;        // 35 x 19 of the middle level
     constexpr int SW = 2 * MW + 3, SH = 2 * MH + 3;              // 73 x 41 of the source level
@@ -429,65 +338,48 @@ static __device__ __forceinline__ void pyrdown2_body(const DevBuffers& d, int le
     __shared__ unsigned short hrow2[MH][P2_TW];
     const int ox = bx * P2_TW, oy = by * P2_TH;                  // level l+2
     const int mx0 = 2 * ox - 2, my0 = 2 * oy - 2;                // level l+1
-    const int sx0 = 2 * mx0 - 2, sy0 = 2 * my0 - 2;              // level l
-    if (sx0 >= 0 && sy0 >= 0 && sx0 + SW + 3 <= ls.w && sy0 + SH <= ls.h) {
-        // tiles inside the source level (nearly all of them): rows of 19 unaligned dwords instead of 73 reflected byte loads
-        struct __attribute__((packed, aligned(1))) UD { unsigned v; };
-        constexpr int DPR = (SW + 3) / 4;
-        for (int i = threadIdx.x; i < DPR * SH; i += 256) {
-            const int ty = i / DPR, c = i - ty * DPR;
-            *reinterpret_cast<unsigned*>(&tile[ty][4 * c]) = reinterpret_cast<const UD*>(src + (size_t)(sy0 + ty) * ls.stride + sx0 + 4 * c)->v;
-        }
-    } else {
-        for (int i = threadIdx.x; i < SW * SH; i += 256) {
-            int ty = i / SW, tx = i - ty * SW;
-            tile[ty][tx] = src[(size_t)reflect101(sy0 + ty, ls.h) * ls.stride + reflect101(sx0 + tx, ls.w)];
-        }
-    }
+    pd_fill_tile<SW>(tile, base + ls.off, ls.stride, ls.w, ls.h, 2 * mx0 - 2, 2 * my0 - 2);
     __syncthreads();
     for (int i = threadIdx.x; i < SH * MW; i += 256) {
-        int ty = i / MW, x = i - ty * MW;
+        const int ty = i / MW, x = i - ty * MW;
         const uint8_t* r = &tile[ty][2 * x];
-        hrow[ty][x] = (unsigned short)(r[2] * 6 + (r[1] + r[3]) * 4 + r[0] + r[4]);
+        hrow[ty][x] = (unsigned short)tap5(r[0], r[1], r[2], r[3], r[4]);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < MH * MW; i += 256) {
-        int y = i / MW, x = i - y * MW;
-        int v = hrow[2 * y + 2][x] * 6 + (hrow[2 * y + 1][x] + hrow[2 * y + 3][x]) * 4 + hrow[2 * y][x] + hrow[2 * y + 4][x];
-        const uint8_t m = (uint8_t)((v + 128) >> 8);
+        const int y = i / MW, x = i - y * MW;
+        const uint8_t m = (uint8_t)pd_round(tap5(hrow[2 * y][x], hrow[2 * y + 1][x], hrow[2 * y + 2][x], hrow[2 * y + 3][x], hrow[2 * y + 4][x]));
         mtile[y][x] = m;
         const int gx = mx0 + x, gy = my0 + y;
         if (x >= 2 && x < 2 + 2 * P2_TW && y >= 2 && y < 2 + 2 * P2_TH && gx < lm.w && gy < lm.h) mid[(size_t)gy * lm.stride + gx] = m;   // the owned 32 x 16
     }
     __syncthreads();
     for (int i = threadIdx.x; i < MH * P2_TW; i += 256) {
-        int ty = i / P2_TW, x = i - ty * P2_TW;
+        const int ty = i / P2_TW, x = i - ty * P2_TW;
         // row / column of the middle tile that holds this (possibly folded) position; outputs beyond the level's edge (never
         // stored) may fold outside the tile: clamped, so that no index leaves the array
         int gy = reflect101(my0 + ty, lm.h) - my0;
         gy = gy < 0 ? 0 : gy > MH - 1 ? MH - 1 : gy;
-        int t[5];
+        unsigned t[5];
 #pragma unroll
         for (int k = 0; k < 5; k++) {
             int gx = reflect101(mx0 + 2 * x + k, lm.w) - mx0;
             gx = gx < 0 ? 0 : gx > MW - 1 ? MW - 1 : gx;
             t[k] = mtile[gy][gx];
         }
-        hrow2[ty][x] = (unsigned short)(t[2] * 6 + (t[1] + t[3]) * 4 + t[0] + t[4]);
+        hrow2[ty][x] = (unsigned short)tap5(t[0], t[1], t[2], t[3], t[4]);
     }
     __syncthreads();
     if (threadIdx.x < P2_TW * P2_TH) {
-        int y = threadIdx.x / P2_TW, x = threadIdx.x - y * P2_TW;
-        int gx = ox + x, gy = oy + y;
-        if (gx < ld.w && gy < ld.h) {
-            int v = hrow2[2 * y + 2][x] * 6 + (hrow2[2 * y + 1][x] + hrow2[2 * y + 3][x]) * 4 + hrow2[2 * y][x] + hrow2[2 * y + 4][x];
-            dst[(size_t)gy * ld.stride + gx] = (uint8_t)((v + 128) >> 8);
-        }
+        const int y = threadIdx.x / P2_TW, x = threadIdx.x - y * P2_TW;
+        const int gx = ox + x, gy = oy + y;
+        if (gx < ld.w && gy < ld.h)
+            dst[(size_t)gy * ld.stride + gx] = (uint8_t)pd_round(tap5(hrow2[2 * y][x], hrow2[2 * y + 1][x], hrow2[2 * y + 2][x], hrow2[2 * y + 3][x], hrow2[2 * y + 4][x]));
     }
 }
-__global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, int ahead) { pyrdown2_body(d, level, blockIdx.x, blockIdx.y, blockIdx.z, ahead); }
+__global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, PyrTarget target) { pyrdown2_body(d, level, target, blockIdx.x, blockIdx.y, blockIdx.z); }
 
-// k_pad_pyramid: the REFLECT_101 border of every level of the T1 slot — what cv::buildOpticalFlowPyramid's copyMakeBorder leaves
+// k_pad_pyramid: the REFLECT_101 border of every level of the target's slot — what cv::buildOpticalFlowPyramid's copyMakeBorder leaves
 // around each level (pyrBorder = BORDER_REFLECT_101).  Pixel (x, y) outside the level takes level(reflect101(y), reflect101(x)), the
 // iterated borderInterpolate rule over the whole pad, also where the pad is wider than the level.  One thread per border DWORD (row
 // starts, the pad and pixel (0, 0) are 4-byte aligned): the ring of a level is cut into its top and bottom bands (pad rows of the
@@ -497,16 +389,15 @@ __global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, int a
 // where a dword straddles a fold of a level narrower than the pad: those go byte by byte.  (First version: one thread, one byte
 // load and one byte store per border pixel — 0.39 ms per 512 sequences; the image stream's kernels run in the gap between two LK
 // launches, so their time is whole-job time.)
-__global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, int ahead) {
+__global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, PyrTarget target) {
     const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;
     const int seq = seq_of(d, sc / 2), cam = sc & 1, level = blockIdx.y;
     const LevelInfo L = d.geom.lv[level];
     const int P = d.geom.pad, w = L.w, h = L.h;
-    uint8_t* img = d.pyr + pyr_index(d, seq, ahead ? d.st[seq].slot_next : d.st[seq].slot_t1, cam) + (size_t)plane * d.geom.pyr_bytes + L.off;
+    uint8_t* img = d.pyr + pyr_index(d, seq, pyr_slot(d.st[seq], target), cam) + (size_t)plane * d.geom.pyr_bytes + L.off;
     const int rowdw = (w + 2 * P + 3) >> 2;                       // dwords of a band row, from x = -P (the last one may reach into the row's stride padding)
     const int xr0 = w & ~3, ldw = P >> 2, sdw = ldw + ((w + P - xr0 + 3) >> 2);   // left + right dwords of an image row
     const int band = P * rowdw, total = 2 * band + h * sdw;
-    struct __attribute__((packed, aligned(1))) UD { unsigned v; };
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
         int x, y;
         if (i < 2 * band) { const int j = i < band ? i : i - band, r = j / rowdw; x = (j - r * rowdw) * 4 - P; y = i < band ? r - P : h + r; }
@@ -520,41 +411,29 @@ __global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, int ahead) {
         *reinterpret_cast<unsigned*>(img + (ptrdiff_t)y * L.stride + x) = v;
     }
 }
-static void launch_pad_pyramid_into(const DevBuffers& d, hipStream_t st, int ahead) {
+static void launch_pad_pyramid(const DevBuffers& d, hipStream_t st, PyrTarget target) {
     const LevelInfo& L0 = d.geom.lv[0];
     const int P = d.geom.pad, ring0 = 2 * P * (L0.w + 2 * P) + 2 * P * L0.h;
     int gx = (ring0 + 4 * 256 - 1) / (4 * 256); if (gx < 1) gx = 1; if (gx > 64) gx = 64;      // ~one border dword per thread at level 0 (the smaller levels stride less)
-    hipLaunchKernelGGL(k_pad_pyramid, dim3(gx, d.geom.nlevels, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, ahead);
+    hipLaunchKernelGGL(k_pad_pyramid, dim3(gx, d.geom.nlevels, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, target);
 }
-void launch_pad_pyramid(const DevBuffers& d, hipStream_t st) { launch_pad_pyramid_into(d, st, 0); }
 
 // levels first .. nlevels-1 from level first-1: pairs of levels per launch where two remain
-static void launch_pyramid_from(const DevBuffers& d, int first, hipStream_t st, int ahead = 0) {
+static void launch_pyramid_from(const DevBuffers& d, int first, hipStream_t st, PyrTarget target) {
     int l = first;
     while (l < d.geom.nlevels) {
         if (l + 1 < d.geom.nlevels) {
             dim3 g((d.geom.lv[l + 1].w + P2_TW - 1) / P2_TW, (d.geom.lv[l + 1].h + P2_TH - 1) / P2_TH, launch_seqs(d) * 2 * d.CN);
-            hipLaunchKernelGGL(k_pyrdown2, g, dim3(256), 0, st, d, l - 1, ahead);
+            hipLaunchKernelGGL(k_pyrdown2, g, dim3(256), 0, st, d, l - 1, target);
             l += 2;
         } else {
             dim3 g((d.geom.lv[l].w + PD_TW - 1) / PD_TW, (d.geom.lv[l].h + PD_TH - 1) / PD_TH, launch_seqs(d) * 2 * d.CN);
-            hipLaunchKernelGGL(k_pyrdown, g, dim3(256), 0, st, d, l, ahead);
+            hipLaunchKernelGGL(k_pyrdown, g, dim3(256), 0, st, d, l, target);
             l += 1;
         }
     }
 }
-void launch_pyramid(const DevBuffers& d, hipStream_t st) { launch_pyramid_from(d, 1, st); launch_pad_pyramid(d, st); }
-// ingest + all pyramid levels of the T1 slot (vo.cpp:74-75, 200-201): single-channel contexts fuse the ingest with the first level
-void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st, bool begin_frame) {
-    if (d.CN == 1 && d.geom.nlevels >= 2) {
-        launch_ingest_pyr1(d, left_right_dev_ptrs, stride, (int)begin_frame, st);
-        launch_pyramid_from(d, 2, st);
-        launch_pad_pyramid(d, st);
-        return;
-    }
-    launch_ingest(d, left_right_dev_ptrs, stride, st, begin_frame);
-    launch_pyramid(d, st);
-}
+void launch_pyramid(const DevBuffers& d, hipStream_t st) { launch_pyramid_from(d, 1, st, PYR_T1); launch_pad_pyramid(d, st, PYR_T1); }
 
 // ---- the next frame's pyramids, ahead of the frame (many-sequence contexts; svo_api.hip issue_frame) ----
 // k_pick_next: one thread per sequence names the slot (a single decision per sequence: the blocks of the ingest that follows must
@@ -575,14 +454,23 @@ bool ingest_ahead_applies(const DevBuffers& d) {
     static const bool off = getenv("SVO_INGEST_AHEAD") && atoi(getenv("SVO_INGEST_AHEAD")) == 0;
     return !off && d.B > SVO_LONE_MAX_SEQ && d.CN == 1 && d.geom.nlevels >= 2;
 }
-void launch_ingest_pyramid_ahead(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st) {
-    hipLaunchKernelGGL(k_pick_next, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
-    launch_ingest_pyr1(d, left_right_dev_ptrs, stride, 2, st);
-    launch_pyramid_from(d, 2, st, 1);
-    launch_pad_pyramid_into(d, st, 1);
-}
 void launch_frame_begin(const DevBuffers& d, hipStream_t st) {
     hipLaunchKernelGGL(k_frame_begin, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
+}
+
+// ingest + all pyramid levels + their borders into the target's slot (vo.cpp:74-75, 200-201): single-channel contexts fuse the
+// ingest with the first level.  A PYR_BEGIN ingest runs the reset, which names its slot T1: that is what the kernels after it build on.
+void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right_dev_ptrs, int stride, hipStream_t st, PyrTarget target) {
+    if (target == PYR_NEXT) hipLaunchKernelGGL(k_pick_next, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
+    const PyrTarget rest = target == PYR_BEGIN ? PYR_T1 : target;
+    if (d.CN == 1 && d.geom.nlevels >= 2) {
+        launch_ingest_pyr1(d, left_right_dev_ptrs, stride, target, st);
+        launch_pyramid_from(d, 2, st, rest);
+    } else {
+        launch_ingest(d, left_right_dev_ptrs, stride, target, st);
+        launch_pyramid_from(d, 1, st, rest);
+    }
+    launch_pad_pyramid(d, st, rest);
 }
 
 // svo_reset_sequence: the fields the constructor sets (vo.h:266-268, svo_api.hip ctx_create) and nothing else — frame_id = 0 makes
@@ -953,21 +841,16 @@ __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_strided(DevBuffers
 // two halves of a launch touch disjoint data (pass 0 of k_fast reads no field the reset writes).  Lone-stream contexts only
 // (SVO_LONE_MAX_SEQ): with many sequences every kernel fills the GPU by itself and the separate launches stay.
 static_assert(EMIT_THREADS == 256, "k_front_b runs emit blocks beside 256-thread pyramid blocks");
+template <bool RECT>
 __global__ __launch_bounds__(256) void k_front_a(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
     const int i = blockIdx.x;
-    if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH>(d, srcs, stride, 1, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
-    const int j = i - n_a;
-    fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
-}
-__global__ __launch_bounds__(256) void k_front_a_rect(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
-    const int i = blockIdx.x;
-    if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH, true>(d, srcs, stride, 1, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
+    if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH, RECT>(d, srcs, stride, PYR_BEGIN, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
     const int j = i - n_a;
     fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
 }
 __global__ __launch_bounds__(256) void k_front_b(DevBuffers d, int px, int py, int n_p, int n_rows) {
     const int i = blockIdx.x;
-    if (i < n_p) { pyrdown2_body(d, 1, i % px, (i / px) % py, i / (px * py)); return; }
+    if (i < n_p) { pyrdown2_body(d, 1, PYR_T1, i % px, (i / px) % py, i / (px * py)); return; }
     const int j = i - n_p;
     bucket_emit_body(d, 0, j % n_rows, j / n_rows, n_rows);
 }
@@ -979,13 +862,13 @@ bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_de
     const int ns = launch_seqs(d);
     const int ax = (d.geom.lv[1].w + PD_TW - 1) / PD_TW, ay = (d.geom.lv[1].h + PD_TH - 1) / PD_TH, n_a = ax * ay * ns * 2;
     const int fx = (d.geom.W + FT_W - 1) / FT_W, fy = (d.geom.H + FT_H - 1) / FT_H, n_f = fx * fy * ns;
-    if (d.rmap) hipLaunchKernelGGL(k_front_a_rect, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
-    else hipLaunchKernelGGL(k_front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
+    const auto front_a = d.rmap ? k_front_a<true> : k_front_a<false>;
+    hipLaunchKernelGGL(front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
     const int px = (d.geom.lv[3].w + P2_TW - 1) / P2_TW, py = (d.geom.lv[3].h + P2_TH - 1) / P2_TH, n_p = px * py * ns * 2;
     const int n_rows = d.cfg.buckets_along_height;
     hipLaunchKernelGGL(k_front_b, dim3(n_p + n_rows * ns), dim3(256), 0, st, d, px, py, n_p, n_rows);
-    launch_pyramid_from(d, 4, st);                                    // a fifth level and beyond (cfg3)
-    launch_pad_pyramid(d, st);
+    launch_pyramid_from(d, 4, st, PYR_T1);                                    // a fifth level and beyond (cfg3)
+    launch_pad_pyramid(d, st, PYR_T1);
     launch_detect(d, 1, -1, st);                                      // the second pass exits at once unless needed (vo.cpp:327-332)
     return true;
 }

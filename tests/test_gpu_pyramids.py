@@ -7,9 +7,9 @@ frame's own images.  Each case asserts through svo_get_last_frame_path that the 
 - pyr1:   a lone stream's k_ingest_pyr1 (2-3 levels, or features_per_bucket > 1), neither bit
 - ahead:  the many-sequence build-ahead on the image stream, SVO_PATH_INGEST_AHEAD, 1-3 frames in flight
 - many:   the many-sequence k_ingest_pyr1 without build-ahead (a child process with SVO_INGEST_AHEAD=0), neither bit
-- one:    a one-level pyramid (k_ingest), neither bit
-- bgr:    channels = 3 (k_ingest_bgr, one pyramid per plane), neither bit
-and each of them rectifying (the _rect kernels; reference = the pyramid of rectify_ref.remap(raw)).
+- one:    a one-level pyramid (k_ingest<1>), neither bit
+- bgr:    channels = 3 (k_ingest<3>, one pyramid per plane), neither bit
+and each of them rectifying (the RECT = true instantiations; reference = the pyramid of rectify_ref.remap(raw)).
 Inputs: host frames packed and with wide rows, pinned frames, device frames with rows 0, 1, 3 and 64 bytes wider than the
 image (0xAB in the gap)."""
 import ctypes as C
