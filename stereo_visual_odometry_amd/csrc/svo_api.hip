@@ -23,6 +23,12 @@ static bool force_lean() {
     static const bool on = getenv("SVO_FORCE_LEAN") && atoi(getenv("SVO_FORCE_LEAN")) != 0;
     return on;
 }
+// The one place that picks the build of the f64 kernels (svo_kernels_pnp.hip: pnp_build) for the launches to come: the 96-register
+// builds when the context shares its device with another many-sequence context's LK grid, or under the test knob.
+static hipError_t choose_pnp_build(DevBuffers& d, bool shares_device) {
+    d.co_resident = (shares_device || force_lean()) ? 1 : 0;
+    return d.co_resident ? prepare_pnp_lean() : hipSuccess;
+}
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -141,6 +147,15 @@ static int dev_alloc(svo_context* c, T** p, size_t count) {
     return SVO_OK;
 }
 
+// what a context derives from its configuration's parameters, once d.CAP and d.geom stand (ctx_create, stage_reconfigure)
+static void derive_from_config(svo_context* c, const svo_config& cfg) {
+    DevBuffers& d = c->d;
+    c->lk_grid = (cfg.max_features > 0 && cfg.max_features < d.CAP) ? cfg.max_features : d.CAP;
+    d.lk_crit = lk_make_crit(cfg, d.geom);
+    double pc = (double)cfg.ransac_confidence; pc = pc > 0. ? pc : 0.; pc = pc < 1. ? pc : 1.;
+    d.ransac_log_num = log(1. - pc > 2.2250738585072014e-308 ? 1. - pc : 2.2250738585072014e-308);
+}
+
 static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width, int height, int cap_override, svo_context** out) {
     if (!out) return fail_arg("out is null");
     *out = nullptr;
@@ -172,13 +187,8 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     d.CAP = rows * cfg.buckets_along_width * cfg.features_per_bucket;
     if (d.CAP < 64) d.CAP = 64;
     if (cap_override > d.CAP) d.CAP = cap_override;
-    c->lk_grid = (cfg.max_features > 0 && cfg.max_features < d.CAP) ? cfg.max_features : d.CAP;
     make_geometry(d.geom, width, height, cfg.win_w, cfg.max_level, lk_pad_for(cfg.win_w));
-    d.lk_crit = lk_make_crit(cfg, d.geom);
-    {
-        double pc = (double)cfg.ransac_confidence; pc = pc > 0. ? pc : 0.; pc = pc < 1. ? pc : 1.;
-        d.ransac_log_num = log(1. - pc > 2.2250738585072014e-308 ? 1. - pc : 2.2250738585072014e-308);
-    }
+    derive_from_config(c, cfg);
     const size_t B = n_seq, CAP = d.CAP;
     int rc;
 #define ALLOC(ptr, count) if ((rc = dev_alloc(c, &(ptr), (count))) != SVO_OK) return rc;
@@ -375,8 +385,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         return SVO_OK;
     }
     const bool shares_device = shares < 0 ? lk_gated(c) : shares != 0;   // read once per frame: both uses below see the same answer
-    d.co_resident = (shares_device || force_lean()) ? 1 : 0;           // picks the 96-register builds of the f64 kernels (svo_kernels_pnp.hip)
-    if (d.co_resident) HIPCHK(prepare_pnp_lean());
+    HIPCHK(choose_pnp_build(d, shares_device));
     int path = d.co_resident ? SVO_PATH_LEAN : 0;
     const uint8_t** dp = d.img_ptrs + (size_t)slot * 2 * B;         // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(d);
@@ -507,8 +516,8 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
         // itself must be re-captured once another many-sequence context exists (and back), or it would keep the full-register
         // builds that cannot start beside the other's LK grid
         const int shares_now = lk_gated(c) ? 1 : 0;
-        const int co_now = (shares_now || force_lean()) ? 1 : 0;
-        if (co_now) HIPCHK(prepare_pnp_lean());                     // before the capture: issue_frame then finds it done
+        HIPCHK(choose_pnp_build(c->d, shares_now != 0));            // before the capture: issue_frame then finds the lean EPnP prepared
+        const int co_now = c->d.co_resident;
         if (!c->gexec[slot] || c->g_stride[slot] != stride || c->g_gn[slot] != gn || c->g_co[slot] != co_now) {
             if (c->gexec[slot]) { (void)hipGraphExecDestroy(c->gexec[slot]); c->gexec[slot] = nullptr; }
             hipGraph_t g = nullptr;
@@ -910,10 +919,7 @@ static bool stage_reconfigure(svo_context* c, const svo_config& cfg) {
     if (!cfg_same_shape(c->d.cfg, cfg) || cfg.ransac_iterations < 1 || cfg.ransac_iterations > c->k_alloc) return false;
     DevBuffers& d = c->d;
     d.cfg = cfg; d.K = cfg.ransac_iterations;
-    c->lk_grid = (cfg.max_features > 0 && cfg.max_features < d.CAP) ? cfg.max_features : d.CAP;
-    d.lk_crit = lk_make_crit(cfg, d.geom);
-    double pc = (double)cfg.ransac_confidence; pc = pc > 0. ? pc : 0.; pc = pc < 1. ? pc : 1.;
-    d.ransac_log_num = log(1. - pc > 2.2250738585072014e-308 ? 1. - pc : 2.2250738585072014e-308);
+    derive_from_config(c, cfg);
     c->lk_room = lk_registers_left(d);
     return true;
 }
@@ -949,15 +955,13 @@ static int stage_ctx(const svo_config& cfg_in, int device, int w, int h, int cap
     svo_config cfg = cfg_in;
     if (cfg.channels == 0) cfg.channels = 1;
     StageCache& sc = stage_cache_of_this_thread(cfg, device, w, h, cap);
-    // a stage context never shares the device with another's LK: it takes the 96-register builds only under the test knob
-    const int lean = force_lean() ? 1 : 0;
+    // (a stage context never shares the device with another's LK: choose_pnp_build(.., false) is lean only under the test knob)
     if (sc.c && sc.device == device && sc.w == w && sc.h == h && sc.c->d.CAP >= cap) {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamSynchronize(sc.c->stream));
         if (cfg_equal(sc.cfg, cfg) || stage_reconfigure(sc.c, cfg)) {
             sc.cfg = cfg;
-            sc.c->d.co_resident = lean;
-            if (lean) HIPCHK(prepare_pnp_lean());
+            HIPCHK(choose_pnp_build(sc.c->d, false));
             *out = sc.c;
             return SVO_OK;
         }
@@ -966,8 +970,7 @@ static int stage_ctx(const svo_config& cfg_in, int device, int w, int h, int cap
     int rc = ctx_create(&cfg, device, 1, w, h, cap, &sc.c);
     if (rc != SVO_OK) { sc.c = nullptr; return rc; }
     sc.cfg = cfg; sc.device = device; sc.w = w; sc.h = h;
-    sc.c->d.co_resident = lean;
-    if (lean) HIPCHK(prepare_pnp_lean());
+    HIPCHK(choose_pnp_build(sc.c->d, false));
     *out = sc.c;
     return SVO_OK;
 }

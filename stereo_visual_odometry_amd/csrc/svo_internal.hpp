@@ -168,8 +168,8 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
 bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out);   // false: no kernel built for this (window, channels, summation mode) — nothing ran
 void launch_compact(const DevBuffers& d, hipStream_t s);
 void launch_triangulate(const DevBuffers& d, hipStream_t s);
-void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = false);
-hipError_t prepare_pnp_lean();   // before the first launch_pnp with co_resident on the current device (the lean EPnP's dynamic LDS)   // expects the subsets drawn (launch_triangulate / k_compact do it)
+void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = false);   // expects the subsets drawn (launch_triangulate / k_compact do it)
+hipError_t prepare_pnp_lean();   // before the first launch_pnp with co_resident on the current device (the lean EPnP's dynamic LDS)
 bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t s);   // lone stream: triangulation || first EPnP chunk in one launch; false = not applicable
 void launch_pnp_subsets(const DevBuffers& d, hipStream_t s);
 void launch_pnp_p3p(const DevBuffers& d, hipStream_t s);                // exactly four points: one P3P, no RANSAC (stage API only)
@@ -200,9 +200,33 @@ LkCrit lk_make_crit(const svo_config& cfg, const Geometry& g);
 
 // ------------------------------------------------------------------------------------------------ subsets (cv::RNG, getSubset)
 // All K 5-subsets of one sequence, drawn with cv::RNG's multiply-with-carry recurrence from the seed (uint64)-1; the number
-// of draws never depends on model quality.  uniform(0, n) = next() % n: the remainder is taken through the 64-bit reciprocal
-// ceil(2^64 / n) (exact for 32-bit operands: the error term x e / (n 2^64) stays below 2^-32 < 1/n), 6 instructions instead
-// of the 32-bit division sequence.
+// of draws never depends on model quality.  The first SVO_RNG_TABLE_N states of that stream are tabulated (svo_rng_table.hpp).
+#include "svo_rng_table.hpp"
+#define SVO_RNG_SEED 0xFFFFFFFFFFFFFFFFull                               // RNG rng((uint64)-1)
+// uniform(0, n) = next() % n of a raw draw x: the remainder is taken through the 64-bit reciprocal ceil(2^64 / n) (exact for 32-bit
+// operands: the error term x e / (n 2^64) stays below 2^-32 < 1/n), 6 instructions instead of the 32-bit division sequence.
+static __device__ __forceinline__ unsigned long long pnp_recip(unsigned n) { return 0xFFFFFFFFFFFFFFFFull / n + 1ull; }
+static __device__ __forceinline__ int pnp_uniform(unsigned x, unsigned n, unsigned long long recip) {
+    return (int)(x - (unsigned)__umul64hi((unsigned long long)x, recip) * n);
+}
+// One getSubset: five distinct indices, each redrawn while it repeats an earlier one.  A raw draw is the next step of the
+// recurrence — or, for a caller that knows how many draws t were made since the seed (TABLE), a table entry while the table lasts.
+template <bool TABLE>
+static __device__ inline void pnp_draw_subset(unsigned long long& state, int& t, unsigned n, unsigned long long recip, int* out) {
+    int idx[5];
+    for (int i = 0; i < 5; i++) {
+        int v; bool dup;
+        do {
+            state = TABLE && t < SVO_RNG_TABLE_N ? SVO_RNG_STATES[t] : (unsigned long long)(unsigned)state * 4164903690ull + (unsigned)(state >> 32);
+            t++;
+            v = pnp_uniform((unsigned)state, n, recip);
+            dup = false;
+            for (int k = 0; k < i; k++) dup |= (idx[k] == v);
+        } while (dup);
+        idx[i] = v;
+    }
+    for (int i = 0; i < 5; i++) out[i] = idx[i];
+}
 // Draws subsets [s.pnp_drawn, upto) and leaves the generator state in s.pnp_rng: the first chunk is drawn beside the
 // triangulation, the rest only as far as the adaptive loop can still reach (k_pnp_decide) — with a static scene that is never.
 static __device__ inline void pnp_draw_subsets(const DevBuffers& d, SeqState& s, int seq, int upto) {
@@ -215,33 +239,19 @@ static __device__ inline void pnp_draw_subsets(const DevBuffers& d, SeqState& s,
         s.pnp_drawn = d.K;
         return;
     }
-    unsigned long long state = s.pnp_drawn == 0 ? 0xFFFFFFFFFFFFFFFFull : s.pnp_rng;      // RNG rng((uint64)-1)
-    const unsigned long long recip = 0xFFFFFFFFFFFFFFFFull / n + 1ull;
-    for (int it = s.pnp_drawn; it < upto; it++) {
-        int idx[5];
-        for (int i = 0; i < 5; i++) {
-            int v; bool dup;
-            do {
-                state = (unsigned long long)(unsigned)state * 4164903690ull + (unsigned)(state >> 32);
-                const unsigned x = (unsigned)state;
-                v = (int)(x - (unsigned)__umul64hi((unsigned long long)x, recip) * n);
-                dup = false;
-                for (int k = 0; k < i; k++) dup |= (idx[k] == v);
-            } while (dup);
-            idx[i] = v;
-        }
-        for (int i = 0; i < 5; i++) out[it * 5 + i] = idx[i];
-    }
+    unsigned long long state = s.pnp_drawn == 0 ? SVO_RNG_SEED : s.pnp_rng;
+    const unsigned long long recip = pnp_recip(n);
+    int t = 0;                                                       // (the position in the stream is not kept between calls)
+    for (int it = s.pnp_drawn; it < upto; it++) pnp_draw_subset<false>(state, t, n, recip, out + it * 5);
     if (upto > s.pnp_drawn) s.pnp_drawn = upto;
     s.pnp_rng = state;
 }
 
-// The first chunk of a lone stream, drawn by the 64 lanes of ONE wave (k_compact's first) from the table of raw generator states
-// (svo_rng_table.hpp): lane h takes subset h at its no-duplicate position (raw draws 5h .. 5h+4), which is right for every subset
-// up to the first one that meets a duplicate (getSubset redraws and the stream shifts); from that subset on lane 0 walks the
-// stream serially, exactly as pnp_draw_subsets does (from the table while it lasts).  Same subsets, same generator state
-// afterwards.  With ~900 tracks no subset of the 32 has a duplicate in two frames of three.  Call with all 64 lanes.
-#include "svo_rng_table.hpp"
+// The first chunk of a lone stream, drawn by the 64 lanes of ONE wave (k_compact's first) from the table: lane h takes subset h at
+// its no-duplicate position (raw draws 5h .. 5h+4), which is right for every subset up to the first one that meets a duplicate
+// (getSubset redraws and the stream shifts); from that subset on lane 0 walks the stream serially, as pnp_draw_subsets does.  Same
+// subsets, same generator state afterwards.  With ~900 tracks no subset of the 32 has a duplicate in two frames of three.  Call
+// with all 64 lanes.
 static __device__ inline void pnp_draw_first_chunk_wave(const DevBuffers& d, SeqState& s, int seq, int n_tracks, int upto) {
     const int lane = threadIdx.x & 63;
     const unsigned n = (unsigned)n_tracks;
@@ -251,14 +261,11 @@ static __device__ inline void pnp_draw_first_chunk_wave(const DevBuffers& d, Seq
         return;
     }
     int* out = d.subsets + (size_t)seq * d.K * 5;
-    const unsigned long long recip = 0xFFFFFFFFFFFFFFFFull / n + 1ull;
+    const unsigned long long recip = pnp_recip(n);
     int v[5]; bool dup = false;
     if (lane < upto) {
 #pragma unroll
-        for (int i = 0; i < 5; i++) {
-            const unsigned x = (unsigned)SVO_RNG_STATES[lane * 5 + i];
-            v[i] = (int)(x - (unsigned)__umul64hi((unsigned long long)x, recip) * n);
-        }
+        for (int i = 0; i < 5; i++) v[i] = pnp_uniform((unsigned)SVO_RNG_STATES[lane * 5 + i], n, recip);
 #pragma unroll
         for (int i = 1; i < 5; i++)
 #pragma unroll
@@ -272,23 +279,8 @@ static __device__ inline void pnp_draw_first_chunk_wave(const DevBuffers& d, Seq
     }
     if (lane == 0) {
         int t = first_bad * 5;                                                 // raw draws consumed so far
-        unsigned long long state = t > 0 ? SVO_RNG_STATES[t - 1] : 0xFFFFFFFFFFFFFFFFull;
-        for (int it = first_bad; it < upto; it++) {
-            int idx[5];
-            for (int i = 0; i < 5; i++) {
-                int w; bool dd;
-                do {
-                    state = t < SVO_RNG_TABLE_N ? SVO_RNG_STATES[t] : (unsigned long long)(unsigned)state * 4164903690ull + (unsigned)(state >> 32);
-                    t++;
-                    const unsigned x = (unsigned)state;
-                    w = (int)(x - (unsigned)__umul64hi((unsigned long long)x, recip) * n);
-                    dd = false;
-                    for (int k = 0; k < i; k++) dd |= (idx[k] == w);
-                } while (dd);
-                idx[i] = w;
-            }
-            for (int i = 0; i < 5; i++) out[it * 5 + i] = idx[i];
-        }
+        unsigned long long state = t > 0 ? SVO_RNG_STATES[t - 1] : SVO_RNG_SEED;
+        for (int it = first_bad; it < upto; it++) pnp_draw_subset<true>(state, t, n, recip, out + it * 5);
         s.pnp_drawn = upto;
         s.pnp_rng = state;
     }

@@ -18,93 +18,10 @@
 #include <atomic>
 
 static __device__ __forceinline__ bool seq_live(const SeqState& s) { return s.active && s.fail_reason == 0; }
-static __device__ int ransac_update_num_iters(double log_num, double ep, int max_iters);
 
 // ------------------------------------------------------------------------------------------------ triangulation
-// ---- the 4 x 4 SVD of the triangulation, register-resident.  jacobi_svd<4, 4> walks its row pairs with run-time indices; on
-// arrays the compiler keeps in VGPRs every such access becomes a select chain (the pair loop body was ~800 VALU instructions,
-// 430 of them v_cndmask).  Here the six pairs are six template instances with compile-time indices: the same rotations in the
-// same order with the same arithmetic (bit-identical results), ~230 instructions per pair.  Only the right singular vector of
-// the SMALLEST singular value is needed (the null vector of the DLT system), so the descending selection sort of the generic
-// routine is replayed on the four values alone to learn which row it would have moved to the last place.
-template <int I, int J>
-static __device__ __forceinline__ bool svd4_rotate(double (&At)[4][4], double (&Wv)[4], double (&Vt)[4][4]) {
-    const double eps = SVO_DBL_EPS * 10;
-    double a = Wv[I], p = 0, b = Wv[J], c, s;
-#pragma unroll
-    for (int k = 0; k < 4; k++) p += At[I][k] * At[J][k];
-    if (fabs(p) <= eps * sqrt(a * b)) return false;
-    p *= 2;
-    double beta = a - b, gamma = sqrt(p * p + beta * beta);
-    jacobi_cs(p, beta, gamma, c, s);
-    a = b = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        double t0 = c * At[I][k] + s * At[J][k];
-        double t1 = -s * At[I][k] + c * At[J][k];
-        At[I][k] = t0; At[J][k] = t1;
-        a += t0 * t0; b += t1 * t1;
-    }
-    Wv[I] = a; Wv[J] = b;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        double t0 = c * Vt[I][k] + s * Vt[J][k];
-        double t1 = -s * Vt[I][k] + c * Vt[J][k];
-        Vt[I][k] = t0; Vt[J][k] = t1;
-    }
-    return true;
-}
-// A: row-major 4 x 4.  X: the row of Vt that svd_rm<4, 4> would return as Vt[12..15].
-static __device__ void svd4_null_vector(const double (&A)[4][4], double (&X)[4]) {
-    double At[4][4], Vt[4][4], Wv[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) { At[i][j] = A[j][i]; Vt[i][j] = i == j ? 1.0 : 0.0; }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) sd += At[i][k] * At[i][k];
-        Wv[i] = sd;
-    }
-#pragma unroll 1
-    for (int iter = 0; iter < 30; iter++) {
-        bool changed = false;
-        changed |= svd4_rotate<0, 1>(At, Wv, Vt); changed |= svd4_rotate<0, 2>(At, Wv, Vt); changed |= svd4_rotate<0, 3>(At, Wv, Vt);
-        changed |= svd4_rotate<1, 2>(At, Wv, Vt); changed |= svd4_rotate<1, 3>(At, Wv, Vt); changed |= svd4_rotate<2, 3>(At, Wv, Vt);
-        if (!changed) break;
-    }
-    double w[4]; int p[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        double sd = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) sd += At[i][k] * At[i][k];
-        w[i] = sqrt(sd); p[i] = i;
-    }
-    // the selection sort of jacobi_svd (descending; the FIRST maximum wins ties), replayed on (value, original row) pairs
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        int j = i; double wj = w[i];
-#pragma unroll
-        for (int k = i + 1; k < 4; k++) { const bool g = wj < w[k]; j = g ? k : j; wj = g ? w[k] : wj; }
-        const double wi = w[i]; const int pi = p[i]; int pj = p[i];
-#pragma unroll
-        for (int k = i + 1; k < 4; k++) { const bool e = j == k; pj = e ? p[k] : pj; w[k] = e ? wi : w[k]; p[k] = e ? pi : p[k]; }
-        w[i] = wj; p[i] = pj;
-    }
-    const int r = p[3];
-#pragma unroll
-    for (int c = 0; c < 4; c++) X[c] = r == 0 ? Vt[0][c] : r == 1 ? Vt[1][c] : r == 2 ? Vt[2][c] : Vt[3][c];
-}
-
-// The last block of every sequence does not triangulate: its first lane draws the RANSAC subsets (they depend on the
-// track count only), so the serial RNG walk hides under the triangulation instead of being a launch of its own.
-// `lanes` tracks per wave: 64 when many sequences fill the GPU; 16 when a single stream runs alone — the Jacobi sweeps of a wave
-// last as long as its slowest lane needs, so with the GPU nearly empty fewer tracks per wave shorten the kernel (same results).
-// one track: the DLT system of the two views (vo.cpp:89-91), its null vector, dehomogenised to f32 (vo.cpp:93-94)
+// one track: the DLT system of the two views (vo.cpp:89-91), its null vector (svd4_null_vector: the right singular vector of the
+// smallest singular value), dehomogenised to f32 (vo.cpp:93-94)
 static __device__ __forceinline__ void triangulate_point(const SeqState& s, float2 pl, float2 pr, float (&w)[3]) {
     double A[4][4], V[4];
     const double xl = pl.x, yl = pl.y, xr = pr.x, yr = pr.y;
@@ -120,8 +37,11 @@ static __device__ __forceinline__ void triangulate_point(const SeqState& s, floa
     const float scale = Wh != 0.f ? 1.f / Wh : 1.f;                                             // convertPointsFromHomogeneous
     w[0] = X * scale; w[1] = Y * scale; w[2] = Z * scale;
 }
-// spare: the last block (bx == nblocks - 1) draws the RANSAC subsets instead of triangulating (many-sequence contexts; a
-// lone stream's k_compact has drawn them already, and its triangulation shares a launch with the first EPnP chunk, k_tri_epnp)
+// `lanes` tracks per wave: 64 when many sequences fill the GPU; 16 when a single stream runs alone — the Jacobi sweeps of a wave
+// last as long as its slowest lane needs, so with the GPU nearly empty fewer tracks per wave shorten the kernel (same results).
+// spare: the last block (bx == nblocks - 1) does not triangulate: its first lane draws the RANSAC subsets (they depend on the
+// track count only), so the serial RNG walk hides under the triangulation instead of being a launch of its own.  (A lone stream's
+// k_compact has drawn them already, and its triangulation shares a launch with the first EPnP chunk: k_tri_epnp, no spare block.)
 static __device__ __forceinline__ void triangulate_body(const DevBuffers& d, int lanes, int bx, int by, int nblocks, bool spare) {
     const int seq = seq_of(d, by);
     SeqState& s = d.st[seq];
@@ -138,21 +58,16 @@ static __device__ __forceinline__ void triangulate_body(const DevBuffers& d, int
     triangulate_point(s, d.tl0[o], d.tr0[o], w);
     d.world[3 * o] = w[0]; d.world[3 * o + 1] = w[1]; d.world[3 * o + 2] = w[2];
 }
-// Two builds (here and for EPnP and the final refine below).  An LK wave holds 104 registers and four of them share a SIMD: 96
-// registers stay free.  A kernel that needs more cannot start beside the LK grid of another context — it waits until that grid
-// drains (traced: k_pnp_epnp 7.5 ms instead of 0.2, k_pnp_final 8.3 ms instead of 0.1) and everything behind it in the stream
-// with it.  The `_lean` builds are capped at 96 registers (amdgpu_num_vgpr counts VGPR + AGPR pairs on gfx950) and spill to
-// scratch: slower alone (32 sequences, one context: EPnP 202 -> 286 us, final 90 -> 362 us), but they run under the other
-// context's LK instead of after it.  Used when several many-sequence contexts share the device (DevBuffers::co_resident).
+// Two builds (here and for EPnP and the final refine below; pnp_build() at the end of the file picks between them).  An LK wave
+// holds 104 registers and four of them share a SIMD: 96 registers stay free.  A kernel that needs more cannot start beside the LK
+// grid of another context — it waits until that grid drains (traced: k_pnp_epnp 7.5 ms instead of 0.2, k_pnp_final 8.3 ms instead
+// of 0.1) and everything behind it in the stream with it.  The `_lean` builds are capped at 96 registers (amdgpu_num_vgpr counts
+// VGPR + AGPR pairs on gfx950) and spill to scratch: slower alone (32 sequences, one context: EPnP 202 -> 286 us, final 90 ->
+// 362 us), but they run under the other context's LK instead of after it.  Used when several many-sequence contexts share the
+// device (DevBuffers::co_resident).  Registers as built (profiles/r07_pnp_code_objects.md; tests/test_pnp_code_object.py pins the
+// cap): k_triangulate 112, no scratch; k_triangulate_lean 96 with 58 spilled.
 __global__ __launch_bounds__(64) void k_triangulate(DevBuffers d, int lanes) { triangulate_body(d, lanes, blockIdx.x, blockIdx.y, gridDim.x, true); }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_triangulate_lean(DevBuffers d, int lanes) { triangulate_body(d, lanes, blockIdx.x, blockIdx.y, gridDim.x, true); }
-void launch_triangulate(const DevBuffers& d, hipStream_t st) {
-    const bool lean = d.co_resident;
-    const int lanes = d.B > SVO_LONE_MAX_SEQ ? 64 : 16;
-    if (lean) hipLaunchKernelGGL(k_triangulate_lean, dim3((d.CAP + lanes - 1) / lanes + 1, launch_seqs(d)), dim3(64), 0, st, d, lanes);
-    else hipLaunchKernelGGL(k_triangulate, dim3((d.CAP + lanes - 1) / lanes + 1, launch_seqs(d)), dim3(64), 0, st, d, lanes);
-}
-
 // (pnp_draw_subsets — cv::RNG + getSubset — lives in svo_internal.hpp: k_compact draws the first chunk for lone-stream contexts)
 // stand-alone launch for callers that enter at launch_pnp without a triangulation before it (svo_camera_to_world)
 __global__ void k_pnp_subsets(DevBuffers d) {
@@ -168,15 +83,15 @@ void launch_pnp_subsets(const DevBuffers& d, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------ EPnP on 5 points
-// 8 or 32 lanes cooperate on one hypothesis (8 or 2 hypotheses per 64-thread block); the matrices live in an LDS arena.
+// 8 or 16 lanes cooperate on one hypothesis (8 or 4 hypotheses per 64-thread block); the matrices live in an LDS arena.
 // The 12x12 one-sided Jacobi SVD of MtM — more than half of EPnP's time — sweeps its row pairs in round-robin order: the 6
-// pairs of a round are disjoint, so they rotate in parallel (one lane per pair, or four: rotate_pair12_quads) and the result is
+// pairs of a round are disjoint, so they rotate in parallel (one lane per pair, or two: rotate_pair12_halves) and the result is
 // bit-identical to the sequential round-robin loop.  The three beta approximations (N = 4, 2, 3 null vectors) are independent
 // after L and rho and run on lanes 0..2.
-#define EP_G 8                                   // lanes per hypothesis, many sequences (k_pnp_epnp_lean); 64 / EP_G hypotheses per block
-#define EP_LEAN_LDS ((64 / EP_G) * EP_STRIDE * sizeof(double))
-#define EP_G_LONE 16                             // lanes per hypothesis when few sequences run (k_pnp_epnp): see rotate_pair12_halves
 #define EP_STRIDE 1032                           // doubles per hypothesis (+8 pad: distinct LDS banks per hypothesis)
+#define EP_G 8                                   // lanes per hypothesis, 96-register build (k_pnp_epnp_lean); 64 / EP_G hypotheses per block
+#define EP_G_LONE 16                             // lanes per hypothesis, full build (k_pnp_epnp, k_tri_epnp): see rotate_pair12_halves
+#define EP_LEAN_LDS ((64 / EP_G) * EP_STRIDE * sizeof(double))
 // arena map (doubles)
 #define EA_AT 0                                  // 144  MtM, then the rotating rows
 #define EA_VT 144                                // 144  rows 8..11: the four basis vectors EPnP reads (normalised rows of At, moved here after the sort)
@@ -201,27 +116,14 @@ static __device__ __forceinline__ double dist2(const double* a, const double* b)
 // the LEFT singular vectors (the normalised rows of the rotated At, as cvSVD(&MtM, &D, &Ut, 0, CV_SVD_MODIFY_A | CV_SVD_U_T)
 // returns them, epnp.cpp), so no Vt is accumulated (round 3; measured against the reference's recording)
 static __device__ bool rotate_pair12(double* At, double* Wv, int i, int j) {
-    const double eps = SVO_DBL_EPS * 10;
-    double* Ai = At + i * 12; double* Aj = At + j * 12;
-    double a = Wv[i], p = 0, b = Wv[j], c, s;
-    for (int k = 0; k < 12; k++) p += Ai[k] * Aj[k];
-    if (fabs(p) <= eps * sqrt(a * b)) return false;
-    p *= 2;
-    double beta = a - b, gamma = sqrt(p * p + beta * beta);
-    jacobi_cs(p, beta, gamma, c, s);
-    a = b = 0;
-    for (int k = 0; k < 12; k++) {
-        double t0 = c * Ai[k] + s * Aj[k];
-        double t1 = -s * Ai[k] + c * Aj[k];
-        Ai[k] = t0; Aj[k] = t1;
-        a += t0 * t0; b += t1 * t1;
-    }
+    double a = Wv[i], b = Wv[j], c, s;
+    if (!hestenes_pair<12>(At + i * 12, At + j * 12, a, b, c, s)) return false;
     Wv[i] = a; Wv[j] = b;
     return true;
 }
 
 // the value a DPP control brings from another lane, for a double (DPP moves 32-bit registers: the halves go separately)
-template <int CTRL> static __device__ __forceinline__ double dpp_move_f64(double v) {
+template <int CTRL> static __device__ __forceinline__ double dpp_f64(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
     hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
@@ -238,7 +140,6 @@ template <int CTRL> static __device__ __forceinline__ double dpp_move_f64(double
 // (row_shl:1).  (Round 2 ran four lanes per pair: a second SIDE rotated the rows of Vt; EPnP reads the left singular vectors
 // since round 3, so that side is gone.)
 static __device__ bool rotate_pair12_halves(double* At, double* Wv, int i, int j, int half) {
-    const double eps = SVO_DBL_EPS * 10;
     const int oi = __mul24(i, 12) + half * 6, oj = __mul24(j, 12) + half * 6;
     double* X = At + oi; double* Y = At + oj;
     double a = Wv[i], b = Wv[j], c, s;
@@ -246,7 +147,7 @@ static __device__ bool rotate_pair12_halves(double* At, double* Wv, int i, int j
 #pragma unroll
     for (int k = 0; k < 6; k++) { x[k] = X[k]; y[k] = Y[k]; }
     __builtin_amdgcn_sched_barrier(0);
-    const double lim = eps * sqrt(a * b);                             // while the rows arrive from LDS
+    const double lim = hestenes_limit(a, b);                          // while the rows arrive from LDS
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int k = 0; k < 6; k++) pr[k] = x[k] * y[k];
@@ -254,15 +155,13 @@ static __device__ bool rotate_pair12_halves(double* At, double* Wv, int i, int j
     double plo = 0;
 #pragma unroll
     for (int k = 0; k < 6; k++) plo += pr[k];                         // lower half: elements 0..5 from zero
-    double pup = dpp_move_f64<0x111>(plo);                            // row_shr:1 -> the upper half continues its neighbour's partial
+    double pup = dpp_f64<0x111>(plo);                                 // row_shr:1 -> the upper half continues its neighbour's partial
 #pragma unroll
     for (int k = 0; k < 6; k++) pup += pr[k];
-    const double pdn = dpp_move_f64<0x101>(pup);                      // row_shl:1 -> and hands the total back
+    const double pdn = dpp_f64<0x101>(pup);                           // row_shl:1 -> and hands the total back
     double p = half ? pup : pdn;
     if (fabs(p) <= lim) return false;
-    p *= 2;
-    double beta = a - b, gamma = sqrt(p * p + beta * beta);
-    jacobi_cs(p, beta, gamma, c, s);
+    hestenes_cs(a, b, p, c, s);
     double ma[6], mb[6], mc[6], md[6], t0[6], t1[6], q0[6], q1[6];
     double alo = 0, blo = 0;
     __builtin_amdgcn_sched_barrier(0);
@@ -277,7 +176,7 @@ static __device__ bool rotate_pair12_halves(double* At, double* Wv, int i, int j
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    double aup = dpp_move_f64<0x111>(alo), bup = dpp_move_f64<0x111>(blo);
+    double aup = dpp_f64<0x111>(alo), bup = dpp_f64<0x111>(blo);
 #pragma unroll
     for (int k = 0; k < 6; k++) { aup += q0[k]; bup += q1[k]; }
     double* Wo = half ? Wv : At + EA_M;                               // the upper lane holds the norms; the lower drops its partial in dead space
@@ -285,90 +184,7 @@ static __device__ bool rotate_pair12_halves(double* At, double* Wv, int i, int j
     return true;
 }
 
-// x = pinv(A) b for A: 6 x n (n = 3, 4, 5) on REGISTERS.  The three beta approximations of EPnP solve 6x4, 6x3 and 6x5 systems on
-// three lanes of one wave — as three template instances they were three code paths the wave executed one after the other; here
-// the system is zero-padded to five columns so that they run one instruction stream.  A zero row of At never rotates (p = 0 <= eps sqrt(a b) = 0), keeps its singular
-// value 0 (<= the threshold: dropped) and leaves the identity columns of Vt alone, so the n x n part is computed exactly as the
-// unpadded routine computes it, bit for bit.
-static __device__ void svd_solve6_reg(const double* A, int n, const double* b, double* x) {
-    constexpr int M = 6, N = 5;
-    double At[N][M], Wv[N], Vt[N][N];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-#pragma unroll
-        for (int j = 0; j < M; j++) At[i][j] = i < n ? A[j * n + i] : 0.0;
-    }
-    jacobi_svd_reg<M, N>(At, Wv, Vt, true);
-    double thr = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) thr += Wv[i];
-    thr *= SVO_DBL_EPS * 2;
-    double xx[N] = {0, 0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        if (Wv[i] <= thr) continue;
-        double s = 0;
-#pragma unroll
-        for (int k = 0; k < M; k++) s += At[i][k] * b[k];
-        s /= Wv[i];
-#pragma unroll
-        for (int k = 0; k < N; k++) xx[k] += s * Vt[i][k];
-    }
-#pragma unroll
-    for (int k = 0; k < N; k++) if (k < n) x[k] = xx[k];
-}
-
-// Householder QR least squares for the 6 x 4 Gauss-Newton step, on registers with compile-time indices (the arithmetic and its
-// order are those of qr_solve<6, 4> in svo_linalg.hpp)
-static __device__ __forceinline__ bool qr_solve64_reg(double (&A)[6][4], double (&b)[6], double (&x)[4]) {
-    constexpr int M = 6, N = 4;
-    double A1[N], A2[N];
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        double eta = 0;
-#pragma unroll
-        for (int i = k; i < M; i++) { double e = fabs(A[i][k]); if (eta < e) eta = e; }
-        if (eta == 0) return false;
-        double sum2 = 0, inv_eta = 1. / eta;
-#pragma unroll
-        for (int i = k; i < M; i++) { A[i][k] *= inv_eta; sum2 += A[i][k] * A[i][k]; }
-        double sigma = sqrt(sum2);
-        if (A[k][k] < 0) sigma = -sigma;
-        A[k][k] += sigma;
-        A1[k] = sigma * A[k][k];
-        A2[k] = -eta * sigma;
-#pragma unroll
-        for (int j = k + 1; j < N; j++) {
-            double sum = 0;
-#pragma unroll
-            for (int i = k; i < M; i++) sum += A[i][k] * A[i][j];
-            double tau = sum / A1[k];
-#pragma unroll
-            for (int i = k; i < M; i++) A[i][j] -= tau * A[i][k];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double tau = 0;
-#pragma unroll
-        for (int i = j; i < M; i++) tau += A[i][j] * b[i];
-        tau /= A1[j];
-#pragma unroll
-        for (int i = j; i < M; i++) b[i] -= tau * A[i][j];
-    }
-    x[N - 1] = b[N - 1] / A2[N - 1];
-#pragma unroll
-    for (int i = N - 2; i >= 0; i--) {
-        double sum = 0;
-#pragma unroll
-        for (int j = i + 1; j < N; j++) sum += A[i][j] * x[j];
-        x[i] = (b[i] - sum) / A2[i];
-    }
-    return true;
-}
-
-static __device__ void epnp_gauss_newton(const double* L, const double* rho, double* betas, double* ws) {
-    (void)ws;
+static __device__ void epnp_gauss_newton(const double* L, const double* rho, double* betas) {
     double bt[4] = {betas[0], betas[1], betas[2], betas[3]};
 #pragma unroll 1
     for (int it = 0; it < 5; it++) {
@@ -527,19 +343,8 @@ static __device__ void epnp_row_norm(double* ar, int i) {
 static __device__ void epnp_sort_rows(double* ar) {
     double w[12]; int id[12];
 #pragma unroll
-    for (int i = 0; i < 12; i++) { w[i] = ar[EA_W + i]; id[i] = i; }
-#pragma unroll
-    for (int i = 0; i < 11; i++) {
-        // position i takes the first maximum of w[i..11]; the displaced pair goes where the maximum was
-        double best = w[i]; int bj = i;
-#pragma unroll
-        for (int k = i + 1; k < 12; k++) if (best < w[k]) { best = w[k]; bj = k; }
-        const double wi = w[i]; const int ii = id[i];
-        int bid = ii;
-#pragma unroll
-        for (int k = i + 1; k < 12; k++) if (k == bj) { bid = id[k]; w[k] = wi; id[k] = ii; }
-        w[i] = best; id[i] = bid;
-    }
+    for (int i = 0; i < 12; i++) w[i] = ar[EA_W + i];
+    sort_desc_perm<12>(w, id);
     int* src = (int*)(ar + EA_M);                                     // M is dead
     src[0] = id[11]; src[1] = id[10]; src[2] = id[9]; src[3] = id[8];
 }
@@ -605,13 +410,14 @@ static __device__ __attribute__((always_inline)) void epnp_branch(double* ar, in
         be[2] = bx[3] / be[0];
         be[3] = 0.0;
     }
-    epnp_gauss_newton(L, rho, be, ws);
+    epnp_gauss_newton(L, rho, be);
     double* res = ar + EA_RES + (branch - 1) * 13;
     res[0] = epnp_compute_R_and_t(ar, be, res + 1, res + 10, ws, fu, fv, uc, vc);
 }
 
 // Hypotheses [h0, h1).  The first chunk (h0 == 0) is always solved; later chunks only up to s.pnp_need, the bound the
 // adaptive loop had reached after the first chunk (the bound only ever shrinks, so nothing beyond it can be consulted).
+static __device__ __forceinline__ int pnp_chunk_end(const SeqState& s, int h0, int h1) { return h0 > 0 ? (s.pnp_need < h1 ? s.pnp_need : h1) : h1; }
 // OWN_TRI: the hypothesis triangulates its five points itself (lanes 0..4, the same triangulate_point, hence the same floats)
 // instead of reading d.world — so that the first chunk can share a launch with the triangulation of all tracks (k_tri_epnp).
 template <int G, bool OWN_TRI = false>    // lanes per hypothesis: 8 (six rotate a pair each) or 16 (twelve: two lanes per pair)
@@ -620,7 +426,7 @@ static __device__ __forceinline__ void pnp_epnp_body(const DevBuffers& d, int h0
     const int seq = seq_of(d, by);
     const SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
-    int hend = h0 > 0 ? (s.pnp_need < h1 ? s.pnp_need : h1) : h1;
+    int hend = pnp_chunk_end(s, h0, h1);
     if (s.n_tracks == 5 && hend > 1) hend = 1;                          // five points: a single direct EPnP, no RANSAC
     if (h0 + bx * HPB >= hend) return;                                  // block-uniform
     const int g = threadIdx.x / G, q = threadIdx.x % G;
@@ -707,9 +513,11 @@ static __device__ __forceinline__ void pnp_epnp_body(const DevBuffers& d, int h0
     }
 }
 
-// Two builds (see k_triangulate_lean): the register-resident linear algebra wants ~300 registers, 32 lanes per hypothesis; the
-// lean build (96 registers, 8 lanes per hypothesis, arena in dynamic LDS — with a static 66 KB arena the compiler ties the
-// register budget to the occupancy the LDS allows and ignores the cap) is for contexts that share the GPU with another's LK.
+// Two builds (see k_triangulate_lean).  The full one keeps the linear algebra in registers (316 VGPRs + 60 AGPRs, no scratch) and runs
+// EP_G_LONE = 16 lanes per hypothesis, its arena of 4 x EP_STRIDE doubles static.  The lean one (96 registers, 547
+// spilled; EP_G = 8 lanes per hypothesis) takes its arena of 8 x EP_STRIDE doubles as dynamic LDS — with a static 66 KB arena
+// the compiler ties the register budget to the occupancy the LDS allows and ignores the cap — and is for contexts that share the
+// GPU with another's LK.
 __global__ __launch_bounds__(64) void k_pnp_epnp(DevBuffers d, int h0, int h1) {
     __shared__ double arena[(64 / EP_G_LONE) * EP_STRIDE];
     pnp_epnp_body<EP_G_LONE>(d, h0, h1, arena, blockIdx.x, blockIdx.y);
@@ -729,14 +537,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void k_pnp
 }
 
 // ------------------------------------------------------------------------------------------------ hypothesis scoring
-static __device__ __forceinline__ bool point_is_inlier(const double* Rt, double fx, double fy, double cx, double cy,
-                                                       const float* w3, float2 c, float thr2) {
-    double X = w3[0], Y = w3[1], Z = w3[2];
-    double x = Rt[0] * X + Rt[1] * Y + Rt[2] * Z + Rt[9];
-    double y = Rt[3] * X + Rt[4] * Y + Rt[5] * Z + Rt[10];
-    double z = Rt[6] * X + Rt[7] * Y + Rt[8] * Z + Rt[11];
+// a world point in the camera frame R X + t, normalised: x / z, y / z and z = 1 / depth (1 at depth zero, as projectPoints has it)
+static __device__ __forceinline__ void project_point(const double* R, double t0, double t1, double t2, double X, double Y, double Z,
+                                                     double& x, double& y, double& z) {
+    x = R[0] * X + R[1] * Y + R[2] * Z + t0;
+    y = R[3] * X + R[4] * Y + R[5] * Z + t1;
+    z = R[6] * X + R[7] * Y + R[8] * Z + t2;
     z = z ? 1. / z : 1;
     x *= z; y *= z;
+}
+static __device__ __forceinline__ bool point_is_inlier(const double* Rt, double fx, double fy, double cx, double cy,
+                                                       const float* w3, float2 c, float thr2) {
+    double x, y, z;
+    project_point(Rt, Rt[9], Rt[10], Rt[11], w3[0], w3[1], w3[2], x, y, z);
     float pu = (float)(x * fx + cx), pv = (float)(y * fy + cy);       // projectPoints: f64 inside, f32 out
     float du = c.x - pu, dv = c.y - pv;
     float e = du * du + dv * dv;                                      // computeError, f32
@@ -747,7 +560,7 @@ __global__ __launch_bounds__(256) void k_pnp_score(DevBuffers d, int h0, int h1)
     const int seq = seq_of(d, blockIdx.y), h = h0 + blockIdx.x;
     const SeqState& s = d.st[seq];
     if (!seq_live(s)) return;
-    if (h >= (h0 > 0 ? (s.pnp_need < h1 ? s.pnp_need : h1) : h1)) return;
+    if (h >= pnp_chunk_end(s, h0, h1)) return;
     if (s.n_tracks == 5) return;                                        // direct solve: nothing is scored
     __shared__ int total;
     __shared__ double Rt[12];
@@ -781,6 +594,23 @@ static __device__ int ransac_update_num_iters(double log_num, double ep, int max
     if (denom < SVO_DBL_MIN) return 0;
     denom = log(denom);
     return denom >= 0 || -log_num >= max_iters * (-denom) ? max_iters : (int)rint(log_num / denom);
+}
+
+// RANSACPointSetRegistrator::run's accept / shrink rule, replayed over the precomputed inlier counts good[0 .. K) of n points,
+// as far as the serial loop would get within the first `upto` hypotheses: a model is accepted when it beats max(best so far, 4),
+// and every acceptance shrinks the iteration bound (niters only decreases).
+struct RansacReplay { int niters, best, max_good, iters_run; };
+static __device__ RansacReplay ransac_replay(const int* good, int n, int K, int upto, double log_num) {
+    RansacReplay r = {K > 1 ? K : 1, -1, 0, 0};
+    for (int it = 0; it < r.niters && it < upto && it < K; it++) {
+        const int g = good[it];
+        r.iters_run = it + 1;
+        if (g > (r.max_good > 4 ? r.max_good : 4)) {
+            r.max_good = g; r.best = it;
+            r.niters = ransac_update_num_iters(log_num, (double)(n - g) / n, r.niters);
+        }
+    }
+    return r;
 }
 
 // Cholesky solve of a 6x6 SPD system (the damped normal equations of the LM step)
@@ -829,15 +659,7 @@ __global__ void k_pnp_decide(DevBuffers d, int c0) {
     if (!seq_live(s)) return;
     const int K = d.K, n = s.n_tracks;
     if (n == 5) { s.pnp_need = 1; return; }
-    const int* good = d.hyp_good + (size_t)seq * K;
-    int niters = K > 1 ? K : 1, max_good = 0;
-    for (int it = 0; it < niters && it < c0 && it < K; it++) {
-        int g = good[it];
-        if (g > (max_good > 4 ? max_good : 4)) {
-            max_good = g;
-            niters = ransac_update_num_iters(d.ransac_log_num, (double)(n - g) / n, niters);
-        }
-    }
+    const int niters = ransac_replay(d.hyp_good + (size_t)seq * K, n, K, c0, d.ransac_log_num).niters;
     s.pnp_need = niters < K ? niters : K;
     pnp_draw_subsets(d, s, seq, s.pnp_need);                         // the subsets of the hypotheses the loop can still reach
 }
@@ -845,22 +667,6 @@ __global__ void k_pnp_decide(DevBuffers d, int c0) {
 #define PF_THREADS 512                           // lone stream; the lean build runs PF_THREADS_LEAN
 #define PF_THREADS_LEAN 256
 #define PF_WAVES (PF_THREADS / 64)                // LDS arrays are sized for the larger block
-// the value of lane (dpp-permuted) of a double: DPP works on 32-bit registers, so move the halves separately
-static __device__ __forceinline__ double dpp_f64(double v, const int ctrl_unused);
-template <int CTRL> static __device__ __forceinline__ double dpp_f64_t(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-static __device__ __forceinline__ double dpp_f64(double v, const int ctrl) {
-    switch (ctrl) {
-        case 0xB1: return dpp_f64_t<0xB1>(v);
-        case 0x4E: return dpp_f64_t<0x4E>(v);
-        case 0x141: return dpp_f64_t<0x141>(v);
-        default: return dpp_f64_t<0x140>(v);
-    }
-}
 struct LmShared {
     double param[6], prev[6], R[9], dRdr[27], JtJ[36], JtErr[6];
     double red[PF_WAVES][28];
@@ -887,7 +693,7 @@ static __device__ __forceinline__ double lm_fold16(double a, double b) {
 }
 template <int CTRL> static __device__ __forceinline__ double lm_fold_row(double a, double b, bool upper) {
     const double keep = upper ? b : a, send = upper ? a : b;
-    return keep + dpp_f64_t<CTRL>(send);
+    return keep + dpp_f64<CTRL>(send);
 }
 static __device__ __forceinline__ double lm_wave_sums28(const double (&acc)[28], int lane) {
     double w[14], u[7], x[4], y[2];
@@ -898,11 +704,11 @@ static __device__ __forceinline__ double lm_wave_sums28(const double (&acc)[28],
     const bool b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
 #pragma unroll
     for (int k = 0; k < 3; k++) x[k] = lm_fold_row<0x140>(u[k], u[k + 4], b3);   // row_mirror: lanes 8..15 of a row take u[k + 4]
-    x[3] = u[3] + dpp_f64_t<0x140>(u[3]);                                     // the odd one out: both halves hold it
+    x[3] = u[3] + dpp_f64<0x140>(u[3]);                                     // the odd one out: both halves hold it
     y[0] = lm_fold_row<0x141>(x[0], x[2], b2);                                // row_half_mirror
     y[1] = lm_fold_row<0x141>(x[1], x[3], b2);
     double z = lm_fold_row<0x4E>(y[0], y[1], b1);                             // quad_perm [2,3,0,1]
-    return z + dpp_f64_t<0xB1>(z);                                            // quad_perm [1,0,3,2]
+    return z + dpp_f64<0xB1>(z);                                            // quad_perm [1,0,3,2]
 }
 static __device__ __forceinline__ int lm_red_slot(int lane) {
     const int m = ((lane >> 1) & 1) + 2 * ((lane >> 2) & 1);                  // which x the lane ended up with
@@ -927,11 +733,8 @@ struct LmPoints { float X[LM_CACHED], Y[LM_CACHED], Z[LM_CACHED], u[LM_CACHED], 
 
 static __device__ __forceinline__ void lm_point(double X, double Y, double Z, double cu, double cv, const double* R, const double* dRdr,
                                                 double t0, double t1, double t2, double fx, double fy, double cx, double cy, double (&acc)[28]) {
-    double x = R[0] * X + R[1] * Y + R[2] * Z + t0;
-    double y = R[3] * X + R[4] * Y + R[5] * Z + t1;
-    double z = R[6] * X + R[7] * Y + R[8] * Z + t2;
-    z = z ? 1. / z : 1;
-    x *= z; y *= z;
+    double x, y, z;
+    project_point(R, t0, t1, t2, X, Y, Z, x, y, z);
     double ex = x * fx + cx - cu, ey = y * fy + cy - cv;
     acc[27] += ex * ex + ey * ey;
     double jx[6], jy[6];
@@ -1025,21 +828,12 @@ static __device__ __forceinline__ void pnp_final_body(const DevBuffers& d) {
     const int n = s.n_tracks, K = d.K;
     const size_t o = (size_t)seq * d.CAP;
     const bool direct = n == 5;      // model_points == npoints (solvepnp.cpp): one EPnP on all points, all inliers, no refine
-    // ---- replay of RANSACPointSetRegistrator::run's accept / shrink rule over the K precomputed inlier counts
+    // ---- the winner of the RANSAC loop (ransac_replay over all K counts)
     if (threadIdx.x == 0 && direct) { s.pnp_best = 0; s.pnp_iters = 0; s.pnp_good = n; sh.total = 0; }
     if (threadIdx.x == 0 && !direct) {
-        const int* good = d.hyp_good + (size_t)seq * K;
-        int niters = K > 1 ? K : 1, max_good = 0, best = -1, iters_run = 0;
-        for (int it = 0; it < niters && it < K; it++) {
-            int g = good[it];
-            iters_run = it + 1;
-            if (g > (max_good > 4 ? max_good : 4)) {
-                max_good = g; best = it;
-                niters = ransac_update_num_iters(d.ransac_log_num, (double)(n - g) / n, niters);
-            }
-        }
-        s.pnp_best = best; s.pnp_iters = iters_run; s.pnp_good = max_good;
-        sh.total = best;
+        const RansacReplay r = ransac_replay(d.hyp_good + (size_t)seq * K, n, K, K, d.ransac_log_num);
+        s.pnp_best = r.best; s.pnp_iters = r.iters_run; s.pnp_good = r.max_good;
+        sh.total = r.best;
     }
     __syncthreads();
     const int best = sh.total;
@@ -1405,16 +1199,6 @@ void launch_inverse_transform(const double* R, const double* t, double* T, hipSt
     hipLaunchKernelGGL(k_inverse_transform, dim3(1), dim3(64), 0, st, R, t, T);
 }
 
-// lone-stream frame pipeline: triangulation || first EPnP chunk (k_tri_epnp); true if launched (then call launch_pnp(.., true))
-bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t st) {
-    static const bool off = getenv("SVO_TRI_EPNP_FUSED") && atoi(getenv("SVO_TRI_EPNP_FUSED")) == 0;
-    if (off || d.B > SVO_LONE_MAX_SEQ || d.co_resident) return false;
-    const int lanes = 16, c0 = pnp_first_chunk(d), hpb = 64 / EP_G_LONE;
-    const int n_e = (c0 + hpb - 1) / hpb, n_t = (d.CAP + lanes - 1) / lanes;
-    hipLaunchKernelGGL(k_tri_epnp, dim3(n_e + n_t, launch_seqs(d)), dim3(64), 0, st, d, lanes, n_e, c0);
-    return true;
-}
-
 // k_pnp_epnp_lean's dynamic LDS arena is more than the 64 KB a kernel gets without asking: ask once per device, and report a
 // refusal (the launches would fail) instead of dropping it
 hipError_t prepare_pnp_lean() {
@@ -1428,21 +1212,53 @@ hipError_t prepare_pnp_lean() {
     return e;
 }
 
-void launch_pnp(const DevBuffers& d, hipStream_t st, bool first_chunk_solved) {
-    // the subsets were drawn by the last block of k_triangulate (stage entry points go through launch_triangulate too)
+// ---- the build switch: everything that differs between the full and the 96-register builds of the stage (see k_triangulate_lean),
+// for the launchers below.  The host chose with DevBuffers::co_resident (and called prepare_pnp_lean).
+struct PnpBuild {
+    void (*triangulate)(DevBuffers, int);
+    void (*epnp)(DevBuffers, int, int);
+    void (*final)(DevBuffers);
+    int tri_lanes;                               // tracks per wave of the triangulation
+    int hpb;                                     // EPnP hypotheses per 64-thread block
+    unsigned epnp_lds;                           // dynamic LDS of an EPnP launch
+    int final_threads;
+    bool fused;                                  // k_tri_epnp applies: a lone stream on the full build
+};
+static PnpBuild pnp_build(const DevBuffers& d) {
+    const bool lone = d.B <= SVO_LONE_MAX_SEQ;
+    const int lanes = lone ? 16 : 64;
+    if (d.co_resident) return {k_triangulate_lean, k_pnp_epnp_lean, k_pnp_final_lean, lanes, 64 / EP_G, (unsigned)EP_LEAN_LDS, PF_THREADS_LEAN, false};
+    return {k_triangulate, k_pnp_epnp, k_pnp_final, lanes, 64 / EP_G_LONE, 0u, PF_THREADS, lone};
+}
+
+void launch_triangulate(const DevBuffers& d, hipStream_t st) {
+    const PnpBuild b = pnp_build(d);
+    hipLaunchKernelGGL(b.triangulate, dim3((d.CAP + b.tri_lanes - 1) / b.tri_lanes + 1, launch_seqs(d)), dim3(64), 0, st, d, b.tri_lanes);
+}
+
+// lone-stream frame pipeline: triangulation || first EPnP chunk (k_tri_epnp); true if launched (then call launch_pnp(.., true))
+bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t st) {
+    static const bool off = getenv("SVO_TRI_EPNP_FUSED") && atoi(getenv("SVO_TRI_EPNP_FUSED")) == 0;
+    const PnpBuild b = pnp_build(d);
+    if (off || !b.fused) return false;
     const int c0 = pnp_first_chunk(d);
-    const bool lean = d.co_resident;                                 // see k_triangulate_lean (the host called prepare_pnp_lean)
-    const int hpb = 64 / (lean ? EP_G : EP_G_LONE), ns = launch_seqs(d);
-    if (first_chunk_solved) { /* k_tri_epnp did it */ }
-    else if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((c0 + hpb - 1) / hpb, ns), dim3(64), EP_LEAN_LDS, st, d, 0, c0);
-    else hipLaunchKernelGGL(k_pnp_epnp, dim3((c0 + hpb - 1) / hpb, ns), dim3(64), 0, st, d, 0, c0);
+    const int n_e = (c0 + b.hpb - 1) / b.hpb, n_t = (d.CAP + b.tri_lanes - 1) / b.tri_lanes;
+    hipLaunchKernelGGL(k_tri_epnp, dim3(n_e + n_t, launch_seqs(d)), dim3(64), 0, st, d, b.tri_lanes, n_e, c0);
+    return true;
+}
+
+// expects the subsets of the first chunk drawn: by the last block of k_triangulate, by k_compact (lone stream) or by
+// launch_pnp_subsets (stage entry points without a triangulation)
+void launch_pnp(const DevBuffers& d, hipStream_t st, bool first_chunk_solved) {
+    const PnpBuild b = pnp_build(d);
+    const int c0 = pnp_first_chunk(d), ns = launch_seqs(d);
+    if (!first_chunk_solved)                                          // (else k_tri_epnp did it)
+        hipLaunchKernelGGL(b.epnp, dim3((c0 + b.hpb - 1) / b.hpb, ns), dim3(64), b.epnp_lds, st, d, 0, c0);
     hipLaunchKernelGGL(k_pnp_score, dim3(c0, ns), dim3(256), 0, st, d, 0, c0);
     if (d.K > c0) {
         hipLaunchKernelGGL(k_pnp_decide, dim3((ns + 63) / 64), dim3(64), 0, st, d, c0);
-        if (lean) hipLaunchKernelGGL(k_pnp_epnp_lean, dim3((d.K - c0 + hpb - 1) / hpb, ns), dim3(64), EP_LEAN_LDS, st, d, c0, d.K);
-        else hipLaunchKernelGGL(k_pnp_epnp, dim3((d.K - c0 + hpb - 1) / hpb, ns), dim3(64), 0, st, d, c0, d.K);
+        hipLaunchKernelGGL(b.epnp, dim3((d.K - c0 + b.hpb - 1) / b.hpb, ns), dim3(64), b.epnp_lds, st, d, c0, d.K);
         hipLaunchKernelGGL(k_pnp_score, dim3(d.K - c0, ns), dim3(256), 0, st, d, c0, d.K);
     }
-    if (lean) hipLaunchKernelGGL(k_pnp_final_lean, dim3(ns), dim3(PF_THREADS_LEAN), 0, st, d);
-    else hipLaunchKernelGGL(k_pnp_final, dim3(ns), dim3(PF_THREADS), 0, st, d);
+    hipLaunchKernelGGL(b.final, dim3(ns), dim3(b.final_threads), 0, st, d);
 }

@@ -1,20 +1,14 @@
 // svo_linalg.hpp — small dense f64 linear algebra for the geometry kernels (device code).
-// One-sided Jacobi SVD (Hestenes) with fixed compile-time sizes.  Only + - * / sqrt in a fixed
-// order and no FMA contraction (-ffp-contract=off), so results are IEEE-reproducible.
+// One-sided Jacobi SVD (Hestenes) on REGISTER arrays of fixed compile-time sizes: every row and pair index is a compile-time
+// constant, only the sweep loop is dynamic.  (Run-time indices would turn every access of a private array into a select chain or a
+// scratch access.)  Each rule of the algorithm is stated once here — the pair step (hestenes_*), the descending sort (sort_desc)
+// — and the 12 x 12 sweep of EPnP in svo_kernels_pnp.hip, which rotates rows in LDS, calls the same pieces.
+// Only + - * / sqrt in a fixed order and no FMA contraction (-ffp-contract=off), so results are IEEE-reproducible.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #define SVO_DBL_EPS 2.2204460492503131e-16
 #define SVO_DBL_MIN 2.2250738585072014e-308
-
-// At: N rows of length M (transpose of an M x N matrix, M >= N).  On exit rows i < n1 of At hold the
-// left singular vectors, Wv[N] the singular values (descending), Vt (N x N) the right singular vectors as rows.
-// A strided view of per-thread data living in LDS as [element][thread]: element i of this thread is base[i * STRIDE].
-template <int STRIDE> struct LdsVec {
-    double* base;
-    __device__ __forceinline__ double& operator[](int i) const { return base[i * STRIDE]; }
-    __device__ __forceinline__ LdsVec operator+(int off) const { return LdsVec{base + off * STRIDE}; }
-};
 
 // c and s of one Hestenes rotation (OpenCV's JacobiSVDImpl_): two arithmetically different forms, chosen by the sign of beta.
 // The lanes of a wave disagree about that sign, so written as if / else the wave walks BOTH division -> square root -> division
@@ -30,78 +24,68 @@ __device__ __forceinline__ void jacobi_cs(double p, double beta, double gamma, d
     s = neg ? r : o;
 }
 
-template <int M, int N, typename PA = double*, typename PW = double*>
-__device__ void jacobi_svd(PA At, PW Wv, PA Vt, int n1) {
-    const double eps = SVO_DBL_EPS * 10, minval = SVO_DBL_MIN;
-    const int max_iter = M > 30 ? M : 30;
-    for (int i = 0; i < N; i++) {
-        double sd = 0;
-        for (int k = 0; k < M; k++) { double t = At[i * M + k]; sd += t * t; }
-        Wv[i] = sd;
-        for (int k = 0; k < N; k++) Vt[i * N + k] = 0;
-        Vt[i * N + i] = 1;
-    }
-#pragma unroll 1
-    for (int iter = 0; iter < max_iter; iter++) {
-        bool changed = false;
-#pragma unroll 1
-        for (int i = 0; i < N - 1; i++)
-#pragma unroll 1
-            for (int j = i + 1; j < N; j++) {
-                PA Ai = At + i * M; PA Aj = At + j * M;
-                double a = Wv[i], p = 0, b = Wv[j], c, s;
-                for (int k = 0; k < M; k++) p += Ai[k] * Aj[k];
-                if (fabs(p) <= eps * sqrt(a * b)) continue;
-                p *= 2;
-                double beta = a - b, gamma = sqrt(p * p + beta * beta);
-                jacobi_cs(p, beta, gamma, c, s);
-                a = b = 0;
-                for (int k = 0; k < M; k++) {
-                    double t0 = c * Ai[k] + s * Aj[k];
-                    double t1 = -s * Ai[k] + c * Aj[k];
-                    Ai[k] = t0; Aj[k] = t1;
-                    a += t0 * t0; b += t1 * t1;
-                }
-                Wv[i] = a; Wv[j] = b;
-                changed = true;
-                PA Vi = Vt + i * N; PA Vj = Vt + j * N;
-                for (int k = 0; k < N; k++) {
-                    double t0 = c * Vi[k] + s * Vj[k];
-                    double t1 = -s * Vi[k] + c * Vj[k];
-                    Vi[k] = t0; Vj[k] = t1;
-                }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < N; i++) {
-        double sd = 0;
-        for (int k = 0; k < M; k++) { double t = At[i * M + k]; sd += t * t; }
-        Wv[i] = sqrt(sd);
-    }
-    for (int i = 0; i < N - 1; i++) {
-        int j = i;
-        for (int k = i + 1; k < N; k++) if (Wv[j] < Wv[k]) j = k;
-        if (i != j) {
-            double t = Wv[i]; Wv[i] = Wv[j]; Wv[j] = t;
-            for (int k = 0; k < M; k++) { t = At[i * M + k]; At[i * M + k] = At[j * M + k]; At[j * M + k] = t; }
-            for (int k = 0; k < N; k++) { t = Vt[i * N + k]; Vt[i * N + k] = Vt[j * N + k]; Vt[j * N + k] = t; }
-        }
-    }
-    for (int i = 0; i < n1; i++) {
-        double sd = i < N ? Wv[i] : 0;
-        double s = sd > minval ? 1 / sd : 0.;
-        for (int k = 0; k < M; k++) At[i * M + k] *= s;
+// ---- one Hestenes pair step (the body of JacobiSVDImpl_'s pair loop) on rows x, y of length M with squared norms a, b ----
+// a pair whose inner product p has |p| <= hestenes_limit(a, b) counts as orthogonal and is left alone
+__device__ __forceinline__ double hestenes_limit(double a, double b) { return SVO_DBL_EPS * 10 * sqrt(a * b); }
+__device__ __forceinline__ void hestenes_cs(double a, double b, double p, double& c, double& s) {
+    p *= 2;
+    const double beta = a - b, gamma = sqrt(p * p + beta * beta);
+    jacobi_cs(p, beta, gamma, c, s);
+}
+// (x, y) <- (c x + s y, -s x + c y); a, b <- the squared norms of the rotated rows, summed in element order
+template <int M>
+__device__ __forceinline__ void hestenes_rotate(double* x, double* y, double c, double s, double& a, double& b) {
+    a = b = 0;
+#pragma unroll
+    for (int k = 0; k < M; k++) {
+        const double t0 = c * x[k] + s * y[k];
+        const double t1 = -s * x[k] + c * y[k];
+        x[k] = t0; y[k] = t1;
+        a += t0 * t0; b += t1 * t1;
     }
 }
+// the whole step; false: the pair was not rotated (then c, s are not set)
+template <int M>
+__device__ __forceinline__ bool hestenes_pair(double* x, double* y, double& a, double& b, double& c, double& s) {
+    double p = 0;
+#pragma unroll
+    for (int k = 0; k < M; k++) p += x[k] * y[k];
+    if (fabs(p) <= hestenes_limit(a, b)) return false;
+    hestenes_cs(a, b, p, c, s);
+    hestenes_rotate<M>(x, y, c, s, a, b);
+    return true;
+}
 
-// The same algorithm on REGISTER arrays with every index a compile-time constant (all loops over rows / pairs unrolled; only the
-// sweep loop is dynamic).  jacobi_svd above walks its row pairs with run-time indices: on private arrays that turns every
-// access into a select chain or a scratch access, in LDS into a dependent ds_read.  This form executes the same rotations in the
-// same order with the same arithmetic — bit-identical results — in a fraction of the instructions, for the small fixed sizes the
-// geometry kernels solve over and over (3 x 3, 4 x 4, 6 x 5).  The selection sort is replayed with predicated row swaps.
+// The descending selection sort that ends JacobiSVDImpl_ (the FIRST maximum wins ties), replayed with predicated moves: place i
+// takes the first maximum of w[i ..], found at run time at place j, and swap(i, k, k == j) is called for every k > i so that
+// whatever belongs to the values (rows, indices) travels with them.
+template <int N, typename Swap>
+__device__ __forceinline__ void sort_desc(double (&w)[N], Swap swap) {
+#pragma unroll
+    for (int i = 0; i < N - 1; i++) {
+        int j = i; double wj = w[i];
+#pragma unroll
+        for (int k = i + 1; k < N; k++) { const bool g = wj < w[k]; j = g ? k : j; wj = g ? w[k] : wj; }
+#pragma unroll
+        for (int k = i + 1; k < N; k++) {
+            const bool e = j == k;
+            { const double x = w[i], y = w[k]; w[i] = e ? y : x; w[k] = e ? x : y; }
+            swap(i, k, e);
+        }
+    }
+}
+// ... on (value, index) pairs: perm[i] = the place the value now at i started from
+template <int N>
+__device__ __forceinline__ void sort_desc_perm(double (&w)[N], int (&perm)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; i++) perm[i] = i;
+    sort_desc<N>(w, [&](int i, int k, bool e) { const int x = perm[i], y = perm[k]; perm[i] = e ? y : x; perm[k] = e ? x : y; });
+}
+
+// The sweeps.  At: N rows of length M (the transpose of an M x N matrix, M >= N).  On exit the rows of At are the left singular
+// vectors times their singular values, Wv the singular values and the rows of Vt the right singular vectors — all UNSORTED.
 template <int M, int N>
-__device__ __forceinline__ void jacobi_svd_reg(double (&At)[N][M], double (&Wv)[N], double (&Vt)[N][N], bool normalize) {
-    const double eps = SVO_DBL_EPS * 10, minval = SVO_DBL_MIN;
+__device__ __forceinline__ void jacobi_sweeps(double (&At)[N][M], double (&Wv)[N], double (&Vt)[N][N]) {
     constexpr int max_iter = M > 30 ? M : 30;
 #pragma unroll
     for (int i = 0; i < N; i++) {
@@ -119,29 +103,10 @@ __device__ __forceinline__ void jacobi_svd_reg(double (&At)[N][M], double (&Wv)[
         for (int i = 0; i < N - 1; i++) {
 #pragma unroll
             for (int j = i + 1; j < N; j++) {
-                double a = Wv[i], p = 0, b = Wv[j], c, s;
-#pragma unroll
-                for (int k = 0; k < M; k++) p += At[i][k] * At[j][k];
-                if (fabs(p) <= eps * sqrt(a * b)) continue;
-                p *= 2;
-                double beta = a - b, gamma = sqrt(p * p + beta * beta);
-                jacobi_cs(p, beta, gamma, c, s);
-                a = b = 0;
-#pragma unroll
-                for (int k = 0; k < M; k++) {
-                    double t0 = c * At[i][k] + s * At[j][k];
-                    double t1 = -s * At[i][k] + c * At[j][k];
-                    At[i][k] = t0; At[j][k] = t1;
-                    a += t0 * t0; b += t1 * t1;
-                }
-                Wv[i] = a; Wv[j] = b;
+                double c, s, va, vb;
+                if (!hestenes_pair<M>(At[i], At[j], Wv[i], Wv[j], c, s)) continue;
                 changed = true;
-#pragma unroll
-                for (int k = 0; k < N; k++) {
-                    double t0 = c * Vt[i][k] + s * Vt[j][k];
-                    double t1 = -s * Vt[i][k] + c * Vt[j][k];
-                    Vt[i][k] = t0; Vt[j][k] = t1;
-                }
+                hestenes_rotate<N>(Vt[i], Vt[j], c, s, va, vb);        // (the norms of V's rows are not needed)
             }
         }
         if (!changed) break;
@@ -153,22 +118,20 @@ __device__ __forceinline__ void jacobi_svd_reg(double (&At)[N][M], double (&Wv)[
         for (int k = 0; k < M; k++) sd += At[i][k] * At[i][k];
         Wv[i] = sqrt(sd);
     }
-    // selection sort, descending, the first maximum wins ties: row i <-> row j with j found at run time, applied as predicated swaps
+}
+
+// The full decomposition: singular values descending, rows of At the left singular vectors (normalised if asked), rows of Vt the
+// right ones.  Everything is inlined, so a caller pays only for the outputs it reads.
+template <int M, int N>
+__device__ __forceinline__ void jacobi_svd_reg(double (&At)[N][M], double (&Wv)[N], double (&Vt)[N][N], bool normalize) {
+    const double minval = SVO_DBL_MIN;
+    jacobi_sweeps<M, N>(At, Wv, Vt);
+    sort_desc<N>(Wv, [&](int i, int k, bool e) {
 #pragma unroll
-    for (int i = 0; i < N - 1; i++) {
-        int j = i; double wj = Wv[i];
+        for (int c = 0; c < M; c++) { const double x = At[i][c], y = At[k][c]; At[i][c] = e ? y : x; At[k][c] = e ? x : y; }
 #pragma unroll
-        for (int k = i + 1; k < N; k++) { const bool g = wj < Wv[k]; j = g ? k : j; wj = g ? Wv[k] : wj; }
-#pragma unroll
-        for (int k = i + 1; k < N; k++) {
-            const bool e = j == k;
-            { const double x = Wv[i], y = Wv[k]; Wv[i] = e ? y : x; Wv[k] = e ? x : y; }
-#pragma unroll
-            for (int c = 0; c < M; c++) { const double x = At[i][c], y = At[k][c]; At[i][c] = e ? y : x; At[k][c] = e ? x : y; }
-#pragma unroll
-            for (int c = 0; c < N; c++) { const double x = Vt[i][c], y = Vt[k][c]; Vt[i][c] = e ? y : x; Vt[k][c] = e ? x : y; }
-        }
-    }
+        for (int c = 0; c < N; c++) { const double x = Vt[i][c], y = Vt[k][c]; Vt[i][c] = e ? y : x; Vt[k][c] = e ? x : y; }
+    });
     if (normalize) {
 #pragma unroll
         for (int i = 0; i < N; i++) {
@@ -180,47 +143,71 @@ __device__ __forceinline__ void jacobi_svd_reg(double (&At)[N][M], double (&Wv)[
     }
 }
 
+// The right singular vector of the SMALLEST singular value of a row-major 4 x 4 matrix (the null vector of the triangulation's DLT
+// system): the last row of Vt.  The left singular vectors are not read, so their part of the sort costs nothing.
+__device__ inline void svd4_null_vector(const double (&A)[4][4], double (&X)[4]) {
+    double At[4][4], Vt[4][4], Wv[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) At[i][j] = A[j][i];
+    }
+    jacobi_svd_reg<4, 4>(At, Wv, Vt, false);
+#pragma unroll
+    for (int c = 0; c < 4; c++) X[c] = Vt[3][c];
+}
+
 // SVD of a row-major M x N matrix A.  Ut: N x M, Vt: N x N.
 template <int M, int N>
 __device__ void svd_rm(const double* A, double* Wv, double* Ut, double* Vt) {
-    if constexpr (M <= 4 && N <= 4) {                                // small: the register form (bit-identical, far fewer instructions)
-        double At[N][M], W[N], V[N][N];
+    double At[N][M], W[N], V[N][N];
 #pragma unroll
-        for (int i = 0; i < N; i++) {
+    for (int i = 0; i < N; i++) {
 #pragma unroll
-            for (int j = 0; j < M; j++) At[i][j] = A[j * N + i];
-        }
-        jacobi_svd_reg<M, N>(At, W, V, true);
+        for (int j = 0; j < M; j++) At[i][j] = A[j * N + i];
+    }
+    jacobi_svd_reg<M, N>(At, W, V, true);
 #pragma unroll
-        for (int i = 0; i < N; i++) {
-            Wv[i] = W[i];
+    for (int i = 0; i < N; i++) {
+        Wv[i] = W[i];
 #pragma unroll
-            for (int j = 0; j < M; j++) Ut[i * M + j] = At[i][j];
+        for (int j = 0; j < M; j++) Ut[i * M + j] = At[i][j];
 #pragma unroll
-            for (int j = 0; j < N; j++) Vt[i * N + j] = V[i][j];
-        }
-    } else {
-        for (int i = 0; i < N; i++) for (int j = 0; j < M; j++) Ut[i * M + j] = A[j * N + i];
-        jacobi_svd<M, N>(Ut, Wv, Vt, N);
+        for (int j = 0; j < N; j++) Vt[i * N + j] = V[i][j];
     }
 }
 
-// x = pinv(A) b by SVD back-substitution; singular values <= 2*eps*sum(w) are dropped.
-template <int M, int N>
-__device__ void svd_solve(const double* A, const double* b, double* x) {
-    double Wv[N], Ut[N * M], Vt[N * N];
-    svd_rm<M, N>(A, Wv, Ut, Vt);
+// x = pinv(A) b for A: 6 x n (n = 3, 4, 5) on REGISTERS.  The three beta approximations of EPnP solve 6x4, 6x3 and 6x5 systems on
+// three lanes of one wave — as three template instances they were three code paths the wave executed one after the other; here
+// the system is zero-padded to five columns so that they run one instruction stream.  A zero row of At never rotates (p = 0 <= eps sqrt(a b) = 0), keeps its singular
+// value 0 (<= the threshold: dropped) and leaves the identity columns of Vt alone, so the n x n part is computed exactly as the
+// unpadded routine computes it, bit for bit.
+__device__ inline void svd_solve6_reg(const double* A, int n, const double* b, double* x) {
+    constexpr int M = 6, N = 5;
+    double At[N][M], Wv[N], Vt[N][N];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+#pragma unroll
+        for (int j = 0; j < M; j++) At[i][j] = i < n ? A[j * n + i] : 0.0;
+    }
+    jacobi_svd_reg<M, N>(At, Wv, Vt, true);
     double thr = 0;
+#pragma unroll
     for (int i = 0; i < N; i++) thr += Wv[i];
     thr *= SVO_DBL_EPS * 2;
-    for (int k = 0; k < N; k++) x[k] = 0;
+    double xx[N] = {0, 0, 0, 0, 0};
+#pragma unroll
     for (int i = 0; i < N; i++) {
         if (Wv[i] <= thr) continue;
         double s = 0;
-        for (int k = 0; k < M; k++) s += Ut[i * M + k] * b[k];
+#pragma unroll
+        for (int k = 0; k < M; k++) s += At[i][k] * b[k];
         s /= Wv[i];
-        for (int k = 0; k < N; k++) x[k] += s * Vt[i * N + k];
+#pragma unroll
+        for (int k = 0; k < N; k++) xx[k] += s * Vt[i][k];
     }
+#pragma unroll
+    for (int k = 0; k < N; k++) if (k < n) x[k] = xx[k];
 }
 
 __device__ inline void inv3_svd(const double A[9], double Ainv[9]) {
@@ -235,38 +222,50 @@ __device__ inline void inv3_svd(const double A[9], double Ainv[9]) {
     }
 }
 
-// Householder QR least squares: A (M x N, row-major, destroyed), b (destroyed) -> x.  false if singular.
-template <int M, int N>
-__device__ bool qr_solve(double* A, double* b, double* x) {
+// Householder QR least squares for the 6 x 4 Gauss-Newton step of EPnP, on registers with compile-time indices: A (destroyed),
+// b (destroyed) -> x.  false if singular.
+__device__ __forceinline__ bool qr_solve64_reg(double (&A)[6][4], double (&b)[6], double (&x)[4]) {
+    constexpr int M = 6, N = 4;
     double A1[N], A2[N];
+#pragma unroll
     for (int k = 0; k < N; k++) {
         double eta = 0;
-        for (int i = k; i < M; i++) { double e = fabs(A[i * N + k]); if (eta < e) eta = e; }
+#pragma unroll
+        for (int i = k; i < M; i++) { double e = fabs(A[i][k]); if (eta < e) eta = e; }
         if (eta == 0) return false;
         double sum2 = 0, inv_eta = 1. / eta;
-        for (int i = k; i < M; i++) { A[i * N + k] *= inv_eta; sum2 += A[i * N + k] * A[i * N + k]; }
+#pragma unroll
+        for (int i = k; i < M; i++) { A[i][k] *= inv_eta; sum2 += A[i][k] * A[i][k]; }
         double sigma = sqrt(sum2);
-        if (A[k * N + k] < 0) sigma = -sigma;
-        A[k * N + k] += sigma;
-        A1[k] = sigma * A[k * N + k];
+        if (A[k][k] < 0) sigma = -sigma;
+        A[k][k] += sigma;
+        A1[k] = sigma * A[k][k];
         A2[k] = -eta * sigma;
+#pragma unroll
         for (int j = k + 1; j < N; j++) {
             double sum = 0;
-            for (int i = k; i < M; i++) sum += A[i * N + k] * A[i * N + j];
+#pragma unroll
+            for (int i = k; i < M; i++) sum += A[i][k] * A[i][j];
             double tau = sum / A1[k];
-            for (int i = k; i < M; i++) A[i * N + j] -= tau * A[i * N + k];
+#pragma unroll
+            for (int i = k; i < M; i++) A[i][j] -= tau * A[i][k];
         }
     }
+#pragma unroll
     for (int j = 0; j < N; j++) {
         double tau = 0;
-        for (int i = j; i < M; i++) tau += A[i * N + j] * b[i];
+#pragma unroll
+        for (int i = j; i < M; i++) tau += A[i][j] * b[i];
         tau /= A1[j];
-        for (int i = j; i < M; i++) b[i] -= tau * A[i * N + j];
+#pragma unroll
+        for (int i = j; i < M; i++) b[i] -= tau * A[i][j];
     }
     x[N - 1] = b[N - 1] / A2[N - 1];
+#pragma unroll
     for (int i = N - 2; i >= 0; i--) {
         double sum = 0;
-        for (int j = i + 1; j < N; j++) sum += A[i * N + j] * x[j];
+#pragma unroll
+        for (int j = i + 1; j < N; j++) sum += A[i][j] * x[j];
         x[i] = (b[i] - sum) / A2[i];
     }
     return true;
