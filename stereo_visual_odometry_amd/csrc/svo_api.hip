@@ -19,10 +19,8 @@ extern "C" const char* svo_last_error(void) { return g_err.c_str(); }
 static thread_local int g_stage_path = 0;                            // svo_get_last_frame_path(NULL): this thread's last stage call
 
 // SVO_FORCE_LEAN=1 (test knob): every context, stage contexts included, takes the 96-register builds of the f64 kernels
-static bool force_lean() {
-    static const bool on = getenv("SVO_FORCE_LEAN") && atoi(getenv("SVO_FORCE_LEAN")) != 0;
-    return on;
-}
+static bool env_on(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }
+static bool force_lean() { static const bool on = env_on("SVO_FORCE_LEAN"); return on; }
 // The one place that picks the build of the f64 kernels (svo_kernels_pnp.hip: pnp_build) for the launches to come: the 96-register
 // builds when the context shares its device with another many-sequence context's LK grid, or under the test knob.
 static hipError_t choose_pnp_build(DevBuffers& d, bool shares_device) {
@@ -48,7 +46,6 @@ static int fail_arg(const char* msg) { g_err = msg; return SVO_ERR_ARG; }
 // device: two LK grids resident together only halve each other's CUs, and HIP-event durations of either would include the other.
 struct LkGate { std::mutex mu; hipEvent_t ev = nullptr; bool armed = false; std::atomic<int> contexts{0}; };
 static LkGate g_lk_gate[SVO_MAX_DEVICES];
-static bool lk_gated(const svo_context* c);
 
 extern "C" int svo_device_count(void) {
     int n = 0;
@@ -84,6 +81,21 @@ static void make_geometry(Geometry& g, int W, int H, int win, int max_level, int
     g.pyr_bytes = base;
 }
 
+// One slot of the results ring: everything a frame in flight owns besides its rows of the [SVO_RING][2 B] tables (ring_row).
+enum StageEvent { EV_F0, EV_PYR, EV_LK0, EV_LK1, EV_TRI, EV_DONE, EV_COUNT };   // stage boundaries, in svo_get_stage_timing's order
+struct GraphKey {                                // what a slot's graph was captured with (image stride, LK grid, co-resident builds)
+    int stride, gn, co;
+    bool operator==(const GraphKey& o) const { return stride == o.stride && gn == o.gn && co == o.co; }
+};
+struct RingSlot {
+    hipEvent_t ev[EV_COUNT] = {};                // EV_F0 and EV_DONE always recorded, the four between on request (stage_timing)
+    hipEvent_t ev_img = nullptr;                 // the frame's pyramids stand (image stream; created with it)
+    hipGraphExec_t gexec = nullptr;              // SVO_GRAPH=1: the slot fixes the pointer table, the result record and the copies
+    GraphKey key = {};
+    int g_path = 0;                              // the SVO_PATH_* bits of that capture
+    bool staged = false;                         // the slot's stage events were recorded (launch-list mode only)
+};
+
 struct svo_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -94,11 +106,10 @@ struct svo_context {
     const uint8_t** h_ptrs = nullptr;            // pinned [SVO_RING][2][B]
     int* h_act = nullptr;                        // pinned [SVO_RING][2 B]: a ragged frame's active list and flags (DevBuffers::act) ...
     int* d_act = nullptr;                        // ... and their device copy, one hipMemcpyAsync per ragged frame (kernels never read host memory for it)
-    hipEvent_t ev_done[SVO_RING] = {}, ev_f0[SVO_RING] = {}, ev_lk0[SVO_RING] = {}, ev_lk1[SVO_RING] = {};
-    hipEvent_t ev_pyr[SVO_RING] = {}, ev_tri[SVO_RING] = {};   // stage boundaries: pyramids built / world points triangulated
+    RingSlot ring[SVO_RING];
     // many-sequence contexts build the NEXT frame's pyramids on a second stream while the current frame is in its LK kernel (issue_frame)
     hipStream_t img_stream = nullptr;
-    hipEvent_t ev_img[SVO_RING] = {}, ev_begin = nullptr;
+    hipEvent_t ev_begin = nullptr;
     bool begin_recorded = false;
     bool staged_inputs = false;                  // this frame's images were copied in on `stream` (host-image calls): the image stream must wait for them
     int head = 0, tail = 0, inflight = 0;        // ring indices: head = next to enqueue, tail = oldest outstanding
@@ -109,19 +120,13 @@ struct svo_context {
     bool projection_set = false;
     int lk_grid = 0;
     int lk_hint = 0;                             // feature count seen in the last collected frame (sizes the LK grid; 0 = unknown)
-    // hipGraph replay of the frame's launch list (one executable graph per results-ring slot: the slot fixes the pointer table,
-    // the result record and the copies; re-captured when the stride or the LK grid size changes)
-    bool use_graph = false;
+    bool use_graph = false;                      // hipGraph replay of the frame's launch list (RingSlot::gexec, replay_graph)
     bool capturing = false;                      // inside hipStreamBeginCapture / EndCapture
     bool counted = false;                        // this context is in its device's LkGate count
     int lk_room = -1;                            // lk_registers_left(d), asked once
     int k_alloc = 0;                             // RANSAC hypotheses the PnP buffers were allocated for
     bool stage_timing = false;                   // record the four stage-boundary events of a frame (svo_set_stage_timing; SVO_STAGE_TIMING=1)
-    hipGraphExec_t gexec[SVO_RING] = {};
-    int g_stride[SVO_RING] = {}, g_gn[SVO_RING] = {}, g_co[SVO_RING] = {};   // what the slot's graph was captured with (stride, LK grid, co-resident builds)
-    int g_path[SVO_RING] = {};                   // ... and the SVO_PATH_* bits of that capture
     int last_path = 0;                           // SVO_PATH_* of the most recently issued frame (svo_get_last_frame_path)
-    bool staged_slot[SVO_RING] = {};             // the slot's stage events were recorded (launch-list mode only)
     // rectification (svo_set_rectification_maps): raw_w > 0 makes the context take RAW frames.  A map is one device buffer
     // ([W*H] short2 + [W*H] u16) per camera; shared[cam] serves every sequence whose own[seq][cam] is null.  Each frame names its
     // maps in the slot's row of the pinned table h_maps (read in place by the ingest kernels, beside h_ptrs), so a map replaced
@@ -137,11 +142,15 @@ struct svo_context {
     size_t staging_bytes = 0;                    // size of `staging` / `h_staging` (host-image calls of a rectifying context stage raw frames)
 };
 
+// a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
+template <typename T> static T* ring_row(const svo_context* c, T* table, int slot) { return table + (size_t)slot * 2 * c->d.B; }
+
 template <typename T>
 static int dev_alloc(svo_context* c, T** p, size_t count) {
     void* q = nullptr;
-    HIPCHK(hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    HIPCHK(hipMemsetAsync(q, 0, count * sizeof(T) > 0 ? count * sizeof(T) : 16, c->stream));
+    const size_t bytes = count * sizeof(T) > 0 ? count * sizeof(T) : 16;
+    HIPCHK(hipMalloc(&q, bytes));
+    HIPCHK(hipMemsetAsync(q, 0, bytes, c->stream));
     c->allocs.push_back(q);
     *p = (T*)q;
     return SVO_OK;
@@ -234,11 +243,7 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     memset((void*)c->h_maps, 0, sizeof(uint8_t*) * SVO_RING * 2 * B);
     HIPCHK(hipHostGetDevicePointer((void**)&c->d_maps, (void*)c->h_maps, 0));
     c->own_map.assign(2 * B, nullptr);
-    for (int i = 0; i < SVO_RING; i++) {
-        HIPCHK(hipEventCreate(&c->ev_done[i])); HIPCHK(hipEventCreate(&c->ev_f0[i]));
-        HIPCHK(hipEventCreate(&c->ev_lk0[i])); HIPCHK(hipEventCreate(&c->ev_lk1[i]));
-        HIPCHK(hipEventCreate(&c->ev_pyr[i])); HIPCHK(hipEventCreate(&c->ev_tri[i]));
-    }
+    for (RingSlot& r : c->ring) for (hipEvent_t& e : r.ev) HIPCHK(hipEventCreate(&e));
     // initial state: rotation = I, translation = 0, last_transform = I (vo.h:266-268); no slots in use
     std::vector<SeqState> hs(B);
     memset(hs.data(), 0, sizeof(SeqState) * B);
@@ -249,21 +254,17 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     }
     HIPCHK(hipMemcpyAsync(d.st, hs.data(), sizeof(SeqState) * B, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    {
-        // SVO_GRAPH=1 replays every frame as a captured hipGraph.  Measured on MI355X, one sequence, synchronous, host images
-        // (scratch/graph_ab.py, same box): 0.718 ms per frame pair with the launch list, 0.737 ms with the graph — the ~25 launches
-        // are issued ahead of the GPU anyway and the graph's dispatch is not cheaper on this runtime — so the launch list stays
-        // the default and the graph is the option.
-        const char* e = getenv("SVO_GRAPH");
-        c->use_graph = e ? atoi(e) != 0 : false;
-        c->lk_room = lk_registers_left(c->d);
-        if (device >= 0 && device < SVO_MAX_DEVICES && n_seq > SVO_LONE_MAX_SEQ) {
-            std::lock_guard<std::mutex> lock(g_lk_gate[device].mu);
-            g_lk_gate[device].contexts++; c->counted = true;
-        }
-        const char* t = getenv("SVO_STAGE_TIMING");
-        c->stage_timing = t ? atoi(t) != 0 : false;
+    // SVO_GRAPH=1 replays every frame as a captured hipGraph.  Measured on MI355X, one sequence, synchronous, host images
+    // (scratch/graph_ab.py, same box): 0.718 ms per frame pair with the launch list, 0.737 ms with the graph — the ~25 launches
+    // are issued ahead of the GPU anyway and the graph's dispatch is not cheaper on this runtime — so the launch list stays
+    // the default and the graph is the option.
+    c->use_graph = env_on("SVO_GRAPH");
+    c->lk_room = lk_registers_left(c->d);
+    if (device >= 0 && device < SVO_MAX_DEVICES && n_seq > SVO_LONE_MAX_SEQ) {
+        std::lock_guard<std::mutex> lock(g_lk_gate[device].mu);
+        g_lk_gate[device].contexts++; c->counted = true;
     }
+    c->stage_timing = env_on("SVO_STAGE_TIMING");
     undo.c = nullptr;
     *out = c;
     return SVO_OK;
@@ -273,22 +274,23 @@ extern "C" int svo_create(const svo_config* cfg, int device, int n_seq, int widt
     return ctx_create(cfg, device, n_seq, width, height, 0, out);
 }
 
-// Several many-sequence contexts on one device.  Two decisions, both read ONCE per frame (issue_frame); `contexts` is an atomic:
-// contexts are created and destroyed on other threads while this one enqueues frames.
-//  * lk_gated: the f64 kernels run as 96-register builds under the OTHER context's LK grid — only if those builds fit beside it
-//    (lk_registers_left >= 96: w = 22 grey, w = 17 / 23 / 31 grey and w = 10 / 12 BGR with float sums; not w = 21 since round 3,
-//    nor w = 10 / 15 grey, nor w = 31 in the default mode).
-//  * lk_chained: the contexts' LK launches wait for each other (one event per device).  Always, when the device is shared: two
+// Several many-sequence contexts on one device.  Two answers, both read ONCE per frame (enqueue_frame) and passed down;
+// `contexts` is an atomic: contexts are created and destroyed on other threads while this one enqueues frames.
+//  * shared: the contexts' LK launches wait for each other (one event per device).  Always, when the device is shared: two
 //    LK grids resident together only share the CUs — measured the same whole-job rate either way at w = 21 (18 370 vs 18 390
 //    frame-pairs/s) — and unchained each launch's duration contains a part of the other's (12.7 ms per launch chained, 13.3-16.4
 //    unchained, varying from run to run), which makes the per-launch figure of the dominant kernel, the one the bench line's
-//    roofline is computed from, meaningless.  SVO_LK_GATE=0 switches both off (measurement).
-static bool lk_shared_device(const svo_context* c) {
+//    roofline is computed from, meaningless.
+//  * lean: the f64 kernels run as 96-register builds under the OTHER context's LK grid — only if those builds fit beside it
+//    (lk_registers_left >= 96: w = 22 grey, w = 17 / 23 / 31 grey and w = 10 / 12 BGR with float sums; not w = 21 since round 3,
+//    nor w = 10 / 15 grey, nor w = 31 in the default mode).
+// SVO_LK_GATE=0 switches both off (measurement).
+struct DeviceSharing { bool shared, lean; };
+static DeviceSharing device_sharing(const svo_context* c) {
     static const bool off = getenv("SVO_LK_GATE") && atoi(getenv("SVO_LK_GATE")) == 0;
-    return !off && c->counted && g_lk_gate[c->device].contexts.load(std::memory_order_relaxed) > 1;
+    const bool shared = !off && c->counted && g_lk_gate[c->device].contexts.load(std::memory_order_relaxed) > 1;
+    return {shared, shared && c->lk_room >= 96};
 }
-static bool lk_gated(const svo_context* c) { return c->lk_room >= 96 && lk_shared_device(c); }
-static bool lk_chained(const svo_context* c) { return lk_shared_device(c); }
 
 extern "C" void svo_destroy(svo_context* c) {
     if (!c) return;
@@ -302,25 +304,15 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
-    if (c->h_staging) (void)hipHostFree(c->h_staging);
-    if (c->h_upload) (void)hipHostFree(c->h_upload);
-    if (c->h_results) (void)hipHostFree(c->h_results);
-    if (c->h_ptrs) (void)hipHostFree((void*)c->h_ptrs);
-    if (c->h_act) (void)hipHostFree(c->h_act);
-    if (c->h_maps) (void)hipHostFree((void*)c->h_maps);
+    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps}) if (p) (void)hipHostFree(p);
     for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
     for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
     for (const auto& r : c->retired) (void)hipFree(r.p);
-    for (int i = 0; i < SVO_RING; i++) {
-        if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
-        if (c->ev_f0[i]) (void)hipEventDestroy(c->ev_f0[i]);
-        if (c->ev_lk0[i]) (void)hipEventDestroy(c->ev_lk0[i]);
-        if (c->ev_lk1[i]) (void)hipEventDestroy(c->ev_lk1[i]);
-        if (c->ev_pyr[i]) (void)hipEventDestroy(c->ev_pyr[i]);
-        if (c->ev_tri[i]) (void)hipEventDestroy(c->ev_tri[i]);
+    for (RingSlot& r : c->ring) {
+        for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
+        if (r.ev_img) (void)hipEventDestroy(r.ev_img);
+        if (r.gexec) (void)hipGraphExecDestroy(r.gexec);
     }
-    for (int i = 0; i < SVO_RING; i++) if (c->gexec[i]) (void)hipGraphExecDestroy(c->gexec[i]);
-    for (int i = 0; i < SVO_RING; i++) if (c->ev_img[i]) (void)hipEventDestroy(c->ev_img[i]);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->img_stream) (void)hipStreamDestroy(c->img_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -361,147 +353,200 @@ static int stage_host_images(svo_context* c, const uint8_t* const* left, const u
 static int in_width(const svo_context* c) { return c->raw_w > 0 ? c->raw_w : c->d.geom.W; }
 static int in_height(const svo_context* c) { return c->raw_w > 0 ? c->raw_h : c->d.geom.H; }
 
-// The launch list of one frame (vo.cpp:41-137 as kernels), between the pointer-table upload and the result download.
-// with_events: record the stage-boundary events (not inside a graph capture).
-// n_act >= 0: a ragged frame — only the n_act sequences listed in the slot's row of h_act take it (its grids cover those alone,
-// through DevBuffers::act); the row is copied to the device on the stream of the frame's first kernel.
-static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, int shares = -1, int n_act = -1) {
-    DevBuffers& d = c->d;
-    const int B = d.B;
+// The frame's view of the context's buffers: c->d plus the slot's rows of the active list and of the map table (every other launch
+// sees the context's own unmasked, plain DevBuffers).  n_act >= 0: a ragged frame — only the n_act sequences listed in the slot's
+// row of h_act take it (its grids cover those alone, through DevBuffers::act).
+static DevBuffers frame_view(const svo_context* c, int slot, int n_act) {
+    DevBuffers f = c->d;
+    if (n_act >= 0) { f.act = ring_row(c, c->d_act, slot); f.n_act = n_act; }
+    if (c->raw_w > 0) f.rmap = ring_row(c, c->d_maps, slot);         // the frame's own maps (fill_slot_rows filled the row)
+    return f;
+}
+// the slot's row of h_act to the device, on the stream of the frame's first kernel (kernels never read host memory for it)
+static hipError_t upload_act(const svo_context* c, int slot, hipStream_t st) {
+    return hipMemcpyAsync(ring_row(c, c->d_act, slot), ring_row(c, c->h_act, slot), sizeof(int) * 2 * (size_t)c->d.B, hipMemcpyHostToDevice, st);
+}
+
+// The front of a many-sequence frame: its pyramids are built on the IMAGE stream, which only waits for the previous frame's reset —
+// so, with frames in flight, they are built while the previous frame sits in its LK kernel.  That kernel fills six of a SIMD's
+// eight wave slots and 480 of its 512 registers (svo_kernels_lk.hip): the ingest, pyramid and border kernels (11-17 registers)
+// are the ones that still fit beside it.  The frame's own stream then resets the state (ev_begin marks that) and goes on.
+static int front_ahead(svo_context* c, const DevBuffers& f, int slot, int stride) {
     hipStream_t s = c->stream;
-    struct ActReset { DevBuffers& d; ~ActReset() { d.act = nullptr; d.n_act = 0; d.rmap = nullptr; } } act_reset{d};   // other launches see an unmasked, plain context
-    if (c->raw_w > 0) d.rmap = c->d_maps + (size_t)slot * 2 * B;     // the frame's own maps (enqueue_frame filled the row)
-    // the slot's row of h_act to the device, on the stream of the frame's first kernel
-    const auto upload_act = [&](hipStream_t st) {
-        return hipMemcpyAsync(c->d_act + (size_t)slot * 2 * B, c->h_act + (size_t)slot * 2 * B, sizeof(int) * 2 * (size_t)B, hipMemcpyHostToDevice, st);
-    };
-    if (n_act >= 0) { d.act = c->d_act + (size_t)slot * 2 * B; d.n_act = n_act; }
-    if (d.act && n_act == 0) {                                         // all idle: the result rows are the whole frame
-        HIPCHK(upload_act(s));
-        if (with_events) { HIPCHK(hipEventRecord(c->ev_pyr[slot], s)); HIPCHK(hipEventRecord(c->ev_lk0[slot], s)); HIPCHK(hipEventRecord(c->ev_lk1[slot], s)); HIPCHK(hipEventRecord(c->ev_tri[slot], s)); }
-        launch_frame_end(d, slot, s);
-        c->begin_recorded = false;
-        c->last_path = 0;
+    RingSlot& r = c->ring[slot];
+    if (!c->img_stream) {
+        HIPCHK(hipStreamCreateWithFlags(&c->img_stream, hipStreamNonBlocking));   // (highest priority measured: same rate, but the two contexts' LK launches then run in lock-step)
+        HIPCHK(hipEventCreateWithFlags(&c->ev_begin, hipEventDisableTiming));
+        for (RingSlot& q : c->ring) HIPCHK(hipEventCreateWithFlags(&q.ev_img, hipEventDisableTiming));
+    }
+    if (c->begin_recorded) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));   // the fields k_pick_next reads are those of the frame in flight
+    else if (c->inflight > 0) {
+        // the frame in flight did not come this way (a replayed graph, an all-idle frame): ev_begin does not mark its reset, so
+        // k_pick_next could read its slot fields before its reset and pick the slot that frame is building — wait for all of it
+        HIPCHK(hipEventRecord(c->ev_begin, s));
+        HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));
+    }
+    if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, r.ev[EV_F0], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
+    if (f.act) HIPCHK(upload_act(c, slot, c->img_stream));
+    launch_ingest_pyramid(f, ring_row(c, f.img_ptrs, slot), stride, c->img_stream, PYR_NEXT);
+    HIPCHK(hipEventRecord(r.ev_img, c->img_stream));
+    HIPCHK(hipStreamWaitEvent(s, r.ev_img, 0));
+    launch_frame_begin(f, s);
+    HIPCHK(hipEventRecord(c->ev_begin, s));
+    return SVO_OK;
+}
+
+// The launch list of one frame (vo.cpp:41-137 as kernels), between the slot's start and done events.
+// with_events: record the stage-boundary events (not inside a graph capture).  n_act: see frame_view.
+static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, DeviceSharing share, int n_act = -1) {
+    hipStream_t s = c->stream;
+    const auto record = [&](StageEvent which) { return with_events ? hipEventRecord(c->ring[slot].ev[which], s) : hipSuccess; };
+    if (n_act == 0) {                                                  // all idle: the result rows are the whole frame
+        HIPCHK(upload_act(c, slot, s));
+        HIPCHK(record(EV_PYR)); HIPCHK(record(EV_LK0)); HIPCHK(record(EV_LK1)); HIPCHK(record(EV_TRI));
+        launch_frame_end(frame_view(c, slot, 0), slot, s);
+        c->begin_recorded = false; c->last_path = 0;
         return SVO_OK;
     }
-    const bool shares_device = shares < 0 ? lk_gated(c) : shares != 0;   // read once per frame: both uses below see the same answer
-    HIPCHK(choose_pnp_build(d, shares_device));
-    int path = d.co_resident ? SVO_PATH_LEAN : 0;
-    const uint8_t** dp = d.img_ptrs + (size_t)slot * 2 * B;         // the slot's pointer table: pinned host memory the kernel reads in place
-    const bool ahead = !c->capturing && ingest_ahead_applies(d);
-    if (d.act && !ahead) HIPCHK(upload_act(s));
-    if (!ahead && launch_front_fused(d, dp, stride, s)) {              // lone stream: ingest + pyramid beside detection, two launches
-        path |= SVO_PATH_FRONT_FUSED;
-        if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));   // stage timers: ms[0] = the fused front, ms[1] ~ 0
-        c->begin_recorded = false;
-    } else if (ahead) {
-        // Many sequences: this frame's pyramids are built on the IMAGE stream, which only waits for the previous frame's reset — so,
-        // with frames in flight, they are built while the previous frame sits in its LK kernel.  That kernel fills six of a SIMD's
-        // eight wave slots and 480 of its 512 registers (svo_kernels_lk.hip): the ingest, pyramid and border kernels (11-17
-        // registers) are the ones that still fit beside it.  The frame's own stream then resets the state and goes on with detection.
-        if (!c->img_stream) {
-            HIPCHK(hipStreamCreateWithFlags(&c->img_stream, hipStreamNonBlocking));   // (highest priority measured: same rate, but the two contexts' LK launches then run in lock-step)
-            HIPCHK(hipEventCreateWithFlags(&c->ev_begin, hipEventDisableTiming));
-            for (int i = 0; i < SVO_RING; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_img[i], hipEventDisableTiming));
-        }
-        if (c->begin_recorded) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));   // the fields k_pick_next reads are those of the frame in flight
-        else if (c->inflight > 0) {
-            // the frame in flight did not come this way (a replayed graph, an all-idle frame): ev_begin does not mark its reset, so
-            // k_pick_next could read its slot fields before its reset and pick the slot that frame is building — wait for all of it
-            HIPCHK(hipEventRecord(c->ev_begin, s));
-            HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));
-        }
-        if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_f0[slot], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
-        if (d.act) HIPCHK(upload_act(c->img_stream));
-        launch_ingest_pyramid(d, dp, stride, c->img_stream, PYR_NEXT);
+    HIPCHK(choose_pnp_build(c->d, share.lean));
+    const DevBuffers f = frame_view(c, slot, n_act);                   // after the build choice: co_resident travels in the view
+    int path = f.co_resident ? SVO_PATH_LEAN : 0;
+    const uint8_t** dp = ring_row(c, f.img_ptrs, slot);                // the slot's pointer table: pinned host memory the kernel reads in place
+    const bool ahead = !c->capturing && ingest_ahead_applies(f);
+    bool detected = false;
+    if (ahead) {
+        if (const int rc = front_ahead(c, f, slot, stride)) return rc;
         path |= SVO_PATH_INGEST_AHEAD;
-        HIPCHK(hipEventRecord(c->ev_img[slot], c->img_stream));
-        HIPCHK(hipStreamWaitEvent(s, c->ev_img[slot], 0));
-        launch_frame_begin(d, s);
-        HIPCHK(hipEventRecord(c->ev_begin, s)); c->begin_recorded = true;
-        if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));
-        launch_detect(d, 0, -1, s);
-        launch_detect(d, 1, -1, s);
     } else {
-        launch_ingest_pyramid(d, dp, stride, s, PYR_BEGIN);           // + the per-frame reset
-        c->begin_recorded = false;
-        if (with_events) HIPCHK(hipEventRecord(c->ev_pyr[slot], s));
-        launch_detect(d, 0, -1, s);
-        launch_detect(d, 1, -1, s);
+        if (f.act) HIPCHK(upload_act(c, slot, s));
+        detected = launch_front_fused(f, dp, stride, s);               // lone stream: ingest + pyramid beside detection, two launches
+        if (detected) path |= SVO_PATH_FRONT_FUSED;
+        else launch_ingest_pyramid(f, dp, stride, s, PYR_BEGIN);       // + the per-frame reset
     }
-    const bool gated = !c->capturing && (shares_device || lk_chained(c));   // chained LK launches (a captured graph cannot wait for another stream's event)
-    if (gated) {
-        LkGate& g = g_lk_gate[c->device];
-        std::lock_guard<std::mutex> lock(g.mu);
-        if (g.armed) HIPCHK(hipStreamWaitEvent(s, g.ev, 0));
+    c->begin_recorded = ahead;
+    HIPCHK(record(EV_PYR));                                            // (fused front: ms[0] = the whole front, ms[1] ~ 0)
+    if (!detected) { launch_detect(f, 0, -1, s); launch_detect(f, 1, -1, s); }
+    // chained LK launches (a captured graph cannot wait for another stream's event): wait before the launch, record after it
+    LkGate* const gate = !c->capturing && share.shared ? &g_lk_gate[c->device] : nullptr;
+    if (gate) {
+        std::lock_guard<std::mutex> lock(gate->mu);
+        if (gate->armed) HIPCHK(hipStreamWaitEvent(s, gate->ev, 0));
         path |= SVO_PATH_LK_CHAINED;
     }
-    if (with_events) HIPCHK(hipEventRecord(c->ev_lk0[slot], s));
-    if (!launch_lk_chain(d, gn, s, 1)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
-    if (with_events) HIPCHK(hipEventRecord(c->ev_lk1[slot], s));
-    if (gated) {
-        LkGate& g = g_lk_gate[c->device];
-        std::lock_guard<std::mutex> lock(g.mu);
-        if (!g.ev) HIPCHK(hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(g.ev, s));
-        g.armed = true;
+    HIPCHK(record(EV_LK0));
+    if (!launch_lk_chain(f, gn, s, 1)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
+    HIPCHK(record(EV_LK1));
+    if (gate) {
+        std::lock_guard<std::mutex> lock(gate->mu);
+        if (!gate->ev) HIPCHK(hipEventCreateWithFlags(&gate->ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(gate->ev, s));
+        gate->armed = true;
     }
-    launch_compact(d, s);
-    const bool tri_epnp = launch_triangulate_epnp_fused(d, s);          // lone stream: the first EPnP chunk runs beside the triangulation
-    if (!tri_epnp) launch_triangulate(d, s);
+    launch_compact(f, s);
+    const bool tri_epnp = launch_triangulate_epnp_fused(f, s);          // lone stream: the first EPnP chunk runs beside the triangulation
     if (tri_epnp) path |= SVO_PATH_TRI_EPNP_FUSED;
-    if (with_events) HIPCHK(hipEventRecord(c->ev_tri[slot], s));       // (fused: the stage timers count that chunk with the triangulation)
-    launch_pnp(d, s, tri_epnp);
-    launch_frame_end(d, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
+    else launch_triangulate(f, s);
+    HIPCHK(record(EV_TRI));                                            // (fused: the stage timers count that chunk with the triangulation)
+    launch_pnp(f, s, tri_epnp);
+    launch_frame_end(f, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
     c->last_path = path;
     return SVO_OK;
 }
 
-// Ragged-frame arguments: every active sequence needs both image pointers (an idle one's are never read, and the arrays themselves
-// may be NULL when no sequence is active).  *n_act = number of active sequences.
-static int check_active(const svo_context* c, const uint8_t* const* left, const uint8_t* const* right, const uint8_t* active, int* n_act) {
+// The one check of a frame's arguments (svo_last_error shows which failed first: the order is part of the interface).  Without a
+// mask both arrays must be there; with one every ACTIVE sequence needs both image pointers — an idle one's are never read, and the
+// arrays may be NULL when no sequence is active.  pointers_last: svo_submit_batch_masked looks at a masked frame's pointers last.
+static int check_stride(const svo_context* c, int stride) {
+    return stride < in_width(c) * c->d.CN ? fail_arg("stride < width * channels (raw width when rectifying)") : SVO_OK;
+}
+static int check_frame_args(const svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride, const uint8_t* active,
+                            bool pointers_last = false) {
+    const auto pointers = [&]() {
+        if (!active) return left && right ? SVO_OK : fail_arg("null argument");
+        for (int i = 0; i < c->d.B; i++)
+            if (active[i] && (!left || !right || !left[i] || !right[i])) return fail_arg("null image pointer for an active sequence");
+        return (int)SVO_OK;
+    };
+    int rc;
+    if (!pointers_last && (rc = pointers()) != SVO_OK) return rc;
+    if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
+    if ((rc = check_stride(c, stride)) != SVO_OK) return rc;
+    return pointers_last ? pointers() : SVO_OK;
+}
+
+// the rectification map of (sequence, camera): its own, else the context's shared one (nullptr: none installed)
+static const uint8_t* map_of(const svo_context* c, int seq, int cam) {
+    const uint8_t* own = c->own_map[2 * seq + cam];
+    return own ? own : c->shared_map[cam];
+}
+
+// The slot's rows of the pinned tables for one frame: image pointers, the active list and flags of a masked frame, the maps of a
+// rectifying context (free: the slot's previous frame has been collected).  *n_act = -1 for a frame every sequence takes — a mask
+// with every flag set is the unmasked frame — else the number of active sequences.
+static int fill_slot_rows(svo_context* c, int slot, const uint8_t* const* left_dev, const uint8_t* const* right_dev, const uint8_t* active, int* n_act) {
     const int B = c->d.B;
-    int n = 0;
-    for (int i = 0; i < B; i++) {
-        if (active && !active[i]) continue;
-        if (!left || !right || !left[i] || !right[i]) return fail_arg("null image pointer for an active sequence");
-        n++;
+    const uint8_t** hp = ring_row(c, c->h_ptrs, slot);
+    *n_act = -1;
+    if (active) {
+        int* ha = ring_row(c, c->h_act, slot);
+        int n = 0;
+        for (int i = 0; i < B; i++) { ha[B + i] = active[i] ? 1 : 0; if (active[i]) ha[n++] = i; }
+        if (n < B) *n_act = n;
     }
-    *n_act = n;
+    const uint8_t** hm = c->raw_w > 0 ? ring_row(c, c->h_maps, slot) : nullptr;
+    for (int i = 0; i < B; i++) {
+        const bool on = !active || active[i];
+        hp[i] = on ? left_dev[i] : nullptr; hp[B + i] = on ? right_dev[i] : nullptr;
+        for (int cam = 0; hm && cam < 2; cam++) {
+            const uint8_t* m = map_of(c, i, cam);
+            if (on && !m) { g_err = "rectifying context: a sequence has no rectification map (svo_set_rectification_maps)"; return SVO_ERR_STATE; }
+            hm[cam * B + i] = on ? m : nullptr;
+        }
+    }
+    return SVO_OK;
+}
+
+// SVO_GRAPH=1: the frame as a replay of the slot's captured launch list, re-captured when its GraphKey differs: the capture bakes
+// in the stride, the LK grid and which builds of the f64 kernels run (a context captured while it had the device to itself would
+// keep the full-register builds that cannot start beside another many-sequence context's LK grid).  *replayed = false: the
+// capture failed and the option is now off — capture is an optimisation, the caller issues the same launches directly.
+static int replay_graph(svo_context* c, int slot, int stride, int gn, DeviceSharing share, bool* replayed) {
+    hipStream_t s = c->stream;
+    RingSlot& r = c->ring[slot];
+    HIPCHK(choose_pnp_build(c->d, share.lean));                        // before the capture: issue_frame then finds the lean EPnP prepared
+    const GraphKey now = {stride, gn, c->d.co_resident};
+    if (!r.gexec || !(r.key == now)) {
+        if (r.gexec) { (void)hipGraphExecDestroy(r.gexec); r.gexec = nullptr; }
+        hipGraph_t g = nullptr;
+        bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        if (ok) {
+            c->capturing = true;
+            const int rc = issue_frame(c, slot, stride, gn, false, share);
+            c->capturing = false;
+            ok = (hipStreamEndCapture(s, &g) == hipSuccess) && rc == SVO_OK && g;
+        }
+        if (ok) ok = hipGraphInstantiate(&r.gexec, g, nullptr, nullptr, 0) == hipSuccess;
+        if (g) (void)hipGraphDestroy(g);
+        if (ok) { r.key = now; r.g_path = c->last_path; }
+        else { (void)hipGetLastError(); r.gexec = nullptr; c->use_graph = false; }
+    }
+    *replayed = c->use_graph;
+    if (!c->use_graph) return SVO_OK;
+    HIPCHK(hipGraphLaunch(r.gexec, s));
+    c->begin_recorded = false;
+    c->last_path = r.g_path | SVO_PATH_GRAPH;
     return SVO_OK;
 }
 
 // Enqueue one frame.  ptrs: host arrays of B DEVICE image pointers.  active: NULL (every sequence takes the frame) or B flags,
-// checked by check_active; a mask with every flag set is the unmasked frame.
+// checked by check_frame_args.
 static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
                          const uint8_t* active = nullptr) {
     if (c->inflight >= SVO_RING) { g_err = "too many frames in flight (collect first)"; return SVO_ERR_STATE; }
-    DevBuffers& d = c->d;
-    const int slot = c->head, B = d.B;
-    const uint8_t** hp = c->h_ptrs + (size_t)slot * 2 * B;
-    int n_act = -1;                                                  // -1: unmasked
-    if (active) {
-        int* ha = c->h_act + (size_t)slot * 2 * B;                   // free: the slot's previous frame has been collected
-        int n = 0;
-        for (int i = 0; i < B; i++) { ha[B + i] = active[i] ? 1 : 0; if (active[i]) ha[n++] = i; }
-        if (n < B) n_act = n;
-    }
-    if (c->raw_w > 0) {                                              // the frame's maps, in the slot's row beside its image pointers
-        const uint8_t** hm = c->h_maps + (size_t)slot * 2 * B;
-        for (int i = 0; i < B; i++) {
-            const bool on = !active || active[i];
-            for (int cam = 0; cam < 2; cam++) {
-                const uint8_t* m = c->own_map[2 * i + cam] ? c->own_map[2 * i + cam] : c->shared_map[cam];
-                if (on && !m) { g_err = "rectifying context: a sequence has no rectification map (svo_set_rectification_maps)"; return SVO_ERR_STATE; }
-                hm[cam * B + i] = on ? m : nullptr;
-            }
-        }
-    }
-    for (int i = 0; i < B; i++) {
-        const bool on = !active || active[i];
-        hp[i] = on ? left_dev[i] : nullptr; hp[B + i] = on ? right_dev[i] : nullptr;
-    }
-    hipStream_t s = c->stream;
+    const int slot = c->head;
+    RingSlot& r = c->ring[slot];
+    int n_act, rc;
+    if ((rc = fill_slot_rows(c, slot, left_dev, right_dev, active, &n_act)) != SVO_OK) return rc;
     // LK grid sized from the last feature counts the host has seen (+30 %); the kernel strides, so an underestimate is only slower
     int gn = c->lk_grid;
     if (c->lk_hint > 0) {
@@ -509,41 +554,15 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
         if (c->use_graph) h = (h + 511) / 512 * 512;                 // coarse steps: the graph is re-captured when this changes
         if (h < gn) gn = h;
     }
-    HIPCHK(hipEventRecord(c->ev_f0[slot], s));
+    const DeviceSharing share = device_sharing(c);                   // read once per frame: every use below sees the same answer
+    HIPCHK(hipEventRecord(r.ev[EV_F0], c->stream));
     bool replayed = false;
-    if (c->use_graph && n_act < 0 && c->raw_w == 0) {                // a ragged or rectifying frame runs from the launch list
-        // the captured launch list bakes in which builds of the f64 kernels run: a context captured while it had the device to
-        // itself must be re-captured once another many-sequence context exists (and back), or it would keep the full-register
-        // builds that cannot start beside the other's LK grid
-        const int shares_now = lk_gated(c) ? 1 : 0;
-        HIPCHK(choose_pnp_build(c->d, shares_now != 0));            // before the capture: issue_frame then finds the lean EPnP prepared
-        const int co_now = c->d.co_resident;
-        if (!c->gexec[slot] || c->g_stride[slot] != stride || c->g_gn[slot] != gn || c->g_co[slot] != co_now) {
-            if (c->gexec[slot]) { (void)hipGraphExecDestroy(c->gexec[slot]); c->gexec[slot] = nullptr; }
-            hipGraph_t g = nullptr;
-            bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-            if (ok) {
-                c->capturing = true;
-                const int rc = issue_frame(c, slot, stride, gn, false, shares_now);
-                c->capturing = false;
-                ok = (hipStreamEndCapture(s, &g) == hipSuccess) && rc == SVO_OK && g;
-            }
-            if (ok) ok = hipGraphInstantiate(&c->gexec[slot], g, nullptr, nullptr, 0) == hipSuccess;
-            if (g) (void)hipGraphDestroy(g);
-            if (!ok) {                                                // capture is an optimisation: without it the same launches are issued directly
-                (void)hipGetLastError();
-                c->gexec[slot] = nullptr; c->use_graph = false;
-            } else { c->g_stride[slot] = stride; c->g_gn[slot] = gn; c->g_co[slot] = co_now; c->g_path[slot] = c->last_path; }
-        }
-        if (c->use_graph) {
-            HIPCHK(hipGraphLaunch(c->gexec[slot], s)); replayed = true; c->begin_recorded = false;
-            c->last_path = c->g_path[slot] | SVO_PATH_GRAPH;
-        }
-    }
-    if (!replayed) { const int rc = issue_frame(c, slot, stride, gn, c->stage_timing, -1, n_act); if (rc != SVO_OK) return rc; }
-    c->staged_slot[slot] = !replayed && c->stage_timing;
+    if (c->use_graph && n_act < 0 && c->raw_w == 0)                  // a ragged or rectifying frame runs from the launch list
+        if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
+    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act)) != SVO_OK) return rc;
+    r.staged = !replayed && c->stage_timing;
     c->staged_inputs = false;
-    HIPCHK(hipEventRecord(c->ev_done[slot], s));
+    HIPCHK(hipEventRecord(r.ev[EV_DONE], c->stream));
     HIPCHK(hipGetLastError());
     c->head = (c->head + 1) % SVO_RING; c->inflight++; c->n_enqueued++;
     return SVO_OK;
@@ -552,7 +571,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
 static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_stats* stats) {
     if (c->inflight <= 0) { g_err = "nothing to collect"; return SVO_ERR_STATE; }
     const int slot = c->tail, B = c->d.B;
-    HIPCHK(hipEventSynchronize(c->ev_done[slot]));
+    HIPCHK(hipEventSynchronize(c->ring[slot].ev[EV_DONE]));
     const FrameResult* r = c->h_results + (size_t)slot * B;
     for (int i = 0; i < B; i++) {
         if (T_out) memcpy(T_out + 16 * i, r[i].T, sizeof(double) * 16);
@@ -574,24 +593,17 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
     return SVO_OK;
 }
 
-extern "C" int svo_submit_batch(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride) {
-    if (!c || !left_dev || !right_dev) return fail_arg("null argument");
-    if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
-    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
-    HIPCHK(hipSetDevice(c->device));
-    return enqueue_frame(c, left_dev, right_dev, stride);
-}
-
 extern "C" int svo_submit_batch_masked(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
                                        const uint8_t* active) {
     if (!c) return fail_arg("null context");
-    if (!active) return svo_submit_batch(c, left_dev, right_dev, stride);
-    if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
-    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
-    int n_act = 0, rc;
-    if ((rc = check_active(c, left_dev, right_dev, active, &n_act)) != SVO_OK) return rc;
+    if (const int rc = check_frame_args(c, left_dev, right_dev, stride, active, active != nullptr)) return rc;
     HIPCHK(hipSetDevice(c->device));
     return enqueue_frame(c, left_dev, right_dev, stride, active);
+}
+
+extern "C" int svo_submit_batch(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride) {
+    if (!c) return fail_arg("null argument");
+    return svo_submit_batch_masked(c, left_dev, right_dev, stride, nullptr);
 }
 
 extern "C" int svo_reset_sequence(svo_context* c, int seq, const float Pl[12], const float Pr[12]) {
@@ -613,22 +625,20 @@ extern "C" int svo_collect(svo_context* c, double* T_out, int* ok_out, svo_frame
     return collect_frame(c, T_out, ok_out, stats);
 }
 
-static int process_batch(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                         int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats) {
-    if (!c->projection_set) { g_err = "svo_set_projection must be called first"; return SVO_ERR_STATE; }
-    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
+extern "C" int svo_process_batch_masked(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                                        int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats) {
+    if (!c) return fail_arg("null context");
+    int rc = check_frame_args(c, left, right, stride, active);
+    if (rc != SVO_OK) return rc;
     if (c->inflight != 0) { g_err = "svo_process_batch with frames in flight"; return SVO_ERR_STATE; }
     HIPCHK(hipSetDevice(c->device));
-    const int W = in_width(c);
-    int rc;
     if (images_on_device) {
         rc = enqueue_frame(c, left, right, stride, active);
     } else {
         // the caller's buffers are only borrowed for the duration of the call: copy to the device first (SURVEY.md §8b "Ownership")
-        const size_t rowb = (size_t)W * c->d.CN;
         std::vector<const uint8_t*> lp, rp;
         if ((rc = stage_host_images(c, left, right, stride, lp, rp, active)) != SVO_OK) return rc;
-        rc = enqueue_frame(c, lp.data(), rp.data(), (int)rowb, active);
+        rc = enqueue_frame(c, lp.data(), rp.data(), in_width(c) * c->d.CN, active);
     }
     if (rc != SVO_OK) return rc;
     return collect_frame(c, T_out, ok_out, stats);
@@ -636,17 +646,8 @@ static int process_batch(svo_context* c, const uint8_t* const* left, const uint8
 
 extern "C" int svo_process_batch(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
                                  int images_on_device, double* T_out, int* ok_out, svo_frame_stats* stats) {
-    if (!c || !left || !right) return fail_arg("null argument");
-    return process_batch(c, left, right, stride, images_on_device, nullptr, T_out, ok_out, stats);
-}
-
-extern "C" int svo_process_batch_masked(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                                        int images_on_device, const uint8_t* active, double* T_out, int* ok_out, svo_frame_stats* stats) {
-    if (!c) return fail_arg("null context");
-    if (!active) return svo_process_batch(c, left, right, stride, images_on_device, T_out, ok_out, stats);
-    int n_act = 0, rc;
-    if ((rc = check_active(c, left, right, active, &n_act)) != SVO_OK) return rc;
-    return process_batch(c, left, right, stride, images_on_device, active, T_out, ok_out, stats);
+    if (!c) return fail_arg("null argument");
+    return svo_process_batch_masked(c, left, right, stride, images_on_device, nullptr, T_out, ok_out, stats);
 }
 
 extern "C" int svo_process(svo_context* c, const uint8_t* left, const uint8_t* right, int stride, double T_out[16], svo_frame_stats* stats) {
@@ -671,6 +672,12 @@ extern "C" void* svo_alloc_pinned(size_t bytes) {
     return p;
 }
 extern "C" void svo_free_pinned(void* p) { if (p) (void)hipHostFree(p); }
+
+// rows of rowb bytes, `stride` apart, packed: one memcpy when they already are
+static void pack_rows(uint8_t* dst, const uint8_t* src, size_t rowb, size_t rows, size_t stride) {
+    if (stride == rowb) memcpy(dst, src, rowb * rows);
+    else for (size_t y = 0; y < rows; y++) memcpy(dst + y * rowb, src + y * stride, rowb);
+}
 
 // Host images -> pinned staging -> device staging (one contiguous H2D copy); fills lp / rp with the device addresses.
 // Images that already live in page-locked memory with packed rows skip the staging copy: the DMA reads them in place (the call
@@ -709,9 +716,7 @@ static int stage_host_images(svo_context* c, const uint8_t* const* left, const u
                 HIPCHK(hipMemcpyAsync(c->staging + img * (cam * B + i), src[i], img, hipMemcpyHostToDevice, c->stream));
                 continue;
             }
-            uint8_t* h = c->h_staging + img * (cam * B + i);
-            if ((size_t)stride == rowb) memcpy(h, src[i], img);
-            else for (int y = 0; y < H; y++) memcpy(h + (size_t)y * rowb, src[i] + (size_t)y * stride, rowb);
+            pack_rows(c->h_staging + img * (cam * B + i), src[i], rowb, (size_t)H, (size_t)stride);
         }
         if (!all_direct) HIPCHK(hipMemcpyAsync(c->staging + img * B * cam, c->h_staging + img * B * cam, img * B, hipMemcpyHostToDevice, c->stream));
     }
@@ -720,6 +725,21 @@ static int stage_host_images(svo_context* c, const uint8_t* const* left, const u
 
 static int read_state(svo_context* c, int seq, SeqState* hs);
 static int set_state(svo_context* c, const SeqState& hs);
+
+// the end of both circularMatching entry points (vo.cpp:203-230): the four LK passes, then every pass's raw points and the mask
+static int circular_tail(svo_context* c, int n, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok) {
+    const DevBuffers& d = c->d;
+    if (!launch_lk_chain(d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(pl1, d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pr1, d.pr1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pr0, d.pr0, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pl0_circle, d.plc, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ok, d.okmask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; i++) ok[i] &= 1;                                       // bit0 = status0..3 && loop closure (vo.cpp:227-230)
+    return SVO_OK;
+}
 
 // VisualOdometry::circularMatching as a member call on the context's own state (vo.h:374-379, vo.cpp:169-240 without the
 // compaction): the T0 side is the pyramid pair the context cached (lastLeftPyramid / lastRightPyramid, vo.h:257-258), the
@@ -731,12 +751,12 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     if (!c || !left_t1 || !right_t1 || n < 0) return fail_arg("bad arguments");
     if (n > 0 && (!pl0 || !pl1 || !pr1 || !pr0 || !pl0_circle || !ok)) return fail_arg("null arrays");
     if (c->d.B != 1) return fail_arg("svo_circular_matching needs a context created with n_seq == 1");
-    if (stride < in_width(c) * c->d.CN) return fail_arg("stride < width * channels (raw width when rectifying)");
+    int rc = check_stride(c, stride); if (rc != SVO_OK) return rc;
     if (c->inflight != 0) { g_err = "svo_circular_matching with frames in flight"; return SVO_ERR_STATE; }
     if (n == 0) return SVO_OK;                                                    // vo.cpp:179-181
     if (n > c->d.CAP) { g_err = "more points than the context's feature capacity"; return SVO_ERR_CAPACITY; }
     HIPCHK(hipSetDevice(c->device));
-    SeqState hs; int rc = read_state(c, 0, &hs); if (rc != SVO_OK) return rc;
+    SeqState hs; if ((rc = read_state(c, 0, &hs)) != SVO_OK) return rc;
     if (hs.frame_id < 1 || hs.slot_pyr_t0 < 0) { g_err = "no cached pyramids: call svo_process first (the reference primes them in stereo_callback, vo.cpp:47-56)"; return SVO_ERR_STATE; }
     const SeqState keep = hs;
     // every error return below leaves the context's tracking state as it was: the guard writes `keep` back unless the call
@@ -753,23 +773,16 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     std::vector<const uint8_t*> lp, rp;
     const uint8_t* l[1] = {left_t1}; const uint8_t* r[1] = {right_t1};
     if ((rc = stage_host_images(c, l, r, stride, lp, rp)) != SVO_OK) return rc;
-    const uint8_t** hp = c->h_ptrs; hp[0] = lp[0]; hp[1] = rp[0];
-    if (c->raw_w > 0) {                                                           // no frame in flight: ring slot 0's map row is free
-        for (int cam = 0; cam < 2; cam++) c->h_maps[cam] = c->own_map[cam] ? c->own_map[cam] : c->shared_map[cam];
-        if (!c->h_maps[0] || !c->h_maps[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
-        c->d.rmap = c->d_maps;
+    const uint8_t** hp = ring_row(c, c->h_ptrs, 0);                               // no frame in flight: ring slot 0's rows are free
+    hp[0] = lp[0]; hp[1] = rp[0];
+    if (c->raw_w > 0) {
+        const uint8_t** hm = ring_row(c, c->h_maps, 0);
+        for (int cam = 0; cam < 2; cam++) hm[cam] = map_of(c, 0, cam);
+        if (!hm[0] || !hm[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
     }
-    launch_ingest_pyramid(c->d, c->d.img_ptrs, in_width(c) * c->d.CN, c->stream, PYR_T1);          // vo.cpp:200-201
-    c->d.rmap = nullptr;
-    if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // vo.cpp:203-230 (the caller gets every pass's raw points)
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pl1, c->d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(pr1, c->d.pr1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(pr0, c->d.pr0, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(pl0_circle, c->d.plc, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(ok, c->d.okmask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; i++) ok[i] &= 1;                                       // bit0 = status0..3 && loop closure (vo.cpp:227-230)
+    const DevBuffers f = frame_view(c, 0, -1);
+    launch_ingest_pyramid(f, ring_row(c, f.img_ptrs, 0), in_width(c) * f.CN, c->stream, PYR_T1);   // vo.cpp:200-201
+    if ((rc = circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok)) != SVO_OK) return rc;
     SeqState out = keep;
     out.slot_pyr_t0 = t1;                                                         // lastLeftPyramid = pyramidl1 (vo.cpp:231-232)
     rc = set_state(c, out);
@@ -786,22 +799,21 @@ extern "C" int svo_set_stage_timing(svo_context* c, int on) {
 extern "C" int svo_get_last_timing(svo_context* c, float* lk_ms, float* frame_ms) {
     if (!c || c->last_slot < 0) return fail_arg("no frame collected yet");
     HIPCHK(hipSetDevice(c->device));
-    const int s = c->last_slot;
+    const RingSlot& r = c->ring[c->last_slot];
     if (lk_ms) {
-        if (!c->staged_slot[s]) { g_err = "no stage events for this frame: call svo_set_stage_timing(ctx, 1) first (and SVO_GRAPH must be off)"; return SVO_ERR_STATE; }
-        HIPCHK(hipEventElapsedTime(lk_ms, c->ev_lk0[s], c->ev_lk1[s]));
+        if (!r.staged) { g_err = "no stage events for this frame: call svo_set_stage_timing(ctx, 1) first (and SVO_GRAPH must be off)"; return SVO_ERR_STATE; }
+        HIPCHK(hipEventElapsedTime(lk_ms, r.ev[EV_LK0], r.ev[EV_LK1]));
     }
-    if (frame_ms) HIPCHK(hipEventElapsedTime(frame_ms, c->ev_f0[s], c->ev_done[s]));
+    if (frame_ms) HIPCHK(hipEventElapsedTime(frame_ms, r.ev[EV_F0], r.ev[EV_DONE]));
     return SVO_OK;
 }
 
 extern "C" int svo_get_stage_timing(svo_context* c, float ms[5]) {
     if (!c || !ms || c->last_slot < 0) return fail_arg("no frame collected yet");
     HIPCHK(hipSetDevice(c->device));
-    const int s = c->last_slot;
-    if (!c->staged_slot[s]) { g_err = "no stage events for this frame: call svo_set_stage_timing(ctx, 1) first (and SVO_GRAPH must be off)"; return SVO_ERR_STATE; }
-    hipEvent_t ev[6] = {c->ev_f0[s], c->ev_pyr[s], c->ev_lk0[s], c->ev_lk1[s], c->ev_tri[s], c->ev_done[s]};
-    for (int i = 0; i < 5; i++) HIPCHK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    const RingSlot& r = c->ring[c->last_slot];
+    if (!r.staged) { g_err = "no stage events for this frame: call svo_set_stage_timing(ctx, 1) first (and SVO_GRAPH must be off)"; return SVO_ERR_STATE; }
+    for (int i = 0; i + 1 < EV_COUNT; i++) HIPCHK(hipEventElapsedTime(&ms[i], r.ev[i], r.ev[i + 1]));
     return SVO_OK;
 }
 
@@ -878,6 +890,16 @@ struct DevTmp {                                   // RAII-ish scratch allocation
         if (e == hipSuccess) { p.push_back(q); *out = (T*)q; }
         return e;
     }
+    // allocate and fill from host memory: count elements, or `rows` packed rows of rowb bytes that lie `stride` apart there
+    template <typename T> hipError_t put(T** out, const void* host, size_t count) {
+        const hipError_t e = get(out, count);
+        return e != hipSuccess ? e : hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice);
+    }
+    hipError_t put_rows(uint8_t** out, const uint8_t* host, size_t rowb, size_t rows, size_t stride) {
+        const hipError_t e = get(out, rowb * rows);
+        return e != hipSuccess ? e : hipMemcpy2D(*out, rowb, host, stride, rowb, rows, hipMemcpyHostToDevice);
+    }
+    template <typename T> static hipError_t download(void* host, const T* dev, size_t count) { return hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost); }
 };
 
 static int use_device(int device) {
@@ -896,22 +918,20 @@ struct CtxGuard { svo_context* c = nullptr; ~CtxGuard() { svo_destroy(c); } };
 // configuration match and its capacity suffices.  Every call overwrites the whole sequence record, so nothing leaks from one
 // call into the next.  svo_stage_cache_clear() frees it (it is deliberately not freed at thread exit: the HIP runtime may be
 // gone by then).
-static bool cfg_equal(const svo_config& a, const svo_config& b) {
-    return a.bucket_start_row == b.bucket_start_row && a.buckets_along_height == b.buckets_along_height && a.buckets_along_width == b.buckets_along_width &&
-           a.features_per_bucket == b.features_per_bucket && a.features_threshold == b.features_threshold &&
-           a.pre_matching_feature_threshold == b.pre_matching_feature_threshold && a.age_threshold == b.age_threshold && a.fast_threshold == b.fast_threshold &&
-           a.ransac_reprojection_error == b.ransac_reprojection_error && a.ransac_iterations == b.ransac_iterations &&
-           a.optical_flow_min_eig_threshold == b.optical_flow_min_eig_threshold &&
-           a.circular_matching_success_threshold == b.circular_matching_success_threshold && a.max_translation_norm == b.max_translation_norm &&
-           a.max_rotation_norm == b.max_rotation_norm && a.win_w == b.win_w && a.win_h == b.win_h && a.max_level == b.max_level &&
-           a.lk_max_count == b.lk_max_count && a.lk_epsilon == b.lk_epsilon && a.ransac_confidence == b.ransac_confidence &&
-           a.max_features == b.max_features && a.channels == b.channels && a.lk_float_sums == b.lk_float_sums;
-}
-// the fields of a configuration that size or shape a context's device buffers (everything else is a parameter kernels read)
-static bool cfg_same_shape(const svo_config& a, const svo_config& b) {
-    return a.bucket_start_row == b.bucket_start_row && a.buckets_along_height == b.buckets_along_height && a.buckets_along_width == b.buckets_along_width &&
-           a.features_per_bucket == b.features_per_bucket && a.win_w == b.win_w && a.win_h == b.win_h && a.max_level == b.max_level && a.channels == b.channels;
-}
+// Every field of svo_config is named exactly once, in one of two lists: the fields that size or shape a context's device
+// buffers, and the parameters kernels only read.  A new field belongs in one of them: the size check stops the build until it is
+// there.  (Compared field by field, not as bytes: a caller's struct may carry uninitialised padding.)
+#define SVO_CFG_SHAPE_FIELDS(X) \
+    X(bucket_start_row) X(buckets_along_height) X(buckets_along_width) X(features_per_bucket) X(win_w) X(win_h) X(max_level) X(channels)
+#define SVO_CFG_PARAM_FIELDS(X) \
+    X(features_threshold) X(pre_matching_feature_threshold) X(age_threshold) X(fast_threshold) X(ransac_reprojection_error) \
+    X(ransac_iterations) X(optical_flow_min_eig_threshold) X(circular_matching_success_threshold) X(max_translation_norm) \
+    X(max_rotation_norm) X(lk_max_count) X(lk_epsilon) X(ransac_confidence) X(max_features) X(lk_float_sums)
+static_assert(sizeof(svo_config) == 112, "svo_config changed: name the new field in SVO_CFG_SHAPE_FIELDS or SVO_CFG_PARAM_FIELDS");
+#define SVO_CFG_SAME(field) && a.field == b.field
+static bool cfg_same_shape(const svo_config& a, const svo_config& b) { return true SVO_CFG_SHAPE_FIELDS(SVO_CFG_SAME); }
+static bool cfg_equal(const svo_config& a, const svo_config& b) { return cfg_same_shape(a, b) SVO_CFG_PARAM_FIELDS(SVO_CFG_SAME); }
+#undef SVO_CFG_SAME
 // A cached stage context takes a new configuration IN PLACE when only parameters changed (thresholds, iteration counts up to the
 // allocated number, confidence, termination criteria, ...): callers that alternate such parameters between calls keep their
 // buffers instead of paying a context's worth of hipMalloc / hipFree per call.
@@ -923,13 +943,13 @@ static bool stage_reconfigure(svo_context* c, const svo_config& cfg) {
     c->lk_room = lk_registers_left(d);
     return true;
 }
-struct StageCache { svo_context* c = nullptr; svo_config cfg; int device = -1, w = 0, h = 0; };
-// One cached context per calling thread.  The thread_local slot holds the pointer for speed; a mutex-protected registry owns the
-// contexts, so that (a) a thread that exits hands its context back (its slot's destructor marks the entry free — the context is
-// then REUSED by the next thread that needs one of the same shape, or freed by svo_stage_cache_clear_all), and (b) nothing is
-// destroyed from a thread-exit destructor, where the HIP runtime may already be gone.  Short-lived worker threads therefore
-// cost at most one context per concurrently LIVE thread, not one per thread ever started.
-struct StageEntry { StageCache sc; bool in_use = false; };
+// One cached context per calling thread; the context itself holds the key it was made for (device, image size, capacity, d.cfg).
+// The thread_local slot holds the entry for speed; a mutex-protected registry owns the contexts, so that (a) a thread that exits
+// hands its context back (its slot's destructor marks the entry free — the context is then REUSED by the next thread that needs
+// one of the same shape, or freed by svo_stage_cache_clear_all), and (b) nothing is destroyed from a thread-exit destructor,
+// where the HIP runtime may already be gone.  Short-lived worker threads therefore cost at most one context per concurrently
+// LIVE thread, not one per thread ever started.
+struct StageEntry { svo_context* c = nullptr; bool in_use = false; };
 static std::mutex g_stage_mu;
 static std::vector<StageEntry*> g_stage_all;
 struct StageSlot {
@@ -937,51 +957,49 @@ struct StageSlot {
     ~StageSlot() { if (e) { std::lock_guard<std::mutex> lock(g_stage_mu); e->in_use = false; e = nullptr; } }
 };
 static thread_local StageSlot g_stage_slot;
-static StageCache& stage_cache_of_this_thread(const svo_config& cfg, int device, int w, int h, int cap) {
+// can the cached context serve a call on this device, at this image size, with this many points?
+static bool stage_fits(const svo_context* c, int device, int w, int h, int cap) {
+    return c && c->device == device && c->d.geom.W == w && c->d.geom.H == h && c->d.CAP >= cap;
+}
+static svo_context*& stage_cache_of_this_thread(int device, int w, int h, int cap) {
     if (!g_stage_slot.e) {
         std::lock_guard<std::mutex> lock(g_stage_mu);
         StageEntry* pick = nullptr;
-        for (StageEntry* e : g_stage_all)                              // an orphan of the same shape first, then any orphan
-            if (!e->in_use && e->sc.c && e->sc.device == device && e->sc.w == w && e->sc.h == h && e->sc.c->d.CAP >= cap) { pick = e; break; }
+        for (StageEntry* e : g_stage_all)                              // an orphan that fits first, then any orphan
+            if (!e->in_use && stage_fits(e->c, device, w, h, cap)) { pick = e; break; }
         if (!pick) for (StageEntry* e : g_stage_all) if (!e->in_use) { pick = e; break; }
         if (!pick) { pick = new StageEntry(); g_stage_all.push_back(pick); }
         pick->in_use = true;
         g_stage_slot.e = pick;
     }
-    (void)cfg;
-    return g_stage_slot.e->sc;
+    return g_stage_slot.e->c;
 }
 static int stage_ctx(const svo_config& cfg_in, int device, int w, int h, int cap, svo_context** out) {
     svo_config cfg = cfg_in;
-    if (cfg.channels == 0) cfg.channels = 1;
-    StageCache& sc = stage_cache_of_this_thread(cfg, device, w, h, cap);
-    // (a stage context never shares the device with another's LK: choose_pnp_build(.., false) is lean only under the test knob)
-    if (sc.c && sc.device == device && sc.w == w && sc.h == h && sc.c->d.CAP >= cap) {
+    if (cfg.channels == 0) cfg.channels = 1;                          // as ctx_create stores it: d.cfg is what the next call is compared with
+    svo_context*& sc = stage_cache_of_this_thread(device, w, h, cap);
+    bool keep = false;
+    if (stage_fits(sc, device, w, h, cap)) {
         HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamSynchronize(sc.c->stream));
-        if (cfg_equal(sc.cfg, cfg) || stage_reconfigure(sc.c, cfg)) {
-            sc.cfg = cfg;
-            HIPCHK(choose_pnp_build(sc.c->d, false));
-            *out = sc.c;
-            return SVO_OK;
-        }
+        HIPCHK(hipStreamSynchronize(sc->stream));
+        keep = cfg_equal(sc->d.cfg, cfg) || stage_reconfigure(sc, cfg);
     }
-    if (sc.c) { svo_destroy(sc.c); sc.c = nullptr; }
-    int rc = ctx_create(&cfg, device, 1, w, h, cap, &sc.c);
-    if (rc != SVO_OK) { sc.c = nullptr; return rc; }
-    sc.cfg = cfg; sc.device = device; sc.w = w; sc.h = h;
-    HIPCHK(choose_pnp_build(sc.c->d, false));
-    *out = sc.c;
+    if (!keep) {
+        if (sc) { svo_destroy(sc); sc = nullptr; }
+        if (const int rc = ctx_create(&cfg, device, 1, w, h, cap, &sc)) return rc;   // (leaves sc null when it fails)
+    }
+    HIPCHK(choose_pnp_build(sc->d, false));   // a stage context never shares the device with another's LK: lean only under the test knob
+    *out = sc;
     return SVO_OK;
 }
 extern "C" void svo_stage_cache_clear(void) {                       // this thread's cached context
-    if (g_stage_slot.e && g_stage_slot.e->sc.c) { svo_destroy(g_stage_slot.e->sc.c); g_stage_slot.e->sc.c = nullptr; }
+    if (g_stage_slot.e && g_stage_slot.e->c) { svo_destroy(g_stage_slot.e->c); g_stage_slot.e->c = nullptr; }
 }
 extern "C" int svo_stage_cache_clear_all(void) {                    // every cached context no live call is using (exited threads' too); returns how many were freed
     std::lock_guard<std::mutex> lock(g_stage_mu);
     int freed = 0;
     for (StageEntry* e : g_stage_all)
-        if (e->sc.c && (!e->in_use || e == g_stage_slot.e)) { svo_destroy(e->sc.c); e->sc.c = nullptr; freed++; }
+        if (e->c && (!e->in_use || e == g_stage_slot.e)) { svo_destroy(e->c); e->c = nullptr; freed++; }
     return freed;
 }
 
@@ -992,8 +1010,7 @@ static int upload_image(svo_context* c, int slot, int cam, const uint8_t* img, i
     const size_t W = c->d.geom.W, H = c->d.geom.H;
     if (!c->h_upload) HIPCHK(hipHostMalloc((void**)&c->h_upload, W * H * 6));
     uint8_t* h = c->h_upload + W * H * (size_t)(slot * 2 + cam);
-    if ((size_t)stride == W) memcpy(h, img, W * H);
-    else for (size_t y = 0; y < H; y++) memcpy(h + y * W, img + y * (size_t)stride, W);
+    pack_rows(h, img, W, H, (size_t)stride);
     const LevelInfo& L0 = c->d.geom.lv[0];
     uint8_t* dst = c->d.pyr + pyr_index(c->d, 0, slot, cam) + L0.off;
     HIPCHK(hipMemcpy2DAsync(dst, (size_t)L0.stride, h, W, W, H, hipMemcpyHostToDevice, c->stream));   // from pinned memory: one strided DMA
@@ -1015,11 +1032,10 @@ extern "C" int svo_fast_score_map(int device, const uint8_t* img, int w, int h, 
     if (!img || !score || w < 7 || h < 7 || stride < w) return fail_arg("bad image arguments");
     int rc = use_device(device); if (rc != SVO_OK) return rc;
     DevTmp t; uint8_t *dimg, *dsc;
-    HIPCHK(t.get(&dimg, (size_t)w * h)); HIPCHK(t.get(&dsc, (size_t)w * h));
-    HIPCHK(hipMemcpy2D(dimg, w, img, stride, w, h, hipMemcpyHostToDevice));
+    HIPCHK(t.put_rows(&dimg, img, w, h, stride)); HIPCHK(t.get(&dsc, (size_t)w * h));
     launch_fast_score_map(dimg, w, h, threshold, dsc, 0);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(score, dsc, (size_t)w * h, hipMemcpyDeviceToHost));
+    HIPCHK(t.download(score, dsc, (size_t)w * h));
     return SVO_OK;
 }
 
@@ -1028,17 +1044,16 @@ extern "C" int svo_fast_detect(int device, const uint8_t* img, int w, int h, int
     if (!img || !n_out || w < 7 || h < 7 || stride < w || cap < 0) return fail_arg("bad arguments");
     int rc = use_device(device); if (rc != SVO_OK) return rc;
     DevTmp t; uint8_t *dimg, *dsc; int *rows, *dn; float2* dxy; float* dresp;
-    HIPCHK(t.get(&dimg, (size_t)w * h)); HIPCHK(t.get(&dsc, (size_t)w * h)); HIPCHK(t.get(&rows, (size_t)h));
+    HIPCHK(t.put_rows(&dimg, img, w, h, stride)); HIPCHK(t.get(&dsc, (size_t)w * h)); HIPCHK(t.get(&rows, (size_t)h));
     HIPCHK(t.get(&dn, 1)); HIPCHK(t.get(&dxy, (size_t)cap)); HIPCHK(t.get(&dresp, (size_t)cap));
-    HIPCHK(hipMemcpy2D(dimg, w, img, stride, w, h, hipMemcpyHostToDevice));
     launch_fast_score_map(dimg, w, h, threshold, dsc, 0);
     launch_score_compact(dsc, w, h, cap, rows, dxy, dresp, dn, 0);
     HIPCHK(hipGetLastError());
     int n = 0;
-    HIPCHK(hipMemcpy(&n, dn, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(t.download(&n, dn, 1));
     int m = n < cap ? n : cap;
-    if (m > 0 && xy) HIPCHK(hipMemcpy(xy, dxy, sizeof(float2) * m, hipMemcpyDeviceToHost));
-    if (m > 0 && resp) HIPCHK(hipMemcpy(resp, dresp, sizeof(float) * m, hipMemcpyDeviceToHost));
+    if (m > 0 && xy) HIPCHK(t.download(xy, dxy, m));
+    if (m > 0 && resp) HIPCHK(t.download(resp, dresp, m));
     *n_out = n;
     return SVO_OK;
 }
@@ -1053,21 +1068,14 @@ extern "C" int svo_bucket_filter(int device, int img_w, int img_h, int* n_io, fl
     const int nb = bah * baw;
     DevTmp t; float2 *dxy, *sxy, *oxy; int *dag, *dst_, *sag, *sst, *sn, *oag, *ost, *dn;
     const size_t outcap = (size_t)n;
-    HIPCHK(t.get(&dxy, (size_t)n)); HIPCHK(t.get(&dag, (size_t)n)); HIPCHK(t.get(&dst_, (size_t)n));
+    HIPCHK(t.put(&dxy, xy, n)); HIPCHK(t.put(&dag, ages, n)); HIPCHK(t.put(&dst_, strengths, n));
     HIPCHK(t.get(&sxy, (size_t)nb * per_bucket)); HIPCHK(t.get(&sag, (size_t)nb * per_bucket)); HIPCHK(t.get(&sst, (size_t)nb * per_bucket));
     HIPCHK(t.get(&sn, (size_t)nb)); HIPCHK(t.get(&oxy, outcap)); HIPCHK(t.get(&oag, outcap)); HIPCHK(t.get(&ost, outcap)); HIPCHK(t.get(&dn, 1));
-    HIPCHK(hipMemcpy(dxy, xy, sizeof(float2) * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dag, ages, sizeof(int) * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dst_, strengths, sizeof(int) * n, hipMemcpyHostToDevice));
     launch_bucket_general(img_w, img_h, n, dxy, dag, dst_, bah, baw, start_row, per_bucket, age_thr, fast_thr, sxy, sag, sst, sn, oxy, oag, ost, dn, 0);
     HIPCHK(hipGetLastError());
     int m = 0;
-    HIPCHK(hipMemcpy(&m, dn, sizeof(int), hipMemcpyDeviceToHost));
-    if (m > 0) {
-        HIPCHK(hipMemcpy(xy, oxy, sizeof(float2) * m, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ages, oag, sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(strengths, ost, sizeof(int) * m, hipMemcpyDeviceToHost));
-    }
+    HIPCHK(t.download(&m, dn, 1));
+    if (m > 0) { HIPCHK(t.download(xy, oxy, m)); HIPCHK(t.download(ages, oag, m)); HIPCHK(t.download(strengths, ost, m)); }
     *n_io = m;
     return SVO_OK;
 }
@@ -1174,16 +1182,7 @@ extern "C" int svo_circular_match(int device, const svo_config* cfg_in, const ui
     hs.frame_id = 1; hs.active = 1; hs.slot_img_t0 = 0; hs.slot_pyr_t0 = 0; hs.n_feat = n; hs.feat_buf = 0;
     if ((rc = build_pyramid_in_slot(c, hs, 1)) != SVO_OK) return rc;             // leaves slot_t1 = 1
     HIPCHK(hipMemcpyAsync(c->d.feat_xy[0], pl0, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-    if (!launch_lk_chain(c->d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(pl1, c->d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(pr1, c->d.pr1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(pr0, c->d.pr0, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(pl0_circle, c->d.plc, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(ok, c->d.okmask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; i++) ok[i] &= 1;                                       // bit0 = status0..3 && loop closure (vo.cpp:227-230)
-    return SVO_OK;
+    return circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok);
 }
 
 extern "C" int svo_find_close_points(int device, int n, const float* p1, const float* p2, float threshold, uint8_t* ok) {
@@ -1191,12 +1190,10 @@ extern "C" int svo_find_close_points(int device, int n, const float* p1, const f
     int rc = use_device(device); if (rc != SVO_OK) return rc;
     if (n == 0) return SVO_OK;
     DevTmp t; float2 *a, *b; uint8_t* o;
-    HIPCHK(t.get(&a, (size_t)n)); HIPCHK(t.get(&b, (size_t)n)); HIPCHK(t.get(&o, (size_t)n));
-    HIPCHK(hipMemcpy(a, p1, sizeof(float2) * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(b, p2, sizeof(float2) * n, hipMemcpyHostToDevice));
+    HIPCHK(t.put(&a, p1, n)); HIPCHK(t.put(&b, p2, n)); HIPCHK(t.get(&o, (size_t)n));
     launch_find_close(n, a, b, threshold, o, 0);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(ok, o, (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(t.download(ok, o, n));
     return SVO_OK;
 }
 
@@ -1260,7 +1257,7 @@ extern "C" int svo_inverse_transform(int device, const double R[9], const double
     HIPCHK(hipMemcpy(buf + 9, t, sizeof(double) * 3, hipMemcpyHostToDevice));
     launch_inverse_transform(buf, buf + 9, buf + 12, 0);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(T, buf + 12, sizeof(double) * 16, hipMemcpyDeviceToHost));
+    HIPCHK(tmp.download(T, buf + 12, 16));
     return SVO_OK;
 }
 
@@ -1394,12 +1391,9 @@ extern "C" int svo_rectify_image(int device, const int16_t* map1, const uint16_t
     int rc = use_device(device); if (rc != SVO_OK) return rc;
     const size_t n = (size_t)w * h, rowb = (size_t)raw_w * channels;
     DevTmp t; short2* dm1; uint16_t* dm2; uint8_t *draw, *dout;
-    HIPCHK(t.get(&dm1, n)); HIPCHK(t.get(&dm2, n)); HIPCHK(t.get(&draw, rowb * raw_h)); HIPCHK(t.get(&dout, n * channels));
-    HIPCHK(hipMemcpy(dm1, map1, n * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dm2, map2, n * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy2D(draw, rowb, raw, (size_t)raw_stride, rowb, (size_t)raw_h, hipMemcpyHostToDevice));
+    HIPCHK(t.put(&dm1, map1, n)); HIPCHK(t.put(&dm2, map2, n)); HIPCHK(t.put_rows(&draw, raw, rowb, raw_h, raw_stride)); HIPCHK(t.get(&dout, n * channels));
     launch_rectify_image(dm1, dm2, w, h, draw, raw_w, raw_h, (int)rowb, channels, dout, 0);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, dout, n * channels, hipMemcpyDeviceToHost));
+    HIPCHK(t.download(out, dout, n * channels));
     return SVO_OK;
 }

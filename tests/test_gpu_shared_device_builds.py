@@ -21,7 +21,7 @@ ROOT = os.path.dirname(HERE)
 POSE_TOL_T = 1e-6                       # as test_gpu_parity.py
 POSE_TOL_R = 1e-6
 W, H, B = 480, 200, 10                  # B > 8: a many-sequence context
-LEAN_ROOM = 96                          # lk_gated() in svo_api.hip
+LEAN_ROOM = 96                          # device_sharing() in svo_api.hip
 
 # (window, channels, lk_float_sums): the builds whose LK leaves >= 96 registers by the compiler's counts
 # (profiles/r04_lk_vgprs.md), plus the metric's window, which must not
