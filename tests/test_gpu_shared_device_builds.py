@@ -356,8 +356,10 @@ def test_ragged_frames_under_lean_builds(api, lean_builds):
 FORCED_SELECTION = [
     ("tests/test_gpu_parity.py", "camera_to_world or five_tracks or failure_paths or outlier_scene or cfg3 or fuzz"),
     ("tests/test_gpu_sequence_lifecycle.py", "idle_invariance or idle_rows or reset or all_idle or null_mask or masked_other"),
+    # the stage entry on degenerate disparities through k_triangulate_lean; the tests themselves assert SVO_PATH_LEAN of every call
+    ("tests/test_gpu_triangulate_edges.py", "test_stage"),
 ]
-FORCED_MIN_PASSES = [30, 10]
+FORCED_MIN_PASSES = [30, 10, 8]
 
 
 def forced_env():
@@ -367,7 +369,7 @@ def forced_env():
     return env
 
 
-@pytest.mark.parametrize("which", [0, 1], ids=["parity", "lifecycle"])
+@pytest.mark.parametrize("which", [0, 1, 2], ids=["parity", "lifecycle", "triangulate"])
 def test_forced_lean_parity_selection(which):
     path, expr = FORCED_SELECTION[which]
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", path, "-k", expr],
