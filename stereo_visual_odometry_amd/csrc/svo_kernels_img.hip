@@ -574,7 +574,8 @@ static __device__ __forceinline__ void offer_tracks(const DevBuffers& d, int seq
         float2 p = xy[i];
         int a = age[i], st = str[i];
         int bh = (int)(p.y / (float)d.bucket_h), bw = (int)(p.x / (float)d.bucket_w);   // feature_set.cpp:122-123
-        if (p.x < 0.f || p.y < 0.f || bh < d.cfg.bucket_start_row || bh >= d.cfg.buckets_along_height || bw >= d.cfg.buckets_along_width) continue;
+        // the index decides, as in the general walk: a coordinate in (-bucket, 0) truncates to 0 and is kept (no float sign test)
+        if (bh < 0 || bw < 0 || bh < d.cfg.bucket_start_row || bh >= d.cfg.buckets_along_height || bw >= d.cfg.buckets_along_width) continue;
         if (a >= d.cfg.age_threshold) continue;                                           // feature_set.cpp:26
         int score = a + (st - d.cfg.fast_threshold) / 20;
         bucket_offer(d, seq, bh, bw, make_bucket_key(score, (unsigned)i, st));
