@@ -162,6 +162,7 @@ int svo_get_lk_registers_left(svo_context* ctx);
 #define SVO_PATH_FRONT_FUSED     8   /* the fused lone-stream front (ingest + pyramid beside detection) */
 #define SVO_PATH_TRI_EPNP_FUSED 16   /* triangulation and the first EPnP chunk in one launch (lone stream) */
 #define SVO_PATH_GRAPH          32   /* the frame replayed a captured hipGraph (SVO_GRAPH=1); the other bits are the capture's */
+#define SVO_PATH_INPUT_CONVERTED 64  /* the frame's ingest converted the caller's pixels to grey (svo_set_input_format) */
 int svo_get_last_frame_path(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
@@ -233,6 +234,53 @@ int svo_set_rectification(svo_context* ctx, int seq, const svo_camera_info* left
 /* Back to a plain context (frames at the rectified size, no remap) from the next frame submitted; results are then bit-identical
  * to a context that never had maps.  The raw size may be set afresh afterwards. */
 int svo_clear_rectification(svo_context* ctx);
+
+/* ------------------------------------------------------------------------------------------------
+ * Input formats — replaces cv_bridge::toCvCopy(img, MONO8) in the reference's ROS node (src/stereo_vo.cpp:6-14), i.e. the
+ * cv::cvtColor(.., ..2GRAY) a colour or YUV camera costs per frame and per camera on the CPU.  A channels == 1 context has an
+ * input format: it describes the BYTES OF THE FRAMES THE CALLER PASSES; the context's own pixel format stays mono8, and the
+ * conversion happens inside frame ingest, while the source tile is staged — no extra pass over memory, nothing downstream
+ * changes.  (channels = 3 is something else: the CLI's BGR quirk, which keeps three planes.)
+ *
+ *   constant                             value   bytes per pixel   grey value of pixel x of a row
+ *   SVO_INPUT_MONO8 (default)            0       1                 the byte
+ *   SVO_INPUT_BGR8 / SVO_INPUT_RGB8      1 / 2   3                 the formula below
+ *   SVO_INPUT_BGRA8 / SVO_INPUT_RGBA8    3 / 4   4                 the formula below, alpha ignored
+ *   SVO_INPUT_UYVY                       5       2                 byte 2x + 1 of the row (COLOR_YUV2GRAY_UYVY: Y extracted)
+ *   SVO_INPUT_YUY2                       6       2                 byte 2x of the row
+ *
+ *   grey = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14
+ * — cv::cvtColor BGR2GRAY for 8-bit images as SURVEY.md Appendix A.7, tools/svo_cli.cpp --gray 1 and
+ * tests/golden/make_run1_fixture.py restate it.
+ * PARITY UNPINNED: equality with cv::cvtColor is believed, not measured (no OpenCV on the machines this was built on).  Newer
+ * OpenCV releases may use 15-bit weights (3735, 19235, 9798, >> 15); on the committed run1 frames the two formulas differ at
+ * 2e-5 of the pixels, by one grey level.  Which one a given cv_bridge build runs has not been verified.  The tests pin the kernels
+ * to a numpy restatement of the table above, bit for bit.
+ *
+ * With rectification the conversion comes first, as image_proc does it (image_mono -> image_rect): each of the four raw taps is
+ * converted to grey, a tap outside the raw image is 0, and the bilinear formula of the rectification section runs on the grey
+ * taps — remap(grey(raw), map1, map2).
+ *
+ * Every frame entry point (svo_process, svo_process_batch[_masked], svo_submit_batch[_masked], svo_circular_matching) then takes
+ * frames of in_width x in_height pixels (the raw size when rectifying) whose rows are `stride` bytes apart and hold
+ * in_width * bytes_per_pixel bytes; stride < in_width * bytes_per_pixel is SVO_ERR_ARG.  The kernels never read a byte outside
+ * [0, in_width * bytes_per_pixel) of a row: the caller's buffers need no slack.  Host images are staged, or read in place when
+ * pinned with packed rows, at in_width * bytes_per_pixel bytes per row.
+ * ---------------------------------------------------------------------------------------------- */
+#define SVO_INPUT_MONO8 0
+#define SVO_INPUT_BGR8  1
+#define SVO_INPUT_RGB8  2
+#define SVO_INPUT_BGRA8 3
+#define SVO_INPUT_RGBA8 4
+#define SVO_INPUT_UYVY  5
+#define SVO_INPUT_YUY2  6
+/* Set the format of the frames submitted from now on.  A channels == 3 context or an unknown format: SVO_ERR_ARG.  Stream-ordered
+ * like svo_clear_rectification: legal with frames in flight, takes effect from the next frame submitted — the kernels are chosen
+ * on the host when a frame is issued, so every frame carries its own format.  SVO_INPUT_MONO8 returns the context to launching
+ * exactly the kernels of a context that never called this.  svo_get_last_frame_path reports SVO_PATH_INPUT_CONVERTED for a frame
+ * whose ingest converted.  Under SVO_GRAPH=1 a converting frame replays a graph captured for its format (the format is part of
+ * what a slot's graph is keyed on, so a format switch re-captures); results are identical to the launch list's. */
+int svo_set_input_format(svo_context* ctx, int format);
 
 /* Introspection (parity tests): currentVOFeatures (vo.h:245) of one sequence, and the last frame's
  * compacted tracks.  Arrays may be NULL.  Returns the count or a negative status.  inlier[] is the is_ok vector of vo.cpp:115-119:
@@ -354,6 +402,11 @@ int svo_init_rectify_map(const double K[9], const double* D, int n_d, const doub
  * bytes apart; channels 1 or 3 (interleaved). */
 int svo_rectify_image(int device, const int16_t* map1, const uint16_t* map2, int w, int h, const uint8_t* raw, int raw_w, int raw_h,
                       int raw_stride, int channels, uint8_t* out);
+
+/* replaces: cv::cvtColor(src, out, COLOR_*2GRAY) / cv_bridge's MONO8 conversion: the grey conversion of the input-format section
+ * alone, on the kernels' device functions.  src: h rows of w pixels in `format` (SVO_INPUT_*), `stride` bytes apart; out: w*h
+ * bytes, packed. */
+int svo_convert_gray(int device, int format, const uint8_t* src, int w, int h, int stride, uint8_t* out);
 
 /* replaces: getInverseTransform(rotation, translation)  (vo.h:469-470, vo.cpp:246-258): [R t; 0 1]^-1, 4x4 row-major.
  * Runs the device function the frame pipeline ends with (one tiny launch). */

@@ -26,8 +26,10 @@ namespace visual_odometry {
 struct StampedImage {
     double stamp = 0;                 // seconds
     int rows = 0, cols = 0;
-    std::vector<uint8_t> mono8;       // owned copy (cv_bridge::toCvCopy semantics, stereo_vo.cpp:6-14)
-    Image view() const { return Image(mono8.data(), rows, cols); }
+    std::vector<uint8_t> mono8;       // owned copy (cv_bridge::toCvCopy semantics, stereo_vo.cpp:6-14) — or, with bytes_per_pixel > 1, the
+                                      // message's own bytes: the VisualOdometry converts them (set_input_encoding), nothing here does
+    int bytes_per_pixel = 1;          // of `mono8`: 1, or the encoding's (bgr8 3, bgra8 4, yuv422 2 ...)
+    Image view() const { return Image(mono8.data(), rows, cols, 0, bytes_per_pixel); }
 };
 
 class StereoSynchronizer {

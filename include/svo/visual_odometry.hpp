@@ -45,7 +45,8 @@ using Mat44 = std::array<double, 16>;     // 4x4 row-major
 struct Image {                                                        // the part of cv::Mat the path uses: 8-bit, 1 or 3 channels
     const uint8_t* data = nullptr;
     int rows = 0, cols = 0, step = 0;                                 // step in bytes
-    int channels = 1;                                                 // 3 = interleaved BGR, as cv::imread returns it (main.cpp:38-39)
+    int channels = 1;                                                 // 3 = interleaved BGR, as cv::imread returns it (main.cpp:38-39);
+                                                                      // with VisualOdometry::set_input_encoding: the encoding's bytes per pixel
     Image() {}
     Image(const uint8_t* d, int r, int c, int s = 0, int cn = 1) : data(d), rows(r), cols(c), step(s ? s : c * cn), channels(cn) {}
     bool empty() const { return !data || rows <= 0 || cols <= 0; }
@@ -181,7 +182,7 @@ class VisualOdometry {                                               // include/
         if (image_left.empty() || image_right.empty()) throw std::runtime_error("stereo_callback: empty image");
         if (image_left.channels != image_right.channels) throw std::runtime_error("stereo_callback: channel mismatch");
         if (!ctx_) {                                                  // the reference learns size and type from the first frame
-            cfg_.channels = image_left.channels;
+            cfg_.channels = in_format_ != SVO_INPUT_MONO8 ? 1 : image_left.channels;   // an encoding's frames become mono8 inside ingest
             svo_throw(svo_create(&cfg_, default_device(), 1, image_left.cols, image_left.rows, &ctx_));
             width_ = image_left.cols; height_ = image_left.rows;
             // like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
@@ -189,6 +190,7 @@ class VisualOdometry {                                               // include/
             if (!have_p_) { leftCameraProjection_.fill(0.f); rightCameraProjection_.fill(0.f); }
             svo_throw(svo_set_projection(ctx_, -1, leftCameraProjection_.data(), rightCameraProjection_.data()));
             if (rect_) apply_rectification();
+            if (in_format_ != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx_, in_format_));
         }
         check_frame(image_left, "left"); check_frame(image_right, "right");
         Mat44 T;
@@ -265,6 +267,21 @@ class VisualOdometry {                                               // include/
         if (ctx_) svo_throw(svo_clear_rectification(ctx_));
     }
 
+    // The sensor_msgs encoding of the frames passed from now on (svo_set_input_format; replaces cv_bridge::toCvCopy(img, MONO8),
+    // stereo_vo.cpp:6-14): "mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422" (UYVY), "yuv422_yuy2".  The conversion to grey runs
+    // on the GPU inside frame ingest (before rectification); Image::channels is then the encoding's bytes per pixel.  Single-channel
+    // objects only; an unknown name throws.  Takes effect from the next frame.
+    void set_input_encoding(const char* encoding) {
+        static const struct { const char* name; int format; } table[] = {
+            {"mono8", SVO_INPUT_MONO8}, {"bgr8", SVO_INPUT_BGR8}, {"rgb8", SVO_INPUT_RGB8}, {"bgra8", SVO_INPUT_BGRA8},
+            {"rgba8", SVO_INPUT_RGBA8}, {"yuv422", SVO_INPUT_UYVY}, {"yuv422_yuy2", SVO_INPUT_YUY2}};
+        int format = -1;
+        for (const auto& e : table) if (encoding && !std::strcmp(encoding, e.name)) format = e.format;
+        if (format < 0) throw std::runtime_error(std::string("set_input_encoding: unknown encoding ") + (encoding ? encoding : "(null)"));
+        if (ctx_) svo_throw(svo_set_input_format(ctx_, format));
+        in_format_ = format;
+    }
+
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
 
@@ -277,7 +294,9 @@ class VisualOdometry {                                               // include/
     void check_frame(const Image& im, const char* which) const {
         if (im.empty()) throw std::runtime_error(std::string(which) + " image is empty");
         const int w = raw_w_ ? raw_w_ : width_, h = raw_w_ ? raw_h_ : height_;     // rectifying: frames are raw
-        if (im.cols != w || im.rows != h || im.channels != cfg_.channels || im.step < im.cols * im.channels)
+        static const int bytes_per_pixel[7] = {1, 3, 3, 4, 4, 2, 2};              // of SVO_INPUT_*
+        const int cn = in_format_ != SVO_INPUT_MONO8 ? bytes_per_pixel[in_format_] : cfg_.channels;
+        if (im.cols != w || im.rows != h || im.channels != cn || im.step < im.cols * im.channels)
             throw std::runtime_error(std::string(which) + " image does not match the size / channels the object takes (the raw size when rectifying)");
     }
     void apply_rectification() {
@@ -291,6 +310,7 @@ class VisualOdometry {                                               // include/
     bool rect_ = false;                                               // set_rectification was called (applied once the context exists)
     svo_camera_info rect_l_{}, rect_r_{};
     int raw_w_ = 0, raw_h_ = 0;                                       // raw frame size while rectifying, else 0
+    int in_format_ = SVO_INPUT_MONO8;                                 // set_input_encoding (applied once the context exists)
 };
 
 }   // namespace visual_odometry

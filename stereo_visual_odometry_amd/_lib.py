@@ -81,6 +81,16 @@ lib.svo_get_last_frame_path.restype = C.c_int
 lib.svo_get_last_frame_path.argtypes = [C.c_void_p]
 # svo_get_last_frame_path bits (svo.h SVO_PATH_*)
 PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
+PATH_INPUT_CONVERTED = 64
+# input formats (svo.h SVO_INPUT_*): what the bytes of the caller's frames are; the sensor_msgs encoding names map onto them
+INPUT_MONO8, INPUT_BGR8, INPUT_RGB8, INPUT_BGRA8, INPUT_RGBA8, INPUT_UYVY, INPUT_YUY2 = range(7)
+INPUT_ENCODINGS = {"mono8": INPUT_MONO8, "bgr8": INPUT_BGR8, "rgb8": INPUT_RGB8, "bgra8": INPUT_BGRA8, "rgba8": INPUT_RGBA8,
+                   "yuv422": INPUT_UYVY, "yuv422_yuy2": INPUT_YUY2}
+INPUT_BPP = (1, 3, 3, 4, 4, 2, 2)
+lib.svo_set_input_format.restype = C.c_int
+lib.svo_set_input_format.argtypes = [C.c_void_p, C.c_int]
+lib.svo_convert_gray.restype = C.c_int
+lib.svo_convert_gray.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
 # ragged / continuous batching (svo.h): active is a host array of n_seq bytes or NULL; Pl / Pr 12 floats each or both NULL
 lib.svo_process_batch_masked.restype = C.c_int
 lib.svo_process_batch_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -114,6 +124,7 @@ EXPORTS = [
     "svo_append_features_from_image", "svo_build_pyramid", "svo_lk_track", "svo_circular_match",
     "svo_find_close_points", "svo_stage_cache_clear", "svo_stage_cache_clear_all", "svo_triangulate", "svo_camera_to_world", "svo_inverse_transform",
     "svo_set_rectification_maps", "svo_set_rectification", "svo_clear_rectification", "svo_init_rectify_map", "svo_rectify_image",
+    "svo_set_input_format", "svo_convert_gray",
 ]
 
 
@@ -154,9 +165,26 @@ def u8img(img):
     return img
 
 
-def u8frame(img):
-    """A frame for the frame pipeline: (H, W) gray, or (H, W, 3) interleaved BGR as the reference CLI feeds it (svo.h: channels)."""
+def u8frame(img, bpp=None):
+    """A frame for the frame pipeline: (H, W) gray, or (H, W, 3) interleaved BGR as the reference CLI feeds it (svo.h: channels);
+    bpp (the bytes per pixel of a context's input format, svo.h SVO_INPUT_*): (H, W, bpp), or (H, W) when bpp is 1."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
-    if not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+    if bpp is not None and bpp > 1:
+        if not (img.ndim == 3 and img.shape[2] == bpp):
+            raise ValueError("8-bit (H, W, %d) image expected for the input format that is set" % bpp)
+    elif not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
         raise ValueError("8-bit (H, W) or (H, W, 3) image expected")
     return img
+
+
+def input_format(fmt):
+    """An SVO_INPUT_* constant or a sensor_msgs encoding name ("mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422" (UYVY),
+    "yuv422_yuy2") -> the constant."""
+    if isinstance(fmt, str):
+        if fmt not in INPUT_ENCODINGS:
+            raise ValueError("unknown image encoding %r (one of %s)" % (fmt, ", ".join(INPUT_ENCODINGS)))
+        return INPUT_ENCODINGS[fmt]
+    fmt = int(fmt)
+    if not 0 <= fmt < len(INPUT_BPP):
+        raise ValueError("unknown input format %d" % fmt)
+    return fmt

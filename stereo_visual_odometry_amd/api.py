@@ -211,6 +211,23 @@ def rectifyImage(raw, map1, map2, device=0):
     return out
 
 
+def convertGray(image, fmt, device=0):
+    """cv::cvtColor(image, ..2GRAY) / cv_bridge's MONO8 conversion on the GPU (svo_convert_gray): the grey conversion of frame
+    ingest alone.  image: (h, w, bpp) uint8 in the format `fmt` (an SVO_INPUT_* constant or a sensor_msgs encoding name; (h, w)
+    for mono8); rows may be strided (a view's strides[0] is passed on) -> (h, w) uint8."""
+    f = _lib.input_format(fmt)
+    bpp = _lib.INPUT_BPP[f]
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or not ((img.ndim == 3 and img.shape[2] == bpp) or (bpp == 1 and img.ndim == 2)):
+        raise ValueError("uint8 (h, w, %d) image expected for this format" % bpp)
+    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != bpp):
+        img = np.ascontiguousarray(img)
+    h, w = img.shape[:2]
+    out = np.zeros((h, w), np.uint8)
+    check(lib.svo_convert_gray(device, f, C.c_void_p(img.ctypes.data), w, h, img.strides[0], ptr(out)))
+    return out
+
+
 # ---------------------------------------------------------------------------- FeatureSet / Bucket
 class FeatureSet:
     """vo.h:132-188 — parallel arrays points / ages / strengths."""
@@ -315,10 +332,31 @@ class BatchVisualOdometry:
         check(lib.svo_create(C.byref(self.cfg), device, n_seq, width, height, C.byref(self._h)))
         self.stats = None
         self.raw_size = None                          # (raw_w, raw_h) while the context rectifies: frames are then raw
+        self.input_format = _lib.INPUT_MONO8          # svo_set_input_format: what the bytes of the caller's frames are
 
     def _in_shape(self):
         """(height, width) of the frames the caller passes: the raw size when rectifying."""
         return (self.raw_size[1], self.raw_size[0]) if self.raw_size else (self.height, self.width)
+
+    def _bpp(self):
+        """Bytes per pixel of the frames the caller passes: the channels of a BGR context, else the input format's."""
+        return 3 if self.cfg.channels == 3 else _lib.INPUT_BPP[self.input_format]
+
+    def _frame_shape(self):
+        bpp = self._bpp()
+        return self._in_shape() + ((bpp,) if bpp > 1 else ())
+
+    def _frame(self, img):
+        return u8frame(img, None if self.cfg.channels == 3 else self._bpp())
+
+    def set_input_format(self, fmt):
+        """The format of the frames passed from now on (svo_set_input_format): an SVO_INPUT_* constant (_lib.INPUT_*) or a
+        sensor_msgs encoding name — "mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422" (UYVY), "yuv422_yuy2".  Frames are then
+        (H, W, bytes per pixel) arrays; the conversion to grey happens inside frame ingest, before rectification.  Single-channel
+        contexts only.  Stream-ordered: legal with frames in flight, from the next frame submitted."""
+        f = _lib.input_format(fmt)
+        check(lib.svo_set_input_format(self._h, f))
+        self.input_format = f
 
     def set_rectification(self, left_info, right_info, seq=-1):
         """Rectify raw frames with these calibrations (svo_set_rectification): `seq` (-1: the shared maps of every sequence
@@ -376,10 +414,10 @@ class BatchVisualOdometry:
         alone and its row is its last good T with ok False and stats.fail_reason 5 (svo_process_batch_masked)."""
         act = self._active(active)
         on = [True] * self.n_seq if act is None else [bool(x) for x in act]
-        L = [u8frame(i) if o else None for i, o in zip(lefts, on)]; R = [u8frame(i) if o else None for i, o in zip(rights, on)]
+        L = [self._frame(i) if o else None for i, o in zip(lefts, on)]; R = [self._frame(i) if o else None for i, o in zip(rights, on)]
         assert len(L) == self.n_seq and len(R) == self.n_seq
-        cn = max(1, self.cfg.channels)
-        assert all(i.shape == self._in_shape() + ((3,) if cn == 3 else ()) for i in L + R if i is not None), "image shape / channels"
+        cn = self._bpp()
+        assert all(i.shape == self._frame_shape() for i in L + R if i is not None), "image shape / channels"
         lp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in L])
         rp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in R])
         T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
@@ -510,6 +548,8 @@ class VisualOdometry(BatchVisualOdometry):
         self._timing = None
         self._rect = None                             # rectification asked for before the context exists: applied at creation
         self.raw_size = None
+        if not self._created:
+            self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
 
     def set_stage_timing(self, on=True):
         self._timing = bool(on)
@@ -538,12 +578,21 @@ class VisualOdometry(BatchVisualOdometry):
         if self._created:
             super().clear_rectification()
 
+    def set_input_format(self, fmt):
+        if self._created:
+            return super().set_input_format(fmt)
+        self.input_format = _lib.input_format(fmt)
+
     def stereo_callback(self, image_left, image_right):
-        L, R = u8frame(image_left), u8frame(image_right)
+        fmt = self.input_format
+        bpp = _lib.INPUT_BPP[fmt] if fmt != _lib.INPUT_MONO8 else None
+        if self._created and self.cfg.channels == 3:
+            bpp = None
+        L, R = u8frame(image_left, bpp), u8frame(image_right, bpp)
         if not self._created:                         # the reference learns the image size (and type) from the first frame
             cfg, device = self._args
             cfg = _lib.copy_config(cfg) if cfg is not None else default_config()       # never write into the caller's struct
-            cfg.channels = 3 if L.ndim == 3 else 1    # colour Mats, as the reference CLI feeds them (main.cpp:38-46)
+            cfg.channels = 3 if L.ndim == 3 and bpp is None else 1    # colour Mats, as the reference CLI feeds them (main.cpp:38-46)
             w, h = L.shape[1], L.shape[0]
             if self._rect is not None and self._rect[0] == "maps":
                 h, w = np.asarray(self._rect[1][1]).shape
@@ -559,6 +608,8 @@ class VisualOdometry(BatchVisualOdometry):
             super().initalize_projection_matricies(*(self._P if self._P is not None else (np.zeros(12, np.float32), np.zeros(12, np.float32))))
             if self._timing is not None:
                 super().set_stage_timing(self._timing)
+            if fmt != _lib.INPUT_MONO8:
+                super().set_input_format(fmt)         # (BatchVisualOdometry.__init__ reset the attribute)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()
@@ -579,7 +630,7 @@ class VisualOdometry(BatchVisualOdometry):
 
     def _check_frame(self, img, which):
         """cv::Mat carries size and type and OpenCV asserts on a mismatch; a raw pointer does not: check before the C call."""
-        want = self._in_shape() + ((3,) if self.cfg.channels == 3 else ())
+        want = self._frame_shape()
         if img.shape != want:
             raise ValueError("%s image has shape %s, the context was created for %s" % (which, img.shape, want))
 
@@ -595,7 +646,7 @@ class VisualOdometry(BatchVisualOdometry):
             return p0, empty, empty, empty                                                  # vo.cpp:179-181
         if not self._created:
             raise RuntimeError("circularMatching: no cached pyramids (call stereo_callback first)")
-        l1, r1 = u8frame(imgLeftT1), u8frame(imgRightT1)
+        l1, r1 = self._frame(imgLeftT1), self._frame(imgRightT1)
         self._check_frame(l1, "left"); self._check_frame(r1, "right")
         n = len(p0)
         outs = [np.zeros((n, 2), np.float32) for _ in range(4)]

@@ -83,9 +83,9 @@ static void make_geometry(Geometry& g, int W, int H, int win, int max_level, int
 
 // One slot of the results ring: everything a frame in flight owns besides its rows of the [SVO_RING][2 B] tables (ring_row).
 enum StageEvent { EV_F0, EV_PYR, EV_LK0, EV_LK1, EV_TRI, EV_DONE, EV_COUNT };   // stage boundaries, in svo_get_stage_timing's order
-struct GraphKey {                                // what a slot's graph was captured with (image stride, LK grid, co-resident builds)
-    int stride, gn, co;
-    bool operator==(const GraphKey& o) const { return stride == o.stride && gn == o.gn && co == o.co; }
+struct GraphKey {                                // what a slot's graph was captured with (image stride, LK grid, co-resident builds, input format)
+    int stride, gn, co, fmt;
+    bool operator==(const GraphKey& o) const { return stride == o.stride && gn == o.gn && co == o.co && fmt == o.fmt; }
 };
 struct RingSlot {
     hipEvent_t ev[EV_COUNT] = {};                // EV_F0 and EV_DONE always recorded, the four between on request (stage_timing)
@@ -140,6 +140,10 @@ struct svo_context {
     std::vector<Retired> retired;                // freed when n_collected >= after
     long long n_enqueued = 0, n_collected = 0;
     size_t staging_bytes = 0;                    // size of `staging` / `h_staging` (host-image calls of a rectifying context stage raw frames)
+    // input format (svo_set_input_format): what the frames submitted from now on hold; in.bpp <= 1 is mono8.  Host state only: the
+    // kernels are chosen at issue time and take `in` as arguments, so every frame carries its own format.
+    int in_format = SVO_INPUT_MONO8;
+    GreyIn in = {};
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -352,6 +356,8 @@ static int stage_host_images(svo_context* c, const uint8_t* const* left, const u
 // the size of the frames the caller passes: the raw size when the context rectifies, else the context's own
 static int in_width(const svo_context* c) { return c->raw_w > 0 ? c->raw_w : c->d.geom.W; }
 static int in_height(const svo_context* c) { return c->raw_w > 0 ? c->raw_h : c->d.geom.H; }
+// bytes per pixel of those frames: the channels of a colour context, else the input format's
+static int in_bpp(const svo_context* c) { return c->d.CN == 3 ? 3 : c->in.bpp > 1 ? c->in.bpp : 1; }
 
 // The frame's view of the context's buffers: c->d plus the slot's rows of the active list and of the map table (every other launch
 // sees the context's own unmasked, plain DevBuffers).  n_act >= 0: a ragged frame — only the n_act sequences listed in the slot's
@@ -360,6 +366,7 @@ static DevBuffers frame_view(const svo_context* c, int slot, int n_act) {
     DevBuffers f = c->d;
     if (n_act >= 0) { f.act = ring_row(c, c->d_act, slot); f.n_act = n_act; }
     if (c->raw_w > 0) f.rmap = ring_row(c, c->d_maps, slot);         // the frame's own maps (fill_slot_rows filled the row)
+    f.in = c->in;                                                    // the format set when the frame is issued
     return f;
 }
 // the slot's row of h_act to the device, on the stream of the frame's first kernel (kernels never read host memory for it)
@@ -410,7 +417,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     }
     HIPCHK(choose_pnp_build(c->d, share.lean));
     const DevBuffers f = frame_view(c, slot, n_act);                   // after the build choice: co_resident travels in the view
-    int path = f.co_resident ? SVO_PATH_LEAN : 0;
+    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0);
     const uint8_t** dp = ring_row(c, f.img_ptrs, slot);                // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(f);
     bool detected = false;
@@ -457,7 +464,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
 // mask both arrays must be there; with one every ACTIVE sequence needs both image pointers — an idle one's are never read, and the
 // arrays may be NULL when no sequence is active.  pointers_last: svo_submit_batch_masked looks at a masked frame's pointers last.
 static int check_stride(const svo_context* c, int stride) {
-    return stride < in_width(c) * c->d.CN ? fail_arg("stride < width * channels (raw width when rectifying)") : SVO_OK;
+    return stride < in_width(c) * in_bpp(c) ? fail_arg("stride < width * channels (raw width when rectifying; bytes per pixel of the input format)") : SVO_OK;
 }
 static int check_frame_args(const svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride, const uint8_t* active,
                             bool pointers_last = false) {
@@ -514,7 +521,7 @@ static int replay_graph(svo_context* c, int slot, int stride, int gn, DeviceShar
     hipStream_t s = c->stream;
     RingSlot& r = c->ring[slot];
     HIPCHK(choose_pnp_build(c->d, share.lean));                        // before the capture: issue_frame then finds the lean EPnP prepared
-    const GraphKey now = {stride, gn, c->d.co_resident};
+    const GraphKey now = {stride, gn, c->d.co_resident, c->in_format};
     if (!r.gexec || !(r.key == now)) {
         if (r.gexec) { (void)hipGraphExecDestroy(r.gexec); r.gexec = nullptr; }
         hipGraph_t g = nullptr;
@@ -638,7 +645,7 @@ extern "C" int svo_process_batch_masked(svo_context* c, const uint8_t* const* le
         // the caller's buffers are only borrowed for the duration of the call: copy to the device first (SURVEY.md §8b "Ownership")
         std::vector<const uint8_t*> lp, rp;
         if ((rc = stage_host_images(c, left, right, stride, lp, rp, active)) != SVO_OK) return rc;
-        rc = enqueue_frame(c, lp.data(), rp.data(), in_width(c) * c->d.CN, active);
+        rc = enqueue_frame(c, lp.data(), rp.data(), in_width(c) * in_bpp(c), active);
     }
     if (rc != SVO_OK) return rc;
     return collect_frame(c, T_out, ok_out, stats);
@@ -686,7 +693,7 @@ static void pack_rows(uint8_t* dst, const uint8_t* src, size_t rowb, size_t rows
 static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
                              std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active) {
     const int B = c->d.B, W = in_width(c), H = in_height(c);
-    const size_t rowb = (size_t)W * c->d.CN, img = rowb * H;
+    const size_t rowb = (size_t)W * in_bpp(c), img = rowb * H;
     if (c->staging_bytes < img * 2 * B) {                             // no frame in flight reads the staging buffers (synchronous calls only)
         if (c->staging) { (void)hipFree(c->staging); c->staging = nullptr; }
         if (c->h_staging) { (void)hipHostFree(c->h_staging); c->h_staging = nullptr; }
@@ -781,7 +788,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
         if (!hm[0] || !hm[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
     }
     const DevBuffers f = frame_view(c, 0, -1);
-    launch_ingest_pyramid(f, ring_row(c, f.img_ptrs, 0), in_width(c) * f.CN, c->stream, PYR_T1);   // vo.cpp:200-201
+    launch_ingest_pyramid(f, ring_row(c, f.img_ptrs, 0), in_width(c) * in_bpp(c), c->stream, PYR_T1);   // vo.cpp:200-201
     if ((rc = circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok)) != SVO_OK) return rc;
     SeqState out = keep;
     out.slot_pyr_t0 = t1;                                                         // lastLeftPyramid = pyramidl1 (vo.cpp:231-232)
@@ -1395,5 +1402,52 @@ extern "C" int svo_rectify_image(int device, const int16_t* map1, const uint16_t
     launch_rectify_image(dm1, dm2, w, h, draw, raw_w, raw_h, (int)rowb, channels, dout, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(t.download(out, dout, n * channels));
+    return SVO_OK;
+}
+
+// ================================================================================================
+// Input formats (svo.h): the format table, the setter and the conversion stage entry point
+// ================================================================================================
+// grey = (B 1868 + G 9617 + R 4899 + 8192) >> 14: the one place the weights are written down.  The
+// kernels weigh bytes 0, 1, 2 of a pixel with w0, w1, w2, so the byte order of a format is the order of its weights.
+static bool grey_in_of(int format, GreyIn* g) {
+    const int WB = 1868, WG = 9617, WR = 4899, RND = 8192, SH = 14;
+    switch (format) {
+        case SVO_INPUT_MONO8: *g = GreyIn{1, 0, 0, 0, 0, 0, 0}; return true;
+        case SVO_INPUT_BGR8:  *g = GreyIn{3, WB, WG, WR, RND, SH, 0}; return true;
+        case SVO_INPUT_RGB8:  *g = GreyIn{3, WR, WG, WB, RND, SH, 0}; return true;
+        case SVO_INPUT_BGRA8: *g = GreyIn{4, WB, WG, WR, RND, SH, 0}; return true;
+        case SVO_INPUT_RGBA8: *g = GreyIn{4, WR, WG, WB, RND, SH, 0}; return true;
+        case SVO_INPUT_UYVY:  *g = GreyIn{2, 0, 0, 0, 0, 0, 1}; return true;
+        case SVO_INPUT_YUY2:  *g = GreyIn{2, 0, 0, 0, 0, 0, 0}; return true;
+    }
+    return false;
+}
+
+extern "C" int svo_set_input_format(svo_context* c, int format) {
+    if (!c) return fail_arg("null context");
+    if (c->d.CN != 1) return fail_arg("svo_set_input_format: a channels = 3 context takes interleaved BGR as it is (svo.h, channels)");
+    GreyIn g;
+    if (!grey_in_of(format, &g)) return fail_arg("svo_set_input_format: unknown format (SVO_INPUT_*)");
+    c->in_format = format; c->in = g;                                 // host state: the next frame issued launches this format's kernels
+    return SVO_OK;
+}
+
+extern "C" int svo_convert_gray(int device, int format, const uint8_t* src, int w, int h, int stride, uint8_t* out) {
+    GreyIn g;
+    if (!src || !out || w < 1 || h < 1) return fail_arg("bad arguments");
+    if (!grey_in_of(format, &g)) return fail_arg("svo_convert_gray: unknown format (SVO_INPUT_*)");
+    const size_t rowb = (size_t)w * g.bpp, n = (size_t)w * h;
+    if ((size_t)stride < rowb) return fail_arg("stride < w * bytes per pixel");
+    int rc = use_device(device); if (rc != SVO_OK) return rc;
+    if (g.bpp == 1) { pack_rows(out, src, rowb, (size_t)h, (size_t)stride); return SVO_OK; }
+    // packed rows on the device, at the caller's own misalignment: the kernel's unaligned loads see the addresses mod 4 it was given
+    const size_t mis = (size_t)((uintptr_t)src & 3);
+    DevTmp t; uint8_t *dsrc, *dout;
+    HIPCHK(t.get(&dsrc, rowb * h + 4)); HIPCHK(t.get(&dout, n));
+    HIPCHK(hipMemcpy2D(dsrc + mis, rowb, src, (size_t)stride, rowb, (size_t)h, hipMemcpyHostToDevice));
+    launch_convert_gray(g, dsrc + mis, w, h, (int)rowb, dout, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(t.download(out, dout, n));
     return SVO_OK;
 }

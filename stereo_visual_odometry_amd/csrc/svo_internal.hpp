@@ -56,6 +56,12 @@ struct SeqState {
 
 struct FrameResult { double T[16]; int ok; svo_frame_stats stats; };
 
+// Input format of a frame (svo.h, svo_set_input_format): how a channels == 1 context reads the caller's bytes.  bpp = bytes per
+// pixel; bpp <= 1 is mono8 — nothing converts and the plain kernels run.  bpp 3 / 4: grey = (byte0 w0 + byte1 w1 + byte2 w2 + rnd)
+// >> shift (byte 3 ignored); bpp 2: grey = byte yoff of the pixel's pair (the Y of YUV 4:2:2).  Scalar kernel arguments: the
+// weights live here, on the host's format table (svo_api.hip), and nowhere in the kernels.
+struct GreyIn { int bpp, w0, w1, w2, rnd, shift, yoff; };
+
 // All device buffers of a context (B sequences, capacity CAP features each).
 struct DevBuffers {
     int B, CAP, NB;                            // NB = buckets_along_height * buckets_along_width
@@ -105,6 +111,9 @@ struct DevBuffers {
     // (a map = [W*H] short2 integer positions, then [W*H] u16 fractions: OpenCV's CV_16SC2 + CV_16UC1 pair), set for the launches
     // of one frame only, like act.  nullptr: the caller's images are level 0 as they stand, and the plain kernels run.
     const uint8_t* const* rmap; int raw_w, raw_h;
+    // Converting contexts (svo_set_input_format): the format of the frame being ingested, set for the launches of one frame only,
+    // like rmap.  in.bpp <= 1: the caller's bytes are grey as they stand, and the plain kernels run.
+    GreyIn in;
 };
 
 // The sequence of the b-th sequence slot of a launch (a block coordinate or a thread index): every per-sequence kernel maps its
@@ -181,6 +190,9 @@ void launch_frame_end(const DevBuffers& d, int ring_slot, hipStream_t s);
 // svo_rectify_image: out (w x h x cn, packed) = the remap of raw through (map1, map2); all device pointers
 void launch_rectify_image(const short2* map1, const uint16_t* map2, int w, int h, const uint8_t* raw, int raw_w, int raw_h, int raw_stride,
                           int cn, uint8_t* out, hipStream_t s);
+
+// svo_convert_gray: out (w x h, packed) = the grey image of src in the format g; device pointers
+void launch_convert_gray(const GreyIn& g, const uint8_t* src, int w, int h, int stride, uint8_t* out, hipStream_t s);
 
 // stage helpers
 void launch_fast_score_map(const uint8_t* img_dev, int w, int h, int threshold, uint8_t* score_dev, hipStream_t s);

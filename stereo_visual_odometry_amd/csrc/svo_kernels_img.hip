@@ -4,6 +4,7 @@
 // Behaviour follows the reference call sites (cited per kernel); the arithmetic of the OpenCV
 // functions they call is restated independently, not translated.
 #include "svo_internal.hpp"
+#include <type_traits>
 
 // cv::borderInterpolate(i, n, BORDER_REFLECT_101) for any i: reflect about the first and the last pixel until i lies inside (the
 // rule repeats with period 2n - 2).  A level narrower or shorter than the border pad needs more than one fold: the LK border of
@@ -43,6 +44,89 @@ __device__ __forceinline__ const short2* rect_map1(const DevBuffers& d, int cam,
 }
 __device__ __forceinline__ const uint16_t* rect_map2(const DevBuffers& d, int cam, int seq) {
     return reinterpret_cast<const uint16_t*>(d.rmap[cam * d.B + seq] + (size_t)4 * d.geom.W * d.geom.H);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Input formats (svo.h, svo_set_input_format): the grey byte of a colour or YUV 4:2:2 pixel, what cv_bridge::toCvCopy(img, MONO8)
+// hands the reference (stereo_vo.cpp:6-14).  BPP = bytes per pixel: 3 / 4 weigh the first three bytes (the
+// order of the weights in g makes it BGR or RGB, the fourth byte is never used), 2 picks the Y byte.  g is uniform: scalar registers.
+// ------------------------------------------------------------------------------------------------
+struct __attribute__((packed, aligned(1))) UD { unsigned v; };          // a dword at any byte address
+struct __attribute__((packed, aligned(1))) UD2 { unsigned v[2]; };
+struct __attribute__((packed, aligned(1))) UD4 { unsigned v[4]; };
+typedef short grey_s2 __attribute__((ext_vector_type(2)));
+// one pixel at p (BPP bytes, all inside the caller's row)
+template <int BPP>
+__device__ __forceinline__ unsigned grey_px(const uint8_t* __restrict__ p, const GreyIn& g) {
+    if constexpr (BPP == 2) return p[g.yoff];
+    else return ((unsigned)p[0] * g.w0 + (unsigned)p[1] * g.w1 + (unsigned)p[2] * g.w2 + g.rnd) >> g.shift;
+}
+// (byte0, byte1) as a 16-bit pair (one v_perm_b32 by the caller) and byte2: v_dot2_i32_i16 against the packed weight pair, seeded
+// with the 24-bit multiply-add of the third channel and the rounding term.  Weights are < 2^15 and the sum < 2^31: exact.
+__device__ __forceinline__ unsigned grey_w3(unsigned pair, unsigned third, unsigned wpair, const GreyIn& g) {
+    const int seed = (int)(__umul24(third, (unsigned)g.w2) + (unsigned)g.rnd);
+    return (unsigned)__builtin_amdgcn_sdot2(__builtin_bit_cast(grey_s2, pair), __builtin_bit_cast(grey_s2, wpair), seed, false) >> g.shift;
+}
+// FOUR consecutive pixels at p (4 BPP bytes, all inside the caller's row) as one dword of grey bytes: unaligned dword loads only —
+// three dwords (BPP 3), one dwordx4 (BPP 4), one dwordx2 and one v_perm_b32 (BPP 2)
+template <int BPP>
+__device__ __forceinline__ unsigned grey4(const uint8_t* __restrict__ p, const GreyIn& g) {
+    if constexpr (BPP == 2) {
+        const UD2 q = *reinterpret_cast<const UD2*>(p);
+        return __builtin_amdgcn_perm(q.v[1], q.v[0], g.yoff ? 0x07050301u : 0x06040200u);
+    } else {
+        const unsigned wpair = (unsigned)g.w0 | ((unsigned)g.w1 << 16);
+        unsigned y0, y1, y2, y3;
+        if constexpr (BPP == 3) {
+            const unsigned a = reinterpret_cast<const UD*>(p)->v, b = reinterpret_cast<const UD*>(p + 4)->v, c = reinterpret_cast<const UD*>(p + 8)->v;
+            y0 = grey_w3(__builtin_amdgcn_perm(a, a, 0x0c010c00u), (a >> 16) & 255u, wpair, g);      // bytes 0 1 | 2
+            y1 = grey_w3(__builtin_amdgcn_perm(b, a, 0x0c040c03u), (b >> 8) & 255u, wpair, g);       // bytes 3 4 | 5
+            y2 = grey_w3(__builtin_amdgcn_perm(b, b, 0x0c030c02u), c & 255u, wpair, g);              // bytes 6 7 | 8
+            y3 = grey_w3(__builtin_amdgcn_perm(c, c, 0x0c020c01u), c >> 24, wpair, g);               // bytes 9 10 | 11
+        } else {
+            const UD4 q = *reinterpret_cast<const UD4*>(p);
+            y0 = grey_w3(__builtin_amdgcn_perm(q.v[0], q.v[0], 0x0c010c00u), (q.v[0] >> 16) & 255u, wpair, g);
+            y1 = grey_w3(__builtin_amdgcn_perm(q.v[1], q.v[1], 0x0c010c00u), (q.v[1] >> 16) & 255u, wpair, g);
+            y2 = grey_w3(__builtin_amdgcn_perm(q.v[2], q.v[2], 0x0c010c00u), (q.v[2] >> 16) & 255u, wpair, g);
+            y3 = grey_w3(__builtin_amdgcn_perm(q.v[3], q.v[3], 0x0c010c00u), (q.v[3] >> 16) & 255u, wpair, g);
+        }
+        return y0 | (y1 << 8) | (y2 << 16) | (y3 << 24);                 // every y is <= 255: the weights sum to 2^shift
+    }
+}
+// remap_px<1> of a raw frame in the format g: each of the four taps is converted to grey first (image_mono -> image_rect), a tap
+// outside the raw image is 0, then the bilinear formula above
+template <int BPP>
+__device__ __forceinline__ void remap_grey_px(const uint8_t* __restrict__ raw, int stride, int rw, int rh, short2 p, unsigned f, const GreyIn& g, uint8_t* out) {
+    const int x0 = p.x, y0 = p.y, fx = f & 31, fy = (f >> 5) & 31;
+    const int w00 = (32 - fx) * (32 - fy), w01 = fx * (32 - fy), w10 = (32 - fx) * fy, w11 = fx * fy;
+    const bool x0in = (unsigned)x0 < (unsigned)rw, x1in = (unsigned)(x0 + 1) < (unsigned)rw;
+    const bool y0in = (unsigned)y0 < (unsigned)rh, y1in = (unsigned)(y0 + 1) < (unsigned)rh;
+    const uint8_t* t = raw + (ptrdiff_t)y0 * stride + (ptrdiff_t)x0 * BPP;
+    const int p00 = (y0in && x0in) ? (int)grey_px<BPP>(t, g) : 0, p01 = (y0in && x1in) ? (int)grey_px<BPP>(t + BPP, g) : 0;
+    const int p10 = (y1in && x0in) ? (int)grey_px<BPP>(t + stride, g) : 0, p11 = (y1in && x1in) ? (int)grey_px<BPP>(t + stride + BPP, g) : 0;
+    *out = (uint8_t)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
+}
+// the kernel instantiation of a run-time bytes-per-pixel count (2, 3 or 4; the host checked it): f(std::integral_constant<int, BPP>)
+template <typename F>
+static void with_bpp(int bpp, F&& f) {
+    if (bpp == 2) f(std::integral_constant<int, 2>{}); else if (bpp == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 4>{});
+}
+
+// svo_convert_gray: a thread per four pixels of a row (grey4 where all four exist, grey_px for a row's last one to three)
+template <int BPP>
+__global__ __launch_bounds__(256) void k_convert_gray(GreyIn g, const uint8_t* __restrict__ src, int w, int h, int stride, uint8_t* __restrict__ out) {
+    const int qpr = (w + 3) >> 2, total = qpr * h;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int y = i / qpr, x = 4 * (i - y * qpr);
+        const uint8_t* p = src + (size_t)y * stride + (size_t)x * BPP;
+        uint8_t* o = out + (size_t)y * w + x;
+        if (x + 4 <= w) { UD u; u.v = grey4<BPP>(p, g); *reinterpret_cast<UD*>(o) = u; }
+        else for (int k = 0; x + k < w; k++) o[k] = (uint8_t)grey_px<BPP>(p + k * BPP, g);
+    }
+}
+void launch_convert_gray(const GreyIn& g, const uint8_t* src, int w, int h, int stride, uint8_t* out, hipStream_t st) {
+    int gx = (((w + 3) >> 2) * h + 255) / 256; if (gx > 4096) gx = 4096;
+    with_bpp(g.bpp, [&](auto b) { hipLaunchKernelGGL(k_convert_gray<decltype(b)::value>, dim3(gx), dim3(256), 0, st, g, src, w, h, stride, out); });
 }
 
 // svo_rectify_image: one thread per output pixel (all channels), packed output rows
@@ -165,7 +249,35 @@ static void launch_ingest_as(const DevBuffers& d, const uint8_t* const* ptrs, in
     int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
     hipLaunchKernelGGL((k_ingest<CN, RECT>), dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, ptrs, stride, target);
 }
+// k_ingest<1, RECT> of a converting context (d.in.bpp = BPP): a pixel is the grey value of the caller's pixel, or the remap of the
+// grey raw frame
+template <int BPP, bool RECT>
+__global__ __launch_bounds__(256) void k_ingest_grey(DevBuffers d, const uint8_t* const* srcs, int stride, PyrTarget target) {
+    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
+    const int W = d.geom.W, H = d.geom.H;
+    const int total = W * H;
+    const uint8_t* src = srcs[cam * d.B + seq];
+    const int slot = ingest_slot(d, seq, target, blockIdx.x == 0 && cam == 0 && threadIdx.x == 0);
+    uint8_t* p0 = d.pyr + pyr_index(d, seq, slot, cam) + d.geom.lv[0].off;
+    const int dstride = d.geom.lv[0].stride;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int y = i / W, x = i - y * W;
+        uint8_t px;
+        if constexpr (RECT) remap_grey_px<BPP>(src, stride, d.raw_w, d.raw_h, rect_map1(d, cam, seq)[i], rect_map2(d, cam, seq)[i], d.in, &px);
+        else px = (uint8_t)grey_px<BPP>(src + (size_t)y * stride + (size_t)x * BPP, d.in);
+        p0[(size_t)y * dstride + x] = px;
+    }
+}
 static void launch_ingest(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    if (d.CN == 1 && d.in.bpp > 1) {
+        int gx = (d.geom.W * d.geom.H + 255) / 256; if (gx > 2048) gx = 2048;
+        with_bpp(d.in.bpp, [&](auto b) {
+            constexpr int BPP = decltype(b)::value;
+            const auto k = d.rmap ? k_ingest_grey<BPP, true> : k_ingest_grey<BPP, false>;
+            hipLaunchKernelGGL(k, dim3(gx, 2, launch_seqs(d)), dim3(256), 0, st, d, ptrs, stride, target);
+        });
+        return;
+    }
     if (d.CN == 3) { if (d.rmap) launch_ingest_as<3, true>(d, ptrs, stride, target, st); else launch_ingest_as<3, false>(d, ptrs, stride, target, st); }
     else { if (d.rmap) launch_ingest_as<1, true>(d, ptrs, stride, target, st); else launch_ingest_as<1, false>(d, ptrs, stride, target, st); }
 }
@@ -177,7 +289,6 @@ static void launch_ingest(const DevBuffers& d, const uint8_t* const* ptrs, int s
 // passes.  The pieces below are shared by every pyrDown kernel; the LDS arrays are declared by the kernel bodies (k_front_a and
 // k_front_b run one of them beside a detection body in one launch) and passed in.
 // ------------------------------------------------------------------------------------------------
-struct __attribute__((packed, aligned(1))) UD { unsigned v; };          // a dword at any byte address
 __device__ __forceinline__ unsigned tap5(unsigned a, unsigned b, unsigned c, unsigned d, unsigned e) { return c * 6 + (b + d) * 4 + a + e; }
 __device__ __forceinline__ unsigned pd_round(unsigned v) { return (v + 128) >> 8; }   // v = a sum of 25 products: <= 256 * 255
 
@@ -197,6 +308,25 @@ __device__ __forceinline__ void pd_fill_tile(uint8_t (&tile)[SH][TS], const uint
         for (int i = threadIdx.x; i < SW * SH; i += 256) {
             const int ty = i / SW, tx = i - ty * SW;
             tile[ty][tx] = src[(size_t)reflect101(sy0 + ty, h) * stride + reflect101(sx0 + tx, w)];
+        }
+    }
+}
+// pd_fill_tile of a caller image in the format g (BPP bytes per pixel): the tile holds grey bytes.  Interior tiles: four pixels per
+// thread, one LDS dword out (grey4: every byte it loads belongs to pixels sx0 .. sx0 + TS - 1 < w of the row); any other tile:
+// the reflected pixel, converted.
+template <int SW, int BPP, int SH, int TS>
+__device__ __forceinline__ void grey_fill_tile(uint8_t (&tile)[SH][TS], const uint8_t* src, int stride, int w, int h, int sx0, int sy0, const GreyIn& g) {
+    static_assert(TS % 4 == 0 && TS > SW, "tile rows are whole dwords");
+    if (sx0 >= 0 && sy0 >= 0 && sx0 + TS <= w && sy0 + SH <= h) {
+        constexpr int DPR = TS / 4;
+        for (int i = threadIdx.x; i < DPR * SH; i += 256) {
+            const int ty = i / DPR, c = i - ty * DPR;
+            *reinterpret_cast<unsigned*>(&tile[ty][4 * c]) = grey4<BPP>(src + (size_t)(sy0 + ty) * stride + (size_t)(sx0 + 4 * c) * BPP, g);
+        }
+    } else {
+        for (int i = threadIdx.x; i < SW * SH; i += 256) {
+            const int ty = i / SW, tx = i - ty * SW;
+            tile[ty][tx] = (uint8_t)grey_px<BPP>(src + (size_t)reflect101(sy0 + ty, h) * stride + (size_t)reflect101(sx0 + tx, w) * BPP, g);
         }
     }
 }
@@ -262,7 +392,9 @@ __global__ __launch_bounds__(256) void k_pyrdown(DevBuffers d, int level, PyrTar
 // RECT (rectifying contexts, d.rmap set): the source tile is filled by remapping the raw frame — tile byte (tx, ty) = the rectified
 // pixel at (reflect101(sx0 + tx), reflect101(sy0 + ty)), the byte the plain form reads from a rectified caller image — and the
 // level-0 store and both pyrDown passes run unchanged on it.  The rectified level 0 never makes a round trip through memory.
-template <int TW, int TH, bool RECT>
+// BPP > 1 (converting contexts, d.in.bpp = BPP): only the tile fill differs — it converts the caller's pixels (the four raw taps of
+// a rectifying one) to grey on the way in; the tile holds grey bytes, and everything after the fill is the same code.
+template <int TW, int TH, bool RECT, int BPP = 1>
 static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, const uint8_t* const* srcs, int stride, PyrTarget target, int bx, int by, int bz) {
     const int seq = seq_of(d, bz >> 1), cam = bz & 1;
     const LevelInfo ls = d.geom.lv[0], ld = d.geom.lv[1];
@@ -279,9 +411,11 @@ static __device__ __forceinline__ void ingest_pyr1_body(const DevBuffers& d, con
         for (int i = threadIdx.x; i < SW * SH; i += 256) {
             const int ty = i / SW, tx = i - ty * SW;
             const int m = reflect101(sy0 + ty, ls.h) * ls.w + reflect101(sx0 + tx, ls.w);
-            remap_px<1>(src, stride, d.raw_w, d.raw_h, m1[m], m2[m], &tile[ty][tx]);
+            if constexpr (BPP == 1) remap_px<1>(src, stride, d.raw_w, d.raw_h, m1[m], m2[m], &tile[ty][tx]);
+            else remap_grey_px<BPP>(src, stride, d.raw_w, d.raw_h, m1[m], m2[m], d.in, &tile[ty][tx]);
         }
-    } else pd_fill_tile<SW>(tile, src, stride, ls.w, ls.h, sx0, sy0);
+    } else if constexpr (BPP == 1) pd_fill_tile<SW>(tile, src, stride, ls.w, ls.h, sx0, sy0);
+    else grey_fill_tile<SW, BPP>(tile, src, stride, ls.w, ls.h, sx0, sy0, d.in);
     __syncthreads();
     // the block's own 2 TW x 2 TH level-0 pixels: in range, so the tile holds the pixels themselves
     if (2 * ox + 2 * TW <= ls.w && 2 * oy + 2 * TH <= ls.h) {     // all inside the level: a dword at a time (tile bytes 4c + 2 .. 4c + 5: two aligned LDS dwords, shifted)
@@ -313,7 +447,26 @@ static void launch_ingest_pyr1_as(const DevBuffers& d, const uint8_t* const* ptr
     dim3 g((d.geom.lv[1].w + TW - 1) / TW, (d.geom.lv[1].h + TH - 1) / TH, launch_seqs(d) * 2);
     hipLaunchKernelGGL((k_ingest_pyr1<TW, TH, RECT>), g, dim3(256), 0, st, d, ptrs, stride, target);
 }
+// the converting forms: symbols of their own beside k_ingest_pyr1 (whose instantiations stay what they were), the same body
+template <int BPP, int TW, int TH, bool RECT>
+__global__ __launch_bounds__(256) void k_ingest_pyr1_grey(DevBuffers d, const uint8_t* const* srcs, int stride, PyrTarget target) {
+    ingest_pyr1_body<TW, TH, RECT, BPP>(d, srcs, stride, target, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+template <int BPP, int TW, int TH>
+static void launch_ingest_pyr1_grey_as(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    dim3 g((d.geom.lv[1].w + TW - 1) / TW, (d.geom.lv[1].h + TH - 1) / TH, launch_seqs(d) * 2);
+    const auto k = d.rmap ? k_ingest_pyr1_grey<BPP, TW, TH, true> : k_ingest_pyr1_grey<BPP, TW, TH, false>;
+    hipLaunchKernelGGL(k, g, dim3(256), 0, st, d, ptrs, stride, target);
+}
 static void launch_ingest_pyr1(const DevBuffers& d, const uint8_t* const* ptrs, int stride, PyrTarget target, hipStream_t st) {
+    if (d.in.bpp > 1) {
+        with_bpp(d.in.bpp, [&](auto b) {
+            constexpr int BPP = decltype(b)::value;
+            if (d.B > SVO_LONE_MAX_SEQ) launch_ingest_pyr1_grey_as<BPP, IG_TW, IG_TH>(d, ptrs, stride, target, st);
+            else launch_ingest_pyr1_grey_as<BPP, PD_TW, PD_TH>(d, ptrs, stride, target, st);
+        });
+        return;
+    }
     if (d.B > SVO_LONE_MAX_SEQ) { if (d.rmap) launch_ingest_pyr1_as<IG_TW, IG_TH, true>(d, ptrs, stride, target, st); else launch_ingest_pyr1_as<IG_TW, IG_TH, false>(d, ptrs, stride, target, st); }
     else { if (d.rmap) launch_ingest_pyr1_as<PD_TW, PD_TH, true>(d, ptrs, stride, target, st); else launch_ingest_pyr1_as<PD_TW, PD_TH, false>(d, ptrs, stride, target, st); }
 }
@@ -849,6 +1002,13 @@ __global__ __launch_bounds__(256) void k_front_a(DevBuffers d, const uint8_t* co
     const int j = i - n_a;
     fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
 }
+template <int BPP, bool RECT>
+__global__ __launch_bounds__(256) void k_front_a_grey(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
+    const int i = blockIdx.x;
+    if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH, RECT, BPP>(d, srcs, stride, PYR_BEGIN, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
+    const int j = i - n_a;
+    fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
+}
 __global__ __launch_bounds__(256) void k_front_b(DevBuffers d, int px, int py, int n_p, int n_rows) {
     const int i = blockIdx.x;
     if (i < n_p) { pyrdown2_body(d, 1, PYR_T1, i % px, (i / px) % py, i / (px * py)); return; }
@@ -863,8 +1023,16 @@ bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_de
     const int ns = launch_seqs(d);
     const int ax = (d.geom.lv[1].w + PD_TW - 1) / PD_TW, ay = (d.geom.lv[1].h + PD_TH - 1) / PD_TH, n_a = ax * ay * ns * 2;
     const int fx = (d.geom.W + FT_W - 1) / FT_W, fy = (d.geom.H + FT_H - 1) / FT_H, n_f = fx * fy * ns;
-    const auto front_a = d.rmap ? k_front_a<true> : k_front_a<false>;
-    hipLaunchKernelGGL(front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
+    if (d.in.bpp > 1) {
+        with_bpp(d.in.bpp, [&](auto b) {
+            constexpr int BPP = decltype(b)::value;
+            const auto front_a = d.rmap ? k_front_a_grey<BPP, true> : k_front_a_grey<BPP, false>;
+            hipLaunchKernelGGL(front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
+        });
+    } else {
+        const auto front_a = d.rmap ? k_front_a<true> : k_front_a<false>;
+        hipLaunchKernelGGL(front_a, dim3(n_a + n_f), dim3(256), 0, st, d, left_right_dev_ptrs, stride, ax, ay, n_a, fx, fy, d.cfg.fast_threshold);
+    }
     const int px = (d.geom.lv[3].w + P2_TW - 1) / P2_TW, py = (d.geom.lv[3].h + P2_TH - 1) / P2_TH, n_p = px * py * ns * 2;
     const int n_rows = d.cfg.buckets_along_height;
     hipLaunchKernelGGL(k_front_b, dim3(n_p + n_rows * ns), dim3(256), 0, st, d, px, py, n_p, n_rows);

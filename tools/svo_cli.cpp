@@ -1,7 +1,7 @@
 // svo_cli — counterpart of the reference's CLI harness `vo <N_FRAMES> <folder>` (reference src/main.cpp:21-47,
 // 315-407) on top of the C++ facade / C-ABI.  SURVEY.md §8 f-1.
 //
-//   svo_cli <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1]
+//   svo_cli <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1|2] [--identity-start 1]
 //                               [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml]
 //
 // Reads folder/left/frameNNNNNN.{pgm,png,jpg} (6 digits, as `run1`) or frameNNNN.{jpg,png,pgm} (4 digits, as the reference's
@@ -170,12 +170,12 @@ int main(int argc, char** argv) {
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
     std::string calib, out = folder + "/result.csv", rect_l, rect_r;
-    bool gray = false, identity_start = false, float_sums = false, ref_format = false;
+    bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false;
     for (int i = 3; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--rectify")) {
             if (i + 2 >= argc) { std::fprintf(stderr, "--rectify needs two camera_info files\n"); return 2; }
             rect_l = argv[i + 1]; rect_r = argv[i + 2]; i++;
-        } else if (!strcmp(argv[i], "--gray")) gray = std::atoi(argv[i + 1]) != 0;
+        } else if (!strcmp(argv[i], "--gray")) { gray = std::atoi(argv[i + 1]) == 1; gray_gpu = std::atoi(argv[i + 1]) == 2; }   // 1: grey on the host; 2: the decoded BGR bytes as bgr8, grey inside frame ingest
         else if (!strcmp(argv[i], "--identity-start")) identity_start = std::atoi(argv[i + 1]) != 0;
         else if (!strcmp(argv[i], "--float-sums")) float_sums = std::atoi(argv[i + 1]) != 0;
         else if (!strcmp(argv[i], "--ref-format")) ref_format = std::atoi(argv[i + 1]) != 0;
@@ -206,6 +206,7 @@ int main(int argc, char** argv) {
         VisualOdometry vo(cfg);
         vo.initalize_projection_matricies(Pl, Pr);
         if (!rect_l.empty()) vo.set_rectification(ci_l, ci_r);
+        if (gray_gpu) vo.set_input_encoding("bgr8");
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
         if (identity_start) { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(pose, I, sizeof(I)); }
