@@ -1078,7 +1078,8 @@ extern "C" int svo_bucket_filter(int device, int img_w, int img_h, int* n_io, fl
     HIPCHK(t.put(&dxy, xy, n)); HIPCHK(t.put(&dag, ages, n)); HIPCHK(t.put(&dst_, strengths, n));
     HIPCHK(t.get(&sxy, (size_t)nb * per_bucket)); HIPCHK(t.get(&sag, (size_t)nb * per_bucket)); HIPCHK(t.get(&sst, (size_t)nb * per_bucket));
     HIPCHK(t.get(&sn, (size_t)nb)); HIPCHK(t.get(&oxy, outcap)); HIPCHK(t.get(&oag, outcap)); HIPCHK(t.get(&ost, outcap)); HIPCHK(t.get(&dn, 1));
-    launch_bucket_general(img_w, img_h, n, dxy, dag, dst_, bah, baw, start_row, per_bucket, age_thr, fast_thr, sxy, sag, sst, sn, oxy, oag, ost, dn, 0);
+    const BucketGrid g = {(img_h + bah - 1) / bah, (img_w + baw - 1) / baw, bah, baw, start_row, age_thr, fast_thr};
+    launch_bucket_general(g, per_bucket, n, dxy, dag, dst_, sxy, sag, sst, sn, oxy, oag, ost, dn, 0);
     HIPCHK(hipGetLastError());
     int m = 0;
     HIPCHK(t.download(&m, dn, 1));

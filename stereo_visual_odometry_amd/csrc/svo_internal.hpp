@@ -129,7 +129,27 @@ __host__ __device__ inline size_t fastimg_index(const DevBuffers& d, int seq, in
     return (size_t)(seq * SVO_PYR_SLOTS + slot) * (size_t)d.geom.W * (size_t)d.geom.H;
 }
 
-// Hypotheses of the first RANSAC chunk (always solved).  16 when many sequences share the GPU; 32 for a lone stream: the GPU is
+// ---- the bucket grid of FeatureSet::filterByBucketLocationInternal: its rules, each written once.  The frame pipeline takes the
+// grid from its context (grid_of), the stage call svo_bucket_filter fills one on the host. ----
+struct BucketGrid { int bucket_h, bucket_w, bah, baw, start_row, age_thr, fast_thr; };   // bucket size in pixels: ceil(image / buckets), feature_set.cpp:91-93, 103-104
+__device__ __forceinline__ BucketGrid grid_of(const DevBuffers& d) {
+    return {d.bucket_h, d.bucket_w, d.cfg.buckets_along_height, d.cfg.buckets_along_width, d.cfg.bucket_start_row, d.cfg.age_threshold, d.cfg.fast_threshold};
+}
+// The bucket (bh, bw) of a point (feature_set.cpp:122-123: f32 division, truncated toward zero), and whether the grid takes it.
+// The INDEX decides: a coordinate in (-bucket, 0) truncates to 0 and is inside, rows before start_row have no capacity (:113-116).
+__device__ __forceinline__ bool bucket_of(const BucketGrid& g, float x, float y, int& bh, int& bw) {
+    bh = (int)(y / (float)g.bucket_h); bw = (int)(x / (float)g.bucket_w);
+    return bh >= 0 && bw >= 0 && bh >= g.start_row && bh < g.bah && bw < g.baw;
+}
+// what Bucket::add_feature compares (feature_set.cpp:16-18); the division truncates toward zero, as C's does
+__device__ __forceinline__ int bucket_score(int age, int strength, int fast_thr) { return age + (strength - fast_thr) / 20; }
+// capacity 1: (score, first come, strength) as one key for a 64-bit atomicMax; order = the candidate's rank in the input list
+__device__ __forceinline__ unsigned long long make_bucket_key(int score, unsigned order, int strength) {
+    int s = score + 32768; s = s < 1 ? 1 : (s > 65535 ? 65535 : s);
+    return ((unsigned long long)s << 48) | ((unsigned long long)(0xFFFFFFFFu - order) << 16) | (unsigned long long)(strength & 0xFFFF);
+}
+
+// Hypotheses of the first RANSAC chunk (always solved). 16 when many sequences share the GPU; 32 for a lone stream: the GPU is
 // empty then, a wider chunk costs no time, and the adaptive loop (11-27 iterations with 30 % outliers) rarely needs a second
 // EPnP launch — which would be another 145 us on the critical path.
 #define SVO_LONE_MAX_SEQ 8      // contexts of up to this many sequences are tuned for latency (wider first RANSAC chunk, 16 lanes per hypothesis ...)
@@ -197,8 +217,7 @@ void launch_convert_gray(const GreyIn& g, const uint8_t* src, int w, int h, int 
 // stage helpers
 void launch_fast_score_map(const uint8_t* img_dev, int w, int h, int threshold, uint8_t* score_dev, hipStream_t s);
 void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* row_counts_dev, float2* xy_dev, float* resp_dev, int* n_dev, hipStream_t s);
-void launch_bucket_general(int img_w, int img_h, int n, const float2* xy, const int* ages, const int* strs,
-                           int bah, int baw, int start_row, int per_bucket, int age_thr, int fast_thr,
+void launch_bucket_general(const BucketGrid& g, int per_bucket, int n, const float2* xy, const int* ages, const int* strs,
                            float2* slot_xy, int* slot_age, int* slot_str, int* slot_n,
                            float2* out_xy, int* out_age, int* out_str, int* n_out, hipStream_t s);
 void launch_lk_single(const DevBuffers& d, int slotA, int camA, int slotB, int camB, int n, const float2* prev, float2* next,

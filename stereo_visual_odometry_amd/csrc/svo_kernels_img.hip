@@ -703,13 +703,6 @@ __device__ __forceinline__ int fast_score(const uint8_t (*pix)[FT_PW + 4], int p
     return -b0 - 1;
 }
 
-struct BucketGrid { int bucket_h, bucket_w, bah, baw, start_row, age_thr, fast_thr; };
-
-__device__ __forceinline__ unsigned long long make_bucket_key(int score, unsigned order, int strength) {
-    int s = score + 32768; s = s < 1 ? 1 : (s > 65535 ? 65535 : s);
-    return ((unsigned long long)s << 48) | ((unsigned long long)(0xFFFFFFFFu - order) << 16) | (unsigned long long)(strength & 0xFFFF);
-}
-
 // Bucket::add_feature for capacity 1 as one 64-bit atomicMax; the first candidate of a bucket also counts it into its grid row,
 // which lets k_bucket_emit place a row's winners without scanning the rows before it.
 __device__ __forceinline__ void bucket_offer(const DevBuffers& d, int seq, int bh, int bw, unsigned long long key) {
@@ -717,55 +710,61 @@ __device__ __forceinline__ void bucket_offer(const DevBuffers& d, int seq, int b
     if (old == 0ull) atomicAdd(&d.bucket_rowcnt[(size_t)seq * d.cfg.buckets_along_height + bh], 1);
 }
 
-// the tracks the feature set already holds, offered to the grid (feature_set.cpp:20-53, 122-124) — the first pass's k_fast blocks
+// the tracks the feature set already holds, offered to the grid (feature_set.cpp:20-53, 122-124) — the first pass's FAST threads
 // share them out before they scan their tiles, the second pass's offer is made by the last block of the first pass's emit
 static __device__ __forceinline__ void offer_tracks(const DevBuffers& d, int seq, int fb, int n, int first, int step) {
+    const BucketGrid g = grid_of(d);
     const float2* xy = d.feat_xy[fb] + (size_t)seq * d.CAP;
     const int* age = d.feat_age[fb] + (size_t)seq * d.CAP;
     const int* str = d.feat_str[fb] + (size_t)seq * d.CAP;
     for (int i = first; i < n; i += step) {
-        float2 p = xy[i];
-        int a = age[i], st = str[i];
-        int bh = (int)(p.y / (float)d.bucket_h), bw = (int)(p.x / (float)d.bucket_w);   // feature_set.cpp:122-123
-        // the index decides, as in the general walk: a coordinate in (-bucket, 0) truncates to 0 and is kept (no float sign test)
-        if (bh < 0 || bw < 0 || bh < d.cfg.bucket_start_row || bh >= d.cfg.buckets_along_height || bw >= d.cfg.buckets_along_width) continue;
-        if (a >= d.cfg.age_threshold) continue;                                           // feature_set.cpp:26
-        int score = a + (st - d.cfg.fast_threshold) / 20;
-        bucket_offer(d, seq, bh, bw, make_bucket_key(score, (unsigned)i, st));
+        const float2 p = xy[i];
+        const int a = age[i], st = str[i];
+        int bh, bw;
+        if (!bucket_of(g, p.x, p.y, bh, bw) || a >= g.age_thr) continue;                  // feature_set.cpp:26
+        bucket_offer(d, seq, bh, bw, make_bucket_key(bucket_score(a, st, g.fast_thr), (unsigned)i, st));
     }
 }
-// MODE 0: frame pipeline, survivors go straight to the bucket keys (features_per_bucket == 1).  MODE 1: one image -> score map
-// (stage API).  MODE 2: frame pipeline -> per-sequence score map (features_per_bucket > 1: the general walk needs the keypoint list).
-template <int MODE>
-static __device__ __forceinline__ void fast_body(const uint8_t* img_single, int w_single, int h_single, uint8_t* score_out,
-                                                 const DevBuffers& d, int pass, int threshold, int bx, int by, int bz, int gdx, int gdy) {
-    constexpr bool TO_BUCKETS = MODE == 0;
+
+// Does detection pass `pass` run for this sequence?  Pass 1 runs where pass 0's emit asked for it.  Pass 0 runs on every frame
+// but a sequence's first, which the per-frame reset records in `active` — but the FAST kernels of pass 0 may share a launch with
+// the ingest block that performs that reset (k_front_a), so they (before_reset) read frame_id > 0, which the reset computes
+// `active` from and does not write; for the same reason they take n_feat, not n_old, as the size of the old set.
+static __device__ __forceinline__ bool detect_pass_runs(const SeqState& s, int pass, bool before_reset = false) {
+    return pass != 0 ? s.do_second : before_reset ? s.frame_id > 0 : s.active;
+}
+
+// ---- where a tile's NMS result goes: sink(gx, gy, score, keep) is called once for every pixel of the tile inside the image ----
+// the dense score map (stage API; frame pipeline at features_per_bucket > 1, where the general walk needs the keypoint list)
+struct ScoreMapSink {
+    uint8_t* score; int W;
+    __device__ __forceinline__ void operator()(int gx, int gy, int s, bool keep) const { score[(size_t)gy * W + gx] = keep ? (uint8_t)s : (uint8_t)0; }
+};
+// straight into the bucket keys (frame pipeline, features_per_bucket == 1): feature_set.cpp:83-87 (age 0, strength = response)
+struct BucketSink {
+    const DevBuffers& d; int seq, pass;
+    __device__ __forceinline__ void operator()(int gx, int gy, int s, bool keep) const {
+        const BucketGrid g = grid_of(d);
+        int bh, bw;
+        if (!keep || !bucket_of(g, (float)gx, (float)gy, bh, bw) || 0 >= g.age_thr) return;
+        const unsigned n_old = pass == 0 ? (unsigned)d.st[seq].n_feat : (unsigned)d.st[seq].n_old;   // pass 0: the set is still the old one
+        const unsigned order = n_old + (unsigned)(gy * d.geom.W + gx);                               // raster rank keeps cv::FAST's output order
+        bucket_offer(d, seq, bh, bw, make_bucket_key(bucket_score(0, s, g.fast_thr), order, s));
+    }
+};
+
+// The tile whose first pixel is (x0, y0) of the W x H image img (rows istride bytes apart): fill, screening, scores, NMS.
+template <class Sink>
+static __device__ __forceinline__ void fast_tile(const uint8_t* img, int istride, int W, int H, int x0, int y0, int threshold, const Sink& sink) {
     __shared__ __attribute__((aligned(4))) uint8_t pix[FT_PH][FT_PW + 4];
     __shared__ uint8_t sc[FT_SH][FT_SW + 2];
     __shared__ unsigned short cand[FT_SH * FT_SW];               // screened pixels of the tile (order is irrelevant)
     __shared__ int ncand;
-    const int seq = MODE == 1 ? 0 : seq_of(d, bz);
-    int W, H, istride; const uint8_t* img;                       // istride: row pitch of img (a pyramid level 0 carries its border)
-    if (MODE != 1) {
-        const SeqState& s = d.st[seq];
-        // Pass 0 reads nothing the per-frame reset writes (`active` is frame_id > 0, `n_old` is n_feat until the first emit), so
-        // that it may run in the SAME launch as the ingest blocks one of whose threads performs that reset (k_front_a).
-        if (pass == 0 ? !(s.frame_id > 0) : !s.do_second) return;
-        W = d.geom.W; H = d.geom.H;
-        // FAST runs on the PREVIOUS left image (vo.cpp:325); for a BGR context on the byte image cv::FAST really scans
-        img = d.CN == 3 ? d.fastimg + fastimg_index(d, seq, s.slot_img_t0) : d.pyr + pyr_index(d, seq, s.slot_img_t0, 0) + d.geom.lv[0].off;
-        istride = d.CN == 3 ? W : d.geom.lv[0].stride;
-        if (MODE == 2) score_out = d.score + (size_t)seq * W * H;
-        if (TO_BUCKETS && pass == 0)                                 // the existing tracks enter the grid here (no launch of their own)
-            offer_tracks(d, seq, s.feat_buf, s.n_feat, (by * gdx + bx) * 256 + threadIdx.x, gdx * gdy * 256);
-    } else { W = w_single; H = h_single; img = img_single; istride = w_single; }
     if (threshold < 0) threshold = 0;
     if (threshold > 255) threshold = 255;
-    const int x0 = bx * FT_W, y0 = by * FT_H;
     if (x0 >= 4 && y0 >= 4 && x0 - 4 + FT_PW <= W && y0 - 4 + FT_PH <= H) {
         // interior tile: 18 unaligned dword loads per row instead of 72 guarded byte loads
         static_assert(FT_PW % 4 == 0, "tile rows are whole dwords");
-        struct __attribute__((packed, aligned(1))) UD { unsigned v; };
         constexpr int DPR = FT_PW / 4;
         for (int i = threadIdx.x; i < DPR * FT_PH; i += 256) {
             int py = i / DPR, c = i - py * DPR;
@@ -813,26 +812,44 @@ static __device__ __forceinline__ void fast_body(const uint8_t* img_single, int 
                     s > sc[oy + 1][ox] && s > sc[oy + 1][ox + 2] &&
                     s > sc[oy][ox] && s > sc[oy][ox + 1] && s > sc[oy][ox + 2] &&
                     s > sc[oy + 2][ox] && s > sc[oy + 2][ox + 1] && s > sc[oy + 2][ox + 2];
-        if (TO_BUCKETS) {
-            if (keep) {
-                // feature_set.cpp:83-87 (age 0, strength = response) + :122-124 bucket index + Bucket::add_feature (:20-53)
-                int bh = (int)((float)gy / (float)d.bucket_h), bw = (int)((float)gx / (float)d.bucket_w);
-                if (bh >= d.cfg.bucket_start_row && bh < d.cfg.buckets_along_height && bw < d.cfg.buckets_along_width && 0 < d.cfg.age_threshold) {
-                    int score = 0 + (s - d.cfg.fast_threshold) / 20;                       // feature_set.cpp:16-18
-                    const unsigned n_old = pass == 0 ? (unsigned)d.st[seq].n_feat : (unsigned)d.st[seq].n_old;   // pass 0: the set is still the old one
-                    unsigned order = n_old + (unsigned)(gy * W + gx);                      // raster rank keeps cv::FAST's output order
-                    bucket_offer(d, seq, bh, bw, make_bucket_key(score, order, s));
-                }
-            }
-        } else {
-            score_out[(size_t)gy * W + gx] = keep ? (uint8_t)s : (uint8_t)0;
-        }
+        sink(gx, gy, s, keep);
     }
 }
+
+// The frame side of a FAST block: what it scans for sequence slot bz — FAST runs on the PREVIOUS left image (vo.cpp:325), for a
+// BGR context on the byte image cv::FAST really scans, else on level 0 of the pyramid, which carries its border (istride) —
+// or false if the pass does not run for the sequence.  Pass 0 of a capacity-1 context (`offer`): the existing tracks enter the
+// grid here (no launch of their own), this thread's share being first, first + step, ...
+struct FastFrame { int seq; const uint8_t* img; int istride; };
+static __device__ __forceinline__ bool fast_frame_begin(const DevBuffers& d, int pass, int bz, bool offer, int first, int step, FastFrame& f) {
+    f.seq = seq_of(d, bz);
+    const SeqState& s = d.st[f.seq];
+    if (!detect_pass_runs(s, pass, true)) return false;
+    f.img = d.CN == 3 ? d.fastimg + fastimg_index(d, f.seq, s.slot_img_t0) : d.pyr + pyr_index(d, f.seq, s.slot_img_t0, 0) + d.geom.lv[0].off;
+    f.istride = d.CN == 3 ? d.geom.W : d.geom.lv[0].stride;
+    if (offer && pass == 0) offer_tracks(d, f.seq, s.feat_buf, s.n_feat, first, step);
+    return true;
+}
+// tile (bx, by) of the fx x fy tiles of sequence slot bz, survivors to the bucket keys: a block of k_fast<0> or of k_front_a
+static __device__ __forceinline__ void fast_frame_block(const DevBuffers& d, int pass, int threshold, int bx, int by, int bz, int fx, int fy) {
+    FastFrame f;
+    if (!fast_frame_begin(d, pass, bz, true, (by * fx + bx) * 256 + threadIdx.x, fx * fy * 256, f)) return;
+    fast_tile(f.img, f.istride, d.geom.W, d.geom.H, bx * FT_W, by * FT_H, threshold, BucketSink{d, f.seq, pass});
+}
+// MODE 0: survivors go straight to the bucket keys (features_per_bucket == 1).  MODE 2: to the sequence's score map
+// (features_per_bucket > 1).  One block per tile and sequence slot.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_fast(const uint8_t* img_single, int w_single, int h_single, uint8_t* score_out,
-                                              DevBuffers d, int pass, int threshold) {
-    fast_body<MODE>(img_single, w_single, h_single, score_out, d, pass, threshold, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
+__global__ __launch_bounds__(256) void k_fast(DevBuffers d, int pass, int threshold) {
+    static_assert(MODE == 0 || MODE == 2, "the stage call's score map is k_fast_score_map");
+    if (MODE == 0) { fast_frame_block(d, pass, threshold, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y); return; }
+    FastFrame f;
+    if (!fast_frame_begin(d, pass, blockIdx.z, false, 0, 0, f)) return;
+    const int W = d.geom.W, H = d.geom.H;
+    fast_tile(f.img, f.istride, W, H, blockIdx.x * FT_W, blockIdx.y * FT_H, threshold, ScoreMapSink{d.score + (size_t)f.seq * W * H, W});
+}
+// one packed image -> score map (stage API)
+__global__ __launch_bounds__(256) void k_fast_score_map(const uint8_t* img, int w, int h, int threshold, uint8_t* score) {
+    fast_tile(img, w, w, h, blockIdx.x * FT_W, blockIdx.y * FT_H, threshold, ScoreMapSink{score, w});
 }
 
 // The SECOND detection pass of a many-sequence context: launched every frame, needed by a sequence that kept < 100 features (vo.cpp:327)
@@ -840,53 +857,64 @@ __global__ __launch_bounds__(256) void k_fast(const uint8_t* img_single, int w_s
 // critical chain just to look at do_second and leave; here a sequence gets FAST_STRIDED_BLOCKS blocks that walk its tiles.
 #define FAST_STRIDED_BLOCKS 32
 __global__ __launch_bounds__(256) void k_fast_strided(DevBuffers d, int pass, int threshold, int fx, int fy) {
-    const SeqState& s = d.st[seq_of(d, blockIdx.z)];
-    if (pass == 0 ? !(s.frame_id > 0) : !s.do_second) return;
+    FastFrame f;
+    if (!fast_frame_begin(d, pass, blockIdx.z, true, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, f)) return;
     for (int t = blockIdx.x; t < fx * fy; t += gridDim.x) {
-        fast_body<0>(nullptr, 0, 0, nullptr, d, pass, threshold, t % fx, t / fx, blockIdx.z, fx, fy);
+        fast_tile(f.img, f.istride, d.geom.W, d.geom.H, (t % fx) * FT_W, (t / fx) * FT_H, threshold, BucketSink{d, f.seq, pass});
         __syncthreads();                                              // the tile arrays in LDS are reused by the next tile
     }
 }
 
+static dim3 fast_grid(int w, int h, int n_seq) { return dim3((w + FT_W - 1) / FT_W, (h + FT_H - 1) / FT_H, n_seq); }
+static dim3 fast_grid(const DevBuffers& d) { return fast_grid(d.geom.W, d.geom.H, launch_seqs(d)); }
+
 void launch_fast_score_map(const uint8_t* img_dev, int w, int h, int threshold, uint8_t* score_dev, hipStream_t st) {
-    DevBuffers dummy = {};
-    dim3 g((w + FT_W - 1) / FT_W, (h + FT_H - 1) / FT_H, 1);
-    hipLaunchKernelGGL(k_fast<1>, g, dim3(256), 0, st, img_dev, w, h, score_dev, dummy, 0, threshold);
+    hipLaunchKernelGGL(k_fast_score_map, fast_grid(w, h, 1), dim3(256), 0, st, img_dev, w, h, threshold, score_dev);
 }
 
-// raster-ordered compaction of a score map into keypoints (cv::FAST output order + KeyPoint::convert, feature_set.cpp:62-66)
-__global__ void k_score_row_count(const uint8_t* score, int w, int h, int* row_counts) {
-    int y = blockIdx.x;
+// ---- a score map as the raster-ordered keypoint list (cv::FAST's output order + KeyPoint::convert, feature_set.cpp:62-66):
+// one 64-lane block per image row counts its keypoints, one thread turns the counts into offsets, one block per row emits ----
+static __device__ __forceinline__ int score_row_count(const uint8_t* row, int w) {
     int cnt = 0;
-    for (int x = threadIdx.x; x < w; x += 64) cnt += score[(size_t)y * w + x] != 0;
+    for (int x = threadIdx.x; x < w; x += 64) cnt += row[x] != 0;
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if (threadIdx.x == 0) row_counts[y] = cnt;
+    return cnt;
 }
-__global__ void k_scan_rows(int* row_counts, int h, int* n_out) {          // single thread; h is a few hundred
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        int acc = 0;
-        for (int y = 0; y < h; y++) { int c = row_counts[y]; row_counts[y] = acc; acc += c; }
-        *n_out = acc;
-    }
+static __device__ __forceinline__ int scan_rows(int* rows, int h, int acc) {       // serial; h is a few hundred
+    for (int y = 0; y < h; y++) { const int c = rows[y]; rows[y] = acc; acc += c; }
+    return acc;
 }
-__global__ void k_score_row_emit(const uint8_t* score, int w, int h, const int* row_off, int cap, float2* xy, float* resp) {
-    int y = blockIdx.x;
-    int base = row_off[y];
+// store(idx, x, score) for every keypoint of the row whose list position idx (base + its rank in the row) is below cap
+template <class Store>
+static __device__ __forceinline__ void score_row_emit(const uint8_t* row, int w, int base, int cap, const Store& store) {
     for (int x0 = 0; x0 < w; x0 += 64) {
-        int x = x0 + threadIdx.x;
-        int s = x < w ? score[(size_t)y * w + x] : 0;
-        unsigned long long m = __ballot(s != 0);
+        const int x = x0 + threadIdx.x;
+        const int s = x < w ? row[x] : 0;
+        const unsigned long long m = __ballot(s != 0);
         if (s) {
-            int idx = base + __popcll(m & ((1ull << threadIdx.x) - 1ull));
-            if (idx < cap) { xy[idx] = make_float2((float)x, (float)y); resp[idx] = (float)s; }
+            const int idx = base + __popcll(m & ((1ull << threadIdx.x) - 1ull));
+            if (idx < cap) store(idx, x, s);
         }
         base += __popcll(m);
     }
 }
+
+// svo_fast_detect: (xy, response) per keypoint
+__global__ void k_score_row_count(const uint8_t* score, int w, int* row_counts) {
+    const int cnt = score_row_count(score + (size_t)blockIdx.x * w, w);
+    if (threadIdx.x == 0) row_counts[blockIdx.x] = cnt;
+}
+__global__ void k_scan_rows(int* row_counts, int h, int* n_out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *n_out = scan_rows(row_counts, h, 0);
+}
+__global__ void k_score_row_emit(const uint8_t* score, int w, const int* row_off, int cap, float2* xy, float* resp) {
+    const int y = blockIdx.x;
+    score_row_emit(score + (size_t)y * w, w, row_off[y], cap, [=](int idx, int x, int s) { xy[idx] = make_float2((float)x, (float)y); resp[idx] = (float)s; });
+}
 void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* row_counts_dev, float2* xy_dev, float* resp_dev, int* n_dev, hipStream_t st) {
-    hipLaunchKernelGGL(k_score_row_count, dim3(h), dim3(64), 0, st, score_dev, w, h, row_counts_dev);
+    hipLaunchKernelGGL(k_score_row_count, dim3(h), dim3(64), 0, st, score_dev, w, row_counts_dev);
     hipLaunchKernelGGL(k_scan_rows, dim3(1), dim3(64), 0, st, row_counts_dev, h, n_dev);
-    hipLaunchKernelGGL(k_score_row_emit, dim3(h), dim3(64), 0, st, score_dev, w, h, row_counts_dev, cap, xy_dev, resp_dev);
+    hipLaunchKernelGGL(k_score_row_emit, dim3(h), dim3(64), 0, st, score_dev, w, row_counts_dev, cap, xy_dev, resp_dev);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -906,7 +934,7 @@ void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* 
 static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int pass, int row, int b, int n_rows) {
     const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
-    if (pass == 0 ? !s.active : !s.do_second) return;
+    if (!detect_pass_runs(s, pass)) return;
     __shared__ int sh_before[EMIT_WAVES], sh_all[EMIT_WAVES], sh_cnt[EMIT_WAVES], sh_last;
     const int fb = s.feat_buf, n_old = s.n_old, W = d.geom.W;
     const int baw = d.cfg.buckets_along_width, bah = d.cfg.buckets_along_height;
@@ -980,8 +1008,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit(DevBuffers d, int 
 // k_fast_strided): the ticket still counts ROWS, so the block that finishes the last row publishes
 #define EMIT_STRIDED_BLOCKS 8
 __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_strided(DevBuffers d, int pass, int n_rows) {
-    const SeqState& s = d.st[seq_of(d, blockIdx.y)];
-    if (pass == 0 ? !s.active : !s.do_second) return;
+    if (!detect_pass_runs(d.st[seq_of(d, blockIdx.y)], pass)) return;
     for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
         bucket_emit_body(d, pass, row, blockIdx.y, n_rows);
         __syncthreads();
@@ -992,22 +1019,23 @@ __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_strided(DevBuffers
 // chains (FAST runs on the PREVIOUS left image, vo.cpp:325): on a nearly empty GPU their kernels ran one after the other, each
 // a few microseconds of work behind a launch.  k_front_a = {ingest + level 1 (with the per-frame reset)  ||  FAST pass 0},
 // k_front_b = {levels 2 and 3  ||  emit of pass 0}: blocks of both kinds in one grid, told apart by their linear index; the
-// two halves of a launch touch disjoint data (pass 0 of k_fast reads no field the reset writes).  Lone-stream contexts only
-// (SVO_LONE_MAX_SEQ): with many sequences every kernel fills the GPU by itself and the separate launches stay.
+// two halves of a launch touch disjoint data (detect_pass_runs).  Lone-stream contexts only (SVO_LONE_MAX_SEQ): with many
+// sequences every kernel fills the GPU by itself and the separate launches stay.  k_front_a_grey: converting contexts (BPP > 1).
 static_assert(EMIT_THREADS == 256, "k_front_b runs emit blocks beside 256-thread pyramid blocks");
-template <bool RECT>
-__global__ __launch_bounds__(256) void k_front_a(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
-    const int i = blockIdx.x;
-    if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH, RECT>(d, srcs, stride, PYR_BEGIN, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
-    const int j = i - n_a;
-    fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
-}
 template <int BPP, bool RECT>
-__global__ __launch_bounds__(256) void k_front_a_grey(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
+static __device__ __forceinline__ void front_a_body(const DevBuffers& d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
     const int i = blockIdx.x;
     if (i < n_a) { ingest_pyr1_body<PD_TW, PD_TH, RECT, BPP>(d, srcs, stride, PYR_BEGIN, i % ax, (i / ax) % ay, i / (ax * ay)); return; }
     const int j = i - n_a;
-    fast_body<0>(nullptr, 0, 0, nullptr, d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
+    fast_frame_block(d, 0, threshold, j % fx, (j / fx) % fy, j / (fx * fy), fx, fy);
+}
+template <bool RECT>
+__global__ __launch_bounds__(256) void k_front_a(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
+    front_a_body<1, RECT>(d, srcs, stride, ax, ay, n_a, fx, fy, threshold);
+}
+template <int BPP, bool RECT>
+__global__ __launch_bounds__(256) void k_front_a_grey(DevBuffers d, const uint8_t* const* srcs, int stride, int ax, int ay, int n_a, int fx, int fy, int threshold) {
+    front_a_body<BPP, RECT>(d, srcs, stride, ax, ay, n_a, fx, fy, threshold);
 }
 __global__ __launch_bounds__(256) void k_front_b(DevBuffers d, int px, int py, int n_p, int n_rows) {
     const int i = blockIdx.x;
@@ -1022,7 +1050,8 @@ bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_de
     if (off || d.B > SVO_LONE_MAX_SEQ || d.CN != 1 || d.geom.nlevels < 4 || d.cfg.features_per_bucket != 1) return false;
     const int ns = launch_seqs(d);
     const int ax = (d.geom.lv[1].w + PD_TW - 1) / PD_TW, ay = (d.geom.lv[1].h + PD_TH - 1) / PD_TH, n_a = ax * ay * ns * 2;
-    const int fx = (d.geom.W + FT_W - 1) / FT_W, fy = (d.geom.H + FT_H - 1) / FT_H, n_f = fx * fy * ns;
+    const dim3 f = fast_grid(d);
+    const int fx = f.x, fy = f.y, n_f = fx * fy * ns;
     if (d.in.bpp > 1) {
         with_bpp(d.in.bpp, [&](auto b) {
             constexpr int BPP = decltype(b)::value;
@@ -1043,97 +1072,43 @@ bool launch_front_fused(const DevBuffers& d, const uint8_t* const* left_right_de
 }
 
 // ------------------------------------------------------------------------------------------------
-// features_per_bucket > 1 inside the frame pipeline: FeatureSet::appendFeaturesFromImage as written (feature_set.cpp:75-89):
-// the pass's input list = existing tracks, then cv::FAST's keypoints in raster order (age 0, strength = response), walked in
-// that order through Bucket::add_feature (fill, then replace the first minimum iff strictly better, :20-53), emitted in
-// bucket-raster order (:132-146).  One thread per bucket walks the whole list: O(N x buckets), the price of a capacity the
-// reference itself only uses in its unit tests (main.cpp:125, 152-157); the default capacity 1 never comes here.
+// General bucketing (any features_per_bucket): FeatureSet::appendFeaturesFromImage as written (feature_set.cpp:75-89).  A pass's
+// input list = existing tracks, then cv::FAST's keypoints in raster order (age 0, strength = response), walked in that order
+// through Bucket::add_feature (fill, then replace the first minimum iff strictly better, :20-53), emitted in bucket-raster
+// order (:132-146).  One thread per bucket walks the whole list: O(N x buckets), the price of a capacity the reference itself
+// only uses in its unit tests (main.cpp:125, 152-157); the default capacity 1 never comes here.  The walk and the emit are
+// written once, for one grid and one list; the frame pipeline (k_gen_*: per sequence, from DevBuffers) and the stage call
+// svo_bucket_filter (k_bucket_walk / k_bucket_order_emit: the caller's list) wrap them.
 // ------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ bool pass_runs(const SeqState& s, int pass) { return pass == 0 ? s.active : s.do_second; }
-
-__global__ void k_gen_row_count(DevBuffers d, int pass) {
-    const int seq = seq_of(d, blockIdx.y), y = blockIdx.x, W = d.geom.W, H = d.geom.H;
-    if (!pass_runs(d.st[seq], pass)) return;
-    const uint8_t* score = d.score + (size_t)seq * W * H;
-    int cnt = 0;
-    for (int x = threadIdx.x; x < W; x += 64) cnt += score[(size_t)y * W + x] != 0;
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if (threadIdx.x == 0) d.kp_rows[(size_t)seq * H + y] = cnt;
-}
-__global__ void k_gen_scan_rows(DevBuffers d, int pass) {          // one lane per sequence; H is a few hundred
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= launch_seqs(d)) return;
-    const int seq = seq_of(d, b);
-    SeqState& s = d.st[seq];
-    if (!pass_runs(s, pass)) return;
-    int* rows = d.kp_rows + (size_t)seq * d.geom.H;
-    int acc = s.n_feat;                                              // keypoints are appended after the existing tracks
-    for (int y = 0; y < d.geom.H; y++) { int c = rows[y]; rows[y] = acc; acc += c; }
-    d.n_cand[seq] = acc < d.KPCAP ? acc : d.KPCAP;
-    s.n_old = s.n_feat;
-}
-__global__ void k_gen_emit_candidates(DevBuffers d, int pass) {
-    const int seq = seq_of(d, blockIdx.y), W = d.geom.W, H = d.geom.H;
-    const SeqState& s = d.st[seq];
-    if (!pass_runs(s, pass)) return;
-    const size_t co = (size_t)seq * d.KPCAP, fo = (size_t)seq * d.CAP;
-    if ((int)blockIdx.x == H) {                                      // the extra block copies the existing tracks to the head of the list
-        const int fb = s.feat_buf;
-        for (int i = threadIdx.x; i < s.n_feat; i += 64) {
-            d.cand_xy[co + i] = d.feat_xy[fb][fo + i]; d.cand_age[co + i] = d.feat_age[fb][fo + i]; d.cand_str[co + i] = d.feat_str[fb][fo + i];
-        }
-        return;
-    }
-    const int y = blockIdx.x;
-    const uint8_t* score = d.score + (size_t)seq * W * H;
-    int base = d.kp_rows[(size_t)seq * H + y];
-    for (int x0 = 0; x0 < W; x0 += 64) {
-        const int x = x0 + threadIdx.x;
-        const int sc = x < W ? score[(size_t)y * W + x] : 0;
-        const unsigned long long m = __ballot(sc != 0);
-        if (sc) {
-            const int idx = base + __popcll(m & ((1ull << threadIdx.x) - 1ull));
-            if (idx < d.KPCAP) { d.cand_xy[co + idx] = make_float2((float)x, (float)y); d.cand_age[co + idx] = 0; d.cand_str[co + idx] = sc; }   // feature_set.cpp:83-87
-        }
-        base += __popcll(m);
-    }
-}
-__global__ void k_gen_bucket_walk(DevBuffers d, int pass) {
-    const int seq = seq_of(d, blockIdx.y), b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= d.NB || !pass_runs(d.st[seq], pass)) return;
-    const int baw = d.cfg.buckets_along_width, bah = d.cfg.buckets_along_height, per = d.cfg.features_per_bucket;
-    const int cap = (b / baw) >= d.cfg.bucket_start_row ? per : 0;                     // feature_set.cpp:113-116
-    const size_t co = (size_t)seq * d.KPCAP, so = ((size_t)seq * d.NB + b) * per;
-    float2* sx = d.slot_xy + so; int* sa = d.slot_age + so; int* ss = d.slot_str + so;
-    const int n = d.n_cand[seq], fthr = d.cfg.fast_threshold;
+// bucket b of the grid: its slots (slot_* + b * per) and their number slot_n[b] from the n candidates
+static __device__ __forceinline__ void bucket_walk(const BucketGrid& g, int per, int n, const float2* xy, const int* age, const int* str,
+                                                   float2* slot_xy, int* slot_age, int* slot_str, int* slot_n, int b) {
+    float2* sx = slot_xy + (size_t)b * per; int* sa = slot_age + (size_t)b * per; int* ss = slot_str + (size_t)b * per;
+    const int cap = (b / g.baw) >= g.start_row ? per : 0;                              // feature_set.cpp:113-116
     int cnt = 0;
     for (int i = 0; i < n && cap > 0; i++) {
-        const float2 p = d.cand_xy[co + i];
-        const int bh = (int)(p.y / (float)d.bucket_h), bw = (int)(p.x / (float)d.bucket_w);   // :122-123
-        if (bh < 0 || bh >= bah || bw < 0 || bw >= baw || bh * baw + bw != b) continue;
-        const int a = d.cand_age[co + i], st = d.cand_str[co + i];
-        if (a >= d.cfg.age_threshold) continue;                                        // :26
+        const float2 p = xy[i];
+        int bh, bw;
+        if (!bucket_of(g, p.x, p.y, bh, bw) || bh * g.baw + bw != b) continue;
+        const int a = age[i], st = str[i];
+        if (a >= g.age_thr) continue;                                                  // :26
         if (cnt < cap) { sx[cnt] = p; sa[cnt] = a; ss[cnt] = st; cnt++; }
         else {
-            const int score = a + (st - fthr) / 20;
-            int smin = sa[0] + (ss[0] - fthr) / 20, imin = 0;
-            for (int k = 1; k < cnt; k++) { const int c = sa[k] + (ss[k] - fthr) / 20; if (c < smin) { smin = c; imin = k; } }
-            if (score > smin) { sx[imin] = p; sa[imin] = a; ss[imin] = st; }
+            int smin = bucket_score(sa[0], ss[0], g.fast_thr), imin = 0;
+            for (int k = 1; k < cnt; k++) { const int c = bucket_score(sa[k], ss[k], g.fast_thr); if (c < smin) { smin = c; imin = k; } }
+            if (bucket_score(a, st, g.fast_thr) > smin) { sx[imin] = p; sa[imin] = a; ss[imin] = st; }
         }
     }
-    d.slot_n[(size_t)seq * d.NB + b] = cnt;
+    slot_n[b] = cnt;
 }
+// The slots of nb buckets in bucket order to out_*[0 .. cap): a block of GEN_EMIT_THREADS threads, each with a run of buckets,
+// a block scan of their counts.  Returns the number of filled slots (which may exceed cap) to every thread.
 #define GEN_EMIT_THREADS 1024
 #define GEN_EMIT_WAVES (GEN_EMIT_THREADS / 64)
-__global__ __launch_bounds__(GEN_EMIT_THREADS) void k_gen_bucket_emit(DevBuffers d, int pass) {
-    const int seq = seq_of(d, blockIdx.x);
-    SeqState& s = d.st[seq];
-    if (!pass_runs(s, pass)) return;
+static __device__ __forceinline__ int bucket_order_emit(int nb, int per, const float2* slot_xy, const int* slot_age, const int* slot_str, const int* sn,
+                                                        int cap, float2* out_xy, int* out_age, int* out_str) {
     __shared__ int wave_tot[GEN_EMIT_WAVES];
     __shared__ int s_total;
-    const int fb = s.feat_buf, nb = d.NB, per = d.cfg.features_per_bucket;
-    const int* sn = d.slot_n + (size_t)seq * nb;
-    float2* nxy = d.feat_xy[fb ^ 1] + (size_t)seq * d.CAP; int* nage = d.feat_age[fb ^ 1] + (size_t)seq * d.CAP; int* nstr = d.feat_str[fb ^ 1] + (size_t)seq * d.CAP;
     const int chunk = (nb + GEN_EMIT_THREADS - 1) / GEN_EMIT_THREADS;
     const int b0 = threadIdx.x * chunk < nb ? threadIdx.x * chunk : nb, b1 = (b0 + chunk < nb) ? b0 + chunk : nb;
     int cnt = 0;
@@ -1147,13 +1122,63 @@ __global__ __launch_bounds__(GEN_EMIT_THREADS) void k_gen_bucket_emit(DevBuffers
     __syncthreads();
     int pos = wave_tot[wv] + incl - cnt;
     for (int b = b0; b < b1; b++) {
-        const size_t so = ((size_t)seq * nb + b) * per;
+        const size_t so = (size_t)b * per;
         for (int k = 0; k < sn[b]; k++, pos++)
-            if (pos < d.CAP) { nxy[pos] = d.slot_xy[so + k]; nage[pos] = d.slot_age[so + k]; nstr[pos] = d.slot_str[so + k]; }
+            if (pos < cap) { out_xy[pos] = slot_xy[so + k]; out_age[pos] = slot_age[so + k]; out_str[pos] = slot_str[so + k]; }
     }
+    return s_total;
+}
+
+// ---- the frame pipeline's wrappers: FAST to the score map (k_fast<2>), the candidate list, the walk, the emit ----
+__global__ void k_gen_row_count(DevBuffers d, int pass) {
+    const int seq = seq_of(d, blockIdx.y), y = blockIdx.x, W = d.geom.W, H = d.geom.H;
+    if (!detect_pass_runs(d.st[seq], pass)) return;
+    const int cnt = score_row_count(d.score + ((size_t)seq * H + y) * W, W);
+    if (threadIdx.x == 0) d.kp_rows[(size_t)seq * H + y] = cnt;
+}
+__global__ void k_gen_scan_rows(DevBuffers d, int pass) {          // one lane per sequence
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
+    SeqState& s = d.st[seq];
+    if (!detect_pass_runs(s, pass)) return;
+    const int n = scan_rows(d.kp_rows + (size_t)seq * d.geom.H, d.geom.H, s.n_feat);   // keypoints are appended after the existing tracks
+    d.n_cand[seq] = n < d.KPCAP ? n : d.KPCAP;
+    s.n_old = s.n_feat;
+}
+__global__ void k_gen_emit_candidates(DevBuffers d, int pass) {
+    const int seq = seq_of(d, blockIdx.y), W = d.geom.W, H = d.geom.H;
+    const SeqState& s = d.st[seq];
+    if (!detect_pass_runs(s, pass)) return;
+    float2* cxy = d.cand_xy + (size_t)seq * d.KPCAP; int* cage = d.cand_age + (size_t)seq * d.KPCAP; int* cstr = d.cand_str + (size_t)seq * d.KPCAP;
+    if ((int)blockIdx.x == H) {                                      // the extra block copies the existing tracks to the head of the list
+        const int fb = s.feat_buf;
+        const size_t fo = (size_t)seq * d.CAP;
+        for (int i = threadIdx.x; i < s.n_feat; i += 64) { cxy[i] = d.feat_xy[fb][fo + i]; cage[i] = d.feat_age[fb][fo + i]; cstr[i] = d.feat_str[fb][fo + i]; }
+        return;
+    }
+    const int y = blockIdx.x;
+    score_row_emit(d.score + ((size_t)seq * H + y) * W, W, d.kp_rows[(size_t)seq * H + y], d.KPCAP,
+                   [=](int idx, int x, int sc) { cxy[idx] = make_float2((float)x, (float)y); cage[idx] = 0; cstr[idx] = sc; });   // feature_set.cpp:83-87
+}
+__global__ void k_gen_bucket_walk(DevBuffers d, int pass) {
+    const int seq = seq_of(d, blockIdx.y), b = blockIdx.x * blockDim.x + threadIdx.x, per = d.cfg.features_per_bucket;
+    if (b >= d.NB || !detect_pass_runs(d.st[seq], pass)) return;
+    const size_t co = (size_t)seq * d.KPCAP, so = (size_t)seq * d.NB * per;
+    bucket_walk(grid_of(d), per, d.n_cand[seq], d.cand_xy + co, d.cand_age + co, d.cand_str + co,
+                d.slot_xy + so, d.slot_age + so, d.slot_str + so, d.slot_n + (size_t)seq * d.NB, b);
+}
+__global__ __launch_bounds__(GEN_EMIT_THREADS) void k_gen_bucket_emit(DevBuffers d, int pass) {
+    const int seq = seq_of(d, blockIdx.x);
+    SeqState& s = d.st[seq];
+    if (!detect_pass_runs(s, pass)) return;
+    const int fb = s.feat_buf, per = d.cfg.features_per_bucket;
+    const size_t so = (size_t)seq * d.NB * per, fo = (size_t)seq * d.CAP;
+    const int filled = bucket_order_emit(d.NB, per, d.slot_xy + so, d.slot_age + so, d.slot_str + so, d.slot_n + (size_t)seq * d.NB,
+                                         d.CAP, d.feat_xy[fb ^ 1] + fo, d.feat_age[fb ^ 1] + fo, d.feat_str[fb ^ 1] + fo);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int total = s_total < d.CAP ? s_total : d.CAP;
+        const int total = filled < d.CAP ? filled : d.CAP;
         s.n_feat = total; s.feat_buf = fb ^ 1;
         s.stats.n_after_detect = total;
         if (pass == 0) s.do_second = total < d.cfg.pre_matching_feature_threshold;   // vo.cpp:327
@@ -1161,9 +1186,8 @@ __global__ __launch_bounds__(GEN_EMIT_THREADS) void k_gen_bucket_emit(DevBuffers
     }
 }
 static void launch_detect_general(const DevBuffers& d, int pass, int th, hipStream_t st) {
-    const int W = d.geom.W, H = d.geom.H, ns = launch_seqs(d);
-    dim3 g((W + FT_W - 1) / FT_W, (H + FT_H - 1) / FT_H, ns);
-    hipLaunchKernelGGL(k_fast<2>, g, dim3(256), 0, st, (const uint8_t*)nullptr, 0, 0, (uint8_t*)nullptr, d, pass, th);
+    const int H = d.geom.H, ns = launch_seqs(d);
+    hipLaunchKernelGGL(k_fast<2>, fast_grid(d), dim3(256), 0, st, d, pass, th);
     hipLaunchKernelGGL(k_gen_row_count, dim3(H, ns), dim3(64), 0, st, d, pass);
     hipLaunchKernelGGL(k_gen_scan_rows, dim3((ns + 63) / 64), dim3(64), 0, st, d, pass);
     hipLaunchKernelGGL(k_gen_emit_candidates, dim3(H + 1, ns), dim3(64), 0, st, d, pass);
@@ -1176,66 +1200,35 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
     if (th_override >= 0) th = th_override;
     if (d.cfg.features_per_bucket > 1) { launch_detect_general(d, pass, th, st); return; }
     // pass 0: k_fast offers the existing tracks itself; pass 1 finds them offered (and n_old set) by the last block of pass 0's emit
-    const int ns = launch_seqs(d);
-    dim3 g((d.geom.W + FT_W - 1) / FT_W, (d.geom.H + FT_H - 1) / FT_H, ns);
+    const dim3 g = fast_grid(d);
     static const bool strided_off = getenv("SVO_SECOND_PASS_STRIDED") && atoi(getenv("SVO_SECOND_PASS_STRIDED")) == 0;
     if (pass == 1 && d.B > SVO_LONE_MAX_SEQ && !strided_off) {
-        hipLaunchKernelGGL(k_fast_strided, dim3(FAST_STRIDED_BLOCKS, 1, ns), dim3(256), 0, st, d, pass, th, (int)g.x, (int)g.y);
-        hipLaunchKernelGGL(k_bucket_emit_strided, dim3(EMIT_STRIDED_BLOCKS, ns), dim3(EMIT_THREADS), 0, st, d, pass, d.cfg.buckets_along_height);
+        hipLaunchKernelGGL(k_fast_strided, dim3(FAST_STRIDED_BLOCKS, 1, g.z), dim3(256), 0, st, d, pass, th, (int)g.x, (int)g.y);
+        hipLaunchKernelGGL(k_bucket_emit_strided, dim3(EMIT_STRIDED_BLOCKS, g.z), dim3(EMIT_THREADS), 0, st, d, pass, d.cfg.buckets_along_height);
         return;
     }
-    hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, (const uint8_t*)nullptr, 0, 0, (uint8_t*)nullptr, d, pass, th);
-    hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, ns), dim3(EMIT_THREADS), 0, st, d, pass);
+    hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, d, pass, th);
+    hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, g.z), dim3(EMIT_THREADS), 0, st, d, pass);
 }
 
-// ------------------------------------------------------------------------------------------------
-// General bucketing (any features_per_bucket): one thread per bucket walks the inputs in order and
-// applies Bucket::add_feature verbatim in behaviour (feature_set.cpp:20-53).  O(N * buckets): only
-// the reference's unit tests use per-bucket capacities other than 1 (main.cpp:125,152-157).
-// ------------------------------------------------------------------------------------------------
-__global__ void k_bucket_general(int img_w, int img_h, int n, const float2* xy, const int* ages, const int* strs,
-                                 int bah, int baw, int start_row, int per_bucket, int age_thr, int fast_thr,
-                                 float2* slot_xy, int* slot_age, int* slot_str, int* slot_n) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= bah * baw) return;
-    int bucket_h = (img_h + bah - 1) / bah, bucket_w = (img_w + baw - 1) / baw;      // feature_set.cpp:91-93,103-104
-    int cap = (b / baw) >= start_row ? per_bucket : 0;                               // :113-116
-    float2* sx = slot_xy + (size_t)b * per_bucket; int* sa = slot_age + (size_t)b * per_bucket; int* ss = slot_str + (size_t)b * per_bucket;
-    int cnt = 0;
-    for (int i = 0; i < n && cap > 0; i++) {
-        float2 p = xy[i];
-        int bh = (int)(p.y / (float)bucket_h), bw = (int)(p.x / (float)bucket_w);
-        if (bh < 0 || bh >= bah || bw < 0 || bw >= baw || bh * baw + bw != b) continue;
-        int a = ages[i], st = strs[i];
-        if (a >= age_thr) continue;
-        if (cnt < cap) { sx[cnt] = p; sa[cnt] = a; ss[cnt] = st; cnt++; }
-        else {
-            int score = a + (st - fast_thr) / 20;
-            int smin = sa[0] + (ss[0] - fast_thr) / 20, imin = 0;
-            for (int k = 1; k < cnt; k++) { int c = sa[k] + (ss[k] - fast_thr) / 20; if (c < smin) { smin = c; imin = k; } }
-            if (score > smin) { sx[imin] = p; sa[imin] = a; ss[imin] = st; }
-        }
-    }
-    slot_n[b] = cnt;
+// ---- the stage call's wrappers (svo_bucket_filter): one grid, the caller's n candidates, n_out = the number emitted ----
+__global__ void k_bucket_walk(BucketGrid g, int per, int n, const float2* xy, const int* ages, const int* strs,
+                              float2* slot_xy, int* slot_age, int* slot_str, int* slot_n) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < g.bah * g.baw) bucket_walk(g, per, n, xy, ages, strs, slot_xy, slot_age, slot_str, slot_n, b);
 }
-__global__ void k_bucket_general_emit(int nb, int per_bucket, const float2* slot_xy, const int* slot_age, const int* slot_str, const int* slot_n,
-                                      float2* out_xy, int* out_age, int* out_str, int* n_out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;                                 // test-sized inputs: serial emit keeps bucket-raster order
-    int m = 0;
-    for (int b = 0; b < nb; b++)
-        for (int k = 0; k < slot_n[b]; k++) {
-            out_xy[m] = slot_xy[(size_t)b * per_bucket + k]; out_age[m] = slot_age[(size_t)b * per_bucket + k]; out_str[m] = slot_str[(size_t)b * per_bucket + k]; m++;
-        }
-    *n_out = m;
+__global__ __launch_bounds__(GEN_EMIT_THREADS) void k_bucket_order_emit(int nb, int per, const float2* slot_xy, const int* slot_age, const int* slot_str,
+                                                                        const int* slot_n, int cap, float2* out_xy, int* out_age, int* out_str, int* n_out) {
+    const int filled = bucket_order_emit(nb, per, slot_xy, slot_age, slot_str, slot_n, cap, out_xy, out_age, out_str);
+    if (threadIdx.x == 0) *n_out = filled < cap ? filled : cap;
 }
-void launch_bucket_general(int img_w, int img_h, int n, const float2* xy, const int* ages, const int* strs,
-                           int bah, int baw, int start_row, int per_bucket, int age_thr, int fast_thr,
+void launch_bucket_general(const BucketGrid& g, int per_bucket, int n, const float2* xy, const int* ages, const int* strs,
                            float2* slot_xy, int* slot_age, int* slot_str, int* slot_n,
                            float2* out_xy, int* out_age, int* out_str, int* n_out, hipStream_t st) {
-    int nb = bah * baw;
-    hipLaunchKernelGGL(k_bucket_general, dim3((nb + 255) / 256), dim3(256), 0, st, img_w, img_h, n, xy, ages, strs, bah, baw, start_row,
-                       per_bucket, age_thr, fast_thr, slot_xy, slot_age, slot_str, slot_n);
-    hipLaunchKernelGGL(k_bucket_general_emit, dim3(1), dim3(64), 0, st, nb, per_bucket, slot_xy, slot_age, slot_str, slot_n, out_xy, out_age, out_str, n_out);
+    const int nb = g.bah * g.baw;
+    hipLaunchKernelGGL(k_bucket_walk, dim3((nb + 255) / 256), dim3(256), 0, st, g, per_bucket, n, xy, ages, strs, slot_xy, slot_age, slot_str, slot_n);
+    hipLaunchKernelGGL(k_bucket_order_emit, dim3(1), dim3(GEN_EMIT_THREADS), 0, st, nb, per_bucket, slot_xy, slot_age, slot_str, slot_n, n,
+                       out_xy, out_age, out_str, n_out);
 }
 
 // ------------------------------------------------------------------------------------------------

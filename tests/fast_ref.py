@@ -159,14 +159,16 @@ def append_features(img, th, xy, ages, strengths, bah, baw, start_row, per_bucke
     return bucket_filter(w, h, xy, ages, strengths, bah, baw, start_row, per_bucket, age_thr, fast_thr)
 
 
-def detect_for_frame(img, cfg):
-    """Detection of one frame from an empty feature set -> (xy, ages, strengths, second_pass): a pass at fast_threshold and,
-    if fewer than pre_matching_feature_threshold features survive, a second at fast_threshold / 4 with the survivors as existing
-    tracks (the bucket score keeps using fast_threshold).  cfg: any object with the configuration's field names."""
+def detect_for_frame(img, cfg, existing=None):
+    """Detection of one frame -> (xy, ages, strengths, second_pass): a pass at fast_threshold and, if fewer than
+    pre_matching_feature_threshold features survive, a second at fast_threshold / 4 with the survivors as existing tracks (the
+    bucket score keeps using fast_threshold).  existing: the feature set the frame starts from as (xy, ages, strengths); None is
+    the empty set.  cfg: any object with the configuration's field names."""
     grid = (cfg.buckets_along_height, cfg.buckets_along_width, cfg.bucket_start_row, cfg.features_per_bucket,
             cfg.age_threshold, cfg.fast_threshold)
     none = np.zeros(0, np.int32)
-    out = append_features(img, cfg.fast_threshold, np.zeros((0, 2), np.float32), none, none, *grid)
+    existing = (np.zeros((0, 2), np.float32), none, none) if existing is None else existing
+    out = append_features(img, cfg.fast_threshold, existing[0], existing[1], existing[2], *grid)
     second = len(out[1]) < cfg.pre_matching_feature_threshold
     if second:
         out = append_features(img, _cdiv(cfg.fast_threshold, 4), out[0], out[1], out[2], *grid)

@@ -305,3 +305,122 @@ def test_frame_detection_nine_sequences_with_different_images(api):
         n = _check_frame(vo.stats[i], vo.last_tracks(i), refs[i], (i, kinds[i]))
         assert n >= 50 or kinds[i] != "texture"
     vo.close()
+
+
+# ---------------------------------------------------------------- more than eight sequences at features_per_bucket = 2
+NINE_KINDS = ["texture", "sparse", "sat", "sparse", "texture", "sat", "sparse", "texture", "sparse"]
+IDLE = (1, 4)
+
+
+@pytest.fixture(scope="module")
+def nine_per2(api):
+    """Nine sequences with different images (the kinds of test_frame_detection_nine_sequences_with_different_images) at capacity
+    2, the same stereo pair every frame: frame 2 detects from the empty set; frame 3 runs with sequences 1 and 4 idle; frame 4
+    with all nine again.  Everything the tests look at is recorded here, with the references (computed once)."""
+    B = len(NINE_KINDS)
+    lefts = [_frame(k, i) for i, k in enumerate(NINE_KINDS)]
+    rights = [scenes.shift_image(im, -3, 0) for im in lefts]
+    cfg = api.default_config(max_translation_norm=5.0, features_per_bucket=2)
+    refs = [_detect_ref(cfg, im) for im in lefts]
+    cfg1 = api.default_config(max_translation_norm=5.0)
+    sparse1 = [_detect_ref(cfg1, lefts[i]) for i in range(B) if NINE_KINDS[i] == "sparse"]
+    vo = api.BatchVisualOdometry(FW, FH, B, cfg); vo.initalize_projection_matricies(*_projection())
+
+    def snapshot():
+        return dict(stats=list(vo.stats), tracks=[vo.last_tracks(i) for i in range(B)], feats=[vo.features(i) for i in range(B)])
+
+    vo.stereo_callback_batch(lefts, rights)
+    vo.stereo_callback_batch(lefts, rights)
+    f2 = snapshot()
+    active = [i not in IDLE for i in range(B)]
+    vo.stereo_callback_batch(lefts, rights, active=active)
+    f3 = snapshot()
+    vo.stereo_callback_batch(lefts, rights)
+    f4 = snapshot()
+    vo.close()
+    return SimpleNamespace(B=B, cfg=cfg, lefts=lefts, refs=refs, sparse1=sparse1, f2=f2, f3=f3, f4=f4)
+
+
+def test_frame_detection_nine_sequences_two_per_bucket(nine_per2):
+    """The general walk, the keypoint list and the block emit behind seq_of() at more than eight sequences; the four sparse
+    sequences take the second pass.  The fixture tells capacity 2 from capacity 1: the reference gives 18 features with a second
+    pass for every sparse sequence at capacity 2 (12 at capacity 1), 3994-4061 for the textures, 627-649 for the saturated."""
+    t = nine_per2
+    for i, k in enumerate(NINE_KINDS):
+        n, second = len(t.refs[i][0]), t.refs[i][3]
+        if k == "sparse":
+            assert n == 18 and second, (i, n, second)
+        elif k == "texture":
+            assert 3994 <= n <= 4061 and not second, (i, n)
+        else:
+            assert 627 <= n <= 649 and not second, (i, n)
+    assert [(len(r[0]), bool(r[3])) for r in t.sparse1] == [(12, True)] * 4
+    for i, k in enumerate(NINE_KINDS):
+        n = _check_frame(t.f2["stats"][i], t.f2["tracks"][i], t.refs[i], (i, k))
+        assert n >= 50 or k != "texture"
+
+
+def test_idle_sequences_keep_their_feature_set_and_grid(nine_per2):
+    """Frame 3 with sequences 1 and 4 idle: the seven active ones detect what the reference detects from the feature set frame 2
+    left them; the idle ones report fail_reason 5 and keep their set; their next active frame detects what the reference detects
+    from that set — an idle frame leaves feature set and grid state alone."""
+    t = nine_per2
+    for i, k in enumerate(NINE_KINDS):
+        if i in IDLE:
+            assert t.f3["stats"][i].fail_reason == 5, i
+            assert same_features(t.f3["feats"][i], t.f2["feats"][i]), i
+            ref = fr.detect_for_frame(t.lefts[i], t.cfg, existing=t.f2["feats"][i])
+            assert len(ref[0]) > 0
+            _check_frame(t.f4["stats"][i], t.f4["tracks"][i], ref, (i, k, "after idle"))
+        else:
+            assert t.f3["stats"][i].fail_reason != 5, i
+            ref = fr.detect_for_frame(t.lefts[i], t.cfg, existing=t.f2["feats"][i])
+            assert len(ref[0]) > 0
+            _check_frame(t.f3["stats"][i], t.f3["tracks"][i], ref, (i, k, "beside idle"))
+
+
+# ---------------------------------------------------------------- svo_bucket_filter: the stage call's wrappers
+def _stage_filter(api, w, h, xy, ages, st, bah, baw, start_row, per, age_thr, fast_thr):
+    oxy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2).copy(); oag = np.ascontiguousarray(ages, np.int32).copy()
+    ost = np.ascontiguousarray(st, np.int32).copy()
+    n = C.c_int(len(oag))
+    api.check(api.lib.svo_bucket_filter(0, w, h, C.byref(n), api.ptr(oxy), api.ptr(oag), api.ptr(ost), bah, baw, start_row, per, age_thr, fast_thr))
+    assert 0 <= n.value <= len(oag)
+    return oxy[:n.value].copy(), oag[:n.value].copy(), ost[:n.value].copy()
+
+
+def test_bucket_filter_stage_call_equals_the_pipeline(api):
+    """The stage call and the frame pipeline run one walk and one emit through two sets of wrappers: on the coarse_per3 grid with
+    track_fixture they give the same set — the pipeline's taken through svo_append_features_from_image on a black image, so that
+    the tracks are its whole input — and that set is the oracle's and the definition's."""
+    cfg = api.default_config(**GRIDS["coarse_per3"])
+    img = _append_image("black")
+    h, w = img.shape
+    bah, baw, row0, per = cfg.buckets_along_height, cfg.buckets_along_width, cfg.bucket_start_row, cfg.features_per_bucket
+    xy, ages, st = fr.track_fixture(w, h, bah, baw, seed=5)
+    want = fr.bucket_filter(w, h, xy, ages, st, bah, baw, row0, per, cfg.age_threshold, cfg.fast_threshold)
+    assert per < len(want[1]) < len(ages)
+    pipeline = _append(api, cfg, img, 20, xy, ages, st)
+    stage = _stage_filter(api, w, h, xy, ages, st, bah, baw, row0, per, cfg.age_threshold, cfg.fast_threshold)
+    assert same_features(stage, pipeline)
+    assert same_features(stage, orc.bucket_filter(w, h, xy, ages, st, bah, baw, row0, per, cfg.age_threshold, cfg.fast_threshold))
+    assert same_features(stage, want)
+
+
+@pytest.mark.parametrize("start_row,n_out", [(0, 96), (1, 72)])
+def test_bucket_filter_every_bucket_full(api, start_row, n_out):
+    """64x32, grid 4x8 of 8x8 buckets, five candidates in every bucket at capacity 3: 96 outputs in one call — more than a wave,
+    fewer than the emit's block — and, with start_row = 1, an empty grid row 0 in front of the rest."""
+    rng = np.random.default_rng(9)
+    w, h, bah, baw, per = 64, 32, 4, 8, 3
+    cells = np.array([(8 * c, 8 * r) for r in range(bah) for c in range(baw)], np.float32)
+    xy = (np.repeat(cells, 5, 0) + rng.uniform(0, 7.99, (5 * len(cells), 2))).astype(np.float32)
+    ages = rng.integers(0, 4, len(xy)).astype(np.int32)
+    st = rng.integers(0, 256, len(xy)).astype(np.int32)
+    order = rng.permutation(len(xy))
+    xy, ages, st = xy[order], ages[order], st[order]
+    want = orc.bucket_filter(w, h, xy, ages, st, bah, baw, start_row, per, 20, 20)
+    assert len(want[1]) == n_out
+    got = _stage_filter(api, w, h, xy, ages, st, bah, baw, start_row, per, 20, 20)
+    assert same_features(got, want), (len(got[1]), n_out)
+    assert same_features(got, fr.bucket_filter(w, h, xy, ages, st, bah, baw, start_row, per, 20, 20))
