@@ -207,6 +207,14 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
 #define ALLOC(ptr, count) if ((rc = dev_alloc(c, &(ptr), (count))) != SVO_OK) return rc;
     ALLOC(d.st, B);
     ALLOC(d.pyr, B * 2 * SVO_PYR_SLOTS * (size_t)d.CN * (size_t)d.geom.pyr_bytes + 256);   // + slack: the LK kernel's unaligned dword loads may read a few bytes past a row
+    // The derivative pyramid of the levels >= 1 (svo_internal.hpp), for the contexts whose pyramids the image stream builds ahead:
+    // many sequences, grey, exact sums.  Cleared here — that IS its constant-zero border, nothing writes there again.  Every other
+    // context keeps the null pointer and its LK kernel differentiates in registers.  SVO_LK_DERIV=0 switches the planes off (A/B).
+    {
+        static const bool off = getenv("SVO_LK_DERIV") && atoi(getenv("SVO_LK_DERIV")) == 0;
+        if (!off && ingest_ahead_applies(d) && !cfg.lk_float_sums)
+            ALLOC(d.deriv, B * 2 * SVO_PYR_SLOTS * 2 * (size_t)deriv_samples(d.geom) + 128);   // + slack: the last row's over-read
+    }
     if (d.CN == 3) ALLOC(d.fastimg, B * SVO_PYR_SLOTS * (size_t)width * (size_t)height + 256);
     for (int k = 0; k < 2; k++) { ALLOC(d.feat_xy[k], B * CAP); ALLOC(d.feat_age[k], B * CAP); ALLOC(d.feat_str[k], B * CAP); }
     ALLOC(d.bucket_keys, B * (size_t)d.NB);

@@ -73,6 +73,8 @@ struct DevBuffers {
     LkCrit lk_crit;                            // LK: lk_make_crit(cfg, geom), recomputed whenever cfg changes
     SeqState* st;                              // [B]
     uint8_t* pyr;                              // [B][SVO_PYR_SLOTS][2 cams][CN planes][pyr_bytes]
+    int16_t* deriv;                            // [B][SVO_PYR_SLOTS][2 cams][Ix, Iy][deriv_samples(geom)] the Scharr images of the levels >= 1 (below), or
+                                               // nullptr: the context keeps none and the LK kernel differentiates every window itself
     uint8_t* fastimg;                          // CN == 3 only: [B][3 slots][W*H] the first W bytes of every interleaved left row —
                                                // the single-channel 'image' cv::FAST sees in a BGR Mat
     float2* feat_xy[2]; int* feat_age[2]; int* feat_str[2];   // [B][CAP] each, double-buffered
@@ -124,6 +126,21 @@ __host__ __device__ inline int launch_seqs(const DevBuffers& d) { return d.act ?
 // plane 0 of the pyramid of (sequence, slot, camera); plane k follows at + k * geom.pyr_bytes
 __host__ __device__ inline size_t pyr_index(const DevBuffers& d, int seq, int slot, int cam) {
     return ((size_t)(seq * SVO_PYR_SLOTS + slot) * 2 + cam) * (size_t)d.CN * (size_t)d.geom.pyr_bytes;
+}
+// ---- the derivative pyramid of the levels >= 1 (many-sequence grey contexts in the exact-sums mode; k_deriv_levels writes it, lk_pass
+// reads it).  What cv::buildOpticalFlowPyramid keeps with withDerivatives = true, for the coarse levels only: level 0 holds three
+// quarters of a pyramid's pixels and a quarter of the LK level visits, the levels above it the reverse.
+// A plane (Ix or Iy) is laid out like the part of an image pyramid behind level 0, one int16 sample per pixel: sample (x, y) of level
+// l >= 1 sits at int16 index lv[l].off - deriv_origin(g) + y * lv[l].stride + x, so the level table addresses it and the image's
+// border (pad >= EXT + 5 on every side) is the derivative's too: wide enough for every window origin in reach ([-W, size) per axis),
+// the window plus one sample and one sample of over-read.  A sample is 4 x the Scharr value of the PADDED level (the reflected pixels
+// at the edge) — the integer lk_pass computes in registers — inside the level, and zero outside it (derivBorder = BORDER_CONSTANT):
+// the buffer is cleared when it is allocated and only the samples inside the levels are ever written.  Row starts and plane bases
+// are multiples of 32 bytes.  The planes of (sequence, slot, camera) belong to the pyramid of the same index, whatever the slot rule does.
+__host__ __device__ inline int deriv_origin(const Geometry& g) { return g.lv[0].stride * (g.lv[0].h + 2 * g.pad); }   // bytes of level 0 with its border
+__host__ __device__ inline int deriv_samples(const Geometry& g) { return g.pyr_bytes - deriv_origin(g); }            // int16 samples of one plane
+__host__ __device__ inline size_t deriv_index(const DevBuffers& d, int seq, int slot, int cam) {                      // the Ix plane; Iy follows at + deriv_samples
+    return ((size_t)(seq * SVO_PYR_SLOTS + slot) * 2 + cam) * 2 * (size_t)deriv_samples(d.geom);
 }
 __host__ __device__ inline size_t fastimg_index(const DevBuffers& d, int seq, int slot) {
     return (size_t)(seq * SVO_PYR_SLOTS + slot) * (size_t)d.geom.W * (size_t)d.geom.H;

@@ -571,6 +571,72 @@ static void launch_pad_pyramid(const DevBuffers& d, hipStream_t st, PyrTarget ta
     hipLaunchKernelGGL(k_pad_pyramid, dim3(gx, d.geom.nlevels, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, target);
 }
 
+// k_deriv_levels: the Scharr images of the levels >= 1 of the target's slot, for the LK kernel (svo_internal.hpp: the derivative
+// pyramid; contexts with d.deriv only).  Runs behind k_pad_pyramid: a sample inside the level is the derivative of the level WITH its
+// REFLECT_101 border, at 4 x the Scharr value, the integers lk_pass computes for itself where there are no planes:
+//   t0(c) = 12 (s[y-1][c] + s[y+1][c]) + 40 s[y][c]      t1(c) = s[y+1][c] - s[y-1][c]
+//   Ix(x, y) = t0(x+1) - t0(x-1)                          Iy(x, y) = 12 (t1(x-1) + t1(x+1)) + 40 t1(x)        (|.| <= 16 320)
+// One launch covers every level >= 1 (blockIdx.x walks their tiles in level order), both cameras and the launch's sequences.  A
+// block stages DV_TH + 2 rows of DV_TW + 8 bytes in LDS with aligned dword loads (pixel (0, 0), the row starts and the tile origins
+// are 4-byte aligned; the halo lies inside the stored border); a thread then owns four consecutive samples of one row and stores
+// them as dwords.  Only samples inside the level are written: the planes' zero border stays as the allocation left it.
+#define DV_TW 64
+#define DV_TH 16
+__host__ __device__ inline int deriv_tiles(const LevelInfo& L) { return ((L.w + DV_TW - 1) / DV_TW) * ((L.h + DV_TH - 1) / DV_TH); }
+__global__ __launch_bounds__(256) void k_deriv_levels(DevBuffers d, PyrTarget target) {
+    constexpr int TDW = DV_TW / 4 + 2;                               // dwords of a staged row: one of halo on either side
+    __shared__ unsigned tile[DV_TH + 2][TDW];
+    int level = 1, t = blockIdx.x;
+    for (; level + 1 < d.geom.nlevels; level++) { const int n = deriv_tiles(d.geom.lv[level]); if (t < n) break; t -= n; }
+    const LevelInfo L = d.geom.lv[level];
+    const int w = L.w, h = L.h, tnx = (w + DV_TW - 1) / DV_TW;
+    const int ty = t / tnx, x0 = (t - ty * tnx) * DV_TW, y0 = ty * DV_TH;
+    if (y0 >= h) return;                                             // (the grid is the exact tile count: never taken)
+    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y, slot = pyr_slot(d.st[seq], target);
+    const uint8_t* __restrict__ img = d.pyr + pyr_index(d, seq, slot, cam) + L.off;
+    for (int i = threadIdx.x; i < (DV_TH + 2) * TDW; i += 256) {
+        const int r = i / TDW, c = i - r * TDW, y = y0 - 1 + r, x = x0 - 4 + 4 * c;
+        // rows -1 .. h and bytes -4 .. w + 6 are inside the stored border (pad >= 8); nothing beyond them is needed
+        tile[r][c] = (y <= h && x < w + 4) ? *reinterpret_cast<const unsigned*>(img + (ptrdiff_t)y * L.stride + x) : 0u;
+    }
+    __syncthreads();
+    const int cx = threadIdx.x & (DV_TW / 4 - 1), ry = threadIdx.x / (DV_TW / 4), x = x0 + 4 * cx, y = y0 + ry;
+    if (y >= h || x >= w) return;
+    int t0[6], t1[6];                                                // columns x - 1 .. x + 4
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        int s[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const unsigned v = c == 0 ? tile[ry + r][cx] >> 24 : c == 5 ? tile[ry + r][cx + 2] : tile[ry + r][cx + 1] >> (8 * (c - 1));
+            s[r] = (int)(v & 0xFFu);
+        }
+        t0[c] = 12 * (s[0] + s[2]) + 40 * s[1];
+        t1[c] = s[2] - s[0];
+    }
+    int ix[4], iy[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { ix[j] = t0[j + 2] - t0[j]; iy[j] = 12 * (t1[j] + t1[j + 2]) + 40 * t1[j + 1]; }
+    int16_t* __restrict__ px = d.deriv + deriv_index(d, seq, slot, cam) + (L.off - deriv_origin(d.geom)) + (ptrdiff_t)y * L.stride + x;
+    int16_t* __restrict__ py = px + deriv_samples(d.geom);
+    const auto pair = [](int lo, int hi) { return ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16); };
+    const int n = w - x;                                             // samples of this thread inside the level (>= 1)
+    if (n >= 4) {
+        *reinterpret_cast<uint2*>(px) = make_uint2(pair(ix[0], ix[1]), pair(ix[2], ix[3]));
+        *reinterpret_cast<uint2*>(py) = make_uint2(pair(iy[0], iy[1]), pair(iy[2], iy[3]));
+    } else {
+        if (n >= 2) { *reinterpret_cast<unsigned*>(px) = pair(ix[0], ix[1]); *reinterpret_cast<unsigned*>(py) = pair(iy[0], iy[1]); }
+        if (n == 1) { px[0] = (int16_t)ix[0]; py[0] = (int16_t)iy[0]; }
+        if (n == 3) { px[2] = (int16_t)ix[2]; py[2] = (int16_t)iy[2]; }
+    }
+}
+static void launch_deriv_levels(const DevBuffers& d, hipStream_t st, PyrTarget target) {
+    if (!d.deriv || d.geom.nlevels < 2) return;
+    int tiles = 0;
+    for (int l = 1; l < d.geom.nlevels; l++) tiles += deriv_tiles(d.geom.lv[l]);
+    hipLaunchKernelGGL(k_deriv_levels, dim3(tiles, 2, launch_seqs(d)), dim3(256), 0, st, d, target);
+}
+
 // levels first .. nlevels-1 from level first-1: pairs of levels per launch where two remain
 static void launch_pyramid_from(const DevBuffers& d, int first, hipStream_t st, PyrTarget target) {
     int l = first;
@@ -624,6 +690,7 @@ void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right
         launch_pyramid_from(d, 1, st, rest);
     }
     launch_pad_pyramid(d, st, rest);
+    launch_deriv_levels(d, st, rest);                                // contexts with a derivative pyramid: every pyramid they build gets its planes
 }
 
 // svo_reset_sequence: the fields the constructor sets (vo.h:266-268, svo_api.hip ctx_create) and nothing else — frame_id = 0 makes

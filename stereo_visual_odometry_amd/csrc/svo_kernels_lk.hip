@@ -222,6 +222,17 @@ __device__ __forceinline__ void load_pairs(const uint8_t* __restrict__ p, unsign
     }
 }
 
+// N int16 samples at p (2-byte aligned: a plane of the derivative pyramid) -> N-1 packed pairs: pair[x] = (v[x], v[x+1]).  The dwords
+// of one unaligned load ARE the even pairs; an odd pair is the upper half of its left neighbour next to the lower half of its right
+// one (one v_perm_b32).  Reads one sample past the N when N is odd.
+template <int N>
+__device__ __forceinline__ void load_pairs16(const int16_t* __restrict__ p, unsigned (&pair)[N - 1]) {
+    constexpr int ND = (N + 1) / 2;
+    struct __attribute__((packed, aligned(2))) UD { unsigned v[ND]; };
+    const UD u = *reinterpret_cast<const UD*>(p);
+#pragma unroll
+    for (int x = 0; x < N - 1; x++) pair[x] = (x & 1) ? hi_lo16(u.v[x >> 1], u.v[(x >> 1) + 1]) : u.v[x >> 1];
+}
 
 // ---- "float sums" mode (svo_config.lk_float_sums; deviation D1 of the oracle reverted) -----------------------------------------
 // OpenCV accumulates the LK normal equations in FLOAT, in the lane order of its SIMD128 code (lkpyramid.cpp, `#if CV_SIMD128 &&
@@ -371,8 +382,11 @@ __device__ __forceinline__ void fs_sum_b(int* __restrict__ lds, float& b1, float
 // CN = image channels: the window sums of LKTrackerInvoker run over every channel of every pixel (x < winSize.width*cn).
 // Each colour plane kk is its own single-channel pyramid (at pyr + kk * pstride), so CN = 3 simply triples the per-lane
 // pixel arrays.  FS = float-sums mode (above): fs_lds is the block's LkFs<W, CN>::LDS_INTS ints of LDS (unused otherwise).
+// derA: the Ix plane of pyrA's derivative pyramid (svo_internal.hpp; grey exact-sums builds only), or nullptr: at the levels >= 1 the
+// template's derivative pairs are then LOADED — samples k_deriv_levels computed once per frame, zero outside the level — instead
+// of being derived from four pixel rows and masked in every visit.  The same integers either way.
 template <int W, int CN, bool FS = false>
-__device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, const uint8_t* __restrict__ pyrB, size_t pstride,
+__device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, const int16_t* __restrict__ derA, const uint8_t* __restrict__ pyrB, size_t pstride,
                         float px, float py, float& outx, float& outy, int& status, const LkCrit& crit,
                         const LkSeg& sg, int& n_visits, int& n_steps, int* fs_lds = nullptr) {
     constexpr int FE = W * CN;                                          // interleaved elements per window row (float-sums mode)
@@ -386,6 +400,8 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
     float nx = 0.f, ny = 0.f;
     status = 1;
     outx = px; outy = py;
+    bool planes = false;
+    if constexpr (CN == 1 && !FS) planes = uni(derA != nullptr);
     for (int level = top; level >= 0; --level) {
         const LevelInfo L = g.lv[level];
         const uint8_t* __restrict__ A = pyrA + L.off;
@@ -425,56 +441,72 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         for (int kk = 0; kk < CN; kk++) {
             const int row = sg.row, xs = sg.xs;
             unsigned Ip[2][PPL], DXp[2][PPL], DYp[2][PPL];             // [row 0/1 of the bilinear][pixel]: packed pairs
-            // source pairs of the four rows: unaligned dword loads.  A window over the image border reads the level's REFLECT_101
-            // border, which is stored with it (Geometry::pad, k_pad_pyramid) — the same bytes the per-byte path used to gather
-            unsigned Q[4][NS - 1];
-            {
-                const uint8_t* p = Abase + (size_t)kk * pstride + (unsigned)(row * L.stride + xs);
+            if (planes && level >= 1) {
+                // the derivative planes hold every sample of the two rows (zero outside the level): two row loads per plane and two
+                // of the image, from the window's own origin
+                const unsigned lane_off = (unsigned)(row * L.stride + xs);
+                const ptrdiff_t org = (ptrdiff_t)uni_i(ipy) * L.stride + uni_i(ipx);
+                const int16_t* __restrict__ dxp = derA + (L.off - deriv_origin(g)) + org + lane_off;
+                const int16_t* __restrict__ dyp = dxp + deriv_samples(g);
+                const uint8_t* __restrict__ ip = A + org + lane_off;
 #pragma unroll
-                for (int r = 0; r < 4; r++) load_pairs<NS>(p + (unsigned)(r * L.stride), Q[r]);
-            }
+                for (int yy = 0; yy < 2; yy++) {
+                    load_pairs16<NB>(dxp + (unsigned)(yy * L.stride), DXp[yy]);
+                    load_pairs16<NB>(dyp + (unsigned)(yy * L.stride), DYp[yy]);
+                    load_pairs<NB>(ip + (unsigned)(yy * L.stride), Ip[yy]);
+                }
+            } else {
+                // source pairs of the four rows: unaligned dword loads.  A window over the image border reads the level's REFLECT_101
+                // border, which is stored with it (Geometry::pad, k_pad_pyramid) — the same bytes the per-byte path used to gather
+                unsigned Q[4][NS - 1];
+                {
+                    const uint8_t* p = Abase + (size_t)kk * pstride + (unsigned)(row * L.stride + xs);
 #pragma unroll
-            for (int yy = 0; yy < 2; yy++) {
-                // the vertical passes are evaluated on the EVEN pairs (columns 2i, 2i+1); an odd pair is the upper half of
-                // its left neighbour next to the lower half of its right one — one v_perm instead of recomputing both columns
-                ushort2v T0[NS - 1]; short2v T1[NS - 1];
-#pragma unroll
-                for (int c = 0; c < NS - 1; c++) {
-                    if ((c & 1) && c + 1 < NS - 1) continue;
-                    const ushort2v q0 = __builtin_bit_cast(ushort2v, Q[yy][c]), q1 = __builtin_bit_cast(ushort2v, Q[yy + 1][c]), q2 = __builtin_bit_cast(ushort2v, Q[yy + 2][c]);
-                    T0[c] = (q0 + q2) * (unsigned short)12 + q1 * (unsigned short)40;           // 4 x Scharr smoothing (<= 16320)
-                    T1[c] = __builtin_bit_cast(short2v, (ushort2v)(q2 - q0));
+                    for (int r = 0; r < 4; r++) load_pairs<NS>(p + (unsigned)(r * L.stride), Q[r]);
                 }
 #pragma unroll
-                for (int c = 1; c + 1 < NS - 1; c += 2) {
-                    T0[c] = __builtin_bit_cast(ushort2v, hi_lo16(__builtin_bit_cast(unsigned, T0[c - 1]), __builtin_bit_cast(unsigned, T0[c + 1])));
-                    T1[c] = __builtin_bit_cast(short2v, hi_lo16(__builtin_bit_cast(unsigned, T1[c - 1]), __builtin_bit_cast(unsigned, T1[c + 1])));
-                }
-                // horizontal passes: evaluated for the even pixels; an odd pixel's pair is again (upper half of its left
-                // neighbour's pair, lower half of its right neighbour's) — unless it is the last pixel, which is computed directly
+                for (int yy = 0; yy < 2; yy++) {
+                    // the vertical passes are evaluated on the EVEN pairs (columns 2i, 2i+1); an odd pair is the upper half of
+                    // its left neighbour next to the lower half of its right one — one v_perm instead of recomputing both columns
+                    ushort2v T0[NS - 1]; short2v T1[NS - 1];
 #pragma unroll
-                for (int x = 0; x < PPL; x++) {
-                    if ((x & 1) && x + 1 < PPL) continue;
-                    DXp[yy][x] = __builtin_bit_cast(unsigned, (ushort2v)(T0[x + 2] - T0[x]));
-                    DYp[yy][x] = __builtin_bit_cast(unsigned, (short2v)((T1[x] + T1[x + 2]) * (short)12 + T1[x + 1] * (short)40));
-                }
+                    for (int c = 0; c < NS - 1; c++) {
+                        if ((c & 1) && c + 1 < NS - 1) continue;
+                        const ushort2v q0 = __builtin_bit_cast(ushort2v, Q[yy][c]), q1 = __builtin_bit_cast(ushort2v, Q[yy + 1][c]), q2 = __builtin_bit_cast(ushort2v, Q[yy + 2][c]);
+                        T0[c] = (q0 + q2) * (unsigned short)12 + q1 * (unsigned short)40;           // 4 x Scharr smoothing (<= 16320)
+                        T1[c] = __builtin_bit_cast(short2v, (ushort2v)(q2 - q0));
+                    }
 #pragma unroll
-                for (int x = 1; x + 1 < PPL; x += 2) {
-                    DXp[yy][x] = hi_lo16(DXp[yy][x - 1], DXp[yy][x + 1]);
-                    DYp[yy][x] = hi_lo16(DYp[yy][x - 1], DYp[yy][x + 1]);
-                }
-#pragma unroll
-                for (int x = 0; x < PPL; x++) Ip[yy][x] = Q[yy + 1][x + 1];
-                if (!interior) {
-                    // the derivative image has a CONSTANT 0 border (buildOpticalFlowPyramid: derivBorder): samples outside the
-                    // level are zero, not derivatives of the reflected image
-                    const int gy = ipy + row + yy;
-                    const bool rowin = gy >= 0 && gy < L.h;
+                    for (int c = 1; c + 1 < NS - 1; c += 2) {
+                        T0[c] = __builtin_bit_cast(ushort2v, hi_lo16(__builtin_bit_cast(unsigned, T0[c - 1]), __builtin_bit_cast(unsigned, T0[c + 1])));
+                        T1[c] = __builtin_bit_cast(short2v, hi_lo16(__builtin_bit_cast(unsigned, T1[c - 1]), __builtin_bit_cast(unsigned, T1[c + 1])));
+                    }
+                    // horizontal passes: evaluated for the even pixels; an odd pixel's pair is again (upper half of its left
+                    // neighbour's pair, lower half of its right neighbour's) — unless it is the last pixel, which is computed directly
 #pragma unroll
                     for (int x = 0; x < PPL; x++) {
-                        const int gx = ipx + xs + x;
-                        const unsigned m = ((rowin && gx >= 0 && gx < L.w) ? 0x0000FFFFu : 0u) | ((rowin && gx + 1 >= 0 && gx + 1 < L.w) ? 0xFFFF0000u : 0u);
-                        DXp[yy][x] &= m; DYp[yy][x] &= m;
+                        if ((x & 1) && x + 1 < PPL) continue;
+                        DXp[yy][x] = __builtin_bit_cast(unsigned, (ushort2v)(T0[x + 2] - T0[x]));
+                        DYp[yy][x] = __builtin_bit_cast(unsigned, (short2v)((T1[x] + T1[x + 2]) * (short)12 + T1[x + 1] * (short)40));
+                    }
+#pragma unroll
+                    for (int x = 1; x + 1 < PPL; x += 2) {
+                        DXp[yy][x] = hi_lo16(DXp[yy][x - 1], DXp[yy][x + 1]);
+                        DYp[yy][x] = hi_lo16(DYp[yy][x - 1], DYp[yy][x + 1]);
+                    }
+#pragma unroll
+                    for (int x = 0; x < PPL; x++) Ip[yy][x] = Q[yy + 1][x + 1];
+                    if (!interior) {
+                        // the derivative image has a CONSTANT 0 border (buildOpticalFlowPyramid: derivBorder): samples outside the
+                        // level are zero, not derivatives of the reflected image
+                        const int gy = ipy + row + yy;
+                        const bool rowin = gy >= 0 && gy < L.h;
+#pragma unroll
+                        for (int x = 0; x < PPL; x++) {
+                            const int gx = ipx + xs + x;
+                            const unsigned m = ((rowin && gx >= 0 && gx < L.w) ? 0x0000FFFFu : 0u) | ((rowin && gx + 1 >= 0 && gx + 1 < L.w) ? 0xFFFF0000u : 0u);
+                            DXp[yy][x] &= m; DYp[yy][x] &= m;
+                        }
                     }
                 }
             }
@@ -704,13 +736,15 @@ LkCrit lk_make_crit(const svo_config& c, const Geometry& g) {
 //   1.8 % slower: default 4.  (An XCD-affine form, XCD x walking the sequences x, x + 8, ... one at a time, fetched least,
 //   39 MB, but took 2.02 ms; it was removed.)
 // The four passes of ONE feature and its masks: one inlined copy inside k_lk_chain (profiles/experiments/lk_queue_fed_persistent.patch fed the same function from a work queue).
-struct LkSeqCtx { const uint8_t *L0, *R0, *L1, *R1; int seq, buf; };
+// p0 / p1: the pyramid number (sequence, slot, camera 0) of the T0 / T1 pair; the right camera's is the next one.  Numbers, not the
+// four pointers (and the four of their derivative planes): two scalar registers held through lk_pass instead of sixteen.
+struct LkSeqCtx { int p0, p1, seq, buf; };
 template <int W, int CN, bool FS>
 __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSeqCtx& q, int idx, const LkSeg& sg, int early_out, int* fs_lds) {
     const LkCrit& crit = d.lk_crit;
     const float thr = crit.thr, Wf = crit.Wf, Hf = crit.Hf;
     const int seq = q.seq;
-    const uint8_t *L0 = q.L0, *R0 = q.R0, *L1 = q.L1, *R1 = q.R1;
+    const int16_t* const dv = (CN == 1 && !FS) ? d.deriv : nullptr;
     const size_t o = (size_t)seq * d.CAP + idx;
     const float2 p0 = d.feat_xy[q.buf][o];                  // pointsLeftT0 = currentVOFeatures.points (vo.cpp:338)
     // the four passes share ONE inlined copy of lk_pass (a loop, not four copies): 4x less code in the instruction cache.
@@ -727,11 +761,15 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
     if (writer) d.pl0[o] = p0;
 #pragma unroll 1
     for (int pass = 0; pass < 4; pass++) {
-        const uint8_t* A = pass == 0 ? L0 : pass == 1 ? L1 : pass == 2 ? R1 : R0;      // vo.cpp:203, 206, 209, 213
-        const uint8_t* Bq = pass == 0 ? L1 : pass == 1 ? R1 : pass == 2 ? R0 : L0;
+        const int na = pass == 0 ? q.p0 : pass == 1 ? q.p1 : pass == 2 ? q.p1 + 1 : q.p0 + 1;      // L0, L1, R1, R0 (vo.cpp:203, 206, 209, 213)
+        const int nb = pass == 0 ? q.p1 : pass == 1 ? q.p1 + 1 : pass == 2 ? q.p0 + 1 : q.p0;      // L1, R1, R0, L0
+        const size_t pbytes = (size_t)CN * (size_t)d.geom.pyr_bytes;
+        const uint8_t* A = d.pyr + (size_t)na * pbytes;
+        const uint8_t* Bq = d.pyr + (size_t)nb * pbytes;
+        const int16_t* dA = dv ? dv + (size_t)na * 2 * (size_t)deriv_samples(d.geom) : nullptr;
         float2* out = pass == 0 ? d.pl1 : pass == 1 ? d.pr1 : pass == 2 ? d.pr0 : d.plc;
         float2 q; int st;
-        lk_pass<W, CN, FS>(d.geom, A, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds);
+        lk_pass<W, CN, FS>(d.geom, A, dA, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds);
         if (pass < 3 && ((q.x < 0) || (q.y < 0) || (q.y >= Hf) || (q.x >= Wf))) flags &= ~2;     // pl1, pr1, pr0 (not the returned point)
         if (writer) out[o] = q;
         cur = q;
@@ -802,11 +840,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_e
     int n = s.n_feat;
     if (d.cfg.max_features > 0 && n > d.cfg.max_features) n = d.cfg.max_features;
     if (fb == 0 && threadIdx.x == 0) s.n_lk = n;
-    const uint8_t* L0 = d.pyr + pyr_index(d, seq, s.slot_pyr_t0, 0);
-    const uint8_t* R0 = d.pyr + pyr_index(d, seq, s.slot_pyr_t0, 1);
-    const uint8_t* L1 = d.pyr + pyr_index(d, seq, s.slot_t1, 0);
-    const uint8_t* R1 = d.pyr + pyr_index(d, seq, s.slot_t1, 1);
-    const LkSeqCtx sc = {L0, R0, L1, R1, seq, s.feat_buf};
+    const LkSeqCtx sc = {(seq * SVO_PYR_SLOTS + s.slot_pyr_t0) * 2, (seq * SVO_PYR_SLOTS + s.slot_t1) * 2, seq, s.feat_buf};   // pyr_index / deriv_index in units of one pyramid
     const LkSeg sg = lk_segment<W>();
     // this block's feature in every round of `slots`: the r-th block of XCD x works in that XCD's q-th run.  slots is a multiple
     // of 8 * chunk, so fb & 7 == blockIdx.x & 7 is the XCD and f runs over 0 .. slots - 1 once as fb does
@@ -825,7 +859,7 @@ __global__ __launch_bounds__(64) void k_lk_single(DevBuffers d, int slotA, int c
     const LkSeg sg = lk_segment<W>();
     for (int idx = blockIdx.x; idx < n; idx += gridDim.x) {
         float2 p = prev[idx], q; int st, nv = 0, ns = 0;
-        lk_pass<W, 1>(d.geom, A, Bp, 0, p.x, p.y, q.x, q.y, st, d.lk_crit, sg, nv, ns);
+        lk_pass<W, 1>(d.geom, A, nullptr, Bp, 0, p.x, p.y, q.x, q.y, st, d.lk_crit, sg, nv, ns);
         if (threadIdx.x == 0) { next[idx] = q; status[idx] = (uint8_t)st; }
     }
 }

@@ -1,0 +1,135 @@
+"""The LK kernel reading the Scharr derivatives of the pyramid levels >= 1 from the per-frame derivative pyramid (k_deriv_levels,
+many-sequence grey contexts) instead of differentiating every window: every case runs a context of nine or more sequences, so the
+many-sequence front builds the planes, and is compared with the CPU oracle — ok flags, every field of svo_frame_stats (the level
+visit and Newton step counters among them) and the surviving feature sets exactly, the pose as tests/test_gpu_parity.py compares
+it — and, byte for byte including the pose, with the same run in a fresh process under SVO_LK_DERIV=0 (no planes: the kernel
+differentiates in registers).  Scenes and runs: tests/lk_deriv_child.py.
+
+Origins at exactly -W and size - 1 cannot be planted through the frame pipeline (FAST keeps three pixels from the image edge and the
+origin of a window is where Newton's iteration takes it); the `borders` scene offers features inside w of all four borders and corners
+with a camera fast enough that tracks leave the frame, and the test checks both."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as orc
+import lk_deriv_child as ldc
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+POSE_TOL = 1e-6          # as tests/test_gpu_parity.py: the f64 pose stage is not part of this change
+
+
+@pytest.fixture(scope="module")
+def api():
+    from stereo_visual_odometry_amd import api as a
+    assert a._lib.device_count() >= 1, "no HIP device"
+    return a
+
+
+@pytest.fixture(scope="module")
+def default_runs(api):
+    """every run of lk_deriv_child in this process (planes on), once for the module"""
+    assert os.environ.get("SVO_LK_DERIV", "1") != "0"
+    return ldc.everything(api)
+
+
+def oracle_frames(name, frames_of_stream, n_streams=2):
+    """per stream, per frame: (ok, T, stats, features) of a fresh oracle fed `frames_of_stream(stream)` [(L, R)]"""
+    out = []
+    for s in range(n_streams):
+        o = orc.VisualOdometry(orc.default_config(**ldc.config_over(name))); o.initalize_projection_matricies(*ldc.projections(name))
+        per = []
+        for L, R in frames_of_stream(s):
+            ok, T = o.stereo_callback(L, R)
+            st = {f[0]: getattr(o.stats, f[0]) for f in o.stats._fields_}
+            per.append((ok, T.reshape(16).copy(), np.array([st[k] for k in sorted(st)], np.int64), [a.copy() for a in o.features()]))
+        out.append(per)
+    return out
+
+
+def same_as_oracle(got, prefix, want, feats=True):
+    ok, T, st, f = want
+    assert bool(got[prefix + "/ok"][0]) == ok, prefix
+    assert np.array_equal(got[prefix + "/stats"], st), (prefix, got[prefix + "/stats"], st)
+    dT = np.abs(got[prefix + "/T"] - T).max()
+    assert dT < POSE_TOL, (prefix, dT)
+    if feats:
+        assert np.array_equal(got[prefix + "/xy"], f[0].view(np.uint32)) and np.array_equal(got[prefix + "/age"], f[1]) and np.array_equal(got[prefix + "/strength"], f[2]), prefix
+
+
+@pytest.mark.parametrize("name", ["four_levels", "small_window", "odd", "borders"])
+def test_scene_equals_the_oracle(api, default_runs, name):
+    sq = ldc.streams(name)
+    want = oracle_frames(name, lambda s: [(sq[s].left[k], sq[s].right[k]) for k in range(ldc.N_FRAMES)])
+    from stereo_visual_odometry_amd import _lib
+    assert all(int(p) & _lib.PATH_INGEST_AHEAD for p in default_runs[name + "/paths"]), "the many-sequence front did not run"
+    for k in range(ldc.N_FRAMES):
+        for i in range(ldc.B):
+            same_as_oracle(default_runs, "%s/%d/%d" % (name, k, i), want[i % 2][k])
+    assert want[0][-1][0] and want[1][-1][0], "the oracle returned no pose: the comparison would be vacuous"
+    if name == "borders":
+        w, h = ldc.SCENES[name][:2]
+        W = ldc.SCENES[name][2]["win_w"]
+        near = np.zeros(8, int)
+        for s in sq:
+            for k in range(ldc.N_FRAMES):
+                xy = orc.fast_detect(s.left[k], 20)[0]
+                x, y = xy[:, 0], xy[:, 1]
+                le, ri, to, bo = x < W, x > w - 1 - W, y < W, y > h - 1 - W
+                near += [le.sum(), ri.sum(), to.sum(), bo.sum(), (le & to).sum(), (ri & to).sum(), (le & bo).sum(), (ri & bo).sum()]
+        assert (near > 0).all(), near
+        names = sorted(f[0] for f in orc.OrcFrameStats._fields_)
+        dead = sum(int(want[s][k][2][names.index(n)]) for s in range(2) for k in range(ldc.N_FRAMES) for n in names if n.startswith("lk_dead"))
+        assert dead > 0, "no track left its level: the out-of-reach exits were not exercised"
+
+
+def test_three_frames_in_flight_with_reset_and_idle_mask(api, default_runs):
+    """Planes follow their pyramid slots: device images three frames ahead, two masked frames, one sequence reset in between."""
+    sq = ldc.streams(ldc.FL_NAME, n=2, n_frames=ldc.FL_FRAMES)
+    masks, fed = ldc.flight_plan()
+    vos = {}
+
+    def fresh():
+        o = orc.VisualOdometry(orc.default_config(**ldc.config_over(ldc.FL_NAME))); o.initalize_projection_matricies(*ldc.projections(ldc.FL_NAME))
+        return o
+
+    tracked = 0
+    names = None
+    for k in range(ldc.FL_FRAMES):
+        for i in range(ldc.FL_B):
+            if k == ldc.FL_RESET_BEFORE and i == ldc.FL_RESET_SEQ:
+                vos[i] = fresh()
+            o = vos.setdefault(i, fresh())
+            j = fed[k][i]
+            prefix = "flight/%d/%d" % (k, i)
+            if j is None:
+                assert not default_runs[prefix + "/ok"][0]
+                continue
+            ok, T = o.stereo_callback(sq[i % 2].left[j], sq[i % 2].right[j])
+            st = {f[0]: getattr(o.stats, f[0]) for f in o.stats._fields_}
+            names = sorted(st)
+            same_as_oracle(default_runs, prefix, (ok, T.reshape(16), np.array([st[n] for n in names], np.int64), None), feats=False)
+            tracked += st["n_into_lk"] > 20
+    assert tracked > ldc.FL_B * 3
+    for i in range(ldc.FL_B):
+        f = vos[i].features()
+        p = "flight/end/%d" % i
+        assert np.array_equal(default_runs[p + "/xy"], f[0].view(np.uint32)) and np.array_equal(default_runs[p + "/age"], f[1]) and np.array_equal(default_runs[p + "/strength"], f[2]), i
+
+
+def test_switch_off_is_byte_equal(api, default_runs, tmp_path):
+    """SVO_LK_DERIV=0 in a fresh process: the same bytes from every run above, the same svo_get_last_frame_path."""
+    out = str(tmp_path / "off.npz")
+    env = dict(os.environ, SVO_LK_DERIV="0")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "lk_deriv_child.py"), out], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "lk deriv child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    off = np.load(out)
+    assert sorted(off.files) == sorted(default_runs)
+    for key in off.files:
+        a, b = off[key], default_runs[key]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), key
