@@ -163,6 +163,7 @@ int svo_get_lk_registers_left(svo_context* ctx);
 #define SVO_PATH_TRI_EPNP_FUSED 16   /* triangulation and the first EPnP chunk in one launch (lone stream) */
 #define SVO_PATH_GRAPH          32   /* the frame replayed a captured hipGraph (SVO_GRAPH=1); the other bits are the capture's */
 #define SVO_PATH_INPUT_CONVERTED 64  /* the frame's ingest converted the caller's pixels to grey (svo_set_input_format) */
+#define SVO_PATH_POSE_COV       128  /* the frame ran k_pose_cov after its refine (svo_set_pose_covariance; also set by svo_pose_covariance) */
 int svo_get_last_frame_path(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
@@ -282,6 +283,42 @@ int svo_clear_rectification(svo_context* ctx);
  * what a slot's graph is keyed on, so a format switch re-captures); results are identical to the launch list's. */
 int svo_set_input_format(svo_context* ctx, int format);
 
+/* ---- Pose covariance ------------------------------------------------------------------------------------------------------
+ * A 6x6 covariance with every pose, computed on the device right after the refine and written into the results ring beside the
+ * pose: no extra copy, no extra synchronisation, valid with frames in flight.  Off by default; mode 0 launches exactly what a
+ * context that never called the setter launches, and no other result of a frame changes by a bit in any mode.
+ *
+ * Definition, for a frame with ok = 1.  p^ = (r^, t^): the rotation vector and translation of the refined solvePnP result (the
+ * cameraToWorld parameters; the returned T = [R^ t^; 0 1]^-1).  The inliers are the m tracks with inlier[i] = 1 of
+ * svo_get_last_tracks; X_i = world[i], u_i = pl1[i], both f32 widened to f64.
+ *   residuals   e_i(p) = pi(R(r) X_i + t) - u_i,   pi(x, y, z) = (fx x / z + cx, fy y / z + cy), fx fy cx cy of K = Pl[:, :3]
+ *   J           the 2m x 6 Jacobian of e with respect to (r, t) at p^ (what the refine's own iterations form);  H = Jt J
+ *   sigma^2     SVO_COV_RESIDUAL: |e(p^)|^2 / (2m - 6);   SVO_COV_FIXED_SIGMA: pixel_sigma^2
+ *   cov_p       sigma^2 H^-1: 6x6 row-major in the order (r0 r1 r2 t0 t1 t2), the covariance of the cameraToWorld parameters
+ *   cov_T       G cov_p Gt: the covariance of the returned T in the order (c0 c1 c2 phi0 phi1 phi2) — position first, as ROS orders
+ *               a pose covariance.  c = -R(r)t t is T's translation column, phi the LEFT perturbation of its rotation block,
+ *               R_out = Exp(phi) R^t.  With c^ = -R^t t^ and the right Jacobian of SO(3)
+ *               Jr(r) = I - (1 - cos th) / th^2 [r]x + (th - sin th) / th^3 [r]x^2   (I - [r]x / 2 for th < 1e-9):
+ *                   G = [ [c^]x Jr(r^)   -R^t ]
+ *                       [    -Jr(r^)       0  ]
+ *   valid = 1   iff ok = 1, m >= 3 (H has rank <= 2m), 2m - 6 > 0 in mode SVO_COV_RESIDUAL, and every Cholesky pivot of H is
+ *               positive — more than 2^-40 of the diagonal entry it is what is left of, so that the rounding noise of a singular H
+ *               does not pass for a pivot.  Otherwise valid = 0 and all 72 numbers are 0.0: failed frames (fail_reason 1-4) and
+ *               idle sequences (fail_reason 5) included.
+ * All arithmetic is f64.  The 96-register build sums in the order of the full one: identical bits either way. */
+#define SVO_COV_OFF 0
+#define SVO_COV_RESIDUAL 1      /* sigma^2 = |e|^2 / (2m - 6) */
+#define SVO_COV_FIXED_SIGMA 2   /* sigma = pixel_sigma */
+/* Set the mode of the frames submitted from now on (legal with frames in flight: every frame carries the mode it was issued with,
+ * as it carries its input format; under SVO_GRAPH=1 a switch re-captures the slot's graph).  A bad mode, or SVO_COV_FIXED_SIGMA
+ * with pixel_sigma <= 0 or not finite: SVO_ERR_ARG (pixel_sigma is not looked at in the other modes). */
+int svo_set_pose_covariance(svo_context* ctx, int mode, double pixel_sigma);
+/* The covariances of the last COLLECTED frame (svo_collect, svo_process*): cov_T and cov_p B x 36 doubles, valid B ints; each may
+ * be NULL.  SVO_ERR_STATE if that frame was issued with SVO_COV_OFF or none was collected yet.  Host memory only: no device
+ * access, no synchronisation.  A frame on which every sequence was idle launches nothing: its rows are zero with valid = 0 as
+ * for any idle sequence, and svo_get_last_frame_path reports 0 for it — without SVO_PATH_POSE_COV — whatever the mode. */
+int svo_get_last_pose_covariance(svo_context* ctx, double* cov_T, double* cov_p, int* valid);
+
 /* Introspection (parity tests): currentVOFeatures (vo.h:245) of one sequence, and the last frame's
  * compacted tracks.  Arrays may be NULL.  Returns the count or a negative status.  inlier[] is the is_ok vector of vo.cpp:115-119:
  * all zero when the frame failed before it was built (RANSAC failure or fewer inliers than features_threshold, vo.cpp:106-113). */
@@ -386,6 +423,15 @@ int svo_triangulate(int device, const float Pl[12], const float Pr[12], int n, c
 int svo_camera_to_world(int device, const float K[9], int n, const float* cam_pts, const float* world_pts,
                         double R[9], double t[3], int* inliers, int* n_inliers, int* success,
                         int ransac_iterations, float reproj_error, float confidence, int* iters_run);
+
+/* The pose covariance of the section above for one point set and one pose, on the frame pipeline's device function: the
+ * counterpart of svo_camera_to_world, taking its inputs (K, cam_pts n x 2 f32, world_pts n x 3 f32) and its outputs R and t.
+ * inliers: n FLAGS (non-zero = the point counts), NULL = every point — NOT svo_camera_to_world's list of n_inliers indices:
+ * set flags[index[k]] = 1 for k < n_inliers first.  mode SVO_COV_RESIDUAL or SVO_COV_FIXED_SIGMA.  cov_p, cov_T (36 doubles each) and valid may be
+ * NULL.  n < 1 or a bad mode / pixel_sigma: SVO_ERR_ARG; a singular H is valid = 0 and zeros, not an error. */
+int svo_pose_covariance(int device, const float K[9], int n, const float* cam_pts, const float* world_pts,
+                        const int* inliers, const double R[9], const double t[3],
+                        int mode, double pixel_sigma, double cov_p[36], double cov_T[36], int* valid);
 
 /* replaces: cv::initUndistortRectifyMap(K, D, R, P[:, :3], (w, h), CV_16SC2, map1, map2) (the map half of
  * image_geometry::PinholeCameraModel::rectifyImage).  Host only, f64, no device needed.  The scalar loop restated exactly

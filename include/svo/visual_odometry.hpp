@@ -191,6 +191,7 @@ class VisualOdometry {                                               // include/
             svo_throw(svo_set_projection(ctx_, -1, leftCameraProjection_.data(), rightCameraProjection_.data()));
             if (rect_) apply_rectification();
             if (in_format_ != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx_, in_format_));
+            if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
         }
         check_frame(image_left, "left"); check_frame(image_right, "right");
         Mat44 T;
@@ -282,6 +283,27 @@ class VisualOdometry {                                               // include/
         in_format_ = format;
     }
 
+    // A 6x6 covariance with every pose from the next frame on (svo_set_pose_covariance): mode SVO_COV_RESIDUAL (sigma^2 from the
+    // frame's own reprojection residuals), SVO_COV_FIXED_SIGMA (sigma = pixel_sigma pixels) or SVO_COV_OFF.  A bad mode or sigma throws.
+    void set_pose_covariance(int mode, double pixel_sigma = 1.0) {
+        if (ctx_) svo_throw(svo_set_pose_covariance(ctx_, mode, pixel_sigma));
+        else if ((mode != SVO_COV_OFF && mode != SVO_COV_RESIDUAL && mode != SVO_COV_FIXED_SIGMA) ||
+                 (mode == SVO_COV_FIXED_SIGMA && !(pixel_sigma > 0 && std::isfinite(pixel_sigma))))
+            throw std::runtime_error("set_pose_covariance: bad mode or pixel_sigma");
+        cov_mode_ = mode; cov_sigma_ = pixel_sigma;
+    }
+    // Of the last stereo_callback (svo_get_last_pose_covariance): cov_T, the covariance of the returned transform in the order
+    // (x y z, rotation about x y z) of nav_msgs/Odometry.pose.covariance, and cov_p, that of the cameraToWorld parameters (r, t);
+    // both row-major 6x6, all zero with valid = false when the frame gave no pose.  Throws when the frame ran with the mode off.
+    struct PoseCovariance { std::array<double, 36> cov_T, cov_p; bool valid; };
+    PoseCovariance last_pose_covariance() const {
+        if (!ctx_) throw std::runtime_error("last_pose_covariance: no frame yet (call stereo_callback first)");
+        PoseCovariance c; int valid = 0;
+        svo_throw(svo_get_last_pose_covariance(ctx_, c.cov_T.data(), c.cov_p.data(), &valid));
+        c.valid = valid != 0;
+        return c;
+    }
+
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
 
@@ -311,6 +333,7 @@ class VisualOdometry {                                               // include/
     svo_camera_info rect_l_{}, rect_r_{};
     int raw_w_ = 0, raw_h_ = 0;                                       // raw frame size while rectifying, else 0
     int in_format_ = SVO_INPUT_MONO8;                                 // set_input_encoding (applied once the context exists)
+    int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
 };
 
 }   // namespace visual_odometry

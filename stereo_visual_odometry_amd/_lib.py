@@ -82,6 +82,17 @@ lib.svo_get_last_frame_path.argtypes = [C.c_void_p]
 # svo_get_last_frame_path bits (svo.h SVO_PATH_*)
 PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
 PATH_INPUT_CONVERTED = 64
+PATH_POSE_COV = 128
+# pose covariance (svo.h SVO_COV_*): cov_T / cov_p are n_seq x 36 doubles, valid n_seq ints
+COV_OFF, COV_RESIDUAL, COV_FIXED_SIGMA = 0, 1, 2
+COV_MODES = {"off": COV_OFF, "residual": COV_RESIDUAL, "fixed": COV_FIXED_SIGMA}
+lib.svo_set_pose_covariance.restype = C.c_int
+lib.svo_set_pose_covariance.argtypes = [C.c_void_p, C.c_int, C.c_double]
+lib.svo_get_last_pose_covariance.restype = C.c_int
+lib.svo_get_last_pose_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_pose_covariance.restype = C.c_int
+lib.svo_pose_covariance.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
 # input formats (svo.h SVO_INPUT_*): what the bytes of the caller's frames are; the sensor_msgs encoding names map onto them
 INPUT_MONO8, INPUT_BGR8, INPUT_RGB8, INPUT_BGRA8, INPUT_RGBA8, INPUT_UYVY, INPUT_YUY2 = range(7)
 INPUT_ENCODINGS = {"mono8": INPUT_MONO8, "bgr8": INPUT_BGR8, "rgb8": INPUT_RGB8, "bgra8": INPUT_BGRA8, "rgba8": INPUT_RGBA8,
@@ -125,6 +136,7 @@ EXPORTS = [
     "svo_find_close_points", "svo_stage_cache_clear", "svo_stage_cache_clear_all", "svo_triangulate", "svo_camera_to_world", "svo_inverse_transform",
     "svo_set_rectification_maps", "svo_set_rectification", "svo_clear_rectification", "svo_init_rectify_map", "svo_rectify_image",
     "svo_set_input_format", "svo_convert_gray",
+    "svo_set_pose_covariance", "svo_get_last_pose_covariance", "svo_pose_covariance",
 ]
 
 
@@ -175,6 +187,25 @@ def u8frame(img, bpp=None):
     elif not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
         raise ValueError("8-bit (H, W) or (H, W, 3) image expected")
     return img
+
+
+def cov_mode(mode):
+    """An SVO_COV_* constant or "off" / "residual" / "fixed" -> the constant (the library checks the range)."""
+    if isinstance(mode, str):
+        if mode not in COV_MODES:
+            raise ValueError("unknown pose-covariance mode %r (one of %s)" % (mode, ", ".join(COV_MODES)))
+        return COV_MODES[mode]
+    return int(mode)
+
+
+def check_cov(mode, pixel_sigma):
+    """(mode, pixel_sigma) as svo_set_pose_covariance checks them -> (constant, float); ValueError otherwise."""
+    m, s = cov_mode(mode), float(pixel_sigma)
+    if m not in COV_MODES.values():
+        raise ValueError("unknown pose-covariance mode %r" % (mode,))
+    if m == COV_FIXED_SIGMA and not (s > 0 and np.isfinite(s)):
+        raise ValueError("pixel_sigma must be positive and finite")
+    return m, s
 
 
 def input_format(fmt):

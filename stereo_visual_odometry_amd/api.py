@@ -95,6 +95,39 @@ def cameraToWorld(cameraProjection, cameraPoints, worldPoints, rotation, transla
     return (inl[:nin.value].copy(), bool(ok.value)), R.reshape(3, 3), t.reshape(3, 1), iters.value
 
 
+def poseCovariance(cameraProjection, cameraPoints, worldPoints, rotation, translation, inliers=None, mode="residual",
+                   pixel_sigma=1.0, device=0, inlier_indices=None):
+    """svo_pose_covariance: the 6x6 covariances of a cameraToWorld result (its inputs, its R and t) -> (cov_p, cov_T, valid).
+    The points that count: inliers = n FLAGS, or inlier_indices = the index list cameraToWorld returns (one of the two; neither =
+    every point).  cov_p is in the order (r, t) of the cameraToWorld parameters, cov_T in the order (position,
+    rotation) of the inverse transform getInverseTransform(R, t), as ROS orders a pose covariance.  A singular system gives
+    valid False and zeros."""
+    K = np.ascontiguousarray(cameraProjection, np.float32).reshape(-1)[:9].copy() if np.size(cameraProjection) == 9 else \
+        np.ascontiguousarray(np.asarray(cameraProjection, np.float32)[:3, :3]).reshape(9)
+    cam = _pts(cameraPoints)
+    world = np.ascontiguousarray(worldPoints, np.float32).reshape(-1, 3)
+    if len(world) != len(cam):
+        raise ValueError("cameraPoints and worldPoints differ in length")
+    R = np.ascontiguousarray(rotation, np.float64).reshape(9)
+    t = np.ascontiguousarray(translation, np.float64).reshape(3)
+    inl = None
+    if inlier_indices is not None:
+        if inliers is not None:
+            raise ValueError("give inliers (flags) or inlier_indices, not both")
+        idx = np.asarray(inlier_indices, np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(cam)):
+            raise ValueError("inlier_indices out of range")
+        inliers = np.zeros(len(cam), bool); inliers[idx] = True
+    if inliers is not None:
+        inl = np.ascontiguousarray(np.asarray(inliers).astype(bool), np.int32)
+        if inl.shape != (len(cam),):
+            raise ValueError("inliers must hold one flag per point")
+    cov_p, cov_T, valid = np.zeros(36), np.zeros(36), C.c_int(0)
+    check(lib.svo_pose_covariance(device, ptr(K), len(cam), ptr(cam), ptr(world), ptr(inl), ptr(R), ptr(t), _lib.cov_mode(mode),
+                                  float(pixel_sigma), ptr(cov_p), ptr(cov_T), C.byref(valid)))
+    return cov_p.reshape(6, 6), cov_T.reshape(6, 6), bool(valid.value)
+
+
 def last_stage_path():
     """svo_get_last_frame_path(NULL): the SVO_PATH_* bits of this thread's last triangulatePoints / cameraToWorld call."""
     return lib.svo_get_last_frame_path(None)
@@ -358,6 +391,21 @@ class BatchVisualOdometry:
         check(lib.svo_set_input_format(self._h, f))
         self.input_format = f
 
+    def set_pose_covariance(self, mode="residual", pixel_sigma=1.0):
+        """A 6x6 covariance with every pose from the next frame submitted on (svo_set_pose_covariance).  mode: "residual" (sigma^2
+        from the frame's own reprojection residuals), "fixed" (sigma = pixel_sigma pixels), "off", or an SVO_COV_* constant.
+        Legal with frames in flight: every frame carries the mode it was issued with.  Read with last_pose_covariance()."""
+        check(lib.svo_set_pose_covariance(self._h, _lib.cov_mode(mode), float(pixel_sigma)))
+
+    def last_pose_covariance(self):
+        """Of the last collected frame -> (cov_T (n_seq, 6, 6), cov_p (n_seq, 6, 6), valid (n_seq,) bool).  cov_T: the returned T,
+        in the order (position, rotation) of a ROS pose covariance; cov_p: the cameraToWorld parameters (r, t).  Rows without a pose
+        (failed frames, idle sequences) are zero with valid False.  SvoError when that frame was issued with the mode off."""
+        cov_T, cov_p = np.zeros((self.n_seq, 36)), np.zeros((self.n_seq, 36))
+        valid = np.zeros(self.n_seq, np.int32)
+        check(lib.svo_get_last_pose_covariance(self._h, ptr(cov_T), ptr(cov_p), ptr(valid)))
+        return cov_T.reshape(-1, 6, 6), cov_p.reshape(-1, 6, 6), valid.astype(bool)
+
     def set_rectification(self, left_info, right_info, seq=-1):
         """Rectify raw frames with these calibrations (svo_set_rectification): `seq` (-1: the shared maps of every sequence
         without its own).  Frames passed from now on are raw (left_info's width x height).  The projection matrices are NOT
@@ -547,6 +595,7 @@ class VisualOdometry(BatchVisualOdometry):
         self._P = None
         self._timing = None
         self._rect = None                             # rectification asked for before the context exists: applied at creation
+        self._cov = None                              # likewise a pose-covariance mode
         self.raw_size = None
         if not self._created:
             self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
@@ -583,6 +632,16 @@ class VisualOdometry(BatchVisualOdometry):
             return super().set_input_format(fmt)
         self.input_format = _lib.input_format(fmt)
 
+    def set_pose_covariance(self, mode="residual", pixel_sigma=1.0):
+        if self._created:
+            return super().set_pose_covariance(mode, pixel_sigma)
+        self._cov = _lib.check_cov(mode, pixel_sigma)                 # checked now, as the library will: not inside the first frame
+
+    def last_pose_covariance(self):
+        if not self._created:
+            raise _lib.SvoError("last_pose_covariance: no frame yet (call stereo_callback first)")
+        return super().last_pose_covariance()
+
     def stereo_callback(self, image_left, image_right):
         fmt = self.input_format
         bpp = _lib.INPUT_BPP[fmt] if fmt != _lib.INPUT_MONO8 else None
@@ -610,6 +669,8 @@ class VisualOdometry(BatchVisualOdometry):
                 super().set_stage_timing(self._timing)
             if fmt != _lib.INPUT_MONO8:
                 super().set_input_format(fmt)         # (BatchVisualOdometry.__init__ reset the attribute)
+            if self._cov is not None:
+                super().set_pose_covariance(*self._cov)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

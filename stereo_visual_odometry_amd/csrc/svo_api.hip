@@ -83,9 +83,11 @@ static void make_geometry(Geometry& g, int W, int H, int win, int max_level, int
 
 // One slot of the results ring: everything a frame in flight owns besides its rows of the [SVO_RING][2 B] tables (ring_row).
 enum StageEvent { EV_F0, EV_PYR, EV_LK0, EV_LK1, EV_TRI, EV_DONE, EV_COUNT };   // stage boundaries, in svo_get_stage_timing's order
-struct GraphKey {                                // what a slot's graph was captured with (image stride, LK grid, co-resident builds, input format)
-    int stride, gn, co, fmt;
-    bool operator==(const GraphKey& o) const { return stride == o.stride && gn == o.gn && co == o.co && fmt == o.fmt; }
+struct GraphKey {                                // what a slot's graph was captured with (image stride, LK grid, co-resident builds, input format, covariance mode)
+    int stride, gn, co, fmt, cov; double cov_sigma2;
+    bool operator==(const GraphKey& o) const {
+        return stride == o.stride && gn == o.gn && co == o.co && fmt == o.fmt && cov == o.cov && (cov != SVO_COV_FIXED_SIGMA || cov_sigma2 == o.cov_sigma2);
+    }
 };
 struct RingSlot {
     hipEvent_t ev[EV_COUNT] = {};                // EV_F0 and EV_DONE always recorded, the four between on request (stage_timing)
@@ -94,6 +96,8 @@ struct RingSlot {
     GraphKey key = {};
     int g_path = 0;                              // the SVO_PATH_* bits of that capture
     bool staged = false;                         // the slot's stage events were recorded (launch-list mode only)
+    int cov_mode = SVO_COV_OFF;                  // the pose-covariance mode the slot's frame was issued with
+    bool masked = false;                         // ... and whether it came with a mask (h_act's row then holds its flags)
 };
 
 struct svo_context {
@@ -144,6 +148,14 @@ struct svo_context {
     // kernels are chosen at issue time and take `in` as arguments, so every frame carries its own format.
     int in_format = SVO_INPUT_MONO8;
     GreyIn in = {};
+    // pose covariance (svo_set_pose_covariance): the mode and sigma^2 of the frames submitted from now on — host state like the input
+    // format, so every frame carries its own (RingSlot::cov_mode).  The pinned ring is allocated when a mode is first switched on.
+    int cov_mode = SVO_COV_OFF;
+    double cov_sigma2 = 1.;
+    PoseCovRow* h_cov = nullptr;                 // pinned [SVO_RING][B], written by k_pose_cov in place (mapped like h_results)
+    PoseCovRow* d_cov = nullptr;                 // its device address
+    std::vector<PoseCovRow> last_cov;            // [B] the rows of the last collected frame ...
+    int last_cov_mode = SVO_COV_OFF;             // ... and the mode it was issued with
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -316,7 +328,7 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
-    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps}) if (p) (void)hipHostFree(p);
+    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps, (void*)c->h_cov}) if (p) (void)hipHostFree(p);
     for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
     for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
     for (const auto& r : c->retired) (void)hipFree(r.p);
@@ -425,7 +437,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     }
     HIPCHK(choose_pnp_build(c->d, share.lean));
     const DevBuffers f = frame_view(c, slot, n_act);                   // after the build choice: co_resident travels in the view
-    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0);
+    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0);
     const uint8_t** dp = ring_row(c, f.img_ptrs, slot);                // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(f);
     bool detected = false;
@@ -463,6 +475,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     else launch_triangulate(f, s);
     HIPCHK(record(EV_TRI));                                            // (fused: the stage timers count that chunk with the triangulation)
     launch_pnp(f, s, tri_epnp);
+    if (c->cov_mode) launch_pose_cov(f, CovArgs{c->d_cov + (size_t)slot * c->d.B, c->cov_mode, c->cov_sigma2}, s);   // into the pinned ring, like the record below
     launch_frame_end(f, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
     c->last_path = path;
     return SVO_OK;
@@ -529,7 +542,7 @@ static int replay_graph(svo_context* c, int slot, int stride, int gn, DeviceShar
     hipStream_t s = c->stream;
     RingSlot& r = c->ring[slot];
     HIPCHK(choose_pnp_build(c->d, share.lean));                        // before the capture: issue_frame then finds the lean EPnP prepared
-    const GraphKey now = {stride, gn, c->d.co_resident, c->in_format};
+    const GraphKey now = {stride, gn, c->d.co_resident, c->in_format, c->cov_mode, c->cov_sigma2};
     if (!r.gexec || !(r.key == now)) {
         if (r.gexec) { (void)hipGraphExecDestroy(r.gexec); r.gexec = nullptr; }
         hipGraph_t g = nullptr;
@@ -576,6 +589,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
     if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
+    r.cov_mode = c->cov_mode; r.masked = active != nullptr;
     c->staged_inputs = false;
     HIPCHK(hipEventRecord(r.ev[EV_DONE], c->stream));
     HIPCHK(hipGetLastError());
@@ -597,6 +611,12 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
         int mx = 0;
         for (int i = 0; i < B; i++) if (r[i].stats.n_after_detect > mx) mx = r[i].stats.n_after_detect;
         if (mx > 0) c->lk_hint = mx;
+    }
+    c->last_cov_mode = c->ring[slot].cov_mode;
+    if (c->last_cov_mode) {                                          // the slot's ring row; idle sequences took no launch: zero rows
+        memcpy(c->last_cov.data(), c->h_cov + (size_t)slot * B, sizeof(PoseCovRow) * B);
+        const int* flags = ring_row(c, c->h_act, slot) + B;
+        for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) memset(&c->last_cov[i], 0, sizeof(PoseCovRow));
     }
     c->last_slot = slot;
     c->tail = (c->tail + 1) % SVO_RING; c->inflight--; c->n_collected++;
@@ -1439,6 +1459,76 @@ extern "C" int svo_set_input_format(svo_context* c, int format) {
     GreyIn g;
     if (!grey_in_of(format, &g)) return fail_arg("svo_set_input_format: unknown format (SVO_INPUT_*)");
     c->in_format = format; c->in = g;                                 // host state: the next frame issued launches this format's kernels
+    return SVO_OK;
+}
+
+// ================================================================================================
+// Pose covariance (svo.h): the setter, the getter and the stage entry point
+// ================================================================================================
+static int check_cov_mode(int mode, double pixel_sigma, bool off_allowed) {
+    if (mode != SVO_COV_RESIDUAL && mode != SVO_COV_FIXED_SIGMA && !(off_allowed && mode == SVO_COV_OFF)) return fail_arg("pose covariance: unknown mode (SVO_COV_*)");
+    if (mode == SVO_COV_FIXED_SIGMA && !(pixel_sigma > 0. && isfinite(pixel_sigma))) return fail_arg("pose covariance: pixel_sigma must be positive and finite");
+    return SVO_OK;
+}
+
+extern "C" int svo_set_pose_covariance(svo_context* c, int mode, double pixel_sigma) {
+    if (!c) return fail_arg("null context");
+    if (const int rc = check_cov_mode(mode, pixel_sigma, true)) return rc;
+    if (mode != SVO_COV_OFF && !c->h_cov) {
+        const size_t rows = (size_t)SVO_RING * c->d.B;
+        HIPCHK(hipSetDevice(c->device));
+        PoseCovRow* h = nullptr; void* dv = nullptr;
+        HIPCHK(hipHostMalloc((void**)&h, sizeof(PoseCovRow) * rows, hipHostMallocMapped));
+        memset(h, 0, sizeof(PoseCovRow) * rows);
+        const hipError_t e = hipHostGetDevicePointer(&dv, (void*)h, 0);
+        if (e != hipSuccess || !dv) { (void)hipHostFree(h); HIPCHK(e != hipSuccess ? e : hipErrorInvalidDevicePointer); }   // the ring exists with both addresses or not at all
+        c->h_cov = h; c->d_cov = (PoseCovRow*)dv;
+        c->last_cov.assign((size_t)c->d.B, PoseCovRow{});
+    }
+    c->cov_mode = mode;                                              // host state: the next frame issued carries it
+    if (mode == SVO_COV_FIXED_SIGMA) c->cov_sigma2 = pixel_sigma * pixel_sigma;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_last_pose_covariance(svo_context* c, double* cov_T, double* cov_p, int* valid) {
+    if (!c) return fail_arg("null context");
+    if (c->last_slot < 0 || c->last_cov_mode == SVO_COV_OFF) { g_err = "no covariance: the last collected frame was issued with SVO_COV_OFF, or none was collected"; return SVO_ERR_STATE; }
+    for (int i = 0; i < c->d.B; i++) {
+        const PoseCovRow& r = c->last_cov[i];
+        if (cov_T) memcpy(cov_T + 36 * i, r.cov_T, sizeof(r.cov_T));
+        if (cov_p) memcpy(cov_p + 36 * i, r.cov_p, sizeof(r.cov_p));
+        if (valid) valid[i] = r.valid;
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_pose_covariance(int device, const float K[9], int n, const float* cam_pts, const float* world_pts,
+                                   const int* inliers, const double R[9], const double t[3],
+                                   int mode, double pixel_sigma, double cov_p[36], double cov_T[36], int* valid) {
+    if (!K || !R || !t || n < 1 || !cam_pts || !world_pts) return fail_arg("bad arguments");
+    int rc = check_cov_mode(mode, pixel_sigma, false); if (rc != SVO_OK) return rc;
+    svo_config cfg; svo_config_default(&cfg);
+    svo_context* c = nullptr; rc = stage_ctx(cfg, device, 64, 64, n, &c); if (rc != SVO_OK) return rc;
+    SeqState hs; memset(&hs, 0, sizeof(hs));
+    hs.active = 1; hs.fail_reason = 0; hs.ok = 1; hs.n_tracks = n;
+    memcpy(hs.K, K, sizeof(float) * 9); memcpy(hs.R, R, sizeof(double) * 9); memcpy(hs.t, t, sizeof(double) * 3);
+    std::vector<uint8_t> in((size_t)n, 1);
+    for (int i = 0; inliers && i < n; i++) in[i] = inliers[i] != 0;
+    DevTmp tmp; PoseCovRow* row;
+    HIPCHK(tmp.get(&row, 1));
+    HIPCHK(hipMemcpyAsync(c->d.tl1, cam_pts, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d.world, world_pts, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d.inlier, in.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = set_state(c, hs)) != SVO_OK) return rc;
+    launch_pose_cov(c->d, CovArgs{row, mode, pixel_sigma * pixel_sigma}, c->stream);
+    HIPCHK(hipGetLastError());
+    g_stage_path = (c->d.co_resident ? SVO_PATH_LEAN : 0) | SVO_PATH_POSE_COV;
+    PoseCovRow h;
+    HIPCHK(hipMemcpyAsync(&h, row, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (cov_p) memcpy(cov_p, h.cov_p, sizeof(h.cov_p));
+    if (cov_T) memcpy(cov_T, h.cov_T, sizeof(h.cov_T));
+    if (valid) *valid = h.valid;
     return SVO_OK;
 }
 

@@ -56,6 +56,12 @@ struct SeqState {
 
 struct FrameResult { double T[16]; int ok; svo_frame_stats stats; };
 
+// One sequence's pose covariance of one frame (svo.h, svo_set_pose_covariance) as k_pose_cov writes it into the pinned ring, and the
+// arguments of that launch: the frame's row of the ring (indexed by sequence), the mode the frame was issued with, pixel_sigma^2.
+// Kernel arguments of their own, not members of DevBuffers: no other kernel's argument block changes.
+struct PoseCovRow { double cov_T[36], cov_p[36]; int valid, pad; };
+struct CovArgs { PoseCovRow* rows; int mode; double sigma2; };
+
 // Input format of a frame (svo.h, svo_set_input_format): how a channels == 1 context reads the caller's bytes.  bpp = bytes per
 // pixel; bpp <= 1 is mono8 — nothing converts and the plain kernels run.  bpp 3 / 4: grey = (byte0 w0 + byte1 w1 + byte2 w2 + rnd)
 // >> shift (byte 3 ignored); bpp 2: grey = byte yoff of the pixel's pair (the Y of YUV 4:2:2).  Scalar kernel arguments: the
@@ -218,6 +224,7 @@ void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = fa
 hipError_t prepare_pnp_lean();   // before the first launch_pnp with co_resident on the current device (the lean EPnP's dynamic LDS)
 bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t s);   // lone stream: triangulation || first EPnP chunk in one launch; false = not applicable
 void launch_pnp_subsets(const DevBuffers& d, hipStream_t s);
+void launch_pose_cov(const DevBuffers& d, const CovArgs& a, hipStream_t s);   // after launch_pnp: the covariance of the refined pose, one block per launched sequence
 void launch_pnp_p3p(const DevBuffers& d, hipStream_t s);                // exactly four points: one P3P, no RANSAC (stage API only)
 void launch_inverse_transform(const double* R, const double* t, double* T, hipStream_t s);   // device pointers
 // the front of a lone stream's frame as two fused launches (ingest + level 1 || FAST pass 0; levels 2-3 || emit), then the second

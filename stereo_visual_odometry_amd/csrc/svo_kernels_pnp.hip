@@ -1262,3 +1262,193 @@ void launch_pnp(const DevBuffers& d, hipStream_t st, bool first_chunk_solved) {
     }
     hipLaunchKernelGGL(b.final, dim3(ns), dim3(b.final_threads), 0, st, d);
 }
+
+// ------------------------------------------------------------------------------------------------ pose covariance
+// k_pose_cov: the 6x6 covariance of the pose k_pnp_final has just refined (svo.h, svo_set_pose_covariance), one block
+// per launched sequence, after k_pnp_final on the frame's stream.  The block evaluates lm_point ONCE more, at the accepted pose
+// (the refine's last JtJ belongs to the point before the last step), over the inliers: H = JtJ and |e|^2 are sums 0..20 and 27 of
+// the same 28 (the six JtErr sums ride along unused: one reduction routine for both kernels).  Thread 0 then factors H (Cholesky,
+// pivots checked), inverts it through the triangular inverse, scales by sigma^2 and propagates through [R t]^-1; the 72 doubles
+// and the flag go straight into the frame's row of a pinned host ring, like the result record k_frame_end writes.
+// Partition: PC_THREADS threads in BOTH builds, thread v takes points v, v + PC_THREADS, ... in that order, the wave sums are
+// added in wave order — the 96-register build differs from the full one in register allocation only and gives its bits.
+#define PC_THREADS 256
+#define PC_WAVES (PC_THREADS / 64)
+struct PcShared {
+    double red[PC_WAVES][28];
+    double R[9], dRdr[27], rv[3];
+    double H[36], L[36], Li[36], G[36], GS[36];
+    double out[72];                                  // cov_T, cov_p as PoseCovRow lays them out
+    int cnt[PC_WAVES];
+    int valid;
+};
+
+// Log of a rotation matrix, accurate at small angles (rodrigues_to_vector follows cv::Rodrigues and returns zero below
+// sin(theta) = 1e-5): r = theta / sin(theta) * vee(R - Rt) / 2, theta = atan2(sin, cos).  Near pi, where the antisymmetric part
+// vanishes, cv::Rodrigues' branch is the accurate one.
+static __device__ void so3_log(const double* R, double* r) {
+    const double vx = (R[7] - R[5]) * 0.5, vy = (R[2] - R[6]) * 0.5, vz = (R[3] - R[1]) * 0.5;
+    const double sn = sqrt(vx * vx + vy * vy + vz * vz), cs = (R[0] + R[4] + R[8] - 1) * 0.5;
+    if (cs < -0.5) { rodrigues_to_vector(R, r); return; }
+    const double k = sn > 1e-8 ? atan2(sn, cs) / sn : 1.;             // theta / sin(theta) = 1 + theta^2 / 6 + ...
+    r[0] = vx * k; r[1] = vy * k; r[2] = vz * k;
+}
+
+// Thread 0: sh.red[0][*] (the totals) -> sh.out; returns the valid flag.  Every matrix lives in LDS and the loops stay rolled:
+// a few thousand dependent f64 operations on one lane either way, and no register array for the compiler to spill.
+static __device__ int pose_cov_solve(PcShared& sh, const double* t, int m, int mode, double sigma2) {
+    // H can only be positive definite with 2m >= 6 rows; the a-posteriori variance needs a redundant row on top of that
+    if (m < 3 || (mode == SVO_COV_RESIDUAL && 2 * m - 6 <= 0)) return 0;
+    {
+        int q = 0;
+        for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) { sh.H[6 * a + b] = sh.H[6 * b + a] = sh.red[0][q++]; }
+    }
+    // Cholesky H = L Lt.  A pivot counts as positive when more than rounding noise is left of its diagonal entry (2^-40 of it: with
+    // kappa(H) up to 1e7 a true pivot keeps > 1e-7 of it, the cancellation noise of a rank-deficient H stays below ~1e-13 of it).
+#pragma unroll 1
+    for (int i = 0; i < 6; i++) {
+#pragma unroll 1
+        for (int j = 0; j <= i; j++) {
+            double v = sh.H[6 * i + j];
+#pragma unroll 1
+            for (int k = 0; k < j; k++) v -= sh.L[6 * i + k] * sh.L[6 * j + k];
+            if (i == j) {
+                if (!(v > sh.H[7 * i] * 9.094947017729282e-13)) return 0;
+                sh.L[7 * i] = sqrt(v);
+            } else sh.L[6 * i + j] = v / sh.L[7 * j];
+        }
+    }
+    // Li = L^-1 (lower triangular), then cov_p = sigma^2 Lit Li: the upper triangle, mirrored (exactly symmetric)
+#pragma unroll 1
+    for (int j = 0; j < 6; j++) {
+        sh.Li[7 * j] = 1. / sh.L[7 * j];
+#pragma unroll 1
+        for (int i = j + 1; i < 6; i++) {
+            double v = 0;
+#pragma unroll 1
+            for (int k = j; k < i; k++) v += sh.L[6 * i + k] * sh.Li[6 * k + j];
+            sh.Li[6 * i + j] = -v / sh.L[7 * i];
+        }
+    }
+    const double s2 = mode == SVO_COV_RESIDUAL ? sh.red[0][27] / (double)(2 * m - 6) : sigma2;
+    double* Sp = sh.out + 36;
+#pragma unroll 1
+    for (int i = 0; i < 6; i++)
+#pragma unroll 1
+        for (int j = i; j < 6; j++) {
+            double v = 0;
+#pragma unroll 1
+            for (int k = j; k < 6; k++) v += sh.Li[6 * k + i] * sh.Li[6 * k + j];
+            Sp[6 * i + j] = Sp[6 * j + i] = s2 * v;
+        }
+    // G = [ [c]x Jr, -Rt ; -Jr, 0 ],  c = -Rt t,  Jr = I - a [r]x + b [r]x^2 the right Jacobian of SO(3) at r
+    const double* r = sh.rv; const double* R = sh.R;
+    const double th2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2], th = sqrt(th2);
+    double ca = 0.5, cb = 0;
+    if (th >= 1e-9) {
+        const double sh2 = sin(0.5 * th);
+        ca = 2. * sh2 * sh2 / th2;                                    // (1 - cos) / theta^2 without the cancellation
+        cb = (th - sin(th)) / (th2 * th);
+    }
+    const double K1[9] = {0, -r[2], r[1], r[2], 0, -r[0], -r[1], r[0], 0};
+    double Jr[9], c[3];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
+        double k2 = 0;
+        for (int k = 0; k < 3; k++) k2 += K1[3 * i + k] * K1[3 * k + j];
+        Jr[3 * i + j] = (i == j ? 1. : 0.) - ca * K1[3 * i + j] + cb * k2;
+    }
+    for (int i = 0; i < 3; i++) c[i] = -(R[i] * t[0] + R[3 + i] * t[1] + R[6 + i] * t[2]);
+    const double C1[9] = {0, -c[2], c[1], c[2], 0, -c[0], -c[1], c[0], 0};
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
+        double v = 0;
+        for (int k = 0; k < 3; k++) v += C1[3 * i + k] * Jr[3 * k + j];
+        sh.G[6 * i + j] = v; sh.G[6 * i + 3 + j] = -R[3 * j + i];
+        sh.G[6 * (3 + i) + j] = -Jr[3 * i + j]; sh.G[6 * (3 + i) + 3 + j] = 0;
+    }
+    // cov_T = G cov_p Gt, the upper triangle mirrored
+#pragma unroll 1
+    for (int i = 0; i < 6; i++)
+#pragma unroll 1
+        for (int j = 0; j < 6; j++) {
+            double v = 0;
+#pragma unroll 1
+            for (int k = 0; k < 6; k++) v += sh.G[6 * i + k] * Sp[6 * k + j];
+            sh.GS[6 * i + j] = v;
+        }
+#pragma unroll 1
+    for (int i = 0; i < 6; i++)
+#pragma unroll 1
+        for (int j = i; j < 6; j++) {
+            double v = 0;
+#pragma unroll 1
+            for (int k = 0; k < 6; k++) v += sh.GS[6 * i + k] * sh.G[6 * j + k];
+            sh.out[6 * i + j] = sh.out[6 * j + i] = v;
+        }
+    return 1;
+}
+
+static __device__ __forceinline__ void pose_cov_body(const DevBuffers& d, const CovArgs& a) {
+    const int seq = seq_of(d, blockIdx.x);
+    const SeqState& s = d.st[seq];
+    __shared__ PcShared sh;
+    // seq_live alone is not enough: the motion gate (fail_reason 4) is raised by thread 0 of k_pnp_final at its very end
+    const bool live = seq_live(s) && s.ok;                             // block-uniform
+    if (threadIdx.x == 0) sh.valid = 0;
+    if (live) {
+        const int n = s.n_tracks;
+        const size_t o = (size_t)seq * d.CAP;
+        if (threadIdx.x == 0) {
+            double Rr[9];
+            so3_log(s.R, sh.rv);
+            rodrigues_to_matrix(sh.rv, Rr, sh.dRdr);                   // dR/dr at the pose; the residuals use s.R itself, the matrix T was made of
+            for (int k = 0; k < 9; k++) sh.R[k] = s.R[k];
+        }
+        __syncthreads();
+        const double fx = s.K[0], fy = s.K[4], cx = s.K[2], cy = s.K[5];
+        const double t0 = s.t[0], t1 = s.t[1], t2 = s.t[2];
+        double acc[28];
+#pragma unroll
+        for (int k = 0; k < 28; k++) acc[k] = 0;
+        int cnt = 0;
+        for (int i0 = 0; i0 < n; i0 += PC_THREADS) {                   // block-uniform trip count: the ballot sees whole waves
+            const int i = i0 + threadIdx.x;
+            const bool in = i < n && d.inlier[o + i];
+            cnt += __popcll(__ballot(in));
+            if (in) {
+                const float2 c = d.tl1[o + i];
+                lm_point(d.world[3 * (o + i)], d.world[3 * (o + i) + 1], d.world[3 * (o + i) + 2], c.x, c.y, sh.R, sh.dRdr, t0, t1, t2, fx, fy, cx, cy, acc);
+            }
+        }
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        const int slot = lm_red_slot(lane);
+        const double tot = lm_wave_sums28(acc, lane);
+        if (slot >= 0) sh.red[wv][slot] = tot;
+        if (lane == 0) sh.cnt[wv] = cnt;
+        __syncthreads();
+        if (threadIdx.x < 28) {
+            double t = sh.red[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < PC_WAVES; w++) t += sh.red[w][threadIdx.x];
+            sh.red[0][threadIdx.x] = t;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int m = 0;
+            for (int w = 0; w < PC_WAVES; w++) m += sh.cnt[w];
+            sh.valid = pose_cov_solve(sh, s.t, m, a.mode, a.sigma2);
+        }
+    }
+    __syncthreads();
+    const int valid = sh.valid;
+    PoseCovRow& row = a.rows[seq];
+    if (threadIdx.x < 72) (threadIdx.x < 36 ? row.cov_T[threadIdx.x] : row.cov_p[threadIdx.x - 36]) = valid ? sh.out[threadIdx.x] : 0.;
+    if (threadIdx.x == 72) { row.valid = valid; row.pad = 0; }
+}
+// Two builds, as for the refine (see k_triangulate_lean); registers as built: profiles/r11_pose_cov_code_object.md,
+// tests/test_pose_cov_code_object.py pins the cap.
+__global__ __launch_bounds__(PC_THREADS) void k_pose_cov(DevBuffers d, CovArgs a) { pose_cov_body(d, a); }
+__global__ __launch_bounds__(PC_THREADS) __attribute__((amdgpu_num_vgpr(48))) void k_pose_cov_lean(DevBuffers d, CovArgs a) { pose_cov_body(d, a); }
+
+void launch_pose_cov(const DevBuffers& d, const CovArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(d.co_resident ? k_pose_cov_lean : k_pose_cov, dim3(launch_seqs(d)), dim3(PC_THREADS), 0, st, d, a);
+}

@@ -1,0 +1,55 @@
+"""The pose-covariance cases whose BITS must not depend on how a frame is issued (tests/test_gpu_pose_cov.py): run in a fresh
+process under SVO_GRAPH=1 or SVO_FORCE_LEAN=1 and compared with the same cases run from the launch list on the full builds.
+Usage: pose_cov_child.py OUT.npz"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+for p in (os.path.dirname(HERE), HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+W, H = 320, 160
+
+
+def run_cases():
+    """-> dict of arrays: every covariance a lone stream, a ten-sequence context and the stage entry produce, and the path bits."""
+    import pose_cov_ref as ref
+    from stereo_visual_odometry_amd import api, synthetic as syn
+    cal = dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0)
+    seq = syn.StereoSequence(cal=cal, n_frames=4, seed=3, step=0.3)
+    P = syn.projection_matrices(cal)
+    out = {}
+    lone = api.VisualOdometry(cfg=api.default_config(max_translation_norm=2.0)); lone.initalize_projection_matricies(*P)
+    lone.set_pose_covariance("residual")
+    rows, paths = [], []
+    for k in range(4):
+        lone.stereo_callback(seq.left[k], seq.right[k])
+        rows.append(np.concatenate([a.reshape(-1) for a in lone.last_pose_covariance()]))
+        paths.append(lone.last_frame_path())
+    out["lone"], out["lone_path"] = np.array(rows), np.array(paths)
+    lone.close()
+    B = 10
+    many = api.BatchVisualOdometry(W, H, B, api.default_config(max_translation_norm=2.0)); many.initalize_projection_matricies(*P)
+    many.set_pose_covariance("fixed", 0.5)
+    rows, paths = [], []
+    for k in range(4):
+        many.stereo_callback_batch([seq.left[k]] * B, [seq.right[k]] * B)
+        rows.append(np.concatenate([a.reshape(-1) for a in many.last_pose_covariance()]))
+        paths.append(many.last_frame_path())
+    out["many"], out["many_path"] = np.array(rows), np.array(paths)
+    many.close()
+    K, world, img, R, t = ref.synthetic_points(600, 77)
+    stage = []
+    for mode in ("residual", "fixed"):
+        cov_p, cov_T, valid = api.poseCovariance(K, img, world, R, t, mode=mode, pixel_sigma=0.5)
+        stage.append(np.concatenate([cov_p.reshape(-1), cov_T.reshape(-1), [float(valid)]]))
+    out["stage"], out["stage_path"] = np.array(stage), np.array([api.last_stage_path()])
+    return out
+
+
+if __name__ == "__main__":
+    np.savez(sys.argv[1], **run_cases())
+    print("pose cov child ok")

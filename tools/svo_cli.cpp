@@ -166,10 +166,10 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
-    std::string calib, out = folder + "/result.csv", rect_l, rect_r;
+    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out;
     bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false;
     for (int i = 3; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--rectify")) {
@@ -181,6 +181,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--ref-format")) ref_format = std::atoi(argv[i + 1]) != 0;
         else if (!strcmp(argv[i], "--calib")) calib = argv[i + 1];
         else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
+        else if (!strcmp(argv[i], "--covariance")) cov_out = argv[i + 1];   // one row per frame: valid, then the 21 upper-triangle entries of cov_T (svo.h), row by row
         else if (!strcmp(argv[i], "--device")) default_device() = std::atoi(argv[i + 1]);
     }
     Mat34f Pl = {322.11376f, 0, 327.47336f, 0, 0, 322.11376f, 176.33722f, 0, 0, 0, 1, 0};               // main.cpp:357-362
@@ -200,6 +201,14 @@ int main(int argc, char** argv) {
     std::ofstream res(out);
     if (!res) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 2; }
     res << "x,y,z,gtx,gty\n";
+    std::ofstream cov;
+    if (!cov_out.empty()) {
+        cov.open(cov_out);
+        if (!cov) { std::fprintf(stderr, "cannot write %s\n", cov_out.c_str()); return 2; }
+        cov << "valid";
+        for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) cov << ",c" << a << b;
+        cov << "\n";
+    }
     try {
         svo_config cfg; svo_config_default(&cfg);
         cfg.lk_float_sums = float_sums ? 1 : 0;
@@ -207,6 +216,7 @@ int main(int argc, char** argv) {
         vo.initalize_projection_matricies(Pl, Pr);
         if (!rect_l.empty()) vo.set_rectification(ci_l, ci_r);
         if (gray_gpu) vo.set_input_encoding("bgr8");
+        if (cov.is_open()) vo.set_pose_covariance(SVO_COV_RESIDUAL);
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
         if (identity_start) { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(pose, I, sizeof(I)); }
@@ -226,6 +236,12 @@ int main(int argc, char** argv) {
             char row[256];
             std::snprintf(row, sizeof(row), ref_format ? "%g,%g,%g,%g,%g\n" : "%.9g,%.9g,%.9g,%.9g,%.9g\n", pose[3], pose[7], pose[11], gtx, gty);
             res << row;
+            if (cov.is_open()) {
+                const VisualOdometry::PoseCovariance c = vo.last_pose_covariance();
+                cov << (c.valid ? 1 : 0);
+                for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) { std::snprintf(row, sizeof(row), ",%.17g", c.cov_T[6 * a + b]); cov << row; }
+                cov << "\n";
+            }
             std::printf("Frame %d: ok=%d tracks=%d inliers=%d\n", i, (int)o.first, vo.stats.n_after_bounds, vo.stats.n_inliers);
             done++;
         }

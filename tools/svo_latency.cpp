@@ -3,7 +3,8 @@
 // src/main.cpp:394).  Reads stereo pairs from a raw file (int32 n, h, w; then n x (left, right) gray images), plays them
 // ping-pong through svo_process and prints the mean / median / p95 wall time per call, with ordinary heap buffers and with
 // page-locked ones (svo_alloc_pinned).
-//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
+//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
+// --covariance: every leg is run twice, without and with the pose covariance (svo_set_pose_covariance, SVO_COV_RESIDUAL).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -13,7 +14,7 @@
 #include <vector>
 #include "svo.h"
 
-static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label) {
+static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false) {
     svo_config cfg; svo_config_default(&cfg);
     cfg.win_w = cfg.win_h = win; cfg.max_translation_norm = max_t;
     svo_context* ctx = nullptr;
@@ -21,6 +22,7 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
     const float Pl[12] = {718.856f, 0, 607.1928f, 0, 0, 718.856f, 185.2157f, 0, 0, 0, 1, 0};
     float Pr[12]; std::memcpy(Pr, Pl, sizeof(Pl)); Pr[3] = -386.1448f;
     svo_set_projection(ctx, -1, Pl, Pr);
+    if (covariance && svo_set_pose_covariance(ctx, SVO_COV_RESIDUAL, 1.0) != SVO_OK) { std::fprintf(stderr, "svo_set_pose_covariance: %s\n", svo_last_error()); std::exit(1); }
     const int n = (int)L.size();
     auto pp = [&](int i) { const int p = i % (2 * n - 2); return p < n ? p : 2 * n - 2 - p; };
     double T[16]; svo_frame_stats st; int n_ok = 0;
@@ -41,7 +43,9 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation]\n"); return 2; }
+    bool covariance = false;
+    if (argc > 2 && !std::strcmp(argv[argc - 1], "--covariance")) { covariance = true; argc--; }
+    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance]\n"); return 2; }
     const int win = argc > 2 ? std::atoi(argv[2]) : 21, calls = argc > 3 ? std::atoi(argv[3]) : 200;
     const double max_t = argc > 4 ? std::atof(argv[4]) : 2.0;
     std::ifstream f(argv[1], std::ios::binary);
@@ -55,11 +59,13 @@ int main(int argc, char** argv) {
     std::vector<const uint8_t*> L(n), R(n);
     for (int k = 0; k < n; k++) { L[k] = heap.data() + img * (2 * k); R[k] = heap.data() + img * (2 * k + 1); }
     run(L, R, w, h, win, calls, max_t, "heap buffers:");
+    if (covariance) run(L, R, w, h, win, calls, max_t, "heap buffers, covariance:", true);
     uint8_t* pin = (uint8_t*)svo_alloc_pinned(heap.size());
     if (pin) {
         std::memcpy(pin, heap.data(), heap.size());
         for (int k = 0; k < n; k++) { L[k] = pin + img * (2 * k); R[k] = pin + img * (2 * k + 1); }
         run(L, R, w, h, win, calls, max_t, "page-locked buffers:");
+        if (covariance) run(L, R, w, h, win, calls, max_t, "page-locked, covariance:", true);
         svo_free_pinned(pin);
     }
     return 0;
