@@ -164,6 +164,7 @@ int svo_get_lk_registers_left(svo_context* ctx);
 #define SVO_PATH_GRAPH          32   /* the frame replayed a captured hipGraph (SVO_GRAPH=1); the other bits are the capture's */
 #define SVO_PATH_INPUT_CONVERTED 64  /* the frame's ingest converted the caller's pixels to grey (svo_set_input_format) */
 #define SVO_PATH_POSE_COV       128  /* the frame ran k_pose_cov after its refine (svo_set_pose_covariance; also set by svo_pose_covariance) */
+#define SVO_PATH_DETECT_MASKED  256  /* the frame's detection applied a detection mask (svo_set_detection_mask; also set by svo_append_features_from_image_masked) */
 int svo_get_last_frame_path(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
@@ -325,6 +326,44 @@ int svo_get_last_pose_covariance(svo_context* ctx, double* cov_T, double* cov_p,
 int svo_get_features(svo_context* ctx, int seq, int cap, float* xy, int* ages, int* strengths);
 int svo_get_last_tracks(svo_context* ctx, int seq, int cap, float* pl0, float* pr0, float* pl1, float* pr1,
                         float* world, uint8_t* inlier);
+/* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
+ * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
+ * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the
+ * rectification are.  A non-zero byte means "features allowed here".  Without a mask a context launches exactly what it always did.
+ *
+ * The rule.  With a mask, the list appendFeaturesFromImage hands to the bucket grid — the existing tracks first, then the new
+ * cv::FAST hits in raster order — is filtered as KeyPointsFilter::runByPixelsMask does it:
+ *   an entry at (x, y) stays iff mask[min((int)(y + 0.5f), H-1)][min((int)(x + 0.5f), W-1)] != 0.
+ * FAST, its threshold and its 3x3 non-max suppression run on the whole image as before; the mask is applied to the survivors,
+ * AFTER NMS, as OpenCV does (a suppressed neighbour of a masked-out winner does not come back).  A filtered entry makes no offer to
+ * the grid; the others keep their rank in the unfiltered list, so ties break exactly as in the filtered one.  A filtered track is
+ * gone from the feature set, as if its bucket had been lost.  The second detection pass (threshold / 4) uses the same mask.
+ *
+ * Which image a mask belongs to.  The detection of call k scans the left image of call k - 1, and the tracks it filters are
+ * positions in that image.  A mask therefore belongs to a left image, not to a call: the mask in force when a frame is submitted
+ * describes THAT FRAME'S left image and is applied when that image is scanned, in the sequence's following call.  A static mask is
+ * set once and holds until it is cleared; a per-frame mask (a segmentation network's output) is set before each submit.  After a
+ * clear the next call still applies the mask of the image it scans; the call after that is unmasked.
+ *
+ * svo_set_detection_mask: seq = -1 installs the one shared mask, seq >= 0 a sequence's own, which overrides the shared one.
+ * mask = NULL clears (seq = -1: all of them).  mask: height rows of width bytes, `stride` bytes apart, in host memory, or
+ * (on_device != 0) in device memory — then the caller's writes to it must be complete, or ordered on svo_get_stream's stream.
+ * The mask is copied into library-owned device memory on the frame stream, like svo_reset_sequence's work: legal with frames in
+ * flight, no host synchronisation for a device mask, and the copy lands between the frames submitted before and after it (a host
+ * mask passes through one pinned staging buffer; a second host mask waits for the first one's copy).  Every scope keeps two slots:
+ * a frame records the slot of its left image and the setter writes the other, so the detection still queued for the previous
+ * image reads what it was given.  (The shared pair has one record for all sequences: with ragged frames, a sequence that stays
+ * idle across two shared-mask changes sees the newer mask on its old image.  A sequence's own pair has no such limit: an idle
+ * sequence's record and slots are not touched.)  Buffers are allocated at first use and freed with the context.
+ * Errors (SVO_ERR_ARG): a channels = 3 context (FAST walks the bytes of the interleaved row there, pixel positions mean nothing),
+ * features_per_bucket > 1 (the general bucket walk takes no mask), stride < width, seq out of range.
+ * svo_get_last_frame_path reports SVO_PATH_DETECT_MASKED for a frame whose detection applied a mask to some sequence.  A lone
+ * stream's masked frame issues the unfused front (ingest, then the masked FAST kernel: one launch more); under SVO_GRAPH=1 masked
+ * frames run from the launch list, as rectifying frames do.
+ * svo_get_detection_mask: the mask in force for the frames submitted next (seq's own, else the shared one; seq = -1: the shared
+ * one) to out (width * height bytes, packed; may be NULL), *present = whether there is one.  Synchronises the context's stream. */
+int svo_set_detection_mask(svo_context* ctx, int seq, const uint8_t* mask, int stride, int on_device);
+int svo_get_detection_mask(svo_context* ctx, int seq, uint8_t* out /* W*H, packed */, int* present);
 /* Diagnostics (pyramid tests): one level of one stored pyramid of sequence seq, WITH its stored border — every level keeps a
  * REFLECT_101 border of `pad` pixels on each side (the LK kernel reads it directly), as cv::buildOpticalFlowPyramid keeps its
  * winSize border.  out gets (h + 2 pad) rows of (w + 2 pad) bytes, packed, from pixel (-pad, -pad); cap is its size in bytes.
@@ -373,6 +412,9 @@ int svo_stage_cache_clear_all(void);
  * i.e. cv::FAST(.., nonmaxSuppression=true).  xy: cap x 2, resp: cap.  *n_out = total found (may exceed cap). */
 int svo_fast_detect(int device, const uint8_t* img, int w, int h, int stride, int threshold,
                     int cap, float* xy, float* resp, int* n_out);
+/* the same behind a detection mask (the section on detection masks: applied to the NMS survivors); mask rows mask_stride apart */
+int svo_fast_detect_masked(int device, const uint8_t* img, int w, int h, int stride, int threshold,
+                           const uint8_t* mask, int mask_stride, int cap, float* xy, float* resp, int* n_out);
 /* the NMS-surviving score map (h*w bytes, 0 where no keypoint) — test hook for the FAST kernel */
 int svo_fast_score_map(int device, const uint8_t* img, int w, int h, int stride, int threshold, uint8_t* score);
 
@@ -388,6 +430,11 @@ int svo_bucket_filter(int device, int img_w, int img_h, int* n_io, float* xy, in
  * (bucket winners are picked with 64-bit atomicMax keys straight from the FAST kernel). cap = array capacity. */
 int svo_append_features_from_image(int device, const svo_config* cfg, const uint8_t* img, int w, int h, int stride,
                                    int fast_threshold, int cap, int* n_io, float* xy, int* ages, int* strengths);
+
+/* the same with a detection mask over the whole list (the tracks passed in, then the FAST hits); features_per_bucket must be 1 */
+int svo_append_features_from_image_masked(int device, const svo_config* cfg, const uint8_t* img, int w, int h, int stride,
+                                          int fast_threshold, const uint8_t* mask, int mask_stride, int cap, int* n_io,
+                                          float* xy, int* ages, int* strengths);
 
 /* replaces: cv::buildOpticalFlowPyramid(img, pyr, winSize, maxLevel)  (vo.cpp:50,52,200,201).
  * Returns the levels as tightly packed u8 images concatenated in `levels_out` (level l is

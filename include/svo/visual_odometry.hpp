@@ -120,6 +120,25 @@ inline std::vector<Point2f> featureDetectionFast(const Image image, const int fa
     return pts;
 }
 
+// the same behind a detection mask (svo.h: an 8-bit image of the frame's size, non-zero = features allowed, applied to the keypoints
+// that survived non-max suppression — what cv::FeatureDetector::detect(image, keypoints, mask) does)
+inline std::vector<Point2f> featureDetectionFast(const Image image, const Image mask, const int fast_threshold,
+                                                 std::vector<float>& response_strengths) {
+    if (mask.empty() || mask.rows != image.rows || mask.cols != image.cols || mask.channels != 1)
+        throw std::runtime_error("featureDetectionFast: the mask must be a single-channel image of the frame's size");
+    int cap = 8192, n = 0;
+    std::vector<Point2f> pts;
+    for (;;) {
+        pts.resize(cap); response_strengths.resize(cap);
+        svo_throw(svo_fast_detect_masked(default_device(), image.data, image.cols, image.rows, image.step, fast_threshold,
+                                         mask.data, mask.step, cap, &pts[0].x, response_strengths.data(), &n));
+        if (n <= cap) break;
+        cap = n;
+    }
+    pts.resize(n); response_strengths.resize(n);
+    return pts;
+}
+
 inline void deletePointsWithFailureStatus(std::vector<Point2f>& point_vector, const std::vector<bool>& isok) {   // vo.h:406-407
     size_t m = 0;
     for (size_t i = 0; i < point_vector.size(); i++)
@@ -192,6 +211,11 @@ class VisualOdometry {                                               // include/
             if (rect_) apply_rectification();
             if (in_format_ != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx_, in_format_));
             if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
+            if (!mask_.empty()) {
+                if ((int)mask_.size() != width_ * height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
+                svo_throw(svo_set_detection_mask(ctx_, -1, mask_.data(), width_, 0));
+                mask_.clear(); mask_.shrink_to_fit();
+            }
         }
         check_frame(image_left, "left"); check_frame(image_right, "right");
         Mat44 T;
@@ -292,6 +316,29 @@ class VisualOdometry {                                               // include/
             throw std::runtime_error("set_pose_covariance: bad mode or pixel_sigma");
         cov_mode_ = mode; cov_sigma_ = pixel_sigma;
     }
+    // Keep features off the zero bytes of `mask` (svo_set_detection_mask): height rows of width bytes, `stride` apart (0: packed), at
+    // the frame's size (the rectified size of a rectifying object).  The mask describes the left image of the frames passed from
+    // now on and is applied when that image is scanned, in the following call; a static mask is set once.  Before the first frame
+    // the object keeps a copy (width x height then come from set_detection_mask's own arguments).
+    void set_detection_mask(const uint8_t* mask, int stride = 0) {
+        if (!mask) { clear_detection_mask(); return; }
+        if (!ctx_) throw std::runtime_error("set_detection_mask: before the first frame, pass the size too: set_detection_mask(mask, stride, width, height)");
+        svo_throw(svo_set_detection_mask(ctx_, -1, mask, stride ? stride : width_, 0));
+    }
+    void set_detection_mask(const uint8_t* mask, int stride, int width, int height) {
+        if (ctx_) {
+            if (width != width_ || height != height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
+            set_detection_mask(mask, stride);
+            return;
+        }
+        if (!mask || width < 1 || height < 1 || (stride && stride < width)) throw std::runtime_error("set_detection_mask: bad arguments");
+        mask_.resize((size_t)width * height);
+        for (int y = 0; y < height; y++) std::memcpy(mask_.data() + (size_t)y * width, mask + (size_t)y * (stride ? stride : width), (size_t)width);
+    }
+    void clear_detection_mask() {
+        mask_.clear();
+        if (ctx_) svo_throw(svo_set_detection_mask(ctx_, -1, nullptr, 0, 0));
+    }
     // Of the last stereo_callback (svo_get_last_pose_covariance): cov_T, the covariance of the returned transform in the order
     // (x y z, rotation about x y z) of nav_msgs/Odometry.pose.covariance, and cov_p, that of the cameraToWorld parameters (r, t);
     // both row-major 6x6, all zero with valid = false when the frame gave no pose.  Throws when the frame ran with the mode off.
@@ -334,6 +381,7 @@ class VisualOdometry {                                               // include/
     int raw_w_ = 0, raw_h_ = 0;                                       // raw frame size while rectifying, else 0
     int in_format_ = SVO_INPUT_MONO8;                                 // set_input_encoding (applied once the context exists)
     int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
+    std::vector<uint8_t> mask_;                                       // set_detection_mask before the first frame: installed at creation
 };
 
 }   // namespace visual_odometry

@@ -83,6 +83,18 @@ lib.svo_get_last_frame_path.argtypes = [C.c_void_p]
 PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
 PATH_INPUT_CONVERTED = 64
 PATH_POSE_COV = 128
+PATH_DETECT_MASKED = 256
+# detection masks (svo.h): mask is a host or device pointer to height rows of width bytes
+lib.svo_set_detection_mask.restype = C.c_int
+lib.svo_set_detection_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+lib.svo_get_detection_mask.restype = C.c_int
+lib.svo_get_detection_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+lib.svo_fast_detect_masked.restype = C.c_int
+lib.svo_fast_detect_masked.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_int)]
+lib.svo_append_features_from_image_masked.restype = C.c_int
+lib.svo_append_features_from_image_masked.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
 # pose covariance (svo.h SVO_COV_*): cov_T / cov_p are n_seq x 36 doubles, valid n_seq ints
 COV_OFF, COV_RESIDUAL, COV_FIXED_SIGMA = 0, 1, 2
 COV_MODES = {"off": COV_OFF, "residual": COV_RESIDUAL, "fixed": COV_FIXED_SIGMA}
@@ -137,6 +149,7 @@ EXPORTS = [
     "svo_set_rectification_maps", "svo_set_rectification", "svo_clear_rectification", "svo_init_rectify_map", "svo_rectify_image",
     "svo_set_input_format", "svo_convert_gray",
     "svo_set_pose_covariance", "svo_get_last_pose_covariance", "svo_pose_covariance",
+    "svo_set_detection_mask", "svo_get_detection_mask", "svo_fast_detect_masked", "svo_append_features_from_image_masked",
 ]
 
 

@@ -26,16 +26,29 @@ def _pts(p):
 
 
 # ---------------------------------------------------------------------------- free functions
-def featureDetectionFast(image, fast_threshold, device=0):
-    """vo.h:393-395 — returns (points (N,2) f32, response_strengths (N,) f32), raster order."""
+def _host_mask(mask, height, width):
+    """A detection mask as a contiguous (height, width) uint8 array; ValueError for another shape or dtype."""
+    m = np.asarray(mask)
+    if m.dtype != np.uint8 or m.shape != (height, width):
+        raise ValueError("detection mask: (%d, %d) uint8 expected, got %s %s" % (height, width, m.shape, m.dtype))
+    return np.ascontiguousarray(m)
+
+
+def featureDetectionFast(image, fast_threshold, device=0, mask=None):
+    """vo.h:393-395 — returns (points (N,2) f32, response_strengths (N,) f32), raster order.  mask: an (H, W) uint8 detection
+    mask (svo.h: non-zero = allowed), applied to the keypoints that survived non-max suppression, as cv::FeatureDetector does."""
     img = u8img(image)
     h, w = img.shape
+    m = _host_mask(mask, h, w) if mask is not None else None
     cap = 4096
     while True:
         xy = np.zeros((cap, 2), np.float32)
         resp = np.zeros(cap, np.float32)
         n = C.c_int(0)
-        check(lib.svo_fast_detect(device, ptr(img), w, h, w, int(fast_threshold), cap, ptr(xy), ptr(resp), C.byref(n)))
+        if m is not None:
+            check(lib.svo_fast_detect_masked(device, ptr(img), w, h, w, int(fast_threshold), ptr(m), w, cap, ptr(xy), ptr(resp), C.byref(n)))
+        else:
+            check(lib.svo_fast_detect(device, ptr(img), w, h, w, int(fast_threshold), cap, ptr(xy), ptr(resp), C.byref(n)))
         if n.value <= cap:
             return xy[:n.value].copy(), resp[:n.value].copy()
         cap = n.value
@@ -291,10 +304,12 @@ class FeatureSet:
     def filterByBucketLocation(self, image):
         self.filterByBucketLocationInternal(image, BUCKETS_ALONG_HEIGHT, BUCKETS_ALONG_WIDTH, BUCKET_START_ROW, FEATURES_PER_BUCKET)
 
-    def appendFeaturesFromImage(self, image, fast_threshold, cfg=None):
-        """vo.h:186-187 — FAST + append (age 0) + default-grid bucket filter, fused on the GPU."""
+    def appendFeaturesFromImage(self, image, fast_threshold, cfg=None, mask=None):
+        """vo.h:186-187 — FAST + append (age 0) + default-grid bucket filter, fused on the GPU.  mask: an (H, W) uint8 detection
+        mask over the whole list, the set's own features included (svo.h)."""
         img = u8img(image)
         h, w = img.shape
+        m = _host_mask(mask, h, w) if mask is not None else None
         cfg = cfg if cfg is not None else default_config()
         rows = max(cfg.buckets_along_height - cfg.bucket_start_row, 0)
         cap = max(rows * cfg.buckets_along_width, 64, self.size())
@@ -302,8 +317,12 @@ class FeatureSet:
         n0 = self.size()
         xy[:n0], ages[:n0], st[:n0] = self.points, self.ages, self.strengths
         n = C.c_int(n0)
-        check(lib.svo_append_features_from_image(self.device, C.byref(cfg), ptr(img), w, h, w, int(fast_threshold), cap,
-                                                 C.byref(n), ptr(xy), ptr(ages), ptr(st)))
+        if m is not None:
+            check(lib.svo_append_features_from_image_masked(self.device, C.byref(cfg), ptr(img), w, h, w, int(fast_threshold), ptr(m), w, cap,
+                                                            C.byref(n), ptr(xy), ptr(ages), ptr(st)))
+        else:
+            check(lib.svo_append_features_from_image(self.device, C.byref(cfg), ptr(img), w, h, w, int(fast_threshold), cap,
+                                                     C.byref(n), ptr(xy), ptr(ages), ptr(st)))
         self.points, self.ages, self.strengths = xy[:n.value].copy(), ages[:n.value].copy(), st[:n.value].copy()
 
 
@@ -405,6 +424,37 @@ class BatchVisualOdometry:
         valid = np.zeros(self.n_seq, np.int32)
         check(lib.svo_get_last_pose_covariance(self._h, ptr(cov_T), ptr(cov_p), ptr(valid)))
         return cov_T.reshape(-1, 6, 6), cov_p.reshape(-1, 6, 6), valid.astype(bool)
+
+    def set_detection_mask(self, mask, seq=-1):
+        """Keep features off the zero pixels of `mask` (svo_set_detection_mask): an (height, width) uint8 numpy array, or a torch
+        device tensor of that shape and dtype, read through data_ptr() with its own row stride (its producer must have finished,
+        or run on stream()).  seq = -1: the shared mask; a sequence's own mask overrides it.  The mask describes the left image of
+        the frames submitted from now on and is applied when that image is scanned, in the following call.  mask = None clears.
+        Legal with frames in flight.  ValueError for a wrong shape or dtype."""
+        if mask is None:
+            check(lib.svo_set_detection_mask(self._h, seq, None, 0, 0))
+            return
+        if hasattr(mask, "data_ptr"):                                 # a torch tensor
+            if tuple(mask.shape) != (self.height, self.width) or "uint8" not in str(mask.dtype) or mask.stride(1) != 1:
+                raise ValueError("detection mask: (%d, %d) uint8 with unit column stride expected, got %s %s"
+                                 % (self.height, self.width, tuple(mask.shape), mask.dtype))
+            if mask.is_cuda:
+                check(lib.svo_set_detection_mask(self._h, seq, C.c_void_p(mask.data_ptr()), int(mask.stride(0)), 1))
+                return
+            mask = mask.numpy()
+        m = _host_mask(mask, self.height, self.width)
+        check(lib.svo_set_detection_mask(self._h, seq, ptr(m), self.width, 0))
+
+    def clear_detection_mask(self, seq=-1):
+        """No mask from the next frame submitted on (seq = -1: none at all).  The next call still applies the mask of the image it scans."""
+        check(lib.svo_set_detection_mask(self._h, seq, None, 0, 0))
+
+    def detection_mask(self, seq=-1):
+        """The mask in force for the frames submitted next: seq's own, else the shared one -> (height, width) uint8, or None."""
+        out = np.zeros((self.height, self.width), np.uint8)
+        present = C.c_int(0)
+        check(lib.svo_get_detection_mask(self._h, seq, ptr(out), C.byref(present)))
+        return out if present.value else None
 
     def set_rectification(self, left_info, right_info, seq=-1):
         """Rectify raw frames with these calibrations (svo_set_rectification): `seq` (-1: the shared maps of every sequence
@@ -596,6 +646,7 @@ class VisualOdometry(BatchVisualOdometry):
         self._timing = None
         self._rect = None                             # rectification asked for before the context exists: applied at creation
         self._cov = None                              # likewise a pose-covariance mode
+        self._mask = None                             # likewise a detection mask
         self.raw_size = None
         if not self._created:
             self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
@@ -637,6 +688,23 @@ class VisualOdometry(BatchVisualOdometry):
             return super().set_pose_covariance(mode, pixel_sigma)
         self._cov = _lib.check_cov(mode, pixel_sigma)                 # checked now, as the library will: not inside the first frame
 
+    def set_detection_mask(self, mask, seq=-1):
+        if self._created:
+            return super().set_detection_mask(mask, seq)
+        if mask is not None and (getattr(mask, "ndim", 0) != 2 or "uint8" not in str(mask.dtype)):
+            raise ValueError("detection mask: a 2-D uint8 array expected")
+        self._mask = mask                                             # its size is checked against the first frame's
+
+    def clear_detection_mask(self, seq=-1):
+        self._mask = None
+        if self._created:
+            super().clear_detection_mask(seq)
+
+    def detection_mask(self, seq=-1):
+        if not self._created:
+            return None if self._mask is None else np.array(self._mask.cpu() if hasattr(self._mask, "cpu") else self._mask, np.uint8)
+        return super().detection_mask(seq)
+
     def last_pose_covariance(self):
         if not self._created:
             raise _lib.SvoError("last_pose_covariance: no frame yet (call stereo_callback first)")
@@ -671,6 +739,8 @@ class VisualOdometry(BatchVisualOdometry):
                 super().set_input_format(fmt)         # (BatchVisualOdometry.__init__ reset the attribute)
             if self._cov is not None:
                 super().set_pose_covariance(*self._cov)
+            if self._mask is not None:
+                super().set_detection_mask(self._mask)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

@@ -99,6 +99,10 @@ struct RingSlot {
     int cov_mode = SVO_COV_OFF;                  // the pose-covariance mode the slot's frame was issued with
     bool masked = false;                         // ... and whether it came with a mask (h_act's row then holds its flags)
 };
+// Detection masks (svo_set_detection_mask): the two slots of one scope (a sequence, or the shared pair).  cur: the slot in force for
+// the frames submitted from now on (-1: none); last: the slot the most recent frame of this scope recorded for its left image — that
+// frame's image is scanned by the NEXT call, so the setter writes the other one.
+struct MaskPair { uint8_t* buf[2] = {nullptr, nullptr}; int cur = -1, last = -1; };
 
 struct svo_context {
     int device = 0;
@@ -156,6 +160,16 @@ struct svo_context {
     PoseCovRow* d_cov = nullptr;                 // its device address
     std::vector<PoseCovRow> last_cov;            // [B] the rows of the last collected frame ...
     int last_cov_mode = SVO_COV_OFF;             // ... and the mode it was issued with
+    // detection masks (svo_set_detection_mask).  Everything below is empty until the first mask is set.  A mask belongs to a left
+    // image: img_mask[seq] is the mask of the sequence's last submitted left image — what the sequence's NEXT detection applies —
+    // and a frame's row of mask_rows is filled from it when the frame is enqueued.
+    MaskPair shared_mask;
+    std::vector<MaskPair> own_mask;              // [B]
+    std::vector<const uint8_t*> img_mask;        // [B]
+    const uint8_t** h_mask_rows = nullptr;       // pinned [SVO_RING][B] ...
+    const uint8_t** d_mask_rows = nullptr;       // ... and the device copy the masked FAST kernels read (one hipMemcpyAsync per masked frame)
+    uint8_t* h_mask_stage = nullptr;             // pinned [W*H]: a host mask's packed rows on their way to the device
+    hipEvent_t ev_mask_stage = nullptr;          // that copy has run: the staging buffer may be written again
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -332,6 +346,11 @@ extern "C" void svo_destroy(svo_context* c) {
     for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
     for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
     for (const auto& r : c->retired) (void)hipFree(r.p);
+    for (int k = 0; k < 2; k++) if (c->shared_mask.buf[k]) (void)hipFree(c->shared_mask.buf[k]);
+    for (const MaskPair& m : c->own_mask) for (int k = 0; k < 2; k++) if (m.buf[k]) (void)hipFree(m.buf[k]);
+    if (c->d_mask_rows) (void)hipFree((void*)c->d_mask_rows);
+    for (void* p : {(void*)c->h_mask_rows, (void*)c->h_mask_stage}) if (p) (void)hipHostFree(p);
+    if (c->ev_mask_stage) (void)hipEventDestroy(c->ev_mask_stage);
     for (RingSlot& r : c->ring) {
         for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
         if (r.ev_img) (void)hipEventDestroy(r.ev_img);
@@ -425,7 +444,9 @@ static int front_ahead(svo_context* c, const DevBuffers& f, int slot, int stride
 
 // The launch list of one frame (vo.cpp:41-137 as kernels), between the slot's start and done events.
 // with_events: record the stage-boundary events (not inside a graph capture).  n_act: see frame_view.
-static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, DeviceSharing share, int n_act = -1) {
+// mrows: the frame's row of d_mask_rows when its detection applies a mask to some sequence (enqueue_frame), else null.
+static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, DeviceSharing share, int n_act = -1,
+                       const uint8_t* const* mrows = nullptr) {
     hipStream_t s = c->stream;
     const auto record = [&](StageEvent which) { return with_events ? hipEventRecord(c->ring[slot].ev[which], s) : hipSuccess; };
     if (n_act == 0) {                                                  // all idle: the result rows are the whole frame
@@ -446,13 +467,17 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         path |= SVO_PATH_INGEST_AHEAD;
     } else {
         if (f.act) HIPCHK(upload_act(c, slot, s));
-        detected = launch_front_fused(f, dp, stride, s);               // lone stream: ingest + pyramid beside detection, two launches
+        detected = !mrows && launch_front_fused(f, dp, stride, s);     // lone stream: ingest + pyramid beside detection, two launches (a masked frame: the unfused front)
         if (detected) path |= SVO_PATH_FRONT_FUSED;
         else launch_ingest_pyramid(f, dp, stride, s, PYR_BEGIN);       // + the per-frame reset
     }
     c->begin_recorded = ahead;
     HIPCHK(record(EV_PYR));                                            // (fused front: ms[0] = the whole front, ms[1] ~ 0)
-    if (!detected) { launch_detect(f, 0, -1, s); launch_detect(f, 1, -1, s); }
+    if (mrows) {                                                       // both passes behind the masks of the image they scan
+        const MaskArgs m = {mrows, f.geom.W};
+        launch_detect_masked(f, m, 0, -1, s); launch_detect_masked(f, m, 1, -1, s);
+        path |= SVO_PATH_DETECT_MASKED;
+    } else if (!detected) { launch_detect(f, 0, -1, s); launch_detect(f, 1, -1, s); }
     // chained LK launches (a captured graph cannot wait for another stream's event): wait before the launch, record after it
     LkGate* const gate = !c->capturing && share.shared ? &g_lk_gate[c->device] : nullptr;
     if (gate) {
@@ -566,6 +591,32 @@ static int replay_graph(svo_context* c, int slot, int stride, int gn, DeviceShar
     return SVO_OK;
 }
 
+// Detection masks of one frame.  The detection of this call scans each active sequence's PREVIOUS left image, so it applies the mask
+// recorded with that image (img_mask); the mask in force now — the sequence's own, else the shared one — is recorded with this
+// frame's left image for the next call.  Idle sequences keep their record.  *mrows: the frame's row of the device table (uploaded
+// here, on the frame's stream) when some active sequence's detection is masked, else null — the frame is then an unmasked one.
+static int take_masks(svo_context* c, int slot, const uint8_t* active, const uint8_t* const** mrows) {
+    *mrows = nullptr;
+    if (c->img_mask.empty()) return SVO_OK;                           // no mask was ever set
+    const int B = c->d.B;
+    const uint8_t** row = c->h_mask_rows + (size_t)slot * B;
+    bool any = false;
+    for (int i = 0; i < B; i++) {
+        const bool on = !active || active[i];
+        row[i] = on ? c->img_mask[i] : nullptr;
+        any |= row[i] != nullptr;
+        if (!on) continue;
+        MaskPair& p = c->own_mask[i].cur >= 0 ? c->own_mask[i] : c->shared_mask;
+        c->img_mask[i] = p.cur >= 0 ? p.buf[p.cur] : nullptr;
+        if (p.cur >= 0) p.last = p.cur;
+    }
+    if (!any) return SVO_OK;
+    const uint8_t** drow = c->d_mask_rows + (size_t)slot * B;
+    HIPCHK(hipMemcpyAsync((void*)drow, (const void*)row, sizeof(uint8_t*) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    *mrows = drow;
+    return SVO_OK;
+}
+
 // Enqueue one frame.  ptrs: host arrays of B DEVICE image pointers.  active: NULL (every sequence takes the frame) or B flags,
 // checked by check_frame_args.
 static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
@@ -584,10 +635,12 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     }
     const DeviceSharing share = device_sharing(c);                   // read once per frame: every use below sees the same answer
     HIPCHK(hipEventRecord(r.ev[EV_F0], c->stream));
+    const uint8_t* const* mrows = nullptr;
+    if ((rc = take_masks(c, slot, active, &mrows)) != SVO_OK) return rc;
     bool replayed = false;
-    if (c->use_graph && n_act < 0 && c->raw_w == 0)                  // a ragged or rectifying frame runs from the launch list
+    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows)        // a ragged, rectifying or masked frame runs from the launch list
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
-    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act)) != SVO_OK) return rc;
+    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
     r.cov_mode = c->cov_mode; r.masked = active != nullptr;
     c->staged_inputs = false;
@@ -1074,14 +1127,17 @@ extern "C" int svo_fast_score_map(int device, const uint8_t* img, int w, int h, 
     return SVO_OK;
 }
 
-extern "C" int svo_fast_detect(int device, const uint8_t* img, int w, int h, int stride, int threshold,
-                               int cap, float* xy, float* resp, int* n_out) {
+static int fast_detect_stage(int device, const uint8_t* img, int w, int h, int stride, int threshold, const uint8_t* mask, int mask_stride,
+                             int cap, float* xy, float* resp, int* n_out) {
     if (!img || !n_out || w < 7 || h < 7 || stride < w || cap < 0) return fail_arg("bad arguments");
+    if (mask && mask_stride < w) return fail_arg("mask_stride < w");
     int rc = use_device(device); if (rc != SVO_OK) return rc;
-    DevTmp t; uint8_t *dimg, *dsc; int *rows, *dn; float2* dxy; float* dresp;
+    DevTmp t; uint8_t *dimg, *dsc, *dmask = nullptr; int *rows, *dn; float2* dxy; float* dresp;
     HIPCHK(t.put_rows(&dimg, img, w, h, stride)); HIPCHK(t.get(&dsc, (size_t)w * h)); HIPCHK(t.get(&rows, (size_t)h));
     HIPCHK(t.get(&dn, 1)); HIPCHK(t.get(&dxy, (size_t)cap)); HIPCHK(t.get(&dresp, (size_t)cap));
-    launch_fast_score_map(dimg, w, h, threshold, dsc, 0);
+    if (mask) HIPCHK(t.put_rows(&dmask, mask, w, h, mask_stride));
+    if (mask) launch_fast_score_map_masked(dimg, w, h, threshold, dmask, w, dsc, 0);
+    else launch_fast_score_map(dimg, w, h, threshold, dsc, 0);
     launch_score_compact(dsc, w, h, cap, rows, dxy, dresp, dn, 0);
     HIPCHK(hipGetLastError());
     int n = 0;
@@ -1091,6 +1147,15 @@ extern "C" int svo_fast_detect(int device, const uint8_t* img, int w, int h, int
     if (m > 0 && resp) HIPCHK(t.download(resp, dresp, m));
     *n_out = n;
     return SVO_OK;
+}
+extern "C" int svo_fast_detect(int device, const uint8_t* img, int w, int h, int stride, int threshold,
+                               int cap, float* xy, float* resp, int* n_out) {
+    return fast_detect_stage(device, img, w, h, stride, threshold, nullptr, 0, cap, xy, resp, n_out);
+}
+extern "C" int svo_fast_detect_masked(int device, const uint8_t* img, int w, int h, int stride, int threshold,
+                                      const uint8_t* mask, int mask_stride, int cap, float* xy, float* resp, int* n_out) {
+    if (!mask) return fail_arg("null mask");
+    return fast_detect_stage(device, img, w, h, stride, threshold, mask, mask_stride, cap, xy, resp, n_out);
 }
 
 extern "C" int svo_bucket_filter(int device, int img_w, int img_h, int* n_io, float* xy, int* ages, int* strengths,
@@ -1116,11 +1181,14 @@ extern "C" int svo_bucket_filter(int device, int img_w, int img_h, int* n_io, fl
     return SVO_OK;
 }
 
-extern "C" int svo_append_features_from_image(int device, const svo_config* cfg_in, const uint8_t* img, int w, int h, int stride,
-                                              int fast_threshold, int cap, int* n_io, float* xy, int* ages, int* strengths) {
+// mask: null (svo_append_features_from_image), or the caller's host mask (svo_append_features_from_image_masked)
+static int append_features_stage(int device, const svo_config* cfg_in, const uint8_t* img, int w, int h, int stride, int fast_threshold,
+                                 const uint8_t* mask, int mask_stride, int cap, int* n_io, float* xy, int* ages, int* strengths) {
     if (!img || !n_io || *n_io < 0 || stride < w || cap < *n_io) return fail_arg("bad arguments");
     svo_config cfg; if (cfg_in) cfg = *cfg_in; else svo_config_default(&cfg);
     cfg.channels = 1;                                                             // stage entry points are single-channel
+    if (mask && mask_stride < w) return fail_arg("mask_stride < w");
+    if (mask && cfg.features_per_bucket > 1) return fail_arg("detection masks need features_per_bucket == 1 (the general bucket walk takes none)");
     svo_context* c = nullptr; int rc = stage_ctx(cfg, device, w, h, *n_io, &c); if (rc != SVO_OK) return rc;
     const int n = *n_io;
     if (n > 0) {
@@ -1139,12 +1207,30 @@ extern "C" int svo_append_features_from_image(int device, const svo_config* cfg_
     HIPCHK(hipMemsetAsync(c->d.bucket_keys, 0, sizeof(unsigned long long) * (size_t)c->d.NB, c->stream));
     HIPCHK(hipMemsetAsync(c->d.bucket_rowcnt, 0, sizeof(int) * (size_t)c->d.cfg.buckets_along_height, c->stream));
     HIPCHK(hipMemsetAsync(c->d.emit_ticket, 0, sizeof(int), c->stream));
-    launch_detect(c->d, 0, fast_threshold, c->stream);
+    DevTmp t;
+    if (mask) {
+        uint8_t* dmask; const uint8_t** drow;
+        HIPCHK(hipStreamSynchronize(c->stream));                                  // the uploads below are synchronous copies on the null stream
+        HIPCHK(t.put_rows(&dmask, mask, w, h, mask_stride));
+        HIPCHK(t.put(&drow, &dmask, 1));
+        launch_detect_masked(c->d, MaskArgs{drow, w}, 0, fast_threshold, c->stream);
+    } else launch_detect(c->d, 0, fast_threshold, c->stream);
     HIPCHK(hipGetLastError());
-    int m = svo_get_features(c, 0, cap, xy, ages, strengths);
+    int m = svo_get_features(c, 0, cap, xy, ages, strengths);                     // synchronises the stream: the scratch mask may go
     if (m < 0) return m;
     *n_io = m;
+    g_stage_path = mask ? SVO_PATH_DETECT_MASKED : 0;
     return SVO_OK;
+}
+extern "C" int svo_append_features_from_image(int device, const svo_config* cfg, const uint8_t* img, int w, int h, int stride,
+                                              int fast_threshold, int cap, int* n_io, float* xy, int* ages, int* strengths) {
+    return append_features_stage(device, cfg, img, w, h, stride, fast_threshold, nullptr, 0, cap, n_io, xy, ages, strengths);
+}
+extern "C" int svo_append_features_from_image_masked(int device, const svo_config* cfg, const uint8_t* img, int w, int h, int stride,
+                                                     int fast_threshold, const uint8_t* mask, int mask_stride, int cap, int* n_io,
+                                                     float* xy, int* ages, int* strengths) {
+    if (!mask) return fail_arg("null mask");
+    return append_features_stage(device, cfg, img, w, h, stride, fast_threshold, mask, mask_stride, cap, n_io, xy, ages, strengths);
 }
 
 extern "C" int svo_build_pyramid(int device, const uint8_t* img, int w, int h, int stride, int win, int max_level,
@@ -1548,5 +1634,64 @@ extern "C" int svo_convert_gray(int device, int format, const uint8_t* src, int 
     launch_convert_gray(g, dsrc + mis, w, h, (int)rowb, dout, 0);
     HIPCHK(hipGetLastError());
     HIPCHK(t.download(out, dout, n));
+    return SVO_OK;
+}
+
+// ================================================================================================
+// Detection masks (svo.h): the setter and the getter.  The per-frame side is take_masks / issue_frame.
+// ================================================================================================
+// first use: the tables every masked frame needs.  All or nothing, so that img_mask.empty() says "no mask was ever set".
+static int mask_tables(svo_context* c) {
+    if (!c->img_mask.empty()) return SVO_OK;
+    const size_t B = (size_t)c->d.B, n = (size_t)c->d.geom.W * c->d.geom.H;
+    if (!c->h_mask_rows) { HIPCHK(hipHostMalloc((void**)&c->h_mask_rows, sizeof(uint8_t*) * SVO_RING * B)); memset((void*)c->h_mask_rows, 0, sizeof(uint8_t*) * SVO_RING * B); }
+    if (!c->d_mask_rows) HIPCHK(hipMalloc((void**)&c->d_mask_rows, sizeof(uint8_t*) * SVO_RING * B));
+    if (!c->h_mask_stage) HIPCHK(hipHostMalloc((void**)&c->h_mask_stage, n));
+    if (!c->ev_mask_stage) HIPCHK(hipEventCreateWithFlags(&c->ev_mask_stage, hipEventDisableTiming));
+    c->own_mask.assign(B, MaskPair{});
+    c->img_mask.assign(B, nullptr);
+    return SVO_OK;
+}
+
+extern "C" int svo_set_detection_mask(svo_context* c, int seq, const uint8_t* mask, int stride, int on_device) {
+    if (!c) return fail_arg("null context");
+    if (c->d.CN != 1) return fail_arg("svo_set_detection_mask: a channels = 3 context runs FAST on the bytes of the interleaved rows, where pixel positions mean nothing");
+    if (c->d.cfg.features_per_bucket > 1) return fail_arg("svo_set_detection_mask: detection masks need features_per_bucket == 1 (the general bucket walk takes none)");
+    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if (!mask) {                                                     // clear: the frames submitted from now on record no mask
+        if (seq < 0) { c->shared_mask.cur = -1; for (MaskPair& p : c->own_mask) p.cur = -1; }
+        else if (!c->own_mask.empty()) c->own_mask[seq].cur = -1;
+        return SVO_OK;
+    }
+    const int W = c->d.geom.W, H = c->d.geom.H;
+    if (stride < W) return fail_arg("svo_set_detection_mask: stride < width");
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = mask_tables(c)) return rc;
+    MaskPair& p = seq < 0 ? c->shared_mask : c->own_mask[seq];
+    const int t = p.last == 0 ? 1 : 0;                               // not the slot the last frame's left image owns
+    if (!p.buf[t]) HIPCHK(hipMalloc((void**)&p.buf[t], (size_t)W * H));
+    // on the frame stream, as svo_reset_sequence's kernel: behind the detection of every frame submitted so far (the last of them
+    // reads the OTHER slot), before that of every later frame
+    if (on_device) HIPCHK(hipMemcpy2DAsync(p.buf[t], (size_t)W, mask, (size_t)stride, (size_t)W, (size_t)H, hipMemcpyDeviceToDevice, c->stream));
+    else {
+        HIPCHK(hipEventSynchronize(c->ev_mask_stage));               // the previous host mask has left the staging buffer (a fresh event is complete)
+        pack_rows(c->h_mask_stage, mask, (size_t)W, (size_t)H, (size_t)stride);
+        HIPCHK(hipMemcpyAsync(p.buf[t], c->h_mask_stage, (size_t)W * H, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipEventRecord(c->ev_mask_stage, c->stream));
+    }
+    p.cur = t;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_detection_mask(svo_context* c, int seq, uint8_t* out, int* present) {
+    if (!c) return fail_arg("null context");
+    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    const MaskPair* p = &c->shared_mask;
+    if (seq >= 0 && !c->own_mask.empty() && c->own_mask[seq].cur >= 0) p = &c->own_mask[seq];
+    if (present) *present = p->cur >= 0;
+    if (p->cur < 0 || !out) return SVO_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, p->buf[p->cur], (size_t)c->d.geom.W * c->d.geom.H, hipMemcpyDeviceToHost));
     return SVO_OK;
 }

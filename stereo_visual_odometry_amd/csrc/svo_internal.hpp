@@ -164,6 +164,19 @@ __device__ __forceinline__ bool bucket_of(const BucketGrid& g, float x, float y,
     bh = (int)(y / (float)g.bucket_h); bw = (int)(x / (float)g.bucket_w);
     return bh >= 0 && bw >= 0 && bh >= g.start_row && bh < g.bah && bw < g.baw;
 }
+// Detection masks (svo.h, svo_set_detection_mask): does the mask (W x H bytes, rows `stride` apart, non-zero = features allowed) keep an
+// entry of the list appendFeaturesFromImage hands to the grid?  KeyPointsFilter::runByPixelsMask's rule, written once: the byte at the
+// rounded position ((int)(v + 0.5f), truncation toward zero), clamped into the image (the lower clamp only guards the load: the
+// frame pipeline's tracks are never negative, vo.cpp:341-359).  Both call sites — the FAST tile's sink and the track offer — use it.
+__host__ __device__ inline bool mask_keeps(const uint8_t* mask, int stride, int W, int H, float x, float y) {
+    int ix = (int)(x + 0.5f), iy = (int)(y + 0.5f);
+    ix = ix < W - 1 ? ix : W - 1; iy = iy < H - 1 ? iy : H - 1;
+    ix = ix > 0 ? ix : 0; iy = iy > 0 ? iy : 0;
+    return mask[(size_t)iy * (size_t)stride + ix] != 0;
+}
+// The masks of one detection launch: rows[seq] = the mask of the left image sequence seq's detection scans (library-owned device
+// memory), or null: everything allowed there.  Kernel arguments of their own, like CovArgs: no existing kernel's argument block changes.
+struct MaskArgs { const uint8_t* const* rows; int stride; };
 // what Bucket::add_feature compares (feature_set.cpp:16-18); the division truncates toward zero, as C's does
 __device__ __forceinline__ int bucket_score(int age, int strength, int fast_thr) { return age + (strength - fast_thr) / 20; }
 // capacity 1: (score, first come, strength) as one key for a 64-bit atomicMax; order = the candidate's rank in the input list
@@ -216,6 +229,8 @@ void launch_frame_begin(const DevBuffers& d, hipStream_t s);
 struct SeqProjection { float Pl[12], Pr[12]; int set; };
 void launch_reset_seq(const DevBuffers& d, int seq, const SeqProjection& p, hipStream_t s);
 void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s);   // pass 0: FAST_THRESHOLD, pass 1: /4 if needed; th_override >= 0 replaces it
+// the same pass with detection masks (features_per_bucket == 1 only): k_fast_masked / k_fast_strided_masked, then the plain emit
+void launch_detect_masked(const DevBuffers& d, const MaskArgs& m, int pass, int th_override, hipStream_t s);
 // grid_n = max features that can enter LK; early_out: a feature stops at its first pass with status 0 (frame pipeline) or runs all four (member call)
 bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out);   // false: no kernel built for this (window, channels, summation mode) — nothing ran
 void launch_compact(const DevBuffers& d, hipStream_t s);
@@ -240,6 +255,8 @@ void launch_convert_gray(const GreyIn& g, const uint8_t* src, int w, int h, int 
 
 // stage helpers
 void launch_fast_score_map(const uint8_t* img_dev, int w, int h, int threshold, uint8_t* score_dev, hipStream_t s);
+// the score map of the keypoints a mask keeps (the mask applied to the NMS survivors): svo_fast_detect_masked
+void launch_fast_score_map_masked(const uint8_t* img_dev, int w, int h, int threshold, const uint8_t* mask_dev, int mask_stride, uint8_t* score_dev, hipStream_t s);
 void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* row_counts_dev, float2* xy_dev, float* resp_dev, int* n_dev, hipStream_t s);
 void launch_bucket_general(const BucketGrid& g, int per_bucket, int n, const float2* xy, const int* ages, const int* strs,
                            float2* slot_xy, int* slot_age, int* slot_str, int* slot_n,

@@ -779,7 +779,9 @@ __device__ __forceinline__ void bucket_offer(const DevBuffers& d, int seq, int b
 
 // the tracks the feature set already holds, offered to the grid (feature_set.cpp:20-53, 122-124) — the first pass's FAST threads
 // share them out before they scan their tiles, the second pass's offer is made by the last block of the first pass's emit
-static __device__ __forceinline__ void offer_tracks(const DevBuffers& d, int seq, int fb, int n, int first, int step) {
+// (mask: the detection mask of the image the tracks lie in, or null — a track it filters out makes no offer, svo.h)
+template <bool MASKED = false>
+static __device__ __forceinline__ void offer_tracks(const DevBuffers& d, int seq, int fb, int n, int first, int step, const uint8_t* mask = nullptr, int mstride = 0) {
     const BucketGrid g = grid_of(d);
     const float2* xy = d.feat_xy[fb] + (size_t)seq * d.CAP;
     const int* age = d.feat_age[fb] + (size_t)seq * d.CAP;
@@ -789,6 +791,7 @@ static __device__ __forceinline__ void offer_tracks(const DevBuffers& d, int seq
         const int a = age[i], st = str[i];
         int bh, bw;
         if (!bucket_of(g, p.x, p.y, bh, bw) || a >= g.age_thr) continue;                  // feature_set.cpp:26
+        if constexpr (MASKED) if (mask && !mask_keeps(mask, mstride, d.geom.W, d.geom.H, p.x, p.y)) continue;
         bucket_offer(d, seq, bh, bw, make_bucket_key(bucket_score(a, st, g.fast_thr), (unsigned)i, st));
     }
 }
@@ -817,6 +820,24 @@ struct BucketSink {
         const unsigned n_old = pass == 0 ? (unsigned)d.st[seq].n_feat : (unsigned)d.st[seq].n_old;   // pass 0: the set is still the old one
         const unsigned order = n_old + (unsigned)(gy * d.geom.W + gx);                               // raster rank keeps cv::FAST's output order
         bucket_offer(d, seq, bh, bw, make_bucket_key(bucket_score(0, s, g.fast_thr), order, s));
+    }
+};
+
+// the same behind a detection mask: one byte load for a pixel that survived NMS (one in a few hundred), none for the others.
+// The survivor keeps its raster rank, so ties break as in the filtered list.  mask == null (a sequence without a mask in a
+// launch where others have one): everything is allowed.
+struct MaskedBucketSink {
+    const DevBuffers& d; int seq, pass; const uint8_t* mask; int mstride;
+    __device__ __forceinline__ void operator()(int gx, int gy, int s, bool keep) const {
+        if (!keep || (mask && !mask_keeps(mask, mstride, d.geom.W, d.geom.H, (float)gx, (float)gy))) return;
+        BucketSink{d, seq, pass}(gx, gy, s, true);
+    }
+};
+// the stage call's score map of the keypoints a mask keeps
+struct MaskedScoreMapSink {
+    uint8_t* score; int W, H; const uint8_t* mask; int mstride;
+    __device__ __forceinline__ void operator()(int gx, int gy, int s, bool keep) const {
+        score[(size_t)gy * W + gx] = keep && mask_keeps(mask, mstride, W, H, (float)gx, (float)gy) ? (uint8_t)s : (uint8_t)0;
     }
 };
 
@@ -888,13 +909,16 @@ static __device__ __forceinline__ void fast_tile(const uint8_t* img, int istride
 // or false if the pass does not run for the sequence.  Pass 0 of a capacity-1 context (`offer`): the existing tracks enter the
 // grid here (no launch of their own), this thread's share being first, first + step, ...
 struct FastFrame { int seq; const uint8_t* img; int istride; };
-static __device__ __forceinline__ bool fast_frame_begin(const DevBuffers& d, int pass, int bz, bool offer, int first, int step, FastFrame& f) {
+template <bool MASKED = false>
+static __device__ __forceinline__ bool fast_frame_begin(const DevBuffers& d, int pass, int bz, bool offer, int first, int step, FastFrame& f,
+                                                        const MaskArgs* m = nullptr) {
     f.seq = seq_of(d, bz);
     const SeqState& s = d.st[f.seq];
     if (!detect_pass_runs(s, pass, true)) return false;
     f.img = d.CN == 3 ? d.fastimg + fastimg_index(d, f.seq, s.slot_img_t0) : d.pyr + pyr_index(d, f.seq, s.slot_img_t0, 0) + d.geom.lv[0].off;
     f.istride = d.CN == 3 ? d.geom.W : d.geom.lv[0].stride;
-    if (offer && pass == 0) offer_tracks(d, f.seq, s.feat_buf, s.n_feat, first, step);
+    if constexpr (MASKED) { if (offer && pass == 0) offer_tracks<true>(d, f.seq, s.feat_buf, s.n_feat, first, step, m->rows[f.seq], m->stride); }
+    else if (offer && pass == 0) offer_tracks(d, f.seq, s.feat_buf, s.n_feat, first, step);
     return true;
 }
 // tile (bx, by) of the fx x fy tiles of sequence slot bz, survivors to the bucket keys: a block of k_fast<0> or of k_front_a
@@ -930,6 +954,30 @@ __global__ __launch_bounds__(256) void k_fast_strided(DevBuffers d, int pass, in
         fast_tile(f.img, f.istride, d.geom.W, d.geom.H, (t % fx) * FT_W, (t / fx) * FT_H, threshold, BucketSink{d, f.seq, pass});
         __syncthreads();                                              // the tile arrays in LDS are reused by the next tile
     }
+}
+
+// ---- detection masks (svo.h, svo_set_detection_mask): the two FAST kernels of the capacity-1 pipeline with MaskArgs.  A sequence
+// whose row is null is offered and scanned unfiltered in the same launch.  The emit kernels are the plain ones: a filtered
+// entry made no offer, and pass 1's re-offer of the new set (bucket_emit_body) offers a set the mask has already been applied to.
+static __device__ __forceinline__ void fast_tile_masked(const DevBuffers& d, const FastFrame& f, int pass, int threshold, int x0, int y0, const uint8_t* mask, int mstride) {
+    fast_tile(f.img, f.istride, d.geom.W, d.geom.H, x0, y0, threshold, MaskedBucketSink{d, f.seq, pass, mask, mstride});
+}
+__global__ __launch_bounds__(256) void k_fast_masked(DevBuffers d, MaskArgs m, int pass, int threshold) {
+    FastFrame f;
+    if (!fast_frame_begin<true>(d, pass, blockIdx.z, true, (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x, gridDim.x * gridDim.y * 256, f, &m)) return;
+    fast_tile_masked(d, f, pass, threshold, blockIdx.x * FT_W, blockIdx.y * FT_H, m.rows[f.seq], m.stride);
+}
+__global__ __launch_bounds__(256) void k_fast_strided_masked(DevBuffers d, MaskArgs m, int pass, int threshold, int fx, int fy) {
+    FastFrame f;
+    if (!fast_frame_begin<true>(d, pass, blockIdx.z, true, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, f, &m)) return;
+    const uint8_t* mask = m.rows[f.seq];
+    for (int t = blockIdx.x; t < fx * fy; t += gridDim.x) {
+        fast_tile_masked(d, f, pass, threshold, (t % fx) * FT_W, (t / fx) * FT_H, mask, m.stride);
+        __syncthreads();                                              // the tile arrays in LDS are reused by the next tile
+    }
+}
+__global__ __launch_bounds__(256) void k_fast_score_map_masked(const uint8_t* img, int w, int h, int threshold, const uint8_t* mask, int mstride, uint8_t* score) {
+    fast_tile(img, w, w, h, blockIdx.x * FT_W, blockIdx.y * FT_H, threshold, MaskedScoreMapSink{score, w, h, mask, mstride});
 }
 
 static dim3 fast_grid(int w, int h, int n_seq) { return dim3((w + FT_W - 1) / FT_W, (h + FT_H - 1) / FT_H, n_seq); }
@@ -977,6 +1025,9 @@ __global__ void k_scan_rows(int* row_counts, int h, int* n_out) {
 __global__ void k_score_row_emit(const uint8_t* score, int w, const int* row_off, int cap, float2* xy, float* resp) {
     const int y = blockIdx.x;
     score_row_emit(score + (size_t)y * w, w, row_off[y], cap, [=](int idx, int x, int s) { xy[idx] = make_float2((float)x, (float)y); resp[idx] = (float)s; });
+}
+void launch_fast_score_map_masked(const uint8_t* img_dev, int w, int h, int threshold, const uint8_t* mask_dev, int mask_stride, uint8_t* score_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_fast_score_map_masked, fast_grid(w, h, 1), dim3(256), 0, st, img_dev, w, h, threshold, mask_dev, mask_stride, score_dev);
 }
 void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* row_counts_dev, float2* xy_dev, float* resp_dev, int* n_dev, hipStream_t st) {
     hipLaunchKernelGGL(k_score_row_count, dim3(h), dim3(64), 0, st, score_dev, w, row_counts_dev);
@@ -1275,6 +1326,22 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
         return;
     }
     hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, d, pass, th);
+    hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, g.z), dim3(EMIT_THREADS), 0, st, d, pass);
+}
+
+// A detection pass behind masks: the masked FAST kernel of the pass (which offers the filtered tracks itself in pass 0), then the
+// plain emit.  Capacity 1 only (svo_set_detection_mask refuses the others).
+void launch_detect_masked(const DevBuffers& d, const MaskArgs& m, int pass, int th_override, hipStream_t st) {
+    int th = pass == 0 ? d.cfg.fast_threshold : d.cfg.fast_threshold / 4;            // vo.cpp:325 / :329-330
+    if (th_override >= 0) th = th_override;
+    const dim3 g = fast_grid(d);
+    static const bool strided_off = getenv("SVO_SECOND_PASS_STRIDED") && atoi(getenv("SVO_SECOND_PASS_STRIDED")) == 0;
+    if (pass == 1 && d.B > SVO_LONE_MAX_SEQ && !strided_off) {
+        hipLaunchKernelGGL(k_fast_strided_masked, dim3(FAST_STRIDED_BLOCKS, 1, g.z), dim3(256), 0, st, d, m, pass, th, (int)g.x, (int)g.y);
+        hipLaunchKernelGGL(k_bucket_emit_strided, dim3(EMIT_STRIDED_BLOCKS, g.z), dim3(EMIT_THREADS), 0, st, d, pass, d.cfg.buckets_along_height);
+        return;
+    }
+    hipLaunchKernelGGL(k_fast_masked, g, dim3(256), 0, st, d, m, pass, th);
     hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, g.z), dim3(EMIT_THREADS), 0, st, d, pass);
 }
 

@@ -1,5 +1,5 @@
 """Single-stream latency without Python in the loop: renders the bench scene's frames, builds tools/svo_latency.cpp (plain g++
-against the C-ABI) and runs it.   python tools/latency_cpp.py [win] [calls]   (MI355X box)"""
+against the C-ABI) and runs it.   python tools/latency_cpp.py [win] [calls] [--covariance | --mask]   (MI355X box; the flag is svo_latency's)"""
 import os
 import subprocess
 import sys
@@ -25,5 +25,5 @@ for movers in (0.0, 0.3):
             f.write(l.tobytes()); f.write(r.tobytes())
         path = f.name
     print("movers %.1f, window %s" % (movers, win), flush=True)
-    subprocess.check_call([exe, path, win, calls])
+    subprocess.check_call([exe, path, win, calls] + (["2.0"] + sys.argv[3:] if len(sys.argv) > 3 else []))
     os.unlink(path)

@@ -166,10 +166,10 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
-    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out;
+    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path;
     bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false;
     for (int i = 3; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--rectify")) {
@@ -182,6 +182,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--calib")) calib = argv[i + 1];
         else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
         else if (!strcmp(argv[i], "--covariance")) cov_out = argv[i + 1];   // one row per frame: valid, then the 21 upper-triangle entries of cov_T (svo.h), row by row
+        else if (!strcmp(argv[i], "--mask")) mask_path = argv[i + 1];       // a static detection mask (svo.h): PGM or PNG of the frame size, non-zero = features allowed; needs --gray 1 or 2
         else if (!strcmp(argv[i], "--device")) default_device() = std::atoi(argv[i + 1]);
     }
     Mat34f Pl = {322.11376f, 0, 327.47336f, 0, 0, 322.11376f, 176.33722f, 0, 0, 0, 1, 0};               // main.cpp:357-362
@@ -201,6 +202,12 @@ int main(int argc, char** argv) {
     std::ofstream res(out);
     if (!res) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 2; }
     res << "x,y,z,gtx,gty\n";
+    Gray mask;
+    if (!mask_path.empty()) {
+        std::vector<uint8_t> d;
+        if (read_file(mask_path, d)) mask = mask_path.size() > 4 && mask_path.substr(mask_path.size() - 4) == ".png" ? read_png(d) : read_pgm(d);
+        if (!mask.ok()) { std::fprintf(stderr, "cannot read mask %s\n", mask_path.c_str()); return 2; }
+    }
     std::ofstream cov;
     if (!cov_out.empty()) {
         cov.open(cov_out);
@@ -224,6 +231,10 @@ int main(int argc, char** argv) {
         for (int i = 0; i < N_FRAMES; i++) {
             Gray l = read_image(folder + "/left", i), r = read_image(folder + "/right", i);
             if (!l.ok() || !r.ok() || l.w != r.w || l.h != r.h) break;                                   // stop at the first missing pair
+            if (i == 0 && mask.ok()) {
+                if (rect_l.empty() && (mask.w != l.w || mask.h != l.h)) { std::fprintf(stderr, "--mask: %d x %d, the frames are %d x %d\n", mask.w, mask.h, l.w, l.h); return 2; }
+                vo.set_detection_mask(mask.px.data(), mask.w, mask.w, mask.h);
+            }
             double gtx = 0, gty = 0;
             if (has_gt) {
                 std::string xs, ys, dxs, dys;
