@@ -164,6 +164,7 @@ int svo_get_lk_registers_left(svo_context* ctx);
 #define SVO_PATH_GRAPH          32   /* the frame replayed a captured hipGraph (SVO_GRAPH=1); the other bits are the capture's */
 #define SVO_PATH_INPUT_CONVERTED 64  /* the frame's ingest converted the caller's pixels to grey (svo_set_input_format) */
 #define SVO_PATH_POSE_COV       128  /* the frame ran k_pose_cov after its refine (svo_set_pose_covariance; also set by svo_pose_covariance) */
+#define SVO_PATH_CLAHE          512  /* the frame's images were equalised (two launches) in front of its ingest (svo_set_clahe; also set by svo_clahe) */
 #define SVO_PATH_DETECT_MASKED  256  /* the frame's detection applied a detection mask (svo_set_detection_mask; also set by svo_append_features_from_image_masked) */
 int svo_get_last_frame_path(svo_context* ctx);
 
@@ -283,6 +284,45 @@ int svo_clear_rectification(svo_context* ctx);
  * whose ingest converted.  Under SVO_GRAPH=1 a converting frame replays a graph captured for its format (the format is part of
  * what a slot's graph is keyed on, so a format switch re-captures); results are identical to the launch list's. */
 int svo_set_input_format(svo_context* ctx, int format);
+
+/* ---- CLAHE: contrast-limited adaptive histogram equalisation in frame ingest ------------------------------------------------
+ * Replaces cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply() on both images of a frame (VINS-Fusion's `equalize`,
+ * ORB-SLAM3's preprocessing): FAST's threshold and LK's minimum-eigenvalue cut are absolute grey-level quantities, so shadow,
+ * tunnels and over-exposed scenes lose features without it.  A channels == 1 context only.  The input is the caller's frame in
+ * grey, in_width x in_height pixels (the raw size when rectifying), after the input-format conversion and before rectification
+ * — remap(clahe(grey(raw))) — each camera from its own histograms.  Detection masks live in the rectified geometry and are
+ * unaffected.
+ *
+ * Definition (w x h image, tiles_x x tiles_y tiles, each 1 .. 16):
+ *  1. Padding.  w % tiles_x == 0 && h % tiles_y == 0: the extended image is the image.  Otherwise it is the image extended on the
+ *     right by tiles_x - (w % tiles_x) columns and at the bottom by tiles_y - (h % tiles_y) rows with REFLECT_101 — a dimension
+ *     that IS divisible is then extended by a whole tiles_* (OpenCV's quirk).  tw = ext_w / tiles_x, th = ext_h / tiles_y,
+ *     area = tw th.  An extension beyond w - 1 / h - 1 (REFLECT_101 undefined) or tw / th == 0 is rejected.
+ *  2. Per tile: the 256-bin histogram of its tw x th pixels of the extended image.  clip_limit > 0:
+ *     clip = max((int)(clip_limit * area / 256), 1) (product and quotient in double); every bin above clip is cut to clip,
+ *     clipped = the sum of the excess; batch = clipped / 256, residual = clipped - 256 batch; every bin += batch; if residual > 0,
+ *     step = max(256 / residual, 1) and for (i = 0; i < 256 && residual > 0; i += step, residual--) hist[i]++.
+ *     clip_limit <= 0: no clipping.
+ *  3. LUT: scale = 255.0f / (float)area; with the running integer sum s over the bins,
+ *     lut[i] = clamp(rint_half_even((float)s * scale), 0, 255).
+ *  4. Interpolation, all f32, every operation rounded on its own (no FMA), in this order; inv_tw = 1.0f / tw, inv_th = 1.0f / th.
+ *     Pixel (x, y) of the original image with value v: txf = (float)x * inv_tw - 0.5f; tx1 = floor(txf), tx2 = tx1 + 1;
+ *     xa = txf - (float)tx1, xa1 = 1.0f - xa; then tx1 = max(tx1, 0), tx2 = min(tx2, tiles_x - 1); the same in y;
+ *     res = (L[ty1][tx1][v] xa1 + L[ty1][tx2][v] xa) ya1 + (L[ty2][tx1][v] xa1 + L[ty2][tx2][v] xa) ya;
+ *     out = clamp(rint_half_even(res), 0, 255).
+ * PARITY UNPINNED: this restates cv::CLAHE::apply for 8-bit images from memory of OpenCV 4.x clahe.cpp; equality with OpenCV is
+ * believed, not measured (no OpenCV on the machines this was built on).  The tests pin the kernels to a numpy restatement of
+ * exactly the text above, bit for bit.
+ *
+ * svo_set_clahe: on = 0 switches it off (the other arguments are not looked at).  Host state like svo_set_input_format: legal with
+ * frames in flight, every frame carries the setting it was issued with, from the next frame submitted.  SVO_ERR_ARG: a
+ * channels == 3 context, tiles outside 1 .. 16, a non-finite clip_limit, a geometry rule 1 rejects for the context's input size
+ * (checked when the setter runs; if svo_set_rectification* later changes the raw size to one rule 1 rejects, the frame submit
+ * fails with SVO_ERR_STATE).  With CLAHE off a context launches exactly what it always did and no new path bit shows; with it on a
+ * frame runs two launches (per-tile LUTs, then interpolation into a library-owned mono8 staging frame) in front of its unchanged
+ * mono8 ingest, on the stream the ingest runs on, and reports SVO_PATH_CLAHE (and SVO_PATH_INPUT_CONVERTED when its format
+ * converts).  Idle sequences of a ragged frame are not touched.  Under SVO_GRAPH=1 CLAHE frames run from the launch list. */
+int svo_set_clahe(svo_context* ctx, int on, double clip_limit, int tiles_x, int tiles_y);
 
 /* ---- Pose covariance ------------------------------------------------------------------------------------------------------
  * A 6x6 covariance with every pose, computed on the device right after the refine and written into the results ring beside the
@@ -500,6 +540,12 @@ int svo_rectify_image(int device, const int16_t* map1, const uint16_t* map2, int
  * alone, on the kernels' device functions.  src: h rows of w pixels in `format` (SVO_INPUT_*), `stride` bytes apart; out: w*h
  * bytes, packed. */
 int svo_convert_gray(int device, int format, const uint8_t* src, int w, int h, int stride, uint8_t* out);
+
+/* replaces: cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(grey(src), out): the CLAHE section's stage alone, on the
+ * frame pipeline's two kernels.  src: h rows of w pixels in `format` (SVO_INPUT_*), `stride` bytes apart; out: w*h grey bytes,
+ * packed.  SVO_ERR_ARG as svo_set_clahe's. */
+int svo_clahe(int device, int format, const uint8_t* src, int w, int h, int stride,
+              double clip_limit, int tiles_x, int tiles_y, uint8_t* out);
 
 /* replaces: getInverseTransform(rotation, translation)  (vo.h:469-470, vo.cpp:246-258): [R t; 0 1]^-1, 4x4 row-major.
  * Runs the device function the frame pipeline ends with (one tiny launch). */

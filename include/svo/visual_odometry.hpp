@@ -211,6 +211,7 @@ class VisualOdometry {                                               // include/
             if (rect_) apply_rectification();
             if (in_format_ != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx_, in_format_));
             if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
+            if (clahe_on_) svo_throw(svo_set_clahe(ctx_, 1, clahe_clip_, clahe_tx_, clahe_ty_));
             if (!mask_.empty()) {
                 if ((int)mask_.size() != width_ * height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
                 svo_throw(svo_set_detection_mask(ctx_, -1, mask_.data(), width_, 0));
@@ -316,6 +317,18 @@ class VisualOdometry {                                               // include/
             throw std::runtime_error("set_pose_covariance: bad mode or pixel_sigma");
         cov_mode_ = mode; cov_sigma_ = pixel_sigma;
     }
+    // Equalise both images of every frame passed from now on (svo_set_clahe; replaces cv::createCLAHE(clip, Size(tx, ty))->apply()
+    // on the caller's CPU): on the grey frame, after set_input_encoding's conversion and before rectification.  tx, ty: 1 .. 16.
+    // Before the first frame the setting is kept and applied when the context is created; bad tiles or a non-finite clip throw at once.
+    void set_clahe(double clip = 2.0, int tx = 8, int ty = 8) {
+        if (ctx_) svo_throw(svo_set_clahe(ctx_, 1, clip, tx, ty));
+        else if (tx < 1 || tx > 16 || ty < 1 || ty > 16 || !std::isfinite(clip)) throw std::runtime_error("set_clahe: tiles must be 1 .. 16 and clip finite");
+        clahe_on_ = true; clahe_clip_ = clip; clahe_tx_ = tx; clahe_ty_ = ty;
+    }
+    void clear_clahe() {
+        clahe_on_ = false;
+        if (ctx_) svo_throw(svo_set_clahe(ctx_, 0, 0., 0, 0));
+    }
     // Keep features off the zero bytes of `mask` (svo_set_detection_mask): height rows of width bytes, `stride` apart (0: packed), at
     // the frame's size (the rectified size of a rectifying object).  The mask describes the left image of the frames passed from
     // now on and is applied when that image is scanned, in the following call; a static mask is set once.  Before the first frame
@@ -382,6 +395,7 @@ class VisualOdometry {                                               // include/
     int in_format_ = SVO_INPUT_MONO8;                                 // set_input_encoding (applied once the context exists)
     int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
     std::vector<uint8_t> mask_;                                       // set_detection_mask before the first frame: installed at creation
+    bool clahe_on_ = false; double clahe_clip_ = 2.0; int clahe_tx_ = 8, clahe_ty_ = 8;   // set_clahe (applied once the context exists)
 };
 
 }   // namespace visual_odometry

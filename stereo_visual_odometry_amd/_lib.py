@@ -84,6 +84,12 @@ PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_F
 PATH_INPUT_CONVERTED = 64
 PATH_POSE_COV = 128
 PATH_DETECT_MASKED = 256
+PATH_CLAHE = 512
+# CLAHE (svo.h): the equalisation in front of frame ingest, and the stage alone
+lib.svo_set_clahe.restype = C.c_int
+lib.svo_set_clahe.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]
+lib.svo_clahe.restype = C.c_int
+lib.svo_clahe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
 # detection masks (svo.h): mask is a host or device pointer to height rows of width bytes
 lib.svo_set_detection_mask.restype = C.c_int
 lib.svo_set_detection_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
@@ -150,6 +156,7 @@ EXPORTS = [
     "svo_set_input_format", "svo_convert_gray",
     "svo_set_pose_covariance", "svo_get_last_pose_covariance", "svo_pose_covariance",
     "svo_set_detection_mask", "svo_get_detection_mask", "svo_fast_detect_masked", "svo_append_features_from_image_masked",
+    "svo_set_clahe", "svo_clahe",
 ]
 
 
@@ -232,3 +239,17 @@ def input_format(fmt):
     if not 0 <= fmt < len(INPUT_BPP):
         raise ValueError("unknown input format %d" % fmt)
     return fmt
+
+
+def check_clahe(clip_limit, tiles):
+    """(clip_limit, tiles) as svo_set_clahe checks them before it looks at a size -> (float, tiles_x, tiles_y); ValueError otherwise."""
+    clip = float(clip_limit)
+    try:
+        tx, ty = (int(t) for t in tiles)
+    except (TypeError, ValueError):
+        raise ValueError("tiles must be a pair (tiles_x, tiles_y)")
+    if not (1 <= tx <= 16 and 1 <= ty <= 16):
+        raise ValueError("CLAHE tiles must be 1 .. 16 in both directions")
+    if not np.isfinite(clip):
+        raise ValueError("CLAHE clip_limit must be finite")
+    return clip, tx, ty

@@ -274,6 +274,24 @@ def convertGray(image, fmt, device=0):
     return out
 
 
+def clahe(image, fmt="mono8", clip_limit=2.0, tiles=(8, 8), device=0):
+    """cv::createCLAHE(clip_limit, tiles)->apply() of the grey image of `image` on the GPU (svo_clahe): the equalisation of frame
+    ingest alone, on its two kernels.  image: (h, w, bpp) uint8 in the format `fmt` ((h, w) for mono8), rows may be strided ->
+    (h, w) uint8.  ValueError for tiles outside 1 .. 16 or a non-finite clip_limit; SvoError when the tiles do not fit the image."""
+    f = _lib.input_format(fmt)
+    bpp = _lib.INPUT_BPP[f]
+    clip, tx, ty = _lib.check_clahe(clip_limit, tiles)
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or not ((img.ndim == 3 and img.shape[2] == bpp) or (bpp == 1 and img.ndim == 2)):
+        raise ValueError("uint8 (h, w, %d) image expected for this format" % bpp)
+    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != bpp):
+        img = np.ascontiguousarray(img)
+    h, w = img.shape[:2]
+    out = np.zeros((h, w), np.uint8)
+    check(lib.svo_clahe(device, f, C.c_void_p(img.ctypes.data), w, h, img.strides[0], clip, tx, ty, ptr(out)))
+    return out
+
+
 # ---------------------------------------------------------------------------- FeatureSet / Bucket
 class FeatureSet:
     """vo.h:132-188 — parallel arrays points / ages / strengths."""
@@ -409,6 +427,18 @@ class BatchVisualOdometry:
         f = _lib.input_format(fmt)
         check(lib.svo_set_input_format(self._h, f))
         self.input_format = f
+
+    def set_clahe(self, clip_limit=2.0, tiles=(8, 8)):
+        """Equalise both images of every frame submitted from now on (svo_set_clahe): cv::createCLAHE(clip_limit, tiles)->apply()
+        of the grey frame, after the input-format conversion and before rectification.  tiles = (tiles_x, tiles_y), each 1 .. 16.
+        Single-channel contexts only.  Legal with frames in flight: every frame carries the setting it was issued with.
+        ValueError for bad tiles or a non-finite clip_limit; SvoError when the tiles do not fit the frame size."""
+        clip, tx, ty = _lib.check_clahe(clip_limit, tiles)
+        check(lib.svo_set_clahe(self._h, 1, clip, tx, ty))
+
+    def clear_clahe(self):
+        """Frames submitted from now on are not equalised: the context launches what it launched before set_clahe."""
+        check(lib.svo_set_clahe(self._h, 0, 0.0, 0, 0))
 
     def set_pose_covariance(self, mode="residual", pixel_sigma=1.0):
         """A 6x6 covariance with every pose from the next frame submitted on (svo_set_pose_covariance).  mode: "residual" (sigma^2
@@ -647,6 +677,7 @@ class VisualOdometry(BatchVisualOdometry):
         self._rect = None                             # rectification asked for before the context exists: applied at creation
         self._cov = None                              # likewise a pose-covariance mode
         self._mask = None                             # likewise a detection mask
+        self._clahe = None                            # likewise a CLAHE setting (clip_limit, tiles_x, tiles_y)
         self.raw_size = None
         if not self._created:
             self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
@@ -687,6 +718,16 @@ class VisualOdometry(BatchVisualOdometry):
         if self._created:
             return super().set_pose_covariance(mode, pixel_sigma)
         self._cov = _lib.check_cov(mode, pixel_sigma)                 # checked now, as the library will: not inside the first frame
+
+    def set_clahe(self, clip_limit=2.0, tiles=(8, 8)):
+        if self._created:
+            return super().set_clahe(clip_limit, tiles)
+        self._clahe = _lib.check_clahe(clip_limit, tiles)             # the fit to the frame size is checked at the first frame
+
+    def clear_clahe(self):
+        self._clahe = None
+        if self._created:
+            super().clear_clahe()
 
     def set_detection_mask(self, mask, seq=-1):
         if self._created:
@@ -741,6 +782,8 @@ class VisualOdometry(BatchVisualOdometry):
                 super().set_pose_covariance(*self._cov)
             if self._mask is not None:
                 super().set_detection_mask(self._mask)
+            if self._clahe is not None:
+                super().set_clahe(self._clahe[0], self._clahe[1:])
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

@@ -170,6 +170,22 @@ struct svo_context {
     const uint8_t** d_mask_rows = nullptr;       // ... and the device copy the masked FAST kernels read (one hipMemcpyAsync per masked frame)
     uint8_t* h_mask_stage = nullptr;             // pinned [W*H]: a host mask's packed rows on their way to the device
     hipEvent_t ev_mask_stage = nullptr;          // that copy has run: the staging buffer may be written again
+    // CLAHE (svo_set_clahe): the setting of the frames submitted from now on — host state like the input format, so every frame
+    // carries its own.  The buffers appear at first use (clahe_buffers): one allocation holds the device table of the staging
+    // frames' addresses ([2][B], what the frame's ingest takes in place of the caller's pointer table) and the frames themselves
+    // (in_width x in_height mono8, packed, `clahe_pitch` bytes apart); the LUTs are [B][2][tiles_y][tiles_x][256].
+    // ONE staging set per context is enough only because a frame's CLAHE launches and the ingest that consumes them are adjacent
+    // on ONE stream — img_stream for build-ahead contexts, `stream` otherwise, the same one for every CLAHE frame of a context
+    // (they are never captured into a graph) — so frame N + 1's equalisation is ordered behind frame N's ingest.  A path that
+    // fills the staging frames from another stream must order itself with an event.
+    bool clahe_on = false;
+    double clahe_clip = 0.;
+    int clahe_tx = 0, clahe_ty = 0;
+    uint8_t* clahe_buf = nullptr;                // [table | frames]
+    size_t clahe_pitch = 0;
+    int clahe_w = 0, clahe_h = 0;                // the frame size clahe_buf was allocated for
+    uint8_t* clahe_lut = nullptr;
+    int clahe_lut_tiles = 0;                     // tiles per image clahe_lut has room for
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -351,6 +367,7 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->d_mask_rows) (void)hipFree((void*)c->d_mask_rows);
     for (void* p : {(void*)c->h_mask_rows, (void*)c->h_mask_stage}) if (p) (void)hipHostFree(p);
     if (c->ev_mask_stage) (void)hipEventDestroy(c->ev_mask_stage);
+    for (void* p : {(void*)c->clahe_buf, (void*)c->clahe_lut}) if (p) (void)hipFree(p);
     for (RingSlot& r : c->ring) {
         for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
         if (r.ev_img) (void)hipEventDestroy(r.ev_img);
@@ -413,11 +430,85 @@ static hipError_t upload_act(const svo_context* c, int slot, hipStream_t st) {
     return hipMemcpyAsync(ring_row(c, c->d_act, slot), ring_row(c, c->h_act, slot), sizeof(int) * 2 * (size_t)c->d.B, hipMemcpyHostToDevice, st);
 }
 
+// ---- CLAHE (svo.h): geometry, buffers and the two launches in front of an ingest ----
+// Rule 1 of the definition for a w x h image: the tile size, or false when the rule rejects the geometry.
+static bool clahe_geometry(int w, int h, int tiles_x, int tiles_y, int* tw, int* th) {
+    if (w < 1 || h < 1 || tiles_x < 1 || tiles_y < 1) return false;
+    int ew = w, eh = h;
+    if (w % tiles_x != 0 || h % tiles_y != 0) {
+        const int ex = tiles_x - w % tiles_x, ey = tiles_y - h % tiles_y;          // a divisible dimension grows by a whole tiles_*
+        if (ex > w - 1 || ey > h - 1) return false;                                // REFLECT_101 undefined
+        ew += ex; eh += ey;
+    }
+    *tw = ew / tiles_x; *th = eh / tiles_y;
+    return *tw > 0 && *th > 0;
+}
+static int check_clahe_params(double clip_limit, int tiles_x, int tiles_y) {
+    if (tiles_x < 1 || tiles_x > 16 || tiles_y < 1 || tiles_y > 16) return fail_arg("CLAHE: tiles must be 1 .. 16 in both directions");
+    if (!isfinite(clip_limit)) return fail_arg("CLAHE: clip_limit must be finite");
+    return SVO_OK;
+}
+// everything of ClaheArgs the definition derives from (size, tiles, clip limit); false: rule 1 rejects the geometry
+static bool clahe_derive(ClaheArgs& a, int w, int h, double clip_limit, int tiles_x, int tiles_y) {
+    int tw, th;
+    if (!clahe_geometry(w, h, tiles_x, tiles_y, &tw, &th)) return false;
+    a.w = w; a.h = h; a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tw = tw; a.th = th;
+    const int area = tw * th;
+    a.clip = 0;
+    if (clip_limit > 0.) {
+        const double v = clip_limit * area / 256.;
+        a.clip = v >= (double)area ? area : ((int)v > 1 ? (int)v : 1);             // (no bin exceeds area: a larger clip cuts nothing either)
+    }
+    a.scale = 255.0f / (float)area; a.inv_tw = 1.0f / (float)tw; a.inv_th = 1.0f / (float)th;
+    return true;
+}
+static void retire_map(svo_context* c, uint8_t* p);
+// The staging frames and LUTs for the context's input size and tile count as they are NOW; buffers of another size that frames in
+// flight may still name are retired like replaced rectification maps.
+static int clahe_buffers(svo_context* c) {
+    const int W = in_width(c), H = in_height(c), B = c->d.B;
+    if (!c->clahe_buf || c->clahe_w != W || c->clahe_h != H) {
+        const size_t table = (sizeof(uint8_t*) * 2 * B + 255) & ~(size_t)255, pitch = ((size_t)W * H + 255) & ~(size_t)255;
+        uint8_t* p = nullptr;
+        HIPCHK(hipMalloc((void**)&p, table + pitch * 2 * B + 256));
+        std::vector<const uint8_t*> ptrs((size_t)2 * B);
+        for (int i = 0; i < 2 * B; i++) ptrs[i] = p + table + pitch * i;
+        if (hipMemcpy(p, ptrs.data(), sizeof(uint8_t*) * 2 * B, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); g_err = "CLAHE: pointer table upload failed"; return SVO_ERR_HIP; }
+        retire_map(c, c->clahe_buf);
+        c->clahe_buf = p; c->clahe_pitch = pitch; c->clahe_w = W; c->clahe_h = H;
+    }
+    const int tiles = c->clahe_tx * c->clahe_ty;
+    if (!c->clahe_lut || c->clahe_lut_tiles < tiles) {
+        uint8_t* p = nullptr;
+        HIPCHK(hipMalloc((void**)&p, (size_t)B * 2 * tiles * 256));
+        retire_map(c, c->clahe_lut);
+        c->clahe_lut = p; c->clahe_lut_tiles = tiles;
+    }
+    return SVO_OK;
+}
+// The frame's two CLAHE launches on st, in front of the ingest that st runs next: srcs / stride are the caller's frames in the format
+// f.in; afterwards they name the staging frames and f.in is mono8 — the ingest runs as a mono8 frame's, maps and active list unchanged.
+static int clahe_front(svo_context* c, DevBuffers& f, const uint8_t* const*& srcs, int& stride, hipStream_t st) {
+    ClaheArgs a = {};
+    if (!clahe_derive(a, in_width(c), in_height(c), c->clahe_clip, c->clahe_tx, c->clahe_ty)) {
+        g_err = "CLAHE: the tiles do not fit the raw size this context now rectifies (svo.h, CLAHE rule 1)";
+        return SVO_ERR_STATE;
+    }
+    if (const int rc = clahe_buffers(c)) return rc;
+    const size_t table = (sizeof(uint8_t*) * 2 * c->d.B + 255) & ~(size_t)255;
+    a.srcs = srcs; a.act = f.act; a.B = c->d.B; a.ncam = 2; a.stride = stride; a.g = f.in;
+    a.lut = c->clahe_lut; a.out = c->clahe_buf + table; a.pitch = c->clahe_pitch;
+    launch_clahe(a, launch_seqs(f), st);
+    srcs = reinterpret_cast<const uint8_t* const*>(c->clahe_buf); stride = a.w;
+    f.in = GreyIn{1, 0, 0, 0, 0, 0, 0};
+    return SVO_OK;
+}
+
 // The front of a many-sequence frame: its pyramids are built on the IMAGE stream, which only waits for the previous frame's reset —
 // so, with frames in flight, they are built while the previous frame sits in its LK kernel.  That kernel fills six of a SIMD's
 // eight wave slots and 480 of its 512 registers (svo_kernels_lk.hip): the ingest, pyramid and border kernels (11-17 registers)
 // are the ones that still fit beside it.  The frame's own stream then resets the state (ev_begin marks that) and goes on.
-static int front_ahead(svo_context* c, const DevBuffers& f, int slot, int stride) {
+static int front_ahead(svo_context* c, DevBuffers& f, int slot, int stride) {
     hipStream_t s = c->stream;
     RingSlot& r = c->ring[slot];
     if (!c->img_stream) {
@@ -434,7 +525,9 @@ static int front_ahead(svo_context* c, const DevBuffers& f, int slot, int stride
     }
     if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, r.ev[EV_F0], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
     if (f.act) HIPCHK(upload_act(c, slot, c->img_stream));
-    launch_ingest_pyramid(f, ring_row(c, f.img_ptrs, slot), stride, c->img_stream, PYR_NEXT);
+    const uint8_t* const* srcs = ring_row(c, f.img_ptrs, slot);
+    if (c->clahe_on) if (const int rc = clahe_front(c, f, srcs, stride, c->img_stream)) return rc;   // behind the waits above, like the ingest
+    launch_ingest_pyramid(f, srcs, stride, c->img_stream, PYR_NEXT);
     HIPCHK(hipEventRecord(r.ev_img, c->img_stream));
     HIPCHK(hipStreamWaitEvent(s, r.ev_img, 0));
     launch_frame_begin(f, s);
@@ -457,9 +550,10 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         return SVO_OK;
     }
     HIPCHK(choose_pnp_build(c->d, share.lean));
-    const DevBuffers f = frame_view(c, slot, n_act);                   // after the build choice: co_resident travels in the view
-    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0);
-    const uint8_t** dp = ring_row(c, f.img_ptrs, slot);                // the slot's pointer table: pinned host memory the kernel reads in place
+    DevBuffers f = frame_view(c, slot, n_act);                         // after the build choice: co_resident travels in the view
+    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0) |
+               (c->clahe_on ? SVO_PATH_CLAHE : 0);
+    const uint8_t* const* dp = ring_row(c, f.img_ptrs, slot);          // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(f);
     bool detected = false;
     if (ahead) {
@@ -467,6 +561,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         path |= SVO_PATH_INGEST_AHEAD;
     } else {
         if (f.act) HIPCHK(upload_act(c, slot, s));
+        if (c->clahe_on) if (const int rc = clahe_front(c, f, dp, stride, s)) return rc;   // the front below then ingests the staging frames as mono8
         detected = !mrows && launch_front_fused(f, dp, stride, s);     // lone stream: ingest + pyramid beside detection, two launches (a masked frame: the unfused front)
         if (detected) path |= SVO_PATH_FRONT_FUSED;
         else launch_ingest_pyramid(f, dp, stride, s, PYR_BEGIN);       // + the per-frame reset
@@ -638,7 +733,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     const uint8_t* const* mrows = nullptr;
     if ((rc = take_masks(c, slot, active, &mrows)) != SVO_OK) return rc;
     bool replayed = false;
-    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows)        // a ragged, rectifying or masked frame runs from the launch list
+    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on)   // a ragged, rectifying, masked or CLAHE frame runs from the launch list
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
     if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
@@ -868,8 +963,11 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
         for (int cam = 0; cam < 2; cam++) hm[cam] = map_of(c, 0, cam);
         if (!hm[0] || !hm[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
     }
-    const DevBuffers f = frame_view(c, 0, -1);
-    launch_ingest_pyramid(f, ring_row(c, f.img_ptrs, 0), in_width(c) * in_bpp(c), c->stream, PYR_T1);   // vo.cpp:200-201
+    DevBuffers f = frame_view(c, 0, -1);
+    const uint8_t* const* srcs = ring_row(c, f.img_ptrs, 0);
+    int packed = in_width(c) * in_bpp(c);
+    if (c->clahe_on && (rc = clahe_front(c, f, srcs, packed, c->stream)) != SVO_OK) return rc;
+    launch_ingest_pyramid(f, srcs, packed, c->stream, PYR_T1);                                            // vo.cpp:200-201
     if ((rc = circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok)) != SVO_OK) return rc;
     SeqState out = keep;
     out.slot_pyr_t0 = t1;                                                         // lastLeftPyramid = pyramidl1 (vo.cpp:231-232)
@@ -1545,6 +1643,45 @@ extern "C" int svo_set_input_format(svo_context* c, int format) {
     GreyIn g;
     if (!grey_in_of(format, &g)) return fail_arg("svo_set_input_format: unknown format (SVO_INPUT_*)");
     c->in_format = format; c->in = g;                                 // host state: the next frame issued launches this format's kernels
+    return SVO_OK;
+}
+
+// ================================================================================================
+// CLAHE (svo.h): the setter and the stage entry point.  The per-frame side is clahe_front.
+// ================================================================================================
+extern "C" int svo_set_clahe(svo_context* c, int on, double clip_limit, int tiles_x, int tiles_y) {
+    if (!c) return fail_arg("null context");
+    if (c->d.CN != 1) return fail_arg("svo_set_clahe: a channels = 3 context takes interleaved BGR as it is (svo.h, channels)");
+    if (!on) { c->clahe_on = false; return SVO_OK; }
+    if (const int rc = check_clahe_params(clip_limit, tiles_x, tiles_y)) return rc;
+    int tw, th;
+    if (!clahe_geometry(in_width(c), in_height(c), tiles_x, tiles_y, &tw, &th)) return fail_arg("svo_set_clahe: the tiles do not fit the context's input size (svo.h, CLAHE rule 1)");
+    c->clahe_on = true; c->clahe_clip = clip_limit; c->clahe_tx = tiles_x; c->clahe_ty = tiles_y;   // host state: the next frame issued carries it
+    return SVO_OK;
+}
+
+extern "C" int svo_clahe(int device, int format, const uint8_t* src, int w, int h, int stride,
+                         double clip_limit, int tiles_x, int tiles_y, uint8_t* out) {
+    ClaheArgs a = {};
+    if (!src || !out || w < 1 || h < 1) return fail_arg("bad arguments");
+    if (!grey_in_of(format, &a.g)) return fail_arg("svo_clahe: unknown format (SVO_INPUT_*)");
+    const size_t rowb = (size_t)w * a.g.bpp, n = (size_t)w * h;
+    if ((size_t)stride < rowb) return fail_arg("stride < w * bytes per pixel");
+    int rc = check_clahe_params(clip_limit, tiles_x, tiles_y); if (rc != SVO_OK) return rc;
+    if (!clahe_derive(a, w, h, clip_limit, tiles_x, tiles_y)) return fail_arg("svo_clahe: the tiles do not fit the image (svo.h, CLAHE rule 1)");
+    rc = use_device(device); if (rc != SVO_OK) return rc;
+    // packed rows on the device, at the caller's own misalignment (as svo_convert_gray)
+    const size_t mis = (size_t)((uintptr_t)src & 3);
+    DevTmp t; uint8_t *dsrc, *dout, *dlut; const uint8_t** dtab;
+    HIPCHK(t.get(&dsrc, rowb * h + 4)); HIPCHK(t.get(&dout, n + 4)); HIPCHK(t.get(&dlut, (size_t)tiles_x * tiles_y * 256));
+    HIPCHK(hipMemcpy2D(dsrc + mis, rowb, src, (size_t)stride, rowb, (size_t)h, hipMemcpyHostToDevice));
+    const uint8_t* first = dsrc + mis;
+    HIPCHK(t.put(&dtab, &first, 1));
+    a.srcs = dtab; a.act = nullptr; a.B = 1; a.ncam = 1; a.stride = (int)rowb; a.lut = dlut; a.out = dout; a.pitch = n;
+    launch_clahe(a, 1, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(t.download(out, dout, n));
+    g_stage_path = SVO_PATH_CLAHE | (a.g.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0);
     return SVO_OK;
 }
 

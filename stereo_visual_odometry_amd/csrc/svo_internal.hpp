@@ -68,6 +68,19 @@ struct CovArgs { PoseCovRow* rows; int mode; double sigma2; };
 // weights live here, on the host's format table (svo_api.hip), and nowhere in the kernels.
 struct GreyIn { int bpp, w0, w1, w2, rnd, shift, yoff; };
 
+// CLAHE (svo.h, svo_set_clahe): the arguments of the two launches in front of a frame's ingest (k_clahe_lut, k_clahe_apply), kernel
+// arguments of their own like CovArgs.  srcs[cam * B + seq]: the caller's frames in the format g (w x h pixels, rows `stride` bytes
+// apart); act: the frame's active list or null (seq_of's rule); lut: [B][ncam][tiles_y][tiles_x][256]; out: the mono8 staging frames,
+// image (cam * B + seq) at out + that * pitch, packed rows of w bytes.  tw, th, clip (0: none), scale, inv_tw and inv_th are derived
+// once on the host (clahe_geometry, svo_api.hip) as svo.h defines them.
+struct ClaheArgs {
+    const uint8_t* const* srcs; const int* act; int B, ncam;
+    int stride, w, h, tiles_x, tiles_y, tw, th, clip;
+    float scale, inv_tw, inv_th;
+    uint8_t* lut; uint8_t* out; size_t pitch;
+    GreyIn g;
+};
+
 // All device buffers of a context (B sequences, capacity CAP features each).
 struct DevBuffers {
     int B, CAP, NB;                            // NB = buckets_along_height * buckets_along_width
@@ -252,6 +265,9 @@ void launch_rectify_image(const short2* map1, const uint16_t* map2, int w, int h
 
 // svo_convert_gray: out (w x h, packed) = the grey image of src in the format g; device pointers
 void launch_convert_gray(const GreyIn& g, const uint8_t* src, int w, int h, int stride, uint8_t* out, hipStream_t s);
+
+// CLAHE: the per-tile LUTs, then the interpolation into the staging frames, for n_seq launched sequences (a.act lists them, or null)
+void launch_clahe(const ClaheArgs& a, int n_seq, hipStream_t s);
 
 // stage helpers
 void launch_fast_score_map(const uint8_t* img_dev, int w, int h, int threshold, uint8_t* score_dev, hipStream_t s);

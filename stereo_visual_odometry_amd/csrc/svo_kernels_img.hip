@@ -129,6 +129,147 @@ void launch_convert_gray(const GreyIn& g, const uint8_t* src, int w, int h, int 
     with_bpp(g.bpp, [&](auto b) { hipLaunchKernelGGL(k_convert_gray<decltype(b)::value>, dim3(gx), dim3(256), 0, st, g, src, w, h, stride, out); });
 }
 
+// ------------------------------------------------------------------------------------------------
+// CLAHE (svo.h, svo_set_clahe): two launches in front of a frame's ingest.  The LUTs need the whole image before the first pixel
+// can be written, so nothing here is fused into the tile fills: k_clahe_lut builds one tile's LUT per block, k_clahe_apply
+// interpolates four LUTs per pixel into a packed mono8 staging frame, which the frame's unchanged mono8 ingest then reads.
+// BPP 1 reads the caller's bytes as they are; 2 / 3 / 4 convert through grey_px / grey4.
+// ------------------------------------------------------------------------------------------------
+template <int BPP>
+__device__ __forceinline__ unsigned clahe_px(const uint8_t* __restrict__ p, const GreyIn& g) {
+    if constexpr (BPP == 1) return p[0]; else return grey_px<BPP>(p, g);
+}
+template <int BPP>
+__device__ __forceinline__ unsigned clahe_px4(const uint8_t* __restrict__ p, const GreyIn& g) {
+    if constexpr (BPP == 1) return reinterpret_cast<const UD*>(p)->v; else return grey4<BPP>(p, g);
+}
+// One block per (tile, camera, launched sequence): per-wave histograms in LDS (LDS atomics), merged one bin per thread, clipped,
+// redistributed, prefix-summed, scaled.  Only a tile that touches the extension computes REFLECT_101 indices (one fold: the host
+// rejected an extension beyond w - 1 / h - 1); an interior tile takes four pixels per thread from unaligned dword loads.
+// The redistribution loop of the definition visits bins 0, step, 2 step ... while residual lasts: bin t gets its + 1 when
+// t % step == 0 and t / step < residual — the same bins, one thread each.
+template <int BPP>
+__global__ __launch_bounds__(256) void k_clahe_lut(ClaheArgs a) {
+    __shared__ unsigned hist[4][256];
+    __shared__ unsigned part[2][4];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int tile = blockIdx.x, cam = blockIdx.y, seq = a.act ? a.act[blockIdx.z] : (int)blockIdx.z;
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+#pragma unroll
+    for (int k = 0; k < 4; k++) hist[k][t] = 0;
+    __syncthreads();
+    const uint8_t* __restrict__ src = a.srcs[cam * a.B + seq];
+    const int x0 = tx * a.tw, y0 = ty * a.th;
+    const bool inside = x0 + a.tw <= a.w && y0 + a.th <= a.h;
+    const int qpr = (a.tw + 3) >> 2, total = qpr * a.th;
+    unsigned* const my = hist[wave];
+    for (int i = t; i < total; i += 256) {
+        const int r = i / qpr, x = 4 * (i - r * qpr);
+        const int ey = y0 + r, sy = ey < a.h ? ey : 2 * a.h - 2 - ey;
+        const uint8_t* row = src + (size_t)sy * a.stride;
+        if (inside && x + 4 <= a.tw) {
+            const unsigned q = clahe_px4<BPP>(row + (size_t)(x0 + x) * BPP, a.g);
+            atomicAdd(&my[q & 255u], 1u); atomicAdd(&my[(q >> 8) & 255u], 1u); atomicAdd(&my[(q >> 16) & 255u], 1u); atomicAdd(&my[q >> 24], 1u);
+        } else {
+            for (int k = 0; k < 4 && x + k < a.tw; k++) {
+                const int ex = x0 + x + k, sx = ex < a.w ? ex : 2 * a.w - 2 - ex;
+                atomicAdd(&my[clahe_px<BPP>(row + (size_t)sx * BPP, a.g)], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    unsigned hv = hist[0][t] + hist[1][t] + hist[2][t] + hist[3][t];
+    if (a.clip > 0) {
+        const unsigned clip = (unsigned)a.clip;
+        unsigned ex = hv > clip ? hv - clip : 0u;
+        hv = hv > clip ? clip : hv;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ex += __shfl_xor(ex, o);
+        if (lane == 0) part[0][wave] = ex;
+        __syncthreads();
+        const unsigned clipped = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+        const unsigned batch = clipped >> 8, residual = clipped & 255u;
+        hv += batch;
+        if (residual > 0) {
+            const unsigned step = 256u / residual;                    // >= 1: residual <= 255
+            if (t % step == 0 && t / step < residual) hv++;
+        }
+    }
+    unsigned s = hv;                                                  // inclusive scan over the 256 bins
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned n = __shfl_up(s, o); if (lane >= o) s += n; }
+    if (lane == 63) part[1][wave] = s;
+    __syncthreads();
+    for (int k = 0; k < wave; k++) s += part[1][k];
+    float f = rintf(__fmul_rn((float)s, a.scale));
+    f = f < 0.f ? 0.f : (f > 255.f ? 255.f : f);
+    a.lut[((size_t)(seq * a.ncam + cam) * (a.tiles_x * a.tiles_y) + tile) * 256 + t] = (uint8_t)(int)f;
+}
+// A block takes up to CLAHE_ROWS pixel rows of one BAND: the rows whose ty1 = floor(y inv_th - 0.5) is blockIdx.y - 1, which all
+// interpolate between the same two LUT rows — staged in LDS, 2 tiles_x 256 bytes.  The band's rows are found by the definition's own
+// f32 expression, evaluated for a candidate range two rows wider than the exact one on both sides; a row of another band is skipped.
+// Each lane handles four pixels of a row: converts them, looks up four LUTs per pixel, interpolates (every f32 operation rounded on
+// its own, in the definition's order) and stores one dword.
+#define CLAHE_ROWS 8
+template <int BPP>
+__global__ __launch_bounds__(256) void k_clahe_apply(ClaheArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t L[2][16 * 256];
+    const int t = threadIdx.x, band = blockIdx.y;
+    const int b = blockIdx.z / a.ncam, cam = blockIdx.z - b * a.ncam, seq = a.act ? a.act[b] : b;
+    const int lo = max((band - 1) * a.th + a.th / 2 - 2, 0), hi = min(band * a.th + (a.th + 1) / 2 + 2, a.h);
+    const int r0 = lo + blockIdx.x * CLAHE_ROWS;
+    if (r0 >= hi) return;
+    const int rowb = a.tiles_x * 256;
+    const uint8_t* lut = a.lut + (size_t)(seq * a.ncam + cam) * ((size_t)rowb * a.tiles_y);
+    const unsigned* la = reinterpret_cast<const unsigned*>(lut + (size_t)max(band - 1, 0) * rowb);
+    const unsigned* lb = reinterpret_cast<const unsigned*>(lut + (size_t)min(band, a.tiles_y - 1) * rowb);
+    for (int i = t; i < rowb / 4; i += 256) {
+        reinterpret_cast<unsigned*>(L[0])[i] = la[i];
+        reinterpret_cast<unsigned*>(L[1])[i] = lb[i];
+    }
+    __syncthreads();
+    const uint8_t* __restrict__ src = a.srcs[cam * a.B + seq];
+    uint8_t* __restrict__ out = a.out + (size_t)(cam * a.B + seq) * a.pitch;
+    const int qpr = (a.w + 3) >> 2, total = qpr * CLAHE_ROWS;
+    for (int i = t; i < total; i += 256) {
+        const int r = i / qpr, y = r0 + r, x = 4 * (i - r * qpr);
+        if (y >= hi) break;
+        const float tyf = __fsub_rn(__fmul_rn((float)y, a.inv_th), 0.5f), ty1f = floorf(tyf);
+        if ((int)ty1f != band - 1) continue;
+        const float ya = __fsub_rn(tyf, ty1f), ya1 = __fsub_rn(1.0f, ya);
+        const uint8_t* p = src + (size_t)y * a.stride + (size_t)x * BPP;
+        uint8_t* o = out + (size_t)y * a.w + x;
+        const bool full = x + 4 <= a.w;
+        const unsigned q = full ? clahe_px4<BPP>(p, a.g) : 0u;
+        unsigned res4 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (!full && x + k >= a.w) break;
+            const unsigned v = full ? (q >> (8 * k)) & 255u : clahe_px<BPP>(p + k * BPP, a.g);
+            const float txf = __fsub_rn(__fmul_rn((float)(x + k), a.inv_tw), 0.5f), tx1f = floorf(txf);
+            const float xa = __fsub_rn(txf, tx1f), xa1 = __fsub_rn(1.0f, xa);
+            const int tx1 = (int)tx1f;
+            const int c1 = min(max(tx1, 0), a.tiles_x - 1) * 256 + (int)v, c2 = min(tx1 + 1, a.tiles_x - 1) * 256 + (int)v;   // (the upper clamp of tx1 never binds: x < tiles_x tw)
+            const float top = __fadd_rn(__fmul_rn((float)L[0][c1], xa1), __fmul_rn((float)L[0][c2], xa));
+            const float bot = __fadd_rn(__fmul_rn((float)L[1][c1], xa1), __fmul_rn((float)L[1][c2], xa));
+            float res = rintf(__fadd_rn(__fmul_rn(top, ya1), __fmul_rn(bot, ya)));
+            res = res < 0.f ? 0.f : (res > 255.f ? 255.f : res);
+            const unsigned byte = (unsigned)(int)res;
+            if (full) res4 |= byte << (8 * k); else o[k] = (uint8_t)byte;
+        }
+        if (full) { UD u; u.v = res4; *reinterpret_cast<UD*>(o) = u; }
+    }
+}
+void launch_clahe(const ClaheArgs& a, int n_seq, hipStream_t st) {
+    const dim3 gl(a.tiles_x * a.tiles_y, a.ncam, n_seq), ga((a.th + 5 + CLAHE_ROWS - 1) / CLAHE_ROWS, a.tiles_y + 1, a.ncam * n_seq);
+    const auto go = [&](auto b) {
+        constexpr int BPP = decltype(b)::value;
+        hipLaunchKernelGGL(k_clahe_lut<BPP>, gl, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_clahe_apply<BPP>, ga, dim3(256), 0, st, a);
+    };
+    if (a.g.bpp <= 1) go(std::integral_constant<int, 1>{}); else with_bpp(a.g.bpp, go);
+}
+
 // svo_rectify_image: one thread per output pixel (all channels), packed output rows
 template <int CN>
 __global__ __launch_bounds__(256) void k_rectify_image(const short2* __restrict__ m1, const uint16_t* __restrict__ m2, int w, int h,

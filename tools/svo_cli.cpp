@@ -166,11 +166,12 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
     std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path;
-    bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false;
+    bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false, clahe = false;
+    double clahe_clip = 2.0; int clahe_tx = 8, clahe_ty = 8;
     for (int i = 3; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--rectify")) {
             if (i + 2 >= argc) { std::fprintf(stderr, "--rectify needs two camera_info files\n"); return 2; }
@@ -183,6 +184,10 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
         else if (!strcmp(argv[i], "--covariance")) cov_out = argv[i + 1];   // one row per frame: valid, then the 21 upper-triangle entries of cov_T (svo.h), row by row
         else if (!strcmp(argv[i], "--mask")) mask_path = argv[i + 1];       // a static detection mask (svo.h): PGM or PNG of the frame size, non-zero = features allowed; needs --gray 1 or 2
+        else if (!strcmp(argv[i], "--clahe")) {                             // clip,tx,ty: CLAHE on the grey frames inside frame ingest (svo.h); needs --gray 1 or 2
+            if (std::sscanf(argv[i + 1], "%lf,%d,%d", &clahe_clip, &clahe_tx, &clahe_ty) != 3) { std::fprintf(stderr, "--clahe needs clip,tx,ty (e.g. 2.0,8,8)\n"); return 2; }
+            clahe = true;
+        }
         else if (!strcmp(argv[i], "--device")) default_device() = std::atoi(argv[i + 1]);
     }
     Mat34f Pl = {322.11376f, 0, 327.47336f, 0, 0, 322.11376f, 176.33722f, 0, 0, 0, 1, 0};               // main.cpp:357-362
@@ -224,6 +229,7 @@ int main(int argc, char** argv) {
         if (!rect_l.empty()) vo.set_rectification(ci_l, ci_r);
         if (gray_gpu) vo.set_input_encoding("bgr8");
         if (cov.is_open()) vo.set_pose_covariance(SVO_COV_RESIDUAL);
+        if (clahe) vo.set_clahe(clahe_clip, clahe_tx, clahe_ty);
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
         if (identity_start) { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(pose, I, sizeof(I)); }

@@ -3,10 +3,11 @@
 // src/main.cpp:394).  Reads stereo pairs from a raw file (int32 n, h, w; then n x (left, right) gray images), plays them
 // ping-pong through svo_process and prints the mean / median / p95 wall time per call, with ordinary heap buffers and with
 // page-locked ones (svo_alloc_pinned).
-//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance | --mask]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
+//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance | --mask | --clahe]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
 // --covariance: every leg is run twice, without and with the pose covariance (svo_set_pose_covariance, SVO_COV_RESIDUAL).
 // --mask: every leg is run twice, without and with a static detection mask (svo_set_detection_mask: the lower quarter of the image
 // closed, a bonnet) — a masked lone-stream frame issues the unfused front, one launch more.
+// --clahe: every leg is run twice, without and with CLAHE (svo_set_clahe, clip 2.0, 8 x 8 tiles): two launches more per frame.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -16,7 +17,7 @@
 #include <vector>
 #include "svo.h"
 
-static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false, bool mask = false) {
+static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false, bool mask = false, bool clahe = false) {
     svo_config cfg; svo_config_default(&cfg);
     cfg.win_w = cfg.win_h = win; cfg.max_translation_norm = max_t;
     svo_context* ctx = nullptr;
@@ -30,6 +31,7 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
         std::fill(m.begin() + (size_t)(h - h / 4) * w, m.end(), (uint8_t)0);
         if (svo_set_detection_mask(ctx, -1, m.data(), w, 0) != SVO_OK) { std::fprintf(stderr, "svo_set_detection_mask: %s\n", svo_last_error()); std::exit(1); }
     }
+    if (clahe && svo_set_clahe(ctx, 1, 2.0, 8, 8) != SVO_OK) { std::fprintf(stderr, "svo_set_clahe: %s\n", svo_last_error()); std::exit(1); }
     const int n = (int)L.size();
     auto pp = [&](int i) { const int p = i % (2 * n - 2); return p < n ? p : 2 * n - 2 - p; };
     double T[16]; svo_frame_stats st; int n_ok = 0;
@@ -50,10 +52,11 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
 }
 
 int main(int argc, char** argv) {
-    bool covariance = false, mask = false;
+    bool covariance = false, mask = false, clahe = false;
     if (argc > 2 && !std::strcmp(argv[argc - 1], "--covariance")) { covariance = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--mask")) { mask = true; argc--; }
-    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance | --mask]\n"); return 2; }
+    else if (argc > 2 && !std::strcmp(argv[argc - 1], "--clahe")) { clahe = true; argc--; }
+    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance | --mask | --clahe]\n"); return 2; }
     const int win = argc > 2 ? std::atoi(argv[2]) : 21, calls = argc > 3 ? std::atoi(argv[3]) : 200;
     const double max_t = argc > 4 ? std::atof(argv[4]) : 2.0;
     std::ifstream f(argv[1], std::ios::binary);
@@ -69,6 +72,7 @@ int main(int argc, char** argv) {
     run(L, R, w, h, win, calls, max_t, "heap buffers:");
     if (covariance) run(L, R, w, h, win, calls, max_t, "heap buffers, covariance:", true);
     if (mask) run(L, R, w, h, win, calls, max_t, "heap buffers, mask:", false, true);
+    if (clahe) run(L, R, w, h, win, calls, max_t, "heap buffers, CLAHE:", false, false, true);
     uint8_t* pin = (uint8_t*)svo_alloc_pinned(heap.size());
     if (pin) {
         std::memcpy(pin, heap.data(), heap.size());
@@ -76,6 +80,7 @@ int main(int argc, char** argv) {
         run(L, R, w, h, win, calls, max_t, "page-locked buffers:");
         if (covariance) run(L, R, w, h, win, calls, max_t, "page-locked, covariance:", true);
         if (mask) run(L, R, w, h, win, calls, max_t, "page-locked, mask:", false, true);
+        if (clahe) run(L, R, w, h, win, calls, max_t, "page-locked, CLAHE:", false, false, true);
         svo_free_pinned(pin);
     }
     return 0;
