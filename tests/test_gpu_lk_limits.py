@@ -1,0 +1,221 @@
+"""The LK kernel's wide-sum paths on maximum-contrast images, bit for bit against the CPU oracle.
+
+The exact-sums kernel reduces the normal matrix A and the mismatch vector b of a window in int32 ("narrow") unless a lane's partial
+reaches 2^25, and then in 16-bit halves after PRE doublings ("wide"); PRE = lk_presplit_steps(PPL * CN) compiles a different
+interleaving of DPP steps for each of its values.  Smooth textures never get there.  The cases here do, provably: tests/lk_limits_scenes.py
+shows from the oracle's derivative images alone that the window totals reach 2^31 (tests/test_lk_limits_ref.py asserts it on the CPU),
+which no int32 reduction can hold — so a wrong DPP control word, a sign error in the split of a negative partial, a PRE one too
+large, a too generous narrow limit or derivative planes that clip would all change the bits compared here.
+
+PRE per case, from LkLayout (PPL = smallest p with W * ceil(W / p) <= 64) and lk_presplit_steps:
+    grey w = 21: PPL 7,  PRE 3        grey w = 31: PPL 16, PRE 2        grey w = 15, 16: PPL 4, PRE 4 (stripes)
+    BGR  w = 21: 21 pixel-channels per lane, PRE 1                      BGR  w = 15: 12 per lane, PRE 2
+BGR kernels are built up to w = 21 only, so BGR w = 31 does not exist; w = 15 stands in as the second BGR window.  The stage calls
+take grey images only; three channels go through a BGR VisualOdometry, whose LK points are FAST corners (integer coordinates: the
+windows of odd w start on a pixel, as the proof needs)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as orc
+import scenes
+import lk_limits_scenes as lim
+import lk_limits_child as lch
+import lk_deriv_child as ldc
+from test_gpu_parity import lk_points
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+POSE_TOL = 1e-6          # as tests/test_gpu_lk_deriv_levels.py
+N_BORDER = 60
+
+
+@pytest.fixture(scope="module")
+def api():
+    from stereo_visual_odometry_amd import api as a
+    assert a._lib.device_count() >= 1, "no HIP device"
+    return a
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def track_both(api, case, max_level):
+    """the case's proof points followed by N_BORDER points on and over every border -> (got, status, oracle's, oracle's status)"""
+    pts = np.concatenate([case.pts, lk_points(case.w, case.h, N_BORDER, case.win)]).astype(np.float32)
+    win = case.win
+    got, gst = api.calcOpticalFlowPyrLK(case.a, case.b, pts, win, max_level)
+    want, wst = orc.lk_track(orc.Pyramid(case.a, (win, win), max_level), orc.Pyramid(case.b, (win, win), max_level), pts, (win, win), max_level)
+    assert np.array_equal(gst, wst), np.flatnonzero(gst != wst)
+    assert np.array_equal(bits(got), bits(want)), np.flatnonzero((bits(got) != bits(want)).any(1))
+    n = lim.N_POINTS
+    assert wst[:n].sum() >= 140, wst[:n].sum()                                   # the proof points are tracked ...
+    assert 2 <= (wst[n:] == 0).sum() <= N_BORDER - 20, (wst[n:] == 0).sum()       # ... and the border points both kept and rejected (the two far outside at least)
+    return pts, want, wst
+
+
+@pytest.mark.parametrize("win", [21, 31])
+@pytest.mark.parametrize("lv", [0, 2])
+def test_binary_blocks_stage_call(api, win, lv):
+    """max_level = 0: A and the first step's b are provably wide at every proof point.  max_level = 2: the coarse levels carry Scharr
+    values of up to 3660 and 1992 of 4080 (w = 31 has two levels only: the third would be smaller than the window), so narrow and
+    wide visits mix within one track."""
+    case = lim.grey_binary(win)
+    assert lim.provably_wide_A(case).all() and lim.provably_wide_b(case).all()
+    track_both(api, case, lv)
+
+
+@pytest.mark.parametrize("win", [15, 16])
+@pytest.mark.parametrize("lv", [0, 2])
+def test_stripes_reach_the_four_step_presplit(api, win, lv):
+    """PRE = 4: four pixels per lane.  Stripes two pixels wide are the only way to 2^31 at these windows (w = 16: k + 0.5 points)."""
+    case = lim.grey_stripes(win)
+    assert lim.presplit_steps(win, 1) == 4 and lim.provably_wide_A(case).all()
+    track_both(api, case, lv)
+
+
+@pytest.mark.parametrize("win", [21, 31])
+def test_negative_extremes(api, win):
+    """The complement image shifted the other way: derivatives and mismatch change sign against the binary case (b1 >= +2^31 here,
+    <= -2^31 there), and the lanes' A12 partials carry both signs through the arithmetic shift of the split."""
+    case = lim.grey_negative(win)
+    s = lim.first_step_sums(case)
+    assert lim.provably_wide_A(case).all() and (s["b1"] >= lim.TWO31).all() and (lim.first_step_sums(lim.grey_binary(win))["b1"] <= -lim.TWO31).all()
+    track_both(api, case, 0)
+    track_both(api, case, 2)
+
+
+@pytest.mark.parametrize("win", [21, 31])
+def test_identical_images_do_not_move(api, win):
+    """A wide, b exactly zero: every step is (0, 0).  A proof point comes back with the bits it went in with (integer origin: p - half
+    and + half are exact); a fractional border point within the two roundings of (p - half) + half, one ulp of a coordinate below
+    256 (2^-16) at the most."""
+    case = lim.grey_identical(win)
+    assert lim.provably_wide_A(case).all()
+    pts, want, wst = track_both(api, case, 0)
+    n = lim.N_POINTS
+    assert wst[:n].all()
+    same = (bits(want[:n]) == bits(pts[:n])).all()
+    assert same
+    keep = wst.astype(bool)
+    moved = float(np.abs(want[keep] - pts[keep]).max())
+    assert moved <= 2.0 ** -16, moved
+
+
+@pytest.mark.parametrize("win,lv", [(21, 0), (31, 0), (21, 2), (16, 0)])
+def test_fused_circular_match(api, win, lv):
+    """The fused four-pass launch (k_lk_chain) on the same images, as test_lk_any_square_window_bit_exact runs it"""
+    case = lim.grey_stripes(win) if win == 16 else lim.grey_binary(win)
+    a, b = case.a, case.b
+    c, d = scenes.shift_image(a, 0, 1), scenes.shift_image(b, 0, 1)              # "right" views: one row lower
+    pts = np.concatenate([case.pts, lk_points(case.w, case.h, N_BORDER, win)]).astype(np.float32)
+    over = dict(win_w=win, win_h=win, max_level=lv)
+    res = api.circularMatching(api.default_config(**over), a, c, b, d, pts)
+    P = [orc.Pyramid(i, (win, win), lv) for i in (a, c, b, d)]
+    ref = orc.circular_match(P[0], P[1], P[2], P[3], pts, orc.default_config(**over))
+    assert np.array_equal(res[4], ref[4])
+    for g, o in zip(res[:4], ref[:4]):
+        assert np.array_equal(bits(g), bits(o))
+    assert ref[4][:lim.N_POINTS].sum() >= 140 and (ref[4][lim.N_POINTS:] == 0).sum() >= 2
+
+
+def stats_of(o):
+    return {n: getattr(o.stats, n) for n in lch.STAT_NAMES}
+
+
+@pytest.mark.parametrize("win,lv", [(21, 0), (15, 0), (21, 2)])
+def test_three_channels(api, win, lv):
+    """A BGR VisualOdometry over three different binary planes: frame 1 tracks frame 0's FAST corners through the four passes with the
+    per-lane partials spanning the channels.  At max_level = 0 the pass L0 -> L1 is provably wide in A, and in b at its first step,
+    at every track whose window lies inside the image."""
+    from stereo_visual_odometry_amd import synthetic as syn
+    case = lim.bgr_binary(win)
+    down = lambda planes: np.ascontiguousarray(np.stack([scenes.shift_image(p, 0, 1) for p in planes], -1))    # noqa: E731
+    fr = [(case.a, down(case.planes_a)), (case.b, down(case.planes_b))]
+    Pl, Pr = syn.projection_matrices(dict(syn.KITTI00, width=case.w, height=case.h, cx=case.w / 2.0, cy=case.h / 2.0))
+    over = dict(win_w=win, win_h=win, max_level=lv, channels=3, max_translation_norm=5.0)
+    g = api.VisualOdometry(cfg=api.default_config(**over)); g.initalize_projection_matricies(Pl, Pr)
+    o = orc.VisualOdometry(orc.default_config(**over)); o.initalize_projection_matricies(Pl, Pr)
+    for k, (L, R) in enumerate(fr):
+        ok_g, T_g = g.stereo_callback(L, R); ok_o, T_o = o.stereo_callback(L, R)
+        assert ok_g == ok_o and g.stats.as_dict() == stats_of(o), (k, g.stats.as_dict(), stats_of(o))
+        assert np.array_equal(bits(g.features()[0]), bits(o.features()[0])) and np.abs(T_g - T_o).max() < POSE_TOL, k
+    to, tg = o.last_tracks(), g.last_tracks()
+    for key in ("pl0", "pr0", "pl1", "pr1"):
+        assert np.array_equal(bits(to[key]), bits(tg[key])), key
+    assert g.cfg.channels == 3 and o.stats.n_into_lk >= 100 and o.stats.n_after_circular >= 100
+    assert lim.presplit_steps(win, 3) == (1 if win == 21 else 2)
+    inside = case.inside(to["pl0"])
+    assert inside.sum() >= 60, inside.sum()
+    assert lim.provably_wide_A(case, to["pl0"][inside]).all() and lim.provably_wide_b(case, to["pl0"][inside]).mean() >= 0.5
+
+
+# ---------------------------------------------------------------- frame pipeline on binarised frames
+@pytest.fixture(scope="module")
+def batch_runs(api):
+    assert os.environ.get("SVO_LK_DERIV", "1") != "0"
+    return lch.run_batch(api)
+
+
+def test_many_sequence_pipeline_with_derivative_planes(api, batch_runs):
+    """Nine sequences, w = 21, four levels, 200 x 169 frames binarised at their median: the many-sequence front builds the derivative
+    planes (4 x Scharr, level 1 reaches 4 x 3824 of the 16 320 the format allows) and the kernel reads them at the levels >= 1.  ok
+    flags, every statistics field and the features exactly, the pose within POSE_TOL — as test_gpu_lk_deriv_levels compares."""
+    from stereo_visual_odometry_amd import _lib
+    want = lch.oracle_frames()
+    assert all(int(p) & _lib.PATH_INGEST_AHEAD for p in batch_runs["paths"]), "the many-sequence front did not run"
+    for k in range(lch.N_FRAMES):
+        for i in range(lch.B):
+            r, p = want[i % 2][k], "%d/%d" % (k, i)
+            assert bool(batch_runs[p + "/ok"][0]) == r["ok"], p
+            assert np.array_equal(batch_runs[p + "/stats"], r["stats"]), (p, batch_runs[p + "/stats"], r["stats"])
+            assert np.abs(batch_runs[p + "/T"] - r["T"]).max() < POSE_TOL, p
+            assert np.array_equal(batch_runs[p + "/xy"], r["xy"]) and np.array_equal(batch_runs[p + "/age"], r["age"]) and np.array_equal(batch_runs[p + "/strength"], r["strength"]), p
+    into = [int(r["stats"][lch.STAT_NAMES.index("n_into_lk")]) for s in want for r in s]
+    after = [int(r["stats"][lch.STAT_NAMES.index("n_after_circular")]) for s in want for r in s]
+    assert max(into) > 20 and max(after) > 10, (into, after)
+    d1 = max(int(np.abs(orc.Pyramid(L, (21, 21), 3).deriv(1)).max()) for s in lch.frames() for L, _ in s)
+    assert d1 >= 3500, d1
+
+
+def test_pipeline_without_the_planes_is_byte_equal(api, batch_runs, tmp_path):
+    """SVO_LK_DERIV=0 in a fresh process: the kernel differentiates in registers and must return the same bytes, pose included"""
+    out = str(tmp_path / "off.npz")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "lk_limits_child.py"), out], env=dict(os.environ, SVO_LK_DERIV="0"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "lk limits child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    off = np.load(out)
+    assert sorted(off.files) == sorted(batch_runs)
+    for key in off.files:
+        a, b = off[key], batch_runs[key]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), key
+
+
+@pytest.mark.parametrize("float_sums", [0, 1])
+def test_lone_stream(api, float_sums):
+    """The same frames through a single-sequence VisualOdometry, in exact-sums and in float-sums mode (per-element products up to
+    8160 * 4080 on OpenCV's summation order): everything a frame produces, the tracks of every frame bit for bit."""
+    want = lch.oracle_frames(float_sums)
+    fr = lch.frames()
+    tracked = 0
+    for s in range(2):
+        g = api.VisualOdometry(cfg=api.default_config(**lch.config_over(float_sums))); g.initalize_projection_matricies(*ldc.projections(lch.NAME))
+        for k, (L, R) in enumerate(fr[s]):
+            r = want[s][k]
+            ok_g, T_g = g.stereo_callback(L, R)
+            st = g.stats.as_dict()
+            assert ok_g == r["ok"] and np.array_equal(np.array([st[n] for n in sorted(st)], np.int64), r["stats"]), (s, k, st, r["stats"])
+            f = g.features()
+            assert np.array_equal(bits(f[0]), r["xy"]) and np.array_equal(f[1], r["age"]) and np.array_equal(f[2], r["strength"]), (s, k)
+            assert np.abs(T_g.reshape(16) - r["T"]).max() < POSE_TOL, (s, k)
+            if r["tracks"] is not None:
+                tg = g.last_tracks()
+                for key in ("pl0", "pr0", "pl1", "pr1"):
+                    assert np.array_equal(bits(r["tracks"][key]), bits(tg[key])), (s, k, key)
+                tracked += len(r["tracks"]["pl0"])
+    assert tracked > 30, tracked
