@@ -12,8 +12,11 @@
 // ds_read_u8 traffic saturated the LDS pipe).  This version keeps everything in registers:
 //   * each lane owns PPL consecutive pixels of one window row; it loads the 4 x (PPL+3) source bytes
 //     it needs straight from the (L2 / Infinity-Cache resident) pyramid with unaligned dword loads,
-//     computes the Scharr derivatives in registers (no derivative pyramid in HBM, no LDS tile) and
-//     keeps I, Ix, Iy of its pixels in VGPRs for the whole Newton loop;
+//     computes the Scharr derivatives in registers (no LDS tile) and keeps I, Ix, Iy of its pixels in VGPRs for the whole
+//     Newton loop.  Level 0 always works that way; at the levels >= 1 a many-sequence grey context in exact-sums mode reads the
+//     derivative pairs from the per-frame derivative pyramid instead (k_deriv_levels, svo_internal.hpp; lk_pass's derA), two
+//     int16 planes per pyramid that the image stream fills once per frame — SVO_LK_DERIV=0 and every other build differentiate
+//     in registers at every level;
 //   * the search-image window (2 rows x (PPL+1) bytes per lane) is also held in VGPRs and only
 //     re-loaded when the INTEGER window position changes — in the sub-pixel phase of the Newton
 //     iteration (most steps) the loop touches no memory at all;
@@ -119,6 +122,19 @@ __device__ __forceinline__ void wave_sums2_narrow(int a, int b, float& fa, float
     u = dpp_row_step<0>(u); u = dpp_row_step<1>(u); u = dpp_row_step<2>(u); u = dpp_row_step<3>(u);
     u = wave_join_rows2(u);
     fa = (float)__builtin_amdgcn_readlane(u, 31); fb = (float)__builtin_amdgcn_readlane(u, 63);
+}
+// ---- wave sums of THREE values in one chain (the normal matrix).  After the fold rows 0-1 hold a's partials and rows 2-3 c's;
+// v_permlane16_swap then exchanges the odd rows of that register with the even rows of b: (r0 + r1) holds a's 16 partials in row 0,
+// c's in row 2, and b's in the odd rows (row 1 = b over lanes 0..31, row 3 = b over lanes 32..63).  Four row steps reduce all
+// three; b's two row totals are added on the scalar unit.  Every intermediate is a sum of distinct lanes' partials of ONE value
+// (no row ever mixes two values), so with every lane's |partial| < 2^25 it stays below 64 * 2^25 = 2^31, b's final scalar sum
+// (all 64 lanes) included.  8 VALU instructions + 4 v_readlane instead of 13 + 3.
+__device__ __forceinline__ void wave_sums3_narrow(int a, int b, int c, float& fa, float& fb, float& fc) {
+    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)wave_fold2(a, c), (unsigned)b, false, false);
+    int u = (int)(r[0] + r[1]);
+    u = dpp_row_step<0>(u); u = dpp_row_step<1>(u); u = dpp_row_step<2>(u); u = dpp_row_step<3>(u);
+    fa = (float)__builtin_amdgcn_readlane(u, 15); fc = (float)__builtin_amdgcn_readlane(u, 47);
+    fb = (float)(__builtin_amdgcn_readlane(u, 31) + __builtin_amdgcn_readlane(u, 63));
 }
 // wide form (any input): the fold and PRE - 1 row steps happen on the int32 partials (PRE doublings cannot overflow), then the
 // register is split into 16-bit halves whose sums fit 23 bits
@@ -546,20 +562,39 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
             // compare bounds all three partials: below 2^25 per lane the wave sums stay inside int32 -> narrow reduction
             const bool big = ((unsigned)pA11 | (unsigned)pA22) >= (1u << 25);
             const bool nar = __builtin_amdgcn_ballot_w64(big) == 0ull;
-            if (nar) { wave_sums2_narrow(pA11, pA22, As[0], As[2]); As[1] = wave_sum_narrow(pA12); }
+            if (nar) wave_sums3_narrow(pA11, pA12, pA22, As[0], As[1], As[2]);
             else { wave_sums2_wide<PRE>(pA11, pA22, As[0], As[2]); As[1] = wave_sum_wide<PRE>(pA12); }
         }
         // |sum diff*Ix| <= 8160 * sqrt(CN W^2 * sum Ix^2) (Cauchy-Schwarz): below 2^31 when sum Ix^2 < 2^62 / (8160^2 CN W^2); 5 % margin
         // covers the float rounding of As.  Then the mismatch sums never leave int32 and take the narrow reduction.
         const bool narrow = As[0] < NARROW_LIMIT && As[2] < NARROW_LIMIT;
         const float A11 = As[0] * FLT_SCALE, A12 = As[1] * FLT_SCALE, A22 = As[2] * FLT_SCALE;
-        float Dt = A11 * A22 - A12 * A12;
+        // A12 is a multiple of 2^-20 below 2^42: its square neither underflows nor overflows, so 4 (A12 A12) below is the float
+        // "4.f * A12 * A12" was (a power of two moves through the rounding) and the determinant's product serves both
+        const float A12sq = A12 * A12;
+        float Dt = A11 * A22 - A12sq;
         // lkpyramid.cpp: minEig = (A22 + A11 - sqrt(...)) / (2 * winSize.area());  if (minEig < minEigThreshold || D < FLT_EPSILON) skip.
         // The f32 division and the f64 comparison are folded into one f32 comparison of the numerator against a cut-off the
         // host found by bisection over the floats (lk_mineig_cut): division by a positive constant is monotone, so
         // "(double)fl(num / den) < threshold"  <=>  "num < cut" exactly.
-        const float eig_num = A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12);
-        if (uni(eig_num < crit.mineig_cut || Dt < 1.1920928955078125e-07f)) {
+        // The exact square root (about 15 instructions of IEEE expansion) serves one comparison, so v_sqrt_f32 screens it.  With
+        // t = A22 + A11 and s = sqrtf(rad): the instruction's root is within 1 ulp of the true one, so at most 1 ulp(s) from s; the
+        // two subtractions t - root round once each, by at most ulp(t) / 2 (|t - s| <= t).  A is positive semi-definite up to the
+        // rounding of its three sums, so s <= t (1 + 2^-21) and ulp(s) <= 2 ulp(t): the two numerators differ by at most
+        // 2 + 1/2 + 1/2 = 3 ulp(t) <= 3 * 2^-23 t.  The band is 4 * 2^-23 t = 2^-21 t (an exact scaling; the comparison's own
+        // subtraction adds a relative 2^-24 of a difference that already exceeds the band): outside it both numerators lie on the
+        // same side of the cut.  Inside it, and for radicands below 2^-96 (where the expansion rescales its denormal-range input
+        // and the bare instruction would not; a flat window's rad = 0 is one), the exact expression decides as before.
+        const float eig_tr = A22 + A11, eig_rad = (A11 - A22) * (A11 - A22) + 4.f * A12sq;
+        const float eig_apx = eig_tr - __builtin_amdgcn_sqrtf(eig_rad);
+        bool eig_low;
+        if (uni(fabsf(eig_apx - crit.mineig_cut) > eig_tr * 4.76837158203125e-07f && eig_rad >= 1.262177448353619e-29f)) eig_low = eig_apx < crit.mineig_cut;
+        else {
+            float rad = eig_rad;
+            asm volatile("" : "+v"(rad));                                   // a real branch: without it both roots are computed and selected
+            eig_low = eig_tr - sqrtf(rad) < crit.mineig_cut;
+        }
+        if (uni(eig_low || Dt < 1.1920928955078125e-07f)) {
             if (level == 0) status = 0;
             continue;
         }
@@ -573,7 +608,8 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         // a pixel and touch no memory.
         int j = 0;
         const int max_count = uni_i(crit.max_count);
-        float pdx = 0.f, pdy = 0.f, ldx = 0.f, ldy = 0.f;
+        float2v pd = {0.f, 0.f};                                             // the previous step's delta: an aligned pair, copied by one v_mov_b64
+        float ldx = 0.f, ldy = 0.f;
         bool moved = false, osc = false, conv = false;
         unsigned P0[CN][PPL], P1[CN][PPL];
         auto load_window = [&](int inx, int iny) __attribute__((always_inline)) {
@@ -648,11 +684,15 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
             }
             // "(double)|v| < 0.01" for a float v is exactly "|v| < nextafterf((float)0.01)": 0.01 lies between the floats
             // 0x3C23D70A and 0x3C23D70B, so v < 0.01 (as doubles) <=> v <= 0x3C23D70A <=> v < 0x3C23D70B
-            if (j > 0 && uni(fabsf(dx + pdx) < 0.010000000707805157f) && uni(fabsf(dy + pdy) < 0.010000000707805157f)) {
+            // Both magnitudes below the bound <=> their maximum below it: every operand is finite (Dt >= FLT_EPSILON, the sums are
+            // integers below 2^31 and the products stay far inside f32 by the bounds above), so v_max_f32 never sees a NaN and one
+            // compare and one branch replace two of each.
+            const float2v dl = {dx, dy}, back = dl + pd;
+            if (j > 0 && uni(fmaxf(fabsf(back.x), fabsf(back.y)) < 0.010000000707805157f)) {
                 osc = true;                                                  // nextPts -= delta * 0.5 (applied after the loop)
                 return true;
             }
-            pdx = dx; pdy = dy;
+            pd = dl;
             return ++j >= max_count;
         };
         // epochs of constant integer origin: the inner loop is pure register arithmetic (measured on MI355X, LK chain ms for 32
@@ -660,9 +700,14 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         bool stop = max_count <= 0;
         while (!stop) {
             const float fx0 = floorf(nx), fy0 = floorf(ny);             // (float)(int)floorf(n) == floorf(n) wherever the origin is in reach
-            const int inx = (int)fx0, iny = (int)fy0;
+            // the origin goes to the scalar unit first (load_window needs it there anyway) and the reach test runs on it
+            // (converted before it is made scalar: the asm keeps the compiler from moving v_readfirstlane above the conversion,
+            // which would then run on the vector unit anyway and need a second v_readfirstlane)
+            int vnx = (int)fx0, vny = (int)fy0;
+            asm("" : "+v"(vnx), "+v"(vny));
+            const int inx = uni_i(vnx), iny = uni_i(vny);
             // -W <= in < size  <=>  (unsigned)(in + W) < (unsigned)(size + W): one compare per axis
-            if (uni((unsigned)(inx + W) >= (unsigned)(L.w + W) || (unsigned)(iny + W) >= (unsigned)(L.h + W))) {
+            if ((unsigned)(inx + W) >= (unsigned)(L.w + W) || (unsigned)(iny + W) >= (unsigned)(L.h + W)) {
                 if (level == 0) status = 0;
                 break;
             }

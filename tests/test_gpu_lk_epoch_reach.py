@@ -1,0 +1,240 @@
+"""The LK kernel's epoch entry and the ends of its Newton loop, bit for bit against the CPU oracle.
+
+Epoch entry.  Whenever the integer origin of the search window changes, the kernel tests that the new origin is in reach of the level,
+-W <= origin < size on both axes, before it loads the window; a track that leaves the reach stops (status 0 at level 0).  The points
+here are planted so that tracks cross each of the four limits: rows of start points within a few pixels of one border, on a texture
+that the second image shows six pixels further out, so that Newton's iteration carries the search window out of the image.  That the
+limits are really met is checked on the CPU with an instrumented copy of the oracle's loop (tests/lk_tail_ref.py, itself compared with
+the oracle on the same points): among the origins the tracks go through are -W (the last in reach), -W - 1 (the first outside),
+size - 1 and size, on x and on y, at level 0 and at the levels >= 1.  The kernel must return the oracle's statuses and points, through
+the single-pass stage call and the fused circular match.
+
+With and without derivative planes: the planes exist only in many-sequence contexts, whose LK points are FAST corners.  A nine-sequence
+context over a fast, yawing occlusion-edge scene (tests/lk_epoch_child.py) is compared with the oracle — every field of
+svo_frame_stats, the level-visit, Newton-step and dead-after-pass counters among them — and byte for byte with the same run in a fresh
+process under SVO_LK_DERIV=0.
+
+Ends of the Newton loop.  300 random points on two frames of an occlusion-edge scene (a moving foreground layer, 160 x 120): the copy
+shows, on the CPU, that more than a tenth of the level visits end by the oscillation rule and more than a tenth at the iteration limit.
+The C interface reports no per-feature counters (svo_frame_stats carries their sums per frame), so per feature the kernel is held to
+the oracle's points and statuses of all four passes — a visit that ended one step early or late returns another point — and the
+sums are compared on the frames of the same scene through VisualOdometry; the per-feature counts of the copy are checked against
+the oracle's totals."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as orc
+import scenes
+import lk_tail_ref as ref
+import lk_epoch_child as ech
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+W_IMG, H_IMG, WIN = 112, 96, 21          # three levels at w = 21: 112 x 96, 56 x 48, 28 x 24
+SHIFT = 6
+SIDES = dict(left=(-SHIFT, 0), right=(SHIFT, 0), top=(0, -SHIFT), bottom=(0, SHIFT))
+POSE_TOL = 1e-6                          # as tests/test_gpu_parity.py
+
+
+@pytest.fixture(scope="module")
+def api():
+    from stereo_visual_odometry_amd import api as a
+    assert a._lib.device_count() >= 1, "no HIP device"
+    return a
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def planted(side, lv):
+    """four rows of start points from outside the border to a few pixels inside it, half a pixel apart"""
+    t = np.arange(-30.0 if lv else -9.0, 4.0, 0.5)
+    out = []
+    for k in range(4):
+        if side in ("left", "right"):
+            o = np.full_like(t, 20 + k * 18.3)
+            out.append(np.stack([t if side == "left" else W_IMG - 1 - t, o], 1))
+        else:
+            o = np.full_like(t, 20 + k * 22.7)
+            out.append(np.stack([o, t if side == "top" else H_IMG - 1 - t], 1))
+    return np.concatenate(out).astype(np.float32)
+
+
+_PLANTED = {}
+
+
+def planted_case(side, lv):
+    """(a, b, points, the limits the tracks met) — the CPU part, once per case"""
+    if (side, lv) not in _PLANTED:
+        a = scenes.random_texture(H_IMG, W_IMG, 31, smooth=2)
+        b = scenes.shift_image(a, *SIDES[side])
+        pts = planted(side, lv)
+        A, B = ref.Levels(a, WIN, lv), ref.Levels(b, WIN, lv)
+        assert A.n == lv + 1
+        r = ref.same_as_oracle(A, B, pts, lv)
+        met = set()
+        for _, level, x, y in r["origins"]:
+            w, h = A.size[level]
+            for axis, v, size in (("x", x, w), ("y", y, h)):
+                for name, limit in (("-W", -WIN), ("-W-1", -WIN - 1), ("size-1", size - 1), ("size", size)):
+                    if v == limit:
+                        met.add((min(level, 1), axis, name))
+        _PLANTED[(side, lv)] = (a, b, pts, met)
+    return _PLANTED[(side, lv)]
+
+
+def limits_wanted(side, lv):
+    axis = "x" if side in ("left", "right") else "y"
+    names = ("-W", "-W-1") if side in ("left", "top") else ("size-1", "size")
+    return {(level, axis, n) for level in ((0, 1) if lv else (0,)) for n in names}
+
+
+@pytest.mark.parametrize("lv", [0, 2])
+@pytest.mark.parametrize("side", list(SIDES))
+def test_planted_origins_single_pass(api, side, lv):
+    a, b, pts, met = planted_case(side, lv)
+    assert limits_wanted(side, lv) <= met, (sorted(limits_wanted(side, lv) - met), sorted(met))
+    got, gst = api.calcOpticalFlowPyrLK(a, b, pts, WIN, lv)
+    want, wst = orc.lk_track(orc.Pyramid(a, (WIN, WIN), lv), orc.Pyramid(b, (WIN, WIN), lv), pts, (WIN, WIN), lv)
+    assert np.array_equal(gst, wst), np.flatnonzero(gst != wst)
+    assert np.array_equal(bits(got), bits(want)), np.flatnonzero((bits(got) != bits(want)).any(1))
+    assert 0 < wst.sum() < len(wst), wst.sum()                   # tracks kept and tracks that left the reach
+
+
+@pytest.mark.parametrize("lv", [0, 2])
+@pytest.mark.parametrize("side", list(SIDES))
+def test_planted_origins_fused_circular_match(api, side, lv):
+    """k_lk_chain on the same points; pass L0 -> L1 is the pair whose origins were checked, the passes after it start where it ended"""
+    a, b, pts, _ = planted_case(side, lv)
+    c, d = scenes.shift_image(a, 0, 1), scenes.shift_image(b, 0, 1)
+    over = dict(win_w=WIN, win_h=WIN, max_level=lv)
+    res = api.circularMatching(api.default_config(**over), a, c, b, d, pts)
+    P = [orc.Pyramid(i, (WIN, WIN), lv) for i in (a, c, b, d)]
+    want = orc.circular_match(P[0], P[1], P[2], P[3], pts, orc.default_config(**over))
+    assert np.array_equal(res[4], want[4]), np.flatnonzero(res[4] != want[4])
+    for k, (g, o) in enumerate(zip(res[:4], want[:4])):
+        assert np.array_equal(bits(g), bits(o)), (k, np.flatnonzero((bits(g) != bits(o)).any(1)))
+
+
+# ---------------------------------------------------------------- nine sequences: with the derivative planes, and without
+@pytest.fixture(scope="module")
+def batch_run(api):
+    assert os.environ.get("SVO_LK_DERIV", "1") != "0"
+    return ech.run(api)
+
+
+def oracle_frames(over, frames):
+    """[(ok, T, stats in name order, features)] of a fresh oracle fed the (left, right) frames"""
+    o = orc.VisualOdometry(orc.default_config(**over)); o.initalize_projection_matricies(*ech.projections())
+    out = []
+    for L, R in frames:
+        ok, T = o.stereo_callback(L, R)
+        st = {f[0]: getattr(o.stats, f[0]) for f in o.stats._fields_}
+        out.append((ok, T.reshape(16).copy(), st, [x.copy() for x in o.features()]))
+    return out
+
+
+def test_nine_sequences_equal_the_oracle(api, batch_run):
+    from stereo_visual_odometry_amd import _lib
+    assert all(int(p) & _lib.PATH_INGEST_AHEAD for p in batch_run["paths"]), "the many-sequence front did not run"
+    sq = ech.streams()
+    want = [oracle_frames(ech.OVER, [(s.left[k], s.right[k]) for k in range(ech.N_FRAMES)]) for s in sq]
+    dead = visits = 0
+    for k in range(ech.N_FRAMES):
+        for i in range(ech.B):
+            ok, T, st, f = want[i % 2][k]
+            p = "%d/%d" % (k, i)
+            assert bool(batch_run[p + "/ok"][0]) == ok, p
+            assert np.array_equal(batch_run[p + "/stats"], np.array([st[n] for n in sorted(st)], np.int64)), (p, batch_run[p + "/stats"], st)
+            assert np.abs(batch_run[p + "/T"] - T).max() < POSE_TOL, p
+            assert np.array_equal(batch_run[p + "/xy"], f[0].view(np.uint32)) and np.array_equal(batch_run[p + "/age"], f[1]) and np.array_equal(batch_run[p + "/strength"], f[2]), p
+            dead += sum(v for n, v in st.items() if n.startswith("lk_dead"))
+            visits += st["lk_level_visits"]
+    assert dead > 100 and visits > 10000, (dead, visits)          # tracks left their levels: the out-of-reach exits ran
+
+
+def test_nine_sequences_without_the_planes_are_byte_equal(api, batch_run, tmp_path):
+    out = str(tmp_path / "off.npz")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "lk_epoch_child.py"), out], env=dict(os.environ, SVO_LK_DERIV="0"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "lk epoch child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    off = np.load(out)
+    assert sorted(off.files) == sorted(batch_run)
+    for key in off.files:
+        a, b = off[key], batch_run[key]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), key
+
+
+# ---------------------------------------------------------------- how the Newton loop ends
+T_W, T_H, T_LV, T_SEED, T_POINTS = 160, 120, 2, 3, 300
+
+
+def termination_frames(n=2):
+    from stereo_visual_odometry_amd import synthetic as syn
+    cal = dict(syn.KITTI00, width=T_W, height=T_H, cx=T_W / 2.0, cy=T_H / 2.0)
+    return syn.StereoSequence(cal=cal, n_frames=n, seed=T_SEED, step=0.6, movers=0.5)
+
+
+_TERM = {}
+
+
+def termination_case():
+    if not _TERM:
+        sq = termination_frames()
+        rng = np.random.default_rng(T_SEED)
+        pts = np.stack([rng.uniform(0, T_W, T_POINTS), rng.uniform(0, T_H, T_POINTS)], 1).astype(np.float32)
+        a, b = sq.left[0], sq.left[1]
+        r = ref.same_as_oracle(ref.Levels(a, WIN, T_LV), ref.Levels(b, WIN, T_LV), pts, T_LV)
+        _TERM.update(sq=sq, pts=pts, r=r)
+    return _TERM
+
+
+def test_termination_rules_stage_calls(api):
+    """seed 3 (chosen on the CPU): 53 % of the level visits end by the oscillation rule, 36 % at the iteration limit, 10 % out of reach"""
+    t = termination_case()
+    sq, pts, r = t["sq"], t["pts"], t["r"]
+    ends = np.array([e[2] for e in r["ends"]])
+    share = {k: float((ends == k).mean()) for k in (ref.END_CONVERGED, ref.END_OSCILLATION, ref.END_LIMIT, ref.END_REACH)}
+    print("level visits %d, Newton steps %d, ended by" % (len(ends), int(r["steps"].sum())), share)
+    assert share[ref.END_OSCILLATION] >= 0.1 and share[ref.END_LIMIT] >= 0.1, share
+    assert r["steps"].max() == 30 * (T_LV + 1) and (r["visits"] == T_LV + 1).sum() > 200
+    a, b, c, d = sq.left[0], sq.right[0], sq.left[1], sq.right[1]
+    got, gst = api.calcOpticalFlowPyrLK(a, c, pts, WIN, T_LV)
+    assert np.array_equal(gst, r["status"]) and np.array_equal(bits(got), bits(r["next"]))     # the copy's = the oracle's (same_as_oracle)
+    over = dict(win_w=WIN, win_h=WIN, max_level=T_LV)
+    res = api.circularMatching(api.default_config(**over), a, b, c, d, pts)
+    P = [orc.Pyramid(i, (WIN, WIN), T_LV) for i in (a, b, c, d)]
+    want = orc.circular_match(P[0], P[1], P[2], P[3], pts, orc.default_config(**over))
+    assert np.array_equal(res[4], want[4]), np.flatnonzero(res[4] != want[4])
+    for k, (g, o) in enumerate(zip(res[:4], want[:4])):
+        assert np.array_equal(bits(g), bits(o)), (k, np.flatnonzero((bits(g) != bits(o)).any(1)))
+    assert np.array_equal(bits(want[0]), bits(r["next"]))                                      # pass L0 -> L1 is the pair the copy ran
+
+
+def test_termination_counters_frame_pipeline(api):
+    """The sums of the per-feature counters, per frame, on four frames of the same scene"""
+    sq = termination_frames(4)
+    over = dict(win_w=WIN, win_h=WIN, max_level=T_LV, bucket_start_row=0, max_translation_norm=5.0)
+    from stereo_visual_odometry_amd import synthetic as syn
+    Pl, Pr = syn.projection_matrices(sq.cal)
+    g = api.VisualOdometry(cfg=api.default_config(**over)); g.initalize_projection_matricies(Pl, Pr)
+    o = orc.VisualOdometry(orc.default_config(**over)); o.initalize_projection_matricies(Pl, Pr)
+    steps = 0
+    for k in range(4):
+        ok_g, T_g = g.stereo_callback(sq.left[k], sq.right[k])
+        ok_o, T_o = o.stereo_callback(sq.left[k], sq.right[k])
+        st_o = {f[0]: getattr(o.stats, f[0]) for f in o.stats._fields_}
+        assert ok_g == ok_o and g.stats.as_dict() == st_o, (k, g.stats.as_dict(), st_o)
+        assert np.array_equal(bits(g.features()[0]), bits(o.features()[0])) and np.abs(T_g - T_o).max() < POSE_TOL, k
+        if st_o["n_into_lk"]:
+            to, tg = o.last_tracks(), g.last_tracks()
+            for key in ("pl0", "pr0", "pl1", "pr1"):
+                assert np.array_equal(bits(to[key]), bits(tg[key])), (k, key)
+        steps += st_o["lk_newton_steps"]
+    assert steps > 5000, steps
