@@ -11,6 +11,8 @@ for p in (os.path.dirname(HERE), HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from gpu_kit import calib  # noqa: E402
+
 B = 9                    # the smallest many-sequence context: from nine sequences on the image stream builds the pyramids ahead
 N_FRAMES = 3
 
@@ -28,11 +30,6 @@ SCENES = {
     "odd": (203, 187, dict(win_w=21, win_h=21, max_level=3), dict(step=0.3)),
     "borders": (200, 169, dict(win_w=21, win_h=21, max_level=3, bucket_start_row=0), dict(step=0.9, yaw_amp_deg=1.2)),
 }
-
-
-def calib(w, h):
-    from stereo_visual_odometry_amd import synthetic as syn
-    return dict(syn.KITTI00, width=w, height=h, cx=w / 2.0, cy=h / 2.0)
 
 
 def config_over(name):

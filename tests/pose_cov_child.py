@@ -11,6 +11,8 @@ for p in (os.path.dirname(HERE), HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from gpu_kit import calib  # noqa: E402
+
 W, H = 320, 160
 
 
@@ -18,7 +20,7 @@ def run_cases():
     """-> dict of arrays: every covariance a lone stream, a ten-sequence context and the stage entry produce, and the path bits."""
     import pose_cov_ref as ref
     from stereo_visual_odometry_amd import api, synthetic as syn
-    cal = dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0)
+    cal = calib(W, H)
     seq = syn.StereoSequence(cal=cal, n_frames=4, seed=3, step=0.3)
     P = syn.projection_matrices(cal)
     out = {}

@@ -3,13 +3,11 @@ libsvo_hip.so, read like test_detect_mask_code_object.py reads the masked detect
 no spills, and within the LDS and VGPR figures found when they were written (profiles/r13_clahe_code_object.md): k_clahe_lut 20 - 21
 VGPRs and 4128 bytes of LDS (four per-wave histograms and the two partial-sum rows), k_clahe_apply 41 VGPRs and 8192 bytes (two LUT
 rows of 16 tiles).  Both stay at or below 64 VGPRs, the step below which a SIMD holds eight waves of a kernel."""
-import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import by_name
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 # Itanium-mangled kernel symbol -> (readable name, LDS bytes, VGPR bound)
 CLAHE = {}
@@ -19,20 +17,8 @@ for bpp in (1, 2, 3, 4):
 
 
 @pytest.fixture(scope="module")
-def clahe_kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_clahe")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- \.agpr_count:", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            if m and m.group(1) in CLAHE:
-                found[m.group(1)] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size):\s+(\d+)", block)}
-    return found
+def clahe_kernels():
+    return by_name(CLAHE)
 
 
 def test_every_clahe_kernel_is_built(clahe_kernels):

@@ -2,13 +2,11 @@
 read like test_img_code_object.py reads the pyramid kernels.  The bodies are shared routines behind thin wrappers
 (svo_kernels_img.hip: fast_tile, bucket_walk, bucket_order_emit); the budget of each wrapper is that of the kernel it replaced,
 measured before the routines were shared (profiles/r09_detect_code_objects.md): the same LDS, no scratch, no more registers."""
-import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import by_prefix
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 # Itanium-mangled prefix of the kernel symbol -> (readable name, LDS bytes, VGPRs before the routines were shared)
 DETECT = {
@@ -21,21 +19,8 @@ DETECT = {
 
 
 @pytest.fixture(scope="module")
-def detect_kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_detect")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- \.agpr_count:", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            key = next((k for k in DETECT if m and m.group(1).startswith(k)), None)
-            if key:
-                found[key] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)", block)}
-    return found
+def detect_kernels():
+    return by_prefix(DETECT)
 
 
 def test_every_detection_kernel_is_built(detect_kernels):

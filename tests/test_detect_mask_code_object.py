@@ -4,13 +4,11 @@ one FAST tile (5432 bytes, as the plain kernels), and at most 64 VGPRs — the s
 where the plain FAST kernels (50 and 61 registers) sit too.  Found when they were written (profiles/r12_detect_mask_code_object.md):
 k_fast_masked 53 VGPRs, k_fast_strided_masked 62, k_fast_score_map_masked 50; 5432 bytes of LDS each; no scratch, no spills.  That
 the plain kernels did not move is test_detect_code_object.py's and test_img_code_object.py's business."""
-import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import by_prefix
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 # Itanium-mangled prefix of the kernel symbol -> (readable name, LDS bytes, VGPR bound)
 MASKED = {
@@ -21,21 +19,8 @@ MASKED = {
 
 
 @pytest.fixture(scope="module")
-def masked_kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_detect_mask")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- \.agpr_count:", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            key = next((k for k in MASKED if m and m.group(1).startswith(k)), None)
-            if key:
-                found[key] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)", block)}
-    return found
+def masked_kernels():
+    return by_prefix(MASKED)
 
 
 def test_every_masked_kernel_is_built(masked_kernels):

@@ -5,13 +5,10 @@ import numpy as np
 
 import detect_mask_ref as ref
 import oracle_lib as orc
+from gpu_kit import f32_bits as bits
 
 W, H = 323, 163
 OVER = dict(max_translation_norm=2.0)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_all_255_mask_reproduces_the_oracle_bit_for_bit():

@@ -6,13 +6,10 @@ import pytest
 
 import fast_ref as fr
 import oracle_lib as orc
+from gpu_kit import f32_bits as bits
 
 NAMES = fr.case_names()
 BIG = [n for n in NAMES if n != "seam" and fr.case_image(n).shape[0] >= 19]          # 19x67 and larger
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_fixture_images_are_what_they_claim():

@@ -6,15 +6,9 @@ import pytest
 
 import oracle_lib as orc
 import scenes
+from gpu_kit import api  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
 
 
 def small_seq(n=3, seed=4):

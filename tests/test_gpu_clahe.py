@@ -17,18 +17,12 @@ import rectify_ref
 import scenes
 import test_gpu_rectify as tr
 from test_gpu_input_format import SIZES, assert_runs_equal, cfg_for, coloured, grey_streams, run, strided
-from test_gpu_rectify import row, same, same_row, snap
+from test_gpu_rectify import row, same_row
+from gpu_kit import api, raw_bits, same, snap  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 CLIP, TILES = 2.0, (8, 8)
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
 
 
 _eq_cache = {}
@@ -346,6 +340,6 @@ def test_setter_before_the_first_frame_and_member_circular_matching(api):
         fs.points, fs.ages, fs.strengths = pts.copy(), np.zeros(len(pts), np.int32), np.ones(len(pts), np.int32)
         res = vo.circularMatching(Lq[1], Rq[1], pts, fs)
         ok, T = vo.stereo_callback(Lq[2], Rq[2])
-        outs.append([tr.bits(np.ascontiguousarray(a)) for a in res] + [tr.bits(fs.points), np.asarray(T).view(np.uint64), np.array([ok])])
+        outs.append([raw_bits(np.ascontiguousarray(a)) for a in res] + [raw_bits(fs.points), np.asarray(T).view(np.uint64), np.array([ok])])
         vo.close()
     assert len(outs[0][0]) > 20 and same(outs[0], outs[1])

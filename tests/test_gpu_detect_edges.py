@@ -13,21 +13,11 @@ import pytest
 import fast_ref as fr
 import oracle_lib as orc
 import scenes
+from gpu_kit import api, f32_bits as bits  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 NAMES = fr.case_names()
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def same_features(got, want):

@@ -4,31 +4,18 @@ features, tracks and inlier masks bit for bit, poses within 1e-6 — on lone-str
 lists, with static, per-sequence and per-frame masks, frames in flight, second passes, dropped tracks, clearing, colour input,
 rectification, ragged frames and SVO_GRAPH=1.  A mask belongs to a left image: the one set before call k is applied by call k + 1."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import detect_mask_ref as ref
 import oracle_lib as orc
+from gpu_kit import api, f32_bits as bits, run_child, same, snap  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = {"even": (320, 160), "odd": (323, 163)}       # tests/test_gpu_input_format.py's: whole 64 x 16 FAST tiles, and partial ones on every side
 OVER = dict(max_translation_norm=2.0)
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def streams_of(n_seq, n_frames, w, h, seed0=900, blank=()):
@@ -293,7 +280,7 @@ def test_clearing_mid_run(api):
 # ------------------------------------------------------------------------------------------------ 4. no-op guarantees
 @pytest.mark.parametrize("n_seq", [1, 10])
 def test_all_255_mask_changes_nothing_and_no_mask_sets_no_bit(api, n_seq):
-    from test_gpu_rectify import row, same, same_row, snap
+    from test_gpu_rectify import row, same_row
     w, h = SIZES["odd"]
     streams, P = streams_of(n_seq, 4, w, h)
     outs = []
@@ -369,8 +356,8 @@ def test_graph_mode_runs_masked_frames_from_the_launch_list(api, tmp_path):
     import detect_mask_child as child
     out = tmp_path / "graph.npz"
     env = dict(os.environ, SVO_GRAPH="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "detect_mask_child.py"), str(out)], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "detect mask child ok" in p.stdout, p.stdout + p.stderr
+    p = run_child("detect_mask_child.py", out, env=env)
+    assert "detect mask child ok" in p.stdout, p.stdout + p.stderr
     d = np.load(out)
     L = api._lib
     for name, n_seq in child.RUNS:

@@ -9,7 +9,6 @@ device inputs).  The format is stream-ordered like svo_clear_rectification."""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,19 +18,13 @@ import input_format_ref as ref
 import pyramid_ref
 import rectify_ref
 import test_gpu_rectify as tr
-from test_gpu_rectify import assert_runs_equal, row, same, same_row, snap
+from test_gpu_rectify import assert_runs_equal, row, same_row
+from gpu_kit import api, calib, raw_bits, run_child, same, snap, streams  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = {"even": (320, 160), "odd": (323, 163)}       # the odd one: full and partial tiles at both tile shapes, edge tiles on all four sides
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
 
 
 _grey_cache = {}
@@ -42,12 +35,8 @@ def grey_streams(n_seq, n_frames, seed0, w, h):
     key = (n_seq, n_frames, seed0, w, h)
     if key not in _grey_cache:
         from stereo_visual_odometry_amd import synthetic as syn
-        cal = dict(syn.KITTI00, width=w, height=h, fx=300.0, fy=300.0, cx=w / 2.0, cy=h / 2.0)
-        out = []
-        for i in range(n_seq):
-            s = syn.StereoSequence(cal=cal, n_frames=n_frames, seed=seed0 + 31 * i, step=0.3)
-            out.append((list(s.left), list(s.right)))
-        _grey_cache[key] = (out, syn.projection_matrices(cal))
+        cal = dict(calib(w, h), fx=300.0, fy=300.0)
+        _grey_cache[key] = (streams(n_seq, n_frames, seed0, w, h, cal=cal), syn.projection_matrices(cal))
     return _grey_cache[key]
 
 
@@ -263,7 +252,7 @@ def test_member_circular_matching_with_a_format(api):
         fs.points, fs.ages, fs.strengths = pts.copy(), np.zeros(len(pts), np.int32), np.ones(len(pts), np.int32)
         res = vo.circularMatching(L[1], R[1], pts, fs)
         ok, T = vo.stereo_callback(L[2], R[2])
-        outs.append([tr.bits(np.ascontiguousarray(a)) for a in res] + [tr.bits(fs.points), np.asarray(T).view(np.uint64), np.array([ok])])
+        outs.append([raw_bits(np.ascontiguousarray(a)) for a in res] + [raw_bits(fs.points), np.asarray(T).view(np.uint64), np.array([ok])])
         if fmt:
             with pytest.raises(ValueError):
                 vo.circularMatching(grey[0][0][1], grey[0][1][1], pts, fs)      # a grey frame is not a bgra8 frame
@@ -297,8 +286,8 @@ def test_graph_mode_gives_the_same_results(api, tmp_path):
     import input_format_child as child
     out = tmp_path / "graph.npz"
     env = dict(os.environ, SVO_GRAPH="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "input_format_child.py"), str(out)], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "input format child ok" in p.stdout, p.stdout + p.stderr
+    p = run_child("input_format_child.py", out, env=env)
+    assert "input format child ok" in p.stdout, p.stdout + p.stderr
     d = np.load(out)
     L = api._lib
     for name, n_seq, mode, fmt in child.RUNS:

@@ -9,26 +9,17 @@ Origins at exactly -W and size - 1 cannot be planted through the frame pipeline 
 origin of a window is where Newton's iteration takes it); the `borders` scene offers features inside w of all four borders and corners
 with a camera fast enough that tracks leave the frame, and the test checks both."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib as orc
 import lk_deriv_child as ldc
+from gpu_kit import api, run_child  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 POSE_TOL = 1e-6          # as tests/test_gpu_parity.py: the f64 pose stage is not part of this change
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
 
 
 @pytest.fixture(scope="module")
@@ -126,8 +117,8 @@ def test_switch_off_is_byte_equal(api, default_runs, tmp_path):
     """SVO_LK_DERIV=0 in a fresh process: the same bytes from every run above, the same svo_get_last_frame_path."""
     out = str(tmp_path / "off.npz")
     env = dict(os.environ, SVO_LK_DERIV="0")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "lk_deriv_child.py"), out], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "lk deriv child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    r = run_child("lk_deriv_child.py", out, env=env)
+    assert "lk deriv child ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
     off = np.load(out)
     assert sorted(off.files) == sorted(default_runs)
     for key in off.files:

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as orc
+from gpu_kit import api, calib, f32_bits as bits  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,13 +21,6 @@ LK_SLOTS = 16384                         # LK_MAX_GRID in svo_kernels_lk.hip: bl
 VARIANTS = {"default": {}, "max_count0": dict(lk_max_count=0), "epsilon0": dict(lk_epsilon=0.0)}
 
 
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
-
-
 @pytest.fixture(scope="module", autouse=True)
 def oracle_threads():
     orc.set_threads(16)                  # the oracle's results do not depend on its thread count
@@ -34,19 +28,10 @@ def oracle_threads():
     orc.set_threads(1)
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def cal():
-    from stereo_visual_odometry_amd import synthetic as syn
-    return dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0)
-
-
 @pytest.fixture(scope="module")
 def seq():
     from stereo_visual_odometry_amd import synthetic as syn
-    return syn.StereoSequence(cal=cal(), n_frames=3, seed=21, step=0.4)
+    return syn.StereoSequence(cal=calib(W, H), n_frames=3, seed=21, step=0.4)
 
 
 def points(seq, n):
@@ -115,7 +100,7 @@ def test_frame_pipeline_counts_and_criteria(api, seq, win, cn, variant):
     """max_features = 1, 63, 64, 65 and unlimited through stereo_callback: statistics (LK level visits, Newton steps, the pass each
     dead feature died in, every count), feature sets and track lists equal the oracle's."""
     from stereo_visual_odometry_amd import synthetic as syn
-    Pl, Pr = syn.projection_matrices(cal())
+    Pl, Pr = syn.projection_matrices(calib(W, H))
     L = [bgr(a) for a in seq.left] if cn == 3 else list(seq.left)
     R = [bgr(a) for a in seq.right] if cn == 3 else list(seq.right)
     visits = 0

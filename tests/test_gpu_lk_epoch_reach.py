@@ -21,8 +21,6 @@ the oracle's points and statuses of all four passes — a visit that ended one s
 sums are compared on the frames of the same scene through VisualOdometry; the per-feature counts of the copy are checked against
 the oracle's totals."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -31,25 +29,14 @@ import oracle_lib as orc
 import scenes
 import lk_tail_ref as ref
 import lk_epoch_child as ech
+from gpu_kit import api, f32_bits as bits, run_child  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 W_IMG, H_IMG, WIN = 112, 96, 21          # three levels at w = 21: 112 x 96, 56 x 48, 28 x 24
 SHIFT = 6
 SIDES = dict(left=(-SHIFT, 0), right=(SHIFT, 0), top=(0, -SHIFT), bottom=(0, SHIFT))
 POSE_TOL = 1e-6                          # as tests/test_gpu_parity.py
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def planted(side, lv):
@@ -161,9 +148,8 @@ def test_nine_sequences_equal_the_oracle(api, batch_run):
 
 def test_nine_sequences_without_the_planes_are_byte_equal(api, batch_run, tmp_path):
     out = str(tmp_path / "off.npz")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "lk_epoch_child.py"), out], env=dict(os.environ, SVO_LK_DERIV="0"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "lk epoch child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    r = run_child("lk_epoch_child.py", out, env=dict(os.environ, SVO_LK_DERIV="0"))
+    assert "lk epoch child ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
     off = np.load(out)
     assert sorted(off.files) == sorted(batch_run)
     for key in off.files:

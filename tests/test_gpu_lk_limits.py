@@ -14,8 +14,6 @@ BGR kernels are built up to w = 21 only, so BGR w = 31 does not exist; w = 15 st
 take grey images only; three channels go through a BGR VisualOdometry, whose LK points are FAST corners (integer coordinates: the
 windows of odd w start on a pixel, as the proof needs)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -26,23 +24,12 @@ import lk_limits_scenes as lim
 import lk_limits_child as lch
 import lk_deriv_child as ldc
 from test_gpu_parity import lk_points
+from gpu_kit import api, f32_bits as bits, run_child  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 POSE_TOL = 1e-6          # as tests/test_gpu_lk_deriv_levels.py
 N_BORDER = 60
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def track_both(api, case, max_level):
@@ -186,9 +173,8 @@ def test_many_sequence_pipeline_with_derivative_planes(api, batch_runs):
 def test_pipeline_without_the_planes_is_byte_equal(api, batch_runs, tmp_path):
     """SVO_LK_DERIV=0 in a fresh process: the kernel differentiates in registers and must return the same bytes, pose included"""
     out = str(tmp_path / "off.npz")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "lk_limits_child.py"), out], env=dict(os.environ, SVO_LK_DERIV="0"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "lk limits child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    r = run_child("lk_limits_child.py", out, env=dict(os.environ, SVO_LK_DERIV="0"))
+    assert "lk limits child ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
     off = np.load(out)
     assert sorted(off.files) == sorted(batch_runs)
     for key in off.files:

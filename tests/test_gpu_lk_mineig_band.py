@@ -21,23 +21,13 @@ import pytest
 
 import oracle_lib as orc
 import scenes
+from gpu_kit import api, f32_bits as bits  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 W_IMG, H_IMG, WIN = 112, 96, 21
 N_POINTS, N_FLIPS = 60, 12
 FIXED = [0.0, 1e-3, 1e-12, -1.0, 1e30]           # besides the flips: the default, "everything passes", "everything fails"
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def bump_centres():

@@ -12,22 +12,12 @@ import pytest
 
 import oracle_lib as orc
 import scenes
+from gpu_kit import api, f32_bits as bits  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 POSE_TOL_T = 1e-6      # metres, per frame  (north_star states 1e-4; the implementation holds 1e-6)
 POSE_TOL_R = 1e-6      # radians, per frame
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1, "no HIP device"
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def rot_angle(Ra, Rb):

@@ -6,14 +6,13 @@ Tolerance (derived, pose_cov_ref.tolerance): |cov_gpu - cov_ref|_F <= 8 (kappa2(
 cov_T alike; every compared case must have kappa2(H) <= 1e7 in the reference, asserted first."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import pose_cov_ref as ref
 import pose_cov_child as child
+from gpu_kit import api, calib, run_child  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +22,6 @@ W, H = child.W, child.H
 PC_THREADS = 256                  # k_pose_cov's block: thread v takes points v, v + 256, ...; n = 257 is the first second point
 KAPPA_MAX = 1e7
 MODES = {"residual": ref.COV_RESIDUAL, "fixed": ref.COV_FIXED_SIGMA}
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
 
 
 def bits(a):
@@ -112,16 +104,11 @@ def test_stage_entry_identity_pose(api):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. pipeline
-def calib():
-    from stereo_visual_odometry_amd import synthetic as syn
-    return dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0)
-
-
 @pytest.fixture(scope="module")
 def frames():
     from stereo_visual_odometry_amd import synthetic as syn
-    s = syn.StereoSequence(cal=calib(), n_frames=5, seed=3, step=0.3)
-    return list(s.left), list(s.right), syn.projection_matrices(calib())
+    s = syn.StereoSequence(cal=calib(W, H), n_frames=5, seed=3, step=0.3)
+    return list(s.left), list(s.right), syn.projection_matrices(calib(W, H))
 
 
 def ref_of_frame(vo, i, T, Pl, mode, sigma=1.0):
@@ -333,8 +320,8 @@ def test_graph_and_lean_builds_give_the_same_bits(launch_list_cases, knob, tmp_p
     env.pop("SVO_GRAPH", None); env.pop("SVO_FORCE_LEAN", None)
     env[knob] = "1"
     out = str(tmp_path / "cases.npz")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "pose_cov_child.py"), out], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "pose cov child ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
+    r = run_child("pose_cov_child.py", out, cwd=ROOT, env=env)
+    assert "pose cov child ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
     got = np.load(out)
     from stereo_visual_odometry_amd import _lib
     bit = _lib.PATH_GRAPH if knob == "SVO_GRAPH" else _lib.PATH_LEAN

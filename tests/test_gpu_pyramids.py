@@ -15,26 +15,17 @@ image (0xAB in the gap)."""
 import ctypes as C
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import pyramid_ref as ref
 import rectify_ref
+from gpu_kit import api, projections, run_child  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 RAW_W, RAW_H = 344, 180          # raw frames of the rectifying cases (test_gpu_rectify.cam_pair)
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
 
 
 def lk_pad_for(win):
@@ -161,12 +152,6 @@ def make_stream(w, h, n, seed, cn=1, black=()):
             a, b = np.zeros_like(a), np.zeros_like(b)
         L.append(a); R.append(b)
     return L, R
-
-
-def projections(w, h):
-    from stereo_visual_odometry_amd import synthetic as syn
-    Pl, Pr = syn.projection_matrices(dict(syn.KITTI00, width=w, height=h, cx=w / 2.0, cy=h / 2.0))
-    return Pl.astype(np.float32), Pr.astype(np.float32)
 
 
 class Ctx:
@@ -352,9 +337,7 @@ def test_frame_pyramids_byte_exact(api, case):
 def test_many_sequences_without_build_ahead():
     """The many-sequence k_ingest_pyr1 on the frame's own stream (SVO_INGEST_AHEAD=0, read once per process): a fresh child."""
     env = dict(os.environ, SVO_INGEST_AHEAD="0")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "pyramid_child.py"), json.dumps(MANY_CASES)], env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    r = run_child("pyramid_child.py", json.dumps(MANY_CASES), env=env, timeout=600)
     assert "pyramid child ok: %d cases" % len(MANY_CASES) in r.stdout
 
 

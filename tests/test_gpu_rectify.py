@@ -8,18 +8,12 @@ import numpy as np
 import pytest
 
 import rectify_ref as ref
+from gpu_kit import api, calib, same, snap, streams  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 W, H = 320, 160                 # rectified (the context's size)
 RW, RH = 344, 180               # raw
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
 
 
 def rot(ax, ay, az):
@@ -50,35 +44,12 @@ def projections(pair):
 
 def raw_streams(n_seq, n_frames, seed0, cn=1):
     """n_seq independent synthetic sequences rendered at the RAW size (their bytes only need texture, not a true lens)."""
-    from stereo_visual_odometry_amd import synthetic as syn
-    cal = dict(syn.KITTI00, width=RW, height=RH, fx=300.0, fy=300.0, cx=RW / 2.0, cy=RH / 2.0)
-    out = []
-    for i in range(n_seq):
-        s = syn.StereoSequence(cal=cal, n_frames=n_frames, seed=seed0 + 31 * i, step=0.3)
-        L, R = list(s.left), list(s.right)
-        if cn == 3:
-            bgr = lambda a: np.ascontiguousarray(np.stack([a, np.roll(a, 1, 0), 255 - a], -1))
-            L, R = [bgr(a) for a in L], [bgr(a) for a in R]
-        out.append((L, R))
-    return out
+    return streams(n_seq, n_frames, seed0, RW, RH, cn, cal=dict(calib(RW, RH), fx=300.0, fy=300.0))
 
 
 def rectified(streams, maps_per_seq):
     return [([ref.remap(a, *maps_per_seq[i][0]) for a in L], [ref.remap(a, *maps_per_seq[i][1]) for a in R])
             for i, (L, R) in enumerate(streams)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
-def snap(vo, i):
-    f = vo.features(i); t = vo.last_tracks(i)
-    return [bits(f[0]), f[1], f[2]] + [bits(t[k]) for k in ("pl0", "pr0", "pl1", "pr1", "world")] + [t["inlier"]]
-
-
-def same(a, b):
-    return len(a) == len(b) and all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
 
 
 def row(ok, T, st):

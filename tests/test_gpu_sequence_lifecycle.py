@@ -6,61 +6,26 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import gpu_kit
+from gpu_kit import api, same as same_snap, snap  # noqa: F401  (the fixture is found by name)
+
 pytestmark = pytest.mark.gpu
 
 W, H = 320, 160
 
 
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
-
-
-def calib():
-    from stereo_visual_odometry_amd import synthetic as syn
-    return dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0)
-
-
 def make_streams(n_seq, n_frames, seed0, cn=1):
-    """n_seq independent synthetic stereo sequences -> [(lefts, rights)]; cn == 3: interleaved BGR frames."""
-    from stereo_visual_odometry_amd import synthetic as syn
-    out = []
-    for i in range(n_seq):
-        s = syn.StereoSequence(cal=calib(), n_frames=n_frames, seed=seed0 + 31 * i, step=0.3)
-        L, R = list(s.left), list(s.right)
-        if cn == 3:
-            bgr = lambda a: np.ascontiguousarray(np.stack([a, np.roll(a, 1, 0), 255 - a], -1))
-            L, R = [bgr(a) for a in L], [bgr(a) for a in R]
-        out.append((L, R))
-    return out
+    return gpu_kit.streams(n_seq, n_frames, seed0, W, H, cn)
 
 
 def projections(scale=1.0):
-    from stereo_visual_odometry_amd import synthetic as syn
-    Pl, Pr = syn.projection_matrices(calib())
-    Pl, Pr = Pl.astype(np.float32).copy(), Pr.astype(np.float32).copy()
+    Pl, Pr = gpu_kit.projections(W, H)
     Pl[0, 0] *= scale; Pr[0, 0] *= scale; Pr[0, 3] *= scale
     return Pl, Pr
 
 
 def cfg_for(api, **over):
     return api.default_config(max_translation_norm=2.0, **over)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
-def snap(vo, i):
-    """Everything a frame leaves behind for sequence i: the feature set and the compacted tracks."""
-    f = vo.features(i); t = vo.last_tracks(i)
-    return [bits(f[0]), f[1], f[2]] + [bits(t[k]) for k in ("pl0", "pr0", "pl1", "pr1", "world")] + [t["inlier"]]
-
-
-def same_snap(a, b):
-    return len(a) == len(b) and all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
 
 
 def row(ok, T, st):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as orc
+from gpu_kit import api, calib, raw_bits as bits, run_child  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,25 +29,9 @@ LEAN_ROOM = 96                          # device_sharing() in svo_api.hip
 CANDIDATES = [(22, 1, 0), (31, 1, 1), (17, 1, 1), (23, 1, 1), (10, 3, 1), (12, 3, 1), (21, 1, 0), (31, 1, 0), (21, 3, 0)]
 
 
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
 def rot_angle(Ra, Rb):
     c = (np.trace(Ra.T @ Rb) - 1) / 2
     return float(np.arccos(np.clip(c, -1, 1)))
-
-
-def cal():
-    from stereo_visual_odometry_amd import synthetic as syn
-    return dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0)
 
 
 def probe(api):
@@ -93,7 +78,7 @@ def make_streams(n_frames, cn, seeds=(70, 71, 72), movers=(0.0, 0.3, 0.3), black
     from stereo_visual_odometry_amd import synthetic as syn
     out = []
     for s, (seed, mv) in enumerate(zip(seeds, movers)):
-        sq = syn.StereoSequence(cal=cal(), n_frames=n_frames, seed=seed, step=0.3, movers=mv)
+        sq = syn.StereoSequence(cal=calib(W, H), n_frames=n_frames, seed=seed, step=0.3, movers=mv)
         L, R = list(sq.left), list(sq.right)
         if s == 2 and black:
             z = np.zeros_like(L[0])
@@ -106,7 +91,7 @@ def make_streams(n_frames, cn, seeds=(70, 71, 72), movers=(0.0, 0.3, 0.3), black
 
 def oracle_runs(streams, over, n_frames):
     from stereo_visual_odometry_amd import synthetic as syn
-    Pl, Pr = syn.projection_matrices(cal())
+    Pl, Pr = syn.projection_matrices(calib(W, H))
     want = []
     for L, R in streams:
         o = orc.VisualOdometry(orc.default_config(**over)); o.initalize_projection_matricies(Pl, Pr)
@@ -126,7 +111,7 @@ class Ctx:
         import torch
         from stereo_visual_odometry_amd import synthetic as syn
         self.vo = api.BatchVisualOdometry(W, H, B, api.default_config(**over))
-        self.vo.initalize_projection_matricies(*syn.projection_matrices(cal()))
+        self.vo.initalize_projection_matricies(*syn.projection_matrices(calib(W, H)))
         self.pick, self.cn = pick, over.get("channels", 1)
         self.dev = [[(torch.from_numpy(np.ascontiguousarray(l)).cuda(), torch.from_numpy(np.ascontiguousarray(r)).cuda())
                      for l, r in zip(L, R)] for L, R in streams]
@@ -383,6 +368,5 @@ def test_forced_lean_parity_selection(which):
 
 def test_forced_lean_takes_the_lean_builds():
     """Under the knob, lone, many-sequence and stage contexts report the lean bit (tests/lean_child.py)."""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "lean_child.py")], cwd=ROOT, env=forced_env(),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "lean child ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
+    r = run_child("lean_child.py", cwd=ROOT, env=forced_env())
+    assert "lean child ok" in r.stdout, (r.stdout + r.stderr)[-3000:]

@@ -22,23 +22,13 @@ import pytest
 
 import oracle_lib as orc
 import triangulate_ref as ref
+from gpu_kit import api, raw_bits as bits  # noqa: F401  (the fixture is found by name)
 
 pytestmark = pytest.mark.gpu
 
 POSE_TOL = 1e-6                         # as test_gpu_parity.py
 PREFIXES = (1, 15, 16, 17, 63, 64, 65)  # the 16- and 64-lane wave shapes of triangulate_body and their neighbours
 FORCED_LEAN = os.environ.get("SVO_FORCE_LEAN") == "1"
-
-
-@pytest.fixture(scope="module")
-def api():
-    from stereo_visual_odometry_amd import api as a
-    assert a._lib.device_count() >= 1
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
 
 
 def rot_angle(Ra, Rb):

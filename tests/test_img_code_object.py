@@ -2,13 +2,11 @@
 the LK kernels.  They run beside the LK kernel's six waves of 80 registers, which leave 32 registers per lane, so none
 may need more; none may use scratch; and their LDS follows from the tile constants (k_front_a / k_front_b run a pyramid body
 beside a detection body, so theirs is the larger of the two)."""
-import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import by_prefix
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 # Itanium-mangled prefix of the kernel symbol -> (readable name, LDS bytes)
 PYRAMID = {
@@ -23,21 +21,8 @@ FRONT = {"_Z9k_front_aILb0EEv": ("k_front_a<false>", 7952, 50), "_Z9k_front_aILb
 
 
 @pytest.fixture(scope="module")
-def img_kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_img")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- \.agpr_count:", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            key = next((k for k in list(PYRAMID) + list(FRONT) if m and m.group(1).startswith(k)), None)
-            if key:
-                found[key] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)", block)}
-    return found
+def img_kernels():
+    return by_prefix(list(PYRAMID) + list(FRONT))
 
 
 def test_every_pyramid_kernel_is_built(img_kernels):

@@ -3,13 +3,11 @@ test_img_code_object.py reads the plain ones.  Only the tile fill differs from t
 the plain kernel's; none may use scratch; and the non-rectifying many-sequence forms run on the image stream beside the LK
 kernel's six waves of 80 registers, which leave 32 registers per lane.  The rectifying x converting forms are
 printed: DESIGN.md section 2 records their counts and what a count above 32 costs the build-ahead path."""
-import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import by_prefix
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 BPPS = (2, 3, 4)                                  # yuv422 | bgr8 rgb8 | bgra8 rgba8
 RECT = {False: "Lb0E", True: "Lb1E"}
@@ -27,21 +25,8 @@ for bpp in BPPS:
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_in")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- \.agpr_count:", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            key = next((k for k in KERNELS if m and m.group(1).startswith(k)), None)
-            if key:
-                found[key] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)", block)}
-    return found
+def kernels():
+    return by_prefix(KERNELS)
 
 
 def test_every_converting_kernel_is_built(kernels):

@@ -4,12 +4,11 @@ hold more, in VGPRs and AGPRs together.  The full EPnP builds keep their linear 
 in static LDS, (64 / EP_G_LONE) hypotheses of EP_STRIDE doubles; the two refine builds share LmShared."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, ROOT, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import ROOT, by_name
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 # Itanium-mangled symbol -> readable name: the twelve kernels of svo_kernels_pnp.hip
 KERNELS = {
@@ -19,7 +18,6 @@ KERNELS = {
     "_Z11k_pnp_final10DevBuffers": "k_pnp_final", "_Z16k_pnp_final_lean10DevBuffers": "k_pnp_final_lean", "_Z9k_pnp_p3p10DevBuffers": "k_pnp_p3p",
     "_Z19k_inverse_transformPKdS0_Pd": "k_inverse_transform",
 }
-FIELDS = r"\.(agpr_count|vgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)"
 
 
 def source_define(name):
@@ -29,20 +27,8 @@ def source_define(name):
 
 
 @pytest.fixture(scope="module")
-def pnp_kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_pnp")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- (?=\.agpr_count:)", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            if m and m.group(1) in KERNELS:
-                found[KERNELS[m.group(1)]] = {k: int(v) for k, v in re.findall(FIELDS, block)}
-    return found
+def pnp_kernels():
+    return {KERNELS[name]: k for name, k in by_name(KERNELS).items()}
 
 
 def test_all_twelve_kernels_are_built(pnp_kernels):

@@ -2,33 +2,18 @@
 test_pnp_code_object.py reads its neighbours.  A co-resident context launches the `_lean` build beside four LK waves of 104
 registers, which leave 96 per lane: it may hold no more, in VGPRs and AGPRs together.  The full build keeps the 28 sums in
 registers (no scratch).  Both share PcShared.  The counts as built are in profiles/r11_pose_cov_code_object.md."""
-import re
-import subprocess
 
 import pytest
 
-from test_lk_code_object import LIB, READELF, device_code_objects
-from test_lk_code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
+from code_object import by_name
+from code_object import pytestmark  # noqa: F401  (same skip rule: the library and llvm-readelf must exist)
 
 KERNELS = {"_Z10k_pose_cov10DevBuffers7CovArgs": "k_pose_cov", "_Z15k_pose_cov_lean10DevBuffers7CovArgs": "k_pose_cov_lean"}
-FIELDS = r"\.(agpr_count|vgpr_count|sgpr_count|private_segment_fixed_size|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)"
 
 
 @pytest.fixture(scope="module")
-def cov_kernels(tmp_path_factory):
-    d = tmp_path_factory.mktemp("co_cov")
-    found = {}
-    objs = device_code_objects(LIB)
-    assert objs, "no AMDGPU code object found in %s (a compressed fat binary?)" % LIB
-    for i, img in enumerate(objs):
-        p = d / ("co%d.elf" % i)
-        p.write_bytes(img)
-        notes = subprocess.run([READELF, "--notes", str(p)], capture_output=True, text=True, check=True).stdout
-        for block in re.split(r"\n\s*- (?=\.agpr_count:)", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            if m and m.group(1) in KERNELS:
-                found[KERNELS[m.group(1)]] = {k: int(v) for k, v in re.findall(FIELDS, block)}
-    return found
+def cov_kernels():
+    return {KERNELS[name]: k for name, k in by_name(KERNELS).items()}
 
 
 def test_both_builds_exist(cov_kernels):
