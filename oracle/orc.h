@@ -52,6 +52,15 @@
  *   D5. EPnP's 12x12 Jacobi SVD sweeps its row pairs in round-robin (Brent-Luk) order instead of OpenCV's
  *       cyclic-by-rows order: same algorithm and convergence test, different (equally valid) pair schedule,
  *       chosen because the n/2 pairs of a round are independent and the GPU rotates them in parallel.
+ *   D6. PARITY UNPINNED.  A solve whose R or t holds a non-finite value is a failed solve: cameraToWorld returns success = 0,
+ *       leaves R and t untouched and reports no inliers (fail_reason 3 in the frame pipeline) — the direct 5-point EPnP, the
+ *       direct P3P and the refined pose of the RANSAC path alike.  Without it five exactly coplanar points come back as
+ *       "success, 5 inliers, R = t = NaN": the fourth control point coincides with the centroid, every alpha_3 is 0, L keeps one
+ *       non-zero column, approximation 1 solves b4 = 0 and forms betas[1] = b4[1] / sqrt(b4[0]) = 0 / 0
+ *       (find_betas_approx_1; approximation 3 the same with b5[3] / sqrt(b5[0]); approximation 2 gives R = 0 and a NaN
+ *       reprojection error), and no NaN error is "smaller" than another, so N stays 1.  A NaN pose passes the motion gate
+ *       (tn > max || angle > max is false for NaN) and would be multiplied into the caller's trajectory.  What OpenCV returns
+ *       for this input cannot be pinned here (no OpenCV); the same expressions stand in its epnp.cpp.  No finite result changes.
  */
 #ifndef ORC_H
 #define ORC_H

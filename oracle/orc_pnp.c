@@ -2,7 +2,7 @@
  * Stands in for cv::triangulatePoints + cv::convertPointsFromHomogeneous (/root/reference/src/vo.cpp:89-94),
  * cv::solvePnPRansac + cv::Rodrigues (vo.cpp:282-313) and the 4x4 inverse of vo.cpp:246-258, restating
  * OpenCV 4.5 modules/calib3d/src/{triangulate,solvepnp,ptsetreg,epnp,calibration}.cpp and
- * modules/core/src/rand.cpp as summarised in SURVEY.md Appendix A.4-A.7.  Deviations D2, D4, D5: orc.h. */
+ * modules/core/src/rand.cpp as summarised in SURVEY.md Appendix A.4-A.7.  Deviations D2, D4, D5, D6: orc.h. */
 #include "orc.h"
 #include "orc_linalg.h"
 #include <float.h>
@@ -450,6 +450,14 @@ int orc_pnp_refine_lm(int n, const double* obj, const double* img, double fx, do
 }
 
 /* ------------------------------------------------------------------ solvePnPRansac as used by cameraToWorld (vo.cpp:282-313) */
+/* D6 (orc.h): a solve whose R or t holds a non-finite value is a failed solve */
+static int pose_is_finite(const double R[9], const double t[3]) {
+    int i;
+    for (i = 0; i < 9; i++) if (!isfinite(R[i])) return 0;
+    for (i = 0; i < 3; i++) if (!isfinite(t[i])) return 0;
+    return 1;
+}
+
 static void epnp_on_subset(const float K[9], const float* world, const float* cam, const int idx[5], int m,
                            double R[9], double t[3]) {
     double fx = K[0], fy = K[4], cx = K[2], cy = K[5], obj[15], img[10];
@@ -517,7 +525,9 @@ int orc_camera_to_world(const float K[9], int n, const float* cam_pts, const flo
         }
         if (!ok) return 0;
         orc_rodrigues_to_vector(bestR, rvec);
-        orc_rodrigues_to_matrix(rvec, R, NULL);           /* vo.cpp:308 */
+        orc_rodrigues_to_matrix(rvec, lastR, NULL);       /* vo.cpp:308 */
+        if (!pose_is_finite(lastR, bestT)) return 0;      /* D6: R, t untouched, no inliers */
+        memcpy(R, lastR, sizeof(double) * 9);
         memcpy(t, bestT, sizeof(double) * 3);
         for (i = 0; i < n; i++) inliers[i] = i;
         *n_inliers = n;
@@ -578,10 +588,12 @@ int orc_camera_to_world(const float K[9], int n, const float* cam_pts, const flo
         }
         orc_rodrigues_to_vector(bestR, rvec);
         orc_pnp_refine_lm(m, obj, img, fx, fy, cx, cy, rvec, bestT);
-        orc_rodrigues_to_matrix(rvec, R, NULL);           /* vo.cpp:308 */
+        orc_rodrigues_to_matrix(rvec, lastR, NULL);       /* vo.cpp:308 */
+        free(obj); free(img);
+        if (!pose_is_finite(lastR, bestT)) { free(mask); free(best_mask); return 0; }   /* D6: R, t untouched, no inliers */
+        memcpy(R, lastR, sizeof(double) * 9);
         memcpy(t, bestT, sizeof(double) * 3);
         *n_inliers = m;
-        free(obj); free(img);
     }
     free(mask); free(best_mask);
     return 1;

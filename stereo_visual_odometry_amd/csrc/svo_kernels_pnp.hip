@@ -920,12 +920,26 @@ static __device__ __forceinline__ void pnp_final_body(const DevBuffers& d) {
     for (int k = 1; k < 64; k <<= 1) { int t = __shfl_up(incl, k); if (lane >= k) incl += t; }
     if (lane == 63) sh.wave_tot[wv] = incl;
     __syncthreads();
-    if (threadIdx.x == 0) { int acc = 0; for (int i = 0; i < (THREADS / 64); i++) { int t = sh.wave_tot[i]; sh.wave_tot[i] = acc; acc += t; } sh.total = acc; }
+    if (threadIdx.x == 0) {
+        int acc = 0; for (int i = 0; i < (THREADS / 64); i++) { int t = sh.wave_tot[i]; sh.wave_tot[i] = acc; acc += t; } sh.total = acc;
+        // rotation = Rodrigues(rvec), translation = tvec (vo.cpp:307-308).  A pose with a non-finite entry is a failed solve
+        // (deviation D6, orc.h): x - x is 0 for every finite x and NaN otherwise
+        rodrigues_to_matrix(sh.param, sh.R, nullptr);
+        double nf = 0;
+        for (int a = 0; a < 9; a++) nf += sh.R[a] - sh.R[a];
+        for (int a = 3; a < 6; a++) nf += sh.param[a] - sh.param[a];
+        if (!(nf == 0)) sh.total = -1;
+    }
     __syncthreads();
     const int n_inl = sh.total;
+    if (n_inl < 0) {                                                                             // D6: R, t untouched, no inliers
+        for (int i = threadIdx.x; i < n; i += THREADS) d.inlier[o + i] = 0;
+        if (threadIdx.x == 0) { s.pnp_best = -1; s.n_inliers = 0; s.fail_reason = 3; }
+        return;
+    }
     if (threadIdx.x == 0) {
-        // success: rotation = Rodrigues(rvec), translation = tvec (vo.cpp:307-308) — before the inlier-count gate
-        rodrigues_to_matrix(sh.param, s.R, nullptr);
+        // success — before the inlier-count gate
+        for (int a = 0; a < 9; a++) s.R[a] = sh.R[a];
         s.t[0] = sh.param[3]; s.t[1] = sh.param[4]; s.t[2] = sh.param[5];
         s.n_inliers = n_inl;
     }
@@ -1180,9 +1194,13 @@ __global__ void k_pnp_p3p(DevBuffers d) {
     }
     s.pnp_iters = 0;
     if (nb == 0) { s.pnp_best = -1; s.fail_reason = 3; return; }           // solvePnP returned false
-    double rv[3];
+    double rv[3], Rn[9], nf = 0;
     rodrigues_to_vector(bestR, rv);                                         // rvec out of solvePnP ...
-    rodrigues_to_matrix(rv, s.R, nullptr);                                  // ... and back to a matrix (vo.cpp:308)
+    rodrigues_to_matrix(rv, Rn, nullptr);                                   // ... and back to a matrix (vo.cpp:308)
+    for (int a = 0; a < 9; a++) nf += Rn[a] - Rn[a];
+    for (int a = 0; a < 3; a++) nf += bestT[a] - bestT[a];
+    if (!(nf == 0)) { s.pnp_best = -1; s.n_inliers = 0; s.fail_reason = 3; return; }   // a non-finite pose is a failed solve (D6, orc.h)
+    for (int a = 0; a < 9; a++) s.R[a] = Rn[a];
     s.t[0] = bestT[0]; s.t[1] = bestT[1]; s.t[2] = bestT[2];
     s.pnp_best = 0; s.pnp_good = 4; s.n_inliers = 4;
     for (int i = 0; i < 4; i++) { d.inlier[o + i] = 1; d.inl_idx[o + i] = i; }

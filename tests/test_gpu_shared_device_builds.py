@@ -343,8 +343,11 @@ FORCED_SELECTION = [
     ("tests/test_gpu_sequence_lifecycle.py", "idle_invariance or idle_rows or reset or all_idle or null_mask or masked_other"),
     # the stage entry on degenerate disparities through k_triangulate_lean; the tests themselves assert SVO_PATH_LEAN of every call
     ("tests/test_gpu_triangulate_edges.py", "test_stage"),
+    # the pose stage at count, chunk and geometry edges through k_pnp_epnp_lean (8 lanes per hypothesis) and k_pnp_final_lean
+    # (256 threads, two virtual threads each); every call asserts SVO_PATH_LEAN there too
+    ("tests/test_gpu_pnp_edges.py", "test_stage"),
 ]
-FORCED_MIN_PASSES = [30, 10, 8]
+FORCED_MIN_PASSES = [30, 10, 8, 139]
 
 
 def forced_env():
@@ -354,7 +357,7 @@ def forced_env():
     return env
 
 
-@pytest.mark.parametrize("which", [0, 1, 2], ids=["parity", "lifecycle", "triangulate"])
+@pytest.mark.parametrize("which", [0, 1, 2, 3], ids=["parity", "lifecycle", "triangulate", "pnp_edges"])
 def test_forced_lean_parity_selection(which):
     path, expr = FORCED_SELECTION[which]
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-p", "no:cacheprovider", path, "-k", expr],
