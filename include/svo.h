@@ -416,6 +416,19 @@ int svo_get_detection_mask(svo_context* ctx, int seq, uint8_t* out /* W*H, packe
 #define SVO_PYR_LAST_LEFT 1   /* lastLeftPyramid's slot (vo.cpp:50-53, 179-181, 231-232): may be older than T1 */
 int svo_get_pyramid(svo_context* ctx, int seq, int which, int cam, int plane, int level,
                     uint8_t* out, int64_t cap, int* w, int* h, int* pad, int* n_levels);
+/* Diagnostics (derivative-plane tests): the Scharr planes the LK kernel loads at the levels >= 1 (many-sequence grey contexts in
+ * the exact-sums mode keep them beside every pyramid), one level of one stored pyramid, WITH the stored border.  ix / iy each get
+ * (h + 2 pad) rows of (w + 2 pad) int16 samples, packed, from sample (-pad, -pad): inside the level 4 x the Scharr derivative of
+ * the level with its REFLECT_101 border, outside it zero (derivBorder = BORDER_CONSTANT).  cap is the size of each array in
+ * samples; either may be NULL.  which, cam, the slot read, the SVO_ERR_STATE refusals (frames in flight, no frame since creation or
+ * reset, no cached lastLeftPyramid) and the synchronisation are svo_get_pyramid's.  level: 1 .. n_levels-1 (level 0 has no planes:
+ * SVO_ERR_ARG).  pad and n_levels are filled once seq, which and cam are valid, w and h once level is; ix == iy == NULL returns
+ * SVO_OK after filling them.  A context that keeps no planes (<= 8 sequences, channels = 3, lk_float_sums = 1, a one-level
+ * pyramid, SVO_LK_DERIV=0 or SVO_INGEST_AHEAD=0 in the environment) returns SVO_ERR_STATE, with a message that says so, whatever
+ * level and the arrays are: that is how a caller asks whether the planes exist.  A pure read: it changes no launch. */
+int svo_get_derivatives(svo_context* ctx, int seq, int which, int cam, int level,
+                        int16_t* ix, int16_t* iy, int64_t cap /* samples per array */,
+                        int* w, int* h, int* pad, int* n_levels);
 /* Timing: HIP-event milliseconds of the dominant kernel (the fused LK chain) in the last processed frame, and of the whole frame.
  * With SVO_GRAPH=1 in the environment a context replays each frame as a captured hipGraph (one per results-ring slot; off by
  * default: measured slightly slower than the launch list on MI355X): stage events are then not recorded and lk_ms /

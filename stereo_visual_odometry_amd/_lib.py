@@ -143,12 +143,16 @@ lib.svo_get_pyramid.restype = C.c_int
 lib.svo_get_pyramid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                 C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
 PYR_T1, PYR_LAST_LEFT = 0, 1
+# derivative-plane read-out (svo.h svo_get_derivatives): the int16 Ix / Iy planes of one level >= 1 with their zero border
+lib.svo_get_derivatives.restype = C.c_int
+lib.svo_get_derivatives.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
 
 # every symbol include/svo.h declares (tests/test_abi.py checks the list against the header)
 EXPORTS = [
     "svo_last_error", "svo_device_count", "svo_config_default", "svo_create", "svo_destroy", "svo_set_projection",
     "svo_process_batch", "svo_process_batch_masked", "svo_submit_batch_masked", "svo_reset_sequence", "svo_process", "svo_alloc_pinned", "svo_free_pinned", "svo_circular_matching", "svo_submit_batch", "svo_collect", "svo_get_features", "svo_get_last_tracks",
-    "svo_get_pyramid",
+    "svo_get_pyramid", "svo_get_derivatives",
     "svo_get_lk_registers_left", "svo_get_last_frame_path", "svo_get_last_timing", "svo_set_stage_timing", "svo_get_stage_timing", "svo_get_stream", "svo_fast_detect", "svo_fast_score_map", "svo_bucket_filter",
     "svo_append_features_from_image", "svo_build_pyramid", "svo_lk_track", "svo_circular_match",
     "svo_find_close_points", "svo_stage_cache_clear", "svo_stage_cache_clear_all", "svo_triangulate", "svo_camera_to_world", "svo_inverse_transform",

@@ -656,6 +656,21 @@ class BatchVisualOdometry:
         check(lib.svo_get_pyramid(self._h, seq, wh, cam, plane, level, ptr(out), out.size, None, None, None, None))
         return out, pad.value
 
+    def derivatives(self, seq, which="t1", cam=0, level=1):
+        """The Scharr planes the LK kernel loads at pyramid level `level` >= 1 of sequence `seq`, WITH their zero border
+        (svo_get_derivatives) -> (ix, iy, pad): int16 (h + 2 pad, w + 2 pad) arrays whose [pad:-pad, pad:-pad] is 4 x the Scharr
+        derivative of the level.  which, cam: as pyramid().  SvoError in a context that keeps no planes (has_derivatives())."""
+        wh = self.PYRAMIDS[which]
+        w, h, pad = C.c_int(), C.c_int(), C.c_int()
+        check(lib.svo_get_derivatives(self._h, seq, wh, cam, level, None, None, 0, C.byref(w), C.byref(h), C.byref(pad), None))
+        ix = np.zeros((h.value + 2 * pad.value, w.value + 2 * pad.value), np.int16); iy = np.zeros_like(ix)
+        check(lib.svo_get_derivatives(self._h, seq, wh, cam, level, ptr(ix), ptr(iy), ix.size, None, None, None, None))
+        return ix, iy, pad.value
+
+    def has_derivatives(self):
+        """Whether the context keeps derivative planes beside its pyramids (many sequences, grey, exact sums, >= 2 levels)."""
+        return lib.svo_get_derivatives(self._h, 0, _lib.PYR_T1, 0, 1, None, None, 0, None, None, None, None) == _lib.SVO_OK
+
     def pyramid_levels(self):
         """Number of levels the context builds (the buildOpticalFlowPyramid stop rule at its window and max_level)."""
         nl = C.c_int()

@@ -1039,6 +1039,16 @@ extern "C" int svo_get_last_tracks(svo_context* c, int seq, int cap, float* pl0,
     return hs.n_tracks;
 }
 
+// the slot a diagnostic read-out (svo_get_pyramid, svo_get_derivatives) reads, and its refusals; synchronises the context's stream
+static int readable_slot(svo_context* c, int seq, int which, int* slot) {
+    if (c->inflight > 0) { g_err = "pyramid read-out with frames in flight (collect first)"; return SVO_ERR_STATE; }
+    SeqState hs; int rc = read_state(c, seq, &hs); if (rc != SVO_OK) return rc;
+    if (hs.frame_id == 0) { g_err = "the sequence has no frame since its creation or its last reset"; return SVO_ERR_STATE; }
+    *slot = which == SVO_PYR_T1 ? hs.slot_t1 : hs.slot_pyr_t0;
+    if (*slot < 0 || *slot >= SVO_PYR_SLOTS) { g_err = "no cached lastLeftPyramid yet"; return SVO_ERR_STATE; }
+    return SVO_OK;
+}
+
 extern "C" int svo_get_pyramid(svo_context* c, int seq, int which, int cam, int plane, int level,
                                uint8_t* out, int64_t cap, int* w, int* h, int* pad, int* n_levels) {
     if (!c || seq < 0 || seq >= c->d.B) return fail_arg("bad context / seq");
@@ -1054,13 +1064,33 @@ extern "C" int svo_get_pyramid(svo_context* c, int seq, int which, int cam, int 
     if (!out) return SVO_OK;
     const size_t pw = (size_t)L.w + 2 * g.pad, ph = (size_t)L.h + 2 * g.pad;
     if (cap < (int64_t)(pw * ph)) return fail_arg("out too small: (h + 2 pad) * (w + 2 pad) bytes needed");
-    if (c->inflight > 0) { g_err = "svo_get_pyramid with frames in flight (collect first)"; return SVO_ERR_STATE; }
-    SeqState hs; int rc = read_state(c, seq, &hs); if (rc != SVO_OK) return rc;
-    if (hs.frame_id == 0) { g_err = "the sequence has no frame since its creation or its last reset"; return SVO_ERR_STATE; }
-    const int slot = which == SVO_PYR_T1 ? hs.slot_t1 : hs.slot_pyr_t0;
-    if (slot < 0 || slot >= SVO_PYR_SLOTS) { g_err = "no cached lastLeftPyramid yet"; return SVO_ERR_STATE; }
+    int slot; const int rc = readable_slot(c, seq, which, &slot); if (rc != SVO_OK) return rc;
     const uint8_t* src = c->d.pyr + pyr_index(c->d, seq, slot, cam) + (size_t)plane * g.pyr_bytes + L.off - (size_t)g.pad * L.stride - g.pad;
     HIPCHK(hipMemcpy2D(out, pw, src, (size_t)L.stride, pw, ph, hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+
+extern "C" int svo_get_derivatives(svo_context* c, int seq, int which, int cam, int level,
+                                   int16_t* ix, int16_t* iy, int64_t cap, int* w, int* h, int* pad, int* n_levels) {
+    if (!c || seq < 0 || seq >= c->d.B) return fail_arg("bad context / seq");
+    if (which != SVO_PYR_T1 && which != SVO_PYR_LAST_LEFT) return fail_arg("which must be SVO_PYR_T1 or SVO_PYR_LAST_LEFT");
+    if (cam < 0 || cam > 1) return fail_arg("bad camera");
+    const Geometry& g = c->d.geom;
+    if (pad) *pad = g.pad;
+    if (n_levels) *n_levels = g.nlevels;
+    if (!c->d.deriv || g.nlevels < 2) { g_err = "no planes: this context keeps no derivative pyramid (its LK kernel differentiates every window itself)"; return SVO_ERR_STATE; }
+    if (level < 1 || level >= g.nlevels) return fail_arg("level out of range: the planes cover the levels 1 .. n_levels - 1");
+    const LevelInfo& L = g.lv[level];
+    if (w) *w = L.w;
+    if (h) *h = L.h;
+    if (!ix && !iy) return SVO_OK;
+    const size_t pw = (size_t)L.w + 2 * g.pad, ph = (size_t)L.h + 2 * g.pad;
+    if (cap < (int64_t)(pw * ph)) return fail_arg("arrays too small: (h + 2 pad) * (w + 2 pad) samples each needed");
+    int slot; const int rc = readable_slot(c, seq, which, &slot); if (rc != SVO_OK) return rc;
+    // sample (-pad, -pad) of the level: the planes are laid out like the image pyramid behind level 0 (svo_internal.hpp)
+    const int16_t* src = c->d.deriv + deriv_index(c->d, seq, slot, cam) + (L.off - deriv_origin(g)) - (ptrdiff_t)g.pad * L.stride - g.pad;
+    if (ix) HIPCHK(hipMemcpy2D(ix, pw * sizeof(int16_t), src, (size_t)L.stride * sizeof(int16_t), pw * sizeof(int16_t), ph, hipMemcpyDeviceToHost));
+    if (iy) HIPCHK(hipMemcpy2D(iy, pw * sizeof(int16_t), src + deriv_samples(g), (size_t)L.stride * sizeof(int16_t), pw * sizeof(int16_t), ph, hipMemcpyDeviceToHost));
     return SVO_OK;
 }
 
