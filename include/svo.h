@@ -166,6 +166,7 @@ int svo_get_lk_registers_left(svo_context* ctx);
 #define SVO_PATH_POSE_COV       128  /* the frame ran k_pose_cov after its refine (svo_set_pose_covariance; also set by svo_pose_covariance) */
 #define SVO_PATH_CLAHE          512  /* the frame's images were equalised (two launches) in front of its ingest (svo_set_clahe; also set by svo_clahe) */
 #define SVO_PATH_DETECT_MASKED  256  /* the frame's detection applied a detection mask (svo_set_detection_mask; also set by svo_append_features_from_image_masked) */
+#define SVO_PATH_TRACK_IDS    1024   /* the frame carried track ids and wrote its observation rows (svo_set_track_output) */
 int svo_get_last_frame_path(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
@@ -366,6 +367,59 @@ int svo_get_last_pose_covariance(svo_context* ctx, double* cov_T, double* cov_p,
 int svo_get_features(svo_context* ctx, int seq, int cap, float* xy, int* ages, int* strengths);
 int svo_get_last_tracks(svo_context* ctx, int seq, int cap, float* pl0, float* pr0, float* pl1, float* pr1,
                         float* world, uint8_t* inlier);
+/* ---- Track ids and per-frame stereo observations ---------------------------------------------------------------------------
+ * What a landmark back end consumes (a sliding-window bundle adjuster, a smart-factor graph, an MSCKF): per frame, a list of
+ * (landmark id, stereo observation).  Off by default; off, a context launches exactly what a context that never called the
+ * setter launches.  On, every feature carries a 64-bit id through the frame and the frame's tracks are written, as rows of
+ * svo_track_obs, into a pinned ring beside the pose: no extra copy, no extra synchronisation, valid with frames in flight.
+ * Nothing a frame already returned (pose, stats, svo_get_features, svo_get_last_tracks) changes by a bit.
+ *
+ * The identity rule.  Per (context, sequence) there is a counter next_id (int64): 0 at creation and after svo_reset_sequence
+ * (stream-ordered like the rest of the reset).
+ *  1. Detection pass (each of the two, feature_set.cpp:75-89).  The pass publishes a feature set of n_out entries in bucket-raster
+ *     order.  An entry that came from the existing list (rank < n_old in the pass's input list — a track that ties with a fresh
+ *     FAST hit at the same pixel wins as first-come) keeps its id.  A fresh FAST hit at output position p gets next_id + p.  After
+ *     the pass next_id += n_out.  Ids are unique and increasing, not dense.  The second pass applies the same rule to the first
+ *     pass's output: a first-pass newcomer displaced in the second pass burns its id.
+ *  2. Circular + bounds compaction (stable).  The id of feature i goes to track and feature position pos, with the age.  Features
+ *     beyond max_features drop out with their ids.
+ *  3. Inlier compaction (only on the path that replaces the feature set by the inliers: fail_reason 0 or 4).  New feature pos takes
+ *     the id of the track it was (the pos-th inlier).  On fail_reason 2 and 3 the feature set, and so its ids, is step 2's output.
+ *  4. Observation row i of a frame is track i of svo_get_last_tracks (RANSAC's row order): its id, the four points, world[i],
+ *     inlier[i], and the age step 2 wrote (the feature's age after this frame's increment, vo.cpp:70-72).  On fail_reason 2 the
+ *     frame did not triangulate: xyz is 0 0 0 and SVO_OBS_HAS_XYZ is clear.  SVO_OBS_INLIER is set only where the frame built
+ *     its inlier vector (fail_reason 0 or 4).
+ * A row whose id appeared in no earlier frame is a first sighting; l0 of a row whose id was in the previous frame's feature set is
+ * that feature's position, bit for bit. */
+typedef struct {            /* 64 bytes */
+    int64_t id;             /* persistent within (context, sequence) since creation / the last svo_reset_sequence */
+    float l0[2], r0[2];     /* the track at T0: left, right */
+    float l1[2], r1[2];     /* the track at T1: left, right — this frame's stereo observation */
+    float xyz[3];           /* world[i] of svo_get_last_tracks: triangulated from (l0, r0), in the T0 left camera frame; 0 0 0 when SVO_OBS_HAS_XYZ is clear */
+    int32_t age;            /* the feature's age after this frame's increment */
+    int32_t flags;          /* SVO_OBS_* */
+    int32_t pad;
+} svo_track_obs;
+#define SVO_OBS_INLIER  1   /* inlier[i] of svo_get_last_tracks */
+#define SVO_OBS_HAS_XYZ 2   /* the frame triangulated (fail_reason 0, 3 or 4) */
+/* on != 0: switch the output on with room for max_rows rows per sequence and frame (1 .. the context's feature capacity: rows of
+ * the default grid x columns, 14 080); the pinned ring [8][n_seq][max_rows] rows plus a {n_tracks, n_rows} header per (slot,
+ * sequence) is allocated at first use and freed with the context.  The features a sequence holds at that moment get the ids
+ * next_id + index and next_id advances by their count (stream-ordered).  on == 0: off again (max_rows is not looked at).
+ * A setup action: SVO_ERR_STATE with frames in flight.  SVO_ERR_ARG: features_per_bucket > 1 (the general bucket walk carries no
+ * ids), a bad max_rows.  While on, svo_get_last_frame_path reports SVO_PATH_TRACK_IDS, a lone stream issues the unfused front (as
+ * a masked frame does), frames run from the launch list under SVO_GRAPH=1, and svo_circular_matching — which overwrites the
+ * feature set behind the ids' back — returns SVO_ERR_STATE. */
+int svo_set_track_output(svo_context* ctx, int on, int max_rows);
+/* The rows of sequence seq in the last COLLECTED frame (svo_collect, svo_process*), from host memory: no device access, no
+ * synchronisation.  *n_tracks (may be NULL) = the frame's full track count; returns min(n_tracks, max_rows, cap) = the rows
+ * written, the first ones in track order.  An idle sequence, a first frame and an all-idle frame have n_tracks = 0.
+ * SVO_ERR_STATE if that frame was issued with the output off or none was collected yet. */
+int svo_get_last_track_obs(svo_context* ctx, int seq, int cap, svo_track_obs* rows, int* n_tracks);
+/* Introspection: the ids of svo_get_features' entries, in its order; returns the count.  Synchronises like svo_get_features.
+ * SVO_ERR_STATE with the output off. */
+int svo_get_feature_ids(svo_context* ctx, int seq, int cap, int64_t* ids);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the

@@ -212,6 +212,7 @@ class VisualOdometry {                                               // include/
             if (in_format_ != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx_, in_format_));
             if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
             if (clahe_on_) svo_throw(svo_set_clahe(ctx_, 1, clahe_clip_, clahe_tx_, clahe_ty_));
+            if (track_rows_ > 0) svo_throw(svo_set_track_output(ctx_, 1, track_rows_));
             if (!mask_.empty()) {
                 if ((int)mask_.size() != width_ * height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
                 svo_throw(svo_set_detection_mask(ctx_, -1, mask_.data(), width_, 0));
@@ -364,6 +365,32 @@ class VisualOdometry {                                               // include/
         return c;
     }
 
+    // Persistent feature ids and per-frame stereo observations for a landmark back end (svo_set_track_output): from the next frame
+    // on every stereo_callback leaves up to max_rows rows of svo_track_obs — (id, the track's four points, its triangulated point,
+    // age, flags), svo.h states the identity rule — read with last_track_observations().  Before the first frame the setting is
+    // kept and applied when the context is created; max_rows < 1 throws at once.
+    void set_track_output(int max_rows) {
+        if (ctx_) svo_throw(svo_set_track_output(ctx_, 1, max_rows));
+        else if (max_rows < 1) throw std::runtime_error("set_track_output: max_rows must be >= 1");
+        track_rows_ = max_rows;
+    }
+    void clear_track_output() {
+        track_rows_ = 0;
+        if (ctx_) svo_throw(svo_set_track_output(ctx_, 0, 0));
+    }
+    // The rows of the last stereo_callback, the first min(tracks, max_rows) in svo_get_last_tracks' order; host memory only.
+    // Throws when that frame ran with the output off.
+    std::vector<svo_track_obs> last_track_observations() const {
+        if (!ctx_) throw std::runtime_error("last_track_observations: no frame yet (call stereo_callback first)");
+        int n_tracks = 0;
+        svo_throw(svo_get_last_track_obs(ctx_, 0, 0, nullptr, &n_tracks));
+        std::vector<svo_track_obs> rows((size_t)(n_tracks > 0 ? n_tracks : 0));
+        const int n = svo_get_last_track_obs(ctx_, 0, (int)rows.size(), rows.data(), nullptr);
+        svo_throw(n);
+        rows.resize((size_t)n);
+        return rows;
+    }
+
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
 
@@ -395,6 +422,7 @@ class VisualOdometry {                                               // include/
     int in_format_ = SVO_INPUT_MONO8;                                 // set_input_encoding (applied once the context exists)
     int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
     std::vector<uint8_t> mask_;                                       // set_detection_mask before the first frame: installed at creation
+    int track_rows_ = 0;                                              // set_track_output (likewise); 0: off
     bool clahe_on_ = false; double clahe_clip_ = 2.0; int clahe_tx_ = 8, clahe_ty_ = 8;   // set_clahe (applied once the context exists)
 };
 

@@ -85,6 +85,26 @@ PATH_INPUT_CONVERTED = 64
 PATH_POSE_COV = 128
 PATH_DETECT_MASKED = 256
 PATH_CLAHE = 512
+PATH_TRACK_IDS = 1024
+# track ids and observation rows (svo.h svo_track_obs): the 64-byte row as a ctypes structure and as a numpy structured dtype
+OBS_INLIER, OBS_HAS_XYZ = 1, 2
+
+
+class SvoTrackObs(C.Structure):
+    _fields_ = [("id", C.c_int64), ("l0", C.c_float * 2), ("r0", C.c_float * 2), ("l1", C.c_float * 2), ("r1", C.c_float * 2),
+                ("xyz", C.c_float * 3), ("age", C.c_int32), ("flags", C.c_int32), ("pad", C.c_int32)]
+
+
+TRACK_OBS_DTYPE = np.dtype([("id", "<i8"), ("l0", "<f4", 2), ("r0", "<f4", 2), ("l1", "<f4", 2), ("r1", "<f4", 2),
+                            ("xyz", "<f4", 3), ("age", "<i4"), ("flags", "<i4"), ("pad", "<i4")])
+assert TRACK_OBS_DTYPE.itemsize == 64 and C.sizeof(SvoTrackObs) == 64
+if hasattr(lib, "svo_set_track_output"):
+    lib.svo_set_track_output.restype = C.c_int
+    lib.svo_set_track_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.svo_get_last_track_obs.restype = C.c_int
+    lib.svo_get_last_track_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    lib.svo_get_feature_ids.restype = C.c_int
+    lib.svo_get_feature_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
 # CLAHE (svo.h): the equalisation in front of frame ingest, and the stage alone
 lib.svo_set_clahe.restype = C.c_int
 lib.svo_set_clahe.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]
@@ -161,6 +181,7 @@ EXPORTS = [
     "svo_set_pose_covariance", "svo_get_last_pose_covariance", "svo_pose_covariance",
     "svo_set_detection_mask", "svo_get_detection_mask", "svo_fast_detect_masked", "svo_append_features_from_image_masked",
     "svo_set_clahe", "svo_clahe",
+    "svo_set_track_output", "svo_get_last_track_obs", "svo_get_feature_ids",
 ]
 
 

@@ -455,6 +455,36 @@ class BatchVisualOdometry:
         check(lib.svo_get_last_pose_covariance(self._h, ptr(cov_T), ptr(cov_p), ptr(valid)))
         return cov_T.reshape(-1, 6, 6), cov_p.reshape(-1, 6, 6), valid.astype(bool)
 
+    def set_track_output(self, max_rows):
+        """Persistent feature ids and per-frame stereo observations from the next frame submitted on (svo_set_track_output):
+        every frame then leaves up to max_rows rows (id, the track's four points, its triangulated point, age, flags) per
+        sequence in a pinned ring beside the pose; read them with last_track_obs().  The features held now get fresh ids.
+        A setup action: SvoError with frames in flight, with features_per_bucket > 1, or for a bad max_rows."""
+        check(lib.svo_set_track_output(self._h, 1, int(max_rows)))
+
+    def clear_track_output(self):
+        """Frames submitted from now on carry no ids: the context launches what it launched before set_track_output."""
+        check(lib.svo_set_track_output(self._h, 0, 0))
+
+    def last_track_obs(self, seq=0, with_count=False):
+        """The observation rows of sequence `seq` in the last collected frame -> a numpy structured array (_lib.TRACK_OBS_DTYPE:
+        id, l0, r0, l1, r1, xyz, age, flags, pad), the first min(n_tracks, max_rows) tracks in svo_get_last_tracks' order.
+        with_count: -> (rows, n_tracks), the frame's full track count.  Host memory only, no synchronisation
+        (svo_get_last_track_obs).  SvoError when that frame was issued with the output off."""
+        n_tracks = C.c_int(0)
+        n = check(lib.svo_get_last_track_obs(self._h, seq, 0, None, C.byref(n_tracks)))
+        rows = np.zeros(max(n_tracks.value, 1), _lib.TRACK_OBS_DTYPE)
+        n = check(lib.svo_get_last_track_obs(self._h, seq, len(rows), ptr(rows), None))
+        rows = rows[:n].copy()
+        return (rows, n_tracks.value) if with_count else rows
+
+    def feature_ids(self, seq=0):
+        """The ids of features(seq)'s entries, in its order (svo_get_feature_ids; synchronises).  SvoError with the output off."""
+        cap = 1 << 15
+        ids = np.zeros(cap, np.int64)
+        n = check(lib.svo_get_feature_ids(self._h, seq, cap, ptr(ids)))
+        return ids[:n].copy()
+
     def set_detection_mask(self, mask, seq=-1):
         """Keep features off the zero pixels of `mask` (svo_set_detection_mask): an (height, width) uint8 numpy array, or a torch
         device tensor of that shape and dtype, read through data_ptr() with its own row stride (its producer must have finished,
@@ -693,6 +723,7 @@ class VisualOdometry(BatchVisualOdometry):
         self._cov = None                              # likewise a pose-covariance mode
         self._mask = None                             # likewise a detection mask
         self._clahe = None                            # likewise a CLAHE setting (clip_limit, tiles_x, tiles_y)
+        self._track_rows = None                       # likewise the track output's max_rows
         self.raw_size = None
         if not self._created:
             self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
@@ -743,6 +774,28 @@ class VisualOdometry(BatchVisualOdometry):
         self._clahe = None
         if self._created:
             super().clear_clahe()
+
+    def set_track_output(self, max_rows):
+        if self._created:
+            return super().set_track_output(max_rows)
+        if int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        self._track_rows = int(max_rows)
+
+    def clear_track_output(self):
+        self._track_rows = None
+        if self._created:
+            super().clear_track_output()
+
+    def last_track_obs(self, seq=0, with_count=False):
+        if not self._created:
+            raise _lib.SvoError("last_track_obs: no frame yet (call stereo_callback first)")
+        return super().last_track_obs(seq, with_count)
+
+    def feature_ids(self, seq=0):
+        if not self._created:
+            raise _lib.SvoError("feature_ids: no frame yet (call stereo_callback first)")
+        return super().feature_ids(seq)
 
     def set_detection_mask(self, mask, seq=-1):
         if self._created:
@@ -799,6 +852,8 @@ class VisualOdometry(BatchVisualOdometry):
                 super().set_detection_mask(self._mask)
             if self._clahe is not None:
                 super().set_clahe(self._clahe[0], self._clahe[1:])
+            if self._track_rows is not None:
+                super().set_track_output(self._track_rows)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

@@ -98,6 +98,7 @@ struct RingSlot {
     bool staged = false;                         // the slot's stage events were recorded (launch-list mode only)
     int cov_mode = SVO_COV_OFF;                  // the pose-covariance mode the slot's frame was issued with
     bool masked = false;                         // ... and whether it came with a mask (h_act's row then holds its flags)
+    bool tracks = false;                         // ... and whether it carried track ids and wrote its observation rows
 };
 // Detection masks (svo_set_detection_mask): the two slots of one scope (a sequence, or the shared pair).  cur: the slot in force for
 // the frames submitted from now on (-1: none); last: the slot the most recent frame of this scope recorded for its left image — that
@@ -186,6 +187,24 @@ struct svo_context {
     int clahe_w = 0, clahe_h = 0;                // the frame size clahe_buf was allocated for
     uint8_t* clahe_lut = nullptr;
     int clahe_lut_tiles = 0;                     // tiles per image clahe_lut has room for
+    // track ids and observation rows (svo_set_track_output).  Everything below is empty until the output is first switched on.
+    // Host state like the covariance mode: a frame carries whether it was issued with the output on (RingSlot::tracks); switching
+    // is refused with frames in flight.  The id buffers are device memory of the context (freed with its other allocations); the
+    // ring is pinned host memory the device writes in place (k_track_obs), re-allocated when max_rows changes.
+    bool track_on = false;
+    int track_rows = 0;                          // max_rows of the ring as allocated
+    IdArgs ids = {};
+    svo_track_obs* h_obs = nullptr;              // pinned, mapped [SVO_RING][B][track_rows] ...
+    svo_track_obs* d_obs = nullptr;              // ... and its device address
+    int* h_obs_hdr = nullptr;                    // pinned, mapped [SVO_RING][B] {n_tracks, n_rows}
+    int* d_obs_hdr = nullptr;
+    // the last collected frame's rows: its slot of the ring, read in place — or, once a later submit is about to reuse that slot
+    // (eight frames in flight), the copy enqueue_frame made of it first
+    bool last_tracks_on = false;                 // that frame was issued with the output on
+    int last_obs_slot = -1;                      // its slot while the ring still holds it, else -1: the copies below do
+    int last_obs_rows = 0;                       // the row pitch of whichever holds it
+    std::vector<svo_track_obs> kept_obs;
+    std::vector<int> kept_hdr;
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -358,7 +377,7 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
-    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps, (void*)c->h_cov}) if (p) (void)hipHostFree(p);
+    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps, (void*)c->h_cov, (void*)c->h_obs, (void*)c->h_obs_hdr}) if (p) (void)hipHostFree(p);
     for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
     for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
     for (const auto& r : c->retired) (void)hipFree(r.p);
@@ -552,7 +571,8 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     HIPCHK(choose_pnp_build(c->d, share.lean));
     DevBuffers f = frame_view(c, slot, n_act);                         // after the build choice: co_resident travels in the view
     int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0) |
-               (c->clahe_on ? SVO_PATH_CLAHE : 0);
+               (c->clahe_on ? SVO_PATH_CLAHE : 0) | (c->track_on ? SVO_PATH_TRACK_IDS : 0);
+    const bool ids = c->track_on;
     const uint8_t* const* dp = ring_row(c, f.img_ptrs, slot);          // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(f);
     bool detected = false;
@@ -562,13 +582,17 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     } else {
         if (f.act) HIPCHK(upload_act(c, slot, s));
         if (c->clahe_on) if (const int rc = clahe_front(c, f, dp, stride, s)) return rc;   // the front below then ingests the staging frames as mono8
-        detected = !mrows && launch_front_fused(f, dp, stride, s);     // lone stream: ingest + pyramid beside detection, two launches (a masked frame: the unfused front)
+        detected = !mrows && !ids && launch_front_fused(f, dp, stride, s);   // lone stream: ingest + pyramid beside detection, two launches (a masked or ids frame: the unfused front)
         if (detected) path |= SVO_PATH_FRONT_FUSED;
         else launch_ingest_pyramid(f, dp, stride, s, PYR_BEGIN);       // + the per-frame reset
     }
     c->begin_recorded = ahead;
     HIPCHK(record(EV_PYR));                                            // (fused front: ms[0] = the whole front, ms[1] ~ 0)
-    if (mrows) {                                                       // both passes behind the masks of the image they scan
+    if (ids) {                                                         // both passes with the ids build of the emit, masked or not
+        const MaskArgs m = {mrows, f.geom.W};
+        launch_detect_ids(f, c->ids, mrows ? &m : nullptr, 0, -1, s); launch_detect_ids(f, c->ids, mrows ? &m : nullptr, 1, -1, s);
+        if (mrows) path |= SVO_PATH_DETECT_MASKED;
+    } else if (mrows) {                                                // both passes behind the masks of the image they scan
         const MaskArgs m = {mrows, f.geom.W};
         launch_detect_masked(f, m, 0, -1, s); launch_detect_masked(f, m, 1, -1, s);
         path |= SVO_PATH_DETECT_MASKED;
@@ -590,12 +614,14 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         gate->armed = true;
     }
     launch_compact(f, s);
+    if (ids) launch_ids_compact(f, c->ids, s);
     const bool tri_epnp = launch_triangulate_epnp_fused(f, s);          // lone stream: the first EPnP chunk runs beside the triangulation
     if (tri_epnp) path |= SVO_PATH_TRI_EPNP_FUSED;
     else launch_triangulate(f, s);
     HIPCHK(record(EV_TRI));                                            // (fused: the stage timers count that chunk with the triangulation)
     launch_pnp(f, s, tri_epnp);
     if (c->cov_mode) launch_pose_cov(f, CovArgs{c->d_cov + (size_t)slot * c->d.B, c->cov_mode, c->cov_sigma2}, s);   // into the pinned ring, like the record below
+    if (ids) launch_track_obs(f, c->ids, TrackObsArgs{c->d_obs + (size_t)slot * c->d.B * c->track_rows, c->d_obs_hdr + (size_t)slot * 2 * c->d.B, c->track_rows}, s);
     launch_frame_end(f, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
     c->last_path = path;
     return SVO_OK;
@@ -712,6 +738,17 @@ static int take_masks(svo_context* c, int slot, const uint8_t* active, const uin
     return SVO_OK;
 }
 
+// The last collected frame's headers and rows out of the ring slot a new frame is about to write, into the context's own copy.
+static void keep_last_obs(svo_context* c) {
+    const size_t B = c->d.B, R = c->track_rows;
+    const int* hdr = c->h_obs_hdr + (size_t)c->last_obs_slot * 2 * B;
+    const svo_track_obs* rows = c->h_obs + (size_t)c->last_obs_slot * B * R;
+    c->kept_hdr.assign(hdr, hdr + 2 * B);
+    c->kept_obs.resize(B * R);
+    for (size_t i = 0; i < B; i++) memcpy(c->kept_obs.data() + i * R, rows + i * R, sizeof(svo_track_obs) * (size_t)hdr[2 * i + 1]);
+    c->last_obs_slot = -1;
+}
+
 // Enqueue one frame.  ptrs: host arrays of B DEVICE image pointers.  active: NULL (every sequence takes the frame) or B flags,
 // checked by check_frame_args.
 static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
@@ -733,11 +770,12 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     const uint8_t* const* mrows = nullptr;
     if ((rc = take_masks(c, slot, active, &mrows)) != SVO_OK) return rc;
     bool replayed = false;
-    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on)   // a ragged, rectifying, masked or CLAHE frame runs from the launch list
+    if (c->track_on && slot == c->last_obs_slot) keep_last_obs(c);    // the frame is about to write the slot svo_get_last_track_obs still reads
+    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on && !c->track_on)   // a ragged, rectifying, masked, CLAHE or track-ids frame runs from the launch list
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
     if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
-    r.cov_mode = c->cov_mode; r.masked = active != nullptr;
+    r.cov_mode = c->cov_mode; r.masked = active != nullptr; r.tracks = c->track_on;
     c->staged_inputs = false;
     HIPCHK(hipEventRecord(r.ev[EV_DONE], c->stream));
     HIPCHK(hipGetLastError());
@@ -765,6 +803,14 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
         memcpy(c->last_cov.data(), c->h_cov + (size_t)slot * B, sizeof(PoseCovRow) * B);
         const int* flags = ring_row(c, c->h_act, slot) + B;
         for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) memset(&c->last_cov[i], 0, sizeof(PoseCovRow));
+    }
+    c->last_tracks_on = c->ring[slot].tracks;
+    c->last_obs_slot = -1;
+    if (c->last_tracks_on) {                                         // read in place; idle sequences took no launch: zero headers
+        int* hdr = c->h_obs_hdr + (size_t)slot * 2 * B;
+        const int* flags = ring_row(c, c->h_act, slot) + B;
+        for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) hdr[2 * i] = hdr[2 * i + 1] = 0;
+        c->last_obs_slot = slot; c->last_obs_rows = c->track_rows;
     }
     c->last_slot = slot;
     c->tail = (c->tail + 1) % SVO_RING; c->inflight--; c->n_collected++;
@@ -797,6 +843,7 @@ extern "C" int svo_reset_sequence(svo_context* c, int seq, const float Pl[12], c
     SeqProjection p = {};
     if (Pl) { memcpy(p.Pl, Pl, sizeof(p.Pl)); memcpy(p.Pr, Pr, sizeof(p.Pr)); p.set = 1; }
     launch_reset_seq(c->d, seq, p, c->stream);                       // behind every frame submitted so far, before every later one
+    if (c->ids.next_id) launch_ids_reset(c->ids, seq < 0 ? 0 : seq, seq < 0 ? c->d.B : 1, c->stream);   // next_id = 0, stream-ordered like the rest
     HIPCHK(hipGetLastError());
     if (Pl && seq < 0) c->projection_set = true;
     return SVO_OK;
@@ -936,6 +983,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     if (c->d.B != 1) return fail_arg("svo_circular_matching needs a context created with n_seq == 1");
     int rc = check_stride(c, stride); if (rc != SVO_OK) return rc;
     if (c->inflight != 0) { g_err = "svo_circular_matching with frames in flight"; return SVO_ERR_STATE; }
+    if (c->track_on) { g_err = "svo_circular_matching with the track output on: it overwrites the feature set behind the ids (svo_set_track_output(ctx, 0, 0) first)"; return SVO_ERR_STATE; }
     if (n == 0) return SVO_OK;                                                    // vo.cpp:179-181
     if (n > c->d.CAP) { g_err = "more points than the context's feature capacity"; return SVO_ERR_CAPACITY; }
     HIPCHK(hipSetDevice(c->device));
@@ -1037,6 +1085,63 @@ extern "C" int svo_get_last_tracks(svo_context* c, int seq, int cap, float* pl0,
         if (inlier) HIPCHK(hipMemcpy(inlier, c->d.inlier + o, (size_t)n, hipMemcpyDeviceToHost));
     }
     return hs.n_tracks;
+}
+
+// ---- track ids and observation rows (svo.h) ----
+extern "C" int svo_set_track_output(svo_context* c, int on, int max_rows) {
+    if (!c) return fail_arg("null context");
+    if (c->inflight != 0) { g_err = "svo_set_track_output with frames in flight: switching is a setup action (collect first)"; return SVO_ERR_STATE; }
+    if (!on) { c->track_on = false; return SVO_OK; }
+    if (c->d.cfg.features_per_bucket > 1) return fail_arg("track ids need features_per_bucket == 1 (the general bucket walk carries no ids)");
+    if (max_rows < 1 || max_rows > c->d.CAP) return fail_arg("max_rows must be 1 .. the context's feature capacity");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t B = c->d.B, CAP = c->d.CAP;
+    if (!c->ids.next_id) {
+        int rc;
+        if ((rc = dev_alloc(c, &c->ids.feat_id[0], B * CAP)) != SVO_OK || (rc = dev_alloc(c, &c->ids.feat_id[1], B * CAP)) != SVO_OK ||
+            (rc = dev_alloc(c, &c->ids.track_id, B * CAP)) != SVO_OK) return rc;
+        if ((rc = dev_alloc(c, &c->ids.next_id, B)) != SVO_OK) { c->ids.next_id = nullptr; return rc; }   // next_id marks the set complete
+    }
+    if (!c->h_obs || c->track_rows != max_rows) {
+        if (c->last_obs_slot >= 0) keep_last_obs(c);                 // the last collected frame's rows outlive the ring they were in
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (void* p : {(void*)c->h_obs, (void*)c->h_obs_hdr}) if (p) (void)hipHostFree(p);
+        c->h_obs = nullptr; c->h_obs_hdr = nullptr; c->track_rows = 0;
+        const size_t rows = (size_t)SVO_RING * B * (size_t)max_rows;
+        HIPCHK(hipHostMalloc((void**)&c->h_obs, sizeof(svo_track_obs) * rows, hipHostMallocMapped));
+        HIPCHK(hipHostMalloc((void**)&c->h_obs_hdr, sizeof(int) * 2 * SVO_RING * B, hipHostMallocMapped));
+        memset(c->h_obs_hdr, 0, sizeof(int) * 2 * SVO_RING * B);
+        HIPCHK(hipHostGetDevicePointer((void**)&c->d_obs, c->h_obs, 0));
+        HIPCHK(hipHostGetDevicePointer((void**)&c->d_obs_hdr, c->h_obs_hdr, 0));
+        c->track_rows = max_rows;
+    }
+    if (!c->track_on) launch_ids_assign(c->d, c->ids, c->stream);     // the features held now: next_id + index
+    HIPCHK(hipGetLastError());
+    c->track_on = true;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_last_track_obs(svo_context* c, int seq, int cap, svo_track_obs* rows, int* n_tracks) {
+    if (!c || seq < 0 || seq >= c->d.B || cap < 0 || (cap > 0 && !rows)) return fail_arg("bad context / seq / cap / rows");
+    if (c->last_slot < 0 || !c->last_tracks_on) { g_err = "the last collected frame was issued with the track output off (or none was collected yet)"; return SVO_ERR_STATE; }
+    const size_t B = c->d.B, R = c->last_obs_rows;
+    const bool ring = c->last_obs_slot >= 0;
+    const int* hdr = ring ? c->h_obs_hdr + (size_t)c->last_obs_slot * 2 * B : c->kept_hdr.data();
+    const svo_track_obs* src = ring ? c->h_obs + (size_t)c->last_obs_slot * B * R : c->kept_obs.data();
+    if (n_tracks) *n_tracks = hdr[2 * seq];
+    const int n = hdr[2 * seq + 1] < cap ? hdr[2 * seq + 1] : cap;
+    if (n > 0) memcpy(rows, src + (size_t)seq * R, sizeof(svo_track_obs) * (size_t)n);
+    return n;
+}
+
+extern "C" int svo_get_feature_ids(svo_context* c, int seq, int cap, int64_t* ids) {
+    if (!c || seq < 0 || seq >= c->d.B || cap < 0) return fail_arg("bad context / seq / cap");
+    if (!c->track_on) { g_err = "svo_get_feature_ids with the track output off"; return SVO_ERR_STATE; }
+    SeqState hs; int rc = read_state(c, seq, &hs); if (rc != SVO_OK) return rc;
+    const int n = hs.n_feat < cap ? hs.n_feat : cap;
+    static_assert(sizeof(long long) == sizeof(int64_t), "ids are 64-bit");
+    if (n > 0 && ids) HIPCHK(hipMemcpy(ids, c->ids.feat_id[hs.feat_buf] + (size_t)seq * c->d.CAP, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    return hs.n_feat;
 }
 
 // the slot a diagnostic read-out (svo_get_pyramid, svo_get_derivatives) reads, and its refusals; synchronises the context's stream

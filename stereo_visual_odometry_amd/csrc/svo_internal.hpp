@@ -190,6 +190,14 @@ __host__ __device__ inline bool mask_keeps(const uint8_t* mask, int stride, int 
 // The masks of one detection launch: rows[seq] = the mask of the left image sequence seq's detection scans (library-owned device
 // memory), or null: everything allowed there.  Kernel arguments of their own, like CovArgs: no existing kernel's argument block changes.
 struct MaskArgs { const uint8_t* const* rows; int stride; };
+// Track ids and per-frame observation rows (svo.h, svo_set_track_output).  The ids live in buffers of their own and travel in an
+// argument struct of their own, like MaskArgs: DevBuffers, SeqState and every existing kernel's argument block stay as they are.
+// feat_id[k]: [B][CAP] the ids of the feature double-buffer's half k (SeqState::feat_buf picks the current one, as for feat_xy);
+// track_id: [B][CAP] the ids of the compacted tracks; next_id: [B] the sequence's counter (svo.h, the identity rule).
+struct IdArgs { long long* feat_id[2]; long long* track_id; long long* next_id; };
+// One frame's rows of the pinned observation ring: rows [B][max_rows], hdr [B] {n_tracks, n_rows} — host memory mapped into the
+// device, written in place by k_track_obs like the result records.
+struct TrackObsArgs { svo_track_obs* rows; int* hdr; int max_rows; };
 // what Bucket::add_feature compares (feature_set.cpp:16-18); the division truncates toward zero, as C's does
 __device__ __forceinline__ int bucket_score(int age, int strength, int fast_thr) { return age + (strength - fast_thr) / 20; }
 // capacity 1: (score, first come, strength) as one key for a 64-bit atomicMax; order = the candidate's rank in the input list
@@ -253,6 +261,14 @@ hipError_t prepare_pnp_lean();   // before the first launch_pnp with co_resident
 bool launch_triangulate_epnp_fused(const DevBuffers& d, hipStream_t s);   // lone stream: triangulation || first EPnP chunk in one launch; false = not applicable
 void launch_pnp_subsets(const DevBuffers& d, hipStream_t s);
 void launch_pose_cov(const DevBuffers& d, const CovArgs& a, hipStream_t s);   // after launch_pnp: the covariance of the refined pose, one block per launched sequence
+// ---- track ids (svo_set_track_output; features_per_bucket == 1 only) ----
+// a detection pass that carries ids: the pass's FAST kernel (masked when m is given), then the ids build of the emit
+void launch_detect_ids(const DevBuffers& d, const IdArgs& ia, const MaskArgs* m, int pass, int th_override, hipStream_t s);
+void launch_ids_compact(const DevBuffers& d, const IdArgs& ia, hipStream_t s);     // behind launch_compact: the ids through its stable ranks
+// behind launch_pnp, before launch_frame_end: the inlier compaction's id move, then the frame's header and rows into the pinned ring
+void launch_track_obs(const DevBuffers& d, const IdArgs& ia, const TrackObsArgs& oa, hipStream_t s);
+void launch_ids_assign(const DevBuffers& d, const IdArgs& ia, hipStream_t s);      // switching on: held features get next_id + index
+void launch_ids_reset(const IdArgs& ia, int seq0, int n, hipStream_t s);           // svo_reset_sequence: next_id = 0
 void launch_pnp_p3p(const DevBuffers& d, hipStream_t s);                // exactly four points: one P3P, no RANSAC (stage API only)
 void launch_inverse_transform(const double* R, const double* t, double* T, hipStream_t s);   // device pointers
 // the front of a lone stream's frame as two fused launches (ingest + level 1 || FAST pass 0; levels 2-3 || emit), then the second

@@ -1190,7 +1190,11 @@ void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* 
 // pass kept too few features (vo.cpp:327) that last block also offers the new set to the grid for the second pass.
 #define EMIT_THREADS 256
 #define EMIT_WAVES (EMIT_THREADS / 64)
-static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int pass, int row, int b, int n_rows) {
+// IDS (svo.h, the identity rule, step 1): the winner's `order` is the only place its source rank exists — an entry of the old list
+// keeps its id, a fresh FAST hit at output position pos gets next_id + pos — and the publishing block advances next_id by the
+// count.  Every block reads next_id before it takes its ticket, the publisher writes it after the last ticket.
+template <bool IDS = false>
+static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int pass, int row, int b, int n_rows, const IdArgs* ia = nullptr) {
     const int seq = seq_of(d, b);
     SeqState& s = d.st[seq];
     if (!detect_pass_runs(s, pass)) return;
@@ -1205,6 +1209,8 @@ static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int
     float2* nxy = d.feat_xy[fb ^ 1] + (size_t)seq * d.CAP;
     int* nage = d.feat_age[fb ^ 1] + (size_t)seq * d.CAP;
     int* nstr = d.feat_str[fb ^ 1] + (size_t)seq * d.CAP;
+    long long id_base = 0; const long long* oid = nullptr; long long* nid = nullptr;
+    if constexpr (IDS) { id_base = ia->next_id[seq]; oid = ia->feat_id[fb] + (size_t)seq * d.CAP; nid = ia->feat_id[fb ^ 1] + (size_t)seq * d.CAP; }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // winners in the rows before this one, and in all rows
     int before = 0, all = 0;
@@ -1228,6 +1234,7 @@ static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int
         for (int w = 0; w < EMIT_WAVES; w++) run += sh_cnt[w];
         if (k != 0ull && pos < d.CAP) {
             const unsigned order = 0xFFFFFFFFu - (unsigned)((k >> 16) & 0xFFFFFFFFull);
+            if constexpr (IDS) nid[pos] = order < (unsigned)n_old ? oid[order] : id_base + pos;
             if (order < (unsigned)n_old) { nxy[pos] = oxy[order]; nage[pos] = oage[order]; nstr[pos] = ostr[order]; }
             else {
                 const unsigned pixi = order - (unsigned)n_old;
@@ -1255,6 +1262,7 @@ static __device__ __forceinline__ void bucket_emit_body(const DevBuffers& d, int
         s.stats.n_after_detect = total;
         if (pass == 0) { s.do_second = second; if (second) s.n_old = total; }
         else s.stats.second_pass = 1;
+        if constexpr (IDS) ia->next_id[seq] = id_base + total;
     }
     if (second) {                                                     // block-uniform
         __threadfence();
@@ -1270,6 +1278,18 @@ __global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_strided(DevBuffers
     if (!detect_pass_runs(d.st[seq_of(d, blockIdx.y)], pass)) return;
     for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
         bucket_emit_body(d, pass, row, blockIdx.y, n_rows);
+        __syncthreads();
+    }
+}
+
+// the ids builds of the two emit kernels (svo_set_track_output); masked and plain detection share them, as they share the emit
+__global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_ids(DevBuffers d, IdArgs ia, int pass) {
+    bucket_emit_body<true>(d, pass, blockIdx.x, blockIdx.y, gridDim.x, &ia);
+}
+__global__ __launch_bounds__(EMIT_THREADS) void k_bucket_emit_strided_ids(DevBuffers d, IdArgs ia, int pass, int n_rows) {
+    if (!detect_pass_runs(d.st[seq_of(d, blockIdx.y)], pass)) return;
+    for (int row = blockIdx.x; row < n_rows; row += gridDim.x) {
+        bucket_emit_body<true>(d, pass, row, blockIdx.y, n_rows, &ia);
         __syncthreads();
     }
 }
@@ -1486,6 +1506,23 @@ void launch_detect_masked(const DevBuffers& d, const MaskArgs& m, int pass, int 
     hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, g.z), dim3(EMIT_THREADS), 0, st, d, pass);
 }
 
+// A detection pass that carries track ids: the pass's FAST kernel — masked when masks are given — then the ids build of the emit.
+void launch_detect_ids(const DevBuffers& d, const IdArgs& ia, const MaskArgs* m, int pass, int th_override, hipStream_t st) {
+    int th = pass == 0 ? d.cfg.fast_threshold : d.cfg.fast_threshold / 4;            // vo.cpp:325 / :329-330
+    if (th_override >= 0) th = th_override;
+    const dim3 g = fast_grid(d);
+    static const bool strided_off = getenv("SVO_SECOND_PASS_STRIDED") && atoi(getenv("SVO_SECOND_PASS_STRIDED")) == 0;
+    if (pass == 1 && d.B > SVO_LONE_MAX_SEQ && !strided_off) {
+        if (m) hipLaunchKernelGGL(k_fast_strided_masked, dim3(FAST_STRIDED_BLOCKS, 1, g.z), dim3(256), 0, st, d, *m, pass, th, (int)g.x, (int)g.y);
+        else hipLaunchKernelGGL(k_fast_strided, dim3(FAST_STRIDED_BLOCKS, 1, g.z), dim3(256), 0, st, d, pass, th, (int)g.x, (int)g.y);
+        hipLaunchKernelGGL(k_bucket_emit_strided_ids, dim3(EMIT_STRIDED_BLOCKS, g.z), dim3(EMIT_THREADS), 0, st, d, ia, pass, d.cfg.buckets_along_height);
+        return;
+    }
+    if (m) hipLaunchKernelGGL(k_fast_masked, g, dim3(256), 0, st, d, *m, pass, th);
+    else hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, d, pass, th);
+    hipLaunchKernelGGL(k_bucket_emit_ids, dim3(d.cfg.buckets_along_height, g.z), dim3(EMIT_THREADS), 0, st, d, ia, pass);
+}
+
 // ---- the stage call's wrappers (svo_bucket_filter): one grid, the caller's n candidates, n_out = the number emitted ----
 __global__ void k_bucket_walk(BucketGrid g, int per, int n, const float2* xy, const int* ages, const int* strs,
                               float2* slot_xy, int* slot_age, int* slot_str, int* slot_n) {
@@ -1599,4 +1636,113 @@ __global__ void k_find_close(int n, const float2* a, const float2* b, float thr,
 }
 void launch_find_close(int n, const float2* a, const float2* b, float thr, uint8_t* ok, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_find_close, dim3((n + 255) / 256), dim3(256), 0, st, n, a, b, thr, ok);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Track ids and observation rows (svo.h, svo_set_track_output): the identity rule's steps 2-4 and the two setup kernels.
+// ------------------------------------------------------------------------------------------------
+// Step 2, behind k_compact: the ids of the features that entered LK through k_compact's stable ranks, recomputed from okmask and
+// n_lk with the same ballot scan, to the tracks and to the feature half k_compact has just made current.  One block per launched
+// sequence.  (k_compact itself is untouched: its registers and its argument block are what they were.)
+#define IDC_THREADS 256
+__global__ __launch_bounds__(IDC_THREADS) void k_ids_compact(DevBuffers d, IdArgs a) {
+    const int seq = seq_of(d, blockIdx.x);
+    const SeqState& s = d.st[seq];
+    if (!s.active || s.n_lk <= 0) return;                            // no LK, no compaction: k_compact did not flip the halves
+    __shared__ int sh_cnt[IDC_THREADS / 64];
+    const int n = s.n_lk, dst = s.feat_buf, src = dst ^ 1;
+    const size_t o = (size_t)seq * d.CAP;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long* sid = a.feat_id[src] + o;
+    long long* did = a.feat_id[dst] + o; long long* tid = a.track_id + o;
+    int run = 0;
+    for (int base = 0; base < n; base += IDC_THREADS) {
+        const int i = base + threadIdx.x;
+        const bool keep = i < n && d.okmask[o + i] == 3;
+        const unsigned long long bal = __ballot(keep);
+        __syncthreads();                                              // the previous round's counts have been read
+        if (lane == 0) sh_cnt[wv] = __popcll(bal);
+        __syncthreads();
+        int pos = run + __popcll(bal & ((1ull << lane) - 1ull));
+        for (int w = 0; w < IDC_THREADS / 64; w++) { const int c = sh_cnt[w]; if (w < wv) pos += c; run += c; }
+        if (keep) { const long long id = sid[i]; tid[pos] = id; did[pos] = id; }
+    }
+}
+void launch_ids_compact(const DevBuffers& d, const IdArgs& ia, hipStream_t st) {
+    hipLaunchKernelGGL(k_ids_compact, dim3(launch_seqs(d)), dim3(IDC_THREADS), 0, st, d, ia);
+}
+
+// Steps 3 and 4, behind the pose stage: one block per launched sequence.  Where k_pnp_final replaced the feature set by the inliers
+// (fail_reason 0 or 4) new feature pos takes the id of track inl_idx[pos]; then the header and the first min(n_tracks, max_rows)
+// rows go straight into the pinned host ring.  A row is 64 bytes = four lanes x 16 bytes: lane 4r + p builds part p of row r in
+// registers and a wave stores 1 KiB of consecutive host memory with one dwordx4 store per lane.  Loads and stores only: no LDS.
+//   part 0: id, l0     part 1: r0, l1     part 2: r1, xyz[0..1]     part 3: xyz[2], age, flags, pad
+#define TO_THREADS 256
+static_assert(sizeof(svo_track_obs) == 64, "a row is four 16-byte parts");
+static __device__ __forceinline__ void track_obs_body(const DevBuffers& d, const IdArgs& a, const TrackObsArgs& oa) {
+    const int seq = seq_of(d, blockIdx.x);
+    const SeqState& s = d.st[seq];
+    const size_t o = (size_t)seq * d.CAP;
+    const int fr = s.fail_reason, fb = s.feat_buf;
+    const int n = s.active ? s.n_tracks : 0;
+    const bool flipped = n > 0 && (fr == 0 || fr == 4);              // k_pnp_final made the inliers the current half
+    if (flipped) {
+        long long* nid = a.feat_id[fb] + o;
+        const int m = s.n_feat;
+        for (int pos = threadIdx.x; pos < m; pos += TO_THREADS) nid[pos] = a.track_id[o + d.inl_idx[o + pos]];
+    }
+    const int* age = d.feat_age[flipped ? fb ^ 1 : fb] + o;          // step 2's output: position = track index
+    const bool has_xyz = fr == 0 || fr == 3 || fr == 4, has_inl = fr == 0 || fr == 4;
+    int rows = n < oa.max_rows ? n : oa.max_rows;
+    if (rows > d.CAP) rows = d.CAP;
+    uint4* out = reinterpret_cast<uint4*>(oa.rows + (size_t)seq * oa.max_rows);
+    for (int t = threadIdx.x; t < rows * 4; t += TO_THREADS) {
+        const int r = t >> 2, part = t & 3;
+        uint4 v;
+        if (part == 0) {
+            const unsigned long long id = (unsigned long long)a.track_id[o + r];
+            const float2 p = d.tl0[o + r];
+            v = make_uint4((unsigned)id, (unsigned)(id >> 32), __float_as_uint(p.x), __float_as_uint(p.y));
+        } else if (part == 1) {
+            const float2 p = d.tr0[o + r], q = d.tl1[o + r];
+            v = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), __float_as_uint(q.x), __float_as_uint(q.y));
+        } else if (part == 2) {
+            const float2 p = d.tr1[o + r];
+            const float* w = d.world + 3 * (o + r);
+            v = make_uint4(__float_as_uint(p.x), __float_as_uint(p.y), has_xyz ? __float_as_uint(w[0]) : 0u, has_xyz ? __float_as_uint(w[1]) : 0u);
+        } else {
+            const unsigned fl = (has_inl && d.inlier[o + r] ? (unsigned)SVO_OBS_INLIER : 0u) | (has_xyz ? (unsigned)SVO_OBS_HAS_XYZ : 0u);
+            v = make_uint4(has_xyz ? __float_as_uint(d.world[3 * (o + r) + 2]) : 0u, (unsigned)age[r], fl, 0u);
+        }
+        out[t] = v;
+    }
+    if (threadIdx.x == 0) { oa.hdr[2 * seq] = n; oa.hdr[2 * seq + 1] = rows; }
+}
+// Two builds, as k_pose_cov has: full registers, and the 48-register one a co-resident context launches beside another's LK grid.
+__global__ __launch_bounds__(TO_THREADS) void k_track_obs(DevBuffers d, IdArgs a, TrackObsArgs oa) { track_obs_body(d, a, oa); }
+__global__ __launch_bounds__(TO_THREADS) __attribute__((amdgpu_num_vgpr(48))) void k_track_obs_lean(DevBuffers d, IdArgs a, TrackObsArgs oa) { track_obs_body(d, a, oa); }
+void launch_track_obs(const DevBuffers& d, const IdArgs& ia, const TrackObsArgs& oa, hipStream_t st) {
+    hipLaunchKernelGGL(d.co_resident ? k_track_obs_lean : k_track_obs, dim3(launch_seqs(d)), dim3(TO_THREADS), 0, st, d, ia, oa);
+}
+
+// Switching the output on: the features every sequence holds get next_id + index, next_id advances by their count.
+__global__ __launch_bounds__(256) void k_ids_assign(DevBuffers d, IdArgs a) {
+    const int seq = blockIdx.x;
+    const SeqState& s = d.st[seq];
+    const int n = s.n_feat < d.CAP ? s.n_feat : d.CAP;
+    const long long base = a.next_id[seq];
+    long long* id = a.feat_id[s.feat_buf] + (size_t)seq * d.CAP;
+    for (int i = threadIdx.x; i < n; i += 256) id[i] = base + i;
+    __syncthreads();                                                  // every thread has read next_id
+    if (threadIdx.x == 0) a.next_id[seq] = base + n;
+}
+void launch_ids_assign(const DevBuffers& d, const IdArgs& ia, hipStream_t st) {
+    hipLaunchKernelGGL(k_ids_assign, dim3(d.B), dim3(256), 0, st, d, ia);
+}
+__global__ void k_ids_reset(IdArgs a, int seq0, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a.next_id[seq0 + i] = 0;
+}
+void launch_ids_reset(const IdArgs& ia, int seq0, int n, hipStream_t st) {
+    hipLaunchKernelGGL(k_ids_reset, dim3((n + 63) / 64), dim3(64), 0, st, ia, seq0, n);
 }

@@ -2,7 +2,7 @@
 """Cost of one optional feature at the bench shape (bench.py's workload: KITTI-00-shaped 1241x376, LK 21x21, maxLevel 3, two
 contexts x 256 sequences, frames resident in HBM, 4 frames in flight per context):
 
-    python tools/feature_bench.py FEATURE [options]        FEATURE: rectify | input_format | pose_cov | detect_mask | clahe
+    python tools/feature_bench.py FEATURE [options]        FEATURE: rectify | input_format | pose_cov | detect_mask | clahe | tracks
 
 A feature is one entry of FEATURES: its legs (the baseline first: the library as it is without the feature's setter, nothing is
 called), per leg the frame format and a setup(vo, context_index), the svo_get_stage_timing stage it reports, and optionally a
@@ -99,6 +99,9 @@ FEATURES = dict(
                      legs=dict(off=("rendered", nothing), shared=("rendered", mask_shared), per_seq=("rendered", mask_per_seq))),
     clahe=dict(stage="ingest+pyramid", evidence=None,
                legs=dict(off=("mono8", nothing), on=("mono8", clahe_on), on_bgr8=("bgr8", clahe_on))),
+    tracks=dict(stage="pnp",                          # the rows of sequence 0 only: reading all of them would be timed with the leg
+                evidence=("rows_of_sequence_0", lambda vo, leg, nbytes: len(vo.last_track_obs(0)) if leg != "off" else 0, False),
+                legs=dict(off=("rendered", nothing), on=("rendered", lambda vo, c: vo.set_track_output(2048)))),
 )
 
 

@@ -25,6 +25,9 @@
 // tools/camera_info_yaml.hpp): the frames are rectified on the GPU (svo_set_rectification, what stereo_image_proc does on
 // the CPU to publish image_rect) and the projection matrices are the files' P (P_right[0][3] = -fx * baseline is the
 // reference's bf); it overrides --calib.
+// `--tracks file.csv` switches the track output on (svo.h, svo_set_track_output) and writes one line per observation row,
+// `frame,id,ul,vl,ur,vr,x,y,z,age,inlier,has_xyz`: this frame's stereo observation (l1, r1) of landmark `id`, and the point
+// triangulated from the previous frame's pair, in the previous frame's left camera frame.
 #include <zlib.h>
 #include <cmath>
 #include <cstdio>
@@ -166,10 +169,10 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
-    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path;
+    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path, tracks_out;
     bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false, clahe = false;
     double clahe_clip = 2.0; int clahe_tx = 8, clahe_ty = 8;
     for (int i = 3; i + 1 < argc; i += 2) {
@@ -183,6 +186,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--calib")) calib = argv[i + 1];
         else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
         else if (!strcmp(argv[i], "--covariance")) cov_out = argv[i + 1];   // one row per frame: valid, then the 21 upper-triangle entries of cov_T (svo.h), row by row
+        else if (!strcmp(argv[i], "--tracks")) tracks_out = argv[i + 1];    // one line per observation row of every frame (svo.h, svo_track_obs)
         else if (!strcmp(argv[i], "--mask")) mask_path = argv[i + 1];       // a static detection mask (svo.h): PGM or PNG of the frame size, non-zero = features allowed; needs --gray 1 or 2
         else if (!strcmp(argv[i], "--clahe")) {                             // clip,tx,ty: CLAHE on the grey frames inside frame ingest (svo.h); needs --gray 1 or 2
             if (std::sscanf(argv[i + 1], "%lf,%d,%d", &clahe_clip, &clahe_tx, &clahe_ty) != 3) { std::fprintf(stderr, "--clahe needs clip,tx,ty (e.g. 2.0,8,8)\n"); return 2; }
@@ -221,6 +225,12 @@ int main(int argc, char** argv) {
         for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) cov << ",c" << a << b;
         cov << "\n";
     }
+    std::ofstream tracks;
+    if (!tracks_out.empty()) {
+        tracks.open(tracks_out);
+        if (!tracks) { std::fprintf(stderr, "cannot write %s\n", tracks_out.c_str()); return 2; }
+        tracks << "frame,id,ul,vl,ur,vr,x,y,z,age,inlier,has_xyz\n";
+    }
     try {
         svo_config cfg; svo_config_default(&cfg);
         cfg.lk_float_sums = float_sums ? 1 : 0;
@@ -230,6 +240,7 @@ int main(int argc, char** argv) {
         if (gray_gpu) vo.set_input_encoding("bgr8");
         if (cov.is_open()) vo.set_pose_covariance(SVO_COV_RESIDUAL);
         if (clahe) vo.set_clahe(clahe_clip, clahe_tx, clahe_ty);
+        if (tracks.is_open()) vo.set_track_output((cfg.buckets_along_height - cfg.bucket_start_row) * cfg.buckets_along_width);   // the grid's capacity: every row
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
         if (identity_start) { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(pose, I, sizeof(I)); }
@@ -258,6 +269,13 @@ int main(int argc, char** argv) {
                 cov << (c.valid ? 1 : 0);
                 for (int a = 0; a < 6; a++) for (int b = a; b < 6; b++) { std::snprintf(row, sizeof(row), ",%.17g", c.cov_T[6 * a + b]); cov << row; }
                 cov << "\n";
+            }
+            if (tracks.is_open()) {
+                for (const svo_track_obs& t : vo.last_track_observations()) {
+                    std::snprintf(row, sizeof(row), "%d,%lld,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%d,%d,%d\n", i, (long long)t.id, t.l1[0], t.l1[1], t.r1[0], t.r1[1],
+                                  t.xyz[0], t.xyz[1], t.xyz[2], t.age, (t.flags & SVO_OBS_INLIER) ? 1 : 0, (t.flags & SVO_OBS_HAS_XYZ) ? 1 : 0);
+                    tracks << row;
+                }
             }
             std::printf("Frame %d: ok=%d tracks=%d inliers=%d\n", i, (int)o.first, vo.stats.n_after_bounds, vo.stats.n_inliers);
             done++;

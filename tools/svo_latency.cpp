@@ -3,11 +3,13 @@
 // src/main.cpp:394).  Reads stereo pairs from a raw file (int32 n, h, w; then n x (left, right) gray images), plays them
 // ping-pong through svo_process and prints the mean / median / p95 wall time per call, with ordinary heap buffers and with
 // page-locked ones (svo_alloc_pinned).
-//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance | --mask | --clahe]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
+//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance | --mask | --clahe | --tracks]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
 // --covariance: every leg is run twice, without and with the pose covariance (svo_set_pose_covariance, SVO_COV_RESIDUAL).
 // --mask: every leg is run twice, without and with a static detection mask (svo_set_detection_mask: the lower quarter of the image
 // closed, a bonnet) — a masked lone-stream frame issues the unfused front, one launch more.
 // --clahe: every leg is run twice, without and with CLAHE (svo_set_clahe, clip 2.0, 8 x 8 tiles): two launches more per frame.
+// --tracks: every leg is run twice, without and with the track output (svo_set_track_output, max_rows 2048): the unfused front, the
+// ids builds of the emit, and two launches more per frame (k_ids_compact, k_track_obs).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -17,7 +19,7 @@
 #include <vector>
 #include "svo.h"
 
-static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false, bool mask = false, bool clahe = false) {
+static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false, bool mask = false, bool clahe = false, bool tracks = false) {
     svo_config cfg; svo_config_default(&cfg);
     cfg.win_w = cfg.win_h = win; cfg.max_translation_norm = max_t;
     svo_context* ctx = nullptr;
@@ -32,6 +34,7 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
         if (svo_set_detection_mask(ctx, -1, m.data(), w, 0) != SVO_OK) { std::fprintf(stderr, "svo_set_detection_mask: %s\n", svo_last_error()); std::exit(1); }
     }
     if (clahe && svo_set_clahe(ctx, 1, 2.0, 8, 8) != SVO_OK) { std::fprintf(stderr, "svo_set_clahe: %s\n", svo_last_error()); std::exit(1); }
+    if (tracks && svo_set_track_output(ctx, 1, 2048) != SVO_OK) { std::fprintf(stderr, "svo_set_track_output: %s\n", svo_last_error()); std::exit(1); }
     const int n = (int)L.size();
     auto pp = [&](int i) { const int p = i % (2 * n - 2); return p < n ? p : 2 * n - 2 - p; };
     double T[16]; svo_frame_stats st; int n_ok = 0;
@@ -52,11 +55,12 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
 }
 
 int main(int argc, char** argv) {
-    bool covariance = false, mask = false, clahe = false;
+    bool covariance = false, mask = false, clahe = false, tracks = false;
     if (argc > 2 && !std::strcmp(argv[argc - 1], "--covariance")) { covariance = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--mask")) { mask = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--clahe")) { clahe = true; argc--; }
-    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance | --mask | --clahe]\n"); return 2; }
+    else if (argc > 2 && !std::strcmp(argv[argc - 1], "--tracks")) { tracks = true; argc--; }
+    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance | --mask | --clahe | --tracks]\n"); return 2; }
     const int win = argc > 2 ? std::atoi(argv[2]) : 21, calls = argc > 3 ? std::atoi(argv[3]) : 200;
     const double max_t = argc > 4 ? std::atof(argv[4]) : 2.0;
     std::ifstream f(argv[1], std::ios::binary);
@@ -73,6 +77,7 @@ int main(int argc, char** argv) {
     if (covariance) run(L, R, w, h, win, calls, max_t, "heap buffers, covariance:", true);
     if (mask) run(L, R, w, h, win, calls, max_t, "heap buffers, mask:", false, true);
     if (clahe) run(L, R, w, h, win, calls, max_t, "heap buffers, CLAHE:", false, false, true);
+    if (tracks) run(L, R, w, h, win, calls, max_t, "heap buffers, tracks:", false, false, false, true);
     uint8_t* pin = (uint8_t*)svo_alloc_pinned(heap.size());
     if (pin) {
         std::memcpy(pin, heap.data(), heap.size());
@@ -81,6 +86,7 @@ int main(int argc, char** argv) {
         if (covariance) run(L, R, w, h, win, calls, max_t, "page-locked, covariance:", true);
         if (mask) run(L, R, w, h, win, calls, max_t, "page-locked, mask:", false, true);
         if (clahe) run(L, R, w, h, win, calls, max_t, "page-locked, CLAHE:", false, false, true);
+        if (tracks) run(L, R, w, h, win, calls, max_t, "page-locked, tracks:", false, false, false, true);
         svo_free_pinned(pin);
     }
     return 0;
