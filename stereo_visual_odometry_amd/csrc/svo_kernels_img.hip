@@ -683,16 +683,25 @@ __global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, PyrTa
 // where a dword straddles a fold of a level narrower than the pad: those go byte by byte.  (First version: one thread, one byte
 // load and one byte store per border pixel — 0.39 ms per 512 sequences; the image stream's kernels run in the gap between two LK
 // launches, so their time is whole-job time.)
+// The grid walks ONE list of the border dwords of all levels (blockIdx.x, in level order; a block stays inside one level), a dword
+// per thread: every block has a full share, whatever the size of its level.  (Before: 64 blocks per level striding over its ring —
+// at the three small levels most of them found nothing to do.)
+__host__ __device__ inline int pad_dwords(const LevelInfo& L, int P) {
+    return 2 * P * ((L.w + 2 * P + 3) >> 2) + L.h * ((P >> 2) + ((L.w + P - (L.w & ~3) + 3) >> 2));
+}
 __global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, PyrTarget target) {
     const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;
-    const int seq = seq_of(d, sc / 2), cam = sc & 1, level = blockIdx.y;
+    const int seq = seq_of(d, sc / 2), cam = sc & 1, P = d.geom.pad;
+    int level = 0, blk = blockIdx.x;
+    for (; level + 1 < d.geom.nlevels; level++) { const int n = (pad_dwords(d.geom.lv[level], P) + 255) >> 8; if (blk < n) break; blk -= n; }
     const LevelInfo L = d.geom.lv[level];
-    const int P = d.geom.pad, w = L.w, h = L.h;
+    const int w = L.w, h = L.h;
     uint8_t* img = d.pyr + pyr_index(d, seq, pyr_slot(d.st[seq], target), cam) + (size_t)plane * d.geom.pyr_bytes + L.off;
     const int rowdw = (w + 2 * P + 3) >> 2;                       // dwords of a band row, from x = -P (the last one may reach into the row's stride padding)
     const int xr0 = w & ~3, ldw = P >> 2, sdw = ldw + ((w + P - xr0 + 3) >> 2);   // left + right dwords of an image row
     const int band = P * rowdw, total = 2 * band + h * sdw;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int i = blk * 256 + threadIdx.x;
+    if (i < total) {
         int x, y;
         if (i < 2 * band) { const int j = i < band ? i : i - band, r = j / rowdw; x = (j - r * rowdw) * 4 - P; y = i < band ? r - P : h + r; }
         else { const int j = i - 2 * band; y = j / sdw; const int k = j - y * sdw; x = k < ldw ? 4 * k - P : xr0 + 4 * (k - ldw); }
@@ -706,10 +715,9 @@ __global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, PyrTarget tar
     }
 }
 static void launch_pad_pyramid(const DevBuffers& d, hipStream_t st, PyrTarget target) {
-    const LevelInfo& L0 = d.geom.lv[0];
-    const int P = d.geom.pad, ring0 = 2 * P * (L0.w + 2 * P) + 2 * P * L0.h;
-    int gx = (ring0 + 4 * 256 - 1) / (4 * 256); if (gx < 1) gx = 1; if (gx > 64) gx = 64;      // ~one border dword per thread at level 0 (the smaller levels stride less)
-    hipLaunchKernelGGL(k_pad_pyramid, dim3(gx, d.geom.nlevels, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, target);
+    int blocks = 0;
+    for (int l = 0; l < d.geom.nlevels; l++) blocks += (pad_dwords(d.geom.lv[l], d.geom.pad) + 255) >> 8;
+    hipLaunchKernelGGL(k_pad_pyramid, dim3(blocks, 1, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, target);
 }
 
 // k_deriv_levels: the Scharr images of the levels >= 1 of the target's slot, for the LK kernel (svo_internal.hpp: the derivative
@@ -717,65 +725,92 @@ static void launch_pad_pyramid(const DevBuffers& d, hipStream_t st, PyrTarget ta
 // REFLECT_101 border, at 4 x the Scharr value, the integers lk_pass computes for itself where there are no planes:
 //   t0(c) = 12 (s[y-1][c] + s[y+1][c]) + 40 s[y][c]      t1(c) = s[y+1][c] - s[y-1][c]
 //   Ix(x, y) = t0(x+1) - t0(x-1)                          Iy(x, y) = 12 (t1(x-1) + t1(x+1)) + 40 t1(x)        (|.| <= 16 320)
-// One launch covers every level >= 1 (blockIdx.x walks their tiles in level order), both cameras and the launch's sequences.  A
-// block stages DV_TH + 2 rows of DV_TW + 8 bytes in LDS with aligned dword loads (pixel (0, 0), the row starts and the tile origins
-// are 4-byte aligned; the halo lies inside the stored border); a thread then owns four consecutive samples of one row and stores
-// them as dwords.  Only samples inside the level are written: the planes' zero border stays as the allocation left it.
-#define DV_TW 64
-#define DV_TH 16
-__host__ __device__ inline int deriv_tiles(const LevelInfo& L) { return ((L.w + DV_TW - 1) / DV_TW) * ((L.h + DV_TH - 1) / DV_TH); }
+// One launch covers every level >= 1 (blockIdx.x walks their work items in level order, a block stays inside one level), both
+// cameras and the launch's sequences.  No LDS: a thread owns DV_VEC = 8 consecutive samples of a row — one 16-byte store per plane —
+// and walks DV_ROWS rows down with three source rows in registers, so a source row is loaded (DV_ROWS + 2) / DV_ROWS times.  The
+// vectors start at x = 8 v - (pad & 7): pixel (0, 0) sits pad bytes behind a 16-byte boundary and pad is a multiple of 4, so that
+// origin makes the 8-byte pixel load and both 16-byte stores aligned.  A source row is three aligned loads — the dword before the
+// vector (its last byte is column x - 1), the vector's 8 bytes, the dword after it (its first byte is column x + 8; loaded only
+// where a sample inside the level needs it) — which stay inside the stored border: bytes -8 .. w + 6 of rows -1 .. h (pad >= 8).
+// Only samples inside the level are written: the planes' zero border stays as the allocation left it; the first and the last
+// vector of a row, which may reach outside, store sample by sample.  (First version: a 64 x 16 LDS tile per block, four samples and
+// 8 bytes per plane per thread.)
+#define DV_VEC 8
+#define DV_ROWS 8
+__host__ __device__ inline int deriv_vectors(const LevelInfo& L, int pad) { return (L.w + (pad & 7) + DV_VEC - 1) / DV_VEC; }
+__host__ __device__ inline int deriv_blocks(const LevelInfo& L, int pad) { return (deriv_vectors(L, pad) * ((L.h + DV_ROWS - 1) / DV_ROWS) + 255) / 256; }
+// A source row in registers: columns 0 .. 11 of the vector (column c = pixel x - 1 + c; 0 .. 9 are used), and pair K = columns
+// 2 K and 2 K + 1 as two 16-bit lanes — the arithmetic runs on such pairs (v_pk_*: every value fits 16 bits), and a pair of
+// results is the dword that is stored.
+typedef short dv_s2 __attribute__((ext_vector_type(2)));
+struct DerivRow { unsigned s0, s1, s2; };
+__device__ __forceinline__ DerivRow deriv_load_row(const uint8_t* __restrict__ p, bool right) {   // p: the vector's first pixel in that row
+    const unsigned lo = *reinterpret_cast<const unsigned*>(p - 4);
+    const uint2 m = *reinterpret_cast<const uint2*>(p);
+    const unsigned hi = right ? *reinterpret_cast<const unsigned*>(p + 8) : 0u;
+    return {__builtin_amdgcn_alignbyte(m.x, lo, 3), __builtin_amdgcn_alignbyte(m.y, m.x, 3), __builtin_amdgcn_alignbyte(hi, m.y, 3)};
+}
+template <int K>
+__device__ __forceinline__ dv_s2 deriv_pair(const DerivRow& r) {
+    const unsigned s = K < 2 ? r.s0 : K < 4 ? r.s1 : r.s2;
+    return __builtin_bit_cast(dv_s2, __builtin_amdgcn_perm(s, s, (K & 1) ? 0x0c030c02u : 0x0c010c00u));
+}
+// pairs K - 1 of Ix and Iy of the row between a and c, from the column sums of pairs K - 1 (t0p, t1p) and K, which it leaves behind
+template <int K>
+__device__ __forceinline__ void deriv_step(const DerivRow& a, const DerivRow& b, const DerivRow& c, dv_s2& t0p, dv_s2& t1p, unsigned (&ix)[DV_VEC / 2], unsigned (&iy)[DV_VEC / 2]) {
+    const dv_s2 pa = deriv_pair<K>(a), pb = deriv_pair<K>(b), pc = deriv_pair<K>(c);
+    const dv_s2 t0 = (pa + pc) * (short)12 + pb * (short)40, t1 = pc - pa;
+    if constexpr (K > 0) {
+        ix[K - 1] = __builtin_bit_cast(unsigned, (dv_s2)(t0 - t0p));                 // columns 2 K, 2 K + 1 minus 2 K - 2, 2 K - 1
+        const dv_s2 mid = __builtin_bit_cast(dv_s2, __builtin_amdgcn_alignbyte(__builtin_bit_cast(unsigned, t1), __builtin_bit_cast(unsigned, t1p), 2));   // columns 2 K - 1, 2 K
+        iy[K - 1] = __builtin_bit_cast(unsigned, (dv_s2)((t1p + t1) * (short)12 + mid * (short)40));
+    }
+    t0p = t0; t1p = t1;
+}
+// the vector's samples of one row: 16 bytes where all eight lie inside the level, else the ones that do, one by one
+__device__ __forceinline__ void deriv_store(int16_t* __restrict__ q, const unsigned (&v)[DV_VEC / 2], int x, int w) {
+    if (x >= 0 && x + DV_VEC <= w) *reinterpret_cast<uint4*>(q) = make_uint4(v[0], v[1], v[2], v[3]);
+    else {
+#pragma unroll
+        for (int j = 0; j < DV_VEC; j++) if ((unsigned)(x + j) < (unsigned)w) q[j] = (int16_t)(v[j >> 1] >> (16 * (j & 1)));
+    }
+}
 __global__ __launch_bounds__(256) void k_deriv_levels(DevBuffers d, PyrTarget target) {
-    constexpr int TDW = DV_TW / 4 + 2;                               // dwords of a staged row: one of halo on either side
-    __shared__ unsigned tile[DV_TH + 2][TDW];
-    int level = 1, t = blockIdx.x;
-    for (; level + 1 < d.geom.nlevels; level++) { const int n = deriv_tiles(d.geom.lv[level]); if (t < n) break; t -= n; }
+    const int P = d.geom.pad;
+    int level = 1, b = blockIdx.x;
+    for (; level + 1 < d.geom.nlevels; level++) { const int n = deriv_blocks(d.geom.lv[level], P); if (b < n) break; b -= n; }
     const LevelInfo L = d.geom.lv[level];
-    const int w = L.w, h = L.h, tnx = (w + DV_TW - 1) / DV_TW;
-    const int ty = t / tnx, x0 = (t - ty * tnx) * DV_TW, y0 = ty * DV_TH;
-    if (y0 >= h) return;                                             // (the grid is the exact tile count: never taken)
+    const int w = L.w, h = L.h, nv = deriv_vectors(L, P);
+    const int i = b * 256 + threadIdx.x, g = i / nv, x = (i - g * nv) * DV_VEC - (P & 7), y0 = g * DV_ROWS;
+    if (y0 >= h) return;
     const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y, slot = pyr_slot(d.st[seq], target);
-    const uint8_t* __restrict__ img = d.pyr + pyr_index(d, seq, slot, cam) + L.off;
-    for (int i = threadIdx.x; i < (DV_TH + 2) * TDW; i += 256) {
-        const int r = i / TDW, c = i - r * TDW, y = y0 - 1 + r, x = x0 - 4 + 4 * c;
-        // rows -1 .. h and bytes -4 .. w + 6 are inside the stored border (pad >= 8); nothing beyond them is needed
-        tile[r][c] = (y <= h && x < w + 4) ? *reinterpret_cast<const unsigned*>(img + (ptrdiff_t)y * L.stride + x) : 0u;
-    }
-    __syncthreads();
-    const int cx = threadIdx.x & (DV_TW / 4 - 1), ry = threadIdx.x / (DV_TW / 4), x = x0 + 4 * cx, y = y0 + ry;
-    if (y >= h || x >= w) return;
-    int t0[6], t1[6];                                                // columns x - 1 .. x + 4
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-        int s[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const unsigned v = c == 0 ? tile[ry + r][cx] >> 24 : c == 5 ? tile[ry + r][cx + 2] : tile[ry + r][cx + 1] >> (8 * (c - 1));
-            s[r] = (int)(v & 0xFFu);
-        }
-        t0[c] = 12 * (s[0] + s[2]) + 40 * s[1];
-        t1[c] = s[2] - s[0];
-    }
-    int ix[4], iy[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) { ix[j] = t0[j + 2] - t0[j]; iy[j] = 12 * (t1[j] + t1[j + 2]) + 40 * t1[j + 1]; }
-    int16_t* __restrict__ px = d.deriv + deriv_index(d, seq, slot, cam) + (L.off - deriv_origin(d.geom)) + (ptrdiff_t)y * L.stride + x;
-    int16_t* __restrict__ py = px + deriv_samples(d.geom);
-    const auto pair = [](int lo, int hi) { return ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16); };
-    const int n = w - x;                                             // samples of this thread inside the level (>= 1)
-    if (n >= 4) {
-        *reinterpret_cast<uint2*>(px) = make_uint2(pair(ix[0], ix[1]), pair(ix[2], ix[3]));
-        *reinterpret_cast<uint2*>(py) = make_uint2(pair(iy[0], iy[1]), pair(iy[2], iy[3]));
-    } else {
-        if (n >= 2) { *reinterpret_cast<unsigned*>(px) = pair(ix[0], ix[1]); *reinterpret_cast<unsigned*>(py) = pair(iy[0], iy[1]); }
-        if (n == 1) { px[0] = (int16_t)ix[0]; py[0] = (int16_t)iy[0]; }
-        if (n == 3) { px[2] = (int16_t)ix[2]; py[2] = (int16_t)iy[2]; }
+    // one uniform base per array and 32-bit offsets beside it (a pyramid is far below 4 GB): two registers where three pointers took six
+    const uint8_t* __restrict__ img = d.pyr + pyr_index(d, seq, slot, cam);
+    int16_t* __restrict__ dx = d.deriv + deriv_index(d, seq, slot, cam);
+    int16_t* __restrict__ dy = dx + deriv_samples(d.geom);
+    unsigned io = (unsigned)(L.off + (y0 - 1) * L.stride + x), so = (unsigned)(L.off - deriv_origin(d.geom) + y0 * L.stride + x);
+    const bool right = x + DV_VEC <= w;                              // column x + 8 is the neighbour of a sample inside the level
+    const int rows = h - y0 < DV_ROWS ? h - y0 : DV_ROWS;
+    DerivRow ra = deriv_load_row(img + io, right), rb = deriv_load_row(img + (io + L.stride), right);
+    io += 2 * L.stride;
+#pragma unroll 1
+    for (int r = 0; r < rows; r++) {
+        const DerivRow rc = deriv_load_row(img + io, right);
+        unsigned ix[DV_VEC / 2], iy[DV_VEC / 2];
+        dv_s2 t0p, t1p;
+        deriv_step<0>(ra, rb, rc, t0p, t1p, ix, iy); deriv_step<1>(ra, rb, rc, t0p, t1p, ix, iy); deriv_step<2>(ra, rb, rc, t0p, t1p, ix, iy);
+        deriv_step<3>(ra, rb, rc, t0p, t1p, ix, iy); deriv_step<4>(ra, rb, rc, t0p, t1p, ix, iy);
+        deriv_store(dx + so, ix, x, w);
+        deriv_store(dy + so, iy, x, w);
+        ra = rb; rb = rc;
+        io += L.stride; so += L.stride;
     }
 }
 static void launch_deriv_levels(const DevBuffers& d, hipStream_t st, PyrTarget target) {
     if (!d.deriv || d.geom.nlevels < 2) return;
-    int tiles = 0;
-    for (int l = 1; l < d.geom.nlevels; l++) tiles += deriv_tiles(d.geom.lv[l]);
-    hipLaunchKernelGGL(k_deriv_levels, dim3(tiles, 2, launch_seqs(d)), dim3(256), 0, st, d, target);
+    int blocks = 0;
+    for (int l = 1; l < d.geom.nlevels; l++) blocks += deriv_blocks(d.geom.lv[l], d.geom.pad);
+    hipLaunchKernelGGL(k_deriv_levels, dim3(blocks, 2, launch_seqs(d)), dim3(256), 0, st, d, target);
 }
 
 // levels first .. nlevels-1 from level first-1: pairs of levels per launch where two remain
@@ -1082,6 +1117,144 @@ __global__ __launch_bounds__(256) void k_fast(DevBuffers d, int pass, int thresh
 // one packed image -> score map (stage API)
 __global__ __launch_bounds__(256) void k_fast_score_map(const uint8_t* img, int w, int h, int threshold, uint8_t* score) {
     fast_tile(img, w, w, h, blockIdx.x * FT_W, blockIdx.y * FT_H, threshold, ScoreMapSink{score, w});
+}
+
+// ---- FAST pass 0 of a plain many-sequence context (no masks, no ids, one feature per bucket): k_fast_batch.  The same tile steps
+// as fast_tile with the same pixel rules — same candidates, same scores, same survivors, same keys — re-shaped for a thousand
+// images per launch, where the tiles' turnover is the cost:
+//  - a 64 x 32 tile: the 4-pixel halo is 41 % on top of the tile instead of 69 %, and a tile queues ~160 candidates, so the
+//    scoring rounds run on two or three full waves instead of one wave and a quarter;
+//  - screening takes FOUR pixels per lane from five LDS dwords (the dword of the pixels, its two neighbours, the rows 3 above and
+//    below) instead of five byte reads per pixel, and a wave queues its candidates with a ballot and ONE LDS add;
+//  - NMS visits the queued candidates only: no other pixel can have a score, and the bucket sink ignores a pixel that is not kept;
+//  - the score runs on 16-bit pairs (fast_score_pk): the same integers from a sixth of the instructions.
+// fast_score on packed pairs.  With d[k] = v - circle[k], a pixel is a corner iff some 9-arc has all d > t (run9 of the "darker" mask)
+// or all d < -t (the "brighter" mask), i.e. iff  A = max_k min_{j<9} d[k+j] > t  or  B = min_k max_{j<9} d[k+j] < -t,  and
+// fast_score's result is max(max(t, A), -min(-t, B)) - 1: the masks and the score are one computation.  Register k holds the pair
+// (d[k], d[k+8]), so the pair of index k + 8 is register k with its halves swapped and the windows starting at k and at k + 8
+// slide together: windows of 2, 4, 8 by doubling, the ninth element last — 32 v_pk_min and 32 v_pk_max for all sixteen arcs
+// (fast_score: 16 x 8 of each, after 64 instructions of mask building).  |d| <= 255: exact in 16 bits.
+typedef short fs_s2 __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ fs_s2 fs_swap(fs_s2 a) { return __builtin_shufflevector(a, a, 1, 0); }
+template <bool MAX> static __device__ __forceinline__ fs_s2 fs_pick(fs_s2 a, fs_s2 b) { return MAX ? __builtin_elementwise_max(a, b) : __builtin_elementwise_min(a, b); }
+// windows of 2 S from windows of S: out[k] = pick(in[k], in[k + S]), indices 8 .. 15 being the swapped registers 0 .. 7
+template <bool MAX, int S>
+static __device__ __forceinline__ void fs_double(const fs_s2 (&in)[8], fs_s2 (&out)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) out[k] = fs_pick<MAX>(in[k], k + S < 8 ? in[k + S] : fs_swap(in[k + S - 8]));
+}
+template <bool MAX>
+static __device__ __forceinline__ int fs_arcs(const fs_s2 (&d)[8]) {   // MAX = false: A above; true: B
+    fs_s2 a[8], b[8];
+    fs_double<MAX, 1>(d, a); fs_double<MAX, 2>(a, b); fs_double<MAX, 4>(b, a);
+#pragma unroll
+    for (int k = 0; k < 8; k++) a[k] = fs_pick<MAX>(a[k], fs_swap(d[k]));          // the ninth element: d[k + 8]
+    fs_s2 r = a[0];
+#pragma unroll
+    for (int k = 1; k < 8; k++) r = fs_pick<!MAX>(r, a[k]);
+    return MAX ? (r.x < r.y ? r.x : r.y) : (r.x > r.y ? r.x : r.y);
+}
+static __device__ __forceinline__ int fast_score_pk(const uint8_t (*pix)[FT_PW + 4], int py, int px, int t) {
+    constexpr int cdx[16] = CIRC_DX, cdy[16] = CIRC_DY;
+    const short v = pix[py][px];
+    fs_s2 d[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = fs_s2{v, v} - fs_s2{(short)pix[py + cdy[k]][px + cdx[k]], (short)pix[py + cdy[k + 8]][px + cdx[k + 8]]};
+    const int A = fs_arcs<false>(d), B = fs_arcs<true>(d);
+    if (A <= t && B >= -t) return 0;
+    const int best = A > t ? A : t, worst = B < -t ? B : -t;
+    return (best > -worst ? best : -worst) - 1;
+}
+#define FB_W 64
+#define FB_H 32
+#define FB_PH (FB_H + 8)
+#define FB_SH (FB_H + 2)
+static_assert(FB_W == FT_W, "fast_score reads rows of FT_PW + 4 bytes");
+static __device__ __forceinline__ void fast_tile_batch(const uint8_t* img, int istride, int W, int H, int x0, int y0, int threshold, const BucketSink& sink) {
+    __shared__ __attribute__((aligned(4))) uint8_t pix[FB_PH][FT_PW + 4];
+    __shared__ __attribute__((aligned(4))) uint8_t sc[FB_SH][FT_SW + 2];
+    __shared__ unsigned short cand[FB_SH * FT_SW];
+    __shared__ int ncand;
+    constexpr int DPR = FT_PW / 4;                                    // dwords of a pixel row
+    if (threshold < 0) threshold = 0;
+    if (threshold > 255) threshold = 255;
+    if (x0 >= 4 && y0 >= 4 && x0 - 4 + FT_PW <= W && y0 - 4 + FB_PH <= H) {
+        for (int i = threadIdx.x; i < DPR * FB_PH; i += 256) {
+            const int py = i / DPR, c = i - py * DPR;
+            *reinterpret_cast<unsigned*>(&pix[py][4 * c]) = reinterpret_cast<const UD*>(img + (size_t)(y0 - 4 + py) * istride + (x0 - 4) + 4 * c)->v;
+        }
+    } else {
+        for (int i = threadIdx.x; i < FB_PH * FT_PW; i += 256) {
+            const int py = i / FT_PW, px = i - py * FT_PW;
+            const int gx = x0 - 4 + px, gy = y0 - 4 + py;
+            pix[py][px] = (gx >= 0 && gx < W && gy >= 0 && gy < H) ? img[(size_t)gy * istride + gx] : (uint8_t)0;
+        }
+    }
+    static_assert(sizeof(sc) % 4 == 0, "the score tile is cleared a dword at a time");
+    for (int i = threadIdx.x; i < (int)sizeof(sc) / 4; i += 256) reinterpret_cast<unsigned*>(&sc[0][0])[i] = 0u;
+    if (threadIdx.x == 0) ncand = 0;
+    __syncthreads();
+    // Screening (fast_tile's rule).  Lane item (sy, c): the four pixels of dword c of pixel row sy + 3, i.e. score-tile columns
+    // sx = 4 c - 3 .. 4 c; every lane of a wave takes part in the ballots, also where its item or its pixels lie outside.
+    const int lane = threadIdx.x & 63;
+    for (int base = 0; base < FB_SH * DPR; base += 256) {
+        const int i = base + threadIdx.x, sy = i / DPR, c = i - sy * DPR;
+        bool pass[4] = {false, false, false, false};
+        if (i < FB_SH * DPR) {
+            const int gy = y0 - 1 + sy;
+            const unsigned* row = reinterpret_cast<const unsigned*>(&pix[sy + 3][0]);
+            const unsigned ctr = row[c], prv = c > 0 ? row[c - 1] : 0u, nxt = row[c + 1];                    // (row[DPR] is the row's padding: read, never used)
+            const unsigned lft = __builtin_amdgcn_alignbyte(ctr, prv, 1), rgt = __builtin_amdgcn_alignbyte(nxt, ctr, 3);   // the pixels 3 to the left / right of the four
+            const unsigned dn = reinterpret_cast<const unsigned*>(&pix[sy + 6][0])[c], up = reinterpret_cast<const unsigned*>(&pix[sy][0])[c];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int sx = 4 * c - 3 + j, gx = x0 - 1 + sx;
+                if (sx >= 0 && sx < FT_SW && gx >= 3 && gx < W - 3 && gy >= 3 && gy < H - 3) {
+                    const int v = (ctr >> (8 * j)) & 255, lo = v - threshold, hi = v + threshold;
+                    const int a = (dn >> (8 * j)) & 255, b = (up >> (8 * j)) & 255, cc = (rgt >> (8 * j)) & 255, e = (lft >> (8 * j)) & 255;   // circle 0, 8, 4, 12
+                    const bool dark = (a < lo || b < lo) && (cc < lo || e < lo);
+                    const bool bright = (a > hi || b > hi) && (cc > hi || e > hi);
+                    pass[j] = dark || bright;
+                }
+            }
+        }
+        unsigned long long m[4];
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { m[j] = __ballot(pass[j]); n += __popcll(m[j]); }
+        if (n == 0) continue;                                         // wave-uniform
+        int at = 0;
+        if (lane == 0) at = atomicAdd(&ncand, n);
+        at = __shfl(at, 0);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (pass[j]) cand[at + __popcll(m[j] & ((1ull << lane) - 1ull))] = (unsigned short)(sy * FT_SW + 4 * c - 3 + j);
+            at += __popcll(m[j]);
+        }
+    }
+    __syncthreads();
+    const int nc = __builtin_amdgcn_readfirstlane(ncand);           // block-uniform: a scalar register
+    for (int k = threadIdx.x; k < nc; k += 256) {
+        const int i = cand[k], sy = i / FT_SW, sx = i - sy * FT_SW;
+        sc[sy][sx] = (uint8_t)fast_score_pk(pix, sy + 3, sx + 3, threshold);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < nc; k += 256) {
+        const int i = cand[k], sy = i / FT_SW, sx = i - sy * FT_SW;
+        const int gx = x0 + sx - 1, gy = y0 + sy - 1;
+        if (sx < 1 || sx > FB_W || sy < 1 || sy > FB_H || gx >= W || gy >= H) continue;   // the ring around the tile: a neighbour's pixel
+        const int s = sc[sy][sx];
+        const bool keep = s != 0 &&
+                          s > sc[sy][sx - 1] && s > sc[sy][sx + 1] &&
+                          s > sc[sy - 1][sx - 1] && s > sc[sy - 1][sx] && s > sc[sy - 1][sx + 1] &&
+                          s > sc[sy + 1][sx - 1] && s > sc[sy + 1][sx] && s > sc[sy + 1][sx + 1];
+        sink(gx, gy, s, keep);
+    }
+}
+__global__ __launch_bounds__(256) void k_fast_batch(DevBuffers d, int pass, int threshold) {
+    FastFrame f;
+    if (!fast_frame_begin(d, pass, blockIdx.z, true, (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x, gridDim.x * gridDim.y * 256, f)) return;
+    fast_tile_batch(f.img, f.istride, d.geom.W, d.geom.H, blockIdx.x * FB_W, blockIdx.y * FB_H, threshold, BucketSink{d, f.seq, pass});
 }
 
 // The SECOND detection pass of a many-sequence context: launched every frame, needed by a sequence that kept < 100 features (vo.cpp:327)
@@ -1486,7 +1659,9 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
         hipLaunchKernelGGL(k_bucket_emit_strided, dim3(EMIT_STRIDED_BLOCKS, g.z), dim3(EMIT_THREADS), 0, st, d, pass, d.cfg.buckets_along_height);
         return;
     }
-    hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, d, pass, th);
+    // pass 0 of a many-sequence context: the batch tile (this launcher serves the contexts without masks and without ids)
+    if (d.B > SVO_LONE_MAX_SEQ) hipLaunchKernelGGL(k_fast_batch, dim3(g.x, (d.geom.H + FB_H - 1) / FB_H, g.z), dim3(256), 0, st, d, pass, th);
+    else hipLaunchKernelGGL(k_fast<0>, g, dim3(256), 0, st, d, pass, th);
     hipLaunchKernelGGL(k_bucket_emit, dim3(d.cfg.buckets_along_height, g.z), dim3(EMIT_THREADS), 0, st, d, pass);
 }
 
