@@ -759,6 +759,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     int n_act, rc;
     if ((rc = fill_slot_rows(c, slot, left_dev, right_dev, active, &n_act)) != SVO_OK) return rc;
     // LK grid sized from the last feature counts the host has seen (+30 %); the kernel strides, so an underestimate is only slower
+    // (tests/test_gpu_count_seams.py, case D: 1025 features on the grid a hint of 20 gives, also in flight and re-captured)
     int gn = c->lk_grid;
     if (c->lk_hint > 0) {
         int h = c->lk_hint + c->lk_hint / 3 + 64;
