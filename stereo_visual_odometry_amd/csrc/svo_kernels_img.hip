@@ -4,6 +4,7 @@
 // Behaviour follows the reference call sites (cited per kernel); the arithmetic of the OpenCV
 // functions they call is restated independently, not translated.
 #include "svo_internal.hpp"
+#include "svo_pyr_walk.hpp"
 #include <type_traits>
 
 // cv::borderInterpolate(i, n, BORDER_REFLECT_101) for any i: reflect about the first and the last pixel until i lies inside (the
@@ -673,9 +674,53 @@ static __device__ __forceinline__ void pyrdown2_body(const DevBuffers& d, int le
 }
 __global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, PyrTarget target) { pyrdown2_body(d, level, target, blockIdx.x, blockIdx.y, blockIdx.z); }
 
+// k_pyr_walk: one pyrDown level without LDS, for the plain many-sequence contexts (pyr_walk_applies).  A thread owns PW_VEC = 8
+// consecutive outputs of a destination row — one aligned 8-byte store — and walks PW_ROWS rows down (svo_pyr_walk.hpp: the plan and
+// the walk, which a host program runs too).  Per destination row it loads the 20 source bytes of two new source rows (from column
+// 2 x0 - 2: the six aligned dwords around them, shifted into place — loading them as they lie, 16 unaligned bytes and a dword,
+// measured the same), runs the horizontal 1-4-6-4-1 pass on 16-bit pairs (v_perm picks the taps of two outputs, v_pk_* sums them:
+// <= 16 * 255) and adds the row into two running column sums instead of keeping five rows: with e = row 2y + 2 and o = row 2y + 1,
+//   out(y) = (A + 4 o + e + 128) >> 8,   A' = B + 4 o + 6 e,   B' = e            (A = rows 2y-2, 2y-1, 2y weighted 1 4 6; B = row 2y)
+// — the same integers as the five-tap sum (<= 256 * 255 + 128: they fit the 16-bit lanes), eight registers of state.
+// Source rows outside the level are the reflected rows (a row offset, no other cost).  The first vector of a row and the last one
+// to three, whose loads would leave the row, take the edge form: every dword from the nearest place inside the row, its bytes
+// folded into place by one v_perm — as cheap as the fast form, which matters: a first version that fetched their reflected bytes
+// one by one took 780 us per 512 sequences where this one takes 420.
+// INGEST: the source is the caller's image (k_ingest_pyr1's job): the thread also stores the level-0 bytes 2 x0 .. 2 x0 + 15 of
+// every source row it is the first to load (rows 2y + 1 and 2y + 2 of its destination rows, row 0 in the first group) from the
+// dwords it holds — 16 bytes at a 4-byte aligned address — and the launch runs the reset duty of ingest_slot.  It walks 16 rows
+// (8 measured 498 us, 16 419 us; the levels >= 2 are as fast with 8).  No byte outside the h rows of w bytes of the caller's image
+// is ever loaded, whatever its stride or alignment: svo_pyr_walk.hpp's plan, checked on the host (tests/test_pyr_walk_cases.py).
+template <bool INGEST>
+__global__ __launch_bounds__(256) void k_pyr_walk(DevBuffers d, const uint8_t* const* srcs, int stride, int level, PyrTarget target) {
+    const int seq = seq_of(d, blockIdx.z), cam = blockIdx.y;
+    const int slot = INGEST ? ingest_slot(d, seq, target, blockIdx.x == 0 && cam == 0 && threadIdx.x == 0) : pyr_slot(d.st[seq], target);
+    const LevelInfo ls = d.geom.lv[level - 1], ld = d.geom.lv[level];
+    const PwPlan p = pw_plan(ls.w, ls.h, d.geom.pad, INGEST ? PW_ROWS_INGEST : PW_ROWS);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pw_items(p)) return;
+    const PwItem it = pw_item(p, i);
+    uint8_t* base = d.pyr + pyr_index(d, seq, slot, cam);
+    const uint8_t* src = INGEST ? srcs[cam * d.B + seq] : base + ls.off;
+    const int ss = INGEST ? stride : ls.stride, rows = pw_item_rows(p, it);
+    if (it.mode == PW_FAST) pw_walk<INGEST, PW_FAST>(src, ss, ls.w, ls.h, base + ls.off, ls.stride, base + ld.off, ld.stride, ld.w, it.x0, it.y0, rows);
+    else if (it.mode == PW_EDGE) pw_walk<INGEST, PW_EDGE>(src, ss, ls.w, ls.h, base + ls.off, ls.stride, base + ld.off, ld.stride, ld.w, it.x0, it.y0, rows);
+    else pw_walk<INGEST, PW_TINY>(src, ss, ls.w, ls.h, base + ls.off, ls.stride, base + ld.off, ld.stride, ld.w, it.x0, it.y0, rows);
+}
+// SVO_PYR_WALK=0 (read once per process) keeps the LDS-tiled kernels for these contexts too: the A/B switch
+static bool pyr_walk_applies(const DevBuffers& d) {
+    static const bool off = getenv("SVO_PYR_WALK") && atoi(getenv("SVO_PYR_WALK")) == 0;
+    return !off && d.B > SVO_LONE_MAX_SEQ && d.CN == 1 && d.in.bpp <= 1 && !d.rmap;
+}
+template <bool INGEST>
+static void launch_pyr_walk(const DevBuffers& d, const uint8_t* const* ptrs, int stride, int level, PyrTarget target, hipStream_t st) {
+    const PwPlan p = pw_plan(d.geom.lv[level - 1].w, d.geom.lv[level - 1].h, d.geom.pad, INGEST ? PW_ROWS_INGEST : PW_ROWS);
+    hipLaunchKernelGGL((k_pyr_walk<INGEST>), dim3((pw_items(p) + 255) / 256, 2, launch_seqs(d)), dim3(256), 0, st, d, ptrs, stride, level, target);
+}
+
 // k_pad_pyramid: the REFLECT_101 border of every level of the target's slot — what cv::buildOpticalFlowPyramid's copyMakeBorder leaves
 // around each level (pyrBorder = BORDER_REFLECT_101).  Pixel (x, y) outside the level takes level(reflect101(y), reflect101(x)), the
-// iterated borderInterpolate rule over the whole pad, also where the pad is wider than the level.  One thread per border DWORD (row
+// iterated borderInterpolate rule over the whole pad, also where the pad is wider than the level.  The border is written in DWORDS (row
 // starts, the pad and pixel (0, 0) are 4-byte aligned): the ring of a level is cut into its top and bottom bands (pad rows of the
 // padded width) and, per image row, the left band and the right band — the latter from the aligned x at or below the level's width,
 // so up to three pixels of the level itself are rewritten with their own values.
@@ -683,40 +728,54 @@ __global__ __launch_bounds__(256) void k_pyrdown2(DevBuffers d, int level, PyrTa
 // where a dword straddles a fold of a level narrower than the pad: those go byte by byte.  (First version: one thread, one byte
 // load and one byte store per border pixel — 0.39 ms per 512 sequences; the image stream's kernels run in the gap between two LK
 // launches, so their time is whole-job time.)
-// The grid walks ONE list of the border dwords of all levels (blockIdx.x, in level order; a block stays inside one level), a dword
-// per thread: every block has a full share, whatever the size of its level.  (Before: 64 blocks per level striding over its ring —
-// at the three small levels most of them found nothing to do.)
-__host__ __device__ inline int pad_dwords(const LevelInfo& L, int P) {
-    return 2 * P * ((L.w + 2 * P + 3) >> 2) + L.h * ((P >> 2) + ((L.w + P - (L.w & ~3) + 3) >> 2));
+// (Second version: one thread per border DWORD of one flat list over all levels — 0.26 ms: two divisions and five folds per dword.)
+// Now by rows.  The dwords written and their values are the same; what changed is who computes them:
+// - top and bottom bands over the level's own columns: band row y there IS row reflect101(y) of the level, at the same alignment,
+//   so a thread copies an aligned 16 bytes (columns xa + 16 c .. + 15, xa = the first 16-byte boundary at or behind pixel 0): one
+//   division per 16 bytes and no fold but the row's;
+// - everything left and right of that — the left and right bands of the image rows, and in the band rows the corners with the few
+//   columns the 16-byte copies leave — PAD_LANES = 8 consecutive threads per row and side: they fold their row once and take the
+//   side's dwords in turn (a band of 28 pixels is 7 or 8 dwords: one round; consecutive lanes store consecutive dwords).  A dword
+//   whose four source bytes lie one fold out is one unaligned load and a byte swap, one inside the level an aligned load; only a
+//   dword that straddles an edge or lies more than one fold out (levels narrower than the pad) folds byte by byte, as before.
+// The grid walks ONE list of the work items of all levels (blockIdx.x, in level order; a block stays inside one level): the sides
+// of all h + 2 pad rows first, then the copies — every block has a full share, whatever the size of its level.
+#define PAD_LANES 4
+__host__ __device__ inline int pad_xa(int P) { return (16 - (P & 15)) & 15; }
+__host__ __device__ inline int pad_chunks(const LevelInfo& L, int P) { return L.w > pad_xa(P) ? (L.w - pad_xa(P)) >> 4 : 0; }
+__host__ __device__ inline int pad_items(const LevelInfo& L, int P) { return 2 * PAD_LANES * (L.h + 2 * P) + 2 * P * pad_chunks(L, P); }
+// the border dword at columns x .. x + 3 (x a multiple of 4, anywhere) of a row whose level pixels start at srow
+__device__ __forceinline__ unsigned pad_dword(const uint8_t* __restrict__ srow, int x, int w) {
+    if (x >= 0 && x + 3 < w) return *reinterpret_cast<const unsigned*>(srow + x);
+    if (x + 3 < 0 && -x < w) return __builtin_bswap32(reinterpret_cast<const UD*>(srow - x - 3)->v);                 // columns -x, -x - 1, ..
+    if (x >= w && 2 * w - 5 - x >= 0) return __builtin_bswap32(reinterpret_cast<const UD*>(srow + (2 * w - 5 - x))->v);   // 2 w - 2 - x, ..
+    return (unsigned)srow[reflect101(x, w)] | ((unsigned)srow[reflect101(x + 1, w)] << 8) | ((unsigned)srow[reflect101(x + 2, w)] << 16) | ((unsigned)srow[reflect101(x + 3, w)] << 24);
 }
 __global__ __launch_bounds__(256) void k_pad_pyramid(DevBuffers d, PyrTarget target) {
     const int plane = blockIdx.z % d.CN, sc = blockIdx.z / d.CN;
     const int seq = seq_of(d, sc / 2), cam = sc & 1, P = d.geom.pad;
     int level = 0, blk = blockIdx.x;
-    for (; level + 1 < d.geom.nlevels; level++) { const int n = (pad_dwords(d.geom.lv[level], P) + 255) >> 8; if (blk < n) break; blk -= n; }
+    for (; level + 1 < d.geom.nlevels; level++) { const int n = (pad_items(d.geom.lv[level], P) + 255) >> 8; if (blk < n) break; blk -= n; }
     const LevelInfo L = d.geom.lv[level];
     const int w = L.w, h = L.h;
     uint8_t* img = d.pyr + pyr_index(d, seq, pyr_slot(d.st[seq], target), cam) + (size_t)plane * d.geom.pyr_bytes + L.off;
-    const int rowdw = (w + 2 * P + 3) >> 2;                       // dwords of a band row, from x = -P (the last one may reach into the row's stride padding)
-    const int xr0 = w & ~3, ldw = P >> 2, sdw = ldw + ((w + P - xr0 + 3) >> 2);   // left + right dwords of an image row
-    const int band = P * rowdw, total = 2 * band + h * sdw;
+    const int nside = 2 * PAD_LANES * (h + 2 * P), nch = pad_chunks(L, P), xa = pad_xa(P), xb = xa + 16 * nch;
     const int i = blk * 256 + threadIdx.x;
-    if (i < total) {
-        int x, y;
-        if (i < 2 * band) { const int j = i < band ? i : i - band, r = j / rowdw; x = (j - r * rowdw) * 4 - P; y = i < band ? r - P : h + r; }
-        else { const int j = i - 2 * band; y = j / sdw; const int k = j - y * sdw; x = k < ldw ? 4 * k - P : xr0 + 4 * (k - ldw); }
-        const uint8_t* srow = img + (size_t)reflect101(y, h) * L.stride;
-        const int s0 = reflect101(x, w), s1 = reflect101(x + 1, w), s2 = reflect101(x + 2, w), s3 = reflect101(x + 3, w);
-        unsigned v;
-        if (s1 == s0 + 1 && s2 == s0 + 2 && s3 == s0 + 3) v = reinterpret_cast<const UD*>(srow + s0)->v;
-        else if (s1 == s0 - 1 && s2 == s0 - 2 && s3 == s0 - 3) v = __builtin_bswap32(reinterpret_cast<const UD*>(srow + s3)->v);
-        else v = (unsigned)srow[s0] | ((unsigned)srow[s1] << 8) | ((unsigned)srow[s2] << 16) | ((unsigned)srow[s3] << 24);
-        *reinterpret_cast<unsigned*>(img + (ptrdiff_t)y * L.stride + x) = v;
+    if (i < nside) {
+        const int rs = i / PAD_LANES, y = (rs >> 1) - P;
+        const bool right = rs & 1, band = y < 0 || y >= h;
+        const uint8_t* srow = img + reflect101(y, h) * L.stride;
+        uint8_t* drow = img + y * L.stride;
+        const int xe = right ? P + ((w + 3) & ~3) : band ? xa : 0;       // the last dword of a row may reach into its stride padding
+        for (int x = (right ? (band ? xb : w & ~3) : -P) + 4 * (i % PAD_LANES); x < xe; x += 4 * PAD_LANES) *reinterpret_cast<unsigned*>(drow + x) = pad_dword(srow, x, w);
+    } else if (i < nside + 2 * P * nch) {
+        const int j = i - nside, r = j / nch, x = xa + 16 * (j - r * nch), y = r < P ? r - P : h + r - P;
+        *reinterpret_cast<uint4*>(img + y * L.stride + x) = *reinterpret_cast<const uint4*>(img + reflect101(y, h) * L.stride + x);
     }
 }
 static void launch_pad_pyramid(const DevBuffers& d, hipStream_t st, PyrTarget target) {
     int blocks = 0;
-    for (int l = 0; l < d.geom.nlevels; l++) blocks += (pad_dwords(d.geom.lv[l], d.geom.pad) + 255) >> 8;
+    for (int l = 0; l < d.geom.nlevels; l++) blocks += (pad_items(d.geom.lv[l], d.geom.pad) + 255) >> 8;
     hipLaunchKernelGGL(k_pad_pyramid, dim3(blocks, 1, launch_seqs(d) * 2 * d.CN), dim3(256), 0, st, d, target);
 }
 
@@ -815,6 +874,10 @@ static void launch_deriv_levels(const DevBuffers& d, hipStream_t st, PyrTarget t
 
 // levels first .. nlevels-1 from level first-1: pairs of levels per launch where two remain
 static void launch_pyramid_from(const DevBuffers& d, int first, hipStream_t st, PyrTarget target) {
+    if (pyr_walk_applies(d)) {                                       // level by level: one more small launch, no LDS
+        for (int l = first; l < d.geom.nlevels; l++) launch_pyr_walk<false>(d, nullptr, 0, l, target, st);
+        return;
+    }
     int l = first;
     while (l < d.geom.nlevels) {
         if (l + 1 < d.geom.nlevels) {
@@ -859,7 +922,8 @@ void launch_ingest_pyramid(const DevBuffers& d, const uint8_t* const* left_right
     if (target == PYR_NEXT) hipLaunchKernelGGL(k_pick_next, dim3((launch_seqs(d) + 63) / 64), dim3(64), 0, st, d);
     const PyrTarget rest = target == PYR_BEGIN ? PYR_T1 : target;
     if (d.CN == 1 && d.geom.nlevels >= 2) {
-        launch_ingest_pyr1(d, left_right_dev_ptrs, stride, target, st);
+        if (pyr_walk_applies(d)) launch_pyr_walk<true>(d, left_right_dev_ptrs, stride, 1, target, st);
+        else launch_ingest_pyr1(d, left_right_dev_ptrs, stride, target, st);
         launch_pyramid_from(d, 2, st, rest);
     } else {
         launch_ingest(d, left_right_dev_ptrs, stride, target, st);
