@@ -167,6 +167,7 @@ int svo_get_lk_registers_left(svo_context* ctx);
 #define SVO_PATH_CLAHE          512  /* the frame's images were equalised (two launches) in front of its ingest (svo_set_clahe; also set by svo_clahe) */
 #define SVO_PATH_DETECT_MASKED  256  /* the frame's detection applied a detection mask (svo_set_detection_mask; also set by svo_append_features_from_image_masked) */
 #define SVO_PATH_TRACK_IDS    1024   /* the frame carried track ids and wrote its observation rows (svo_set_track_output) */
+#define SVO_PATH_MOTION_PRIOR 2048   /* some active sequence of the frame used a motion prior: k_lk_chain_prior ran in k_lk_chain's place (svo_set_motion_prior) */
 int svo_get_last_frame_path(svo_context* ctx);
 
 int svo_submit_batch(svo_context* ctx, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride);
@@ -458,6 +459,58 @@ int svo_get_feature_ids(svo_context* ctx, int seq, int cap, int64_t* ids);
  * one) to out (width * height bytes, packed; may be NULL), *present = whether there is one.  Synchronises the context's stream. */
 int svo_set_detection_mask(svo_context* ctx, int seq, const uint8_t* mask, int stride, int on_device);
 int svo_get_detection_mask(svo_context* ctx, int seq, uint8_t* out /* W*H, packed */, int* present);
+/* ---- Motion prior: seed the temporal LK passes with a predicted flow ---------------------------------------------------------
+ * What OpenCV users get from OPTFLOW_USE_INITIAL_FLOW, fed from a gyro, a wheel model or the previous pose.  The reference calls
+ * calcOpticalFlowPyrLK with flags = 0 and has none, so this is off by default: a context that never sets a prior launches exactly
+ * what it always did.  Both temporal passes of circularMatching (L0 -> L1 and R1 -> R0) otherwise start their search at the
+ * feature's own position; in a turn every feature moves by fx tan(yaw step) pixels and the pyramid runs out of reach.
+ *
+ * A prior is a 3x3 homography H (f32, row-major) that maps pixel coordinates in the sequence's previous frame (T0) to predicted
+ * pixel coordinates in the frame being submitted (T1).  The rectified cameras share K, so one H serves both cameras; its inverse Hi
+ * serves the backward pass.
+ *
+ * Prediction pred(M, (x, y)), M = m0 .. m8.  Every operation is f32 and rounded once, nothing is fused, division is IEEE:
+ *   X = (m0 x + m1 y) + m2,   Y = (m3 x + m4 y) + m5,   D = (m6 x + m7 y) + m8.
+ *   If D > 0 and X / D, Y / D are both finite the guess is (X / D, Y / D); otherwise it is (x, y) (a NaN anywhere ends here).
+ *
+ * LK with a guess (OPTFLOW_USE_INITIAL_FLOW): at the top level nextPt = guess * 2^-top instead of prevPt * 2^-top.  The template
+ * still comes from prevPt, and every test, rule and counter of the pass is otherwise unchanged: guess == prevPt gives the bits of
+ * the pass without a guess.
+ *
+ * Circular matching with a prior: pass 0 (L0 -> L1) starts from pred(H, pl0), pass 2 (R1 -> R0) from pred(Hi, pr1); passes 1 and 3
+ * (the stereo passes) start as always.  Masks, early-out, bounds tests, the loop-closure threshold and the work counters are unchanged.
+ *
+ * Hi when the caller passes none: the adjugate of H widened to f64 (each cofactor a d - b c in f64), divided by
+ * det = h0 C00 + h1 C01 + h2 C02, each entry rounded to f32.  A det that is 0 or not finite is SVO_ERR_ARG.
+ *
+ * Scope.  A prior is one-shot and per sequence: it belongs to the next frame that sequence takes and is consumed by it.  An idle
+ * frame of a masked submit does not consume it.  A frame without a prior for a sequence tracks that sequence exactly as without
+ * the feature, bit for bit, also when other sequences of the same launch have one.  svo_reset_sequence drops a pending prior.
+ *
+ * Ordering.  The setters are host state plus, per frame, one small copy on the frame's stream from a pinned block of its
+ * results-ring slot: stream-ordered, no host synchronisation, legal with frames in flight — every frame carries its own priors, as
+ * it carries its input format.  A frame in which some active sequence has a prior launches k_lk_chain_prior where it would launch
+ * k_lk_chain, reports SVO_PATH_MOTION_PRIOR, and under SVO_GRAPH=1 runs from the launch list, as masked frames do.
+ *
+ * SVO_ERR_ARG: a channels = 3 context, an lk_float_sums = 1 context (that mode exists to reproduce the reference's recording, which
+ * has no prior), seq out of range, a non-finite entry, a singular H with Hi = NULL.  svo_circular_matching (the member form) returns
+ * SVO_ERR_STATE while a prior is pending.
+ *
+ * svo_set_motion_prior: seq = -1 sets every sequence; H = NULL clears a pending prior (Hi is not looked at); Hi = NULL makes the
+ * library invert H as above.
+ * svo_set_motion_priors: one call per frame at batch sizes.  H (and Hi, or NULL: inverted) hold n_seq x 9 floats; has: n_seq
+ * bytes, non-zero = the sequence gets its row, zero = its pending prior is cleared; NULL = every sequence gets its row.  Nothing
+ * is changed when any used row is refused.
+ * svo_get_motion_prior: what the next frame of seq will use — *pending (0 / 1), and with a prior pending H and Hi (each may be
+ * NULL).  Host side only: no device access, no synchronisation.
+ * svo_motion_prior_from_rotation: pure host helper.  H = f32(K R K^-1), Hi = f32(K Rt K^-1), K = Pl[:, :3], computed in f64 (K^-1 by
+ * the adjugate).  R (3x3 row-major) rotates T0-camera coordinates into T1-camera coordinates: a gyro's integrated increment moved
+ * into the camera frame.  Either output may be NULL.  SVO_ERR_ARG: a singular K, a non-finite entry. */
+int svo_set_motion_prior(svo_context* ctx, int seq, const float H[9], const float Hi[9]);
+int svo_set_motion_priors(svo_context* ctx, const float* H /* n_seq x 9 */, const float* Hi /* n_seq x 9 or NULL */, const uint8_t* has /* n_seq or NULL = all */);
+int svo_get_motion_prior(svo_context* ctx, int seq, float H[9], float Hi[9], int* pending);
+int svo_motion_prior_from_rotation(const float Pl[12], const double R[9], float H[9], float Hi[9]);
+
 /* Diagnostics (pyramid tests): one level of one stored pyramid of sequence seq, WITH its stored border — every level keeps a
  * REFLECT_101 border of `pad` pixels on each side (the LK kernel reads it directly), as cv::buildOpticalFlowPyramid keeps its
  * winSize border.  out gets (h + 2 pad) rows of (w + 2 pad) bytes, packed, from pixel (-pad, -pad); cap is its size in bytes.
@@ -556,12 +609,26 @@ int svo_lk_track(int device, const uint8_t* prev_img, const uint8_t* next_img, i
                  int n, const float* prev_pts, float* next_pts, uint8_t* status,
                  int win, int max_level, int max_count, double epsilon, double min_eig_threshold);
 
+/* The same with OPTFLOW_USE_INITIAL_FLOW (the motion-prior section: LK with a guess): guess_pts (n x 2) is where the top level's
+ * search of each point starts.  guess_pts == prev_pts gives svo_lk_track's bits. */
+int svo_lk_track_guess(int device, const uint8_t* prev_img, const uint8_t* next_img, int w, int h, int stride,
+                       int n, const float* prev_pts, const float* guess_pts, float* next_pts, uint8_t* status,
+                       int win, int max_level, int max_count, double epsilon, double min_eig_threshold);
+
 /* replaces: VisualOdometry::circularMatching  (vo.h:374-379, vo.cpp:169-240) without the compaction:
  * the four LK passes L0->L1->R1->R0->L0, fused in one kernel, plus the status / loop-closure mask
  * (vo.cpp:217-230).  Outputs n points each and ok[n]. */
 int svo_circular_match(int device, const svo_config* cfg, const uint8_t* l0, const uint8_t* r0,
                        const uint8_t* l1, const uint8_t* r1, int w, int h, int stride,
                        int n, const float* pl0, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok);
+
+/* The same with a motion prior (the motion-prior section: circular matching with a prior) on k_lk_chain_prior, all four passes run:
+ * H maps T0 pixels to T1 pixels; Hi its inverse, or NULL: the library inverts H.  cfg->channels and cfg->lk_float_sums are taken as
+ * 1 and 0.  SVO_ERR_ARG as svo_set_motion_prior's.  H = identity gives svo_circular_match's bits. */
+int svo_circular_match_prior(int device, const svo_config* cfg, const uint8_t* l0, const uint8_t* r0,
+                             const uint8_t* l1, const uint8_t* r1, int w, int h, int stride,
+                             int n, const float* pl0, const float H[9], const float Hi[9],
+                             float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok);
 
 /* replaces: findClosePoints(points_1, points_2, threshold)  (vo.h:430-432, vo.cpp:265-280) */
 int svo_find_close_points(int device, int n, const float* p1, const float* p2, float threshold, uint8_t* ok);

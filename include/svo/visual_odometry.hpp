@@ -391,6 +391,22 @@ class VisualOdometry {                                               // include/
         return rows;
     }
 
+    // Seed the temporal LK passes of the NEXT stereo_callback with a predicted flow (svo_set_motion_prior; OpenCV's
+    // OPTFLOW_USE_INITIAL_FLOW, which the reference does not use): H (3x3 row-major f32) maps pixels of the previous frame to
+    // predicted pixels of the next one; Hi is its inverse, nullptr: the library inverts H.  One-shot: consumed by that frame.
+    // H = nullptr clears a pending prior.  Needs the context, i.e. a first frame: before it there is no previous frame to predict from.
+    void set_motion_prior(const float* H, const float* Hi = nullptr) {
+        if (!ctx_) throw std::runtime_error("set_motion_prior: no frame yet (the prior predicts from the previous frame)");
+        svo_throw(svo_set_motion_prior(ctx_, 0, H, Hi));
+    }
+    // The same from a rotation (svo_motion_prior_from_rotation): R (3x3 row-major f64) rotates T0-camera coordinates into T1-camera
+    // coordinates — a gyro's integrated increment moved into the camera frame; K is the left projection matrix's.
+    void set_rotation_prior(const double* R) {
+        float H[9], Hi[9];
+        svo_throw(svo_motion_prior_from_rotation(leftCameraProjection_.data(), R, H, Hi));
+        set_motion_prior(H, Hi);
+    }
+
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
 

@@ -105,6 +105,22 @@ if hasattr(lib, "svo_set_track_output"):
     lib.svo_get_last_track_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     lib.svo_get_feature_ids.restype = C.c_int
     lib.svo_get_feature_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+# motion priors (svo.h): H / Hi are 9 float32 each (n_seq x 9 in the batch setter), has n_seq bytes; R is 9 float64
+PATH_MOTION_PRIOR = 2048
+lib.svo_set_motion_prior.restype = C.c_int
+lib.svo_set_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+lib.svo_set_motion_priors.restype = C.c_int
+lib.svo_set_motion_priors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_get_motion_prior.restype = C.c_int
+lib.svo_get_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+lib.svo_motion_prior_from_rotation.restype = C.c_int
+lib.svo_motion_prior_from_rotation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_lk_track_guess.restype = C.c_int
+lib.svo_lk_track_guess.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
+lib.svo_circular_match_prior.restype = C.c_int
+lib.svo_circular_match_prior.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 # CLAHE (svo.h): the equalisation in front of frame ingest, and the stage alone
 lib.svo_set_clahe.restype = C.c_int
 lib.svo_set_clahe.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]
@@ -182,6 +198,8 @@ EXPORTS = [
     "svo_set_detection_mask", "svo_get_detection_mask", "svo_fast_detect_masked", "svo_append_features_from_image_masked",
     "svo_set_clahe", "svo_clahe",
     "svo_set_track_output", "svo_get_last_track_obs", "svo_get_feature_ids",
+    "svo_set_motion_prior", "svo_set_motion_priors", "svo_get_motion_prior", "svo_motion_prior_from_rotation",
+    "svo_lk_track_guess", "svo_circular_match_prior",
 ]
 
 

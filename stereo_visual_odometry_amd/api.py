@@ -182,16 +182,59 @@ def buildOpticalFlowPyramid(image, win, max_level, device=0):
 
 
 def calcOpticalFlowPyrLK(prev_img, next_img, prev_pts, win=10, max_level=3, max_count=30, epsilon=1e-4,
-                         min_eig_threshold=OPTICAL_FLOW_MIN_EIG_THRESHOLD, device=0):
-    """cv::calcOpticalFlowPyrLK as called at vo.cpp:203-215 -> (next_pts, status)."""
+                         min_eig_threshold=OPTICAL_FLOW_MIN_EIG_THRESHOLD, device=0, guess=None):
+    """cv::calcOpticalFlowPyrLK as called at vo.cpp:203-215 -> (next_pts, status).  guess: (N, 2) points where the top level's
+    search starts (OPTFLOW_USE_INITIAL_FLOW, svo_lk_track_guess); None: at the points themselves (flags = 0)."""
     a, b = u8img(prev_img), u8img(next_img)
     h, w = a.shape
     p = _pts(prev_pts)
     out = np.zeros_like(p)
     st = np.zeros(len(p), np.uint8)
-    check(lib.svo_lk_track(device, ptr(a), ptr(b), w, h, w, len(p), ptr(p), ptr(out), ptr(st), int(win), int(max_level),
-                           int(max_count), C.c_double(epsilon), C.c_double(min_eig_threshold)))
+    if guess is None:
+        check(lib.svo_lk_track(device, ptr(a), ptr(b), w, h, w, len(p), ptr(p), ptr(out), ptr(st), int(win), int(max_level),
+                               int(max_count), C.c_double(epsilon), C.c_double(min_eig_threshold)))
+        return out, st
+    g = _pts(guess)
+    if g.shape != p.shape:
+        raise ValueError("guess must hold one point per tracked point")
+    check(lib.svo_lk_track_guess(device, ptr(a), ptr(b), w, h, w, len(p), ptr(p), ptr(g), ptr(out), ptr(st), int(win), int(max_level),
+                                 int(max_count), C.c_double(epsilon), C.c_double(min_eig_threshold)))
     return out, st
+
+
+lk_track = calcOpticalFlowPyrLK
+
+
+def _h9(M, what):
+    m = np.ascontiguousarray(M, np.float32)
+    if m.size != 9:
+        raise ValueError("%s: a 3x3 matrix expected" % what)
+    return m.reshape(9)
+
+
+def motion_prior_from_rotation(Pl, R):
+    """(H, Hi) = f32(K R K^-1), f32(K R^T K^-1) with K = Pl[:, :3] (svo_motion_prior_from_rotation; host only).  R rotates
+    T0-camera coordinates into T1-camera coordinates."""
+    pl = np.ascontiguousarray(Pl, np.float32).reshape(12)
+    r = np.ascontiguousarray(R, np.float64).reshape(9)
+    H, Hi = np.zeros(9, np.float32), np.zeros(9, np.float32)
+    check(lib.svo_motion_prior_from_rotation(ptr(pl), ptr(r), ptr(H), ptr(Hi)))
+    return H.reshape(3, 3), Hi.reshape(3, 3)
+
+
+def circular_match_prior(cfg, l0, r0, l1, r1, points_left_t0, H, Hi=None, device=0):
+    """circularMatching() with a motion prior (svo_circular_match_prior): the temporal passes start at pred(H, .) / pred(Hi, .);
+    Hi = None lets the library invert H -> (pl1, pr1, pr0, pl0_circle, ok)."""
+    imgs = [u8img(i) for i in (l0, r0, l1, r1)]
+    h, w = imgs[0].shape
+    p = _pts(points_left_t0)
+    n = len(p)
+    hm, him = _h9(H, "H"), (None if Hi is None else _h9(Hi, "Hi"))
+    outs = [np.zeros((n, 2), np.float32) for _ in range(4)]
+    ok = np.zeros(n, np.uint8)
+    check(lib.svo_circular_match_prior(device, C.byref(cfg), ptr(imgs[0]), ptr(imgs[1]), ptr(imgs[2]), ptr(imgs[3]), w, h, w, n,
+                                       ptr(p), ptr(hm), ptr(him), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), ptr(ok)))
+    return outs[0], outs[1], outs[2], outs[3], ok
 
 
 def circularMatching(cfg, l0, r0, l1, r1, points_left_t0, device=0):
@@ -485,6 +528,48 @@ class BatchVisualOdometry:
         n = check(lib.svo_get_feature_ids(self._h, seq, cap, ptr(ids)))
         return ids[:n].copy()
 
+    def set_motion_prior(self, H, Hi=None, seq=-1):
+        """Seed the temporal LK passes of the next frame sequence `seq` (-1: every sequence) takes (svo_set_motion_prior): H, a 3x3
+        homography, maps pixels of the sequence's previous frame to predicted pixels of the frame submitted next; Hi is its
+        inverse (None: the library inverts H).  One-shot: consumed by that frame.  H = None clears a pending prior.  Legal with
+        frames in flight.  SvoError for a BGR or float-sums context, a non-finite entry, a singular H."""
+        if H is None:
+            check(lib.svo_set_motion_prior(self._h, seq, None, None))
+            return
+        hm, him = _h9(H, "H"), (None if Hi is None else _h9(Hi, "Hi"))
+        check(lib.svo_set_motion_prior(self._h, seq, ptr(hm), ptr(him)))
+
+    def set_motion_priors(self, Hs, has=None, His=None):
+        """One prior per sequence in one call (svo_set_motion_priors): Hs (n_seq, 3, 3); has: n_seq flags, a false one clears that
+        sequence's pending prior (None: every sequence gets its row); His: the inverses (None: inverted by the library)."""
+        hs = np.ascontiguousarray(Hs, np.float32)
+        if hs.size != 9 * self.n_seq:
+            raise ValueError("Hs must hold n_seq = %d 3x3 matrices" % self.n_seq)
+        his = None
+        if His is not None:
+            his = np.ascontiguousarray(His, np.float32)
+            if his.size != 9 * self.n_seq:
+                raise ValueError("His must hold n_seq = %d 3x3 matrices" % self.n_seq)
+        check(lib.svo_set_motion_priors(self._h, ptr(hs), ptr(his), ptr(self._active(has))))
+
+    def set_rotation_prior(self, R, seq=-1, Pl=None):
+        """set_motion_prior with the homography of a pure rotation: R (3x3) rotates T0-camera coordinates into T1-camera
+        coordinates (a gyro's integrated increment moved into the camera frame).  Pl: the left projection matrix (K = Pl[:, :3]);
+        None: the one last passed to initalize_projection_matricies."""
+        Pl = Pl if Pl is not None else getattr(self, "_Pl", None)
+        if Pl is None:
+            raise ValueError("set_rotation_prior: no projection matrix yet (initalize_projection_matricies, or pass Pl)")
+        H, Hi = motion_prior_from_rotation(Pl, R)
+        self.set_motion_prior(H, Hi, seq)
+
+    def motion_prior(self, seq=0):
+        """The prior the next frame of sequence `seq` will use -> (H, Hi) as 3x3 float32 arrays, or None (svo_get_motion_prior;
+        host side only)."""
+        H, Hi = np.zeros(9, np.float32), np.zeros(9, np.float32)
+        pending = C.c_int(0)
+        check(lib.svo_get_motion_prior(self._h, seq, ptr(H), ptr(Hi), C.byref(pending)))
+        return (H.reshape(3, 3), Hi.reshape(3, 3)) if pending.value else None
+
     def set_detection_mask(self, mask, seq=-1):
         """Keep features off the zero pixels of `mask` (svo_set_detection_mask): an (height, width) uint8 numpy array, or a torch
         device tensor of that shape and dtype, read through data_ptr() with its own row stride (its producer must have finished,
@@ -556,6 +641,7 @@ class BatchVisualOdometry:
         Pl = np.ascontiguousarray(leftCameraProjection, np.float32).reshape(12)
         Pr = np.ascontiguousarray(rightCameraProjection, np.float32).reshape(12)
         check(lib.svo_set_projection(self._h, seq, ptr(Pl), ptr(Pr)))
+        self._Pl = Pl.copy()                          # set_rotation_prior's K
 
     def _active(self, active):
         """None, or n_seq truthy flags -> a uint8 array for the masked entry points."""
@@ -819,6 +905,25 @@ class VisualOdometry(BatchVisualOdometry):
             raise _lib.SvoError("last_pose_covariance: no frame yet (call stereo_callback first)")
         return super().last_pose_covariance()
 
+    def set_motion_prior(self, H, Hi=None, seq=-1):
+        if self._created:
+            return super().set_motion_prior(H, Hi, seq)
+        # before the first frame: held, handed to the context when it is created — and consumed, unused, by that first frame
+        self._prior = None if H is None else (_h9(H, "H").copy(), None if Hi is None else _h9(Hi, "Hi").copy())
+
+    def set_rotation_prior(self, R, seq=-1, Pl=None):
+        if Pl is None and self._P is not None:
+            Pl = self._P[0]
+        return super().set_rotation_prior(R, seq, Pl)
+
+    def motion_prior(self, seq=0):
+        if not self._created:
+            p = getattr(self, "_prior", None)
+            if p is None:
+                return None
+            return p[0].reshape(3, 3), (p[1].reshape(3, 3) if p[1] is not None else None)
+        return super().motion_prior(seq)
+
     def stereo_callback(self, image_left, image_right):
         fmt = self.input_format
         bpp = _lib.INPUT_BPP[fmt] if fmt != _lib.INPUT_MONO8 else None
@@ -854,6 +959,9 @@ class VisualOdometry(BatchVisualOdometry):
                 super().set_clahe(self._clahe[0], self._clahe[1:])
             if self._track_rows is not None:
                 super().set_track_output(self._track_rows)
+            if getattr(self, "_prior", None) is not None:
+                super().set_motion_prior(self._prior[0], self._prior[1])
+                self._prior = None
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

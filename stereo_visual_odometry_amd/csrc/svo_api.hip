@@ -4,6 +4,7 @@
 // (second FAST pass, too-few-tracks gate, RANSAC failure, motion gate, stale-pyramid quirk) is taken
 // on the device from SeqState, so a frame needs no host round trip until its pose is read back.
 #include "svo_internal.hpp"
+#include "svo_prior.hpp"
 #include <stdio.h>
 #include <string.h>
 #include <stddef.h>
@@ -205,6 +206,14 @@ struct svo_context {
     int last_obs_rows = 0;                       // the row pitch of whichever holds it
     std::vector<svo_track_obs> kept_obs;
     std::vector<int> kept_hdr;
+    // motion priors (svo_set_motion_prior).  Everything below is empty until the first setter.  prior_next[seq] is the prior the
+    // sequence's next frame will use (has = 1) — host state, consumed when that frame is enqueued (take_priors): the frame's rows go
+    // into its slot's row of the pinned ring and from there, with one copy on the frame's stream, into the slot's device row that
+    // k_lk_chain_prior reads.  A slot's rows are free once its frame has been collected, so every frame in flight keeps its own.
+    std::vector<PriorRow> prior_next;            // [B]
+    int n_prior = 0;                             // how many of them are pending
+    PriorRow* h_prior = nullptr;                 // pinned [SVO_RING][B]
+    PriorRow* d_prior = nullptr;                 // device [SVO_RING][B]
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -386,7 +395,8 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->d_mask_rows) (void)hipFree((void*)c->d_mask_rows);
     for (void* p : {(void*)c->h_mask_rows, (void*)c->h_mask_stage}) if (p) (void)hipHostFree(p);
     if (c->ev_mask_stage) (void)hipEventDestroy(c->ev_mask_stage);
-    for (void* p : {(void*)c->clahe_buf, (void*)c->clahe_lut}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)c->clahe_buf, (void*)c->clahe_lut, (void*)c->d_prior}) if (p) (void)hipFree(p);
+    if (c->h_prior) (void)hipHostFree(c->h_prior);
     for (RingSlot& r : c->ring) {
         for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
         if (r.ev_img) (void)hipEventDestroy(r.ev_img);
@@ -557,8 +567,9 @@ static int front_ahead(svo_context* c, DevBuffers& f, int slot, int stride) {
 // The launch list of one frame (vo.cpp:41-137 as kernels), between the slot's start and done events.
 // with_events: record the stage-boundary events (not inside a graph capture).  n_act: see frame_view.
 // mrows: the frame's row of d_mask_rows when its detection applies a mask to some sequence (enqueue_frame), else null.
+// prow: the frame's device row of motion priors when some active sequence has one (take_priors), else null.
 static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, DeviceSharing share, int n_act = -1,
-                       const uint8_t* const* mrows = nullptr) {
+                       const uint8_t* const* mrows = nullptr, const PriorRow* prow = nullptr) {
     hipStream_t s = c->stream;
     const auto record = [&](StageEvent which) { return with_events ? hipEventRecord(c->ring[slot].ev[which], s) : hipSuccess; };
     if (n_act == 0) {                                                  // all idle: the result rows are the whole frame
@@ -605,7 +616,8 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         path |= SVO_PATH_LK_CHAINED;
     }
     HIPCHK(record(EV_LK0));
-    if (!launch_lk_chain(f, gn, s, 1)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
+    if (!launch_lk_chain(f, gn, s, 1, prow)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // with priors: k_lk_chain_prior, the LK launch of this frame in every respect
+    if (prow) path |= SVO_PATH_MOTION_PRIOR;
     HIPCHK(record(EV_LK1));
     if (gate) {
         std::lock_guard<std::mutex> lock(gate->mu);
@@ -738,6 +750,28 @@ static int take_masks(svo_context* c, int slot, const uint8_t* active, const uin
     return SVO_OK;
 }
 
+// Motion priors of one frame: every active sequence with a pending prior hands it to this frame (one-shot: it is consumed here) —
+// idle sequences keep theirs.  *prow: the frame's device row, filled by one copy on the frame's stream from the slot's pinned row,
+// when some active sequence has one; else null, and the frame is an ordinary one.
+static int take_priors(svo_context* c, int slot, const uint8_t* active, const PriorRow** prow) {
+    *prow = nullptr;
+    if (c->n_prior == 0) return SVO_OK;
+    const int B = c->d.B;
+    PriorRow* row = c->h_prior + (size_t)slot * B;
+    bool any = false;
+    for (int i = 0; i < B; i++) {
+        PriorRow& p = c->prior_next[i];
+        const bool take = p.has && (!active || active[i]);
+        if (take) { row[i] = p; p.has = 0; c->n_prior--; any = true; }
+        else row[i].has = 0;
+    }
+    if (!any) return SVO_OK;
+    PriorRow* drow = c->d_prior + (size_t)slot * B;
+    HIPCHK(hipMemcpyAsync(drow, row, sizeof(PriorRow) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    *prow = drow;
+    return SVO_OK;
+}
+
 // The last collected frame's headers and rows out of the ring slot a new frame is about to write, into the context's own copy.
 static void keep_last_obs(svo_context* c) {
     const size_t B = c->d.B, R = c->track_rows;
@@ -770,11 +804,13 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     HIPCHK(hipEventRecord(r.ev[EV_F0], c->stream));
     const uint8_t* const* mrows = nullptr;
     if ((rc = take_masks(c, slot, active, &mrows)) != SVO_OK) return rc;
+    const PriorRow* prow = nullptr;
+    if ((rc = take_priors(c, slot, active, &prow)) != SVO_OK) return rc;
     bool replayed = false;
     if (c->track_on && slot == c->last_obs_slot) keep_last_obs(c);    // the frame is about to write the slot svo_get_last_track_obs still reads
-    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on && !c->track_on)   // a ragged, rectifying, masked, CLAHE or track-ids frame runs from the launch list
+    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on && !c->track_on && !prow)   // a ragged, rectifying, masked, CLAHE, track-ids or motion-prior frame runs from the launch list
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
-    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows)) != SVO_OK) return rc;
+    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows, prow)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
     r.cov_mode = c->cov_mode; r.masked = active != nullptr; r.tracks = c->track_on;
     c->staged_inputs = false;
@@ -847,6 +883,8 @@ extern "C" int svo_reset_sequence(svo_context* c, int seq, const float Pl[12], c
     if (c->ids.next_id) launch_ids_reset(c->ids, seq < 0 ? 0 : seq, seq < 0 ? c->d.B : 1, c->stream);   // next_id = 0, stream-ordered like the rest
     HIPCHK(hipGetLastError());
     if (Pl && seq < 0) c->projection_set = true;
+    for (int i = seq < 0 ? 0 : seq; c->n_prior > 0 && i < (seq < 0 ? c->d.B : seq + 1); i++)   // a pending motion prior belonged to the stream that ends here
+        if (c->prior_next[i].has) { c->prior_next[i].has = 0; c->n_prior--; }
     return SVO_OK;
 }
 
@@ -957,10 +995,86 @@ static int stage_host_images(svo_context* c, const uint8_t* const* left, const u
 static int read_state(svo_context* c, int seq, SeqState* hs);
 static int set_state(svo_context* c, const SeqState& hs);
 
+// ---- motion priors (svo.h): the host arithmetic, the buffers, the setters ----
+// One prior as the kernels take it (svo_prior.hpp has the arithmetic): H checked, Hi the caller's or H's inverse rounded to f32.
+static int make_prior_row(const float* H, const float* Hi, PriorRow* out) {
+    if (const char* err = prior_make(H, Hi, out->H, out->Hi)) return fail_arg(err);
+    out->has = 1; out->pad = 0;
+    return SVO_OK;
+}
+// can this context take a prior at all?  (k_lk_chain_prior is the grey, exact-sums build)
+static int check_prior_context(const svo_context* c) {
+    if (c->d.CN != 1) return fail_arg("motion priors need a channels == 1 context");
+    if (c->d.cfg.lk_float_sums) return fail_arg("motion priors need lk_float_sums == 0 (that mode reproduces the reference's recording, which has no prior)");
+    return SVO_OK;
+}
+// the pinned ring and its device copy, at first use
+static int prior_buffers(svo_context* c) {
+    if (c->d_prior) return SVO_OK;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t bytes = sizeof(PriorRow) * SVO_RING * (size_t)c->d.B;
+    PriorRow *h = nullptr, *dv = nullptr;
+    HIPCHK(hipHostMalloc((void**)&h, bytes));
+    if (hipMalloc((void**)&dv, bytes) != hipSuccess) { (void)hipHostFree(h); g_err = "motion prior: hipMalloc failed"; return SVO_ERR_HIP; }
+    memset(h, 0, bytes);
+    c->h_prior = h; c->d_prior = dv;
+    c->prior_next.assign((size_t)c->d.B, PriorRow{});
+    return SVO_OK;
+}
+static void set_pending(svo_context* c, int seq, const PriorRow* row /* null: clear */) {
+    PriorRow& p = c->prior_next[seq];
+    c->n_prior += (row ? 1 : 0) - (p.has ? 1 : 0);
+    if (row) p = *row; else p.has = 0;
+}
+
+extern "C" int svo_set_motion_prior(svo_context* c, int seq, const float H[9], const float Hi[9]) {
+    if (!c) return fail_arg("null context");
+    int rc = check_prior_context(c); if (rc != SVO_OK) return rc;
+    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    const int s0 = seq < 0 ? 0 : seq, s1 = seq < 0 ? c->d.B : seq + 1;
+    if (!H) {                                                                     // clear: nothing to do before the first prior
+        for (int i = s0; c->d_prior && i < s1; i++) set_pending(c, i, nullptr);
+        return SVO_OK;
+    }
+    PriorRow row;
+    if ((rc = make_prior_row(H, Hi, &row)) != SVO_OK) return rc;
+    if ((rc = prior_buffers(c)) != SVO_OK) return rc;
+    for (int i = s0; i < s1; i++) set_pending(c, i, &row);
+    return SVO_OK;
+}
+
+extern "C" int svo_set_motion_priors(svo_context* c, const float* H, const float* Hi, const uint8_t* has) {
+    if (!c || !H) return fail_arg("null argument");
+    int rc = check_prior_context(c); if (rc != SVO_OK) return rc;
+    const int B = c->d.B;
+    std::vector<PriorRow> rows((size_t)B);
+    for (int i = 0; i < B; i++)                                                   // every used row is checked before anything changes
+        if ((!has || has[i]) && (rc = make_prior_row(H + 9 * i, Hi ? Hi + 9 * i : nullptr, &rows[i])) != SVO_OK) return rc;
+    if ((rc = prior_buffers(c)) != SVO_OK) return rc;
+    for (int i = 0; i < B; i++) set_pending(c, i, (!has || has[i]) ? &rows[i] : nullptr);
+    return SVO_OK;
+}
+
+extern "C" int svo_get_motion_prior(svo_context* c, int seq, float H[9], float Hi[9], int* pending) {
+    if (!c || seq < 0 || seq >= c->d.B) return fail_arg("bad context / seq");
+    const bool on = c->n_prior > 0 && c->prior_next[seq].has;
+    if (pending) *pending = on ? 1 : 0;
+    if (on && H) memcpy(H, c->prior_next[seq].H, sizeof(float) * 9);
+    if (on && Hi) memcpy(Hi, c->prior_next[seq].Hi, sizeof(float) * 9);
+    return SVO_OK;
+}
+
+extern "C" int svo_motion_prior_from_rotation(const float Pl[12], const double R[9], float H[9], float Hi[9]) {
+    if (!Pl || !R) return fail_arg("null argument");
+    if (const char* err = prior_from_rotation(Pl, R, H, Hi)) return fail_arg(err);
+    return SVO_OK;
+}
+
 // the end of both circularMatching entry points (vo.cpp:203-230): the four LK passes, then every pass's raw points and the mask
-static int circular_tail(svo_context* c, int n, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok) {
+// (prior: the device row of a motion prior — svo_circular_match_prior — or null)
+static int circular_tail(svo_context* c, int n, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok, const PriorRow* prior = nullptr) {
     const DevBuffers& d = c->d;
-    if (!launch_lk_chain(d, n, c->stream, 0)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
+    if (!launch_lk_chain(d, n, c->stream, 0, prior)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(pl1, d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(pr1, d.pr1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
@@ -985,6 +1099,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     int rc = check_stride(c, stride); if (rc != SVO_OK) return rc;
     if (c->inflight != 0) { g_err = "svo_circular_matching with frames in flight"; return SVO_ERR_STATE; }
     if (c->track_on) { g_err = "svo_circular_matching with the track output on: it overwrites the feature set behind the ids (svo_set_track_output(ctx, 0, 0) first)"; return SVO_ERR_STATE; }
+    if (c->n_prior > 0) { g_err = "svo_circular_matching with a motion prior pending: priors belong to the frame pipeline (svo_set_motion_prior(ctx, -1, NULL, NULL) clears them; svo_circular_match_prior is the stage call)"; return SVO_ERR_STATE; }
     if (n == 0) return SVO_OK;                                                    // vo.cpp:179-181
     if (n > c->d.CAP) { g_err = "more points than the context's feature capacity"; return SVO_ERR_CAPACITY; }
     HIPCHK(hipSetDevice(c->device));
@@ -1496,9 +1611,10 @@ extern "C" int svo_build_pyramid(int device, const uint8_t* img, int w, int h, i
     return SVO_OK;
 }
 
-extern "C" int svo_lk_track(int device, const uint8_t* prev_img, const uint8_t* next_img, int w, int h, int stride,
-                            int n, const float* prev_pts, float* next_pts, uint8_t* status,
-                            int win, int max_level, int max_count, double epsilon, double min_eig_threshold) {
+// both forms of the cv::calcOpticalFlowPyrLK-shaped call: guess_pts null is flags = 0, else OPTFLOW_USE_INITIAL_FLOW
+static int lk_track_stage(int device, const uint8_t* prev_img, const uint8_t* next_img, int w, int h, int stride,
+                          int n, const float* prev_pts, const float* guess_pts, float* next_pts, uint8_t* status,
+                          int win, int max_level, int max_count, double epsilon, double min_eig_threshold) {
     if (!prev_img || !next_img || n < 0 || stride < w) return fail_arg("bad arguments");
     if (n > 0 && (!prev_pts || !next_pts || !status)) return fail_arg("null arrays");
     svo_config cfg; svo_config_default(&cfg);
@@ -1512,7 +1628,8 @@ extern "C" int svo_lk_track(int device, const uint8_t* prev_img, const uint8_t* 
     if ((rc = build_pyramid_in_slot(c, hs, 0)) != SVO_OK) return rc;
     if ((rc = build_pyramid_in_slot(c, hs, 1)) != SVO_OK) return rc;
     HIPCHK(hipMemcpyAsync(c->d.pl0, prev_pts, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-    launch_lk_single(c->d, 0, 0, 1, 0, n, c->d.pl0, c->d.pl1, c->d.okmask, c->stream);
+    if (guess_pts) HIPCHK(hipMemcpyAsync(c->d.pr1, guess_pts, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));   // (pr1: scratch of this call)
+    launch_lk_single(c->d, 0, 0, 1, 0, n, c->d.pl0, c->d.pl1, c->d.okmask, c->stream, guess_pts ? c->d.pr1 : nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(next_pts, c->d.pl1, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(status, c->d.okmask, (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -1520,15 +1637,38 @@ extern "C" int svo_lk_track(int device, const uint8_t* prev_img, const uint8_t* 
     return SVO_OK;
 }
 
-extern "C" int svo_circular_match(int device, const svo_config* cfg_in, const uint8_t* l0, const uint8_t* r0,
-                                  const uint8_t* l1, const uint8_t* r1, int w, int h, int stride,
-                                  int n, const float* pl0, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok) {
+extern "C" int svo_lk_track(int device, const uint8_t* prev_img, const uint8_t* next_img, int w, int h, int stride,
+                            int n, const float* prev_pts, float* next_pts, uint8_t* status,
+                            int win, int max_level, int max_count, double epsilon, double min_eig_threshold) {
+    return lk_track_stage(device, prev_img, next_img, w, h, stride, n, prev_pts, nullptr, next_pts, status, win, max_level, max_count, epsilon, min_eig_threshold);
+}
+
+extern "C" int svo_lk_track_guess(int device, const uint8_t* prev_img, const uint8_t* next_img, int w, int h, int stride,
+                                  int n, const float* prev_pts, const float* guess_pts, float* next_pts, uint8_t* status,
+                                  int win, int max_level, int max_count, double epsilon, double min_eig_threshold) {
+    if (n > 0 && !guess_pts) return fail_arg("null arrays");
+    return lk_track_stage(device, prev_img, next_img, w, h, stride, n, prev_pts, n > 0 ? guess_pts : nullptr, next_pts, status, win, max_level, max_count, epsilon,
+                          min_eig_threshold);
+}
+
+// both forms of the stage call: prior null is svo_circular_match, else the row of svo_circular_match_prior (k_lk_chain_prior)
+static int circular_match_stage(int device, const svo_config* cfg_in, const uint8_t* l0, const uint8_t* r0,
+                                const uint8_t* l1, const uint8_t* r1, int w, int h, int stride,
+                                int n, const float* pl0, const PriorRow* prior, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok) {
     if (!l0 || !r0 || !l1 || !r1 || n < 0 || stride < w) return fail_arg("bad arguments");
     if (n > 0 && (!pl0 || !pl1 || !pr1 || !pr0 || !pl0_circle || !ok)) return fail_arg("null arrays");
     svo_config cfg; if (cfg_in) cfg = *cfg_in; else svo_config_default(&cfg);
     cfg.max_features = 0; cfg.channels = 1;
+    if (prior) cfg.lk_float_sums = 0;
     svo_context* c = nullptr; int rc = stage_ctx(cfg, device, w, h, n, &c); if (rc != SVO_OK) return rc;
     if (n == 0) return SVO_OK;                                                    // vo.cpp:179-181
+    const PriorRow* drow = nullptr;
+    if (prior) {                                                                  // the context's first rows: nothing of it is in flight
+        if ((rc = prior_buffers(c)) != SVO_OK) return rc;
+        c->h_prior[0] = *prior;
+        HIPCHK(hipMemcpyAsync(c->d_prior, c->h_prior, sizeof(PriorRow), hipMemcpyHostToDevice, c->stream));
+        drow = c->d_prior;
+    }
     if ((rc = upload_image(c, 0, 0, l0, stride)) != SVO_OK) return rc;
     if ((rc = upload_image(c, 0, 1, r0, stride)) != SVO_OK) return rc;
     if ((rc = upload_image(c, 1, 0, l1, stride)) != SVO_OK) return rc;
@@ -1538,7 +1678,23 @@ extern "C" int svo_circular_match(int device, const svo_config* cfg_in, const ui
     hs.frame_id = 1; hs.active = 1; hs.slot_img_t0 = 0; hs.slot_pyr_t0 = 0; hs.n_feat = n; hs.feat_buf = 0;
     if ((rc = build_pyramid_in_slot(c, hs, 1)) != SVO_OK) return rc;             // leaves slot_t1 = 1
     HIPCHK(hipMemcpyAsync(c->d.feat_xy[0], pl0, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-    return circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok);
+    return circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok, drow);
+}
+
+extern "C" int svo_circular_match(int device, const svo_config* cfg_in, const uint8_t* l0, const uint8_t* r0,
+                                  const uint8_t* l1, const uint8_t* r1, int w, int h, int stride,
+                                  int n, const float* pl0, float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok) {
+    return circular_match_stage(device, cfg_in, l0, r0, l1, r1, w, h, stride, n, pl0, nullptr, pl1, pr1, pr0, pl0_circle, ok);
+}
+
+extern "C" int svo_circular_match_prior(int device, const svo_config* cfg_in, const uint8_t* l0, const uint8_t* r0,
+                                        const uint8_t* l1, const uint8_t* r1, int w, int h, int stride,
+                                        int n, const float* pl0, const float H[9], const float Hi[9],
+                                        float* pl1, float* pr1, float* pr0, float* pl0_circle, uint8_t* ok) {
+    if (!H) return fail_arg("null argument");
+    PriorRow row;
+    if (const int rc = make_prior_row(H, Hi, &row)) return rc;
+    return circular_match_stage(device, cfg_in, l0, r0, l1, r1, w, h, stride, n, pl0, &row, pl1, pr1, pr0, pl0_circle, ok);
 }
 
 extern "C" int svo_find_close_points(int device, int n, const float* p1, const float* p2, float threshold, uint8_t* ok) {

@@ -198,6 +198,10 @@ struct IdArgs { long long* feat_id[2]; long long* track_id; long long* next_id; 
 // One frame's rows of the pinned observation ring: rows [B][max_rows], hdr [B] {n_tracks, n_rows} — host memory mapped into the
 // device, written in place by k_track_obs like the result records.
 struct TrackObsArgs { svo_track_obs* rows; int* hdr; int max_rows; };
+// Motion priors (svo.h, svo_set_motion_prior): one sequence's row of a frame's priors — the homography T0 -> T1, its inverse, and
+// whether the sequence has one in this frame.  The frame's rows ([B], indexed by sequence) are a kernel argument of k_lk_chain_prior
+// alone, like MaskArgs: DevBuffers and every existing kernel's argument block stay as they are.
+struct PriorRow { float H[9], Hi[9]; int has, pad; };
 // what Bucket::add_feature compares (feature_set.cpp:16-18); the division truncates toward zero, as C's does
 __device__ __forceinline__ int bucket_score(int age, int strength, int fast_thr) { return age + (strength - fast_thr) / 20; }
 // capacity 1: (score, first come, strength) as one key for a 64-bit atomicMax; order = the candidate's rank in the input list
@@ -253,7 +257,8 @@ void launch_detect(const DevBuffers& d, int pass, int th_override, hipStream_t s
 // the same pass with detection masks (features_per_bucket == 1 only): k_fast_masked / k_fast_strided_masked, then the plain emit
 void launch_detect_masked(const DevBuffers& d, const MaskArgs& m, int pass, int th_override, hipStream_t s);
 // grid_n = max features that can enter LK; early_out: a feature stops at its first pass with status 0 (frame pipeline) or runs all four (member call)
-bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out);   // false: no kernel built for this (window, channels, summation mode) — nothing ran
+// prior: the frame's rows of motion priors (device, [B]) — k_lk_chain_prior then runs in k_lk_chain's place — or null
+bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out, const PriorRow* prior = nullptr);   // false: no kernel built for this (window, channels, summation mode) — nothing ran
 void launch_compact(const DevBuffers& d, hipStream_t s);
 void launch_triangulate(const DevBuffers& d, hipStream_t s);
 void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = false);   // expects the subsets drawn (launch_triangulate / k_compact do it)
@@ -293,8 +298,9 @@ void launch_score_compact(const uint8_t* score_dev, int w, int h, int cap, int* 
 void launch_bucket_general(const BucketGrid& g, int per_bucket, int n, const float2* xy, const int* ages, const int* strs,
                            float2* slot_xy, int* slot_age, int* slot_str, int* slot_n,
                            float2* out_xy, int* out_age, int* out_str, int* n_out, hipStream_t s);
+// guess: the points the top level's search starts at (k_lk_single_guess), or null: the points themselves (k_lk_single)
 void launch_lk_single(const DevBuffers& d, int slotA, int camA, int slotB, int camB, int n, const float2* prev, float2* next,
-                      uint8_t* status, hipStream_t s);
+                      uint8_t* status, hipStream_t s, const float2* guess = nullptr);
 void launch_find_close(int n, const float2* a, const float2* b, float thr, uint8_t* ok, hipStream_t s);
 bool lk_window_supported(int win);
 int lk_registers_left(const DevBuffers& d);   // VGPRs per SIMD lane beside a full set of this context's LK waves (-1: unknown)

@@ -52,6 +52,7 @@ template <int W> struct LkLayout {
 // Border width the kernel's reads need around every pyramid level at window `win` (Geometry::pad): the template reads rows and
 // columns origin - 1 .. origin + EXT + 1 (+ up to 3 bytes of the last dword) with origin in [-win, size), the search window
 // origin .. origin + EXT.  Same PPL / EXT recipe as LkLayout.
+#ifndef SVO_LK_PRIOR_TU
 int lk_pad_for(int win) {
     if (win < 1) win = 1;
     int ppl = win;
@@ -59,6 +60,7 @@ int lk_pad_for(int win) {
     const int ext = ((win + ppl - 1) / ppl) * ppl;
     return (ext + 5 + 3) & ~3;
 }
+#endif
 
 // one doubling step of the in-row DPP reduction (S = 0..3: lane pairs, quads, half rows, rows)
 template <int S>
@@ -401,10 +403,14 @@ __device__ __forceinline__ void fs_sum_b(int* __restrict__ lds, float& b1, float
 // derA: the Ix plane of pyrA's derivative pyramid (svo_internal.hpp; grey exact-sums builds only), or nullptr: at the levels >= 1 the
 // template's derivative pairs are then LOADED — samples k_deriv_levels computed once per frame, zero outside the level — instead
 // of being derived from four pixel rows and masked in every visit.  The same integers either way.
-template <int W, int CN, bool FS = false>
+// GUESS (svo.h, motion prior; OpenCV's OPTFLOW_USE_INITIAL_FLOW): the search of the top level starts at (gx, gy) * 2^-top instead of
+// the point's own position there; the template still comes from (px, py) and nothing else changes, so a guess equal to the point
+// gives the bits of the build without the flag.  The scaled guess is parked in outx / outy, which cross the level loop anyway: the
+// guess itself is dead before the first template is built and costs the Newton loop no register.
+template <int W, int CN, bool FS = false, bool GUESS = false>
 __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, const int16_t* __restrict__ derA, const uint8_t* __restrict__ pyrB, size_t pstride,
                         float px, float py, float& outx, float& outy, int& status, const LkCrit& crit,
-                        const LkSeg& sg, int& n_visits, int& n_steps, int* fs_lds = nullptr) {
+                        const LkSeg& sg, int& n_visits, int& n_steps, int* fs_lds = nullptr, float gx = 0.f, float gy = 0.f) {
     constexpr int FE = W * CN;                                          // interleaved elements per window row (float-sums mode)
     using LL = LkLayout<W>;
     constexpr int PPL = LL::PPL, EXT = LL::EXT, NS = LL::NS, NB = LL::NB;
@@ -416,6 +422,10 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
     float nx = 0.f, ny = 0.f;
     status = 1;
     outx = px; outy = py;
+    if constexpr (GUESS) {
+        const float top_scale = __int_as_float((127 - top) << 23);          // 2^-top, exact
+        outx = gx * top_scale; outy = gy * top_scale;
+    }
     bool planes = false;
     if constexpr (CN == 1 && !FS) planes = uni(derA != nullptr);
     for (int level = top; level >= 0; --level) {
@@ -424,7 +434,9 @@ __device__ void lk_pass(const Geometry& g, const uint8_t* __restrict__ pyrA, con
         const uint8_t* __restrict__ Bm = pyrB + L.off;
         const float scale = __int_as_float((127 - level) << 23);            // 2^-level, exact (= 1.f / (1 << level))
         float ppx = px * scale, ppy = py * scale;
-        if (level == top) { nx = ppx; ny = ppy; } else { nx = outx * 2.f; ny = outy * 2.f; }
+        if (level == top) {
+            if constexpr (GUESS) { nx = outx; ny = outy; } else { nx = ppx; ny = ppy; }
+        } else { nx = outx * 2.f; ny = outy * 2.f; }
         outx = nx; outy = ny;
         ppx -= half; ppy -= half;
         const int ipx = (int)floorf(ppx), ipy = (int)floorf(ppy);
@@ -750,6 +762,7 @@ __device__ __forceinline__ LkSeg lk_segment() {
 
 // The termination criteria and the image limits of a configuration, as the kernels use them: computed once per configuration on the
 // host (svo_api.hip, beside lk_mineig_cut) and passed by value inside DevBuffers, so no wave repeats the f64 arithmetic at entry.
+#ifndef SVO_LK_PRIOR_TU
 LkCrit lk_make_crit(const svo_config& c, const Geometry& g) {
     LkCrit k;
     int mc = c.lk_max_count; mc = mc < 0 ? 0 : (mc > 100 ? 100 : mc);       // TermCriteria normalisation (lkpyramid.cpp)
@@ -763,6 +776,7 @@ LkCrit lk_make_crit(const svo_config& c, const Geometry& g) {
     k.Wf = (float)g.W; k.Hf = (float)g.H;
     return k;
 }
+#endif
 
 // ---- fused circular matching: L0 -> L1 -> R1 -> R0 -> L0 + masks (vo.cpp:203-230, 341-359) ----
 // Block -> (sequence, feature) mapping.  Workgroups are dealt round-robin over the 8 XCDs (block b lands on XCD b % 8,
@@ -784,8 +798,23 @@ LkCrit lk_make_crit(const svo_config& c, const Geometry& g) {
 // p0 / p1: the pyramid number (sequence, slot, camera 0) of the T0 / T1 pair; the right camera's is the next one.  Numbers, not the
 // four pointers (and the four of their derivative planes): two scalar registers held through lk_pass instead of sixteen.
 struct LkSeqCtx { int p0, p1, seq, buf; };
-template <int W, int CN, bool FS>
-__device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSeqCtx& q, int idx, const LkSeg& sg, int early_out, int* fs_lds) {
+// pred(M, p) of the motion prior (svo.h): the homography's image of p, every operation f32 and rounded once (this file is built
+// without contraction), IEEE division; p itself where the denominator is not positive or a quotient is not finite (NaN included).
+__device__ __forceinline__ float2 lk_pred(const float* __restrict__ m, float2 p) {
+    const float X = (m[0] * p.x + m[1] * p.y) + m[2];
+    const float Y = (m[3] * p.x + m[4] * p.y) + m[5];
+    const float D = (m[6] * p.x + m[7] * p.y) + m[8];
+    const float u = X / D, v = Y / D;
+    const bool ok = D > 0.f && fabsf(u) < __builtin_inff() && fabsf(v) < __builtin_inff();
+    return ok ? make_float2(u, v) : p;
+}
+// PRIOR (k_lk_chain_prior): pr is the sequence's row of the frame's motion priors.  With pr->has the temporal passes 0 (L0 -> L1) and
+// 2 (R1 -> R0) start their search at pred(H, .) / pred(Hi, .) of their point; the stereo passes, and every pass of a sequence
+// without a prior, start at the point itself — which is what the build without the flag computes, bit for bit.  The row's address
+// is wave-uniform: its entries come through the scalar cache and are dead before lk_pass.
+template <int W, int CN, bool FS, bool PRIOR = false>
+__device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSeqCtx& q, int idx, const LkSeg& sg, int early_out, int* fs_lds,
+                                                 const PriorRow* __restrict__ pr = nullptr) {
     const LkCrit& crit = d.lk_crit;
     const float thr = crit.thr, Wf = crit.Wf, Hf = crit.Hf;
     const int seq = q.seq;
@@ -814,7 +843,13 @@ __device__ __forceinline__ void lk_chain_feature(const DevBuffers& d, const LkSe
         const int16_t* dA = dv ? dv + (size_t)na * 2 * (size_t)deriv_samples(d.geom) : nullptr;
         float2* out = pass == 0 ? d.pl1 : pass == 1 ? d.pr1 : pass == 2 ? d.pr0 : d.plc;
         float2 q; int st;
-        lk_pass<W, CN, FS>(d.geom, A, dA, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds);
+        if constexpr (PRIOR) {
+            float2 gs = cur;
+            if ((pass & 1) == 0 && pr->has) gs = lk_pred(pass == 0 ? pr->H : pr->Hi, cur);
+            lk_pass<W, CN, FS, true>(d.geom, A, dA, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds, gs.x, gs.y);
+        } else {
+            lk_pass<W, CN, FS>(d.geom, A, dA, Bq, (size_t)d.geom.pyr_bytes, cur.x, cur.y, q.x, q.y, st, crit, sg, n_visits, n_steps, fs_lds);
+        }
         if (pass < 3 && ((q.x < 0) || (q.y < 0) || (q.y >= Hf) || (q.x >= Wf))) flags &= ~2;     // pl1, pr1, pr0 (not the returned point)
         if (writer) out[o] = q;
         cur = q;
@@ -894,6 +929,28 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_e
     const int f = (q * 8 + x) * chunk + (r - q * chunk);
     for (int idx = f; idx < n; idx += slots) lk_chain_feature<W, CN, FS>(d, sc, idx, sg, early_out, fs_lds);
 }
+// The chain launch of a frame in which some active sequence has a motion prior (svo.h): grey, exact sums.  prior: the frame's rows,
+// indexed by sequence.  The block -> (sequence, feature) mapping, the feature loop, the derivative-plane path and the wave table are
+// those of k_lk_chain<W, 1, false>, which it replaces in that frame — the body is k_lk_chain's, statement for statement.  A copy, not
+// a function both kernels call: with the body moved out of k_lk_chain the compiler schedules all 88 existing builds differently
+// (same instructions, other order and registers), and those are pinned to what they were.
+template <int W>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64), amdgpu_waves_per_eu(LK_MIN_WAVES(W, 1, false), LK_MAX_WAVES(W, 1, false)))) void k_lk_chain_prior(DevBuffers d, int slots, int chunk, int early_out, const PriorRow* __restrict__ prior) {
+    const int b = blockIdx.x / slots, fb = blockIdx.x - b * slots;
+    if (b >= launch_seqs(d)) return;
+    const int seq = seq_of(d, b);
+    SeqState& s = d.st[seq];
+    if (!s.active) return;
+    int n = s.n_feat;
+    if (d.cfg.max_features > 0 && n > d.cfg.max_features) n = d.cfg.max_features;
+    if (fb == 0 && threadIdx.x == 0) s.n_lk = n;
+    const LkSeqCtx sc = {(seq * SVO_PYR_SLOTS + s.slot_pyr_t0) * 2, (seq * SVO_PYR_SLOTS + s.slot_t1) * 2, seq, s.feat_buf};
+    const LkSeg sg = lk_segment<W>();
+    const int x = fb & 7, r = fb >> 3;
+    const int q = r / chunk;
+    const int f = (q * 8 + x) * chunk + (r - q * chunk);
+    for (int idx = f; idx < n; idx += slots) lk_chain_feature<W, 1, false, true>(d, sc, idx, sg, early_out, nullptr, prior + seq);
+}
 
 // ---- single pass, for the cv::calcOpticalFlowPyrLK-shaped stage API ----
 template <int W>
@@ -909,11 +966,27 @@ __global__ __launch_bounds__(64) void k_lk_single(DevBuffers d, int slotA, int c
     }
 }
 
+// the same pass from a caller's guess (svo_lk_track_guess: OPTFLOW_USE_INITIAL_FLOW)
+template <int W>
+__global__ __launch_bounds__(64) void k_lk_single_guess(DevBuffers d, int slotA, int camA, int slotB, int camB, int n,
+                                                        const float2* prev, const float2* guess, float2* next, uint8_t* status) {
+    const uint8_t* A = d.pyr + pyr_index(d, 0, slotA, camA);
+    const uint8_t* Bp = d.pyr + pyr_index(d, 0, slotB, camB);
+    const LkSeg sg = lk_segment<W>();
+    for (int idx = blockIdx.x; idx < n; idx += gridDim.x) {
+        const float2 p = prev[idx], gs = guess[idx];
+        float2 q; int st, nv = 0, ns = 0;
+        lk_pass<W, 1, false, true>(d.geom, A, nullptr, Bp, 0, p.x, p.y, q.x, q.y, st, d.lk_crit, sg, nv, ns, nullptr, gs.x, gs.y);
+        if (threadIdx.x == 0) { next[idx] = q; status[idx] = (uint8_t)st; }
+    }
+}
+
 #define LK_MAX_GRID 16384
 static int lk_chunk() { static int v = -1; if (v < 0) { const char* e = getenv("SVO_LK_CHUNK"); v = e ? atoi(e) : 4; if (v < 1) v = 1; if (v > 2048) v = 2048; } return v; }
 
 // Smallest float x with (double)(float)(x / (2 w^2)) >= threshold — found by bisection over the floats in their numeric order
 // (IEEE f32 division on the host, the same operation the kernel would do).  +inf if no finite float qualifies.
+#ifndef SVO_LK_PRIOR_TU
 float lk_mineig_cut(int win, double threshold) {
     const float den = (float)(2 * win * win);
     auto key_to_float = [](uint32_t k) { uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; float f; memcpy(&f, &b, 4); return f; };   // increasing in k
@@ -924,6 +997,7 @@ float lk_mineig_cut(int win, double threshold) {
     while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (ok(mid)) hi = mid; else lo = mid; }
     return key_to_float(hi);
 }
+#endif
 
 // The built kernels.  winSize is a mutable member in the reference (vo.h:251), so every square window from 5 to 31 is built for
 // grey input and 5 to 21 for BGR (beyond that a lane would hold three planes of >= 11 pixels of template and search window:
@@ -951,6 +1025,27 @@ static bool lk_dispatch(int win, int cn, bool fs, F&& f) {
     else return false;
 }
 
+// ---- launchers.  The motion-prior kernels (k_lk_chain_prior, k_lk_single_guess) are built in a translation unit of their own
+// (svo_kernels_lk_prior.hip: this file again with SVO_LK_PRIOR_TU defined), so that this one's code object holds exactly the kernels
+// it held before them, at the addresses they had: with the 54 new kernels in the same code object k_lk_chain<21> moved and its
+// launches took 0.1 - 0.2 % longer at the bench shape (measured A/B against the parent library: hipcc-built kernels move that much
+// with their placement).  The two *_grid functions below are that unit's whole interface.
+bool launch_lk_chain_prior_grid(const DevBuffers& d, unsigned blocks, int gx, int chunk, hipStream_t st, int early_out, const PriorRow* prior);
+void launch_lk_single_guess_grid(const DevBuffers& d, int gx, int slotA, int camA, int slotB, int camB, int n, const float2* prev, const float2* guess,
+                                 float2* next, uint8_t* status, hipStream_t st);
+#ifdef SVO_LK_PRIOR_TU
+bool launch_lk_chain_prior_grid(const DevBuffers& d, unsigned blocks, int gx, int chunk, hipStream_t st, int early_out, const PriorRow* prior) {
+    return lk_dispatch(d.cfg.win_w, 1, false, [&](auto w, auto, auto) {
+        hipLaunchKernelGGL((k_lk_chain_prior<w>), dim3(blocks), dim3(64), 0, st, d, gx, chunk, early_out, prior);
+    });
+}
+void launch_lk_single_guess_grid(const DevBuffers& d, int gx, int slotA, int camA, int slotB, int camB, int n, const float2* prev, const float2* guess,
+                                 float2* next, uint8_t* status, hipStream_t st) {
+    lk_dispatch(d.cfg.win_w, 1, false, [&](auto w, auto, auto) {
+        hipLaunchKernelGGL((k_lk_single_guess<w>), dim3(gx), dim3(64), 0, st, d, slotA, camA, slotB, camB, n, prev, guess, next, status);
+    });
+}
+#else
 bool lk_window_supported(int win) { return lk_built(win, 1, false); }
 bool lk_window_supported_cn(int win, int cn) { return lk_built(win, cn, false); }
 
@@ -972,13 +1067,15 @@ int lk_registers_left(const DevBuffers& d) {
     return 512 - waves * alloc;
 }
 
-bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t st, int early_out) {
+bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t st, int early_out, const PriorRow* prior) {
     if (grid_n < 1) grid_n = 1;
     if (grid_n > d.CAP) grid_n = d.CAP;
     const int chunk = lk_chunk();
     int gx = grid_n > LK_MAX_GRID ? LK_MAX_GRID : grid_n;
     gx = (gx + 8 * chunk - 1) / (8 * chunk) * (8 * chunk);           // blocks per sequence: whole runs on every XCD
     const unsigned blocks = (unsigned)gx * (unsigned)launch_seqs(d);
+    // the frame's motion priors (grey, exact sums: the setters refuse every other context): k_lk_chain_prior in k_lk_chain's place, on the same grid
+    if (prior) return d.CN == 1 && !d.cfg.lk_float_sums && launch_lk_chain_prior_grid(d, blocks, gx, chunk, st, early_out, prior);
     // false: no kernel is built for this window / channel count / summation mode; the caller reports it
     return lk_dispatch(d.cfg.win_w, d.CN, d.cfg.lk_float_sums != 0, [&](auto w, auto cn, auto fs) {
         hipLaunchKernelGGL((k_lk_chain<w, cn, fs>), dim3(blocks), dim3(64), 0, st, d, gx, chunk, early_out);
@@ -986,10 +1083,12 @@ bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t st, int early_
 }
 
 void launch_lk_single(const DevBuffers& d, int slotA, int camA, int slotB, int camB, int n, const float2* prev, float2* next,
-                      uint8_t* status, hipStream_t st) {
+                      uint8_t* status, hipStream_t st, const float2* guess) {
     if (n <= 0) return;
     const int gx = n > LK_MAX_GRID ? LK_MAX_GRID : n;
+    if (guess) { launch_lk_single_guess_grid(d, gx, slotA, camA, slotB, camB, n, prev, guess, next, status, st); return; }
     lk_dispatch(d.cfg.win_w, 1, false, [&](auto w, auto, auto) {
         hipLaunchKernelGGL((k_lk_single<w>), dim3(gx), dim3(64), 0, st, d, slotA, camA, slotB, camB, n, prev, next, status);
     });
 }
+#endif

@@ -2,11 +2,13 @@
 """Cost of one optional feature at the bench shape (bench.py's workload: KITTI-00-shaped 1241x376, LK 21x21, maxLevel 3, two
 contexts x 256 sequences, frames resident in HBM, 4 frames in flight per context):
 
-    python tools/feature_bench.py FEATURE [options]        FEATURE: rectify | input_format | pose_cov | detect_mask | clahe | tracks
+    python tools/feature_bench.py FEATURE [options]        FEATURE: rectify | input_format | pose_cov | detect_mask | clahe | tracks | prior
 
 A feature is one entry of FEATURES: its legs (the baseline first: the library as it is without the feature's setter, nothing is
 called), per leg the frame format and a setup(vo, context_index), the svo_get_stage_timing stage it reports, and optionally a
-counter that shows the leg took its path.  Everything else is shared, so every feature is measured the same way: one discarded run
+counter that shows the leg took its path (and `stats`: fields of svo_frame_stats summed over the round).  A setup may return a
+function called before every submit with (vo, T0 frame index per sequence or -1, T1 frame index per sequence): per-frame setters,
+such as the motion prior's.  Everything else is shared, so every feature is measured the same way: one discarded run
 of the baseline leg first (the first leg a process runs is measured 2 - 3 % faster than the same leg later), then --repeat rounds
 with the legs alternating inside every round.  Prints one JSON line (and writes it to --out): per leg and round frame-pairs/s, the
 stage's milliseconds, inliers and the counter; the other legs as multiples of the baseline, round by round and best against best;
@@ -85,6 +87,29 @@ def clahe_on(vo, c):
     vo.set_clahe(2.0, (8, 8))
 
 
+def prior_setup(kind):
+    """the motion-prior legs: before every submit, every sequence with a previous frame gets a prior — the identity (the mechanism's
+    cost: same tracks, one more copy, the prior kernel) or the rotation between the two frames it is about to track (what it buys)"""
+    def setup(vo, c):
+        from stereo_visual_odometry_amd import api
+        table = {}
+
+        def before(vo, f0, f1):
+            Hs, His = np.zeros((vo.n_seq, 3, 3), np.float32), np.zeros((vo.n_seq, 3, 3), np.float32)
+            for i, (a, b) in enumerate(zip(f0, f1)):
+                if a < 0:
+                    continue
+                if (a, b) not in table:
+                    R = np.eye(3) if kind == "identity" else (np.linalg.inv(POSES[a]) @ POSES[b])[:3, :3].T
+                    table[(a, b)] = api.motion_prior_from_rotation(PL, R)
+                Hs[i], His[i] = table[(a, b)]
+            vo.set_motion_priors(Hs, has=[a >= 0 for a in f0], His=His)
+        return before
+    return setup
+
+
+POSES, PL = [], None                                  # the pool's camera poses per frame and the left projection matrix (main fills them)
+
 # legs: name -> (frame format, setup), the baseline first.  evidence: (name, f(vo, leg, frame_bytes) read after every recorded
 # collect and summed over the round, whether the sum is divided by the round's frame pairs)
 FEATURES = dict(
@@ -102,6 +127,9 @@ FEATURES = dict(
     tracks=dict(stage="pnp",                          # the rows of sequence 0 only: reading all of them would be timed with the leg
                 evidence=("rows_of_sequence_0", lambda vo, leg, nbytes: len(vo.last_track_obs(0)) if leg != "off" else 0, False),
                 legs=dict(off=("rendered", nothing), on=("rendered", lambda vo, c: vo.set_track_output(2048)))),
+    prior=dict(stage="lk", evidence=("prior_frames", lambda vo, leg, nbytes: int(bool(vo.last_frame_path() & 2048)), False),   # SVO_PATH_MOTION_PRIOR
+               stats=("n_after_circular", "lk_newton_steps"),
+               legs=dict(off=("rendered", nothing), identity=("rendered", prior_setup("identity")), rotation=("rendered", prior_setup("rotation")))),
 )
 
 
@@ -118,6 +146,7 @@ def main():
     ap.add_argument("--legs", default=None, help="comma-separated, default: every leg of the feature")
     ap.add_argument("--repeat", type=int, default=3, help="rounds of the legs, alternating them in every round")
     ap.add_argument("--package", default=None, help="directory holding the stereo_visual_odometry_amd package to import (default: this checkout)")
+    ap.add_argument("--yaw-amp", type=float, default=None, help="yaw_amp_deg of the rendered scenes (default: the bench's); the per-frame yaw step is at most yaw_amp * 2 pi / 16")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
 
@@ -139,8 +168,13 @@ def main():
     cal = syn.KITTI00
     W, H, F, B, C = cal["width"], cal["height"], args.frames, args.seqs, args.contexts
     Bc = B // C
-    pool = bench.render_pool([dict(cal=cal, n_frames=F, seed=0x5EED0002 + g, movers=0.3, step=0.5, cell_px=16.6) for g in range(args.pool)],
-                             max(1, min(16, bench.host_cores())))
+    scene = dict(cal=cal, n_frames=F, movers=0.3, step=0.5, cell_px=16.6)
+    if args.yaw_amp is not None:
+        scene["yaw_amp_deg"] = args.yaw_amp
+    pool = bench.render_pool([dict(scene, seed=0x5EED0002 + g) for g in range(args.pool)], max(1, min(16, bench.host_cores())))
+    global PL
+    POSES[:] = pool[0].poses                           # the same trajectory in every scene of the pool: the seed only draws the texture
+    PL = syn.projection_matrices(cal)[0]
     gen = torch.Generator(device="cpu"); gen.manual_seed(1)
 
     def frames_of(side, fmt):
@@ -181,24 +215,32 @@ def main():
                 rp.append(right.data_ptr() + (g * F + f) * img)
             return lp, rp
 
-        vos = []
+        def frame_ids(step, c):
+            return [ping_pong(step + (b // args.pool) * 3) for b in range(c * Bc, (c + 1) * Bc)]
+
+        vos, hooks = [], []
         for c in range(C):
             v = api.BatchVisualOdometry(W, H, Bc, api.default_config(**over))
             v.initalize_projection_matricies(Pl, Pr)
             v.set_stage_timing(True)
             if BPP[fmt] != 1:
                 v.set_input_format(fmt)
-            setup(v, c)
+            hooks.append(setup(v, c))
             vos.append(v)
         ms, inl, seen = [], [], 0
+        sums = {k: 0 for k in feature.get("stats", ())}
+        ok_frames = 0
 
         def run(first, count, record):
-            nonlocal seen
+            nonlocal seen, ok_frames
             sub = col = 0
             while col < count:
                 while sub < count and sub - col < args.depth:
                     for c, vo in enumerate(vos):
                         lp, rp = ptrs(first + sub, c)
+                        if hooks[c]:
+                            s = first + sub
+                            hooks[c](vo, frame_ids(s - 1, c) if s > 0 else [-1] * Bc, frame_ids(s, c))
                         vo.submit_device(lp, rp, W * BPP[fmt])
                     sub += 1
                 for vo in vos:
@@ -206,6 +248,9 @@ def main():
                     if record:
                         ms.append(vo.stage_timing()[feature["stage"]])
                         inl.append(sum(s.n_inliers for s in vo.stats))
+                        ok_frames += sum(s.fail_reason == 0 for s in vo.stats)
+                        for k in sums:
+                            sums[k] += sum(getattr(s, k) for s in vo.stats)
                         if feature["evidence"]:
                             seen += feature["evidence"][1](vo, leg, img)
                 col += 1
@@ -219,6 +264,8 @@ def main():
             v.close()
         del left, right
         r = {"frame_pairs_per_s": B * args.steps / dt, stage_field: float(np.mean(ms)), "inliers": int(np.sum(inl))}
+        if sums:
+            r.update(sums, ok_frames=int(ok_frames))
         if feature["evidence"]:
             r[feature["evidence"][0]] = seen // (B * args.steps) if feature["evidence"][2] else seen
         return r

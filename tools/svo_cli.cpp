@@ -28,6 +28,9 @@
 // `--tracks file.csv` switches the track output on (svo.h, svo_set_track_output) and writes one line per observation row,
 // `frame,id,ul,vl,ur,vr,x,y,z,age,inlier,has_xyz`: this frame's stereo observation (l1, r1) of landmark `id`, and the point
 // triangulated from the previous frame's pair, in the previous frame's left camera frame.
+// `--prior file.csv` gives frame i the motion prior of line i (svo.h, svo_set_motion_prior): nine numbers, the row-major homography
+// that maps pixels of frame i - 1 to predicted pixels of frame i; an empty line (and every line past the file's end, and line 0)
+// means no prior for that frame.  Needs --gray 1 or 2.
 #include <zlib.h>
 #include <cmath>
 #include <cstdio>
@@ -169,10 +172,10 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv] [--prior file.csv]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
-    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path, tracks_out;
+    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path, tracks_out, prior_path;
     bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false, clahe = false;
     double clahe_clip = 2.0; int clahe_tx = 8, clahe_ty = 8;
     for (int i = 3; i + 1 < argc; i += 2) {
@@ -187,6 +190,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
         else if (!strcmp(argv[i], "--covariance")) cov_out = argv[i + 1];   // one row per frame: valid, then the 21 upper-triangle entries of cov_T (svo.h), row by row
         else if (!strcmp(argv[i], "--tracks")) tracks_out = argv[i + 1];    // one line per observation row of every frame (svo.h, svo_track_obs)
+        else if (!strcmp(argv[i], "--prior")) prior_path = argv[i + 1];     // one line of 9 numbers per frame (svo.h, motion prior); an empty line: no prior
         else if (!strcmp(argv[i], "--mask")) mask_path = argv[i + 1];       // a static detection mask (svo.h): PGM or PNG of the frame size, non-zero = features allowed; needs --gray 1 or 2
         else if (!strcmp(argv[i], "--clahe")) {                             // clip,tx,ty: CLAHE on the grey frames inside frame ingest (svo.h); needs --gray 1 or 2
             if (std::sscanf(argv[i + 1], "%lf,%d,%d", &clahe_clip, &clahe_tx, &clahe_ty) != 3) { std::fprintf(stderr, "--clahe needs clip,tx,ty (e.g. 2.0,8,8)\n"); return 2; }
@@ -216,6 +220,19 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> d;
         if (read_file(mask_path, d)) mask = mask_path.size() > 4 && mask_path.substr(mask_path.size() - 4) == ".png" ? read_png(d) : read_pgm(d);
         if (!mask.ok()) { std::fprintf(stderr, "cannot read mask %s\n", mask_path.c_str()); return 2; }
+    }
+    std::vector<std::vector<float>> priors;                           // [frame] 9 numbers, or empty
+    if (!prior_path.empty()) {
+        std::ifstream pf(prior_path);
+        if (!pf) { std::fprintf(stderr, "cannot read %s\n", prior_path.c_str()); return 2; }
+        for (std::string line; std::getline(pf, line);) {
+            for (char& ch : line) if (ch == ',' || ch == ';' || ch == '\r') ch = ' ';
+            std::vector<float> h;
+            std::istringstream is(line);
+            for (float v; is >> v;) h.push_back(v);
+            if (!h.empty() && h.size() != 9) { std::fprintf(stderr, "--prior: line %zu has %zu numbers, not 9\n", priors.size() + 1, h.size()); return 2; }
+            priors.push_back(h);
+        }
     }
     std::ofstream cov;
     if (!cov_out.empty()) {
@@ -258,6 +275,7 @@ int main(int argc, char** argv) {
                 std::getline(gt, xs, ','); std::getline(gt, ys, ','); std::getline(gt, dxs, ','); std::getline(gt, dys, ',');
                 gtx = atof(xs.c_str()); gty = atof(ys.c_str());
             }
+            if (i > 0 && (size_t)i < priors.size() && !priors[i].empty()) vo.set_motion_prior(priors[i].data());   // consumed by this frame
             auto o = gray ? vo.stereo_callback(Image(l.px.data(), l.h, l.w), Image(r.px.data(), r.h, r.w))
                           : vo.stereo_callback(Image(l.bgr.data(), l.h, l.w, 0, 3), Image(r.bgr.data(), r.h, r.w, 0, 3));
             matmul4(pose, o.second.data(), pose);                                                         // applied even when !ok (main.cpp:394-396)
