@@ -510,6 +510,43 @@ int svo_set_motion_prior(svo_context* ctx, int seq, const float H[9], const floa
 int svo_set_motion_priors(svo_context* ctx, const float* H /* n_seq x 9 */, const float* Hi /* n_seq x 9 or NULL */, const uint8_t* has /* n_seq or NULL = all */);
 int svo_get_motion_prior(svo_context* ctx, int seq, float H[9], float Hi[9], int* pending);
 int svo_motion_prior_from_rotation(const float Pl[12], const double R[9], float H[9], float Hi[9]);
+/* Predicted priors: the prior from each sequence's own last pose, computed on the device.  With frames in flight the host has not
+ * seen frame k-1's pose when it submits frame k, so it cannot hand that pose over through the setters above without collecting
+ * first; the rotation is on the device already, on the stream the next frame runs on.  In SVO_PRIOR_LAST_ROTATION one small launch
+ * (k_prior_predict, one thread per sequence that takes the frame) at the head of every frame turns it into the frame's prior rows.
+ *
+ * The rule, per sequence that takes a frame:
+ *  1. A pending explicit prior (svo_set_motion_prior / svo_set_motion_priors) wins: it is consumed as always, its bits untouched.
+ *  2. Otherwise, in SVO_PRIOR_LAST_ROTATION, the sequence gets a predicted prior if the last frame it took returned ok = 1 and it
+ *     has not been reset since (svo_reset_sequence: the first frames after a reset get none).  An idle frame writes no state, so a
+ *     sequence that resumes after a pause predicts from the last frame it took, however many frames it sat out.  The prior is
+ *       H = f32(K R K^-1),  Hi = f32(K Rt K^-1),
+ *     K = Pl[:, :3] of the sequence's left projection matrix, R the rotation that frame's solve ended with: the transpose of the
+ *     upper-left 3x3 of the transform it returned, R[i][j] = T[4 j + i] (the inverse transform stores Rt exactly).  The arithmetic is
+ *     svo_motion_prior_from_rotation's: f64 throughout, K^-1 by the adjugate divided by det = k0 C00 + k1 C01 + k2 C02, a product's
+ *     three terms summed left to right ((a b + c d) + e f), K R first and then (K R) K^-1, nothing fused, each entry rounded to f32
+ *     once.  A singular K, or a non-finite entry in K, R, H or Hi, gives no prior.
+ *  3. Otherwise the sequence has no prior in this frame and tracks exactly as without the feature, bit for bit.  A failed frame
+ *     therefore seeds nothing: a bad pose cannot feed on itself, and the frame after it searches from the features' own positions.
+ * Host equivalent: a context in SVO_PRIOR_EXPLICIT that collects every frame and, before the next submit, calls
+ * svo_motion_prior_from_rotation(Pl, R, H, Hi) and svo_set_motion_prior(ctx, seq, H, Hi) for every sequence whose collected frame
+ * returned ok = 1 (R from that frame's T as above) submits the same frames: the same 18 floats, the same results in every bit.
+ *
+ * svo_set_motion_prior_mode: host state carried per frame, like the input format — legal with frames in flight, in force from the
+ * next submit.  SVO_PRIOR_EXPLICIT (the default) is everything above this paragraph and nothing else: a context that never sets the
+ * mode launches exactly what it always did.  While SVO_PRIOR_LAST_ROTATION is set every frame some sequence takes launches
+ * k_prior_predict and k_lk_chain_prior, reports SVO_PATH_MOTION_PRIOR | SVO_PATH_PRIOR_PREDICTED, and under SVO_GRAPH=1 runs from
+ * the launch list; a frame on which every sequence is idle launches neither.  The frame entry points only: svo_circular_matching
+ * and the stage calls are unchanged.  SVO_ERR_ARG: an unknown mode, a channels = 3 context, an lk_float_sums = 1 context.
+ * svo_get_last_motion_prior: what the frame last collected used for seq — *source 0 none (H, Hi untouched), 1 an explicit prior,
+ * 2 a predicted one; H and Hi (each may be NULL) are the 18 floats k_lk_chain_prior read.  An idle sequence of that frame reports
+ * 0.  Host memory only, no synchronisation.  SVO_ERR_STATE before the first collect; a context that never had a prior reports 0. */
+#define SVO_PRIOR_EXPLICIT      0   /* default: only what the setters give */
+#define SVO_PRIOR_LAST_ROTATION 1   /* a sequence without an explicit prior for a frame gets one predicted from its last pose */
+#define SVO_PATH_PRIOR_PREDICTED 4096 /* svo_get_last_frame_path: the frame was issued in SVO_PRIOR_LAST_ROTATION and ran k_prior_predict */
+int svo_set_motion_prior_mode(svo_context* ctx, int mode);
+int svo_get_motion_prior_mode(svo_context* ctx, int* mode);
+int svo_get_last_motion_prior(svo_context* ctx, int seq, float H[9], float Hi[9], int* source);
 
 /* Diagnostics (pyramid tests): one level of one stored pyramid of sequence seq, WITH its stored border — every level keeps a
  * REFLECT_101 border of `pad` pixels on each side (the LK kernel reads it directly), as cv::buildOpticalFlowPyramid keeps its

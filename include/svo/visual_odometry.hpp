@@ -213,6 +213,7 @@ class VisualOdometry {                                               // include/
             if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
             if (clahe_on_) svo_throw(svo_set_clahe(ctx_, 1, clahe_clip_, clahe_tx_, clahe_ty_));
             if (track_rows_ > 0) svo_throw(svo_set_track_output(ctx_, 1, track_rows_));
+            if (prior_mode_ != SVO_PRIOR_EXPLICIT) svo_throw(svo_set_motion_prior_mode(ctx_, prior_mode_));
             if (!mask_.empty()) {
                 if ((int)mask_.size() != width_ * height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
                 svo_throw(svo_set_detection_mask(ctx_, -1, mask_.data(), width_, 0));
@@ -406,6 +407,22 @@ class VisualOdometry {                                               // include/
         svo_throw(svo_motion_prior_from_rotation(leftCameraProjection_.data(), R, H, Hi));
         set_motion_prior(H, Hi);
     }
+    // Without a gyro: SVO_PRIOR_LAST_ROTATION makes every stereo_callback that has no explicit prior predict one on the device from
+    // the rotation of the last frame, when that frame gave a pose (svo_set_motion_prior_mode; svo.h has the rule).  Before the first
+    // frame the mode is kept and applied when the context is created; an unknown mode throws at once.
+    void set_motion_prior_mode(int mode) {
+        if (mode != SVO_PRIOR_EXPLICIT && mode != SVO_PRIOR_LAST_ROTATION) throw std::runtime_error("set_motion_prior_mode: unknown mode");
+        if (ctx_) svo_throw(svo_set_motion_prior_mode(ctx_, mode));
+        prior_mode_ = mode;
+    }
+    // What the last stereo_callback used (svo_get_last_motion_prior): source 0 none, 1 explicit, 2 predicted; H, Hi valid when != 0.
+    struct MotionPrior { std::array<float, 9> H, Hi; int source; };
+    MotionPrior last_motion_prior() const {
+        if (!ctx_) throw std::runtime_error("last_motion_prior: no frame yet (call stereo_callback first)");
+        MotionPrior p{};
+        svo_throw(svo_get_last_motion_prior(ctx_, 0, p.H.data(), p.Hi.data(), &p.source));
+        return p;
+    }
 
     // functor form for boost::bind / message_filters style registration (src/stereo_vo.cpp:61-62)
     void operator()(const Image& l, const Image& r) { stereo_callback(l, r); }
@@ -439,6 +456,7 @@ class VisualOdometry {                                               // include/
     int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
     std::vector<uint8_t> mask_;                                       // set_detection_mask before the first frame: installed at creation
     int track_rows_ = 0;                                              // set_track_output (likewise); 0: off
+    int prior_mode_ = SVO_PRIOR_EXPLICIT;                             // set_motion_prior_mode (likewise)
     bool clahe_on_ = false; double clahe_clip_ = 2.0; int clahe_tx_ = 8, clahe_ty_ = 8;   // set_clahe (applied once the context exists)
 };
 

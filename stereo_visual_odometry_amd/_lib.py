@@ -115,6 +115,15 @@ lib.svo_get_motion_prior.restype = C.c_int
 lib.svo_get_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
 lib.svo_motion_prior_from_rotation.restype = C.c_int
 lib.svo_motion_prior_from_rotation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+PATH_PRIOR_PREDICTED = 4096
+PRIOR_EXPLICIT, PRIOR_LAST_ROTATION = 0, 1
+PRIOR_MODES = {"explicit": PRIOR_EXPLICIT, "last_rotation": PRIOR_LAST_ROTATION}
+lib.svo_set_motion_prior_mode.restype = C.c_int
+lib.svo_set_motion_prior_mode.argtypes = [C.c_void_p, C.c_int]
+lib.svo_get_motion_prior_mode.restype = C.c_int
+lib.svo_get_motion_prior_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+lib.svo_get_last_motion_prior.restype = C.c_int
+lib.svo_get_last_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
 lib.svo_lk_track_guess.restype = C.c_int
 lib.svo_lk_track_guess.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
@@ -200,6 +209,7 @@ EXPORTS = [
     "svo_set_track_output", "svo_get_last_track_obs", "svo_get_feature_ids",
     "svo_set_motion_prior", "svo_set_motion_priors", "svo_get_motion_prior", "svo_motion_prior_from_rotation",
     "svo_lk_track_guess", "svo_circular_match_prior",
+    "svo_set_motion_prior_mode", "svo_get_motion_prior_mode", "svo_get_last_motion_prior",
 ]
 
 

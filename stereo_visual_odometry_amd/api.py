@@ -570,6 +570,28 @@ class BatchVisualOdometry:
         check(lib.svo_get_motion_prior(self._h, seq, ptr(H), ptr(Hi), C.byref(pending)))
         return (H.reshape(3, 3), Hi.reshape(3, 3)) if pending.value else None
 
+    def set_motion_prior_mode(self, mode):
+        """"last_rotation": every sequence without an explicit prior for a frame gets one predicted on the device from its own last
+        pose (svo_set_motion_prior_mode, SVO_PRIOR_LAST_ROTATION; svo.h has the rule) — the prior for callers without a gyro, and
+        the one that works with frames in flight.  "explicit" (the default): only what the setters give.  In force from the next
+        submit.  SvoError for a BGR or float-sums context."""
+        if mode not in _lib.PRIOR_MODES:
+            raise ValueError("motion prior mode: one of %s expected" % sorted(_lib.PRIOR_MODES))
+        check(lib.svo_set_motion_prior_mode(self._h, _lib.PRIOR_MODES[mode]))
+
+    def motion_prior_mode(self):
+        m = C.c_int(0)
+        check(lib.svo_get_motion_prior_mode(self._h, C.byref(m)))
+        return {v: k for k, v in _lib.PRIOR_MODES.items()}[m.value]
+
+    def last_motion_prior(self, seq=0):
+        """The prior the frame last collected used for sequence `seq` (svo_get_last_motion_prior) -> (H, Hi, source) with source 1
+        an explicit prior, 2 a predicted one; None when it used none."""
+        H, Hi = np.zeros(9, np.float32), np.zeros(9, np.float32)
+        src = C.c_int(0)
+        check(lib.svo_get_last_motion_prior(self._h, seq, ptr(H), ptr(Hi), C.byref(src)))
+        return (H.reshape(3, 3), Hi.reshape(3, 3), src.value) if src.value else None
+
     def set_detection_mask(self, mask, seq=-1):
         """Keep features off the zero pixels of `mask` (svo_set_detection_mask): an (height, width) uint8 numpy array, or a torch
         device tensor of that shape and dtype, read through data_ptr() with its own row stride (its producer must have finished,
@@ -911,6 +933,21 @@ class VisualOdometry(BatchVisualOdometry):
         # before the first frame: held, handed to the context when it is created — and consumed, unused, by that first frame
         self._prior = None if H is None else (_h9(H, "H").copy(), None if Hi is None else _h9(Hi, "Hi").copy())
 
+    def set_motion_prior_mode(self, mode):
+        if self._created:
+            return super().set_motion_prior_mode(mode)
+        if mode not in _lib.PRIOR_MODES:
+            raise ValueError("motion prior mode: one of %s expected" % sorted(_lib.PRIOR_MODES))
+        self._prior_mode = mode                                       # applied when the first frame creates the context
+
+    def motion_prior_mode(self):
+        return super().motion_prior_mode() if self._created else getattr(self, "_prior_mode", "explicit")
+
+    def last_motion_prior(self, seq=0):
+        if not self._created:
+            raise _lib.SvoError("last_motion_prior: no frame yet (call stereo_callback first)")
+        return super().last_motion_prior(seq)
+
     def set_rotation_prior(self, R, seq=-1, Pl=None):
         if Pl is None and self._P is not None:
             Pl = self._P[0]
@@ -962,6 +999,8 @@ class VisualOdometry(BatchVisualOdometry):
             if getattr(self, "_prior", None) is not None:
                 super().set_motion_prior(self._prior[0], self._prior[1])
                 self._prior = None
+            if getattr(self, "_prior_mode", None) is not None:
+                super().set_motion_prior_mode(self._prior_mode)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

@@ -100,6 +100,7 @@ struct RingSlot {
     int cov_mode = SVO_COV_OFF;                  // the pose-covariance mode the slot's frame was issued with
     bool masked = false;                         // ... and whether it came with a mask (h_act's row then holds its flags)
     bool tracks = false;                         // ... and whether it carried track ids and wrote its observation rows
+    bool priors = false;                         // ... and whether it had motion-prior rows (h_prior's row then holds them)
 };
 // Detection masks (svo_set_detection_mask): the two slots of one scope (a sequence, or the shared pair).  cur: the slot in force for
 // the frames submitted from now on (-1: none); last: the slot the most recent frame of this scope recorded for its left image — that
@@ -212,8 +213,16 @@ struct svo_context {
     // k_lk_chain_prior reads.  A slot's rows are free once its frame has been collected, so every frame in flight keeps its own.
     std::vector<PriorRow> prior_next;            // [B]
     int n_prior = 0;                             // how many of them are pending
-    PriorRow* h_prior = nullptr;                 // pinned [SVO_RING][B]
+    PriorRow* h_prior = nullptr;                 // pinned [SVO_RING][B], mapped: k_prior_predict writes the rows it predicts in place
     PriorRow* d_prior = nullptr;                 // device [SVO_RING][B]
+    // SVO_PRIOR_LAST_ROTATION (svo_set_motion_prior_mode): host state read when a frame is enqueued, like the input format.  A frame
+    // issued in this mode always has its device row; k_prior_predict, first on the frame's stream, fills the rows no explicit prior
+    // filled.  h_prior_act: the frame's own list of the sequences that take it, for that kernel alone (mapped, read in place).
+    int prior_mode = SVO_PRIOR_EXPLICIT;
+    PriorRow* hd_prior = nullptr;                // h_prior as the device sees it
+    int* h_prior_act = nullptr;                  // pinned [SVO_RING][B], mapped
+    int* hd_prior_act = nullptr;
+    std::vector<PriorRow> last_prior;            // [B]: the rows of the frame last collected (svo_get_last_motion_prior); empty: it had none
 };
 
 // a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
@@ -396,7 +405,7 @@ extern "C" void svo_destroy(svo_context* c) {
     for (void* p : {(void*)c->h_mask_rows, (void*)c->h_mask_stage}) if (p) (void)hipHostFree(p);
     if (c->ev_mask_stage) (void)hipEventDestroy(c->ev_mask_stage);
     for (void* p : {(void*)c->clahe_buf, (void*)c->clahe_lut, (void*)c->d_prior}) if (p) (void)hipFree(p);
-    if (c->h_prior) (void)hipHostFree(c->h_prior);
+    for (void* p : {(void*)c->h_prior, (void*)c->h_prior_act}) if (p) (void)hipHostFree(p);
     for (RingSlot& r : c->ring) {
         for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
         if (r.ev_img) (void)hipEventDestroy(r.ev_img);
@@ -567,10 +576,14 @@ static int front_ahead(svo_context* c, DevBuffers& f, int slot, int stride) {
 // The launch list of one frame (vo.cpp:41-137 as kernels), between the slot's start and done events.
 // with_events: record the stage-boundary events (not inside a graph capture).  n_act: see frame_view.
 // mrows: the frame's row of d_mask_rows when its detection applies a mask to some sequence (enqueue_frame), else null.
-// prow: the frame's device row of motion priors when some active sequence has one (take_priors), else null.
+// pri: the frame's motion priors (take_priors) — rows: its device row when some active sequence has an explicit prior or the frame
+// predicts (SVO_PRIOR_LAST_ROTATION), else null; predict: k_prior_predict fills the rows no explicit prior filled; uploaded: the
+// explicit rows were copied into the device row.
+struct FramePriors { PriorRow* rows = nullptr; bool predict = false, uploaded = false; };
 static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, DeviceSharing share, int n_act = -1,
-                       const uint8_t* const* mrows = nullptr, const PriorRow* prow = nullptr) {
+                       const uint8_t* const* mrows = nullptr, const FramePriors& pri = FramePriors()) {
     hipStream_t s = c->stream;
+    const PriorRow* const prow = pri.rows;
     const auto record = [&](StageEvent which) { return with_events ? hipEventRecord(c->ring[slot].ev[which], s) : hipSuccess; };
     if (n_act == 0) {                                                  // all idle: the result rows are the whole frame
         HIPCHK(upload_act(c, slot, s));
@@ -579,6 +592,11 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
         c->begin_recorded = false; c->last_path = 0;
         return SVO_OK;
     }
+    // the predicted priors first: SeqState::ok and R are the previous frame's (k_pnp_final ran on this stream) until the per-frame
+    // reset below clears ok — the PYR_BEGIN ingest, the fused front, or launch_frame_begin behind front_ahead
+    if (pri.predict)
+        launch_prior_predict(c->d, n_act >= 0 ? c->hd_prior_act + (size_t)slot * c->d.B : nullptr, n_act >= 0 ? n_act : c->d.B, pri.uploaded,
+                             pri.rows, c->hd_prior + (size_t)slot * c->d.B, s);
     HIPCHK(choose_pnp_build(c->d, share.lean));
     DevBuffers f = frame_view(c, slot, n_act);                         // after the build choice: co_resident travels in the view
     int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0) |
@@ -617,7 +635,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     }
     HIPCHK(record(EV_LK0));
     if (!launch_lk_chain(f, gn, s, 1, prow)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // with priors: k_lk_chain_prior, the LK launch of this frame in every respect
-    if (prow) path |= SVO_PATH_MOTION_PRIOR;
+    if (prow) path |= SVO_PATH_MOTION_PRIOR | (pri.predict ? SVO_PATH_PRIOR_PREDICTED : 0);
     HIPCHK(record(EV_LK1));
     if (gate) {
         std::lock_guard<std::mutex> lock(gate->mu);
@@ -752,10 +770,14 @@ static int take_masks(svo_context* c, int slot, const uint8_t* active, const uin
 
 // Motion priors of one frame: every active sequence with a pending prior hands it to this frame (one-shot: it is consumed here) —
 // idle sequences keep theirs.  *prow: the frame's device row, filled by one copy on the frame's stream from the slot's pinned row,
-// when some active sequence has one; else null, and the frame is an ordinary one.
-static int take_priors(svo_context* c, int slot, const uint8_t* active, const PriorRow** prow) {
-    *prow = nullptr;
-    if (c->n_prior == 0) return SVO_OK;
+// when some active sequence has one; else null, and the frame is an ordinary one.  In SVO_PRIOR_LAST_ROTATION the frame always has
+// its device row and k_prior_predict fills what no explicit prior filled: the copy is then made only when one was taken, and the
+// slot's list of the sequences that take the frame is written for that kernel.
+static int take_priors(svo_context* c, int slot, const uint8_t* active, FramePriors* pri) {
+    *pri = FramePriors();
+    const bool predict = c->prior_mode == SVO_PRIOR_LAST_ROTATION;
+    c->ring[slot].priors = false;
+    if (c->n_prior == 0 && !predict) return SVO_OK;
     const int B = c->d.B;
     PriorRow* row = c->h_prior + (size_t)slot * B;
     bool any = false;
@@ -763,12 +785,17 @@ static int take_priors(svo_context* c, int slot, const uint8_t* active, const Pr
         PriorRow& p = c->prior_next[i];
         const bool take = p.has && (!active || active[i]);
         if (take) { row[i] = p; p.has = 0; c->n_prior--; any = true; }
-        else row[i].has = 0;
+        else { row[i].has = 0; row[i].source = 0; }
     }
-    if (!any) return SVO_OK;
+    if (!any && !predict) return SVO_OK;
     PriorRow* drow = c->d_prior + (size_t)slot * B;
-    HIPCHK(hipMemcpyAsync(drow, row, sizeof(PriorRow) * (size_t)B, hipMemcpyHostToDevice, c->stream));
-    *prow = drow;
+    if (any) HIPCHK(hipMemcpyAsync(drow, row, sizeof(PriorRow) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    if (predict && active) {
+        int* list = c->h_prior_act + (size_t)slot * B;
+        for (int i = 0, n = 0; i < B; i++) if (active[i]) list[n++] = i;
+    }
+    pri->rows = drow; pri->predict = predict; pri->uploaded = any;
+    c->ring[slot].priors = true;
     return SVO_OK;
 }
 
@@ -804,13 +831,13 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
     HIPCHK(hipEventRecord(r.ev[EV_F0], c->stream));
     const uint8_t* const* mrows = nullptr;
     if ((rc = take_masks(c, slot, active, &mrows)) != SVO_OK) return rc;
-    const PriorRow* prow = nullptr;
-    if ((rc = take_priors(c, slot, active, &prow)) != SVO_OK) return rc;
+    FramePriors pri;
+    if ((rc = take_priors(c, slot, active, &pri)) != SVO_OK) return rc;
     bool replayed = false;
     if (c->track_on && slot == c->last_obs_slot) keep_last_obs(c);    // the frame is about to write the slot svo_get_last_track_obs still reads
-    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on && !c->track_on && !prow)   // a ragged, rectifying, masked, CLAHE, track-ids or motion-prior frame runs from the launch list
+    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on && !c->track_on && !pri.rows)   // a ragged, rectifying, masked, CLAHE, track-ids or motion-prior frame runs from the launch list
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
-    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows, prow)) != SVO_OK) return rc;
+    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows, pri)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
     r.cov_mode = c->cov_mode; r.masked = active != nullptr; r.tracks = c->track_on;
     c->staged_inputs = false;
@@ -848,6 +875,11 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
         const int* flags = ring_row(c, c->h_act, slot) + B;
         for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) hdr[2 * i] = hdr[2 * i + 1] = 0;
         c->last_obs_slot = slot; c->last_obs_rows = c->track_rows;
+    }
+    c->last_prior.clear();
+    if (c->ring[slot].priors) {                                      // the slot's pinned row: the host's explicit rows, k_prior_predict's in place; idle sequences took none
+        const PriorRow* row = c->h_prior + (size_t)slot * B;
+        c->last_prior.assign(row, row + B);
     }
     c->last_slot = slot;
     c->tail = (c->tail + 1) % SVO_RING; c->inflight--; c->n_collected++;
@@ -999,7 +1031,7 @@ static int set_state(svo_context* c, const SeqState& hs);
 // One prior as the kernels take it (svo_prior.hpp has the arithmetic): H checked, Hi the caller's or H's inverse rounded to f32.
 static int make_prior_row(const float* H, const float* Hi, PriorRow* out) {
     if (const char* err = prior_make(H, Hi, out->H, out->Hi)) return fail_arg(err);
-    out->has = 1; out->pad = 0;
+    out->has = 1; out->source = 0;
     return SVO_OK;
 }
 // can this context take a prior at all?  (k_lk_chain_prior is the grey, exact-sums build)
@@ -1012,12 +1044,23 @@ static int check_prior_context(const svo_context* c) {
 static int prior_buffers(svo_context* c) {
     if (c->d_prior) return SVO_OK;
     HIPCHK(hipSetDevice(c->device));
-    const size_t bytes = sizeof(PriorRow) * SVO_RING * (size_t)c->d.B;
+    const size_t bytes = sizeof(PriorRow) * SVO_RING * (size_t)c->d.B, act_bytes = sizeof(int) * SVO_RING * (size_t)c->d.B;
     PriorRow *h = nullptr, *dv = nullptr;
-    HIPCHK(hipHostMalloc((void**)&h, bytes));
-    if (hipMalloc((void**)&dv, bytes) != hipSuccess) { (void)hipHostFree(h); g_err = "motion prior: hipMalloc failed"; return SVO_ERR_HIP; }
-    memset(h, 0, bytes);
-    c->h_prior = h; c->d_prior = dv;
+    int* ha = nullptr;
+    void *hd = nullptr, *had = nullptr;
+    bool ok = hipHostMalloc((void**)&h, bytes, hipHostMallocMapped) == hipSuccess && hipHostMalloc((void**)&ha, act_bytes, hipHostMallocMapped) == hipSuccess &&
+              hipHostGetDevicePointer(&hd, h, 0) == hipSuccess && hipHostGetDevicePointer(&had, ha, 0) == hipSuccess &&
+              hipMalloc((void**)&dv, bytes) == hipSuccess;
+    ok = ok && hipMemsetAsync(dv, 0, bytes, c->stream) == hipSuccess;  // on the frames' stream: before any frame that names the rows
+    if (!ok) {
+        (void)hipGetLastError();
+        if (h) (void)hipHostFree(h);
+        if (ha) (void)hipHostFree(ha);
+        if (dv) (void)hipFree(dv);
+        g_err = "motion prior: buffer allocation failed"; return SVO_ERR_HIP;
+    }
+    memset(h, 0, bytes); memset(ha, 0, act_bytes);
+    c->h_prior = h; c->d_prior = dv; c->hd_prior = (PriorRow*)hd; c->h_prior_act = ha; c->hd_prior_act = (int*)had;
     c->prior_next.assign((size_t)c->d.B, PriorRow{});
     return SVO_OK;
 }
@@ -1061,6 +1104,33 @@ extern "C" int svo_get_motion_prior(svo_context* c, int seq, float H[9], float H
     if (pending) *pending = on ? 1 : 0;
     if (on && H) memcpy(H, c->prior_next[seq].H, sizeof(float) * 9);
     if (on && Hi) memcpy(Hi, c->prior_next[seq].Hi, sizeof(float) * 9);
+    return SVO_OK;
+}
+
+extern "C" int svo_set_motion_prior_mode(svo_context* c, int mode) {
+    if (!c) return fail_arg("null context");
+    if (mode != SVO_PRIOR_EXPLICIT && mode != SVO_PRIOR_LAST_ROTATION) return fail_arg("unknown motion prior mode");
+    int rc = check_prior_context(c); if (rc != SVO_OK) return rc;
+    if (mode == SVO_PRIOR_LAST_ROTATION && (rc = prior_buffers(c)) != SVO_OK) return rc;
+    c->prior_mode = mode;                                                         // host state: the frames submitted from now on
+    return SVO_OK;
+}
+
+extern "C" int svo_get_motion_prior_mode(svo_context* c, int* mode) {
+    if (!c || !mode) return fail_arg("null argument");
+    *mode = c->prior_mode;
+    return SVO_OK;
+}
+
+extern "C" int svo_get_last_motion_prior(svo_context* c, int seq, float H[9], float Hi[9], int* source) {
+    if (!c || !source || seq < 0 || seq >= c->d.B) return fail_arg("bad context / seq / null source");
+    if (c->last_slot < 0) { g_err = "svo_get_last_motion_prior: no frame collected yet"; return SVO_ERR_STATE; }
+    *source = 0;
+    if (c->last_prior.empty() || !c->last_prior[seq].has) return SVO_OK;         // the frame had no prior rows, or none for seq
+    const PriorRow& p = c->last_prior[seq];
+    *source = p.source == PRIOR_SOURCE_PREDICTED ? 2 : 1;
+    if (H) memcpy(H, p.H, sizeof(float) * 9);
+    if (Hi) memcpy(Hi, p.Hi, sizeof(float) * 9);
     return SVO_OK;
 }
 

@@ -198,10 +198,9 @@ struct IdArgs { long long* feat_id[2]; long long* track_id; long long* next_id; 
 // One frame's rows of the pinned observation ring: rows [B][max_rows], hdr [B] {n_tracks, n_rows} — host memory mapped into the
 // device, written in place by k_track_obs like the result records.
 struct TrackObsArgs { svo_track_obs* rows; int* hdr; int max_rows; };
-// Motion priors (svo.h, svo_set_motion_prior): one sequence's row of a frame's priors — the homography T0 -> T1, its inverse, and
-// whether the sequence has one in this frame.  The frame's rows ([B], indexed by sequence) are a kernel argument of k_lk_chain_prior
-// alone, like MaskArgs: DevBuffers and every existing kernel's argument block stay as they are.
-struct PriorRow { float H[9], Hi[9]; int has, pad; };
+// Motion priors (svo.h, svo_set_motion_prior): PriorRow, one sequence's row of a frame's priors, lives in svo_prior.hpp beside the
+// arithmetic that fills it, where a host compiler can read it too.
+#include "svo_prior.hpp"
 // what Bucket::add_feature compares (feature_set.cpp:16-18); the division truncates toward zero, as C's does
 __device__ __forceinline__ int bucket_score(int age, int strength, int fast_thr) { return age + (strength - fast_thr) / 20; }
 // capacity 1: (score, first come, strength) as one key for a 64-bit atomicMax; order = the candidate's rank in the input list
@@ -259,6 +258,10 @@ void launch_detect_masked(const DevBuffers& d, const MaskArgs& m, int pass, int 
 // grid_n = max features that can enter LK; early_out: a feature stops at its first pass with status 0 (frame pipeline) or runs all four (member call)
 // prior: the frame's rows of motion priors (device, [B]) — k_lk_chain_prior then runs in k_lk_chain's place — or null
 bool launch_lk_chain(const DevBuffers& d, int grid_n, hipStream_t s, int early_out, const PriorRow* prior = nullptr);   // false: no kernel built for this (window, channels, summation mode) — nothing ran
+// SVO_PRIOR_LAST_ROTATION: k_prior_predict (svo_kernels_prior.hip) over the n sequences listed in act (mapped host memory; null:
+// sequences 0 .. n-1), first thing on the frame's stream.  rows / host_rows: the frame's device row and its row of the pinned ring;
+// uploaded: explicit priors were copied into `rows` in front of it
+void launch_prior_predict(const DevBuffers& d, const int* act, int n, bool uploaded, PriorRow* rows, PriorRow* host_rows, hipStream_t s);
 void launch_compact(const DevBuffers& d, hipStream_t s);
 void launch_triangulate(const DevBuffers& d, hipStream_t s);
 void launch_pnp(const DevBuffers& d, hipStream_t s, bool first_chunk_solved = false);   // expects the subsets drawn (launch_triangulate / k_compact do it)

@@ -108,7 +108,13 @@ def prior_setup(kind):
     return setup
 
 
-POSES, PL = [], None                                  # the pool's camera poses per frame and the left projection matrix (main fills them)
+def prior_auto(vo, c):
+    """the leg without a host prior: every frame predicts one on the device from each sequence's last pose (SVO_PRIOR_LAST_ROTATION) —
+    read against `rotation`, the ground truth, as its ceiling and `off` as its floor"""
+    vo.set_motion_prior_mode("last_rotation")
+
+
+POSES, PL = [], None                                 # the pool's camera poses per frame and the left projection matrix (main fills them)
 
 # legs: name -> (frame format, setup), the baseline first.  evidence: (name, f(vo, leg, frame_bytes) read after every recorded
 # collect and summed over the round, whether the sum is divided by the round's frame pairs)
@@ -129,7 +135,9 @@ FEATURES = dict(
                 legs=dict(off=("rendered", nothing), on=("rendered", lambda vo, c: vo.set_track_output(2048)))),
     prior=dict(stage="lk", evidence=("prior_frames", lambda vo, leg, nbytes: int(bool(vo.last_frame_path() & 2048)), False),   # SVO_PATH_MOTION_PRIOR
                stats=("n_after_circular", "lk_newton_steps"),
-               legs=dict(off=("rendered", nothing), identity=("rendered", prior_setup("identity")), rotation=("rendered", prior_setup("rotation")))),
+               legs=dict(off=("rendered", nothing), identity=("rendered", prior_setup("identity")), rotation=("rendered", prior_setup("rotation")),
+                         auto=("rendered", prior_auto)),
+               on_request=("auto",)),                 # run when --legs names it: the default set stays off, identity, rotation
 )
 
 
@@ -143,7 +151,7 @@ def main():
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--pool", type=int, default=16)
     ap.add_argument("--frames", type=int, default=10)
-    ap.add_argument("--legs", default=None, help="comma-separated, default: every leg of the feature")
+    ap.add_argument("--legs", default=None, help="comma-separated, default: every leg of the feature but those it runs on request (prior: auto)")
     ap.add_argument("--repeat", type=int, default=3, help="rounds of the legs, alternating them in every round")
     ap.add_argument("--package", default=None, help="directory holding the stereo_visual_odometry_amd package to import (default: this checkout)")
     ap.add_argument("--yaw-amp", type=float, default=None, help="yaw_amp_deg of the rendered scenes (default: the bench's); the per-frame yaw step is at most yaw_amp * 2 pi / 16")
@@ -159,7 +167,7 @@ def main():
         raise SystemExit("feature_bench.py needs a GPU")
     feature = FEATURES[args.feature]
     base = next(iter(feature["legs"]))
-    legs = args.legs.split(",") if args.legs else list(feature["legs"])
+    legs = args.legs.split(",") if args.legs else [k for k in feature["legs"] if k not in feature.get("on_request", ())]
     unknown = [k for k in legs if k not in feature["legs"]]
     if unknown:
         raise SystemExit("%s has no leg %s (it has %s)" % (args.feature, ",".join(unknown), ",".join(feature["legs"])))

@@ -30,7 +30,8 @@
 // triangulated from the previous frame's pair, in the previous frame's left camera frame.
 // `--prior file.csv` gives frame i the motion prior of line i (svo.h, svo_set_motion_prior): nine numbers, the row-major homography
 // that maps pixels of frame i - 1 to predicted pixels of frame i; an empty line (and every line past the file's end, and line 0)
-// means no prior for that frame.  Needs --gray 1 or 2.
+// means no prior for that frame.  Needs --gray 1 or 2.  `--prior auto` asks for no file: every frame predicts its prior on the device
+// from the rotation of the frame before (svo_set_motion_prior_mode, SVO_PRIOR_LAST_ROTATION) — the prior of a rig without a gyro.
 #include <zlib.h>
 #include <cmath>
 #include <cstdio>
@@ -172,7 +173,7 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv] [--prior file.csv]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv] [--prior file.csv | auto]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
     std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path, tracks_out, prior_path;
@@ -222,7 +223,8 @@ int main(int argc, char** argv) {
         if (!mask.ok()) { std::fprintf(stderr, "cannot read mask %s\n", mask_path.c_str()); return 2; }
     }
     std::vector<std::vector<float>> priors;                           // [frame] 9 numbers, or empty
-    if (!prior_path.empty()) {
+    const bool prior_auto = prior_path == "auto";
+    if (!prior_path.empty() && !prior_auto) {
         std::ifstream pf(prior_path);
         if (!pf) { std::fprintf(stderr, "cannot read %s\n", prior_path.c_str()); return 2; }
         for (std::string line; std::getline(pf, line);) {
@@ -257,6 +259,7 @@ int main(int argc, char** argv) {
         if (gray_gpu) vo.set_input_encoding("bgr8");
         if (cov.is_open()) vo.set_pose_covariance(SVO_COV_RESIDUAL);
         if (clahe) vo.set_clahe(clahe_clip, clahe_tx, clahe_ty);
+        if (prior_auto) vo.set_motion_prior_mode(SVO_PRIOR_LAST_ROTATION);
         if (tracks.is_open()) vo.set_track_output((cfg.buckets_along_height - cfg.bucket_start_row) * cfg.buckets_along_width);   // the grid's capacity: every row
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
