@@ -421,6 +421,54 @@ int svo_get_last_track_obs(svo_context* ctx, int seq, int cap, svo_track_obs* ro
  * SVO_ERR_STATE with the output off. */
 int svo_get_feature_ids(svo_context* ctx, int seq, int cap, int64_t* ids);
 
+/* ---- Binary descriptors for the observation rows ------------------------------------------------------------------------------
+ * What a landmark back end needs to recognise a place again (loop closure, relocalisation, map merging): an appearance descriptor
+ * per landmark.  Off by default; off, a context launches exactly what it launched before.  On, every frame writes one 32-byte
+ * descriptor per observation row into a second pinned ring: row i describes l1 of observation row i on that frame's LEFT image as
+ * ingest left it (after format conversion, CLAHE and rectification: level 0 of the frame's pyramid).  Compare with the Hamming
+ * distance.
+ *
+ * The descriptor is a steered BRIEF-256 in ORB's construction (intensity-centroid orientation, a rotated test pattern, comparisons
+ * of smoothed pixels) with every step defined on integers: the rules below ARE the contract, and the kernel agrees with them in
+ * every bit.  Parity with OpenCV's cv::ORB is UNPINNED and NOT CLAIMED: OpenCV was not available where this was written, and its
+ * learned pattern table is not ours — a descriptor from here does not match one from cv::ORB, nor a vocabulary trained on them.
+ *
+ *  Centre.   cx = clamp((int)(x + 0.5f), 0, W - 1), cy likewise with H: the rounding of a detection mask's look-up (truncation
+ *            toward zero, then the clamp).
+ *  Patch.    P(dx, dy), dx, dy in [-15, 15] = the grey byte of the image at (cx + dx, cy + dy); a coordinate outside the image is
+ *            reflected (REFLECT_101: -i for i < 0, 2 n - 2 - i for i >= n).  W, H >= 16 is required, so one reflection suffices.
+ *  Orientation.  m10 = sum dx P, m01 = sum dy P over the disc dx^2 + dy^2 <= 240 (749 pixels): exact integers, |m| < 2^21.
+ *            bin = the SMALLEST k in 0 .. 29 that maximises m10 C[k] + m01 S[k] (int64), with C = round(2^14 cos(12 k deg)),
+ *            S = round(2^14 sin(12 k deg)) as literals:
+ *              C[0..14] = 16384 16026 14968 13255 10963 8192 5063 1713 -1713 -5063 -8192 -10963 -13255 -14968 -16026, C[k+15] = -C[k]
+ *              S[0..14] = 0 3406 6664 9630 12176 14189 15582 16294 16294 15582 14189 12176 9630 6664 3406,           S[k+15] = -S[k]
+ *            The first maximum wins: m10 = 0, m01 > 0 ties bins 7 and 8 and gives 7; m10 = 0, m01 < 0 gives 22; a flat patch gives 0.
+ *  Smoothing.  B(u, v) = sum of P over the 5 x 5 box centred at (u, v), |u|, |v| <= 13: an integer in 0 .. 6375.
+ *  Pattern.  256 tests (ax, ay, bx, by), int8, ax^2 + ay^2 <= 169, bx^2 + by^2 <= 169, a != b: the library's own table
+ *            (svo_descriptor_pattern), Gaussian point pairs with sigma = 31 / 5 written by tools/make_brief_pattern.py.
+ *  Rotation of a point (px, py) by the bin:  rx = (px C[bin] - py S[bin] + 8192) >> 14,  ry = (px S[bin] + py C[bin] + 8192) >> 14
+ *            (arithmetic shift).  For every integer point of norm <= 13 and every bin |rx|, |ry| <= 13: every box lies in the patch.
+ *  Bits.     bit i = B(rot a_i) < B(rot b_i); bit i is bit i % 8 (LSB first) of byte i / 8.  A row is SVO_DESC_BYTES = 32 bytes.
+ *
+ * The bin is a 12-degree quantisation of the patch's intensity-centroid direction: it makes the descriptor follow in-plane rotation
+ * in steps, it is not a scale or viewpoint normalisation, and two views whose direction falls on either side of a bin boundary
+ * differ by one bin's rotation of the pattern. */
+#define SVO_DESC_BYTES 32
+#define SVO_PATH_DESCRIPTORS 8192 /* svo_get_last_frame_path: the frame wrote descriptor rows (k_track_desc); also set by svo_describe_points */
+/* on != 0: frames submitted from now on write descriptor rows; the pinned ring [8][n_seq][max_rows][32] bytes (max_rows: the track
+ * output's) is allocated at first use, re-allocated when svo_set_track_output changes max_rows, freed with the context.  A setup
+ * action: SVO_ERR_STATE with frames in flight, or with the track output off — a descriptor row describes an observation row, and
+ * svo_set_track_output(ctx, 0, ...) switches the descriptors off too.  SVO_ERR_ARG: a channels = 3 context, an image smaller than
+ * 16 in either dimension.  While on, svo_get_last_frame_path reports SVO_PATH_DESCRIPTORS. */
+int svo_set_descriptor_output(svo_context* ctx, int on);
+/* The descriptor rows of sequence seq in the last COLLECTED frame, from host memory: no device access, no synchronisation.  desc:
+ * cap rows of 32 bytes.  Returns the rows written = what svo_get_last_track_obs returns for that frame and cap; *n_tracks (may be
+ * NULL) = the frame's full track count.  SVO_ERR_STATE if that frame was issued with descriptors off or none was collected yet. */
+int svo_get_last_track_descriptors(svo_context* ctx, int seq, int cap, uint8_t* desc, int* n_tracks);
+/* The library's tables: pattern[4 i .. 4 i + 3] = (ax, ay, bx, by) of test i; cs[0..29] = C, cs[30..59] = S.  Either may be NULL
+ * (both NULL: SVO_ERR_ARG).  Needs no device. */
+int svo_descriptor_pattern(int8_t pattern[1024], int32_t cs[60]);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the
@@ -717,6 +765,11 @@ int svo_convert_gray(int device, int format, const uint8_t* src, int w, int h, i
  * packed.  SVO_ERR_ARG as svo_set_clahe's. */
 int svo_clahe(int device, int format, const uint8_t* src, int w, int h, int stride,
               double clip_limit, int tiles_x, int tiles_y, uint8_t* out);
+
+/* The descriptor section's stage alone, on the frame pipeline's device function: the descriptors (n rows of 32 bytes) and, when bins
+ * is not NULL, the orientation bins of n points xy (x, y pairs) of the w x h grey image img, rows `stride` bytes apart.  n = 0 is
+ * legal.  SVO_ERR_ARG: w or h < 16, stride < w, a non-finite coordinate.  Not cv::ORB's output (see the section above). */
+int svo_describe_points(int device, const uint8_t* img, int w, int h, int stride, int n, const float* xy, uint8_t* desc, int* bins);
 
 /* replaces: getInverseTransform(rotation, translation)  (vo.h:469-470, vo.cpp:246-258): [R t; 0 1]^-1, 4x4 row-major.
  * Runs the device function the frame pipeline ends with (one tiny launch). */

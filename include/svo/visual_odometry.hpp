@@ -213,6 +213,7 @@ class VisualOdometry {                                               // include/
             if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
             if (clahe_on_) svo_throw(svo_set_clahe(ctx_, 1, clahe_clip_, clahe_tx_, clahe_ty_));
             if (track_rows_ > 0) svo_throw(svo_set_track_output(ctx_, 1, track_rows_));
+            if (track_rows_ > 0 && desc_on_) svo_throw(svo_set_descriptor_output(ctx_, 1));
             if (prior_mode_ != SVO_PRIOR_EXPLICIT) svo_throw(svo_set_motion_prior_mode(ctx_, prior_mode_));
             if (!mask_.empty()) {
                 if ((int)mask_.size() != width_ * height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
@@ -376,7 +377,7 @@ class VisualOdometry {                                               // include/
         track_rows_ = max_rows;
     }
     void clear_track_output() {
-        track_rows_ = 0;
+        track_rows_ = 0; desc_on_ = false;                            // the descriptors ride on the track output
         if (ctx_) svo_throw(svo_set_track_output(ctx_, 0, 0));
     }
     // The rows of the last stereo_callback, the first min(tracks, max_rows) in svo_get_last_tracks' order; host memory only.
@@ -387,6 +388,27 @@ class VisualOdometry {                                               // include/
         svo_throw(svo_get_last_track_obs(ctx_, 0, 0, nullptr, &n_tracks));
         std::vector<svo_track_obs> rows((size_t)(n_tracks > 0 ? n_tracks : 0));
         const int n = svo_get_last_track_obs(ctx_, 0, (int)rows.size(), rows.data(), nullptr);
+        svo_throw(n);
+        rows.resize((size_t)n);
+        return rows;
+    }
+
+    // A 32-byte binary descriptor beside every observation row (svo_set_descriptor_output; svo.h defines it: a steered BRIEF-256 of
+    // the library's own, not cv::ORB's): needs set_track_output first, goes off with it.  Before the first frame the setting is kept
+    // and applied, behind the track output, when the context is created.
+    void set_descriptor_output(bool on) {
+        if (ctx_) svo_throw(svo_set_descriptor_output(ctx_, on ? 1 : 0));
+        else if (on && track_rows_ < 1) throw std::runtime_error("set_descriptor_output: the track output is off (set_track_output first)");
+        desc_on_ = on;
+    }
+    // The descriptors of the last stereo_callback: 32 bytes per row, row i describes last_track_observations()[i]; host memory only.
+    // Throws when that frame ran with descriptors off.
+    std::vector<std::array<uint8_t, SVO_DESC_BYTES>> last_track_descriptors() const {
+        if (!ctx_) throw std::runtime_error("last_track_descriptors: no frame yet (call stereo_callback first)");
+        int n_tracks = 0;
+        svo_throw(svo_get_last_track_descriptors(ctx_, 0, 0, nullptr, &n_tracks));
+        std::vector<std::array<uint8_t, SVO_DESC_BYTES>> rows((size_t)(n_tracks > 0 ? n_tracks : 0));
+        const int n = svo_get_last_track_descriptors(ctx_, 0, (int)rows.size(), rows.empty() ? nullptr : rows[0].data(), nullptr);
         svo_throw(n);
         rows.resize((size_t)n);
         return rows;
@@ -456,6 +478,7 @@ class VisualOdometry {                                               // include/
     int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
     std::vector<uint8_t> mask_;                                       // set_detection_mask before the first frame: installed at creation
     int track_rows_ = 0;                                              // set_track_output (likewise); 0: off
+    bool desc_on_ = false;                                            // set_descriptor_output (likewise, behind the track output)
     int prior_mode_ = SVO_PRIOR_EXPLICIT;                             // set_motion_prior_mode (likewise)
     bool clahe_on_ = false; double clahe_clip_ = 2.0; int clahe_tx_ = 8, clahe_ty_ = 8;   // set_clahe (applied once the context exists)
 };

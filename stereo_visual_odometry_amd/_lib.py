@@ -105,6 +105,17 @@ if hasattr(lib, "svo_set_track_output"):
     lib.svo_get_last_track_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     lib.svo_get_feature_ids.restype = C.c_int
     lib.svo_get_feature_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+# binary descriptors (svo.h, "Binary descriptors"): rows of DESC_BYTES bytes beside the observation rows
+PATH_DESCRIPTORS = 8192
+DESC_BYTES = 32
+lib.svo_set_descriptor_output.restype = C.c_int
+lib.svo_set_descriptor_output.argtypes = [C.c_void_p, C.c_int]
+lib.svo_get_last_track_descriptors.restype = C.c_int
+lib.svo_get_last_track_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+lib.svo_describe_points.restype = C.c_int
+lib.svo_describe_points.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_descriptor_pattern.restype = C.c_int
+lib.svo_descriptor_pattern.argtypes = [C.c_void_p, C.c_void_p]
 # motion priors (svo.h): H / Hi are 9 float32 each (n_seq x 9 in the batch setter), has n_seq bytes; R is 9 float64
 PATH_MOTION_PRIOR = 2048
 lib.svo_set_motion_prior.restype = C.c_int
@@ -210,6 +221,7 @@ EXPORTS = [
     "svo_set_motion_prior", "svo_set_motion_priors", "svo_get_motion_prior", "svo_motion_prior_from_rotation",
     "svo_lk_track_guess", "svo_circular_match_prior",
     "svo_set_motion_prior_mode", "svo_get_motion_prior_mode", "svo_get_last_motion_prior",
+    "svo_set_descriptor_output", "svo_get_last_track_descriptors", "svo_describe_points", "svo_descriptor_pattern",
 ]
 
 

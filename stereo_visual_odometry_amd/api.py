@@ -335,6 +335,30 @@ def clahe(image, fmt="mono8", clip_limit=2.0, tiles=(8, 8), device=0):
     return out
 
 
+def describe_points(image, xy, device=0):
+    """The steered BRIEF-256 descriptors of the points xy ((n, 2) float32: x, y) of a grey image on the GPU (svo_describe_points):
+    the descriptor output of the frame pipeline alone, on its device function.  image: (h, w) uint8, h, w >= 16, rows may be
+    strided -> (desc (n, 32) uint8, bins (n,) int32).  Not cv::ORB's descriptors (svo.h, "Binary descriptors")."""
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("uint8 (h, w) image expected")
+    if img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img)
+    p = _pts(xy)
+    n = len(p)
+    desc, bins = np.zeros((n, _lib.DESC_BYTES), np.uint8), np.zeros(n, np.int32)
+    check(lib.svo_describe_points(device, C.c_void_p(img.ctypes.data), img.shape[1], img.shape[0], img.strides[0], n, ptr(p), ptr(desc), ptr(bins)))
+    return desc, bins
+
+
+def descriptor_pattern():
+    """The descriptor's tables (svo_descriptor_pattern; no device needed) -> (pattern (256, 4) int8: ax, ay, bx, by per test,
+    C (30,) int32, S (30,) int32)."""
+    pat, cs = np.zeros((256, 4), np.int8), np.zeros(60, np.int32)
+    check(lib.svo_descriptor_pattern(ptr(pat), ptr(cs)))
+    return pat, cs[:30].copy(), cs[30:].copy()
+
+
 # ---------------------------------------------------------------------------- FeatureSet / Bucket
 class FeatureSet:
     """vo.h:132-188 — parallel arrays points / ages / strengths."""
@@ -520,6 +544,22 @@ class BatchVisualOdometry:
         n = check(lib.svo_get_last_track_obs(self._h, seq, len(rows), ptr(rows), None))
         rows = rows[:n].copy()
         return (rows, n_tracks.value) if with_count else rows
+
+    def set_descriptor_output(self, on=True):
+        """A 32-byte steered BRIEF descriptor beside every observation row, from the next frame submitted on
+        (svo_set_descriptor_output); needs the track output, and goes off with it.  SvoError with frames in flight, with the track
+        output off, or on a channels = 3 context."""
+        check(lib.svo_set_descriptor_output(self._h, 1 if on else 0))
+
+    def last_track_descriptors(self, seq=0):
+        """The descriptor rows of sequence seq in the last collected frame -> (n, 32) uint8: row i describes row i of
+        last_track_obs(seq).  Host memory only, no synchronisation (svo_get_last_track_descriptors).  SvoError when that frame was
+        issued with descriptors off."""
+        n_tracks = C.c_int(0)
+        check(lib.svo_get_last_track_descriptors(self._h, seq, 0, None, C.byref(n_tracks)))
+        desc = np.zeros((max(n_tracks.value, 1), _lib.DESC_BYTES), np.uint8)
+        n = check(lib.svo_get_last_track_descriptors(self._h, seq, len(desc), ptr(desc), None))
+        return desc[:n].copy()
 
     def feature_ids(self, seq=0):
         """The ids of features(seq)'s entries, in its order (svo_get_feature_ids; synchronises).  SvoError with the output off."""
@@ -892,6 +932,7 @@ class VisualOdometry(BatchVisualOdometry):
 
     def clear_track_output(self):
         self._track_rows = None
+        self._desc = False                                            # the descriptors ride on the track output
         if self._created:
             super().clear_track_output()
 
@@ -899,6 +940,18 @@ class VisualOdometry(BatchVisualOdometry):
         if not self._created:
             raise _lib.SvoError("last_track_obs: no frame yet (call stereo_callback first)")
         return super().last_track_obs(seq, with_count)
+
+    def set_descriptor_output(self, on=True):
+        if self._created:
+            return super().set_descriptor_output(on)
+        if on and self._track_rows is None:
+            raise _lib.SvoError("set_descriptor_output: the track output is off (set_track_output first)")
+        self._desc = bool(on)                                         # applied, behind the track output, when the first frame creates the context
+
+    def last_track_descriptors(self, seq=0):
+        if not self._created:
+            raise _lib.SvoError("last_track_descriptors: no frame yet (call stereo_callback first)")
+        return super().last_track_descriptors(seq)
 
     def feature_ids(self, seq=0):
         if not self._created:
@@ -996,6 +1049,8 @@ class VisualOdometry(BatchVisualOdometry):
                 super().set_clahe(self._clahe[0], self._clahe[1:])
             if self._track_rows is not None:
                 super().set_track_output(self._track_rows)
+                if getattr(self, "_desc", False):
+                    super().set_descriptor_output(True)
             if getattr(self, "_prior", None) is not None:
                 super().set_motion_prior(self._prior[0], self._prior[1])
                 self._prior = None

@@ -101,6 +101,7 @@ struct RingSlot {
     bool masked = false;                         // ... and whether it came with a mask (h_act's row then holds its flags)
     bool tracks = false;                         // ... and whether it carried track ids and wrote its observation rows
     bool priors = false;                         // ... and whether it had motion-prior rows (h_prior's row then holds them)
+    bool desc = false;                           // ... and whether it wrote descriptor rows beside its observation rows
 };
 // Detection masks (svo_set_detection_mask): the two slots of one scope (a sequence, or the shared pair).  cur: the slot in force for
 // the frames submitted from now on (-1: none); last: the slot the most recent frame of this scope recorded for its left image — that
@@ -207,6 +208,15 @@ struct svo_context {
     int last_obs_rows = 0;                       // the row pitch of whichever holds it
     std::vector<svo_track_obs> kept_obs;
     std::vector<int> kept_hdr;
+    // binary descriptors (svo_set_descriptor_output): a row of 32 bytes beside every observation row, in a pinned mapped ring of the
+    // same shape ([SVO_RING][B][track_rows][32]) that k_track_desc writes in place.  It rides on the track output: the same max_rows,
+    // the same headers, the same slot, the same moment for the host copy (keep_last_obs).  Empty until first switched on.
+    bool desc_on = false;
+    int desc_rows = 0;                           // the max_rows the ring was allocated for (0: no ring)
+    uint8_t* h_desc = nullptr;
+    uint8_t* d_desc = nullptr;
+    bool last_desc_on = false;                   // the last collected frame was issued with descriptors on
+    std::vector<uint8_t> kept_desc;              // [B][last_obs_rows][32] beside kept_obs
     // motion priors (svo_set_motion_prior).  Everything below is empty until the first setter.  prior_next[seq] is the prior the
     // sequence's next frame will use (has = 1) — host state, consumed when that frame is enqueued (take_priors): the frame's rows go
     // into its slot's row of the pinned ring and from there, with one copy on the frame's stream, into the slot's device row that
@@ -395,7 +405,7 @@ extern "C" void svo_destroy(svo_context* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
-    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps, (void*)c->h_cov, (void*)c->h_obs, (void*)c->h_obs_hdr}) if (p) (void)hipHostFree(p);
+    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps, (void*)c->h_cov, (void*)c->h_obs, (void*)c->h_obs_hdr, (void*)c->h_desc}) if (p) (void)hipHostFree(p);
     for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
     for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
     for (const auto& r : c->retired) (void)hipFree(r.p);
@@ -600,7 +610,7 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     HIPCHK(choose_pnp_build(c->d, share.lean));
     DevBuffers f = frame_view(c, slot, n_act);                         // after the build choice: co_resident travels in the view
     int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0) |
-               (c->clahe_on ? SVO_PATH_CLAHE : 0) | (c->track_on ? SVO_PATH_TRACK_IDS : 0);
+               (c->clahe_on ? SVO_PATH_CLAHE : 0) | (c->track_on ? SVO_PATH_TRACK_IDS : 0) | (c->track_on && c->desc_on ? SVO_PATH_DESCRIPTORS : 0);
     const bool ids = c->track_on;
     const uint8_t* const* dp = ring_row(c, f.img_ptrs, slot);          // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(f);
@@ -652,6 +662,8 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     launch_pnp(f, s, tri_epnp);
     if (c->cov_mode) launch_pose_cov(f, CovArgs{c->d_cov + (size_t)slot * c->d.B, c->cov_mode, c->cov_sigma2}, s);   // into the pinned ring, like the record below
     if (ids) launch_track_obs(f, c->ids, TrackObsArgs{c->d_obs + (size_t)slot * c->d.B * c->track_rows, c->d_obs_hdr + (size_t)slot * 2 * c->d.B, c->track_rows}, s);
+    if (ids && c->desc_on)             // every observation row's descriptor, on the T1 pyramid k_frame_end is about to rename
+        launch_track_desc(f, DescArgs{c->d_desc + (size_t)slot * c->d.B * c->track_rows * SVO_DESC_BYTES, c->track_rows}, s);
     launch_frame_end(f, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
     c->last_path = path;
     return SVO_OK;
@@ -807,6 +819,11 @@ static void keep_last_obs(svo_context* c) {
     c->kept_hdr.assign(hdr, hdr + 2 * B);
     c->kept_obs.resize(B * R);
     for (size_t i = 0; i < B; i++) memcpy(c->kept_obs.data() + i * R, rows + i * R, sizeof(svo_track_obs) * (size_t)hdr[2 * i + 1]);
+    if (c->last_desc_on) {                                           // that frame's descriptor rows lie in the same slot of their ring
+        const uint8_t* desc = c->h_desc + (size_t)c->last_obs_slot * B * R * SVO_DESC_BYTES;
+        c->kept_desc.resize(B * R * SVO_DESC_BYTES);
+        for (size_t i = 0; i < B; i++) memcpy(c->kept_desc.data() + i * R * SVO_DESC_BYTES, desc + i * R * SVO_DESC_BYTES, (size_t)SVO_DESC_BYTES * (size_t)hdr[2 * i + 1]);
+    }
     c->last_obs_slot = -1;
 }
 
@@ -839,7 +856,7 @@ static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const u
         if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
     if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows, pri)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
-    r.cov_mode = c->cov_mode; r.masked = active != nullptr; r.tracks = c->track_on;
+    r.cov_mode = c->cov_mode; r.masked = active != nullptr; r.tracks = c->track_on; r.desc = c->track_on && c->desc_on;
     c->staged_inputs = false;
     HIPCHK(hipEventRecord(r.ev[EV_DONE], c->stream));
     HIPCHK(hipGetLastError());
@@ -868,7 +885,7 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
         const int* flags = ring_row(c, c->h_act, slot) + B;
         for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) memset(&c->last_cov[i], 0, sizeof(PoseCovRow));
     }
-    c->last_tracks_on = c->ring[slot].tracks;
+    c->last_tracks_on = c->ring[slot].tracks; c->last_desc_on = c->ring[slot].desc;
     c->last_obs_slot = -1;
     if (c->last_tracks_on) {                                         // read in place; idle sequences took no launch: zero headers
         int* hdr = c->h_obs_hdr + (size_t)slot * 2 * B;
@@ -1273,11 +1290,29 @@ extern "C" int svo_get_last_tracks(svo_context* c, int seq, int cap, float* pl0,
     return hs.n_tracks;
 }
 
+// the descriptor ring at the track output's max_rows: allocated at first use, re-allocated when max_rows has changed.  The caller
+// has kept the last collected frame's rows (keep_last_obs) if the old ring still held them, and no frame is in flight.
+static int desc_ring(svo_context* c) {
+    if (c->h_desc && c->desc_rows == c->track_rows) return SVO_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->h_desc) (void)hipHostFree(c->h_desc);
+    c->h_desc = nullptr; c->d_desc = nullptr; c->desc_rows = 0;
+    const size_t bytes = (size_t)SVO_RING * c->d.B * (size_t)c->track_rows * SVO_DESC_BYTES;
+    uint8_t* h = nullptr; void* dv = nullptr;
+    HIPCHK(hipHostMalloc((void**)&h, bytes, hipHostMallocMapped));
+    memset(h, 0, bytes);
+    const hipError_t e = hipHostGetDevicePointer(&dv, (void*)h, 0);
+    if (e != hipSuccess || !dv) { (void)hipHostFree(h); HIPCHK(e != hipSuccess ? e : hipErrorInvalidDevicePointer); }   // both addresses or no ring
+    c->h_desc = h; c->d_desc = (uint8_t*)dv; c->desc_rows = c->track_rows;
+    return SVO_OK;
+}
+
 // ---- track ids and observation rows (svo.h) ----
 extern "C" int svo_set_track_output(svo_context* c, int on, int max_rows) {
     if (!c) return fail_arg("null context");
     if (c->inflight != 0) { g_err = "svo_set_track_output with frames in flight: switching is a setup action (collect first)"; return SVO_ERR_STATE; }
-    if (!on) { c->track_on = false; return SVO_OK; }
+    if (!on) { c->track_on = false; c->desc_on = false; return SVO_OK; }   // the descriptors ride on the track output
     if (c->d.cfg.features_per_bucket > 1) return fail_arg("track ids need features_per_bucket == 1 (the general bucket walk carries no ids)");
     if (max_rows < 1 || max_rows > c->d.CAP) return fail_arg("max_rows must be 1 .. the context's feature capacity");
     HIPCHK(hipSetDevice(c->device));
@@ -1300,6 +1335,7 @@ extern "C" int svo_set_track_output(svo_context* c, int on, int max_rows) {
         HIPCHK(hipHostGetDevicePointer((void**)&c->d_obs, c->h_obs, 0));
         HIPCHK(hipHostGetDevicePointer((void**)&c->d_obs_hdr, c->h_obs_hdr, 0));
         c->track_rows = max_rows;
+        if (c->desc_on) if (const int rc = desc_ring(c)) { c->desc_on = false; return rc; }   // the descriptor ring follows max_rows
     }
     if (!c->track_on) launch_ids_assign(c->d, c->ids, c->stream);     // the features held now: next_id + index
     HIPCHK(hipGetLastError());
@@ -1317,6 +1353,32 @@ extern "C" int svo_get_last_track_obs(svo_context* c, int seq, int cap, svo_trac
     if (n_tracks) *n_tracks = hdr[2 * seq];
     const int n = hdr[2 * seq + 1] < cap ? hdr[2 * seq + 1] : cap;
     if (n > 0) memcpy(rows, src + (size_t)seq * R, sizeof(svo_track_obs) * (size_t)n);
+    return n;
+}
+
+// ---- binary descriptors (svo.h) ----
+extern "C" int svo_set_descriptor_output(svo_context* c, int on) {
+    if (!c) return fail_arg("null context");
+    if (c->inflight != 0) { g_err = "svo_set_descriptor_output with frames in flight: switching is a setup action (collect first)"; return SVO_ERR_STATE; }
+    if (!on) { c->desc_on = false; return SVO_OK; }
+    if (c->d.CN != 1) return fail_arg("svo_set_descriptor_output: descriptors are defined on a grey image (channels = 1 contexts only)");
+    if (c->d.geom.W < 16 || c->d.geom.H < 16) return fail_arg("svo_set_descriptor_output: the image must be at least 16 x 16");
+    if (!c->track_on) { g_err = "svo_set_descriptor_output with the track output off: a descriptor row describes an observation row (svo_set_track_output first)"; return SVO_ERR_STATE; }
+    if (const int rc = desc_ring(c)) return rc;
+    c->desc_on = true;                                               // host state: the next frame issued carries it
+    return SVO_OK;
+}
+
+extern "C" int svo_get_last_track_descriptors(svo_context* c, int seq, int cap, uint8_t* desc, int* n_tracks) {
+    if (!c || seq < 0 || seq >= c->d.B || cap < 0 || (cap > 0 && !desc)) return fail_arg("bad context / seq / cap / desc");
+    if (c->last_slot < 0 || !c->last_tracks_on || !c->last_desc_on) { g_err = "the last collected frame was issued with the descriptor output off (or none was collected yet)"; return SVO_ERR_STATE; }
+    const size_t B = c->d.B, R = c->last_obs_rows;
+    const bool ring = c->last_obs_slot >= 0;
+    const int* hdr = ring ? c->h_obs_hdr + (size_t)c->last_obs_slot * 2 * B : c->kept_hdr.data();
+    const uint8_t* src = ring ? c->h_desc + (size_t)c->last_obs_slot * B * R * SVO_DESC_BYTES : c->kept_desc.data();
+    if (n_tracks) *n_tracks = hdr[2 * seq];
+    const int n = hdr[2 * seq + 1] < cap ? hdr[2 * seq + 1] : cap;
+    if (n > 0) memcpy(desc, src + (size_t)seq * R * SVO_DESC_BYTES, (size_t)SVO_DESC_BYTES * (size_t)n);
     return n;
 }
 
@@ -2114,6 +2176,31 @@ extern "C" int svo_pose_covariance(int device, const float K[9], int n, const fl
     if (cov_p) memcpy(cov_p, h.cov_p, sizeof(h.cov_p));
     if (cov_T) memcpy(cov_T, h.cov_T, sizeof(h.cov_T));
     if (valid) *valid = h.valid;
+    return SVO_OK;
+}
+
+// ---- binary descriptors (svo.h): the stage alone, and the tables ----
+extern "C" int svo_describe_points(int device, const uint8_t* img, int w, int h, int stride, int n, const float* xy, uint8_t* desc, int* bins) {
+    if (!img || n < 0 || (n > 0 && (!xy || !desc))) return fail_arg("bad arguments");
+    if (w < 16 || h < 16) return fail_arg("svo_describe_points: the image must be at least 16 x 16");
+    if (stride < w) return fail_arg("stride < w");
+    for (int i = 0; i < 2 * n; i++) if (!isfinite(xy[i])) return fail_arg("svo_describe_points: a non-finite coordinate");
+    int rc = use_device(device); if (rc != SVO_OK) return rc;
+    g_stage_path = SVO_PATH_DESCRIPTORS;
+    if (n == 0) return SVO_OK;
+    DevTmp t; uint8_t *dimg, *ddesc; float2* dxy; int* dbins;
+    HIPCHK(t.put_rows(&dimg, img, (size_t)w, (size_t)h, (size_t)stride));
+    HIPCHK(t.put(&dxy, xy, (size_t)n)); HIPCHK(t.get(&ddesc, (size_t)n * SVO_DESC_BYTES)); HIPCHK(t.get(&dbins, (size_t)n));
+    launch_describe_points(dimg, w, h, w, dxy, n, ddesc, dbins, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(t.download(desc, ddesc, (size_t)n * SVO_DESC_BYTES));
+    if (bins) HIPCHK(t.download(bins, dbins, (size_t)n));
+    return SVO_OK;
+}
+
+extern "C" int svo_descriptor_pattern(int8_t pattern[1024], int32_t cs[60]) {
+    if (!pattern && !cs) return fail_arg("null argument");
+    desc_copy_tables(pattern, cs);                                   // svo_kernels_desc.hip: the tables live with the kernels
     return SVO_OK;
 }
 

@@ -198,6 +198,10 @@ struct IdArgs { long long* feat_id[2]; long long* track_id; long long* next_id; 
 // One frame's rows of the pinned observation ring: rows [B][max_rows], hdr [B] {n_tracks, n_rows} — host memory mapped into the
 // device, written in place by k_track_obs like the result records.
 struct TrackObsArgs { svo_track_obs* rows; int* hdr; int max_rows; };
+// One frame's rows of the pinned descriptor ring (svo.h, svo_set_descriptor_output): rows [B][max_rows][32] bytes, host memory mapped
+// into the device, written in place by k_track_desc.  Row i describes observation row i; the row count is k_track_obs's own
+// (min(n_tracks, max_rows) of an active sequence), taken from SeqState as that kernel takes it.  Arguments of their own, again.
+struct DescArgs { uint8_t* rows; int max_rows; };
 // Motion priors (svo.h, svo_set_motion_prior): PriorRow, one sequence's row of a frame's priors, lives in svo_prior.hpp beside the
 // arithmetic that fills it, where a host compiler can read it too.
 #include "svo_prior.hpp"
@@ -275,6 +279,12 @@ void launch_detect_ids(const DevBuffers& d, const IdArgs& ia, const MaskArgs* m,
 void launch_ids_compact(const DevBuffers& d, const IdArgs& ia, hipStream_t s);     // behind launch_compact: the ids through its stable ranks
 // behind launch_pnp, before launch_frame_end: the inlier compaction's id move, then the frame's header and rows into the pinned ring
 void launch_track_obs(const DevBuffers& d, const IdArgs& ia, const TrackObsArgs& oa, hipStream_t s);
+// ---- binary descriptors (svo_set_descriptor_output; svo_kernels_desc.hip) ----
+// behind launch_track_obs, before launch_frame_end: the descriptor of every observation row, into the frame's rows of the pinned ring
+void launch_track_desc(const DevBuffers& d, const DescArgs& a, hipStream_t s);
+// svo_describe_points: n points of a plain image (device pointers; bins may be null); n <= 0 launches nothing
+void launch_describe_points(const uint8_t* img, int w, int h, int stride, const float2* xy, int n, uint8_t* desc, int* bins, hipStream_t s);
+void desc_copy_tables(int8_t* pattern /* [1024] or null */, int32_t* cs /* [60]: cos, then sin; or null */);   // svo_descriptor_pattern; host only
 void launch_ids_assign(const DevBuffers& d, const IdArgs& ia, hipStream_t s);      // switching on: held features get next_id + index
 void launch_ids_reset(const IdArgs& ia, int seq0, int n, hipStream_t s);           // svo_reset_sequence: next_id = 0
 void launch_pnp_p3p(const DevBuffers& d, hipStream_t s);                // exactly four points: one P3P, no RANSAC (stage API only)

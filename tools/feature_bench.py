@@ -2,7 +2,7 @@
 """Cost of one optional feature at the bench shape (bench.py's workload: KITTI-00-shaped 1241x376, LK 21x21, maxLevel 3, two
 contexts x 256 sequences, frames resident in HBM, 4 frames in flight per context):
 
-    python tools/feature_bench.py FEATURE [options]        FEATURE: rectify | input_format | pose_cov | detect_mask | clahe | tracks | prior
+    python tools/feature_bench.py FEATURE [options]        FEATURE: rectify | input_format | pose_cov | detect_mask | clahe | tracks | prior | descriptors
 
 A feature is one entry of FEATURES: its legs (the baseline first: the library as it is without the feature's setter, nothing is
 called), per leg the frame format and a setup(vo, context_index), the svo_get_stage_timing stage it reports, and optionally a
@@ -87,6 +87,12 @@ def clahe_on(vo, c):
     vo.set_clahe(2.0, (8, 8))
 
 
+def descriptors_on(vo, c):
+    """the descriptor leg: the track output at the `tracks` feature's max_rows, and a 32-byte descriptor beside every row"""
+    vo.set_track_output(2048)
+    vo.set_descriptor_output(True)
+
+
 def prior_setup(kind):
     """the motion-prior legs: before every submit, every sequence with a previous frame gets a prior — the identity (the mechanism's
     cost: same tracks, one more copy, the prior kernel) or the rotation between the two frames it is about to track (what it buys)"""
@@ -133,6 +139,9 @@ FEATURES = dict(
     tracks=dict(stage="pnp",                          # the rows of sequence 0 only: reading all of them would be timed with the leg
                 evidence=("rows_of_sequence_0", lambda vo, leg, nbytes: len(vo.last_track_obs(0)) if leg != "off" else 0, False),
                 legs=dict(off=("rendered", nothing), on=("rendered", lambda vo, c: vo.set_track_output(2048)))),
+    descriptors=dict(stage="pnp",                     # k_track_desc runs behind the pose stage; the rows of sequence 0 only, as for tracks
+                     evidence=("descriptor_rows_of_sequence_0", lambda vo, leg, nbytes: len(vo.last_track_descriptors(0)) if leg == "descriptors" else 0, False),
+                     legs=dict(off=("rendered", nothing), tracks=("rendered", lambda vo, c: vo.set_track_output(2048)), descriptors=("rendered", descriptors_on))),
     prior=dict(stage="lk", evidence=("prior_frames", lambda vo, leg, nbytes: int(bool(vo.last_frame_path() & 2048)), False),   # SVO_PATH_MOTION_PRIOR
                stats=("n_after_circular", "lk_newton_steps"),
                legs=dict(off=("rendered", nothing), identity=("rendered", prior_setup("identity")), rotation=("rendered", prior_setup("rotation")),

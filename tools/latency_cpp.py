@@ -1,5 +1,5 @@
 """Single-stream latency without Python in the loop: renders the bench scene's frames, builds tools/svo_latency.cpp (plain g++
-against the C-ABI) and runs it.   python tools/latency_cpp.py [win] [calls] [--covariance | --mask | --clahe | --tracks | --prior | --prior-auto]   (MI355X box; the flag is svo_latency's)"""
+against the C-ABI) and runs it.   python tools/latency_cpp.py [win] [calls] [--covariance | --mask | --clahe | --tracks [--descriptors] | --prior | --prior-auto]   (MI355X box; the flag is svo_latency's)"""
 import os
 import subprocess
 import sys

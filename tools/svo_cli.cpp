@@ -28,6 +28,9 @@
 // `--tracks file.csv` switches the track output on (svo.h, svo_set_track_output) and writes one line per observation row,
 // `frame,id,ul,vl,ur,vr,x,y,z,age,inlier,has_xyz`: this frame's stereo observation (l1, r1) of landmark `id`, and the point
 // triangulated from the previous frame's pair, in the previous frame's left camera frame.
+// `--descriptors file.csv` switches the track output and the descriptor output on (svo.h, svo_set_descriptor_output) and writes one
+// line per observation row, `frame,id,descriptor`: the row's 32 descriptor bytes as 64 hex digits, byte 0 first.  The ids are
+// `--tracks`'s, and both files may be written in one run.
 // `--prior file.csv` gives frame i the motion prior of line i (svo.h, svo_set_motion_prior): nine numbers, the row-major homography
 // that maps pixels of frame i - 1 to predicted pixels of frame i; an empty line (and every line past the file's end, and line 0)
 // means no prior for that frame.  Needs --gray 1 or 2.  `--prior auto` asks for no file: every frame predicts its prior on the device
@@ -173,10 +176,10 @@ static void matmul4(const double* A, const double* B, double* C) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv] [--prior file.csv | auto]\n", argv[0]); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: %s <N_FRAMES> <folder> [--calib file.yaml] [--out result.csv] [--device d] [--gray 1] [--identity-start 1] [--float-sums 1] [--ref-format 1] [--rectify left.yaml right.yaml] [--covariance file.csv] [--mask file.pgm] [--clahe clip,tx,ty] [--tracks file.csv] [--descriptors file.csv] [--prior file.csv | auto]\n", argv[0]); return 2; }
     const int N_FRAMES = std::atoi(argv[1]);
     const std::string folder = argv[2];
-    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path, tracks_out, prior_path;
+    std::string calib, out = folder + "/result.csv", rect_l, rect_r, cov_out, mask_path, tracks_out, desc_out, prior_path;
     bool gray = false, gray_gpu = false, identity_start = false, float_sums = false, ref_format = false, clahe = false;
     double clahe_clip = 2.0; int clahe_tx = 8, clahe_ty = 8;
     for (int i = 3; i + 1 < argc; i += 2) {
@@ -191,6 +194,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--out")) out = argv[i + 1];
         else if (!strcmp(argv[i], "--covariance")) cov_out = argv[i + 1];   // one row per frame: valid, then the 21 upper-triangle entries of cov_T (svo.h), row by row
         else if (!strcmp(argv[i], "--tracks")) tracks_out = argv[i + 1];    // one line per observation row of every frame (svo.h, svo_track_obs)
+        else if (!strcmp(argv[i], "--descriptors")) desc_out = argv[i + 1]; // one line per observation row: frame, id, the 32 descriptor bytes in hex (svo.h)
         else if (!strcmp(argv[i], "--prior")) prior_path = argv[i + 1];     // one line of 9 numbers per frame (svo.h, motion prior); an empty line: no prior
         else if (!strcmp(argv[i], "--mask")) mask_path = argv[i + 1];       // a static detection mask (svo.h): PGM or PNG of the frame size, non-zero = features allowed; needs --gray 1 or 2
         else if (!strcmp(argv[i], "--clahe")) {                             // clip,tx,ty: CLAHE on the grey frames inside frame ingest (svo.h); needs --gray 1 or 2
@@ -250,6 +254,12 @@ int main(int argc, char** argv) {
         if (!tracks) { std::fprintf(stderr, "cannot write %s\n", tracks_out.c_str()); return 2; }
         tracks << "frame,id,ul,vl,ur,vr,x,y,z,age,inlier,has_xyz\n";
     }
+    std::ofstream descs;
+    if (!desc_out.empty()) {
+        descs.open(desc_out);
+        if (!descs) { std::fprintf(stderr, "cannot write %s\n", desc_out.c_str()); return 2; }
+        descs << "frame,id,descriptor\n";
+    }
     try {
         svo_config cfg; svo_config_default(&cfg);
         cfg.lk_float_sums = float_sums ? 1 : 0;
@@ -260,7 +270,8 @@ int main(int argc, char** argv) {
         if (cov.is_open()) vo.set_pose_covariance(SVO_COV_RESIDUAL);
         if (clahe) vo.set_clahe(clahe_clip, clahe_tx, clahe_ty);
         if (prior_auto) vo.set_motion_prior_mode(SVO_PRIOR_LAST_ROTATION);
-        if (tracks.is_open()) vo.set_track_output((cfg.buckets_along_height - cfg.bucket_start_row) * cfg.buckets_along_width);   // the grid's capacity: every row
+        if (tracks.is_open() || descs.is_open()) vo.set_track_output((cfg.buckets_along_height - cfg.bucket_start_row) * cfg.buckets_along_width);   // the grid's capacity: every row
+        if (descs.is_open()) vo.set_descriptor_output(true);
         const double theta = (26.0 / 360) * 2 * M_PI;                                                    // main.cpp:368-373
         double pose[16] = {1, 0, 0, 0, 0, cos(theta), sin(theta), 0, 0, -sin(theta), cos(theta), 0, 0, 0, 0, 1};
         if (identity_start) { const double I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; memcpy(pose, I, sizeof(I)); }
@@ -296,6 +307,15 @@ int main(int argc, char** argv) {
                     std::snprintf(row, sizeof(row), "%d,%lld,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%d,%d,%d\n", i, (long long)t.id, t.l1[0], t.l1[1], t.r1[0], t.r1[1],
                                   t.xyz[0], t.xyz[1], t.xyz[2], t.age, (t.flags & SVO_OBS_INLIER) ? 1 : 0, (t.flags & SVO_OBS_HAS_XYZ) ? 1 : 0);
                     tracks << row;
+                }
+            }
+            if (descs.is_open()) {
+                const auto obs = vo.last_track_observations();
+                const auto desc = vo.last_track_descriptors();
+                for (size_t r = 0; r < desc.size() && r < obs.size(); r++) {
+                    int at = std::snprintf(row, sizeof(row), "%d,%lld,", i, (long long)obs[r].id);
+                    for (int b = 0; b < SVO_DESC_BYTES; b++) at += std::snprintf(row + at, sizeof(row) - (size_t)at, "%02x", (unsigned)desc[r][(size_t)b]);
+                    descs << row << "\n";
                 }
             }
             std::printf("Frame %d: ok=%d tracks=%d inliers=%d\n", i, (int)o.first, vo.stats.n_after_bounds, vo.stats.n_inliers);

@@ -3,13 +3,15 @@
 // src/main.cpp:394).  Reads stereo pairs from a raw file (int32 n, h, w; then n x (left, right) gray images), plays them
 // ping-pong through svo_process and prints the mean / median / p95 wall time per call, with ordinary heap buffers and with
 // page-locked ones (svo_alloc_pinned).
-//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance | --mask | --clahe | --tracks | --prior | --prior-auto]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
+//   svo_latency frames.bin [win=21] [calls=200] [max_translation=2.0] [--covariance | --mask | --clahe | --tracks [--descriptors] | --prior | --prior-auto]   (KITTI-00 intrinsics: the file comes from tools/latency_cpp.py)
 // --covariance: every leg is run twice, without and with the pose covariance (svo_set_pose_covariance, SVO_COV_RESIDUAL).
 // --mask: every leg is run twice, without and with a static detection mask (svo_set_detection_mask: the lower quarter of the image
 // closed, a bonnet) — a masked lone-stream frame issues the unfused front, one launch more.
 // --clahe: every leg is run twice, without and with CLAHE (svo_set_clahe, clip 2.0, 8 x 8 tiles): two launches more per frame.
 // --tracks: every leg is run twice, without and with the track output (svo_set_track_output, max_rows 2048): the unfused front, the
 // ids builds of the emit, and two launches more per frame (k_ids_compact, k_track_obs).
+// --tracks --descriptors: a third run of every leg with the descriptor output on top of the track output (svo_set_descriptor_output):
+// one launch more per frame (k_track_desc) and 32 bytes more per row over PCIe.
 // --prior: every leg is run twice, without and with a motion prior before every call (svo_set_motion_prior): the identity homography —
 // the frame file holds no poses — so the tracks are the same and the difference is the mechanism's cost: the setter, one small copy
 // on the frame's stream, k_lk_chain_prior in k_lk_chain's place.
@@ -24,7 +26,7 @@
 #include <vector>
 #include "svo.h"
 
-static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false, bool mask = false, bool clahe = false, bool tracks = false, int prior = 0 /* 1: the identity before every call, 2: SVO_PRIOR_LAST_ROTATION */) {
+static double run(const std::vector<const uint8_t*>& L, const std::vector<const uint8_t*>& R, int w, int h, int win, int calls, double max_t, const char* label, bool covariance = false, bool mask = false, bool clahe = false, bool tracks = false, int prior = 0 /* 1: the identity before every call, 2: SVO_PRIOR_LAST_ROTATION */, bool descriptors = false) {
     svo_config cfg; svo_config_default(&cfg);
     cfg.win_w = cfg.win_h = win; cfg.max_translation_norm = max_t;
     svo_context* ctx = nullptr;
@@ -40,6 +42,7 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
     }
     if (clahe && svo_set_clahe(ctx, 1, 2.0, 8, 8) != SVO_OK) { std::fprintf(stderr, "svo_set_clahe: %s\n", svo_last_error()); std::exit(1); }
     if (tracks && svo_set_track_output(ctx, 1, 2048) != SVO_OK) { std::fprintf(stderr, "svo_set_track_output: %s\n", svo_last_error()); std::exit(1); }
+    if (descriptors && svo_set_descriptor_output(ctx, 1) != SVO_OK) { std::fprintf(stderr, "svo_set_descriptor_output: %s\n", svo_last_error()); std::exit(1); }
     if (prior == 2 && svo_set_motion_prior_mode(ctx, SVO_PRIOR_LAST_ROTATION) != SVO_OK) { std::fprintf(stderr, "svo_set_motion_prior_mode: %s\n", svo_last_error()); std::exit(1); }
     const int n = (int)L.size();
     auto pp = [&](int i) { const int p = i % (2 * n - 2); return p < n ? p : 2 * n - 2 - p; };
@@ -63,14 +66,15 @@ static double run(const std::vector<const uint8_t*>& L, const std::vector<const 
 }
 
 int main(int argc, char** argv) {
-    bool covariance = false, mask = false, clahe = false, tracks = false; int prior = 0;
+    bool covariance = false, mask = false, clahe = false, tracks = false, descriptors = false; int prior = 0;
+    if (argc > 3 && !std::strcmp(argv[argc - 1], "--descriptors") && !std::strcmp(argv[argc - 2], "--tracks")) { descriptors = true; argc--; }
     if (argc > 2 && !std::strcmp(argv[argc - 1], "--covariance")) { covariance = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--mask")) { mask = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--clahe")) { clahe = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--tracks")) { tracks = true; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--prior")) { prior = 1; argc--; }
     else if (argc > 2 && !std::strcmp(argv[argc - 1], "--prior-auto")) { prior = 2; argc--; }
-    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance | --mask | --clahe | --tracks | --prior | --prior-auto]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: svo_latency frames.bin [win] [calls] [max_translation] [--covariance | --mask | --clahe | --tracks [--descriptors] | --prior | --prior-auto]\n"); return 2; }
     const int win = argc > 2 ? std::atoi(argv[2]) : 21, calls = argc > 3 ? std::atoi(argv[3]) : 200;
     const double max_t = argc > 4 ? std::atof(argv[4]) : 2.0;
     std::ifstream f(argv[1], std::ios::binary);
@@ -88,6 +92,7 @@ int main(int argc, char** argv) {
     if (mask) run(L, R, w, h, win, calls, max_t, "heap buffers, mask:", false, true);
     if (clahe) run(L, R, w, h, win, calls, max_t, "heap buffers, CLAHE:", false, false, true);
     if (tracks) run(L, R, w, h, win, calls, max_t, "heap buffers, tracks:", false, false, false, true);
+    if (descriptors) run(L, R, w, h, win, calls, max_t, "heap buffers, descriptors:", false, false, false, true, 0, true);
     if (prior) run(L, R, w, h, win, calls, max_t, prior == 2 ? "heap buffers, prior auto:" : "heap buffers, prior:", false, false, false, false, prior);
     uint8_t* pin = (uint8_t*)svo_alloc_pinned(heap.size());
     if (pin) {
@@ -98,6 +103,7 @@ int main(int argc, char** argv) {
         if (mask) run(L, R, w, h, win, calls, max_t, "page-locked, mask:", false, true);
         if (clahe) run(L, R, w, h, win, calls, max_t, "page-locked, CLAHE:", false, false, true);
         if (tracks) run(L, R, w, h, win, calls, max_t, "page-locked, tracks:", false, false, false, true);
+        if (descriptors) run(L, R, w, h, win, calls, max_t, "page-locked, descriptors:", false, false, false, true, 0, true);
         if (prior) run(L, R, w, h, win, calls, max_t, prior == 2 ? "page-locked, prior auto:" : "page-locked, prior:", false, false, false, false, prior);
         svo_free_pinned(pin);
     }
