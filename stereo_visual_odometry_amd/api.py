@@ -865,13 +865,17 @@ class VisualOdometry(BatchVisualOdometry):
         if width is not None:
             super().__init__(width, height, 1, cfg, device)
             self._created = True
-        self._P = None
+        # settings asked for before the context exists: held here (None: not asked for), applied by _apply_pending at the first frame
+        self._P = None                                # projection matrices (kept: set_rotation_prior reads them)
         self._timing = None
-        self._rect = None                             # rectification asked for before the context exists: applied at creation
-        self._cov = None                              # likewise a pose-covariance mode
-        self._mask = None                             # likewise a detection mask
-        self._clahe = None                            # likewise a CLAHE setting (clip_limit, tiles_x, tiles_y)
-        self._track_rows = None                       # likewise the track output's max_rows
+        self._rect = None                             # ("info", left, right) or ("maps", maps, raw_size)
+        self._cov = None                              # (mode, pixel_sigma)
+        self._mask = None
+        self._clahe = None                            # (clip_limit, tiles_x, tiles_y)
+        self._track_rows = None                       # the track output's max_rows
+        self._desc = False                            # descriptors beside the track output
+        self._prior = None                            # (H, Hi): an explicit prior, consumed by the first frame
+        self._prior_mode = None
         self.raw_size = None
         if not self._created:
             self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
@@ -961,7 +965,7 @@ class VisualOdometry(BatchVisualOdometry):
     def set_detection_mask(self, mask, seq=-1):
         if self._created:
             return super().set_detection_mask(mask, seq)
-        if mask is not None and (getattr(mask, "ndim", 0) != 2 or "uint8" not in str(mask.dtype)):
+        if mask is not None and (not hasattr(mask, "ndim") or mask.ndim != 2 or "uint8" not in str(mask.dtype)):
             raise ValueError("detection mask: a 2-D uint8 array expected")
         self._mask = mask                                             # its size is checked against the first frame's
 
@@ -994,7 +998,7 @@ class VisualOdometry(BatchVisualOdometry):
         self._prior_mode = mode                                       # applied when the first frame creates the context
 
     def motion_prior_mode(self):
-        return super().motion_prior_mode() if self._created else getattr(self, "_prior_mode", "explicit")
+        return super().motion_prior_mode() if self._created else (self._prior_mode or "explicit")
 
     def last_motion_prior(self, seq=0):
         if not self._created:
@@ -1008,11 +1012,42 @@ class VisualOdometry(BatchVisualOdometry):
 
     def motion_prior(self, seq=0):
         if not self._created:
-            p = getattr(self, "_prior", None)
+            p = self._prior
             if p is None:
                 return None
             return p[0].reshape(3, 3), (p[1].reshape(3, 3) if p[1] is not None else None)
         return super().motion_prior(seq)
+
+    def _apply_pending(self, fmt):
+        """Hand the context, just created, what was asked for before it existed — in this order (the track output before the
+        descriptors that ride on it; the explicit prior is consumed)."""
+        if self._rect is not None:
+            if self._rect[0] == "info":
+                super().set_rectification(self._rect[1], self._rect[2])
+            else:
+                super().set_rectification_maps(*self._rect[1], raw_size=self._rect[2])
+        # like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
+        # initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
+        super().initalize_projection_matricies(*(self._P if self._P is not None else (np.zeros(12, np.float32), np.zeros(12, np.float32))))
+        if self._timing is not None:
+            super().set_stage_timing(self._timing)
+        if fmt != _lib.INPUT_MONO8:
+            super().set_input_format(fmt)             # (BatchVisualOdometry.__init__ reset the attribute)
+        if self._cov is not None:
+            super().set_pose_covariance(*self._cov)
+        if self._mask is not None:
+            super().set_detection_mask(self._mask)
+        if self._clahe is not None:
+            super().set_clahe(self._clahe[0], self._clahe[1:])
+        if self._track_rows is not None:
+            super().set_track_output(self._track_rows)
+            if self._desc:
+                super().set_descriptor_output(True)
+        if self._prior is not None:
+            super().set_motion_prior(self._prior[0], self._prior[1])
+            self._prior = None
+        if self._prior_mode is not None:
+            super().set_motion_prior_mode(self._prior_mode)
 
     def stereo_callback(self, image_left, image_right):
         fmt = self.input_format
@@ -1029,33 +1064,7 @@ class VisualOdometry(BatchVisualOdometry):
                 h, w = np.asarray(self._rect[1][1]).shape
             super().__init__(w, h, 1, cfg, device)
             self._created = True
-            if self._rect is not None:
-                if self._rect[0] == "info":
-                    super().set_rectification(self._rect[1], self._rect[2])
-                else:
-                    super().set_rectification_maps(*self._rect[1], raw_size=self._rect[2])
-            # like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
-            # initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
-            super().initalize_projection_matricies(*(self._P if self._P is not None else (np.zeros(12, np.float32), np.zeros(12, np.float32))))
-            if self._timing is not None:
-                super().set_stage_timing(self._timing)
-            if fmt != _lib.INPUT_MONO8:
-                super().set_input_format(fmt)         # (BatchVisualOdometry.__init__ reset the attribute)
-            if self._cov is not None:
-                super().set_pose_covariance(*self._cov)
-            if self._mask is not None:
-                super().set_detection_mask(self._mask)
-            if self._clahe is not None:
-                super().set_clahe(self._clahe[0], self._clahe[1:])
-            if self._track_rows is not None:
-                super().set_track_output(self._track_rows)
-                if getattr(self, "_desc", False):
-                    super().set_descriptor_output(True)
-            if getattr(self, "_prior", None) is not None:
-                super().set_motion_prior(self._prior[0], self._prior[1])
-                self._prior = None
-            if getattr(self, "_prior_mode", None) is not None:
-                super().set_motion_prior_mode(self._prior_mode)
+            self._apply_pending(fmt)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()

@@ -13,6 +13,8 @@
 #include <atomic>
 #include <mutex>
 #include <vector>
+#include <algorithm>
+#include <initializer_list>
 #include <math.h>
 
 static thread_local std::string g_err;
@@ -82,12 +84,52 @@ static void make_geometry(Geometry& g, int W, int H, int win, int max_level, int
     g.pyr_bytes = base;
 }
 
-// One slot of the results ring: everything a frame in flight owns besides its rows of the [SVO_RING][2 B] tables (ring_row).
+// One pinned host table of SVO_RING slots, `pitch` elements apart: slot k is the row of the frame in ring slot k, free once that
+// frame has been collected.  Two flavours (rings_alloc):
+//  * RING_MAPPED: kernels read or write the host table in place; `m` is its device address.
+//  * RING_UPLOADED: kernels read a device copy `d`, filled by one upload(slot, stream) per frame on the frame's stream.
+// The motion-prior ring is both: its explicit rows are uploaded, and k_prior_predict writes the rows it predicts into the host
+// table in place.
+enum RingKind { RING_MAPPED = 1, RING_UPLOADED = 2 };
+template <typename T> struct Ring {
+    T *h = nullptr, *m = nullptr, *d = nullptr;
+    size_t pitch = 0;
+    T* row(int slot) const { return h + (size_t)slot * pitch; }
+    T* mapped_row(int slot) const { return m + (size_t)slot * pitch; }
+    T* dev_row(int slot) const { return (d ? d : m) + (size_t)slot * pitch; }          // what the frame's kernels are given
+    hipError_t upload(int slot, hipStream_t st) const { return hipMemcpyAsync((void*)dev_row(slot), (const void*)row(slot), sizeof(T) * pitch, hipMemcpyHostToDevice, st); }
+};
+
+// Everything a frame is issued with that a setter can change.  The context holds the record of the frames to come (`next`: the
+// setters write it and nothing else); enqueue_frame copies it into the frame's ring slot BEFORE the frame is issued, with the
+// facts of that one frame, and everything that issues the frame reads the slot's record; collect_frame copies it into `last`.
+struct FrameSettings {
+    int in_format = SVO_INPUT_MONO8;             // svo_set_input_format; in.bpp <= 1 is mono8.  The kernels are chosen at issue time and take `in` as arguments
+    GreyIn in = {};
+    int cov_mode = SVO_COV_OFF; double cov_sigma2 = 1.;   // svo_set_pose_covariance
+    bool clahe_on = false;                       // svo_set_clahe
+    double clahe_clip = 0.; int clahe_tx = 0, clahe_ty = 0;
+    bool track_on = false, desc_on = false;      // svo_set_track_output, svo_set_descriptor_output (the descriptors ride on the track output)
+    int prior_mode = SVO_PRIOR_EXPLICIT;         // svo_set_motion_prior_mode
+    // the facts of one frame (enqueue_frame; false in `next`)
+    bool ragged = false;                         // it came with an active list: the act ring's row holds its flags
+    bool has_masks = false;                      // its detection applies a mask to some sequence: its row of the mask ring is uploaded
+    bool has_priors = false;                     // it has motion-prior rows: its row of the prior ring holds them
+    bool desc() const { return track_on && desc_on; }
+};
+// the SVO_PATH_* bits that follow from the settings alone
+static int settings_path(const FrameSettings& s) {
+    return (s.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (s.cov_mode ? SVO_PATH_POSE_COV : 0) | (s.clahe_on ? SVO_PATH_CLAHE : 0) |
+           (s.track_on ? SVO_PATH_TRACK_IDS : 0) | (s.desc() ? SVO_PATH_DESCRIPTORS : 0);
+}
+
+// One slot of the results ring: everything a frame in flight owns besides its rows of the pinned rings.
 enum StageEvent { EV_F0, EV_PYR, EV_LK0, EV_LK1, EV_TRI, EV_DONE, EV_COUNT };   // stage boundaries, in svo_get_stage_timing's order
-struct GraphKey {                                // what a slot's graph was captured with (image stride, LK grid, co-resident builds, input format, covariance mode)
-    int stride, gn, co, fmt, cov; double cov_sigma2;
+struct GraphKey {                                // what a slot's graph was captured with: the settings it bakes in (input format, covariance mode), image stride, LK grid, co-resident builds
+    FrameSettings fs; int stride, gn, co;
     bool operator==(const GraphKey& o) const {
-        return stride == o.stride && gn == o.gn && co == o.co && fmt == o.fmt && cov == o.cov && (cov != SVO_COV_FIXED_SIGMA || cov_sigma2 == o.cov_sigma2);
+        return stride == o.stride && gn == o.gn && co == o.co && fs.in_format == o.fs.in_format && fs.cov_mode == o.fs.cov_mode &&
+               (fs.cov_mode != SVO_COV_FIXED_SIGMA || fs.cov_sigma2 == o.fs.cov_sigma2);
     }
 };
 struct RingSlot {
@@ -97,27 +139,41 @@ struct RingSlot {
     GraphKey key = {};
     int g_path = 0;                              // the SVO_PATH_* bits of that capture
     bool staged = false;                         // the slot's stage events were recorded (launch-list mode only)
-    int cov_mode = SVO_COV_OFF;                  // the pose-covariance mode the slot's frame was issued with
-    bool masked = false;                         // ... and whether it came with a mask (h_act's row then holds its flags)
-    bool tracks = false;                         // ... and whether it carried track ids and wrote its observation rows
-    bool priors = false;                         // ... and whether it had motion-prior rows (h_prior's row then holds them)
-    bool desc = false;                           // ... and whether it wrote descriptor rows beside its observation rows
+    FrameSettings fs;                            // what the slot's frame was issued with
 };
 // Detection masks (svo_set_detection_mask): the two slots of one scope (a sequence, or the shared pair).  cur: the slot in force for
 // the frames submitted from now on (-1: none); last: the slot the most recent frame of this scope recorded for its left image — that
 // frame's image is scanned by the NEXT call, so the setter writes the other one.
 struct MaskPair { uint8_t* buf[2] = {nullptr, nullptr}; int cur = -1, last = -1; };
 
+// The last collected frame: what it was issued with, and its optional rows, under one of two policies.
+//  * Small rows (covariance, motion prior) are copied here when the frame is collected.
+//  * Large rows (observations, their headers, descriptors) are read in place, in ring slot obs_slot, and copied into kept_* only
+//    when that slot is about to be written again (keep_last_obs: a submit eight frames later, or a re-allocation of the rings).
+struct LastFrame {
+    int slot = -1;                               // its ring slot (-1: no frame collected yet); the slot's events time it
+    FrameSettings fs;
+    std::vector<PoseCovRow> cov;                 // [B], valid when fs.cov_mode
+    std::vector<PriorRow> prior;                 // [B], valid when fs.has_priors
+    int obs_slot = -1, obs_rows = 0;             // the slot while the rings still hold the rows, else -1: the copies below do; the row pitch (max_rows) of whichever holds them
+    std::vector<svo_track_obs> kept_obs;
+    std::vector<int> kept_hdr;
+    std::vector<uint8_t> kept_desc;              // [B][obs_rows][32] beside kept_obs
+};
+
 struct svo_context {
     int device = 0;
     hipStream_t stream = nullptr;
     DevBuffers d = {};
-    std::vector<void*> allocs;
-    // host side of the results ring
-    FrameResult* h_results = nullptr;            // pinned [SVO_RING][B]
-    const uint8_t** h_ptrs = nullptr;            // pinned [SVO_RING][2][B]
-    int* h_act = nullptr;                        // pinned [SVO_RING][2 B]: a ragged frame's active list and flags (DevBuffers::act) ...
-    int* d_act = nullptr;                        // ... and their device copy, one hipMemcpyAsync per ragged frame (kernels never read host memory for it)
+    // Ownership: device memory registers in `allocs` and pinned host memory in `pinned` when it is allocated (dev_alloc,
+    // pinned_alloc, rings_alloc), and svo_destroy frees by walking the two.  Only the buffers that are replaced while frames may
+    // still name them have owners of their own: the rectification maps, the CLAHE buffers and the mask pairs (retire).
+    std::vector<void*> allocs, pinned;
+    FrameSettings next;                          // the settings of the frames submitted from now on
+    LastFrame last;
+    Ring<FrameResult> results;                   // [B] mapped: k_frame_end stores the records there directly (d.results)
+    Ring<const uint8_t*> ptrs;                   // [2][B] mapped: the frame's image pointers, read in place by the ingest (d.img_ptrs)
+    Ring<int> act;                               // [2 B] uploaded: a ragged frame's active list and flags (DevBuffers::act)
     RingSlot ring[SVO_RING];
     // many-sequence contexts build the NEXT frame's pyramids on a second stream while the current frame is in its LK kernel (issue_frame)
     hipStream_t img_stream = nullptr;
@@ -125,9 +181,9 @@ struct svo_context {
     bool begin_recorded = false;
     bool staged_inputs = false;                  // this frame's images were copied in on `stream` (host-image calls): the image stream must wait for them
     int head = 0, tail = 0, inflight = 0;        // ring indices: head = next to enqueue, tail = oldest outstanding
-    int last_slot = -1;
     uint8_t* staging = nullptr;                  // device [2][B][W*H] for host-image calls
     uint8_t* h_staging = nullptr;                // pinned host mirror of `staging`
+    size_t staging_bytes = 0;                    // size of both (host-image calls of a rectifying context stage raw frames)
     uint8_t* h_upload = nullptr;                 // pinned [6][W*H]: the stage entry points' image uploads (slot x camera)
     bool projection_set = false;
     int lk_grid = 0;
@@ -141,112 +197,124 @@ struct svo_context {
     int last_path = 0;                           // SVO_PATH_* of the most recently issued frame (svo_get_last_frame_path)
     // rectification (svo_set_rectification_maps): raw_w > 0 makes the context take RAW frames.  A map is one device buffer
     // ([W*H] short2 + [W*H] u16) per camera; shared[cam] serves every sequence whose own[seq][cam] is null.  Each frame names its
-    // maps in the slot's row of the pinned table h_maps (read in place by the ingest kernels, beside h_ptrs), so a map replaced
-    // with frames in flight is only retired: freed once every frame enqueued before its replacement has been collected.
+    // maps in its row of the map ring (read in place by the ingest kernels, beside ptrs), so a map replaced with frames in flight
+    // is only retired: freed once every frame enqueued before its replacement has been collected.
     int raw_w = 0, raw_h = 0;
     uint8_t* shared_map[2] = {};
     std::vector<uint8_t*> own_map;               // [B][2]
-    const uint8_t** h_maps = nullptr;            // pinned [SVO_RING][2][B]
-    const uint8_t* const* d_maps = nullptr;      // its device address
+    Ring<const uint8_t*> maps;                   // [2][B] mapped
     struct Retired { uint8_t* p; long long after; };
     std::vector<Retired> retired;                // freed when n_collected >= after
     long long n_enqueued = 0, n_collected = 0;
-    size_t staging_bytes = 0;                    // size of `staging` / `h_staging` (host-image calls of a rectifying context stage raw frames)
-    // input format (svo_set_input_format): what the frames submitted from now on hold; in.bpp <= 1 is mono8.  Host state only: the
-    // kernels are chosen at issue time and take `in` as arguments, so every frame carries its own format.
-    int in_format = SVO_INPUT_MONO8;
-    GreyIn in = {};
-    // pose covariance (svo_set_pose_covariance): the mode and sigma^2 of the frames submitted from now on — host state like the input
-    // format, so every frame carries its own (RingSlot::cov_mode).  The pinned ring is allocated when a mode is first switched on.
-    int cov_mode = SVO_COV_OFF;
-    double cov_sigma2 = 1.;
-    PoseCovRow* h_cov = nullptr;                 // pinned [SVO_RING][B], written by k_pose_cov in place (mapped like h_results)
-    PoseCovRow* d_cov = nullptr;                 // its device address
-    std::vector<PoseCovRow> last_cov;            // [B] the rows of the last collected frame ...
-    int last_cov_mode = SVO_COV_OFF;             // ... and the mode it was issued with
+    Ring<PoseCovRow> cov;                        // [B] mapped, written by k_pose_cov in place; allocated when a mode is first switched on
     // detection masks (svo_set_detection_mask).  Everything below is empty until the first mask is set.  A mask belongs to a left
     // image: img_mask[seq] is the mask of the sequence's last submitted left image — what the sequence's NEXT detection applies —
     // and a frame's row of mask_rows is filled from it when the frame is enqueued.
     MaskPair shared_mask;
     std::vector<MaskPair> own_mask;              // [B]
     std::vector<const uint8_t*> img_mask;        // [B]
-    const uint8_t** h_mask_rows = nullptr;       // pinned [SVO_RING][B] ...
-    const uint8_t** d_mask_rows = nullptr;       // ... and the device copy the masked FAST kernels read (one hipMemcpyAsync per masked frame)
+    Ring<const uint8_t*> mask_rows;              // [B] uploaded: the device copy is what the masked FAST kernels read
     uint8_t* h_mask_stage = nullptr;             // pinned [W*H]: a host mask's packed rows on their way to the device
     hipEvent_t ev_mask_stage = nullptr;          // that copy has run: the staging buffer may be written again
-    // CLAHE (svo_set_clahe): the setting of the frames submitted from now on — host state like the input format, so every frame
-    // carries its own.  The buffers appear at first use (clahe_buffers): one allocation holds the device table of the staging
-    // frames' addresses ([2][B], what the frame's ingest takes in place of the caller's pointer table) and the frames themselves
-    // (in_width x in_height mono8, packed, `clahe_pitch` bytes apart); the LUTs are [B][2][tiles_y][tiles_x][256].
+    // CLAHE buffers, at first use (clahe_buffers): one allocation holds the device table of the staging frames' addresses ([2][B],
+    // what the frame's ingest takes in place of the caller's pointer table) and the frames themselves (in_width x in_height mono8,
+    // packed, `clahe_pitch` bytes apart); the LUTs are [B][2][tiles_y][tiles_x][256].
     // ONE staging set per context is enough only because a frame's CLAHE launches and the ingest that consumes them are adjacent
     // on ONE stream — img_stream for build-ahead contexts, `stream` otherwise, the same one for every CLAHE frame of a context
     // (they are never captured into a graph) — so frame N + 1's equalisation is ordered behind frame N's ingest.  A path that
     // fills the staging frames from another stream must order itself with an event.
-    bool clahe_on = false;
-    double clahe_clip = 0.;
-    int clahe_tx = 0, clahe_ty = 0;
     uint8_t* clahe_buf = nullptr;                // [table | frames]
     size_t clahe_pitch = 0;
     int clahe_w = 0, clahe_h = 0;                // the frame size clahe_buf was allocated for
     uint8_t* clahe_lut = nullptr;
     int clahe_lut_tiles = 0;                     // tiles per image clahe_lut has room for
-    // track ids and observation rows (svo_set_track_output).  Everything below is empty until the output is first switched on.
-    // Host state like the covariance mode: a frame carries whether it was issued with the output on (RingSlot::tracks); switching
-    // is refused with frames in flight.  The id buffers are device memory of the context (freed with its other allocations); the
-    // ring is pinned host memory the device writes in place (k_track_obs), re-allocated when max_rows changes.
-    bool track_on = false;
-    int track_rows = 0;                          // max_rows of the ring as allocated
+    // track ids and observation rows (svo_set_track_output), empty until the output is first switched on; switching is refused with
+    // frames in flight.  The id buffers are device memory of the context; the rings are written in place (k_track_obs,
+    // k_track_desc) and re-allocated when max_rows changes.  The descriptor ring has the shape of the observation ring, a row of
+    // 32 bytes beside every observation row: the same max_rows, headers, slot and moment for the host copy (keep_last_obs).
+    int track_rows = 0;                          // max_rows of the observation ring as allocated
     IdArgs ids = {};
-    svo_track_obs* h_obs = nullptr;              // pinned, mapped [SVO_RING][B][track_rows] ...
-    svo_track_obs* d_obs = nullptr;              // ... and its device address
-    int* h_obs_hdr = nullptr;                    // pinned, mapped [SVO_RING][B] {n_tracks, n_rows}
-    int* d_obs_hdr = nullptr;
-    // the last collected frame's rows: its slot of the ring, read in place — or, once a later submit is about to reuse that slot
-    // (eight frames in flight), the copy enqueue_frame made of it first
-    bool last_tracks_on = false;                 // that frame was issued with the output on
-    int last_obs_slot = -1;                      // its slot while the ring still holds it, else -1: the copies below do
-    int last_obs_rows = 0;                       // the row pitch of whichever holds it
-    std::vector<svo_track_obs> kept_obs;
-    std::vector<int> kept_hdr;
-    // binary descriptors (svo_set_descriptor_output): a row of 32 bytes beside every observation row, in a pinned mapped ring of the
-    // same shape ([SVO_RING][B][track_rows][32]) that k_track_desc writes in place.  It rides on the track output: the same max_rows,
-    // the same headers, the same slot, the same moment for the host copy (keep_last_obs).  Empty until first switched on.
-    bool desc_on = false;
-    int desc_rows = 0;                           // the max_rows the ring was allocated for (0: no ring)
-    uint8_t* h_desc = nullptr;
-    uint8_t* d_desc = nullptr;
-    bool last_desc_on = false;                   // the last collected frame was issued with descriptors on
-    std::vector<uint8_t> kept_desc;              // [B][last_obs_rows][32] beside kept_obs
+    Ring<svo_track_obs> obs;                     // [B][track_rows] mapped
+    Ring<int> obs_hdr;                           // [B] {n_tracks, n_rows} mapped
+    Ring<uint8_t> desc;                          // [B][track_rows as it was allocated][32] mapped
     // motion priors (svo_set_motion_prior).  Everything below is empty until the first setter.  prior_next[seq] is the prior the
-    // sequence's next frame will use (has = 1) — host state, consumed when that frame is enqueued (take_priors): the frame's rows go
-    // into its slot's row of the pinned ring and from there, with one copy on the frame's stream, into the slot's device row that
-    // k_lk_chain_prior reads.  A slot's rows are free once its frame has been collected, so every frame in flight keeps its own.
+    // sequence's next frame will use (has = 1) — consumed when that frame is enqueued (take_priors): the frame's rows go into its
+    // row of the prior ring and from there, with one upload on the frame's stream, into the device row that k_lk_chain_prior reads.
+    // A frame issued in SVO_PRIOR_LAST_ROTATION always has its device row; k_prior_predict, first on the frame's stream, fills the
+    // rows no explicit prior filled, for the sequences listed in the frame's row of prior_act.
     std::vector<PriorRow> prior_next;            // [B]
     int n_prior = 0;                             // how many of them are pending
-    PriorRow* h_prior = nullptr;                 // pinned [SVO_RING][B], mapped: k_prior_predict writes the rows it predicts in place
-    PriorRow* d_prior = nullptr;                 // device [SVO_RING][B]
-    // SVO_PRIOR_LAST_ROTATION (svo_set_motion_prior_mode): host state read when a frame is enqueued, like the input format.  A frame
-    // issued in this mode always has its device row; k_prior_predict, first on the frame's stream, fills the rows no explicit prior
-    // filled.  h_prior_act: the frame's own list of the sequences that take it, for that kernel alone (mapped, read in place).
-    int prior_mode = SVO_PRIOR_EXPLICIT;
-    PriorRow* hd_prior = nullptr;                // h_prior as the device sees it
-    int* h_prior_act = nullptr;                  // pinned [SVO_RING][B], mapped
-    int* hd_prior_act = nullptr;
-    std::vector<PriorRow> last_prior;            // [B]: the rows of the frame last collected (svo_get_last_motion_prior); empty: it had none
+    Ring<PriorRow> prior;                        // [B] mapped and uploaded
+    Ring<int> prior_act;                         // [B] mapped
 };
 
-// a slot's row of one of the [SVO_RING][2 B] tables (h_ptrs / d.img_ptrs, h_act / d_act, h_maps / d_maps)
-template <typename T> static T* ring_row(const svo_context* c, T* table, int slot) { return table + (size_t)slot * 2 * c->d.B; }
-
-template <typename T>
-static int dev_alloc(svo_context* c, T** p, size_t count) {
+template <typename T> static int dev_alloc(svo_context* c, T** p, size_t count) {
     void* q = nullptr;
     const size_t bytes = count * sizeof(T) > 0 ? count * sizeof(T) : 16;
     HIPCHK(hipMalloc(&q, bytes));
+    c->allocs.push_back(q);                                           // registered first: a failed clear leaves nothing behind
     HIPCHK(hipMemsetAsync(q, 0, bytes, c->stream));
-    c->allocs.push_back(q);
     *p = (T*)q;
     return SVO_OK;
+}
+template <typename T> static int pinned_alloc(svo_context* c, T** p, size_t bytes) {
+    HIPCHK(hipHostMalloc((void**)p, bytes));
+    c->pinned.push_back((void*)*p);
+    return SVO_OK;
+}
+// free a registered buffer ahead of the context's end (a buffer that grows, a ring re-allocated at another pitch)
+static void unregister(std::vector<void*>& reg, const void* p) { reg.erase(std::remove(reg.begin(), reg.end(), p), reg.end()); }
+static void dev_free(svo_context* c, void* p) { if (p) { unregister(c->allocs, p); (void)hipFree(p); } }
+static void pinned_free(svo_context* c, void* p) { if (p) { unregister(c->pinned, p); (void)hipHostFree(p); } }
+
+// The one allocation of rings: a set of EMPTY rings, each cleared, all or nothing — on any failure everything this call allocated is
+// freed, the rings are empty again and the HIP error is returned.  The device copy of an uploaded ring is cleared on the context's
+// stream: before any frame that names its rows.
+struct RingSpec { void **h, **m, **d; size_t* pitch_out; size_t elem, pitch; int kind; };
+template <typename T> static RingSpec ring_spec(Ring<T>& r, size_t pitch, int kind) { return {(void**)&r.h, (void**)&r.m, (void**)&r.d, &r.pitch, sizeof(T), pitch, kind}; }
+static hipError_t rings_alloc(svo_context* c, std::initializer_list<RingSpec> set) {
+    hipError_t e = hipSuccess;
+    for (const RingSpec& s : set) {
+        const size_t bytes = s.elem * s.pitch * SVO_RING;
+        if (e == hipSuccess) e = hipHostMalloc(s.h, bytes, (s.kind & RING_MAPPED) ? hipHostMallocMapped : hipHostMallocDefault);
+        if (e == hipSuccess) memset(*s.h, 0, bytes);
+        if (e == hipSuccess && (s.kind & RING_MAPPED)) { e = hipHostGetDevicePointer(s.m, *s.h, 0); if (e == hipSuccess && !*s.m) e = hipErrorInvalidDevicePointer; }
+        if (e == hipSuccess && (s.kind & RING_UPLOADED)) e = hipMalloc(s.d, bytes);
+        if (e == hipSuccess && *s.d) e = hipMemsetAsync(*s.d, 0, bytes, c->stream);
+        *s.pitch_out = s.pitch;
+    }
+    for (const RingSpec& s : set) {
+        if (e == hipSuccess) { c->pinned.push_back(*s.h); if (*s.d) c->allocs.push_back(*s.d); continue; }
+        if (*s.h) (void)hipHostFree(*s.h);
+        if (*s.d) (void)hipFree(*s.d);
+        *s.h = *s.m = *s.d = nullptr; *s.pitch_out = 0;
+    }
+    return e;
+}
+template <typename T> static void ring_free(svo_context* c, Ring<T>& r) { pinned_free(c, (void*)r.h); dev_free(c, (void*)r.d); r = Ring<T>(); }
+
+static int read_state(svo_context* c, int seq, SeqState* hs) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(hs, c->d.st + seq, sizeof(SeqState), hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+static int set_state(svo_context* c, const SeqState& hs) {
+    HIPCHK(hipMemcpyAsync(c->d.st, &hs, sizeof(SeqState), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));      // hs is a stack object
+    return SVO_OK;
+}
+// the sequences a setter's `seq` names: [*s0, *s1), -1 being all of them
+static int seq_range(const svo_context* c, int seq, int* s0 = nullptr, int* s1 = nullptr) {
+    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if (s0) { *s0 = seq < 0 ? 0 : seq; *s1 = seq < 0 ? c->d.B : seq + 1; }
+    return SVO_OK;
+}
+// a buffer that frames in flight may still name (a replaced map, CLAHE buffer): freed once every frame enqueued so far has been collected
+static void retire(svo_context* c, uint8_t* p) {
+    if (!p) return;
+    if (c->inflight == 0) (void)hipFree(p);
+    else c->retired.push_back({p, c->n_enqueued});
 }
 
 // what a context derives from its configuration's parameters, once d.CAP and d.geom stand (ctx_create, stage_reconfigure)
@@ -320,7 +388,6 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     ALLOC(d.tl0, B * CAP); ALLOC(d.tr0, B * CAP); ALLOC(d.tl1, B * CAP); ALLOC(d.tr1, B * CAP);
     ALLOC(d.world, B * CAP * 3); ALLOC(d.inlier, B * CAP); ALLOC(d.inl_idx, B * CAP);
     ALLOC(d.subsets, B * (size_t)d.K * 5); ALLOC(d.hyp, B * (size_t)d.K * 12); ALLOC(d.hyp_good, B * (size_t)d.K);
-    ALLOC(c->d_act, (size_t)SVO_RING * 2 * B);
     {
         double* lam = nullptr;
         ALLOC(lam, 33);
@@ -333,16 +400,11 @@ static int ctx_create(const svo_config* cfg_in, int device, int n_seq, int width
     }
 #undef ALLOC
     // the results ring lives in pinned HOST memory that the device can write: k_frame_end stores the B records there directly
-    // (180 B per sequence over PCIe) instead of a device buffer plus a copy operation per frame
-    HIPCHK(hipHostMalloc((void**)&c->h_results, sizeof(FrameResult) * SVO_RING * B, hipHostMallocMapped));
-    memset(c->h_results, 0, sizeof(FrameResult) * SVO_RING * B);
-    { void* dv = nullptr; HIPCHK(hipHostGetDevicePointer(&dv, c->h_results, 0)); d.results = (FrameResult*)dv; }
-    HIPCHK(hipHostMalloc((void**)&c->h_ptrs, sizeof(uint8_t*) * SVO_RING * 2 * B, hipHostMallocMapped));
-    HIPCHK(hipHostGetDevicePointer((void**)&d.img_ptrs, (void*)c->h_ptrs, 0));   // read in place by k_ingest: no per-frame upload
-    HIPCHK(hipHostMalloc((void**)&c->h_act, sizeof(int) * SVO_RING * 2 * B));
-    HIPCHK(hipHostMalloc((void**)&c->h_maps, sizeof(uint8_t*) * SVO_RING * 2 * B, hipHostMallocMapped));
-    memset((void*)c->h_maps, 0, sizeof(uint8_t*) * SVO_RING * 2 * B);
-    HIPCHK(hipHostGetDevicePointer((void**)&c->d_maps, (void*)c->h_maps, 0));
+    // (180 B per sequence over PCIe) instead of a device buffer plus a copy operation per frame; the pointer tables are read in
+    // place by k_ingest: no per-frame upload
+    HIPCHK(rings_alloc(c, {ring_spec(c->results, B, RING_MAPPED), ring_spec(c->ptrs, 2 * B, RING_MAPPED), ring_spec(c->act, 2 * B, RING_UPLOADED),
+                           ring_spec(c->maps, 2 * B, RING_MAPPED)}));
+    d.results = c->results.m; d.img_ptrs = c->ptrs.m;
     c->own_map.assign(2 * B, nullptr);
     for (RingSlot& r : c->ring) for (hipEvent_t& e : r.ev) HIPCHK(hipEventCreate(&e));
     // initial state: rotation = I, translation = 0, last_transform = I (vo.h:266-268); no slots in use
@@ -404,18 +466,13 @@ extern "C" void svo_destroy(svo_context* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
-    if (c->staging) (void)hipFree(c->staging);
-    for (void* p : {(void*)c->h_staging, (void*)c->h_upload, (void*)c->h_results, (void*)c->h_ptrs, (void*)c->h_act, (void*)c->h_maps, (void*)c->h_cov, (void*)c->h_obs, (void*)c->h_obs_hdr, (void*)c->h_desc}) if (p) (void)hipHostFree(p);
-    for (int k = 0; k < 2; k++) if (c->shared_map[k]) (void)hipFree(c->shared_map[k]);
+    for (void* p : c->pinned) (void)hipHostFree(p);
+    // the buffers with owners of their own (svo_context, Ownership)
+    for (uint8_t* p : {c->shared_map[0], c->shared_map[1], c->shared_mask.buf[0], c->shared_mask.buf[1], c->clahe_buf, c->clahe_lut}) if (p) (void)hipFree(p);
     for (uint8_t* p : c->own_map) if (p) (void)hipFree(p);
+    for (const MaskPair& m : c->own_mask) for (uint8_t* p : m.buf) if (p) (void)hipFree(p);
     for (const auto& r : c->retired) (void)hipFree(r.p);
-    for (int k = 0; k < 2; k++) if (c->shared_mask.buf[k]) (void)hipFree(c->shared_mask.buf[k]);
-    for (const MaskPair& m : c->own_mask) for (int k = 0; k < 2; k++) if (m.buf[k]) (void)hipFree(m.buf[k]);
-    if (c->d_mask_rows) (void)hipFree((void*)c->d_mask_rows);
-    for (void* p : {(void*)c->h_mask_rows, (void*)c->h_mask_stage}) if (p) (void)hipHostFree(p);
     if (c->ev_mask_stage) (void)hipEventDestroy(c->ev_mask_stage);
-    for (void* p : {(void*)c->clahe_buf, (void*)c->clahe_lut, (void*)c->d_prior}) if (p) (void)hipFree(p);
-    for (void* p : {(void*)c->h_prior, (void*)c->h_prior_act}) if (p) (void)hipHostFree(p);
     for (RingSlot& r : c->ring) {
         for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
         if (r.ev_img) (void)hipEventDestroy(r.ev_img);
@@ -435,14 +492,15 @@ extern "C" int svo_get_last_frame_path(svo_context* c) { return c ? c->last_path
 
 extern "C" int svo_set_projection(svo_context* c, int seq, const float Pl[12], const float Pr[12]) {
     if (!c || !Pl || !Pr) return fail_arg("null argument");
-    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    int s0, s1;
+    if (const int rc = seq_range(c, seq, &s0, &s1)) return rc;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     // Pl, Pr, K are adjacent members of SeqState: one strided 2-D copy writes them into every selected sequence's record
     // (row = the 33 floats, pitch = sizeof(SeqState)) instead of three blocking copies per sequence
     static_assert(offsetof(SeqState, Pr) == offsetof(SeqState, Pl) + sizeof(float) * 12 && offsetof(SeqState, K) == offsetof(SeqState, Pl) + sizeof(float) * 24,
                   "Pl, Pr, K must be contiguous");
-    const int s0 = seq < 0 ? 0 : seq, ns = seq < 0 ? c->d.B : 1;
+    const int ns = s1 - s0;
     std::vector<float> rows((size_t)ns * 33);
     for (int s = 0; s < ns; s++) {
         float* r = rows.data() + (size_t)s * 33;
@@ -455,27 +513,22 @@ extern "C" int svo_set_projection(svo_context* c, int seq, const float Pl[12], c
     return SVO_OK;
 }
 
-static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active = nullptr);
 // the size of the frames the caller passes: the raw size when the context rectifies, else the context's own
 static int in_width(const svo_context* c) { return c->raw_w > 0 ? c->raw_w : c->d.geom.W; }
 static int in_height(const svo_context* c) { return c->raw_w > 0 ? c->raw_h : c->d.geom.H; }
 // bytes per pixel of those frames: the channels of a colour context, else the input format's
-static int in_bpp(const svo_context* c) { return c->d.CN == 3 ? 3 : c->in.bpp > 1 ? c->in.bpp : 1; }
+static int in_bpp(const svo_context* c) { return c->d.CN == 3 ? 3 : c->next.in.bpp > 1 ? c->next.in.bpp : 1; }
 
 // The frame's view of the context's buffers: c->d plus the slot's rows of the active list and of the map table (every other launch
 // sees the context's own unmasked, plain DevBuffers).  n_act >= 0: a ragged frame — only the n_act sequences listed in the slot's
-// row of h_act take it (its grids cover those alone, through DevBuffers::act).
+// row of the act ring take it (its grids cover those alone, through DevBuffers::act); that row is uploaded on the stream of the
+// frame's first kernel (kernels never read host memory for it).
 static DevBuffers frame_view(const svo_context* c, int slot, int n_act) {
     DevBuffers f = c->d;
-    if (n_act >= 0) { f.act = ring_row(c, c->d_act, slot); f.n_act = n_act; }
-    if (c->raw_w > 0) f.rmap = ring_row(c, c->d_maps, slot);         // the frame's own maps (fill_slot_rows filled the row)
-    f.in = c->in;                                                    // the format set when the frame is issued
+    if (n_act >= 0) { f.act = c->act.dev_row(slot); f.n_act = n_act; }
+    if (c->raw_w > 0) f.rmap = c->maps.dev_row(slot);                // the frame's own maps (fill_slot_rows filled the row)
+    f.in = c->ring[slot].fs.in;                                      // the format the frame was enqueued with
     return f;
-}
-// the slot's row of h_act to the device, on the stream of the frame's first kernel (kernels never read host memory for it)
-static hipError_t upload_act(const svo_context* c, int slot, hipStream_t st) {
-    return hipMemcpyAsync(ring_row(c, c->d_act, slot), ring_row(c, c->h_act, slot), sizeof(int) * 2 * (size_t)c->d.B, hipMemcpyHostToDevice, st);
 }
 
 // ---- CLAHE (svo.h): geometry, buffers and the two launches in front of an ingest ----
@@ -510,10 +563,9 @@ static bool clahe_derive(ClaheArgs& a, int w, int h, double clip_limit, int tile
     a.scale = 255.0f / (float)area; a.inv_tw = 1.0f / (float)tw; a.inv_th = 1.0f / (float)th;
     return true;
 }
-static void retire_map(svo_context* c, uint8_t* p);
 // The staging frames and LUTs for the context's input size and tile count as they are NOW; buffers of another size that frames in
 // flight may still name are retired like replaced rectification maps.
-static int clahe_buffers(svo_context* c) {
+static int clahe_buffers(svo_context* c, const FrameSettings& fs) {
     const int W = in_width(c), H = in_height(c), B = c->d.B;
     if (!c->clahe_buf || c->clahe_w != W || c->clahe_h != H) {
         const size_t table = (sizeof(uint8_t*) * 2 * B + 255) & ~(size_t)255, pitch = ((size_t)W * H + 255) & ~(size_t)255;
@@ -522,27 +574,27 @@ static int clahe_buffers(svo_context* c) {
         std::vector<const uint8_t*> ptrs((size_t)2 * B);
         for (int i = 0; i < 2 * B; i++) ptrs[i] = p + table + pitch * i;
         if (hipMemcpy(p, ptrs.data(), sizeof(uint8_t*) * 2 * B, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); g_err = "CLAHE: pointer table upload failed"; return SVO_ERR_HIP; }
-        retire_map(c, c->clahe_buf);
+        retire(c, c->clahe_buf);
         c->clahe_buf = p; c->clahe_pitch = pitch; c->clahe_w = W; c->clahe_h = H;
     }
-    const int tiles = c->clahe_tx * c->clahe_ty;
+    const int tiles = fs.clahe_tx * fs.clahe_ty;
     if (!c->clahe_lut || c->clahe_lut_tiles < tiles) {
         uint8_t* p = nullptr;
         HIPCHK(hipMalloc((void**)&p, (size_t)B * 2 * tiles * 256));
-        retire_map(c, c->clahe_lut);
+        retire(c, c->clahe_lut);
         c->clahe_lut = p; c->clahe_lut_tiles = tiles;
     }
     return SVO_OK;
 }
 // The frame's two CLAHE launches on st, in front of the ingest that st runs next: srcs / stride are the caller's frames in the format
 // f.in; afterwards they name the staging frames and f.in is mono8 — the ingest runs as a mono8 frame's, maps and active list unchanged.
-static int clahe_front(svo_context* c, DevBuffers& f, const uint8_t* const*& srcs, int& stride, hipStream_t st) {
+static int clahe_front(svo_context* c, const FrameSettings& fs, DevBuffers& f, const uint8_t* const*& srcs, int& stride, hipStream_t st) {
     ClaheArgs a = {};
-    if (!clahe_derive(a, in_width(c), in_height(c), c->clahe_clip, c->clahe_tx, c->clahe_ty)) {
+    if (!clahe_derive(a, in_width(c), in_height(c), fs.clahe_clip, fs.clahe_tx, fs.clahe_ty)) {
         g_err = "CLAHE: the tiles do not fit the raw size this context now rectifies (svo.h, CLAHE rule 1)";
         return SVO_ERR_STATE;
     }
-    if (const int rc = clahe_buffers(c)) return rc;
+    if (const int rc = clahe_buffers(c, fs)) return rc;
     const size_t table = (sizeof(uint8_t*) * 2 * c->d.B + 255) & ~(size_t)255;
     a.srcs = srcs; a.act = f.act; a.B = c->d.B; a.ncam = 2; a.stride = stride; a.g = f.in;
     a.lut = c->clahe_lut; a.out = c->clahe_buf + table; a.pitch = c->clahe_pitch;
@@ -572,9 +624,9 @@ static int front_ahead(svo_context* c, DevBuffers& f, int slot, int stride) {
         HIPCHK(hipStreamWaitEvent(c->img_stream, c->ev_begin, 0));
     }
     if (c->staged_inputs) HIPCHK(hipStreamWaitEvent(c->img_stream, r.ev[EV_F0], 0));   // host-image call: the H2D copies were queued on `stream` before this frame's start event
-    if (f.act) HIPCHK(upload_act(c, slot, c->img_stream));
-    const uint8_t* const* srcs = ring_row(c, f.img_ptrs, slot);
-    if (c->clahe_on) if (const int rc = clahe_front(c, f, srcs, stride, c->img_stream)) return rc;   // behind the waits above, like the ingest
+    if (f.act) HIPCHK(c->act.upload(slot, c->img_stream));
+    const uint8_t* const* srcs = c->ptrs.dev_row(slot);
+    if (r.fs.clahe_on) if (const int rc = clahe_front(c, r.fs, f, srcs, stride, c->img_stream)) return rc;   // behind the waits above, like the ingest
     launch_ingest_pyramid(f, srcs, stride, c->img_stream, PYR_NEXT);
     HIPCHK(hipEventRecord(r.ev_img, c->img_stream));
     HIPCHK(hipStreamWaitEvent(s, r.ev_img, 0));
@@ -583,20 +635,34 @@ static int front_ahead(svo_context* c, DevBuffers& f, int slot, int stride) {
     return SVO_OK;
 }
 
-// The launch list of one frame (vo.cpp:41-137 as kernels), between the slot's start and done events.
-// with_events: record the stage-boundary events (not inside a graph capture).  n_act: see frame_view.
-// mrows: the frame's row of d_mask_rows when its detection applies a mask to some sequence (enqueue_frame), else null.
-// pri: the frame's motion priors (take_priors) — rows: its device row when some active sequence has an explicit prior or the frame
-// predicts (SVO_PRIOR_LAST_ROTATION), else null; predict: k_prior_predict fills the rows no explicit prior filled; uploaded: the
-// explicit rows were copied into the device row.
+// What enqueue_frame decides for one frame besides its settings (RingSlot::fs), handed to issue_frame and replay_graph.
+// n_act: see frame_view.  mrows: the frame's row of the mask ring's device copy when its detection applies a mask to some sequence
+// (take_masks), else null.  pri: the frame's motion priors (take_priors) — rows: its device row when some active sequence has an
+// explicit prior or the frame predicts (SVO_PRIOR_LAST_ROTATION), else null; predict: k_prior_predict fills the rows no explicit
+// prior filled; uploaded: the explicit rows were copied into the device row.
 struct FramePriors { PriorRow* rows = nullptr; bool predict = false, uploaded = false; };
-static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_events, DeviceSharing share, int n_act = -1,
-                       const uint8_t* const* mrows = nullptr, const FramePriors& pri = FramePriors()) {
+struct FramePlan {
+    int slot = 0, stride = 0, gn = 0, n_act = -1;   // gn: the LK grid
+    bool with_events = false;                    // record the stage-boundary events (a graph capture records none)
+    DeviceSharing share = {};
+    const uint8_t* const* mrows = nullptr;
+    FramePriors pri;
+};
+// can the frame run as a replay of its slot's captured graph?  (a ragged, rectifying, masked, CLAHE, track-ids or motion-prior frame: no)
+static bool graph_replayable(const svo_context* c, const FrameSettings& fs, int n_act) {
+    return c->use_graph && n_act < 0 && c->raw_w == 0 && !fs.has_masks && !fs.clahe_on && !fs.track_on && !fs.has_priors;
+}
+
+// The launch list of one frame (vo.cpp:41-137 as kernels), between the slot's start and done events.
+static int issue_frame(svo_context* c, const FramePlan& p) {
     hipStream_t s = c->stream;
-    const PriorRow* const prow = pri.rows;
-    const auto record = [&](StageEvent which) { return with_events ? hipEventRecord(c->ring[slot].ev[which], s) : hipSuccess; };
+    const int slot = p.slot, n_act = p.n_act;
+    const FrameSettings& fs = c->ring[slot].fs;
+    const PriorRow* const prow = p.pri.rows;
+    int stride = p.stride;
+    const auto record = [&](StageEvent which) { return p.with_events && !c->capturing ? hipEventRecord(c->ring[slot].ev[which], s) : hipSuccess; };
     if (n_act == 0) {                                                  // all idle: the result rows are the whole frame
-        HIPCHK(upload_act(c, slot, s));
+        HIPCHK(c->act.upload(slot, s));
         HIPCHK(record(EV_PYR)); HIPCHK(record(EV_LK0)); HIPCHK(record(EV_LK1)); HIPCHK(record(EV_TRI));
         launch_frame_end(frame_view(c, slot, 0), slot, s);
         c->begin_recorded = false; c->last_path = 0;
@@ -604,48 +670,47 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     }
     // the predicted priors first: SeqState::ok and R are the previous frame's (k_pnp_final ran on this stream) until the per-frame
     // reset below clears ok — the PYR_BEGIN ingest, the fused front, or launch_frame_begin behind front_ahead
-    if (pri.predict)
-        launch_prior_predict(c->d, n_act >= 0 ? c->hd_prior_act + (size_t)slot * c->d.B : nullptr, n_act >= 0 ? n_act : c->d.B, pri.uploaded,
-                             pri.rows, c->hd_prior + (size_t)slot * c->d.B, s);
-    HIPCHK(choose_pnp_build(c->d, share.lean));
+    if (p.pri.predict)
+        launch_prior_predict(c->d, n_act >= 0 ? c->prior_act.mapped_row(slot) : nullptr, n_act >= 0 ? n_act : c->d.B, p.pri.uploaded,
+                             p.pri.rows, c->prior.mapped_row(slot), s);
+    HIPCHK(choose_pnp_build(c->d, p.share.lean));
     DevBuffers f = frame_view(c, slot, n_act);                         // after the build choice: co_resident travels in the view
-    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | (f.in.bpp > 1 ? SVO_PATH_INPUT_CONVERTED : 0) | (c->cov_mode ? SVO_PATH_POSE_COV : 0) |
-               (c->clahe_on ? SVO_PATH_CLAHE : 0) | (c->track_on ? SVO_PATH_TRACK_IDS : 0) | (c->track_on && c->desc_on ? SVO_PATH_DESCRIPTORS : 0);
-    const bool ids = c->track_on;
-    const uint8_t* const* dp = ring_row(c, f.img_ptrs, slot);          // the slot's pointer table: pinned host memory the kernel reads in place
+    int path = (f.co_resident ? SVO_PATH_LEAN : 0) | settings_path(fs);
+    const bool ids = fs.track_on;
+    const uint8_t* const* dp = c->ptrs.dev_row(slot);                  // the slot's pointer table: pinned host memory the kernel reads in place
     const bool ahead = !c->capturing && ingest_ahead_applies(f);
     bool detected = false;
     if (ahead) {
         if (const int rc = front_ahead(c, f, slot, stride)) return rc;
         path |= SVO_PATH_INGEST_AHEAD;
     } else {
-        if (f.act) HIPCHK(upload_act(c, slot, s));
-        if (c->clahe_on) if (const int rc = clahe_front(c, f, dp, stride, s)) return rc;   // the front below then ingests the staging frames as mono8
-        detected = !mrows && !ids && launch_front_fused(f, dp, stride, s);   // lone stream: ingest + pyramid beside detection, two launches (a masked or ids frame: the unfused front)
+        if (f.act) HIPCHK(c->act.upload(slot, s));
+        if (fs.clahe_on) if (const int rc = clahe_front(c, fs, f, dp, stride, s)) return rc;   // the front below then ingests the staging frames as mono8
+        detected = !p.mrows && !ids && launch_front_fused(f, dp, stride, s);   // lone stream: ingest + pyramid beside detection, two launches (a masked or ids frame: the unfused front)
         if (detected) path |= SVO_PATH_FRONT_FUSED;
         else launch_ingest_pyramid(f, dp, stride, s, PYR_BEGIN);       // + the per-frame reset
     }
     c->begin_recorded = ahead;
     HIPCHK(record(EV_PYR));                                            // (fused front: ms[0] = the whole front, ms[1] ~ 0)
     if (ids) {                                                         // both passes with the ids build of the emit, masked or not
-        const MaskArgs m = {mrows, f.geom.W};
-        launch_detect_ids(f, c->ids, mrows ? &m : nullptr, 0, -1, s); launch_detect_ids(f, c->ids, mrows ? &m : nullptr, 1, -1, s);
-        if (mrows) path |= SVO_PATH_DETECT_MASKED;
-    } else if (mrows) {                                                // both passes behind the masks of the image they scan
-        const MaskArgs m = {mrows, f.geom.W};
+        const MaskArgs m = {p.mrows, f.geom.W};
+        launch_detect_ids(f, c->ids, p.mrows ? &m : nullptr, 0, -1, s); launch_detect_ids(f, c->ids, p.mrows ? &m : nullptr, 1, -1, s);
+        if (p.mrows) path |= SVO_PATH_DETECT_MASKED;
+    } else if (p.mrows) {                                                // both passes behind the masks of the image they scan
+        const MaskArgs m = {p.mrows, f.geom.W};
         launch_detect_masked(f, m, 0, -1, s); launch_detect_masked(f, m, 1, -1, s);
         path |= SVO_PATH_DETECT_MASKED;
     } else if (!detected) { launch_detect(f, 0, -1, s); launch_detect(f, 1, -1, s); }
     // chained LK launches (a captured graph cannot wait for another stream's event): wait before the launch, record after it
-    LkGate* const gate = !c->capturing && share.shared ? &g_lk_gate[c->device] : nullptr;
+    LkGate* const gate = !c->capturing && p.share.shared ? &g_lk_gate[c->device] : nullptr;
     if (gate) {
         std::lock_guard<std::mutex> lock(gate->mu);
         if (gate->armed) HIPCHK(hipStreamWaitEvent(s, gate->ev, 0));
         path |= SVO_PATH_LK_CHAINED;
     }
     HIPCHK(record(EV_LK0));
-    if (!launch_lk_chain(f, gn, s, 1, prow)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // with priors: k_lk_chain_prior, the LK launch of this frame in every respect
-    if (prow) path |= SVO_PATH_MOTION_PRIOR | (pri.predict ? SVO_PATH_PRIOR_PREDICTED : 0);
+    if (!launch_lk_chain(f, p.gn, s, 1, prow)) { g_err = "no LK kernel is built for this window / channel count"; return SVO_ERR_STATE; }   // with priors: k_lk_chain_prior, the LK launch of this frame in every respect
+    if (prow) path |= SVO_PATH_MOTION_PRIOR | (p.pri.predict ? SVO_PATH_PRIOR_PREDICTED : 0);
     HIPCHK(record(EV_LK1));
     if (gate) {
         std::lock_guard<std::mutex> lock(gate->mu);
@@ -660,10 +725,10 @@ static int issue_frame(svo_context* c, int slot, int stride, int gn, bool with_e
     else launch_triangulate(f, s);
     HIPCHK(record(EV_TRI));                                            // (fused: the stage timers count that chunk with the triangulation)
     launch_pnp(f, s, tri_epnp);
-    if (c->cov_mode) launch_pose_cov(f, CovArgs{c->d_cov + (size_t)slot * c->d.B, c->cov_mode, c->cov_sigma2}, s);   // into the pinned ring, like the record below
-    if (ids) launch_track_obs(f, c->ids, TrackObsArgs{c->d_obs + (size_t)slot * c->d.B * c->track_rows, c->d_obs_hdr + (size_t)slot * 2 * c->d.B, c->track_rows}, s);
-    if (ids && c->desc_on)             // every observation row's descriptor, on the T1 pyramid k_frame_end is about to rename
-        launch_track_desc(f, DescArgs{c->d_desc + (size_t)slot * c->d.B * c->track_rows * SVO_DESC_BYTES, c->track_rows}, s);
+    if (fs.cov_mode) launch_pose_cov(f, CovArgs{c->cov.dev_row(slot), fs.cov_mode, fs.cov_sigma2}, s);   // into the pinned ring, like the record below
+    if (ids) launch_track_obs(f, c->ids, TrackObsArgs{c->obs.dev_row(slot), c->obs_hdr.dev_row(slot), c->track_rows}, s);
+    if (fs.desc())                     // every observation row's descriptor, on the T1 pyramid k_frame_end is about to rename
+        launch_track_desc(f, DescArgs{c->desc.dev_row(slot), c->track_rows}, s);
     launch_frame_end(f, slot, s);      // writes the result records straight into the pinned host ring (d.results is host memory mapped into the device)
     c->last_path = path;
     return SVO_OK;
@@ -696,20 +761,20 @@ static const uint8_t* map_of(const svo_context* c, int seq, int cam) {
     return own ? own : c->shared_map[cam];
 }
 
-// The slot's rows of the pinned tables for one frame: image pointers, the active list and flags of a masked frame, the maps of a
+// The slot's rows of the pinned rings for one frame: image pointers, the active list and flags of a masked frame, the maps of a
 // rectifying context (free: the slot's previous frame has been collected).  *n_act = -1 for a frame every sequence takes — a mask
 // with every flag set is the unmasked frame — else the number of active sequences.
 static int fill_slot_rows(svo_context* c, int slot, const uint8_t* const* left_dev, const uint8_t* const* right_dev, const uint8_t* active, int* n_act) {
     const int B = c->d.B;
-    const uint8_t** hp = ring_row(c, c->h_ptrs, slot);
+    const uint8_t** hp = c->ptrs.row(slot);
     *n_act = -1;
     if (active) {
-        int* ha = ring_row(c, c->h_act, slot);
+        int* ha = c->act.row(slot);
         int n = 0;
         for (int i = 0; i < B; i++) { ha[B + i] = active[i] ? 1 : 0; if (active[i]) ha[n++] = i; }
         if (n < B) *n_act = n;
     }
-    const uint8_t** hm = c->raw_w > 0 ? ring_row(c, c->h_maps, slot) : nullptr;
+    const uint8_t** hm = c->raw_w > 0 ? c->maps.row(slot) : nullptr;
     for (int i = 0; i < B; i++) {
         const bool on = !active || active[i];
         hp[i] = on ? left_dev[i] : nullptr; hp[B + i] = on ? right_dev[i] : nullptr;
@@ -726,18 +791,18 @@ static int fill_slot_rows(svo_context* c, int slot, const uint8_t* const* left_d
 // in the stride, the LK grid and which builds of the f64 kernels run (a context captured while it had the device to itself would
 // keep the full-register builds that cannot start beside another many-sequence context's LK grid).  *replayed = false: the
 // capture failed and the option is now off — capture is an optimisation, the caller issues the same launches directly.
-static int replay_graph(svo_context* c, int slot, int stride, int gn, DeviceSharing share, bool* replayed) {
+static int replay_graph(svo_context* c, const FramePlan& p, bool* replayed) {
     hipStream_t s = c->stream;
-    RingSlot& r = c->ring[slot];
-    HIPCHK(choose_pnp_build(c->d, share.lean));                        // before the capture: issue_frame then finds the lean EPnP prepared
-    const GraphKey now = {stride, gn, c->d.co_resident, c->in_format, c->cov_mode, c->cov_sigma2};
+    RingSlot& r = c->ring[p.slot];
+    HIPCHK(choose_pnp_build(c->d, p.share.lean));                      // before the capture: issue_frame then finds the lean EPnP prepared
+    const GraphKey now = {r.fs, p.stride, p.gn, c->d.co_resident};
     if (!r.gexec || !(r.key == now)) {
         if (r.gexec) { (void)hipGraphExecDestroy(r.gexec); r.gexec = nullptr; }
         hipGraph_t g = nullptr;
         bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
         if (ok) {
             c->capturing = true;
-            const int rc = issue_frame(c, slot, stride, gn, false, share);
+            const int rc = issue_frame(c, p);
             c->capturing = false;
             ok = (hipStreamEndCapture(s, &g) == hipSuccess) && rc == SVO_OK && g;
         }
@@ -756,75 +821,84 @@ static int replay_graph(svo_context* c, int slot, int stride, int gn, DeviceShar
 
 // Detection masks of one frame.  The detection of this call scans each active sequence's PREVIOUS left image, so it applies the mask
 // recorded with that image (img_mask); the mask in force now — the sequence's own, else the shared one — is recorded with this
-// frame's left image for the next call.  Idle sequences keep their record.  *mrows: the frame's row of the device table (uploaded
+// frame's left image for the next call.  Idle sequences keep their record.  p->mrows: the frame's row of the device table (uploaded
 // here, on the frame's stream) when some active sequence's detection is masked, else null — the frame is then an unmasked one.
-static int take_masks(svo_context* c, int slot, const uint8_t* active, const uint8_t* const** mrows) {
-    *mrows = nullptr;
+static int take_masks(svo_context* c, const uint8_t* active, FramePlan* p) {
+    p->mrows = nullptr;
     if (c->img_mask.empty()) return SVO_OK;                           // no mask was ever set
     const int B = c->d.B;
-    const uint8_t** row = c->h_mask_rows + (size_t)slot * B;
+    const uint8_t** row = c->mask_rows.row(p->slot);
     bool any = false;
     for (int i = 0; i < B; i++) {
         const bool on = !active || active[i];
         row[i] = on ? c->img_mask[i] : nullptr;
         any |= row[i] != nullptr;
         if (!on) continue;
-        MaskPair& p = c->own_mask[i].cur >= 0 ? c->own_mask[i] : c->shared_mask;
-        c->img_mask[i] = p.cur >= 0 ? p.buf[p.cur] : nullptr;
-        if (p.cur >= 0) p.last = p.cur;
+        MaskPair& m = c->own_mask[i].cur >= 0 ? c->own_mask[i] : c->shared_mask;
+        c->img_mask[i] = m.cur >= 0 ? m.buf[m.cur] : nullptr;
+        if (m.cur >= 0) m.last = m.cur;
     }
     if (!any) return SVO_OK;
-    const uint8_t** drow = c->d_mask_rows + (size_t)slot * B;
-    HIPCHK(hipMemcpyAsync((void*)drow, (const void*)row, sizeof(uint8_t*) * (size_t)B, hipMemcpyHostToDevice, c->stream));
-    *mrows = drow;
+    HIPCHK(c->mask_rows.upload(p->slot, c->stream));
+    p->mrows = c->mask_rows.dev_row(p->slot);
     return SVO_OK;
 }
 
 // Motion priors of one frame: every active sequence with a pending prior hands it to this frame (one-shot: it is consumed here) —
-// idle sequences keep theirs.  *prow: the frame's device row, filled by one copy on the frame's stream from the slot's pinned row,
-// when some active sequence has one; else null, and the frame is an ordinary one.  In SVO_PRIOR_LAST_ROTATION the frame always has
-// its device row and k_prior_predict fills what no explicit prior filled: the copy is then made only when one was taken, and the
-// slot's list of the sequences that take the frame is written for that kernel.
-static int take_priors(svo_context* c, int slot, const uint8_t* active, FramePriors* pri) {
-    *pri = FramePriors();
-    const bool predict = c->prior_mode == SVO_PRIOR_LAST_ROTATION;
-    c->ring[slot].priors = false;
+// idle sequences keep theirs.  p->pri.rows: the frame's device row, filled by one upload on the frame's stream from the slot's pinned
+// row, when some active sequence has one; else null, and the frame is an ordinary one.  In SVO_PRIOR_LAST_ROTATION the frame always
+// has its device row and k_prior_predict fills what no explicit prior filled: the upload is then made only when one was taken, and
+// the slot's list of the sequences that take the frame is written for that kernel.
+static int take_priors(svo_context* c, const FrameSettings& fs, const uint8_t* active, FramePlan* p) {
+    p->pri = FramePriors();
+    const bool predict = fs.prior_mode == SVO_PRIOR_LAST_ROTATION;
     if (c->n_prior == 0 && !predict) return SVO_OK;
-    const int B = c->d.B;
-    PriorRow* row = c->h_prior + (size_t)slot * B;
+    const int B = c->d.B, slot = p->slot;
+    PriorRow* row = c->prior.row(slot);
     bool any = false;
     for (int i = 0; i < B; i++) {
-        PriorRow& p = c->prior_next[i];
-        const bool take = p.has && (!active || active[i]);
-        if (take) { row[i] = p; p.has = 0; c->n_prior--; any = true; }
+        PriorRow& q = c->prior_next[i];
+        const bool take = q.has && (!active || active[i]);
+        if (take) { row[i] = q; q.has = 0; c->n_prior--; any = true; }
         else { row[i].has = 0; row[i].source = 0; }
     }
     if (!any && !predict) return SVO_OK;
-    PriorRow* drow = c->d_prior + (size_t)slot * B;
-    if (any) HIPCHK(hipMemcpyAsync(drow, row, sizeof(PriorRow) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    if (any) HIPCHK(c->prior.upload(slot, c->stream));
     if (predict && active) {
-        int* list = c->h_prior_act + (size_t)slot * B;
+        int* list = c->prior_act.row(slot);
         for (int i = 0, n = 0; i < B; i++) if (active[i]) list[n++] = i;
     }
-    pri->rows = drow; pri->predict = predict; pri->uploaded = any;
-    c->ring[slot].priors = true;
+    p->pri.rows = c->prior.dev_row(slot); p->pri.predict = predict; p->pri.uploaded = any;
     return SVO_OK;
 }
 
-// The last collected frame's headers and rows out of the ring slot a new frame is about to write, into the context's own copy.
+// The last collected frame's large rows, wherever they are now: its slot of the rings, or the kept copies.
+struct LastRows { const int* hdr; const svo_track_obs* obs; const uint8_t* desc; size_t pitch; };   // pitch: rows per sequence
+static LastRows last_rows(const svo_context* c) {
+    const LastFrame& l = c->last;
+    if (l.obs_slot < 0) return {l.kept_hdr.data(), l.kept_obs.data(), l.kept_desc.data(), (size_t)l.obs_rows};
+    return {c->obs_hdr.row(l.obs_slot), c->obs.row(l.obs_slot), l.fs.desc() ? c->desc.row(l.obs_slot) : nullptr, (size_t)l.obs_rows};
+}
+// one sequence's rows of `elem` bytes each out of `src` (LastRows::obs or ::desc); returns how many were copied
+static int copy_last_rows(const LastRows& lr, const void* src, size_t elem, int seq, int cap, void* out, int* n_tracks) {
+    if (n_tracks) *n_tracks = lr.hdr[2 * seq];
+    const int n = lr.hdr[2 * seq + 1] < cap ? lr.hdr[2 * seq + 1] : cap;
+    if (n > 0) memcpy(out, (const uint8_t*)src + (size_t)seq * lr.pitch * elem, elem * (size_t)n);
+    return n;
+}
+// Those rows out of the ring slot that is about to be written again, into the context's own copies (LastFrame, second policy).
 static void keep_last_obs(svo_context* c) {
-    const size_t B = c->d.B, R = c->track_rows;
-    const int* hdr = c->h_obs_hdr + (size_t)c->last_obs_slot * 2 * B;
-    const svo_track_obs* rows = c->h_obs + (size_t)c->last_obs_slot * B * R;
-    c->kept_hdr.assign(hdr, hdr + 2 * B);
-    c->kept_obs.resize(B * R);
-    for (size_t i = 0; i < B; i++) memcpy(c->kept_obs.data() + i * R, rows + i * R, sizeof(svo_track_obs) * (size_t)hdr[2 * i + 1]);
-    if (c->last_desc_on) {                                           // that frame's descriptor rows lie in the same slot of their ring
-        const uint8_t* desc = c->h_desc + (size_t)c->last_obs_slot * B * R * SVO_DESC_BYTES;
-        c->kept_desc.resize(B * R * SVO_DESC_BYTES);
-        for (size_t i = 0; i < B; i++) memcpy(c->kept_desc.data() + i * R * SVO_DESC_BYTES, desc + i * R * SVO_DESC_BYTES, (size_t)SVO_DESC_BYTES * (size_t)hdr[2 * i + 1]);
+    LastFrame& l = c->last;
+    const LastRows lr = last_rows(c);
+    const size_t B = c->d.B, R = lr.pitch;
+    l.kept_hdr.assign(lr.hdr, lr.hdr + 2 * B);
+    l.kept_obs.resize(B * R);
+    if (lr.desc) l.kept_desc.resize(B * R * SVO_DESC_BYTES);
+    for (size_t i = 0; i < B; i++) {
+        copy_last_rows(lr, lr.obs, sizeof(svo_track_obs), (int)i, (int)R, l.kept_obs.data() + i * R, nullptr);
+        if (lr.desc) copy_last_rows(lr, lr.desc, SVO_DESC_BYTES, (int)i, (int)R, l.kept_desc.data() + i * R * SVO_DESC_BYTES, nullptr);
     }
-    c->last_obs_slot = -1;
+    l.obs_slot = -1;
 }
 
 // Enqueue one frame.  ptrs: host arrays of B DEVICE image pointers.  active: NULL (every sequence takes the frame) or B flags,
@@ -832,31 +906,31 @@ static void keep_last_obs(svo_context* c) {
 static int enqueue_frame(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
                          const uint8_t* active = nullptr) {
     if (c->inflight >= SVO_RING) { g_err = "too many frames in flight (collect first)"; return SVO_ERR_STATE; }
-    const int slot = c->head;
-    RingSlot& r = c->ring[slot];
-    int n_act, rc;
-    if ((rc = fill_slot_rows(c, slot, left_dev, right_dev, active, &n_act)) != SVO_OK) return rc;
+    RingSlot& r = c->ring[c->head];
+    FramePlan p;
+    p.slot = c->head; p.stride = stride; p.with_events = c->stage_timing;
+    int rc;
+    if ((rc = fill_slot_rows(c, p.slot, left_dev, right_dev, active, &p.n_act)) != SVO_OK) return rc;
     // LK grid sized from the last feature counts the host has seen (+30 %); the kernel strides, so an underestimate is only slower
     // (tests/test_gpu_count_seams.py, case D: 1025 features on the grid a hint of 20 gives, also in flight and re-captured)
-    int gn = c->lk_grid;
+    p.gn = c->lk_grid;
     if (c->lk_hint > 0) {
         int h = c->lk_hint + c->lk_hint / 3 + 64;
         if (c->use_graph) h = (h + 511) / 512 * 512;                 // coarse steps: the graph is re-captured when this changes
-        if (h < gn) gn = h;
+        if (h < p.gn) p.gn = h;
     }
-    const DeviceSharing share = device_sharing(c);                   // read once per frame: every use below sees the same answer
+    p.share = device_sharing(c);                                     // read once per frame: every use below sees the same answer
     HIPCHK(hipEventRecord(r.ev[EV_F0], c->stream));
-    const uint8_t* const* mrows = nullptr;
-    if ((rc = take_masks(c, slot, active, &mrows)) != SVO_OK) return rc;
-    FramePriors pri;
-    if ((rc = take_priors(c, slot, active, &pri)) != SVO_OK) return rc;
+    FrameSettings& fs = r.fs = c->next;                              // the frame's own record (the slot is free): a setter called from now on is the next frame's
+    fs.ragged = active != nullptr;
+    if ((rc = take_masks(c, active, &p)) != SVO_OK) return rc;
+    if ((rc = take_priors(c, fs, active, &p)) != SVO_OK) return rc;
+    fs.has_masks = p.mrows != nullptr; fs.has_priors = p.pri.rows != nullptr;
+    if (fs.track_on && p.slot == c->last.obs_slot) keep_last_obs(c);  // the frame is about to write the slot svo_get_last_track_obs still reads
     bool replayed = false;
-    if (c->track_on && slot == c->last_obs_slot) keep_last_obs(c);    // the frame is about to write the slot svo_get_last_track_obs still reads
-    if (c->use_graph && n_act < 0 && c->raw_w == 0 && !mrows && !c->clahe_on && !c->track_on && !pri.rows)   // a ragged, rectifying, masked, CLAHE, track-ids or motion-prior frame runs from the launch list
-        if ((rc = replay_graph(c, slot, stride, gn, share, &replayed)) != SVO_OK) return rc;
-    if (!replayed && (rc = issue_frame(c, slot, stride, gn, c->stage_timing, share, n_act, mrows, pri)) != SVO_OK) return rc;
+    if (graph_replayable(c, fs, p.n_act) && (rc = replay_graph(c, p, &replayed)) != SVO_OK) return rc;
+    if (!replayed && (rc = issue_frame(c, p)) != SVO_OK) return rc;
     r.staged = !replayed && c->stage_timing;
-    r.cov_mode = c->cov_mode; r.masked = active != nullptr; r.tracks = c->track_on; r.desc = c->track_on && c->desc_on;
     c->staged_inputs = false;
     HIPCHK(hipEventRecord(r.ev[EV_DONE], c->stream));
     HIPCHK(hipGetLastError());
@@ -868,46 +942,90 @@ static int collect_frame(svo_context* c, double* T_out, int* ok_out, svo_frame_s
     if (c->inflight <= 0) { g_err = "nothing to collect"; return SVO_ERR_STATE; }
     const int slot = c->tail, B = c->d.B;
     HIPCHK(hipEventSynchronize(c->ring[slot].ev[EV_DONE]));
-    const FrameResult* r = c->h_results + (size_t)slot * B;
+    const FrameResult* r = c->results.row(slot);
+    int mx = 0;
     for (int i = 0; i < B; i++) {
         if (T_out) memcpy(T_out + 16 * i, r[i].T, sizeof(double) * 16);
         if (ok_out) ok_out[i] = r[i].ok;
         if (stats) stats[i] = r[i].stats;
+        if (r[i].stats.n_after_detect > mx) mx = r[i].stats.n_after_detect;
     }
-    {
-        int mx = 0;
-        for (int i = 0; i < B; i++) if (r[i].stats.n_after_detect > mx) mx = r[i].stats.n_after_detect;
-        if (mx > 0) c->lk_hint = mx;
+    if (mx > 0) c->lk_hint = mx;
+    LastFrame& l = c->last;
+    const FrameSettings& fs = l.fs = c->ring[slot].fs;
+    if (fs.cov_mode) memcpy(l.cov.data(), c->cov.row(slot), sizeof(PoseCovRow) * B);
+    if (fs.has_priors) l.prior.assign(c->prior.row(slot), c->prior.row(slot) + B);   // the host's explicit rows, k_prior_predict's in place
+    l.obs_slot = fs.track_on ? slot : -1;                            // read in place
+    if (fs.track_on) l.obs_rows = c->track_rows;
+    const int* flags = c->act.row(slot) + B;
+    for (int i = 0; fs.ragged && i < B; i++) {                       // idle sequences took no launch: zero rows, zero headers (their prior rows say has = 0 already)
+        if (flags[i]) continue;
+        if (fs.cov_mode) memset(&l.cov[i], 0, sizeof(PoseCovRow));
+        if (fs.track_on) c->obs_hdr.row(slot)[2 * i] = c->obs_hdr.row(slot)[2 * i + 1] = 0;
     }
-    c->last_cov_mode = c->ring[slot].cov_mode;
-    if (c->last_cov_mode) {                                          // the slot's ring row; idle sequences took no launch: zero rows
-        memcpy(c->last_cov.data(), c->h_cov + (size_t)slot * B, sizeof(PoseCovRow) * B);
-        const int* flags = ring_row(c, c->h_act, slot) + B;
-        for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) memset(&c->last_cov[i], 0, sizeof(PoseCovRow));
-    }
-    c->last_tracks_on = c->ring[slot].tracks; c->last_desc_on = c->ring[slot].desc;
-    c->last_obs_slot = -1;
-    if (c->last_tracks_on) {                                         // read in place; idle sequences took no launch: zero headers
-        int* hdr = c->h_obs_hdr + (size_t)slot * 2 * B;
-        const int* flags = ring_row(c, c->h_act, slot) + B;
-        for (int i = 0; c->ring[slot].masked && i < B; i++) if (!flags[i]) hdr[2 * i] = hdr[2 * i + 1] = 0;
-        c->last_obs_slot = slot; c->last_obs_rows = c->track_rows;
-    }
-    c->last_prior.clear();
-    if (c->ring[slot].priors) {                                      // the slot's pinned row: the host's explicit rows, k_prior_predict's in place; idle sequences took none
-        const PriorRow* row = c->h_prior + (size_t)slot * B;
-        c->last_prior.assign(row, row + B);
-    }
-    c->last_slot = slot;
+    c->last.slot = slot;
     c->tail = (c->tail + 1) % SVO_RING; c->inflight--; c->n_collected++;
-    if (!c->retired.empty()) {                                       // maps no frame in flight can name any more
+    if (!c->retired.empty()) {                                       // buffers no frame in flight can name any more
         size_t k = 0;
-        for (const auto& r : c->retired) { if (r.after <= c->n_collected) (void)hipFree(r.p); else c->retired[k++] = r; }
+        for (const auto& q : c->retired) { if (q.after <= c->n_collected) (void)hipFree(q.p); else c->retired[k++] = q; }
         c->retired.resize(k);
     }
     return SVO_OK;
 }
 
+// Is p page-locked host memory the DMA engines can read in place (hipHostMalloc / hipHostRegister / svo_alloc_pinned)?
+static bool host_pointer_is_pinned(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // older runtimes: an error for pageable memory
+    return a.type == hipMemoryTypeHost;
+}
+// rows of rowb bytes, `stride` apart, packed: one memcpy when they already are
+static void pack_rows(uint8_t* dst, const uint8_t* src, size_t rowb, size_t rows, size_t stride) {
+    if (stride == rowb) memcpy(dst, src, rowb * rows);
+    else for (size_t y = 0; y < rows; y++) memcpy(dst + y * rowb, src + y * stride, rowb);
+}
+// Host images -> pinned staging -> device staging (one contiguous H2D copy); fills lp / rp with the device addresses.
+// Images that already live in page-locked memory with packed rows skip the staging copy: the DMA reads them in place (the call
+// is synchronous, the caller's buffer outlives it) — 40 us of host memcpy less per KITTI-sized pair on the single-stream path.
+// active (ragged frame): idle sequences' images are not read (their pointers may be NULL; their staging areas keep old bytes).
+static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
+                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active = nullptr) {
+    const int B = c->d.B, W = in_width(c), H = in_height(c);
+    const size_t rowb = (size_t)W * in_bpp(c), img = rowb * H;
+    if (c->staging_bytes < img * 2 * B) {                             // no frame in flight reads the staging buffers (synchronous calls only)
+        dev_free(c, c->staging); pinned_free(c, c->h_staging);
+        c->staging = nullptr; c->h_staging = nullptr; c->staging_bytes = 0;
+        if (const int rc = dev_alloc(c, &c->staging, img * 2 * B)) return rc;
+        if (const int rc = pinned_alloc(c, &c->h_staging, img * 2 * B)) return rc;
+        c->staging_bytes = img * 2 * B;
+    }
+    // rows are packed into pinned memory on the CPU (handles any stride), then contiguous async H2D copies (a 2-D copy from
+    // pageable memory degenerates into per-row transfers: 3.5 ms per 1241x376 image).  All left images first, so that their
+    // DMA runs while the CPU packs the right ones.
+    lp.resize(B); rp.resize(B);
+    c->staged_inputs = true;
+    for (int cam = 0; cam < 2; cam++) {
+        const uint8_t* const* src = cam ? right : left;
+        bool all_direct = (size_t)stride == rowb;
+        for (int i = 0; i < B && all_direct; i++) {
+            if (active && !active[i]) continue;
+            if (!src[i]) return fail_arg("null image pointer");
+            all_direct = host_pointer_is_pinned(src[i]);
+        }
+        for (int i = 0; i < B; i++) {
+            (cam ? rp : lp)[i] = c->staging + img * (cam * B + i);
+            if (active && !active[i]) continue;
+            if (!src[i]) return fail_arg("null image pointer");
+            if (all_direct) {
+                HIPCHK(hipMemcpyAsync(c->staging + img * (cam * B + i), src[i], img, hipMemcpyHostToDevice, c->stream));
+                continue;
+            }
+            pack_rows(c->h_staging + img * (cam * B + i), src[i], rowb, (size_t)H, (size_t)stride);
+        }
+        if (!all_direct) HIPCHK(hipMemcpyAsync(c->staging + img * B * cam, c->h_staging + img * B * cam, img * B, hipMemcpyHostToDevice, c->stream));
+    }
+    return SVO_OK;
+}
 extern "C" int svo_submit_batch_masked(svo_context* c, const uint8_t* const* left_dev, const uint8_t* const* right_dev, int stride,
                                        const uint8_t* active) {
     if (!c) return fail_arg("null context");
@@ -923,16 +1041,17 @@ extern "C" int svo_submit_batch(svo_context* c, const uint8_t* const* left_dev, 
 
 extern "C" int svo_reset_sequence(svo_context* c, int seq, const float Pl[12], const float Pr[12]) {
     if (!c) return fail_arg("null context");
-    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    int s0, s1;
+    if (const int rc = seq_range(c, seq, &s0, &s1)) return rc;
     if ((Pl == nullptr) != (Pr == nullptr)) return fail_arg("Pl and Pr must both be given or both be NULL");
     HIPCHK(hipSetDevice(c->device));
     SeqProjection p = {};
     if (Pl) { memcpy(p.Pl, Pl, sizeof(p.Pl)); memcpy(p.Pr, Pr, sizeof(p.Pr)); p.set = 1; }
     launch_reset_seq(c->d, seq, p, c->stream);                       // behind every frame submitted so far, before every later one
-    if (c->ids.next_id) launch_ids_reset(c->ids, seq < 0 ? 0 : seq, seq < 0 ? c->d.B : 1, c->stream);   // next_id = 0, stream-ordered like the rest
+    if (c->ids.next_id) launch_ids_reset(c->ids, s0, s1 - s0, c->stream);   // next_id = 0, stream-ordered like the rest
     HIPCHK(hipGetLastError());
     if (Pl && seq < 0) c->projection_set = true;
-    for (int i = seq < 0 ? 0 : seq; c->n_prior > 0 && i < (seq < 0 ? c->d.B : seq + 1); i++)   // a pending motion prior belonged to the stream that ends here
+    for (int i = s0; c->n_prior > 0 && i < s1; i++)   // a pending motion prior belonged to the stream that ends here
         if (c->prior_next[i].has) { c->prior_next[i].has = 0; c->n_prior--; }
     return SVO_OK;
 }
@@ -977,72 +1096,12 @@ extern "C" int svo_process(svo_context* c, const uint8_t* left, const uint8_t* r
     return rc != SVO_OK ? rc : ok;
 }
 
-// Is p page-locked host memory the DMA engines can read in place (hipHostMalloc / hipHostRegister / svo_alloc_pinned)?
-static bool host_pointer_is_pinned(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // older runtimes: an error for pageable memory
-    return a.type == hipMemoryTypeHost;
-}
-
 extern "C" void* svo_alloc_pinned(size_t bytes) {
     void* p = nullptr;
     if (hipHostMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     return p;
 }
 extern "C" void svo_free_pinned(void* p) { if (p) (void)hipHostFree(p); }
-
-// rows of rowb bytes, `stride` apart, packed: one memcpy when they already are
-static void pack_rows(uint8_t* dst, const uint8_t* src, size_t rowb, size_t rows, size_t stride) {
-    if (stride == rowb) memcpy(dst, src, rowb * rows);
-    else for (size_t y = 0; y < rows; y++) memcpy(dst + y * rowb, src + y * stride, rowb);
-}
-
-// Host images -> pinned staging -> device staging (one contiguous H2D copy); fills lp / rp with the device addresses.
-// Images that already live in page-locked memory with packed rows skip the staging copy: the DMA reads them in place (the call
-// is synchronous, the caller's buffer outlives it) — 40 us of host memcpy less per KITTI-sized pair on the single-stream path.
-// active (ragged frame): idle sequences' images are not read (their pointers may be NULL; their staging areas keep old bytes).
-static int stage_host_images(svo_context* c, const uint8_t* const* left, const uint8_t* const* right, int stride,
-                             std::vector<const uint8_t*>& lp, std::vector<const uint8_t*>& rp, const uint8_t* active) {
-    const int B = c->d.B, W = in_width(c), H = in_height(c);
-    const size_t rowb = (size_t)W * in_bpp(c), img = rowb * H;
-    if (c->staging_bytes < img * 2 * B) {                             // no frame in flight reads the staging buffers (synchronous calls only)
-        if (c->staging) { (void)hipFree(c->staging); c->staging = nullptr; }
-        if (c->h_staging) { (void)hipHostFree(c->h_staging); c->h_staging = nullptr; }
-        c->staging_bytes = 0;
-        HIPCHK(hipMalloc((void**)&c->staging, img * 2 * B));
-        HIPCHK(hipHostMalloc((void**)&c->h_staging, img * 2 * B));
-        c->staging_bytes = img * 2 * B;
-    }
-    // rows are packed into pinned memory on the CPU (handles any stride), then contiguous async H2D copies (a 2-D copy from
-    // pageable memory degenerates into per-row transfers: 3.5 ms per 1241x376 image).  All left images first, so that their
-    // DMA runs while the CPU packs the right ones.
-    lp.resize(B); rp.resize(B);
-    c->staged_inputs = true;
-    for (int cam = 0; cam < 2; cam++) {
-        const uint8_t* const* src = cam ? right : left;
-        bool all_direct = (size_t)stride == rowb;
-        for (int i = 0; i < B && all_direct; i++) {
-            if (active && !active[i]) continue;
-            if (!src[i]) return fail_arg("null image pointer");
-            all_direct = host_pointer_is_pinned(src[i]);
-        }
-        for (int i = 0; i < B; i++) {
-            (cam ? rp : lp)[i] = c->staging + img * (cam * B + i);
-            if (active && !active[i]) continue;
-            if (!src[i]) return fail_arg("null image pointer");
-            if (all_direct) {
-                HIPCHK(hipMemcpyAsync(c->staging + img * (cam * B + i), src[i], img, hipMemcpyHostToDevice, c->stream));
-                continue;
-            }
-            pack_rows(c->h_staging + img * (cam * B + i), src[i], rowb, (size_t)H, (size_t)stride);
-        }
-        if (!all_direct) HIPCHK(hipMemcpyAsync(c->staging + img * B * cam, c->h_staging + img * B * cam, img * B, hipMemcpyHostToDevice, c->stream));
-    }
-    return SVO_OK;
-}
-
-static int read_state(svo_context* c, int seq, SeqState* hs);
-static int set_state(svo_context* c, const SeqState& hs);
 
 // ---- motion priors (svo.h): the host arithmetic, the buffers, the setters ----
 // One prior as the kernels take it (svo_prior.hpp has the arithmetic): H checked, Hi the caller's or H's inverse rounded to f32.
@@ -1057,28 +1116,15 @@ static int check_prior_context(const svo_context* c) {
     if (c->d.cfg.lk_float_sums) return fail_arg("motion priors need lk_float_sums == 0 (that mode reproduces the reference's recording, which has no prior)");
     return SVO_OK;
 }
-// the pinned ring and its device copy, at first use
+// the prior ring and the list ring of the predicting frames, at first use
 static int prior_buffers(svo_context* c) {
-    if (c->d_prior) return SVO_OK;
+    if (c->prior.h) return SVO_OK;
     HIPCHK(hipSetDevice(c->device));
-    const size_t bytes = sizeof(PriorRow) * SVO_RING * (size_t)c->d.B, act_bytes = sizeof(int) * SVO_RING * (size_t)c->d.B;
-    PriorRow *h = nullptr, *dv = nullptr;
-    int* ha = nullptr;
-    void *hd = nullptr, *had = nullptr;
-    bool ok = hipHostMalloc((void**)&h, bytes, hipHostMallocMapped) == hipSuccess && hipHostMalloc((void**)&ha, act_bytes, hipHostMallocMapped) == hipSuccess &&
-              hipHostGetDevicePointer(&hd, h, 0) == hipSuccess && hipHostGetDevicePointer(&had, ha, 0) == hipSuccess &&
-              hipMalloc((void**)&dv, bytes) == hipSuccess;
-    ok = ok && hipMemsetAsync(dv, 0, bytes, c->stream) == hipSuccess;  // on the frames' stream: before any frame that names the rows
-    if (!ok) {
-        (void)hipGetLastError();
-        if (h) (void)hipHostFree(h);
-        if (ha) (void)hipHostFree(ha);
-        if (dv) (void)hipFree(dv);
-        g_err = "motion prior: buffer allocation failed"; return SVO_ERR_HIP;
+    const size_t B = (size_t)c->d.B;
+    if (rings_alloc(c, {ring_spec(c->prior, B, RING_MAPPED | RING_UPLOADED), ring_spec(c->prior_act, B, RING_MAPPED)}) != hipSuccess) {
+        (void)hipGetLastError(); g_err = "motion prior: buffer allocation failed"; return SVO_ERR_HIP;
     }
-    memset(h, 0, bytes); memset(ha, 0, act_bytes);
-    c->h_prior = h; c->d_prior = dv; c->hd_prior = (PriorRow*)hd; c->h_prior_act = ha; c->hd_prior_act = (int*)had;
-    c->prior_next.assign((size_t)c->d.B, PriorRow{});
+    c->prior_next.assign(B, PriorRow{});
     return SVO_OK;
 }
 static void set_pending(svo_context* c, int seq, const PriorRow* row /* null: clear */) {
@@ -1090,10 +1136,10 @@ static void set_pending(svo_context* c, int seq, const PriorRow* row /* null: cl
 extern "C" int svo_set_motion_prior(svo_context* c, int seq, const float H[9], const float Hi[9]) {
     if (!c) return fail_arg("null context");
     int rc = check_prior_context(c); if (rc != SVO_OK) return rc;
-    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
-    const int s0 = seq < 0 ? 0 : seq, s1 = seq < 0 ? c->d.B : seq + 1;
+    int s0, s1;
+    if ((rc = seq_range(c, seq, &s0, &s1)) != SVO_OK) return rc;
     if (!H) {                                                                     // clear: nothing to do before the first prior
-        for (int i = s0; c->d_prior && i < s1; i++) set_pending(c, i, nullptr);
+        for (int i = s0; c->prior.h && i < s1; i++) set_pending(c, i, nullptr);
         return SVO_OK;
     }
     PriorRow row;
@@ -1129,22 +1175,22 @@ extern "C" int svo_set_motion_prior_mode(svo_context* c, int mode) {
     if (mode != SVO_PRIOR_EXPLICIT && mode != SVO_PRIOR_LAST_ROTATION) return fail_arg("unknown motion prior mode");
     int rc = check_prior_context(c); if (rc != SVO_OK) return rc;
     if (mode == SVO_PRIOR_LAST_ROTATION && (rc = prior_buffers(c)) != SVO_OK) return rc;
-    c->prior_mode = mode;                                                         // host state: the frames submitted from now on
+    c->next.prior_mode = mode;
     return SVO_OK;
 }
 
 extern "C" int svo_get_motion_prior_mode(svo_context* c, int* mode) {
     if (!c || !mode) return fail_arg("null argument");
-    *mode = c->prior_mode;
+    *mode = c->next.prior_mode;
     return SVO_OK;
 }
 
 extern "C" int svo_get_last_motion_prior(svo_context* c, int seq, float H[9], float Hi[9], int* source) {
     if (!c || !source || seq < 0 || seq >= c->d.B) return fail_arg("bad context / seq / null source");
-    if (c->last_slot < 0) { g_err = "svo_get_last_motion_prior: no frame collected yet"; return SVO_ERR_STATE; }
+    if (c->last.slot < 0) { g_err = "svo_get_last_motion_prior: no frame collected yet"; return SVO_ERR_STATE; }
     *source = 0;
-    if (c->last_prior.empty() || !c->last_prior[seq].has) return SVO_OK;         // the frame had no prior rows, or none for seq
-    const PriorRow& p = c->last_prior[seq];
+    if (!c->last.fs.has_priors || !c->last.prior[seq].has) return SVO_OK;        // the frame had no prior rows, or none for seq
+    const PriorRow& p = c->last.prior[seq];
     *source = p.source == PRIOR_SOURCE_PREDICTED ? 2 : 1;
     if (H) memcpy(H, p.H, sizeof(float) * 9);
     if (Hi) memcpy(Hi, p.Hi, sizeof(float) * 9);
@@ -1185,7 +1231,7 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     if (c->d.B != 1) return fail_arg("svo_circular_matching needs a context created with n_seq == 1");
     int rc = check_stride(c, stride); if (rc != SVO_OK) return rc;
     if (c->inflight != 0) { g_err = "svo_circular_matching with frames in flight"; return SVO_ERR_STATE; }
-    if (c->track_on) { g_err = "svo_circular_matching with the track output on: it overwrites the feature set behind the ids (svo_set_track_output(ctx, 0, 0) first)"; return SVO_ERR_STATE; }
+    if (c->next.track_on) { g_err = "svo_circular_matching with the track output on: it overwrites the feature set behind the ids (svo_set_track_output(ctx, 0, 0) first)"; return SVO_ERR_STATE; }
     if (c->n_prior > 0) { g_err = "svo_circular_matching with a motion prior pending: priors belong to the frame pipeline (svo_set_motion_prior(ctx, -1, NULL, NULL) clears them; svo_circular_match_prior is the stage call)"; return SVO_ERR_STATE; }
     if (n == 0) return SVO_OK;                                                    // vo.cpp:179-181
     if (n > c->d.CAP) { g_err = "more points than the context's feature capacity"; return SVO_ERR_CAPACITY; }
@@ -1207,17 +1253,18 @@ extern "C" int svo_circular_matching(svo_context* c, const uint8_t* left_t1, con
     std::vector<const uint8_t*> lp, rp;
     const uint8_t* l[1] = {left_t1}; const uint8_t* r[1] = {right_t1};
     if ((rc = stage_host_images(c, l, r, stride, lp, rp)) != SVO_OK) return rc;
-    const uint8_t** hp = ring_row(c, c->h_ptrs, 0);                               // no frame in flight: ring slot 0's rows are free
+    const uint8_t** hp = c->ptrs.row(0);                                          // no frame in flight: ring slot 0's rows and record are free
     hp[0] = lp[0]; hp[1] = rp[0];
+    const FrameSettings& fs = c->ring[0].fs = c->next;
     if (c->raw_w > 0) {
-        const uint8_t** hm = ring_row(c, c->h_maps, 0);
+        const uint8_t** hm = c->maps.row(0);
         for (int cam = 0; cam < 2; cam++) hm[cam] = map_of(c, 0, cam);
         if (!hm[0] || !hm[1]) { g_err = "rectifying context without rectification maps"; return SVO_ERR_STATE; }
     }
     DevBuffers f = frame_view(c, 0, -1);
-    const uint8_t* const* srcs = ring_row(c, f.img_ptrs, 0);
+    const uint8_t* const* srcs = c->ptrs.dev_row(0);
     int packed = in_width(c) * in_bpp(c);
-    if (c->clahe_on && (rc = clahe_front(c, f, srcs, packed, c->stream)) != SVO_OK) return rc;
+    if (fs.clahe_on && (rc = clahe_front(c, fs, f, srcs, packed, c->stream)) != SVO_OK) return rc;
     launch_ingest_pyramid(f, srcs, packed, c->stream, PYR_T1);                                            // vo.cpp:200-201
     if ((rc = circular_tail(c, n, pl1, pr1, pr0, pl0_circle, ok)) != SVO_OK) return rc;
     SeqState out = keep;
@@ -1234,9 +1281,9 @@ extern "C" int svo_set_stage_timing(svo_context* c, int on) {
 }
 
 extern "C" int svo_get_last_timing(svo_context* c, float* lk_ms, float* frame_ms) {
-    if (!c || c->last_slot < 0) return fail_arg("no frame collected yet");
+    if (!c || c->last.slot < 0) return fail_arg("no frame collected yet");
     HIPCHK(hipSetDevice(c->device));
-    const RingSlot& r = c->ring[c->last_slot];
+    const RingSlot& r = c->ring[c->last.slot];
     if (lk_ms) {
         if (!r.staged) { g_err = "no stage events for this frame: call svo_set_stage_timing(ctx, 1) first (and SVO_GRAPH must be off)"; return SVO_ERR_STATE; }
         HIPCHK(hipEventElapsedTime(lk_ms, r.ev[EV_LK0], r.ev[EV_LK1]));
@@ -1246,18 +1293,11 @@ extern "C" int svo_get_last_timing(svo_context* c, float* lk_ms, float* frame_ms
 }
 
 extern "C" int svo_get_stage_timing(svo_context* c, float ms[5]) {
-    if (!c || !ms || c->last_slot < 0) return fail_arg("no frame collected yet");
+    if (!c || !ms || c->last.slot < 0) return fail_arg("no frame collected yet");
     HIPCHK(hipSetDevice(c->device));
-    const RingSlot& r = c->ring[c->last_slot];
+    const RingSlot& r = c->ring[c->last.slot];
     if (!r.staged) { g_err = "no stage events for this frame: call svo_set_stage_timing(ctx, 1) first (and SVO_GRAPH must be off)"; return SVO_ERR_STATE; }
     for (int i = 0; i + 1 < EV_COUNT; i++) HIPCHK(hipEventElapsedTime(&ms[i], r.ev[i], r.ev[i + 1]));
-    return SVO_OK;
-}
-
-static int read_state(svo_context* c, int seq, SeqState* hs) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(hs, c->d.st + seq, sizeof(SeqState), hipMemcpyDeviceToHost));
     return SVO_OK;
 }
 
@@ -1293,18 +1333,12 @@ extern "C" int svo_get_last_tracks(svo_context* c, int seq, int cap, float* pl0,
 // the descriptor ring at the track output's max_rows: allocated at first use, re-allocated when max_rows has changed.  The caller
 // has kept the last collected frame's rows (keep_last_obs) if the old ring still held them, and no frame is in flight.
 static int desc_ring(svo_context* c) {
-    if (c->h_desc && c->desc_rows == c->track_rows) return SVO_OK;
+    const size_t pitch = (size_t)c->d.B * c->track_rows * SVO_DESC_BYTES;
+    if (c->desc.pitch == pitch) return SVO_OK;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->h_desc) (void)hipHostFree(c->h_desc);
-    c->h_desc = nullptr; c->d_desc = nullptr; c->desc_rows = 0;
-    const size_t bytes = (size_t)SVO_RING * c->d.B * (size_t)c->track_rows * SVO_DESC_BYTES;
-    uint8_t* h = nullptr; void* dv = nullptr;
-    HIPCHK(hipHostMalloc((void**)&h, bytes, hipHostMallocMapped));
-    memset(h, 0, bytes);
-    const hipError_t e = hipHostGetDevicePointer(&dv, (void*)h, 0);
-    if (e != hipSuccess || !dv) { (void)hipHostFree(h); HIPCHK(e != hipSuccess ? e : hipErrorInvalidDevicePointer); }   // both addresses or no ring
-    c->h_desc = h; c->d_desc = (uint8_t*)dv; c->desc_rows = c->track_rows;
+    ring_free(c, c->desc);
+    HIPCHK(rings_alloc(c, {ring_spec(c->desc, pitch, RING_MAPPED)}));
     return SVO_OK;
 }
 
@@ -1312,79 +1346,60 @@ static int desc_ring(svo_context* c) {
 extern "C" int svo_set_track_output(svo_context* c, int on, int max_rows) {
     if (!c) return fail_arg("null context");
     if (c->inflight != 0) { g_err = "svo_set_track_output with frames in flight: switching is a setup action (collect first)"; return SVO_ERR_STATE; }
-    if (!on) { c->track_on = false; c->desc_on = false; return SVO_OK; }   // the descriptors ride on the track output
+    if (!on) { c->next.track_on = false; c->next.desc_on = false; return SVO_OK; }   // the descriptors ride on the track output
     if (c->d.cfg.features_per_bucket > 1) return fail_arg("track ids need features_per_bucket == 1 (the general bucket walk carries no ids)");
     if (max_rows < 1 || max_rows > c->d.CAP) return fail_arg("max_rows must be 1 .. the context's feature capacity");
     HIPCHK(hipSetDevice(c->device));
     const size_t B = c->d.B, CAP = c->d.CAP;
-    if (!c->ids.next_id) {
+    if (!c->ids.next_id) {                                           // allocated last: next_id marks the set complete
         int rc;
         if ((rc = dev_alloc(c, &c->ids.feat_id[0], B * CAP)) != SVO_OK || (rc = dev_alloc(c, &c->ids.feat_id[1], B * CAP)) != SVO_OK ||
-            (rc = dev_alloc(c, &c->ids.track_id, B * CAP)) != SVO_OK) return rc;
-        if ((rc = dev_alloc(c, &c->ids.next_id, B)) != SVO_OK) { c->ids.next_id = nullptr; return rc; }   // next_id marks the set complete
+            (rc = dev_alloc(c, &c->ids.track_id, B * CAP)) != SVO_OK || (rc = dev_alloc(c, &c->ids.next_id, B)) != SVO_OK) return rc;
     }
-    if (!c->h_obs || c->track_rows != max_rows) {
-        if (c->last_obs_slot >= 0) keep_last_obs(c);                 // the last collected frame's rows outlive the ring they were in
+    if (!c->obs.h || c->track_rows != max_rows) {
+        if (c->last.obs_slot >= 0) keep_last_obs(c);                 // the last collected frame's rows outlive the ring they were in
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (void* p : {(void*)c->h_obs, (void*)c->h_obs_hdr}) if (p) (void)hipHostFree(p);
-        c->h_obs = nullptr; c->h_obs_hdr = nullptr; c->track_rows = 0;
-        const size_t rows = (size_t)SVO_RING * B * (size_t)max_rows;
-        HIPCHK(hipHostMalloc((void**)&c->h_obs, sizeof(svo_track_obs) * rows, hipHostMallocMapped));
-        HIPCHK(hipHostMalloc((void**)&c->h_obs_hdr, sizeof(int) * 2 * SVO_RING * B, hipHostMallocMapped));
-        memset(c->h_obs_hdr, 0, sizeof(int) * 2 * SVO_RING * B);
-        HIPCHK(hipHostGetDevicePointer((void**)&c->d_obs, c->h_obs, 0));
-        HIPCHK(hipHostGetDevicePointer((void**)&c->d_obs_hdr, c->h_obs_hdr, 0));
+        ring_free(c, c->obs); ring_free(c, c->obs_hdr); c->track_rows = 0;
+        HIPCHK(rings_alloc(c, {ring_spec(c->obs, B * (size_t)max_rows, RING_MAPPED), ring_spec(c->obs_hdr, 2 * B, RING_MAPPED)}));
         c->track_rows = max_rows;
-        if (c->desc_on) if (const int rc = desc_ring(c)) { c->desc_on = false; return rc; }   // the descriptor ring follows max_rows
+        if (c->next.desc_on) if (const int rc = desc_ring(c)) { c->next.desc_on = false; return rc; }   // the descriptor ring follows max_rows
     }
-    if (!c->track_on) launch_ids_assign(c->d, c->ids, c->stream);     // the features held now: next_id + index
+    if (!c->next.track_on) launch_ids_assign(c->d, c->ids, c->stream);     // the features held now: next_id + index
     HIPCHK(hipGetLastError());
-    c->track_on = true;
+    c->next.track_on = true;
     return SVO_OK;
 }
 
 extern "C" int svo_get_last_track_obs(svo_context* c, int seq, int cap, svo_track_obs* rows, int* n_tracks) {
     if (!c || seq < 0 || seq >= c->d.B || cap < 0 || (cap > 0 && !rows)) return fail_arg("bad context / seq / cap / rows");
-    if (c->last_slot < 0 || !c->last_tracks_on) { g_err = "the last collected frame was issued with the track output off (or none was collected yet)"; return SVO_ERR_STATE; }
-    const size_t B = c->d.B, R = c->last_obs_rows;
-    const bool ring = c->last_obs_slot >= 0;
-    const int* hdr = ring ? c->h_obs_hdr + (size_t)c->last_obs_slot * 2 * B : c->kept_hdr.data();
-    const svo_track_obs* src = ring ? c->h_obs + (size_t)c->last_obs_slot * B * R : c->kept_obs.data();
-    if (n_tracks) *n_tracks = hdr[2 * seq];
-    const int n = hdr[2 * seq + 1] < cap ? hdr[2 * seq + 1] : cap;
-    if (n > 0) memcpy(rows, src + (size_t)seq * R, sizeof(svo_track_obs) * (size_t)n);
-    return n;
+    if (c->last.slot < 0 || !c->last.fs.track_on) { g_err = "the last collected frame was issued with the track output off (or none was collected yet)"; return SVO_ERR_STATE; }
+    const LastRows lr = last_rows(c);
+    return copy_last_rows(lr, lr.obs, sizeof(svo_track_obs), seq, cap, rows, n_tracks);
 }
 
 // ---- binary descriptors (svo.h) ----
 extern "C" int svo_set_descriptor_output(svo_context* c, int on) {
     if (!c) return fail_arg("null context");
     if (c->inflight != 0) { g_err = "svo_set_descriptor_output with frames in flight: switching is a setup action (collect first)"; return SVO_ERR_STATE; }
-    if (!on) { c->desc_on = false; return SVO_OK; }
+    if (!on) { c->next.desc_on = false; return SVO_OK; }
     if (c->d.CN != 1) return fail_arg("svo_set_descriptor_output: descriptors are defined on a grey image (channels = 1 contexts only)");
     if (c->d.geom.W < 16 || c->d.geom.H < 16) return fail_arg("svo_set_descriptor_output: the image must be at least 16 x 16");
-    if (!c->track_on) { g_err = "svo_set_descriptor_output with the track output off: a descriptor row describes an observation row (svo_set_track_output first)"; return SVO_ERR_STATE; }
+    if (!c->next.track_on) { g_err = "svo_set_descriptor_output with the track output off: a descriptor row describes an observation row (svo_set_track_output first)"; return SVO_ERR_STATE; }
     if (const int rc = desc_ring(c)) return rc;
-    c->desc_on = true;                                               // host state: the next frame issued carries it
+    c->next.desc_on = true;
     return SVO_OK;
 }
 
 extern "C" int svo_get_last_track_descriptors(svo_context* c, int seq, int cap, uint8_t* desc, int* n_tracks) {
     if (!c || seq < 0 || seq >= c->d.B || cap < 0 || (cap > 0 && !desc)) return fail_arg("bad context / seq / cap / desc");
-    if (c->last_slot < 0 || !c->last_tracks_on || !c->last_desc_on) { g_err = "the last collected frame was issued with the descriptor output off (or none was collected yet)"; return SVO_ERR_STATE; }
-    const size_t B = c->d.B, R = c->last_obs_rows;
-    const bool ring = c->last_obs_slot >= 0;
-    const int* hdr = ring ? c->h_obs_hdr + (size_t)c->last_obs_slot * 2 * B : c->kept_hdr.data();
-    const uint8_t* src = ring ? c->h_desc + (size_t)c->last_obs_slot * B * R * SVO_DESC_BYTES : c->kept_desc.data();
-    if (n_tracks) *n_tracks = hdr[2 * seq];
-    const int n = hdr[2 * seq + 1] < cap ? hdr[2 * seq + 1] : cap;
-    if (n > 0) memcpy(desc, src + (size_t)seq * R * SVO_DESC_BYTES, (size_t)SVO_DESC_BYTES * (size_t)n);
-    return n;
+    if (c->last.slot < 0 || !c->last.fs.desc()) { g_err = "the last collected frame was issued with the descriptor output off (or none was collected yet)"; return SVO_ERR_STATE; }
+    const LastRows lr = last_rows(c);
+    return copy_last_rows(lr, lr.desc, SVO_DESC_BYTES, seq, cap, desc, n_tracks);
 }
 
 extern "C" int svo_get_feature_ids(svo_context* c, int seq, int cap, int64_t* ids) {
     if (!c || seq < 0 || seq >= c->d.B || cap < 0) return fail_arg("bad context / seq / cap");
-    if (!c->track_on) { g_err = "svo_get_feature_ids with the track output off"; return SVO_ERR_STATE; }
+    if (!c->next.track_on) { g_err = "svo_get_feature_ids with the track output off"; return SVO_ERR_STATE; }
     SeqState hs; int rc = read_state(c, seq, &hs); if (rc != SVO_OK) return rc;
     const int n = hs.n_feat < cap ? hs.n_feat : cap;
     static_assert(sizeof(long long) == sizeof(int64_t), "ids are 64-bit");
@@ -1577,17 +1592,12 @@ extern "C" int svo_stage_cache_clear_all(void) {                    // every cac
 // (slot, camera), so the copies of one call never overwrite each other before they have run.
 static int upload_image(svo_context* c, int slot, int cam, const uint8_t* img, int stride) {
     const size_t W = c->d.geom.W, H = c->d.geom.H;
-    if (!c->h_upload) HIPCHK(hipHostMalloc((void**)&c->h_upload, W * H * 6));
+    if (!c->h_upload) if (const int rc = pinned_alloc(c, &c->h_upload, W * H * 6)) return rc;
     uint8_t* h = c->h_upload + W * H * (size_t)(slot * 2 + cam);
     pack_rows(h, img, W, H, (size_t)stride);
     const LevelInfo& L0 = c->d.geom.lv[0];
     uint8_t* dst = c->d.pyr + pyr_index(c->d, 0, slot, cam) + L0.off;
     HIPCHK(hipMemcpy2DAsync(dst, (size_t)L0.stride, h, W, W, H, hipMemcpyHostToDevice, c->stream));   // from pinned memory: one strided DMA
-    return SVO_OK;
-}
-static int set_state(svo_context* c, const SeqState& hs) {
-    HIPCHK(hipMemcpyAsync(c->d.st, &hs, sizeof(SeqState), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));      // hs is a stack object
     return SVO_OK;
 }
 static int build_pyramid_in_slot(svo_context* c, SeqState& hs, int slot) {
@@ -1797,9 +1807,9 @@ static int circular_match_stage(int device, const svo_config* cfg_in, const uint
     const PriorRow* drow = nullptr;
     if (prior) {                                                                  // the context's first rows: nothing of it is in flight
         if ((rc = prior_buffers(c)) != SVO_OK) return rc;
-        c->h_prior[0] = *prior;
-        HIPCHK(hipMemcpyAsync(c->d_prior, c->h_prior, sizeof(PriorRow), hipMemcpyHostToDevice, c->stream));
-        drow = c->d_prior;
+        c->prior.row(0)[0] = *prior;
+        HIPCHK(c->prior.upload(0, c->stream));
+        drow = c->prior.dev_row(0);
     }
     if ((rc = upload_image(c, 0, 0, l0, stride)) != SVO_OK) return rc;
     if ((rc = upload_image(c, 0, 1, r0, stride)) != SVO_OK) return rc;
@@ -1965,11 +1975,6 @@ extern "C" int svo_init_rectify_map(const double K[9], const double* D, int n_d,
     return SVO_OK;
 }
 
-static void retire_map(svo_context* c, uint8_t* p) {
-    if (!p) return;
-    if (c->inflight == 0) (void)hipFree(p);                                       // every frame that could name it has been collected
-    else c->retired.push_back({p, c->n_enqueued});
-}
 static int upload_map(svo_context* c, const int16_t* m1, const uint16_t* m2, uint8_t** out) {
     const size_t n = (size_t)c->d.geom.W * c->d.geom.H;
     uint8_t* p = nullptr;
@@ -1986,7 +1991,7 @@ static int upload_map(svo_context* c, const int16_t* m1, const uint16_t* m2, uin
 extern "C" int svo_set_rectification_maps(svo_context* c, int seq, int raw_w, int raw_h, const int16_t* map1_l, const uint16_t* map2_l,
                                           const int16_t* map1_r, const uint16_t* map2_r) {
     if (!c) return fail_arg("null context");
-    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if (const int rc = seq_range(c, seq)) return rc;
     if (!map1_l || !map2_l || !map1_r || !map2_r) return fail_arg("null map");
     if (raw_w < 1 || raw_h < 1 || raw_w > 32767 || raw_h > 32767) return fail_arg("raw size must be 1 .. 32767");
     if (c->raw_w > 0 && (raw_w != c->raw_w || raw_h != c->raw_h)) return fail_arg("raw size differs from the one this context rectifies (svo_clear_rectification first)");
@@ -1997,7 +2002,7 @@ extern "C" int svo_set_rectification_maps(svo_context* c, int seq, int raw_w, in
     if (rc != SVO_OK) { if (m[0]) (void)hipFree(m[0]); return rc; }
     for (int cam = 0; cam < 2; cam++) {
         uint8_t*& slot = seq < 0 ? c->shared_map[cam] : c->own_map[2 * seq + cam];
-        retire_map(c, slot);
+        retire(c, slot);
         slot = m[cam];
     }
     c->raw_w = c->d.raw_w = raw_w; c->raw_h = c->d.raw_h = raw_h;
@@ -2021,8 +2026,8 @@ extern "C" int svo_set_rectification(svo_context* c, int seq, const svo_camera_i
 extern "C" int svo_clear_rectification(svo_context* c) {
     if (!c) return fail_arg("null context");
     HIPCHK(hipSetDevice(c->device));
-    for (int cam = 0; cam < 2; cam++) { retire_map(c, c->shared_map[cam]); c->shared_map[cam] = nullptr; }
-    for (uint8_t*& p : c->own_map) { retire_map(c, p); p = nullptr; }
+    for (int cam = 0; cam < 2; cam++) { retire(c, c->shared_map[cam]); c->shared_map[cam] = nullptr; }
+    for (uint8_t*& p : c->own_map) { retire(c, p); p = nullptr; }
     c->raw_w = c->raw_h = c->d.raw_w = c->d.raw_h = 0;
     return SVO_OK;
 }
@@ -2066,7 +2071,7 @@ extern "C" int svo_set_input_format(svo_context* c, int format) {
     if (c->d.CN != 1) return fail_arg("svo_set_input_format: a channels = 3 context takes interleaved BGR as it is (svo.h, channels)");
     GreyIn g;
     if (!grey_in_of(format, &g)) return fail_arg("svo_set_input_format: unknown format (SVO_INPUT_*)");
-    c->in_format = format; c->in = g;                                 // host state: the next frame issued launches this format's kernels
+    c->next.in_format = format; c->next.in = g;
     return SVO_OK;
 }
 
@@ -2076,11 +2081,11 @@ extern "C" int svo_set_input_format(svo_context* c, int format) {
 extern "C" int svo_set_clahe(svo_context* c, int on, double clip_limit, int tiles_x, int tiles_y) {
     if (!c) return fail_arg("null context");
     if (c->d.CN != 1) return fail_arg("svo_set_clahe: a channels = 3 context takes interleaved BGR as it is (svo.h, channels)");
-    if (!on) { c->clahe_on = false; return SVO_OK; }
+    if (!on) { c->next.clahe_on = false; return SVO_OK; }
     if (const int rc = check_clahe_params(clip_limit, tiles_x, tiles_y)) return rc;
     int tw, th;
     if (!clahe_geometry(in_width(c), in_height(c), tiles_x, tiles_y, &tw, &th)) return fail_arg("svo_set_clahe: the tiles do not fit the context's input size (svo.h, CLAHE rule 1)");
-    c->clahe_on = true; c->clahe_clip = clip_limit; c->clahe_tx = tiles_x; c->clahe_ty = tiles_y;   // host state: the next frame issued carries it
+    c->next.clahe_on = true; c->next.clahe_clip = clip_limit; c->next.clahe_tx = tiles_x; c->next.clahe_ty = tiles_y;
     return SVO_OK;
 }
 
@@ -2121,27 +2126,21 @@ static int check_cov_mode(int mode, double pixel_sigma, bool off_allowed) {
 extern "C" int svo_set_pose_covariance(svo_context* c, int mode, double pixel_sigma) {
     if (!c) return fail_arg("null context");
     if (const int rc = check_cov_mode(mode, pixel_sigma, true)) return rc;
-    if (mode != SVO_COV_OFF && !c->h_cov) {
-        const size_t rows = (size_t)SVO_RING * c->d.B;
+    if (mode != SVO_COV_OFF && !c->cov.h) {
         HIPCHK(hipSetDevice(c->device));
-        PoseCovRow* h = nullptr; void* dv = nullptr;
-        HIPCHK(hipHostMalloc((void**)&h, sizeof(PoseCovRow) * rows, hipHostMallocMapped));
-        memset(h, 0, sizeof(PoseCovRow) * rows);
-        const hipError_t e = hipHostGetDevicePointer(&dv, (void*)h, 0);
-        if (e != hipSuccess || !dv) { (void)hipHostFree(h); HIPCHK(e != hipSuccess ? e : hipErrorInvalidDevicePointer); }   // the ring exists with both addresses or not at all
-        c->h_cov = h; c->d_cov = (PoseCovRow*)dv;
-        c->last_cov.assign((size_t)c->d.B, PoseCovRow{});
+        HIPCHK(rings_alloc(c, {ring_spec(c->cov, (size_t)c->d.B, RING_MAPPED)}));
+        c->last.cov.assign((size_t)c->d.B, PoseCovRow{});
     }
-    c->cov_mode = mode;                                              // host state: the next frame issued carries it
-    if (mode == SVO_COV_FIXED_SIGMA) c->cov_sigma2 = pixel_sigma * pixel_sigma;
+    c->next.cov_mode = mode;
+    if (mode == SVO_COV_FIXED_SIGMA) c->next.cov_sigma2 = pixel_sigma * pixel_sigma;
     return SVO_OK;
 }
 
 extern "C" int svo_get_last_pose_covariance(svo_context* c, double* cov_T, double* cov_p, int* valid) {
     if (!c) return fail_arg("null context");
-    if (c->last_slot < 0 || c->last_cov_mode == SVO_COV_OFF) { g_err = "no covariance: the last collected frame was issued with SVO_COV_OFF, or none was collected"; return SVO_ERR_STATE; }
+    if (c->last.slot < 0 || c->last.fs.cov_mode == SVO_COV_OFF) { g_err = "no covariance: the last collected frame was issued with SVO_COV_OFF, or none was collected"; return SVO_ERR_STATE; }
     for (int i = 0; i < c->d.B; i++) {
-        const PoseCovRow& r = c->last_cov[i];
+        const PoseCovRow& r = c->last.cov[i];
         if (cov_T) memcpy(cov_T + 36 * i, r.cov_T, sizeof(r.cov_T));
         if (cov_p) memcpy(cov_p + 36 * i, r.cov_p, sizeof(r.cov_p));
         if (valid) valid[i] = r.valid;
@@ -2230,9 +2229,8 @@ extern "C" int svo_convert_gray(int device, int format, const uint8_t* src, int 
 static int mask_tables(svo_context* c) {
     if (!c->img_mask.empty()) return SVO_OK;
     const size_t B = (size_t)c->d.B, n = (size_t)c->d.geom.W * c->d.geom.H;
-    if (!c->h_mask_rows) { HIPCHK(hipHostMalloc((void**)&c->h_mask_rows, sizeof(uint8_t*) * SVO_RING * B)); memset((void*)c->h_mask_rows, 0, sizeof(uint8_t*) * SVO_RING * B); }
-    if (!c->d_mask_rows) HIPCHK(hipMalloc((void**)&c->d_mask_rows, sizeof(uint8_t*) * SVO_RING * B));
-    if (!c->h_mask_stage) HIPCHK(hipHostMalloc((void**)&c->h_mask_stage, n));
+    if (!c->mask_rows.h) HIPCHK(rings_alloc(c, {ring_spec(c->mask_rows, B, RING_UPLOADED)}));
+    if (!c->h_mask_stage) if (const int rc = pinned_alloc(c, &c->h_mask_stage, n)) return rc;
     if (!c->ev_mask_stage) HIPCHK(hipEventCreateWithFlags(&c->ev_mask_stage, hipEventDisableTiming));
     c->own_mask.assign(B, MaskPair{});
     c->img_mask.assign(B, nullptr);
@@ -2243,7 +2241,7 @@ extern "C" int svo_set_detection_mask(svo_context* c, int seq, const uint8_t* ma
     if (!c) return fail_arg("null context");
     if (c->d.CN != 1) return fail_arg("svo_set_detection_mask: a channels = 3 context runs FAST on the bytes of the interleaved rows, where pixel positions mean nothing");
     if (c->d.cfg.features_per_bucket > 1) return fail_arg("svo_set_detection_mask: detection masks need features_per_bucket == 1 (the general bucket walk takes none)");
-    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if (const int rc = seq_range(c, seq)) return rc;
     if (!mask) {                                                     // clear: the frames submitted from now on record no mask
         if (seq < 0) { c->shared_mask.cur = -1; for (MaskPair& p : c->own_mask) p.cur = -1; }
         else if (!c->own_mask.empty()) c->own_mask[seq].cur = -1;
@@ -2271,7 +2269,7 @@ extern "C" int svo_set_detection_mask(svo_context* c, int seq, const uint8_t* ma
 
 extern "C" int svo_get_detection_mask(svo_context* c, int seq, uint8_t* out, int* present) {
     if (!c) return fail_arg("null context");
-    if (seq < -1 || seq >= c->d.B) return fail_arg("seq out of range");
+    if (const int rc = seq_range(c, seq)) return rc;
     const MaskPair* p = &c->shared_mask;
     if (seq >= 0 && !c->own_mask.empty() && c->own_mask[seq].cur >= 0) p = &c->own_mask[seq];
     if (present) *present = p->cur >= 0;

@@ -96,6 +96,53 @@ def test_create_destroy_cycles_do_not_leak(api):
     assert free0 - free1 < 64 << 20                           # no growth beyond allocator noise
 
 
+def test_create_destroy_cycles_with_every_lazy_buffer_do_not_leak(api):
+    """The same probe over contexts that switch on every lazily allocated buffer and run two frames before they close.
+
+    Device memory only: pinned host memory is invisible to mem_get_info.  What guards it is the rule of svo_api.hip that every
+    pinned allocation registers with its context when it is made, and that svo_destroy frees by walking that registry."""
+    import torch
+    from stereo_visual_odometry_amd import synthetic as syn
+    W, H, B = 640, 360, 4
+    Pl, Pr = syn.projection_matrices(dict(syn.KITTI00, width=W, height=H, cx=W / 2.0, cy=H / 2.0))
+    xs, ys = np.meshgrid(np.arange(W, dtype=np.int16), np.arange(H, dtype=np.int16))
+    map1, map2 = np.ascontiguousarray(np.stack([xs, ys], -1)), np.zeros((H, W), np.uint16)     # the identity maps
+    frames = [[scenes.random_texture(H, W, 10 * k + i) for i in range(B)] for k in range(2)]
+    mask = np.full((H, W), 255, np.uint8); mask[:, : W // 4] = 0
+    # Bytes per cycle of each group of device buffers that is freed by an owner of its own, were that group alone leaked:
+    #   maps          2 cameras x W H (4 + 2) B                                  = 2 764 800   -> 64 MiB after  25 cycles
+    #   ids           3 x B x CAP x 8 B + B x 8 B, CAP = (92 - 4) x 160 = 14 080 = 1 351 712   ->               50
+    #   CLAHE staging 256 B table + 2 B frames of W H (a multiple of 256) + 256  = 1 843 712   ->               37
+    #   mask pair     both buffers of the shared pair (set twice, a frame apart) = 460 800     ->              146
+    # (64 MiB = 67 108 864 B.)  150 cycles put the smallest of them, the mask pair, at 69 120 000 B.
+    cycles = 150
+    assert cycles * 2 * W * H > 64 << 20
+
+    def cycle():
+        vo = api.BatchVisualOdometry(W, H, B)
+        vo.initalize_projection_matricies(Pl, Pr)
+        vo.set_rectification_maps(map1, map2, map1, map2, raw_size=(W, H))      # shared maps
+        vo.set_detection_mask(mask)                                             # shared mask: one buffer of the pair ...
+        vo.set_clahe(2.0, (8, 8))
+        vo.set_pose_covariance("residual")
+        vo.set_track_output(64)
+        vo.set_descriptor_output(True)
+        vo.set_motion_prior_mode("last_rotation")
+        vo.stereo_callback_batch(frames[0], frames[0])
+        vo.set_detection_mask(mask)                                             # ... and, a frame later, the other
+        vo.stereo_callback_batch(frames[1], frames[1])
+        vo.close()
+
+    cycle()                                                   # the first use of a kernel loads its code object and sizes the runtime's scratch: not a context's memory
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(cycles):
+        cycle()
+    free1 = torch.cuda.mem_get_info()[0]
+    print("free device memory fell by %d B over %d cycles" % (free0 - free1, cycles))
+    assert free0 - free1 < 64 << 20                           # no growth beyond allocator noise
+
+
 def test_tiny_and_untextured_images(api):
     """32x32 frames (single pyramid level for a 21-px window is refused; 10-px window gives 2 levels) and flat frames."""
     from stereo_visual_odometry_amd import synthetic as syn
