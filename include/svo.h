@@ -469,6 +469,77 @@ int svo_get_last_track_descriptors(svo_context* ctx, int seq, int cap, uint8_t* 
  * (both NULL: SVO_ERR_ARG).  Needs no device. */
 int svo_descriptor_pattern(int8_t pattern[1024], int32_t cs[60]);
 
+/* ---- Descriptor index: exact 2-nearest-neighbour Hamming matching on the device -------------------------------------------------
+ * What the descriptors are for: recognising a place again.  An index is an append-only array of rows (descriptor[32], id) in device
+ * memory, 40 bytes per row, numbered from 0 in the order they were added.  A search is brute force and exact; it is defined on
+ * integers, and the kernels agree with the definition below in every bit.
+ *
+ *  Distance.   d(q, r) = the popcount of the 256-bit XOR of query q and the descriptor of row r: 0 .. 256.
+ *  Order.      key(q, r) = (d(q, r), r), compared lexicographically: the smaller distance wins, at equal distances the smaller row.
+ *  Row range.  A search runs over the rows [row_lo, row_hi).  Rows arrive in time order, so a loop closer keeps the recent past out
+ *              with row_hi.
+ *  Best.       row = the row of the smallest key in the range.
+ *  Second.     row2 = the row of the smallest key among the rows of the range whose id DIFFERS from id[row].  A landmark seen in k
+ *              frames has k rows, all close to each other: a plain second-nearest row would nearly always be the same landmark
+ *              again, and a ratio test (dist / dist2) would then reject every good match.
+ *
+ * What cv::BFMatcher(NORM_HAMMING).knnMatch(k = 2) is to an OpenCV user, except for the second neighbour's id rule.  PARITY
+ * UNPINNED: which of several rows at one distance cv::BFMatcher returns was not measured (no OpenCV on the machines this was built
+ * on); no equality with it is claimed, the order above is the contract.
+ *
+ * An index owns one non-blocking stream and its own pinned staging.  svo_desc_index_add and svo_desc_index_match are synchronous to
+ * the caller and wait for that stream only — no device-wide synchronisation, nothing on a context's streams — so both are legal
+ * while any context has frames in flight, and change no bit of what those frames return.  One index is used by one thread at a
+ * time. */
+typedef struct svo_desc_index svo_desc_index;
+#define SVO_MATCH_NONE (-1)      /* row / row2: an empty range / no row with another id */
+#define SVO_MATCH_NO_DIST 257    /* dist / dist2 where the row is SVO_MATCH_NONE: above every distance, so `dist * 10 < dist2 * 7` passes for a lone candidate */
+typedef struct {                 /* 32 bytes */
+    uint64_t id, id2;            /* id[row], id[row2]; 0 where the row is SVO_MATCH_NONE */
+    int32_t  row, row2;          /* SVO_MATCH_NONE: an empty range / no row with another id */
+    uint16_t dist, dist2;        /* 0 .. 256; SVO_MATCH_NO_DIST with SVO_MATCH_NONE */
+    uint32_t reserved;           /* 0 */
+} svo_desc_match;
+/* An empty index with room for capacity rows on `device`: 1 <= capacity <= 1 << 24 (a row number takes 24 bits of a search's packed
+ * key), else SVO_ERR_ARG.  40 bytes of device memory per row, allocated here. */
+int svo_desc_index_create(int device, int capacity, svo_desc_index** out);
+void svo_desc_index_destroy(svo_desc_index* index);
+/* Append n rows from host memory: desc n x 32 bytes, ids n values.  All n or none: size + n > capacity is SVO_ERR_ARG and adds
+ * nothing.  *first_row (may be NULL) = the row number of the first one.  n = 0 is legal. */
+int svo_desc_index_add(svo_desc_index* index, int n, const uint8_t* desc, const uint64_t* ids, int* first_row);
+/* Append, in row order, the observation + descriptor rows of sequence seq of ctx's last COLLECTED frame whose flags contain every
+ * bit of need_flags (SVO_OBS_INLIER: the frame's inliers; 0: every row), read from the two pinned rings; the id of a row is its
+ * svo_track_obs id.  *first_row, *n_added may be NULL.  SVO_ERR_STATE exactly where svo_get_last_track_descriptors gives it;
+ * SVO_ERR_ARG as svo_desc_index_add's (nothing added) and for a bad ctx / seq. */
+int svo_desc_index_add_frame(svo_desc_index* index, svo_context* ctx, int seq, uint32_t need_flags, int* first_row, int* n_added);
+int svo_desc_index_size(const svo_desc_index* index);
+/* Keep the first n_rows rows (0 clears the index); rows added afterwards take their numbers.  n_rows > size or < 0: SVO_ERR_ARG. */
+int svo_desc_index_truncate(svo_desc_index* index, int n_rows);
+/* The best and second-best row of [row_lo, row_hi) for each of n queries (host, n x 32 bytes) into out (host, n rows).
+ * row_hi = -1: the index's size.  n = 0 and row_lo == row_hi (every row of out is then SVO_MATCH_NONE) are legal.
+ * SVO_ERR_ARG: row_lo < 0, row_hi > size, row_lo > row_hi. */
+int svo_desc_index_match(svo_desc_index* index, int n, const uint8_t* query, int row_lo, int row_hi, svo_desc_match* out);
+/* Tuning: the rows of the index one block of the search walks (0 = the default, 1024).  The search cuts the range at the multiples
+ * of this number and keeps a 16-byte partial result per (query, piece) in a device scratch owned by the index.  The scratch starts
+ * at 64 KiB and at least doubles whenever a search needs more, so an index that grows frame by frame re-allocates O(log size)
+ * times; a search of up to 65 536 pieces needs 64 MiB of it at most (more pieces mean fewer queries per launch, 64 at least).
+ * Outgrown buffers are freed with the index — freeing device memory waits for the whole device — and sum to less than the buffer
+ * in use: below 128 MiB in all up to 65 536 pieces.  The results do not depend on this number.  SVO_ERR_ARG: rows < 0 or > 1 << 24. */
+int svo_desc_index_set_chunk_rows(svo_desc_index* index, int rows);
+int svo_desc_index_get_chunk_rows(const svo_desc_index* index);
+/* Diagnostics, for tools/desc_match_bench.py and the tests; nothing a search returns depends on them.  svo_desc_index_set_timing:
+ * on != 0 records two HIP events around the kernels of every later svo_desc_index_match and reads their time after the call's
+ * synchronisation; off (the default) a search records nothing.  svo_desc_index_get_stats: the device time of the last search's
+ * kernels in milliseconds (summed over its launches, the copies not in it; 0 with timing off or when nothing was launched), how
+ * often the scratch was allocated, its size, and the bytes of the buffers it has outgrown. */
+typedef struct {
+    float    last_kernels_ms;
+    int32_t  scratch_allocations;
+    uint64_t scratch_bytes, scratch_bytes_outgrown;
+} svo_desc_index_stats;
+int svo_desc_index_set_timing(svo_desc_index* index, int on);
+int svo_desc_index_get_stats(const svo_desc_index* index, svo_desc_index_stats* stats);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the

@@ -483,4 +483,44 @@ class VisualOdometry {                                               // include/
     bool clahe_on_ = false; double clahe_clip_ = 2.0; int clahe_tx_ = 8, clahe_ty_ = 8;   // set_clahe (applied once the context exists)
 };
 
+// A device-resident index of (descriptor, id) rows with an exact 2-nearest-neighbour Hamming search (svo.h, "Descriptor index"): per
+// query the best row of a range, and the best row with ANOTHER id.  add and match are synchronous and wait for the index's own stream
+// only, so both may be called between a VisualOdometry's frames or while another context has frames in flight.
+class DescriptorIndex {
+   public:
+    using Descriptor = std::array<uint8_t, SVO_DESC_BYTES>;
+    explicit DescriptorIndex(int capacity, int device = default_device()) { svo_throw(svo_desc_index_create(device, capacity, &index_)); }
+    ~DescriptorIndex() { svo_desc_index_destroy(index_); }
+    DescriptorIndex(const DescriptorIndex&) = delete;
+    DescriptorIndex& operator=(const DescriptorIndex&) = delete;
+    DescriptorIndex(DescriptorIndex&& o) noexcept : index_(o.index_) { o.index_ = nullptr; }
+
+    // append rows (all or none) -> the row number of the first one
+    int add(const std::vector<Descriptor>& desc, const std::vector<uint64_t>& ids) {
+        if (desc.size() != ids.size()) throw std::runtime_error("DescriptorIndex::add: one id per descriptor row expected");
+        int first = 0;
+        svo_throw(svo_desc_index_add(index_, (int)desc.size(), desc.empty() ? nullptr : desc[0].data(), ids.data(), &first));
+        return first;
+    }
+    // append the rows of vo's last stereo_callback whose flags contain need_flags (SVO_OBS_INLIER: its inliers) -> {first row, rows added}
+    std::pair<int, int> add_frame(VisualOdometry& vo, uint32_t need_flags = SVO_OBS_INLIER) {
+        if (!vo.handle()) throw std::runtime_error("DescriptorIndex::add_frame: no frame yet (call stereo_callback first)");
+        int first = 0, n = 0;
+        svo_throw(svo_desc_index_add_frame(index_, vo.handle(), 0, need_flags, &first, &n));
+        return {first, n};
+    }
+    // per query the best and the second-best (by id) row of [row_lo, row_hi); row_hi = -1: every row from row_lo on
+    std::vector<svo_desc_match> match(const std::vector<Descriptor>& query, int row_lo = 0, int row_hi = -1) {
+        std::vector<svo_desc_match> out(query.size());
+        svo_throw(svo_desc_index_match(index_, (int)query.size(), query.empty() ? nullptr : query[0].data(), row_lo, row_hi, out.data()));
+        return out;
+    }
+    int size() const { return svo_desc_index_size(index_); }
+    void truncate(int n_rows) { svo_throw(svo_desc_index_truncate(index_, n_rows)); }
+    svo_desc_index* handle() { return index_; }
+
+   private:
+    svo_desc_index* index_ = nullptr;
+};
+
 }   // namespace visual_odometry

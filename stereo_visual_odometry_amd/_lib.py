@@ -116,6 +116,38 @@ lib.svo_describe_points.restype = C.c_int
 lib.svo_describe_points.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 lib.svo_descriptor_pattern.restype = C.c_int
 lib.svo_descriptor_pattern.argtypes = [C.c_void_p, C.c_void_p]
+# descriptor index (svo.h, "Descriptor index"): the 32-byte result row as a numpy structured dtype
+MATCH_NONE, MATCH_NO_DIST = -1, 257
+DESC_MATCH_DTYPE = np.dtype([("id", "<u8"), ("id2", "<u8"), ("row", "<i4"), ("row2", "<i4"), ("dist", "<u2"), ("dist2", "<u2"), ("reserved", "<u4")])
+assert DESC_MATCH_DTYPE.itemsize == 32
+lib.svo_desc_index_create.restype = C.c_int
+lib.svo_desc_index_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+lib.svo_desc_index_destroy.restype = None
+lib.svo_desc_index_destroy.argtypes = [C.c_void_p]
+lib.svo_desc_index_add.restype = C.c_int
+lib.svo_desc_index_add.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+lib.svo_desc_index_add_frame.restype = C.c_int
+lib.svo_desc_index_add_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+lib.svo_desc_index_size.restype = C.c_int
+lib.svo_desc_index_size.argtypes = [C.c_void_p]
+lib.svo_desc_index_truncate.restype = C.c_int
+lib.svo_desc_index_truncate.argtypes = [C.c_void_p, C.c_int]
+lib.svo_desc_index_match.restype = C.c_int
+lib.svo_desc_index_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+lib.svo_desc_index_set_chunk_rows.restype = C.c_int
+lib.svo_desc_index_set_chunk_rows.argtypes = [C.c_void_p, C.c_int]
+lib.svo_desc_index_get_chunk_rows.restype = C.c_int
+lib.svo_desc_index_get_chunk_rows.argtypes = [C.c_void_p]
+
+
+class SvoDescIndexStats(C.Structure):
+    _fields_ = [("last_kernels_ms", C.c_float), ("scratch_allocations", C.c_int32), ("scratch_bytes", C.c_uint64), ("scratch_bytes_outgrown", C.c_uint64)]
+
+
+lib.svo_desc_index_set_timing.restype = C.c_int
+lib.svo_desc_index_set_timing.argtypes = [C.c_void_p, C.c_int]
+lib.svo_desc_index_get_stats.restype = C.c_int
+lib.svo_desc_index_get_stats.argtypes = [C.c_void_p, C.POINTER(SvoDescIndexStats)]
 # motion priors (svo.h): H / Hi are 9 float32 each (n_seq x 9 in the batch setter), has n_seq bytes; R is 9 float64
 PATH_MOTION_PRIOR = 2048
 lib.svo_set_motion_prior.restype = C.c_int
@@ -222,6 +254,9 @@ EXPORTS = [
     "svo_lk_track_guess", "svo_circular_match_prior",
     "svo_set_motion_prior_mode", "svo_get_motion_prior_mode", "svo_get_last_motion_prior",
     "svo_set_descriptor_output", "svo_get_last_track_descriptors", "svo_describe_points", "svo_descriptor_pattern",
+    "svo_desc_index_create", "svo_desc_index_destroy", "svo_desc_index_add", "svo_desc_index_add_frame", "svo_desc_index_size",
+    "svo_desc_index_truncate", "svo_desc_index_match", "svo_desc_index_set_chunk_rows", "svo_desc_index_get_chunk_rows",
+    "svo_desc_index_set_timing", "svo_desc_index_get_stats",
 ]
 
 

@@ -359,6 +359,86 @@ def descriptor_pattern():
     return pat, cs[:30].copy(), cs[30:].copy()
 
 
+class DescriptorIndex:
+    """A device-resident index of (descriptor, id) rows with an exact 2-nearest-neighbour Hamming search (svo.h, "Descriptor index"):
+    the best row of a range, and the best row with ANOTHER id.  add and match are synchronous and wait for the index's own stream
+    only: both are legal while a context has frames in flight."""
+
+    def __init__(self, capacity, device=0):
+        self._h = C.c_void_p()
+        check(lib.svo_desc_index_create(int(device), int(capacity), C.byref(self._h)))
+        self.capacity = int(capacity)
+
+    @staticmethod
+    def _rows(desc, what):
+        d = np.ascontiguousarray(desc, dtype=np.uint8)
+        if d.ndim != 2 or d.shape[1] != _lib.DESC_BYTES:
+            raise ValueError("%s: an (n, %d) uint8 array expected" % (what, _lib.DESC_BYTES))
+        return d
+
+    def add(self, desc, ids):
+        """Append rows: desc (n, 32) uint8, ids (n,) integers -> the row number of the first one.  All or none."""
+        d = self._rows(desc, "desc")
+        i = np.ascontiguousarray(ids).astype(np.uint64, copy=False).reshape(-1)
+        if len(i) != len(d):
+            raise ValueError("one id per descriptor row expected")
+        first = C.c_int(0)
+        check(lib.svo_desc_index_add(self._h, len(d), ptr(d), ptr(i), C.byref(first)))
+        return first.value
+
+    def add_frame(self, vo, seq=0, need_flags=_lib.OBS_INLIER):
+        """Append the rows of sequence seq of vo's last collected frame whose flags contain need_flags -> (first_row, n_added)."""
+        h = getattr(vo, "_h", None)
+        if h is None or not h.value or not getattr(vo, "_created", True):
+            raise _lib.SvoError("libsvo_hip status %d: add_frame: no frame yet (call stereo_callback first)" % _lib.SVO_ERR_STATE)
+        first, n = C.c_int(0), C.c_int(0)
+        check(lib.svo_desc_index_add_frame(self._h, h, int(seq), int(need_flags), C.byref(first), C.byref(n)))
+        return first.value, n.value
+
+    def match(self, query, row_lo=0, row_hi=-1):
+        """query (n, 32) uint8 against the rows [row_lo, row_hi) (row_hi = -1: all) -> a structured array of n rows with the fields of
+        svo_desc_match: id, id2, row, row2 (-1: none), dist, dist2 (257 with -1), reserved."""
+        q = self._rows(query, "query")
+        out = np.zeros(len(q), _lib.DESC_MATCH_DTYPE)
+        check(lib.svo_desc_index_match(self._h, len(q), ptr(q), int(row_lo), int(row_hi), ptr(out)))
+        return out
+
+    @property
+    def size(self):
+        return check(lib.svo_desc_index_size(self._h))
+
+    def truncate(self, n_rows):
+        check(lib.svo_desc_index_truncate(self._h, int(n_rows)))
+
+    @property
+    def chunk_rows(self):
+        """tuning: the rows of the index one block of the search walks; assign 0 for the default"""
+        return check(lib.svo_desc_index_get_chunk_rows(self._h))
+
+    @chunk_rows.setter
+    def chunk_rows(self, rows):
+        check(lib.svo_desc_index_set_chunk_rows(self._h, int(rows)))
+
+    def set_timing(self, on=True):
+        """diagnostics: record HIP events around the kernels of every later match (off by default)"""
+        check(lib.svo_desc_index_set_timing(self._h, int(bool(on))))
+
+    def stats(self):
+        """diagnostics (svo_desc_index_get_stats) -> dict: last_kernels_ms (0 unless set_timing), scratch_allocations, scratch_bytes,
+        scratch_bytes_outgrown"""
+        st = _lib.SvoDescIndexStats()
+        check(lib.svo_desc_index_get_stats(self._h, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in st._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib.svo_desc_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
 # ---------------------------------------------------------------------------- FeatureSet / Bucket
 class FeatureSet:
     """vo.h:132-188 — parallel arrays points / ages / strengths."""

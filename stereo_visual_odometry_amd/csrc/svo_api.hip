@@ -5,6 +5,7 @@
 // on the device from SeqState, so a frame needs no host round trip until its pose is read back.
 #include "svo_internal.hpp"
 #include "svo_prior.hpp"
+#include "svo_match_internal.hpp"
 #include <stdio.h>
 #include <string.h>
 #include <stddef.h>
@@ -19,6 +20,7 @@
 
 static thread_local std::string g_err;
 extern "C" const char* svo_last_error(void) { return g_err.c_str(); }
+void svo_set_error(const char* msg) { g_err = msg; }                 // for the library's other host files (svo_match_internal.hpp declares it)
 static thread_local int g_stage_path = 0;                            // svo_get_last_frame_path(NULL): this thread's last stage call
 
 // SVO_FORCE_LEAN=1 (test knob): every context, stage contexts included, takes the 96-register builds of the f64 kernels

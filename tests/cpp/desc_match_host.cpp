@@ -1,0 +1,88 @@
+// A stand-alone host program over stereo_visual_odometry_amd/csrc/svo_match.hpp — the text k_desc_match and k_desc_match_merge run —
+// built with AddressSanitizer and UBSan by tests/test_desc_match_host.py.  On randomised rows with heavy ties in the distance and
+// duplicate ids it checks, against the brute-force definition of include/svo.h ("Descriptor index"):
+//   the packed key (order, round trip, the "no row" key);
+//   match_update over a whole range, rows in order;
+//   match_merge over EVERY split point of the range, in both argument orders;
+//   match_merge over every 3-way split, in both groupings.
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+#include "../../stereo_visual_odometry_amd/csrc/svo_match.hpp"
+
+struct Row { uint32_t dist; uint64_t id; };
+
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+static uint32_t rnd(uint32_t n) {                       // xorshift64*: uniform enough for a test
+    rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
+    return (uint32_t)((rng_state * 0x2545F4914F6CDD1Dull) >> 33) % n;
+}
+
+// the definition: the smallest (dist, row) of [lo, hi); the smallest among the rows whose id differs from the best's
+static MatchState brute(const std::vector<Row>& rows, int first_row, int lo, int hi) {
+    MatchState s = match_empty();
+    int best = -1;
+    for (int i = lo; i < hi; i++)
+        if (best < 0 || rows[i].dist < rows[best].dist) best = i;      // the first minimum: the lower row at equal distances
+    if (best < 0) return s;
+    s.k1 = match_make_key(rows[best].dist, (uint32_t)(first_row + best)); s.id1 = rows[best].id;
+    int second = -1;
+    for (int i = lo; i < hi; i++)
+        if (rows[i].id != rows[best].id && (second < 0 || rows[i].dist < rows[second].dist)) second = i;
+    if (second >= 0) s.k2 = match_make_key(rows[second].dist, (uint32_t)(first_row + second));
+    return s;
+}
+
+static MatchState stream(const std::vector<Row>& rows, int first_row, int lo, int hi) {
+    MatchState s = match_empty();
+    for (int i = lo; i < hi; i++) match_update(s, match_make_key(rows[i].dist, (uint32_t)(first_row + i)), rows[i].id);
+    return s;
+}
+
+static bool same(const MatchState& a, const MatchState& b) { return a.k1 == b.k1 && a.k2 == b.k2 && a.id1 == b.id1; }
+
+static int fails = 0;
+static void expect(bool ok, const char* what, int a = 0, int b = 0, int c = 0) {
+    if (!ok && fails++ < 10) std::printf("FAILED: %s (%d %d %d)\n", what, a, b, c);
+}
+
+int main() {
+    // ---- the key
+    expect(match_make_key(3, 5) < match_make_key(4, 0), "the smaller distance wins");
+    expect(match_make_key(3, 5) < match_make_key(3, 6), "at equal distances the smaller row wins");
+    expect(match_make_key(256, SVO_MATCH_MAX_ROWS - 1) < SVO_MATCH_KEY_NONE, "every key of a row is below the no-row key");
+    expect(match_key_dist(match_make_key(256, SVO_MATCH_MAX_ROWS - 1)) == 256 && match_key_row(match_make_key(256, SVO_MATCH_MAX_ROWS - 1)) == SVO_MATCH_MAX_ROWS - 1,
+           "round trip at the largest distance and row");
+    expect(match_key_dist(match_make_key(0, 0)) == 0 && match_key_row(match_make_key(0, 0)) == 0 && !match_key_none(match_make_key(0, 0)), "round trip at 0, 0");
+    expect(match_key_row(SVO_MATCH_KEY_NONE) == -1 && match_key_dist(SVO_MATCH_KEY_NONE) == SVO_MATCH_DIST_NONE && match_key_none(SVO_MATCH_KEY_NONE), "the no-row key");
+    expect(same(match_merge(match_empty(), match_empty()), match_empty()), "two empty states merge to the empty state");
+
+    // ---- randomised rows: distances from a handful of values (ties), ids from a handful of values (duplicates), id 0 included
+    long checked = 0;
+    for (int trial = 0; trial < 400; trial++) {
+        const int m = (int)rnd(33);                               // 0 .. 32 rows
+        const uint32_t n_dist = 1 + rnd(4), n_id = 1 + rnd(4);    // 1 .. 4 distinct distances / ids
+        const uint32_t far = rnd(2) ? 253 : 0;                    // some trials at the top of the distance range: 253 .. 256
+        const int first_row = rnd(2) ? 0 : SVO_MATCH_MAX_ROWS - 32 - (int)rnd(8);   // some at the top of the row range
+        std::vector<Row> rows((size_t)m);
+        for (auto& r : rows) { r.dist = far + rnd(n_dist); r.id = rnd(n_id) * 0x100000001ull; }   // both halves of an id matter
+        const MatchState want = brute(rows, first_row, 0, m);
+        expect(same(stream(rows, first_row, 0, m), want), "match_update over the whole range", trial, m);
+        for (int s = 0; s <= m; s++) {
+            const MatchState a = stream(rows, first_row, 0, s), b = stream(rows, first_row, s, m);
+            expect(same(a, brute(rows, first_row, 0, s)) && same(b, brute(rows, first_row, s, m)), "match_update over a part", trial, m, s);
+            expect(same(match_merge(a, b), want), "match_merge at a split point", trial, m, s);
+            expect(same(match_merge(b, a), want), "match_merge at a split point, arguments swapped", trial, m, s);
+            for (int t = s; t <= m; t++) {
+                const MatchState p = stream(rows, first_row, s, t), q = stream(rows, first_row, t, m);
+                expect(same(match_merge(match_merge(a, p), q), want), "3-way split, left grouping", trial, s, t);
+                expect(same(match_merge(a, match_merge(p, q)), want), "3-way split, right grouping", trial, s, t);
+                expect(same(match_merge(match_merge(q, a), p), want), "3-way split, out of row order", trial, s, t);
+                checked += 3;
+            }
+        }
+    }
+    if (fails) { std::printf("%d checks failed\n", fails); return 1; }
+    std::printf("DESC MATCH HOST OK (%ld three-way merges)\n", checked);
+    return 0;
+}
