@@ -531,7 +531,8 @@ int svo_desc_index_get_chunk_rows(const svo_desc_index* index);
  * on != 0 records two HIP events around the kernels of every later svo_desc_index_match and reads their time after the call's
  * synchronisation; off (the default) a search records nothing.  svo_desc_index_get_stats: the device time of the last search's
  * kernels in milliseconds (summed over its launches, the copies not in it; 0 with timing off or when nothing was launched), how
- * often the scratch was allocated, its size, and the bytes of the buffers it has outgrown. */
+ * often the scratch was allocated, its size, and the bytes of the buffers it has outgrown.  After svo_desc_index_select or
+ * svo_desc_index_localize with timing on, last_kernels_ms is the device time of the selection kernel alone. */
 typedef struct {
     float    last_kernels_ms;
     int32_t  scratch_allocations;
@@ -539,6 +540,68 @@ typedef struct {
 } svo_desc_index_stats;
 int svo_desc_index_set_timing(svo_desc_index* index, int on);
 int svo_desc_index_get_stats(const svo_desc_index* index, svo_desc_index_stats* stats);
+
+/* ---- Relocalisation: where is this camera in the map? ----------------------------------------------------------------------------
+ * An index may carry a 3-D point per row: the landmark in the caller's map frame.  One call then takes a frame's (descriptor, pixel)
+ * pairs, searches, selects a consistent candidate set on the device and runs the RANSAC-PnP of svo_camera_to_world on it: one host
+ * synchronisation, no host round trip between the search and the pose.  Like add and match, every call here waits for the index's
+ * own stream only and is legal with frames in flight.
+ *
+ * The selection is defined on integers.  Per query j (0 .. n - 1) let m_j be its search result over [row_lo, row_hi)
+ * (svo_desc_index_match's row j), and tag[r] the tag of row r's point:
+ *  1. Accept.      j is accepted when m_j.row != SVO_MATCH_NONE, tag[m_j.row] != SVO_POINT_NONE, m_j.dist <= max_dist and
+ *                  m_j.dist * ratio_den < m_j.dist2 * ratio_num — strictly; dist2 = SVO_MATCH_NO_DIST (257) of a lone candidate passes.
+ *  2. One pixel per landmark.  Among the accepted queries with the same m_j.id only the smallest (m_j.dist, j) survives.
+ *  3. Candidates.  The survivors in increasing j: candidate c carries (query j, row m_j.row, pixel xy[j], point xyz[m_j.row]).
+ *  4. Gate.        n_candidates < min_candidates: success = 0, the PnP does nothing and iters_run = 0. */
+#define SVO_POINT_NONE (-1)      /* the tag of an index row without a point */
+#define SVO_RELOC_MAX_QUERIES 4096
+typedef struct {
+    int32_t row_lo, row_hi;      /* the rows searched, as svo_desc_index_match's (row_hi = -1: the index's size) */
+    int32_t max_dist;            /* rule 1: 0 .. 256 */
+    int32_t ratio_num, ratio_den; /* rule 1: 1 .. 1 << 20 each */
+    int32_t min_candidates;      /* rule 4: >= 6 (with 4 or 5 points svo_camera_to_world takes direct routes chosen on the host) */
+    int32_t ransac_iterations;   /* these three as svo_camera_to_world's */
+    float   reproj_error, confidence;
+} svo_reloc_params;
+typedef struct {
+    int32_t success, n_candidates, n_inliers, iters_run;
+    double  R[9], t[3];          /* in: the extrinsic guess; out: the pose on success (untouched otherwise): x_cam = R X_map + t */
+    double  T[16];               /* out, on success: the inverse, the camera in the map (row-major 4 x 4); zeros otherwise */
+} svo_reloc_result;
+/* max_dist = 40, ratio 7 / 10, min_candidates = 6, the whole index; iterations, error and confidence from svo_config_default */
+void svo_reloc_params_default(svo_reloc_params* params);
+/* Give the index's rows points: capacity x 16 bytes of device memory, a row being {float x, y, z; int32_t tag}.  Legal only while
+ * the index is empty (SVO_ERR_STATE otherwise); enabling twice is legal.  svo_desc_index_add on such an index writes SVO_POINT_NONE
+ * rows; svo_desc_index_truncate drops the points with their rows. */
+int svo_desc_index_enable_points(svo_desc_index* index);
+/* svo_desc_index_add with a point per row: xyz n x 3 floats in the map frame, tags n values >= 0 (NULL: all 0; a frame number is
+ * the intended use).  All n rows or none.  SVO_ERR_STATE: an index without points.  SVO_ERR_ARG: a negative tag, a non-finite
+ * coordinate, and svo_desc_index_add's. */
+int svo_desc_index_add_points(svo_desc_index* index, int n, const uint8_t* desc, const uint64_t* ids, const float* xyz,
+                              const int32_t* tags, int* first_row);
+/* svo_desc_index_add_frame with SVO_OBS_HAS_XYZ always required, and each row's point moved into the map.  An observation row's xyz
+ * is in the T0 left camera frame — the frame BEFORE the one just collected (svo_track_obs) — so cam_to_map (16 doubles, row-major
+ * 4 x 4; NULL: the identity) is the pose of the PREVIOUS frame's left camera in the map, not the pose svo_collect has just returned.
+ * Per coordinate r the stored value is f32(T[4r] x + T[4r+1] y + T[4r+2] z + T[4r+3]), evaluated in f64 from left to right
+ * without contraction.  SVO_ERR_STATE: an index without points; SVO_ERR_ARG: a negative tag, a non-finite entry of cam_to_map or
+ * result. */
+int svo_desc_index_add_frame_points(svo_desc_index* index, svo_context* ctx, int seq, uint32_t need_flags, const double* cam_to_map,
+                                    int32_t tag, int* first_row, int* n_added);
+/* The selection alone: rules 1 - 3 for n <= SVO_RELOC_MAX_QUERIES queries (host: query n x 32 bytes, xy n x 2 floats; xy may be NULL
+ * when cand_xy is) -> *n_candidates and, where non-NULL, per candidate its query, its row, its pixel (2 floats) and its point
+ * (3 floats), each with room for n entries — the arrays the PnP of svo_desc_index_localize reads.  ransac_* and min_candidates > n
+ * play no part.  SVO_ERR_STATE: an index without points.  SVO_ERR_ARG: n > 4096, a bad row range, max_dist outside 0 .. 256, a ratio
+ * term outside 1 .. 1 << 20, min_candidates < 6. */
+int svo_desc_index_select(svo_desc_index* index, int n, const uint8_t* query, const float* xy, const svo_reloc_params* params,
+                          int* n_candidates, int32_t* cand_query, int32_t* cand_row, float* cand_xy, float* cand_xyz);
+/* Search, select, RANSAC-PnP.  K: the 3 x 3 camera matrix; result->R, t: the guess going in.  cand_query, cand_row, cand_inlier
+ * (each n entries, each may be NULL): per candidate its query, its row and whether the PnP kept it (1 / 0).  For the candidate
+ * arrays svo_desc_index_select returns, success, R, t, the inlier set and iters_run equal svo_camera_to_world's on those arrays
+ * with the same guess and parameters in every bit: the same kernels on the same inputs.  Errors as svo_desc_index_select's. */
+int svo_desc_index_localize(svo_desc_index* index, const float K[9], int n, const uint8_t* query, const float* xy,
+                            const svo_reloc_params* params, svo_reloc_result* result, int32_t* cand_query, int32_t* cand_row,
+                            uint8_t* cand_inlier);
 
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.

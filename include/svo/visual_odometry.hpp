@@ -515,6 +515,51 @@ class DescriptorIndex {
         svo_throw(svo_desc_index_match(index_, (int)query.size(), query.empty() ? nullptr : query[0].data(), row_lo, row_hi, out.data()));
         return out;
     }
+    // ---- relocalisation (svo.h, "Relocalisation"): rows with 3-D points, and the camera's pose in the map from one call
+    struct Candidates { std::vector<int32_t> query, row; std::vector<uint8_t> inlier; };   // inlier: localize only
+    static svo_reloc_params default_params() { svo_reloc_params p; svo_reloc_params_default(&p); return p; }
+    void enable_points() { svo_throw(svo_desc_index_enable_points(index_)); }              // while the index is empty
+    // add with a point per row: xyz holds 3 floats per row in the map frame; tags (>= 0) may be empty: all 0
+    int add_points(const std::vector<Descriptor>& desc, const std::vector<uint64_t>& ids, const std::vector<float>& xyz, const std::vector<int32_t>& tags = {}) {
+        if (desc.size() != ids.size() || xyz.size() != 3 * desc.size() || (!tags.empty() && tags.size() != desc.size()))
+            throw std::runtime_error("DescriptorIndex::add_points: one id, one point and one tag per descriptor row expected");
+        int first = 0;
+        svo_throw(svo_desc_index_add_points(index_, (int)desc.size(), desc.empty() ? nullptr : desc[0].data(), ids.data(), xyz.data(),
+                                            tags.empty() ? nullptr : tags.data(), &first));
+        return first;
+    }
+    // add_frame with each row's point moved into the map.  cam_to_map: the pose (row-major 4 x 4) of the PREVIOUS frame's left camera
+    // in the map — an observation row's xyz is in the T0 camera frame — or nullptr for the identity.
+    std::pair<int, int> add_frame(VisualOdometry& vo, const double* cam_to_map, int32_t tag, uint32_t need_flags = SVO_OBS_INLIER) {
+        if (!vo.handle()) throw std::runtime_error("DescriptorIndex::add_frame: no frame yet (call stereo_callback first)");
+        int first = 0, n = 0;
+        svo_throw(svo_desc_index_add_frame_points(index_, vo.handle(), 0, need_flags, cam_to_map, tag, &first, &n));
+        return {first, n};
+    }
+    // the selection alone: the candidates' queries and rows, in increasing query
+    Candidates select(const std::vector<Descriptor>& query, const std::vector<float>& xy, const svo_reloc_params& params) {
+        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::select: one pixel per query expected");
+        Candidates c;
+        c.query.resize(query.size()); c.row.resize(query.size());
+        int k = 0;
+        svo_throw(svo_desc_index_select(index_, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &k,
+                                        c.query.data(), c.row.data(), nullptr, nullptr));
+        c.query.resize((size_t)k); c.row.resize((size_t)k);
+        return c;
+    }
+    // search, select and RANSAC-PnP: result.R, t hold the guess going in and the pose (x_cam = R X_map + t) on success, result.T the
+    // camera in the map; candidates (may be null) receives the candidate lists with the PnP's inlier flags
+    svo_reloc_result localize(const float K[9], const std::vector<Descriptor>& query, const std::vector<float>& xy, const svo_reloc_params& params,
+                              svo_reloc_result result, Candidates* candidates = nullptr) {
+        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::localize: one pixel per query expected");
+        Candidates c;
+        c.query.resize(query.size()); c.row.resize(query.size()); c.inlier.resize(query.size());
+        svo_throw(svo_desc_index_localize(index_, K, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &result,
+                                          c.query.data(), c.row.data(), c.inlier.data()));
+        c.query.resize((size_t)result.n_candidates); c.row.resize((size_t)result.n_candidates); c.inlier.resize((size_t)result.n_candidates);
+        if (candidates) *candidates = std::move(c);
+        return result;
+    }
     int size() const { return svo_desc_index_size(index_); }
     void truncate(int n_rows) { svo_throw(svo_desc_index_truncate(index_, n_rows)); }
     svo_desc_index* handle() { return index_; }

@@ -148,6 +148,34 @@ lib.svo_desc_index_set_timing.restype = C.c_int
 lib.svo_desc_index_set_timing.argtypes = [C.c_void_p, C.c_int]
 lib.svo_desc_index_get_stats.restype = C.c_int
 lib.svo_desc_index_get_stats.argtypes = [C.c_void_p, C.POINTER(SvoDescIndexStats)]
+# relocalisation (svo.h, "Relocalisation"): points in the index, select and localize
+POINT_NONE, RELOC_MAX_QUERIES = -1, 4096
+
+
+class SvoRelocParams(C.Structure):
+    _fields_ = [("row_lo", C.c_int32), ("row_hi", C.c_int32), ("max_dist", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32),
+                ("min_candidates", C.c_int32), ("ransac_iterations", C.c_int32), ("reproj_error", C.c_float), ("confidence", C.c_float)]
+
+
+class SvoRelocResult(C.Structure):
+    _fields_ = [("success", C.c_int32), ("n_candidates", C.c_int32), ("n_inliers", C.c_int32), ("iters_run", C.c_int32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("T", C.c_double * 16)]
+
+
+lib.svo_reloc_params_default.restype = None
+lib.svo_reloc_params_default.argtypes = [C.POINTER(SvoRelocParams)]
+lib.svo_desc_index_enable_points.restype = C.c_int
+lib.svo_desc_index_enable_points.argtypes = [C.c_void_p]
+lib.svo_desc_index_add_points.restype = C.c_int
+lib.svo_desc_index_add_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+lib.svo_desc_index_add_frame_points.restype = C.c_int
+lib.svo_desc_index_add_frame_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+lib.svo_desc_index_select.restype = C.c_int
+lib.svo_desc_index_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams), C.POINTER(C.c_int),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_desc_index_localize.restype = C.c_int
+lib.svo_desc_index_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
+                                        C.POINTER(SvoRelocResult), C.c_void_p, C.c_void_p, C.c_void_p]
 # motion priors (svo.h): H / Hi are 9 float32 each (n_seq x 9 in the batch setter), has n_seq bytes; R is 9 float64
 PATH_MOTION_PRIOR = 2048
 lib.svo_set_motion_prior.restype = C.c_int
@@ -257,6 +285,8 @@ EXPORTS = [
     "svo_desc_index_create", "svo_desc_index_destroy", "svo_desc_index_add", "svo_desc_index_add_frame", "svo_desc_index_size",
     "svo_desc_index_truncate", "svo_desc_index_match", "svo_desc_index_set_chunk_rows", "svo_desc_index_get_chunk_rows",
     "svo_desc_index_set_timing", "svo_desc_index_get_stats",
+    "svo_reloc_params_default", "svo_desc_index_enable_points", "svo_desc_index_add_points", "svo_desc_index_add_frame_points",
+    "svo_desc_index_select", "svo_desc_index_localize",
 ]
 
 

@@ -6,6 +6,7 @@ functions featureDetectionFast / deletePointsWithFailureStatus / deleteFeaturesW
 findClosePoints / cameraToWorld / getInverseTransform (vo.h:393-470).  cv::Mat becomes numpy,
 std::vector<cv::Point2f> becomes an (N,2) float32 array.  All arithmetic runs on the GPU.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -359,15 +360,98 @@ def descriptor_pattern():
     return pat, cs[:30].copy(), cs[30:].copy()
 
 
+RelocResult = collections.namedtuple("RelocResult", "success n_candidates n_inliers iters_run R t T")
+
+
 class DescriptorIndex:
     """A device-resident index of (descriptor, id) rows with an exact 2-nearest-neighbour Hamming search (svo.h, "Descriptor index"):
     the best row of a range, and the best row with ANOTHER id.  add and match are synchronous and wait for the index's own stream
     only: both are legal while a context has frames in flight."""
 
-    def __init__(self, capacity, device=0):
+    def __init__(self, capacity, device=0, points=False):
         self._h = C.c_void_p()
         check(lib.svo_desc_index_create(int(device), int(capacity), C.byref(self._h)))
         self.capacity = int(capacity)
+        if points:
+            self.enable_points()
+
+    def enable_points(self):
+        """Give the rows 3-D points (svo.h, "Relocalisation"); legal only while the index is empty."""
+        check(lib.svo_desc_index_enable_points(self._h))
+
+    def add_points(self, desc, ids, xyz, tags=None):
+        """add with a point per row: xyz (n, 3) float32 in the map frame, tags (n,) int32 >= 0 (None: all 0) -> the first row's number."""
+        d = self._rows(desc, "desc")
+        i = np.ascontiguousarray(ids).astype(np.uint64, copy=False).reshape(-1)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        t = None if tags is None else np.ascontiguousarray(tags, np.int32).reshape(-1)
+        if len(i) != len(d) or len(p) != len(d) or (t is not None and len(t) != len(d)):
+            raise ValueError("one id, one point and one tag per descriptor row expected")
+        first = C.c_int(0)
+        check(lib.svo_desc_index_add_points(self._h, len(d), ptr(d), ptr(i), ptr(p), ptr(t), C.byref(first)))
+        return first.value
+
+    def add_frame_points(self, vo, cam_to_map=None, tag=0, seq=0, need_flags=_lib.OBS_INLIER):
+        """add_frame with each row's point moved into the map -> (first_row, n_added).  cam_to_map (4, 4) float64 is the pose of the
+        PREVIOUS frame's left camera in the map (an observation row's xyz is in the T0 camera frame); None: the identity."""
+        h = getattr(vo, "_h", None)
+        if h is None or not h.value or not getattr(vo, "_created", True):
+            raise _lib.SvoError("libsvo_hip status %d: add_frame_points: no frame yet (call stereo_callback first)" % _lib.SVO_ERR_STATE)
+        T = None if cam_to_map is None else np.ascontiguousarray(cam_to_map, np.float64).reshape(16)
+        first, n = C.c_int(0), C.c_int(0)
+        check(lib.svo_desc_index_add_frame_points(self._h, h, int(seq), int(need_flags), ptr(T), int(tag), C.byref(first), C.byref(n)))
+        return first.value, n.value
+
+    @staticmethod
+    def reloc_params(**over):
+        """svo_reloc_params_default with fields replaced: row_lo, row_hi, max_dist, ratio_num, ratio_den, min_candidates,
+        ransac_iterations, reproj_error, confidence"""
+        p = _lib.SvoRelocParams()
+        lib.svo_reloc_params_default(C.byref(p))
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise AttributeError("svo_reloc_params has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+    def _queries(self, query, xy):
+        q = self._rows(query, "query")
+        p = _pts(xy)
+        if len(p) != len(q):
+            raise ValueError("one pixel per query expected")
+        return q, p
+
+    def select(self, query, xy, params=None, **over):
+        """The relocaliser's selection alone (svo_desc_index_select): query (n, 32) uint8, xy (n, 2) float32 -> a dict of the candidates'
+        query (k,) int32, row (k,) int32, xy (k, 2) float32 and xyz (k, 3) float32, in increasing query."""
+        q, p = self._queries(query, xy)
+        prm = params if params is not None else self.reloc_params(**over)
+        n = len(q)
+        cq, cr = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        cxy, cxyz = np.zeros((max(n, 1), 2), np.float32), np.zeros((max(n, 1), 3), np.float32)
+        k = C.c_int(0)
+        check(lib.svo_desc_index_select(self._h, n, ptr(q), ptr(p), C.byref(prm), C.byref(k), ptr(cq), ptr(cr), ptr(cxy), ptr(cxyz)))
+        k = k.value
+        return dict(query=cq[:k].copy(), row=cr[:k].copy(), xy=cxy[:k].copy(), xyz=cxyz[:k].copy())
+
+    def localize(self, K, query, xy, rotation=None, translation=None, params=None, **over):
+        """Search, select and RANSAC-PnP in one call (svo_desc_index_localize) -> (RelocResult, candidates): the record holds success,
+        n_candidates, n_inliers, iters_run, R (3, 3), t (3, 1) with x_cam = R X_map + t (the guess going in, unchanged without
+        success) and T (4, 4), the camera in the map; candidates is a dict of query, row (k,) int32 and inlier (k,) bool."""
+        q, p = self._queries(query, xy)
+        prm = params if params is not None else self.reloc_params(**over)
+        Kf = np.ascontiguousarray(np.asarray(K, np.float32).reshape(-1)[:9]) if np.size(K) == 9 else \
+            np.ascontiguousarray(np.asarray(K, np.float32)[:3, :3]).reshape(9)
+        res = _lib.SvoRelocResult()
+        res.R[:] = list(np.asarray(np.eye(3) if rotation is None else rotation, np.float64).reshape(9))
+        res.t[:] = list(np.asarray(np.zeros(3) if translation is None else translation, np.float64).reshape(3))
+        n = len(q)
+        cq, cr, ci = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        check(lib.svo_desc_index_localize(self._h, ptr(Kf), n, ptr(q), ptr(p), C.byref(prm), C.byref(res), ptr(cq), ptr(cr), ptr(ci)))
+        k = res.n_candidates
+        rec = RelocResult(bool(res.success), k, res.n_inliers, res.iters_run, np.array(res.R[:]).reshape(3, 3), np.array(res.t[:]).reshape(3, 1),
+                          np.array(res.T[:]).reshape(4, 4))
+        return rec, dict(query=cq[:k].copy(), row=cr[:k].copy(), inlier=ci[:k].astype(bool))
 
     @staticmethod
     def _rows(desc, what):

@@ -6,6 +6,7 @@
 #include "svo_internal.hpp"
 #include "svo_prior.hpp"
 #include "svo_match_internal.hpp"
+#include "svo_reloc_internal.hpp"
 #include <stdio.h>
 #include <string.h>
 #include <stddef.h>
@@ -1872,18 +1873,33 @@ extern "C" int svo_triangulate(int device, const float Pl[12], const float Pr[12
     return SVO_OK;
 }
 
+// the stage context of a stand-alone RANSAC-PnP over up to cap points: svo_camera_to_world's, and the relocaliser's
+static int pnp_stage_ctx(int device, int cap, int ransac_iterations, float reproj_error, float confidence, svo_context** out) {
+    svo_config cfg; svo_config_default(&cfg);
+    cfg.ransac_iterations = ransac_iterations > 1 ? ransac_iterations : 1;
+    cfg.ransac_reprojection_error = reproj_error; cfg.ransac_confidence = confidence;
+    cfg.features_threshold = 0;                                                  // cameraToWorld itself has no inlier-count gate
+    cfg.max_translation_norm = 1e300; cfg.max_rotation_norm = 1e300;             // nor motion gates
+    return stage_ctx(cfg, device, 64, 64, cap, out);
+}
+// svo_reloc_internal.hpp: the same context for svo_desc_index_localize (svo_match_api.hip), which enqueues on its index's stream
+int svo_reloc_stage_ctx(int device, int cap, int ransac_iterations, float reproj_error, float confidence, const DevBuffers** d) {
+    svo_context* c = nullptr;
+    const int rc = pnp_stage_ctx(device, cap, ransac_iterations, reproj_error, confidence, &c);
+    if (rc != SVO_OK) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));   // a context created just now may still be clearing its buffers on its own stream; otherwise idle
+    g_stage_path = c->d.co_resident ? SVO_PATH_LEAN : 0;
+    *d = &c->d;
+    return SVO_OK;
+}
+
 extern "C" int svo_camera_to_world(int device, const float K[9], int n, const float* cam_pts, const float* world_pts,
                                    double R[9], double t[3], int* inliers, int* n_inliers, int* success,
                                    int ransac_iterations, float reproj_error, float confidence, int* iters_run) {
     if (!K || !R || !t || !n_inliers || !success || n < 0 || (n > 0 && (!cam_pts || !world_pts))) return fail_arg("bad arguments");
     *n_inliers = 0; *success = 0; if (iters_run) *iters_run = 0;
     if (n < 4) return fail_arg("cameraToWorld needs at least 4 points (cv::solvePnPRansac asserts npoints >= 4)");
-    svo_config cfg; svo_config_default(&cfg);
-    cfg.ransac_iterations = ransac_iterations > 1 ? ransac_iterations : 1;
-    cfg.ransac_reprojection_error = reproj_error; cfg.ransac_confidence = confidence;
-    cfg.features_threshold = 0;                                                  // cameraToWorld itself has no inlier-count gate
-    cfg.max_translation_norm = 1e300; cfg.max_rotation_norm = 1e300;             // nor motion gates
-    svo_context* c = nullptr; int rc = stage_ctx(cfg, device, 64, 64, n, &c); if (rc != SVO_OK) return rc;
+    svo_context* c = nullptr; int rc = pnp_stage_ctx(device, n, ransac_iterations, reproj_error, confidence, &c); if (rc != SVO_OK) return rc;
     SeqState hs; memset(&hs, 0, sizeof(hs));
     hs.active = 1; hs.fail_reason = 0; hs.n_tracks = n; hs.n_feat = n; hs.feat_buf = 0;
     memcpy(hs.K, K, sizeof(float) * 9); memcpy(hs.R, R, sizeof(double) * 9); memcpy(hs.t, t, sizeof(double) * 3);

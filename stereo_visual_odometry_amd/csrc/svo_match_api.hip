@@ -1,7 +1,11 @@
 // svo_match_api.hip — host side of the descriptor index (include/svo.h, "Descriptor index"): the index object, the append copies,
 // the batched search and the C-ABI.  An index owns one non-blocking stream and its own pinned staging; add and match wait for that
 // stream alone, so they are legal beside any context's frames in flight.  The kernels are in svo_kernels_match.hip.
-#include "svo_match_internal.hpp"
+// The relocaliser (include/svo.h, "Relocalisation") is here too: the points of an index, and select / localize, which put the search,
+// k_reloc_select (svo_kernels_reloc.hip) and the RANSAC-PnP kernels on the index's stream and wait once.
+#include "svo_reloc_internal.hpp"
+#include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
@@ -24,6 +28,8 @@
 
 static int fail(int rc, const char* msg) { svo_set_error(msg); return rc; }
 
+struct RelocDevOut;
+struct RelocHost;
 struct svo_desc_index {
     int device = 0, capacity = 0, size = 0, chunk_rows = MATCH_DEFAULT_CHUNK;
     hipStream_t stream = nullptr;
@@ -40,7 +46,24 @@ struct svo_desc_index {
     size_t part_cap = 0, outgrown_states = 0;
     int part_allocs = 0;
     std::vector<void*> outgrown;                      // earlier d_part buffers: hipFree waits for the whole device, so they go with the index
+    // svo_desc_index_enable_points: all null without
+    RelocPoint* d_points = nullptr;                   // [capacity]
+    float2* d_qxy = nullptr;                          // [MATCH_STAGE_ROWS] the queries' pixels
+    RelocDevOut* d_reloc = nullptr;                   // what k_reloc_select reports
+    RelocHost* h_reloc = nullptr;                     // pinned: the point rows of an upload, a call's state row and everything it reads back
 };
+
+// k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
+struct RelocDevOut { int32_t n_cand, pad[3]; int32_t cand_query[MATCH_STAGE_ROWS], cand_row[MATCH_STAGE_ROWS]; };
+struct RelocHost {
+    RelocPoint points[MATCH_STAGE_ROWS];
+    SeqState up, down;                                // the state row going in, and as k_pnp_final left it
+    RelocDevOut out;
+    uint8_t inlier[MATCH_STAGE_ROWS];
+    float cand_xy[MATCH_STAGE_ROWS * 2], cand_xyz[MATCH_STAGE_ROWS * 3];
+};
+static_assert(sizeof(RelocPoint) == 16, "a point row is 16 bytes");
+static_assert(MATCH_STAGE_ROWS == SVO_RELOC_MAX_QUERIES, "one staged search per relocalisation");
 
 static_assert(sizeof(svo_desc_match) == 32, "svo_desc_match is 32 bytes");
 
@@ -50,6 +73,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         if (x->stream) (void)hipStreamSynchronize(x->stream);
         for (hipEvent_t e : x->ev) if (e) (void)hipEventDestroy(e);
         for (void* p : x->outgrown) (void)hipFree(p);
+        (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
         (void)hipFree(x->d_part); (void)hipFree(x->d_out); (void)hipFree(x->d_query); (void)hipFree(x->d_ids); (void)hipFree(x->d_desc);
         (void)hipHostFree(x->h_out); (void)hipHostFree(x->h_stage);
         if (x->stream) (void)hipStreamDestroy(x->stream);
@@ -114,8 +138,8 @@ extern "C" int svo_desc_index_get_stats(const svo_desc_index* x, svo_desc_index_
     return SVO_OK;
 }
 
-extern "C" int svo_desc_index_add(svo_desc_index* x, int n, const uint8_t* desc, const uint64_t* ids, int* first_row) {
-    if (!x || n < 0 || (n > 0 && (!desc || !ids))) return fail(SVO_ERR_ARG, "svo_desc_index_add: bad index / n / desc / ids");
+// the append behind svo_desc_index_add (pts null) and svo_desc_index_add_points: on an index with points a row without one is SVO_POINT_NONE
+static int index_add(svo_desc_index* x, int n, const uint8_t* desc, const uint64_t* ids, const RelocPoint* pts, int* first_row) {
     if (n > x->capacity - x->size) return fail(SVO_ERR_ARG, "svo_desc_index_add: size + n exceeds the index's capacity (nothing was added)");
     if (first_row) *first_row = x->size;
     if (n == 0) return SVO_OK;
@@ -127,14 +151,58 @@ extern "C" int svo_desc_index_add(svo_desc_index* x, int n, const uint8_t* desc,
         memcpy(h_ids, ids + i0, m * sizeof(uint64_t));
         MHIP(hipMemcpyAsync(x->d_desc + at * SVO_DESC_BYTES, x->h_stage, m * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
         MHIP(hipMemcpyAsync(x->d_ids + at, h_ids, m * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
+        if (x->d_points) {
+            for (size_t i = 0; i < m; i++) x->h_reloc->points[i] = pts ? pts[i0 + i] : RelocPoint{0.f, 0.f, 0.f, SVO_POINT_NONE};
+            MHIP(hipMemcpyAsync(x->d_points + at, x->h_reloc->points, m * sizeof(RelocPoint), hipMemcpyHostToDevice, x->stream));
+        }
         MHIP(hipStreamSynchronize(x->stream));        // the staging is free again
     }
     x->size += n;
     return SVO_OK;
 }
 
-extern "C" int svo_desc_index_add_frame(svo_desc_index* x, svo_context* ctx, int seq, uint32_t need_flags, int* first_row, int* n_added) {
+extern "C" int svo_desc_index_add(svo_desc_index* x, int n, const uint8_t* desc, const uint64_t* ids, int* first_row) {
+    if (!x || n < 0 || (n > 0 && (!desc || !ids))) return fail(SVO_ERR_ARG, "svo_desc_index_add: bad index / n / desc / ids");
+    return index_add(x, n, desc, ids, nullptr, first_row);
+}
+
+extern "C" int svo_desc_index_enable_points(svo_desc_index* x) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (x->size != 0) return fail(SVO_ERR_STATE, "svo_desc_index_enable_points: the index already holds rows (points are enabled on an empty index)");
+    if (x->d_points) return SVO_OK;
+    MHIP(hipSetDevice(x->device));
+    MHIP(hipHostMalloc((void**)&x->h_reloc, sizeof(RelocHost), hipHostMallocDefault));
+    MHIP(hipMalloc((void**)&x->d_qxy, (size_t)MATCH_STAGE_ROWS * sizeof(float2)));
+    MHIP(hipMalloc((void**)&x->d_reloc, sizeof(RelocDevOut)));
+    MHIP(hipMalloc((void**)&x->d_points, (size_t)x->capacity * sizeof(RelocPoint)));   // last: d_points says "enabled"
+    return SVO_OK;
+}
+
+// the point rows of an append: finite coordinates, tags >= 0 (null: 0)
+static int make_points(int n, const float* xyz, const int32_t* tags, int32_t tag, std::vector<RelocPoint>& pts) {
+    pts.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int32_t t = tags ? tags[i] : tag;
+        if (t < 0) return fail(SVO_ERR_ARG, "a point's tag must be >= 0 (nothing was added)");
+        if (!isfinite(xyz[3 * i]) || !isfinite(xyz[3 * i + 1]) || !isfinite(xyz[3 * i + 2])) return fail(SVO_ERR_ARG, "a point has a non-finite coordinate (nothing was added)");
+        pts[(size_t)i] = RelocPoint{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], t};
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_add_points(svo_desc_index* x, int n, const uint8_t* desc, const uint64_t* ids, const float* xyz,
+                                         const int32_t* tags, int* first_row) {
+    if (!x || n < 0 || (n > 0 && (!desc || !ids || !xyz))) return fail(SVO_ERR_ARG, "svo_desc_index_add_points: bad index / n / desc / ids / xyz");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_add_points: the index has no points (svo_desc_index_enable_points)");
+    std::vector<RelocPoint> pts;
+    const int rc = make_points(n, xyz, tags, 0, pts);
+    if (rc != SVO_OK) return rc;
+    return index_add(x, n, desc, ids, pts.data(), first_row);
+}
+
+// svo_desc_index_add_frame (T null, no points) and svo_desc_index_add_frame_points (with_points: every row's xyz through T, or as it is)
+static int add_frame_rows(svo_desc_index* x, svo_context* ctx, int seq, uint32_t need_flags, bool with_points, const double* T, int32_t tag,
+                          int* first_row, int* n_added) {
     int n_tracks = 0;
     int rc = svo_get_last_track_descriptors(ctx, seq, 0, nullptr, &n_tracks);     // its refusals are this call's: context, seq, the frame's state
     if (rc < 0) return rc;
@@ -145,17 +213,39 @@ extern "C" int svo_desc_index_add_frame(svo_desc_index* x, svo_context* ctx, int
     rc = svo_get_last_track_descriptors(ctx, seq, n_obs, desc.data(), nullptr);
     if (rc < 0) return rc;
     std::vector<uint64_t> ids;
+    std::vector<float> xyz;
     int n = 0;
     for (int i = 0; i < rc; i++) {                    // the rows that carry need_flags, packed in row order
         if (((uint32_t)obs[i].flags & need_flags) != need_flags) continue;
         if (n != i) memcpy(&desc[(size_t)n * SVO_DESC_BYTES], &desc[(size_t)i * SVO_DESC_BYTES], SVO_DESC_BYTES);
         ids.push_back((uint64_t)obs[i].id);
+        if (with_points) {
+            float p[3] = {obs[i].xyz[0], obs[i].xyz[1], obs[i].xyz[2]};
+            if (T) reloc_map_point(T, obs[i].xyz, p);
+            xyz.insert(xyz.end(), p, p + 3);
+        }
         n++;
     }
     if (n_added) *n_added = 0;
-    rc = svo_desc_index_add(x, n, desc.data(), ids.data(), first_row);
+    std::vector<RelocPoint> pts;
+    if (with_points && (rc = make_points(n, xyz.data(), nullptr, tag, pts)) != SVO_OK) return rc;
+    rc = index_add(x, n, desc.data(), ids.data(), with_points ? pts.data() : nullptr, first_row);
     if (rc == SVO_OK && n_added) *n_added = n;
     return rc;
+}
+
+extern "C" int svo_desc_index_add_frame(svo_desc_index* x, svo_context* ctx, int seq, uint32_t need_flags, int* first_row, int* n_added) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    return add_frame_rows(x, ctx, seq, need_flags, false, nullptr, 0, first_row, n_added);
+}
+
+extern "C" int svo_desc_index_add_frame_points(svo_desc_index* x, svo_context* ctx, int seq, uint32_t need_flags, const double* cam_to_map,
+                                               int32_t tag, int* first_row, int* n_added) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_add_frame_points: the index has no points (svo_desc_index_enable_points)");
+    if (tag < 0) return fail(SVO_ERR_ARG, "svo_desc_index_add_frame_points: the tag must be >= 0");
+    if (cam_to_map) for (int i = 0; i < 16; i++) if (!isfinite(cam_to_map[i])) return fail(SVO_ERR_ARG, "svo_desc_index_add_frame_points: cam_to_map has a non-finite entry");
+    return add_frame_rows(x, ctx, seq, need_flags | SVO_OBS_HAS_XYZ, true, cam_to_map, tag, first_row, n_added);
 }
 
 // Room for `need` partial states.  The scratch at least doubles whenever it grows (from MATCH_PART_FIRST), so an index whose searches
@@ -174,14 +264,8 @@ static int part_room(svo_desc_index* x, size_t need) {
     return SVO_OK;
 }
 
-extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* query, int row_lo, int row_hi, svo_desc_match* out) {
-    if (!x || n < 0 || (n > 0 && (!query || !out))) return fail(SVO_ERR_ARG, "svo_desc_index_match: bad index / n / query / out");
-    if (row_hi == -1) row_hi = x->size;
-    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "svo_desc_index_match: the row range must satisfy 0 <= row_lo <= row_hi <= size");
-    x->last_ms = 0.f;
-    if (n == 0) return SVO_OK;
-    MHIP(hipSetDevice(x->device));
-    const MatchRange r = match_range(row_lo, row_hi, x->chunk_rows);
+// the queries of one launch of a search of n queries over r, and the scratch's room for it: the partial-state budget decides
+static int match_batch(svo_desc_index* x, int n, const MatchRange& r, size_t* out) {
     size_t batch = MATCH_STAGE_ROWS;
     if (r.n_chunks > 0) {
         size_t fit = MATCH_PART_BUDGET / (size_t)r.n_chunks / 64 * 64;
@@ -191,6 +275,21 @@ extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* que
         const int rc = part_room(x, batch * (size_t)r.n_chunks);
         if (rc != SVO_OK) return rc;
     }
+    *out = batch;
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* query, int row_lo, int row_hi, svo_desc_match* out) {
+    if (!x || n < 0 || (n > 0 && (!query || !out))) return fail(SVO_ERR_ARG, "svo_desc_index_match: bad index / n / query / out");
+    if (row_hi == -1) row_hi = x->size;
+    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "svo_desc_index_match: the row range must satisfy 0 <= row_lo <= row_hi <= size");
+    x->last_ms = 0.f;
+    if (n == 0) return SVO_OK;
+    MHIP(hipSetDevice(x->device));
+    const MatchRange r = match_range(row_lo, row_hi, x->chunk_rows);
+    size_t batch = 0;
+    const int rc = match_batch(x, n, r, &batch);
+    if (rc != SVO_OK) return rc;
     for (size_t i0 = 0; i0 < (size_t)n; i0 += batch) {
         const int m = (int)((size_t)n - i0 < batch ? (size_t)n - i0 : batch);
         memcpy(x->h_stage, query + i0 * SVO_DESC_BYTES, (size_t)m * SVO_DESC_BYTES);
@@ -210,4 +309,108 @@ extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* que
         }
     }
     return SVO_OK;
+}
+
+// ---- the relocaliser (include/svo.h, "Relocalisation") ----
+extern "C" void svo_reloc_params_default(svo_reloc_params* p) {
+    if (!p) return;
+    svo_config cfg; svo_config_default(&cfg);
+    p->row_lo = 0; p->row_hi = -1; p->max_dist = 40; p->ratio_num = 7; p->ratio_den = 10; p->min_candidates = 6;
+    p->ransac_iterations = cfg.ransac_iterations; p->reproj_error = cfg.ransac_reprojection_error; p->confidence = cfg.ransac_confidence;
+}
+
+// What select and localize share.  Everything is enqueued on the index's stream — the uploads, the search (as many launches as the
+// partial-state budget asks for, back to back, the queries uploaded once), k_reloc_select, the PnP kernels when K is given, the
+// copies back — and the host waits once.  K == nullptr: the selection alone.
+static int reloc_run(svo_desc_index* x, const float* K, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
+                     svo_reloc_result* res, int* n_candidates, int32_t* cand_query, int32_t* cand_row, uint8_t* cand_inlier,
+                     float* cand_xy, float* cand_xyz) {
+    if (!x || !p || n < 0 || (n > 0 && !query)) return fail(SVO_ERR_ARG, "relocalisation: bad index / params / n / query");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "relocalisation: the index has no points (svo_desc_index_enable_points)");
+    if (n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "relocalisation: at most 4096 queries per call");
+    if (n > 0 && !xy && (K || cand_xy)) return fail(SVO_ERR_ARG, "relocalisation: null xy");
+    int row_lo = p->row_lo, row_hi = p->row_hi == -1 ? x->size : p->row_hi;
+    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "relocalisation: the row range must satisfy 0 <= row_lo <= row_hi <= size");
+    if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
+    if (p->ratio_num < 1 || p->ratio_num > SVO_RELOC_MAX_RATIO || p->ratio_den < 1 || p->ratio_den > SVO_RELOC_MAX_RATIO)
+        return fail(SVO_ERR_ARG, "relocalisation: ratio_num and ratio_den must be 1 .. 1 << 20");
+    if (p->min_candidates < 6) return fail(SVO_ERR_ARG, "relocalisation: min_candidates must be >= 6 (4 and 5 points take svo_camera_to_world's direct routes)");
+    x->last_ms = 0.f;
+    MHIP(hipSetDevice(x->device));
+    const DevBuffers* d = nullptr;
+    int rc = svo_reloc_stage_ctx(x->device, n > 64 ? n : 64, p->ransac_iterations, p->reproj_error, p->confidence, &d);
+    if (rc != SVO_OK) return rc;
+    const MatchRange r = match_range(row_lo, row_hi, x->chunk_rows);
+    size_t batch = 0;
+    if ((rc = match_batch(x, n, r, &batch)) != SVO_OK) return rc;
+    RelocHost* h = x->h_reloc;
+    float* h_xy = (float*)(x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES);   // the ids' part of the staging: 8 bytes a row
+    if (n > 0) {
+        memcpy(x->h_stage, query, (size_t)n * SVO_DESC_BYTES);
+        if (xy) memcpy(h_xy, xy, (size_t)n * sizeof(float2)); else memset(h_xy, 0, (size_t)n * sizeof(float2));
+        MHIP(hipMemcpyAsync(x->d_query, x->h_stage, (size_t)n * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
+        MHIP(hipMemcpyAsync(x->d_qxy, h_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, x->stream));
+    }
+    if (K) {                                          // the state row as svo_camera_to_world sets it; k_reloc_select fills in the count
+        SeqState& hs = h->up;
+        memset(&hs, 0, sizeof(hs));
+        hs.active = 1; hs.fail_reason = 0; hs.feat_buf = 0;
+        memcpy(hs.K, K, sizeof(float) * 9); memcpy(hs.R, res->R, sizeof(double) * 9); memcpy(hs.t, res->t, sizeof(double) * 3);
+        MHIP(hipMemcpyAsync(d->st, &hs, sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
+    }
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += batch) {  // batch is a multiple of 64 rows, or all of them
+        const int m = (int)((size_t)n - i0 < batch ? (size_t)n - i0 : batch);
+        launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, (const uint32_t*)(x->d_query + i0 * SVO_DESC_BYTES), m, r, x->d_part, x->stream);
+        launch_desc_match_merge(x->d_part, x->d_ids, m, r, x->d_out + i0, x->stream);
+    }
+    RelocArgs a;
+    a.match = x->d_out; a.points = x->d_points; a.xy = x->d_qxy; a.n = n;
+    a.rule = RelocRule{p->max_dist, p->ratio_num, p->ratio_den}; a.min_candidates = p->min_candidates;
+    a.out_xy = d->tl1; a.out_xyz = d->world; a.st = d->st;
+    a.cand_query = x->d_reloc->cand_query; a.cand_row = x->d_reloc->cand_row; a.n_cand = &x->d_reloc->n_cand;
+    if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
+    launch_reloc_select(a, x->stream);
+    if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
+    if (K) { launch_pnp_subsets(*d, x->stream); launch_pnp(*d, x->stream); }
+    MHIP(hipGetLastError());
+    MHIP(hipMemcpyAsync(&h->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+    if (n > 0) {
+        MHIP(hipMemcpyAsync(h->out.cand_row, x->d_reloc->cand_row, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        if (cand_xy) MHIP(hipMemcpyAsync(h->cand_xy, d->tl1, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
+        if (cand_xyz) MHIP(hipMemcpyAsync(h->cand_xyz, d->world, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+        if (K) MHIP(hipMemcpyAsync(h->inlier, d->inlier, (size_t)n, hipMemcpyDeviceToHost, x->stream));
+    }
+    if (K) MHIP(hipMemcpyAsync(&h->down, d->st, sizeof(SeqState), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
+    if (x->timing) MHIP(hipEventElapsedTime(&x->last_ms, x->ev[0], x->ev[1]));
+    const int nc = h->out.n_cand;
+    if (n_candidates) *n_candidates = nc;
+    if (cand_query) memcpy(cand_query, h->out.cand_query, (size_t)nc * sizeof(int32_t));
+    if (cand_row) memcpy(cand_row, h->out.cand_row, (size_t)nc * sizeof(int32_t));
+    if (cand_xy) memcpy(cand_xy, h->cand_xy, (size_t)nc * sizeof(float2));
+    if (cand_xyz) memcpy(cand_xyz, h->cand_xyz, (size_t)nc * 3 * sizeof(float));
+    if (!K) return SVO_OK;
+    const SeqState& hs = h->down;
+    res->success = 0; res->n_candidates = nc; res->n_inliers = 0; res->iters_run = 0;
+    memset(res->T, 0, sizeof(res->T));
+    if (cand_inlier) memset(cand_inlier, 0, (size_t)nc);
+    if (nc < p->min_candidates) return SVO_OK;        // rule 4: every PnP kernel found the row not live
+    res->iters_run = hs.pnp_iters;
+    if (hs.pnp_best < 0) return SVO_OK;               // no pose: R, t untouched, as svo_camera_to_world leaves them
+    memcpy(res->R, hs.R, sizeof(double) * 9); memcpy(res->t, hs.t, sizeof(double) * 3); memcpy(res->T, hs.last_T, sizeof(double) * 16);
+    res->success = 1; res->n_inliers = hs.n_inliers;
+    if (cand_inlier) memcpy(cand_inlier, h->inlier, (size_t)nc);
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_select(svo_desc_index* x, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
+                                     int* n_candidates, int32_t* cand_query, int32_t* cand_row, float* cand_xy, float* cand_xyz) {
+    return reloc_run(x, nullptr, n, query, xy, p, nullptr, n_candidates, cand_query, cand_row, nullptr, cand_xy, cand_xyz);
+}
+
+extern "C" int svo_desc_index_localize(svo_desc_index* x, const float K[9], int n, const uint8_t* query, const float* xy,
+                                       const svo_reloc_params* p, svo_reloc_result* res, int32_t* cand_query, int32_t* cand_row,
+                                       uint8_t* cand_inlier) {
+    if (!K || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize: null K / result");
+    return reloc_run(x, K, n, query, xy, p, res, nullptr, cand_query, cand_row, cand_inlier, nullptr, nullptr);
 }

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""What a relocalisation costs (include/svo.h, "Relocalisation"), against the path it replaces on the same library:
+
+    python tools/reloc_bench.py [--out FILE] [--sizes 65536,1048576] [--queries 2048] [--rounds 15]
+
+Per index size: an index of random rows with points in which the first --queries rows are landmarks of a scene
+(tests/reloc_cases.py: exact projections, an eighth of the pixels moved), and the queries are those rows' descriptors with three bits
+flipped.  Timed in alternating rounds, medians reported:
+  localize   one svo_desc_index_localize call;
+  by hand    svo_desc_index_match, then the host filter INTEGRATION.md used to describe (threshold, ratio, one pixel per landmark, the
+             points from a host-side mirror of the rows; vectorised numpy), then svo_camera_to_world.
+Both paths must return the same pose bits before anything is timed.  Then the device time of k_reloc_select alone (HIP events around
+it: svo_desc_index_set_timing) on that input, and on the dedupe's worst case: 4096 queries, all accepted, all of different
+landmarks.  One child python per index size, one after the other, each under its own time limit; the first failure ends the run.
+Prints one JSON line."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def host_filter(m, xy, xyz, max_dist=40, num=7, den=10):
+    """rules 1 - 3 on the host from the match rows and a mirror of the points -> (pixels, points) of the candidates"""
+    ok = (m["row"] >= 0) & (m["dist"] <= max_dist) & (m["dist"].astype(np.int64) * den < m["dist2"].astype(np.int64) * num)
+    j = np.flatnonzero(ok)
+    order = np.lexsort((j, m["dist"][j], m["id"][j]))             # per id the smallest (dist, j) first
+    first = np.ones(len(j), bool)
+    first[1:] = m["id"][j][order][1:] != m["id"][j][order][:-1]
+    keep = np.sort(j[order][first])
+    return xy[keep], xyz[m["row"][keep]]
+
+
+def child(size, n, rounds):
+    import reloc_cases as cases
+    from stereo_visual_odometry_amd import api
+    s = cases.scene(n, size, outliers=n // 8)
+    rng = np.random.default_rng(size)
+    ix = api.DescriptorIndex(size, points=True)
+    ix.add_points(s["desc"], s["ids"], s["xyz"], s["tags"])
+    rest = size - n
+    mirror, head = [s["xyz"]], [s["desc"]]                        # head: the descriptors of the index's first rows, for the worst case below
+    for i0 in range(0, rest, 1 << 16):
+        m = min(1 << 16, rest - i0)
+        p, d = rng.normal(size=(m, 3)).astype(np.float32), rng.integers(0, 256, (m, 32), dtype=np.uint8)
+        ix.add_points(d, (1 << 32) + i0 + np.arange(m, dtype=np.uint64), p)
+        mirror.append(p)
+        if i0 == 0:
+            head.append(d)
+    xyz = np.concatenate(mirror)
+    prm = ix.reloc_params()
+
+    def by_hand():
+        cxy, cxyz = host_filter(ix.match(s["query"]), s["xy"], xyz)
+        return api.cameraToWorld(s["K"], cxy, cxyz, np.eye(3), np.zeros(3), prm.ransac_iterations, prm.reproj_error, prm.confidence), len(cxy)
+
+    def localize():
+        return ix.localize(s["K"], s["query"], s["xy"], params=prm)
+
+    for _ in range(3):
+        ((inl, ok), R, t, iters), k = by_hand()
+        res, cand = localize()
+    assert ok and res.success and res.n_candidates == k and res.R.tobytes() == R.tobytes() and res.t.tobytes() == t.tobytes(), "the two paths differ"
+    t_loc, t_hand = [], []
+    for _ in range(rounds):
+        t0 = time.perf_counter(); localize(); t_loc.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter(); by_hand(); t_hand.append((time.perf_counter() - t0) * 1e3)
+    ix.set_timing(True)
+    kern = []
+    for _ in range(rounds):
+        ix.select(s["query"], s["xy"], params=prm)
+        kern.append(ix.stats()["last_kernels_ms"])
+    r = dict(size=size, queries=n, rounds=rounds, candidates=k, inliers=int(res.n_inliers), iters_run=int(res.iters_run),
+             localize_ms_median=float(np.median(t_loc)), localize_ms_min=float(min(t_loc)),
+             by_hand_ms_median=float(np.median(t_hand)), by_hand_ms_min=float(min(t_hand)),
+             select_kernel_ms_median=float(np.median(kern)), select_kernel_ms_min=float(min(kern)))
+    all_desc = np.concatenate(head)[:4096]
+    if len(all_desc) == 4096:                                     # the dedupe's worst case: the first 4096 rows found again, all accepted, all distinct
+        wide = ix.reloc_params(max_dist=256, ratio_num=1 << 20, ratio_den=1, row_lo=0, row_hi=4096)
+        kern = []
+        for _ in range(rounds):
+            got = ix.select(all_desc, np.zeros((4096, 2), np.float32), params=wide)
+            kern.append(ix.stats()["last_kernels_ms"])
+        assert len(got["query"]) == 4096, len(got["query"])
+        r.update(worst_case_candidates=4096, worst_case_select_kernel_ms_median=float(np.median(kern)), worst_case_select_kernel_ms_min=float(min(kern)))
+    ix.close()
+    print(json.dumps(r))
+
+
+def step(cmd, limit, what):
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
+    if r.returncode != 0:
+        raise SystemExit("%s failed (exit status %s):\n%s\n%s" % (what, r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+    lines = r.stdout.strip().splitlines()
+    return lines[-1] if lines else ""
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="65536,1048576")
+    ap.add_argument("--queries", type=int, default=2048)
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child is not None:
+        return child(args.child, args.queries, args.rounds)
+    out = dict(shape="%d queries of a scene inside an index of random rows with points; alternating rounds" % args.queries, sizes=[])
+    for s in (int(x) for x in args.sizes.split(",")):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", str(s), "--queries", str(args.queries), "--rounds", str(args.rounds)]
+        out["sizes"].append(json.loads(step(cmd, 400, "the relocalisation at %d rows" % s)))
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
