@@ -532,7 +532,9 @@ int svo_desc_index_get_chunk_rows(const svo_desc_index* index);
  * synchronisation; off (the default) a search records nothing.  svo_desc_index_get_stats: the device time of the last search's
  * kernels in milliseconds (summed over its launches, the copies not in it; 0 with timing off or when nothing was launched), how
  * often the scratch was allocated, its size, and the bytes of the buffers it has outgrown.  After svo_desc_index_select or
- * svo_desc_index_localize with timing on, last_kernels_ms is the device time of the selection kernel alone. */
+ * svo_desc_index_localize with timing on, last_kernels_ms is the device time of the selection kernel alone.  After a guided call
+ * ("Guided search") with timing on it is the device time of the projection kernel plus the guided search kernels (after
+ * svo_desc_index_project: the projection kernel alone). */
 typedef struct {
     float    last_kernels_ms;
     int32_t  scratch_allocations;
@@ -602,6 +604,64 @@ int svo_desc_index_select(svo_desc_index* index, int n, const uint8_t* query, co
 int svo_desc_index_localize(svo_desc_index* index, const float K[9], int n, const uint8_t* query, const float* xy,
                             const svo_reloc_params* params, svo_reloc_result* result, int32_t* cand_query, int32_t* cand_row,
                             uint8_t* cand_inlier);
+
+/* ---- Guided search: search only where a pose prior projects ---------------------------------------------------------------------
+ * A camera that tracks in a map knows roughly where it is: the last map pose composed with the frame's odometry, or a loop closer's
+ * hypothesis.  The calls below project the index's points with that prior and match each query only against the rows that land near
+ * its pixel (what ORB-SLAM's SearchByProjection does).  The search is cheaper, and in repeated structure — two landmarks that look
+ * alike — dist2 becomes the nearest OTHER landmark that could be at this pixel, so the ratio test of "Relocalisation" works where the
+ * unguided one rejects every correct match.  A second family beside the unguided calls, which are unchanged.
+ *
+ * A guide is a pose prior x_cam = R X_map + t (the convention of svo_reloc_result) and a radius in pixels.  K is the call's 3 x 3
+ * camera matrix; the projection uses K[0], K[2], K[4] and K[5] only (fx, cx, fy, cy), widened to f64.  The PnP still gets all of K.
+ *  1. Projection of row r with point (x, y, z) and tag, in f64, every product, quotient and sum rounded on its own (no contraction),
+ *     left to right as in svo_desc_index_add_frame_points:
+ *       Xc = ((R0 x + R1 y) + R2 z) + t0,   Yc likewise with R3, R4, R5, t1,   Zc with R6, R7, R8, t2;
+ *       u = f32(fx (Xc / Zc) + cx),   v = f32(fy (Yc / Zc) + cy).
+ *     The row is VISIBLE when its tag is not SVO_POINT_NONE, Zc > 0 strictly, and u and v are both finite after the rounding to f32.
+ *     An invisible row's projection is (+inf, +inf).
+ *  2. Gate.  Row r is ADMISSIBLE for query j with pixel (x_j, y_j) when |u_r - x_j| <= radius and |v_r - y_j| <= radius; the
+ *     subtractions, absolute values and comparisons are f32 and both limits are inclusive.  An invisible row is admissible for
+ *     nobody; a query with a non-finite pixel admits nothing (inf - inf is NaN and the comparison fails).
+ *  3. Search.  svo_desc_index_match's definition over the admissible rows of [row_lo, row_hi) only: best by (dist, row), second =
+ *     the best admissible row of another id.  No admissible row: SVO_MATCH_NONE and SVO_MATCH_NO_DIST, as for an empty range.
+ *  4. Selection and PnP.  Rules 1 - 4 of "Relocalisation", unchanged, on those result rows.
+ * The results do not depend on the chunk size, on the order in which the library visits the queries, or on anything else internal.
+ *
+ * Every call is synchronous, waits for the index's own stream only, is legal with frames in flight and synchronises once.  The
+ * projection runs on every call — nothing is cached between calls — into a device array of capacity x 8 bytes that the index
+ * allocates at its first guided call and frees with the index (with 32 KiB for the queries' order, below).  A guided search is one
+ * launch over all its queries: where queries x pieces would exceed the scratch's 64 MiB budget (svo_desc_index_set_chunk_rows) the
+ * rows of a piece double until it fits.
+ * SVO_ERR_ARG: radius negative or not finite; a non-finite entry of R, t or K; n > SVO_RELOC_MAX_QUERIES (the guided match too: it
+ * shares the 4096-row pixel staging); a NULL K or guide; and the refusals of the unguided call of the same name.  SVO_ERR_STATE: an
+ * index without points. */
+typedef struct {
+    double  R[9], t[3];          /* the prior: x_cam = R X_map + t */
+    float   radius;              /* rule 2, in pixels: finite, >= 0 */
+    int32_t reserved;            /* 0 */
+} svo_reloc_guide;
+/* Rule 1 alone, the stage on its own (as svo_describe_points is for the descriptors): uv (host) receives (row_hi - row_lo) x 2
+ * floats, the projections of rows [row_lo, row_hi); row_hi = -1: the index's size.  The radius is checked and not used. */
+int svo_desc_index_project(svo_desc_index* index, const float K[9], const svo_reloc_guide* guide, int row_lo, int row_hi, float* uv);
+/* Rules 1 - 3: svo_desc_index_match with a pixel per query (xy: n x 2 floats) and the gate.  n <= SVO_RELOC_MAX_QUERIES. */
+int svo_desc_index_match_guided(svo_desc_index* index, const float K[9], const svo_reloc_guide* guide, int n, const uint8_t* query,
+                                const float* xy, int row_lo, int row_hi, svo_desc_match* out);
+/* svo_desc_index_select and svo_desc_index_localize over the guided search; xy is required.  result->R, t going in remain the PnP's
+ * extrinsic guess and are not tied to the guide — passing the guide's R, t is the usual choice.  For the arrays
+ * svo_desc_index_select_guided returns, svo_desc_index_localize_guided equals svo_camera_to_world in every bit, as
+ * svo_desc_index_localize does for svo_desc_index_select's. */
+int svo_desc_index_select_guided(svo_desc_index* index, const float K[9], const svo_reloc_guide* guide, int n, const uint8_t* query,
+                                 const float* xy, const svo_reloc_params* params, int* n_candidates, int32_t* cand_query,
+                                 int32_t* cand_row, float* cand_xy, float* cand_xyz);
+int svo_desc_index_localize_guided(svo_desc_index* index, const float K[9], const svo_reloc_guide* guide, int n, const uint8_t* query,
+                                   const float* xy, const svo_reloc_params* params, svo_reloc_result* result, int32_t* cand_query,
+                                   int32_t* cand_row, uint8_t* cand_inlier);
+/* Tuning and diagnostics.  A wave of the guided search serves 64 queries and skips a row that none of them admits, which pays when
+ * the 64 sit close together in the image: the library sorts a call's queries by image cell (side 2 x radius, cells in raster order,
+ * ties by j) and lets lane `slot` serve the slot-th query of that order; everything it returns is under the queries' own numbers.
+ * on = 0 serves the queries in the caller's order instead (default: on).  The results do not depend on it. */
+int svo_desc_index_set_guided_sort(svo_desc_index* index, int on);
 
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.

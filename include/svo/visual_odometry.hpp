@@ -560,6 +560,53 @@ class DescriptorIndex {
         if (candidates) *candidates = std::move(c);
         return result;
     }
+    // ---- guided search (svo.h, "Guided search"): the same calls over the rows a pose prior projects near each query's pixel
+    // a guide from the prior x_cam = R X_map + t (row-major 3 x 3, 3) and the gate's radius in pixels
+    static svo_reloc_guide guide(const double R[9], const double t[3], float radius) {
+        svo_reloc_guide g;
+        for (int i = 0; i < 9; i++) g.R[i] = R[i];
+        for (int i = 0; i < 3; i++) g.t[i] = t[i];
+        g.radius = radius; g.reserved = 0;
+        return g;
+    }
+    // the projections of rows [row_lo, row_hi) with the prior, 2 floats per row; an invisible row is (+inf, +inf)
+    std::vector<float> project(const float K[9], const svo_reloc_guide& g, int row_lo = 0, int row_hi = -1) {
+        const int hi = row_hi == -1 ? size() : row_hi;
+        std::vector<float> uv(2 * (size_t)(hi > row_lo ? hi - row_lo : 0));
+        svo_throw(svo_desc_index_project(index_, K, &g, row_lo, row_hi, uv.data()));
+        return uv;
+    }
+    std::vector<svo_desc_match> match_guided(const float K[9], const svo_reloc_guide& g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
+                                             int row_lo = 0, int row_hi = -1) {
+        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::match_guided: one pixel per query expected");
+        std::vector<svo_desc_match> out(query.size());
+        svo_throw(svo_desc_index_match_guided(index_, K, &g, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), row_lo, row_hi, out.data()));
+        return out;
+    }
+    Candidates select_guided(const float K[9], const svo_reloc_guide& g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
+                             const svo_reloc_params& params) {
+        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::select_guided: one pixel per query expected");
+        Candidates c;
+        c.query.resize(query.size()); c.row.resize(query.size());
+        int k = 0;
+        svo_throw(svo_desc_index_select_guided(index_, K, &g, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &k,
+                                               c.query.data(), c.row.data(), nullptr, nullptr));
+        c.query.resize((size_t)k); c.row.resize((size_t)k);
+        return c;
+    }
+    // result.R, t: the PnP's guess going in — the guide's R, t is the usual choice
+    svo_reloc_result localize_guided(const float K[9], const svo_reloc_guide& g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
+                                     const svo_reloc_params& params, svo_reloc_result result, Candidates* candidates = nullptr) {
+        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::localize_guided: one pixel per query expected");
+        Candidates c;
+        c.query.resize(query.size()); c.row.resize(query.size()); c.inlier.resize(query.size());
+        svo_throw(svo_desc_index_localize_guided(index_, K, &g, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &result,
+                                                 c.query.data(), c.row.data(), c.inlier.data()));
+        c.query.resize((size_t)result.n_candidates); c.row.resize((size_t)result.n_candidates); c.inlier.resize((size_t)result.n_candidates);
+        if (candidates) *candidates = std::move(c);
+        return result;
+    }
+    void set_guided_sort(bool on) { svo_throw(svo_desc_index_set_guided_sort(index_, on ? 1 : 0)); }
     int size() const { return svo_desc_index_size(index_); }
     void truncate(int n_rows) { svo_throw(svo_desc_index_truncate(index_, n_rows)); }
     svo_desc_index* handle() { return index_; }

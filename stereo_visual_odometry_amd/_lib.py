@@ -176,6 +176,25 @@ lib.svo_desc_index_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_
 lib.svo_desc_index_localize.restype = C.c_int
 lib.svo_desc_index_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
                                         C.POINTER(SvoRelocResult), C.c_void_p, C.c_void_p, C.c_void_p]
+# guided search (svo.h, "Guided search"): the same calls behind a pose prior's projection gate
+
+
+class SvoRelocGuide(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("radius", C.c_float), ("reserved", C.c_int32)]
+
+
+lib.svo_desc_index_project.restype = C.c_int
+lib.svo_desc_index_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_int, C.c_void_p]
+lib.svo_desc_index_match_guided.restype = C.c_int
+lib.svo_desc_index_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+lib.svo_desc_index_select_guided.restype = C.c_int
+lib.svo_desc_index_select_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
+                                             C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_desc_index_localize_guided.restype = C.c_int
+lib.svo_desc_index_localize_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
+                                               C.POINTER(SvoRelocResult), C.c_void_p, C.c_void_p, C.c_void_p]
+lib.svo_desc_index_set_guided_sort.restype = C.c_int
+lib.svo_desc_index_set_guided_sort.argtypes = [C.c_void_p, C.c_int]
 # motion priors (svo.h): H / Hi are 9 float32 each (n_seq x 9 in the batch setter), has n_seq bytes; R is 9 float64
 PATH_MOTION_PRIOR = 2048
 lib.svo_set_motion_prior.restype = C.c_int
@@ -287,6 +306,8 @@ EXPORTS = [
     "svo_desc_index_set_timing", "svo_desc_index_get_stats",
     "svo_reloc_params_default", "svo_desc_index_enable_points", "svo_desc_index_add_points", "svo_desc_index_add_frame_points",
     "svo_desc_index_select", "svo_desc_index_localize",
+    "svo_desc_index_project", "svo_desc_index_match_guided", "svo_desc_index_select_guided", "svo_desc_index_localize_guided",
+    "svo_desc_index_set_guided_sort",
 ]
 
 

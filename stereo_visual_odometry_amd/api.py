@@ -453,6 +453,79 @@ class DescriptorIndex:
                           np.array(res.T[:]).reshape(4, 4))
         return rec, dict(query=cq[:k].copy(), row=cr[:k].copy(), inlier=ci[:k].astype(bool))
 
+    # ---- guided search (svo.h, "Guided search"): the same calls behind the projection gate of a pose prior
+    @staticmethod
+    def _K9(K):
+        return np.ascontiguousarray(np.asarray(K, np.float32).reshape(-1)[:9]) if np.size(K) == 9 else \
+            np.ascontiguousarray(np.asarray(K, np.float32)[:3, :3]).reshape(9)
+
+    @staticmethod
+    def guide(R, t, radius):
+        """svo_reloc_guide: the prior x_cam = R X_map + t (R (3, 3), t 3 values, float64) and the gate's radius in pixels"""
+        g = _lib.SvoRelocGuide()
+        g.R[:] = list(np.asarray(R, np.float64).reshape(9))
+        g.t[:] = list(np.asarray(t, np.float64).reshape(3))
+        g.radius = float(radius)
+        return g
+
+    def set_guided_sort(self, on=True):
+        """tuning: serve a guided call's queries in image-cell order (the default) or in the caller's; the results do not depend on it"""
+        check(lib.svo_desc_index_set_guided_sort(self._h, int(bool(on))))
+
+    def project(self, K, R, t, row_lo=0, row_hi=-1):
+        """The projections of the rows [row_lo, row_hi) with the prior (svo_desc_index_project) -> (m, 2) float32; an invisible row
+        (no point, not in front of the camera, not finite in float32) is (+inf, +inf)."""
+        hi = self.size if row_hi == -1 else int(row_hi)
+        uv = np.zeros((max(hi - int(row_lo), 0), 2), np.float32)
+        g = self.guide(R, t, 0.0)
+        Kf = self._K9(K)
+        check(lib.svo_desc_index_project(self._h, ptr(Kf), C.byref(g), int(row_lo), int(row_hi), ptr(uv)))
+        return uv
+
+    def match_guided(self, K, R, t, radius, query, xy, row_lo=0, row_hi=-1):
+        """match over the rows whose projection lies within radius pixels (per axis, inclusive) of the query's pixel
+        (svo_desc_index_match_guided) -> the structured rows match returns"""
+        q, p = self._queries(query, xy)
+        out = np.zeros(len(q), _lib.DESC_MATCH_DTYPE)
+        g = self.guide(R, t, radius)
+        Kf = self._K9(K)
+        check(lib.svo_desc_index_match_guided(self._h, ptr(Kf), C.byref(g), len(q), ptr(q), ptr(p), int(row_lo), int(row_hi), ptr(out)))
+        return out
+
+    def select_guided(self, K, R, t, radius, query, xy, params=None, **over):
+        """select over the guided search (svo_desc_index_select_guided) -> the dict select returns"""
+        q, p = self._queries(query, xy)
+        prm = params if params is not None else self.reloc_params(**over)
+        n = len(q)
+        cq, cr = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        cxy, cxyz = np.zeros((max(n, 1), 2), np.float32), np.zeros((max(n, 1), 3), np.float32)
+        k = C.c_int(0)
+        g = self.guide(R, t, radius)
+        Kf = self._K9(K)
+        check(lib.svo_desc_index_select_guided(self._h, ptr(Kf), C.byref(g), n, ptr(q), ptr(p), C.byref(prm), C.byref(k), ptr(cq), ptr(cr),
+                                               ptr(cxy), ptr(cxyz)))
+        k = k.value
+        return dict(query=cq[:k].copy(), row=cr[:k].copy(), xy=cxy[:k].copy(), xyz=cxyz[:k].copy())
+
+    def localize_guided(self, K, R, t, radius, query, xy, rotation=None, translation=None, params=None, **over):
+        """localize over the guided search (svo_desc_index_localize_guided) -> what localize returns.  rotation, translation: the
+        PnP's extrinsic guess; None: the guide's R, t, the usual choice."""
+        q, p = self._queries(query, xy)
+        prm = params if params is not None else self.reloc_params(**over)
+        res = _lib.SvoRelocResult()
+        res.R[:] = list(np.asarray(R if rotation is None else rotation, np.float64).reshape(9))
+        res.t[:] = list(np.asarray(t if translation is None else translation, np.float64).reshape(3))
+        n = len(q)
+        cq, cr, ci = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        g = self.guide(R, t, radius)
+        Kf = self._K9(K)
+        check(lib.svo_desc_index_localize_guided(self._h, ptr(Kf), C.byref(g), n, ptr(q), ptr(p), C.byref(prm), C.byref(res), ptr(cq), ptr(cr),
+                                                 ptr(ci)))
+        k = res.n_candidates
+        rec = RelocResult(bool(res.success), k, res.n_inliers, res.iters_run, np.array(res.R[:]).reshape(3, 3), np.array(res.t[:]).reshape(3, 1),
+                          np.array(res.T[:]).reshape(4, 4))
+        return rec, dict(query=cq[:k].copy(), row=cr[:k].copy(), inlier=ci[:k].astype(bool))
+
     @staticmethod
     def _rows(desc, what):
         d = np.ascontiguousarray(desc, dtype=np.uint8)

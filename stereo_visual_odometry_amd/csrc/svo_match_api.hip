@@ -3,7 +3,10 @@
 // stream alone, so they are legal beside any context's frames in flight.  The kernels are in svo_kernels_match.hip.
 // The relocaliser (include/svo.h, "Relocalisation") is here too: the points of an index, and select / localize, which put the search,
 // k_reloc_select (svo_kernels_reloc.hip) and the RANSAC-PnP kernels on the index's stream and wait once.
-#include "svo_reloc_internal.hpp"
+// And the guided search (include/svo.h, "Guided search"): project, match_guided, and select / localize with a guide, which put
+// k_guide_project and k_desc_match_guided (svo_kernels_guide.hip) where the unguided calls put k_desc_match.
+#include "svo_guide_internal.hpp"
+#include <algorithm>
 #include <math.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -51,6 +54,11 @@ struct svo_desc_index {
     float2* d_qxy = nullptr;                          // [MATCH_STAGE_ROWS] the queries' pixels
     RelocDevOut* d_reloc = nullptr;                   // what k_reloc_select reports
     RelocHost* h_reloc = nullptr;                     // pinned: the point rows of an upload, a call's state row and everything it reads back
+    // the guided search: all null until the first guided call (guide_room)
+    float2* d_uv = nullptr;                           // [capacity] the rows' projections of the call in progress
+    int32_t* d_order = nullptr;                       // [MATCH_STAGE_ROWS] the query each lane slot serves
+    int32_t* h_order = nullptr;                       // pinned, likewise
+    bool guided_sort = true;                          // svo_desc_index_set_guided_sort
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -73,6 +81,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         if (x->stream) (void)hipStreamSynchronize(x->stream);
         for (hipEvent_t e : x->ev) if (e) (void)hipEventDestroy(e);
         for (void* p : x->outgrown) (void)hipFree(p);
+        (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
         (void)hipFree(x->d_part); (void)hipFree(x->d_out); (void)hipFree(x->d_query); (void)hipFree(x->d_ids); (void)hipFree(x->d_desc);
         (void)hipHostFree(x->h_out); (void)hipHostFree(x->h_stage);
@@ -311,6 +320,130 @@ extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* que
     return SVO_OK;
 }
 
+// ---- the guided search (include/svo.h, "Guided search") ----
+extern "C" int svo_desc_index_set_guided_sort(svo_desc_index* x, int on) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    x->guided_sort = on != 0;
+    return SVO_OK;
+}
+
+// a guided call's own refusals, and the prior as the projection reads it
+static int guide_check(const svo_desc_index* x, const float* K, const svo_reloc_guide* g, GuidePose* pose) {
+    if (!x || !K || !g) return fail(SVO_ERR_ARG, "guided search: null index / K / guide");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "guided search: the index has no points (svo_desc_index_enable_points)");
+    if (!isfinite(g->radius) || g->radius < 0.f) return fail(SVO_ERR_ARG, "guided search: the radius must be finite and >= 0");
+    for (int i = 0; i < 9; i++) if (!isfinite(g->R[i]) || !isfinite(K[i])) return fail(SVO_ERR_ARG, "guided search: R or K has a non-finite entry");
+    for (int i = 0; i < 3; i++) if (!isfinite(g->t[i])) return fail(SVO_ERR_ARG, "guided search: t has a non-finite entry");
+    *pose = guide_pose(g->R, g->t, K);
+    return SVO_OK;
+}
+
+// the buffers of the guided search, allocated at the first guided call and freed with the index
+static int guide_room(svo_desc_index* x) {
+    if (x->d_uv) return SVO_OK;
+    MHIP(hipHostMalloc((void**)&x->h_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t), hipHostMallocDefault));
+    MHIP(hipMalloc((void**)&x->d_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t)));
+    MHIP(hipMalloc((void**)&x->d_uv, (size_t)x->capacity * sizeof(float2)));          // last: d_uv says "allocated"
+    return SVO_OK;
+}
+
+// The order in which the lanes of a guided search serve the n queries, into h_order.  A wave skips a row only when none of its 64
+// queries admits it, so queries that sit close together in the image share a wave: sorted by image cell (side 2 * radius, 1 px at
+// least; cells in raster order; a non-finite pixel last), ties by j.  Sort off: 0 .. n - 1.  The results do not depend on it.
+static void guide_order(const svo_desc_index* x, int n, const float* xy, float radius, int32_t* order) {
+    for (int j = 0; j < n; j++) order[j] = j;
+    if (!x->guided_sort || !xy) return;
+    const double side = 2. * (double)radius > 1. ? 2. * (double)radius : 1.;
+    const int64_t lim = (int64_t)1 << 30;
+    std::vector<int64_t> key((size_t)n);
+    for (int j = 0; j < n; j++) {
+        const double cx = floor((double)xy[2 * j] / side), cy = floor((double)xy[2 * j + 1] / side);
+        if (!isfinite(cx) || !isfinite(cy)) { key[(size_t)j] = INT64_MAX; continue; }
+        const int64_t ix = cx < (double)-lim ? -lim : cx > (double)lim ? lim : (int64_t)cx, iy = cy < (double)-lim ? -lim : cy > (double)lim ? lim : (int64_t)cy;
+        key[(size_t)j] = (iy + lim) * (2 * lim + 1) + (ix + lim);
+    }
+    std::sort(order, order + n, [&](int32_t a, int32_t b) { return key[(size_t)a] != key[(size_t)b] ? key[(size_t)a] < key[(size_t)b] : a < b; });
+}
+
+// The geometry of a guided search of n queries.  Its partial states are stored under the queries' own numbers, so the search is one
+// launch over all of them: where n x chunks is beyond the partial-state budget the rows of a chunk double until it fits (n <= 4096
+// and at most 1 << 24 rows: 16 384 rows a chunk at most).  The results do not depend on the chunk.
+static MatchRange guided_range(int row_lo, int row_hi, int chunk_rows, int n) {
+    MatchRange r = match_range(row_lo, row_hi, chunk_rows);
+    while ((size_t)n * (size_t)r.n_chunks > MATCH_PART_BUDGET) r = match_range(row_lo, row_hi, chunk_rows *= 2);
+    return r;
+}
+
+// the queries' pixels and lane order up, the projection and the guided search enqueued on the index's stream: d_out[0 .. n) when it
+// has run.  The queries are in d_query already.  With timing on, ev[0] and ev[1] are recorded around the kernels.
+static int guided_search(svo_desc_index* x, const GuidePose& pose, float radius, int n, const float* xy, int row_lo, int row_hi) {
+    int rc = guide_room(x);
+    if (rc != SVO_OK) return rc;
+    const MatchRange r = guided_range(row_lo, row_hi, x->chunk_rows, n);
+    if (n > 0 && r.n_chunks > 0 && (rc = part_room(x, (size_t)n * (size_t)r.n_chunks)) != SVO_OK) return rc;
+    float* h_xy = (float*)(x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES);   // the ids' part of the staging: 8 bytes a row
+    if (n > 0) {
+        if (xy) memcpy(h_xy, xy, (size_t)n * sizeof(float2)); else memset(h_xy, 0, (size_t)n * sizeof(float2));
+        guide_order(x, n, xy, radius, x->h_order);
+        MHIP(hipMemcpyAsync(x->d_qxy, h_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, x->stream));
+        MHIP(hipMemcpyAsync(x->d_order, x->h_order, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, x->stream));
+    }
+    if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
+    launch_guide_project(x->d_points, pose, row_lo, row_hi, x->d_uv, x->stream);
+    launch_desc_match_guided((const uint32_t*)x->d_desc, x->d_ids, x->d_uv, (const uint32_t*)x->d_query, x->d_qxy, x->d_order, n, radius, r,
+                             x->d_part, x->stream);
+    launch_desc_match_merge(x->d_part, x->d_ids, n, r, x->d_out, x->stream);
+    MHIP(hipGetLastError());
+    if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
+    return SVO_OK;
+}
+
+static int row_range(const svo_desc_index* x, int& row_lo, int& row_hi) {
+    if (row_hi == -1) row_hi = x->size;
+    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "guided search: the row range must satisfy 0 <= row_lo <= row_hi <= size");
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_project(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int row_lo, int row_hi, float* uv) {
+    GuidePose pose;
+    int rc = guide_check(x, K, g, &pose);
+    if (rc != SVO_OK || (rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
+    if (row_hi > row_lo && !uv) return fail(SVO_ERR_ARG, "svo_desc_index_project: null uv");
+    x->last_ms = 0.f;
+    if (row_hi == row_lo) return SVO_OK;
+    MHIP(hipSetDevice(x->device));
+    if ((rc = guide_room(x)) != SVO_OK) return rc;
+    if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
+    launch_guide_project(x->d_points, pose, row_lo, row_hi, x->d_uv, x->stream);
+    MHIP(hipGetLastError());
+    if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
+    MHIP(hipMemcpyAsync(uv, x->d_uv + row_lo, (size_t)(row_hi - row_lo) * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));
+    if (x->timing) MHIP(hipEventElapsedTime(&x->last_ms, x->ev[0], x->ev[1]));
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_match_guided(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int n, const uint8_t* query,
+                                           const float* xy, int row_lo, int row_hi, svo_desc_match* out) {
+    GuidePose pose;
+    int rc = guide_check(x, K, g, &pose);
+    if (rc != SVO_OK) return rc;
+    if (n < 0 || (n > 0 && (!query || !xy || !out))) return fail(SVO_ERR_ARG, "svo_desc_index_match_guided: bad n / query / xy / out");
+    if (n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "svo_desc_index_match_guided: at most 4096 queries per call");
+    if ((rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
+    x->last_ms = 0.f;
+    if (n == 0) return SVO_OK;
+    MHIP(hipSetDevice(x->device));
+    memcpy(x->h_stage, query, (size_t)n * SVO_DESC_BYTES);
+    MHIP(hipMemcpyAsync(x->d_query, x->h_stage, (size_t)n * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
+    if ((rc = guided_search(x, pose, g->radius, n, xy, row_lo, row_hi)) != SVO_OK) return rc;
+    MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));
+    memcpy(out, x->h_out, (size_t)n * sizeof(svo_desc_match));
+    if (x->timing) MHIP(hipEventElapsedTime(&x->last_ms, x->ev[0], x->ev[1]));
+    return SVO_OK;
+}
+
 // ---- the relocaliser (include/svo.h, "Relocalisation") ----
 extern "C" void svo_reloc_params_default(svo_reloc_params* p) {
     if (!p) return;
@@ -321,14 +454,17 @@ extern "C" void svo_reloc_params_default(svo_reloc_params* p) {
 
 // What select and localize share.  Everything is enqueued on the index's stream — the uploads, the search (as many launches as the
 // partial-state budget asks for, back to back, the queries uploaded once), k_reloc_select, the PnP kernels when K is given, the
-// copies back — and the host waits once.  K == nullptr: the selection alone.
-static int reloc_run(svo_desc_index* x, const float* K, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
+// copies back — and the host waits once.  K == nullptr: the selection alone.  guide != nullptr (with Kg, the camera matrix of its
+// projection): the guided search in the unguided one's place, and the timing around its kernels.
+static int reloc_run(svo_desc_index* x, const float* K, const float* Kg, const svo_reloc_guide* guide, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
                      svo_reloc_result* res, int* n_candidates, int32_t* cand_query, int32_t* cand_row, uint8_t* cand_inlier,
                      float* cand_xy, float* cand_xyz) {
     if (!x || !p || n < 0 || (n > 0 && !query)) return fail(SVO_ERR_ARG, "relocalisation: bad index / params / n / query");
     if (!x->d_points) return fail(SVO_ERR_STATE, "relocalisation: the index has no points (svo_desc_index_enable_points)");
     if (n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "relocalisation: at most 4096 queries per call");
-    if (n > 0 && !xy && (K || cand_xy)) return fail(SVO_ERR_ARG, "relocalisation: null xy");
+    if (n > 0 && !xy && (K || cand_xy || guide)) return fail(SVO_ERR_ARG, "relocalisation: null xy");
+    GuidePose pose;
+    if (guide) { const int grc = guide_check(x, Kg, guide, &pose); if (grc != SVO_OK) return grc; }
     int row_lo = p->row_lo, row_hi = p->row_hi == -1 ? x->size : p->row_hi;
     if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "relocalisation: the row range must satisfy 0 <= row_lo <= row_hi <= size");
     if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
@@ -342,7 +478,7 @@ static int reloc_run(svo_desc_index* x, const float* K, int n, const uint8_t* qu
     if (rc != SVO_OK) return rc;
     const MatchRange r = match_range(row_lo, row_hi, x->chunk_rows);
     size_t batch = 0;
-    if ((rc = match_batch(x, n, r, &batch)) != SVO_OK) return rc;
+    if (!guide && (rc = match_batch(x, n, r, &batch)) != SVO_OK) return rc;
     RelocHost* h = x->h_reloc;
     float* h_xy = (float*)(x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES);   // the ids' part of the staging: 8 bytes a row
     if (n > 0) {
@@ -358,7 +494,8 @@ static int reloc_run(svo_desc_index* x, const float* K, int n, const uint8_t* qu
         memcpy(hs.K, K, sizeof(float) * 9); memcpy(hs.R, res->R, sizeof(double) * 9); memcpy(hs.t, res->t, sizeof(double) * 3);
         MHIP(hipMemcpyAsync(d->st, &hs, sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
     }
-    for (size_t i0 = 0; i0 < (size_t)n; i0 += batch) {  // batch is a multiple of 64 rows, or all of them
+    if (guide && (rc = guided_search(x, pose, guide->radius, n, xy, row_lo, row_hi)) != SVO_OK) return rc;
+    for (size_t i0 = 0; !guide && i0 < (size_t)n; i0 += batch) {  // batch is a multiple of 64 rows, or all of them
         const int m = (int)((size_t)n - i0 < batch ? (size_t)n - i0 : batch);
         launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, (const uint32_t*)(x->d_query + i0 * SVO_DESC_BYTES), m, r, x->d_part, x->stream);
         launch_desc_match_merge(x->d_part, x->d_ids, m, r, x->d_out + i0, x->stream);
@@ -368,9 +505,9 @@ static int reloc_run(svo_desc_index* x, const float* K, int n, const uint8_t* qu
     a.rule = RelocRule{p->max_dist, p->ratio_num, p->ratio_den}; a.min_candidates = p->min_candidates;
     a.out_xy = d->tl1; a.out_xyz = d->world; a.st = d->st;
     a.cand_query = x->d_reloc->cand_query; a.cand_row = x->d_reloc->cand_row; a.n_cand = &x->d_reloc->n_cand;
-    if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
+    if (x->timing && !guide) MHIP(hipEventRecord(x->ev[0], x->stream));
     launch_reloc_select(a, x->stream);
-    if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
+    if (x->timing && !guide) MHIP(hipEventRecord(x->ev[1], x->stream));
     if (K) { launch_pnp_subsets(*d, x->stream); launch_pnp(*d, x->stream); }
     MHIP(hipGetLastError());
     MHIP(hipMemcpyAsync(&h->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
@@ -405,12 +542,26 @@ static int reloc_run(svo_desc_index* x, const float* K, int n, const uint8_t* qu
 
 extern "C" int svo_desc_index_select(svo_desc_index* x, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
                                      int* n_candidates, int32_t* cand_query, int32_t* cand_row, float* cand_xy, float* cand_xyz) {
-    return reloc_run(x, nullptr, n, query, xy, p, nullptr, n_candidates, cand_query, cand_row, nullptr, cand_xy, cand_xyz);
+    return reloc_run(x, nullptr, nullptr, nullptr, n, query, xy, p, nullptr, n_candidates, cand_query, cand_row, nullptr, cand_xy, cand_xyz);
 }
 
 extern "C" int svo_desc_index_localize(svo_desc_index* x, const float K[9], int n, const uint8_t* query, const float* xy,
                                        const svo_reloc_params* p, svo_reloc_result* res, int32_t* cand_query, int32_t* cand_row,
                                        uint8_t* cand_inlier) {
     if (!K || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize: null K / result");
-    return reloc_run(x, K, n, query, xy, p, res, nullptr, cand_query, cand_row, cand_inlier, nullptr, nullptr);
+    return reloc_run(x, K, nullptr, nullptr, n, query, xy, p, res, nullptr, cand_query, cand_row, cand_inlier, nullptr, nullptr);
+}
+
+extern "C" int svo_desc_index_select_guided(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int n, const uint8_t* query,
+                                            const float* xy, const svo_reloc_params* p, int* n_candidates, int32_t* cand_query,
+                                            int32_t* cand_row, float* cand_xy, float* cand_xyz) {
+    if (!K || !g) return fail(SVO_ERR_ARG, "svo_desc_index_select_guided: null K / guide");
+    return reloc_run(x, nullptr, K, g, n, query, xy, p, nullptr, n_candidates, cand_query, cand_row, nullptr, cand_xy, cand_xyz);
+}
+
+extern "C" int svo_desc_index_localize_guided(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int n, const uint8_t* query,
+                                              const float* xy, const svo_reloc_params* p, svo_reloc_result* res, int32_t* cand_query,
+                                              int32_t* cand_row, uint8_t* cand_inlier) {
+    if (!K || !g || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize_guided: null K / guide / result");
+    return reloc_run(x, K, K, g, n, query, xy, p, res, nullptr, cand_query, cand_row, cand_inlier, nullptr, nullptr);
 }

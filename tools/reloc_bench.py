@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a relocalisation costs (include/svo.h, "Relocalisation"), against the path it replaces on the same library:
 
-    python tools/reloc_bench.py [--out FILE] [--sizes 65536,1048576] [--queries 2048] [--rounds 15]
+    python tools/reloc_bench.py [--out FILE] [--sizes 65536,1048576] [--queries 2048] [--rounds 15] [--guided RADIUS]
 
 Per index size: an index of random rows with points in which the first --queries rows are landmarks of a scene
 (tests/reloc_cases.py: exact projections, an eighth of the pixels moved), and the queries are those rows' descriptors with three bits
@@ -12,7 +12,14 @@ flipped.  Timed in alternating rounds, medians reported:
 Both paths must return the same pose bits before anything is timed.  Then the device time of k_reloc_select alone (HIP events around
 it: svo_desc_index_set_timing) on that input, and on the dedupe's worst case: 4096 queries, all accepted, all of different
 landmarks.  One child python per index size, one after the other, each under its own time limit; the first failure ends the run.
-Prints one JSON line."""
+Prints one JSON line.
+
+--guided RADIUS runs the guided leg instead (include/svo.h, "Guided search"): every row of the index is a point spread over a
+1241 x 376 view (KITTI's, 4 .. 40 m deep), the first --queries rows are the landmarks the frame sees, and the prior is the true pose
+off by 0.005 rad and 0.05 m, so that RADIUS px admits the fraction of the rows a tracker's frame would.  In one process and
+alternating rounds: the unguided localize, and localize_guided with the query sort on and off — the whole call, and the search
+kernels alone (svo_desc_index_set_timing: k_desc_match + merge for the unguided search, k_guide_project + k_desc_match_guided + merge
+for the guided one)."""
 import argparse
 import json
 import os
@@ -94,6 +101,71 @@ def child(size, n, rounds):
     print(json.dumps(r))
 
 
+def child_guided(size, n, rounds, radius):
+    import guide_cases as gcases
+    from reloc_cases import flip
+    from stereo_visual_odometry_amd import api
+    rng = np.random.default_rng(size)
+    K = np.array([[718.856, 0, 607.1928], [0, 718.856, 185.2157], [0, 0, 1]], np.float32)
+    ix = api.DescriptorIndex(size, points=True)
+    head = None
+    for i0 in range(0, size, 1 << 16):
+        m = min(1 << 16, size - i0)
+        z = rng.uniform(4, 40, m)
+        px = np.stack([rng.uniform(0, 1241, m), rng.uniform(0, 376, m)], 1)
+        p = np.stack([(px[:, 0] - K[0, 2]) / K[0, 0] * z, (px[:, 1] - K[1, 2]) / K[1, 1] * z, z], 1).astype(np.float32)
+        d = rng.integers(0, 256, (m, 32), dtype=np.uint8)
+        ix.add_points(d, (1 << 32) + i0 + np.arange(m, dtype=np.uint64), p)
+        if i0 == 0:
+            head = (d[:n], p[:n])
+    query = np.stack([flip(rng, d, 3) for d in head[0]])
+    c = head[1].astype(np.float64)                                # the true pose is the identity
+    xy = (c[:, :2] / c[:, 2:] * [K[0, 0], K[1, 1]] + [K[0, 2], K[1, 2]]).astype(np.float32)
+    xy[:n // 8] += 50                                             # an eighth of the pixels moved: outside the gate, or outliers
+    R0, t0 = gcases.rot(0.003, -0.003, 0.002), np.array([0.03, -0.03, 0.03])
+    prm = ix.reloc_params()
+    guide = (K, R0, t0, radius)
+
+    def unguided():
+        return ix.localize(K, query, xy, R0, t0, params=prm)
+
+    def guided():
+        return ix.localize_guided(*guide, query, xy, params=prm)
+
+    uv = ix.project(K, R0, t0, 0, min(size, 1 << 16))
+    adm = (np.abs(uv[None, :, 0] - xy[:64, None, 0]) <= radius) & (np.abs(uv[None, :, 1] - xy[:64, None, 1]) <= radius)
+    legs = {}
+    for _ in range(3):
+        ru, _ = unguided()
+        rg, _ = guided()
+    assert ru.success and rg.success, "a leg does not localize"
+    times = dict(unguided=[], guided_sort_on=[], guided_sort_off=[])
+    for _ in range(rounds):
+        t0_ = time.perf_counter(); unguided(); times["unguided"].append((time.perf_counter() - t0_) * 1e3)
+        ix.set_guided_sort(True)
+        t0_ = time.perf_counter(); guided(); times["guided_sort_on"].append((time.perf_counter() - t0_) * 1e3)
+        ix.set_guided_sort(False)
+        t0_ = time.perf_counter(); roff, _ = guided(); times["guided_sort_off"].append((time.perf_counter() - t0_) * 1e3)
+    assert roff.R.tobytes() == rg.R.tobytes() and roff.n_candidates == rg.n_candidates, "the sort changed the result"
+    ix.set_timing(True)
+    kern = dict(unguided=[], guided_sort_on=[], guided_sort_off=[], project=[])
+    for _ in range(rounds):
+        ix.match(query); kern["unguided"].append(ix.stats()["last_kernels_ms"])
+        ix.set_guided_sort(True)
+        ix.select_guided(*guide, query, xy, params=prm); kern["guided_sort_on"].append(ix.stats()["last_kernels_ms"])
+        ix.set_guided_sort(False)
+        ix.select_guided(*guide, query, xy, params=prm); kern["guided_sort_off"].append(ix.stats()["last_kernels_ms"])
+        ix.project(K, R0, t0); kern["project"].append(ix.stats()["last_kernels_ms"])
+    r = dict(size=size, queries=n, rounds=rounds, radius=radius, admitted_fraction_of_rows=float(adm.mean()),
+             unguided_candidates=int(ru.n_candidates), unguided_inliers=int(ru.n_inliers), guided_candidates=int(rg.n_candidates), guided_inliers=int(rg.n_inliers))
+    for k, v in times.items():
+        r["%s_call_ms_median" % k] = float(np.median(v)); r["%s_call_ms_min" % k] = float(min(v))
+    for k, v in kern.items():
+        r["%s_kernels_ms_median" % k] = float(np.median(v)); r["%s_kernels_ms_min" % k] = float(min(v))
+    ix.close()
+    print(json.dumps(r))
+
+
 def step(cmd, limit, what):
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
     if r.returncode != 0:
@@ -108,13 +180,18 @@ def main():
     ap.add_argument("--queries", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--guided", type=float, default=None, metavar="RADIUS", help="the guided leg at this radius in pixels, beside the unguided one")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child is not None:
-        return child(args.child, args.queries, args.rounds)
+        return child_guided(args.child, args.queries, args.rounds, args.guided) if args.guided is not None else child(args.child, args.queries, args.rounds)
     out = dict(shape="%d queries of a scene inside an index of random rows with points; alternating rounds" % args.queries, sizes=[])
+    if args.guided is not None:
+        out["shape"] = "%d queries of a frame inside an index of points spread over a 1241 x 376 view; guided at %g px; alternating rounds" % (args.queries, args.guided)
     for s in (int(x) for x in args.sizes.split(",")):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", str(s), "--queries", str(args.queries), "--rounds", str(args.rounds)]
+        if args.guided is not None:
+            cmd += ["--guided", str(args.guided)]
         out["sizes"].append(json.loads(step(cmd, 400, "the relocalisation at %d rows" % s)))
     line = json.dumps(out)
     print(line)
