@@ -499,7 +499,7 @@ class DescriptorIndex {
     int add(const std::vector<Descriptor>& desc, const std::vector<uint64_t>& ids) {
         if (desc.size() != ids.size()) throw std::runtime_error("DescriptorIndex::add: one id per descriptor row expected");
         int first = 0;
-        svo_throw(svo_desc_index_add(index_, (int)desc.size(), desc.empty() ? nullptr : desc[0].data(), ids.data(), &first));
+        svo_throw(svo_desc_index_add(index_, (int)desc.size(), rows(desc), ids.data(), &first));
         return first;
     }
     // append the rows of vo's last stereo_callback whose flags contain need_flags (SVO_OBS_INLIER: its inliers) -> {first row, rows added}
@@ -512,7 +512,7 @@ class DescriptorIndex {
     // per query the best and the second-best (by id) row of [row_lo, row_hi); row_hi = -1: every row from row_lo on
     std::vector<svo_desc_match> match(const std::vector<Descriptor>& query, int row_lo = 0, int row_hi = -1) {
         std::vector<svo_desc_match> out(query.size());
-        svo_throw(svo_desc_index_match(index_, (int)query.size(), query.empty() ? nullptr : query[0].data(), row_lo, row_hi, out.data()));
+        svo_throw(svo_desc_index_match(index_, (int)query.size(), rows(query), row_lo, row_hi, out.data()));
         return out;
     }
     // ---- relocalisation (svo.h, "Relocalisation"): rows with 3-D points, and the camera's pose in the map from one call
@@ -524,7 +524,7 @@ class DescriptorIndex {
         if (desc.size() != ids.size() || xyz.size() != 3 * desc.size() || (!tags.empty() && tags.size() != desc.size()))
             throw std::runtime_error("DescriptorIndex::add_points: one id, one point and one tag per descriptor row expected");
         int first = 0;
-        svo_throw(svo_desc_index_add_points(index_, (int)desc.size(), desc.empty() ? nullptr : desc[0].data(), ids.data(), xyz.data(),
+        svo_throw(svo_desc_index_add_points(index_, (int)desc.size(), rows(desc), ids.data(), xyz.data(),
                                             tags.empty() ? nullptr : tags.data(), &first));
         return first;
     }
@@ -538,27 +538,13 @@ class DescriptorIndex {
     }
     // the selection alone: the candidates' queries and rows, in increasing query
     Candidates select(const std::vector<Descriptor>& query, const std::vector<float>& xy, const svo_reloc_params& params) {
-        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::select: one pixel per query expected");
-        Candidates c;
-        c.query.resize(query.size()); c.row.resize(query.size());
-        int k = 0;
-        svo_throw(svo_desc_index_select(index_, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &k,
-                                        c.query.data(), c.row.data(), nullptr, nullptr));
-        c.query.resize((size_t)k); c.row.resize((size_t)k);
-        return c;
+        return select_("select", nullptr, nullptr, query, xy, params);
     }
     // search, select and RANSAC-PnP: result.R, t hold the guess going in and the pose (x_cam = R X_map + t) on success, result.T the
     // camera in the map; candidates (may be null) receives the candidate lists with the PnP's inlier flags
     svo_reloc_result localize(const float K[9], const std::vector<Descriptor>& query, const std::vector<float>& xy, const svo_reloc_params& params,
                               svo_reloc_result result, Candidates* candidates = nullptr) {
-        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::localize: one pixel per query expected");
-        Candidates c;
-        c.query.resize(query.size()); c.row.resize(query.size()); c.inlier.resize(query.size());
-        svo_throw(svo_desc_index_localize(index_, K, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &result,
-                                          c.query.data(), c.row.data(), c.inlier.data()));
-        c.query.resize((size_t)result.n_candidates); c.row.resize((size_t)result.n_candidates); c.inlier.resize((size_t)result.n_candidates);
-        if (candidates) *candidates = std::move(c);
-        return result;
+        return localize_("localize", K, nullptr, query, xy, params, result, candidates);
     }
     // ---- guided search (svo.h, "Guided search"): the same calls over the rows a pose prior projects near each query's pixel
     // a guide from the prior x_cam = R X_map + t (row-major 3 x 3, 3) and the gate's radius in pixels
@@ -578,33 +564,19 @@ class DescriptorIndex {
     }
     std::vector<svo_desc_match> match_guided(const float K[9], const svo_reloc_guide& g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
                                              int row_lo = 0, int row_hi = -1) {
-        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::match_guided: one pixel per query expected");
+        one_pixel_each("match_guided", query, xy);
         std::vector<svo_desc_match> out(query.size());
-        svo_throw(svo_desc_index_match_guided(index_, K, &g, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), row_lo, row_hi, out.data()));
+        svo_throw(svo_desc_index_match_guided(index_, K, &g, (int)query.size(), rows(query), xy.data(), row_lo, row_hi, out.data()));
         return out;
     }
     Candidates select_guided(const float K[9], const svo_reloc_guide& g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
                              const svo_reloc_params& params) {
-        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::select_guided: one pixel per query expected");
-        Candidates c;
-        c.query.resize(query.size()); c.row.resize(query.size());
-        int k = 0;
-        svo_throw(svo_desc_index_select_guided(index_, K, &g, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &k,
-                                               c.query.data(), c.row.data(), nullptr, nullptr));
-        c.query.resize((size_t)k); c.row.resize((size_t)k);
-        return c;
+        return select_("select_guided", K, &g, query, xy, params);
     }
     // result.R, t: the PnP's guess going in — the guide's R, t is the usual choice
     svo_reloc_result localize_guided(const float K[9], const svo_reloc_guide& g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
                                      const svo_reloc_params& params, svo_reloc_result result, Candidates* candidates = nullptr) {
-        if (xy.size() != 2 * query.size()) throw std::runtime_error("DescriptorIndex::localize_guided: one pixel per query expected");
-        Candidates c;
-        c.query.resize(query.size()); c.row.resize(query.size()); c.inlier.resize(query.size());
-        svo_throw(svo_desc_index_localize_guided(index_, K, &g, (int)query.size(), query.empty() ? nullptr : query[0].data(), xy.data(), &params, &result,
-                                                 c.query.data(), c.row.data(), c.inlier.data()));
-        c.query.resize((size_t)result.n_candidates); c.row.resize((size_t)result.n_candidates); c.inlier.resize((size_t)result.n_candidates);
-        if (candidates) *candidates = std::move(c);
-        return result;
+        return localize_("localize_guided", K, &g, query, xy, params, result, candidates);
     }
     void set_guided_sort(bool on) { svo_throw(svo_desc_index_set_guided_sort(index_, on ? 1 : 0)); }
     int size() const { return svo_desc_index_size(index_); }
@@ -612,6 +584,36 @@ class DescriptorIndex {
     svo_desc_index* handle() { return index_; }
 
    private:
+    // the rows of a possibly empty descriptor vector
+    static const uint8_t* rows(const std::vector<Descriptor>& d) { return d.empty() ? nullptr : d[0].data(); }
+    static void one_pixel_each(const char* what, const std::vector<Descriptor>& query, const std::vector<float>& xy) {
+        if (xy.size() != 2 * query.size()) throw std::runtime_error(std::string("DescriptorIndex::") + what + ": one pixel per query expected");
+    }
+    // the candidate lists of a call over n queries, with or without the inlier list: sized before the call, cut to its count after
+    static Candidates room(size_t n, bool inlier) { Candidates c; c.query.resize(n); c.row.resize(n); c.inlier.resize(inlier ? n : 0); return c; }
+    static void shrink(Candidates& c, int k) { c.query.resize((size_t)k); c.row.resize((size_t)k); if (!c.inlier.empty()) c.inlier.resize((size_t)k); }
+    // select and localize; g (with its K) null: the unguided search
+    Candidates select_(const char* what, const float* K, const svo_reloc_guide* g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
+                       const svo_reloc_params& params) {
+        one_pixel_each(what, query, xy);
+        Candidates c = room(query.size(), false);
+        int k = 0, n = (int)query.size();
+        svo_throw(g ? svo_desc_index_select_guided(index_, K, g, n, rows(query), xy.data(), &params, &k, c.query.data(), c.row.data(), nullptr, nullptr)
+                    : svo_desc_index_select(index_, n, rows(query), xy.data(), &params, &k, c.query.data(), c.row.data(), nullptr, nullptr));
+        shrink(c, k);
+        return c;
+    }
+    svo_reloc_result localize_(const char* what, const float* K, const svo_reloc_guide* g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
+                               const svo_reloc_params& params, svo_reloc_result result, Candidates* candidates) {
+        one_pixel_each(what, query, xy);
+        Candidates c = room(query.size(), true);
+        const int n = (int)query.size();
+        svo_throw(g ? svo_desc_index_localize_guided(index_, K, g, n, rows(query), xy.data(), &params, &result, c.query.data(), c.row.data(), c.inlier.data())
+                    : svo_desc_index_localize(index_, K, n, rows(query), xy.data(), &params, &result, c.query.data(), c.row.data(), c.inlier.data()));
+        shrink(c, result.n_candidates);
+        if (candidates) *candidates = std::move(c);
+        return result;
+    }
     svo_desc_index* index_ = nullptr;
 };
 

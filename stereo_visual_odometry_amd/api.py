@@ -391,12 +391,18 @@ class DescriptorIndex:
         check(lib.svo_desc_index_add_points(self._h, len(d), ptr(d), ptr(i), ptr(p), ptr(t), C.byref(first)))
         return first.value
 
+    @staticmethod
+    def _frame_handle(vo, what):
+        """vo's context, once it has a frame"""
+        h = getattr(vo, "_h", None)
+        if h is None or not h.value or not getattr(vo, "_created", True):
+            raise _lib.SvoError("libsvo_hip status %d: %s: no frame yet (call stereo_callback first)" % (_lib.SVO_ERR_STATE, what))
+        return h
+
     def add_frame_points(self, vo, cam_to_map=None, tag=0, seq=0, need_flags=_lib.OBS_INLIER):
         """add_frame with each row's point moved into the map -> (first_row, n_added).  cam_to_map (4, 4) float64 is the pose of the
         PREVIOUS frame's left camera in the map (an observation row's xyz is in the T0 camera frame); None: the identity."""
-        h = getattr(vo, "_h", None)
-        if h is None or not h.value or not getattr(vo, "_created", True):
-            raise _lib.SvoError("libsvo_hip status %d: add_frame_points: no frame yet (call stereo_callback first)" % _lib.SVO_ERR_STATE)
+        h = self._frame_handle(vo, "add_frame_points")
         T = None if cam_to_map is None else np.ascontiguousarray(cam_to_map, np.float64).reshape(16)
         first, n = C.c_int(0), C.c_int(0)
         check(lib.svo_desc_index_add_frame_points(self._h, h, int(seq), int(need_flags), ptr(T), int(tag), C.byref(first), C.byref(n)))
@@ -421,44 +427,62 @@ class DescriptorIndex:
             raise ValueError("one pixel per query expected")
         return q, p
 
-    def select(self, query, xy, params=None, **over):
-        """The relocaliser's selection alone (svo_desc_index_select): query (n, 32) uint8, xy (n, 2) float32 -> a dict of the candidates'
-        query (k,) int32, row (k,) int32, xy (k, 2) float32 and xyz (k, 3) float32, in increasing query."""
+    @staticmethod
+    def _K9(K):
+        return np.ascontiguousarray(np.asarray(K, np.float32).reshape(-1)[:9]) if np.size(K) == 9 else \
+            np.ascontiguousarray(np.asarray(K, np.float32)[:3, :3]).reshape(9)
+
+    def _select(self, query, xy, params, over, guide=None):
+        """select's body; guide: None, or (K, R, t, radius) for the guided search"""
         q, p = self._queries(query, xy)
         prm = params if params is not None else self.reloc_params(**over)
         n = len(q)
         cq, cr = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
         cxy, cxyz = np.zeros((max(n, 1), 2), np.float32), np.zeros((max(n, 1), 3), np.float32)
         k = C.c_int(0)
-        check(lib.svo_desc_index_select(self._h, n, ptr(q), ptr(p), C.byref(prm), C.byref(k), ptr(cq), ptr(cr), ptr(cxy), ptr(cxyz)))
+        tail = (n, ptr(q), ptr(p), C.byref(prm), C.byref(k), ptr(cq), ptr(cr), ptr(cxy), ptr(cxyz))
+        if guide is None:
+            check(lib.svo_desc_index_select(self._h, *tail))
+        else:
+            Kf, g = self._K9(guide[0]), self.guide(*guide[1:])
+            check(lib.svo_desc_index_select_guided(self._h, ptr(Kf), C.byref(g), *tail))
         k = k.value
         return dict(query=cq[:k].copy(), row=cr[:k].copy(), xy=cxy[:k].copy(), xyz=cxyz[:k].copy())
 
-    def localize(self, K, query, xy, rotation=None, translation=None, params=None, **over):
-        """Search, select and RANSAC-PnP in one call (svo_desc_index_localize) -> (RelocResult, candidates): the record holds success,
-        n_candidates, n_inliers, iters_run, R (3, 3), t (3, 1) with x_cam = R X_map + t (the guess going in, unchanged without
-        success) and T (4, 4), the camera in the map; candidates is a dict of query, row (k,) int32 and inlier (k,) bool."""
+    def _localize(self, K, query, xy, rotation, translation, params, over, guide=None):
+        """localize's body; rotation, translation: the extrinsic guess; guide: None, or (R, t, radius) for the guided search"""
         q, p = self._queries(query, xy)
         prm = params if params is not None else self.reloc_params(**over)
-        Kf = np.ascontiguousarray(np.asarray(K, np.float32).reshape(-1)[:9]) if np.size(K) == 9 else \
-            np.ascontiguousarray(np.asarray(K, np.float32)[:3, :3]).reshape(9)
+        Kf = self._K9(K)
         res = _lib.SvoRelocResult()
-        res.R[:] = list(np.asarray(np.eye(3) if rotation is None else rotation, np.float64).reshape(9))
-        res.t[:] = list(np.asarray(np.zeros(3) if translation is None else translation, np.float64).reshape(3))
+        res.R[:] = list(np.asarray(rotation, np.float64).reshape(9))
+        res.t[:] = list(np.asarray(translation, np.float64).reshape(3))
         n = len(q)
         cq, cr, ci = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
-        check(lib.svo_desc_index_localize(self._h, ptr(Kf), n, ptr(q), ptr(p), C.byref(prm), C.byref(res), ptr(cq), ptr(cr), ptr(ci)))
+        tail = (n, ptr(q), ptr(p), C.byref(prm), C.byref(res), ptr(cq), ptr(cr), ptr(ci))
+        if guide is None:
+            check(lib.svo_desc_index_localize(self._h, ptr(Kf), *tail))
+        else:
+            g = self.guide(*guide)
+            check(lib.svo_desc_index_localize_guided(self._h, ptr(Kf), C.byref(g), *tail))
         k = res.n_candidates
         rec = RelocResult(bool(res.success), k, res.n_inliers, res.iters_run, np.array(res.R[:]).reshape(3, 3), np.array(res.t[:]).reshape(3, 1),
                           np.array(res.T[:]).reshape(4, 4))
         return rec, dict(query=cq[:k].copy(), row=cr[:k].copy(), inlier=ci[:k].astype(bool))
 
-    # ---- guided search (svo.h, "Guided search"): the same calls behind the projection gate of a pose prior
-    @staticmethod
-    def _K9(K):
-        return np.ascontiguousarray(np.asarray(K, np.float32).reshape(-1)[:9]) if np.size(K) == 9 else \
-            np.ascontiguousarray(np.asarray(K, np.float32)[:3, :3]).reshape(9)
+    def select(self, query, xy, params=None, **over):
+        """The relocaliser's selection alone (svo_desc_index_select): query (n, 32) uint8, xy (n, 2) float32 -> a dict of the candidates'
+        query (k,) int32, row (k,) int32, xy (k, 2) float32 and xyz (k, 3) float32, in increasing query."""
+        return self._select(query, xy, params, over)
 
+    def localize(self, K, query, xy, rotation=None, translation=None, params=None, **over):
+        """Search, select and RANSAC-PnP in one call (svo_desc_index_localize) -> (RelocResult, candidates): the record holds success,
+        n_candidates, n_inliers, iters_run, R (3, 3), t (3, 1) with x_cam = R X_map + t (the guess going in, unchanged without
+        success) and T (4, 4), the camera in the map; candidates is a dict of query, row (k,) int32 and inlier (k,) bool."""
+        return self._localize(K, query, xy, np.eye(3) if rotation is None else rotation, np.zeros(3) if translation is None else translation,
+                              params, over)
+
+    # ---- guided search (svo.h, "Guided search"): the same calls behind the projection gate of a pose prior
     @staticmethod
     def guide(R, t, radius):
         """svo_reloc_guide: the prior x_cam = R X_map + t (R (3, 3), t 3 values, float64) and the gate's radius in pixels"""
@@ -477,8 +501,7 @@ class DescriptorIndex:
         (no point, not in front of the camera, not finite in float32) is (+inf, +inf)."""
         hi = self.size if row_hi == -1 else int(row_hi)
         uv = np.zeros((max(hi - int(row_lo), 0), 2), np.float32)
-        g = self.guide(R, t, 0.0)
-        Kf = self._K9(K)
+        Kf, g = self._K9(K), self.guide(R, t, 0.0)
         check(lib.svo_desc_index_project(self._h, ptr(Kf), C.byref(g), int(row_lo), int(row_hi), ptr(uv)))
         return uv
 
@@ -487,44 +510,19 @@ class DescriptorIndex:
         (svo_desc_index_match_guided) -> the structured rows match returns"""
         q, p = self._queries(query, xy)
         out = np.zeros(len(q), _lib.DESC_MATCH_DTYPE)
-        g = self.guide(R, t, radius)
-        Kf = self._K9(K)
+        Kf, g = self._K9(K), self.guide(R, t, radius)
         check(lib.svo_desc_index_match_guided(self._h, ptr(Kf), C.byref(g), len(q), ptr(q), ptr(p), int(row_lo), int(row_hi), ptr(out)))
         return out
 
     def select_guided(self, K, R, t, radius, query, xy, params=None, **over):
         """select over the guided search (svo_desc_index_select_guided) -> the dict select returns"""
-        q, p = self._queries(query, xy)
-        prm = params if params is not None else self.reloc_params(**over)
-        n = len(q)
-        cq, cr = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-        cxy, cxyz = np.zeros((max(n, 1), 2), np.float32), np.zeros((max(n, 1), 3), np.float32)
-        k = C.c_int(0)
-        g = self.guide(R, t, radius)
-        Kf = self._K9(K)
-        check(lib.svo_desc_index_select_guided(self._h, ptr(Kf), C.byref(g), n, ptr(q), ptr(p), C.byref(prm), C.byref(k), ptr(cq), ptr(cr),
-                                               ptr(cxy), ptr(cxyz)))
-        k = k.value
-        return dict(query=cq[:k].copy(), row=cr[:k].copy(), xy=cxy[:k].copy(), xyz=cxyz[:k].copy())
+        return self._select(query, xy, params, over, guide=(K, R, t, radius))
 
     def localize_guided(self, K, R, t, radius, query, xy, rotation=None, translation=None, params=None, **over):
         """localize over the guided search (svo_desc_index_localize_guided) -> what localize returns.  rotation, translation: the
         PnP's extrinsic guess; None: the guide's R, t, the usual choice."""
-        q, p = self._queries(query, xy)
-        prm = params if params is not None else self.reloc_params(**over)
-        res = _lib.SvoRelocResult()
-        res.R[:] = list(np.asarray(R if rotation is None else rotation, np.float64).reshape(9))
-        res.t[:] = list(np.asarray(t if translation is None else translation, np.float64).reshape(3))
-        n = len(q)
-        cq, cr, ci = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
-        g = self.guide(R, t, radius)
-        Kf = self._K9(K)
-        check(lib.svo_desc_index_localize_guided(self._h, ptr(Kf), C.byref(g), n, ptr(q), ptr(p), C.byref(prm), C.byref(res), ptr(cq), ptr(cr),
-                                                 ptr(ci)))
-        k = res.n_candidates
-        rec = RelocResult(bool(res.success), k, res.n_inliers, res.iters_run, np.array(res.R[:]).reshape(3, 3), np.array(res.t[:]).reshape(3, 1),
-                          np.array(res.T[:]).reshape(4, 4))
-        return rec, dict(query=cq[:k].copy(), row=cr[:k].copy(), inlier=ci[:k].astype(bool))
+        return self._localize(K, query, xy, R if rotation is None else rotation, t if translation is None else translation, params, over,
+                              guide=(R, t, radius))
 
     @staticmethod
     def _rows(desc, what):
@@ -545,9 +543,7 @@ class DescriptorIndex:
 
     def add_frame(self, vo, seq=0, need_flags=_lib.OBS_INLIER):
         """Append the rows of sequence seq of vo's last collected frame whose flags contain need_flags -> (first_row, n_added)."""
-        h = getattr(vo, "_h", None)
-        if h is None or not h.value or not getattr(vo, "_created", True):
-            raise _lib.SvoError("libsvo_hip status %d: add_frame: no frame yet (call stereo_callback first)" % _lib.SVO_ERR_STATE)
+        h = self._frame_handle(vo, "add_frame")
         first, n = C.c_int(0), C.c_int(0)
         check(lib.svo_desc_index_add_frame(self._h, h, int(seq), int(need_flags), C.byref(first), C.byref(n)))
         return first.value, n.value

@@ -1,5 +1,5 @@
-// svo_guide_internal.hpp — what the guided search's translation units share (svo_kernels_guide.hip: k_guide_project,
-// k_desc_match_guided and their launchers; svo_match_api.hip: the C-ABI of include/svo.h, "Guided search").
+// svo_guide_internal.hpp — the two launchers a search with a guide puts where an unguided one puts launch_desc_match: the projection
+// and the gated search (svo_kernels_guide.hip), for search_enqueue (svo_match_api.hip).  The merge behind them is the unguided one.
 #pragma once
 #include "svo_reloc_internal.hpp"
 #include "svo_guide.hpp"

@@ -26,18 +26,11 @@ __global__ void __launch_bounds__(GUIDE_PROJECT_BLOCK) k_guide_project(const Rel
     uv[row] = make_float2(u, v);
 }
 
-static __device__ __forceinline__ uint32_t guided_dist(const uint32_t (&q)[8], const uint4 a, const uint4 b) {
-    uint32_t d = __popc(q[0] ^ a.x);
-    d += __popc(q[1] ^ a.y); d += __popc(q[2] ^ a.z); d += __popc(q[3] ^ a.w);
-    d += __popc(q[4] ^ b.x); d += __popc(q[5] ^ b.y); d += __popc(q[6] ^ b.z); d += __popc(q[7] ^ b.w);
-    return d;
-}
-
 // one row somebody admits: row, and so both addresses, are wave-uniform
 static __device__ __forceinline__ void guided_row(MatchState& s, const uint32_t (&qd)[8], const uint32_t* __restrict__ desc,
                                                   const uint64_t* __restrict__ ids, int row, bool admits) {
     const uint4* rp = reinterpret_cast<const uint4*>(desc + (size_t)row * 8);
-    const match_key k = match_make_key(guided_dist(qd, rp[0], rp[1]), (uint32_t)row);
+    const match_key k = match_make_key(match_dist(qd, rp[0], rp[1]), (uint32_t)row);
     const uint64_t id = ids[row];
     if (admits) match_update(s, k, id);
 }
@@ -59,15 +52,10 @@ __global__ void __launch_bounds__(GUIDED_BLOCK) k_desc_match_guided(const uint32
     const int slot = blockIdx.y * GUIDED_BLOCK + threadIdx.x;
     if (slot >= n) return;                            // a lane beyond n reads nothing, writes nothing and takes no part in a ballot
     const int q = order[slot];
-    int r0 = (r.chunk0 + (int)blockIdx.x) * r.chunk_rows, r1 = r0 + r.chunk_rows;      // as k_desc_match's chunk: clipped to the range
-    r0 = r0 > r.row_lo ? r0 : r.row_lo;
-    r1 = r1 < r.row_hi ? r1 : r.row_hi;
+    int r0, r1;
+    match_chunk_rows(r, blockIdx.x, r0, r1);
     uint32_t qd[8];
-    {
-        const uint4* qp = reinterpret_cast<const uint4*>(query + (size_t)q * 8);
-        const uint4 a = qp[0], b = qp[1];
-        qd[0] = a.x; qd[1] = a.y; qd[2] = a.z; qd[3] = a.w; qd[4] = b.x; qd[5] = b.y; qd[6] = b.z; qd[7] = b.w;
-    }
+    match_load_query(query, q, qd);
     const float2 px = qxy[q];
     MatchState s = match_empty();
     int row = r0;

@@ -12,21 +12,6 @@
 // No LDS, no atomics.
 #include "svo_match_internal.hpp"
 
-static __device__ __forceinline__ uint32_t match_dist(const uint32_t (&q)[8], const uint4 a, const uint4 b) {
-    uint32_t d = __popc(q[0] ^ a.x);
-    d += __popc(q[1] ^ a.y); d += __popc(q[2] ^ a.z); d += __popc(q[3] ^ a.w);
-    d += __popc(q[4] ^ b.x); d += __popc(q[5] ^ b.y); d += __popc(q[6] ^ b.z); d += __popc(q[7] ^ b.w);
-    return d;
-}
-
-// the rows chunk j of the search walks: [r0, r1), inside [row_lo, row_hi)
-static __device__ __forceinline__ void match_chunk_rows(const MatchRange& r, int j, int& r0, int& r1) {
-    r0 = (r.chunk0 + j) * r.chunk_rows;               // <= row_hi < 2^24, chunk_rows <= 2^24: no overflow
-    r1 = r0 + r.chunk_rows;
-    r0 = r0 > r.row_lo ? r0 : r.row_lo;
-    r1 = r1 < r.row_hi ? r1 : r.row_hi;
-}
-
 #define MATCH_BLOCK 64                                // one wave per block, one lane per query
 __global__ void __launch_bounds__(MATCH_BLOCK) k_desc_match(const uint32_t* __restrict__ desc, const uint64_t* __restrict__ ids,
                                                             const uint32_t* __restrict__ query, int n, MatchRange r,
@@ -36,11 +21,7 @@ __global__ void __launch_bounds__(MATCH_BLOCK) k_desc_match(const uint32_t* __re
     int r0, r1;
     match_chunk_rows(r, blockIdx.x, r0, r1);
     uint32_t qd[8];
-    {
-        const uint4* qp = reinterpret_cast<const uint4*>(query + (size_t)q * 8);
-        const uint4 a = qp[0], b = qp[1];
-        qd[0] = a.x; qd[1] = a.y; qd[2] = a.z; qd[3] = a.w; qd[4] = b.x; qd[5] = b.y; qd[6] = b.z; qd[7] = b.w;
-    }
+    match_load_query(query, q, qd);
     MatchState s = match_empty();
 #pragma unroll 4
     for (int row = r0; row < r1; row++) {             // row, and so both addresses below, are wave-uniform

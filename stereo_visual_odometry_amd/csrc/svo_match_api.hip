@@ -1,10 +1,14 @@
-// svo_match_api.hip — host side of the descriptor index (include/svo.h, "Descriptor index"): the index object, the append copies,
-// the batched search and the C-ABI.  An index owns one non-blocking stream and its own pinned staging; add and match wait for that
-// stream alone, so they are legal beside any context's frames in flight.  The kernels are in svo_kernels_match.hip.
-// The relocaliser (include/svo.h, "Relocalisation") is here too: the points of an index, and select / localize, which put the search,
-// k_reloc_select (svo_kernels_reloc.hip) and the RANSAC-PnP kernels on the index's stream and wait once.
-// And the guided search (include/svo.h, "Guided search"): project, match_guided, and select / localize with a guide, which put
-// k_guide_project and k_desc_match_guided (svo_kernels_guide.hip) where the unguided calls put k_desc_match.
+// svo_match_api.hip — host side of the descriptor index (include/svo.h, "Descriptor index", "Relocalisation", "Guided search"): the
+// index object, the append copies, the search and the C-ABI.  An index owns one non-blocking stream and its own pinned staging; every
+// call waits for that stream alone, so it is legal beside any context's frames in flight.
+//
+// Every searching call goes one way: row_range settles the rows, search_plan the launch geometry and its room, stage_queries puts up
+// to MATCH_STAGE_ROWS queries and their pixels on the device, and search_enqueue puts the search on the stream — k_desc_match or, with
+// a guide, k_guide_project and k_desc_match_guided, then k_desc_match_merge — and leaves d_out[0 .. n) without waiting.  match and
+// match_guided copy that back stage by stage; reloc_run, behind select and localize with or without a guide, puts k_reloc_select and
+// the RANSAC-PnP kernels behind it and waits once.
+// Timing (svo_desc_index_set_timing): a call marks the one span it times — its search, its selection or its projection — and reads
+// it into last_ms after its wait.  match times one span per stage, around all of the stage's launches, and sums over its stages.
 #include "svo_guide_internal.hpp"
 #include <algorithm>
 #include <math.h>
@@ -36,12 +40,12 @@ struct RelocHost;
 struct svo_desc_index {
     int device = 0, capacity = 0, size = 0, chunk_rows = MATCH_DEFAULT_CHUNK;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};            // around the two kernels of a launch, recorded while `timing` is on
+    hipEvent_t ev[2] = {nullptr, nullptr};            // around the span a call times, recorded while `timing` is on (span_mark)
     bool timing = false;                              // svo_desc_index_set_timing
-    float last_ms = 0.f;                              // the last timed search's kernels, summed over its launches
+    float last_ms = 0.f;                              // the last call's timed span, summed over its stages (span_read)
     uint8_t* d_desc = nullptr;                        // [capacity][32]
     uint64_t* d_ids = nullptr;                        // [capacity]
-    uint8_t* h_stage = nullptr;                       // pinned: MATCH_STAGE_ROWS descriptors (or queries), then MATCH_STAGE_ROWS ids
+    uint8_t* h_stage = nullptr;                       // pinned: MATCH_STAGE_ROWS descriptors (or queries), then MATCH_STAGE_ROWS ids (or pixels)
     svo_desc_match* h_out = nullptr;                  // pinned: MATCH_STAGE_ROWS result rows
     uint8_t* d_query = nullptr;                       // [MATCH_STAGE_ROWS][32]
     svo_desc_match* d_out = nullptr;                  // [MATCH_STAGE_ROWS]
@@ -257,10 +261,18 @@ extern "C" int svo_desc_index_add_frame_points(svo_desc_index* x, svo_context* c
     return add_frame_rows(x, ctx, seq, need_flags | SVO_OBS_HAS_XYZ, true, cam_to_map, tag, first_row, n_added);
 }
 
+// ---- the search: rows, plan, staging, enqueue, timing (the header comment has the path) ----
+// the one row-range rule: row_hi == -1 is the index's size
+static int row_range(const svo_desc_index* x, int& row_lo, int& row_hi) {
+    if (row_hi == -1) row_hi = x->size;
+    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "the row range must satisfy 0 <= row_lo <= row_hi <= size");
+    return SVO_OK;
+}
+
 // Room for `need` partial states.  The scratch at least doubles whenever it grows (from MATCH_PART_FIRST), so an index whose searches
 // lengthen frame by frame allocates O(log) times and the buffers it has outgrown — kept until the index goes, since hipFree waits for
 // the whole device — sum to less than the one in use.  Up to MATCH_PART_BUDGET the doubling stops at the budget, which every search
-// of at most 65 536 chunks fits (svo_desc_index_match sizes its batches to it); beyond, a search needs 64 queries x its chunks.
+// of at most 65 536 chunks fits (search_plan sizes a launch to it); beyond, a search needs 64 queries x its chunks.
 static int part_room(svo_desc_index* x, size_t need) {
     if (need <= x->part_cap) return SVO_OK;
     size_t cap = x->part_cap ? 2 * x->part_cap : MATCH_PART_FIRST;
@@ -273,77 +285,26 @@ static int part_room(svo_desc_index* x, size_t need) {
     return SVO_OK;
 }
 
-// the queries of one launch of a search of n queries over r, and the scratch's room for it: the partial-state budget decides
-static int match_batch(svo_desc_index* x, int n, const MatchRange& r, size_t* out) {
-    size_t batch = MATCH_STAGE_ROWS;
-    if (r.n_chunks > 0) {
-        size_t fit = MATCH_PART_BUDGET / (size_t)r.n_chunks / 64 * 64;
-        if (fit < 64) fit = 64;
-        if (fit < batch) batch = fit;
-        if ((size_t)n < batch) batch = (size_t)n;
-        const int rc = part_room(x, batch * (size_t)r.n_chunks);
-        if (rc != SVO_OK) return rc;
-    }
-    *out = batch;
-    return SVO_OK;
-}
-
-extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* query, int row_lo, int row_hi, svo_desc_match* out) {
-    if (!x || n < 0 || (n > 0 && (!query || !out))) return fail(SVO_ERR_ARG, "svo_desc_index_match: bad index / n / query / out");
-    if (row_hi == -1) row_hi = x->size;
-    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "svo_desc_index_match: the row range must satisfy 0 <= row_lo <= row_hi <= size");
-    x->last_ms = 0.f;
-    if (n == 0) return SVO_OK;
-    MHIP(hipSetDevice(x->device));
-    const MatchRange r = match_range(row_lo, row_hi, x->chunk_rows);
-    size_t batch = 0;
-    const int rc = match_batch(x, n, r, &batch);
-    if (rc != SVO_OK) return rc;
-    for (size_t i0 = 0; i0 < (size_t)n; i0 += batch) {
-        const int m = (int)((size_t)n - i0 < batch ? (size_t)n - i0 : batch);
-        memcpy(x->h_stage, query + i0 * SVO_DESC_BYTES, (size_t)m * SVO_DESC_BYTES);
-        MHIP(hipMemcpyAsync(x->d_query, x->h_stage, (size_t)m * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
-        if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
-        launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, (const uint32_t*)x->d_query, m, r, x->d_part, x->stream);
-        launch_desc_match_merge(x->d_part, x->d_ids, m, r, x->d_out, x->stream);
-        MHIP(hipGetLastError());
-        if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
-        MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)m * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));
-        memcpy(out + i0, x->h_out, (size_t)m * sizeof(svo_desc_match));
-        if (x->timing) {
-            float ms = 0.f;
-            MHIP(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-            x->last_ms += ms;
-        }
-    }
-    return SVO_OK;
-}
-
-// ---- the guided search (include/svo.h, "Guided search") ----
-extern "C" int svo_desc_index_set_guided_sort(svo_desc_index* x, int on) {
-    if (!x) return fail(SVO_ERR_ARG, "null index");
-    x->guided_sort = on != 0;
-    return SVO_OK;
-}
-
-// a guided call's own refusals, and the prior as the projection reads it
-static int guide_check(const svo_desc_index* x, const float* K, const svo_reloc_guide* g, GuidePose* pose) {
-    if (!x || !K || !g) return fail(SVO_ERR_ARG, "guided search: null index / K / guide");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "guided search: the index has no points (svo_desc_index_enable_points)");
-    if (!isfinite(g->radius) || g->radius < 0.f) return fail(SVO_ERR_ARG, "guided search: the radius must be finite and >= 0");
-    for (int i = 0; i < 9; i++) if (!isfinite(g->R[i]) || !isfinite(K[i])) return fail(SVO_ERR_ARG, "guided search: R or K has a non-finite entry");
-    for (int i = 0; i < 3; i++) if (!isfinite(g->t[i])) return fail(SVO_ERR_ARG, "guided search: t has a non-finite entry");
-    *pose = guide_pose(g->R, g->t, K);
-    return SVO_OK;
-}
-
 // the buffers of the guided search, allocated at the first guided call and freed with the index
 static int guide_room(svo_desc_index* x) {
     if (x->d_uv) return SVO_OK;
     MHIP(hipHostMalloc((void**)&x->h_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t), hipHostMallocDefault));
     MHIP(hipMalloc((void**)&x->d_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t)));
     MHIP(hipMalloc((void**)&x->d_uv, (size_t)x->capacity * sizeof(float2)));          // last: d_uv says "allocated"
+    return SVO_OK;
+}
+
+// a guided search's prior as the kernels read it, and the caller's pixels, which order its lanes (guide_order)
+struct SearchGuide { GuidePose pose; float radius; const float* xy; };
+
+// a guided call's own refusals, and its guide
+static int guide_check(const svo_desc_index* x, const float* K, const svo_reloc_guide* g, const float* xy, SearchGuide* sg) {
+    if (!x || !K || !g) return fail(SVO_ERR_ARG, "guided search: null index / K / guide");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "guided search: the index has no points (svo_desc_index_enable_points)");
+    if (!isfinite(g->radius) || g->radius < 0.f) return fail(SVO_ERR_ARG, "guided search: the radius must be finite and >= 0");
+    for (int i = 0; i < 9; i++) if (!isfinite(g->R[i]) || !isfinite(K[i])) return fail(SVO_ERR_ARG, "guided search: R or K has a non-finite entry");
+    for (int i = 0; i < 3; i++) if (!isfinite(g->t[i])) return fail(SVO_ERR_ARG, "guided search: t has a non-finite entry");
+    *sg = SearchGuide{guide_pose(g->R, g->t, K), g->radius, xy};
     return SVO_OK;
 }
 
@@ -365,83 +326,131 @@ static void guide_order(const svo_desc_index* x, int n, const float* xy, float r
     std::sort(order, order + n, [&](int32_t a, int32_t b) { return key[(size_t)a] != key[(size_t)b] ? key[(size_t)a] < key[(size_t)b] : a < b; });
 }
 
-// The geometry of a guided search of n queries.  Its partial states are stored under the queries' own numbers, so the search is one
-// launch over all of them: where n x chunks is beyond the partial-state budget the rows of a chunk double until it fits (n <= 4096
-// and at most 1 << 24 rows: 16 384 rows a chunk at most).  The results do not depend on the chunk.
-static MatchRange guided_range(int row_lo, int row_hi, int chunk_rows, int n) {
-    MatchRange r = match_range(row_lo, row_hi, chunk_rows);
-    while ((size_t)n * (size_t)r.n_chunks > MATCH_PART_BUDGET) r = match_range(row_lo, row_hi, chunk_rows *= 2);
-    return r;
+// The plan of a search of n <= MATCH_STAGE_ROWS queries: its rows in chunks, the queries of one launch, and the guide if it has one.
+struct SearchPlan { MatchRange r; int batch; const SearchGuide* guide; };
+
+// The two ways a search fits the partial-state budget, and the room for the one chosen.  Unguided: the chunks stay as they are set
+// and the queries go in launches of the largest multiple of 64 (64 at least) whose partial states fit.  Guided: the partial states
+// are stored under the queries' own numbers, so the search is one launch over all of them, and the rows of a chunk double until it
+// fits (n <= 4096 and at most 1 << 24 rows: 16 384 rows a chunk at most).  The results depend on neither.
+static int search_plan(svo_desc_index* x, int n, int row_lo, int row_hi, const SearchGuide* guide, SearchPlan* p) {
+    int chunk_rows = x->chunk_rows;
+    *p = SearchPlan{match_range(row_lo, row_hi, chunk_rows), n, guide};
+    if (guide) {
+        if (const int rc = guide_room(x); rc != SVO_OK) return rc;
+        while ((size_t)n * (size_t)p->r.n_chunks > MATCH_PART_BUDGET) p->r = match_range(row_lo, row_hi, chunk_rows *= 2);
+    } else if (p->r.n_chunks > 0) {
+        size_t fit = MATCH_PART_BUDGET / (size_t)p->r.n_chunks / 64 * 64;
+        if (fit < 64) fit = 64;
+        if (fit < (size_t)n) p->batch = (int)fit;
+    }
+    return p->batch > 0 && p->r.n_chunks > 0 ? part_room(x, (size_t)p->batch * (size_t)p->r.n_chunks) : SVO_OK;
 }
 
-// the queries' pixels and lane order up, the projection and the guided search enqueued on the index's stream: d_out[0 .. n) when it
-// has run.  The queries are in d_query already.  With timing on, ev[0] and ev[1] are recorded around the kernels.
-static int guided_search(svo_desc_index* x, const GuidePose& pose, float radius, int n, const float* xy, int row_lo, int row_hi) {
-    int rc = guide_room(x);
-    if (rc != SVO_OK) return rc;
-    const MatchRange r = guided_range(row_lo, row_hi, x->chunk_rows, n);
-    if (n > 0 && r.n_chunks > 0 && (rc = part_room(x, (size_t)n * (size_t)r.n_chunks)) != SVO_OK) return rc;
-    float* h_xy = (float*)(x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES);   // the ids' part of the staging: 8 bytes a row
-    if (n > 0) {
-        if (xy) memcpy(h_xy, xy, (size_t)n * sizeof(float2)); else memset(h_xy, 0, (size_t)n * sizeof(float2));
-        guide_order(x, n, xy, radius, x->h_order);
-        MHIP(hipMemcpyAsync(x->d_qxy, h_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, x->stream));
+// The one staging step: n <= MATCH_STAGE_ROWS queries into d_query and, for a call that has pixels, their pixels into d_qxy (xy
+// null: zeros).  The pixels ride in the ids' part of the pinned staging, 8 bytes a row.  The staging is free: every call ends in a wait.
+static int stage_queries(svo_desc_index* x, int n, const uint8_t* query, bool pixels, const float* xy) {
+    if (n <= 0) return SVO_OK;
+    memcpy(x->h_stage, query, (size_t)n * SVO_DESC_BYTES);
+    MHIP(hipMemcpyAsync(x->d_query, x->h_stage, (size_t)n * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
+    if (!pixels) return SVO_OK;
+    float* h_xy = (float*)(x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES);
+    if (xy) memcpy(h_xy, xy, (size_t)n * sizeof(float2)); else memset(h_xy, 0, (size_t)n * sizeof(float2));
+    MHIP(hipMemcpyAsync(x->d_qxy, h_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, x->stream));
+    return SVO_OK;
+}
+
+// The timing bracket.  A call begins by clearing last_ms; it marks both edges of the one span it times (`here`: this is that span),
+// and reads the span after its wait.  With timing off nothing is recorded and last_ms stays 0.
+static hipError_t call_begin(svo_desc_index* x) { x->last_ms = 0.f; return hipSetDevice(x->device); }
+static hipError_t span_mark(svo_desc_index* x, bool here, int edge) { return x->timing && here ? hipEventRecord(x->ev[edge], x->stream) : hipSuccess; }
+static hipError_t span_read(svo_desc_index* x) {
+    float ms = 0.f;
+    const hipError_t e = x->timing ? hipEventElapsedTime(&ms, x->ev[0], x->ev[1]) : hipSuccess;
+    x->last_ms += ms;
+    return e;
+}
+
+// The one enqueue: the search of the n staged queries (stage_queries) by plan p on the index's stream, d_out[0 .. n) when it has run;
+// no wait.  Guided: the lane order up, the projection, and one launch of the guided kernel.  Unguided: launches of p.batch queries
+// (a multiple of 64 rows, or all of them) back to back.  timed: the search is the span the call times.
+static int search_enqueue(svo_desc_index* x, const SearchPlan& p, int n, bool timed) {
+    const SearchGuide* g = p.guide;
+    if (g && n > 0) {
+        guide_order(x, n, g->xy, g->radius, x->h_order);
         MHIP(hipMemcpyAsync(x->d_order, x->h_order, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, x->stream));
     }
-    if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
-    launch_guide_project(x->d_points, pose, row_lo, row_hi, x->d_uv, x->stream);
-    launch_desc_match_guided((const uint32_t*)x->d_desc, x->d_ids, x->d_uv, (const uint32_t*)x->d_query, x->d_qxy, x->d_order, n, radius, r,
-                             x->d_part, x->stream);
-    launch_desc_match_merge(x->d_part, x->d_ids, n, r, x->d_out, x->stream);
+    MHIP(span_mark(x, timed, 0));
+    if (g) launch_guide_project(x->d_points, g->pose, p.r.row_lo, p.r.row_hi, x->d_uv, x->stream);
+    for (int i0 = 0; i0 < n; i0 += p.batch) {         // guided: p.batch == n
+        const int m = n - i0 < p.batch ? n - i0 : p.batch;
+        const uint32_t* query = (const uint32_t*)(x->d_query + (size_t)i0 * SVO_DESC_BYTES);
+        if (g) launch_desc_match_guided((const uint32_t*)x->d_desc, x->d_ids, x->d_uv, query, x->d_qxy, x->d_order, m, g->radius, p.r, x->d_part, x->stream);
+        else launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, query, m, p.r, x->d_part, x->stream);
+        launch_desc_match_merge(x->d_part, x->d_ids, m, p.r, x->d_out + i0, x->stream);
+    }
     MHIP(hipGetLastError());
-    if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
+    MHIP(span_mark(x, timed, 1));
     return SVO_OK;
 }
 
-static int row_range(const svo_desc_index* x, int& row_lo, int& row_hi) {
-    if (row_hi == -1) row_hi = x->size;
-    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "guided search: the row range must satisfy 0 <= row_lo <= row_hi <= size");
+// What match and match_guided share: the row range, then stage by stage (a guided call is one stage) the queries up, the search,
+// the result rows back and the wait.  times: the search kernels (guided: with the projection), one span per stage
+static int match_run(svo_desc_index* x, const SearchGuide* guide, int n, const uint8_t* query, int row_lo, int row_hi, svo_desc_match* out) {
+    int rc = row_range(x, row_lo, row_hi);
+    if (rc != SVO_OK) return rc;
+    MHIP(call_begin(x));
+    if (n == 0) return SVO_OK;
+    SearchPlan plan;
+    if ((rc = search_plan(x, n < MATCH_STAGE_ROWS ? n : MATCH_STAGE_ROWS, row_lo, row_hi, guide, &plan)) != SVO_OK) return rc;
+    for (int i0 = 0; i0 < n; i0 += MATCH_STAGE_ROWS) {
+        const int m = n - i0 < MATCH_STAGE_ROWS ? n - i0 : MATCH_STAGE_ROWS;
+        if ((rc = stage_queries(x, m, query + (size_t)i0 * SVO_DESC_BYTES, guide != nullptr, guide ? guide->xy : nullptr)) != SVO_OK ||
+            (rc = search_enqueue(x, plan, m, true)) != SVO_OK) return rc;
+        MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)m * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        memcpy(out + i0, x->h_out, (size_t)m * sizeof(svo_desc_match));
+        MHIP(span_read(x));
+    }
     return SVO_OK;
 }
 
+extern "C" int svo_desc_index_match(svo_desc_index* x, int n, const uint8_t* query, int row_lo, int row_hi, svo_desc_match* out) {
+    if (!x || n < 0 || (n > 0 && (!query || !out))) return fail(SVO_ERR_ARG, "svo_desc_index_match: bad index / n / query / out");
+    return match_run(x, nullptr, n, query, row_lo, row_hi, out);
+}
+
+// ---- the guided search (include/svo.h, "Guided search") ----
+extern "C" int svo_desc_index_set_guided_sort(svo_desc_index* x, int on) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    x->guided_sort = on != 0;
+    return SVO_OK;
+}
+
+// times: the projection kernel
 extern "C" int svo_desc_index_project(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int row_lo, int row_hi, float* uv) {
-    GuidePose pose;
-    int rc = guide_check(x, K, g, &pose);
+    SearchGuide sg;
+    int rc = guide_check(x, K, g, nullptr, &sg);
     if (rc != SVO_OK || (rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
     if (row_hi > row_lo && !uv) return fail(SVO_ERR_ARG, "svo_desc_index_project: null uv");
-    x->last_ms = 0.f;
+    MHIP(call_begin(x));
     if (row_hi == row_lo) return SVO_OK;
-    MHIP(hipSetDevice(x->device));
-    if ((rc = guide_room(x)) != SVO_OK) return rc;
-    if (x->timing) MHIP(hipEventRecord(x->ev[0], x->stream));
-    launch_guide_project(x->d_points, pose, row_lo, row_hi, x->d_uv, x->stream);
-    MHIP(hipGetLastError());
-    if (x->timing) MHIP(hipEventRecord(x->ev[1], x->stream));
+    SearchPlan plan;                                  // a guided search of no queries is the projection
+    if ((rc = search_plan(x, 0, row_lo, row_hi, &sg, &plan)) != SVO_OK || (rc = search_enqueue(x, plan, 0, true)) != SVO_OK) return rc;
     MHIP(hipMemcpyAsync(uv, x->d_uv + row_lo, (size_t)(row_hi - row_lo) * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));
-    if (x->timing) MHIP(hipEventElapsedTime(&x->last_ms, x->ev[0], x->ev[1]));
+    MHIP(span_read(x));
     return SVO_OK;
 }
 
 extern "C" int svo_desc_index_match_guided(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int n, const uint8_t* query,
                                            const float* xy, int row_lo, int row_hi, svo_desc_match* out) {
-    GuidePose pose;
-    int rc = guide_check(x, K, g, &pose);
+    SearchGuide sg;
+    int rc = guide_check(x, K, g, xy, &sg);
     if (rc != SVO_OK) return rc;
     if (n < 0 || (n > 0 && (!query || !xy || !out))) return fail(SVO_ERR_ARG, "svo_desc_index_match_guided: bad n / query / xy / out");
     if (n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "svo_desc_index_match_guided: at most 4096 queries per call");
-    if ((rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
-    x->last_ms = 0.f;
-    if (n == 0) return SVO_OK;
-    MHIP(hipSetDevice(x->device));
-    memcpy(x->h_stage, query, (size_t)n * SVO_DESC_BYTES);
-    MHIP(hipMemcpyAsync(x->d_query, x->h_stage, (size_t)n * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
-    if ((rc = guided_search(x, pose, g->radius, n, xy, row_lo, row_hi)) != SVO_OK) return rc;
-    MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
-    MHIP(hipStreamSynchronize(x->stream));
-    memcpy(out, x->h_out, (size_t)n * sizeof(svo_desc_match));
-    if (x->timing) MHIP(hipEventElapsedTime(&x->last_ms, x->ev[0], x->ev[1]));
-    return SVO_OK;
+    return match_run(x, &sg, n, query, row_lo, row_hi, out);
 }
 
 // ---- the relocaliser (include/svo.h, "Relocalisation") ----
@@ -452,116 +461,106 @@ extern "C" void svo_reloc_params_default(svo_reloc_params* p) {
     p->ransac_iterations = cfg.ransac_iterations; p->reproj_error = cfg.ransac_reprojection_error; p->confidence = cfg.ransac_confidence;
 }
 
-// What select and localize share.  Everything is enqueued on the index's stream — the uploads, the search (as many launches as the
-// partial-state budget asks for, back to back, the queries uploaded once), k_reloc_select, the PnP kernels when K is given, the
-// copies back — and the host waits once.  K == nullptr: the selection alone.  guide != nullptr (with Kg, the camera matrix of its
-// projection): the guided search in the unguided one's place, and the timing around its kernels.
-static int reloc_run(svo_desc_index* x, const float* K, const float* Kg, const svo_reloc_guide* guide, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
-                     svo_reloc_result* res, int* n_candidates, int32_t* cand_query, int32_t* cand_row, uint8_t* cand_inlier,
-                     float* cand_xy, float* cand_xyz) {
-    if (!x || !p || n < 0 || (n > 0 && !query)) return fail(SVO_ERR_ARG, "relocalisation: bad index / params / n / query");
+// What a relocalising call asks for — K: the camera matrix of the guide's projection and of the PnP; guide: null for the unguided
+// search — and where its results go, each null when not wanted.  res says "localize": without it the call is the selection alone.
+struct RelocRequest { const float* K; const svo_reloc_guide* guide; int n; const uint8_t* query; const float* xy; const svo_reloc_params* p; };
+struct RelocOutputs { int* n_candidates; int32_t* cand_query; int32_t* cand_row; float* cand_xy; float* cand_xyz; svo_reloc_result* res = nullptr; uint8_t* cand_inlier = nullptr; };
+
+// What select and localize share, with and without a guide.  Everything is enqueued on the index's stream — the uploads, the search,
+// k_reloc_select, the PnP kernels for localize, the copies back — and the host waits once.
+// times: a guided call its projection and guided search kernels, an unguided one the selection kernel
+static int reloc_run(svo_desc_index* x, const RelocRequest& q, const RelocOutputs& o) {
+    const int n = q.n;
+    const svo_reloc_params* p = q.p; svo_reloc_result* res = o.res;
+    if (!x || !p || n < 0 || (n > 0 && !q.query)) return fail(SVO_ERR_ARG, "relocalisation: bad index / params / n / query");
     if (!x->d_points) return fail(SVO_ERR_STATE, "relocalisation: the index has no points (svo_desc_index_enable_points)");
     if (n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "relocalisation: at most 4096 queries per call");
-    if (n > 0 && !xy && (K || cand_xy || guide)) return fail(SVO_ERR_ARG, "relocalisation: null xy");
-    GuidePose pose;
-    if (guide) { const int grc = guide_check(x, Kg, guide, &pose); if (grc != SVO_OK) return grc; }
-    int row_lo = p->row_lo, row_hi = p->row_hi == -1 ? x->size : p->row_hi;
-    if (row_lo < 0 || row_hi > x->size || row_lo > row_hi) return fail(SVO_ERR_ARG, "relocalisation: the row range must satisfy 0 <= row_lo <= row_hi <= size");
+    if (n > 0 && !q.xy && (res || o.cand_xy || q.guide)) return fail(SVO_ERR_ARG, "relocalisation: null xy");
+    SearchGuide sg;
+    int rc, row_lo = p->row_lo, row_hi = p->row_hi;
+    if (q.guide && (rc = guide_check(x, q.K, q.guide, q.xy, &sg)) != SVO_OK) return rc;
+    if ((rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
     if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
     if (p->ratio_num < 1 || p->ratio_num > SVO_RELOC_MAX_RATIO || p->ratio_den < 1 || p->ratio_den > SVO_RELOC_MAX_RATIO)
         return fail(SVO_ERR_ARG, "relocalisation: ratio_num and ratio_den must be 1 .. 1 << 20");
     if (p->min_candidates < 6) return fail(SVO_ERR_ARG, "relocalisation: min_candidates must be >= 6 (4 and 5 points take svo_camera_to_world's direct routes)");
-    x->last_ms = 0.f;
-    MHIP(hipSetDevice(x->device));
+    const bool times_search = q.guide != nullptr;
+    MHIP(call_begin(x));
     const DevBuffers* d = nullptr;
-    int rc = svo_reloc_stage_ctx(x->device, n > 64 ? n : 64, p->ransac_iterations, p->reproj_error, p->confidence, &d);
-    if (rc != SVO_OK) return rc;
-    const MatchRange r = match_range(row_lo, row_hi, x->chunk_rows);
-    size_t batch = 0;
-    if (!guide && (rc = match_batch(x, n, r, &batch)) != SVO_OK) return rc;
+    SearchPlan plan;
+    if ((rc = svo_reloc_stage_ctx(x->device, n > 64 ? n : 64, p->ransac_iterations, p->reproj_error, p->confidence, &d)) != SVO_OK ||
+        (rc = search_plan(x, n, row_lo, row_hi, q.guide ? &sg : nullptr, &plan)) != SVO_OK || (rc = stage_queries(x, n, q.query, true, q.xy)) != SVO_OK) return rc;
     RelocHost* h = x->h_reloc;
-    float* h_xy = (float*)(x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES);   // the ids' part of the staging: 8 bytes a row
-    if (n > 0) {
-        memcpy(x->h_stage, query, (size_t)n * SVO_DESC_BYTES);
-        if (xy) memcpy(h_xy, xy, (size_t)n * sizeof(float2)); else memset(h_xy, 0, (size_t)n * sizeof(float2));
-        MHIP(hipMemcpyAsync(x->d_query, x->h_stage, (size_t)n * SVO_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
-        MHIP(hipMemcpyAsync(x->d_qxy, h_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, x->stream));
-    }
-    if (K) {                                          // the state row as svo_camera_to_world sets it; k_reloc_select fills in the count
+    if (res) {                                        // the state row as svo_camera_to_world sets it; k_reloc_select fills in the count
         SeqState& hs = h->up;
         memset(&hs, 0, sizeof(hs));
         hs.active = 1; hs.fail_reason = 0; hs.feat_buf = 0;
-        memcpy(hs.K, K, sizeof(float) * 9); memcpy(hs.R, res->R, sizeof(double) * 9); memcpy(hs.t, res->t, sizeof(double) * 3);
+        memcpy(hs.K, q.K, sizeof(float) * 9); memcpy(hs.R, res->R, sizeof(double) * 9); memcpy(hs.t, res->t, sizeof(double) * 3);
         MHIP(hipMemcpyAsync(d->st, &hs, sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
     }
-    if (guide && (rc = guided_search(x, pose, guide->radius, n, xy, row_lo, row_hi)) != SVO_OK) return rc;
-    for (size_t i0 = 0; !guide && i0 < (size_t)n; i0 += batch) {  // batch is a multiple of 64 rows, or all of them
-        const int m = (int)((size_t)n - i0 < batch ? (size_t)n - i0 : batch);
-        launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, (const uint32_t*)(x->d_query + i0 * SVO_DESC_BYTES), m, r, x->d_part, x->stream);
-        launch_desc_match_merge(x->d_part, x->d_ids, m, r, x->d_out + i0, x->stream);
-    }
+    if ((rc = search_enqueue(x, plan, n, times_search)) != SVO_OK) return rc;
     RelocArgs a;
     a.match = x->d_out; a.points = x->d_points; a.xy = x->d_qxy; a.n = n;
     a.rule = RelocRule{p->max_dist, p->ratio_num, p->ratio_den}; a.min_candidates = p->min_candidates;
     a.out_xy = d->tl1; a.out_xyz = d->world; a.st = d->st;
     a.cand_query = x->d_reloc->cand_query; a.cand_row = x->d_reloc->cand_row; a.n_cand = &x->d_reloc->n_cand;
-    if (x->timing && !guide) MHIP(hipEventRecord(x->ev[0], x->stream));
+    MHIP(span_mark(x, !times_search, 0));
     launch_reloc_select(a, x->stream);
-    if (x->timing && !guide) MHIP(hipEventRecord(x->ev[1], x->stream));
-    if (K) { launch_pnp_subsets(*d, x->stream); launch_pnp(*d, x->stream); }
+    MHIP(span_mark(x, !times_search, 1));
+    if (res) { launch_pnp_subsets(*d, x->stream); launch_pnp(*d, x->stream); }
     MHIP(hipGetLastError());
     MHIP(hipMemcpyAsync(&h->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
     if (n > 0) {
         MHIP(hipMemcpyAsync(h->out.cand_row, x->d_reloc->cand_row, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-        if (cand_xy) MHIP(hipMemcpyAsync(h->cand_xy, d->tl1, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
-        if (cand_xyz) MHIP(hipMemcpyAsync(h->cand_xyz, d->world, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
-        if (K) MHIP(hipMemcpyAsync(h->inlier, d->inlier, (size_t)n, hipMemcpyDeviceToHost, x->stream));
+        if (o.cand_xy) MHIP(hipMemcpyAsync(h->cand_xy, d->tl1, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
+        if (o.cand_xyz) MHIP(hipMemcpyAsync(h->cand_xyz, d->world, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+        if (res) MHIP(hipMemcpyAsync(h->inlier, d->inlier, (size_t)n, hipMemcpyDeviceToHost, x->stream));
     }
-    if (K) MHIP(hipMemcpyAsync(&h->down, d->st, sizeof(SeqState), hipMemcpyDeviceToHost, x->stream));
+    if (res) MHIP(hipMemcpyAsync(&h->down, d->st, sizeof(SeqState), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
-    if (x->timing) MHIP(hipEventElapsedTime(&x->last_ms, x->ev[0], x->ev[1]));
+    MHIP(span_read(x));
     const int nc = h->out.n_cand;
-    if (n_candidates) *n_candidates = nc;
-    if (cand_query) memcpy(cand_query, h->out.cand_query, (size_t)nc * sizeof(int32_t));
-    if (cand_row) memcpy(cand_row, h->out.cand_row, (size_t)nc * sizeof(int32_t));
-    if (cand_xy) memcpy(cand_xy, h->cand_xy, (size_t)nc * sizeof(float2));
-    if (cand_xyz) memcpy(cand_xyz, h->cand_xyz, (size_t)nc * 3 * sizeof(float));
-    if (!K) return SVO_OK;
+    if (o.n_candidates) *o.n_candidates = nc;
+    if (o.cand_query) memcpy(o.cand_query, h->out.cand_query, (size_t)nc * sizeof(int32_t));
+    if (o.cand_row) memcpy(o.cand_row, h->out.cand_row, (size_t)nc * sizeof(int32_t));
+    if (o.cand_xy) memcpy(o.cand_xy, h->cand_xy, (size_t)nc * sizeof(float2));
+    if (o.cand_xyz) memcpy(o.cand_xyz, h->cand_xyz, (size_t)nc * 3 * sizeof(float));
+    if (!res) return SVO_OK;
     const SeqState& hs = h->down;
     res->success = 0; res->n_candidates = nc; res->n_inliers = 0; res->iters_run = 0;
     memset(res->T, 0, sizeof(res->T));
-    if (cand_inlier) memset(cand_inlier, 0, (size_t)nc);
+    if (o.cand_inlier) memset(o.cand_inlier, 0, (size_t)nc);
     if (nc < p->min_candidates) return SVO_OK;        // rule 4: every PnP kernel found the row not live
     res->iters_run = hs.pnp_iters;
     if (hs.pnp_best < 0) return SVO_OK;               // no pose: R, t untouched, as svo_camera_to_world leaves them
     memcpy(res->R, hs.R, sizeof(double) * 9); memcpy(res->t, hs.t, sizeof(double) * 3); memcpy(res->T, hs.last_T, sizeof(double) * 16);
     res->success = 1; res->n_inliers = hs.n_inliers;
-    if (cand_inlier) memcpy(cand_inlier, h->inlier, (size_t)nc);
+    if (o.cand_inlier) memcpy(o.cand_inlier, h->inlier, (size_t)nc);
     return SVO_OK;
 }
 
 extern "C" int svo_desc_index_select(svo_desc_index* x, int n, const uint8_t* query, const float* xy, const svo_reloc_params* p,
                                      int* n_candidates, int32_t* cand_query, int32_t* cand_row, float* cand_xy, float* cand_xyz) {
-    return reloc_run(x, nullptr, nullptr, nullptr, n, query, xy, p, nullptr, n_candidates, cand_query, cand_row, nullptr, cand_xy, cand_xyz);
+    return reloc_run(x, RelocRequest{nullptr, nullptr, n, query, xy, p}, RelocOutputs{n_candidates, cand_query, cand_row, cand_xy, cand_xyz});
 }
 
 extern "C" int svo_desc_index_localize(svo_desc_index* x, const float K[9], int n, const uint8_t* query, const float* xy,
                                        const svo_reloc_params* p, svo_reloc_result* res, int32_t* cand_query, int32_t* cand_row,
                                        uint8_t* cand_inlier) {
     if (!K || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize: null K / result");
-    return reloc_run(x, K, nullptr, nullptr, n, query, xy, p, res, nullptr, cand_query, cand_row, cand_inlier, nullptr, nullptr);
+    return reloc_run(x, RelocRequest{K, nullptr, n, query, xy, p}, RelocOutputs{nullptr, cand_query, cand_row, nullptr, nullptr, res, cand_inlier});
 }
 
 extern "C" int svo_desc_index_select_guided(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int n, const uint8_t* query,
                                             const float* xy, const svo_reloc_params* p, int* n_candidates, int32_t* cand_query,
                                             int32_t* cand_row, float* cand_xy, float* cand_xyz) {
     if (!K || !g) return fail(SVO_ERR_ARG, "svo_desc_index_select_guided: null K / guide");
-    return reloc_run(x, nullptr, K, g, n, query, xy, p, nullptr, n_candidates, cand_query, cand_row, nullptr, cand_xy, cand_xyz);
+    return reloc_run(x, RelocRequest{K, g, n, query, xy, p}, RelocOutputs{n_candidates, cand_query, cand_row, cand_xy, cand_xyz});
 }
 
 extern "C" int svo_desc_index_localize_guided(svo_desc_index* x, const float K[9], const svo_reloc_guide* g, int n, const uint8_t* query,
                                               const float* xy, const svo_reloc_params* p, svo_reloc_result* res, int32_t* cand_query,
                                               int32_t* cand_row, uint8_t* cand_inlier) {
     if (!K || !g || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize_guided: null K / guide / result");
-    return reloc_run(x, K, K, g, n, query, xy, p, res, nullptr, cand_query, cand_row, cand_inlier, nullptr, nullptr);
+    return reloc_run(x, RelocRequest{K, g, n, query, xy, p}, RelocOutputs{nullptr, cand_query, cand_row, nullptr, nullptr, res, cand_inlier});
 }

@@ -1,5 +1,6 @@
-// svo_match_internal.hpp — what the descriptor index's two translation units share (svo_kernels_match.hip: the kernels and their
-// launchers; svo_match_api.hip: the index object and the C-ABI of include/svo.h, "Descriptor index").
+// svo_match_internal.hpp — the search of the descriptor index as its translation units share it: the geometry of a search and the
+// launchers of k_desc_match and k_desc_match_merge (svo_kernels_match.hip) for the host side (svo_match_api.hip), and the device
+// code that k_desc_match and k_desc_match_guided (svo_kernels_guide.hip) have in common.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,3 +28,28 @@ void launch_desc_match_merge(const MatchPartial* part, const uint64_t* ids, int 
 
 // the text svo_last_error() returns on this thread (svo_api.hip owns it)
 void svo_set_error(const char* msg);
+
+#if defined(__HIPCC__)
+// query q's eight dwords, which a lane keeps in VGPRs for its whole walk
+static __device__ __forceinline__ void match_load_query(const uint32_t* __restrict__ query, int q, uint32_t (&qd)[8]) {
+    const uint4* qp = reinterpret_cast<const uint4*>(query + (size_t)q * 8);
+    const uint4 a = qp[0], b = qp[1];
+    qd[0] = a.x; qd[1] = a.y; qd[2] = a.z; qd[3] = a.w; qd[4] = b.x; qd[5] = b.y; qd[6] = b.z; qd[7] = b.w;
+}
+
+// the Hamming distance of a query and a row read as two 16-byte halves
+static __device__ __forceinline__ uint32_t match_dist(const uint32_t (&q)[8], const uint4 a, const uint4 b) {
+    uint32_t d = __popc(q[0] ^ a.x);
+    d += __popc(q[1] ^ a.y); d += __popc(q[2] ^ a.z); d += __popc(q[3] ^ a.w);
+    d += __popc(q[4] ^ b.x); d += __popc(q[5] ^ b.y); d += __popc(q[6] ^ b.z); d += __popc(q[7] ^ b.w);
+    return d;
+}
+
+// the rows chunk j of the search walks: [r0, r1), inside [row_lo, row_hi)
+static __device__ __forceinline__ void match_chunk_rows(const MatchRange& r, int j, int& r0, int& r1) {
+    r0 = (r.chunk0 + j) * r.chunk_rows;               // <= row_hi < 2^24, chunk_rows <= 2^24: no overflow
+    r1 = r0 + r.chunk_rows;
+    r0 = r0 > r.row_lo ? r0 : r.row_lo;
+    r1 = r1 < r.row_hi ? r1 : r.row_hi;
+}
+#endif

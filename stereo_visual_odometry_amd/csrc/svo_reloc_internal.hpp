@@ -1,5 +1,5 @@
-// svo_reloc_internal.hpp — what the relocaliser's translation units share (svo_kernels_reloc.hip: k_reloc_select and its launcher;
-// svo_match_api.hip: the index's points and the C-ABI of include/svo.h, "Relocalisation"; svo_api.hip: the stage context).
+// svo_reloc_internal.hpp — what follows the search in a relocalising call: k_reloc_select's arguments and launcher
+// (svo_kernels_reloc.hip) and the PnP stage context it feeds (svo_api.hip), both for reloc_run (svo_match_api.hip).
 #pragma once
 #include "svo_internal.hpp"
 #include "svo_match_internal.hpp"
