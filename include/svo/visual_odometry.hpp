@@ -105,19 +105,28 @@ class Bucket {                                                       // include/
     int size() { return features.size(); }
 };
 
-inline std::vector<Point2f> featureDetectionFast(const Image image, const int fast_threshold,
-                                                 std::vector<float>& response_strengths) {          // vo.h:393-395
+// the body of both forms of featureDetectionFast (not part of the reference's surface): detect into room for `cap` keypoints, again
+// with more room when there were more; mask null: no mask
+inline std::vector<Point2f> fast_detect_all(const Image& image, const uint8_t* mask, int mask_step, int fast_threshold,
+                                            std::vector<float>& response_strengths) {
     int cap = 8192, n = 0;
     std::vector<Point2f> pts;
     for (;;) {
         pts.resize(cap); response_strengths.resize(cap);
-        svo_throw(svo_fast_detect(default_device(), image.data, image.cols, image.rows, image.step, fast_threshold, cap,
-                                  &pts[0].x, response_strengths.data(), &n));
+        svo_throw(mask ? svo_fast_detect_masked(default_device(), image.data, image.cols, image.rows, image.step, fast_threshold,
+                                                mask, mask_step, cap, &pts[0].x, response_strengths.data(), &n)
+                       : svo_fast_detect(default_device(), image.data, image.cols, image.rows, image.step, fast_threshold, cap,
+                                         &pts[0].x, response_strengths.data(), &n));
         if (n <= cap) break;
         cap = n;
     }
     pts.resize(n); response_strengths.resize(n);
     return pts;
+}
+
+inline std::vector<Point2f> featureDetectionFast(const Image image, const int fast_threshold,
+                                                 std::vector<float>& response_strengths) {          // vo.h:393-395
+    return fast_detect_all(image, nullptr, 0, fast_threshold, response_strengths);
 }
 
 // the same behind a detection mask (svo.h: an 8-bit image of the frame's size, non-zero = features allowed, applied to the keypoints
@@ -126,17 +135,7 @@ inline std::vector<Point2f> featureDetectionFast(const Image image, const Image 
                                                  std::vector<float>& response_strengths) {
     if (mask.empty() || mask.rows != image.rows || mask.cols != image.cols || mask.channels != 1)
         throw std::runtime_error("featureDetectionFast: the mask must be a single-channel image of the frame's size");
-    int cap = 8192, n = 0;
-    std::vector<Point2f> pts;
-    for (;;) {
-        pts.resize(cap); response_strengths.resize(cap);
-        svo_throw(svo_fast_detect_masked(default_device(), image.data, image.cols, image.rows, image.step, fast_threshold,
-                                         mask.data, mask.step, cap, &pts[0].x, response_strengths.data(), &n));
-        if (n <= cap) break;
-        cap = n;
-    }
-    pts.resize(n); response_strengths.resize(n);
-    return pts;
+    return fast_detect_all(image, mask.data, mask.step, fast_threshold, response_strengths);
 }
 
 inline void deletePointsWithFailureStatus(std::vector<Point2f>& point_vector, const std::vector<bool>& isok) {   // vo.h:406-407
@@ -181,7 +180,9 @@ inline Mat44 getInverseTransform(const Mat33d& rotation, const Vec3d& translatio
 
 class VisualOdometry {                                               // include/vo.h:231-380
    public:
-    Mat34f leftCameraProjection_, rightCameraProjection_;           // vo.h:273
+    // vo.h:273.  Like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
+    // initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
+    Mat34f leftCameraProjection_{}, rightCameraProjection_{};
     VisualOdometry() { svo_config_default(&cfg_); }
     explicit VisualOdometry(const svo_config& cfg) : cfg_(cfg) {}
     // the 2-argument form src/stereo_vo.cpp:50 calls (missing from the reference's own header)
@@ -192,7 +193,6 @@ class VisualOdometry {                                               // include/
 
     void initalize_projection_matricies(const Mat34f leftCameraProjection, const Mat34f rightCameraProjection) {   // vo.h:307-309
         leftCameraProjection_ = leftCameraProjection; rightCameraProjection_ = rightCameraProjection;
-        have_p_ = true;
         if (ctx_) svo_throw(svo_set_projection(ctx_, -1, leftCameraProjection_.data(), rightCameraProjection_.data()));
     }
 
@@ -200,27 +200,7 @@ class VisualOdometry {                                               // include/
     std::pair<bool, Mat44> stereo_callback(const Image& image_left, const Image& image_right) {
         if (image_left.empty() || image_right.empty()) throw std::runtime_error("stereo_callback: empty image");
         if (image_left.channels != image_right.channels) throw std::runtime_error("stereo_callback: channel mismatch");
-        if (!ctx_) {                                                  // the reference learns size and type from the first frame
-            cfg_.channels = in_format_ != SVO_INPUT_MONO8 ? 1 : image_left.channels;   // an encoding's frames become mono8 inside ingest
-            svo_throw(svo_create(&cfg_, default_device(), 1, image_left.cols, image_left.rows, &ctx_));
-            width_ = image_left.cols; height_ = image_left.rows;
-            // like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
-            // initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
-            if (!have_p_) { leftCameraProjection_.fill(0.f); rightCameraProjection_.fill(0.f); }
-            svo_throw(svo_set_projection(ctx_, -1, leftCameraProjection_.data(), rightCameraProjection_.data()));
-            if (rect_) apply_rectification();
-            if (in_format_ != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx_, in_format_));
-            if (cov_mode_ != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx_, cov_mode_, cov_sigma_));
-            if (clahe_on_) svo_throw(svo_set_clahe(ctx_, 1, clahe_clip_, clahe_tx_, clahe_ty_));
-            if (track_rows_ > 0) svo_throw(svo_set_track_output(ctx_, 1, track_rows_));
-            if (track_rows_ > 0 && desc_on_) svo_throw(svo_set_descriptor_output(ctx_, 1));
-            if (prior_mode_ != SVO_PRIOR_EXPLICIT) svo_throw(svo_set_motion_prior_mode(ctx_, prior_mode_));
-            if (!mask_.empty()) {
-                if ((int)mask_.size() != width_ * height_) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
-                svo_throw(svo_set_detection_mask(ctx_, -1, mask_.data(), width_, 0));
-                mask_.clear(); mask_.shrink_to_fit();
-            }
-        }
+        if (!ctx_) first_frame(image_left);
         check_frame(image_left, "left"); check_frame(image_right, "right");
         Mat44 T;
         int rc = svo_process(ctx_, image_left.data, image_right.data, image_left.step, T.data(), &stats);
@@ -288,11 +268,11 @@ class VisualOdometry {                                               // include/
     // frame when the call comes before it: then the raw size, as image_rect has).  Projection matrices are not touched: pass
     // left.P / right.P to initalize_projection_matricies.  Takes effect from the next frame.
     void set_rectification(const svo_camera_info& left, const svo_camera_info& right) {
-        rect_l_ = left; rect_r_ = right; rect_ = true;
-        if (ctx_) apply_rectification();
+        if (ctx_) svo_throw(svo_set_rectification(ctx_, -1, &left, &right));
+        held_.rect_l = left; held_.rect_r = right; held_.rect = true;
     }
     void clear_rectification() {                                     // back to rectified input (svo_clear_rectification)
-        rect_ = false; raw_w_ = raw_h_ = 0;
+        held_.rect = false;
         if (ctx_) svo_throw(svo_clear_rectification(ctx_));
     }
 
@@ -308,28 +288,26 @@ class VisualOdometry {                                               // include/
         for (const auto& e : table) if (encoding && !std::strcmp(encoding, e.name)) format = e.format;
         if (format < 0) throw std::runtime_error(std::string("set_input_encoding: unknown encoding ") + (encoding ? encoding : "(null)"));
         if (ctx_) svo_throw(svo_set_input_format(ctx_, format));
-        in_format_ = format;
+        held_.in_format = format;
     }
 
     // A 6x6 covariance with every pose from the next frame on (svo_set_pose_covariance): mode SVO_COV_RESIDUAL (sigma^2 from the
     // frame's own reprojection residuals), SVO_COV_FIXED_SIGMA (sigma = pixel_sigma pixels) or SVO_COV_OFF.  A bad mode or sigma throws.
     void set_pose_covariance(int mode, double pixel_sigma = 1.0) {
         if (ctx_) svo_throw(svo_set_pose_covariance(ctx_, mode, pixel_sigma));
-        else if ((mode != SVO_COV_OFF && mode != SVO_COV_RESIDUAL && mode != SVO_COV_FIXED_SIGMA) ||
-                 (mode == SVO_COV_FIXED_SIGMA && !(pixel_sigma > 0 && std::isfinite(pixel_sigma))))
-            throw std::runtime_error("set_pose_covariance: bad mode or pixel_sigma");
-        cov_mode_ = mode; cov_sigma_ = pixel_sigma;
+        else check_cov(mode, pixel_sigma);
+        held_.cov_mode = mode; held_.cov_sigma = pixel_sigma;
     }
     // Equalise both images of every frame passed from now on (svo_set_clahe; replaces cv::createCLAHE(clip, Size(tx, ty))->apply()
     // on the caller's CPU): on the grey frame, after set_input_encoding's conversion and before rectification.  tx, ty: 1 .. 16.
     // Before the first frame the setting is kept and applied when the context is created; bad tiles or a non-finite clip throw at once.
     void set_clahe(double clip = 2.0, int tx = 8, int ty = 8) {
         if (ctx_) svo_throw(svo_set_clahe(ctx_, 1, clip, tx, ty));
-        else if (tx < 1 || tx > 16 || ty < 1 || ty > 16 || !std::isfinite(clip)) throw std::runtime_error("set_clahe: tiles must be 1 .. 16 and clip finite");
-        clahe_on_ = true; clahe_clip_ = clip; clahe_tx_ = tx; clahe_ty_ = ty;
+        else check_clahe(clip, tx, ty);
+        held_.clahe_on = true; held_.clahe_clip = clip; held_.clahe_tx = tx; held_.clahe_ty = ty;
     }
     void clear_clahe() {
-        clahe_on_ = false;
+        held_.clahe_on = false;
         if (ctx_) svo_throw(svo_set_clahe(ctx_, 0, 0., 0, 0));
     }
     // Keep features off the zero bytes of `mask` (svo_set_detection_mask): height rows of width bytes, `stride` apart (0: packed), at
@@ -348,11 +326,11 @@ class VisualOdometry {                                               // include/
             return;
         }
         if (!mask || width < 1 || height < 1 || (stride && stride < width)) throw std::runtime_error("set_detection_mask: bad arguments");
-        mask_.resize((size_t)width * height);
-        for (int y = 0; y < height; y++) std::memcpy(mask_.data() + (size_t)y * width, mask + (size_t)y * (stride ? stride : width), (size_t)width);
+        held_.mask.resize((size_t)width * height);
+        for (int y = 0; y < height; y++) std::memcpy(held_.mask.data() + (size_t)y * width, mask + (size_t)y * (stride ? stride : width), (size_t)width);
     }
     void clear_detection_mask() {
-        mask_.clear();
+        held_.mask.clear();
         if (ctx_) svo_throw(svo_set_detection_mask(ctx_, -1, nullptr, 0, 0));
     }
     // Of the last stereo_callback (svo_get_last_pose_covariance): cov_T, the covariance of the returned transform in the order
@@ -360,9 +338,8 @@ class VisualOdometry {                                               // include/
     // both row-major 6x6, all zero with valid = false when the frame gave no pose.  Throws when the frame ran with the mode off.
     struct PoseCovariance { std::array<double, 36> cov_T, cov_p; bool valid; };
     PoseCovariance last_pose_covariance() const {
-        if (!ctx_) throw std::runtime_error("last_pose_covariance: no frame yet (call stereo_callback first)");
         PoseCovariance c; int valid = 0;
-        svo_throw(svo_get_last_pose_covariance(ctx_, c.cov_T.data(), c.cov_p.data(), &valid));
+        svo_throw(svo_get_last_pose_covariance(need_frame("last_pose_covariance"), c.cov_T.data(), c.cov_p.data(), &valid));
         c.valid = valid != 0;
         return c;
     }
@@ -374,23 +351,16 @@ class VisualOdometry {                                               // include/
     void set_track_output(int max_rows) {
         if (ctx_) svo_throw(svo_set_track_output(ctx_, 1, max_rows));
         else if (max_rows < 1) throw std::runtime_error("set_track_output: max_rows must be >= 1");
-        track_rows_ = max_rows;
+        held_.track_rows = max_rows;
     }
     void clear_track_output() {
-        track_rows_ = 0; desc_on_ = false;                            // the descriptors ride on the track output
+        held_.track_rows = 0; held_.desc_on = false;                            // the descriptors ride on the track output
         if (ctx_) svo_throw(svo_set_track_output(ctx_, 0, 0));
     }
     // The rows of the last stereo_callback, the first min(tracks, max_rows) in svo_get_last_tracks' order; host memory only.
     // Throws when that frame ran with the output off.
     std::vector<svo_track_obs> last_track_observations() const {
-        if (!ctx_) throw std::runtime_error("last_track_observations: no frame yet (call stereo_callback first)");
-        int n_tracks = 0;
-        svo_throw(svo_get_last_track_obs(ctx_, 0, 0, nullptr, &n_tracks));
-        std::vector<svo_track_obs> rows((size_t)(n_tracks > 0 ? n_tracks : 0));
-        const int n = svo_get_last_track_obs(ctx_, 0, (int)rows.size(), rows.data(), nullptr);
-        svo_throw(n);
-        rows.resize((size_t)n);
-        return rows;
+        return last_rows<svo_track_obs>("last_track_observations", svo_get_last_track_obs);
     }
 
     // A 32-byte binary descriptor beside every observation row (svo_set_descriptor_output; svo.h defines it: a steered BRIEF-256 of
@@ -398,20 +368,13 @@ class VisualOdometry {                                               // include/
     // and applied, behind the track output, when the context is created.
     void set_descriptor_output(bool on) {
         if (ctx_) svo_throw(svo_set_descriptor_output(ctx_, on ? 1 : 0));
-        else if (on && track_rows_ < 1) throw std::runtime_error("set_descriptor_output: the track output is off (set_track_output first)");
-        desc_on_ = on;
+        else if (on && held_.track_rows < 1) throw std::runtime_error("set_descriptor_output: the track output is off (set_track_output first)");
+        held_.desc_on = on;
     }
     // The descriptors of the last stereo_callback: 32 bytes per row, row i describes last_track_observations()[i]; host memory only.
     // Throws when that frame ran with descriptors off.
     std::vector<std::array<uint8_t, SVO_DESC_BYTES>> last_track_descriptors() const {
-        if (!ctx_) throw std::runtime_error("last_track_descriptors: no frame yet (call stereo_callback first)");
-        int n_tracks = 0;
-        svo_throw(svo_get_last_track_descriptors(ctx_, 0, 0, nullptr, &n_tracks));
-        std::vector<std::array<uint8_t, SVO_DESC_BYTES>> rows((size_t)(n_tracks > 0 ? n_tracks : 0));
-        const int n = svo_get_last_track_descriptors(ctx_, 0, (int)rows.size(), rows.empty() ? nullptr : rows[0].data(), nullptr);
-        svo_throw(n);
-        rows.resize((size_t)n);
-        return rows;
+        return last_rows<std::array<uint8_t, SVO_DESC_BYTES>>("last_track_descriptors", svo_get_last_track_descriptors);
     }
 
     // Seed the temporal LK passes of the NEXT stereo_callback with a predicted flow (svo_set_motion_prior; OpenCV's
@@ -419,8 +382,7 @@ class VisualOdometry {                                               // include/
     // predicted pixels of the next one; Hi is its inverse, nullptr: the library inverts H.  One-shot: consumed by that frame.
     // H = nullptr clears a pending prior.  Needs the context, i.e. a first frame: before it there is no previous frame to predict from.
     void set_motion_prior(const float* H, const float* Hi = nullptr) {
-        if (!ctx_) throw std::runtime_error("set_motion_prior: no frame yet (the prior predicts from the previous frame)");
-        svo_throw(svo_set_motion_prior(ctx_, 0, H, Hi));
+        svo_throw(svo_set_motion_prior(need_frame("set_motion_prior", "the prior predicts from the previous frame"), 0, H, Hi));
     }
     // The same from a rotation (svo_motion_prior_from_rotation): R (3x3 row-major f64) rotates T0-camera coordinates into T1-camera
     // coordinates — a gyro's integrated increment moved into the camera frame; K is the left projection matrix's.
@@ -435,14 +397,13 @@ class VisualOdometry {                                               // include/
     void set_motion_prior_mode(int mode) {
         if (mode != SVO_PRIOR_EXPLICIT && mode != SVO_PRIOR_LAST_ROTATION) throw std::runtime_error("set_motion_prior_mode: unknown mode");
         if (ctx_) svo_throw(svo_set_motion_prior_mode(ctx_, mode));
-        prior_mode_ = mode;
+        held_.prior_mode = mode;
     }
     // What the last stereo_callback used (svo_get_last_motion_prior): source 0 none, 1 explicit, 2 predicted; H, Hi valid when != 0.
     struct MotionPrior { std::array<float, 9> H, Hi; int source; };
     MotionPrior last_motion_prior() const {
-        if (!ctx_) throw std::runtime_error("last_motion_prior: no frame yet (call stereo_callback first)");
         MotionPrior p{};
-        svo_throw(svo_get_last_motion_prior(ctx_, 0, p.H.data(), p.Hi.data(), &p.source));
+        svo_throw(svo_get_last_motion_prior(need_frame("last_motion_prior"), 0, p.H.data(), p.Hi.data(), &p.source));
         return p;
     }
 
@@ -457,30 +418,85 @@ class VisualOdometry {                                               // include/
     // frame against the context (a shorter or narrower buffer would be read past its end)
     void check_frame(const Image& im, const char* which) const {
         if (im.empty()) throw std::runtime_error(std::string(which) + " image is empty");
-        const int w = raw_w_ ? raw_w_ : width_, h = raw_w_ ? raw_h_ : height_;     // rectifying: frames are raw
+        const int w = held_.rect ? held_.rect_l.width : width_, h = held_.rect ? held_.rect_l.height : height_;   // rectifying: frames are raw
         static const int bytes_per_pixel[7] = {1, 3, 3, 4, 4, 2, 2};              // of SVO_INPUT_*
-        const int cn = in_format_ != SVO_INPUT_MONO8 ? bytes_per_pixel[in_format_] : cfg_.channels;
+        const int cn = held_.in_format != SVO_INPUT_MONO8 ? bytes_per_pixel[held_.in_format] : cfg_.channels;
         if (im.cols != w || im.rows != h || im.channels != cn || im.step < im.cols * im.channels)
             throw std::runtime_error(std::string(which) + " image does not match the size / channels the object takes (the raw size when rectifying)");
     }
-    void apply_rectification() {
-        svo_throw(svo_set_rectification(ctx_, -1, &rect_l_, &rect_r_));
-        raw_w_ = rect_l_.width; raw_h_ = rect_l_.height;
+    friend class DescriptorIndex;                                     // (need_frame)
+    // the context, once a frame has created it
+    svo_context* need_frame(const char* what, const char* why = "call stereo_callback first") const {
+        if (!ctx_) throw std::runtime_error(std::string(what) + ": no frame yet (" + why + ")");
+        return ctx_;
+    }
+    // the rows of the last stereo_callback through a (ctx, seq, cap, rows, n_tracks) getter: sized by a first call, filled by a second
+    template <class Row, class Elem>
+    std::vector<Row> last_rows(const char* what, int (*get)(svo_context*, int, int, Elem*, int*)) const {
+        svo_context* ctx = need_frame(what);
+        int n_tracks = 0;
+        svo_throw(get(ctx, 0, 0, nullptr, &n_tracks));
+        std::vector<Row> rows((size_t)(n_tracks > 0 ? n_tracks : 0));
+        const int n = get(ctx, 0, (int)rows.size(), rows.empty() ? nullptr : reinterpret_cast<Elem*>(rows.data()), nullptr);
+        svo_throw(n);
+        rows.resize((size_t)n);
+        return rows;
+    }
+
+    // What the setters asked for ("Facades: settings before the first frame"): held until the first frame creates the
+    // context, and kept current afterwards (check_frame reads in_format).  The projection matrices are the public members above.
+    struct Held {
+        bool rect = false; svo_camera_info rect_l{}, rect_r{};        // set_rectification: frames are then raw, rect_l.width x rect_l.height
+        int in_format = SVO_INPUT_MONO8;                              // set_input_encoding
+        int cov_mode = SVO_COV_OFF; double cov_sigma = 1.0;           // set_pose_covariance
+        std::vector<uint8_t> mask;                                    // set_detection_mask with a size, packed; emptied once installed
+        bool clahe_on = false; double clahe_clip = 2.0; int clahe_tx = 8, clahe_ty = 8;   // set_clahe
+        int track_rows = 0;                                           // set_track_output; 0: off
+        bool desc_on = false;                                         // set_descriptor_output, behind the track output
+        int prior_mode = SVO_PRIOR_EXPLICIT;                          // set_motion_prior_mode
+    };
+    // svo_set_pose_covariance's and svo_set_clahe's checks of their arguments (svo_api.hip: check_cov_mode, check_clahe_params), for
+    // the calls that come before there is a context to ask
+    static void check_cov(int mode, double pixel_sigma) {
+        if ((mode != SVO_COV_OFF && mode != SVO_COV_RESIDUAL && mode != SVO_COV_FIXED_SIGMA) ||
+            (mode == SVO_COV_FIXED_SIGMA && !(pixel_sigma > 0 && std::isfinite(pixel_sigma))))
+            throw std::runtime_error("set_pose_covariance: bad mode or pixel_sigma");
+    }
+    static void check_clahe(double clip, int tx, int ty) {
+        if (tx < 1 || tx > 16 || ty < 1 || ty > 16 || !std::isfinite(clip)) throw std::runtime_error("set_clahe: tiles must be 1 .. 16 and clip finite");
+    }
+    // Every held setting onto ctx, a context just created for width x height frames, in the order both facades use: rectification,
+    // projection, input format, covariance, detection mask, CLAHE (its fit check sees the raw size: after the rectification), track
+    // output, descriptors (they ride on it), prior mode.
+    void apply(svo_context* ctx, int width, int height) const {
+        if (held_.rect) svo_throw(svo_set_rectification(ctx, -1, &held_.rect_l, &held_.rect_r));
+        svo_throw(svo_set_projection(ctx, -1, leftCameraProjection_.data(), rightCameraProjection_.data()));
+        if (held_.in_format != SVO_INPUT_MONO8) svo_throw(svo_set_input_format(ctx, held_.in_format));
+        if (held_.cov_mode != SVO_COV_OFF) svo_throw(svo_set_pose_covariance(ctx, held_.cov_mode, held_.cov_sigma));
+        if (!held_.mask.empty()) {
+            if (held_.mask.size() != (size_t)width * height) throw std::runtime_error("set_detection_mask: the mask is not of the frame's size");
+            svo_throw(svo_set_detection_mask(ctx, -1, held_.mask.data(), width, 0));
+        }
+        if (held_.clahe_on) svo_throw(svo_set_clahe(ctx, 1, held_.clahe_clip, held_.clahe_tx, held_.clahe_ty));
+        if (held_.track_rows > 0) svo_throw(svo_set_track_output(ctx, 1, held_.track_rows));
+        if (held_.track_rows > 0 && held_.desc_on) svo_throw(svo_set_descriptor_output(ctx, 1));
+        if (held_.prior_mode != SVO_PRIOR_EXPLICIT) svo_throw(svo_set_motion_prior_mode(ctx, held_.prior_mode));
+    }
+    // The reference learns size and type from the first frame: create the context for it, apply what is held, and only then adopt it.
+    // A setting the context refuses (CLAHE tiles that do not fit this size, ...) throws with the object still before its first frame
+    // and everything held: correct the setting and pass the frame again.
+    void first_frame(const Image& im) {
+        cfg_.channels = held_.in_format != SVO_INPUT_MONO8 ? 1 : im.channels;   // an encoding's frames become mono8 inside ingest
+        svo_context* ctx = nullptr;
+        svo_throw(svo_create(&cfg_, default_device(), 1, im.cols, im.rows, &ctx));
+        try { apply(ctx, im.cols, im.rows); } catch (...) { svo_destroy(ctx); throw; }
+        ctx_ = ctx; width_ = im.cols; height_ = im.rows;
+        held_.mask.clear(); held_.mask.shrink_to_fit();
     }
     svo_config cfg_;
     svo_context* ctx_ = nullptr;
-    bool have_p_ = false;
     int width_ = 0, height_ = 0;                                      // learnt from the first frame
-    bool rect_ = false;                                               // set_rectification was called (applied once the context exists)
-    svo_camera_info rect_l_{}, rect_r_{};
-    int raw_w_ = 0, raw_h_ = 0;                                       // raw frame size while rectifying, else 0
-    int in_format_ = SVO_INPUT_MONO8;                                 // set_input_encoding (applied once the context exists)
-    int cov_mode_ = SVO_COV_OFF; double cov_sigma_ = 1.0;             // set_pose_covariance (likewise)
-    std::vector<uint8_t> mask_;                                       // set_detection_mask before the first frame: installed at creation
-    int track_rows_ = 0;                                              // set_track_output (likewise); 0: off
-    bool desc_on_ = false;                                            // set_descriptor_output (likewise, behind the track output)
-    int prior_mode_ = SVO_PRIOR_EXPLICIT;                             // set_motion_prior_mode (likewise)
-    bool clahe_on_ = false; double clahe_clip_ = 2.0; int clahe_tx_ = 8, clahe_ty_ = 8;   // set_clahe (applied once the context exists)
+    Held held_;
 };
 
 // A device-resident index of (descriptor, id) rows with an exact 2-nearest-neighbour Hamming search (svo.h, "Descriptor index"): per
@@ -504,9 +520,8 @@ class DescriptorIndex {
     }
     // append the rows of vo's last stereo_callback whose flags contain need_flags (SVO_OBS_INLIER: its inliers) -> {first row, rows added}
     std::pair<int, int> add_frame(VisualOdometry& vo, uint32_t need_flags = SVO_OBS_INLIER) {
-        if (!vo.handle()) throw std::runtime_error("DescriptorIndex::add_frame: no frame yet (call stereo_callback first)");
         int first = 0, n = 0;
-        svo_throw(svo_desc_index_add_frame(index_, vo.handle(), 0, need_flags, &first, &n));
+        svo_throw(svo_desc_index_add_frame(index_, vo.need_frame("DescriptorIndex::add_frame"), 0, need_flags, &first, &n));
         return {first, n};
     }
     // per query the best and the second-best (by id) row of [row_lo, row_hi); row_hi = -1: every row from row_lo on
@@ -531,9 +546,8 @@ class DescriptorIndex {
     // add_frame with each row's point moved into the map.  cam_to_map: the pose (row-major 4 x 4) of the PREVIOUS frame's left camera
     // in the map — an observation row's xyz is in the T0 camera frame — or nullptr for the identity.
     std::pair<int, int> add_frame(VisualOdometry& vo, const double* cam_to_map, int32_t tag, uint32_t need_flags = SVO_OBS_INLIER) {
-        if (!vo.handle()) throw std::runtime_error("DescriptorIndex::add_frame: no frame yet (call stereo_callback first)");
         int first = 0, n = 0;
-        svo_throw(svo_desc_index_add_frame_points(index_, vo.handle(), 0, need_flags, cam_to_map, tag, &first, &n));
+        svo_throw(svo_desc_index_add_frame_points(index_, vo.need_frame("DescriptorIndex::add_frame"), 0, need_flags, cam_to_map, tag, &first, &n));
         return {first, n};
     }
     // the selection alone: the candidates' queries and rows, in increasing query

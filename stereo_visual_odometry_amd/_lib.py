@@ -30,6 +30,28 @@ if not os.environ.get("SVO_NO_TORCH_PRELOAD"):
 lib = C.CDLL(LIB_PATH)
 
 SVO_OK, SVO_ERR_ARG, SVO_ERR_HIP, SVO_ERR_CAPACITY, SVO_ERR_STATE = 0, -1, -2, -3, -4
+# svo_get_last_frame_path bits (svo.h SVO_PATH_*)
+PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
+PATH_INPUT_CONVERTED, PATH_POSE_COV, PATH_DETECT_MASKED, PATH_CLAHE, PATH_TRACK_IDS = 64, 128, 256, 512, 1024
+PATH_MOTION_PRIOR, PATH_PRIOR_PREDICTED, PATH_DESCRIPTORS = 2048, 4096, 8192
+# observation rows (svo.h svo_track_obs flags), descriptor rows, descriptor-index results, relocalisation
+OBS_INLIER, OBS_HAS_XYZ = 1, 2
+DESC_BYTES = 32
+MATCH_NONE, MATCH_NO_DIST = -1, 257
+POINT_NONE, RELOC_MAX_QUERIES = -1, 4096
+# motion priors (svo.h SVO_PRIOR_*)
+PRIOR_EXPLICIT, PRIOR_LAST_ROTATION = 0, 1
+PRIOR_MODES = {"explicit": PRIOR_EXPLICIT, "last_rotation": PRIOR_LAST_ROTATION}
+# pose covariance (svo.h SVO_COV_*)
+COV_OFF, COV_RESIDUAL, COV_FIXED_SIGMA = 0, 1, 2
+COV_MODES = {"off": COV_OFF, "residual": COV_RESIDUAL, "fixed": COV_FIXED_SIGMA}
+# input formats (svo.h SVO_INPUT_*): what the bytes of the caller's frames are; the sensor_msgs encoding names map onto them
+INPUT_MONO8, INPUT_BGR8, INPUT_RGB8, INPUT_BGRA8, INPUT_RGBA8, INPUT_UYVY, INPUT_YUY2 = range(7)
+INPUT_ENCODINGS = {"mono8": INPUT_MONO8, "bgr8": INPUT_BGR8, "rgb8": INPUT_RGB8, "bgra8": INPUT_BGRA8, "rgba8": INPUT_RGBA8,
+                   "yuv422": INPUT_UYVY, "yuv422_yuy2": INPUT_YUY2}
+INPUT_BPP = (1, 3, 3, 4, 4, 2, 2)
+# svo_get_pyramid / svo_get_derivatives: which pyramid pair
+PYR_T1, PYR_LAST_LEFT = 0, 1
 
 
 class SvoError(RuntimeError):
@@ -66,31 +88,8 @@ class SvoCameraInfo(C.Structure):
                 ("width", C.c_int), ("height", C.c_int)]
 
 
-lib.svo_last_error.restype = C.c_char_p
-lib.svo_alloc_pinned.restype = C.c_void_p
-lib.svo_alloc_pinned.argtypes = [C.c_size_t]
-lib.svo_free_pinned.restype = None
-lib.svo_free_pinned.argtypes = [C.c_void_p]
-lib.svo_get_stream.restype = C.c_void_p
-lib.svo_stage_cache_clear.restype = None
-lib.svo_stage_cache_clear.argtypes = []
-lib.svo_get_stream.argtypes = [C.c_void_p]
-lib.svo_get_lk_registers_left.restype = C.c_int
-lib.svo_get_lk_registers_left.argtypes = [C.c_void_p]
-lib.svo_get_last_frame_path.restype = C.c_int
-lib.svo_get_last_frame_path.argtypes = [C.c_void_p]
-# svo_get_last_frame_path bits (svo.h SVO_PATH_*)
-PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
-PATH_INPUT_CONVERTED = 64
-PATH_POSE_COV = 128
-PATH_DETECT_MASKED = 256
-PATH_CLAHE = 512
-PATH_TRACK_IDS = 1024
-# track ids and observation rows (svo.h svo_track_obs): the 64-byte row as a ctypes structure and as a numpy structured dtype
-OBS_INLIER, OBS_HAS_XYZ = 1, 2
-
-
 class SvoTrackObs(C.Structure):
+    """svo_track_obs: the 64-byte observation row; TRACK_OBS_DTYPE is the same row as a numpy structured dtype"""
     _fields_ = [("id", C.c_int64), ("l0", C.c_float * 2), ("r0", C.c_float * 2), ("l1", C.c_float * 2), ("r1", C.c_float * 2),
                 ("xyz", C.c_float * 3), ("age", C.c_int32), ("flags", C.c_int32), ("pad", C.c_int32)]
 
@@ -98,58 +97,13 @@ class SvoTrackObs(C.Structure):
 TRACK_OBS_DTYPE = np.dtype([("id", "<i8"), ("l0", "<f4", 2), ("r0", "<f4", 2), ("l1", "<f4", 2), ("r1", "<f4", 2),
                             ("xyz", "<f4", 3), ("age", "<i4"), ("flags", "<i4"), ("pad", "<i4")])
 assert TRACK_OBS_DTYPE.itemsize == 64 and C.sizeof(SvoTrackObs) == 64
-if hasattr(lib, "svo_set_track_output"):
-    lib.svo_set_track_output.restype = C.c_int
-    lib.svo_set_track_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.svo_get_last_track_obs.restype = C.c_int
-    lib.svo_get_last_track_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-    lib.svo_get_feature_ids.restype = C.c_int
-    lib.svo_get_feature_ids.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-# binary descriptors (svo.h, "Binary descriptors"): rows of DESC_BYTES bytes beside the observation rows
-PATH_DESCRIPTORS = 8192
-DESC_BYTES = 32
-lib.svo_set_descriptor_output.restype = C.c_int
-lib.svo_set_descriptor_output.argtypes = [C.c_void_p, C.c_int]
-lib.svo_get_last_track_descriptors.restype = C.c_int
-lib.svo_get_last_track_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_describe_points.restype = C.c_int
-lib.svo_describe_points.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_descriptor_pattern.restype = C.c_int
-lib.svo_descriptor_pattern.argtypes = [C.c_void_p, C.c_void_p]
-# descriptor index (svo.h, "Descriptor index"): the 32-byte result row as a numpy structured dtype
-MATCH_NONE, MATCH_NO_DIST = -1, 257
+# svo_desc_match: the descriptor index's 32-byte result row
 DESC_MATCH_DTYPE = np.dtype([("id", "<u8"), ("id2", "<u8"), ("row", "<i4"), ("row2", "<i4"), ("dist", "<u2"), ("dist2", "<u2"), ("reserved", "<u4")])
 assert DESC_MATCH_DTYPE.itemsize == 32
-lib.svo_desc_index_create.restype = C.c_int
-lib.svo_desc_index_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-lib.svo_desc_index_destroy.restype = None
-lib.svo_desc_index_destroy.argtypes = [C.c_void_p]
-lib.svo_desc_index_add.restype = C.c_int
-lib.svo_desc_index_add.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_desc_index_add_frame.restype = C.c_int
-lib.svo_desc_index_add_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-lib.svo_desc_index_size.restype = C.c_int
-lib.svo_desc_index_size.argtypes = [C.c_void_p]
-lib.svo_desc_index_truncate.restype = C.c_int
-lib.svo_desc_index_truncate.argtypes = [C.c_void_p, C.c_int]
-lib.svo_desc_index_match.restype = C.c_int
-lib.svo_desc_index_match.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-lib.svo_desc_index_set_chunk_rows.restype = C.c_int
-lib.svo_desc_index_set_chunk_rows.argtypes = [C.c_void_p, C.c_int]
-lib.svo_desc_index_get_chunk_rows.restype = C.c_int
-lib.svo_desc_index_get_chunk_rows.argtypes = [C.c_void_p]
 
 
 class SvoDescIndexStats(C.Structure):
     _fields_ = [("last_kernels_ms", C.c_float), ("scratch_allocations", C.c_int32), ("scratch_bytes", C.c_uint64), ("scratch_bytes_outgrown", C.c_uint64)]
-
-
-lib.svo_desc_index_set_timing.restype = C.c_int
-lib.svo_desc_index_set_timing.argtypes = [C.c_void_p, C.c_int]
-lib.svo_desc_index_get_stats.restype = C.c_int
-lib.svo_desc_index_get_stats.argtypes = [C.c_void_p, C.POINTER(SvoDescIndexStats)]
-# relocalisation (svo.h, "Relocalisation"): points in the index, select and localize
-POINT_NONE, RELOC_MAX_QUERIES = -1, 4096
 
 
 class SvoRelocParams(C.Structure):
@@ -162,153 +116,113 @@ class SvoRelocResult(C.Structure):
                 ("R", C.c_double * 9), ("t", C.c_double * 3), ("T", C.c_double * 16)]
 
 
-lib.svo_reloc_params_default.restype = None
-lib.svo_reloc_params_default.argtypes = [C.POINTER(SvoRelocParams)]
-lib.svo_desc_index_enable_points.restype = C.c_int
-lib.svo_desc_index_enable_points.argtypes = [C.c_void_p]
-lib.svo_desc_index_add_points.restype = C.c_int
-lib.svo_desc_index_add_points.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_desc_index_add_frame_points.restype = C.c_int
-lib.svo_desc_index_add_frame_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_int32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-lib.svo_desc_index_select.restype = C.c_int
-lib.svo_desc_index_select.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams), C.POINTER(C.c_int),
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_desc_index_localize.restype = C.c_int
-lib.svo_desc_index_localize.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
-                                        C.POINTER(SvoRelocResult), C.c_void_p, C.c_void_p, C.c_void_p]
-# guided search (svo.h, "Guided search"): the same calls behind a pose prior's projection gate
-
-
 class SvoRelocGuide(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("radius", C.c_float), ("reserved", C.c_int32)]
 
 
-lib.svo_desc_index_project.restype = C.c_int
-lib.svo_desc_index_project.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_int, C.c_void_p]
-lib.svo_desc_index_match_guided.restype = C.c_int
-lib.svo_desc_index_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-lib.svo_desc_index_select_guided.restype = C.c_int
-lib.svo_desc_index_select_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
-                                             C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_desc_index_localize_guided.restype = C.c_int
-lib.svo_desc_index_localize_guided.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SvoRelocGuide), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SvoRelocParams),
-                                               C.POINTER(SvoRelocResult), C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_desc_index_set_guided_sort.restype = C.c_int
-lib.svo_desc_index_set_guided_sort.argtypes = [C.c_void_p, C.c_int]
-# motion priors (svo.h): H / Hi are 9 float32 each (n_seq x 9 in the batch setter), has n_seq bytes; R is 9 float64
-PATH_MOTION_PRIOR = 2048
-lib.svo_set_motion_prior.restype = C.c_int
-lib.svo_set_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-lib.svo_set_motion_priors.restype = C.c_int
-lib.svo_set_motion_priors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_get_motion_prior.restype = C.c_int
-lib.svo_get_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_motion_prior_from_rotation.restype = C.c_int
-lib.svo_motion_prior_from_rotation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-PATH_PRIOR_PREDICTED = 4096
-PRIOR_EXPLICIT, PRIOR_LAST_ROTATION = 0, 1
-PRIOR_MODES = {"explicit": PRIOR_EXPLICIT, "last_rotation": PRIOR_LAST_ROTATION}
-lib.svo_set_motion_prior_mode.restype = C.c_int
-lib.svo_set_motion_prior_mode.argtypes = [C.c_void_p, C.c_int]
-lib.svo_get_motion_prior_mode.restype = C.c_int
-lib.svo_get_motion_prior_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_get_last_motion_prior.restype = C.c_int
-lib.svo_get_last_motion_prior.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_lk_track_guess.restype = C.c_int
-lib.svo_lk_track_guess.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
-lib.svo_circular_match_prior.restype = C.c_int
-lib.svo_circular_match_prior.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-# CLAHE (svo.h): the equalisation in front of frame ingest, and the stage alone
-lib.svo_set_clahe.restype = C.c_int
-lib.svo_set_clahe.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]
-lib.svo_clahe.restype = C.c_int
-lib.svo_clahe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
-# detection masks (svo.h): mask is a host or device pointer to height rows of width bytes
-lib.svo_set_detection_mask.restype = C.c_int
-lib.svo_set_detection_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
-lib.svo_get_detection_mask.restype = C.c_int
-lib.svo_get_detection_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-lib.svo_fast_detect_masked.restype = C.c_int
-lib.svo_fast_detect_masked.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                       C.POINTER(C.c_int)]
-lib.svo_append_features_from_image_masked.restype = C.c_int
-lib.svo_append_features_from_image_masked.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                      C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
-# pose covariance (svo.h SVO_COV_*): cov_T / cov_p are n_seq x 36 doubles, valid n_seq ints
-COV_OFF, COV_RESIDUAL, COV_FIXED_SIGMA = 0, 1, 2
-COV_MODES = {"off": COV_OFF, "residual": COV_RESIDUAL, "fixed": COV_FIXED_SIGMA}
-lib.svo_set_pose_covariance.restype = C.c_int
-lib.svo_set_pose_covariance.argtypes = [C.c_void_p, C.c_int, C.c_double]
-lib.svo_get_last_pose_covariance.restype = C.c_int
-lib.svo_get_last_pose_covariance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_pose_covariance.restype = C.c_int
-lib.svo_pose_covariance.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-# input formats (svo.h SVO_INPUT_*): what the bytes of the caller's frames are; the sensor_msgs encoding names map onto them
-INPUT_MONO8, INPUT_BGR8, INPUT_RGB8, INPUT_BGRA8, INPUT_RGBA8, INPUT_UYVY, INPUT_YUY2 = range(7)
-INPUT_ENCODINGS = {"mono8": INPUT_MONO8, "bgr8": INPUT_BGR8, "rgb8": INPUT_RGB8, "bgra8": INPUT_BGRA8, "rgba8": INPUT_RGBA8,
-                   "yuv422": INPUT_UYVY, "yuv422_yuy2": INPUT_YUY2}
-INPUT_BPP = (1, 3, 3, 4, 4, 2, 2)
-lib.svo_set_input_format.restype = C.c_int
-lib.svo_set_input_format.argtypes = [C.c_void_p, C.c_int]
-lib.svo_convert_gray.restype = C.c_int
-lib.svo_convert_gray.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-# ragged / continuous batching (svo.h): active is a host array of n_seq bytes or NULL; Pl / Pr 12 floats each or both NULL
-lib.svo_process_batch_masked.restype = C.c_int
-lib.svo_process_batch_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_submit_batch_masked.restype = C.c_int
-lib.svo_submit_batch_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-lib.svo_reset_sequence.restype = C.c_int
-lib.svo_reset_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-# rectification (svo.h): maps are int16 (h, w, 2) + uint16 (h, w) host arrays
-lib.svo_init_rectify_map.restype = C.c_int
-lib.svo_init_rectify_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-lib.svo_set_rectification_maps.restype = C.c_int
-lib.svo_set_rectification_maps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-lib.svo_set_rectification.restype = C.c_int
-lib.svo_set_rectification.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-lib.svo_clear_rectification.restype = C.c_int
-lib.svo_clear_rectification.argtypes = [C.c_void_p]
-lib.svo_rectify_image.restype = C.c_int
-lib.svo_rectify_image.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-# pyramid read-out (svo.h svo_get_pyramid): one level with its stored border, packed
-lib.svo_get_pyramid.restype = C.c_int
-lib.svo_get_pyramid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
-                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-PYR_T1, PYR_LAST_LEFT = 0, 1
-# derivative-plane read-out (svo.h svo_get_derivatives): the int16 Ix / Iy planes of one level >= 1 with their zero border
-lib.svo_get_derivatives.restype = C.c_int
-lib.svo_get_derivatives.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
-                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-
-# every symbol include/svo.h declares (tests/test_abi.py checks the list against the header)
-EXPORTS = [
-    "svo_last_error", "svo_device_count", "svo_config_default", "svo_create", "svo_destroy", "svo_set_projection",
-    "svo_process_batch", "svo_process_batch_masked", "svo_submit_batch_masked", "svo_reset_sequence", "svo_process", "svo_alloc_pinned", "svo_free_pinned", "svo_circular_matching", "svo_submit_batch", "svo_collect", "svo_get_features", "svo_get_last_tracks",
-    "svo_get_pyramid", "svo_get_derivatives",
-    "svo_get_lk_registers_left", "svo_get_last_frame_path", "svo_get_last_timing", "svo_set_stage_timing", "svo_get_stage_timing", "svo_get_stream", "svo_fast_detect", "svo_fast_score_map", "svo_bucket_filter",
-    "svo_append_features_from_image", "svo_build_pyramid", "svo_lk_track", "svo_circular_match",
-    "svo_find_close_points", "svo_stage_cache_clear", "svo_stage_cache_clear_all", "svo_triangulate", "svo_camera_to_world", "svo_inverse_transform",
-    "svo_set_rectification_maps", "svo_set_rectification", "svo_clear_rectification", "svo_init_rectify_map", "svo_rectify_image",
-    "svo_set_input_format", "svo_convert_gray",
-    "svo_set_pose_covariance", "svo_get_last_pose_covariance", "svo_pose_covariance",
-    "svo_set_detection_mask", "svo_get_detection_mask", "svo_fast_detect_masked", "svo_append_features_from_image_masked",
-    "svo_set_clahe", "svo_clahe",
-    "svo_set_track_output", "svo_get_last_track_obs", "svo_get_feature_ids",
-    "svo_set_motion_prior", "svo_set_motion_priors", "svo_get_motion_prior", "svo_motion_prior_from_rotation",
-    "svo_lk_track_guess", "svo_circular_match_prior",
-    "svo_set_motion_prior_mode", "svo_get_motion_prior_mode", "svo_get_last_motion_prior",
-    "svo_set_descriptor_output", "svo_get_last_track_descriptors", "svo_describe_points", "svo_descriptor_pattern",
-    "svo_desc_index_create", "svo_desc_index_destroy", "svo_desc_index_add", "svo_desc_index_add_frame", "svo_desc_index_size",
-    "svo_desc_index_truncate", "svo_desc_index_match", "svo_desc_index_set_chunk_rows", "svo_desc_index_get_chunk_rows",
-    "svo_desc_index_set_timing", "svo_desc_index_get_stats",
-    "svo_reloc_params_default", "svo_desc_index_enable_points", "svo_desc_index_add_points", "svo_desc_index_add_frame_points",
-    "svo_desc_index_select", "svo_desc_index_localize",
-    "svo_desc_index_project", "svo_desc_index_match_guided", "svo_desc_index_select_guided", "svo_desc_index_localize_guided",
-    "svo_desc_index_set_guided_sort",
-]
+# Every function include/svo.h declares, in its order: name -> (restype, argtypes).  tests/test_abi.py parses the header and compares
+# it with this table argument by argument.  Every pointer or array argument is P: an array's ptr(), C.byref(x), a ctypes array, None
+# or a raw address (a tensor's data_ptr()).
+I, I32, U32, I64, SZ, F, D, P = C.c_int, C.c_int32, C.c_uint32, C.c_int64, C.c_size_t, C.c_float, C.c_double, C.c_void_p
+PROTOTYPES = {
+    "svo_last_error": (C.c_char_p, ()),
+    "svo_device_count": (I, ()),
+    "svo_config_default": (None, (P,)),
+    "svo_create": (I, (P, I, I, I, I, P)),
+    "svo_destroy": (None, (P,)),
+    "svo_set_projection": (I, (P, I, P, P)),
+    "svo_process_batch": (I, (P, P, P, I, I, P, P, P)),
+    "svo_alloc_pinned": (P, (SZ,)),
+    "svo_free_pinned": (None, (P,)),
+    "svo_process": (I, (P, P, P, I, P, P)),
+    "svo_circular_matching": (I, (P, P, P, I, I, P, P, P, P, P, P)),
+    "svo_get_lk_registers_left": (I, (P,)),
+    "svo_get_last_frame_path": (I, (P,)),
+    "svo_submit_batch": (I, (P, P, P, I)),
+    "svo_collect": (I, (P, P, P, P)),
+    "svo_process_batch_masked": (I, (P, P, P, I, I, P, P, P, P)),
+    "svo_submit_batch_masked": (I, (P, P, P, I, P)),
+    "svo_reset_sequence": (I, (P, I, P, P)),
+    "svo_set_rectification_maps": (I, (P, I, I, I, P, P, P, P)),
+    "svo_set_rectification": (I, (P, I, P, P)),
+    "svo_clear_rectification": (I, (P,)),
+    "svo_set_input_format": (I, (P, I)),
+    "svo_set_clahe": (I, (P, I, D, I, I)),
+    "svo_set_pose_covariance": (I, (P, I, D)),
+    "svo_get_last_pose_covariance": (I, (P, P, P, P)),
+    "svo_get_features": (I, (P, I, I, P, P, P)),
+    "svo_get_last_tracks": (I, (P, I, I, P, P, P, P, P, P)),
+    "svo_set_track_output": (I, (P, I, I)),
+    "svo_get_last_track_obs": (I, (P, I, I, P, P)),
+    "svo_get_feature_ids": (I, (P, I, I, P)),
+    "svo_set_descriptor_output": (I, (P, I)),
+    "svo_get_last_track_descriptors": (I, (P, I, I, P, P)),
+    "svo_descriptor_pattern": (I, (P, P)),
+    "svo_desc_index_create": (I, (I, I, P)),
+    "svo_desc_index_destroy": (None, (P,)),
+    "svo_desc_index_add": (I, (P, I, P, P, P)),
+    "svo_desc_index_add_frame": (I, (P, P, I, U32, P, P)),
+    "svo_desc_index_size": (I, (P,)),
+    "svo_desc_index_truncate": (I, (P, I)),
+    "svo_desc_index_match": (I, (P, I, P, I, I, P)),
+    "svo_desc_index_set_chunk_rows": (I, (P, I)),
+    "svo_desc_index_get_chunk_rows": (I, (P,)),
+    "svo_desc_index_set_timing": (I, (P, I)),
+    "svo_desc_index_get_stats": (I, (P, P)),
+    "svo_reloc_params_default": (None, (P,)),
+    "svo_desc_index_enable_points": (I, (P,)),
+    "svo_desc_index_add_points": (I, (P, I, P, P, P, P, P)),
+    "svo_desc_index_add_frame_points": (I, (P, P, I, U32, P, I32, P, P)),
+    "svo_desc_index_select": (I, (P, I, P, P, P, P, P, P, P, P)),
+    "svo_desc_index_localize": (I, (P, P, I, P, P, P, P, P, P, P)),
+    "svo_desc_index_project": (I, (P, P, P, I, I, P)),
+    "svo_desc_index_match_guided": (I, (P, P, P, I, P, P, I, I, P)),
+    "svo_desc_index_select_guided": (I, (P, P, P, I, P, P, P, P, P, P, P, P)),
+    "svo_desc_index_localize_guided": (I, (P, P, P, I, P, P, P, P, P, P, P)),
+    "svo_desc_index_set_guided_sort": (I, (P, I)),
+    "svo_set_detection_mask": (I, (P, I, P, I, I)),
+    "svo_get_detection_mask": (I, (P, I, P, P)),
+    "svo_set_motion_prior": (I, (P, I, P, P)),
+    "svo_set_motion_priors": (I, (P, P, P, P)),
+    "svo_get_motion_prior": (I, (P, I, P, P, P)),
+    "svo_motion_prior_from_rotation": (I, (P, P, P, P)),
+    "svo_set_motion_prior_mode": (I, (P, I)),
+    "svo_get_motion_prior_mode": (I, (P, P)),
+    "svo_get_last_motion_prior": (I, (P, I, P, P, P)),
+    "svo_get_pyramid": (I, (P, I, I, I, I, I, P, I64, P, P, P, P)),
+    "svo_get_derivatives": (I, (P, I, I, I, I, P, P, I64, P, P, P, P)),
+    "svo_get_last_timing": (I, (P, P, P)),
+    "svo_set_stage_timing": (I, (P, I)),
+    "svo_get_stage_timing": (I, (P, P)),
+    "svo_get_stream": (P, (P,)),
+    "svo_stage_cache_clear": (None, ()),
+    "svo_stage_cache_clear_all": (I, ()),
+    "svo_fast_detect": (I, (I, P, I, I, I, I, I, P, P, P)),
+    "svo_fast_detect_masked": (I, (I, P, I, I, I, I, P, I, I, P, P, P)),
+    "svo_fast_score_map": (I, (I, P, I, I, I, I, P)),
+    "svo_bucket_filter": (I, (I, I, I, P, P, P, P, I, I, I, I, I, I)),
+    "svo_append_features_from_image": (I, (I, P, P, I, I, I, I, I, P, P, P, P)),
+    "svo_append_features_from_image_masked": (I, (I, P, P, I, I, I, I, P, I, I, P, P, P, P)),
+    "svo_build_pyramid": (I, (I, P, I, I, I, I, I, P, I64, P)),
+    "svo_lk_track": (I, (I, P, P, I, I, I, I, P, P, P, I, I, I, D, D)),
+    "svo_lk_track_guess": (I, (I, P, P, I, I, I, I, P, P, P, P, I, I, I, D, D)),
+    "svo_circular_match": (I, (I, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P)),
+    "svo_circular_match_prior": (I, (I, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P)),
+    "svo_find_close_points": (I, (I, I, P, P, F, P)),
+    "svo_triangulate": (I, (I, P, P, I, P, P, P)),
+    "svo_camera_to_world": (I, (I, P, I, P, P, P, P, P, P, P, I, F, F, P)),
+    "svo_pose_covariance": (I, (I, P, I, P, P, P, P, P, I, D, P, P, P)),
+    "svo_init_rectify_map": (I, (P, P, I, P, P, I, I, P, P)),
+    "svo_rectify_image": (I, (I, P, P, I, I, P, I, I, I, I, P)),
+    "svo_convert_gray": (I, (I, I, P, I, I, I, P)),
+    "svo_clahe": (I, (I, I, P, I, I, I, D, I, I, P)),
+    "svo_describe_points": (I, (I, P, I, I, I, I, P, P, P)),
+    "svo_inverse_transform": (I, (I, P, P, P)),
+}
+for _name, (_restype, _argtypes) in PROTOTYPES.items():
+    _fn = getattr(lib, _name)                         # a symbol the library lacks fails the import here
+    _fn.restype, _fn.argtypes = _restype, list(_argtypes)
+EXPORTS = list(PROTOTYPES)
 
 
 def check(rc):

@@ -8,6 +8,7 @@ std::vector<cv::Point2f> becomes an (N,2) float32 array.  All arithmetic runs on
 """
 import collections
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -24,6 +25,24 @@ MAX_TRANSLATION_NORM, MAX_ROTATION_NORM = 0.1, 0.5
 
 def _pts(p):
     return np.ascontiguousarray(p, np.float32).reshape(-1, 2)
+
+
+def _K9(K):
+    """The camera matrix as 9 float32: a 3x3 (or its 9 values), or the left 3x3 of a 3x4 projection matrix."""
+    k = np.asarray(K, np.float32)
+    return np.ascontiguousarray(k.reshape(-1) if k.size == 9 else k[:3, :3]).reshape(9).copy()
+
+
+def _strided_u8(image, f):
+    """An image in the format f (an SVO_INPUT_* constant) for the stage calls that take a row stride -> a uint8 (h, w, bpp) array,
+    (h, w) for mono8, whose rows may be strided: a view's strides[0] is passed on."""
+    bpp = _lib.INPUT_BPP[f]
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or not ((img.ndim == 3 and img.shape[2] == bpp) or (bpp == 1 and img.ndim == 2)):
+        raise ValueError("uint8 (h, w, %d) image expected for this format" % bpp)
+    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != bpp):
+        img = np.ascontiguousarray(img)
+    return img
 
 
 # ---------------------------------------------------------------------------- free functions
@@ -95,8 +114,7 @@ def cameraToWorld(cameraProjection, cameraPoints, worldPoints, rotation, transla
     """vo.h:452-456 — returns ((inliers, success), rotation, translation, iterations_run): the reference's pair, then its two
     in/out arguments (the updated values on success, the inputs on failure, vo.cpp:307-311), then how many RANSAC iterations
     the adaptive loop ran (a counter the reference does not expose)."""
-    K = np.ascontiguousarray(cameraProjection, np.float32).reshape(-1)[:9].copy() if np.size(cameraProjection) == 9 else \
-        np.ascontiguousarray(np.asarray(cameraProjection, np.float32)[:3, :3]).reshape(9)
+    K = _K9(cameraProjection)
     cam = _pts(cameraPoints)
     world = np.ascontiguousarray(worldPoints, np.float32).reshape(-1, 3)
     n = len(cam)
@@ -116,8 +134,7 @@ def poseCovariance(cameraProjection, cameraPoints, worldPoints, rotation, transl
     every point).  cov_p is in the order (r, t) of the cameraToWorld parameters, cov_T in the order (position,
     rotation) of the inverse transform getInverseTransform(R, t), as ROS orders a pose covariance.  A singular system gives
     valid False and zeros."""
-    K = np.ascontiguousarray(cameraProjection, np.float32).reshape(-1)[:9].copy() if np.size(cameraProjection) == 9 else \
-        np.ascontiguousarray(np.asarray(cameraProjection, np.float32)[:3, :3]).reshape(9)
+    K = _K9(cameraProjection)
     cam = _pts(cameraPoints)
     world = np.ascontiguousarray(worldPoints, np.float32).reshape(-1, 3)
     if len(world) != len(cam):
@@ -306,12 +323,7 @@ def convertGray(image, fmt, device=0):
     ingest alone.  image: (h, w, bpp) uint8 in the format `fmt` (an SVO_INPUT_* constant or a sensor_msgs encoding name; (h, w)
     for mono8); rows may be strided (a view's strides[0] is passed on) -> (h, w) uint8."""
     f = _lib.input_format(fmt)
-    bpp = _lib.INPUT_BPP[f]
-    img = np.asarray(image)
-    if img.dtype != np.uint8 or not ((img.ndim == 3 and img.shape[2] == bpp) or (bpp == 1 and img.ndim == 2)):
-        raise ValueError("uint8 (h, w, %d) image expected for this format" % bpp)
-    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != bpp):
-        img = np.ascontiguousarray(img)
+    img = _strided_u8(image, f)
     h, w = img.shape[:2]
     out = np.zeros((h, w), np.uint8)
     check(lib.svo_convert_gray(device, f, C.c_void_p(img.ctypes.data), w, h, img.strides[0], ptr(out)))
@@ -323,13 +335,8 @@ def clahe(image, fmt="mono8", clip_limit=2.0, tiles=(8, 8), device=0):
     ingest alone, on its two kernels.  image: (h, w, bpp) uint8 in the format `fmt` ((h, w) for mono8), rows may be strided ->
     (h, w) uint8.  ValueError for tiles outside 1 .. 16 or a non-finite clip_limit; SvoError when the tiles do not fit the image."""
     f = _lib.input_format(fmt)
-    bpp = _lib.INPUT_BPP[f]
     clip, tx, ty = _lib.check_clahe(clip_limit, tiles)
-    img = np.asarray(image)
-    if img.dtype != np.uint8 or not ((img.ndim == 3 and img.shape[2] == bpp) or (bpp == 1 and img.ndim == 2)):
-        raise ValueError("uint8 (h, w, %d) image expected for this format" % bpp)
-    if img.strides[-1] != 1 or (img.ndim == 3 and img.strides[1] != bpp):
-        img = np.ascontiguousarray(img)
+    img = _strided_u8(image, f)
     h, w = img.shape[:2]
     out = np.zeros((h, w), np.uint8)
     check(lib.svo_clahe(device, f, C.c_void_p(img.ctypes.data), w, h, img.strides[0], clip, tx, ty, ptr(out)))
@@ -394,10 +401,7 @@ class DescriptorIndex:
     @staticmethod
     def _frame_handle(vo, what):
         """vo's context, once it has a frame"""
-        h = getattr(vo, "_h", None)
-        if h is None or not h.value or not getattr(vo, "_created", True):
-            raise _lib.SvoError("libsvo_hip status %d: %s: no frame yet (call stereo_callback first)" % (_lib.SVO_ERR_STATE, what))
-        return h
+        return vo._need_frame(what, prefix="libsvo_hip status %d: " % _lib.SVO_ERR_STATE)
 
     def add_frame_points(self, vo, cam_to_map=None, tag=0, seq=0, need_flags=_lib.OBS_INLIER):
         """add_frame with each row's point moved into the map -> (first_row, n_added).  cam_to_map (4, 4) float64 is the pose of the
@@ -427,11 +431,6 @@ class DescriptorIndex:
             raise ValueError("one pixel per query expected")
         return q, p
 
-    @staticmethod
-    def _K9(K):
-        return np.ascontiguousarray(np.asarray(K, np.float32).reshape(-1)[:9]) if np.size(K) == 9 else \
-            np.ascontiguousarray(np.asarray(K, np.float32)[:3, :3]).reshape(9)
-
     def _select(self, query, xy, params, over, guide=None):
         """select's body; guide: None, or (K, R, t, radius) for the guided search"""
         q, p = self._queries(query, xy)
@@ -444,7 +443,7 @@ class DescriptorIndex:
         if guide is None:
             check(lib.svo_desc_index_select(self._h, *tail))
         else:
-            Kf, g = self._K9(guide[0]), self.guide(*guide[1:])
+            Kf, g = _K9(guide[0]), self.guide(*guide[1:])
             check(lib.svo_desc_index_select_guided(self._h, ptr(Kf), C.byref(g), *tail))
         k = k.value
         return dict(query=cq[:k].copy(), row=cr[:k].copy(), xy=cxy[:k].copy(), xyz=cxyz[:k].copy())
@@ -453,7 +452,7 @@ class DescriptorIndex:
         """localize's body; rotation, translation: the extrinsic guess; guide: None, or (R, t, radius) for the guided search"""
         q, p = self._queries(query, xy)
         prm = params if params is not None else self.reloc_params(**over)
-        Kf = self._K9(K)
+        Kf = _K9(K)
         res = _lib.SvoRelocResult()
         res.R[:] = list(np.asarray(rotation, np.float64).reshape(9))
         res.t[:] = list(np.asarray(translation, np.float64).reshape(3))
@@ -501,7 +500,7 @@ class DescriptorIndex:
         (no point, not in front of the camera, not finite in float32) is (+inf, +inf)."""
         hi = self.size if row_hi == -1 else int(row_hi)
         uv = np.zeros((max(hi - int(row_lo), 0), 2), np.float32)
-        Kf, g = self._K9(K), self.guide(R, t, 0.0)
+        Kf, g = _K9(K), self.guide(R, t, 0.0)
         check(lib.svo_desc_index_project(self._h, ptr(Kf), C.byref(g), int(row_lo), int(row_hi), ptr(uv)))
         return uv
 
@@ -510,7 +509,7 @@ class DescriptorIndex:
         (svo_desc_index_match_guided) -> the structured rows match returns"""
         q, p = self._queries(query, xy)
         out = np.zeros(len(q), _lib.DESC_MATCH_DTYPE)
-        Kf, g = self._K9(K), self.guide(R, t, radius)
+        Kf, g = _K9(K), self.guide(R, t, radius)
         check(lib.svo_desc_index_match_guided(self._h, ptr(Kf), C.byref(g), len(q), ptr(q), ptr(p), int(row_lo), int(row_hi), ptr(out)))
         return out
 
@@ -704,6 +703,25 @@ class BatchVisualOdometry:
         self.raw_size = None                          # (raw_w, raw_h) while the context rectifies: frames are then raw
         self.input_format = _lib.INPUT_MONO8          # svo_set_input_format: what the bytes of the caller's frames are
 
+    def _has_context(self):
+        """False for a VisualOdometry before its first frame, and for a closed object"""
+        return bool(self._h.value)
+
+    def _need_frame(self, what, exc=_lib.SvoError, prefix=""):
+        """The context; without one, the error of a call that reads a frame's results"""
+        if not self._has_context():
+            raise exc("%s%s: no frame yet (call stereo_callback first)" % (prefix, what))
+        return self._h
+
+    def _last_rows(self, getter, seq, row_shape, dtype):
+        """The rows of sequence seq in the last collected frame through a (ctx, seq, cap, rows, n_tracks) getter: sized by a first
+        call, filled by a second -> (rows, n_tracks)."""
+        n_tracks = C.c_int(0)
+        check(getter(self._h, seq, 0, None, C.byref(n_tracks)))
+        rows = np.zeros((max(n_tracks.value, 1),) + row_shape, dtype)
+        n = check(getter(self._h, seq, len(rows), ptr(rows), None))
+        return rows[:n].copy(), n_tracks.value
+
     def _in_shape(self):
         """(height, width) of the frames the caller passes: the raw size when rectifying."""
         return (self.raw_size[1], self.raw_size[0]) if self.raw_size else (self.height, self.width)
@@ -771,12 +789,8 @@ class BatchVisualOdometry:
         id, l0, r0, l1, r1, xyz, age, flags, pad), the first min(n_tracks, max_rows) tracks in svo_get_last_tracks' order.
         with_count: -> (rows, n_tracks), the frame's full track count.  Host memory only, no synchronisation
         (svo_get_last_track_obs).  SvoError when that frame was issued with the output off."""
-        n_tracks = C.c_int(0)
-        n = check(lib.svo_get_last_track_obs(self._h, seq, 0, None, C.byref(n_tracks)))
-        rows = np.zeros(max(n_tracks.value, 1), _lib.TRACK_OBS_DTYPE)
-        n = check(lib.svo_get_last_track_obs(self._h, seq, len(rows), ptr(rows), None))
-        rows = rows[:n].copy()
-        return (rows, n_tracks.value) if with_count else rows
+        rows, n_tracks = self._last_rows(lib.svo_get_last_track_obs, seq, (), _lib.TRACK_OBS_DTYPE)
+        return (rows, n_tracks) if with_count else rows
 
     def set_descriptor_output(self, on=True):
         """A 32-byte steered BRIEF descriptor beside every observation row, from the next frame submitted on
@@ -788,11 +802,7 @@ class BatchVisualOdometry:
         """The descriptor rows of sequence seq in the last collected frame -> (n, 32) uint8: row i describes row i of
         last_track_obs(seq).  Host memory only, no synchronisation (svo_get_last_track_descriptors).  SvoError when that frame was
         issued with descriptors off."""
-        n_tracks = C.c_int(0)
-        check(lib.svo_get_last_track_descriptors(self._h, seq, 0, None, C.byref(n_tracks)))
-        desc = np.zeros((max(n_tracks.value, 1), _lib.DESC_BYTES), np.uint8)
-        n = check(lib.svo_get_last_track_descriptors(self._h, seq, len(desc), ptr(desc), None))
-        return desc[:n].copy()
+        return self._last_rows(lib.svo_get_last_track_descriptors, seq, (_lib.DESC_BYTES,), np.uint8)[0]
 
     def feature_ids(self, seq=0):
         """The ids of features(seq)'s entries, in its order (svo_get_feature_ids; synchronises).  SvoError with the output off."""
@@ -922,7 +932,7 @@ class BatchVisualOdometry:
         self.raw_size = None
 
     def close(self):
-        if getattr(self, "_h", None) and self._h.value:
+        if self._has_context():
             lib.svo_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -938,8 +948,17 @@ class BatchVisualOdometry:
         check(lib.svo_set_projection(self._h, seq, ptr(Pl), ptr(Pr)))
         self._Pl = Pl.copy()                          # set_rotation_prior's K
 
+    def _results(self, call):
+        """Run call(T_out, ok_out, stats), one of the entry points that hand a frame's results back -> (ok (n_seq,) bool,
+        T (n_seq, 4, 4) f64), with the frame's counters in self.stats."""
+        T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
+        st = (SvoFrameStats * self.n_seq)()
+        check(call(ptr(T), ptr(ok), st))
+        self.stats = list(st)
+        return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
+
     def _active(self, active):
-        """None, or n_seq truthy flags -> a uint8 array for the masked entry points."""
+        """None (a null list: every sequence takes the frame), or n_seq truthy flags -> a uint8 array for the masked entry points."""
         if active is None:
             return None
         a = np.ascontiguousarray(np.asarray(active).astype(bool), np.uint8)
@@ -959,35 +978,18 @@ class BatchVisualOdometry:
         assert all(i.shape == self._frame_shape() for i in L + R if i is not None), "image shape / channels"
         lp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in L])
         rp = (C.c_void_p * self.n_seq)(*[i.ctypes.data if i is not None else None for i in R])
-        T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
-        st = (SvoFrameStats * self.n_seq)()
-        if act is None:
-            check(lib.svo_process_batch(self._h, lp, rp, self._in_shape()[1] * cn, 0, ptr(T), ptr(ok), st))
-        else:
-            check(lib.svo_process_batch_masked(self._h, lp, rp, self._in_shape()[1] * cn, 0, ptr(act), ptr(T), ptr(ok), st))
-        self.stats = list(st)
-        return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
+        return self._results(lambda *out: lib.svo_process_batch_masked(self._h, lp, rp, self._in_shape()[1] * cn, 0, ptr(act), *out))
 
     def process_device(self, left_ptrs, right_ptrs, stride, active=None):
         """device pointers (ints; None for idle sequences) -> same outputs; inputs stay resident in HBM."""
         act = self._active(active)
         lp = (C.c_void_p * self.n_seq)(*left_ptrs); rp = (C.c_void_p * self.n_seq)(*right_ptrs)
-        T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
-        st = (SvoFrameStats * self.n_seq)()
-        if act is None:
-            check(lib.svo_process_batch(self._h, lp, rp, stride, 1, ptr(T), ptr(ok), st))
-        else:
-            check(lib.svo_process_batch_masked(self._h, lp, rp, stride, 1, ptr(act), ptr(T), ptr(ok), st))
-        self.stats = list(st)
-        return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
+        return self._results(lambda *out: lib.svo_process_batch_masked(self._h, lp, rp, stride, 1, ptr(act), *out))
 
     def submit_device(self, left_ptrs, right_ptrs, stride, active=None):
         act = self._active(active)
         lp = (C.c_void_p * self.n_seq)(*left_ptrs); rp = (C.c_void_p * self.n_seq)(*right_ptrs)
-        if act is None:
-            check(lib.svo_submit_batch(self._h, lp, rp, stride))
-        else:
-            check(lib.svo_submit_batch_masked(self._h, lp, rp, stride, ptr(act)))
+        check(lib.svo_submit_batch_masked(self._h, lp, rp, stride, ptr(act)))
 
     def reset_sequence(self, seq=-1, Pl=None, Pr=None):
         """Return sequence `seq` (-1: all) to a fresh context's state, optionally with new projection matrices (both or
@@ -1001,11 +1003,7 @@ class BatchVisualOdometry:
         check(lib.svo_reset_sequence(self._h, seq, ptr(pl), ptr(pr)))
 
     def collect(self):
-        T = np.zeros((self.n_seq, 16)); ok = np.zeros(self.n_seq, np.int32)
-        st = (SvoFrameStats * self.n_seq)()
-        check(lib.svo_collect(self._h, ptr(T), ptr(ok), st))
-        self.stats = list(st)
-        return ok.astype(bool), T.reshape(self.n_seq, 4, 4)
+        return self._results(lambda *out: lib.svo_collect(self._h, *out))
 
     def set_stage_timing(self, on=True):
         """Record the stage-boundary events of every frame from now on (svo_set_stage_timing): last_timing()'s LK time and
@@ -1031,14 +1029,12 @@ class BatchVisualOdometry:
     def last_frame_path(self):
         """svo_get_last_frame_path: the SVO_PATH_* bits (_lib.PATH_*) of the most recently issued frame — which builds and
         launch shapes it took; 0 before the first frame."""
-        h = getattr(self, "_h", None)                 # a VisualOdometry exists from its first frame on
-        return lib.svo_get_last_frame_path(h) if h is not None and h.value else 0
+        return lib.svo_get_last_frame_path(self._h) if self._has_context() else 0
 
     def lk_registers_left(self):
         """svo_get_lk_registers_left: VGPRs a SIMD keeps beside this context's LK waves (>= 96: a shared device runs the
         96-register f64 builds)."""
-        h = getattr(self, "_h", None)
-        return lib.svo_get_lk_registers_left(h) if h is not None and h.value else -1
+        return lib.svo_get_lk_registers_left(self._h) if self._has_context() else -1
 
     def features(self, seq=0):
         cap = 1 << 15
@@ -1089,215 +1085,202 @@ class BatchVisualOdometry:
         return nl.value
 
 
+def _deferrable(slot):
+    """A VisualOdometry setter that may come before the first frame.  With a context it is BatchVisualOdometry's setter of the same
+    name.  Without one the decorated body checks the arguments as the library would, at once, and returns those to hold for that
+    setter in the slot (None: nothing, the slot is emptied); VisualOdometry._apply hands them over when the first frame comes."""
+    def wrap(check):
+        setter = getattr(BatchVisualOdometry, check.__name__)
+
+        @functools.wraps(setter)
+        def method(self, *args, **kw):
+            if self._has_context():
+                return setter(self, *args, **kw)
+            held = check(self, *args, **kw)
+            self._held.pop(slot, None)
+            if held is not None:
+                self._held[slot] = (check.__name__, held)
+        return method
+    return wrap
+
+
+def _after_first_frame(getter):
+    """A BatchVisualOdometry getter of a frame's results as VisualOdometry has it: SvoError before the first frame."""
+    @functools.wraps(getter)
+    def method(self, *args, **kw):
+        self._need_frame(getter.__name__)
+        return getter(self, *args, **kw)
+    return method
+
+
 class VisualOdometry(BatchVisualOdometry):
     """vo.h:231-380 — one stereo stream.  stereo_callback(left, right) -> (success, 4x4 float64)."""
 
     def __init__(self, width=None, height=None, cfg=None, device=0):
         self._args = (cfg, device)
-        self._created = False
+        self._h = C.c_void_p()                        # no context before the first frame, unless the size is given here
+        self._held = {}                               # slot -> (setter's name, its arguments): asked for before the context exists
+        self.raw_size = None
         if width is not None:
             super().__init__(width, height, 1, cfg, device)
-            self._created = True
-        # settings asked for before the context exists: held here (None: not asked for), applied by _apply_pending at the first frame
-        self._P = None                                # projection matrices (kept: set_rotation_prior reads them)
-        self._timing = None
-        self._rect = None                             # ("info", left, right) or ("maps", maps, raw_size)
-        self._cov = None                              # (mode, pixel_sigma)
-        self._mask = None
-        self._clahe = None                            # (clip_limit, tiles_x, tiles_y)
-        self._track_rows = None                       # the track output's max_rows
-        self._desc = False                            # descriptors beside the track output
-        self._prior = None                            # (H, Hi): an explicit prior, consumed by the first frame
-        self._prior_mode = None
-        self.raw_size = None
-        if not self._created:
-            self.input_format = _lib.INPUT_MONO8      # a format set before the context exists is applied at creation, too
 
-    def set_stage_timing(self, on=True):
-        self._timing = bool(on)
-        if self._created:
-            super().set_stage_timing(on)
+    # ---- settings before the first frame (DESIGN.md, "Facades: settings before the first frame").  The slots, in the order _apply
+    # hands them to the new context: CLAHE's fit check must see the raw size, so it follows the rectification; the descriptors ride
+    # on the track output; the explicit prior is consumed by the first frame.  Below, each slot's setters with their checks.
+    _ORDER = ("rectification", "projection", "timing", "format", "covariance", "mask", "clahe", "track", "descriptors", "prior", "prior_mode")
 
-    def initalize_projection_matricies(self, leftCameraProjection, rightCameraProjection, seq=-1):
-        self._P = (leftCameraProjection, rightCameraProjection)
-        if self._created:
-            super().initalize_projection_matricies(leftCameraProjection, rightCameraProjection)
-
+    @_deferrable("rectification")
     def set_rectification(self, left_info, right_info, seq=-1):
-        if self._created:
-            return super().set_rectification(left_info, right_info, seq)
-        self._rect = ("info", left_info, right_info)  # the rectified size is then the raw size (as ROS's image_rect)
+        return left_info, right_info                  # the rectified size is then the raw size (as ROS's image_rect)
 
+    @_deferrable("rectification")
     def set_rectification_maps(self, map1_l, map2_l, map1_r, map2_r, seq=-1, raw_size=None):
-        if self._created:
-            return super().set_rectification_maps(map1_l, map2_l, map1_r, map2_r, seq, raw_size)
         if raw_size is None:
             raise ValueError("raw_size = (raw_w, raw_h) is required for the first maps")
-        self._rect = ("maps", (map1_l, map2_l, map1_r, map2_r), raw_size)
+        return map1_l, map2_l, map1_r, map2_r, -1, raw_size           # the context's size is then the maps'
 
+    @_deferrable("rectification")
     def clear_rectification(self):
-        self._rect = None
-        if self._created:
-            super().clear_rectification()
+        return None
 
+    @_deferrable("projection")
+    def initalize_projection_matricies(self, leftCameraProjection, rightCameraProjection, seq=-1):
+        return leftCameraProjection, rightCameraProjection
+
+    @_deferrable("timing")
+    def set_stage_timing(self, on=True):
+        return (bool(on),)
+
+    @_deferrable("format")
     def set_input_format(self, fmt):
-        if self._created:
-            return super().set_input_format(fmt)
-        self.input_format = _lib.input_format(fmt)
+        f = _lib.input_format(fmt)
+        return (f,) if f != _lib.INPUT_MONO8 else None                # mono8 is a new context's format (and a BGR context takes no setter)
 
+    @_deferrable("covariance")
     def set_pose_covariance(self, mode="residual", pixel_sigma=1.0):
-        if self._created:
-            return super().set_pose_covariance(mode, pixel_sigma)
-        self._cov = _lib.check_cov(mode, pixel_sigma)                 # checked now, as the library will: not inside the first frame
+        return _lib.check_cov(mode, pixel_sigma)
 
-    def set_clahe(self, clip_limit=2.0, tiles=(8, 8)):
-        if self._created:
-            return super().set_clahe(clip_limit, tiles)
-        self._clahe = _lib.check_clahe(clip_limit, tiles)             # the fit to the frame size is checked at the first frame
-
-    def clear_clahe(self):
-        self._clahe = None
-        if self._created:
-            super().clear_clahe()
-
-    def set_track_output(self, max_rows):
-        if self._created:
-            return super().set_track_output(max_rows)
-        if int(max_rows) < 1:
-            raise ValueError("max_rows must be >= 1")
-        self._track_rows = int(max_rows)
-
-    def clear_track_output(self):
-        self._track_rows = None
-        self._desc = False                                            # the descriptors ride on the track output
-        if self._created:
-            super().clear_track_output()
-
-    def last_track_obs(self, seq=0, with_count=False):
-        if not self._created:
-            raise _lib.SvoError("last_track_obs: no frame yet (call stereo_callback first)")
-        return super().last_track_obs(seq, with_count)
-
-    def set_descriptor_output(self, on=True):
-        if self._created:
-            return super().set_descriptor_output(on)
-        if on and self._track_rows is None:
-            raise _lib.SvoError("set_descriptor_output: the track output is off (set_track_output first)")
-        self._desc = bool(on)                                         # applied, behind the track output, when the first frame creates the context
-
-    def last_track_descriptors(self, seq=0):
-        if not self._created:
-            raise _lib.SvoError("last_track_descriptors: no frame yet (call stereo_callback first)")
-        return super().last_track_descriptors(seq)
-
-    def feature_ids(self, seq=0):
-        if not self._created:
-            raise _lib.SvoError("feature_ids: no frame yet (call stereo_callback first)")
-        return super().feature_ids(seq)
-
+    @_deferrable("mask")
     def set_detection_mask(self, mask, seq=-1):
-        if self._created:
-            return super().set_detection_mask(mask, seq)
         if mask is not None and (not hasattr(mask, "ndim") or mask.ndim != 2 or "uint8" not in str(mask.dtype)):
             raise ValueError("detection mask: a 2-D uint8 array expected")
-        self._mask = mask                                             # its size is checked against the first frame's
+        return (mask,) if mask is not None else None                  # its size is checked against the first frame's
 
+    @_deferrable("mask")
     def clear_detection_mask(self, seq=-1):
-        self._mask = None
-        if self._created:
-            super().clear_detection_mask(seq)
+        return None
 
-    def detection_mask(self, seq=-1):
-        if not self._created:
-            return None if self._mask is None else np.array(self._mask.cpu() if hasattr(self._mask, "cpu") else self._mask, np.uint8)
-        return super().detection_mask(seq)
+    @_deferrable("clahe")
+    def set_clahe(self, clip_limit=2.0, tiles=(8, 8)):
+        clip, tx, ty = _lib.check_clahe(clip_limit, tiles)            # the fit to the frame size is checked at the first frame
+        return clip, (tx, ty)
 
-    def last_pose_covariance(self):
-        if not self._created:
-            raise _lib.SvoError("last_pose_covariance: no frame yet (call stereo_callback first)")
-        return super().last_pose_covariance()
+    @_deferrable("clahe")
+    def clear_clahe(self):
+        return None
 
+    @_deferrable("track")
+    def set_track_output(self, max_rows):
+        if int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        return (int(max_rows),)
+
+    @_deferrable("track")
+    def clear_track_output(self):
+        self._held.pop("descriptors", None)                           # the descriptors ride on the track output
+        return None
+
+    @_deferrable("descriptors")
+    def set_descriptor_output(self, on=True):
+        if on and "track" not in self._held:
+            raise _lib.SvoError("set_descriptor_output: the track output is off (set_track_output first)")
+        return (True,) if on else None
+
+    @_deferrable("prior")
     def set_motion_prior(self, H, Hi=None, seq=-1):
-        if self._created:
-            return super().set_motion_prior(H, Hi, seq)
-        # before the first frame: held, handed to the context when it is created — and consumed, unused, by that first frame
-        self._prior = None if H is None else (_h9(H, "H").copy(), None if Hi is None else _h9(Hi, "Hi").copy())
+        return None if H is None else (_h9(H, "H").copy(), None if Hi is None else _h9(Hi, "Hi").copy())
 
+    @_deferrable("prior_mode")
     def set_motion_prior_mode(self, mode):
-        if self._created:
-            return super().set_motion_prior_mode(mode)
         if mode not in _lib.PRIOR_MODES:
             raise ValueError("motion prior mode: one of %s expected" % sorted(_lib.PRIOR_MODES))
-        self._prior_mode = mode                                       # applied when the first frame creates the context
+        return (mode,)
+
+    def _apply(self, ctx):
+        """Hand ctx, a context just created, every held setting in _ORDER.  Like the reference, a first frame needs no projection
+        matrices (vo.cpp:47-56 only caches): until initalize_projection_matricies is called they are all-zero, as the reference's
+        empty Mats effectively are."""
+        zero = np.zeros(12, np.float32)
+        held = dict(self._held)
+        held.setdefault("projection", ("initalize_projection_matricies", (zero, zero)))
+        for slot in self._ORDER:
+            if slot in held:
+                setter, args = held[slot]
+                getattr(ctx, setter)(*args)
+
+    def _first_frame(self, L, colour):
+        """The reference learns the image size (and type) from the first frame: create the context at that size, _apply the held
+        settings to it, and only then adopt it.  A setting the context refuses (CLAHE tiles that do not fit this size, ...)
+        raises with the object still before its first frame and its record intact: correct the setting, pass the frame again."""
+        cfg, device = self._args
+        cfg = _lib.copy_config(cfg) if cfg is not None else default_config()       # never write into the caller's struct
+        cfg.channels = 3 if colour else 1                 # colour Mats, as the reference CLI feeds them (main.cpp:38-46)
+        h, w = L.shape[:2]
+        setter, args = self._held.get("rectification", (None, None))
+        if setter == "set_rectification_maps":
+            h, w = np.asarray(args[1]).shape
+        ctx = BatchVisualOdometry(w, h, 1, cfg, device)
+        try:
+            self._apply(ctx)
+        except Exception:
+            ctx.close()
+            raise
+        self.__dict__.update(vars(ctx))                   # the context and what BatchVisualOdometry knows about it
+        ctx._h = C.c_void_p()                             # (ctx no longer owns it)
+        self._held = {}
+
+    def _held_args(self, slot):
+        """What the slot holds before the first frame, or None"""
+        return self._held[slot][1] if slot in self._held else None
+
+    last_track_obs = _after_first_frame(BatchVisualOdometry.last_track_obs)
+    last_track_descriptors = _after_first_frame(BatchVisualOdometry.last_track_descriptors)
+    feature_ids = _after_first_frame(BatchVisualOdometry.feature_ids)
+    last_pose_covariance = _after_first_frame(BatchVisualOdometry.last_pose_covariance)
+    last_motion_prior = _after_first_frame(BatchVisualOdometry.last_motion_prior)
+
+    def pyramid(self, seq=0, which="t1", cam=0, level=0, plane=0):
+        self._need_frame("pyramid", RuntimeError)
+        return super().pyramid(seq, which, cam, level, plane)
+
+    def detection_mask(self, seq=-1):
+        if self._has_context():
+            return super().detection_mask(seq)
+        m = self._held_args("mask")
+        return None if m is None else np.array(m[0].cpu() if hasattr(m[0], "cpu") else m[0], np.uint8)
 
     def motion_prior_mode(self):
-        return super().motion_prior_mode() if self._created else (self._prior_mode or "explicit")
-
-    def last_motion_prior(self, seq=0):
-        if not self._created:
-            raise _lib.SvoError("last_motion_prior: no frame yet (call stereo_callback first)")
-        return super().last_motion_prior(seq)
-
-    def set_rotation_prior(self, R, seq=-1, Pl=None):
-        if Pl is None and self._P is not None:
-            Pl = self._P[0]
-        return super().set_rotation_prior(R, seq, Pl)
+        return super().motion_prior_mode() if self._has_context() else (self._held_args("prior_mode") or ("explicit",))[0]
 
     def motion_prior(self, seq=0):
-        if not self._created:
-            p = self._prior
-            if p is None:
-                return None
-            return p[0].reshape(3, 3), (p[1].reshape(3, 3) if p[1] is not None else None)
-        return super().motion_prior(seq)
+        if self._has_context():
+            return super().motion_prior(seq)
+        p = self._held_args("prior")
+        return None if p is None else (p[0].reshape(3, 3), p[1].reshape(3, 3) if p[1] is not None else None)
 
-    def _apply_pending(self, fmt):
-        """Hand the context, just created, what was asked for before it existed — in this order (the track output before the
-        descriptors that ride on it; the explicit prior is consumed)."""
-        if self._rect is not None:
-            if self._rect[0] == "info":
-                super().set_rectification(self._rect[1], self._rect[2])
-            else:
-                super().set_rectification_maps(*self._rect[1], raw_size=self._rect[2])
-        # like the reference, a first frame needs no projection matrices (vo.cpp:47-56 only caches); until
-        # initalize_projection_matricies is called they are all-zero, as the reference's empty Mats effectively are
-        super().initalize_projection_matricies(*(self._P if self._P is not None else (np.zeros(12, np.float32), np.zeros(12, np.float32))))
-        if self._timing is not None:
-            super().set_stage_timing(self._timing)
-        if fmt != _lib.INPUT_MONO8:
-            super().set_input_format(fmt)             # (BatchVisualOdometry.__init__ reset the attribute)
-        if self._cov is not None:
-            super().set_pose_covariance(*self._cov)
-        if self._mask is not None:
-            super().set_detection_mask(self._mask)
-        if self._clahe is not None:
-            super().set_clahe(self._clahe[0], self._clahe[1:])
-        if self._track_rows is not None:
-            super().set_track_output(self._track_rows)
-            if self._desc:
-                super().set_descriptor_output(True)
-        if self._prior is not None:
-            super().set_motion_prior(self._prior[0], self._prior[1])
-            self._prior = None
-        if self._prior_mode is not None:
-            super().set_motion_prior_mode(self._prior_mode)
+    def set_rotation_prior(self, R, seq=-1, Pl=None):
+        if Pl is None and not self._has_context() and "projection" in self._held:
+            Pl = self._held_args("projection")[0]
+        return super().set_rotation_prior(R, seq, Pl)
 
     def stereo_callback(self, image_left, image_right):
-        fmt = self.input_format
+        fmt = self.input_format if self._has_context() else (self._held_args("format") or (_lib.INPUT_MONO8,))[0]
         bpp = _lib.INPUT_BPP[fmt] if fmt != _lib.INPUT_MONO8 else None
-        if self._created and self.cfg.channels == 3:
+        if self._has_context() and self.cfg.channels == 3:
             bpp = None
         L, R = u8frame(image_left, bpp), u8frame(image_right, bpp)
-        if not self._created:                         # the reference learns the image size (and type) from the first frame
-            cfg, device = self._args
-            cfg = _lib.copy_config(cfg) if cfg is not None else default_config()       # never write into the caller's struct
-            cfg.channels = 3 if L.ndim == 3 and bpp is None else 1    # colour Mats, as the reference CLI feeds them (main.cpp:38-46)
-            w, h = L.shape[1], L.shape[0]
-            if self._rect is not None and self._rect[0] == "maps":
-                h, w = np.asarray(self._rect[1][1]).shape
-            super().__init__(w, h, 1, cfg, device)
-            self._created = True
-            self._apply_pending(fmt)
+        if not self._has_context():
+            self._first_frame(L, colour=L.ndim == 3 and bpp is None)
         self._check_frame(L, "left"); self._check_frame(R, "right")
         T = np.zeros(16)
         st = SvoFrameStats()
@@ -1305,15 +1288,10 @@ class VisualOdometry(BatchVisualOdometry):
         self.stats = st
         return bool(rc), T.reshape(4, 4)
 
-    def pyramid(self, seq=0, which="t1", cam=0, level=0, plane=0):
-        if not self._created:
-            raise RuntimeError("pyramid: no frame yet (call stereo_callback first)")
-        return super().pyramid(seq, which, cam, level, plane)
-
     def reset(self):
         """Start over as a freshly constructed object with the same projection matrices: the next stereo_callback is a first
         frame.  The reference has no counterpart (it constructs a new VisualOdometry); this wraps svo_reset_sequence."""
-        if self._created:
+        if self._has_context():
             self.reset_sequence(0)
 
     def _check_frame(self, img, which):
@@ -1332,7 +1310,7 @@ class VisualOdometry(BatchVisualOdometry):
         empty = np.zeros((0, 2), np.float32)
         if len(p0) == 0:
             return p0, empty, empty, empty                                                  # vo.cpp:179-181
-        if not self._created:
+        if not self._has_context():
             raise RuntimeError("circularMatching: no cached pyramids (call stereo_callback first)")
         l1, r1 = self._frame(imgLeftT1), self._frame(imgRightT1)
         self._check_frame(l1, "left"); self._check_frame(r1, "right")

@@ -25,6 +25,50 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.EXPORTS) == syms
 
 
+def header_prototypes():
+    """Every `ret name(args);` of include/svo.h -> {name: (ret, [arg, ...])}: ret is "int", "void", "void*" or "const char*"; an arg is
+    "*" for a pointer or an array, else its scalar type's name."""
+    txt = open(os.path.join(ROOT, "include", "svo.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    protos = {}
+    for ret, name, args in re.findall(r"^[ \t]*((?:const\s+)?\w+\s*\*?)\s*(svo_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", txt, flags=re.M):
+        assert name not in protos, name
+        kinds = []
+        for a in (" ".join(a.split()) for a in args.split(",")):
+            if a == "void":
+                continue
+            words = [w for w in a.split()[:-1] if w != "const"]              # the last word is the argument's name
+            kinds.append("*" if "*" in a or "[" in a else words[0])
+            assert kinds[-1] == "*" or len(words) == 1, a
+        protos[name] = (re.sub(r"\s*\*", "*", ret.strip()), kinds)
+    return protos
+
+
+def test_prototype_table_matches_the_header():
+    """_lib.PROTOTYPES, the one place the binding's restype / argtypes come from, against every prototype of include/svo.h: the same
+    functions in the same order, the same number of arguments, and per argument and for the return the ctypes type of the C type."""
+    from stereo_visual_odometry_amd import _lib
+    scalars = {"int": C.c_int32, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "size_t": C.c_size_t,
+               "float": C.c_float, "double": C.c_double}
+    returns = {"int": C.c_int, "void": None, "void*": C.c_void_p, "const char*": C.c_char_p}
+    protos = header_prototypes()
+    assert len(protos) >= 93 and sorted(protos) == header_symbols()
+    assert list(_lib.PROTOTYPES) == list(protos)
+    assert C.sizeof(C.c_int) == 4
+    for name, (ret, kinds) in protos.items():
+        restype, argtypes = _lib.PROTOTYPES[name]
+        fn = getattr(_lib.lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name       # the table is what is installed
+        assert restype is returns[ret], (name, ret, restype)
+        assert len(argtypes) == len(kinds), (name, len(argtypes), len(kinds))
+        for i, (kind, t) in enumerate(zip(kinds, argtypes)):
+            if kind == "*":
+                assert t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer), (name, i, t)
+            else:
+                assert t is scalars[kind], (name, i, kind, t)
+
+
 def test_config_default_matches_reference_constants():
     from stereo_visual_odometry_amd import _lib
     c = _lib.default_config()
