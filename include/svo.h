@@ -28,7 +28,8 @@ typedef enum {
     SVO_ERR_ARG = -1,      /* bad argument (null pointer, size mismatch, unsupported window ...) */
     SVO_ERR_HIP = -2,      /* HIP runtime error / no device; svo_last_error() has the text */
     SVO_ERR_CAPACITY = -3, /* input exceeds the capacity the context was created with */
-    SVO_ERR_STATE = -4     /* call order violated (e.g. projection not set) */
+    SVO_ERR_STATE = -4,    /* call order violated (e.g. projection not set) */
+    SVO_ERR_INTERNAL = -5  /* the library found a state it rules out ("Index maintenance": the latest-per-id table overflowed) */
 } svo_status;
 
 /* The reference's compile-time constants (include/vo.h:53-127, 251-252; src/vo.cpp:183-184, 295)
@@ -662,6 +663,70 @@ int svo_desc_index_localize_guided(svo_desc_index* index, const float K[9], cons
  * ties by j) and lets lane `slot` serve the slot-th query of that order; everything it returns is under the queries' own numbers.
  * on = 0 serves the queries in the caller's order instead (default: on).  The results do not depend on it. */
 int svo_desc_index_set_guided_sort(svo_desc_index* index, int on);
+
+/* ---- Index maintenance: retire rows and move points on the device ---------------------------------------------------------------
+ * A map forgets and is corrected.  svo_desc_index_retire drops rows anywhere in the index and closes the gaps in place;
+ * svo_desc_index_transform_points moves the points of a span of rows through a 4 x 4 transform (a loop closure's correction, a
+ * merged map's alignment).  Both run on the device, are synchronous, wait for the index's own stream only and are legal with frames
+ * in flight; a refused call changes nothing.
+ *
+ * The retire rule.  Let n0 be the size before the call and S = [row_lo, row_hi) the scope (row_hi = -1: n0).
+ *   alive1(r):  r in S, SVO_RETIRE_SCOPE is clear, with SVO_RETIRE_BY_TAG tag_lo <= tag[r] <= tag_hi (plain int32 compares; a row
+ *               without a point has the tag SVO_POINT_NONE = -1), and with SVO_RETIRE_BY_IDS id[r] is not among ids[0 .. n_ids).
+ *   keep(r):    r is not in S; or alive1(r) and — with SVO_RETIRE_LATEST_PER_ID — there is no r' > r with alive1(r') and
+ *               id[r'] == id[r].  "Latest" is decided among the scope's survivors of the other rules only.
+ *   kept_before[r] = #{r' < r : keep(r')} for r = 0 .. n0; the new size is kept_before[n0].
+ * A kept row r becomes row kept_before[r]: its descriptor, its id and (where the index has points) its point are carried bit for
+ * bit, and the order of the rows is preserved.  kept_before is the whole remapping: a stored row number or frame boundary f becomes
+ * kept_before[f], and row r was kept iff kept_before[r + 1] > kept_before[r].  flags == 0 keeps everything and is legal; a window
+ * with tag_lo > tag_hi drops the scope, as SVO_RETIRE_SCOPE does (one frame's rows: [first_row[k], first_row[k + 1])).
+ * SVO_ERR_STATE: SVO_RETIRE_BY_TAG on an index without points.  SVO_ERR_ARG: unknown flag bits; a scope that svo_desc_index_match
+ * refuses as a row range; n_ids < 0 or > 1 << 24; SVO_RETIRE_BY_IDS with ids == NULL and n_ids > 0.  SVO_ERR_INTERNAL: the
+ * latest-per-id table overflowed, which its size rules out; nothing was changed.
+ *
+ * The transform rule.  Row r is selected when r is in [row_lo, row_hi) and tag_lo <= tag[r] <= tag_hi with tag[r] != SVO_POINT_NONE.
+ * Coordinate c (0, 1, 2) of a selected row's point (x, y, z) becomes f32(((T[4c] x + T[4c+1] y) + T[4c+2] z) + T[4c+3]), evaluated
+ * in f64, every operation rounded on its own, left to right, without contraction: svo_desc_index_add_frame_points' formula.  A
+ * selected row whose result has a non-finite coordinate is left as it is and counted in *n_skipped — the index never holds a
+ * non-finite point; the other selected rows are counted in *n_moved (either may be NULL).  Tags, ids and descriptors are untouched.
+ * SVO_ERR_ARG: a non-finite entry of T, a bad row range.  SVO_ERR_STATE: an index without points.
+ *
+ * Memory.  There is no second copy of the index.  A retire call works in a scratch the index owns; with m the scope's rows,
+ * R(b) = b rounded up to a multiple of 256 and slots(m) the smallest power of two >= max(2, 2 m), a call needs
+ *   need = R(m) + R(4 (m + 1)) + R(4 (ceil(m / 256) + 257)) + [LATEST_PER_ID: R(4 slots(m))] + [BY_IDS: R(8 n_ids)]
+ *          + R(56 min(retire_slab_rows, n0 - row_lo))
+ * bytes: the keep flags, the ranks, the block counts, the latest-per-id table, the sorted id list and the bounce buffer through
+ * which one slab of rows moves (rows are compacted slab after slab in row order, so nothing is read after it could have been
+ * overwritten).  The scratch is 64 KiB times a power of two, the smallest that holds the largest call so far: at most
+ * max(65 536, 2 need - 1) bytes.  It at least doubles when it grows, so an index retired again and again as it grows allocates
+ * O(log size) times; outgrown buffers are freed with the index and sum to less than the one in use.  flags == 0 and an empty scope
+ * need nothing.  kept_before reaches the host in pieces through the index's pinned staging, and only when it is asked for. */
+#define SVO_RETIRE_BY_TAG        1   /* drop rows of the scope whose tag is outside [tag_lo, tag_hi] */
+#define SVO_RETIRE_BY_IDS        2   /* drop rows of the scope whose id is in ids[0 .. n_ids) */
+#define SVO_RETIRE_LATEST_PER_ID 4   /* of the rows of the scope that survive the two rules above, keep per id only the newest */
+#define SVO_RETIRE_SCOPE         8   /* drop every row of the scope */
+typedef struct {
+    uint32_t flags;                  /* SVO_RETIRE_* bits */
+    int32_t  row_lo, row_hi;         /* the scope [row_lo, row_hi), row_hi = -1: the size; rows outside it are kept */
+    int32_t  tag_lo, tag_hi;         /* SVO_RETIRE_BY_TAG: inclusive */
+    int32_t  n_ids;                  /* 0 .. 1 << 24 */
+    const uint64_t* ids;             /* SVO_RETIRE_BY_IDS: host memory, any order, duplicates allowed */
+} svo_retire_rule;
+typedef struct {
+    float    last_kernels_ms;        /* the device time of the last retire's or transform's kernels (svo_desc_index_set_timing on; else 0) */
+    int32_t  scratch_allocations;    /* how often the retire scratch was allocated */
+    uint64_t scratch_bytes, scratch_bytes_outgrown;
+} svo_desc_retire_stats;
+/* kept_before: size-before-the-call + 1 entries, or NULL; *n_kept (may be NULL): the new size */
+int svo_desc_index_retire(svo_desc_index* index, const svo_retire_rule* rule, int32_t* kept_before, int* n_kept);
+/* T: 16 doubles, row-major 4 x 4; row_hi = -1: the index's size */
+int svo_desc_index_transform_points(svo_desc_index* index, const double T[16], int row_lo, int row_hi, int32_t tag_lo, int32_t tag_hi,
+                                    int* n_moved, int* n_skipped);
+/* Tuning: the rows of one slab of retire's compaction (0 = the default, 262 144: a bounce buffer of 14 MiB at most).  The results
+ * do not depend on it.  SVO_ERR_ARG: rows < 0 or > 1 << 24. */
+int svo_desc_index_set_retire_slab_rows(svo_desc_index* index, int rows);
+int svo_desc_index_get_retire_slab_rows(const svo_desc_index* index);
+int svo_desc_index_get_retire_stats(const svo_desc_index* index, svo_desc_retire_stats* stats);
 
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.

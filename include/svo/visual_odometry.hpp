@@ -593,6 +593,29 @@ class DescriptorIndex {
         return localize_("localize_guided", K, &g, query, xy, params, result, candidates);
     }
     void set_guided_sort(bool on) { svo_throw(svo_desc_index_set_guided_sort(index_, on ? 1 : 0)); }
+    // ---- index maintenance (svo.h, "Index maintenance"): drop rows anywhere and move points, both on the device
+    // a rule over the scope [row_lo, row_hi) with no flag set: set flags, the tag window and the id list (which must outlive the call)
+    static svo_retire_rule retire_rule(int row_lo = 0, int row_hi = -1) {
+        svo_retire_rule r;
+        r.flags = 0; r.row_lo = row_lo; r.row_hi = row_hi; r.tag_lo = 0; r.tag_hi = 0; r.n_ids = 0; r.ids = nullptr;
+        return r;
+    }
+    // drop what the rule says and close the gaps in place -> kept_before, size-before + 1 entries: row r became row kept_before[r],
+    // and the last entry is the new size
+    std::vector<int32_t> retire(const svo_retire_rule& rule) {
+        std::vector<int32_t> kept_before((size_t)size() + 1);
+        svo_throw(svo_desc_index_retire(index_, &rule, kept_before.data(), nullptr));
+        return kept_before;
+    }
+    // the points of rows [rows.first, rows.second) whose tag lies in [tags.first, tags.second] through T (row-major 4 x 4)
+    // -> {moved, skipped}: a skipped row's result was not finite in float and the row is unchanged
+    std::pair<int, int> transform_points(const double T[16], std::pair<int, int> rows = {0, -1}, std::pair<int32_t, int32_t> tags = {0, INT32_MAX}) {
+        int moved = 0, skipped = 0;
+        svo_throw(svo_desc_index_transform_points(index_, T, rows.first, rows.second, tags.first, tags.second, &moved, &skipped));
+        return {moved, skipped};
+    }
+    int retire_slab_rows() const { return svo_desc_index_get_retire_slab_rows(index_); }
+    void retire_slab_rows(int rows) { svo_throw(svo_desc_index_set_retire_slab_rows(index_, rows)); }   // 0: the default
     int size() const { return svo_desc_index_size(index_); }
     void truncate(int n_rows) { svo_throw(svo_desc_index_truncate(index_, n_rows)); }
     svo_desc_index* handle() { return index_; }

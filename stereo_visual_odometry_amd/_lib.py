@@ -29,7 +29,7 @@ if not os.environ.get("SVO_NO_TORCH_PRELOAD"):
 
 lib = C.CDLL(LIB_PATH)
 
-SVO_OK, SVO_ERR_ARG, SVO_ERR_HIP, SVO_ERR_CAPACITY, SVO_ERR_STATE = 0, -1, -2, -3, -4
+SVO_OK, SVO_ERR_ARG, SVO_ERR_HIP, SVO_ERR_CAPACITY, SVO_ERR_STATE, SVO_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
 # svo_get_last_frame_path bits (svo.h SVO_PATH_*)
 PATH_LEAN, PATH_LK_CHAINED, PATH_INGEST_AHEAD, PATH_FRONT_FUSED, PATH_TRI_EPNP_FUSED, PATH_GRAPH = 1, 2, 4, 8, 16, 32
 PATH_INPUT_CONVERTED, PATH_POSE_COV, PATH_DETECT_MASKED, PATH_CLAHE, PATH_TRACK_IDS = 64, 128, 256, 512, 1024
@@ -39,6 +39,8 @@ OBS_INLIER, OBS_HAS_XYZ = 1, 2
 DESC_BYTES = 32
 MATCH_NONE, MATCH_NO_DIST = -1, 257
 POINT_NONE, RELOC_MAX_QUERIES = -1, 4096
+# index maintenance (svo.h SVO_RETIRE_*)
+RETIRE_BY_TAG, RETIRE_BY_IDS, RETIRE_LATEST_PER_ID, RETIRE_SCOPE = 1, 2, 4, 8
 # motion priors (svo.h SVO_PRIOR_*)
 PRIOR_EXPLICIT, PRIOR_LAST_ROTATION = 0, 1
 PRIOR_MODES = {"explicit": PRIOR_EXPLICIT, "last_rotation": PRIOR_LAST_ROTATION}
@@ -120,6 +122,15 @@ class SvoRelocGuide(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("radius", C.c_float), ("reserved", C.c_int32)]
 
 
+class SvoRetireRule(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("row_lo", C.c_int32), ("row_hi", C.c_int32), ("tag_lo", C.c_int32), ("tag_hi", C.c_int32),
+                ("n_ids", C.c_int32), ("ids", C.c_void_p)]
+
+
+class SvoDescRetireStats(C.Structure):
+    _fields_ = SvoDescIndexStats._fields_
+
+
 # Every function include/svo.h declares, in its order: name -> (restype, argtypes).  tests/test_abi.py parses the header and compares
 # it with this table argument by argument.  Every pointer or array argument is P: an array's ptr(), C.byref(x), a ctypes array, None
 # or a raw address (a tensor's data_ptr()).
@@ -180,6 +191,11 @@ PROTOTYPES = {
     "svo_desc_index_select_guided": (I, (P, P, P, I, P, P, P, P, P, P, P, P)),
     "svo_desc_index_localize_guided": (I, (P, P, P, I, P, P, P, P, P, P, P)),
     "svo_desc_index_set_guided_sort": (I, (P, I)),
+    "svo_desc_index_retire": (I, (P, P, P, P)),
+    "svo_desc_index_transform_points": (I, (P, P, I, I, I32, I32, P, P)),
+    "svo_desc_index_set_retire_slab_rows": (I, (P, I)),
+    "svo_desc_index_get_retire_slab_rows": (I, (P,)),
+    "svo_desc_index_get_retire_stats": (I, (P, P)),
     "svo_set_detection_mask": (I, (P, I, P, I, I)),
     "svo_get_detection_mask": (I, (P, I, P, P)),
     "svo_set_motion_prior": (I, (P, I, P, P)),

@@ -582,6 +582,57 @@ class DescriptorIndex:
         check(lib.svo_desc_index_get_stats(self._h, C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in st._fields_}
 
+    # ---- index maintenance (svo.h, "Index maintenance"): drop rows anywhere, move points, both on the device
+    def retire(self, rows=(0, -1), tags=None, drop_ids=None, latest_per_id=False, scope=False, want_map=True):
+        """Drop rows of the scope rows = (row_lo, row_hi) and close the gaps in place (svo_desc_index_retire): tags = (tag_lo, tag_hi)
+        keeps the scope's rows whose tag is inside the inclusive window, drop_ids drops those whose id is listed, latest_per_id keeps
+        per id only the newest of the survivors, scope drops the whole scope.  -> kept_before (size before + 1,) int32, the remapping
+        of every stored row number (its last entry is the new size), or with want_map False the new size alone."""
+        rule = _lib.SvoRetireRule()
+        rule.row_lo, rule.row_hi = int(rows[0]), int(rows[1])
+        ids = None
+        if tags is not None:
+            rule.flags |= _lib.RETIRE_BY_TAG
+            rule.tag_lo, rule.tag_hi = int(tags[0]), int(tags[1])
+        if drop_ids is not None:
+            rule.flags |= _lib.RETIRE_BY_IDS
+            ids = np.ascontiguousarray(drop_ids).astype(np.uint64, copy=False).reshape(-1)
+            rule.n_ids, rule.ids = len(ids), (ids.ctypes.data if len(ids) else None)   # ids stays alive until the call returns
+        if latest_per_id:
+            rule.flags |= _lib.RETIRE_LATEST_PER_ID
+        if scope:
+            rule.flags |= _lib.RETIRE_SCOPE
+        kept_before = np.zeros(self.size + 1, np.int32) if want_map else None
+        n_kept = C.c_int(0)
+        check(lib.svo_desc_index_retire(self._h, C.byref(rule), ptr(kept_before), C.byref(n_kept)))
+        return kept_before if want_map else n_kept.value
+
+    def transform_points(self, T, rows=(0, -1), tags=None):
+        """Move the points of the rows of rows = (row_lo, row_hi) whose tag lies in tags = (tag_lo, tag_hi) (None: every row with a
+        point) through T (4, 4) float64 (svo_desc_index_transform_points) -> (n_moved, n_skipped); a skipped row's result was not
+        finite in float32 and the row is unchanged."""
+        M = np.ascontiguousarray(T, np.float64).reshape(16)
+        lo, hi = (0, np.iinfo(np.int32).max) if tags is None else (int(tags[0]), int(tags[1]))
+        moved, skipped = C.c_int(0), C.c_int(0)
+        check(lib.svo_desc_index_transform_points(self._h, ptr(M), int(rows[0]), int(rows[1]), lo, hi, C.byref(moved), C.byref(skipped)))
+        return moved.value, skipped.value
+
+    @property
+    def retire_slab_rows(self):
+        """tuning: the rows of one slab of retire's in-place compaction; assign 0 for the default"""
+        return check(lib.svo_desc_index_get_retire_slab_rows(self._h))
+
+    @retire_slab_rows.setter
+    def retire_slab_rows(self, rows):
+        check(lib.svo_desc_index_set_retire_slab_rows(self._h, int(rows)))
+
+    def retire_stats(self):
+        """diagnostics (svo_desc_index_get_retire_stats) -> dict: last_kernels_ms (0 unless set_timing), scratch_allocations,
+        scratch_bytes, scratch_bytes_outgrown of the retire scratch"""
+        st = _lib.SvoDescRetireStats()
+        check(lib.svo_desc_index_get_retire_stats(self._h, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in st._fields_}
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib.svo_desc_index_destroy(self._h)

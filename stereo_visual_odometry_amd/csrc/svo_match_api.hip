@@ -9,7 +9,13 @@
 // the RANSAC-PnP kernels behind it and waits once.
 // Timing (svo_desc_index_set_timing): a call marks the one span it times — its search, its selection or its projection — and reads
 // it into last_ms after its wait.  match times one span per stage, around all of the stage's launches, and sums over its stages.
+//
+// Maintenance (include/svo.h, "Index maintenance"; the kernels are in svo_kernels_retire.hip): retire settles the scope, sorts the
+// id list, takes room in a scratch of its own (retire_room), puts the flags, the table and the ranks on the stream and waits for the
+// count of kept rows and the table's flag; only then do rows move, slab by slab through the bounce buffer, and a second wait ends
+// the call.  transform_points is one launch and one wait.  Both time their kernels into retire_ms, apart from last_ms.
 #include "svo_guide_internal.hpp"
+#include "svo_retire_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -37,6 +43,7 @@ static int fail(int rc, const char* msg) { svo_set_error(msg); return rc; }
 
 struct RelocDevOut;
 struct RelocHost;
+struct RetireDown { RetireCtl ctl; int32_t kept, pad[3]; };   // a retire call reads ctl.table_full and kept, a transform the whole ctl
 struct svo_desc_index {
     int device = 0, capacity = 0, size = 0, chunk_rows = MATCH_DEFAULT_CHUNK;
     hipStream_t stream = nullptr;
@@ -63,6 +70,14 @@ struct svo_desc_index {
     int32_t* d_order = nullptr;                       // [MATCH_STAGE_ROWS] the query each lane slot serves
     int32_t* h_order = nullptr;                       // pinned, likewise
     bool guided_sort = true;                          // svo_desc_index_set_guided_sort
+    // index maintenance: all null until the first retire or transform_points (retire_ctl_room, retire_room)
+    int retire_slab = RETIRE_DEFAULT_SLAB;            // svo_desc_index_set_retire_slab_rows
+    uint8_t* d_retire = nullptr;                      // [retire_cap] bytes, cut by retire_layout: grows by doubling like d_part
+    size_t retire_cap = 0, retire_outgrown = 0;
+    int retire_allocs = 0;
+    float retire_ms = 0.f;                            // the last maintenance call's kernels, with timing on
+    RetireCtl* d_retire_ctl = nullptr;
+    RetireDown* h_retire = nullptr;                   // pinned: what a call reads back before it decides
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -85,6 +100,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         if (x->stream) (void)hipStreamSynchronize(x->stream);
         for (hipEvent_t e : x->ev) if (e) (void)hipEventDestroy(e);
         for (void* p : x->outgrown) (void)hipFree(p);
+        (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
         (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
         (void)hipFree(x->d_part); (void)hipFree(x->d_out); (void)hipFree(x->d_query); (void)hipFree(x->d_ids); (void)hipFree(x->d_desc);
@@ -563,4 +579,180 @@ extern "C" int svo_desc_index_localize_guided(svo_desc_index* x, const float K[9
                                               int32_t* cand_row, uint8_t* cand_inlier) {
     if (!K || !g || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize_guided: null K / guide / result");
     return reloc_run(x, RelocRequest{K, g, n, query, xy, p}, RelocOutputs{nullptr, cand_query, cand_row, nullptr, nullptr, res, cand_inlier});
+}
+
+// ---- index maintenance (include/svo.h, "Index maintenance") ----
+#define RETIRE_SCRATCH_FIRST ((size_t)1 << 16)        // the scratch's first size in bytes; it doubles from there
+#define RETIRE_STAGE_BYTES ((size_t)MATCH_STAGE_ROWS * (SVO_DESC_BYTES + sizeof(uint64_t)))   // h_stage, which carries the ids up and kept_before down
+
+static int retire_ctl_room(svo_desc_index* x) {
+    if (x->d_retire_ctl) return SVO_OK;
+    MHIP(hipHostMalloc((void**)&x->h_retire, sizeof(RetireDown), hipHostMallocDefault));
+    MHIP(hipMalloc((void**)&x->d_retire_ctl, sizeof(RetireCtl)));             // last: d_retire_ctl says "allocated"
+    return SVO_OK;
+}
+
+// Room for `need` bytes of retire scratch: part_room's pattern.  The size is 64 KiB times a power of two, the smallest that holds
+// the largest call so far — below twice its need — and the outgrown buffers, freed with the index, sum to less than the one in use.
+static int retire_room(svo_desc_index* x, size_t need) {
+    if (need <= x->retire_cap) return SVO_OK;
+    size_t cap = x->retire_cap ? 2 * x->retire_cap : RETIRE_SCRATCH_FIRST;
+    while (cap < need) cap *= 2;
+    uint8_t* p = nullptr;
+    MHIP(hipMalloc((void**)&p, cap));
+    if (x->d_retire) { x->outgrown.push_back(x->d_retire); x->retire_outgrown += x->retire_cap; }
+    x->d_retire = p; x->retire_cap = cap; x->retire_allocs++;
+    return SVO_OK;
+}
+
+static hipError_t retire_span_read(svo_desc_index* x) {
+    float ms = 0.f;
+    const hipError_t e = x->timing ? hipEventElapsedTime(&ms, x->ev[0], x->ev[1]) : hipSuccess;
+    x->retire_ms += ms;
+    return e;
+}
+
+extern "C" int svo_desc_index_set_retire_slab_rows(svo_desc_index* x, int rows) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (rows < 0 || rows > RETIRE_MAX_ROWS) return fail(SVO_ERR_ARG, "svo_desc_index_set_retire_slab_rows: rows must be 0 (default) .. 1 << 24");
+    x->retire_slab = rows ? rows : RETIRE_DEFAULT_SLAB;
+    return SVO_OK;
+}
+extern "C" int svo_desc_index_get_retire_slab_rows(const svo_desc_index* x) { return x ? x->retire_slab : fail(SVO_ERR_ARG, "null index"); }
+
+extern "C" int svo_desc_index_get_retire_stats(const svo_desc_index* x, svo_desc_retire_stats* st) {
+    if (!x || !st) return fail(SVO_ERR_ARG, "null index / stats");
+    st->last_kernels_ms = x->retire_ms;
+    st->scratch_allocations = x->retire_allocs;
+    st->scratch_bytes = (uint64_t)x->retire_cap;
+    st->scratch_bytes_outgrown = (uint64_t)x->retire_outgrown;
+    return SVO_OK;
+}
+
+// the sorted id list onto the device through the pinned staging, piece by piece
+static int retire_upload_ids(svo_desc_index* x, const std::vector<uint64_t>& sorted, uint64_t* d_sorted) {
+    const size_t piece = RETIRE_STAGE_BYTES / sizeof(uint64_t);
+    for (size_t i0 = 0; i0 < sorted.size(); i0 += piece) {
+        const size_t m = sorted.size() - i0 < piece ? sorted.size() - i0 : piece;
+        memcpy(x->h_stage, sorted.data() + i0, m * sizeof(uint64_t));
+        MHIP(hipMemcpyAsync(d_sorted + i0, x->h_stage, m * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));        // the staging is free again
+    }
+    return SVO_OK;
+}
+
+// kept_before[row_lo + i] = row_lo + rank[i] for the scope's rows, piece by piece through the pinned staging
+static int retire_download_ranks(svo_desc_index* x, const int32_t* d_rank, int row_lo, int m, int32_t* kept_before) {
+    const int piece = (int)(RETIRE_STAGE_BYTES / sizeof(int32_t));
+    const int32_t* h = (const int32_t*)x->h_stage;
+    for (int i0 = 0; i0 < m; i0 += piece) {
+        const int n = m - i0 < piece ? m - i0 : piece;
+        MHIP(hipMemcpyAsync(x->h_stage, d_rank + i0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        for (int i = 0; i < n; i++) kept_before[row_lo + i0 + i] = row_lo + h[i];
+    }
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* rule, int32_t* kept_before, int* n_kept) {
+    if (!x || !rule) return fail(SVO_ERR_ARG, "svo_desc_index_retire: null index / rule");
+    const uint32_t flags = rule->flags;
+    if (flags & ~RETIRE_ALL_FLAGS) return fail(SVO_ERR_ARG, "svo_desc_index_retire: unknown flag bits");
+    int row_lo = rule->row_lo, row_hi = rule->row_hi;
+    int rc = row_range(x, row_lo, row_hi);
+    if (rc != SVO_OK) return rc;
+    if (rule->n_ids < 0 || rule->n_ids > RETIRE_MAX_IDS) return fail(SVO_ERR_ARG, "svo_desc_index_retire: n_ids must be 0 .. 1 << 24");
+    if ((flags & RETIRE_BY_IDS) && rule->n_ids > 0 && !rule->ids) return fail(SVO_ERR_ARG, "svo_desc_index_retire: null ids");
+    if ((flags & RETIRE_BY_TAG) && !x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_retire: BY_TAG on an index without points (svo_desc_index_enable_points)");
+    x->retire_ms = 0.f;
+    MHIP(hipSetDevice(x->device));
+    const int n0 = x->size, m = row_hi - row_lo;
+    int kept = m;                                     // of the scope's rows
+    bool ranks_down = false;
+    if (flags != 0 && m > 0) {
+        std::vector<uint64_t> sorted;
+        if (flags & RETIRE_BY_IDS) {
+            sorted.assign(rule->ids, rule->ids + rule->n_ids);
+            std::sort(sorted.begin(), sorted.end());
+            sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+        }
+        const int slab = n0 - row_lo < x->retire_slab ? n0 - row_lo : x->retire_slab;
+        const RetireLayout l = retire_layout(m, n0 - row_lo, (int32_t)sorted.size(), x->retire_slab, flags);
+        if ((rc = retire_ctl_room(x)) != SVO_OK || (rc = retire_room(x, l.total)) != SVO_OK) return rc;
+        uint8_t* keep = x->d_retire + l.keep;
+        int32_t* rank = (int32_t*)(x->d_retire + l.rank);
+        int32_t* counts = (int32_t*)(x->d_retire + l.counts);
+        int32_t* table = (int32_t*)(x->d_retire + l.table);
+        uint64_t* d_sorted = (uint64_t*)(x->d_retire + l.ids);
+        void* bounce = x->d_retire + l.bounce;
+        const RetireRows rows{(uint4*)x->d_desc, x->d_ids, (uint4*)x->d_points};
+        if ((rc = retire_upload_ids(x, sorted, d_sorted)) != SVO_OK) return rc;
+        MHIP(hipMemsetAsync(&x->d_retire_ctl->table_full, 0, sizeof(int32_t), x->stream));
+        const uint32_t slots = retire_table_slots(m);
+        if (flags & RETIRE_LATEST_PER_ID) MHIP(hipMemsetAsync(table, 0xFF, (size_t)slots * sizeof(int32_t), x->stream));   // RETIRE_EMPTY
+        MHIP(span_mark(x, true, 0));
+        launch_retire_flags(rows, row_lo, m, flags, rule->tag_lo, rule->tag_hi, d_sorted, (int32_t)sorted.size(), keep, x->stream);
+        if (flags & RETIRE_LATEST_PER_ID) launch_retire_latest(rows, row_lo, m, keep, table, slots, x->d_retire_ctl, x->stream);
+        launch_retire_ranks(keep, m, counts, rank, x->stream);
+        MHIP(hipGetLastError());
+        MHIP(span_mark(x, true, 1));
+        MHIP(hipMemcpyAsync(&x->h_retire->ctl.table_full, &x->d_retire_ctl->table_full, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipMemcpyAsync(&x->h_retire->kept, rank + m, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));        // nothing has moved yet: a failure up to here changes nothing
+        MHIP(retire_span_read(x));
+        if (x->h_retire->ctl.table_full) return fail(SVO_ERR_INTERNAL, "svo_desc_index_retire: the latest-per-id table overflowed (nothing was changed)");
+        kept = x->h_retire->kept;
+        if (kept_before && kept < m) {
+            if ((rc = retire_download_ranks(x, rank, row_lo, m, kept_before)) != SVO_OK) return rc;
+            ranks_down = true;
+        }
+        if (kept < m) {                               // the scope's slabs, then the rows behind it, which all stay and move down
+            MHIP(span_mark(x, true, 0));
+            for (int a = 0; a < m; a += slab)
+                launch_retire_slab(rows, row_lo + a, m - a < slab ? m - a : slab, keep + a, rank + a, row_lo, bounce, slab, x->stream);
+            for (int a = row_hi; a < n0; a += slab)
+                launch_retire_slab(rows, a, n0 - a < slab ? n0 - a : slab, nullptr, nullptr, row_lo + kept + (a - row_hi), bounce, slab, x->stream);
+            MHIP(hipGetLastError());
+            MHIP(span_mark(x, true, 1));
+            MHIP(hipStreamSynchronize(x->stream));
+            MHIP(retire_span_read(x));
+        }
+    }
+    if (kept_before) {
+        for (int r = 0; r <= row_lo; r++) kept_before[r] = r;
+        if (!ranks_down) for (int r = row_lo; r < row_hi; r++) kept_before[r] = r;       // every row of the scope stayed
+        for (int r = row_hi; r <= n0; r++) kept_before[r] = r - (m - kept);
+    }
+    x->size = n0 - (m - kept);
+    if (n_kept) *n_kept = x->size;
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_transform_points(svo_desc_index* x, const double T[16], int row_lo, int row_hi, int32_t tag_lo, int32_t tag_hi,
+                                               int* n_moved, int* n_skipped) {
+    if (!x || !T) return fail(SVO_ERR_ARG, "svo_desc_index_transform_points: null index / T");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_transform_points: the index has no points (svo_desc_index_enable_points)");
+    for (int i = 0; i < 16; i++) if (!isfinite(T[i])) return fail(SVO_ERR_ARG, "svo_desc_index_transform_points: T has a non-finite entry");
+    int rc = row_range(x, row_lo, row_hi);
+    if (rc != SVO_OK) return rc;
+    x->retire_ms = 0.f;
+    MHIP(hipSetDevice(x->device));
+    int moved = 0, skipped = 0;
+    if (row_hi > row_lo) {
+        if ((rc = retire_ctl_room(x)) != SVO_OK) return rc;
+        RetireT t;
+        memcpy(t.m, T, sizeof(t.m));
+        MHIP(hipMemsetAsync(x->d_retire_ctl, 0, sizeof(RetireCtl), x->stream));
+        MHIP(span_mark(x, true, 0));
+        launch_transform_points((uint4*)x->d_points, t, row_lo, row_hi, tag_lo, tag_hi, x->d_retire_ctl, x->stream);
+        MHIP(hipGetLastError());
+        MHIP(span_mark(x, true, 1));
+        MHIP(hipMemcpyAsync(&x->h_retire->ctl, x->d_retire_ctl, sizeof(RetireCtl), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        MHIP(retire_span_read(x));
+        for (const RetireCounts& c : x->h_retire->ctl.counts) { moved += c.n_moved; skipped += c.n_skipped; }
+    }
+    if (n_moved) *n_moved = moved;
+    if (n_skipped) *n_skipped = skipped;
+    return SVO_OK;
 }
