@@ -728,6 +728,63 @@ int svo_desc_index_set_retire_slab_rows(svo_desc_index* index, int rows);
 int svo_desc_index_get_retire_slab_rows(const svo_desc_index* index);
 int svo_desc_index_get_retire_stats(const svo_desc_index* index, svo_desc_retire_stats* stats);
 
+/* ---- Batched relocalisation: many cameras against one index in one call ------------------------------------------------------------
+ * A many-sequence context tracks hundreds of cameras per step; the calls above serve one camera each, and most of such a call is
+ * launch latency.  svo_desc_index_localize_batch serves n_cameras cameras in one call: one upload, the searches of all cameras in a
+ * few launches, one selection launch with a block per camera, the RANSAC-PnP kernels over n_cameras sequences, one host
+ * synchronisation.
+ *
+ * The contract, which is the whole definition.  Camera b has the queries [query_begin[b], query_begin[b + 1]) of query and xy, the
+ * camera matrix K + 9 b, the guide guides[b], and results[b].R, t going in as its extrinsic guess.
+ *  - results[b] equals, in every bit, what svo_desc_index_localize_guided returns for that slice alone with the same params; with
+ *    guides == NULL, what svo_desc_index_localize returns.
+ *  - The first results[b].n_candidates entries of cand_query, cand_row and cand_inlier (each may be NULL) at offset query_begin[b]
+ *    equal that single call's arrays; cand_query is numbered inside the slice, 0 .. n_b - 1.  Nothing beyond those entries is written.
+ *  - The results do not depend on the chunk size, on the order of the lanes, on how the library groups cameras into launches, or on
+ *    the number of cameras.
+ * A camera has at most SVO_RELOC_MAX_QUERIES queries, a call 0 .. SVO_RELOC_BATCH_MAX_CAMERAS cameras (0 is legal and launches
+ * nothing) and at most SVO_RELOC_BATCH_MAX_QUERIES queries in all.  A camera without queries gets success = 0, n_candidates = 0.
+ * params is one record for the call; guided and unguided cameras do not mix.
+ * SVO_ERR_ARG / SVO_ERR_STATE: wherever the single call gives them for any camera; also query_begin[0] != 0, a decreasing offset, a
+ * slice above 4096, a total above 1 << 20, n_cameras outside 0 .. 1024.  Every refusal is decided before anything is uploaded or
+ * enqueued and leaves results untouched.
+ * The call synchronises once, waits for the index's own stream only, and is legal with frames in flight; one index is used by one
+ * thread at a time.  With svo_desc_index_set_timing on, last_kernels_ms is the device span from the first kernel the call launches
+ * to the last.
+ *
+ * How it runs (none of it shows in the results).  The guided search projects inside the search kernel, tile by tile into LDS: no
+ * array of projections exists (cameras x rows x 8 bytes would be 4 GiB at 512 cameras and 1 << 20 rows).  Partial states are kept
+ * per (query, piece), so a launch serves a group of consecutive cameras whose queries x pieces fit the scratch's 64 MiB budget; the
+ * rows of a piece double from svo_desc_index_set_chunk_rows' number until the widest slice (64 queries at least) fits alone.  With
+ * svo_desc_index_set_guided_sort on, each camera's lanes are ordered on the device by image cell (side 2 x radius, 1 px at least,
+ * raster order, a non-finite pixel last; ties by j); off, and without guides, the lanes take the queries as they come.
+ * The PnP runs in a stage context of its own that the index owns: n_cameras sequences, configured as svo_camera_to_world's.  Above 8
+ * cameras the PnP kernels take their many-sequence builds, which give the lone builds' bits.
+ *
+ * Memory, all owned by the index, allocated at the first batch call and freed with the index.  With C cameras, Q queries in all and
+ * R(b) = b rounded up to a multiple of 256, a call needs a device staging of
+ *   R(32 Q) + R(8 Q) + R(4 (C + 1)) + R(136 C)         the queries, their pixels, the offsets, the cameras' priors (one copy up)
+ *   + R(4 C) + 2 R(4 Q) + R(Q)                         the candidate counts, the two candidate lists, the inlier flags (one copy down)
+ *   + R(4 Q) + R(32 Q)                                 the lane order and the search's result rows
+ * bytes, a pinned staging of the first two lines, and 2 C pinned state rows.  The staging is separate from the 4096-row staging of
+ * the single calls.  Its capacities in cameras (16 at first) and queries (4096 at first) each at least double when a call outgrows
+ * them; outgrown blocks, and outgrown stage contexts (sequences and points per sequence at least double likewise), are freed with
+ * the index and sum to less than the ones in use. */
+#define SVO_RELOC_BATCH_MAX_CAMERAS 1024
+#define SVO_RELOC_BATCH_MAX_QUERIES (1 << 20)
+int svo_desc_index_localize_batch(svo_desc_index* index, int n_cameras,
+                                  const float* K,                  /* n_cameras x 9 */
+                                  const svo_reloc_guide* guides,   /* n_cameras, or NULL: the unguided search for every camera */
+                                  const int32_t* query_begin,      /* n_cameras + 1 offsets into query / xy: [0] = 0, non-decreasing */
+                                  const uint8_t* query, const float* xy,   /* total x 32 bytes, total x 2 floats */
+                                  const svo_reloc_params* params,  /* one for the call */
+                                  svo_reloc_result* results,       /* n_cameras; R, t going in: each camera's extrinsic guess */
+                                  int32_t* cand_query, int32_t* cand_row, uint8_t* cand_inlier);   /* total entries each, each may be NULL */
+/* Diagnostic: the lane order of the last batch call as global query numbers — entries [query_begin[b], query_begin[b + 1]) are a
+ * permutation of camera b's slice; the identity where the order kernel did not run.  *n: the call's total; order receives
+ * min(cap, *n) entries.  SVO_ERR_STATE: no batch call yet, or the staging has grown since. */
+int svo_desc_index_get_batch_order(const svo_desc_index* index, int cap, int32_t* order, int* n);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the

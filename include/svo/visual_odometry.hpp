@@ -593,6 +593,52 @@ class DescriptorIndex {
         return localize_("localize_guided", K, &g, query, xy, params, result, candidates);
     }
     void set_guided_sort(bool on) { svo_throw(svo_desc_index_set_guided_sort(index_, on ? 1 : 0)); }
+    // ---- batched relocalisation (svo.h, "Batched relocalisation"): many cameras in one call
+    // One camera of a batch.  In: K, the guide (read by a guided batch only), the queries with a pixel each, and result.R, t, the
+    // PnP's guess.  Out: result and candidates, what localize / localize_guided return for this camera alone, bit for bit.
+    struct BatchCamera {
+        float K[9];
+        svo_reloc_guide guide;
+        std::vector<Descriptor> query;
+        std::vector<float> xy;
+        svo_reloc_result result;
+        Candidates candidates;
+    };
+    // localize_guided (guided) or localize for the n_cameras cameras at cams, in one call and one synchronisation
+    void localize_batch(BatchCamera* cams, size_t n_cameras, bool guided, const svo_reloc_params& params) {
+        std::vector<float> K(9 * n_cameras), xy;
+        std::vector<svo_reloc_guide> guides(guided ? n_cameras : 0);
+        std::vector<int32_t> begin(n_cameras + 1, 0);
+        std::vector<Descriptor> query;
+        std::vector<svo_reloc_result> results(n_cameras);
+        for (size_t b = 0; b < n_cameras; b++) {
+            one_pixel_each("localize_batch", cams[b].query, cams[b].xy);
+            for (int i = 0; i < 9; i++) K[9 * b + (size_t)i] = cams[b].K[i];
+            if (guided) guides[b] = cams[b].guide;
+            query.insert(query.end(), cams[b].query.begin(), cams[b].query.end());
+            xy.insert(xy.end(), cams[b].xy.begin(), cams[b].xy.end());
+            begin[b + 1] = (int32_t)query.size();
+            results[b] = cams[b].result;
+        }
+        Candidates all = room(query.size(), true);
+        svo_throw(svo_desc_index_localize_batch(index_, (int)n_cameras, K.data(), guided ? guides.data() : nullptr, begin.data(), rows(query), xy.data(), &params,
+                                                results.data(), all.query.data(), all.row.data(), all.inlier.data()));
+        for (size_t b = 0; b < n_cameras; b++) {
+            const size_t lo = (size_t)begin[b], k = (size_t)results[b].n_candidates;
+            cams[b].result = results[b];
+            cams[b].candidates.query.assign(all.query.begin() + (long)lo, all.query.begin() + (long)(lo + k));
+            cams[b].candidates.row.assign(all.row.begin() + (long)lo, all.row.begin() + (long)(lo + k));
+            cams[b].candidates.inlier.assign(all.inlier.begin() + (long)lo, all.inlier.begin() + (long)(lo + k));
+        }
+    }
+    // diagnostics: the lane order of the last localize_batch as global query numbers
+    std::vector<int32_t> batch_order() {
+        int n = 0;
+        svo_throw(svo_desc_index_get_batch_order(index_, 0, nullptr, &n));
+        std::vector<int32_t> order((size_t)n);
+        svo_throw(svo_desc_index_get_batch_order(index_, n, order.data(), &n));
+        return order;
+    }
     // ---- index maintenance (svo.h, "Index maintenance"): drop rows anywhere and move points, both on the device
     // a rule over the scope [row_lo, row_hi) with no flag set: set flags, the tag window and the id list (which must outlive the call)
     static svo_retire_rule retire_rule(int row_lo = 0, int row_hi = -1) {

@@ -39,6 +39,7 @@ OBS_INLIER, OBS_HAS_XYZ = 1, 2
 DESC_BYTES = 32
 MATCH_NONE, MATCH_NO_DIST = -1, 257
 POINT_NONE, RELOC_MAX_QUERIES = -1, 4096
+RELOC_BATCH_MAX_CAMERAS, RELOC_BATCH_MAX_QUERIES = 1024, 1 << 20
 # index maintenance (svo.h SVO_RETIRE_*)
 RETIRE_BY_TAG, RETIRE_BY_IDS, RETIRE_LATEST_PER_ID, RETIRE_SCOPE = 1, 2, 4, 8
 # motion priors (svo.h SVO_PRIOR_*)
@@ -196,6 +197,8 @@ PROTOTYPES = {
     "svo_desc_index_set_retire_slab_rows": (I, (P, I)),
     "svo_desc_index_get_retire_slab_rows": (I, (P,)),
     "svo_desc_index_get_retire_stats": (I, (P, P)),
+    "svo_desc_index_localize_batch": (I, (P, I, P, P, P, P, P, P, P, P, P, P)),
+    "svo_desc_index_get_batch_order": (I, (P, I, P, P)),
     "svo_set_detection_mask": (I, (P, I, P, I, I)),
     "svo_get_detection_mask": (I, (P, I, P, P)),
     "svo_set_motion_prior": (I, (P, I, P, P)),

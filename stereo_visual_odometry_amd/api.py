@@ -523,6 +523,54 @@ class DescriptorIndex:
         return self._localize(K, query, xy, R if rotation is None else rotation, t if translation is None else translation, params, over,
                               guide=(R, t, radius))
 
+    # ---- batched relocalisation (svo.h, "Batched relocalisation"): many cameras in one call
+    def localize_batch(self, K, queries, xys, guides=None, rotations=None, translations=None, params=None, **over):
+        """localize (guides None) or localize_guided for many cameras in one call (svo_desc_index_localize_batch) -> a list with, per
+        camera, the (RelocResult, candidates) the single call returns, bit for bit.  K: (B, 3, 3) camera matrices, or one (3, 3) for
+        all; queries, xys: per camera an (n_b, 32) uint8 and an (n_b, 2) float32 array; guides: per camera (R, t, radius); rotations,
+        translations: per camera the PnP's extrinsic guess (None: the guide's R, t, or the identity and zero without guides)."""
+        B = len(queries)
+        if len(xys) != B or (guides is not None and len(guides) != B):
+            raise ValueError("one pixel array and one guide per camera expected")
+        Kf = np.ascontiguousarray(K, np.float32)
+        Kf = np.ascontiguousarray(np.broadcast_to(Kf.reshape(-1, 9) if Kf.size != 9 else Kf.reshape(1, 9), (B, 9)))
+        pairs = [self._queries(q, p) for q, p in zip(queries, xys)]
+        begin = np.zeros(B + 1, np.int32)
+        begin[1:] = np.cumsum([len(q) for q, _ in pairs])
+        total = int(begin[-1])
+        q = np.concatenate([a for a, _ in pairs]) if total else np.zeros((0, _lib.DESC_BYTES), np.uint8)
+        p = np.concatenate([b for _, b in pairs]) if total else np.zeros((0, 2), np.float32)
+        prm = params if params is not None else self.reloc_params(**over)
+        g = None
+        if guides is not None:
+            g = (_lib.SvoRelocGuide * max(B, 1))()
+            for b in range(B):
+                g[b] = self.guide(*guides[b])
+        res = (_lib.SvoRelocResult * max(B, 1))()
+        for b in range(B):
+            R0 = rotations[b] if rotations is not None else (guides[b][0] if guides is not None else np.eye(3))
+            t0 = translations[b] if translations is not None else (guides[b][1] if guides is not None else np.zeros(3))
+            res[b].R[:] = list(np.asarray(R0, np.float64).reshape(9))
+            res[b].t[:] = list(np.asarray(t0, np.float64).reshape(3))
+        cq, cr, ci = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.uint8)
+        check(lib.svo_desc_index_localize_batch(self._h, B, ptr(Kf), g, ptr(begin), ptr(q), ptr(p), C.byref(prm), res, ptr(cq), ptr(cr), ptr(ci)))
+        out = []
+        for b in range(B):
+            r, lo = res[b], int(begin[b])
+            k = r.n_candidates
+            rec = RelocResult(bool(r.success), k, r.n_inliers, r.iters_run, np.array(r.R[:]).reshape(3, 3), np.array(r.t[:]).reshape(3, 1),
+                              np.array(r.T[:]).reshape(4, 4))
+            out.append((rec, dict(query=cq[lo:lo + k].copy(), row=cr[lo:lo + k].copy(), inlier=ci[lo:lo + k].astype(bool))))
+        return out
+
+    def batch_order(self):
+        """diagnostics (svo_desc_index_get_batch_order): the lane order of the last localize_batch as global query numbers, (total,) int32"""
+        n = C.c_int(0)
+        check(lib.svo_desc_index_get_batch_order(self._h, 0, None, C.byref(n)))
+        order = np.zeros(max(n.value, 1), np.int32)
+        check(lib.svo_desc_index_get_batch_order(self._h, n.value, ptr(order), C.byref(n)))
+        return order[:n.value].copy()
+
     @staticmethod
     def _rows(desc, what):
         d = np.ascontiguousarray(desc, dtype=np.uint8)

@@ -7,6 +7,7 @@
 #include "svo_prior.hpp"
 #include "svo_match_internal.hpp"
 #include "svo_reloc_internal.hpp"
+#include "svo_reloc_batch_internal.hpp"
 #include <stdio.h>
 #include <string.h>
 #include <stddef.h>
@@ -1874,13 +1875,16 @@ extern "C" int svo_triangulate(int device, const float Pl[12], const float Pr[12
 }
 
 // the stage context of a stand-alone RANSAC-PnP over up to cap points: svo_camera_to_world's, and the relocaliser's
-static int pnp_stage_ctx(int device, int cap, int ransac_iterations, float reproj_error, float confidence, svo_context** out) {
+static svo_config pnp_stage_config(int ransac_iterations, float reproj_error, float confidence) {
     svo_config cfg; svo_config_default(&cfg);
     cfg.ransac_iterations = ransac_iterations > 1 ? ransac_iterations : 1;
     cfg.ransac_reprojection_error = reproj_error; cfg.ransac_confidence = confidence;
     cfg.features_threshold = 0;                                                  // cameraToWorld itself has no inlier-count gate
     cfg.max_translation_norm = 1e300; cfg.max_rotation_norm = 1e300;             // nor motion gates
-    return stage_ctx(cfg, device, 64, 64, cap, out);
+    return cfg;
+}
+static int pnp_stage_ctx(int device, int cap, int ransac_iterations, float reproj_error, float confidence, svo_context** out) {
+    return stage_ctx(pnp_stage_config(ransac_iterations, reproj_error, confidence), device, 64, 64, cap, out);
 }
 // svo_reloc_internal.hpp: the same context for svo_desc_index_localize (svo_match_api.hip), which enqueues on its index's stream
 int svo_reloc_stage_ctx(int device, int cap, int ransac_iterations, float reproj_error, float confidence, const DevBuffers** d) {
@@ -1890,6 +1894,37 @@ int svo_reloc_stage_ctx(int device, int cap, int ransac_iterations, float reproj
     HIPCHK(hipStreamSynchronize(c->stream));   // a context created just now may still be clearing its buffers on its own stream; otherwise idle
     g_stage_path = c->d.co_resident ? SVO_PATH_LEAN : 0;
     *d = &c->d;
+    return SVO_OK;
+}
+// svo_reloc_batch_internal.hpp: the index's own context of n_seq sequences for svo_desc_index_localize_batch, through the same
+// configuration.  It takes no part in the device's LK gate: it never runs an LK grid, and a many-sequence context beside it must
+// launch what it launches alone.
+int svo_reloc_batch_ctx(int device, int n_seq, int cap, int ransac_iterations, float reproj_error, float confidence, svo_context** held,
+                        svo_context** outgrown, DevBuffers* d) {
+    svo_config cfg = pnp_stage_config(ransac_iterations, reproj_error, confidence);
+    if (cfg.channels == 0) cfg.channels = 1;
+    svo_context* c = *held;
+    *outgrown = nullptr;
+    HIPCHK(hipSetDevice(device));
+    const bool fits = c && c->d.B >= n_seq && c->d.CAP >= cap;
+    if (!fits || !(cfg_equal(c->d.cfg, cfg) || stage_reconfigure(c, cfg))) {
+        int seqs = n_seq, room = cap;
+        if (c) {                                                                 // what was outgrown at least doubles; the rest stays
+            seqs = c->d.B >= n_seq ? c->d.B : std::max(n_seq, 2 * c->d.B);
+            room = c->d.CAP >= cap ? c->d.CAP : std::max(cap, 2 * c->d.CAP);
+        }
+        svo_context* fresh = nullptr;
+        if (const int rc = ctx_create(&cfg, device, seqs, 64, 64, room, &fresh)) return rc;
+        if (fresh->counted) {
+            std::lock_guard<std::mutex> lock(g_lk_gate[device].mu);
+            g_lk_gate[device].contexts--; fresh->counted = false;
+        }
+        HIPCHK(hipStreamSynchronize(fresh->stream));                             // it may still be clearing its buffers on its own stream
+        *outgrown = c; *held = c = fresh;
+    }
+    HIPCHK(choose_pnp_build(c->d, false));
+    *d = c->d;
+    d->B = n_seq;
     return SVO_OK;
 }
 

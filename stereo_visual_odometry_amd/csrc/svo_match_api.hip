@@ -14,8 +14,13 @@
 // id list, takes room in a scratch of its own (retire_room), puts the flags, the table and the ranks on the stream and waits for the
 // count of kept rows and the table's flag; only then do rows move, slab by slab through the bounce buffer, and a second wait ends
 // the call.  transform_points is one launch and one wait.  Both time their kernels into retire_ms, apart from last_ms.
+//
+// The batch (include/svo.h, "Batched relocalisation"; the kernels are in svo_kernels_reloc_batch.hip, the plan in svo_reloc_batch.hpp):
+// localize_batch is reloc_run for many cameras at once, with a staging (batch_room) and a PnP stage context of its own, both owned by
+// the index; the single calls' 4096-row staging and their path above are untouched by it.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
+#include "svo_reloc_batch_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -78,6 +83,16 @@ struct svo_desc_index {
     float retire_ms = 0.f;                            // the last maintenance call's kernels, with timing on
     RetireCtl* d_retire_ctl = nullptr;
     RetireDown* h_retire = nullptr;                   // pinned: what a call reads back before it decides
+    // batched relocalisation: all null until the first svo_desc_index_localize_batch (batch_room)
+    uint8_t* d_batch = nullptr;                       // the device staging: room for rb_layout(batch_cams, batch_queries), cut per call
+    uint8_t* h_batch = nullptr;                       // pinned: its first down_end bytes, cut alike
+    SeqState* h_batch_st = nullptr;                   // pinned: [2][batch_cams] the state rows going up, and as k_pnp_final left them
+    size_t batch_cams = 0, batch_queries = 0;         // each at least doubles when it grows
+    std::vector<void*> outgrown_pinned;               // earlier pinned staging: freed with the index, like `outgrown`
+    svo_context* batch_ctx = nullptr;                 // the PnP stage context of B sequences (svo_reloc_batch_ctx)
+    std::vector<svo_context*> batch_ctx_outgrown;     // earlier ones, destroyed with the index
+    int batch_last_cams = 0, batch_total = -1;                             // the last batch call's queries (-1: none yet), and whether d_batch holds its order
+    bool batch_ordered = false;
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -100,6 +115,10 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         if (x->stream) (void)hipStreamSynchronize(x->stream);
         for (hipEvent_t e : x->ev) if (e) (void)hipEventDestroy(e);
         for (void* p : x->outgrown) (void)hipFree(p);
+        for (void* p : x->outgrown_pinned) (void)hipHostFree(p);
+        for (svo_context* c : x->batch_ctx_outgrown) svo_destroy(c);
+        svo_destroy(x->batch_ctx);
+        (void)hipFree(x->d_batch); (void)hipHostFree(x->h_batch); (void)hipHostFree(x->h_batch_st);
         (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
         (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
@@ -579,6 +598,170 @@ extern "C" int svo_desc_index_localize_guided(svo_desc_index* x, const float K[9
                                               int32_t* cand_row, uint8_t* cand_inlier) {
     if (!K || !g || !res) return fail(SVO_ERR_ARG, "svo_desc_index_localize_guided: null K / guide / result");
     return reloc_run(x, RelocRequest{K, g, n, query, xy, p}, RelocOutputs{nullptr, cand_query, cand_row, nullptr, nullptr, res, cand_inlier});
+}
+
+// ---- batched relocalisation (include/svo.h, "Batched relocalisation"; the kernels are in svo_kernels_reloc_batch.hip, the plan and
+// the staging's layout in svo_reloc_batch.hpp) ----
+#define BATCH_FIRST_CAMS 16                           // the staging's first room: cameras, queries
+#define BATCH_FIRST_QUERIES 4096
+
+// Room for a call of `cams` cameras and `queries` queries in the batch's staging: a device block, a pinned block and the pinned state
+// rows.  Either capacity at least doubles when it is outgrown; the outgrown blocks go with the index.
+static int batch_room(svo_desc_index* x, size_t cams, size_t queries) {
+    if (x->d_batch && cams <= x->batch_cams && queries <= x->batch_queries) return SVO_OK;
+    const size_t nc = rb_grow(x->batch_cams, cams, BATCH_FIRST_CAMS), nq = rb_grow(x->batch_queries, queries, BATCH_FIRST_QUERIES);
+    const RbLayout l = rb_layout(nc, nq);
+    uint8_t *d = nullptr, *h = nullptr;
+    SeqState* hs = nullptr;
+    MHIP(hipMalloc((void**)&d, l.total));
+    if (hipError_t e = hipHostMalloc((void**)&h, l.down_end, hipHostMallocDefault); e != hipSuccess) { (void)hipFree(d); MHIP(e); }
+    if (hipError_t e = hipHostMalloc((void**)&hs, 2 * nc * sizeof(SeqState), hipHostMallocDefault); e != hipSuccess) { (void)hipFree(d); (void)hipHostFree(h); MHIP(e); }
+    if (x->d_batch) { x->outgrown.push_back(x->d_batch); x->outgrown_pinned.push_back(x->h_batch); x->outgrown_pinned.push_back(x->h_batch_st); }
+    x->d_batch = d; x->h_batch = h; x->h_batch_st = hs; x->batch_cams = nc; x->batch_queries = nq;
+    x->batch_total = -1;                              // the order of the last call stayed in the old block
+    return SVO_OK;
+}
+
+static const char* batch_offsets_text(RbOffsets e) {
+    switch (e) {
+    case RB_OFFSETS_COUNT: return "svo_desc_index_localize_batch: n_cameras must be 0 .. 1024";
+    case RB_OFFSETS_NULL: return "svo_desc_index_localize_batch: null query_begin";
+    case RB_OFFSETS_FIRST: return "svo_desc_index_localize_batch: query_begin[0] must be 0";
+    case RB_OFFSETS_ORDER: return "svo_desc_index_localize_batch: query_begin must not decrease";
+    case RB_OFFSETS_SLICE: return "svo_desc_index_localize_batch: at most 4096 queries per camera";
+    default: return "svo_desc_index_localize_batch: at most 1 << 20 queries in all";
+    }
+}
+
+// Everything is decided first — the refusals of the single calls for every camera, and the offsets' own — then one upload, the order,
+// the search group by group (rb_next_group), the selection, the PnP over n_cameras sequences, the inlier flags, the copies back, and
+// the call's one wait.
+// times: from the first kernel to the last
+extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, const float* K, const svo_reloc_guide* guides,
+                                             const int32_t* query_begin, const uint8_t* query, const float* xy, const svo_reloc_params* p,
+                                             svo_reloc_result* results, int32_t* cand_query, int32_t* cand_row, uint8_t* cand_inlier) {
+    if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null index / params");
+    if (const RbOffsets e = rb_check_offsets(n_cameras, query_begin); e != RB_OFFSETS_OK) return fail(SVO_ERR_ARG, batch_offsets_text(e));
+    if (n_cameras > 0 && (!K || !results)) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null K / results");
+    const int total = n_cameras > 0 ? query_begin[n_cameras] : 0;
+    if (total > 0 && (!query || !xy)) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null query / xy");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "relocalisation: the index has no points (svo_desc_index_enable_points)");
+    std::vector<SearchGuide> sg((size_t)(guides ? n_cameras : 0));
+    int rc, row_lo = p->row_lo, row_hi = p->row_hi;
+    for (int b = 0; b < n_cameras && guides; b++)
+        if ((rc = guide_check(x, K + 9 * b, guides + b, nullptr, &sg[(size_t)b])) != SVO_OK) return rc;
+    if ((rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
+    if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
+    if (p->ratio_num < 1 || p->ratio_num > SVO_RELOC_MAX_RATIO || p->ratio_den < 1 || p->ratio_den > SVO_RELOC_MAX_RATIO)
+        return fail(SVO_ERR_ARG, "relocalisation: ratio_num and ratio_den must be 1 .. 1 << 20");
+    if (p->min_candidates < 6) return fail(SVO_ERR_ARG, "relocalisation: min_candidates must be >= 6 (4 and 5 points take svo_camera_to_world's direct routes)");
+    MHIP(call_begin(x));
+    if (n_cameras == 0) return SVO_OK;
+    // ---- room: the plan's partial states, the staging, the stage context
+    const int max_slice = rb_max_slice(n_cameras, query_begin);
+    const RbRange r = rb_plan_range(row_lo, row_hi, x->chunk_rows, max_slice);
+    const MatchRange mr{r.row_lo, r.row_hi, r.chunk_rows, r.chunk0, r.n_chunks};
+    size_t states = 0;
+    for (int cam = 0; cam < n_cameras;) {
+        const RbGroup g = rb_next_group(n_cameras, query_begin, cam, r.n_chunks);
+        states = rb_group_states(g, r.n_chunks) > states ? rb_group_states(g, r.n_chunks) : states;
+        cam = g.cam1;
+    }
+    DevBuffers d;
+    svo_context* old = nullptr;
+    rc = svo_reloc_batch_ctx(x->device, n_cameras, max_slice > 64 ? max_slice : 64, p->ransac_iterations, p->reproj_error, p->confidence,
+                             &x->batch_ctx, &old, &d);
+    if (old) x->batch_ctx_outgrown.push_back(old);
+    if (rc != SVO_OK || (states > 0 && (rc = part_room(x, states)) != SVO_OK) || (rc = batch_room(x, (size_t)n_cameras, (size_t)total)) != SVO_OK) return rc;
+    // ---- the upload: one copy of the staging's first part, one of the state rows
+    const RbLayout l = rb_layout((size_t)n_cameras, (size_t)total);             // cut for this call: it fits the blocks, and the copies carry no slack
+    uint8_t *h = x->h_batch, *dv = x->d_batch;
+    memcpy(h + l.query, query, (size_t)total * SVO_DESC_BYTES);
+    memcpy(h + l.xy, xy, (size_t)total * sizeof(float2));
+    memcpy(h + l.begin, query_begin, (size_t)(n_cameras + 1) * sizeof(int32_t));
+    RelocBatchCam* h_cams = (RelocBatchCam*)(h + l.cams);
+    SeqState *h_up = x->h_batch_st, *h_down = x->h_batch_st + x->batch_cams;
+    for (int b = 0; b < n_cameras; b++) {             // the state row as reloc_run sets it
+        h_cams[b] = guides ? RelocBatchCam{sg[(size_t)b].pose, sg[(size_t)b].radius, 0} : RelocBatchCam{};
+        SeqState& hs = h_up[b];
+        memset(&hs, 0, sizeof(hs));
+        hs.active = 1; hs.fail_reason = 0; hs.feat_buf = 0;
+        memcpy(hs.K, K + 9 * b, sizeof(float) * 9); memcpy(hs.R, results[b].R, sizeof(double) * 9); memcpy(hs.t, results[b].t, sizeof(double) * 3);
+    }
+    MHIP(hipMemcpyAsync(dv, h, l.up_end, hipMemcpyHostToDevice, x->stream));
+    MHIP(hipMemcpyAsync(d.st, h_up, (size_t)n_cameras * sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
+    const uint32_t* d_query = (const uint32_t*)(dv + l.query);
+    const float2* d_qxy = (const float2*)(dv + l.xy);
+    const int32_t* d_begin = (const int32_t*)(dv + l.begin);
+    const RelocBatchCam* d_cams = (const RelocBatchCam*)(dv + l.cams);
+    int32_t *d_order = (int32_t*)(dv + l.order), *d_ncand = (int32_t*)(dv + l.n_cand);
+    int32_t *d_cq = (int32_t*)(dv + l.cand_query), *d_cr = (int32_t*)(dv + l.cand_row);
+    svo_desc_match* d_match = (svo_desc_match*)(dv + l.match);
+    // ---- the kernels
+    const bool ordered = guides && x->guided_sort && total > 0;
+    MHIP(span_mark(x, true, 0));
+    if (ordered) launch_reloc_batch_order(d_qxy, d_begin, d_cams, n_cameras, d_order, x->stream);
+    for (int cam = 0; cam < n_cameras;) {             // a group's partial states are merged before the next group overwrites them
+        const RbGroup g = rb_next_group(n_cameras, query_begin, cam, r.n_chunks);
+        const int m = g.q1 - g.q0;
+        if (guides) {
+            const RelocBatchSearch a{(const uint32_t*)x->d_desc, x->d_ids, x->d_points, d_cams, d_begin, d_query, d_qxy, ordered ? d_order : nullptr,
+                                     r, g.cam0, g.q0, x->d_part};
+            launch_desc_match_guided_batch(a, rb_guided_grid(g, r.n_chunks), x->stream);
+        } else {
+            launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, d_query + (size_t)g.q0 * 8, m, mr, x->d_part, x->stream);
+        }
+        launch_desc_match_merge(x->d_part, x->d_ids, m, mr, d_match + g.q0, x->stream);
+        cam = g.cam1;
+    }
+    const RelocBatchSelect sel{d_match, x->d_points, d_qxy, d_begin, RelocRule{p->max_dist, p->ratio_num, p->ratio_den}, p->min_candidates,
+                               d.tl1, d.world, d.st, d.CAP, d_cq, d_cr, d_ncand};
+    launch_reloc_select_batch(sel, n_cameras, x->stream);
+    launch_pnp_subsets(d, x->stream);
+    launch_pnp(d, x->stream);
+    launch_reloc_batch_inliers(d.inlier, d.CAP, d_begin, d_ncand, n_cameras, max_slice, dv + l.inlier, x->stream);
+    MHIP(hipGetLastError());
+    MHIP(span_mark(x, true, 1));
+    x->batch_total = total; x->batch_last_cams = n_cameras; x->batch_ordered = ordered;
+    // ---- back: the counts, the lists and the flags in one copy, the state rows in another
+    MHIP(hipMemcpyAsync(h + l.n_cand, dv + l.n_cand, l.down_end - l.n_cand, hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipMemcpyAsync(h_down, d.st, (size_t)n_cameras * sizeof(SeqState), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
+    MHIP(span_read(x));
+    const int32_t* h_ncand = (const int32_t*)(h + l.n_cand);
+    const int32_t *h_cq = (const int32_t*)(h + l.cand_query), *h_cr = (const int32_t*)(h + l.cand_row);
+    for (int b = 0; b < n_cameras; b++) {             // reloc_run's reading of one camera
+        const int q0 = query_begin[b], nc = h_ncand[b];
+        svo_reloc_result* res = results + b;
+        const SeqState& hs = h_down[b];
+        if (cand_query) memcpy(cand_query + q0, h_cq + q0, (size_t)nc * sizeof(int32_t));
+        if (cand_row) memcpy(cand_row + q0, h_cr + q0, (size_t)nc * sizeof(int32_t));
+        res->success = 0; res->n_candidates = nc; res->n_inliers = 0; res->iters_run = 0;
+        memset(res->T, 0, sizeof(res->T));
+        if (cand_inlier) memset(cand_inlier + q0, 0, (size_t)nc);
+        if (nc < p->min_candidates) continue;         // rule 4: every PnP kernel found the row not live
+        res->iters_run = hs.pnp_iters;
+        if (hs.pnp_best < 0) continue;                // no pose: R, t untouched
+        memcpy(res->R, hs.R, sizeof(double) * 9); memcpy(res->t, hs.t, sizeof(double) * 3); memcpy(res->T, hs.last_T, sizeof(double) * 16);
+        res->success = 1; res->n_inliers = hs.n_inliers;
+        if (cand_inlier) memcpy(cand_inlier + q0, h + l.inlier + q0, (size_t)nc);
+    }
+    return SVO_OK;
+}
+
+// diagnostic: the lane order of the last batch call as global query numbers (the identity where k_reloc_batch_order did not run)
+extern "C" int svo_desc_index_get_batch_order(const svo_desc_index* x, int cap, int32_t* order, int* n) {
+    if (!x || !n || cap < 0 || (cap > 0 && !order)) return fail(SVO_ERR_ARG, "svo_desc_index_get_batch_order: null index / n / order");
+    if (x->batch_total < 0) return fail(SVO_ERR_STATE, "svo_desc_index_get_batch_order: no batch call has been made (or the staging has grown since)");
+    *n = x->batch_total;
+    const int m = cap < x->batch_total ? cap : x->batch_total;
+    if (m == 0) return SVO_OK;
+    if (!x->batch_ordered) { for (int i = 0; i < m; i++) order[i] = i; return SVO_OK; }
+    MHIP(hipSetDevice(x->device));
+    const RbLayout l = rb_layout((size_t)x->batch_last_cams, (size_t)x->batch_total);
+    MHIP(hipMemcpyAsync(order, x->d_batch + l.order, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));
+    return SVO_OK;
 }
 
 // ---- index maintenance (include/svo.h, "Index maintenance") ----

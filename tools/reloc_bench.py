@@ -19,7 +19,14 @@ Prints one JSON line.
 off by 0.005 rad and 0.05 m, so that RADIUS px admits the fraction of the rows a tracker's frame would.  In one process and
 alternating rounds: the unguided localize, and localize_guided with the query sort on and off — the whole call, and the search
 kernels alone (svo_desc_index_set_timing: k_desc_match + merge for the unguided search, k_guide_project + k_desc_match_guided + merge
-for the guided one)."""
+for the guided one).
+
+--batch B[,B...] runs the batched leg (include/svo.h, "Batched relocalisation") on the guided leg's index and frame: one
+svo_desc_index_localize_batch call of B cameras — each camera the frame's queries under a prior of its own — against a loop of B
+single calls, through the C entries with the arguments prepared, in the same process and alternating rounds, guided (at --guided,
+24 px by default) and unguided.  Before any timing both paths must return the same result records, byte for byte.  Per leg: the
+medians with the rounds' minimum and maximum beside them, their ratio, and the batch call's device span (last_kernels_ms), so that
+the host's share of the call shows.  The issue's sweep: --batch 1,8,64,256,512."""
 import argparse
 import json
 import os
@@ -166,6 +173,85 @@ def child_guided(size, n, rounds, radius):
     print(json.dumps(r))
 
 
+def child_batch(size, n, rounds, radius, counts):
+    """svo_desc_index_localize_batch against a loop of B single calls, guided and unguided, on child_guided's index and frame"""
+    import ctypes as C
+    import guide_cases as gcases
+    from reloc_cases import flip
+    from stereo_visual_odometry_amd import _lib, api
+    lib, ptr = _lib.lib, _lib.ptr
+    rng = np.random.default_rng(size)
+    K = np.array([[718.856, 0, 607.1928], [0, 718.856, 185.2157], [0, 0, 1]], np.float32)
+    ix = api.DescriptorIndex(size, points=True)
+    head = None
+    for i0 in range(0, size, 1 << 16):
+        m = min(1 << 16, size - i0)
+        z = rng.uniform(4, 40, m)
+        px = np.stack([rng.uniform(0, 1241, m), rng.uniform(0, 376, m)], 1)
+        p = np.stack([(px[:, 0] - K[0, 2]) / K[0, 0] * z, (px[:, 1] - K[1, 2]) / K[1, 1] * z, z], 1).astype(np.float32)
+        d = rng.integers(0, 256, (m, 32), dtype=np.uint8)
+        ix.add_points(d, (1 << 32) + i0 + np.arange(m, dtype=np.uint64), p)
+        if i0 == 0:
+            head = (d[:n], p[:n])
+    query = np.stack([flip(rng, d, 3) for d in head[0]])
+    c = head[1].astype(np.float64)
+    xy = (c[:, :2] / c[:, 2:] * [K[0, 0], K[1, 1]] + [K[0, 2], K[1, 2]]).astype(np.float32)
+    xy[:n // 8] += 50
+    prm = ix.reloc_params()
+    legs = []
+    for B in counts:
+        # every camera its own prior: the true pose off by about 0.005 rad and 0.05 m, differently per camera
+        guides = [ix.guide(gcases.rot(0.003 + 1e-5 * b, -0.003 + 2e-5 * b, 0.002), np.array([0.03, -0.03, 0.03]) + 1e-4 * b, radius) for b in range(B)]
+        g = (_lib.SvoRelocGuide * B)(*guides)
+        Kf = np.ascontiguousarray(np.broadcast_to(K.reshape(1, 9), (B, 9)))
+        q_all, xy_all = np.ascontiguousarray(np.tile(query, (B, 1))), np.ascontiguousarray(np.tile(xy, (B, 1)))
+        begin = (np.arange(B + 1) * n).astype(np.int32)
+        res_b, res_s = (_lib.SvoRelocResult * B)(), (_lib.SvoRelocResult * B)()
+
+        def guess(res):
+            for b in range(B):
+                res[b].R[:] = guides[b].R[:]; res[b].t[:] = guides[b].t[:]
+
+        def batch(guided):
+            guess(res_b)
+            t0 = time.perf_counter()
+            rc = lib.svo_desc_index_localize_batch(ix._h, B, ptr(Kf), g if guided else None, ptr(begin), ptr(q_all), ptr(xy_all), C.byref(prm), res_b, None, None, None)
+            dt = (time.perf_counter() - t0) * 1e3
+            assert rc == 0, _lib.lib.svo_last_error()
+            return dt
+
+        def loop(guided):
+            guess(res_s)
+            t0 = time.perf_counter()
+            for b in range(B):
+                if guided:
+                    rc = lib.svo_desc_index_localize_guided(ix._h, ptr(K), C.byref(guides[b]), n, ptr(query), ptr(xy), C.byref(prm), C.byref(res_s[b]), None, None, None)
+                else:
+                    rc = lib.svo_desc_index_localize(ix._h, ptr(K), n, ptr(query), ptr(xy), C.byref(prm), C.byref(res_s[b]), None, None, None)
+                assert rc == 0, _lib.lib.svo_last_error()
+            return (time.perf_counter() - t0) * 1e3
+
+        for guided in (True, False):
+            batch(guided); loop(guided)
+            assert bytes(res_b) == bytes(res_s), "the batch call and the loop of single calls differ (B = %d, guided = %s)" % (B, guided)
+            assert all(r.success for r in res_b), "a camera does not localize"
+            r_n = max(3, min(rounds, 4096 // B))                  # fewer rounds where one takes long
+            tb, tl, kb = [], [], []
+            ix.set_timing(True)
+            for _ in range(r_n):
+                tb.append(batch(guided)); kb.append(ix.stats()["last_kernels_ms"])
+                ix.set_timing(False)
+                tl.append(loop(guided))
+                ix.set_timing(True)
+            ix.set_timing(False)
+            legs.append(dict(cameras=B, guided=guided, rounds=r_n, batch_call_ms_median=float(np.median(tb)), batch_call_ms_min=float(min(tb)),
+                             batch_call_ms_max=float(max(tb)), batch_kernels_ms_median=float(np.median(kb)), loop_ms_median=float(np.median(tl)),
+                             loop_ms_min=float(min(tl)), loop_ms_max=float(max(tl)), loop_over_batch=float(np.median(tl) / np.median(tb)),
+                             per_camera_batch_ms=float(np.median(tb) / B), per_camera_loop_ms=float(np.median(tl) / B)))
+    ix.close()
+    print(json.dumps(dict(size=size, queries=n, radius=radius, legs=legs)))
+
+
 def step(cmd, limit, what):
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
     if r.returncode != 0:
@@ -181,18 +267,28 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--guided", type=float, default=None, metavar="RADIUS", help="the guided leg at this radius in pixels, beside the unguided one")
+    ap.add_argument("--batch", default=None, metavar="B[,B...]", help="svo_desc_index_localize_batch of B cameras against a loop of B single calls (guided at --guided, default 24 px, and unguided)")
     ap.add_argument("--child", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.batch is not None and args.guided is None:
+        args.guided = 24.0
+    if args.child is not None and args.batch is not None:
+        return child_batch(args.child, args.queries, args.rounds, args.guided, [int(b) for b in args.batch.split(",")])
     if args.child is not None:
         return child_guided(args.child, args.queries, args.rounds, args.guided) if args.guided is not None else child(args.child, args.queries, args.rounds)
     out = dict(shape="%d queries of a scene inside an index of random rows with points; alternating rounds" % args.queries, sizes=[])
-    if args.guided is not None:
+    if args.batch is not None:
+        out["shape"] = ("one batch call of B cameras against a loop of B single calls in the same process, alternating rounds; %d queries per camera of a frame "
+                        "inside an index of points spread over a 1241 x 376 view; every camera its own prior; guided at %g px, and unguided" % (args.queries, args.guided))
+    elif args.guided is not None:
         out["shape"] = "%d queries of a frame inside an index of points spread over a 1241 x 376 view; guided at %g px; alternating rounds" % (args.queries, args.guided)
     for s in (int(x) for x in args.sizes.split(",")):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", str(s), "--queries", str(args.queries), "--rounds", str(args.rounds)]
         if args.guided is not None:
             cmd += ["--guided", str(args.guided)]
-        out["sizes"].append(json.loads(step(cmd, 400, "the relocalisation at %d rows" % s)))
+        if args.batch is not None:
+            cmd += ["--batch", args.batch]
+        out["sizes"].append(json.loads(step(cmd, 900 if args.batch else 400, "the relocalisation at %d rows" % s)))
     line = json.dumps(out)
     print(line)
     if args.out:
