@@ -785,6 +785,93 @@ int svo_desc_index_localize_batch(svo_desc_index* index, int n_cameras,
  * min(cap, *n) entries.  SVO_ERR_STATE: no batch call yet, or the staging has grown since. */
 int svo_desc_index_get_batch_order(const svo_desc_index* index, int cap, int32_t* order, int* n);
 
+/* ---- Map alignment: the rigid transform between two row spans of the index ----------------------------------------------------------
+ * Merging a second sequence's map, and closing a loop, need the transform between two sets of landmarks that are already in the
+ * index: a 3-D to 3-D alignment, not a PnP from one image's pixels.  svo_desc_index_align searches the descriptors of a SOURCE span
+ * S = [src_lo, src_hi) in a DESTINATION span D = [dst_lo, dst_hi), pairs rows up, and fits x_dst = R x_src + t by RANSAC and refit,
+ * all on the device: no descriptor leaves it, one host synchronisation.  The result's T goes straight into
+ * svo_desc_index_transform_points(index, T, src_lo, src_hi, ...).  Only SE(3): stereo maps are metric.  Sim(3) (a scale) is not offered.
+ *
+ * Both spans follow the row_hi = -1 convention.  S has n = src_hi - src_lo <= SVO_ALIGN_MAX_ROWS rows, and S and D share no row
+ * (spans that touch are legal; an empty span shares nothing).  Rules 1 - 5 are defined on integers.  tag[r], id[r], xyz[r]: row r's.
+ *  1. Search.  For j = 0 .. n - 1, m_j is svo_desc_index_match's result row for the query "descriptor of row src_lo + j" over D,
+ *     equal in every bit: the same kernels read the query from the index itself.
+ *  2. Accept.  j is accepted when tag[src_lo + j] != SVO_POINT_NONE and rule 1 of "Relocalisation" holds for m_j: a row with a
+ *     point, dist <= max_dist, dist * ratio_den < dist2 * ratio_num strictly (257 passes).
+ *  3. One source row per destination landmark.  Among the accepted j with the same m_j.id only the smallest (m_j.dist, j) survives
+ *     (rule 2 of "Relocalisation").
+ *  4. One destination per source landmark.  Among the survivors of rule 3 with the same id[src_lo + j] only the smallest
+ *     (m_j.dist, j) survives: a landmark seen in k frames has k source rows and would otherwise vote k times.
+ *  5. Pairs.  The survivors in increasing j: pair c is (src row src_lo + j, dst row m_j.row, p_c = xyz[src row], q_c = xyz[dst row]).
+ *     n_pairs < min_pairs: success = 0, nothing further runs, every other field of the result is 0 and best_hypothesis is -1.
+ *  6. Hypotheses.  H = hypotheses, 1 .. SVO_ALIGN_MAX_HYPOTHESES, all evaluated: there is no adaptive stop.  Hypothesis h (0 .. H - 1)
+ *     draws three distinct pair numbers with a counter-based generator: draw k = 0, 1, .. is
+ *         (mix64((uint64_t)h << 32 | k) >> 32) % n_pairs,
+ *     mix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
+ *     (splitmix64's finaliser, modulo 2^64).  A draw equal to an earlier one of the same hypothesis is skipped.  After 64 draws a
+ *     position still missing takes the smallest pair number not yet used, so the loop ends whatever the generator gives.
+ *     svo_align_sample is that function.
+ *  7. Model.  Horn's closed form in f64 on the three pairs, the points widened from f32: the centroids, the centred 3 x 3
+ *     cross-covariance, the symmetric 4 x 4 matrix, its eigenvectors by cyclic Jacobi, the one of the largest eigenvalue as a unit
+ *     quaternion, R, and t = c_q - R c_p.  A model with a non-finite entry scores 0.
+ *  8. Score.  count_h = #{c : |R p_c + t - q_c|^2 <= inlier_dist^2}, in f64, the compare inclusive (inlier_dist widened, then
+ *     squared).  best = the largest count; at equal counts the smallest h.
+ *  9. Refit.  The inlier set starts as best's.  Up to refit_rounds times, while the set has at least 3 members: fit the model of
+ *     rule 7 to all members; the new set is every pair within inlier_dist of that model; the round is counted; stop when the set
+ *     did not change.  Every sum is taken in a fixed order that depends on the pair numbers only: the same call gives the same bits.
+ * 10. Result.  The model is the last one fitted (best's where no round ran), the inliers the last set.  success = n_inliers >=
+ *     min_pairs.  On success R, t (x_dst = R x_src + t), T (the same as a row-major 4 x 4) and rms (the root of the inliers' mean
+ *     squared residual); zeros otherwise.  n_pairs, n_inliers, best_hypothesis, best_count and refit_rounds_run always.
+ *
+ * Against an f64 reference that takes its eigenvectors and sums another way the models differ in their last bits, so a pair whose
+ * residual sits within rounding of inlier_dist may fall on either side; apart from such pairs the sets are the reference's.
+ *
+ * Every call is synchronous, synchronises once, waits for the index's own stream only and is legal with frames in flight.  A refused
+ * call changes nothing, its outputs included.  With svo_desc_index_set_timing on, last_kernels_ms is the device span from the first
+ * kernel the call launches to the last.
+ * SVO_ERR_STATE: an index without points.  SVO_ERR_ARG: a span svo_desc_index_match refuses as a row range; n > 4096; spans that
+ * share a row; and, for svo_desc_index_pair_rows and svo_desc_index_align, max_dist outside 0 .. 256, a ratio term outside
+ * 1 .. 1 << 20, min_pairs outside 3 .. 4096, hypotheses outside 1 .. 1024, refit_rounds outside 0 .. 8, inlier_dist not finite or <= 0.
+ *
+ * Memory.  The search's n result rows (32 n bytes) go where svo_desc_index_match's go, the index's 4096-row result buffer (128 KiB,
+ * held since the index was created).  The rest is one device block the index allocates at the first pair_rows or align call and
+ * frees with the index, laid out for n = 4096 and H = 1024 with every part rounded up to 256 bytes: the result row (136 bytes), the
+ * two row lists (4 n each), the inlier flags (n), the packed pairs (24 n), the H counts (4 H) and the H models (96 H): 237 824
+ * bytes; its first 37 120 bytes have a pinned twin.  Below 400 KiB in all. */
+#define SVO_ALIGN_MAX_ROWS 4096
+#define SVO_ALIGN_MAX_HYPOTHESES 1024
+typedef struct {
+    int32_t src_lo, src_hi;      /* S: the rows that move; at most SVO_ALIGN_MAX_ROWS */
+    int32_t dst_lo, dst_hi;      /* D: the rows searched */
+    int32_t max_dist;            /* rule 2: 0 .. 256 */
+    int32_t ratio_num, ratio_den; /* rule 2: 1 .. 1 << 20 each */
+    int32_t min_pairs;           /* rules 5 and 10: 3 .. 4096 */
+    int32_t hypotheses;          /* rule 6: 1 .. SVO_ALIGN_MAX_HYPOTHESES */
+    int32_t refit_rounds;        /* rule 9: 0 .. 8 */
+    float   inlier_dist;         /* rules 8 and 9, in the map's unit: finite, > 0 */
+    int32_t reserved;            /* 0 */
+} svo_align_params;
+typedef struct {
+    int32_t success, n_pairs, n_inliers, best_hypothesis, best_count, refit_rounds_run;
+    double  R[9], t[3];          /* x_dst = R x_src + t */
+    double  T[16];               /* the same, row-major 4 x 4: svo_desc_index_transform_points' argument */
+    double  rms;
+} svo_align_result;
+/* max_dist = 40, ratio 7 / 10 (svo_reloc_params_default's), min_pairs = 6, hypotheses = 256, refit_rounds = 4, src = dst = {0, -1}
+ * (the caller sets the spans).  inlier_dist is an argument because no default in metres has been measured for any stereo rig: it
+ * depends on the baseline, the depth and the triangulation's noise, and this header does not invent one. */
+void svo_align_params_default(svo_align_params* params, float inlier_dist);
+/* Rule 6's sampler on the host: out[0 .. 3) for hypothesis h of n_pairs pairs.  SVO_ERR_ARG: n_pairs < 3, NULL out. */
+int svo_align_sample(uint32_t h, int32_t n_pairs, int32_t* out);
+/* Rule 1 alone: out (host) receives n result rows.  The index needs no points for this call. */
+int svo_desc_index_match_rows(svo_desc_index* index, int src_lo, int src_hi, int dst_lo, int dst_hi, svo_desc_match* out);
+/* Rules 1 - 5: *n_pairs and, where non-NULL, the pairs' source and destination rows, each with room for n entries.  Every
+ * parameter is checked as svo_desc_index_align checks it; min_pairs, hypotheses, refit_rounds and inlier_dist play no other part. */
+int svo_desc_index_pair_rows(svo_desc_index* index, const svo_align_params* params, int* n_pairs, int32_t* pair_src, int32_t* pair_dst);
+/* All of it.  pair_src, pair_dst, pair_inlier (1 / 0): n entries each, each may be NULL; the first result->n_pairs are written. */
+int svo_desc_index_align(svo_desc_index* index, const svo_align_params* params, svo_align_result* result, int32_t* pair_src,
+                         int32_t* pair_dst, uint8_t* pair_inlier);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the

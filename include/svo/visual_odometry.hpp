@@ -660,6 +660,33 @@ class DescriptorIndex {
         svo_throw(svo_desc_index_transform_points(index_, T, rows.first, rows.second, tags.first, tags.second, &moved, &skipped));
         return {moved, skipped};
     }
+    // ---- map alignment (svo.h, "Map alignment"): the rigid transform between two row spans, found on the device
+    struct Pairs { std::vector<int32_t> src, dst; std::vector<uint8_t> inlier; };          // inlier: align only
+    // svo_align_params_default; the caller sets the spans.  inlier_dist has no default: none has been measured for any rig
+    static svo_align_params align_params(float inlier_dist) { svo_align_params p; svo_align_params_default(&p, inlier_dist); return p; }
+    // match with the descriptors of rows [src.first, src.second) as the queries, over rows [dst.first, dst.second)
+    std::vector<svo_desc_match> match_rows(std::pair<int, int> src, std::pair<int, int> dst) {
+        std::vector<svo_desc_match> out(span_rows(src.first, src.second));
+        svo_throw(svo_desc_index_match_rows(index_, src.first, src.second, dst.first, dst.second, out.data()));
+        return out;
+    }
+    // rules 1 - 5: one pair of rows per landmark on either side, in increasing source row
+    Pairs pair_rows(const svo_align_params& prm) {
+        Pairs p = pairs_room(prm, false);
+        int k = 0;
+        svo_throw(svo_desc_index_pair_rows(index_, &prm, &k, p.src.data(), p.dst.data()));
+        p.src.resize((size_t)k); p.dst.resize((size_t)k);
+        return p;
+    }
+    // x_dst = R x_src + t between the source span's landmarks and their matches; result.T is transform_points' argument
+    svo_align_result align(const svo_align_params& prm, Pairs* pairs = nullptr) {
+        Pairs p = pairs_room(prm, true);
+        svo_align_result r;
+        svo_throw(svo_desc_index_align(index_, &prm, &r, p.src.data(), p.dst.data(), p.inlier.data()));
+        p.src.resize((size_t)r.n_pairs); p.dst.resize((size_t)r.n_pairs); p.inlier.resize((size_t)r.n_pairs);
+        if (pairs) *pairs = std::move(p);
+        return r;
+    }
     int retire_slab_rows() const { return svo_desc_index_get_retire_slab_rows(index_); }
     void retire_slab_rows(int rows) { svo_throw(svo_desc_index_set_retire_slab_rows(index_, rows)); }   // 0: the default
     int size() const { return svo_desc_index_size(index_); }
@@ -669,6 +696,13 @@ class DescriptorIndex {
    private:
     // the rows of a possibly empty descriptor vector
     static const uint8_t* rows(const std::vector<Descriptor>& d) { return d.empty() ? nullptr : d[0].data(); }
+    // the rows of a span as the library will resolve it (0 for one it will refuse), and the room for its pairs
+    size_t span_rows(int lo, int hi) const { const int h = hi == -1 || hi > size() ? size() : hi; return lo >= 0 && h > lo ? (size_t)(h - lo) : 0; }
+    Pairs pairs_room(const svo_align_params& prm, bool inlier) const {
+        const size_t n = span_rows(prm.src_lo, prm.src_hi);
+        Pairs p; p.src.resize(n); p.dst.resize(n); p.inlier.resize(inlier ? n : 0);
+        return p;
+    }
     static void one_pixel_each(const char* what, const std::vector<Descriptor>& query, const std::vector<float>& xy) {
         if (xy.size() != 2 * query.size()) throw std::runtime_error(std::string("DescriptorIndex::") + what + ": one pixel per query expected");
     }

@@ -40,6 +40,7 @@ DESC_BYTES = 32
 MATCH_NONE, MATCH_NO_DIST = -1, 257
 POINT_NONE, RELOC_MAX_QUERIES = -1, 4096
 RELOC_BATCH_MAX_CAMERAS, RELOC_BATCH_MAX_QUERIES = 1024, 1 << 20
+ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES = 4096, 1024
 # index maintenance (svo.h SVO_RETIRE_*)
 RETIRE_BY_TAG, RETIRE_BY_IDS, RETIRE_LATEST_PER_ID, RETIRE_SCOPE = 1, 2, 4, 8
 # motion priors (svo.h SVO_PRIOR_*)
@@ -123,6 +124,16 @@ class SvoRelocGuide(C.Structure):
     _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("radius", C.c_float), ("reserved", C.c_int32)]
 
 
+class SvoAlignParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("src_lo", "src_hi", "dst_lo", "dst_hi", "max_dist", "ratio_num", "ratio_den", "min_pairs",
+                                         "hypotheses", "refit_rounds")] + [("inlier_dist", C.c_float), ("reserved", C.c_int32)]
+
+
+class SvoAlignResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("success", "n_pairs", "n_inliers", "best_hypothesis", "best_count", "refit_rounds_run")] + \
+               [("R", C.c_double * 9), ("t", C.c_double * 3), ("T", C.c_double * 16), ("rms", C.c_double)]
+
+
 class SvoRetireRule(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("row_lo", C.c_int32), ("row_hi", C.c_int32), ("tag_lo", C.c_int32), ("tag_hi", C.c_int32),
                 ("n_ids", C.c_int32), ("ids", C.c_void_p)]
@@ -199,6 +210,11 @@ PROTOTYPES = {
     "svo_desc_index_get_retire_stats": (I, (P, P)),
     "svo_desc_index_localize_batch": (I, (P, I, P, P, P, P, P, P, P, P, P, P)),
     "svo_desc_index_get_batch_order": (I, (P, I, P, P)),
+    "svo_align_params_default": (None, (P, F)),
+    "svo_align_sample": (I, (U32, I32, P)),
+    "svo_desc_index_match_rows": (I, (P, I, I, I, I, P)),
+    "svo_desc_index_pair_rows": (I, (P, P, P, P, P)),
+    "svo_desc_index_align": (I, (P, P, P, P, P, P)),
     "svo_set_detection_mask": (I, (P, I, P, I, I)),
     "svo_get_detection_mask": (I, (P, I, P, P)),
     "svo_set_motion_prior": (I, (P, I, P, P)),

@@ -368,6 +368,7 @@ def descriptor_pattern():
 
 
 RelocResult = collections.namedtuple("RelocResult", "success n_candidates n_inliers iters_run R t T")
+AlignResult = collections.namedtuple("AlignResult", "success n_pairs n_inliers best_hypothesis best_count refit_rounds_run R t T rms")
 
 
 class DescriptorIndex:
@@ -680,6 +681,55 @@ class DescriptorIndex:
         st = _lib.SvoDescRetireStats()
         check(lib.svo_desc_index_get_retire_stats(self._h, C.byref(st)))
         return {f[0]: getattr(st, f[0]) for f in st._fields_}
+
+    # ---- map alignment (svo.h, "Map alignment"): the rigid transform between two row spans, found on the device
+    @staticmethod
+    def align_params(src, dst, inlier_dist, **over):
+        """svo_align_params_default with the spans src = (lo, hi), dst = (lo, hi) and fields replaced: max_dist, ratio_num, ratio_den,
+        min_pairs, hypotheses, refit_rounds.  inlier_dist has no default: none has been measured for any rig."""
+        p = _lib.SvoAlignParams()
+        lib.svo_align_params_default(C.byref(p), float(inlier_dist))
+        p.src_lo, p.src_hi, p.dst_lo, p.dst_hi = int(src[0]), int(src[1]), int(dst[0]), int(dst[1])
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise AttributeError("svo_align_params has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+    def _span_rows(self, span):
+        """the rows of a span as the library will resolve it (0 for one it will refuse)"""
+        lo, hi, size = int(span[0]), int(span[1]), self.size
+        return max(0, (size if hi == -1 or hi > size else hi) - lo) if lo >= 0 else 0
+
+    def match_rows(self, src, dst):
+        """match with the descriptors of the rows src = (lo, hi) as the queries, searched in the rows dst = (lo, hi), without a host
+        copy of them (svo_desc_index_match_rows) -> match's structured array, one row per source row."""
+        out = np.zeros(self._span_rows(src), _lib.DESC_MATCH_DTYPE)
+        check(lib.svo_desc_index_match_rows(self._h, int(src[0]), int(src[1]), int(dst[0]), int(dst[1]), ptr(out)))
+        return out
+
+    def pair_rows(self, src, dst, inlier_dist=1.0, params=None, **over):
+        """Rules 1 - 5 of "Map alignment" (svo_desc_index_pair_rows) -> (pair_src, pair_dst) int32 row numbers, one pair per landmark
+        on either side, in increasing source row."""
+        p = params if params is not None else self.align_params(src, dst, inlier_dist, **over)
+        n = self._span_rows((p.src_lo, p.src_hi))
+        ps, pd, k = np.zeros(n, np.int32), np.zeros(n, np.int32), C.c_int(0)
+        check(lib.svo_desc_index_pair_rows(self._h, C.byref(p), C.byref(k), ptr(ps), ptr(pd)))
+        return ps[:k.value].copy(), pd[:k.value].copy()
+
+    def align(self, src, dst, inlier_dist, params=None, **over):
+        """The rigid transform x_dst = R x_src + t between the landmarks of the rows src and their matches in the rows dst
+        (svo_desc_index_align) -> (AlignResult, pairs): pairs is a dict of src, dst (row numbers) and inlier (uint8) per pair.
+        result.T is transform_points' argument for the source span."""
+        p = params if params is not None else self.align_params(src, dst, inlier_dist, **over)
+        n = self._span_rows((p.src_lo, p.src_hi))
+        ps, pd, pi = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        r = _lib.SvoAlignResult()
+        check(lib.svo_desc_index_align(self._h, C.byref(p), C.byref(r), ptr(ps), ptr(pd), ptr(pi)))
+        k = r.n_pairs
+        res = AlignResult(bool(r.success), k, r.n_inliers, r.best_hypothesis, r.best_count, r.refit_rounds_run,
+                          np.array(r.R, np.float64).reshape(3, 3), np.array(r.t, np.float64), np.array(r.T, np.float64).reshape(4, 4), r.rms)
+        return res, {"src": ps[:k].copy(), "dst": pd[:k].copy(), "inlier": pi[:k].copy()}
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

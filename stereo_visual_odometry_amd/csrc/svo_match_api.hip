@@ -18,9 +18,14 @@
 // The batch (include/svo.h, "Batched relocalisation"; the kernels are in svo_kernels_reloc_batch.hip, the plan in svo_reloc_batch.hpp):
 // localize_batch is reloc_run for many cameras at once, with a staging (batch_room) and a PnP stage context of its own, both owned by
 // the index; the single calls' 4096-row staging and their path above are untouched by it.
+//
+// The alignment (include/svo.h, "Map alignment"; the kernels are in svo_kernels_align.hip, the rules in svo_align.hpp): align_run,
+// behind match_rows, pair_rows and align, is the same search with the index's own rows as its queries — nothing is staged — then
+// k_align_pairs, k_align_score and k_align_fit, one copy back and one wait.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
 #include "svo_reloc_batch_internal.hpp"
+#include "svo_align_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -93,6 +98,9 @@ struct svo_desc_index {
     std::vector<svo_context*> batch_ctx_outgrown;     // earlier ones, destroyed with the index
     int batch_last_cams = 0, batch_total = -1;                             // the last batch call's queries (-1: none yet), and whether d_batch holds its order
     bool batch_ordered = false;
+    // map alignment: null until the first svo_desc_index_pair_rows or svo_desc_index_align (align_room)
+    uint8_t* d_align = nullptr;                       // align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES)
+    uint8_t* h_align = nullptr;                       // pinned: its first down_end bytes
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -119,6 +127,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         for (svo_context* c : x->batch_ctx_outgrown) svo_destroy(c);
         svo_destroy(x->batch_ctx);
         (void)hipFree(x->d_batch); (void)hipHostFree(x->h_batch); (void)hipHostFree(x->h_batch_st);
+        (void)hipFree(x->d_align); (void)hipHostFree(x->h_align);
         (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
         (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
@@ -408,8 +417,9 @@ static hipError_t span_read(svo_desc_index* x) {
 
 // The one enqueue: the search of the n staged queries (stage_queries) by plan p on the index's stream, d_out[0 .. n) when it has run;
 // no wait.  Guided: the lane order up, the projection, and one launch of the guided kernel.  Unguided: launches of p.batch queries
-// (a multiple of 64 rows, or all of them) back to back.  timed: the search is the span the call times.
-static int search_enqueue(svo_desc_index* x, const SearchPlan& p, int n, bool timed) {
+// (a multiple of 64 rows, or all of them) back to back.  timed: the search is the span the call times.  from: the queries where they
+// are not the staged ones — rows of the index itself (align_run).
+static int search_enqueue(svo_desc_index* x, const SearchPlan& p, int n, bool timed, const uint8_t* from = nullptr) {
     const SearchGuide* g = p.guide;
     if (g && n > 0) {
         guide_order(x, n, g->xy, g->radius, x->h_order);
@@ -419,7 +429,7 @@ static int search_enqueue(svo_desc_index* x, const SearchPlan& p, int n, bool ti
     if (g) launch_guide_project(x->d_points, g->pose, p.r.row_lo, p.r.row_hi, x->d_uv, x->stream);
     for (int i0 = 0; i0 < n; i0 += p.batch) {         // guided: p.batch == n
         const int m = n - i0 < p.batch ? n - i0 : p.batch;
-        const uint32_t* query = (const uint32_t*)(x->d_query + (size_t)i0 * SVO_DESC_BYTES);
+        const uint32_t* query = (const uint32_t*)((from ? from : x->d_query) + (size_t)i0 * SVO_DESC_BYTES);
         if (g) launch_desc_match_guided((const uint32_t*)x->d_desc, x->d_ids, x->d_uv, query, x->d_qxy, x->d_order, m, g->radius, p.r, x->d_part, x->stream);
         else launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, query, m, p.r, x->d_part, x->stream);
         launch_desc_match_merge(x->d_part, x->d_ids, m, p.r, x->d_out + i0, x->stream);
@@ -762,6 +772,132 @@ extern "C" int svo_desc_index_get_batch_order(const svo_desc_index* x, int cap, 
     MHIP(hipMemcpyAsync(order, x->d_batch + l.order, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));
     return SVO_OK;
+}
+
+// ---- map alignment (include/svo.h, "Map alignment"; the kernels are in svo_kernels_align.hip, the rules in svo_align.hpp) ----
+extern "C" void svo_align_params_default(svo_align_params* p, float inlier_dist) {
+    if (!p) return;
+    svo_reloc_params r; svo_reloc_params_default(&r);
+    p->src_lo = 0; p->src_hi = -1; p->dst_lo = 0; p->dst_hi = -1;
+    p->max_dist = r.max_dist; p->ratio_num = r.ratio_num; p->ratio_den = r.ratio_den;
+    p->min_pairs = 6; p->hypotheses = 256; p->refit_rounds = 4; p->inlier_dist = inlier_dist; p->reserved = 0;
+}
+
+extern "C" int svo_align_sample(uint32_t h, int32_t n_pairs, int32_t* out) {
+    if (!out || n_pairs < 3) return fail(SVO_ERR_ARG, "svo_align_sample: null out / n_pairs < 3");
+    int32_t pick[3];
+    align_sample(h, n_pairs, pick);
+    memcpy(out, pick, sizeof(pick));
+    return SVO_OK;
+}
+
+static const char* align_refusal_text(AlignRefusal e) {
+    switch (e) {
+    case ALIGN_SRC_RANGE: return "map alignment: the source span must satisfy 0 <= src_lo <= src_hi <= size";
+    case ALIGN_DST_RANGE: return "map alignment: the destination span must satisfy 0 <= dst_lo <= dst_hi <= size";
+    case ALIGN_ROWS: return "map alignment: at most 4096 source rows per call";
+    case ALIGN_OVERLAP: return "map alignment: the source and the destination span share a row";
+    case ALIGN_MAX_DIST: return "map alignment: max_dist must be 0 .. 256";
+    case ALIGN_RATIO: return "map alignment: ratio_num and ratio_den must be 1 .. 1 << 20";
+    case ALIGN_MIN_PAIRS: return "map alignment: min_pairs must be 3 .. 4096";
+    case ALIGN_HYPOTHESES: return "map alignment: hypotheses must be 1 .. 1024";
+    case ALIGN_REFIT: return "map alignment: refit_rounds must be 0 .. 8";
+    default: return "map alignment: inlier_dist must be finite and > 0";
+    }
+}
+
+// the alignment's device block and its pinned twin, allocated at the first call that pairs and freed with the index
+static int align_room(svo_desc_index* x) {
+    if (x->d_align) return SVO_OK;
+    const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
+    if (!x->h_align) MHIP(hipHostMalloc((void**)&x->h_align, l.down_end, hipHostMallocDefault));
+    MHIP(hipMalloc((void**)&x->d_align, l.total));    // last: d_align says "allocated"
+    return SVO_OK;
+}
+
+// What match_rows (stage 1), pair_rows (2) and align (3) share.  q: the request, checked and with its spans resolved.  Everything is
+// enqueued on the index's stream — the search with rows [src_lo, src_hi) of the index as its queries, the pair kernel, the two
+// RANSAC kernels, one copy back — and the host waits once.
+// times: from the first kernel to the last
+static int align_run(svo_desc_index* x, const AlignRequest& q, int stage, svo_desc_match* rows, int* n_pairs, svo_align_result* res,
+                     int32_t* pair_src, int32_t* pair_dst, uint8_t* pair_inlier) {
+    const int n = q.src_hi - q.src_lo;
+    int rc;
+    MHIP(call_begin(x));
+    SearchPlan plan;
+    if ((stage > 1 && (rc = align_room(x)) != SVO_OK) || (rc = search_plan(x, n, q.dst_lo, q.dst_hi, nullptr, &plan)) != SVO_OK) return rc;
+    if ((rc = search_enqueue(x, plan, n, true, x->d_desc + (size_t)q.src_lo * SVO_DESC_BYTES)) != SVO_OK) return rc;
+    if (stage == 1) {
+        if (n > 0) MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        MHIP(span_read(x));
+        if (n > 0) memcpy(rows, x->h_out, (size_t)n * sizeof(svo_desc_match));
+        return SVO_OK;
+    }
+    const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
+    uint8_t *dv = x->d_align, *h = x->h_align;
+    AlignOut* d_res = (AlignOut*)(dv + l.out);
+    float* d_pairs = (float*)(dv + l.pairs);
+    uint8_t* d_inlier = dv + l.pair_inlier;
+    const AlignPairsArgs pa{x->d_out, x->d_points, x->d_ids, q.src_lo, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den},
+                            (int32_t*)(dv + l.pair_src), (int32_t*)(dv + l.pair_dst), d_inlier, d_pairs, d_res};
+    launch_align_pairs(pa, x->stream);
+    if (stage == 3) {
+        const AlignFitArgs fa{d_pairs, q.hypotheses, q.min_pairs, q.refit_rounds, align_dist2(q.inlier_dist),
+                              (int32_t*)(dv + l.counts), (AlignModel*)(dv + l.models), d_inlier, d_res};
+        launch_align_score(fa, x->stream);
+        launch_align_fit(fa, x->stream);
+    }
+    MHIP(hipGetLastError());
+    MHIP(span_mark(x, true, 1));                      // the span's end moves from the search's last kernel to the call's
+    MHIP(hipMemcpyAsync(h, dv, l.down_end, hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
+    MHIP(span_read(x));
+    const AlignOut& o = *(const AlignOut*)(h + l.out);
+    const int np = o.n_pairs;
+    if (n_pairs) *n_pairs = np;
+    if (pair_src) memcpy(pair_src, h + l.pair_src, (size_t)np * sizeof(int32_t));
+    if (pair_dst) memcpy(pair_dst, h + l.pair_dst, (size_t)np * sizeof(int32_t));
+    if (pair_inlier) memcpy(pair_inlier, h + l.pair_inlier, (size_t)np);
+    if (!res) return SVO_OK;
+    memset(res, 0, sizeof(*res));
+    res->success = o.success; res->n_pairs = np; res->n_inliers = o.n_inliers; res->best_hypothesis = o.best_hypothesis;
+    res->best_count = o.best_count; res->refit_rounds_run = o.refit_rounds_run;
+    if (!o.success) return SVO_OK;
+    memcpy(res->R, o.R, sizeof(o.R)); memcpy(res->t, o.t, sizeof(o.t)); res->rms = o.rms;
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) res->T[4 * r + c] = o.R[3 * r + c]; res->T[4 * r + 3] = o.t[r]; }
+    res->T[15] = 1.;
+    return SVO_OK;
+}
+
+static AlignRequest align_request(const svo_align_params* p) {
+    return AlignRequest{p->src_lo, p->src_hi, p->dst_lo, p->dst_hi, p->max_dist, p->ratio_num, p->ratio_den, p->min_pairs, p->hypotheses,
+                        p->refit_rounds, p->inlier_dist};
+}
+
+extern "C" int svo_desc_index_match_rows(svo_desc_index* x, int src_lo, int src_hi, int dst_lo, int dst_hi, svo_desc_match* out) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    AlignRequest q{src_lo, src_hi, dst_lo, dst_hi, 0, 1, 1, 3, 1, 0, 1.f};
+    if (const AlignRefusal e = align_check_spans(q, x->size); e != ALIGN_OK) return fail(SVO_ERR_ARG, align_refusal_text(e));
+    if (q.src_hi > q.src_lo && !out) return fail(SVO_ERR_ARG, "svo_desc_index_match_rows: null out");
+    return align_run(x, q, 1, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int svo_desc_index_pair_rows(svo_desc_index* x, const svo_align_params* p, int* n_pairs, int32_t* pair_src, int32_t* pair_dst) {
+    if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_pair_rows: null index / params");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "map alignment: the index has no points (svo_desc_index_enable_points)");
+    AlignRequest q = align_request(p);
+    if (const AlignRefusal e = align_check(q, x->size); e != ALIGN_OK) return fail(SVO_ERR_ARG, align_refusal_text(e));
+    return align_run(x, q, 2, nullptr, n_pairs, nullptr, pair_src, pair_dst, nullptr);
+}
+
+extern "C" int svo_desc_index_align(svo_desc_index* x, const svo_align_params* p, svo_align_result* res, int32_t* pair_src, int32_t* pair_dst,
+                                    uint8_t* pair_inlier) {
+    if (!x || !p || !res) return fail(SVO_ERR_ARG, "svo_desc_index_align: null index / params / result");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "map alignment: the index has no points (svo_desc_index_enable_points)");
+    AlignRequest q = align_request(p);
+    if (const AlignRefusal e = align_check(q, x->size); e != ALIGN_OK) return fail(SVO_ERR_ARG, align_refusal_text(e));
+    return align_run(x, q, 3, nullptr, nullptr, res, pair_src, pair_dst, pair_inlier);
 }
 
 // ---- index maintenance (include/svo.h, "Index maintenance") ----

@@ -1,0 +1,145 @@
+"""The map alignment's reference (tests/align_ref.py) against independent statements of the same rules, without a GPU: the pair rules
+against a naive dictionary version on scenes with several rows per landmark on both sides, equal distances, rows without points and
+a lone destination landmark; the refit's R, t against an SVD Kabsch on the same inlier set; the sampler against the library's
+svo_align_sample through ctypes and against its own definition; and that on the GPU tests' scenes the reference ends with exactly
+the true inlier set, no residual near the threshold."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import align_cases as ac
+import align_ref as aref
+import desc_match_ref as mref
+
+
+def naive_pairs(case, max_dist=40, ratio_num=7, ratio_den=10):
+    """rules 2 - 5 with a dictionary per rule"""
+    (s0, s1), (d0, d1) = case["src"], case["dst"]
+    m = mref.match(case["desc"][s0:s1], case["desc"], case["ids"], d0, d1)
+    tags, ids = case["tags"], case["ids"]
+    best = {}
+    for j in range(s1 - s0):
+        row, dist, dist2 = int(m[j]["row"]), int(m[j]["dist"]), int(m[j]["dist2"])
+        if tags[s0 + j] == -1 or row < 0 or tags[row] == -1 or dist > max_dist or not dist * ratio_den < dist2 * ratio_num:
+            continue
+        k = int(m[j]["id"])
+        if k not in best or (dist, j) < best[k]:
+            best[k] = (dist, j)
+    best2 = {}
+    for dist, j in best.values():
+        k = int(ids[s0 + j])
+        if k not in best2 or (dist, j) < best2[k]:
+            best2[k] = (dist, j)
+    js = sorted(j for _, j in best2.values())
+    return [s0 + j for j in js], [int(m[j]["row"]) for j in js]
+
+
+@pytest.mark.parametrize("name", ac.PAIR_SCENES)
+def test_pair_rules_against_a_dictionary_version(name):
+    case = ac.pair_scene(name)
+    ps, pd = aref.pairs(case["desc"], case["ids"], case["tags"], case["src"], case["dst"])
+    want_s, want_d = naive_pairs(case)
+    assert ps.tolist() == want_s and pd.tolist() == want_d
+    ids = case["ids"]
+    assert len(set(ids[ps].tolist())) == len(ps) and len(set(ids[pd].tolist())) == len(pd)       # one pair per landmark on either side
+    assert (case["tags"][ps] >= 0).all() and (case["tags"][pd] >= 0).all()
+    (s0, s1), (d0, d1) = case["src"], case["dst"]
+    assert ((ps >= s0) & (ps < s1)).all() and ((pd >= d0) & (pd < d1)).all() and (np.diff(ps) > 0).all()
+    print(name, "rows", s1 - s0, "pairs", len(ps))
+    if name == "lone":
+        assert len(ps) == 1                           # five source landmarks look like the one destination landmark: rule 3 keeps one
+    elif name == "empty":
+        assert len(ps) == 0
+    else:
+        assert 20 < len(ps) < s1 - s0                 # the scene exercises both rules: fewer pairs than rows
+
+
+def test_the_scenes_exercise_what_they_are_for():
+    c = ac.pair_scene("k_rows")
+    (s0, s1), (d0, d1) = c["src"], c["dst"]
+    assert np.unique(c["ids"][s0:s1], return_counts=True)[1].max() == 3 and np.unique(c["ids"][d0:d1], return_counts=True)[1].max() == 3
+    e = ac.pair_scene("equal")
+    m = mref.match(e["desc"][e["src"][0]:e["src"][1]], e["desc"], e["ids"], *e["dst"])
+    assert (m["dist"] == 0).all() and (m["dist2"] == 0).any()            # ties everywhere, and landmarks that look alike
+    p = ac.pair_scene("no_points")
+    assert (p["tags"][p["src"][0]:p["src"][1]] == -1).any() and (p["tags"][p["dst"][0]:p["dst"][1]] == -1).any()
+    lone = ac.pair_scene("lone")
+    m = mref.match(lone["desc"][lone["src"][0]:lone["src"][1]], lone["desc"], lone["ids"], *lone["dst"])
+    assert (m["dist2"] == 257).all() and (m["row2"] == -1).all()
+
+
+def kabsch(P, Q):
+    cp, cq = P.mean(0), Q.mean(0)
+    U, _, Vt = np.linalg.svd((Q - cq).T @ (P - cp))
+    D = np.diag([1, 1, np.sign(np.linalg.det(U @ Vt))])
+    R = U @ D @ Vt
+    return R, cq - R @ cp
+
+
+@pytest.mark.parametrize("n, share, H, sigma", [c for c in ac.MOTION_CASES if c[0] <= 1025])
+def test_refit_against_svd_kabsch(n, share, H, sigma):
+    """Horn's quaternion and the SVD solve the same least-squares problem.  Both are backward stable and the problem is well
+    conditioned (points spread over +-30 m, the largest eigenvalue far from the next), so R agrees to a few units of 2^-52 and t,
+    which multiplies R's error by a centroid of up to 70 m, to a hundred times that."""
+    case, want = ac.motion_scene(n, share, sigma), ac.motion_reference(n, share, H, sigma)
+    assert want["success"] and want["refit_rounds_run"] >= 1
+    inl = want["inlier"].astype(bool)
+    P, Q = case["xyz"][want["pair_src"]][inl].astype(np.float64), case["xyz"][want["pair_dst"]][inl].astype(np.float64)
+    R, t = kabsch(P, Q)
+    print(n, "R", np.abs(R - want["R"]).max(), "t", np.abs(t - want["t"]).max())
+    assert np.abs(R - want["R"]).max() < 1e-14 and np.abs(t - want["t"]).max() < 1e-12
+    assert abs(np.linalg.det(want["R"]) - 1) < 1e-14
+
+
+@pytest.mark.parametrize("n, share, H, sigma", ac.MOTION_CASES)
+def test_reference_ends_with_the_true_inlier_set(n, share, H, sigma):
+    """the condition the GPU tests rest on: every scene ends with exactly the true inliers, and no residual of the final model lies
+    within 10 % of inlier_dist of the threshold"""
+    case, want = ac.motion_scene(n, share, sigma), ac.motion_reference(n, share, H, sigma)
+    print(n, share, H, sigma, {k: want[k] for k in ("n_pairs", "n_inliers", "best_hypothesis", "best_count", "refit_rounds_run", "rms", "margin", "margin_final")})
+    assert want["n_pairs"] == n and want["success"] and want["margin_final"] > 0.1
+    assert np.array_equal(want["pair_src"], np.arange(n, 2 * n))
+    assert np.array_equal(want["inlier"].astype(bool), ~case["outlier"])
+    assert np.abs(want["t"] - case["t"]).max() < 0.02 and aref.rotation_angle(want["R"], case["R"]) < 1e-3
+    if sigma == 0:
+        assert want["margin"] > 1e-6                  # the noise-free scenes are the ones whose best hypothesis is asserted on the GPU
+
+
+def test_sampler_definition():
+    for n in (3, 4, 5, 63, 64, 65, 1000, 4096):
+        for h in (0, 1, 7, 255, 1023, 2 ** 32 - 1):
+            s = aref.sample(h, n)
+            assert len(set(s)) == 3 and all(0 <= v < n for v in s)
+    assert aref.sample(5, 3, max_draws=0) == [0, 1, 2]                     # the fallback alone
+    first = (aref.mix64(5 << 32) >> 32) % 3
+    assert aref.sample(5, 3, max_draws=1) == [first] + [v for v in range(3) if v != first]
+    # splitmix64's first outputs from state 0 are its finaliser at 0 and at the increment: published values
+    assert aref.mix64(0) == 0xE220A8397B1DCDAF and aref.mix64(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
+    most3 = max(aref.sample(h, 3, with_draws=True)[1] for h in range(8))
+    most63 = max(aref.sample(h, n, with_draws=True)[1] for h in range(1024) for n in (63, 64, 65, 1024, 4096))
+    print("draws: n_pairs 3, 8 hypotheses:", most3, " n_pairs >= 63, 1024 hypotheses:", most63)
+    assert most3 == 13 and most63 <= 5              # as counted when the generator was chosen
+
+
+def test_sampler_equals_the_library():
+    from stereo_visual_odometry_amd import _lib
+    out = (C.c_int32 * 3)()
+    for n in list(range(3, 12)) + [63, 64, 65, 257, 1000, 4095, 4096, 2 ** 31 - 1]:
+        for h in list(range(8)) + [255, 1023, 65535, 2 ** 31, 2 ** 32 - 1]:
+            assert _lib.lib.svo_align_sample(h, n, out) == 0
+            assert list(out) == aref.sample(h, n), (h, n)
+    assert _lib.lib.svo_align_sample(0, 2, out) == _lib.SVO_ERR_ARG and _lib.lib.svo_align_sample(0, 3, None) == _lib.SVO_ERR_ARG
+
+
+def test_params_default():
+    from stereo_visual_odometry_amd import _lib, api
+    p = api.DescriptorIndex.align_params((5, 9), (0, 5), 0.25, hypotheses=64)
+    r = api.DescriptorIndex.reloc_params()
+    assert (p.src_lo, p.src_hi, p.dst_lo, p.dst_hi) == (5, 9, 0, 5) and p.inlier_dist == 0.25 and p.reserved == 0
+    assert (p.max_dist, p.ratio_num, p.ratio_den) == (r.max_dist, r.ratio_num, r.ratio_den) == (40, 7, 10)
+    assert (p.min_pairs, p.hypotheses, p.refit_rounds) == (6, 64, 4)
+    q = _lib.SvoAlignParams()
+    _lib.lib.svo_align_params_default(C.byref(q), 1.5)
+    assert (q.src_lo, q.src_hi, q.dst_lo, q.dst_hi, q.hypotheses, q.inlier_dist) == (0, -1, 0, -1, 256, 1.5)
+    assert C.sizeof(_lib.SvoAlignParams) == 48 and C.sizeof(_lib.SvoAlignResult) == 256
