@@ -872,6 +872,91 @@ int svo_desc_index_pair_rows(svo_desc_index* index, const svo_align_params* para
 int svo_desc_index_align(svo_desc_index* index, const svo_align_params* params, svo_align_result* result, int32_t* pair_src,
                          int32_t* pair_dst, uint8_t* pair_inlier);
 
+/* ---- Landmark fusion: one id per landmark after a map merge or loop closure ---------------------------------------------------------
+ * After svo_desc_index_align and svo_desc_index_transform_points have laid a second sequence's landmarks, or a loop's recent ones, on
+ * top of the first, every landmark of the overlap exists under two ids with near-identical descriptors and near-identical points.  A
+ * query from that place finds one copy as `row` and the other as `row2` with dist2 ~ dist, rule 1 of "Relocalisation" rejects it, the
+ * guided search does not help (both copies project to one pixel), and SVO_RETIRE_LATEST_PER_ID cannot thin the copies, because it
+ * keys on the id.  svo_desc_index_fuse gives the two copies ONE id (what ORB-SLAM's SearchAndFuse does): it searches the descriptors
+ * of a SOURCE span S = [src_lo, src_hi) in a DESTINATION span D = [dst_lo, dst_hi) among the rows whose POINT lies near the source
+ * row's, pairs rows up, and renames the source landmarks' ids to their partners' in a RELABEL span L = [relabel_lo, relabel_hi) (the
+ * whole index by default), all on the device: no descriptor, point or id leaves it, one host synchronisation.  No point is averaged
+ * or snapped: each row keeps its own triangulation.
+ *
+ * The three spans follow the row_hi = -1 convention.  S has n = src_hi - src_lo <= SVO_FUSE_MAX_ROWS rows; S and D share no row
+ * (spans that touch are legal; an empty span shares nothing); L is any span.  Every rule is defined on integers and f32 compares.
+ * tag[r], id[r], (x_r, y_r, z_r): row r's.
+ *  1. Gate.  Row r of D is ADMISSIBLE for the source row s when tag[r] != SVO_POINT_NONE, tag[s] != SVO_POINT_NONE, and
+ *     |x_r - x_s| <= radius, |y_r - y_s| <= radius and |z_r - z_s| <= radius; the subtractions, absolute values and comparisons are
+ *     f32 and every limit is inclusive: a cube of side 2 x radius in the map's unit, the 3-D counterpart of rule 2 of "Guided
+ *     search".  A source row without a point admits nothing.
+ *  2. Search.  For j = 0 .. n - 1, m_j is svo_desc_index_match's definition for the query "descriptor of row src_lo + j" over the
+ *     admissible rows of D only: best by (dist, row), second = the best admissible row of another id than the best row's.  Nothing
+ *     admissible: SVO_MATCH_NONE and SVO_MATCH_NO_DIST, as for an empty range.  The result does not depend on the chunk size.
+ *  3. Accept, one source row per destination landmark, one destination per source landmark, pairs: rules 2 - 5 of "Map alignment"
+ *     unchanged on those m_j, the orderings by (m_j.dist, j) included.  Pair c, in increasing j, is (src row src_lo + j, dst row
+ *     m_j.row).  There is no min_pairs gate: zero pairs is a success that changes nothing.
+ *  4. Map.  from_c = id[pair_src[c]] and to_c = id[pair_dst[c]], both read before anything is written.  A pair with from_c == to_c is
+ *     counted in n_same and maps nothing; the others are counted in n_fused.  By rule 3 the from_c are distinct.
+ *  5. Relabel.  Every row r of L with id[r] == from_c for a mapping pair c gets id[r] = to_c: one simultaneous step on the ids as they
+ *     were.  With a -> b and b -> c in one call, a's rows become b and b's rows become c; no chain is followed.  Descriptors, points,
+ *     tags, the order of the rows and the size are untouched.  n_rows_relabelled counts the rows whose id changed.
+ *  6. Refusals.  A refused call changes nothing, its outputs included.  SVO_ERR_STATE: an index without points (match_near, pair_near
+ *     and fuse; not relabel).  SVO_ERR_ARG: a span svo_desc_index_match refuses as a row range; n > 4096; S and D sharing a row;
+ *     radius negative or not finite; and, for pair_near and fuse, max_dist outside 0 .. 256 or a ratio term outside 1 .. 1 << 20.
+ * A later call that meets a landmark already fused finds its own id on the other side and counts it in n_same, so a large overlap is
+ * fused span after span (one keyframe of at most 4096 rows a call), and a repeated call changes nothing.
+ *
+ * svo_desc_index_relabel is rule 5 alone on host lists, for a back end that fused landmarks itself: entry i maps from_ids[i] to
+ * to_ids[i].  An entry with from == to is ignored, as if it were not in the list; where a `from` value occurs in more than one of the
+ * remaining entries, the one at the smallest list position wins.  It needs no points.  SVO_ERR_ARG: n outside 0 .. SVO_FUSE_MAX_LIST,
+ * a NULL list with n > 0, a bad row range.
+ *
+ * Every call is synchronous, waits for the index's own stream only and is legal with frames in flight; match_near, pair_near and fuse
+ * synchronise once, and so does relabel after its lists have gone up (through the index's pinned staging, in pieces of 20 480
+ * entries, as svo_desc_index_retire's ids do).  With svo_desc_index_set_timing on, last_kernels_ms (svo_desc_index_get_stats) is the
+ * device span from the first kernel the call launches to the last.
+ *
+ * Memory.  The search's n result rows go where svo_desc_index_match's go, its partial states into the search's scratch, and the
+ * pairs into "Map alignment"'s device block (237 824 bytes, allocated at the first call that pairs).  The map and the table live in
+ * the maintenance scratch of "Index maintenance" (the same buffer, the same growth rule): with e the entries of the list — n for
+ * pair_near and fuse, the list's length for relabel — R(b) = b rounded up to a multiple of 256 and slots(e) the smallest power of two
+ * >= max(2, 2 e), a call needs
+ *   need = 8 448 + 2 R(8 e) + R(4 slots(e))
+ * bytes: what the kernels report (64 bytes and 128 cache lines of row counts), the `from` and the `to` list, and the table of list
+ * positions.  e = 4096: 106 752 bytes; e = 1 << 20: 24 MiB + 8 448.  An 8 256-byte pinned block receives the counts. */
+#define SVO_FUSE_MAX_ROWS 4096
+#define SVO_FUSE_MAX_LIST (1 << 20)
+typedef struct {
+    int32_t src_lo, src_hi;          /* S: the rows whose landmarks are renamed; at most SVO_FUSE_MAX_ROWS */
+    int32_t dst_lo, dst_hi;          /* D: the rows searched */
+    int32_t relabel_lo, relabel_hi;  /* L: the rows whose ids may change */
+    int32_t max_dist;                /* rule 3: 0 .. 256 */
+    int32_t ratio_num, ratio_den;    /* rule 3: 1 .. 1 << 20 each */
+    float   radius;                  /* rule 1, in the map's unit: finite, >= 0 */
+    int32_t reserved;                /* 0 */
+} svo_fuse_params;
+typedef struct {
+    int32_t n_pairs;                 /* rule 3 */
+    int32_t n_same, n_fused;         /* rule 4: n_same + n_fused == n_pairs */
+    int32_t n_rows_relabelled;       /* rule 5 */
+} svo_fuse_result;
+/* max_dist = 40, ratio 7 / 10 (svo_reloc_params_default's), src = dst = relabel = {0, -1} (the caller sets S and D).  radius is an
+ * argument for the reason svo_align_params_default's inlier_dist is one: how far two triangulations of one landmark lie apart
+ * depends on the baseline, the depth and the alignment's residual, no value in metres has been measured for any stereo rig, and
+ * this header does not invent one. */
+void svo_fuse_params_default(svo_fuse_params* params, float radius);
+/* Rules 1 - 2: out (host) receives n result rows. */
+int svo_desc_index_match_near(svo_desc_index* index, int src_lo, int src_hi, int dst_lo, int dst_hi, float radius, svo_desc_match* out);
+/* Rules 1 - 3, the dry run: *n_pairs and, where non-NULL, the pairs' source and destination rows, each with room for n entries.
+ * Every parameter is checked as svo_desc_index_fuse checks it; the relabel span plays no other part. */
+int svo_desc_index_pair_near(svo_desc_index* index, const svo_fuse_params* params, int* n_pairs, int32_t* pair_src, int32_t* pair_dst);
+/* Rule 5 alone.  from_ids, to_ids: n entries each, host memory; row_hi = -1: the index's size; *n_rows_relabelled may be NULL. */
+int svo_desc_index_relabel(svo_desc_index* index, int n, const uint64_t* from_ids, const uint64_t* to_ids, int row_lo, int row_hi,
+                           int* n_rows_relabelled);
+/* All of it.  pair_src, pair_dst: n entries each, each may be NULL; the first result->n_pairs are written.  result may be NULL. */
+int svo_desc_index_fuse(svo_desc_index* index, const svo_fuse_params* params, svo_fuse_result* result, int32_t* pair_src, int32_t* pair_dst);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the

@@ -687,6 +687,42 @@ class DescriptorIndex {
         if (pairs) *pairs = std::move(p);
         return r;
     }
+    // ---- landmark fusion (svo.h, "Landmark fusion"): one id per landmark where two spans of rows overlap, on the device
+    // svo_fuse_params_default; the caller sets the spans.  radius (the map's unit) has no default: none has been measured for any rig
+    static svo_fuse_params fuse_params(float radius) { svo_fuse_params p; svo_fuse_params_default(&p, radius); return p; }
+    // match_rows among the rows of dst whose point lies within radius of the source row's on every axis
+    std::vector<svo_desc_match> match_near(std::pair<int, int> src, std::pair<int, int> dst, float radius) {
+        std::vector<svo_desc_match> out(span_rows(src.first, src.second));
+        svo_throw(svo_desc_index_match_near(index_, src.first, src.second, dst.first, dst.second, radius, out.data()));
+        return out;
+    }
+    // rules 1 - 3, the dry run of fuse: one pair of rows per landmark on either side, in increasing source row
+    Pairs pair_near(const svo_fuse_params& prm) {
+        const size_t n = span_rows(prm.src_lo, prm.src_hi);
+        Pairs p; p.src.resize(n); p.dst.resize(n);
+        int k = 0;
+        svo_throw(svo_desc_index_pair_near(index_, &prm, &k, p.src.data(), p.dst.data()));
+        p.src.resize((size_t)k); p.dst.resize((size_t)k);
+        return p;
+    }
+    // every row of [rows.first, rows.second) whose id is from_ids[i] gets to_ids[i], in one simultaneous step -> the rows changed
+    int relabel(const std::vector<uint64_t>& from_ids, const std::vector<uint64_t>& to_ids, std::pair<int, int> rows = {0, -1}) {
+        if (from_ids.size() != to_ids.size()) throw std::runtime_error("DescriptorIndex::relabel: one `to` id per `from` id expected");
+        if (from_ids.size() > (size_t)SVO_FUSE_MAX_LIST) throw std::runtime_error("DescriptorIndex::relabel: at most 1 << 20 entries");
+        int changed = 0;
+        svo_throw(svo_desc_index_relabel(index_, (int)from_ids.size(), from_ids.data(), to_ids.data(), rows.first, rows.second, &changed));
+        return changed;
+    }
+    // the source span's landmarks take the ids of their partners in the destination span, in the rows of the relabel span
+    svo_fuse_result fuse(const svo_fuse_params& prm, Pairs* pairs = nullptr) {
+        const size_t n = span_rows(prm.src_lo, prm.src_hi);
+        Pairs p; p.src.resize(n); p.dst.resize(n);
+        svo_fuse_result r;
+        svo_throw(svo_desc_index_fuse(index_, &prm, &r, p.src.data(), p.dst.data()));
+        p.src.resize((size_t)r.n_pairs); p.dst.resize((size_t)r.n_pairs);
+        if (pairs) *pairs = std::move(p);
+        return r;
+    }
     int retire_slab_rows() const { return svo_desc_index_get_retire_slab_rows(index_); }
     void retire_slab_rows(int rows) { svo_throw(svo_desc_index_set_retire_slab_rows(index_, rows)); }   // 0: the default
     int size() const { return svo_desc_index_size(index_); }

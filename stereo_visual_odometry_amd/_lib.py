@@ -134,6 +134,15 @@ class SvoAlignResult(C.Structure):
                [("R", C.c_double * 9), ("t", C.c_double * 3), ("T", C.c_double * 16), ("rms", C.c_double)]
 
 
+class SvoFuseParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("src_lo", "src_hi", "dst_lo", "dst_hi", "relabel_lo", "relabel_hi", "max_dist", "ratio_num",
+                                         "ratio_den")] + [("radius", C.c_float), ("reserved", C.c_int32)]
+
+
+class SvoFuseResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_pairs", "n_same", "n_fused", "n_rows_relabelled")]
+
+
 class SvoRetireRule(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("row_lo", C.c_int32), ("row_hi", C.c_int32), ("tag_lo", C.c_int32), ("tag_hi", C.c_int32),
                 ("n_ids", C.c_int32), ("ids", C.c_void_p)]
@@ -215,6 +224,11 @@ PROTOTYPES = {
     "svo_desc_index_match_rows": (I, (P, I, I, I, I, P)),
     "svo_desc_index_pair_rows": (I, (P, P, P, P, P)),
     "svo_desc_index_align": (I, (P, P, P, P, P, P)),
+    "svo_fuse_params_default": (None, (P, F)),
+    "svo_desc_index_match_near": (I, (P, I, I, I, I, F, P)),
+    "svo_desc_index_pair_near": (I, (P, P, P, P, P)),
+    "svo_desc_index_relabel": (I, (P, I, P, P, I, I, P)),
+    "svo_desc_index_fuse": (I, (P, P, P, P, P)),
     "svo_set_detection_mask": (I, (P, I, P, I, I)),
     "svo_get_detection_mask": (I, (P, I, P, P)),
     "svo_set_motion_prior": (I, (P, I, P, P)),

@@ -369,6 +369,7 @@ def descriptor_pattern():
 
 RelocResult = collections.namedtuple("RelocResult", "success n_candidates n_inliers iters_run R t T")
 AlignResult = collections.namedtuple("AlignResult", "success n_pairs n_inliers best_hypothesis best_count refit_rounds_run R t T rms")
+FuseResult = collections.namedtuple("FuseResult", "n_pairs n_same n_fused n_rows_relabelled")
 
 
 class DescriptorIndex:
@@ -730,6 +731,57 @@ class DescriptorIndex:
         res = AlignResult(bool(r.success), k, r.n_inliers, r.best_hypothesis, r.best_count, r.refit_rounds_run,
                           np.array(r.R, np.float64).reshape(3, 3), np.array(r.t, np.float64), np.array(r.T, np.float64).reshape(4, 4), r.rms)
         return res, {"src": ps[:k].copy(), "dst": pd[:k].copy(), "inlier": pi[:k].copy()}
+
+    # ---- landmark fusion (svo.h, "Landmark fusion"): one id per landmark where two spans of rows overlap, on the device
+    @staticmethod
+    def fuse_params(src, dst, radius, relabel=(0, -1), **over):
+        """svo_fuse_params_default with the spans src, dst, relabel = (lo, hi) and fields replaced: max_dist, ratio_num, ratio_den.
+        radius (the map's unit) has no default: none has been measured for any rig."""
+        p = _lib.SvoFuseParams()
+        lib.svo_fuse_params_default(C.byref(p), float(radius))
+        p.src_lo, p.src_hi, p.dst_lo, p.dst_hi = int(src[0]), int(src[1]), int(dst[0]), int(dst[1])
+        p.relabel_lo, p.relabel_hi = int(relabel[0]), int(relabel[1])
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise AttributeError("svo_fuse_params has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+    def match_near(self, src, dst, radius):
+        """match_rows among the rows of dst whose point lies within radius of the source row's on every axis
+        (svo_desc_index_match_near) -> match's structured array, one row per source row."""
+        out = np.zeros(self._span_rows(src), _lib.DESC_MATCH_DTYPE)
+        check(lib.svo_desc_index_match_near(self._h, int(src[0]), int(src[1]), int(dst[0]), int(dst[1]), float(radius), ptr(out)))
+        return out
+
+    def pair_near(self, src, dst, radius, params=None, **over):
+        """Rules 1 - 3 of "Landmark fusion", the dry run of fuse (svo_desc_index_pair_near) -> (pair_src, pair_dst) int32 row numbers."""
+        p = params if params is not None else self.fuse_params(src, dst, radius, **over)
+        n = self._span_rows((p.src_lo, p.src_hi))
+        ps, pd, k = np.zeros(n, np.int32), np.zeros(n, np.int32), C.c_int(0)
+        check(lib.svo_desc_index_pair_near(self._h, C.byref(p), C.byref(k), ptr(ps), ptr(pd)))
+        return ps[:k.value].copy(), pd[:k.value].copy()
+
+    def relabel(self, from_ids, to_ids, rows=(0, -1)):
+        """Every row of rows = (row_lo, row_hi) whose id is from_ids[i] gets the id to_ids[i], in one simultaneous step
+        (svo_desc_index_relabel); entries with from == to are ignored, of a repeated `from` the first entry wins -> the rows changed."""
+        f = np.ascontiguousarray(from_ids).astype(np.uint64, copy=False).reshape(-1)
+        t = np.ascontiguousarray(to_ids).astype(np.uint64, copy=False).reshape(-1)
+        if len(f) != len(t):
+            raise ValueError("one `to` id per `from` id expected")
+        k = C.c_int(0)
+        check(lib.svo_desc_index_relabel(self._h, len(f), ptr(f) if len(f) else None, ptr(t) if len(t) else None, int(rows[0]), int(rows[1]), C.byref(k)))
+        return k.value
+
+    def fuse(self, src, dst, radius, relabel=(0, -1), params=None, **over):
+        """Give the landmarks of the rows src the ids of their partners in the rows dst, in the rows of relabel (svo_desc_index_fuse)
+        -> (FuseResult, pairs): pairs is a dict of src and dst row numbers per pair."""
+        p = params if params is not None else self.fuse_params(src, dst, radius, relabel, **over)
+        n = self._span_rows((p.src_lo, p.src_hi))
+        ps, pd = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        r = _lib.SvoFuseResult()
+        check(lib.svo_desc_index_fuse(self._h, C.byref(p), C.byref(r), ptr(ps), ptr(pd)))
+        return FuseResult(r.n_pairs, r.n_same, r.n_fused, r.n_rows_relabelled), {"src": ps[:r.n_pairs].copy(), "dst": pd[:r.n_pairs].copy()}
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -22,10 +22,15 @@
 // The alignment (include/svo.h, "Map alignment"; the kernels are in svo_kernels_align.hip, the rules in svo_align.hpp): align_run,
 // behind match_rows, pair_rows and align, is the same search with the index's own rows as its queries — nothing is staged — then
 // k_align_pairs, k_align_score and k_align_fit, one copy back and one wait.
+//
+// The fusion (include/svo.h, "Landmark fusion"; the kernels are in svo_kernels_fuse.hip, the rules in svo_fuse.hpp): fuse_run, behind
+// match_near, pair_near and fuse, is k_desc_match_near and the merge over the unguided plan, then k_align_pairs, k_fuse_map,
+// k_fuse_insert and k_fuse_sweep, two copies back and one wait.  relabel puts its host lists where k_fuse_map would and runs the last two.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
 #include "svo_reloc_batch_internal.hpp"
 #include "svo_align_internal.hpp"
+#include "svo_fuse_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -101,6 +106,8 @@ struct svo_desc_index {
     // map alignment: null until the first svo_desc_index_pair_rows or svo_desc_index_align (align_room)
     uint8_t* d_align = nullptr;                       // align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES)
     uint8_t* h_align = nullptr;                       // pinned: its first down_end bytes
+    // landmark fusion: null until the first pair_near, relabel or fuse (fuse_ctl_room); the lists and the table live in d_retire
+    FuseCtl* h_fuse = nullptr;                        // pinned: what a call reads back
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -127,7 +134,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         for (svo_context* c : x->batch_ctx_outgrown) svo_destroy(c);
         svo_destroy(x->batch_ctx);
         (void)hipFree(x->d_batch); (void)hipHostFree(x->h_batch); (void)hipHostFree(x->h_batch_st);
-        (void)hipFree(x->d_align); (void)hipHostFree(x->h_align);
+        (void)hipFree(x->d_align); (void)hipHostFree(x->h_align); (void)hipHostFree(x->h_fuse);
         (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
         (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
@@ -1073,5 +1080,178 @@ extern "C" int svo_desc_index_transform_points(svo_desc_index* x, const double T
     }
     if (n_moved) *n_moved = moved;
     if (n_skipped) *n_skipped = skipped;
+    return SVO_OK;
+}
+
+// ---- landmark fusion (include/svo.h, "Landmark fusion"; the kernels are in svo_kernels_fuse.hip, the rules in svo_fuse.hpp) ----
+extern "C" void svo_fuse_params_default(svo_fuse_params* p, float radius) {
+    if (!p) return;
+    svo_reloc_params r; svo_reloc_params_default(&r);
+    p->src_lo = 0; p->src_hi = -1; p->dst_lo = 0; p->dst_hi = -1; p->relabel_lo = 0; p->relabel_hi = -1;
+    p->max_dist = r.max_dist; p->ratio_num = r.ratio_num; p->ratio_den = r.ratio_den;
+    p->radius = radius; p->reserved = 0;
+}
+
+static const char* fuse_refusal_text(FuseRefusal e) {
+    switch (e) {
+    case FUSE_SRC_RANGE: return "landmark fusion: the source span must satisfy 0 <= src_lo <= src_hi <= size";
+    case FUSE_DST_RANGE: return "landmark fusion: the destination span must satisfy 0 <= dst_lo <= dst_hi <= size";
+    case FUSE_RELABEL_RANGE: return "landmark fusion: the relabel span must satisfy 0 <= relabel_lo <= relabel_hi <= size";
+    case FUSE_ROWS: return "landmark fusion: at most 4096 source rows per call";
+    case FUSE_OVERLAP: return "landmark fusion: the source and the destination span share a row";
+    case FUSE_RADIUS: return "landmark fusion: the radius must be finite and >= 0";
+    case FUSE_MAX_DIST: return "landmark fusion: max_dist must be 0 .. 256";
+    default: return "landmark fusion: ratio_num and ratio_den must be 1 .. 1 << 20";
+    }
+}
+
+static int fuse_ctl_room(svo_desc_index* x) {
+    if (x->h_fuse) return SVO_OK;
+    MHIP(hipHostMalloc((void**)&x->h_fuse, sizeof(FuseCtl), hipHostMallocDefault));
+    return SVO_OK;
+}
+
+// one list of a relabel call onto the device through the pinned staging, piece by piece (retire_upload_ids' way)
+static int fuse_upload_list(svo_desc_index* x, const uint64_t* src, size_t n, uint64_t* d_dst) {
+    const size_t piece = RETIRE_STAGE_BYTES / sizeof(uint64_t);
+    for (size_t i0 = 0; i0 < n; i0 += piece) {
+        const size_t m = n - i0 < piece ? n - i0 : piece;
+        memcpy(x->h_stage, src + i0, m * sizeof(uint64_t));
+        MHIP(hipMemcpyAsync(d_dst + i0, x->h_stage, m * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));        // the staging is free again
+    }
+    return SVO_OK;
+}
+
+// the counts of a call as the host reads them after its wait; the table's flag cannot be raised at load <= 1/2
+static int fuse_counts(const FuseCtl& c, int* n_rows) {
+    if (c.table_full) return fail(SVO_ERR_INTERNAL, "landmark fusion: the table overflowed");
+    int rows = 0;
+    for (const FuseCount& k : c.counts) rows += k.n_rows_relabelled;
+    *n_rows = rows;
+    return SVO_OK;
+}
+
+// What match_near (stage 1), pair_near (2) and fuse (3) share.  q: the request, checked and with its spans resolved.  Everything is
+// enqueued on the index's stream — the gated search with rows [src_lo, src_hi) of the index as its queries, in launches of the
+// unguided plan's size, the pair kernel, the map, the table and the sweep, the copies back — and the host waits once.
+// times: from the first kernel to the last
+static int fuse_run(svo_desc_index* x, const FuseRequest& q, int stage, svo_desc_match* rows, int* n_pairs, svo_fuse_result* res,
+                    int32_t* pair_src, int32_t* pair_dst) {
+    const int n = q.src_hi - q.src_lo;
+    int rc;
+    MHIP(call_begin(x));
+    SearchPlan plan;
+    const FuseLayout fl = fuse_layout(n);
+    if ((stage > 1 && (rc = align_room(x)) != SVO_OK) || (stage > 2 && ((rc = fuse_ctl_room(x)) != SVO_OK || (rc = retire_room(x, fl.total)) != SVO_OK)) ||
+        (rc = search_plan(x, n, q.dst_lo, q.dst_hi, nullptr, &plan)) != SVO_OK) return rc;
+    FuseCtl* ctl = nullptr;
+    int32_t* table = nullptr;
+    if (stage > 2) {
+        ctl = (FuseCtl*)(x->d_retire + fl.ctl); table = (int32_t*)(x->d_retire + fl.table);
+        MHIP(hipMemsetAsync(ctl, 0, sizeof(FuseCtl), x->stream));
+        MHIP(hipMemsetAsync(table, 0xFF, (size_t)fuse_table_slots(n) * sizeof(int32_t), x->stream));      // FUSE_EMPTY
+    }
+    MHIP(span_mark(x, true, 0));
+    for (int i0 = 0; i0 < n; i0 += plan.batch) {
+        const int m = n - i0 < plan.batch ? n - i0 : plan.batch;
+        launch_desc_match_near((const uint32_t*)x->d_desc, x->d_ids, x->d_points, q.src_lo + i0, m, q.radius, plan.r, x->d_part, x->stream);
+        launch_desc_match_merge(x->d_part, x->d_ids, m, plan.r, x->d_out + i0, x->stream);
+    }
+    if (stage == 1) {
+        MHIP(hipGetLastError());
+        MHIP(span_mark(x, true, 1));
+        if (n > 0) MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        MHIP(span_read(x));
+        if (n > 0) memcpy(rows, x->h_out, (size_t)n * sizeof(svo_desc_match));
+        return SVO_OK;
+    }
+    const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
+    uint8_t *dv = x->d_align, *h = x->h_align;
+    AlignOut* d_res = (AlignOut*)(dv + l.out);
+    int32_t *d_src = (int32_t*)(dv + l.pair_src), *d_dst = (int32_t*)(dv + l.pair_dst);
+    const AlignPairsArgs pa{x->d_out, x->d_points, x->d_ids, q.src_lo, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den},
+                            d_src, d_dst, dv + l.pair_inlier, (float*)(dv + l.pairs), d_res};
+    launch_align_pairs(pa, x->stream);
+    if (stage == 3) {
+        uint64_t *from = (uint64_t*)(x->d_retire + fl.from), *to = (uint64_t*)(x->d_retire + fl.to);
+        launch_fuse_map(&d_res->n_pairs, n, d_src, d_dst, x->d_ids, from, to, ctl, x->stream);
+        launch_fuse_relabel(from, to, &d_res->n_pairs, n, table, fuse_table_slots(n), x->d_ids, q.relabel_lo, q.relabel_hi, ctl, x->stream);
+    }
+    MHIP(hipGetLastError());
+    MHIP(span_mark(x, true, 1));
+    MHIP(hipMemcpyAsync(h, dv, l.pair_inlier, hipMemcpyDeviceToHost, x->stream));          // the result row and the two row lists
+    if (stage == 3) MHIP(hipMemcpyAsync(x->h_fuse, ctl, sizeof(FuseCtl), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
+    MHIP(span_read(x));
+    const int np = ((const AlignOut*)(h + l.out))->n_pairs;
+    int n_rows = 0;
+    if (stage == 3 && (rc = fuse_counts(*x->h_fuse, &n_rows)) != SVO_OK) return rc;
+    if (n_pairs) *n_pairs = np;
+    if (pair_src) memcpy(pair_src, h + l.pair_src, (size_t)np * sizeof(int32_t));
+    if (pair_dst) memcpy(pair_dst, h + l.pair_dst, (size_t)np * sizeof(int32_t));
+    if (res) { res->n_pairs = np; res->n_same = x->h_fuse->n_same; res->n_fused = x->h_fuse->n_fused; res->n_rows_relabelled = n_rows; }
+    return SVO_OK;
+}
+
+static FuseRequest fuse_request(const svo_fuse_params* p) {
+    return FuseRequest{p->src_lo, p->src_hi, p->dst_lo, p->dst_hi, p->relabel_lo, p->relabel_hi, p->max_dist, p->ratio_num, p->ratio_den, p->radius};
+}
+
+extern "C" int svo_desc_index_match_near(svo_desc_index* x, int src_lo, int src_hi, int dst_lo, int dst_hi, float radius, svo_desc_match* out) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "landmark fusion: the index has no points (svo_desc_index_enable_points)");
+    FuseRequest q{src_lo, src_hi, dst_lo, dst_hi, 0, -1, 0, 1, 1, radius};
+    if (const FuseRefusal e = fuse_check_search(q, x->size); e != FUSE_OK) return fail(SVO_ERR_ARG, fuse_refusal_text(e));
+    if (q.src_hi > q.src_lo && !out) return fail(SVO_ERR_ARG, "svo_desc_index_match_near: null out");
+    return fuse_run(x, q, 1, out, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int svo_desc_index_pair_near(svo_desc_index* x, const svo_fuse_params* p, int* n_pairs, int32_t* pair_src, int32_t* pair_dst) {
+    if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_pair_near: null index / params");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "landmark fusion: the index has no points (svo_desc_index_enable_points)");
+    FuseRequest q = fuse_request(p);
+    if (const FuseRefusal e = fuse_check(q, x->size); e != FUSE_OK) return fail(SVO_ERR_ARG, fuse_refusal_text(e));
+    return fuse_run(x, q, 2, nullptr, n_pairs, nullptr, pair_src, pair_dst);
+}
+
+extern "C" int svo_desc_index_fuse(svo_desc_index* x, const svo_fuse_params* p, svo_fuse_result* res, int32_t* pair_src, int32_t* pair_dst) {
+    if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_fuse: null index / params");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "landmark fusion: the index has no points (svo_desc_index_enable_points)");
+    FuseRequest q = fuse_request(p);
+    if (const FuseRefusal e = fuse_check(q, x->size); e != FUSE_OK) return fail(SVO_ERR_ARG, fuse_refusal_text(e));
+    return fuse_run(x, q, 3, nullptr, nullptr, res, pair_src, pair_dst);
+}
+
+// times: the insert and the sweep
+extern "C" int svo_desc_index_relabel(svo_desc_index* x, int n, const uint64_t* from_ids, const uint64_t* to_ids, int row_lo, int row_hi,
+                                      int* n_rows_relabelled) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (n < 0 || n > FUSE_MAX_LIST) return fail(SVO_ERR_ARG, "svo_desc_index_relabel: n must be 0 .. 1 << 20");
+    if (n > 0 && (!from_ids || !to_ids)) return fail(SVO_ERR_ARG, "svo_desc_index_relabel: null from_ids / to_ids");
+    int rc = row_range(x, row_lo, row_hi);
+    if (rc != SVO_OK) return rc;
+    MHIP(call_begin(x));
+    int n_rows = 0;
+    if (n > 0 && row_hi > row_lo) {
+        const FuseLayout fl = fuse_layout(n);
+        if ((rc = fuse_ctl_room(x)) != SVO_OK || (rc = retire_room(x, fl.total)) != SVO_OK) return rc;
+        FuseCtl* ctl = (FuseCtl*)(x->d_retire + fl.ctl);
+        uint64_t *from = (uint64_t*)(x->d_retire + fl.from), *to = (uint64_t*)(x->d_retire + fl.to);
+        int32_t* table = (int32_t*)(x->d_retire + fl.table);
+        if ((rc = fuse_upload_list(x, from_ids, (size_t)n, from)) != SVO_OK || (rc = fuse_upload_list(x, to_ids, (size_t)n, to)) != SVO_OK) return rc;
+        MHIP(hipMemsetAsync(ctl, 0, sizeof(FuseCtl), x->stream));
+        MHIP(hipMemsetAsync(table, 0xFF, (size_t)fuse_table_slots(n) * sizeof(int32_t), x->stream));      // FUSE_EMPTY
+        MHIP(span_mark(x, true, 0));
+        launch_fuse_relabel(from, to, nullptr, n, table, fuse_table_slots(n), x->d_ids, row_lo, row_hi, ctl, x->stream);
+        MHIP(hipGetLastError());
+        MHIP(span_mark(x, true, 1));
+        MHIP(hipMemcpyAsync(x->h_fuse, ctl, sizeof(FuseCtl), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        MHIP(span_read(x));
+        if ((rc = fuse_counts(*x->h_fuse, &n_rows)) != SVO_OK) return rc;
+    }
+    if (n_rows_relabelled) *n_rows_relabelled = n_rows;
     return SVO_OK;
 }
