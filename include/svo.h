@@ -535,7 +535,9 @@ int svo_desc_index_get_chunk_rows(const svo_desc_index* index);
  * often the scratch was allocated, its size, and the bytes of the buffers it has outgrown.  After svo_desc_index_select or
  * svo_desc_index_localize with timing on, last_kernels_ms is the device time of the selection kernel alone.  After a guided call
  * ("Guided search") with timing on it is the device time of the projection kernel plus the guided search kernels (after
- * svo_desc_index_project: the projection kernel alone). */
+ * svo_desc_index_project: the projection kernel alone).  After svo_desc_index_tag_votes, svo_desc_index_places or
+ * svo_desc_index_places_from_ids ("Place candidates") with timing on it is the device span of the new kernels alone — the clearing
+ * of the bins, the sweep and, for the two places calls, the compaction and the pick — not the search and the selection in front. */
 typedef struct {
     float    last_kernels_ms;
     int32_t  scratch_allocations;
@@ -956,6 +958,84 @@ int svo_desc_index_relabel(svo_desc_index* index, int n, const uint64_t* from_id
                            int* n_rows_relabelled);
 /* All of it.  pair_src, pair_dst: n entries each, each may be NULL; the first result->n_pairs are written.  result may be NULL. */
 int svo_desc_index_fuse(svo_desc_index* index, const svo_fuse_params* params, svo_fuse_result* result, int32_t* pair_src, int32_t* pair_dst);
+
+/* ---- Place candidates: which keyframes of the map a frame resembles ------------------------------------------------------------------
+ * svo_desc_index_localize, svo_desc_index_align and svo_desc_index_fuse take the row span of a keyframe; these calls find it (what
+ * ORB-SLAM's DetectLoopCandidates does, and with ids in place of descriptors its UpdateLocalKeyFrames).  A keyframe is a TAG: the
+ * caller tags the rows of one keyframe alike ("Relocalisation").  The score of a tag is covisibility — how many of the rows under
+ * it belong to a landmark the frame recognised — counted by a sweep over the index's ids and tags on the device: no id or tag leaves
+ * it and the caller keeps no first_row table.  Voting with svo_desc_index_match's best row alone would be the wrong vote: a landmark
+ * seen from k keyframes has k rows and the best one falls on any of them, which smears a place's votes over its neighbours.
+ *
+ * Every rule is defined on integers.  tag[r], id[r]: row r's; row_hi = -1 is the index's size.
+ *  1. Recognised landmarks.  Rules 1 - 3 of "Relocalisation" unchanged over [row_lo, row_hi) with max_dist, ratio_num, ratio_den,
+ *     without pixels (svo_desc_index_select with xy = NULL): candidate c is (cand_query[c], cand_row[c]).  M is the set of the
+ *     candidates' ids id[cand_row[c]]: at most SVO_PLACE_MAX_IDS ids, one candidate per landmark.  n_landmarks = |M|.
+ *  2. Votes.  Row r of [row_lo, row_hi) QUALIFIES when tag_lo <= tag[r] <= tag_hi; tag_lo >= 0, so a row without a point
+ *     (SVO_POINT_NONE) never does.  For the qualifying rows of tag t: rows[t] is their number, row_first[t] the smallest r,
+ *     row_end[t] the largest r + 1, votes[t] the number of them with id[r] in M.  Plain counts of rows: a landmark with two rows
+ *     under one tag counts twice.  A tag without a qualifying row has 0 in all four.  Arrays over the span are indexed t - tag_lo.
+ *     Every output is a sum, a minimum or a maximum of integers: the same bits on every run.
+ *  3. Places.  P = the tags of the span with votes[t] >= min_votes.  Up to max_places times, while P is not empty: the tag of P
+ *     with the largest votes, at equal votes the smallest tag (the older keyframe, the larger loop), is emitted as
+ *     {tag, votes, rows, row_first, row_end}, and every t with |t - tag| <= separation leaves P.  separation keeps the consecutive
+ *     keyframes of one place from filling the list.  n_tags_voted counts the tags of the span with votes[t] >= 1.
+ *  4. Refusals.  A refused call changes nothing, its outputs included.  SVO_ERR_STATE: an index without points (tags live there).
+ *     SVO_ERR_ARG: a row range svo_desc_index_match refuses; tag_lo < 0; tag_hi < tag_lo; tag_hi - tag_lo + 1 > SVO_PLACE_MAX_TAGS;
+ *     n_ids outside 0 .. SVO_PLACE_MAX_IDS or a NULL list with n_ids > 0; for the two places calls min_votes < 1, separation < 0,
+ *     max_places outside 1 .. SVO_PLACE_MAX_PLACES; for svo_desc_index_places n outside 0 .. 4096, max_dist outside 0 .. 256 and a
+ *     ratio term outside 1 .. 1 << 20.
+ * The rows of a tag need not be contiguous ([row_first, row_end) then holds other tags' rows too: after a fuse and a retire the
+ * caller decides whether the span is still the keyframe), and row_hi keeps a loop closer's most recent keyframes out of the vote.
+ *
+ * Every call is synchronous, runs in the index's own stream, is legal with frames in flight, changes nothing in the index and
+ * synchronises with the host once.  svo_desc_index_set_timing: see there.
+ *
+ * Memory.  The id list, the bins (16 bytes a tag) and rule 3's list (8 bytes a tag; not for tag_votes) live in the maintenance
+ * scratch of "Index maintenance" (the same buffer, the same growth rule): with b = tag_hi - tag_lo + 1 and R as in "Landmark
+ * fusion", need = 2 304 + R(8 n_ids) + R(16 b) + R(8 b) bytes; 4096 ids and 1 << 20 tags: 24 MiB + 35 072.  A pinned block of the
+ * same growth rule receives 2 080 bytes (places) or 2 080 + 16 b bytes (tag_votes).  A sweep block holds M in 8 n_ids + 4 slots
+ * bytes of LDS (slots as in "Landmark fusion"): 64 KiB at most. */
+#define SVO_PLACE_MAX_TAGS (1 << 20)
+#define SVO_PLACE_MAX_PLACES 64
+#define SVO_PLACE_MAX_IDS 4096
+typedef struct {
+    int32_t row_lo, row_hi;          /* the rows searched (rule 1) and swept (rule 2) */
+    int32_t max_dist;                /* rule 1: 0 .. 256 */
+    int32_t ratio_num, ratio_den;    /* rule 1: 1 .. 1 << 20 each */
+    int32_t tag_lo, tag_hi;          /* rule 2: the tags that get a bin, inclusive; at most SVO_PLACE_MAX_TAGS of them */
+    int32_t min_votes;               /* rule 3: >= 1 */
+    int32_t separation;              /* rule 3: >= 0 */
+    int32_t max_places;              /* rule 3: 1 .. SVO_PLACE_MAX_PLACES */
+} svo_place_params;
+typedef struct {
+    int32_t tag, votes, rows;        /* rule 2's counts of the tag */
+    int32_t row_first, row_end;      /* its rows lie in [row_first, row_end): the span svo_desc_index_localize, align and fuse take */
+    int32_t reserved[3];             /* 0 */
+} svo_place;
+typedef struct {
+    int32_t n_landmarks;             /* |M| */
+    int32_t n_tags_voted;            /* the tags of the span with at least one vote */
+    int32_t n_places;                /* the places written */
+} svo_place_result;
+/* rows = {0, -1}, max_dist = 40, ratio 7 / 10 (svo_reloc_params_default's), tags = {0, SVO_PLACE_MAX_TAGS - 1}, min_votes = 1,
+ * separation = 0, max_places = 8. */
+void svo_place_params_default(svo_place_params* params);
+/* Rule 2 alone with the caller's id list as M (host memory; duplicates are legal, M is a set): the stage the tests read, and the
+ * local-map query "which keyframes saw the landmarks I am tracking".  votes, rows, row_first, row_end: tag_hi - tag_lo + 1 host
+ * entries each, each may be NULL. */
+int svo_desc_index_tag_votes(svo_desc_index* index, int n_ids, const uint64_t* ids, int row_lo, int row_hi, int32_t tag_lo, int32_t tag_hi,
+                             int32_t* votes, int32_t* rows, int32_t* row_first, int32_t* row_end);
+/* Rules 1 - 3 for n descriptors of 32 bytes.  places: room for params->max_places entries, the first result->n_places are written.
+ * cand_query, cand_row: n entries each, each may be NULL; the first result->n_landmarks are written, as svo_desc_index_select's. */
+int svo_desc_index_places(svo_desc_index* index, int n, const uint8_t* query, const svo_place_params* params, svo_place_result* result,
+                          svo_place* places, int32_t* cand_query, int32_t* cand_row);
+/* Rules 2 - 3 for a back end that knows its landmarks: M is the id list.  max_dist and the ratio play no part and are not checked. */
+int svo_desc_index_places_from_ids(svo_desc_index* index, int n_ids, const uint64_t* ids, const svo_place_params* params,
+                                   svo_place_result* result, svo_place* places);
+/* Diagnostics, for tools/place_bench.py: on = 0 makes the sweep issue every qualifying row's four atomics on its own in place of one
+ * set per run of equal tags in a wave (the default, on != 0).  The results do not depend on it. */
+int svo_desc_index_set_place_combine(svo_desc_index* index, int on);
 
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.

@@ -723,6 +723,39 @@ class DescriptorIndex {
         if (pairs) *pairs = std::move(p);
         return r;
     }
+    // ---- place candidates (svo.h, "Place candidates"): which keyframes (tags) of the map a frame resembles, on the device
+    static svo_place_params place_params() { svo_place_params p; svo_place_params_default(&p); return p; }
+    struct Places { svo_place_result result; std::vector<svo_place> places; };              // places: rule 3's order
+    struct TagVotes { std::vector<int32_t> votes, rows, row_first, row_end; };               // indexed tag - tags.first
+    // rules 1 - 3: the keyframes whose rows hold the most landmarks these descriptors recognise; cand: the recognised landmarks, as select's
+    Places places(const std::vector<Descriptor>& query, const svo_place_params& prm, Candidates* cand = nullptr) {
+        if (query.size() > (size_t)SVO_PLACE_MAX_IDS) throw std::runtime_error("DescriptorIndex::places: at most 4096 queries");
+        Places p; p.places.resize(SVO_PLACE_MAX_PLACES);
+        Candidates c = room(query.size(), false);
+        svo_throw(svo_desc_index_places(index_, (int)query.size(), rows(query), &prm, &p.result, p.places.data(), c.query.data(), c.row.data()));
+        p.places.resize((size_t)p.result.n_places);
+        shrink(c, query.empty() ? 0 : p.result.n_landmarks);
+        if (cand) *cand = std::move(c);
+        return p;
+    }
+    // rules 2 - 3 for landmarks known by id: the keyframes that saw what a tracker holds
+    Places places_from_ids(const std::vector<uint64_t>& ids, const svo_place_params& prm) {
+        if (ids.size() > (size_t)SVO_PLACE_MAX_IDS) throw std::runtime_error("DescriptorIndex::places_from_ids: at most 4096 ids");
+        Places p; p.places.resize(SVO_PLACE_MAX_PLACES);
+        svo_throw(svo_desc_index_places_from_ids(index_, (int)ids.size(), ids.data(), &prm, &p.result, p.places.data()));
+        p.places.resize((size_t)p.result.n_places);
+        return p;
+    }
+    // rule 2 alone: per tag of [tags.first, tags.second] the rows of [rows.first, rows.second) under it and those whose id is listed
+    TagVotes tag_votes(const std::vector<uint64_t>& ids, std::pair<int, int> rows = {0, -1}, std::pair<int32_t, int32_t> tags = {0, 0}) {
+        if (ids.size() > (size_t)SVO_PLACE_MAX_IDS) throw std::runtime_error("DescriptorIndex::tag_votes: at most 4096 ids");
+        const int64_t span = (int64_t)tags.second - (int64_t)tags.first + 1;
+        const size_t nb = tags.first >= 0 && span >= 1 && span <= SVO_PLACE_MAX_TAGS ? (size_t)span : 1;   // a span the library refuses: room for nothing
+        TagVotes v; v.votes.resize(nb); v.rows.resize(nb); v.row_first.resize(nb); v.row_end.resize(nb);
+        svo_throw(svo_desc_index_tag_votes(index_, (int)ids.size(), ids.data(), rows.first, rows.second, tags.first, tags.second, v.votes.data(),
+                                           v.rows.data(), v.row_first.data(), v.row_end.data()));
+        return v;
+    }
     int retire_slab_rows() const { return svo_desc_index_get_retire_slab_rows(index_); }
     void retire_slab_rows(int rows) { svo_throw(svo_desc_index_set_retire_slab_rows(index_, rows)); }   // 0: the default
     int size() const { return svo_desc_index_size(index_); }

@@ -143,6 +143,20 @@ class SvoFuseResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_pairs", "n_same", "n_fused", "n_rows_relabelled")]
 
 
+class SvoPlaceParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("row_lo", "row_hi", "max_dist", "ratio_num", "ratio_den", "tag_lo", "tag_hi", "min_votes", "separation",
+                                         "max_places")]
+
+
+class SvoPlaceResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_landmarks", "n_tags_voted", "n_places")]
+
+
+PLACE_DTYPE = np.dtype([("tag", "<i4"), ("votes", "<i4"), ("rows", "<i4"), ("row_first", "<i4"), ("row_end", "<i4"), ("reserved", "<i4", 3)])
+assert PLACE_DTYPE.itemsize == 32
+PLACE_MAX_TAGS, PLACE_MAX_PLACES, PLACE_MAX_IDS = 1 << 20, 64, 4096
+
+
 class SvoRetireRule(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("row_lo", C.c_int32), ("row_hi", C.c_int32), ("tag_lo", C.c_int32), ("tag_hi", C.c_int32),
                 ("n_ids", C.c_int32), ("ids", C.c_void_p)]
@@ -229,6 +243,11 @@ PROTOTYPES = {
     "svo_desc_index_pair_near": (I, (P, P, P, P, P)),
     "svo_desc_index_relabel": (I, (P, I, P, P, I, I, P)),
     "svo_desc_index_fuse": (I, (P, P, P, P, P)),
+    "svo_place_params_default": (None, (P,)),
+    "svo_desc_index_tag_votes": (I, (P, I, P, I, I, I, I, P, P, P, P)),
+    "svo_desc_index_places": (I, (P, I, P, P, P, P, P, P)),
+    "svo_desc_index_places_from_ids": (I, (P, I, P, P, P, P)),
+    "svo_desc_index_set_place_combine": (I, (P, I)),
     "svo_set_detection_mask": (I, (P, I, P, I, I)),
     "svo_get_detection_mask": (I, (P, I, P, P)),
     "svo_set_motion_prior": (I, (P, I, P, P)),

@@ -370,6 +370,7 @@ def descriptor_pattern():
 RelocResult = collections.namedtuple("RelocResult", "success n_candidates n_inliers iters_run R t T")
 AlignResult = collections.namedtuple("AlignResult", "success n_pairs n_inliers best_hypothesis best_count refit_rounds_run R t T rms")
 FuseResult = collections.namedtuple("FuseResult", "n_pairs n_same n_fused n_rows_relabelled")
+PlaceResult = collections.namedtuple("PlaceResult", "n_landmarks n_tags_voted n_places")
 
 
 class DescriptorIndex:
@@ -782,6 +783,60 @@ class DescriptorIndex:
         r = _lib.SvoFuseResult()
         check(lib.svo_desc_index_fuse(self._h, C.byref(p), C.byref(r), ptr(ps), ptr(pd)))
         return FuseResult(r.n_pairs, r.n_same, r.n_fused, r.n_rows_relabelled), {"src": ps[:r.n_pairs].copy(), "dst": pd[:r.n_pairs].copy()}
+
+    # ---- place candidates (svo.h, "Place candidates"): which keyframes (tags) of the map a frame resembles, on the device
+    @staticmethod
+    def place_params(rows=(0, -1), tags=(0, _lib.PLACE_MAX_TAGS - 1), **over):
+        """svo_place_params_default with the rows and the tags = (tag_lo, tag_hi) and fields replaced: max_dist, ratio_num, ratio_den,
+        min_votes, separation, max_places"""
+        p = _lib.SvoPlaceParams()
+        lib.svo_place_params_default(C.byref(p))
+        p.row_lo, p.row_hi, p.tag_lo, p.tag_hi = int(rows[0]), int(rows[1]), int(tags[0]), int(tags[1])
+        for k, v in over.items():
+            if not hasattr(p, k):
+                raise AttributeError("svo_place_params has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _id_list(ids):
+        return np.ascontiguousarray(ids).astype(np.uint64, copy=False).reshape(-1)
+
+    def tag_votes(self, ids, rows=(0, -1), tags=(0, 0)):
+        """Rule 2 of "Place candidates" with ids as the set M (svo_desc_index_tag_votes): per tag of tags = (tag_lo, tag_hi), over the
+        rows of rows = (row_lo, row_hi) -> (votes, rows, row_first, row_end), four int32 arrays indexed tag - tag_lo."""
+        i = self._id_list(ids)
+        nb = max(0, min(int(tags[1]) - int(tags[0]) + 1, _lib.PLACE_MAX_TAGS)) if int(tags[0]) >= 0 else 0
+        out = [np.zeros(max(nb, 1), np.int32) for _ in range(4)]
+        check(lib.svo_desc_index_tag_votes(self._h, len(i), ptr(i) if len(i) else None, int(rows[0]), int(rows[1]), int(tags[0]), int(tags[1]),
+                                           *(ptr(a) for a in out)))
+        return tuple(a[:nb] for a in out)
+
+    def places(self, query, rows=(0, -1), tags=(0, _lib.PLACE_MAX_TAGS - 1), min_votes=1, separation=0, max_places=8, params=None, **over):
+        """The keyframes whose rows hold the most landmarks this frame recognises (svo_desc_index_places): query (n, 32) uint8 ->
+        (PlaceResult, places, candidates): places is a structured array (tag, votes, rows, row_first, row_end) in rule 3's order,
+        candidates a dict of the recognised landmarks' query and row, as select's."""
+        q = self._rows(query, "query")
+        p = params if params is not None else self.place_params(rows, tags, min_votes=min_votes, separation=separation, max_places=max_places, **over)
+        n = len(q)
+        res, out = _lib.SvoPlaceResult(), np.zeros(_lib.PLACE_MAX_PLACES, _lib.PLACE_DTYPE)
+        cq, cr = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        check(lib.svo_desc_index_places(self._h, n, ptr(q) if n else None, C.byref(p), C.byref(res), ptr(out), ptr(cq), ptr(cr)))
+        k = res.n_landmarks if n else 0
+        return PlaceResult(res.n_landmarks, res.n_tags_voted, res.n_places), out[:res.n_places].copy(), dict(query=cq[:k].copy(), row=cr[:k].copy())
+
+    def places_from_ids(self, ids, rows=(0, -1), tags=(0, _lib.PLACE_MAX_TAGS - 1), min_votes=1, separation=0, max_places=8, params=None, **over):
+        """Rules 2 - 3 of "Place candidates" for landmarks known by id (svo_desc_index_places_from_ids): the keyframes that saw the
+        landmarks a tracker holds -> (PlaceResult, places)."""
+        i = self._id_list(ids)
+        p = params if params is not None else self.place_params(rows, tags, min_votes=min_votes, separation=separation, max_places=max_places, **over)
+        res, out = _lib.SvoPlaceResult(), np.zeros(_lib.PLACE_MAX_PLACES, _lib.PLACE_DTYPE)
+        check(lib.svo_desc_index_places_from_ids(self._h, len(i), ptr(i) if len(i) else None, C.byref(p), C.byref(res), ptr(out)))
+        return PlaceResult(res.n_landmarks, res.n_tags_voted, res.n_places), out[:res.n_places].copy()
+
+    def set_place_combine(self, on=True):
+        """diagnostics: one set of atomics per run of equal tags in a wave (the default) or four per row; the results do not depend on it"""
+        check(lib.svo_desc_index_set_place_combine(self._h, int(bool(on))))
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -26,11 +26,16 @@
 // The fusion (include/svo.h, "Landmark fusion"; the kernels are in svo_kernels_fuse.hip, the rules in svo_fuse.hpp): fuse_run, behind
 // match_near, pair_near and fuse, is k_desc_match_near and the merge over the unguided plan, then k_align_pairs, k_fuse_map,
 // k_fuse_insert and k_fuse_sweep, two copies back and one wait.  relabel puts its host lists where k_fuse_map would and runs the last two.
+//
+// The place candidates (include/svo.h, "Place candidates"; the kernels are in svo_kernels_place.hip, the rules in svo_place.hpp):
+// place_run, behind tag_votes, places and places_from_ids, is — for places — the unguided search and k_reloc_select as select runs
+// them, then k_place_sweep over the ids and tags, k_place_compact and k_place_pick, the copies back and one wait.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
 #include "svo_reloc_batch_internal.hpp"
 #include "svo_align_internal.hpp"
 #include "svo_fuse_internal.hpp"
+#include "svo_place_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -108,6 +113,10 @@ struct svo_desc_index {
     uint8_t* h_align = nullptr;                       // pinned: its first down_end bytes
     // landmark fusion: null until the first pair_near, relabel or fuse (fuse_ctl_room); the lists and the table live in d_retire
     FuseCtl* h_fuse = nullptr;                        // pinned: what a call reads back
+    // place candidates: null until the first tag_votes, places or places_from_ids (place_host_room); the device side lives in d_retire
+    uint8_t* h_place = nullptr;                       // pinned, [place_host_cap] bytes: a PlaceCtl, then tag_votes' bins; grows by doubling
+    size_t place_host_cap = 0;
+    bool place_combine = true;                        // svo_desc_index_set_place_combine
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -134,7 +143,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         for (svo_context* c : x->batch_ctx_outgrown) svo_destroy(c);
         svo_destroy(x->batch_ctx);
         (void)hipFree(x->d_batch); (void)hipHostFree(x->h_batch); (void)hipHostFree(x->h_batch_st);
-        (void)hipFree(x->d_align); (void)hipHostFree(x->h_align); (void)hipHostFree(x->h_fuse);
+        (void)hipFree(x->d_align); (void)hipHostFree(x->h_align); (void)hipHostFree(x->h_fuse); (void)hipHostFree(x->h_place);
         (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
         (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
@@ -1254,4 +1263,164 @@ extern "C" int svo_desc_index_relabel(svo_desc_index* x, int n, const uint64_t* 
     }
     if (n_rows_relabelled) *n_rows_relabelled = n_rows;
     return SVO_OK;
+}
+
+// ---- place candidates (include/svo.h, "Place candidates"; the kernels are in svo_kernels_place.hip, the rules in svo_place.hpp) ----
+extern "C" void svo_place_params_default(svo_place_params* p) {
+    if (!p) return;
+    svo_reloc_params r; svo_reloc_params_default(&r);
+    p->row_lo = 0; p->row_hi = -1; p->max_dist = r.max_dist; p->ratio_num = r.ratio_num; p->ratio_den = r.ratio_den;
+    p->tag_lo = 0; p->tag_hi = SVO_PLACE_MAX_TAGS - 1; p->min_votes = 1; p->separation = 0; p->max_places = 8;
+}
+
+extern "C" int svo_desc_index_set_place_combine(svo_desc_index* x, int on) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    x->place_combine = on != 0;
+    return SVO_OK;
+}
+
+static const char* place_refusal_text(PlaceRefusal e) {
+    switch (e) {
+    case PLACE_ROW_RANGE: return "place candidates: the row range must satisfy 0 <= row_lo <= row_hi <= size";
+    case PLACE_TAG_LO: return "place candidates: tag_lo must be >= 0";
+    case PLACE_TAG_HI: return "place candidates: tag_hi must be >= tag_lo";
+    case PLACE_TAG_SPAN: return "place candidates: at most 1 << 20 tags per call";
+    case PLACE_MIN_VOTES: return "place candidates: min_votes must be >= 1";
+    case PLACE_SEPARATION: return "place candidates: separation must be >= 0";
+    case PLACE_MAX_PLACES_RANGE: return "place candidates: max_places must be 1 .. 64";
+    case PLACE_MAX_DIST: return "place candidates: max_dist must be 0 .. 256";
+    default: return "place candidates: ratio_num and ratio_den must be 1 .. 1 << 20";
+    }
+}
+
+// Room for `need` bytes of pinned memory for a call's results: retire_room's pattern; the outgrown blocks go with the index.
+static int place_host_room(svo_desc_index* x, size_t need) {
+    if (need <= x->place_host_cap) return SVO_OK;
+    size_t cap = x->place_host_cap ? 2 * x->place_host_cap : RETIRE_SCRATCH_FIRST;
+    while (cap < need) cap *= 2;
+    uint8_t* p = nullptr;
+    MHIP(hipHostMalloc((void**)&p, cap, hipHostMallocDefault));
+    if (x->h_place) x->outgrown_pinned.push_back(x->h_place);
+    x->h_place = p; x->place_host_cap = cap;
+    return SVO_OK;
+}
+
+// where a call's results go, each null when not wanted
+struct PlaceOutputs {
+    int32_t *votes, *rows, *row_first, *row_end;      // tag_votes: one entry per bin
+    svo_place_result* res; svo_place* places;         // the two places calls
+    int32_t *cand_query, *cand_row;                   // places
+};
+
+// What tag_votes (pick false, query null), places_from_ids (pick, query null) and places (pick, with queries) share.  q: the request,
+// checked and with its row range resolved.  Everything is enqueued on the index's stream — for places the queries up, the search and
+// k_reloc_select; else the id list up — then the clearing of the bins, the sweep, the compaction and the pick, the copies back, and
+// the host waits once.  times: from the clearing to the last place kernel
+static int place_run(svo_desc_index* x, const PlaceRequest& q, bool pick, int n, const uint8_t* query, const uint64_t* ids, const PlaceOutputs& o) {
+    int rc;
+    MHIP(call_begin(x));
+    const int n_bins = q.tag_hi - q.tag_lo + 1;
+    const PlaceLayout l = place_layout(n, n_bins, pick);
+    const size_t down = sizeof(PlaceCtl) + (pick ? 0 : sizeof(PlaceBin) * (size_t)n_bins);
+    if ((rc = retire_room(x, l.total)) != SVO_OK || (rc = place_host_room(x, down)) != SVO_OK) return rc;
+    PlaceCtl* ctl = (PlaceCtl*)(x->d_retire + l.ctl);
+    uint64_t* d_list = (uint64_t*)(x->d_retire + l.ids);
+    PlaceBin* bins = (PlaceBin*)(x->d_retire + l.bins);
+    PlaceSweepArgs a{d_list, nullptr, nullptr, n, x->d_ids, x->d_points, q.row_lo, q.row_hi, q.tag_lo, q.tag_hi, bins, ctl};
+    if (query) {                                      // rule 1: svo_desc_index_select's path, without pixels and without its copies back
+        const DevBuffers* d = nullptr;
+        SearchPlan plan;
+        svo_reloc_params rp; svo_reloc_params_default(&rp);
+        if ((rc = svo_reloc_stage_ctx(x->device, n > 64 ? n : 64, rp.ransac_iterations, rp.reproj_error, rp.confidence, &d)) != SVO_OK ||
+            (rc = search_plan(x, n, q.row_lo, q.row_hi, nullptr, &plan)) != SVO_OK || (rc = stage_queries(x, n, query, true, nullptr)) != SVO_OK ||
+            (rc = search_enqueue(x, plan, n, false)) != SVO_OK) return rc;
+        RelocArgs s;
+        s.match = x->d_out; s.points = x->d_points; s.xy = x->d_qxy; s.n = n;
+        s.rule = RelocRule{q.max_dist, q.ratio_num, q.ratio_den}; s.min_candidates = rp.min_candidates;
+        s.out_xy = d->tl1; s.out_xyz = d->world; s.st = d->st;
+        s.cand_query = x->d_reloc->cand_query; s.cand_row = x->d_reloc->cand_row; s.n_cand = &x->d_reloc->n_cand;
+        launch_reloc_select(s, x->stream);
+        a.list = nullptr; a.m_rows = x->d_reloc->cand_row; a.n_dev = &x->d_reloc->n_cand;
+    } else if (n > 0) {                               // n <= 4096 ids: one piece of the pinned staging
+        memcpy(x->h_stage, ids, (size_t)n * sizeof(uint64_t));
+        MHIP(hipMemcpyAsync(d_list, x->h_stage, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
+    }
+    MHIP(span_mark(x, true, 0));
+    MHIP(hipMemsetAsync(ctl, 0, sizeof(PlaceCtl), x->stream));
+    MHIP(hipMemsetAsync(bins, 0, sizeof(PlaceBin) * (size_t)n_bins, x->stream));
+    launch_place_sweep(a, x->place_combine, x->stream);
+    if (pick) launch_place_pick(bins, n_bins, q.tag_lo, q.min_votes, q.separation, q.max_places, (uint64_t*)(x->d_retire + l.keys), ctl, x->stream);
+    MHIP(hipGetLastError());
+    MHIP(span_mark(x, true, 1));
+    uint8_t* h = x->h_place;
+    MHIP(hipMemcpyAsync(h, ctl, sizeof(PlaceCtl), hipMemcpyDeviceToHost, x->stream));
+    if (!pick) MHIP(hipMemcpyAsync(h + sizeof(PlaceCtl), bins, sizeof(PlaceBin) * (size_t)n_bins, hipMemcpyDeviceToHost, x->stream));
+    RelocHost* hr = x->h_reloc;
+    if (query && n > 0) {
+        MHIP(hipMemcpyAsync(&hr->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipMemcpyAsync(hr->out.cand_row, x->d_reloc->cand_row, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+    }
+    MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
+    MHIP(span_read(x));
+    const PlaceCtl& c = *(const PlaceCtl*)h;
+    if (c.set_full) return fail(SVO_ERR_INTERNAL, "place candidates: the set overflowed");
+    if (!pick) {
+        const PlaceBin* b = (const PlaceBin*)(h + sizeof(PlaceCtl));
+        for (int i = 0; i < n_bins; i++) {
+            if (o.votes) o.votes[i] = b[i].votes;
+            if (o.rows) o.rows[i] = b[i].rows;
+            if (o.row_first) o.row_first[i] = place_row_first(b[i]);
+            if (o.row_end) o.row_end[i] = place_row_end(b[i]);
+        }
+        return SVO_OK;
+    }
+    if (o.res) { o.res->n_landmarks = c.n_landmarks; o.res->n_tags_voted = c.n_tags_voted; o.res->n_places = c.n_places; }
+    if (o.places) memcpy(o.places, c.places, (size_t)c.n_places * sizeof(svo_place));
+    if (query && n > 0) {
+        const int nc = hr->out.n_cand;
+        if (o.cand_query) memcpy(o.cand_query, hr->out.cand_query, (size_t)nc * sizeof(int32_t));
+        if (o.cand_row) memcpy(o.cand_row, hr->out.cand_row, (size_t)nc * sizeof(int32_t));
+    }
+    return SVO_OK;
+}
+
+static int place_ids_check(const svo_desc_index* x, int n_ids, const uint64_t* ids) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "place candidates: the index has no points (svo_desc_index_enable_points)");
+    if (n_ids < 0 || n_ids > SVO_PLACE_MAX_IDS) return fail(SVO_ERR_ARG, "place candidates: n_ids must be 0 .. 4096");
+    if (n_ids > 0 && !ids) return fail(SVO_ERR_ARG, "place candidates: null ids");
+    return SVO_OK;
+}
+
+static PlaceRequest place_request(const svo_place_params* p) {
+    return PlaceRequest{p->row_lo, p->row_hi, p->max_dist, p->ratio_num, p->ratio_den, p->tag_lo, p->tag_hi, p->min_votes, p->separation, p->max_places};
+}
+
+extern "C" int svo_desc_index_tag_votes(svo_desc_index* x, int n_ids, const uint64_t* ids, int row_lo, int row_hi, int32_t tag_lo, int32_t tag_hi,
+                                        int32_t* votes, int32_t* rows, int32_t* row_first, int32_t* row_end) {
+    if (const int rc = place_ids_check(x, n_ids, ids); rc != SVO_OK) return rc;
+    PlaceRequest q{row_lo, row_hi, 0, 1, 1, tag_lo, tag_hi, 1, 0, 1};
+    if (const PlaceRefusal e = place_check_votes(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
+    return place_run(x, q, false, n_ids, nullptr, ids, PlaceOutputs{votes, rows, row_first, row_end, nullptr, nullptr, nullptr, nullptr});
+}
+
+extern "C" int svo_desc_index_places_from_ids(svo_desc_index* x, int n_ids, const uint64_t* ids, const svo_place_params* p,
+                                              svo_place_result* res, svo_place* places) {
+    if (const int rc = place_ids_check(x, n_ids, ids); rc != SVO_OK) return rc;
+    if (!p) return fail(SVO_ERR_ARG, "svo_desc_index_places_from_ids: null params");
+    PlaceRequest q = place_request(p);
+    if (const PlaceRefusal e = place_check_pick(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
+    return place_run(x, q, true, n_ids, nullptr, ids, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, nullptr, nullptr});
+}
+
+extern "C" int svo_desc_index_places(svo_desc_index* x, int n, const uint8_t* query, const svo_place_params* p, svo_place_result* res,
+                                     svo_place* places, int32_t* cand_query, int32_t* cand_row) {
+    if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_places: null index / params");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "place candidates: the index has no points (svo_desc_index_enable_points)");
+    if (n < 0 || n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "svo_desc_index_places: n must be 0 .. 4096");
+    if (n > 0 && !query) return fail(SVO_ERR_ARG, "svo_desc_index_places: null query");
+    PlaceRequest q = place_request(p);
+    if (const PlaceRefusal e = place_check(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
+    if (n == 0) return place_run(x, q, true, 0, nullptr, nullptr, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, nullptr, nullptr});
+    return place_run(x, q, true, n, query, nullptr, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, cand_query, cand_row});
 }

@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""What finding a frame's place candidates in a descriptor index costs on the device (include/svo.h, "Place candidates"), and what
+the host path it replaces costs:
+
+    python tools/place_bench.py [--out FILE] [--sizes 65536,1048576] [--spans 256,65536] [--queries 2048] [--repeats 7] [--host-repeats 3]
+
+One process.  Per index size and tag span: an index of `size` rows with random descriptors, keyframe after keyframe of size / span
+rows, tag = the keyframe's number, every landmark id on four rows, one in each of four consecutive keyframes.  The queries are the
+descriptors of `queries` rows of different landmarks with up to 8 bits flipped; the id list is those landmarks' ids.  The legs run
+alternately, each once as a warm-up and then --repeats times (the host legs --host-repeats times), and are reported as the median,
+the smallest and the largest wall time of the synchronous call in milliseconds:
+
+  places           svo_desc_index_places: the search, the selection and the new kernels; beside it the device span of the new kernels
+                   alone (HIP events: svo_desc_index_set_timing)
+  places_from_ids  svo_desc_index_places_from_ids: the id list up and the new kernels; their span beside it
+  match            svo_desc_index_match alone, the unchanged search: its wall time and its kernels' span
+  host_1, host_16  the path the calls replace: svo_desc_index_match, then on the caller's own copies of every row's id and tag the
+                   accepted queries' ids (rule 1 in numpy), numpy.isin of the rows' ids, numpy.bincount per tag and a greedy pick,
+                   the rows split over 1 and 16 threads.  Its places equal the device's (checked, untimed).
+
+And once per size, `sweep`: svo_desc_index_tag_votes' kernels (the clearing of the bins and k_place_sweep) with `queries` ids, with
+and without the wave-combined atomics, on an index whose rows all carry ONE tag (span 1) and on one whose rows each carry their OWN
+tag (span = size, at most 1 << 20).  Beside the span: the bytes the sweep fetches — 8 bytes of id and the 16-byte point row whose
+last dword is the tag, so 24 bytes a row: lines fetched, not bytes used — over that time.
+
+Figures, not pass marks.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SEEN_IN = 4
+SWEEP_BYTES_PER_ROW = 24
+
+
+def scene(size, span, n_q, seed=7):
+    rng = np.random.default_rng(seed)
+    desc = rng.integers(0, 256, (size, 32), dtype=np.uint8)
+    per = max(size // span, 1)                                            # rows of one keyframe
+    tags = np.minimum(np.arange(size) // per, span - 1).astype(np.int32)
+    # landmark l has row j of keyframes 4 g .. 4 g + 3 (g = its group): ids repeat with a period of one keyframe inside a group of four
+    frame = np.arange(size) // per
+    ids = ((frame // SEEN_IN).astype(np.uint64) << np.uint64(32)) + (np.arange(size) % per).astype(np.uint64)
+    first = np.unique(ids, return_index=True)[1]                          # one row of every landmark
+    src = first[rng.choice(len(first), n_q, replace=False)]
+    q = desc[src].copy()
+    flips = rng.integers(0, 256, (n_q, 8))
+    for b in range(8):
+        on = rng.random(n_q) < 0.5
+        q[np.flatnonzero(on), flips[on, b] >> 3] ^= (1 << (flips[on, b] & 7)).astype(np.uint8)
+    xyz = rng.uniform(0, 10, (size, 3)).astype(np.float32)
+    return dict(desc=desc, ids=ids, xyz=xyz, tags=tags, query=q, query_ids=ids[src].copy())
+
+
+def host_places(m, ids, tags, n_bins, max_places, pool, threads, max_dist=40, ratio_num=7, ratio_den=10):
+    """the host path behind the search's result rows m -> the places as (tag, votes) pairs"""
+    ok = (m["row"] >= 0) & (m["dist"].astype(np.int64) <= max_dist) & (m["dist"].astype(np.int64) * ratio_den < m["dist2"].astype(np.int64) * ratio_num)
+    M = np.unique(m["id"][ok])                                            # rule 2 of "Relocalisation" leaves one candidate per id: the same set
+    cuts = np.linspace(0, len(ids), threads + 1).astype(int)
+
+    def part(k):
+        lo, hi = cuts[k], cuts[k + 1]
+        hit = np.isin(ids[lo:hi], M)
+        return np.bincount(tags[lo:hi][hit], minlength=n_bins)
+
+    votes = sum(pool.map(part, range(threads))) if threads > 1 else part(0)
+    out, alive = [], votes >= 1
+    while len(out) < max_places and alive.any():                          # separation 0: the greedy pick is a sort
+        b = int(np.flatnonzero(alive)[np.argmax(votes[alive])])
+        out.append((b, int(votes[b])))
+        alive[b] = False
+    return out
+
+
+def stats(v):
+    return {"wall_ms_median": float(np.median(v)), "wall_ms_min": float(min(v)), "wall_ms_max": float(max(v))}
+
+
+def build(api, s):
+    ix = api.DescriptorIndex(len(s["desc"]), points=True)
+    ix.add_points(s["desc"], s["ids"], s["xyz"], s["tags"])
+    ix.set_timing(True)
+    return ix
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--sizes", default="65536,1048576")
+    ap.add_argument("--spans", default="256,65536")
+    ap.add_argument("--queries", type=int, default=2048)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--host-repeats", type=int, default=3)
+    a = ap.parse_args()
+    from stereo_visual_odometry_amd import api
+    res = {"tool": "place_bench", "queries": a.queries, "ids": a.queries, "repeats": a.repeats, "host_repeats": a.host_repeats,
+           "sweep_bytes_per_row": SWEEP_BYTES_PER_ROW, "sizes": {}}
+    pool = ThreadPoolExecutor(16)
+    for size in (int(v) for v in a.sizes.split(",")):
+        per_size = {"spans": {}}
+        for span in (int(v) for v in a.spans.split(",")):
+            s = scene(size, span, a.queries)
+            ix = build(api, s)
+            tags_kw = dict(tags=(0, span - 1))
+            got = {}
+
+            def leg_places():
+                got["places"] = ix.places(s["query"], **tags_kw)
+                return ix.stats()["last_kernels_ms"]
+
+            def leg_ids():
+                got["ids"] = ix.places_from_ids(s["query_ids"], **tags_kw)
+                return ix.stats()["last_kernels_ms"]
+
+            def leg_match():
+                got["match"] = ix.match(s["query"])
+                return ix.stats()["last_kernels_ms"]
+
+            def leg_host(threads):
+                m = ix.match(s["query"])
+                got["host"] = host_places(m, s["ids"], s["tags"], span, 8, pool, threads)
+                return 0.0
+
+            legs = {"places": (leg_places, a.repeats), "places_from_ids": (leg_ids, a.repeats), "match": (leg_match, a.repeats),
+                    "host_1": (lambda: leg_host(1), a.host_repeats), "host_16": (lambda: leg_host(16), a.host_repeats)}
+            walls, kern = {k: [] for k in legs}, {k: [] for k in legs}
+            for rep in range(max(a.repeats, a.host_repeats) + 1):         # alternating; the first round is the warm-up
+                for k, (f, reps) in legs.items():
+                    if rep > reps:
+                        continue
+                    t0 = time.perf_counter()
+                    ms = f()
+                    if rep:
+                        walls[k].append((time.perf_counter() - t0) * 1e3); kern[k].append(ms)
+            out = {k: stats(v) for k, v in walls.items()}
+            for k in ("places", "places_from_ids", "match"):
+                out[k]["kernels_ms_median"] = float(np.median(kern[k]))
+            r, places, _ = got["places"]
+            dev = [(int(p["tag"]), int(p["votes"])) for p in places]
+            out.update(n_landmarks=int(r.n_landmarks), n_tags_voted=int(r.n_tags_voted), n_places=int(r.n_places), top_votes=dev[0][1] if dev else 0,
+                       host_equals_device=bool(dev == got["host"]), from_ids_equals_places=bool(got["ids"][1].tobytes() == places.tobytes()))
+            per_size["spans"][str(span)] = out
+            ix.close()
+        # the sweep alone, with and without the wave-combined atomics
+        sweep = {}
+        base = scene(size, 1, a.queries)
+        for name, tags, span in (("one_tag_for_all", np.zeros(size, np.int32), 1), ("one_tag_per_row", np.arange(size, dtype=np.int32), min(size, 1 << 20))):
+            ix = build(api, dict(base, tags=np.minimum(tags, span - 1)))
+            for combine in (True, False):
+                ix.set_place_combine(combine)
+                ms, votes = [], None
+                for rep in range(a.repeats + 1):
+                    votes = ix.tag_votes(base["query_ids"], (0, -1), (0, span - 1))[0]
+                    if rep:
+                        ms.append(ix.stats()["last_kernels_ms"])
+                med = float(np.median(ms))
+                sweep["%s_%s" % (name, "combined" if combine else "plain")] = dict(
+                    kernels_ms_median=med, kernels_ms_min=float(min(ms)), kernels_ms_max=float(max(ms)), bins=span, votes=int(votes.sum()),
+                    fetched_gb_per_s=SWEEP_BYTES_PER_ROW * size / (med * 1e-3) / 1e9 if med > 0 else None)
+            ix.close()
+        per_size["sweep"] = sweep
+        res["sizes"][str(size)] = per_size
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
