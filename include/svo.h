@@ -1037,6 +1037,65 @@ int svo_desc_index_places_from_ids(svo_desc_index* index, int n_ids, const uint6
  * set per run of equal tags in a wave (the default, on != 0).  The results do not depend on it. */
 int svo_desc_index_set_place_combine(svo_desc_index* index, int on);
 
+/* ---- Landmark consolidation: medoid descriptor and mean point per landmark --------------------------------------------------------
+ * A landmark seen in k frames has k rows, each with one view's descriptor and one triangulation.  svo_desc_index_consolidate leaves
+ * one row per landmark: the most central of the observed descriptors and the mean of the points that agree with it.  It runs on the
+ * device, in place, is synchronous, waits for the index's own stream only and is legal with frames in flight.  The rules are the
+ * whole definition; the result equals a sequential program's in every bit.  Let n0 be the size before the call and
+ * S = [row_lo, row_hi) the scope (row_hi = -1: n0).
+ *  1. Members.  Row r is a member when r is in S, tag[r] != SVO_POINT_NONE and tag_lo <= tag[r] <= tag_hi.  A group is the set of
+ *     members with one id, in ascending rows r_0 < ... < r_(k-1).  Every non-member — a row outside S, a row without a point, a row
+ *     outside the tag window — is kept and carried bit for bit.
+ *  2. Views.  The views of a group are its last min(k, SVO_CONSOLIDATE_MAX_VIEWS) members.  The older members of a larger group are
+ *     dropped without contributing; such a group is counted in n_capped_groups.
+ *  3. Medoid.  For view i, s_i is the sum over the group's views j of d(i, j), the search's Hamming distance.  The medoid is the view
+ *     with the smallest s_i, at equal sums the one with the larger row.  (ORB-SLAM's ComputeDistinctiveDescriptors takes the least
+ *     median; this rule is the sum, and no parity with it is claimed.)
+ *  4. Point.  View j is near when |p_j[c] - p_medoid[c]| <= radius in f32 on all three axes c ("Landmark fusion"'s gate); the
+ *     medoid is always near, the other views are counted in n_far_views.  Coordinate c of the new point is
+ *     f32(sum_c / (double)n_near), where sum_c is the f64 sum of the near views' coordinates in ascending row order, starting from
+ *     0.0, every addition and the division rounded on its own, without contraction.
+ *  5. Result.  Of a group of two or more, only r_(k-1) is kept: it takes the medoid's descriptor and rule 4's point and keeps its
+ *     own id and its own tag.  A group of one row is left as it is, in every bit.  kept_before (n0 + 1 entries, or NULL), the new
+ *     size, the order of the rows and the remapping of stored row numbers are exactly svo_desc_index_retire's.
+ * The result record: n_members; n_groups; n_dropped = n_members - n_groups; n_far_views; n_capped_groups; n_kept, the new size.  A
+ * second identical call changes nothing.  radius is in the map's unit; no default is measured for any rig.
+ * Refusals, each decided before the first write to the index: a refused call changes nothing.  SVO_ERR_ARG: a row range
+ * svo_desc_index_match refuses, a radius that is not finite or negative.  SVO_ERR_STATE: an index without points.
+ * SVO_ERR_INTERNAL: the table of ids overflowed, which its size rules out.
+ *
+ * What it costs in information.  After consolidation a landmark has one row and so one tag: in "Place candidates" it votes for the
+ * keyframe of its latest view only, exactly as after SVO_RETIRE_LATEST_PER_ID.  Consolidate what has left the window the place
+ * search looks at (tag_hi), not the whole index.  Consolidation does not cross ids: run svo_desc_index_fuse first.
+ *
+ * Memory.  All working memory is the maintenance scratch of "Index maintenance" (the same buffer, the same growth rule).  With m the
+ * scope's rows and R and slots as there, a call needs
+ *   need = R(m) + R(4 (m + 1)) + R(4 (ceil(m / 256) + 257)) + 2 R(4 slots(m)) + R(4 m) + R(56 min(retire_slab_rows, n0 - row_lo))
+ * bytes: retire's keep flags, ranks and block counts, the table of latest rows, the members counted per slot, the member list and
+ * the bounce buffer.  An empty scope needs nothing.
+ *
+ * svo_desc_index_read_rows copies the rows [row_lo, row_hi) (row_hi = -1: the size) to the host: desc 32 bytes a row, ids, xyz three
+ * floats a row, tags; each may be NULL.  A row without a point reads xyz = +inf and tag = SVO_POINT_NONE.  The data comes through the
+ * index's pinned staging 4096 rows at a time on the index's stream; the call is legal with frames in flight.  With
+ * svo_desc_index_add_points (and svo_desc_index_add for the runs of rows without a point) it saves and restores a map.
+ * SVO_ERR_STATE: xyz or tags asked of an index without points.  SVO_ERR_ARG: a row range svo_desc_index_match refuses. */
+#define SVO_CONSOLIDATE_MAX_VIEWS 64
+typedef struct {
+    int32_t row_lo, row_hi;          /* the scope [row_lo, row_hi), row_hi = -1: the size */
+    int32_t tag_lo, tag_hi;          /* rule 1: inclusive */
+    float   radius;                  /* rule 4: finite, >= 0 */
+    int32_t reserved;                /* 0 */
+} svo_consolidate_params;
+typedef struct {
+    int32_t n_members, n_groups, n_dropped, n_far_views, n_capped_groups, n_kept;
+    int32_t reserved[2];             /* 0 */
+} svo_consolidate_result;
+/* the whole index, tags 0 .. INT32_MAX */
+void svo_consolidate_params_default(svo_consolidate_params* params, float radius);
+/* result may be NULL; kept_before: size-before-the-call + 1 entries, or NULL */
+int svo_desc_index_consolidate(svo_desc_index* index, const svo_consolidate_params* params, svo_consolidate_result* result, int32_t* kept_before);
+int svo_desc_index_read_rows(svo_desc_index* index, int row_lo, int row_hi, uint8_t* desc, uint64_t* ids, float* xyz, int32_t* tags);
+
 /* ---- Detection masks: keep features off marked regions of the left image ----------------------------------------------------
  * What OpenCV users pass to FeatureDetector::detect(image, keypoints, mask); the reference calls cv::FAST directly and has none.
  * A mask is an 8-bit image of the context's size width x height — the rectified, grey geometry, whatever the input format and the

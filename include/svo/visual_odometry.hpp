@@ -756,6 +756,26 @@ class DescriptorIndex {
                                            v.rows.data(), v.row_first.data(), v.row_end.data()));
         return v;
     }
+    // ---- landmark consolidation (svo.h, "Landmark consolidation"): one row per landmark, and the rows read back
+    // svo_consolidate_params_default: the whole index, every tag.  radius (the map's unit) has no default: none has been measured
+    static svo_consolidate_params consolidate_params(float radius) { svo_consolidate_params p; svo_consolidate_params_default(&p, radius); return p; }
+    // each group's latest row takes the medoid descriptor and the gated mean point, the others go; kept_before: retire's remapping
+    svo_consolidate_result consolidate(const svo_consolidate_params& prm, std::vector<int32_t>* kept_before = nullptr) {
+        std::vector<int32_t> map((size_t)size() + 1);
+        svo_consolidate_result r;
+        svo_throw(svo_desc_index_consolidate(index_, &prm, &r, map.data()));
+        if (kept_before) *kept_before = std::move(map);
+        return r;
+    }
+    struct Rows { std::vector<Descriptor> desc; std::vector<uint64_t> ids; std::vector<float> xyz; std::vector<int32_t> tags; };
+    // rows [row_lo, row_hi) back on the host; xyz (3 floats a row, +inf without a point) and tags only on an index with points
+    Rows read_rows(int row_lo = 0, int row_hi = -1, bool points = true) {
+        const size_t n = span_rows(row_lo, row_hi);
+        Rows r; r.desc.resize(n); r.ids.resize(n); r.xyz.resize(points ? 3 * n : 0); r.tags.resize(points ? n : 0);
+        svo_throw(svo_desc_index_read_rows(index_, row_lo, row_hi, n ? r.desc[0].data() : nullptr, r.ids.data(), points ? r.xyz.data() : nullptr,
+                                           points ? r.tags.data() : nullptr));
+        return r;
+    }
     int retire_slab_rows() const { return svo_desc_index_get_retire_slab_rows(index_); }
     void retire_slab_rows(int rows) { svo_throw(svo_desc_index_set_retire_slab_rows(index_, rows)); }   // 0: the default
     int size() const { return svo_desc_index_size(index_); }

@@ -157,6 +157,18 @@ assert PLACE_DTYPE.itemsize == 32
 PLACE_MAX_TAGS, PLACE_MAX_PLACES, PLACE_MAX_IDS = 1 << 20, 64, 4096
 
 
+class SvoConsolidateParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("row_lo", "row_hi", "tag_lo", "tag_hi")] + [("radius", C.c_float), ("reserved", C.c_int32)]
+
+
+class SvoConsolidateResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_members", "n_groups", "n_dropped", "n_far_views", "n_capped_groups", "n_kept")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
+CONSOLIDATE_MAX_VIEWS = 64
+
+
 class SvoRetireRule(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("row_lo", C.c_int32), ("row_hi", C.c_int32), ("tag_lo", C.c_int32), ("tag_hi", C.c_int32),
                 ("n_ids", C.c_int32), ("ids", C.c_void_p)]
@@ -248,6 +260,9 @@ PROTOTYPES = {
     "svo_desc_index_places": (I, (P, I, P, P, P, P, P, P)),
     "svo_desc_index_places_from_ids": (I, (P, I, P, P, P, P)),
     "svo_desc_index_set_place_combine": (I, (P, I)),
+    "svo_consolidate_params_default": (None, (P, F)),
+    "svo_desc_index_consolidate": (I, (P, P, P, P)),
+    "svo_desc_index_read_rows": (I, (P, I, I, P, P, P, P)),
     "svo_set_detection_mask": (I, (P, I, P, I, I)),
     "svo_get_detection_mask": (I, (P, I, P, P)),
     "svo_set_motion_prior": (I, (P, I, P, P)),

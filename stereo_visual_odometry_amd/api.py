@@ -371,6 +371,7 @@ RelocResult = collections.namedtuple("RelocResult", "success n_candidates n_inli
 AlignResult = collections.namedtuple("AlignResult", "success n_pairs n_inliers best_hypothesis best_count refit_rounds_run R t T rms")
 FuseResult = collections.namedtuple("FuseResult", "n_pairs n_same n_fused n_rows_relabelled")
 PlaceResult = collections.namedtuple("PlaceResult", "n_landmarks n_tags_voted n_places")
+ConsolidateResult = collections.namedtuple("ConsolidateResult", "n_members n_groups n_dropped n_far_views n_capped_groups n_kept")
 
 
 class DescriptorIndex:
@@ -837,6 +838,39 @@ class DescriptorIndex:
     def set_place_combine(self, on=True):
         """diagnostics: one set of atomics per run of equal tags in a wave (the default) or four per row; the results do not depend on it"""
         check(lib.svo_desc_index_set_place_combine(self._h, int(bool(on))))
+
+    # ---- landmark consolidation (svo.h, "Landmark consolidation"): one row per landmark, and the rows read back
+    @staticmethod
+    def consolidate_params(radius, rows=(0, -1), tags=None):
+        """svo_consolidate_params_default with the scope rows = (row_lo, row_hi) and the window tags = (tag_lo, tag_hi) (None: every
+        tag).  radius (the map's unit) has no default: none has been measured for any rig."""
+        p = _lib.SvoConsolidateParams()
+        lib.svo_consolidate_params_default(C.byref(p), float(radius))
+        p.row_lo, p.row_hi = int(rows[0]), int(rows[1])
+        if tags is not None:
+            p.tag_lo, p.tag_hi = int(tags[0]), int(tags[1])
+        return p
+
+    def consolidate(self, radius, rows=(0, -1), tags=None, want_map=True, params=None):
+        """Leave one row per landmark among the rows of rows = (row_lo, row_hi) whose tag lies in tags: the group's latest row with the
+        medoid descriptor and the mean of the points within radius of the medoid's (svo_desc_index_consolidate) ->
+        (ConsolidateResult, kept_before): kept_before is retire's remapping, (size before + 1,) int32, or None with want_map False."""
+        p = params if params is not None else self.consolidate_params(radius, rows, tags)
+        kept_before = np.zeros(self.size + 1, np.int32) if want_map else None
+        r = _lib.SvoConsolidateResult()
+        check(lib.svo_desc_index_consolidate(self._h, C.byref(p), C.byref(r), ptr(kept_before)))
+        return ConsolidateResult(r.n_members, r.n_groups, r.n_dropped, r.n_far_views, r.n_capped_groups, r.n_kept), kept_before
+
+    def read_rows(self, rows=(0, -1), want=("desc", "ids", "xyz", "tags")):
+        """The rows of rows = (row_lo, row_hi) back on the host (svo_desc_index_read_rows) -> (desc (m, 32) uint8, ids (m,) uint64,
+        xyz (m, 3) float32, tags (m,) int32); a row without a point reads xyz = +inf and tag = -1.  An output not named in want is
+        not read and is None."""
+        m = self._span_rows(rows)
+        out = dict(desc=np.zeros((m, _lib.DESC_BYTES), np.uint8), ids=np.zeros(m, np.uint64), xyz=np.zeros((m, 3), np.float32),
+                   tags=np.zeros(m, np.int32))
+        got = [out[k] if k in want else None for k in ("desc", "ids", "xyz", "tags")]
+        check(lib.svo_desc_index_read_rows(self._h, int(rows[0]), int(rows[1]), *(ptr(a) for a in got)))
+        return tuple(got)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -30,12 +30,17 @@
 // The place candidates (include/svo.h, "Place candidates"; the kernels are in svo_kernels_place.hip, the rules in svo_place.hpp):
 // place_run, behind tag_votes, places and places_from_ids, is — for places — the unguided search and k_reloc_select as select runs
 // them, then k_place_sweep over the ids and tags, k_place_compact and k_place_pick, the copies back and one wait.
+//
+// The consolidation (include/svo.h, "Landmark consolidation"; the kernels are in svo_kernels_consolidate.hip, the rules in
+// svo_consolidate.hpp): consolidate is a retire whose keep flags come from launch_consolidate, which also rewrites each group's latest
+// row; the ranks, the two waits and the move of the rows (retire_move_rows) are retire's.  read_rows is index_add's staging run downwards.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
 #include "svo_reloc_batch_internal.hpp"
 #include "svo_align_internal.hpp"
 #include "svo_fuse_internal.hpp"
 #include "svo_place_internal.hpp"
+#include "svo_consolidate_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -989,6 +994,30 @@ static int retire_download_ranks(svo_desc_index* x, const int32_t* d_rank, int r
     return SVO_OK;
 }
 
+// The move of a call that keeps `kept` of its scope's m rows, kept < m: the scope's slabs, then the rows behind it, which all stay and
+// move down; the call's second wait.
+static int retire_move_rows(svo_desc_index* x, const RetireRows& rows, int row_lo, int row_hi, int kept, const uint8_t* keep, const int32_t* rank,
+                            void* bounce, int slab) {
+    const int n0 = x->size, m = row_hi - row_lo;
+    MHIP(span_mark(x, true, 0));
+    for (int a = 0; a < m; a += slab)
+        launch_retire_slab(rows, row_lo + a, m - a < slab ? m - a : slab, keep + a, rank + a, row_lo, bounce, slab, x->stream);
+    for (int a = row_hi; a < n0; a += slab)
+        launch_retire_slab(rows, a, n0 - a < slab ? n0 - a : slab, nullptr, nullptr, row_lo + kept + (a - row_hi), bounce, slab, x->stream);
+    MHIP(hipGetLastError());
+    MHIP(span_mark(x, true, 1));
+    MHIP(hipStreamSynchronize(x->stream));
+    MHIP(retire_span_read(x));
+    return SVO_OK;
+}
+
+// kept_before outside the scope, and inside it where the ranks did not come down because every row of the scope stayed
+static void retire_fill_map(int32_t* kept_before, int row_lo, int row_hi, int n0, int kept, bool ranks_down) {
+    for (int r = 0; r <= row_lo; r++) kept_before[r] = r;
+    if (!ranks_down) for (int r = row_lo; r < row_hi; r++) kept_before[r] = r;
+    for (int r = row_hi; r <= n0; r++) kept_before[r] = r - (row_hi - row_lo - kept);
+}
+
 extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* rule, int32_t* kept_before, int* n_kept) {
     if (!x || !rule) return fail(SVO_ERR_ARG, "svo_desc_index_retire: null index / rule");
     const uint32_t flags = rule->flags;
@@ -1041,23 +1070,9 @@ extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* r
             if ((rc = retire_download_ranks(x, rank, row_lo, m, kept_before)) != SVO_OK) return rc;
             ranks_down = true;
         }
-        if (kept < m) {                               // the scope's slabs, then the rows behind it, which all stay and move down
-            MHIP(span_mark(x, true, 0));
-            for (int a = 0; a < m; a += slab)
-                launch_retire_slab(rows, row_lo + a, m - a < slab ? m - a : slab, keep + a, rank + a, row_lo, bounce, slab, x->stream);
-            for (int a = row_hi; a < n0; a += slab)
-                launch_retire_slab(rows, a, n0 - a < slab ? n0 - a : slab, nullptr, nullptr, row_lo + kept + (a - row_hi), bounce, slab, x->stream);
-            MHIP(hipGetLastError());
-            MHIP(span_mark(x, true, 1));
-            MHIP(hipStreamSynchronize(x->stream));
-            MHIP(retire_span_read(x));
-        }
+        if (kept < m && (rc = retire_move_rows(x, rows, row_lo, row_hi, kept, keep, rank, bounce, slab)) != SVO_OK) return rc;
     }
-    if (kept_before) {
-        for (int r = 0; r <= row_lo; r++) kept_before[r] = r;
-        if (!ranks_down) for (int r = row_lo; r < row_hi; r++) kept_before[r] = r;       // every row of the scope stayed
-        for (int r = row_hi; r <= n0; r++) kept_before[r] = r - (m - kept);
-    }
+    if (kept_before) retire_fill_map(kept_before, row_lo, row_hi, n0, kept, ranks_down);
     x->size = n0 - (m - kept);
     if (n_kept) *n_kept = x->size;
     return SVO_OK;
@@ -1423,4 +1438,104 @@ extern "C" int svo_desc_index_places(svo_desc_index* x, int n, const uint8_t* qu
     if (const PlaceRefusal e = place_check(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
     if (n == 0) return place_run(x, q, true, 0, nullptr, nullptr, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, nullptr, nullptr});
     return place_run(x, q, true, n, query, nullptr, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, cand_query, cand_row});
+}
+
+// ---- landmark consolidation (include/svo.h, "Landmark consolidation"; the kernels are in svo_kernels_consolidate.hip, the rules in
+// svo_consolidate.hpp): the flags, the table, the member list and the group kernel on the stream, then retire's ranks, one wait for
+// the counts and the table's flag, and retire's move of the rows and its second wait ----
+extern "C" void svo_consolidate_params_default(svo_consolidate_params* p, float radius) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->row_lo = 0; p->row_hi = -1; p->tag_lo = 0; p->tag_hi = INT32_MAX; p->radius = radius;
+}
+
+extern "C" int svo_desc_index_consolidate(svo_desc_index* x, const svo_consolidate_params* p, svo_consolidate_result* res, int32_t* kept_before) {
+    if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_consolidate: null index / params");
+    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_consolidate: the index has no points (svo_desc_index_enable_points)");
+    ConsRequest q{p->row_lo, p->row_hi, p->tag_lo, p->tag_hi, p->radius};
+    switch (cons_check(q, x->size)) {
+        case CONS_RANGE: return fail(SVO_ERR_ARG, "svo_desc_index_consolidate: the row range must satisfy 0 <= row_lo <= row_hi <= size");
+        case CONS_RADIUS: return fail(SVO_ERR_ARG, "svo_desc_index_consolidate: radius must be finite and >= 0");
+        case CONS_OK: break;
+    }
+    x->retire_ms = 0.f;
+    MHIP(hipSetDevice(x->device));
+    const int row_lo = q.row_lo, row_hi = q.row_hi, n0 = x->size, m = row_hi - row_lo;
+    int rc, kept = m;                                 // of the scope's rows
+    bool ranks_down = false;
+    svo_consolidate_result r;
+    memset(&r, 0, sizeof(r));
+    if (m > 0) {
+        const int slab = n0 - row_lo < x->retire_slab ? n0 - row_lo : x->retire_slab;
+        const ConsLayout l = cons_layout(m, n0 - row_lo, x->retire_slab);
+        if ((rc = retire_ctl_room(x)) != SVO_OK || (rc = retire_room(x, l.total)) != SVO_OK) return rc;
+        ConsCtl* d_ctl = (ConsCtl*)x->d_retire_ctl;
+        const ConsCtl* h_ctl = (const ConsCtl*)&x->h_retire->ctl;
+        ConsWork w;
+        w.row_lo = row_lo; w.n = m; w.tag_lo = q.tag_lo; w.tag_hi = q.tag_hi;
+        w.keep = x->d_retire + l.keep;
+        w.offset = (int32_t*)(x->d_retire + l.rank);
+        w.sums = (int32_t*)(x->d_retire + l.counts);
+        w.table = (int32_t*)(x->d_retire + l.table);
+        w.count = (int32_t*)(x->d_retire + l.count);
+        w.slots = retire_table_slots(m);
+        w.list = (int32_t*)(x->d_retire + l.list);
+        w.ctl = d_ctl;
+        void* bounce = x->d_retire + l.bounce;
+        const RetireRows rows{(uint4*)x->d_desc, x->d_ids, (uint4*)x->d_points};
+        MHIP(hipMemsetAsync(d_ctl, 0, sizeof(ConsCtl), x->stream));
+        MHIP(hipMemsetAsync(w.table, 0xFF, (size_t)w.slots * sizeof(int32_t), x->stream));   // RETIRE_EMPTY
+        MHIP(hipMemsetAsync(w.count, 0, (size_t)w.slots * sizeof(int32_t), x->stream));
+        MHIP(span_mark(x, true, 0));
+        launch_consolidate(rows, w, q.radius, x->stream);
+        launch_retire_ranks(w.keep, m, w.sums, w.offset, x->stream);             // the offsets have served: their room takes the ranks
+        MHIP(hipGetLastError());
+        MHIP(span_mark(x, true, 1));
+        MHIP(hipMemcpyAsync(&x->h_retire->ctl, d_ctl, sizeof(ConsCtl), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipMemcpyAsync(&x->h_retire->kept, w.offset + m, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));        // with the flag up nothing was written; without it no row has moved yet
+        MHIP(retire_span_read(x));
+        if (h_ctl->table_full) return fail(SVO_ERR_INTERNAL, "svo_desc_index_consolidate: the table of ids overflowed (nothing was changed)");
+        for (const ConsCounts& c : h_ctl->counts) {
+            r.n_members += c.n_members; r.n_groups += c.n_groups; r.n_far_views += c.n_far_views; r.n_capped_groups += c.n_capped_groups;
+        }
+        kept = x->h_retire->kept;
+        if (kept_before && kept < m) {
+            if ((rc = retire_download_ranks(x, w.offset, row_lo, m, kept_before)) != SVO_OK) return rc;
+            ranks_down = true;
+        }
+        if (kept < m && (rc = retire_move_rows(x, rows, row_lo, row_hi, kept, w.keep, w.offset, bounce, slab)) != SVO_OK) return rc;
+    }
+    if (kept_before) retire_fill_map(kept_before, row_lo, row_hi, n0, kept, ranks_down);
+    x->size = n0 - (m - kept);
+    r.n_dropped = m - kept;
+    r.n_kept = x->size;
+    if (res) *res = r;
+    return SVO_OK;
+}
+
+// ---- svo_desc_index_read_rows (include/svo.h, "Landmark consolidation"): the rows come down MATCH_STAGE_ROWS at a time through the
+// pinned staging an append goes up through ----
+extern "C" int svo_desc_index_read_rows(svo_desc_index* x, int row_lo, int row_hi, uint8_t* desc, uint64_t* ids, float* xyz, int32_t* tags) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if ((xyz || tags) && !x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_read_rows: the index has no points (svo_desc_index_enable_points)");
+    if (const int rc = row_range(x, row_lo, row_hi); rc != SVO_OK) return rc;
+    MHIP(hipSetDevice(x->device));
+    uint8_t* h_ids = x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES;
+    for (int r0 = row_lo; r0 < row_hi; r0 += MATCH_STAGE_ROWS) {
+        const size_t m = (size_t)(row_hi - r0 < MATCH_STAGE_ROWS ? row_hi - r0 : MATCH_STAGE_ROWS), at = (size_t)r0, to = (size_t)(r0 - row_lo);
+        if (desc) MHIP(hipMemcpyAsync(x->h_stage, x->d_desc + at * SVO_DESC_BYTES, m * SVO_DESC_BYTES, hipMemcpyDeviceToHost, x->stream));
+        if (ids) MHIP(hipMemcpyAsync(h_ids, x->d_ids + at, m * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+        if (xyz || tags) MHIP(hipMemcpyAsync(x->h_reloc->points, x->d_points + at, m * sizeof(RelocPoint), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));
+        if (desc) memcpy(desc + to * SVO_DESC_BYTES, x->h_stage, m * SVO_DESC_BYTES);
+        if (ids) memcpy(ids + to, h_ids, m * sizeof(uint64_t));
+        for (size_t i = 0; i < m && (xyz || tags); i++) {
+            const RelocPoint& pt = x->h_reloc->points[i];
+            const bool none = pt.tag == SVO_POINT_NONE;
+            if (tags) tags[to + i] = pt.tag;
+            if (xyz) { xyz[3 * (to + i)] = none ? INFINITY : pt.x; xyz[3 * (to + i) + 1] = none ? INFINITY : pt.y; xyz[3 * (to + i) + 2] = none ? INFINITY : pt.z; }
+        }
+    }
+    return SVO_OK;
 }
