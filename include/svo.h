@@ -787,6 +787,71 @@ int svo_desc_index_localize_batch(svo_desc_index* index, int n_cameras,
  * min(cap, *n) entries.  SVO_ERR_STATE: no batch call yet, or the staging has grown since. */
 int svo_desc_index_get_batch_order(const svo_desc_index* index, int cap, int32_t* order, int* n);
 
+/* ---- Batched insertion: many sequences' frames into the index in one call -----------------------------------------------------------
+ * svo_desc_index_add_frame serves one sequence per call and runs on the host: it copies the rows out of the pinned rings, packs
+ * them, transforms the points, and pays three uploads and a synchronisation.  A many-sequence context that builds one map pays that
+ * once per sequence and step.  svo_desc_index_add_frames appends the selected rows of n entries — sequences of ctx's last COLLECTED
+ * frame — in one call: the filter, the order-preserving compaction, the f64 point transform and the id offset run on the device,
+ * which reads the rows where the frame's kernels left them, in the host-mapped rings; one host synchronisation per call.
+ *
+ * The rules.
+ *  1. Entries.  Entry b is sequence seqs[b]; seqs == NULL: entry b is sequence b.  Duplicates are legal (they are what a loop of
+ *     single calls would do).  1 <= n <= SVO_INSERT_MAX_ENTRIES; svo_desc_index_add_obs also takes n = 0 and adds nothing.  An entry
+ *     whose sequence has no rows in the last collected frame — a first frame, a sequence idle under the mask: n_tracks = 0, as
+ *     svo_get_last_track_obs reports — contributes none.
+ *  2. Keep.  Row i of entry b is kept iff (flags & need) == need; need = need_flags for the plain call, need_flags | SVO_OBS_HAS_XYZ
+ *     with points.
+ *  3. Order.  Kept rows are appended in entry order, and inside an entry in row order.  n_added[b] is entry b's kept count,
+ *     first_row[b] the size before the call plus the counts of the entries before b.  The rows of a sequence are scanned up to the
+ *     stored-row count of its header, min(n_tracks, max_rows), as the single call scans them.
+ *  4. Id.  id = (uint64_t)obs.id + id_base[b] modulo 2^64; id_base == NULL: all zero.  Two sequences' track ids both start at 0:
+ *     id_base (say seq << 48) keeps them apart in one index.  The single calls keep their rule, id = obs.id.
+ *  5. Point and tag.  Per coordinate the arithmetic of svo_desc_index_add_frame_points — f64, left to right, no contraction,
+ *     rounded to f32 — through cam_to_map + 16 b; cam_to_map == NULL stores xyz as it is.  The tag is tags[b] >= 0 (tags == NULL:
+ *     all zero).  On an index with points the plain call writes SVO_POINT_NONE rows, as svo_desc_index_add does.
+ *  6. All or nothing.  SVO_ERR_ARG, size unchanged and every row below size untouched when the kept rows exceed capacity - size, a
+ *     cam_to_map entry is not finite, a tag is negative, or a kept row's point is not finite.  (Rows beyond size are never read; the
+ *     kernels may have written there.)  size moves once, after the synchronisation.
+ *  7. Refusals otherwise: the single calls', for any entry — a null index or context, a sequence outside the context, SVO_ERR_STATE
+ *     where svo_get_last_track_descriptors gives it and for the points call on an index without points — all decided before anything
+ *     is launched.
+ *  8. The contract is the definition.  With id_base zero, the index after the call, first_row and n_added equal, in every bit, those
+ *     of the loop of svo_desc_index_add_frame[_points] over the entries.
+ * first_row and n_added (n entries each) may be NULL.  The calls are synchronous, wait for the index's own stream only, are legal
+ * with frames in flight and change no bit of what those frames return.
+ *
+ * svo_desc_index_add_obs is the same stage on the caller's own rows in host memory: entry b has the rows [row_begin[b],
+ * row_begin[b + 1]) of obs and desc (row_begin[0] = 0, non-decreasing, at most 1 << 18 rows in all); with_points != 0 is the points
+ * call (cam_to_map, tags as above), 0 the plain call (both ignored).
+ *
+ * How it runs (none of it shows in the results).  SVO_INSERT_PATH_RING: the rows are still in their slot of the rings and index and
+ * context are on one device: the kernels read the rings in place over the host link — 4 bytes of every row's flags, then the id, the
+ * point and the descriptor of the kept rows only.  SVO_INSERT_PATH_STAGED: the rows are in the context's kept copies (eight frames
+ * were submitted since the collect) or on another device, or are the caller's (add_obs): they go up through a pinned staging in
+ * groups of whole entries of at most 1 << 18 rows (96 bytes a row: under 24 MiB; it starts at 64 KiB and doubles), one
+ * synchronisation per group, the same kernels.  The working memory is the maintenance scratch ("Index maintenance").
+ * svo_desc_index_get_insert_stats: the last call's path, the rows it scanned and added, and with svo_desc_index_set_timing on the
+ * device span of its kernels (summed over a staged call's groups; the copies are not in it). */
+#define SVO_INSERT_MAX_ENTRIES 1024
+#define SVO_INSERT_MAX_OBS_ROWS (1 << 18)
+#define SVO_INSERT_PATH_NONE   0   /* no batched insertion yet */
+#define SVO_INSERT_PATH_RING   1
+#define SVO_INSERT_PATH_STAGED 2
+typedef struct {
+    float    last_kernels_ms;
+    int32_t  last_path;          /* SVO_INSERT_PATH_* */
+    uint64_t rows_scanned, rows_added;
+} svo_desc_insert_stats;
+int svo_desc_index_add_frames(svo_desc_index* index, svo_context* ctx, int n, const int32_t* seqs, uint32_t need_flags,
+                              const uint64_t* id_base, int32_t* first_row, int32_t* n_added);
+int svo_desc_index_add_frames_points(svo_desc_index* index, svo_context* ctx, int n, const int32_t* seqs, uint32_t need_flags,
+                                     const uint64_t* id_base, const double* cam_to_map /* n x 16 or NULL */,
+                                     const int32_t* tags /* n or NULL */, int32_t* first_row, int32_t* n_added);
+int svo_desc_index_add_obs(svo_desc_index* index, int n, const int32_t* row_begin /* n + 1 */, const svo_track_obs* obs,
+                           const uint8_t* desc, uint32_t need_flags, const uint64_t* id_base, int with_points,
+                           const double* cam_to_map, const int32_t* tags, int32_t* first_row, int32_t* n_added);
+int svo_desc_index_get_insert_stats(const svo_desc_index* index, svo_desc_insert_stats* stats);
+
 /* ---- Map alignment: the rigid transform between two row spans of the index ----------------------------------------------------------
  * Merging a second sequence's map, and closing a loop, need the transform between two sets of landmarks that are already in the
  * index: a 3-D to 3-D alignment, not a PnP from one image's pixels.  svo_desc_index_align searches the descriptors of a SOURCE span

@@ -776,6 +776,39 @@ class DescriptorIndex {
                                            points ? r.tags.data() : nullptr));
         return r;
     }
+    // ---- batched insertion (svo.h, "Batched insertion"): many sequences of a context's last collected frame, or the caller's own
+    // observation rows, filtered, packed and transformed on the device in one call
+    struct Inserted { std::vector<int32_t> first_row, n_added; };
+    // what a call may give per entry; an empty vector is the C call's NULL (every sequence in order, no id offset, xyz as it is, tag 0)
+    struct InsertArgs {
+        std::vector<int32_t> seqs;                 // add_frames only
+        std::vector<uint64_t> id_base;
+        std::vector<double> cam_to_map;            // 16 per entry, with points only
+        std::vector<int32_t> tags;                 // with points only
+    };
+    // n: the entries (with seqs given, seqs.size()).  with_points: svo_desc_index_add_frames_points
+    Inserted add_frames(svo_context* ctx, int n, bool with_points = false, const InsertArgs& a = InsertArgs(), uint32_t need_flags = SVO_OBS_INLIER) {
+        if (!a.seqs.empty()) n = (int)a.seqs.size();
+        insert_sizes("add_frames", n, a);
+        Inserted r; r.first_row.resize((size_t)(n > 0 ? n : 0)); r.n_added.resize(r.first_row.size());
+        if (with_points)
+            svo_throw(svo_desc_index_add_frames_points(index_, ctx, n, opt(a.seqs), need_flags, opt(a.id_base), opt(a.cam_to_map), opt(a.tags), r.first_row.data(), r.n_added.data()));
+        else
+            svo_throw(svo_desc_index_add_frames(index_, ctx, n, opt(a.seqs), need_flags, opt(a.id_base), r.first_row.data(), r.n_added.data()));
+        return r;
+    }
+    // entry b: the rows [row_begin[b], row_begin[b + 1]) of obs and desc
+    Inserted add_obs(const std::vector<int32_t>& row_begin, const std::vector<svo_track_obs>& obs, const std::vector<Descriptor>& desc, bool with_points = false,
+                     const InsertArgs& a = InsertArgs(), uint32_t need_flags = SVO_OBS_INLIER) {
+        const int n = row_begin.empty() ? 0 : (int)row_begin.size() - 1;
+        if (obs.size() != desc.size() || (n > 0 && (size_t)row_begin.back() != obs.size())) throw std::runtime_error("DescriptorIndex::add_obs: one descriptor per observation row, row_begin ending at their number, expected");
+        insert_sizes("add_obs", n, a);
+        Inserted r; r.first_row.resize((size_t)n); r.n_added.resize((size_t)n);
+        svo_throw(svo_desc_index_add_obs(index_, n, row_begin.data(), obs.data(), rows(desc), need_flags, opt(a.id_base), with_points ? 1 : 0, opt(a.cam_to_map), opt(a.tags),
+                                         r.first_row.data(), r.n_added.data()));
+        return r;
+    }
+    svo_desc_insert_stats insert_stats() const { svo_desc_insert_stats s; svo_throw(svo_desc_index_get_insert_stats(index_, &s)); return s; }
     int retire_slab_rows() const { return svo_desc_index_get_retire_slab_rows(index_); }
     void retire_slab_rows(int rows) { svo_throw(svo_desc_index_set_retire_slab_rows(index_, rows)); }   // 0: the default
     int size() const { return svo_desc_index_size(index_); }
@@ -785,6 +818,13 @@ class DescriptorIndex {
    private:
     // the rows of a possibly empty descriptor vector
     static const uint8_t* rows(const std::vector<Descriptor>& d) { return d.empty() ? nullptr : d[0].data(); }
+    // an optional per-entry array of a batched insertion, and their sizes against the entries
+    template <typename T> static const T* opt(const std::vector<T>& v) { return v.empty() ? nullptr : v.data(); }
+    static void insert_sizes(const char* what, int n, const InsertArgs& a) {
+        const size_t m = (size_t)(n > 0 ? n : 0);
+        if ((!a.id_base.empty() && a.id_base.size() != m) || (!a.cam_to_map.empty() && a.cam_to_map.size() != 16 * m) || (!a.tags.empty() && a.tags.size() != m))
+            throw std::runtime_error(std::string("DescriptorIndex::") + what + ": id_base, cam_to_map (16 each) and tags hold one per entry, or nothing");
+    }
     // the rows of a span as the library will resolve it (0 for one it will refuse), and the room for its pairs
     size_t span_rows(int lo, int hi) const { const int h = hi == -1 || hi > size() ? size() : hi; return lo >= 0 && h > lo ? (size_t)(h - lo) : 0; }
     Pairs pairs_room(const svo_align_params& prm, bool inlier) const {

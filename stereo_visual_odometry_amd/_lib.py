@@ -169,6 +169,14 @@ class SvoConsolidateResult(C.Structure):
 CONSOLIDATE_MAX_VIEWS = 64
 
 
+class SvoDescInsertStats(C.Structure):
+    _fields_ = [("last_kernels_ms", C.c_float), ("last_path", C.c_int32), ("rows_scanned", C.c_uint64), ("rows_added", C.c_uint64)]
+
+
+INSERT_MAX_ENTRIES, INSERT_MAX_OBS_ROWS = 1024, 1 << 18
+INSERT_PATH_NONE, INSERT_PATH_RING, INSERT_PATH_STAGED = 0, 1, 2
+
+
 class SvoRetireRule(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("row_lo", C.c_int32), ("row_hi", C.c_int32), ("tag_lo", C.c_int32), ("tag_hi", C.c_int32),
                 ("n_ids", C.c_int32), ("ids", C.c_void_p)]
@@ -245,6 +253,10 @@ PROTOTYPES = {
     "svo_desc_index_get_retire_stats": (I, (P, P)),
     "svo_desc_index_localize_batch": (I, (P, I, P, P, P, P, P, P, P, P, P, P)),
     "svo_desc_index_get_batch_order": (I, (P, I, P, P)),
+    "svo_desc_index_add_frames": (I, (P, P, I, P, U32, P, P, P)),
+    "svo_desc_index_add_frames_points": (I, (P, P, I, P, U32, P, P, P, P, P)),
+    "svo_desc_index_add_obs": (I, (P, I, P, P, P, U32, P, I, P, P, P, P)),
+    "svo_desc_index_get_insert_stats": (I, (P, P)),
     "svo_align_params_default": (None, (P, F)),
     "svo_align_sample": (I, (U32, I32, P)),
     "svo_desc_index_match_rows": (I, (P, I, I, I, I, P)),

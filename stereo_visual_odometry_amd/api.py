@@ -872,6 +872,72 @@ class DescriptorIndex:
         check(lib.svo_desc_index_read_rows(self._h, int(rows[0]), int(rows[1]), *(ptr(a) for a in got)))
         return tuple(got)
 
+    # ---- batched insertion (svo.h, "Batched insertion"): many sequences' frames, or the caller's own rows, in one call
+    @staticmethod
+    def _insert_args(n, id_base, cam_to_map, tags):
+        """the per-entry arrays of a batched insertion, each None or n entries long"""
+        base = None if id_base is None else np.ascontiguousarray(id_base).astype(np.uint64, copy=False).reshape(-1)
+        T = None if cam_to_map is None else np.ascontiguousarray(cam_to_map, np.float64).reshape(-1, 16)
+        t = None if tags is None else np.ascontiguousarray(tags, np.int32).reshape(-1)
+        for a, what in ((base, "id_base"), (T, "cam_to_map"), (t, "tags")):
+            if a is not None and len(a) != n:
+                raise ValueError("%s: one per entry expected (%d, got %d)" % (what, n, len(a)))
+        return base, T, t
+
+    def _add_frames(self, vo, points, seqs, need_flags, id_base, cam_to_map, tags):
+        h = self._frame_handle(vo, "add_frames_points" if points else "add_frames")
+        s = None if seqs is None else np.ascontiguousarray(seqs, np.int32).reshape(-1)
+        n = len(s) if s is not None else int(vo.n_seq)
+        base, T, t = self._insert_args(n, id_base, cam_to_map, tags)
+        first, added = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        if points:
+            check(lib.svo_desc_index_add_frames_points(self._h, h, n, ptr(s), int(need_flags), ptr(base), ptr(T), ptr(t), ptr(first), ptr(added)))
+        else:
+            check(lib.svo_desc_index_add_frames(self._h, h, n, ptr(s), int(need_flags), ptr(base), ptr(first), ptr(added)))
+        return first, added
+
+    def add_frames(self, vo, seqs=None, need_flags=_lib.OBS_INLIER, id_base=None):
+        """add_frame for many sequences of vo's last collected frame in one call, filtered and packed on the device
+        (svo_desc_index_add_frames) -> (first_row, n_added), (n,) int32 each.  seqs: the entries' sequences (None: every sequence of
+        vo, in order); id_base (n,) uint64: added to entry b's track ids modulo 2**64 (None: zeros) — seq << 48 keeps the
+        sequences' ids apart."""
+        return self._add_frames(vo, False, seqs, need_flags, id_base, None, None)
+
+    def add_frames_points(self, vo, cam_to_map=None, tags=None, seqs=None, need_flags=_lib.OBS_INLIER, id_base=None):
+        """add_frames with each row's point moved into the map through its entry's cam_to_map ((n, 4, 4) float64; None: as it is)
+        and tagged tags[b] >= 0 (None: zeros) -> (first_row, n_added)."""
+        return self._add_frames(vo, True, seqs, need_flags, id_base, cam_to_map, tags)
+
+    def add_obs(self, obs_list, desc_list, need_flags=_lib.OBS_INLIER, id_base=None, with_points=False, cam_to_map=None, tags=None):
+        """The same stage on the caller's own rows (svo_desc_index_add_obs): entry b is obs_list[b] (TRACK_OBS_DTYPE rows) with
+        desc_list[b] ((rows, 32) uint8) -> (first_row, n_added)."""
+        n = len(obs_list)
+        if len(desc_list) != n:
+            raise ValueError("one descriptor block per observation block expected")
+        obs = [np.ascontiguousarray(o, _lib.TRACK_OBS_DTYPE).reshape(-1) for o in obs_list]
+        desc = [self._rows(d, "desc") if len(d) else np.zeros((0, _lib.DESC_BYTES), np.uint8) for d in desc_list]
+        if any(len(o) != len(d) for o, d in zip(obs, desc)):
+            raise ValueError("one descriptor row per observation row expected")
+        begin = np.zeros(n + 1, np.int64)
+        begin[1:] = np.cumsum([len(o) for o in obs])
+        if begin[-1] >= 1 << 31:
+            raise ValueError("too many rows")
+        all_obs = np.concatenate(obs) if n else np.zeros(0, _lib.TRACK_OBS_DTYPE)
+        all_desc = np.ascontiguousarray(np.concatenate(desc)) if n else np.zeros((0, _lib.DESC_BYTES), np.uint8)
+        base, T, t = self._insert_args(n, id_base, cam_to_map, tags)
+        first, added = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        begin32 = begin.astype(np.int32)
+        check(lib.svo_desc_index_add_obs(self._h, n, ptr(begin32), ptr(all_obs), ptr(all_desc), int(need_flags), ptr(base),
+                                         int(bool(with_points)), ptr(T), ptr(t), ptr(first), ptr(added)))
+        return first, added
+
+    def insert_stats(self):
+        """diagnostics of the last batched insertion (svo_desc_index_get_insert_stats) -> dict: last_kernels_ms (0 unless
+        set_timing), last_path (INSERT_PATH_*), rows_scanned, rows_added"""
+        st = _lib.SvoDescInsertStats()
+        check(lib.svo_desc_index_get_insert_stats(self._h, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in st._fields_}
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             lib.svo_desc_index_destroy(self._h)

@@ -1401,6 +1401,21 @@ extern "C" int svo_get_last_track_descriptors(svo_context* c, int seq, int cap, 
     return copy_last_rows(lr, lr.desc, SVO_DESC_BYTES, seq, cap, desc, n_tracks);
 }
 
+// the same rows where they lie, for the index's batched insertion (svo_internal.hpp)
+int svo_last_rows_view(svo_context* c, SvoLastRowsView* v) {
+    if (!c || !v) return fail_arg("bad context");
+    *v = SvoLastRowsView{};
+    v->B = c->d.B; v->device = c->device;
+    const LastFrame& l = c->last;
+    v->track_on = l.slot >= 0 && l.fs.track_on; v->desc_on = l.slot >= 0 && l.fs.desc();
+    if (!v->desc_on) { g_err = "the last collected frame was issued with the descriptor output off (or none was collected yet)"; return SVO_ERR_STATE; }
+    const LastRows lr = last_rows(c);
+    v->hdr = lr.hdr; v->obs_h = lr.obs; v->desc_h = lr.desc; v->pitch = lr.pitch;
+    v->in_ring = l.obs_slot >= 0;
+    if (v->in_ring) { v->obs_m = c->obs.mapped_row(l.obs_slot); v->desc_m = c->desc.mapped_row(l.obs_slot); }
+    return SVO_OK;
+}
+
 extern "C" int svo_get_feature_ids(svo_context* c, int seq, int cap, int64_t* ids) {
     if (!c || seq < 0 || seq >= c->d.B || cap < 0) return fail_arg("bad context / seq / cap");
     if (!c->next.track_on) { g_err = "svo_get_feature_ids with the track output off"; return SVO_ERR_STATE; }

@@ -408,3 +408,19 @@ static __device__ inline void pnp_draw_first_chunk_wave(const DevBuffers& d, Seq
         s.pnp_rng = state;
     }
 }
+
+// The last collected frame's observation and descriptor rows as the descriptor index's batched insertion reads them (svo_api.hip;
+// for svo_match_api.hip, not exported through include/svo.h).  hdr: {n_tracks, n_rows} per sequence; the rows of sequence i begin at
+// row i * pitch of obs and desc.  in_ring: the rows are still in their slot of the host-mapped rings and obs_m, desc_m are that
+// slot's device addresses on `device`; otherwise they are in the context's kept copies (plain host memory) and obs_m, desc_m are null.
+// desc_h and desc_m are null when the frame had no descriptor rows.  B and device are filled for every context; the return is
+// SVO_ERR_ARG for a null context, SVO_ERR_STATE exactly where svo_get_last_track_descriptors gives it, else SVO_OK.
+struct SvoLastRowsView {
+    int B, device;
+    bool track_on, desc_on, in_ring;
+    const int* hdr;
+    const svo_track_obs *obs_h, *obs_m;
+    const uint8_t *desc_h, *desc_m;
+    size_t pitch;
+};
+int svo_last_rows_view(svo_context* c, SvoLastRowsView* v);

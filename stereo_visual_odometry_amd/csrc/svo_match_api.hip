@@ -34,6 +34,12 @@
 // The consolidation (include/svo.h, "Landmark consolidation"; the kernels are in svo_kernels_consolidate.hip, the rules in
 // svo_consolidate.hpp): consolidate is a retire whose keep flags come from launch_consolidate, which also rewrites each group's latest
 // row; the ranks, the two waits and the move of the rows (retire_move_rows) are retire's.  read_rows is index_add's staging run downwards.
+//
+// The batched insertion (include/svo.h, "Batched insertion"; the kernels are in svo_kernels_insert.hip, the rules in svo_insert.hpp):
+// add_frames and add_frames_points settle their refusals and the entries' rows from the context's last-frame view
+// (svo_last_rows_view), then insert_group puts the entries up, runs the three kernels over the ring slot in place — or, group by
+// group, over rows staged through a pinned buffer (insert_staged, which is all of add_obs) — brings the counts and the flags back and
+// waits; size moves once, at the end.  The working memory is the retire scratch.  The single calls (add_frame_rows) are untouched.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
 #include "svo_reloc_batch_internal.hpp"
@@ -41,6 +47,7 @@
 #include "svo_fuse_internal.hpp"
 #include "svo_place_internal.hpp"
 #include "svo_consolidate_internal.hpp"
+#include "svo_insert_internal.hpp"
 #include <algorithm>
 #include <math.h>
 #include <stddef.h>
@@ -122,6 +129,13 @@ struct svo_desc_index {
     uint8_t* h_place = nullptr;                       // pinned, [place_host_cap] bytes: a PlaceCtl, then tag_votes' bins; grows by doubling
     size_t place_host_cap = 0;
     bool place_combine = true;                        // svo_desc_index_set_place_combine
+    // batched insertion: null until the first add_frames, add_frames_points or add_obs (insert_host_room, insert_rows_room); the device side lives in d_retire
+    uint8_t* h_insert = nullptr;                      // pinned: the entries and transforms going up, then (at INSERT_HOST_DOWN) the control block and the counts coming down
+    uint8_t* h_insert_rows = nullptr;                 // pinned, [insert_rows_cap] bytes: a staged group's observation rows, then its descriptor rows; grows by doubling
+    size_t insert_rows_cap = 0;
+    float insert_ms = 0.f;                            // the last batched insertion's kernels, with timing on
+    int insert_path = 0;                              // SVO_INSERT_PATH_* of the last batched insertion
+    uint64_t insert_scanned = 0, insert_added = 0;
 };
 
 // k_reloc_select's result lists, on the device and in the pinned block: the count and the queries lead, so that one copy takes both
@@ -149,6 +163,7 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
         svo_destroy(x->batch_ctx);
         (void)hipFree(x->d_batch); (void)hipHostFree(x->h_batch); (void)hipHostFree(x->h_batch_st);
         (void)hipFree(x->d_align); (void)hipHostFree(x->h_align); (void)hipHostFree(x->h_fuse); (void)hipHostFree(x->h_place);
+        (void)hipHostFree(x->h_insert); (void)hipHostFree(x->h_insert_rows);
         (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
         (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
         (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
@@ -1537,5 +1552,204 @@ extern "C" int svo_desc_index_read_rows(svo_desc_index* x, int row_lo, int row_h
             if (xyz) { xyz[3 * (to + i)] = none ? INFINITY : pt.x; xyz[3 * (to + i) + 1] = none ? INFINITY : pt.y; xyz[3 * (to + i) + 2] = none ? INFINITY : pt.z; }
         }
     }
+    return SVO_OK;
+}
+
+// ---- batched insertion (include/svo.h, "Batched insertion") ----
+#define INSERT_STAGE_FIRST ((size_t)1 << 16)          // the row staging's first size in bytes; it doubles from there
+static const size_t INSERT_HOST_DOWN = insert_layout(INSERT_MAX_ENTRIES, 0, 0).up_end;   // where h_insert keeps what comes down
+static_assert(sizeof(InsertEntry) == 32 && sizeof(InsertCtl) == 64, "the entry and the control block as the kernels read them");
+static_assert(sizeof(svo_track_obs) == INSERT_OBS_BYTES && offsetof(svo_track_obs, id) == INSERT_OBS_ID && offsetof(svo_track_obs, xyz) == INSERT_OBS_XYZ &&
+              offsetof(svo_track_obs, flags) == INSERT_OBS_FLAGS && SVO_DESC_BYTES == INSERT_DESC_BYTES && SVO_OBS_HAS_XYZ == INSERT_HAS_XYZ &&
+              SVO_INSERT_MAX_ENTRIES == INSERT_MAX_ENTRIES && SVO_INSERT_MAX_OBS_ROWS == INSERT_MAX_OBS_ROWS, "svo_insert.hpp restates include/svo.h");
+
+// what a call asks for beyond its entries: per-entry arrays indexed by the call's entry number, each may be null
+struct InsertCall { uint32_t need; bool with_points; const uint64_t* id_base; const double* cam_to_map; const int32_t* tags; };
+
+static int insert_host_room(svo_desc_index* x) {
+    if (x->h_insert) return SVO_OK;
+    const InsertLayout l = insert_layout(INSERT_MAX_ENTRIES, 0, 0);
+    MHIP(hipHostMalloc((void**)&x->h_insert, INSERT_HOST_DOWN + (l.down_end - l.down), hipHostMallocDefault));
+    return SVO_OK;
+}
+
+// room for `need` bytes of staged rows: part_room's pattern, the outgrown blocks freed with the index
+static int insert_rows_room(svo_desc_index* x, size_t need) {
+    if (need <= x->insert_rows_cap) return SVO_OK;
+    size_t cap = x->insert_rows_cap ? 2 * x->insert_rows_cap : INSERT_STAGE_FIRST;
+    while (cap < need) cap *= 2;
+    uint8_t* p = nullptr;
+    MHIP(hipHostMalloc((void**)&p, cap, hipHostMallocDefault));
+    if (x->h_insert_rows) x->outgrown_pinned.push_back(x->h_insert_rows);
+    x->h_insert_rows = p; x->insert_rows_cap = cap;
+    return SVO_OK;
+}
+
+// the refusals every batched insertion shares (rules 6 and 7, the part that needs no rows)
+static int insert_check(const svo_desc_index* x, int n, const InsertCall& c) {
+    if (c.with_points && !x->d_points) return fail(SVO_ERR_STATE, "batched insertion with points: the index has no points (svo_desc_index_enable_points)");
+    for (int b = 0; b < n && c.tags; b++) if (c.tags[b] < 0) return fail(SVO_ERR_ARG, "batched insertion: a tag must be >= 0 (nothing was added)");
+    for (size_t i = 0; c.cam_to_map && i < (size_t)16 * n; i++)
+        if (!isfinite(c.cam_to_map[i])) return fail(SVO_ERR_ARG, "batched insertion: cam_to_map has a non-finite entry (nothing was added)");
+    return SVO_OK;
+}
+
+// entry k of a group of n_group entries, entry b of the call, into the pinned block: its rows, its tag, its id offset, its transform
+static void insert_entry_fill(svo_desc_index* x, int n_group, int k, int b, int32_t begin, int32_t rows, const InsertCall& c) {
+    ((InsertEntry*)x->h_insert)[k] = InsertEntry{begin, rows, 0, c.tags ? c.tags[b] : 0, c.id_base ? c.id_base[b] : 0, 0};
+    if (c.cam_to_map) memcpy(x->h_insert + insert_layout(n_group, 0, 0).T + (size_t)k * 12 * sizeof(double), c.cam_to_map + (size_t)16 * b, 12 * sizeof(double));
+}
+
+// One group of n entries, filled in the pinned block (insert_entry_fill): the entries up, the kernels, the counts and flags down, one
+// wait.  The rows are read at obs, desc (device addresses: the ring slot) or, with staged_rows > 0, from h_insert_rows through the
+// scratch.  The kept rows go to rows at + 0 ..; n_added[0 .. n), *total.  Rule 6's refusals that only the device sees end it here.
+static int insert_group(svo_desc_index* x, int n, const InsertCall& c, const uint8_t* obs, const uint8_t* desc, int staged_rows, int at,
+                        int32_t* n_added, int* total) {
+    const int tiles = insert_plan(n, (InsertEntry*)x->h_insert);
+    *total = 0;
+    if (tiles == 0) { memset(n_added, 0, sizeof(int32_t) * (size_t)n); return SVO_OK; }
+    const InsertLayout l = insert_layout(n, tiles, staged_rows);
+    if (const int rc = retire_room(x, l.total); rc != SVO_OK) return rc;
+    uint8_t* d = x->d_retire;
+    if (staged_rows > 0) {
+        MHIP(hipMemcpyAsync(d + l.obs, x->h_insert_rows, (size_t)staged_rows * INSERT_OBS_BYTES, hipMemcpyHostToDevice, x->stream));
+        MHIP(hipMemcpyAsync(d + l.desc, x->h_insert_rows + (size_t)staged_rows * INSERT_OBS_BYTES, (size_t)staged_rows * INSERT_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
+        obs = d + l.obs; desc = d + l.desc;
+    }
+    MHIP(hipMemcpyAsync(d, x->h_insert, c.cam_to_map ? l.up_end : l.T, hipMemcpyHostToDevice, x->stream));
+    InsertWork w;
+    w.obs = obs; w.desc = desc;
+    w.entry = (const InsertEntry*)(d + l.entry); w.T = c.cam_to_map ? (const double*)(d + l.T) : nullptr;
+    w.n = n; w.tiles = tiles;
+    w.mask = (uint64_t*)(d + l.mask); w.offset = (int32_t*)(d + l.offset);
+    w.ctl = (InsertCtl*)(d + l.down); w.n_added = (int32_t*)(d + l.n_added);
+    w.need = c.need; w.with_points = c.with_points ? 1 : 0;
+    w.at = at; w.room = x->capacity - at;
+    const bool timed = x->timing;
+    if (timed) MHIP(hipEventRecord(x->ev[0], x->stream));
+    launch_insert(InsertRows{x->d_desc, x->d_ids, (uint4*)x->d_points}, w, x->stream);
+    MHIP(hipGetLastError());
+    if (timed) MHIP(hipEventRecord(x->ev[1], x->stream));
+    uint8_t* down = x->h_insert + INSERT_HOST_DOWN;
+    MHIP(hipMemcpyAsync(down, d + l.down, sizeof(InsertCtl) + sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));
+    if (timed) { float ms = 0.f; MHIP(hipEventElapsedTime(&ms, x->ev[0], x->ev[1])); x->insert_ms += ms; }
+    const InsertCtl* ctl = (const InsertCtl*)down;
+    if (ctl->over) return fail(SVO_ERR_ARG, "batched insertion: the kept rows exceed the index's capacity (nothing was added)");
+    if (ctl->nonfinite) return fail(SVO_ERR_ARG, "batched insertion: a kept row's point has a non-finite coordinate (nothing was added)");
+    memcpy(n_added, down + sizeof(InsertCtl), sizeof(int32_t) * (size_t)n);
+    *total = ctl->total;
+    return SVO_OK;
+}
+
+// the call's begin and end around its groups
+static int insert_begin(svo_desc_index* x, int path) {
+    MHIP(call_begin(x));
+    x->insert_ms = 0.f; x->insert_path = path; x->insert_scanned = x->insert_added = 0;
+    return insert_host_room(x);
+}
+static void insert_end(svo_desc_index* x, int n, const int32_t* counts, int total, int32_t* first_row, int32_t* n_added) {
+    int32_t at = x->size;
+    for (int b = 0; b < n; b++) {
+        if (first_row) first_row[b] = at;
+        if (n_added) n_added[b] = counts[b];
+        at += counts[b];
+    }
+    x->size += total;                                 // the one place size moves
+    x->insert_added = (uint64_t)total;
+}
+
+// Entries whose rows are in host memory — entry b has rows[b] rows from row begin[b] of obs and desc — through the row staging in
+// groups of whole entries of at most INSERT_MAX_OBS_ROWS rows (an entry has at most that many).  counts: n entries; *total.
+static int insert_staged(svo_desc_index* x, int n, const int64_t* begin, const int32_t* rows, const uint8_t* obs, const uint8_t* desc,
+                         const InsertCall& c, int32_t* counts, int* total) {
+    *total = 0;
+    for (int g0 = 0; g0 < n;) {
+        int g1 = g0; int32_t m = 0;
+        while (g1 < n && (g1 == g0 || m + rows[g1] <= INSERT_MAX_OBS_ROWS)) m += rows[g1++];
+        if (const int rc = insert_rows_room(x, (size_t)m * (INSERT_OBS_BYTES + INSERT_DESC_BYTES)); rc != SVO_OK) return rc;
+        for (int b = g0, at = 0; b < g1; at += rows[b], b++) {
+            insert_entry_fill(x, g1 - g0, b - g0, b, at, rows[b], c);
+            if (rows[b] == 0) continue;
+            memcpy(x->h_insert_rows + (size_t)at * INSERT_OBS_BYTES, obs + (size_t)begin[b] * INSERT_OBS_BYTES, (size_t)rows[b] * INSERT_OBS_BYTES);
+            memcpy(x->h_insert_rows + (size_t)m * INSERT_OBS_BYTES + (size_t)at * INSERT_DESC_BYTES, desc + (size_t)begin[b] * INSERT_DESC_BYTES, (size_t)rows[b] * INSERT_DESC_BYTES);
+        }
+        int added = 0;
+        if (const int rc = insert_group(x, g1 - g0, c, nullptr, nullptr, m, x->size + *total, counts + g0, &added); rc != SVO_OK) return rc;
+        *total += added; x->insert_scanned += (uint64_t)m;
+        g0 = g1;
+    }
+    return SVO_OK;
+}
+
+// svo_desc_index_add_frames (with_points false) and svo_desc_index_add_frames_points
+static int add_frames_run(svo_desc_index* x, svo_context* ctx, int n, const int32_t* seqs, const InsertCall& c, int32_t* first_row, int32_t* n_added) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (n < 1 || n > INSERT_MAX_ENTRIES) return fail(SVO_ERR_ARG, "batched insertion: n must be 1 .. 1024 entries");
+    int rc = insert_check(x, n, c);
+    if (rc != SVO_OK) return rc;
+    SvoLastRowsView v;
+    const int state = svo_last_rows_view(ctx, &v);    // a null context; the frame's state comes after the entries' sequences, as in the single call
+    if (state == SVO_ERR_ARG) return state;
+    for (int b = 0; b < n; b++) { const int s = seqs ? seqs[b] : b; if (s < 0 || s >= v.B) return fail(SVO_ERR_ARG, "batched insertion: an entry's sequence is outside the context"); }
+    if (state != SVO_OK) return state;
+    const bool ring = v.in_ring && v.device == x->device;
+    if ((rc = insert_begin(x, ring ? SVO_INSERT_PATH_RING : SVO_INSERT_PATH_STAGED)) != SVO_OK) return rc;
+    std::vector<int32_t> rows((size_t)n), counts((size_t)n);
+    std::vector<int64_t> begin((size_t)n);
+    for (int b = 0; b < n; b++) {                     // the rows the single call scans: min(n_rows, max(n_tracks, 0)), inside the pitch
+        const int s = seqs ? seqs[b] : b, cap = v.hdr[2 * s] > 0 ? v.hdr[2 * s] : 0;
+        int32_t r = v.hdr[2 * s + 1] < cap ? v.hdr[2 * s + 1] : cap;
+        if (r < 0) r = 0;
+        if ((size_t)r > v.pitch) r = (int32_t)v.pitch;
+        rows[(size_t)b] = r; begin[(size_t)b] = (int64_t)s * (int64_t)v.pitch;
+    }
+    int total = 0;
+    if (ring) {
+        for (int b = 0; b < n; b++) { insert_entry_fill(x, n, b, b, (int32_t)begin[(size_t)b], rows[(size_t)b], c); x->insert_scanned += (uint64_t)rows[(size_t)b]; }
+        rc = insert_group(x, n, c, (const uint8_t*)v.obs_m, v.desc_m, 0, x->size, counts.data(), &total);
+    } else {
+        rc = insert_staged(x, n, begin.data(), rows.data(), (const uint8_t*)v.obs_h, v.desc_h, c, counts.data(), &total);
+    }
+    if (rc != SVO_OK) return rc;
+    insert_end(x, n, counts.data(), total, first_row, n_added);
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_add_frames(svo_desc_index* x, svo_context* ctx, int n, const int32_t* seqs, uint32_t need_flags, const uint64_t* id_base,
+                                         int32_t* first_row, int32_t* n_added) {
+    return add_frames_run(x, ctx, n, seqs, InsertCall{insert_need(need_flags, false), false, id_base, nullptr, nullptr}, first_row, n_added);
+}
+
+extern "C" int svo_desc_index_add_frames_points(svo_desc_index* x, svo_context* ctx, int n, const int32_t* seqs, uint32_t need_flags, const uint64_t* id_base,
+                                                const double* cam_to_map, const int32_t* tags, int32_t* first_row, int32_t* n_added) {
+    return add_frames_run(x, ctx, n, seqs, InsertCall{insert_need(need_flags, true), true, id_base, cam_to_map, tags}, first_row, n_added);
+}
+
+extern "C" int svo_desc_index_add_obs(svo_desc_index* x, int n, const int32_t* row_begin, const svo_track_obs* obs, const uint8_t* desc, uint32_t need_flags,
+                                      const uint64_t* id_base, int with_points, const double* cam_to_map, const int32_t* tags, int32_t* first_row, int32_t* n_added) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (n < 0 || n > INSERT_MAX_ENTRIES || (n > 0 && !row_begin)) return fail(SVO_ERR_ARG, "svo_desc_index_add_obs: n must be 0 .. 1024 entries, with their row_begin");
+    if (n == 0) return SVO_OK;
+    if (row_begin[0] != 0) return fail(SVO_ERR_ARG, "svo_desc_index_add_obs: row_begin[0] must be 0");
+    for (int b = 0; b < n; b++) if (row_begin[b + 1] < row_begin[b]) return fail(SVO_ERR_ARG, "svo_desc_index_add_obs: row_begin must not decrease");
+    if (row_begin[n] > INSERT_MAX_OBS_ROWS) return fail(SVO_ERR_ARG, "svo_desc_index_add_obs: at most 1 << 18 rows per call");
+    if (row_begin[n] > 0 && (!obs || !desc)) return fail(SVO_ERR_ARG, "svo_desc_index_add_obs: null obs / desc");
+    const InsertCall c{insert_need(need_flags, with_points != 0), with_points != 0, id_base, with_points ? cam_to_map : nullptr, with_points ? tags : nullptr};
+    int rc = insert_check(x, n, c);
+    if (rc != SVO_OK || (rc = insert_begin(x, SVO_INSERT_PATH_STAGED)) != SVO_OK) return rc;
+    std::vector<int32_t> rows((size_t)n), counts((size_t)n);
+    std::vector<int64_t> begin((size_t)n);
+    for (int b = 0; b < n; b++) { begin[(size_t)b] = row_begin[b]; rows[(size_t)b] = row_begin[b + 1] - row_begin[b]; }
+    int total = 0;
+    if ((rc = insert_staged(x, n, begin.data(), rows.data(), (const uint8_t*)obs, desc, c, counts.data(), &total)) != SVO_OK) return rc;
+    insert_end(x, n, counts.data(), total, first_row, n_added);
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_get_insert_stats(const svo_desc_index* x, svo_desc_insert_stats* st) {
+    if (!x || !st) return fail(SVO_ERR_ARG, "null index / stats");
+    st->last_kernels_ms = x->insert_ms; st->last_path = x->insert_path;
+    st->rows_scanned = x->insert_scanned; st->rows_added = x->insert_added;
     return SVO_OK;
 }

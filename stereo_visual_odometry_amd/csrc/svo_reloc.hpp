@@ -37,7 +37,7 @@ SVO_RELOC_HD static inline bool reloc_loses(uint64_t id_a, uint32_t key_a, uint6
 // The transform of svo_desc_index_add_frame_points: a point p of the T0 left camera frame into the map through T (4 x 4, row-major,
 // the pose of that camera in the map).  Per coordinate f32(T[4r] x + T[4r+1] y + T[4r+2] z + T[4r+3]) in f64, left to right; the
 // translation units that include this are built without contraction (-ffp-contract=off), so no product fuses with a sum.
-static inline void reloc_map_point(const double T[16], const float p[3], float out[3]) {
+SVO_RELOC_HD static inline void reloc_map_point(const double T[16], const float p[3], float out[3]) {
     for (int r = 0; r < 3; r++) {
         double v = T[4 * r] * (double)p[0];
         v = v + T[4 * r + 1] * (double)p[1];
