@@ -63,3 +63,15 @@ SVO_MATCH_HD static inline MatchState match_merge(const MatchState& a, const Mat
     const match_key other = a.id1 != b.id1 ? l_k1 : l_k2;
     return MatchState{w_k1, other < w_k2 ? other : w_k2, w_id1};
 }
+
+// ---- the capacity rule of the index's growable buffers (svo_match_api.hip: grow), host only.  A buffer of `cap` units that must
+// hold `need`: it never shrinks; when it grows it doubles from `first` (from twice its size, once it has one) until the need fits, so
+// a buffer allocates O(log) times and the ones it has outgrown sum to less than the one in use; up to `clamp` (0: none) the
+// doubling stops at the clamp.  So need <= capacity < max(2 * need, first + 1) for the largest need so far.
+#include <stddef.h>
+static inline size_t match_grow_capacity(size_t cap, size_t need, size_t first, size_t clamp) {
+    if (need <= cap) return cap;
+    size_t c = cap ? 2 * cap : first;
+    while (c < need) c *= 2;
+    return clamp && need <= clamp && c > clamp ? clamp : c;
+}

@@ -1,45 +1,41 @@
-// svo_match_api.hip — host side of the descriptor index (include/svo.h, "Descriptor index", "Relocalisation", "Guided search"): the
-// index object, the append copies, the search and the C-ABI.  An index owns one non-blocking stream and its own pinned staging; every
-// call waits for that stream alone, so it is legal beside any context's frames in flight.
+// svo_match_api.hip — host side of the descriptor index (include/svo.h, "Descriptor index" to "Batched insertion"): the index object,
+// the append copies, the search and the C-ABI.  An index owns one non-blocking stream and its own pinned staging; every call waits
+// for that stream alone, so it is legal beside any context's frames in flight.
 //
-// Every searching call goes one way: row_range settles the rows, search_plan the launch geometry and its room, stage_queries puts up
-// to MATCH_STAGE_ROWS queries and their pixels on the device, and search_enqueue puts the search on the stream — k_desc_match or, with
-// a guide, k_guide_project and k_desc_match_guided, then k_desc_match_merge — and leaves d_out[0 .. n) without waiting.  match and
-// match_guided copy that back stage by stage; reloc_run, behind select and localize with or without a guide, puts k_reloc_select and
-// the RANSAC-PnP kernels behind it and waits once.
-// Timing (svo_desc_index_set_timing): a call marks the one span it times — its search, its selection or its projection — and reads
-// it into last_ms after its wait.  match times one span per stage, around all of the stage's launches, and sums over its stages.
+// Memory: every block of an index, device or pinned, comes from index_block, which records it; svo_desc_index_destroy frees what is
+// recorded and nothing is freed before (hipFree waits for the whole device).  An allocate-once pointer takes its block through room,
+// a buffer that grows — the partial states, the maintenance scratch, the pinned blocks of places and of staged rows — through grow,
+// by the capacity rule of svo_match.hpp; the batch's staging keeps its own rule (rb_grow).
+// Timing (svo_desc_index_set_timing): a call marks the one span it times (span_mark) and reads it after its wait (span_read) into its
+// figure: last_ms, the maintenance calls' retire_ms, the batched insertion's insert_ms.  match times one span per stage and sums.
 //
-// Maintenance (include/svo.h, "Index maintenance"; the kernels are in svo_kernels_retire.hip): retire settles the scope, sorts the
-// id list, takes room in a scratch of its own (retire_room), puts the flags, the table and the ranks on the stream and waits for the
-// count of kept rows and the table's flag; only then do rows move, slab by slab through the bounce buffer, and a second wait ends
-// the call.  transform_points is one launch and one wait.  Both time their kernels into retire_ms, apart from last_ms.
+// The search: row_range settles the rows, search_plan the launch geometry and its room, stage_queries puts up to MATCH_STAGE_ROWS
+// queries and their pixels on the device, and search_enqueue puts the search on the stream — k_desc_match, or with a guide
+// k_guide_project and k_desc_match_guided, or for a near plan k_desc_match_near, then k_desc_match_merge — and leaves d_out[0 .. n)
+// without waiting.  rows_down ends a call, or a stage, that returns those rows: match, match_guided, match_rows, match_near.
 //
-// The batch (include/svo.h, "Batched relocalisation"; the kernels are in svo_kernels_reloc_batch.hip, the plan in svo_reloc_batch.hpp):
-// localize_batch is reloc_run for many cameras at once, with a staging (batch_room) and a PnP stage context of its own, both owned by
-// the index; the single calls' 4096-row staging and their path above are untouched by it.
+// Relocalisation: reloc_run, behind select and localize with or without a guide, puts the selection (select_enqueue) and the
+// RANSAC-PnP kernels behind the search, the candidate lists down (cands_down) and waits once.  localize_batch (the kernels are in
+// svo_kernels_reloc_batch.hip, the plan in svo_reloc_batch.hpp) is that for many cameras, with a staging (batch_room) and a PnP stage
+// context of its own; both share the parameters' refusals, the state row (reloc_state_row) and the reading of a camera (reloc_read).
 //
-// The alignment (include/svo.h, "Map alignment"; the kernels are in svo_kernels_align.hip, the rules in svo_align.hpp): align_run,
-// behind match_rows, pair_rows and align, is the same search with the index's own rows as its queries — nothing is staged — then
-// k_align_pairs, k_align_score and k_align_fit, one copy back and one wait.
+// The pair stage (pairs_enqueue, pairs_read) follows a search whose queries are rows of the index.  align_run, behind match_rows,
+// pair_rows and align (svo_kernels_align.hip, svo_align.hpp), adds k_align_score and k_align_fit; fuse_run, behind match_near,
+// pair_near and fuse (svo_kernels_fuse.hip, svo_fuse.hpp), searches near and adds k_fuse_map and the relabelling, which relabel runs
+// alone on host lists (fuse_begin puts either's lists, control block and table in place).  One copy back, or two, and one wait.
 //
-// The fusion (include/svo.h, "Landmark fusion"; the kernels are in svo_kernels_fuse.hip, the rules in svo_fuse.hpp): fuse_run, behind
-// match_near, pair_near and fuse, is k_desc_match_near and the merge over the unguided plan, then k_align_pairs, k_fuse_map,
-// k_fuse_insert and k_fuse_sweep, two copies back and one wait.  relabel puts its host lists where k_fuse_map would and runs the last two.
+// Place candidates (svo_kernels_place.hip, svo_place.hpp): place_run, behind tag_votes, places and places_from_ids, is — for places —
+// the unguided search and the selection, else the id list up (upload_list), then the sweep and the pick, the copies back, one wait.
 //
-// The place candidates (include/svo.h, "Place candidates"; the kernels are in svo_kernels_place.hip, the rules in svo_place.hpp):
-// place_run, behind tag_votes, places and places_from_ids, is — for places — the unguided search and k_reloc_select as select runs
-// them, then k_place_sweep over the ids and tags, k_place_compact and k_place_pick, the copies back and one wait.
+// Maintenance (svo_kernels_retire.hip, svo_kernels_consolidate.hip): retire puts its flags, table and ranks on the stream, consolidate
+// the group kernel and the ranks; retire_finish is the end of both — the first wait, before which nothing has moved, the ranks down,
+// the move of the rows slab by slab and the second wait, the map, size.  transform_points is one launch and one wait.  read_rows is
+// index_add's staging run downwards.
 //
-// The consolidation (include/svo.h, "Landmark consolidation"; the kernels are in svo_kernels_consolidate.hip, the rules in
-// svo_consolidate.hpp): consolidate is a retire whose keep flags come from launch_consolidate, which also rewrites each group's latest
-// row; the ranks, the two waits and the move of the rows (retire_move_rows) are retire's.  read_rows is index_add's staging run downwards.
-//
-// The batched insertion (include/svo.h, "Batched insertion"; the kernels are in svo_kernels_insert.hip, the rules in svo_insert.hpp):
-// add_frames and add_frames_points settle their refusals and the entries' rows from the context's last-frame view
-// (svo_last_rows_view), then insert_group puts the entries up, runs the three kernels over the ring slot in place — or, group by
-// group, over rows staged through a pinned buffer (insert_staged, which is all of add_obs) — brings the counts and the flags back and
-// waits; size moves once, at the end.  The working memory is the retire scratch.  The single calls (add_frame_rows) are untouched.
+// Batched insertion (svo_kernels_insert.hip, svo_insert.hpp): add_frames and add_frames_points settle their refusals and the
+// entries' rows from the context's last-frame view, then insert_group puts the entries up, runs the kernels over the ring slot in
+// place — or, group by group, over rows staged through a pinned buffer (insert_staged, which is all of add_obs) — brings the counts
+// and the flags back and waits; size moves once, at the end.  The single calls (add_frame_rows) are untouched.
 #include "svo_guide_internal.hpp"
 #include "svo_retire_internal.hpp"
 #include "svo_reloc_batch_internal.hpp"
@@ -72,10 +68,18 @@
     } while (0)
 
 static int fail(int rc, const char* msg) { svo_set_error(msg); return rc; }
+// the refusal of a call that needs points on an index without them, under the call's prefix (svo_set_error copies its argument)
+static int no_points(const char* prefix) {
+    char b[192];
+    snprintf(b, sizeof(b), "%s: the index has no points (svo_desc_index_enable_points)", prefix);
+    return fail(SVO_ERR_STATE, b);
+}
 
 struct RelocDevOut;
 struct RelocHost;
 struct RetireDown { RetireCtl ctl; int32_t kept, pad[3]; };   // a retire call reads ctl.table_full and kept, a transform the whole ctl
+// A buffer that grows by match_grow_capacity and never shrinks: its bytes, the bytes of the buffers it has outgrown, its allocations
+struct GrowBuf { uint8_t* p = nullptr; size_t cap = 0, outgrown = 0; int allocs = 0; };
 struct svo_desc_index {
     int device = 0, capacity = 0, size = 0, chunk_rows = MATCH_DEFAULT_CHUNK;
     hipStream_t stream = nullptr;
@@ -88,25 +92,22 @@ struct svo_desc_index {
     svo_desc_match* h_out = nullptr;                  // pinned: MATCH_STAGE_ROWS result rows
     uint8_t* d_query = nullptr;                       // [MATCH_STAGE_ROWS][32]
     svo_desc_match* d_out = nullptr;                  // [MATCH_STAGE_ROWS]
-    MatchPartial* d_part = nullptr;                   // [part_cap]: grows by doubling, never shrinks (part_room)
-    size_t part_cap = 0, outgrown_states = 0;
-    int part_allocs = 0;
-    std::vector<void*> outgrown;                      // earlier d_part buffers: hipFree waits for the whole device, so they go with the index
+    std::vector<void*> dev_blocks, pinned_blocks;     // every block the index has allocated (index_block), outgrown ones included: hipFree waits for the whole device, so all go with the index
+    GrowBuf part;                                     // the partial states of a search, as bytes (grow, PART_*)
+    MatchPartial* d_part() const { return (MatchPartial*)part.p; }
     // svo_desc_index_enable_points: all null without
     RelocPoint* d_points = nullptr;                   // [capacity]
     float2* d_qxy = nullptr;                          // [MATCH_STAGE_ROWS] the queries' pixels
     RelocDevOut* d_reloc = nullptr;                   // what k_reloc_select reports
     RelocHost* h_reloc = nullptr;                     // pinned: the point rows of an upload, a call's state row and everything it reads back
-    // the guided search: all null until the first guided call (guide_room)
+    // the guided search: null until the first guided call (guide_room)
     float2* d_uv = nullptr;                           // [capacity] the rows' projections of the call in progress
     int32_t* d_order = nullptr;                       // [MATCH_STAGE_ROWS] the query each lane slot serves
     int32_t* h_order = nullptr;                       // pinned, likewise
     bool guided_sort = true;                          // svo_desc_index_set_guided_sort
-    // index maintenance: all null until the first retire or transform_points (retire_ctl_room, retire_room)
+    // index maintenance: null until the first call that needs them (retire_ctl_room, grow)
     int retire_slab = RETIRE_DEFAULT_SLAB;            // svo_desc_index_set_retire_slab_rows
-    uint8_t* d_retire = nullptr;                      // [retire_cap] bytes, cut by retire_layout: grows by doubling like d_part
-    size_t retire_cap = 0, retire_outgrown = 0;
-    int retire_allocs = 0;
+    GrowBuf retire;                                   // the maintenance scratch, cut by retire_layout and the later features' layouts
     float retire_ms = 0.f;                            // the last maintenance call's kernels, with timing on
     RetireCtl* d_retire_ctl = nullptr;
     RetireDown* h_retire = nullptr;                   // pinned: what a call reads back before it decides
@@ -115,7 +116,6 @@ struct svo_desc_index {
     uint8_t* h_batch = nullptr;                       // pinned: its first down_end bytes, cut alike
     SeqState* h_batch_st = nullptr;                   // pinned: [2][batch_cams] the state rows going up, and as k_pnp_final left them
     size_t batch_cams = 0, batch_queries = 0;         // each at least doubles when it grows
-    std::vector<void*> outgrown_pinned;               // earlier pinned staging: freed with the index, like `outgrown`
     svo_context* batch_ctx = nullptr;                 // the PnP stage context of B sequences (svo_reloc_batch_ctx)
     std::vector<svo_context*> batch_ctx_outgrown;     // earlier ones, destroyed with the index
     int batch_last_cams = 0, batch_total = -1;                             // the last batch call's queries (-1: none yet), and whether d_batch holds its order
@@ -123,16 +123,14 @@ struct svo_desc_index {
     // map alignment: null until the first svo_desc_index_pair_rows or svo_desc_index_align (align_room)
     uint8_t* d_align = nullptr;                       // align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES)
     uint8_t* h_align = nullptr;                       // pinned: its first down_end bytes
-    // landmark fusion: null until the first pair_near, relabel or fuse (fuse_ctl_room); the lists and the table live in d_retire
+    // landmark fusion: null until the first pair_near, relabel or fuse (fuse_ctl_room); the lists and the table live in the maintenance scratch
     FuseCtl* h_fuse = nullptr;                        // pinned: what a call reads back
-    // place candidates: null until the first tag_votes, places or places_from_ids (place_host_room); the device side lives in d_retire
-    uint8_t* h_place = nullptr;                       // pinned, [place_host_cap] bytes: a PlaceCtl, then tag_votes' bins; grows by doubling
-    size_t place_host_cap = 0;
+    // place candidates: null until the first tag_votes, places or places_from_ids (grow); the device side lives in the maintenance scratch
+    GrowBuf place;                                    // pinned: a PlaceCtl, then tag_votes' bins
     bool place_combine = true;                        // svo_desc_index_set_place_combine
-    // batched insertion: null until the first add_frames, add_frames_points or add_obs (insert_host_room, insert_rows_room); the device side lives in d_retire
+    // batched insertion: null until the first add_frames, add_frames_points or add_obs (insert_host_room, grow); the device side lives in the maintenance scratch
     uint8_t* h_insert = nullptr;                      // pinned: the entries and transforms going up, then (at INSERT_HOST_DOWN) the control block and the counts coming down
-    uint8_t* h_insert_rows = nullptr;                 // pinned, [insert_rows_cap] bytes: a staged group's observation rows, then its descriptor rows; grows by doubling
-    size_t insert_rows_cap = 0;
+    GrowBuf insert_rows;                              // pinned: a staged group's observation rows, then its descriptor rows
     float insert_ms = 0.f;                            // the last batched insertion's kernels, with timing on
     int insert_path = 0;                              // SVO_INSERT_PATH_* of the last batched insertion
     uint64_t insert_scanned = 0, insert_added = 0;
@@ -156,34 +154,48 @@ extern "C" void svo_desc_index_destroy(svo_desc_index* x) {
     if (!x) return;
     if (hipSetDevice(x->device) == hipSuccess) {
         if (x->stream) (void)hipStreamSynchronize(x->stream);
-        for (hipEvent_t e : x->ev) if (e) (void)hipEventDestroy(e);
-        for (void* p : x->outgrown) (void)hipFree(p);
-        for (void* p : x->outgrown_pinned) (void)hipHostFree(p);
+        for (void* p : x->dev_blocks) (void)hipFree(p);
+        for (void* p : x->pinned_blocks) (void)hipHostFree(p);
         for (svo_context* c : x->batch_ctx_outgrown) svo_destroy(c);
         svo_destroy(x->batch_ctx);
-        (void)hipFree(x->d_batch); (void)hipHostFree(x->h_batch); (void)hipHostFree(x->h_batch_st);
-        (void)hipFree(x->d_align); (void)hipHostFree(x->h_align); (void)hipHostFree(x->h_fuse); (void)hipHostFree(x->h_place);
-        (void)hipHostFree(x->h_insert); (void)hipHostFree(x->h_insert_rows);
-        (void)hipFree(x->d_retire); (void)hipFree(x->d_retire_ctl); (void)hipHostFree(x->h_retire);
-        (void)hipFree(x->d_uv); (void)hipFree(x->d_order); (void)hipHostFree(x->h_order);
-        (void)hipFree(x->d_reloc); (void)hipFree(x->d_qxy); (void)hipFree(x->d_points); (void)hipHostFree(x->h_reloc);
-        (void)hipFree(x->d_part); (void)hipFree(x->d_out); (void)hipFree(x->d_query); (void)hipFree(x->d_ids); (void)hipFree(x->d_desc);
-        (void)hipHostFree(x->h_out); (void)hipHostFree(x->h_stage);
+        for (hipEvent_t e : x->ev) if (e) (void)hipEventDestroy(e);
         if (x->stream) (void)hipStreamDestroy(x->stream);
     }
     delete x;
+}
+
+// The one allocator: a block of device or pinned memory that the index owns from here on and frees when it goes, not before.
+static int index_block(svo_desc_index* x, void** p, size_t bytes, bool pinned) {
+    if (pinned) MHIP(hipHostMalloc(p, bytes, hipHostMallocDefault)); else MHIP(hipMalloc(p, bytes));
+    (pinned ? x->pinned_blocks : x->dev_blocks).push_back(*p);
+    return SVO_OK;
+}
+// An allocate-once pointer: a block for it unless it has one.  A room of several is one of these each, so a call that comes back
+// after a failed allocation takes up where that one stopped.
+template <class T> static int room(svo_desc_index* x, T*& p, size_t bytes, bool pinned) { return p ? SVO_OK : index_block(x, (void**)&p, bytes, pinned); }
+#define ROOM(call) do { if (const int _rc = (call); _rc != SVO_OK) return _rc; } while (0)
+
+// Room for `need` bytes in a growable buffer, by the rule of match_grow_capacity (svo_match.hpp).  The buffer it outgrows stays the
+// index's block until the index goes; its bytes are counted.
+static int grow(svo_desc_index* x, GrowBuf& b, size_t need, size_t first, size_t clamp, bool pinned) {
+    const size_t cap = match_grow_capacity(b.cap, need, first, clamp);
+    if (cap == b.cap) return SVO_OK;
+    void* p = nullptr;
+    ROOM(index_block(x, &p, cap, pinned));
+    b.outgrown += b.cap; b.p = (uint8_t*)p; b.cap = cap; b.allocs++;
+    return SVO_OK;
 }
 
 static int index_alloc(svo_desc_index* x) {
     MHIP(hipSetDevice(x->device));
     MHIP(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
     MHIP(hipEventCreate(&x->ev[0])); MHIP(hipEventCreate(&x->ev[1]));
-    MHIP(hipMalloc((void**)&x->d_desc, (size_t)x->capacity * SVO_DESC_BYTES));
-    MHIP(hipMalloc((void**)&x->d_ids, (size_t)x->capacity * sizeof(uint64_t)));
-    MHIP(hipMalloc((void**)&x->d_query, (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES));
-    MHIP(hipMalloc((void**)&x->d_out, (size_t)MATCH_STAGE_ROWS * sizeof(svo_desc_match)));
-    MHIP(hipHostMalloc((void**)&x->h_stage, (size_t)MATCH_STAGE_ROWS * (SVO_DESC_BYTES + sizeof(uint64_t)), hipHostMallocDefault));
-    MHIP(hipHostMalloc((void**)&x->h_out, (size_t)MATCH_STAGE_ROWS * sizeof(svo_desc_match), hipHostMallocDefault));
+    ROOM(room(x, x->d_desc, (size_t)x->capacity * SVO_DESC_BYTES, false));
+    ROOM(room(x, x->d_ids, (size_t)x->capacity * sizeof(uint64_t), false));
+    ROOM(room(x, x->d_query, (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES, false));
+    ROOM(room(x, x->d_out, (size_t)MATCH_STAGE_ROWS * sizeof(svo_desc_match), false));
+    ROOM(room(x, x->h_stage, (size_t)MATCH_STAGE_ROWS * (SVO_DESC_BYTES + sizeof(uint64_t)), true));
+    ROOM(room(x, x->h_out, (size_t)MATCH_STAGE_ROWS * sizeof(svo_desc_match), true));
     return SVO_OK;
 }
 
@@ -225,9 +237,9 @@ extern "C" int svo_desc_index_set_timing(svo_desc_index* x, int on) {
 extern "C" int svo_desc_index_get_stats(const svo_desc_index* x, svo_desc_index_stats* st) {
     if (!x || !st) return fail(SVO_ERR_ARG, "null index / stats");
     st->last_kernels_ms = x->last_ms;
-    st->scratch_allocations = x->part_allocs;
-    st->scratch_bytes = (uint64_t)x->part_cap * sizeof(MatchPartial);
-    st->scratch_bytes_outgrown = (uint64_t)x->outgrown_states * sizeof(MatchPartial);
+    st->scratch_allocations = x->part.allocs;
+    st->scratch_bytes = (uint64_t)x->part.cap;
+    st->scratch_bytes_outgrown = (uint64_t)x->part.outgrown;
     return SVO_OK;
 }
 
@@ -262,13 +274,11 @@ extern "C" int svo_desc_index_add(svo_desc_index* x, int n, const uint8_t* desc,
 extern "C" int svo_desc_index_enable_points(svo_desc_index* x) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
     if (x->size != 0) return fail(SVO_ERR_STATE, "svo_desc_index_enable_points: the index already holds rows (points are enabled on an empty index)");
-    if (x->d_points) return SVO_OK;
     MHIP(hipSetDevice(x->device));
-    MHIP(hipHostMalloc((void**)&x->h_reloc, sizeof(RelocHost), hipHostMallocDefault));
-    MHIP(hipMalloc((void**)&x->d_qxy, (size_t)MATCH_STAGE_ROWS * sizeof(float2)));
-    MHIP(hipMalloc((void**)&x->d_reloc, sizeof(RelocDevOut)));
-    MHIP(hipMalloc((void**)&x->d_points, (size_t)x->capacity * sizeof(RelocPoint)));   // last: d_points says "enabled"
-    return SVO_OK;
+    ROOM(room(x, x->h_reloc, sizeof(RelocHost), true));
+    ROOM(room(x, x->d_qxy, (size_t)MATCH_STAGE_ROWS * sizeof(float2), false));
+    ROOM(room(x, x->d_reloc, sizeof(RelocDevOut), false));
+    return room(x, x->d_points, (size_t)x->capacity * sizeof(RelocPoint), false);          // d_points is what says "enabled"
 }
 
 // the point rows of an append: finite coordinates, tags >= 0 (null: 0)
@@ -286,7 +296,7 @@ static int make_points(int n, const float* xyz, const int32_t* tags, int32_t tag
 extern "C" int svo_desc_index_add_points(svo_desc_index* x, int n, const uint8_t* desc, const uint64_t* ids, const float* xyz,
                                          const int32_t* tags, int* first_row) {
     if (!x || n < 0 || (n > 0 && (!desc || !ids || !xyz))) return fail(SVO_ERR_ARG, "svo_desc_index_add_points: bad index / n / desc / ids / xyz");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_add_points: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("svo_desc_index_add_points");
     std::vector<RelocPoint> pts;
     const int rc = make_points(n, xyz, tags, 0, pts);
     if (rc != SVO_OK) return rc;
@@ -335,7 +345,7 @@ extern "C" int svo_desc_index_add_frame(svo_desc_index* x, svo_context* ctx, int
 extern "C" int svo_desc_index_add_frame_points(svo_desc_index* x, svo_context* ctx, int seq, uint32_t need_flags, const double* cam_to_map,
                                                int32_t tag, int* first_row, int* n_added) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_add_frame_points: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("svo_desc_index_add_frame_points");
     if (tag < 0) return fail(SVO_ERR_ARG, "svo_desc_index_add_frame_points: the tag must be >= 0");
     if (cam_to_map) for (int i = 0; i < 16; i++) if (!isfinite(cam_to_map[i])) return fail(SVO_ERR_ARG, "svo_desc_index_add_frame_points: cam_to_map has a non-finite entry");
     return add_frame_rows(x, ctx, seq, need_flags | SVO_OBS_HAS_XYZ, true, cam_to_map, tag, first_row, n_added);
@@ -349,29 +359,17 @@ static int row_range(const svo_desc_index* x, int& row_lo, int& row_hi) {
     return SVO_OK;
 }
 
-// Room for `need` partial states.  The scratch at least doubles whenever it grows (from MATCH_PART_FIRST), so an index whose searches
-// lengthen frame by frame allocates O(log) times and the buffers it has outgrown — kept until the index goes, since hipFree waits for
-// the whole device — sum to less than the one in use.  Up to MATCH_PART_BUDGET the doubling stops at the budget, which every search
-// of at most 65 536 chunks fits (search_plan sizes a launch to it); beyond, a search needs 64 queries x its chunks.
-static int part_room(svo_desc_index* x, size_t need) {
-    if (need <= x->part_cap) return SVO_OK;
-    size_t cap = x->part_cap ? 2 * x->part_cap : MATCH_PART_FIRST;
-    while (cap < need) cap *= 2;
-    if (need <= MATCH_PART_BUDGET && cap > MATCH_PART_BUDGET) cap = MATCH_PART_BUDGET;
-    MatchPartial* p = nullptr;
-    MHIP(hipMalloc((void**)&p, cap * sizeof(MatchPartial)));
-    if (x->d_part) { x->outgrown.push_back(x->d_part); x->outgrown_states += x->part_cap; }
-    x->d_part = p; x->part_cap = cap; x->part_allocs++;
-    return SVO_OK;
+// Room for `states` partial states (grow).  Up to the budget the doubling stops at the budget, which every search of at most 65 536
+// chunks fits (search_plan sizes a launch to it); beyond, a search needs 64 queries x its chunks.
+static int part_states(svo_desc_index* x, size_t states) {
+    return grow(x, x->part, states * sizeof(MatchPartial), MATCH_PART_FIRST * sizeof(MatchPartial), MATCH_PART_BUDGET * sizeof(MatchPartial), false);
 }
 
-// the buffers of the guided search, allocated at the first guided call and freed with the index
+// the buffers of the guided search, allocated at the first guided call
 static int guide_room(svo_desc_index* x) {
-    if (x->d_uv) return SVO_OK;
-    MHIP(hipHostMalloc((void**)&x->h_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t), hipHostMallocDefault));
-    MHIP(hipMalloc((void**)&x->d_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t)));
-    MHIP(hipMalloc((void**)&x->d_uv, (size_t)x->capacity * sizeof(float2)));          // last: d_uv says "allocated"
-    return SVO_OK;
+    ROOM(room(x, x->h_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t), true));
+    ROOM(room(x, x->d_order, (size_t)MATCH_STAGE_ROWS * sizeof(int32_t), false));
+    return room(x, x->d_uv, (size_t)x->capacity * sizeof(float2), false);
 }
 
 // a guided search's prior as the kernels read it, and the caller's pixels, which order its lanes (guide_order)
@@ -380,7 +378,7 @@ struct SearchGuide { GuidePose pose; float radius; const float* xy; };
 // a guided call's own refusals, and its guide
 static int guide_check(const svo_desc_index* x, const float* K, const svo_reloc_guide* g, const float* xy, SearchGuide* sg) {
     if (!x || !K || !g) return fail(SVO_ERR_ARG, "guided search: null index / K / guide");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "guided search: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("guided search");
     if (!isfinite(g->radius) || g->radius < 0.f) return fail(SVO_ERR_ARG, "guided search: the radius must be finite and >= 0");
     for (int i = 0; i < 9; i++) if (!isfinite(g->R[i]) || !isfinite(K[i])) return fail(SVO_ERR_ARG, "guided search: R or K has a non-finite entry");
     for (int i = 0; i < 3; i++) if (!isfinite(g->t[i])) return fail(SVO_ERR_ARG, "guided search: t has a non-finite entry");
@@ -407,7 +405,8 @@ static void guide_order(const svo_desc_index* x, int n, const float* xy, float r
 }
 
 // The plan of a search of n <= MATCH_STAGE_ROWS queries: its rows in chunks, the queries of one launch, and the guide if it has one.
-struct SearchPlan { MatchRange r; int batch; const SearchGuide* guide; };
+// near_lo >= 0: the queries are rows near_lo .. of the index and a row competes only within near_radius of the query's point (fuse_run).
+struct SearchPlan { MatchRange r; int batch; const SearchGuide* guide; int near_lo = -1; float near_radius = 0.f; };
 
 // The two ways a search fits the partial-state budget, and the room for the one chosen.  Unguided: the chunks stay as they are set
 // and the queries go in launches of the largest multiple of 64 (64 at least) whose partial states fit.  Guided: the partial states
@@ -415,7 +414,7 @@ struct SearchPlan { MatchRange r; int batch; const SearchGuide* guide; };
 // fits (n <= 4096 and at most 1 << 24 rows: 16 384 rows a chunk at most).  The results depend on neither.
 static int search_plan(svo_desc_index* x, int n, int row_lo, int row_hi, const SearchGuide* guide, SearchPlan* p) {
     int chunk_rows = x->chunk_rows;
-    *p = SearchPlan{match_range(row_lo, row_hi, chunk_rows), n, guide};
+    *p = SearchPlan{match_range(row_lo, row_hi, chunk_rows), n, guide};    // not near: fuse_run says so itself
     if (guide) {
         if (const int rc = guide_room(x); rc != SVO_OK) return rc;
         while ((size_t)n * (size_t)p->r.n_chunks > MATCH_PART_BUDGET) p->r = match_range(row_lo, row_hi, chunk_rows *= 2);
@@ -424,7 +423,7 @@ static int search_plan(svo_desc_index* x, int n, int row_lo, int row_hi, const S
         if (fit < 64) fit = 64;
         if (fit < (size_t)n) p->batch = (int)fit;
     }
-    return p->batch > 0 && p->r.n_chunks > 0 ? part_room(x, (size_t)p->batch * (size_t)p->r.n_chunks) : SVO_OK;
+    return p->batch > 0 && p->r.n_chunks > 0 ? part_states(x, (size_t)p->batch * (size_t)p->r.n_chunks) : SVO_OK;
 }
 
 // The one staging step: n <= MATCH_STAGE_ROWS queries into d_query and, for a call that has pixels, their pixels into d_qxy (xy
@@ -441,20 +440,21 @@ static int stage_queries(svo_desc_index* x, int n, const uint8_t* query, bool pi
 }
 
 // The timing bracket.  A call begins by clearing last_ms; it marks both edges of the one span it times (`here`: this is that span),
-// and reads the span after its wait.  With timing off nothing is recorded and last_ms stays 0.
+// and reads the span after its wait into its figure: last_ms, or the maintenance calls' retire_ms, or the batched insertion's
+// insert_ms.  With timing off nothing is recorded and the figure stays 0.
 static hipError_t call_begin(svo_desc_index* x) { x->last_ms = 0.f; return hipSetDevice(x->device); }
 static hipError_t span_mark(svo_desc_index* x, bool here, int edge) { return x->timing && here ? hipEventRecord(x->ev[edge], x->stream) : hipSuccess; }
-static hipError_t span_read(svo_desc_index* x) {
+static hipError_t span_read(svo_desc_index* x, float& figure) {
     float ms = 0.f;
     const hipError_t e = x->timing ? hipEventElapsedTime(&ms, x->ev[0], x->ev[1]) : hipSuccess;
-    x->last_ms += ms;
+    figure += ms;
     return e;
 }
 
 // The one enqueue: the search of the n staged queries (stage_queries) by plan p on the index's stream, d_out[0 .. n) when it has run;
 // no wait.  Guided: the lane order up, the projection, and one launch of the guided kernel.  Unguided: launches of p.batch queries
-// (a multiple of 64 rows, or all of them) back to back.  timed: the search is the span the call times.  from: the queries where they
-// are not the staged ones — rows of the index itself (align_run).
+// (a multiple of 64 rows, or all of them) back to back, of the plain kernel or, for a near plan, the gated one.  timed: the search is
+// the span the call times, or its beginning.  from: the queries where they are not the staged ones — rows of the index itself (align_run).
 static int search_enqueue(svo_desc_index* x, const SearchPlan& p, int n, bool timed, const uint8_t* from = nullptr) {
     const SearchGuide* g = p.guide;
     if (g && n > 0) {
@@ -466,12 +466,22 @@ static int search_enqueue(svo_desc_index* x, const SearchPlan& p, int n, bool ti
     for (int i0 = 0; i0 < n; i0 += p.batch) {         // guided: p.batch == n
         const int m = n - i0 < p.batch ? n - i0 : p.batch;
         const uint32_t* query = (const uint32_t*)((from ? from : x->d_query) + (size_t)i0 * SVO_DESC_BYTES);
-        if (g) launch_desc_match_guided((const uint32_t*)x->d_desc, x->d_ids, x->d_uv, query, x->d_qxy, x->d_order, m, g->radius, p.r, x->d_part, x->stream);
-        else launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, query, m, p.r, x->d_part, x->stream);
-        launch_desc_match_merge(x->d_part, x->d_ids, m, p.r, x->d_out + i0, x->stream);
+        if (g) launch_desc_match_guided((const uint32_t*)x->d_desc, x->d_ids, x->d_uv, query, x->d_qxy, x->d_order, m, g->radius, p.r, x->d_part(), x->stream);
+        else if (p.near_lo >= 0) launch_desc_match_near((const uint32_t*)x->d_desc, x->d_ids, x->d_points, p.near_lo + i0, m, p.near_radius, p.r, x->d_part(), x->stream);
+        else launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, query, m, p.r, x->d_part(), x->stream);
+        launch_desc_match_merge(x->d_part(), x->d_ids, m, p.r, x->d_out + i0, x->stream);
     }
     MHIP(hipGetLastError());
     MHIP(span_mark(x, timed, 1));
+    return SVO_OK;
+}
+
+// The end of a call, or of a stage, that returns the search's result rows: d_out[0 .. n) down, the wait, the rows out, the span read.
+static int rows_down(svo_desc_index* x, int n, svo_desc_match* out) {
+    if (n > 0) MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));
+    if (n > 0) memcpy(out, x->h_out, (size_t)n * sizeof(svo_desc_match));
+    MHIP(span_read(x, x->last_ms));
     return SVO_OK;
 }
 
@@ -487,11 +497,7 @@ static int match_run(svo_desc_index* x, const SearchGuide* guide, int n, const u
     for (int i0 = 0; i0 < n; i0 += MATCH_STAGE_ROWS) {
         const int m = n - i0 < MATCH_STAGE_ROWS ? n - i0 : MATCH_STAGE_ROWS;
         if ((rc = stage_queries(x, m, query + (size_t)i0 * SVO_DESC_BYTES, guide != nullptr, guide ? guide->xy : nullptr)) != SVO_OK ||
-            (rc = search_enqueue(x, plan, m, true)) != SVO_OK) return rc;
-        MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)m * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));
-        memcpy(out + i0, x->h_out, (size_t)m * sizeof(svo_desc_match));
-        MHIP(span_read(x));
+            (rc = search_enqueue(x, plan, m, true)) != SVO_OK || (rc = rows_down(x, m, out + i0)) != SVO_OK) return rc;
     }
     return SVO_OK;
 }
@@ -520,7 +526,7 @@ extern "C" int svo_desc_index_project(svo_desc_index* x, const float K[9], const
     if ((rc = search_plan(x, 0, row_lo, row_hi, &sg, &plan)) != SVO_OK || (rc = search_enqueue(x, plan, 0, true)) != SVO_OK) return rc;
     MHIP(hipMemcpyAsync(uv, x->d_uv + row_lo, (size_t)(row_hi - row_lo) * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));
-    MHIP(span_read(x));
+    MHIP(span_read(x, x->last_ms));
     return SVO_OK;
 }
 
@@ -547,6 +553,60 @@ extern "C" void svo_reloc_params_default(svo_reloc_params* p) {
 struct RelocRequest { const float* K; const svo_reloc_guide* guide; int n; const uint8_t* query; const float* xy; const svo_reloc_params* p; };
 struct RelocOutputs { int* n_candidates; int32_t* cand_query; int32_t* cand_row; float* cand_xy; float* cand_xyz; svo_reloc_result* res = nullptr; uint8_t* cand_inlier = nullptr; };
 
+// ---- the pieces the single calls and the batch share
+// the refusals over a call's parameters, behind those of its rows
+static int reloc_params_check(const svo_reloc_params* p) {
+    if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
+    if (p->ratio_num < 1 || p->ratio_num > SVO_RELOC_MAX_RATIO || p->ratio_den < 1 || p->ratio_den > SVO_RELOC_MAX_RATIO)
+        return fail(SVO_ERR_ARG, "relocalisation: ratio_num and ratio_den must be 1 .. 1 << 20");
+    if (p->min_candidates < 6) return fail(SVO_ERR_ARG, "relocalisation: min_candidates must be >= 6 (4 and 5 points take svo_camera_to_world's direct routes)");
+    return SVO_OK;
+}
+
+// a camera's state row going up, as svo_camera_to_world sets it; the selection kernel fills in the count
+static void reloc_state_row(SeqState& hs, const float* K, const svo_reloc_result& guess) {
+    memset(&hs, 0, sizeof(hs));
+    hs.active = 1; hs.fail_reason = 0; hs.feat_buf = 0;
+    memcpy(hs.K, K, sizeof(float) * 9); memcpy(hs.R, guess.R, sizeof(double) * 9); memcpy(hs.t, guess.t, sizeof(double) * 3);
+}
+
+// a camera's result from its state row as k_pnp_final left it, its nc candidates and their inlier flags
+static void reloc_read(const SeqState& hs, int nc, int min_candidates, const uint8_t* inlier, svo_reloc_result* res, uint8_t* cand_inlier) {
+    res->success = 0; res->n_candidates = nc; res->n_inliers = 0; res->iters_run = 0;
+    memset(res->T, 0, sizeof(res->T));
+    if (cand_inlier) memset(cand_inlier, 0, (size_t)nc);
+    if (nc < min_candidates) return;                  // rule 4: every PnP kernel found the row not live
+    res->iters_run = hs.pnp_iters;
+    if (hs.pnp_best < 0) return;                      // no pose: R, t untouched, as svo_camera_to_world leaves them
+    memcpy(res->R, hs.R, sizeof(double) * 9); memcpy(res->t, hs.t, sizeof(double) * 3); memcpy(res->T, hs.last_T, sizeof(double) * 16);
+    res->success = 1; res->n_inliers = hs.n_inliers;
+    if (cand_inlier) memcpy(cand_inlier, inlier, (size_t)nc);
+}
+
+// k_reloc_select over the n results in d_out, for the single calls and for places: the candidates' pixels, points and count into the
+// stage context d, their queries and rows into d_reloc
+static void select_enqueue(svo_desc_index* x, const DevBuffers* d, int n, RelocRule rule, int min_candidates) {
+    RelocArgs a;
+    a.match = x->d_out; a.points = x->d_points; a.xy = x->d_qxy; a.n = n;
+    a.rule = rule; a.min_candidates = min_candidates;
+    a.out_xy = d->tl1; a.out_xyz = d->world; a.st = d->st;
+    a.cand_query = x->d_reloc->cand_query; a.cand_row = x->d_reloc->cand_row; a.n_cand = &x->d_reloc->n_cand;
+    launch_reloc_select(a, x->stream);
+}
+// the candidate lists on their way down into h_reloc->out: the count and the queries in one copy, the rows in another ...
+static int cands_down(svo_desc_index* x, int n) {
+    MHIP(hipMemcpyAsync(&x->h_reloc->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+    if (n > 0) MHIP(hipMemcpyAsync(x->h_reloc->out.cand_row, x->d_reloc->cand_row, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+    return SVO_OK;
+}
+// ... and, after the wait, out to the caller -> their number
+static int cands_read(const svo_desc_index* x, int32_t* cand_query, int32_t* cand_row) {
+    const RelocDevOut& o = x->h_reloc->out;
+    if (cand_query) memcpy(cand_query, o.cand_query, (size_t)o.n_cand * sizeof(int32_t));
+    if (cand_row) memcpy(cand_row, o.cand_row, (size_t)o.n_cand * sizeof(int32_t));
+    return o.n_cand;
+}
+
 // What select and localize share, with and without a guide.  Everything is enqueued on the index's stream — the uploads, the search,
 // k_reloc_select, the PnP kernels for localize, the copies back — and the host waits once.
 // times: a guided call its projection and guided search kernels, an unguided one the selection kernel
@@ -554,17 +614,14 @@ static int reloc_run(svo_desc_index* x, const RelocRequest& q, const RelocOutput
     const int n = q.n;
     const svo_reloc_params* p = q.p; svo_reloc_result* res = o.res;
     if (!x || !p || n < 0 || (n > 0 && !q.query)) return fail(SVO_ERR_ARG, "relocalisation: bad index / params / n / query");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "relocalisation: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("relocalisation");
     if (n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "relocalisation: at most 4096 queries per call");
     if (n > 0 && !q.xy && (res || o.cand_xy || q.guide)) return fail(SVO_ERR_ARG, "relocalisation: null xy");
     SearchGuide sg;
     int rc, row_lo = p->row_lo, row_hi = p->row_hi;
     if (q.guide && (rc = guide_check(x, q.K, q.guide, q.xy, &sg)) != SVO_OK) return rc;
     if ((rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
-    if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
-    if (p->ratio_num < 1 || p->ratio_num > SVO_RELOC_MAX_RATIO || p->ratio_den < 1 || p->ratio_den > SVO_RELOC_MAX_RATIO)
-        return fail(SVO_ERR_ARG, "relocalisation: ratio_num and ratio_den must be 1 .. 1 << 20");
-    if (p->min_candidates < 6) return fail(SVO_ERR_ARG, "relocalisation: min_candidates must be >= 6 (4 and 5 points take svo_camera_to_world's direct routes)");
+    if ((rc = reloc_params_check(p)) != SVO_OK) return rc;
     const bool times_search = q.guide != nullptr;
     MHIP(call_begin(x));
     const DevBuffers* d = nullptr;
@@ -572,51 +629,30 @@ static int reloc_run(svo_desc_index* x, const RelocRequest& q, const RelocOutput
     if ((rc = svo_reloc_stage_ctx(x->device, n > 64 ? n : 64, p->ransac_iterations, p->reproj_error, p->confidence, &d)) != SVO_OK ||
         (rc = search_plan(x, n, row_lo, row_hi, q.guide ? &sg : nullptr, &plan)) != SVO_OK || (rc = stage_queries(x, n, q.query, true, q.xy)) != SVO_OK) return rc;
     RelocHost* h = x->h_reloc;
-    if (res) {                                        // the state row as svo_camera_to_world sets it; k_reloc_select fills in the count
-        SeqState& hs = h->up;
-        memset(&hs, 0, sizeof(hs));
-        hs.active = 1; hs.fail_reason = 0; hs.feat_buf = 0;
-        memcpy(hs.K, q.K, sizeof(float) * 9); memcpy(hs.R, res->R, sizeof(double) * 9); memcpy(hs.t, res->t, sizeof(double) * 3);
-        MHIP(hipMemcpyAsync(d->st, &hs, sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
+    if (res) {
+        reloc_state_row(h->up, q.K, *res);
+        MHIP(hipMemcpyAsync(d->st, &h->up, sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
     }
     if ((rc = search_enqueue(x, plan, n, times_search)) != SVO_OK) return rc;
-    RelocArgs a;
-    a.match = x->d_out; a.points = x->d_points; a.xy = x->d_qxy; a.n = n;
-    a.rule = RelocRule{p->max_dist, p->ratio_num, p->ratio_den}; a.min_candidates = p->min_candidates;
-    a.out_xy = d->tl1; a.out_xyz = d->world; a.st = d->st;
-    a.cand_query = x->d_reloc->cand_query; a.cand_row = x->d_reloc->cand_row; a.n_cand = &x->d_reloc->n_cand;
     MHIP(span_mark(x, !times_search, 0));
-    launch_reloc_select(a, x->stream);
+    select_enqueue(x, d, n, RelocRule{p->max_dist, p->ratio_num, p->ratio_den}, p->min_candidates);
     MHIP(span_mark(x, !times_search, 1));
     if (res) { launch_pnp_subsets(*d, x->stream); launch_pnp(*d, x->stream); }
     MHIP(hipGetLastError());
-    MHIP(hipMemcpyAsync(&h->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+    if ((rc = cands_down(x, n)) != SVO_OK) return rc;
     if (n > 0) {
-        MHIP(hipMemcpyAsync(h->out.cand_row, x->d_reloc->cand_row, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
         if (o.cand_xy) MHIP(hipMemcpyAsync(h->cand_xy, d->tl1, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, x->stream));
         if (o.cand_xyz) MHIP(hipMemcpyAsync(h->cand_xyz, d->world, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, x->stream));
         if (res) MHIP(hipMemcpyAsync(h->inlier, d->inlier, (size_t)n, hipMemcpyDeviceToHost, x->stream));
     }
     if (res) MHIP(hipMemcpyAsync(&h->down, d->st, sizeof(SeqState), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
-    MHIP(span_read(x));
-    const int nc = h->out.n_cand;
+    MHIP(span_read(x, x->last_ms));
+    const int nc = cands_read(x, o.cand_query, o.cand_row);
     if (o.n_candidates) *o.n_candidates = nc;
-    if (o.cand_query) memcpy(o.cand_query, h->out.cand_query, (size_t)nc * sizeof(int32_t));
-    if (o.cand_row) memcpy(o.cand_row, h->out.cand_row, (size_t)nc * sizeof(int32_t));
     if (o.cand_xy) memcpy(o.cand_xy, h->cand_xy, (size_t)nc * sizeof(float2));
     if (o.cand_xyz) memcpy(o.cand_xyz, h->cand_xyz, (size_t)nc * 3 * sizeof(float));
-    if (!res) return SVO_OK;
-    const SeqState& hs = h->down;
-    res->success = 0; res->n_candidates = nc; res->n_inliers = 0; res->iters_run = 0;
-    memset(res->T, 0, sizeof(res->T));
-    if (o.cand_inlier) memset(o.cand_inlier, 0, (size_t)nc);
-    if (nc < p->min_candidates) return SVO_OK;        // rule 4: every PnP kernel found the row not live
-    res->iters_run = hs.pnp_iters;
-    if (hs.pnp_best < 0) return SVO_OK;               // no pose: R, t untouched, as svo_camera_to_world leaves them
-    memcpy(res->R, hs.R, sizeof(double) * 9); memcpy(res->t, hs.t, sizeof(double) * 3); memcpy(res->T, hs.last_T, sizeof(double) * 16);
-    res->success = 1; res->n_inliers = hs.n_inliers;
-    if (o.cand_inlier) memcpy(o.cand_inlier, h->inlier, (size_t)nc);
+    if (res) reloc_read(h->down, nc, p->min_candidates, h->inlier, res, o.cand_inlier);
     return SVO_OK;
 }
 
@@ -652,17 +688,16 @@ extern "C" int svo_desc_index_localize_guided(svo_desc_index* x, const float K[9
 #define BATCH_FIRST_QUERIES 4096
 
 // Room for a call of `cams` cameras and `queries` queries in the batch's staging: a device block, a pinned block and the pinned state
-// rows.  Either capacity at least doubles when it is outgrown; the outgrown blocks go with the index.
+// rows.  Either capacity at least doubles when it is outgrown (rb_grow); the outgrown blocks go with the index, like every block.
 static int batch_room(svo_desc_index* x, size_t cams, size_t queries) {
     if (x->d_batch && cams <= x->batch_cams && queries <= x->batch_queries) return SVO_OK;
     const size_t nc = rb_grow(x->batch_cams, cams, BATCH_FIRST_CAMS), nq = rb_grow(x->batch_queries, queries, BATCH_FIRST_QUERIES);
     const RbLayout l = rb_layout(nc, nq);
-    uint8_t *d = nullptr, *h = nullptr;
+    uint8_t *d = nullptr, *h = nullptr;               // all three, then the switch: a failure leaves the staging as it was
     SeqState* hs = nullptr;
-    MHIP(hipMalloc((void**)&d, l.total));
-    if (hipError_t e = hipHostMalloc((void**)&h, l.down_end, hipHostMallocDefault); e != hipSuccess) { (void)hipFree(d); MHIP(e); }
-    if (hipError_t e = hipHostMalloc((void**)&hs, 2 * nc * sizeof(SeqState), hipHostMallocDefault); e != hipSuccess) { (void)hipFree(d); (void)hipHostFree(h); MHIP(e); }
-    if (x->d_batch) { x->outgrown.push_back(x->d_batch); x->outgrown_pinned.push_back(x->h_batch); x->outgrown_pinned.push_back(x->h_batch_st); }
+    ROOM(room(x, d, l.total, false));
+    ROOM(room(x, h, l.down_end, true));
+    ROOM(room(x, hs, 2 * nc * sizeof(SeqState), true));
     x->d_batch = d; x->h_batch = h; x->h_batch_st = hs; x->batch_cams = nc; x->batch_queries = nq;
     x->batch_total = -1;                              // the order of the last call stayed in the old block
     return SVO_OK;
@@ -691,16 +726,13 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
     if (n_cameras > 0 && (!K || !results)) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null K / results");
     const int total = n_cameras > 0 ? query_begin[n_cameras] : 0;
     if (total > 0 && (!query || !xy)) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null query / xy");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "relocalisation: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("relocalisation");
     std::vector<SearchGuide> sg((size_t)(guides ? n_cameras : 0));
     int rc, row_lo = p->row_lo, row_hi = p->row_hi;
     for (int b = 0; b < n_cameras && guides; b++)
         if ((rc = guide_check(x, K + 9 * b, guides + b, nullptr, &sg[(size_t)b])) != SVO_OK) return rc;
     if ((rc = row_range(x, row_lo, row_hi)) != SVO_OK) return rc;
-    if (p->max_dist < 0 || p->max_dist > 256) return fail(SVO_ERR_ARG, "relocalisation: max_dist must be 0 .. 256");
-    if (p->ratio_num < 1 || p->ratio_num > SVO_RELOC_MAX_RATIO || p->ratio_den < 1 || p->ratio_den > SVO_RELOC_MAX_RATIO)
-        return fail(SVO_ERR_ARG, "relocalisation: ratio_num and ratio_den must be 1 .. 1 << 20");
-    if (p->min_candidates < 6) return fail(SVO_ERR_ARG, "relocalisation: min_candidates must be >= 6 (4 and 5 points take svo_camera_to_world's direct routes)");
+    if ((rc = reloc_params_check(p)) != SVO_OK) return rc;
     MHIP(call_begin(x));
     if (n_cameras == 0) return SVO_OK;
     // ---- room: the plan's partial states, the staging, the stage context
@@ -718,7 +750,7 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
     rc = svo_reloc_batch_ctx(x->device, n_cameras, max_slice > 64 ? max_slice : 64, p->ransac_iterations, p->reproj_error, p->confidence,
                              &x->batch_ctx, &old, &d);
     if (old) x->batch_ctx_outgrown.push_back(old);
-    if (rc != SVO_OK || (states > 0 && (rc = part_room(x, states)) != SVO_OK) || (rc = batch_room(x, (size_t)n_cameras, (size_t)total)) != SVO_OK) return rc;
+    if (rc != SVO_OK || (states > 0 && (rc = part_states(x, states)) != SVO_OK) || (rc = batch_room(x, (size_t)n_cameras, (size_t)total)) != SVO_OK) return rc;
     // ---- the upload: one copy of the staging's first part, one of the state rows
     const RbLayout l = rb_layout((size_t)n_cameras, (size_t)total);             // cut for this call: it fits the blocks, and the copies carry no slack
     uint8_t *h = x->h_batch, *dv = x->d_batch;
@@ -727,12 +759,9 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
     memcpy(h + l.begin, query_begin, (size_t)(n_cameras + 1) * sizeof(int32_t));
     RelocBatchCam* h_cams = (RelocBatchCam*)(h + l.cams);
     SeqState *h_up = x->h_batch_st, *h_down = x->h_batch_st + x->batch_cams;
-    for (int b = 0; b < n_cameras; b++) {             // the state row as reloc_run sets it
+    for (int b = 0; b < n_cameras; b++) {
         h_cams[b] = guides ? RelocBatchCam{sg[(size_t)b].pose, sg[(size_t)b].radius, 0} : RelocBatchCam{};
-        SeqState& hs = h_up[b];
-        memset(&hs, 0, sizeof(hs));
-        hs.active = 1; hs.fail_reason = 0; hs.feat_buf = 0;
-        memcpy(hs.K, K + 9 * b, sizeof(float) * 9); memcpy(hs.R, results[b].R, sizeof(double) * 9); memcpy(hs.t, results[b].t, sizeof(double) * 3);
+        reloc_state_row(h_up[b], K + 9 * b, results[b]);
     }
     MHIP(hipMemcpyAsync(dv, h, l.up_end, hipMemcpyHostToDevice, x->stream));
     MHIP(hipMemcpyAsync(d.st, h_up, (size_t)n_cameras * sizeof(SeqState), hipMemcpyHostToDevice, x->stream));
@@ -752,12 +781,12 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
         const int m = g.q1 - g.q0;
         if (guides) {
             const RelocBatchSearch a{(const uint32_t*)x->d_desc, x->d_ids, x->d_points, d_cams, d_begin, d_query, d_qxy, ordered ? d_order : nullptr,
-                                     r, g.cam0, g.q0, x->d_part};
+                                     r, g.cam0, g.q0, x->d_part()};
             launch_desc_match_guided_batch(a, rb_guided_grid(g, r.n_chunks), x->stream);
         } else {
-            launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, d_query + (size_t)g.q0 * 8, m, mr, x->d_part, x->stream);
+            launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, d_query + (size_t)g.q0 * 8, m, mr, x->d_part(), x->stream);
         }
-        launch_desc_match_merge(x->d_part, x->d_ids, m, mr, d_match + g.q0, x->stream);
+        launch_desc_match_merge(x->d_part(), x->d_ids, m, mr, d_match + g.q0, x->stream);
         cam = g.cam1;
     }
     const RelocBatchSelect sel{d_match, x->d_points, d_qxy, d_begin, RelocRule{p->max_dist, p->ratio_num, p->ratio_den}, p->min_candidates,
@@ -773,24 +802,14 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
     MHIP(hipMemcpyAsync(h + l.n_cand, dv + l.n_cand, l.down_end - l.n_cand, hipMemcpyDeviceToHost, x->stream));
     MHIP(hipMemcpyAsync(h_down, d.st, (size_t)n_cameras * sizeof(SeqState), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
-    MHIP(span_read(x));
+    MHIP(span_read(x, x->last_ms));
     const int32_t* h_ncand = (const int32_t*)(h + l.n_cand);
     const int32_t *h_cq = (const int32_t*)(h + l.cand_query), *h_cr = (const int32_t*)(h + l.cand_row);
-    for (int b = 0; b < n_cameras; b++) {             // reloc_run's reading of one camera
+    for (int b = 0; b < n_cameras; b++) {
         const int q0 = query_begin[b], nc = h_ncand[b];
-        svo_reloc_result* res = results + b;
-        const SeqState& hs = h_down[b];
         if (cand_query) memcpy(cand_query + q0, h_cq + q0, (size_t)nc * sizeof(int32_t));
         if (cand_row) memcpy(cand_row + q0, h_cr + q0, (size_t)nc * sizeof(int32_t));
-        res->success = 0; res->n_candidates = nc; res->n_inliers = 0; res->iters_run = 0;
-        memset(res->T, 0, sizeof(res->T));
-        if (cand_inlier) memset(cand_inlier + q0, 0, (size_t)nc);
-        if (nc < p->min_candidates) continue;         // rule 4: every PnP kernel found the row not live
-        res->iters_run = hs.pnp_iters;
-        if (hs.pnp_best < 0) continue;                // no pose: R, t untouched
-        memcpy(res->R, hs.R, sizeof(double) * 9); memcpy(res->t, hs.t, sizeof(double) * 3); memcpy(res->T, hs.last_T, sizeof(double) * 16);
-        res->success = 1; res->n_inliers = hs.n_inliers;
-        if (cand_inlier) memcpy(cand_inlier + q0, h + l.inlier + q0, (size_t)nc);
+        reloc_read(h_down[b], nc, p->min_candidates, h + l.inlier + q0, results + b, cand_inlier ? cand_inlier + q0 : nullptr);
     }
     return SVO_OK;
 }
@@ -842,13 +861,31 @@ static const char* align_refusal_text(AlignRefusal e) {
     }
 }
 
-// the alignment's device block and its pinned twin, allocated at the first call that pairs and freed with the index
+// the alignment's device block and its pinned twin, allocated at the first call that pairs
 static int align_room(svo_desc_index* x) {
-    if (x->d_align) return SVO_OK;
     const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
-    if (!x->h_align) MHIP(hipHostMalloc((void**)&x->h_align, l.down_end, hipHostMallocDefault));
-    MHIP(hipMalloc((void**)&x->d_align, l.total));    // last: d_align says "allocated"
-    return SVO_OK;
+    ROOM(room(x, x->h_align, l.down_end, true));
+    return room(x, x->d_align, l.total, false);
+}
+
+// ---- the pair stage that the alignment and the fusion share: k_align_pairs over the n results in d_out, the queries being rows
+// src_lo .. of the index, into the alignment's block, cut here
+struct PairStage { AlignLayout l; AlignOut* out; int32_t *src, *dst; uint8_t* inlier; float* pairs; };
+static PairStage pairs_enqueue(svo_desc_index* x, int src_lo, int n, RelocRule rule) {
+    const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
+    uint8_t* dv = x->d_align;
+    const PairStage s{l, (AlignOut*)(dv + l.out), (int32_t*)(dv + l.pair_src), (int32_t*)(dv + l.pair_dst), dv + l.pair_inlier, (float*)(dv + l.pairs)};
+    launch_align_pairs(AlignPairsArgs{x->d_out, x->d_points, x->d_ids, src_lo, n, rule, s.src, s.dst, s.inlier, s.pairs, s.out}, x->stream);
+    return s;
+}
+// the pairs out of the pinned twin, after the wait -> their number
+static int pairs_read(const svo_desc_index* x, const AlignLayout& l, int* n_pairs, int32_t* pair_src, int32_t* pair_dst) {
+    const uint8_t* h = x->h_align;
+    const int np = ((const AlignOut*)(h + l.out))->n_pairs;
+    if (n_pairs) *n_pairs = np;
+    if (pair_src) memcpy(pair_src, h + l.pair_src, (size_t)np * sizeof(int32_t));
+    if (pair_dst) memcpy(pair_dst, h + l.pair_dst, (size_t)np * sizeof(int32_t));
+    return np;
 }
 
 // What match_rows (stage 1), pair_rows (2) and align (3) share.  q: the request, checked and with its spans resolved.  Everything is
@@ -863,24 +900,13 @@ static int align_run(svo_desc_index* x, const AlignRequest& q, int stage, svo_de
     SearchPlan plan;
     if ((stage > 1 && (rc = align_room(x)) != SVO_OK) || (rc = search_plan(x, n, q.dst_lo, q.dst_hi, nullptr, &plan)) != SVO_OK) return rc;
     if ((rc = search_enqueue(x, plan, n, true, x->d_desc + (size_t)q.src_lo * SVO_DESC_BYTES)) != SVO_OK) return rc;
-    if (stage == 1) {
-        if (n > 0) MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));
-        MHIP(span_read(x));
-        if (n > 0) memcpy(rows, x->h_out, (size_t)n * sizeof(svo_desc_match));
-        return SVO_OK;
-    }
-    const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
+    if (stage == 1) return rows_down(x, n, rows);
+    const PairStage ps = pairs_enqueue(x, q.src_lo, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den});
+    const AlignLayout& l = ps.l;
     uint8_t *dv = x->d_align, *h = x->h_align;
-    AlignOut* d_res = (AlignOut*)(dv + l.out);
-    float* d_pairs = (float*)(dv + l.pairs);
-    uint8_t* d_inlier = dv + l.pair_inlier;
-    const AlignPairsArgs pa{x->d_out, x->d_points, x->d_ids, q.src_lo, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den},
-                            (int32_t*)(dv + l.pair_src), (int32_t*)(dv + l.pair_dst), d_inlier, d_pairs, d_res};
-    launch_align_pairs(pa, x->stream);
     if (stage == 3) {
-        const AlignFitArgs fa{d_pairs, q.hypotheses, q.min_pairs, q.refit_rounds, align_dist2(q.inlier_dist),
-                              (int32_t*)(dv + l.counts), (AlignModel*)(dv + l.models), d_inlier, d_res};
+        const AlignFitArgs fa{ps.pairs, q.hypotheses, q.min_pairs, q.refit_rounds, align_dist2(q.inlier_dist),
+                              (int32_t*)(dv + l.counts), (AlignModel*)(dv + l.models), ps.inlier, ps.out};
         launch_align_score(fa, x->stream);
         launch_align_fit(fa, x->stream);
     }
@@ -888,12 +914,9 @@ static int align_run(svo_desc_index* x, const AlignRequest& q, int stage, svo_de
     MHIP(span_mark(x, true, 1));                      // the span's end moves from the search's last kernel to the call's
     MHIP(hipMemcpyAsync(h, dv, l.down_end, hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
-    MHIP(span_read(x));
+    MHIP(span_read(x, x->last_ms));
     const AlignOut& o = *(const AlignOut*)(h + l.out);
-    const int np = o.n_pairs;
-    if (n_pairs) *n_pairs = np;
-    if (pair_src) memcpy(pair_src, h + l.pair_src, (size_t)np * sizeof(int32_t));
-    if (pair_dst) memcpy(pair_dst, h + l.pair_dst, (size_t)np * sizeof(int32_t));
+    const int np = pairs_read(x, l, n_pairs, pair_src, pair_dst);
     if (pair_inlier) memcpy(pair_inlier, h + l.pair_inlier, (size_t)np);
     if (!res) return SVO_OK;
     memset(res, 0, sizeof(*res));
@@ -921,7 +944,7 @@ extern "C" int svo_desc_index_match_rows(svo_desc_index* x, int src_lo, int src_
 
 extern "C" int svo_desc_index_pair_rows(svo_desc_index* x, const svo_align_params* p, int* n_pairs, int32_t* pair_src, int32_t* pair_dst) {
     if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_pair_rows: null index / params");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "map alignment: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("map alignment");
     AlignRequest q = align_request(p);
     if (const AlignRefusal e = align_check(q, x->size); e != ALIGN_OK) return fail(SVO_ERR_ARG, align_refusal_text(e));
     return align_run(x, q, 2, nullptr, n_pairs, nullptr, pair_src, pair_dst, nullptr);
@@ -930,7 +953,7 @@ extern "C" int svo_desc_index_pair_rows(svo_desc_index* x, const svo_align_param
 extern "C" int svo_desc_index_align(svo_desc_index* x, const svo_align_params* p, svo_align_result* res, int32_t* pair_src, int32_t* pair_dst,
                                     uint8_t* pair_inlier) {
     if (!x || !p || !res) return fail(SVO_ERR_ARG, "svo_desc_index_align: null index / params / result");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "map alignment: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("map alignment");
     AlignRequest q = align_request(p);
     if (const AlignRefusal e = align_check(q, x->size); e != ALIGN_OK) return fail(SVO_ERR_ARG, align_refusal_text(e));
     return align_run(x, q, 3, nullptr, nullptr, res, pair_src, pair_dst, pair_inlier);
@@ -941,31 +964,12 @@ extern "C" int svo_desc_index_align(svo_desc_index* x, const svo_align_params* p
 #define RETIRE_STAGE_BYTES ((size_t)MATCH_STAGE_ROWS * (SVO_DESC_BYTES + sizeof(uint64_t)))   // h_stage, which carries the ids up and kept_before down
 
 static int retire_ctl_room(svo_desc_index* x) {
-    if (x->d_retire_ctl) return SVO_OK;
-    MHIP(hipHostMalloc((void**)&x->h_retire, sizeof(RetireDown), hipHostMallocDefault));
-    MHIP(hipMalloc((void**)&x->d_retire_ctl, sizeof(RetireCtl)));             // last: d_retire_ctl says "allocated"
-    return SVO_OK;
+    ROOM(room(x, x->h_retire, sizeof(RetireDown), true));
+    return room(x, x->d_retire_ctl, sizeof(RetireCtl), false);
 }
 
-// Room for `need` bytes of retire scratch: part_room's pattern.  The size is 64 KiB times a power of two, the smallest that holds
-// the largest call so far — below twice its need — and the outgrown buffers, freed with the index, sum to less than the one in use.
-static int retire_room(svo_desc_index* x, size_t need) {
-    if (need <= x->retire_cap) return SVO_OK;
-    size_t cap = x->retire_cap ? 2 * x->retire_cap : RETIRE_SCRATCH_FIRST;
-    while (cap < need) cap *= 2;
-    uint8_t* p = nullptr;
-    MHIP(hipMalloc((void**)&p, cap));
-    if (x->d_retire) { x->outgrown.push_back(x->d_retire); x->retire_outgrown += x->retire_cap; }
-    x->d_retire = p; x->retire_cap = cap; x->retire_allocs++;
-    return SVO_OK;
-}
-
-static hipError_t retire_span_read(svo_desc_index* x) {
-    float ms = 0.f;
-    const hipError_t e = x->timing ? hipEventElapsedTime(&ms, x->ev[0], x->ev[1]) : hipSuccess;
-    x->retire_ms += ms;
-    return e;
-}
+// Room for `need` bytes of maintenance scratch (grow): 64 KiB times a power of two, the smallest that holds the largest call so far.
+static int retire_scratch(svo_desc_index* x, size_t need) { return grow(x, x->retire, need, RETIRE_SCRATCH_FIRST, 0, false); }
 
 extern "C" int svo_desc_index_set_retire_slab_rows(svo_desc_index* x, int rows) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
@@ -978,20 +982,21 @@ extern "C" int svo_desc_index_get_retire_slab_rows(const svo_desc_index* x) { re
 extern "C" int svo_desc_index_get_retire_stats(const svo_desc_index* x, svo_desc_retire_stats* st) {
     if (!x || !st) return fail(SVO_ERR_ARG, "null index / stats");
     st->last_kernels_ms = x->retire_ms;
-    st->scratch_allocations = x->retire_allocs;
-    st->scratch_bytes = (uint64_t)x->retire_cap;
-    st->scratch_bytes_outgrown = (uint64_t)x->retire_outgrown;
+    st->scratch_allocations = x->retire.allocs;
+    st->scratch_bytes = (uint64_t)x->retire.cap;
+    st->scratch_bytes_outgrown = (uint64_t)x->retire.outgrown;
     return SVO_OK;
 }
 
-// the sorted id list onto the device through the pinned staging, piece by piece
-static int retire_upload_ids(svo_desc_index* x, const std::vector<uint64_t>& sorted, uint64_t* d_sorted) {
+// The one list upload: n 64-bit values onto the device through the pinned staging, piece by piece, with a wait behind each piece,
+// which frees the staging again — but for the last one's where the caller puts up one piece and waits once itself (wait_last false).
+static int upload_list(svo_desc_index* x, const uint64_t* src, size_t n, uint64_t* d_dst, bool wait_last = true) {
     const size_t piece = RETIRE_STAGE_BYTES / sizeof(uint64_t);
-    for (size_t i0 = 0; i0 < sorted.size(); i0 += piece) {
-        const size_t m = sorted.size() - i0 < piece ? sorted.size() - i0 : piece;
-        memcpy(x->h_stage, sorted.data() + i0, m * sizeof(uint64_t));
-        MHIP(hipMemcpyAsync(d_sorted + i0, x->h_stage, m * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));        // the staging is free again
+    for (size_t i0 = 0; i0 < n; i0 += piece) {
+        const size_t m = n - i0 < piece ? n - i0 : piece;
+        memcpy(x->h_stage, src + i0, m * sizeof(uint64_t));
+        MHIP(hipMemcpyAsync(d_dst + i0, x->h_stage, m * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
+        if (wait_last || i0 + m < n) MHIP(hipStreamSynchronize(x->stream));
     }
     return SVO_OK;
 }
@@ -1022,7 +1027,7 @@ static int retire_move_rows(svo_desc_index* x, const RetireRows& rows, int row_l
     MHIP(hipGetLastError());
     MHIP(span_mark(x, true, 1));
     MHIP(hipStreamSynchronize(x->stream));
-    MHIP(retire_span_read(x));
+    MHIP(span_read(x, x->retire_ms));
     return SVO_OK;
 }
 
@@ -1032,6 +1037,36 @@ static void retire_fill_map(int32_t* kept_before, int row_lo, int row_hi, int n0
     if (!ranks_down) for (int r = row_lo; r < row_hi; r++) kept_before[r] = r;
     for (int r = row_hi; r <= n0; r++) kept_before[r] = r - (row_hi - row_lo - kept);
 }
+
+// The end that retire and consolidate share, from where the kernels that flag and rank the scope's rows are on the stream to where
+// size has moved.  keep, rank: the scope's flags and ranks in the scratch (null: no kernel ran, every row stays); ctl_bytes: how much
+// of the control block the caller reads.  The control block and the count of kept rows come down and the first wait ends the part
+// that changes nothing: with the table's flag up the call ends there, under `overflow`.  Then the ranks down where the caller wants
+// the map, the move of the rows and its wait (retire_move_rows), the rest of the map, and size.  -> *kept of the scope's rows.
+static int retire_finish(svo_desc_index* x, const RetireRows& rows, int row_lo, int row_hi, const uint8_t* keep, const int32_t* rank, void* bounce,
+                         size_t ctl_bytes, const char* overflow, int32_t* kept_before, int* kept) {
+    const int n0 = x->size, m = row_hi - row_lo, slab = n0 - row_lo < x->retire_slab ? n0 - row_lo : x->retire_slab;
+    int rc;
+    bool ranks_down = false;
+    *kept = m;
+    if (keep) {
+        MHIP(hipMemcpyAsync(&x->h_retire->ctl, x->d_retire_ctl, ctl_bytes, hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipMemcpyAsync(&x->h_retire->kept, rank + m, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipStreamSynchronize(x->stream));        // nothing has moved yet: a failure up to here changes nothing
+        MHIP(span_read(x, x->retire_ms));
+        if (x->h_retire->ctl.table_full) return fail(SVO_ERR_INTERNAL, overflow);
+        *kept = x->h_retire->kept;
+        if (kept_before && *kept < m) {
+            if ((rc = retire_download_ranks(x, rank, row_lo, m, kept_before)) != SVO_OK) return rc;
+            ranks_down = true;
+        }
+        if (*kept < m && (rc = retire_move_rows(x, rows, row_lo, row_hi, *kept, keep, rank, bounce, slab)) != SVO_OK) return rc;
+    }
+    if (kept_before) retire_fill_map(kept_before, row_lo, row_hi, n0, *kept, ranks_down);
+    x->size = n0 - (m - *kept);
+    return SVO_OK;
+}
+static_assert(offsetof(RetireCtl, table_full) == 0 && offsetof(ConsCtl, table_full) == 0, "retire_finish reads the flag where both control blocks keep it");
 
 extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* rule, int32_t* kept_before, int* n_kept) {
     if (!x || !rule) return fail(SVO_ERR_ARG, "svo_desc_index_retire: null index / rule");
@@ -1046,8 +1081,10 @@ extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* r
     x->retire_ms = 0.f;
     MHIP(hipSetDevice(x->device));
     const int n0 = x->size, m = row_hi - row_lo;
-    int kept = m;                                     // of the scope's rows
-    bool ranks_down = false;
+    const RetireRows rows{(uint4*)x->d_desc, x->d_ids, (uint4*)x->d_points};
+    const uint8_t* keep = nullptr;                    // stays null where no kernel runs
+    int32_t* rank = nullptr;
+    void* bounce = nullptr;
     if (flags != 0 && m > 0) {
         std::vector<uint64_t> sorted;
         if (flags & RETIRE_BY_IDS) {
@@ -1055,40 +1092,28 @@ extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* r
             std::sort(sorted.begin(), sorted.end());
             sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
         }
-        const int slab = n0 - row_lo < x->retire_slab ? n0 - row_lo : x->retire_slab;
         const RetireLayout l = retire_layout(m, n0 - row_lo, (int32_t)sorted.size(), x->retire_slab, flags);
-        if ((rc = retire_ctl_room(x)) != SVO_OK || (rc = retire_room(x, l.total)) != SVO_OK) return rc;
-        uint8_t* keep = x->d_retire + l.keep;
-        int32_t* rank = (int32_t*)(x->d_retire + l.rank);
-        int32_t* counts = (int32_t*)(x->d_retire + l.counts);
-        int32_t* table = (int32_t*)(x->d_retire + l.table);
-        uint64_t* d_sorted = (uint64_t*)(x->d_retire + l.ids);
-        void* bounce = x->d_retire + l.bounce;
-        const RetireRows rows{(uint4*)x->d_desc, x->d_ids, (uint4*)x->d_points};
-        if ((rc = retire_upload_ids(x, sorted, d_sorted)) != SVO_OK) return rc;
+        if ((rc = retire_ctl_room(x)) != SVO_OK || (rc = retire_scratch(x, l.total)) != SVO_OK) return rc;
+        uint8_t* d_keep = x->retire.p + l.keep;
+        rank = (int32_t*)(x->retire.p + l.rank);
+        int32_t* counts = (int32_t*)(x->retire.p + l.counts);
+        int32_t* table = (int32_t*)(x->retire.p + l.table);
+        uint64_t* d_sorted = (uint64_t*)(x->retire.p + l.ids);
+        keep = d_keep; bounce = x->retire.p + l.bounce;
+        if ((rc = upload_list(x, sorted.data(), sorted.size(), d_sorted)) != SVO_OK) return rc;
         MHIP(hipMemsetAsync(&x->d_retire_ctl->table_full, 0, sizeof(int32_t), x->stream));
         const uint32_t slots = retire_table_slots(m);
         if (flags & RETIRE_LATEST_PER_ID) MHIP(hipMemsetAsync(table, 0xFF, (size_t)slots * sizeof(int32_t), x->stream));   // RETIRE_EMPTY
         MHIP(span_mark(x, true, 0));
-        launch_retire_flags(rows, row_lo, m, flags, rule->tag_lo, rule->tag_hi, d_sorted, (int32_t)sorted.size(), keep, x->stream);
-        if (flags & RETIRE_LATEST_PER_ID) launch_retire_latest(rows, row_lo, m, keep, table, slots, x->d_retire_ctl, x->stream);
-        launch_retire_ranks(keep, m, counts, rank, x->stream);
+        launch_retire_flags(rows, row_lo, m, flags, rule->tag_lo, rule->tag_hi, d_sorted, (int32_t)sorted.size(), d_keep, x->stream);
+        if (flags & RETIRE_LATEST_PER_ID) launch_retire_latest(rows, row_lo, m, d_keep, table, slots, x->d_retire_ctl, x->stream);
+        launch_retire_ranks(d_keep, m, counts, rank, x->stream);
         MHIP(hipGetLastError());
         MHIP(span_mark(x, true, 1));
-        MHIP(hipMemcpyAsync(&x->h_retire->ctl.table_full, &x->d_retire_ctl->table_full, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipMemcpyAsync(&x->h_retire->kept, rank + m, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));        // nothing has moved yet: a failure up to here changes nothing
-        MHIP(retire_span_read(x));
-        if (x->h_retire->ctl.table_full) return fail(SVO_ERR_INTERNAL, "svo_desc_index_retire: the latest-per-id table overflowed (nothing was changed)");
-        kept = x->h_retire->kept;
-        if (kept_before && kept < m) {
-            if ((rc = retire_download_ranks(x, rank, row_lo, m, kept_before)) != SVO_OK) return rc;
-            ranks_down = true;
-        }
-        if (kept < m && (rc = retire_move_rows(x, rows, row_lo, row_hi, kept, keep, rank, bounce, slab)) != SVO_OK) return rc;
     }
-    if (kept_before) retire_fill_map(kept_before, row_lo, row_hi, n0, kept, ranks_down);
-    x->size = n0 - (m - kept);
+    int kept = m;                                     // of the scope's rows
+    if ((rc = retire_finish(x, rows, row_lo, row_hi, keep, rank, bounce, sizeof(int32_t),
+                            "svo_desc_index_retire: the latest-per-id table overflowed (nothing was changed)", kept_before, &kept)) != SVO_OK) return rc;
     if (n_kept) *n_kept = x->size;
     return SVO_OK;
 }
@@ -1096,7 +1121,7 @@ extern "C" int svo_desc_index_retire(svo_desc_index* x, const svo_retire_rule* r
 extern "C" int svo_desc_index_transform_points(svo_desc_index* x, const double T[16], int row_lo, int row_hi, int32_t tag_lo, int32_t tag_hi,
                                                int* n_moved, int* n_skipped) {
     if (!x || !T) return fail(SVO_ERR_ARG, "svo_desc_index_transform_points: null index / T");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_transform_points: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("svo_desc_index_transform_points");
     for (int i = 0; i < 16; i++) if (!isfinite(T[i])) return fail(SVO_ERR_ARG, "svo_desc_index_transform_points: T has a non-finite entry");
     int rc = row_range(x, row_lo, row_hi);
     if (rc != SVO_OK) return rc;
@@ -1114,7 +1139,7 @@ extern "C" int svo_desc_index_transform_points(svo_desc_index* x, const double T
         MHIP(span_mark(x, true, 1));
         MHIP(hipMemcpyAsync(&x->h_retire->ctl, x->d_retire_ctl, sizeof(RetireCtl), hipMemcpyDeviceToHost, x->stream));
         MHIP(hipStreamSynchronize(x->stream));
-        MHIP(retire_span_read(x));
+        MHIP(span_read(x, x->retire_ms));
         for (const RetireCounts& c : x->h_retire->ctl.counts) { moved += c.n_moved; skipped += c.n_skipped; }
     }
     if (n_moved) *n_moved = moved;
@@ -1144,21 +1169,18 @@ static const char* fuse_refusal_text(FuseRefusal e) {
     }
 }
 
-static int fuse_ctl_room(svo_desc_index* x) {
-    if (x->h_fuse) return SVO_OK;
-    MHIP(hipHostMalloc((void**)&x->h_fuse, sizeof(FuseCtl), hipHostMallocDefault));
-    return SVO_OK;
-}
+static int fuse_ctl_room(svo_desc_index* x) { return room(x, x->h_fuse, sizeof(FuseCtl), true); }
 
-// one list of a relabel call onto the device through the pinned staging, piece by piece (retire_upload_ids' way)
-static int fuse_upload_list(svo_desc_index* x, const uint64_t* src, size_t n, uint64_t* d_dst) {
-    const size_t piece = RETIRE_STAGE_BYTES / sizeof(uint64_t);
-    for (size_t i0 = 0; i0 < n; i0 += piece) {
-        const size_t m = n - i0 < piece ? n - i0 : piece;
-        memcpy(x->h_stage, src + i0, m * sizeof(uint64_t));
-        MHIP(hipMemcpyAsync(d_dst + i0, x->h_stage, m * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));        // the staging is free again
-    }
+// A call's lists and table in the maintenance scratch (room for fuse_layout(n) is there): the host lists of a relabel call up,
+// where k_fuse_map would put a fuse call's, then the control block and the table cleared.
+struct FuseDev { FuseCtl* ctl; uint64_t *from, *to; int32_t* table; };
+static int fuse_begin(svo_desc_index* x, int n, const uint64_t* from_ids, const uint64_t* to_ids, FuseDev* f) {
+    const FuseLayout fl = fuse_layout(n);
+    uint8_t* d = x->retire.p;
+    *f = FuseDev{(FuseCtl*)(d + fl.ctl), (uint64_t*)(d + fl.from), (uint64_t*)(d + fl.to), (int32_t*)(d + fl.table)};
+    if (from_ids) { ROOM(upload_list(x, from_ids, (size_t)n, f->from)); ROOM(upload_list(x, to_ids, (size_t)n, f->to)); }
+    MHIP(hipMemsetAsync(f->ctl, 0, sizeof(FuseCtl), x->stream));
+    MHIP(hipMemsetAsync(f->table, 0xFF, (size_t)fuse_table_slots(n) * sizeof(int32_t), x->stream));      // FUSE_EMPTY
     return SVO_OK;
 }
 
@@ -1172,8 +1194,8 @@ static int fuse_counts(const FuseCtl& c, int* n_rows) {
 }
 
 // What match_near (stage 1), pair_near (2) and fuse (3) share.  q: the request, checked and with its spans resolved.  Everything is
-// enqueued on the index's stream — the gated search with rows [src_lo, src_hi) of the index as its queries, in launches of the
-// unguided plan's size, the pair kernel, the map, the table and the sweep, the copies back — and the host waits once.
+// enqueued on the index's stream — the clears, the near search with rows [src_lo, src_hi) of the index as its queries (the unguided
+// plan, marked near), the pair kernel, the map, the table and the sweep, the copies back — and the host waits once.
 // times: from the first kernel to the last
 static int fuse_run(svo_desc_index* x, const FuseRequest& q, int stage, svo_desc_match* rows, int* n_pairs, svo_fuse_result* res,
                     int32_t* pair_src, int32_t* pair_dst) {
@@ -1181,55 +1203,26 @@ static int fuse_run(svo_desc_index* x, const FuseRequest& q, int stage, svo_desc
     int rc;
     MHIP(call_begin(x));
     SearchPlan plan;
-    const FuseLayout fl = fuse_layout(n);
-    if ((stage > 1 && (rc = align_room(x)) != SVO_OK) || (stage > 2 && ((rc = fuse_ctl_room(x)) != SVO_OK || (rc = retire_room(x, fl.total)) != SVO_OK)) ||
+    if ((stage > 1 && (rc = align_room(x)) != SVO_OK) || (stage > 2 && ((rc = fuse_ctl_room(x)) != SVO_OK || (rc = retire_scratch(x, fuse_layout(n).total)) != SVO_OK)) ||
         (rc = search_plan(x, n, q.dst_lo, q.dst_hi, nullptr, &plan)) != SVO_OK) return rc;
-    FuseCtl* ctl = nullptr;
-    int32_t* table = nullptr;
-    if (stage > 2) {
-        ctl = (FuseCtl*)(x->d_retire + fl.ctl); table = (int32_t*)(x->d_retire + fl.table);
-        MHIP(hipMemsetAsync(ctl, 0, sizeof(FuseCtl), x->stream));
-        MHIP(hipMemsetAsync(table, 0xFF, (size_t)fuse_table_slots(n) * sizeof(int32_t), x->stream));      // FUSE_EMPTY
-    }
-    MHIP(span_mark(x, true, 0));
-    for (int i0 = 0; i0 < n; i0 += plan.batch) {
-        const int m = n - i0 < plan.batch ? n - i0 : plan.batch;
-        launch_desc_match_near((const uint32_t*)x->d_desc, x->d_ids, x->d_points, q.src_lo + i0, m, q.radius, plan.r, x->d_part, x->stream);
-        launch_desc_match_merge(x->d_part, x->d_ids, m, plan.r, x->d_out + i0, x->stream);
-    }
-    if (stage == 1) {
-        MHIP(hipGetLastError());
-        MHIP(span_mark(x, true, 1));
-        if (n > 0) MHIP(hipMemcpyAsync(x->h_out, x->d_out, (size_t)n * sizeof(svo_desc_match), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));
-        MHIP(span_read(x));
-        if (n > 0) memcpy(rows, x->h_out, (size_t)n * sizeof(svo_desc_match));
-        return SVO_OK;
-    }
-    const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
-    uint8_t *dv = x->d_align, *h = x->h_align;
-    AlignOut* d_res = (AlignOut*)(dv + l.out);
-    int32_t *d_src = (int32_t*)(dv + l.pair_src), *d_dst = (int32_t*)(dv + l.pair_dst);
-    const AlignPairsArgs pa{x->d_out, x->d_points, x->d_ids, q.src_lo, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den},
-                            d_src, d_dst, dv + l.pair_inlier, (float*)(dv + l.pairs), d_res};
-    launch_align_pairs(pa, x->stream);
+    plan.near_lo = q.src_lo; plan.near_radius = q.radius;
+    FuseDev f{};
+    if ((stage > 2 && (rc = fuse_begin(x, n, nullptr, nullptr, &f)) != SVO_OK) || (rc = search_enqueue(x, plan, n, true)) != SVO_OK) return rc;
+    if (stage == 1) return rows_down(x, n, rows);
+    const PairStage ps = pairs_enqueue(x, q.src_lo, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den});
     if (stage == 3) {
-        uint64_t *from = (uint64_t*)(x->d_retire + fl.from), *to = (uint64_t*)(x->d_retire + fl.to);
-        launch_fuse_map(&d_res->n_pairs, n, d_src, d_dst, x->d_ids, from, to, ctl, x->stream);
-        launch_fuse_relabel(from, to, &d_res->n_pairs, n, table, fuse_table_slots(n), x->d_ids, q.relabel_lo, q.relabel_hi, ctl, x->stream);
+        launch_fuse_map(&ps.out->n_pairs, n, ps.src, ps.dst, x->d_ids, f.from, f.to, f.ctl, x->stream);
+        launch_fuse_relabel(f.from, f.to, &ps.out->n_pairs, n, f.table, fuse_table_slots(n), x->d_ids, q.relabel_lo, q.relabel_hi, f.ctl, x->stream);
     }
     MHIP(hipGetLastError());
-    MHIP(span_mark(x, true, 1));
-    MHIP(hipMemcpyAsync(h, dv, l.pair_inlier, hipMemcpyDeviceToHost, x->stream));          // the result row and the two row lists
-    if (stage == 3) MHIP(hipMemcpyAsync(x->h_fuse, ctl, sizeof(FuseCtl), hipMemcpyDeviceToHost, x->stream));
+    MHIP(span_mark(x, true, 1));                      // the span's end moves from the search's last kernel to the call's
+    MHIP(hipMemcpyAsync(x->h_align, x->d_align, ps.l.pair_inlier, hipMemcpyDeviceToHost, x->stream));   // the result row and the two row lists
+    if (stage == 3) MHIP(hipMemcpyAsync(x->h_fuse, f.ctl, sizeof(FuseCtl), hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
-    MHIP(span_read(x));
-    const int np = ((const AlignOut*)(h + l.out))->n_pairs;
+    MHIP(span_read(x, x->last_ms));
     int n_rows = 0;
     if (stage == 3 && (rc = fuse_counts(*x->h_fuse, &n_rows)) != SVO_OK) return rc;
-    if (n_pairs) *n_pairs = np;
-    if (pair_src) memcpy(pair_src, h + l.pair_src, (size_t)np * sizeof(int32_t));
-    if (pair_dst) memcpy(pair_dst, h + l.pair_dst, (size_t)np * sizeof(int32_t));
+    const int np = pairs_read(x, ps.l, n_pairs, pair_src, pair_dst);
     if (res) { res->n_pairs = np; res->n_same = x->h_fuse->n_same; res->n_fused = x->h_fuse->n_fused; res->n_rows_relabelled = n_rows; }
     return SVO_OK;
 }
@@ -1240,7 +1233,7 @@ static FuseRequest fuse_request(const svo_fuse_params* p) {
 
 extern "C" int svo_desc_index_match_near(svo_desc_index* x, int src_lo, int src_hi, int dst_lo, int dst_hi, float radius, svo_desc_match* out) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "landmark fusion: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("landmark fusion");
     FuseRequest q{src_lo, src_hi, dst_lo, dst_hi, 0, -1, 0, 1, 1, radius};
     if (const FuseRefusal e = fuse_check_search(q, x->size); e != FUSE_OK) return fail(SVO_ERR_ARG, fuse_refusal_text(e));
     if (q.src_hi > q.src_lo && !out) return fail(SVO_ERR_ARG, "svo_desc_index_match_near: null out");
@@ -1249,7 +1242,7 @@ extern "C" int svo_desc_index_match_near(svo_desc_index* x, int src_lo, int src_
 
 extern "C" int svo_desc_index_pair_near(svo_desc_index* x, const svo_fuse_params* p, int* n_pairs, int32_t* pair_src, int32_t* pair_dst) {
     if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_pair_near: null index / params");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "landmark fusion: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("landmark fusion");
     FuseRequest q = fuse_request(p);
     if (const FuseRefusal e = fuse_check(q, x->size); e != FUSE_OK) return fail(SVO_ERR_ARG, fuse_refusal_text(e));
     return fuse_run(x, q, 2, nullptr, n_pairs, nullptr, pair_src, pair_dst);
@@ -1257,7 +1250,7 @@ extern "C" int svo_desc_index_pair_near(svo_desc_index* x, const svo_fuse_params
 
 extern "C" int svo_desc_index_fuse(svo_desc_index* x, const svo_fuse_params* p, svo_fuse_result* res, int32_t* pair_src, int32_t* pair_dst) {
     if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_fuse: null index / params");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "landmark fusion: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("landmark fusion");
     FuseRequest q = fuse_request(p);
     if (const FuseRefusal e = fuse_check(q, x->size); e != FUSE_OK) return fail(SVO_ERR_ARG, fuse_refusal_text(e));
     return fuse_run(x, q, 3, nullptr, nullptr, res, pair_src, pair_dst);
@@ -1274,21 +1267,15 @@ extern "C" int svo_desc_index_relabel(svo_desc_index* x, int n, const uint64_t* 
     MHIP(call_begin(x));
     int n_rows = 0;
     if (n > 0 && row_hi > row_lo) {
-        const FuseLayout fl = fuse_layout(n);
-        if ((rc = fuse_ctl_room(x)) != SVO_OK || (rc = retire_room(x, fl.total)) != SVO_OK) return rc;
-        FuseCtl* ctl = (FuseCtl*)(x->d_retire + fl.ctl);
-        uint64_t *from = (uint64_t*)(x->d_retire + fl.from), *to = (uint64_t*)(x->d_retire + fl.to);
-        int32_t* table = (int32_t*)(x->d_retire + fl.table);
-        if ((rc = fuse_upload_list(x, from_ids, (size_t)n, from)) != SVO_OK || (rc = fuse_upload_list(x, to_ids, (size_t)n, to)) != SVO_OK) return rc;
-        MHIP(hipMemsetAsync(ctl, 0, sizeof(FuseCtl), x->stream));
-        MHIP(hipMemsetAsync(table, 0xFF, (size_t)fuse_table_slots(n) * sizeof(int32_t), x->stream));      // FUSE_EMPTY
+        FuseDev f;
+        if ((rc = fuse_ctl_room(x)) != SVO_OK || (rc = retire_scratch(x, fuse_layout(n).total)) != SVO_OK || (rc = fuse_begin(x, n, from_ids, to_ids, &f)) != SVO_OK) return rc;
         MHIP(span_mark(x, true, 0));
-        launch_fuse_relabel(from, to, nullptr, n, table, fuse_table_slots(n), x->d_ids, row_lo, row_hi, ctl, x->stream);
+        launch_fuse_relabel(f.from, f.to, nullptr, n, f.table, fuse_table_slots(n), x->d_ids, row_lo, row_hi, f.ctl, x->stream);
         MHIP(hipGetLastError());
         MHIP(span_mark(x, true, 1));
-        MHIP(hipMemcpyAsync(x->h_fuse, ctl, sizeof(FuseCtl), hipMemcpyDeviceToHost, x->stream));
+        MHIP(hipMemcpyAsync(x->h_fuse, f.ctl, sizeof(FuseCtl), hipMemcpyDeviceToHost, x->stream));
         MHIP(hipStreamSynchronize(x->stream));
-        MHIP(span_read(x));
+        MHIP(span_read(x, x->last_ms));
         if ((rc = fuse_counts(*x->h_fuse, &n_rows)) != SVO_OK) return rc;
     }
     if (n_rows_relabelled) *n_rows_relabelled = n_rows;
@@ -1323,18 +1310,6 @@ static const char* place_refusal_text(PlaceRefusal e) {
     }
 }
 
-// Room for `need` bytes of pinned memory for a call's results: retire_room's pattern; the outgrown blocks go with the index.
-static int place_host_room(svo_desc_index* x, size_t need) {
-    if (need <= x->place_host_cap) return SVO_OK;
-    size_t cap = x->place_host_cap ? 2 * x->place_host_cap : RETIRE_SCRATCH_FIRST;
-    while (cap < need) cap *= 2;
-    uint8_t* p = nullptr;
-    MHIP(hipHostMalloc((void**)&p, cap, hipHostMallocDefault));
-    if (x->h_place) x->outgrown_pinned.push_back(x->h_place);
-    x->h_place = p; x->place_host_cap = cap;
-    return SVO_OK;
-}
-
 // where a call's results go, each null when not wanted
 struct PlaceOutputs {
     int32_t *votes, *rows, *row_first, *row_end;      // tag_votes: one entry per bin
@@ -1352,10 +1327,10 @@ static int place_run(svo_desc_index* x, const PlaceRequest& q, bool pick, int n,
     const int n_bins = q.tag_hi - q.tag_lo + 1;
     const PlaceLayout l = place_layout(n, n_bins, pick);
     const size_t down = sizeof(PlaceCtl) + (pick ? 0 : sizeof(PlaceBin) * (size_t)n_bins);
-    if ((rc = retire_room(x, l.total)) != SVO_OK || (rc = place_host_room(x, down)) != SVO_OK) return rc;
-    PlaceCtl* ctl = (PlaceCtl*)(x->d_retire + l.ctl);
-    uint64_t* d_list = (uint64_t*)(x->d_retire + l.ids);
-    PlaceBin* bins = (PlaceBin*)(x->d_retire + l.bins);
+    if ((rc = retire_scratch(x, l.total)) != SVO_OK || (rc = grow(x, x->place, down, RETIRE_SCRATCH_FIRST, 0, true)) != SVO_OK) return rc;
+    PlaceCtl* ctl = (PlaceCtl*)(x->retire.p + l.ctl);
+    uint64_t* d_list = (uint64_t*)(x->retire.p + l.ids);
+    PlaceBin* bins = (PlaceBin*)(x->retire.p + l.bins);
     PlaceSweepArgs a{d_list, nullptr, nullptr, n, x->d_ids, x->d_points, q.row_lo, q.row_hi, q.tag_lo, q.tag_hi, bins, ctl};
     if (query) {                                      // rule 1: svo_desc_index_select's path, without pixels and without its copies back
         const DevBuffers* d = nullptr;
@@ -1364,34 +1339,24 @@ static int place_run(svo_desc_index* x, const PlaceRequest& q, bool pick, int n,
         if ((rc = svo_reloc_stage_ctx(x->device, n > 64 ? n : 64, rp.ransac_iterations, rp.reproj_error, rp.confidence, &d)) != SVO_OK ||
             (rc = search_plan(x, n, q.row_lo, q.row_hi, nullptr, &plan)) != SVO_OK || (rc = stage_queries(x, n, query, true, nullptr)) != SVO_OK ||
             (rc = search_enqueue(x, plan, n, false)) != SVO_OK) return rc;
-        RelocArgs s;
-        s.match = x->d_out; s.points = x->d_points; s.xy = x->d_qxy; s.n = n;
-        s.rule = RelocRule{q.max_dist, q.ratio_num, q.ratio_den}; s.min_candidates = rp.min_candidates;
-        s.out_xy = d->tl1; s.out_xyz = d->world; s.st = d->st;
-        s.cand_query = x->d_reloc->cand_query; s.cand_row = x->d_reloc->cand_row; s.n_cand = &x->d_reloc->n_cand;
-        launch_reloc_select(s, x->stream);
+        select_enqueue(x, d, n, RelocRule{q.max_dist, q.ratio_num, q.ratio_den}, rp.min_candidates);
         a.list = nullptr; a.m_rows = x->d_reloc->cand_row; a.n_dev = &x->d_reloc->n_cand;
-    } else if (n > 0) {                               // n <= 4096 ids: one piece of the pinned staging
-        memcpy(x->h_stage, ids, (size_t)n * sizeof(uint64_t));
-        MHIP(hipMemcpyAsync(d_list, x->h_stage, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, x->stream));
+    } else if ((rc = upload_list(x, ids, (size_t)n, d_list, false)) != SVO_OK) {    // n <= 4096 ids: one piece of the pinned staging, no wait
+        return rc;
     }
     MHIP(span_mark(x, true, 0));
     MHIP(hipMemsetAsync(ctl, 0, sizeof(PlaceCtl), x->stream));
     MHIP(hipMemsetAsync(bins, 0, sizeof(PlaceBin) * (size_t)n_bins, x->stream));
     launch_place_sweep(a, x->place_combine, x->stream);
-    if (pick) launch_place_pick(bins, n_bins, q.tag_lo, q.min_votes, q.separation, q.max_places, (uint64_t*)(x->d_retire + l.keys), ctl, x->stream);
+    if (pick) launch_place_pick(bins, n_bins, q.tag_lo, q.min_votes, q.separation, q.max_places, (uint64_t*)(x->retire.p + l.keys), ctl, x->stream);
     MHIP(hipGetLastError());
     MHIP(span_mark(x, true, 1));
-    uint8_t* h = x->h_place;
+    uint8_t* h = x->place.p;
     MHIP(hipMemcpyAsync(h, ctl, sizeof(PlaceCtl), hipMemcpyDeviceToHost, x->stream));
     if (!pick) MHIP(hipMemcpyAsync(h + sizeof(PlaceCtl), bins, sizeof(PlaceBin) * (size_t)n_bins, hipMemcpyDeviceToHost, x->stream));
-    RelocHost* hr = x->h_reloc;
-    if (query && n > 0) {
-        MHIP(hipMemcpyAsync(&hr->out, x->d_reloc, offsetof(RelocDevOut, cand_query) + (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipMemcpyAsync(hr->out.cand_row, x->d_reloc->cand_row, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-    }
+    if (query && (rc = cands_down(x, n)) != SVO_OK) return rc;            // a call with queries has n > 0
     MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
-    MHIP(span_read(x));
+    MHIP(span_read(x, x->last_ms));
     const PlaceCtl& c = *(const PlaceCtl*)h;
     if (c.set_full) return fail(SVO_ERR_INTERNAL, "place candidates: the set overflowed");
     if (!pick) {
@@ -1406,17 +1371,13 @@ static int place_run(svo_desc_index* x, const PlaceRequest& q, bool pick, int n,
     }
     if (o.res) { o.res->n_landmarks = c.n_landmarks; o.res->n_tags_voted = c.n_tags_voted; o.res->n_places = c.n_places; }
     if (o.places) memcpy(o.places, c.places, (size_t)c.n_places * sizeof(svo_place));
-    if (query && n > 0) {
-        const int nc = hr->out.n_cand;
-        if (o.cand_query) memcpy(o.cand_query, hr->out.cand_query, (size_t)nc * sizeof(int32_t));
-        if (o.cand_row) memcpy(o.cand_row, hr->out.cand_row, (size_t)nc * sizeof(int32_t));
-    }
+    if (query) cands_read(x, o.cand_query, o.cand_row);
     return SVO_OK;
 }
 
 static int place_ids_check(const svo_desc_index* x, int n_ids, const uint64_t* ids) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "place candidates: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("place candidates");
     if (n_ids < 0 || n_ids > SVO_PLACE_MAX_IDS) return fail(SVO_ERR_ARG, "place candidates: n_ids must be 0 .. 4096");
     if (n_ids > 0 && !ids) return fail(SVO_ERR_ARG, "place candidates: null ids");
     return SVO_OK;
@@ -1446,7 +1407,7 @@ extern "C" int svo_desc_index_places_from_ids(svo_desc_index* x, int n_ids, cons
 extern "C" int svo_desc_index_places(svo_desc_index* x, int n, const uint8_t* query, const svo_place_params* p, svo_place_result* res,
                                      svo_place* places, int32_t* cand_query, int32_t* cand_row) {
     if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_places: null index / params");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "place candidates: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("place candidates");
     if (n < 0 || n > SVO_RELOC_MAX_QUERIES) return fail(SVO_ERR_ARG, "svo_desc_index_places: n must be 0 .. 4096");
     if (n > 0 && !query) return fail(SVO_ERR_ARG, "svo_desc_index_places: null query");
     PlaceRequest q = place_request(p);
@@ -1466,7 +1427,7 @@ extern "C" void svo_consolidate_params_default(svo_consolidate_params* p, float 
 
 extern "C" int svo_desc_index_consolidate(svo_desc_index* x, const svo_consolidate_params* p, svo_consolidate_result* res, int32_t* kept_before) {
     if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_consolidate: null index / params");
-    if (!x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_consolidate: the index has no points (svo_desc_index_enable_points)");
+    if (!x->d_points) return no_points("svo_desc_index_consolidate");
     ConsRequest q{p->row_lo, p->row_hi, p->tag_lo, p->tag_hi, p->radius};
     switch (cons_check(q, x->size)) {
         case CONS_RANGE: return fail(SVO_ERR_ARG, "svo_desc_index_consolidate: the row range must satisfy 0 <= row_lo <= row_hi <= size");
@@ -1477,27 +1438,25 @@ extern "C" int svo_desc_index_consolidate(svo_desc_index* x, const svo_consolida
     MHIP(hipSetDevice(x->device));
     const int row_lo = q.row_lo, row_hi = q.row_hi, n0 = x->size, m = row_hi - row_lo;
     int rc, kept = m;                                 // of the scope's rows
-    bool ranks_down = false;
     svo_consolidate_result r;
     memset(&r, 0, sizeof(r));
+    const RetireRows rows{(uint4*)x->d_desc, x->d_ids, (uint4*)x->d_points};
+    ConsWork w{};                                     // w.keep stays null where no kernel runs
+    void* bounce = nullptr;
     if (m > 0) {
-        const int slab = n0 - row_lo < x->retire_slab ? n0 - row_lo : x->retire_slab;
         const ConsLayout l = cons_layout(m, n0 - row_lo, x->retire_slab);
-        if ((rc = retire_ctl_room(x)) != SVO_OK || (rc = retire_room(x, l.total)) != SVO_OK) return rc;
+        if ((rc = retire_ctl_room(x)) != SVO_OK || (rc = retire_scratch(x, l.total)) != SVO_OK) return rc;
         ConsCtl* d_ctl = (ConsCtl*)x->d_retire_ctl;
-        const ConsCtl* h_ctl = (const ConsCtl*)&x->h_retire->ctl;
-        ConsWork w;
         w.row_lo = row_lo; w.n = m; w.tag_lo = q.tag_lo; w.tag_hi = q.tag_hi;
-        w.keep = x->d_retire + l.keep;
-        w.offset = (int32_t*)(x->d_retire + l.rank);
-        w.sums = (int32_t*)(x->d_retire + l.counts);
-        w.table = (int32_t*)(x->d_retire + l.table);
-        w.count = (int32_t*)(x->d_retire + l.count);
+        w.keep = x->retire.p + l.keep;
+        w.offset = (int32_t*)(x->retire.p + l.rank);
+        w.sums = (int32_t*)(x->retire.p + l.counts);
+        w.table = (int32_t*)(x->retire.p + l.table);
+        w.count = (int32_t*)(x->retire.p + l.count);
         w.slots = retire_table_slots(m);
-        w.list = (int32_t*)(x->d_retire + l.list);
+        w.list = (int32_t*)(x->retire.p + l.list);
         w.ctl = d_ctl;
-        void* bounce = x->d_retire + l.bounce;
-        const RetireRows rows{(uint4*)x->d_desc, x->d_ids, (uint4*)x->d_points};
+        bounce = x->retire.p + l.bounce;
         MHIP(hipMemsetAsync(d_ctl, 0, sizeof(ConsCtl), x->stream));
         MHIP(hipMemsetAsync(w.table, 0xFF, (size_t)w.slots * sizeof(int32_t), x->stream));   // RETIRE_EMPTY
         MHIP(hipMemsetAsync(w.count, 0, (size_t)w.slots * sizeof(int32_t), x->stream));
@@ -1506,23 +1465,13 @@ extern "C" int svo_desc_index_consolidate(svo_desc_index* x, const svo_consolida
         launch_retire_ranks(w.keep, m, w.sums, w.offset, x->stream);             // the offsets have served: their room takes the ranks
         MHIP(hipGetLastError());
         MHIP(span_mark(x, true, 1));
-        MHIP(hipMemcpyAsync(&x->h_retire->ctl, d_ctl, sizeof(ConsCtl), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipMemcpyAsync(&x->h_retire->kept, w.offset + m, sizeof(int32_t), hipMemcpyDeviceToHost, x->stream));
-        MHIP(hipStreamSynchronize(x->stream));        // with the flag up nothing was written; without it no row has moved yet
-        MHIP(retire_span_read(x));
-        if (h_ctl->table_full) return fail(SVO_ERR_INTERNAL, "svo_desc_index_consolidate: the table of ids overflowed (nothing was changed)");
-        for (const ConsCounts& c : h_ctl->counts) {
+    }
+    if ((rc = retire_finish(x, rows, row_lo, row_hi, w.keep, w.offset, bounce, sizeof(ConsCtl),
+                            "svo_desc_index_consolidate: the table of ids overflowed (nothing was changed)", kept_before, &kept)) != SVO_OK) return rc;
+    if (m > 0)
+        for (const ConsCounts& c : ((const ConsCtl*)&x->h_retire->ctl)->counts) {
             r.n_members += c.n_members; r.n_groups += c.n_groups; r.n_far_views += c.n_far_views; r.n_capped_groups += c.n_capped_groups;
         }
-        kept = x->h_retire->kept;
-        if (kept_before && kept < m) {
-            if ((rc = retire_download_ranks(x, w.offset, row_lo, m, kept_before)) != SVO_OK) return rc;
-            ranks_down = true;
-        }
-        if (kept < m && (rc = retire_move_rows(x, rows, row_lo, row_hi, kept, w.keep, w.offset, bounce, slab)) != SVO_OK) return rc;
-    }
-    if (kept_before) retire_fill_map(kept_before, row_lo, row_hi, n0, kept, ranks_down);
-    x->size = n0 - (m - kept);
     r.n_dropped = m - kept;
     r.n_kept = x->size;
     if (res) *res = r;
@@ -1533,7 +1482,7 @@ extern "C" int svo_desc_index_consolidate(svo_desc_index* x, const svo_consolida
 // pinned staging an append goes up through ----
 extern "C" int svo_desc_index_read_rows(svo_desc_index* x, int row_lo, int row_hi, uint8_t* desc, uint64_t* ids, float* xyz, int32_t* tags) {
     if (!x) return fail(SVO_ERR_ARG, "null index");
-    if ((xyz || tags) && !x->d_points) return fail(SVO_ERR_STATE, "svo_desc_index_read_rows: the index has no points (svo_desc_index_enable_points)");
+    if ((xyz || tags) && !x->d_points) return no_points("svo_desc_index_read_rows");
     if (const int rc = row_range(x, row_lo, row_hi); rc != SVO_OK) return rc;
     MHIP(hipSetDevice(x->device));
     uint8_t* h_ids = x->h_stage + (size_t)MATCH_STAGE_ROWS * SVO_DESC_BYTES;
@@ -1567,27 +1516,13 @@ static_assert(sizeof(svo_track_obs) == INSERT_OBS_BYTES && offsetof(svo_track_ob
 struct InsertCall { uint32_t need; bool with_points; const uint64_t* id_base; const double* cam_to_map; const int32_t* tags; };
 
 static int insert_host_room(svo_desc_index* x) {
-    if (x->h_insert) return SVO_OK;
     const InsertLayout l = insert_layout(INSERT_MAX_ENTRIES, 0, 0);
-    MHIP(hipHostMalloc((void**)&x->h_insert, INSERT_HOST_DOWN + (l.down_end - l.down), hipHostMallocDefault));
-    return SVO_OK;
-}
-
-// room for `need` bytes of staged rows: part_room's pattern, the outgrown blocks freed with the index
-static int insert_rows_room(svo_desc_index* x, size_t need) {
-    if (need <= x->insert_rows_cap) return SVO_OK;
-    size_t cap = x->insert_rows_cap ? 2 * x->insert_rows_cap : INSERT_STAGE_FIRST;
-    while (cap < need) cap *= 2;
-    uint8_t* p = nullptr;
-    MHIP(hipHostMalloc((void**)&p, cap, hipHostMallocDefault));
-    if (x->h_insert_rows) x->outgrown_pinned.push_back(x->h_insert_rows);
-    x->h_insert_rows = p; x->insert_rows_cap = cap;
-    return SVO_OK;
+    return room(x, x->h_insert, INSERT_HOST_DOWN + (l.down_end - l.down), true);
 }
 
 // the refusals every batched insertion shares (rules 6 and 7, the part that needs no rows)
 static int insert_check(const svo_desc_index* x, int n, const InsertCall& c) {
-    if (c.with_points && !x->d_points) return fail(SVO_ERR_STATE, "batched insertion with points: the index has no points (svo_desc_index_enable_points)");
+    if (c.with_points && !x->d_points) return no_points("batched insertion with points");
     for (int b = 0; b < n && c.tags; b++) if (c.tags[b] < 0) return fail(SVO_ERR_ARG, "batched insertion: a tag must be >= 0 (nothing was added)");
     for (size_t i = 0; c.cam_to_map && i < (size_t)16 * n; i++)
         if (!isfinite(c.cam_to_map[i])) return fail(SVO_ERR_ARG, "batched insertion: cam_to_map has a non-finite entry (nothing was added)");
@@ -1609,11 +1544,11 @@ static int insert_group(svo_desc_index* x, int n, const InsertCall& c, const uin
     *total = 0;
     if (tiles == 0) { memset(n_added, 0, sizeof(int32_t) * (size_t)n); return SVO_OK; }
     const InsertLayout l = insert_layout(n, tiles, staged_rows);
-    if (const int rc = retire_room(x, l.total); rc != SVO_OK) return rc;
-    uint8_t* d = x->d_retire;
+    if (const int rc = retire_scratch(x, l.total); rc != SVO_OK) return rc;
+    uint8_t* d = x->retire.p;
     if (staged_rows > 0) {
-        MHIP(hipMemcpyAsync(d + l.obs, x->h_insert_rows, (size_t)staged_rows * INSERT_OBS_BYTES, hipMemcpyHostToDevice, x->stream));
-        MHIP(hipMemcpyAsync(d + l.desc, x->h_insert_rows + (size_t)staged_rows * INSERT_OBS_BYTES, (size_t)staged_rows * INSERT_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
+        MHIP(hipMemcpyAsync(d + l.obs, x->insert_rows.p, (size_t)staged_rows * INSERT_OBS_BYTES, hipMemcpyHostToDevice, x->stream));
+        MHIP(hipMemcpyAsync(d + l.desc, x->insert_rows.p + (size_t)staged_rows * INSERT_OBS_BYTES, (size_t)staged_rows * INSERT_DESC_BYTES, hipMemcpyHostToDevice, x->stream));
         obs = d + l.obs; desc = d + l.desc;
     }
     MHIP(hipMemcpyAsync(d, x->h_insert, c.cam_to_map ? l.up_end : l.T, hipMemcpyHostToDevice, x->stream));
@@ -1625,15 +1560,14 @@ static int insert_group(svo_desc_index* x, int n, const InsertCall& c, const uin
     w.ctl = (InsertCtl*)(d + l.down); w.n_added = (int32_t*)(d + l.n_added);
     w.need = c.need; w.with_points = c.with_points ? 1 : 0;
     w.at = at; w.room = x->capacity - at;
-    const bool timed = x->timing;
-    if (timed) MHIP(hipEventRecord(x->ev[0], x->stream));
+    MHIP(span_mark(x, true, 0));
     launch_insert(InsertRows{x->d_desc, x->d_ids, (uint4*)x->d_points}, w, x->stream);
     MHIP(hipGetLastError());
-    if (timed) MHIP(hipEventRecord(x->ev[1], x->stream));
+    MHIP(span_mark(x, true, 1));
     uint8_t* down = x->h_insert + INSERT_HOST_DOWN;
     MHIP(hipMemcpyAsync(down, d + l.down, sizeof(InsertCtl) + sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, x->stream));
     MHIP(hipStreamSynchronize(x->stream));
-    if (timed) { float ms = 0.f; MHIP(hipEventElapsedTime(&ms, x->ev[0], x->ev[1])); x->insert_ms += ms; }
+    MHIP(span_read(x, x->insert_ms));
     const InsertCtl* ctl = (const InsertCtl*)down;
     if (ctl->over) return fail(SVO_ERR_ARG, "batched insertion: the kept rows exceed the index's capacity (nothing was added)");
     if (ctl->nonfinite) return fail(SVO_ERR_ARG, "batched insertion: a kept row's point has a non-finite coordinate (nothing was added)");
@@ -1667,12 +1601,12 @@ static int insert_staged(svo_desc_index* x, int n, const int64_t* begin, const i
     for (int g0 = 0; g0 < n;) {
         int g1 = g0; int32_t m = 0;
         while (g1 < n && (g1 == g0 || m + rows[g1] <= INSERT_MAX_OBS_ROWS)) m += rows[g1++];
-        if (const int rc = insert_rows_room(x, (size_t)m * (INSERT_OBS_BYTES + INSERT_DESC_BYTES)); rc != SVO_OK) return rc;
+        if (const int rc = grow(x, x->insert_rows, (size_t)m * (INSERT_OBS_BYTES + INSERT_DESC_BYTES), INSERT_STAGE_FIRST, 0, true); rc != SVO_OK) return rc;
         for (int b = g0, at = 0; b < g1; at += rows[b], b++) {
             insert_entry_fill(x, g1 - g0, b - g0, b, at, rows[b], c);
             if (rows[b] == 0) continue;
-            memcpy(x->h_insert_rows + (size_t)at * INSERT_OBS_BYTES, obs + (size_t)begin[b] * INSERT_OBS_BYTES, (size_t)rows[b] * INSERT_OBS_BYTES);
-            memcpy(x->h_insert_rows + (size_t)m * INSERT_OBS_BYTES + (size_t)at * INSERT_DESC_BYTES, desc + (size_t)begin[b] * INSERT_DESC_BYTES, (size_t)rows[b] * INSERT_DESC_BYTES);
+            memcpy(x->insert_rows.p + (size_t)at * INSERT_OBS_BYTES, obs + (size_t)begin[b] * INSERT_OBS_BYTES, (size_t)rows[b] * INSERT_OBS_BYTES);
+            memcpy(x->insert_rows.p + (size_t)m * INSERT_OBS_BYTES + (size_t)at * INSERT_DESC_BYTES, desc + (size_t)begin[b] * INSERT_DESC_BYTES, (size_t)rows[b] * INSERT_DESC_BYTES);
         }
         int added = 0;
         if (const int rc = insert_group(x, g1 - g0, c, nullptr, nullptr, m, x->size + *total, counts + g0, &added); rc != SVO_OK) return rc;

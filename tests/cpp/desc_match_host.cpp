@@ -5,6 +5,8 @@
 //   match_update over a whole range, rows in order;
 //   match_merge over EVERY split point of the range, in both argument orders;
 //   match_merge over every 3-way split, in both groupings.
+// And the capacity rule of the index's growable buffers (match_grow_capacity): the sequence from empty, the clamp at the budget, a
+// need above the budget, no growth for a smaller need, and need <= cap < max(2 * need, first + 1) along randomised needs.
 #include <cstdint>
 #include <cstdio>
 #include <vector>
@@ -80,6 +82,43 @@ int main() {
                 expect(same(match_merge(match_merge(q, a), p), want), "3-way split, out of row order", trial, s, t);
                 checked += 3;
             }
+        }
+    }
+    // ---- the capacity rule, with the partial states' figures: 64 KiB first, a budget of 64 MiB
+    const size_t first = (size_t)64 << 10, budget = (size_t)64 << 20;
+    expect(match_grow_capacity(0, 0, first, budget) == 0, "no need, no buffer");
+    expect(match_grow_capacity(0, 1, first, budget) == first && match_grow_capacity(0, first, first, budget) == first, "the first size holds every need up to itself");
+    size_t cap = 0;
+    int grown = 0;
+    for (size_t need = 1; need <= budget; need += need < 4096 ? 1 : need / 3) {          // from empty: powers of two times the first size
+        const size_t next = match_grow_capacity(cap, need, first, budget);
+        expect(next >= cap && next >= need && (next == cap || next >= 2 * cap), "it grows by doubling at least", (int)(need >> 10));
+        expect(next % first == 0 && ((next / first) & (next / first - 1)) == 0, "a power of two times the first size", (int)(need >> 10));
+        expect(next < (2 * need > first + 1 ? 2 * need : first + 1), "below twice the need", (int)(need >> 10));
+        if (next != cap) grown++;
+        cap = next;
+    }
+    expect(cap == budget && grown == 11, "64 KiB to 64 MiB in eleven allocations", grown);
+    expect(match_grow_capacity(first, first + 1, first, budget) == 2 * first, "one byte more doubles");
+    expect(match_grow_capacity(first, 5 * first, first, budget) == 8 * first, "a jump lands on the doubling that holds it");
+    expect(match_grow_capacity(budget / 2, budget / 2 + 1, first, budget) == budget, "the doubling that reaches the budget");
+    expect(match_grow_capacity(3 * first, budget - 5, first, budget) == budget, "the doubling stops at the budget while the need fits it (3, 6, 12 .. x 64 KiB would pass it)");
+    expect(match_grow_capacity(3 * first, budget - 5, first, 0) == 3 * first * 512, "without a clamp it does not stop");
+    expect(match_grow_capacity(budget, budget + 1, first, budget) == 2 * budget, "a need above the budget doubles on");
+    expect(match_grow_capacity(0, budget + 1, first, budget) == 2 * budget && match_grow_capacity(first, 5 * budget, first, budget) == 8 * budget, "above the budget from anywhere");
+    expect(match_grow_capacity(8 * first, 3 * first, first, budget) == 8 * first && match_grow_capacity(8 * first, 0, first, budget) == 8 * first &&
+           match_grow_capacity(2 * budget, budget, first, budget) == 2 * budget, "a smaller need changes nothing: it never shrinks");
+    for (int trial = 0; trial < 2000; trial++) {              // the invariant tests/test_gpu_desc_match.py asserts on the GPU, along needs that rise and fall
+        const size_t clamp = rnd(2) ? budget : 0;
+        size_t c = 0, largest = 0, outgrown = 0;
+        for (int step = 0; step < 40; step++) {
+            const size_t need = (size_t)rnd(1u << (8 + rnd(20))) + 1;
+            const size_t next = match_grow_capacity(c, need, first, clamp);
+            largest = need > largest ? need : largest;
+            if (next != c) outgrown += c;
+            c = next;
+            expect(largest <= c && c < (2 * largest > first + 1 ? 2 * largest : first + 1), "need <= cap < max(2 * need, first + 1)", trial, step);
+            expect(outgrown < c, "the outgrown buffers sum to less than the one in use", trial, step);
         }
     }
     if (fails) { std::printf("%d checks failed\n", fails); return 1; }

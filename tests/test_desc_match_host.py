@@ -1,6 +1,8 @@
 """tests/cpp/desc_match_host.cpp — a stand-alone program over stereo_visual_odometry_amd/csrc/svo_match.hpp, the integer rules of the
-descriptor index's search compiled for the host from the text the kernels run — built with AddressSanitizer and UBSan and run, as
-tests/test_descriptor_host.py does for the descriptor rules.  And the facade round trip (tests/cpp/desc_index_test.cpp) compiles and
+descriptor index's search compiled for the host from the text the kernels run, and the capacity rule of the index's growable buffers
+(match_grow_capacity: the sequence from empty, the clamp at the budget, a need above it, no growth for a smaller need, and
+need <= cap < max(2 * need, first + 1)) — built with AddressSanitizer and UBSan and run, as tests/test_descriptor_host.py does for
+the descriptor rules.  And the facade round trip (tests/cpp/desc_index_test.cpp) compiles and
 links with g++; tests/test_gpu_desc_index_facade.py runs it."""
 import os
 import subprocess
