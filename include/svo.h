@@ -1102,6 +1102,69 @@ int svo_desc_index_places_from_ids(svo_desc_index* index, int n_ids, const uint6
  * set per run of equal tags in a wave (the default, on != 0).  The results do not depend on it. */
 int svo_desc_index_set_place_combine(svo_desc_index* index, int on);
 
+/* ---- Batched place candidates: every camera's keyframe votes in one call --------------------------------------------------------------
+ * A map back end asks per step which keyframes of the map each camera resembles (loop-closure and map-merge candidates, the
+ * tracker's local map); the calls above serve one camera each, with an upload, launches, a copy back and a host wait per camera.
+ * These serve n_cameras cameras in one call: one upload, ONE sweep that reads every row of the index once for the whole call, one
+ * pick launch with a block per camera, one host synchronisation.  Three of rule 2's four arrays — rows, row_first, row_end — depend
+ * on the row range and the tag window alone, so they exist once; only votes is per camera.
+ *
+ * The contract, which is the whole definition.  Camera b owns the slice [begin[b], begin[b + 1]) of ids (id_begin) or of query
+ * (query_begin); one params record — one row range, one tag window — holds for the call, as in "Batched relocalisation".
+ *  - results[b], the first results[b].n_places entries of places + b * params->max_places and, for places_batch, the first
+ *    results[b].n_landmarks entries of cand_query and cand_row at offset query_begin[b] (cand_query numbered inside the slice) equal,
+ *    in every bit, what svo_desc_index_places_from_ids, or svo_desc_index_places, returns for that slice alone.
+ *  - votes + b * n_bins (n_bins = tag_hi - tag_lo + 1; camera-major) equals svo_desc_index_tag_votes' votes for that slice; rows,
+ *    row_first and row_end (n_bins entries each) equal any single call's.
+ *  - Nothing beyond those entries is written.  Each output pointer may be NULL.
+ *  - The results do not depend on the number of cameras or their order, on how the library groups cameras into launches, or on
+ *    svo_desc_index_set_chunk_rows.
+ *  - An id may appear in any number of cameras' lists and more than once in one camera's list: M is a set per camera.  0 and
+ *    2^64 - 1 are ids like any other.
+ * Refusals, each decided before anything is uploaded or enqueued; a refused call leaves every output untouched.  SVO_ERR_STATE /
+ * SVO_ERR_ARG: whatever the single call refuses for any slice ("Place candidates", rule 4; a NULL list or NULL queries with a
+ * total above 0); the offsets' rules of "Batched relocalisation" — begin[0] != 0, a decreasing offset, a slice above 4096, a total
+ * above SVO_PLACE_BATCH_MAX_IDS, n_cameras outside 0 .. SVO_PLACE_BATCH_MAX_CAMERAS; and n_cameras x n_bins above
+ * SVO_PLACE_BATCH_MAX_BINS (narrow the tag window, or split the cameras over calls).  Zero cameras is legal, launches nothing and
+ * writes nothing.
+ *
+ * Every call is synchronous, runs in the index's own stream, synchronises with the host once, is legal with frames in flight and
+ * changes nothing in the index (svo_desc_index_get_batch_order reports no batch call after places_batch: it used that staging).
+ * With svo_desc_index_set_timing on, last_kernels_ms is, as after svo_desc_index_places, the device span of these kernels alone —
+ * the clearing, the table, the sweep and the pick — not the search and the selection in front.
+ *
+ * How it runs (none of it shows in the results).  The ids of all cameras form one list; position p's key is the pair (ids[p],
+ * camera of p), read through the list, which never changes while the table lives.  A global open-addressing table of list
+ * positions (slots as in "Landmark fusion", on the total) is hashed by the id alone and claimed with a 32-bit compare-and-swap per
+ * distinct pair; results[b].n_landmarks counts camera b's fresh inserts.  The sweep — one lane per row — accumulates the shared
+ * bins with the single sweep's wave-combined runs and, for a row whose tag qualifies, walks from hash(id) to the first empty slot,
+ * adding 1 to votes[camera][bin] at every slot that holds its id.  Rule 3 runs with a block per camera over its row of votes.
+ * For places_batch the search and the selection in front are "Batched relocalisation"'s, unguided, without pixels and without its
+ * PnP, through that section's staging and stage context; the list is gathered on the device from the selection's candidate rows.
+ *
+ * Memory.  The device side lives in the maintenance scratch of "Index maintenance" (the same buffer, the same growth rule).  With C
+ * cameras, T ids or queries in all, b bins, P = max_places (0 for tag_votes_batch) and R, slots as in "Landmark fusion", a call needs
+ *   need = R(16 C) + R(32 P C) + R(16 b) + R(4 C b)      a record per camera, the places, the shared bins, the votes (what comes down)
+ *        + R(4 (C + 1)) + R(8 T) + R(4 T) + R(4 slots(T)) the offsets, the id list, the camera of every position, the table
+ * bytes: 512 cameras of 2048 ids and 256 bins, P = 8: 20 MiB + 669 952; the limits (C x b = 1 << 24, T = 1 << 20): about 100 MiB.
+ * The pinned block of "Place candidates" (the same growth rule) holds R(4 (C + 1)) + R(8 T) bytes going up and, coming down,
+ * R(16 C) + R(32 P C) bytes (the two places calls) or R(16 C) + R(16 b) + R(4 C b) (tag_votes_batch).  places_batch also takes
+ * "Batched relocalisation"'s stagings and partial states for T queries. */
+#define SVO_PLACE_BATCH_MAX_CAMERAS 1024
+#define SVO_PLACE_BATCH_MAX_IDS (1 << 20)
+#define SVO_PLACE_BATCH_MAX_BINS (1 << 24)
+/* Rule 2 for every camera.  id_begin: n_cameras + 1 offsets into ids.  votes: n_cameras x n_bins; rows, row_first, row_end: n_bins. */
+int svo_desc_index_tag_votes_batch(svo_desc_index* index, int n_cameras, const int32_t* id_begin, const uint64_t* ids, int row_lo, int row_hi,
+                                   int32_t tag_lo, int32_t tag_hi, int32_t* votes, int32_t* rows, int32_t* row_first, int32_t* row_end);
+/* Rules 2 - 3 for every camera.  results: n_cameras; places: n_cameras x params->max_places. */
+int svo_desc_index_places_from_ids_batch(svo_desc_index* index, int n_cameras, const int32_t* id_begin, const uint64_t* ids,
+                                         const svo_place_params* params, svo_place_result* results, svo_place* places);
+/* Rules 1 - 3 for every camera.  query_begin: n_cameras + 1 offsets into query (32 bytes a descriptor); cand_query, cand_row: total
+ * entries each, camera b's at query_begin[b]. */
+int svo_desc_index_places_batch(svo_desc_index* index, int n_cameras, const int32_t* query_begin, const uint8_t* query,
+                                const svo_place_params* params, svo_place_result* results, svo_place* places, int32_t* cand_query,
+                                int32_t* cand_row);
+
 /* ---- Landmark consolidation: medoid descriptor and mean point per landmark --------------------------------------------------------
  * A landmark seen in k frames has k rows, each with one view's descriptor and one triangulation.  svo_desc_index_consolidate leaves
  * one row per landmark: the most central of the observed descriptors and the mean of the points that agree with it.  It runs on the

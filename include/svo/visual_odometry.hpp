@@ -756,6 +756,45 @@ class DescriptorIndex {
                                            v.rows.data(), v.row_first.data(), v.row_end.data()));
         return v;
     }
+    // ---- batched place candidates (svo.h, "Batched place candidates"): every camera's keyframe votes in one call
+    // camera b's result is what the single call returns for ids[b] or query[b] alone, bit for bit
+    struct TagVotesBatch { std::vector<int32_t> votes, rows, row_first, row_end; size_t n_bins; };   // votes: camera-major, votes[b * n_bins + tag - tags.first]
+    std::vector<Places> places_from_ids_batch(const std::vector<std::vector<uint64_t>>& ids, const svo_place_params& prm) {
+        std::vector<int32_t> begin;
+        const std::vector<uint64_t> all = concat_(ids, begin);
+        PlacesRoom r(ids.size(), prm);
+        svo_throw(svo_desc_index_places_from_ids_batch(index_, (int)ids.size(), begin.data(), all.data(), &prm, r.results.data(), r.places.data()));
+        return r.split();
+    }
+    // cands: per camera the recognised landmarks, query numbers inside the camera's own vector
+    std::vector<Places> places_batch(const std::vector<std::vector<Descriptor>>& query, const svo_place_params& prm, std::vector<Candidates>* cands = nullptr) {
+        std::vector<int32_t> begin;
+        const std::vector<Descriptor> all = concat_(query, begin);
+        PlacesRoom r(query.size(), prm);
+        Candidates c = room(all.size(), false);
+        svo_throw(svo_desc_index_places_batch(index_, (int)query.size(), begin.data(), rows(all), &prm, r.results.data(), r.places.data(), c.query.data(),
+                                              c.row.data()));
+        if (cands) {
+            cands->assign(query.size(), Candidates());
+            for (size_t b = 0; b < query.size(); b++) {
+                const long lo = (long)begin[b], k = query[b].empty() ? 0 : (long)r.results[b].n_landmarks;
+                (*cands)[b].query.assign(c.query.begin() + lo, c.query.begin() + lo + k);
+                (*cands)[b].row.assign(c.row.begin() + lo, c.row.begin() + lo + k);
+            }
+        }
+        return r.split();
+    }
+    TagVotesBatch tag_votes_batch(const std::vector<std::vector<uint64_t>>& ids, std::pair<int, int> rows = {0, -1}, std::pair<int32_t, int32_t> tags = {0, 0}) {
+        std::vector<int32_t> begin;
+        const std::vector<uint64_t> all = concat_(ids, begin);
+        const int64_t span = (int64_t)tags.second - (int64_t)tags.first + 1;
+        const bool fits = tags.first >= 0 && span >= 1 && span <= SVO_PLACE_MAX_TAGS && (int64_t)ids.size() * span <= SVO_PLACE_BATCH_MAX_BINS;
+        TagVotesBatch v; v.n_bins = fits ? (size_t)span : 1;   // a span the library refuses: room for nothing
+        v.votes.resize(fits ? ids.size() * v.n_bins : 1); v.rows.resize(v.n_bins); v.row_first.resize(v.n_bins); v.row_end.resize(v.n_bins);
+        svo_throw(svo_desc_index_tag_votes_batch(index_, (int)ids.size(), begin.data(), all.data(), rows.first, rows.second, tags.first, tags.second,
+                                                 v.votes.data(), v.rows.data(), v.row_first.data(), v.row_end.data()));
+        return v;
+    }
     // ---- landmark consolidation (svo.h, "Landmark consolidation"): one row per landmark, and the rows read back
     // svo_consolidate_params_default: the whole index, every tag.  radius (the map's unit) has no default: none has been measured
     static svo_consolidate_params consolidate_params(float radius) { svo_consolidate_params p; svo_consolidate_params_default(&p, radius); return p; }
@@ -838,6 +877,34 @@ class DescriptorIndex {
     // the candidate lists of a call over n queries, with or without the inlier list: sized before the call, cut to its count after
     static Candidates room(size_t n, bool inlier) { Candidates c; c.query.resize(n); c.row.resize(n); c.inlier.resize(inlier ? n : 0); return c; }
     static void shrink(Candidates& c, int k) { c.query.resize((size_t)k); c.row.resize((size_t)k); if (!c.inlier.empty()) c.inlier.resize((size_t)k); }
+    // a batch's per-camera vectors as one, with the n + 1 offsets the C call takes
+    template <typename T> static std::vector<T> concat_(const std::vector<std::vector<T>>& per_camera, std::vector<int32_t>& begin) {
+        std::vector<T> all;
+        begin.assign(1, 0);
+        for (const std::vector<T>& v : per_camera) {
+            all.insert(all.end(), v.begin(), v.end());
+            begin.push_back((int32_t)all.size());
+        }
+        return all;
+    }
+    // the results of a batched places call: sized before the call, split per camera after
+    struct PlacesRoom {
+        std::vector<svo_place_result> results;
+        std::vector<svo_place> places;
+        size_t per_camera;
+        PlacesRoom(size_t n_cameras, const svo_place_params& prm)
+            : results(n_cameras), per_camera(prm.max_places >= 1 && prm.max_places <= SVO_PLACE_MAX_PLACES ? (size_t)prm.max_places : 1) {
+            places.resize(n_cameras * per_camera);
+        }
+        std::vector<Places> split() const {
+            std::vector<Places> out(results.size());
+            for (size_t b = 0; b < results.size(); b++) {
+                out[b].result = results[b];
+                out[b].places.assign(places.begin() + (long)(b * per_camera), places.begin() + (long)(b * per_camera) + results[b].n_places);
+            }
+            return out;
+        }
+    };
     // select and localize; g (with its K) null: the unguided search
     Candidates select_(const char* what, const float* K, const svo_reloc_guide* g, const std::vector<Descriptor>& query, const std::vector<float>& xy,
                        const svo_reloc_params& params) {

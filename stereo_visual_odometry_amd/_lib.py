@@ -155,6 +155,7 @@ class SvoPlaceResult(C.Structure):
 PLACE_DTYPE = np.dtype([("tag", "<i4"), ("votes", "<i4"), ("rows", "<i4"), ("row_first", "<i4"), ("row_end", "<i4"), ("reserved", "<i4", 3)])
 assert PLACE_DTYPE.itemsize == 32
 PLACE_MAX_TAGS, PLACE_MAX_PLACES, PLACE_MAX_IDS = 1 << 20, 64, 4096
+PLACE_BATCH_MAX_CAMERAS, PLACE_BATCH_MAX_IDS, PLACE_BATCH_MAX_BINS = 1024, 1 << 20, 1 << 24
 
 
 class SvoConsolidateParams(C.Structure):
@@ -272,6 +273,9 @@ PROTOTYPES = {
     "svo_desc_index_places": (I, (P, I, P, P, P, P, P, P)),
     "svo_desc_index_places_from_ids": (I, (P, I, P, P, P, P)),
     "svo_desc_index_set_place_combine": (I, (P, I)),
+    "svo_desc_index_tag_votes_batch": (I, (P, I, P, P, I, I, I32, I32, P, P, P, P)),
+    "svo_desc_index_places_from_ids_batch": (I, (P, I, P, P, P, P, P)),
+    "svo_desc_index_places_batch": (I, (P, I, P, P, P, P, P, P, P)),
     "svo_consolidate_params_default": (None, (P, F)),
     "svo_desc_index_consolidate": (I, (P, P, P, P)),
     "svo_desc_index_read_rows": (I, (P, I, I, P, P, P, P)),

@@ -835,6 +835,61 @@ class DescriptorIndex:
         check(lib.svo_desc_index_places_from_ids(self._h, len(i), ptr(i) if len(i) else None, C.byref(p), C.byref(res), ptr(out)))
         return PlaceResult(res.n_landmarks, res.n_tags_voted, res.n_places), out[:res.n_places].copy()
 
+    # ---- batched place candidates (svo.h, "Batched place candidates"): every camera's keyframe votes in one call
+    @staticmethod
+    def _slices(arrays, empty):
+        """per-camera arrays -> (the offsets, (B + 1,) int32, and the arrays concatenated)"""
+        begin = np.zeros(len(arrays) + 1, np.int32)
+        begin[1:] = np.cumsum([len(a) for a in arrays])
+        return begin, (np.concatenate(arrays) if int(begin[-1]) else empty)
+
+    def tag_votes_batch(self, ids_list, rows=(0, -1), tags=(0, 0)):
+        """tag_votes for many cameras in one call (svo_desc_index_tag_votes_batch): ids_list holds one id list per camera ->
+        (votes, rows, row_first, row_end): votes is (B, b) int32, camera b's row what tag_votes returns for its list; the other
+        three, (b,) int32 each, are the same for every camera."""
+        B = len(ids_list)
+        begin, i = self._slices([self._id_list(a) for a in ids_list], np.zeros(0, np.uint64))
+        nb = max(0, min(int(tags[1]) - int(tags[0]) + 1, _lib.PLACE_MAX_TAGS)) if int(tags[0]) >= 0 else 0
+        if B * nb > _lib.PLACE_BATCH_MAX_BINS:
+            nb = 0                                     # a window the library refuses: room for nothing
+        votes = np.zeros((B, nb) if B * nb else (1, 1), np.int32)
+        out = [np.zeros(max(nb, 1), np.int32) for _ in range(3)]
+        check(lib.svo_desc_index_tag_votes_batch(self._h, B, ptr(begin), ptr(i) if len(i) else None, int(rows[0]), int(rows[1]), int(tags[0]), int(tags[1]),
+                                                 ptr(votes), *(ptr(a) for a in out)))
+        return (votes if B * nb else np.zeros((B, nb), np.int32),) + tuple(a[:nb] for a in out)
+
+    def _places_out(self, B, p):
+        return (_lib.SvoPlaceResult * max(B, 1))(), np.zeros((max(B, 1), p.max_places if 1 <= p.max_places <= _lib.PLACE_MAX_PLACES else 1), _lib.PLACE_DTYPE)
+
+    def places_from_ids_batch(self, ids_list, rows=(0, -1), tags=(0, _lib.PLACE_MAX_TAGS - 1), min_votes=1, separation=0, max_places=8, params=None, **over):
+        """places_from_ids for many cameras in one call (svo_desc_index_places_from_ids_batch): ids_list holds one id list per camera
+        -> a list with, per camera, the (PlaceResult, places) the single call returns, bit for bit."""
+        B = len(ids_list)
+        begin, i = self._slices([self._id_list(a) for a in ids_list], np.zeros(0, np.uint64))
+        p = params if params is not None else self.place_params(rows, tags, min_votes=min_votes, separation=separation, max_places=max_places, **over)
+        res, out = self._places_out(B, p)
+        check(lib.svo_desc_index_places_from_ids_batch(self._h, B, ptr(begin), ptr(i) if len(i) else None, C.byref(p), res, ptr(out)))
+        return [(PlaceResult(res[b].n_landmarks, res[b].n_tags_voted, res[b].n_places), out[b, :res[b].n_places].copy()) for b in range(B)]
+
+    def places_batch(self, queries, rows=(0, -1), tags=(0, _lib.PLACE_MAX_TAGS - 1), min_votes=1, separation=0, max_places=8, params=None, **over):
+        """places for many cameras in one call (svo_desc_index_places_batch): queries holds one (n_b, 32) uint8 array per camera -> a
+        list with, per camera, the (PlaceResult, places, candidates) the single call returns, bit for bit; candidates' query numbers
+        count inside the camera's own array."""
+        B = len(queries)
+        begin, q = self._slices([self._rows(a, "query") for a in queries], np.zeros((0, _lib.DESC_BYTES), np.uint8))
+        p = params if params is not None else self.place_params(rows, tags, min_votes=min_votes, separation=separation, max_places=max_places, **over)
+        res, out = self._places_out(B, p)
+        total = int(begin[-1])
+        cq, cr = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32)
+        check(lib.svo_desc_index_places_batch(self._h, B, ptr(begin), ptr(q) if total else None, C.byref(p), res, ptr(out), ptr(cq), ptr(cr)))
+        ret = []
+        for b in range(B):
+            lo = int(begin[b])
+            k = res[b].n_landmarks if begin[b + 1] > lo else 0
+            ret.append((PlaceResult(res[b].n_landmarks, res[b].n_tags_voted, res[b].n_places), out[b, :res[b].n_places].copy(),
+                        dict(query=cq[lo:lo + k].copy(), row=cr[lo:lo + k].copy())))
+        return ret
+
     def set_place_combine(self, on=True):
         """diagnostics: one set of atomics per run of equal tags in a wave (the default) or four per row; the results do not depend on it"""
         check(lib.svo_desc_index_set_place_combine(self._h, int(bool(on))))

@@ -26,6 +26,9 @@
 //
 // Place candidates (svo_kernels_place.hip, svo_place.hpp): place_run, behind tag_votes, places and places_from_ids, is — for places —
 // the unguided search and the selection, else the id list up (upload_list), then the sweep and the pick, the copies back, one wait.
+// place_batch_run (svo_kernels_place_batch.hip, svo_place_batch.hpp), behind tag_votes_batch, places_batch and places_from_ids_batch,
+// is that for many cameras: localize_batch's staging, unguided search and selection without its PnP, or the offsets and the ids up,
+// then one table of (id, camera) pairs, one sweep for all cameras and a pick block per camera, one copy back or two, one wait.
 //
 // Maintenance (svo_kernels_retire.hip, svo_kernels_consolidate.hip): retire puts its flags, table and ranks on the stream, consolidate
 // the group kernel and the ranks; retire_finish is the end of both — the first wait, before which nothing has moved, the ranks down,
@@ -42,6 +45,7 @@
 #include "svo_align_internal.hpp"
 #include "svo_fuse_internal.hpp"
 #include "svo_place_internal.hpp"
+#include "svo_place_batch_internal.hpp"
 #include "svo_consolidate_internal.hpp"
 #include "svo_insert_internal.hpp"
 #include <algorithm>
@@ -126,7 +130,7 @@ struct svo_desc_index {
     // landmark fusion: null until the first pair_near, relabel or fuse (fuse_ctl_room); the lists and the table live in the maintenance scratch
     FuseCtl* h_fuse = nullptr;                        // pinned: what a call reads back
     // place candidates: null until the first tag_votes, places or places_from_ids (grow); the device side lives in the maintenance scratch
-    GrowBuf place;                                    // pinned: a PlaceCtl, then tag_votes' bins
+    GrowBuf place;                                    // pinned: a PlaceCtl, then tag_votes' bins; a batch call's PbStage
     bool place_combine = true;                        // svo_desc_index_set_place_combine
     // batched insertion: null until the first add_frames, add_frames_points or add_obs (insert_host_room, grow); the device side lives in the maintenance scratch
     uint8_t* h_insert = nullptr;                      // pinned: the entries and transforms going up, then (at INSERT_HOST_DOWN) the control block and the counts coming down
@@ -703,15 +707,29 @@ static int batch_room(svo_desc_index* x, size_t cams, size_t queries) {
     return SVO_OK;
 }
 
-static const char* batch_offsets_text(RbOffsets e) {
+// the refusal of a batch's offsets under the call's name: `begin` names the offsets' argument, `what` what they count
+static int batch_offsets_fail(RbOffsets e, const char* call, const char* begin, const char* what) {
+    char b[192];
     switch (e) {
-    case RB_OFFSETS_COUNT: return "svo_desc_index_localize_batch: n_cameras must be 0 .. 1024";
-    case RB_OFFSETS_NULL: return "svo_desc_index_localize_batch: null query_begin";
-    case RB_OFFSETS_FIRST: return "svo_desc_index_localize_batch: query_begin[0] must be 0";
-    case RB_OFFSETS_ORDER: return "svo_desc_index_localize_batch: query_begin must not decrease";
-    case RB_OFFSETS_SLICE: return "svo_desc_index_localize_batch: at most 4096 queries per camera";
-    default: return "svo_desc_index_localize_batch: at most 1 << 20 queries in all";
+    case RB_OFFSETS_COUNT: snprintf(b, sizeof(b), "%s: n_cameras must be 0 .. 1024", call); break;
+    case RB_OFFSETS_NULL: snprintf(b, sizeof(b), "%s: null %s", call, begin); break;
+    case RB_OFFSETS_FIRST: snprintf(b, sizeof(b), "%s: %s[0] must be 0", call, begin); break;
+    case RB_OFFSETS_ORDER: snprintf(b, sizeof(b), "%s: %s must not decrease", call, begin); break;
+    case RB_OFFSETS_SLICE: snprintf(b, sizeof(b), "%s: at most 4096 %s per camera", call, what); break;
+    default: snprintf(b, sizeof(b), "%s: at most 1 << 20 %s in all", call, what); break;
     }
+    return fail(SVO_ERR_ARG, b);
+}
+
+// the partial states the largest group of a batch's search writes (rb_next_group)
+static size_t batch_group_states(int n_cameras, const int32_t* begin, int n_chunks) {
+    size_t states = 0;
+    for (int cam = 0; cam < n_cameras;) {
+        const RbGroup g = rb_next_group(n_cameras, begin, cam, n_chunks);
+        states = rb_group_states(g, n_chunks) > states ? rb_group_states(g, n_chunks) : states;
+        cam = g.cam1;
+    }
+    return states;
 }
 
 // Everything is decided first — the refusals of the single calls for every camera, and the offsets' own — then one upload, the order,
@@ -722,7 +740,8 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
                                              const int32_t* query_begin, const uint8_t* query, const float* xy, const svo_reloc_params* p,
                                              svo_reloc_result* results, int32_t* cand_query, int32_t* cand_row, uint8_t* cand_inlier) {
     if (!x || !p) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null index / params");
-    if (const RbOffsets e = rb_check_offsets(n_cameras, query_begin); e != RB_OFFSETS_OK) return fail(SVO_ERR_ARG, batch_offsets_text(e));
+    if (const RbOffsets e = rb_check_offsets(n_cameras, query_begin); e != RB_OFFSETS_OK)
+        return batch_offsets_fail(e, "svo_desc_index_localize_batch", "query_begin", "queries");
     if (n_cameras > 0 && (!K || !results)) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null K / results");
     const int total = n_cameras > 0 ? query_begin[n_cameras] : 0;
     if (total > 0 && (!query || !xy)) return fail(SVO_ERR_ARG, "svo_desc_index_localize_batch: null query / xy");
@@ -739,12 +758,7 @@ extern "C" int svo_desc_index_localize_batch(svo_desc_index* x, int n_cameras, c
     const int max_slice = rb_max_slice(n_cameras, query_begin);
     const RbRange r = rb_plan_range(row_lo, row_hi, x->chunk_rows, max_slice);
     const MatchRange mr{r.row_lo, r.row_hi, r.chunk_rows, r.chunk0, r.n_chunks};
-    size_t states = 0;
-    for (int cam = 0; cam < n_cameras;) {
-        const RbGroup g = rb_next_group(n_cameras, query_begin, cam, r.n_chunks);
-        states = rb_group_states(g, r.n_chunks) > states ? rb_group_states(g, r.n_chunks) : states;
-        cam = g.cam1;
-    }
+    const size_t states = batch_group_states(n_cameras, query_begin, r.n_chunks);
     DevBuffers d;
     svo_context* old = nullptr;
     rc = svo_reloc_batch_ctx(x->device, n_cameras, max_slice > 64 ? max_slice : 64, p->ransac_iterations, p->reproj_error, p->confidence,
@@ -1414,6 +1428,163 @@ extern "C" int svo_desc_index_places(svo_desc_index* x, int n, const uint8_t* qu
     if (const PlaceRefusal e = place_check(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
     if (n == 0) return place_run(x, q, true, 0, nullptr, nullptr, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, nullptr, nullptr});
     return place_run(x, q, true, n, query, nullptr, PlaceOutputs{nullptr, nullptr, nullptr, nullptr, res, places, cand_query, cand_row});
+}
+
+// ---- batched place candidates (include/svo.h, "Batched place candidates"; the kernels are in svo_kernels_place_batch.hip, the rules
+// and the layouts in svo_place_batch.hpp) ----
+// where a batch call's results go, each null when not wanted
+struct PlaceBatchOutputs {
+    int32_t *votes, *rows, *row_first, *row_end;      // tag_votes_batch: cameras x bins, then one entry per bin each
+    svo_place_result* res; svo_place* places;         // the two places calls: one per camera, max_places per camera
+    int32_t *cand_query, *cand_row;                   // places_batch: every camera's at its slice
+};
+
+// What tag_votes_batch (pick false, query null), places_from_ids_batch (pick, query null) and places_batch (pick, with queries)
+// share.  q: the request, checked and with its row range resolved; begin: the checked offsets.  Everything is enqueued on the index's
+// stream — for places_batch the queries up through the batched relocalisation's staging, the unguided search group by group and
+// k_reloc_select_batch; else the offsets and the id list up — then the clearing, the table, the sweep and the pick, the copies back,
+// and the host waits once.  times: from the clearing to the last place kernel
+static int place_batch_run(svo_desc_index* x, const PlaceRequest& q, bool pick, int n_cameras, const int32_t* begin, const uint8_t* query,
+                           const uint64_t* ids, const PlaceBatchOutputs& o) {
+    int rc;
+    MHIP(call_begin(x));
+    if (n_cameras == 0) return SVO_OK;
+    const int total = begin[n_cameras], n_bins = q.tag_hi - q.tag_lo + 1;
+    const size_t C = (size_t)n_cameras, P = pick ? (size_t)q.max_places : 0;
+    const bool searched = query && total > 0;         // cameras without queries recognise nothing: empty lists
+    const PbLayout l = pb_layout(C, (size_t)total, (size_t)n_bins, P);
+    const PbStage hs = pb_stage(l, C, (size_t)total, pick);
+    if ((rc = retire_scratch(x, l.total)) != SVO_OK || (rc = grow(x, x->place, hs.total, RETIRE_SCRATCH_FIRST, 0, true)) != SVO_OK) return rc;
+    uint8_t *dv = x->retire.p, *h = x->place.p;
+    PbCam* d_cams = (PbCam*)(dv + l.cams);
+    PlaceBin* d_bins = (PlaceBin*)(dv + l.bins);
+    int32_t* d_votes = (int32_t*)(dv + l.votes);
+    PbTableArgs t{(const int32_t*)(dv + l.begin), nullptr, nullptr, x->d_ids, (uint64_t*)(dv + l.list), (int32_t*)(dv + l.cam), (int32_t*)(dv + l.table),
+                  fuse_table_slots(total) - 1, d_cams};
+    RbLayout bl{};
+    if (searched) {                                   // rule 1: svo_desc_index_localize_batch's path without guides, pixels and PnP
+        const int max_slice = rb_max_slice(n_cameras, begin);
+        const RbRange r = rb_plan_range(q.row_lo, q.row_hi, x->chunk_rows, max_slice);
+        const MatchRange mr{r.row_lo, r.row_hi, r.chunk_rows, r.chunk0, r.n_chunks};
+        const size_t states = batch_group_states(n_cameras, begin, r.n_chunks);
+        svo_reloc_params rp; svo_reloc_params_default(&rp);
+        DevBuffers d;
+        svo_context* old = nullptr;
+        rc = svo_reloc_batch_ctx(x->device, n_cameras, max_slice > 64 ? max_slice : 64, rp.ransac_iterations, rp.reproj_error, rp.confidence,
+                                 &x->batch_ctx, &old, &d);
+        if (old) x->batch_ctx_outgrown.push_back(old);
+        if (rc != SVO_OK || (states > 0 && (rc = part_states(x, states)) != SVO_OK) || (rc = batch_room(x, C, (size_t)total)) != SVO_OK) return rc;
+        bl = rb_layout(C, (size_t)total);
+        uint8_t *hb = x->h_batch, *db = x->d_batch;
+        memcpy(hb + bl.query, query, (size_t)total * SVO_DESC_BYTES);
+        memset(hb + bl.xy, 0, bl.begin - bl.xy);      // no pixels
+        memcpy(hb + bl.begin, begin, (C + 1) * sizeof(int32_t));
+        memset(hb + bl.cams, 0, bl.up_end - bl.cams); // no priors
+        MHIP(hipMemcpyAsync(db, hb, bl.up_end, hipMemcpyHostToDevice, x->stream));
+        x->batch_total = -1;                          // the staging no longer holds a localize_batch's order
+        const uint32_t* d_query = (const uint32_t*)(db + bl.query);
+        const int32_t* d_begin = (const int32_t*)(db + bl.begin);
+        svo_desc_match* d_match = (svo_desc_match*)(db + bl.match);
+        for (int cam = 0; cam < n_cameras;) {         // a group's partial states are merged before the next group overwrites them
+            const RbGroup g = rb_next_group(n_cameras, begin, cam, r.n_chunks);
+            const int m = g.q1 - g.q0;
+            launch_desc_match((const uint32_t*)x->d_desc, x->d_ids, d_query + (size_t)g.q0 * 8, m, mr, x->d_part(), x->stream);
+            launch_desc_match_merge(x->d_part(), x->d_ids, m, mr, d_match + g.q0, x->stream);
+            cam = g.cam1;
+        }
+        const RelocBatchSelect sel{d_match, x->d_points, (const float2*)(db + bl.xy), d_begin, RelocRule{q.max_dist, q.ratio_num, q.ratio_den},
+                                   rp.min_candidates, d.tl1, d.world, d.st, d.CAP, (int32_t*)(db + bl.cand_query), (int32_t*)(db + bl.cand_row),
+                                   (int32_t*)(db + bl.n_cand)};
+        launch_reloc_select_batch(sel, n_cameras, x->stream);
+        t.begin = d_begin; t.n_dev = (const int32_t*)(db + bl.n_cand); t.m_rows = (const int32_t*)(db + bl.cand_row);
+    } else {                                          // the offsets and the ids in one copy
+        memcpy(h + hs.begin, begin, (C + 1) * sizeof(int32_t));
+        if (total > 0 && ids) memcpy(h + hs.ids, ids, (size_t)total * sizeof(uint64_t));
+        MHIP(hipMemcpyAsync(dv + l.begin, h, hs.up_end, hipMemcpyHostToDevice, x->stream));         // [begin, list) of the scratch is cut alike
+    }
+    MHIP(span_mark(x, true, 0));
+    MHIP(hipMemsetAsync(dv + l.cams, 0, l.down_end, x->stream));          // the records, the places, the bins, the votes
+    MHIP(hipMemsetAsync(t.table, 0xFF, 4 * ((size_t)t.mask + 1), x->stream));                        // PLACE_EMPTY
+    launch_place_batch_table(t, n_cameras, x->stream);
+    launch_place_batch_sweep(PbSweepArgs{t.table, t.mask, t.list, t.cam, x->d_ids, x->d_points, q.row_lo, q.row_hi, q.tag_lo, q.tag_hi, n_bins, d_bins,
+                                         d_votes}, x->stream);
+    if (pick) launch_place_batch_pick(d_votes, d_bins, n_bins, q.tag_lo, q.min_votes, q.separation, q.max_places, (PlaceOut*)(dv + l.places), d_cams,
+                                      n_cameras, x->stream);
+    MHIP(hipGetLastError());
+    MHIP(span_mark(x, true, 1));
+    uint8_t* down = h + hs.down;
+    MHIP(hipMemcpyAsync(down, dv + l.cams, pick ? l.bins : l.down_end, hipMemcpyDeviceToHost, x->stream));
+    if (searched) MHIP(hipMemcpyAsync(x->h_batch + bl.n_cand, x->d_batch + bl.n_cand, bl.inlier - bl.n_cand, hipMemcpyDeviceToHost, x->stream));
+    MHIP(hipStreamSynchronize(x->stream));            // the call's one wait
+    MHIP(span_read(x, x->last_ms));
+    const PbCam* c = (const PbCam*)(down + l.cams);
+    for (int b = 0; b < n_cameras; b++)
+        if (c[b].set_full) return fail(SVO_ERR_INTERNAL, "batched place candidates: the table overflowed");
+    if (!pick) {
+        const PlaceBin* bins = (const PlaceBin*)(down + l.bins);
+        if (o.votes) memcpy(o.votes, down + l.votes, C * (size_t)n_bins * sizeof(int32_t));
+        for (int i = 0; i < n_bins; i++) {
+            if (o.rows) o.rows[i] = bins[i].rows;
+            if (o.row_first) o.row_first[i] = place_row_first(bins[i]);
+            if (o.row_end) o.row_end[i] = place_row_end(bins[i]);
+        }
+        return SVO_OK;
+    }
+    const svo_place* places = (const svo_place*)(down + l.places);
+    const int32_t* h_ncand = (const int32_t*)(x->h_batch + bl.n_cand);
+    for (int b = 0; b < n_cameras; b++) {
+        if (o.res) { o.res[b].n_landmarks = c[b].n_landmarks; o.res[b].n_tags_voted = c[b].n_tags_voted; o.res[b].n_places = c[b].n_places; }
+        if (o.places) memcpy(o.places + (size_t)b * P, places + (size_t)b * P, (size_t)c[b].n_places * sizeof(svo_place));
+        if (!searched) continue;
+        const int q0 = begin[b], nc = h_ncand[b];
+        if (o.cand_query) memcpy(o.cand_query + q0, x->h_batch + bl.cand_query + (size_t)q0 * 4, (size_t)nc * sizeof(int32_t));
+        if (o.cand_row) memcpy(o.cand_row + q0, x->h_batch + bl.cand_row + (size_t)q0 * 4, (size_t)nc * sizeof(int32_t));
+    }
+    return SVO_OK;
+}
+
+// the refusals the three batch calls share, in the single calls' order: the index, the offsets, the points, the list
+static int place_batch_check(const svo_desc_index* x, const char* call, int n_cameras, const int32_t* begin, const void* list, const char* begin_name,
+                             const char* what) {
+    if (!x) return fail(SVO_ERR_ARG, "null index");
+    if (const RbOffsets e = rb_check_offsets(n_cameras, begin); e != RB_OFFSETS_OK) return batch_offsets_fail(e, call, begin_name, what);
+    if (!x->d_points) return no_points("place candidates");
+    if (n_cameras > 0 && begin[n_cameras] > 0 && !list) return fail(SVO_ERR_ARG, "batched place candidates: null ids / query");
+    return SVO_OK;
+}
+static int place_batch_bins_check(int n_cameras, const PlaceRequest& q) {
+    if (pb_check_bins(n_cameras, q.tag_lo, q.tag_hi) != PB_OK)
+        return fail(SVO_ERR_ARG, "batched place candidates: n_cameras x (tag_hi - tag_lo + 1) exceeds 1 << 24 bins: narrow the tag window (or split the cameras over calls)");
+    return SVO_OK;
+}
+
+extern "C" int svo_desc_index_tag_votes_batch(svo_desc_index* x, int n_cameras, const int32_t* id_begin, const uint64_t* ids, int row_lo, int row_hi,
+                                              int32_t tag_lo, int32_t tag_hi, int32_t* votes, int32_t* rows, int32_t* row_first, int32_t* row_end) {
+    if (const int rc = place_batch_check(x, "svo_desc_index_tag_votes_batch", n_cameras, id_begin, ids, "id_begin", "ids"); rc != SVO_OK) return rc;
+    PlaceRequest q{row_lo, row_hi, 0, 1, 1, tag_lo, tag_hi, 1, 0, 1};
+    if (const PlaceRefusal e = place_check_votes(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
+    if (const int rc = place_batch_bins_check(n_cameras, q); rc != SVO_OK) return rc;
+    return place_batch_run(x, q, false, n_cameras, id_begin, nullptr, ids, PlaceBatchOutputs{votes, rows, row_first, row_end, nullptr, nullptr, nullptr, nullptr});
+}
+
+extern "C" int svo_desc_index_places_from_ids_batch(svo_desc_index* x, int n_cameras, const int32_t* id_begin, const uint64_t* ids,
+                                                    const svo_place_params* p, svo_place_result* results, svo_place* places) {
+    if (const int rc = place_batch_check(x, "svo_desc_index_places_from_ids_batch", n_cameras, id_begin, ids, "id_begin", "ids"); rc != SVO_OK) return rc;
+    if (!p) return fail(SVO_ERR_ARG, "svo_desc_index_places_from_ids_batch: null params");
+    PlaceRequest q = place_request(p);
+    if (const PlaceRefusal e = place_check_pick(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
+    if (const int rc = place_batch_bins_check(n_cameras, q); rc != SVO_OK) return rc;
+    return place_batch_run(x, q, true, n_cameras, id_begin, nullptr, ids, PlaceBatchOutputs{nullptr, nullptr, nullptr, nullptr, results, places, nullptr, nullptr});
+}
+
+extern "C" int svo_desc_index_places_batch(svo_desc_index* x, int n_cameras, const int32_t* query_begin, const uint8_t* query, const svo_place_params* p,
+                                           svo_place_result* results, svo_place* places, int32_t* cand_query, int32_t* cand_row) {
+    if (const int rc = place_batch_check(x, "svo_desc_index_places_batch", n_cameras, query_begin, query, "query_begin", "queries"); rc != SVO_OK) return rc;
+    if (!p) return fail(SVO_ERR_ARG, "svo_desc_index_places_batch: null params");
+    PlaceRequest q = place_request(p);
+    if (const PlaceRefusal e = place_check(q, x->size); e != PLACE_OK) return fail(SVO_ERR_ARG, place_refusal_text(e));
+    if (const int rc = place_batch_bins_check(n_cameras, q); rc != SVO_OK) return rc;
+    return place_batch_run(x, q, true, n_cameras, query_begin, query, nullptr, PlaceBatchOutputs{nullptr, nullptr, nullptr, nullptr, results, places, cand_query, cand_row});
 }
 
 // ---- landmark consolidation (include/svo.h, "Landmark consolidation"; the kernels are in svo_kernels_consolidate.hip, the rules in

@@ -3,6 +3,7 @@
 the host path it replaces costs:
 
     python tools/place_bench.py [--out FILE] [--sizes 65536,1048576] [--spans 256,65536] [--queries 2048] [--repeats 7] [--host-repeats 3]
+    python tools/place_bench.py --batch 1,8,64,256,512 [--out FILE] [--sizes 65536,1048576] [--batch-span 256] [--queries 2048] [--repeats 7]
 
 One process.  Per index size and tag span: an index of `size` rows with random descriptors, keyframe after keyframe of size / span
 rows, tag = the keyframe's number, every landmark id on four rows, one in each of four consecutive keyframes.  The queries are the
@@ -22,6 +23,14 @@ And once per size, `sweep`: svo_desc_index_tag_votes' kernels (the clearing of t
 and without the wave-combined atomics, on an index whose rows all carry ONE tag (span 1) and on one whose rows each carry their OWN
 tag (span = size, at most 1 << 20).  Beside the span: the bytes the sweep fetches — 8 bytes of id and the 16-byte point row whose
 last dword is the tag, so 24 bytes a row: lines fetched, not bytes used — over that time.
+
+With --batch 1,8,64,256,512 the tool measures the batched calls instead (include/svo.h, "Batched place candidates"): per index size, at
+--batch-span tags (256), every camera holds `queries` descriptors, or ids, of landmarks of its own random draw.  Per camera count the
+three batch calls run against a loop of the single calls over the same cameras in the same process, the legs alternating, one
+warm-up round and then --repeats rounds: the median, the smallest and the largest wall time, and for the batch legs the device span
+of the new kernels alone.  The results are compared, untimed.  And the worst case for the table: places_from_ids_batch where every
+camera holds the SAME ids (a probe chain as long as the camera count) and, as far as the index has landmarks enough, where no two
+cameras share an id.
 
 Figures, not pass marks.  Prints one JSON line."""
 import argparse
@@ -79,6 +88,92 @@ def host_places(m, ids, tags, n_bins, max_places, pool, threads, max_dist=40, ra
     return out
 
 
+def camera_sets(s, cameras, n_q, mode="random"):
+    """per camera n_q queries and the ids of their landmarks: `random` — every camera its own draw —, `shared` — all the same —, or
+    `disjoint` — no landmark twice in the call (None where the index has too few)"""
+    first = np.unique(s["ids"], return_index=True)[1]
+    if mode == "disjoint" and cameras * n_q > len(first):
+        return None, None
+    rng = np.random.default_rng(77)
+    if mode == "disjoint":
+        src = rng.permutation(len(first))[:cameras * n_q].reshape(cameras, n_q)
+    elif mode == "shared":
+        src = np.tile(rng.choice(len(first), n_q, replace=False), (cameras, 1))
+    else:
+        src = np.stack([rng.choice(len(first), n_q, replace=False) for _ in range(cameras)])
+    queries, ids = [], []
+    for b in range(cameras):
+        rows = first[src[b]]
+        q = s["desc"][rows].copy()
+        q[np.arange(n_q), rng.integers(0, 32, n_q)] ^= np.uint8(1) << rng.integers(0, 8, n_q).astype(np.uint8)     # one bit flipped
+        queries.append(q); ids.append(s["ids"][rows].copy())
+    return queries, ids
+
+
+def same_places(a, b):
+    return bool(all(x[0] == y[0] and x[1].tobytes() == y[1].tobytes() for x, y in zip(a, b)))
+
+
+def batch_main(a, api):
+    """the batched calls against a loop of the single calls"""
+    span = a.batch_span
+    res = {"tool": "place_bench --batch", "queries": a.queries, "ids": a.queries, "tags": span, "repeats": a.repeats, "sizes": {}}
+    for size in (int(v) for v in a.sizes.split(",")):
+        s = scene(size, span, a.queries)
+        ix = build(api, s)
+        kw = dict(tags=(0, span - 1))
+        per_size = {}
+        for cameras in (int(v) for v in a.batch.split(",")):
+            queries, ids = camera_sets(s, cameras, a.queries)
+            got = {}
+
+            def batch_leg(name, f):
+                def run():
+                    got[name] = f()
+                    return ix.stats()["last_kernels_ms"]
+                return run
+
+            def loop_leg(name, f, per_camera):
+                def run():
+                    got[name] = [f(x, **kw) for x in per_camera]
+                    return 0.0
+                return run
+
+            legs = {"tag_votes_batch": batch_leg("tag_votes_batch", lambda: ix.tag_votes_batch(ids, (0, -1), kw["tags"])),
+                    "tag_votes_loop": loop_leg("tag_votes_loop", lambda x, tags: ix.tag_votes(x, (0, -1), tags), ids),
+                    "places_from_ids_batch": batch_leg("places_from_ids_batch", lambda: ix.places_from_ids_batch(ids, **kw)),
+                    "places_from_ids_loop": loop_leg("places_from_ids_loop", ix.places_from_ids, ids)}
+            if not a.no_search:
+                legs.update({"places_batch": batch_leg("places_batch", lambda: ix.places_batch(queries, **kw)),
+                             "places_loop": loop_leg("places_loop", ix.places, queries)})
+            for mode in ("shared", "disjoint"):                           # the table's worst case and its best
+                _, lst = camera_sets(s, cameras, a.queries, mode)
+                if lst is not None:
+                    legs["places_from_ids_batch_" + mode] = batch_leg(mode, lambda lst=lst: ix.places_from_ids_batch(lst, **kw))
+            walls, kern = {k: [] for k in legs}, {k: [] for k in legs}
+            for rep in range(a.repeats + 1):                              # alternating; the first round is the warm-up
+                for k, f in legs.items():
+                    t0 = time.perf_counter()
+                    ms = f()
+                    if rep:
+                        walls[k].append((time.perf_counter() - t0) * 1e3); kern[k].append(ms)
+            out = {k: stats(v) for k, v in walls.items()}
+            for k in legs:
+                if "batch" in k:
+                    out[k]["kernels_ms_median"] = float(np.median(kern[k]))
+            out["batch_equals_loop"] = dict(
+                tag_votes=bool(all(got["tag_votes_batch"][0][b].tobytes() == one[0].tobytes() for b, one in enumerate(got["tag_votes_loop"]))),
+                places_from_ids=same_places(got["places_from_ids_batch"], got["places_from_ids_loop"]),
+                places=same_places(got["places_batch"], got["places_loop"]) if not a.no_search else None)
+            out["votes_in_all"] = int(got["tag_votes_batch"][0].sum())
+            out["landmarks_camera_0"] = int(got["places_from_ids_batch"][0][0].n_landmarks)
+            per_size[str(cameras)] = out
+            print("size %d cameras %d: %s" % (size, cameras, json.dumps(out)), file=sys.stderr, flush=True)
+        ix.close()
+        res["sizes"][str(size)] = per_size
+    return res
+
+
 def stats(v):
     return {"wall_ms_median": float(np.median(v)), "wall_ms_min": float(min(v)), "wall_ms_max": float(max(v))}
 
@@ -98,8 +193,18 @@ def main():
     ap.add_argument("--queries", type=int, default=2048)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--host-repeats", type=int, default=3)
+    ap.add_argument("--batch", help="camera counts, e.g. 1,8,64,256,512: measure the batched calls against loops of the single calls")
+    ap.add_argument("--batch-span", type=int, default=256)
+    ap.add_argument("--no-search", action="store_true", help="--batch: leave out places_batch and its loop (the searches dominate the run)")
     a = ap.parse_args()
     from stereo_visual_odometry_amd import api
+    if a.batch:
+        line = json.dumps(batch_main(a, api))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     res = {"tool": "place_bench", "queries": a.queries, "ids": a.queries, "repeats": a.repeats, "host_repeats": a.host_repeats,
            "sweep_bytes_per_row": SWEEP_BYTES_PER_ROW, "sizes": {}}
     pool = ThreadPoolExecutor(16)
