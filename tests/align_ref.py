@@ -70,6 +70,24 @@ def horn(P, Q):
     return R, cq - R @ cp
 
 
+def kabsch(P, Q):
+    """the same least-squares problem as horn through the SVD of the centred cross-covariance, the determinant's sign set right"""
+    cp, cq = P.mean(0), Q.mean(0)
+    U, _, Vt = np.linalg.svd((Q - cq).T @ (P - cp))
+    D = np.diag([1, 1, np.sign(np.linalg.det(U @ Vt))])
+    R = U @ D @ Vt
+    return R, cq - R @ cp
+
+
+def disagreement(P, Q):
+    """how far the two f64 methods, horn and kabsch, are apart on the same pairs -> (the angle between their rotations in radians,
+    the distance in metres between their images of the pairs' source centroid): what a test may ask of a third f64 method at most"""
+    P, Q = np.asarray(P, np.float64), np.asarray(Q, np.float64)
+    (Rh, th), (Rk, tk) = horn(P, Q), kabsch(P, Q)
+    c = P.mean(0)
+    return rotation_angle(Rh, Rk), float(np.linalg.norm((Rh @ c + th) - (Rk @ c + tk)))
+
+
 def residual2(R, t, P, Q):
     r = P @ R.T + t - Q
     return (r * r).sum(1)
@@ -141,3 +159,37 @@ def rotation_angle(Ra, Rb):
     D = np.asarray(Ra, np.float64) @ np.asarray(Rb, np.float64).T
     s = 0.5 * np.sqrt((D[2, 1] - D[1, 2]) ** 2 + (D[0, 2] - D[2, 0]) ** 2 + (D[1, 0] - D[0, 1]) ** 2)
     return float(np.arctan2(s, 0.5 * (np.trace(D) - 1.0)))
+
+
+BAND = 1e-9                                           # check_model: residuals this close to the threshold (relative) may fall on either side
+
+
+def check_model(res, pairs, xyz, inlier_dist, min_pairs=None):
+    """Rule 10's invariants of one result, recomputed in f64 from the returned R and t alone — no second model is involved, so they
+    hold wherever the rotation is ambiguous.  res: the library's AlignResult or fit's dict; pairs: src, dst (row numbers) and inlier
+    per pair; xyz: the index's points.  Asserts: every entry finite; on success |R^T R - I| <= 1e-12, |det R - 1| <= 1e-12, T is R and
+    t over the row 0 0 0 1, every flagged pair's residual <= inlier_dist and every other pair's above it (pairs within BAND x
+    inlier_dist of the threshold excepted, and counted), rms the flagged pairs' to 1e-9; on failure R, t, T and rms zero; always
+    n_inliers == the flags' sum and, with min_pairs, success == (n_inliers >= min_pairs).
+    -> dict: n_band (the pairs excepted), ortho, det (the two errors), rms, nearest (the smallest | |r| - d | / d)."""
+    get = (lambda k: res[k]) if isinstance(res, dict) else (lambda k: getattr(res, k))
+    R, t, T, rms = (np.asarray(get(k), np.float64) for k in ("R", "t", "T", "rms"))
+    flags = np.asarray(pairs["inlier"]).astype(bool)
+    assert np.isfinite(R).all() and np.isfinite(t).all() and np.isfinite(T).all() and np.isfinite(rms)
+    assert len(flags) == get("n_pairs") and int(get("n_inliers")) == int(flags.sum())
+    if min_pairs is not None:
+        assert bool(get("success")) == (int(get("n_inliers")) >= min_pairs)
+    if not get("success"):
+        assert not R.any() and not t.any() and not T.any() and rms == 0.0
+        return dict(n_band=0, ortho=0.0, det=0.0, rms=0.0, nearest=np.inf)
+    ortho, det = float(np.abs(R.T @ R - np.eye(3)).max()), float(abs(np.linalg.det(R) - 1.0))
+    assert ortho <= 1e-12 and det <= 1e-12, (ortho, det)
+    assert np.array_equal(T[:3, :3], R) and np.array_equal(T[:3, 3], t) and np.array_equal(T[3], [0, 0, 0, 1])
+    xyz = np.asarray(xyz, np.float32).astype(np.float64).reshape(-1, 3)
+    d = float(np.float32(inlier_dist))
+    r = np.sqrt(residual2(R, t, xyz[np.asarray(pairs["src"])], xyz[np.asarray(pairs["dst"])]))
+    band = np.abs(r - d) <= BAND * d
+    assert ((r <= d) == flags)[~band].all(), "a flag disagrees with its pair's recomputed residual"
+    want_rms = float(np.sqrt((r[flags] ** 2).sum() / flags.sum())) if flags.any() else 0.0
+    assert abs(float(rms) - want_rms) <= 1e-9, (float(rms), want_rms)
+    return dict(n_band=int(band.sum()), ortho=ortho, det=det, rms=want_rms, nearest=float((np.abs(r - d) / d).min()) if len(r) else np.inf)

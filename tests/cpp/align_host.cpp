@@ -134,6 +134,110 @@ static void test_model() {
     CHECK(!align_model_finite(m) && !align_is_inlier(m, pq[0], d2));
 }
 
+// ---- Horn's closed form where the eigenvector pick, the Jacobi's early returns and the centroid subtraction do the work
+// The column of the Jacobi's U that align_horn takes, by align_horn's own rule (the first of the largest eigenvalues), from the
+// text of the header: the same 4 x 4 matrix through the same align_jacobi4.  -> the index, and the quaternion
+static int horn_index(const double (&s)[9], double (&q)[4]) {
+    double Qs[16] = {0}, evs[4], U[16];
+    Qs[0] = s[0] + s[4] + s[8]; Qs[5] = s[0] - s[4] - s[8]; Qs[10] = s[4] - s[8] - s[0]; Qs[15] = s[8] - s[0] - s[4];
+    Qs[4] = Qs[1] = s[5] - s[7]; Qs[8] = Qs[2] = s[6] - s[2]; Qs[12] = Qs[3] = s[1] - s[3];
+    Qs[9] = Qs[6] = s[3] + s[1]; Qs[13] = Qs[7] = s[6] + s[2]; Qs[14] = Qs[11] = s[7] + s[5];
+    align_jacobi4(Qs, evs, U);
+    int i_ev = 0;
+    for (int i = 1; i < 4; i++) if (evs[i] > evs[i_ev]) i_ev = i;
+    for (int i = 0; i < 4; i++) q[i] = U[4 * i + i_ev];
+    return i_ev;
+}
+
+enum Cloud { CLOUD_GENERIC, CLOUD_PLANE, CLOUD_LINE, CLOUD_TWO };
+struct HornCase { const char* name; double angle, axis[3]; Cloud cloud; float offset; bool shift; };
+
+// n <= 8 pairs of a case: source points that are exact in f32, their images rounded to f32.  -> the largest coordinate
+static double horn_case_pairs(const HornCase& hc, int n, float (&pq)[8][6]) {
+    static const float P[8][3] = {{1.f, 2.f, 3.f}, {-20.f, 5.f, 7.f}, {4.f, -25.f, 11.f}, {9.f, 9.f, -14.f},
+                                  {-7.5f, 13.25f, 21.f}, {16.f, -3.5f, -9.f}, {-12.f, -18.f, 5.5f}, {27.f, 22.f, -1.25f}};
+    const double na = sqrt(hc.axis[0] * hc.axis[0] + hc.axis[1] * hc.axis[1] + hc.axis[2] * hc.axis[2]);
+    const double a[3] = {hc.axis[0] / na, hc.axis[1] / na, hc.axis[2] / na}, c = cos(hc.angle), s = sin(hc.angle);
+    double R[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R[3 * i + j] = (i == j ? c : 0.) + (1 - c) * a[i] * a[j];
+    R[1] -= s * a[2]; R[2] += s * a[1]; R[3] += s * a[2]; R[5] -= s * a[0]; R[6] -= s * a[1]; R[7] += s * a[0];
+    const double t[3] = {hc.shift ? 12. : 0., hc.shift ? -3. : 0., hc.shift ? 40. : 0.};
+    double most = 0.;
+    for (int k = 0; k < n; k++) {
+        const float* p = P[hc.cloud == CLOUD_TWO ? (k == n - 1 ? 1 : 0) : k];       // two points: all but the last pair are one point
+        float x = p[0], y = p[1], z = p[2];
+        if (hc.cloud == CLOUD_PLANE) z = (float)(0.3 * x - 0.2 * y + 1.);
+        if (hc.cloud == CLOUD_LINE) { y = 2.f * x + 1.f; z = -x + 3.f; }
+        pq[k][0] = x + hc.offset; pq[k][1] = y + hc.offset; pq[k][2] = z + hc.offset;
+        for (int i = 0; i < 3; i++) {
+            pq[k][3 + i] = (float)(R[3 * i] * (double)pq[k][0] + R[3 * i + 1] * (double)pq[k][1] + R[3 * i + 2] * (double)pq[k][2] + t[i]);
+            most = fmax(most, fmax(fabs((double)pq[k][i]), fabs((double)pq[k][3 + i])));
+        }
+    }
+    return most;
+}
+
+// One case at n pairs: rule 7's sums in the pairs' order, align_horn, and at n = 3 align_model3, which must give the same bits.
+// The result is finite, orthonormal with det +1 to 1e-12, and fits its pairs to the f32 rounding of their coordinates.  Horn's
+// optimum has no larger a sum of squared residuals than the true motion, whose residuals are the rounding of the images: at most
+// half an ulp of the largest coordinate on each of 3 n coordinates, so every residual is within sqrt(3 n) half ulps — also where the
+// optimum is not unique (a line, two points).  1e-12 of the largest coordinate is added for the f64 arithmetic itself.
+static int horn_case_run(const HornCase& hc, int n) {
+    float pq[8][6];
+    const double most = horn_case_pairs(hc, n, pq);
+    double cp[3] = {0, 0, 0}, cq[3] = {0, 0, 0}, s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 3; i++) {
+        for (int k = 0; k < n; k++) { cp[i] += (double)pq[k][i]; cq[i] += (double)pq[k][3 + i]; }
+        cp[i] /= (double)n; cq[i] /= (double)n;
+    }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            for (int k = 0; k < n; k++) s[3 * i + j] += ((double)pq[k][i] - cp[i]) * ((double)pq[k][3 + j] - cq[j]);
+    AlignModel m;
+    align_horn(cp, cq, s, m);
+    if (n == 3) {
+        AlignModel m3;
+        align_model3(pq[0], pq[1], pq[2], m3);
+        for (int i = 0; i < 9; i++) CHECK(m3.R[i] == m.R[i]);
+        for (int i = 0; i < 3; i++) CHECK(m3.t[i] == m.t[i]);
+    }
+    CHECK(align_model_finite(m));
+    const double* R = m.R;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) CHECK(fabs(R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j] - (i == j ? 1. : 0.)) <= 1e-12);
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+    CHECK(fabs(det - 1.) <= 1e-12);
+    const double half_ulp = 0.5 * ((double)nextafterf((float)most, std::numeric_limits<float>::infinity()) - (double)(float)most);
+    const double bound = sqrt(3. * n) * half_ulp + 1e-12 * most;
+    double worst = 0.;
+    for (int k = 0; k < n; k++) worst = fmax(worst, sqrt(align_residual2(m, pq[k])));
+    CHECK(worst <= bound);
+    double q[4];
+    const int i_ev = horn_index(s, q);
+    CHECK(m.R[0] == ((q[0] * q[0] + q[1] * q[1]) - q[2] * q[2]) - q[3] * q[3]);   // the quaternion align_horn took
+    printf("  %-28s n %d: eigenvector %d, q0 %+.3e, worst residual %.3g m (bound %.3g m)\n", hc.name, n, i_ev, q[0], worst, bound);
+    return i_ev;
+}
+
+static void test_model_geometry() {
+    const double pi = 3.14159265358979323846;
+    const HornCase cases[] = {
+        {"pi about x", pi, {1, 0, 0}, CLOUD_GENERIC, 0.f, true}, {"pi about y", pi, {0, 1, 0}, CLOUD_GENERIC, 0.f, true},
+        {"pi about z", pi, {0, 0, 1}, CLOUD_GENERIC, 0.f, true}, {"pi about (1, 2, 3)", pi, {1, 2, 3}, CLOUD_GENERIC, 0.f, true},
+        {"2 pi / 3 about (1, 1, 1)", 2 * pi / 3, {1, 1, 1}, CLOUD_GENERIC, 0.f, true}, {"identity", 0., {1, 2, 3}, CLOUD_GENERIC, 0.f, false},
+        {"planar", 0.7, {1, 2, 3}, CLOUD_PLANE, 0.f, true}, {"collinear", 0.7, {1, 2, 3}, CLOUD_LINE, 0.f, true},
+        {"two points", 0.7, {1, 2, 3}, CLOUD_TWO, 0.f, true}, {"at +5000 m", 0.7, {1, 2, 3}, CLOUD_GENERIC, 5000.f, true},
+        {"planar, pi about (3, -1, 2)", pi, {3, -1, 2}, CLOUD_PLANE, 0.f, true},
+    };
+    int seen[4] = {0, 0, 0, 0};
+    printf("Horn's closed form, case by case:\n");
+    for (const HornCase& hc : cases)
+        for (const int n : {3, 8}) seen[horn_case_run(hc, n)]++;
+    printf("eigenvector index taken: 0 x %d, 1 x %d, 2 x %d, 3 x %d\n", seen[0], seen[1], seen[2], seen[3]);
+    CHECK(seen[0] > 0 && seen[1] > 0 && seen[2] > 0 && seen[3] > 0);
+}
+
 static void test_layout() {
     const AlignLayout l = align_layout(ALIGN_MAX_ROWS, ALIGN_MAX_HYPOTHESES);
     CHECK(sizeof(AlignOut) == 136 && sizeof(AlignModel) == 96);
@@ -150,6 +254,7 @@ int main() {
     test_overlap();
     test_sampler();
     test_model();
+    test_model_geometry();
     test_layout();
     if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }
     printf("ALIGN HOST OK\n");

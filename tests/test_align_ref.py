@@ -11,6 +11,7 @@ import pytest
 import align_cases as ac
 import align_ref as aref
 import desc_match_ref as mref
+from align_ref import kabsch
 
 
 def naive_pairs(case, max_dist=40, ratio_num=7, ratio_den=10):
@@ -67,14 +68,6 @@ def test_the_scenes_exercise_what_they_are_for():
     lone = ac.pair_scene("lone")
     m = mref.match(lone["desc"][lone["src"][0]:lone["src"][1]], lone["desc"], lone["ids"], *lone["dst"])
     assert (m["dist2"] == 257).all() and (m["row2"] == -1).all()
-
-
-def kabsch(P, Q):
-    cp, cq = P.mean(0), Q.mean(0)
-    U, _, Vt = np.linalg.svd((Q - cq).T @ (P - cp))
-    D = np.diag([1, 1, np.sign(np.linalg.det(U @ Vt))])
-    R = U @ D @ Vt
-    return R, cq - R @ cp
 
 
 @pytest.mark.parametrize("n, share, H, sigma", [c for c in ac.MOTION_CASES if c[0] <= 1025])
